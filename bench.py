@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Headline benchmark: 256x256x3 satellite patches through the modelv2 hot path.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B] [--dump-outputs DIR] [--full]
 
 One "step" = one pass of the hot path over one batch of B synthetic patches per
 GPU (inputs resident in HBM before the timed region): analysis -> hyper-analysis
@@ -11,6 +11,10 @@ then the cross-GPU all-reduce of the metric sums: BASELINE.json config 3, the
 largest single-GPU configuration (`--no-entropy` drops the coder: config 2;
 `--size 512 --channels 4 --batch 32` is the per-GPU shape of config 5).
 Prints ONE JSON line on rank 0 (contract in the task statement).
+
+A plain run sets up, warms up, times the K steps and prints the line (`--dump-outputs DIR` also writes what the
+last timed step computed as DIR/<name>.npy).  `--full` adds what the headline figure does not need: HIP events
+around the dominant kernel's launches in the timed steps (the `roofline` object) and the CPU baseline.
 
 For N > 1 the driver launches this file with torch.distributed.run, one rank
 per GPU; images are sharded by global index, there is no data-path collective.
@@ -27,8 +31,14 @@ sys.path.insert(0, ROOT)
 # The workload uses five HIP streams per process (main, hyperprior branch, two coder streams, RCCL's).  The HIP
 # runtime maps streams onto 4 hardware queues by default; a fifth stream then shares a queue, and the metric
 # all-reduce queued behind a 4.7 ms encoder kernel cost 2 ms per step under torch.distributed.run (6 720 instead
-# of 8 520 patches/s).  Must be set before the runtime initialises.
-os.environ.setdefault("GPU_MAX_HW_QUEUES", "8")
+# of 8 520 patches/s).  Must be set before the runtime initialises; a smaller value in the environment (4, the
+# runtime's own default, is often exported) is raised to 8.
+try:
+    _queues = int(os.environ.get("GPU_MAX_HW_QUEUES", "0"))
+except ValueError:
+    _queues = 0
+if _queues < 8:
+    os.environ["GPU_MAX_HW_QUEUES"] = "8"
 
 import numpy as np  # noqa: E402
 import torch  # noqa: E402
@@ -49,6 +59,8 @@ class KernelTimer:
     def __init__(self):
         self.enabled = False
         self.only = None             # None: every conv launch; else the set of kernel symbols that get events
+        self.events = True           # False: only note the symbols in `seen` (a plain run's timed steps carry no events)
+        self.seen = set()            # symbols bracketed (or, without events, passed) while enabled since reset()
         self.records = []
         self.pool = []
         self.used = 0
@@ -69,10 +81,14 @@ class KernelTimer:
 
     def reset(self):
         self.records = []
+        self.seen = set()
         self.used = 0
 
     def record(self, name, flops, launch, exec_flops):
         if not self.enabled or (self.only is not None and name not in self.only):
+            return launch()
+        self.seen.add(name)
+        if not self.events:
             return launch()
         e0, e1 = self._event(), self._event()
         e0.record()
@@ -131,6 +147,55 @@ def cpu_baseline(sd, patches, H, W, threads, with_coder, budget_s):
     return 1.0 / float(np.median(times)), n
 
 
+DUMP_BUDGET_BYTES = 64 * 10**6
+DUMP_SAMPLE = 8              # images of the batch whose per-element outputs are written
+
+
+def dump_outputs(path, out, bpp, msssim, totals, coded):
+    """What the last timed step handed its caller, as <path>/<name>.npy (float32, or float64 where the path computes
+    in it): per-image bpp and MS-SSIM, the reduced metric sums, the coded string lengths for the whole batch; for a
+    fixed sample of the batch's images (seeded, at most DUMP_SAMPLE, fewer if the files would exceed
+    DUMP_BUDGET_BYTES) the forward outputs (x_hat, y, y_tilde, nll_y, z, z_tilde, nll_z, sigma, nu) and the z / y
+    strings as byte values, zero past each string's length."""
+    B = int(bpp.shape[0])
+    per_image = {k: out[k] for k in ("x_hat", "y", "y_tilde", "nll_y", "z", "z_tilde", "nll_z", "sigma", "nu")
+                 if out.get(k) is not None}
+    for k in ("sigma", "nu"):
+        t = per_image.get(k)
+        if t is not None and t.dim() == 4 and t.stride(2) == 0 and t.stride(3) == 0:
+            per_image[k] = t[:, :, 0, 0]             # spatially constant (expanded view): one value per channel
+    lengths = coded["lengths"].cpu().numpy().astype(np.int64) if coded is not None else None
+    if coded is not None:
+        raw, cap_z = coded["bytes"], coded["cap_z"]
+        per_image["z_strings"] = raw[:, :max(1, int(lengths[:, 0].max()))]
+        per_image["y_strings"] = raw[:, cap_z:cap_z + max(1, int(lengths[:, 1].max()))]
+    fixed = {"bpp": bpp, "ms_ssim": msssim, "metric_sums": totals}
+    if lengths is not None:
+        fixed["string_lengths"] = torch.from_numpy(lengths).double()
+    fixed_bytes = sum(t.numel() * 8 for t in fixed.values())
+    image_bytes = sum(t[0].numel() * 4 for t in per_image.values())
+    k = min(B, DUMP_SAMPLE)
+    while k > 1 and fixed_bytes + k * (image_bytes + 8) > DUMP_BUDGET_BYTES:
+        k //= 2
+    idx = np.sort(np.random.default_rng(0).choice(B, size=k, replace=False))
+    arrays = {"image_index": idx.astype(np.float64)}
+    for name, t in fixed.items():
+        a = t.detach().cpu().numpy()
+        arrays[name] = a if a.dtype == np.float64 else a.astype(np.float32)
+    sel = torch.from_numpy(idx)
+    for name, t in per_image.items():
+        a = t.detach()[sel.to(t.device)].cpu().numpy()
+        if name.endswith("_strings"):
+            a = a.astype(np.float32)
+            col = np.arange(a.shape[1])[None, :]
+            a[col >= lengths[idx, 0 if name == "z_strings" else 1][:, None]] = 0.0
+        arrays[name] = a if a.dtype == np.float64 else a.astype(np.float32)
+    os.makedirs(path, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), np.ascontiguousarray(a))
+    return sum(a.nbytes for a in arrays.values())
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -139,8 +204,15 @@ def main():
     ap.add_argument("--batch", type=int, default=64, help="patches per GPU per step")
     ap.add_argument("--size", type=int, default=256)
     ap.add_argument("--channels", type=int, default=3)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--kernels", action="store_true", help="also print the per-kernel event timings to stderr")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline figure does not need: HIP events around the dominant kernel's "
+                         "launches in the timed steps (`roofline`) and the CPU baseline (unless --no-cpu-baseline)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed as DIR/<name>.npy (rank 0's shard)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--kernels", action="store_true",
+                    help="bracket every conv launch of the timed steps with HIP events (adds `roofline`) and print the "
+                         "per-kernel timings to stderr")
     ap.add_argument("--streams-per-wg", type=int, default=1,
                     help="range-coder waves per workgroup (1..16; 1: a wave has its CU's scalar unit to itself, "
                          "4.4 instead of 5.1 ms per batch and a 1 %% faster step than 4)")
@@ -168,6 +240,7 @@ def main():
                          "CDF tables and the range coder of the z,y strings also run on the GPU (second stream)")
     ap.add_argument("--entropy", action="store_true", help="(default; kept for older command lines)")
     args = ap.parse_args()
+    kernel_events = args.full or args.kernels        # HIP events inside the timed steps
 
     rank = int(os.environ.get("RANK", "0"))
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
@@ -214,6 +287,7 @@ def main():
     zero = torch.zeros((), dtype=torch.float64, device=dev)
 
     pending = []
+    last_step = {}
 
     # --lanes L: step i runs on stream i % L, so the tail of one batch's kernels (workgroups of a persistent kernel
     # finish up to one tile apart) and its small layers overlap the next batch's; every lane is joined before the
@@ -266,6 +340,7 @@ def main():
         t = torch.stack([bpp.sum(), msssim.double().sum(), count, real])
         D.reduce_metric_sums(t)                                  # the one collective: 4 x fp64
         totals.copy_(t)
+        last_step.update(out=out, bpp=bpp, msssim=msssim)        # what the caller of this step receives
         return out
 
     def barrier():
@@ -295,7 +370,10 @@ def main():
         warm = timer.summary()
         if warm:
             timer.only = {max(warm.items(), key=lambda kv: kv[1][1])[0]}
-    timer.reserve(per_step * args.steps + 8)
+    if kernel_events:
+        timer.reserve(per_step * args.steps + 8)
+    else:
+        timer.events = False     # the timed steps only note the dominant symbol (it names `dtype`), no events
     if coder is not None:
         coder.reserve_events(args.steps + 1)
     model.reserve_stage_events(args.steps + 2)
@@ -305,7 +383,8 @@ def main():
     marks = []
     t0 = time.perf_counter()
     for i in range(args.steps):
-        marks.append(timer.mark())
+        if kernel_events:
+            marks.append(timer.mark())
         run_step(i)
     drain()
     if lanes is not None:
@@ -329,6 +408,9 @@ def main():
         err = int(coder.last["err"].item())
         if err:
             raise SystemExit(f"range coder reported error flags {err:#x} (support wider than Lmax?): mean_bpp_coded would be wrong")
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, last_step["out"], last_step["bpp"], last_step["msssim"], totals,
+                     coder.last if coder is not None else None)
 
     decoder_stats = e2e_stats = None
     if args.decode and rank == 0:
@@ -422,31 +504,62 @@ def main():
             for k, (c, t, f, ex) in sorted(agg.items(), key=lambda kv: -kv[1][1]):
                 print(f"{k:40s} {c:5d} launches {t / args.steps * 1e3:8.3f} ms/step  {f / t / 1e12:7.1f} TF/s algorithmic "
                       f"{ex / t / 1e12:7.1f} executed", file=sys.stderr)
-        name, (cnt, secs, flops, exflops) = max(agg.items(), key=lambda kv: kv[1][1])
-        executed = exflops / secs / 1e12
-        algorithmic = flops / secs / 1e12
-        # the split-bf16 Winograd kernels run on the bf16 MFMA path (3 bf16 MFMAs per fp32-equivalent one)
-        is_bf16 = "bf16" in name
-        peak = PEAK_BF16_MFMA_TFLOPS if is_bf16 else PEAK_FP32_MFMA_TFLOPS
-        conv_secs = sum(v[1] for v in agg.values())
+        roofline = None
+        if kernel_events:
+            name, (cnt, secs, flops, exflops) = max(agg.items(), key=lambda kv: kv[1][1])
+            executed = exflops / secs / 1e12
+            algorithmic = flops / secs / 1e12
+            # the split-bf16 Winograd kernels run on the bf16 MFMA path (3 bf16 MFMAs per fp32-equivalent one)
+            is_bf16 = "bf16" in name
+            peak = PEAK_BF16_MFMA_TFLOPS if is_bf16 else PEAK_FP32_MFMA_TFLOPS
+            conv_secs = sum(v[1] for v in agg.values())
 
-        def from_profile(fname, key=None):
-            """Numbers of a SEPARATE rocprofv3 --pmc pass, committed under profiles/ (not measured by
-            this invocation): returned with the file they come from, or (None, None)."""
-            path = os.path.join(ROOT, "profiles", fname)
-            if not os.path.exists(path):
-                return None, None
-            with open(path) as f:
-                d = json.load(f)
-            v = d.get(name)
-            if key is not None and isinstance(v, dict):
-                v = v.get(key)
-            return v, f"profiles/{fname}" + (f" (commit {d['_commit']})" if "_commit" in d else "")
+            def from_profile(fname, key=None):
+                """Numbers of a SEPARATE rocprofv3 --pmc pass, committed under profiles/ (not measured by
+                this invocation): returned with the file they come from, or (None, None)."""
+                path = os.path.join(ROOT, "profiles", fname)
+                if not os.path.exists(path):
+                    return None, None
+                with open(path) as f:
+                    d = json.load(f)
+                v = d.get(name)
+                if key is not None and isinstance(v, dict):
+                    v = v.get(key)
+                return v, f"profiles/{fname}" + (f" (commit {d['_commit']})" if "_commit" in d else "")
 
-        traffic, traffic_src = from_profile("pmc_traffic.json")
-        mfma_pmc, mfma_src = from_profile("mfma_util.json", "mfma_util")
-        if (H, W, C) != (256, 256, 3):
-            traffic = traffic_src = mfma_pmc = mfma_src = None      # the committed PMC passes are 256x256x3
+            traffic, traffic_src = from_profile("pmc_traffic.json")
+            mfma_pmc, mfma_src = from_profile("mfma_util.json", "mfma_util")
+            if (H, W, C) != (256, 256, 3):
+                traffic = traffic_src = mfma_pmc = mfma_src = None      # the committed PMC passes are 256x256x3
+            roofline = {
+                "bound": "mfma",
+                "kernel": name,
+                "launches": cnt,
+                "avg_launch_ms": secs / cnt * 1e3,
+                # FLOPs the kernel's algorithm executes on the MFMA pipe (Winograd F(2x2,3x3) with
+                # zero-position skipping: 12.25 of every 25 direct-convolution MACs of a 5x5/s2
+                # layer) / its HIP-event time; frac <= 1 by construction
+                "achieved": executed,
+                "peak": peak,
+                "peak_dtype": "bf16 MFMA (fp32 operands split into 2 bf16 planes, 3 products, fp32 accumulate)"
+                              if is_bf16 else "fp32-input MFMA",
+                "unit": "TFLOP/s",
+                "frac": executed / peak,
+                "traffic": traffic,
+                "traffic_source": traffic_src,
+                # direct-convolution FLOP count of SURVEY.md §8(d) / the same time: may exceed the
+                # peak because Winograd executes fewer multiplies; not a roofline fraction
+                "algorithmic_tflops": algorithmic,
+                "algorithmic_over_fp32_mfma_peak": algorithmic / PEAK_FP32_MFMA_TFLOPS,
+                "mfma_busy_pmc": mfma_pmc,
+                "mfma_busy_source": mfma_src,
+                "events": "every conv launch bracketed (--kernels: costs ~4 % of the step)" if timer.only is None
+                          else "launches of the dominant symbol bracketed; it was picked from the fully bracketed "
+                               "last warm-up step",
+            }
+            if timer.only is None:
+                roofline["all_conv_algorithmic_tflops"] = sum(v[2] for v in agg.values()) / conv_secs / 1e12
+                roofline["conv_share_of_step"] = conv_secs / elapsed
         coder_stats = None
         if coder is not None and coder.times:
             ms = [e0.elapsed_time(e1) for e0, e1 in coder.times[-args.steps:]]
@@ -472,7 +585,7 @@ def main():
             "scaling": "weak",
             "vs_baseline": None,          # BASELINE.md holds no published throughput for this metric
             "dtype": "f32 (Winograd contractions as split-bf16 MFMA with fp32 accumulate)"
-                     if any("bf16" in k for k in agg) else "f32",
+                     if any("bf16" in k for k in timer.seen) else "f32",
             "data": "synthetic",
             "config": {
                 "workload": f"batch={B}/GPU {H}x{W}x{C} synthetic patches, modelv2 encode->decode "
@@ -492,37 +605,9 @@ def main():
             "coder": coder_stats,
             "decoder": decoder_stats,
             "e2e": e2e_stats,
-            "roofline": {
-                "bound": "mfma",
-                "kernel": name,
-                "launches": cnt,
-                "avg_launch_ms": secs / cnt * 1e3,
-                # FLOPs the kernel's algorithm executes on the MFMA pipe (Winograd F(2x2,3x3) with
-                # zero-position skipping: 12.25 of every 25 direct-convolution MACs of a 5x5/s2
-                # layer) / its HIP-event time; frac <= 1 by construction
-                "achieved": executed,
-                "peak": peak,
-                "peak_dtype": "bf16 MFMA (fp32 operands split into 2 bf16 planes, 3 products, fp32 accumulate)"
-                              if is_bf16 else "fp32-input MFMA",
-                "unit": "TFLOP/s",
-                "frac": executed / peak,
-                "traffic": traffic,
-                "traffic_source": traffic_src,
-                # direct-convolution FLOP count of SURVEY.md §8(d) / the same time: may exceed the
-                # peak because Winograd executes fewer multiplies; not a roofline fraction
-                "algorithmic_tflops": algorithmic,
-                "algorithmic_over_fp32_mfma_peak": algorithmic / PEAK_FP32_MFMA_TFLOPS,
-                "mfma_busy_pmc": mfma_pmc,
-                "mfma_busy_source": mfma_src,
-                "events": "every conv launch bracketed (--kernels: costs ~4 % of the step)" if timer.only is None
-                          else "launches of the dominant symbol bracketed; it was picked from the fully bracketed "
-                               "last warm-up step",
-            },
+            "roofline": roofline,
         }
-        if timer.only is None:
-            res["roofline"]["all_conv_algorithmic_tflops"] = sum(v[2] for v in agg.values()) / conv_secs / 1e12
-            res["roofline"]["conv_share_of_step"] = conv_secs / elapsed
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             # the GPU box gives one job a 16-CPU share of a larger host
             cores = min(len(os.sched_getaffinity(0)), 16)
             with_coder = not args.no_entropy

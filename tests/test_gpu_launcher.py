@@ -12,7 +12,7 @@ import pytest
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-ARGS = ["bench.py", "--steps", "10", "--warmup", "4", "--no-cpu-baseline"]
+ARGS = ["bench.py", "--steps", "10", "--warmup", "4", "--full", "--no-cpu-baseline"]   # --full: `roofline`
 
 
 def _run(cmd):
