@@ -1,0 +1,434 @@
+// Whole-image codec glue (codec.py): an image of any size to tiles of the model's patch size and back, and a
+// batch of coder outputs to one DSIC2 container and back.  All of it is byte movement: every kernel is
+// memory-bound and works in 16-byte units (dwordx4 loads where the source is aligned, alignbyte funnels of
+// dword loads where it is not, dwordx4 stores on aligned destination chunks, byte stores only at the ragged
+// ends of a segment).  One workgroup covers a block of rows of one tile, or a slice of one string.
+//
+// Tile geometry (codec.tile_grid): Hp = ceil16(H), tiles_y = ceil(Hp / th), origin of tile row i =
+// min(i*th, Hp - th); tile row i owns padded rows [i*th, min((i+1)*th, Hp)) (the last row of tiles shifts
+// inward and its overlap rows belong to the earlier tile).  Columns likewise; tiles are numbered row-major.
+#include "common.h"
+
+namespace dsic {
+
+constexpr int kTileRows = 16;  // rows of one tile per workgroup (th, tw are multiples of 16)
+
+struct Grid {
+  int H, W, Hp, Wp, th, tw, ny, nx;
+  __host__ __device__ int oy(int i) const { return min(i * th, Hp - th); }
+  __host__ __device__ int ox(int j) const { return min(j * tw, Wp - tw); }
+};
+
+static Grid make_grid(int H, int W, int th, int tw) {
+  Grid g;
+  g.H = H, g.W = W, g.th = th, g.tw = tw;
+  g.Hp = round_up(H, 16), g.Wp = round_up(W, 16);
+  g.ny = ceil_div(g.Hp, th), g.nx = ceil_div(g.Wp, tw);
+  return g;
+}
+
+// reflect without repeating the edge (layout.hip reflect_pad_br_kernel); p < 2H-1 by the padding precondition
+__device__ __forceinline__ int reflect(int p, int n) { return p < n ? p : 2 * (n - 1) - p; }
+
+// 16 bytes from any address: aligned dword loads funnelled by __builtin_amdgcn_alignbyte.  The dwords read
+// start at the aligned-down address of p and end at the dword holding p[15], so no byte outside the
+// allocation's dwords is touched.
+__device__ __forceinline__ uint4 load16_any(const uint8_t* p) {
+  const uintptr_t a = (uintptr_t)p;
+  if ((a & 15) == 0) return *(const uint4*)p;
+  const int sh = a & 3;
+  const uint32_t* w = (const uint32_t*)(a - sh);
+  const uint32_t w0 = w[0], w1 = w[1], w2 = w[2], w3 = w[3];
+  if (sh == 0) return make_uint4(w0, w1, w2, w3);
+  const uint32_t w4 = w[4];
+  return make_uint4(__builtin_amdgcn_alignbyte(w1, w0, sh), __builtin_amdgcn_alignbyte(w2, w1, sh),
+                    __builtin_amdgcn_alignbyte(w3, w2, sh), __builtin_amdgcn_alignbyte(w4, w3, sh));
+}
+
+// n bytes src -> dst (any alignments), split over `parts` workgroups of blockDim.x threads: the destination's
+// aligned 16-byte chunks are whole dwordx4 stores, the ragged head and tail are byte stores (their neighbours
+// belong to another string or to the header and are written by another workgroup).
+__device__ void copy_bytes(uint8_t* dst, const uint8_t* src, int64_t n, int part, int parts) {
+  if (n <= 0) return;
+  int64_t head = (16 - ((uintptr_t)dst & 15)) & 15;
+  if (head > n) head = n;
+  const int64_t nfull = (n - head) >> 4;
+  const int64_t tail = head + 16 * nfull;
+  if (part == 0) {
+    for (int64_t i = threadIdx.x; i < head; i += blockDim.x) dst[i] = src[i];
+    for (int64_t i = tail + threadIdx.x; i < n; i += blockDim.x) dst[i] = src[i];
+  }
+  for (int64_t c = (int64_t)part * blockDim.x + threadIdx.x; c < nfull; c += (int64_t)parts * blockDim.x)
+    *(uint4*)(dst + head + 16 * c) = load16_any(src + head + 16 * c);
+}
+
+// exclusive prefix sum over a 256-thread workgroup; *total = sum of all v
+__device__ long long block_exclusive_scan(long long v, long long* lds4, long long* total) {
+  const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
+  long long s = v;
+#pragma unroll
+  for (int o = 1; o < 64; o <<= 1) {
+    const long long t = __shfl_up(s, o, 64);
+    if (lane >= o) s += t;
+  }
+  if (lane == 63) lds4[wid] = s;
+  __syncthreads();
+  long long base = 0, tot = 0;
+#pragma unroll
+  for (int w = 0; w < 4; ++w) {
+    base += w < wid ? lds4[w] : 0;
+    tot += lds4[w];
+  }
+  __syncthreads();
+  *total = tot;
+  return base + s - v;
+}
+
+// ---- tile gather ------------------------------------------------------------------------------------------
+
+// uint8 HWC image -> tiles [n][th][tw][C].  A tile row is tw*C bytes, a multiple of 16.
+__global__ __launch_bounds__(256) void gather_u8_kernel(const uint8_t* __restrict__ img, uint8_t* __restrict__ tiles,
+                                                        Grid g, int C, int first) {
+  const int t = first + blockIdx.y;
+  const int oy = g.oy(t / g.nx), ox = g.ox(t % g.nx);
+  const int row_bytes = g.tw * C, vpr = row_bytes >> 4;
+  const int r0 = blockIdx.x * kTileRows;
+  uint8_t* dst = tiles + ((size_t)blockIdx.y * g.th + r0) * row_bytes;
+  for (int i = threadIdx.x; i < kTileRows * vpr; i += blockDim.x) {
+    const int r = i / vpr, j0 = (i - r * vpr) << 4;
+    const uint8_t* src_row = img + (size_t)reflect(oy + r0 + r, g.H) * g.W * C;
+    uint4 v;
+    if (ox + (j0 + 15) / C < g.W) {
+      v = load16_any(src_row + (size_t)ox * C + j0);
+    } else {  // the run reaches the reflected columns
+      uint8_t b[16];
+      int px = j0 / C, c = j0 - px * C;
+#pragma unroll
+      for (int k = 0; k < 16; ++k) {
+        b[k] = src_row[(size_t)reflect(ox + px, g.W) * C + c];
+        if (++c == C) c = 0, ++px;
+      }
+      __builtin_memcpy(&v, b, 16);
+    }
+    *(uint4*)(dst + (size_t)r * row_bytes + j0) = v;
+  }
+}
+
+// float32 CHW image -> tiles [n][C][th][tw]; blockIdx.z = channel
+__global__ __launch_bounds__(256) void gather_f32_kernel(const float* __restrict__ img, float* __restrict__ tiles,
+                                                         Grid g, int first) {
+  const int t = first + blockIdx.y, c = blockIdx.z, C = gridDim.z;
+  const int oy = g.oy(t / g.nx), ox = g.ox(t % g.nx);
+  const int vpr = g.tw >> 2;
+  const int r0 = blockIdx.x * kTileRows;
+  float* dst = tiles + (((size_t)blockIdx.y * C + c) * g.th + r0) * g.tw;
+  for (int i = threadIdx.x; i < kTileRows * vpr; i += blockDim.x) {
+    const int r = i / vpr, j0 = (i - r * vpr) << 2;
+    const float* src_row = img + ((size_t)c * g.H + reflect(oy + r0 + r, g.H)) * g.W;
+    const int x0 = ox + j0;
+    float4 v;
+    if (x0 + 3 < g.W && (((uintptr_t)(src_row + x0)) & 15) == 0) {
+      v = *(const float4*)(src_row + x0);
+    } else {
+      v = make_float4(src_row[reflect(x0, g.W)], src_row[reflect(x0 + 1, g.W)], src_row[reflect(x0 + 2, g.W)],
+                      src_row[reflect(x0 + 3, g.W)]);
+    }
+    *(float4*)(dst + (size_t)r * g.tw + j0) = v;
+  }
+}
+
+// ---- tile stitch ------------------------------------------------------------------------------------------
+
+__device__ __forceinline__ float clamp01(float v) { return v < 0.f ? 0.f : (v > 1.f ? 1.f : v); }  // torch clamp(0,1)
+
+// the owned part of tile t in image coordinates: rows [y0,y1), columns [x0,x1); (oy, ox) its origin
+struct Owned {
+  int y0, y1, x0, x1, oy, ox;
+};
+__device__ __forceinline__ Owned owned(const Grid& g, int t) {
+  const int i = t / g.nx, j = t % g.nx;
+  return {i * g.th, min(min((i + 1) * g.th, g.Hp), g.H), j * g.tw, min(min((j + 1) * g.tw, g.Wp), g.W), g.oy(i),
+          g.ox(j)};
+}
+
+// tiles [n][C][th][tw] -> clamp(0,1) into the float32 CHW image; blockIdx.z = channel
+__global__ __launch_bounds__(256) void stitch_f32_kernel(const float* __restrict__ tiles, float* __restrict__ img,
+                                                         Grid g, int first) {
+  const int t = first + blockIdx.y, c = blockIdx.z, C = gridDim.z;
+  const Owned o = owned(g, t);
+  const int ya = o.y0 + blockIdx.x * kTileRows;
+  const int rows = min(kTileRows, o.y1 - ya);
+  if (rows <= 0) return;
+  const float* src = tiles + ((size_t)blockIdx.y * C + c) * g.th * g.tw;
+  // 4-float chunks aligned in the image (its base is 16-byte aligned): chunk q covers elements [4q, 4q+4)
+  const int64_t plane = (int64_t)c * g.H * g.W;
+  const int cpr = (o.x1 - o.x0) / 4 + 2;  // chunks a row segment can touch
+  for (int i = threadIdx.x; i < rows * cpr; i += blockDim.x) {
+    const int r = i / cpr, k = i - r * cpr;
+    const int y = ya + r;
+    const int64_t e0 = plane + (int64_t)y * g.W + o.x0, e1 = e0 + (o.x1 - o.x0);
+    const int64_t q0 = ((e0 >> 2) + k) << 2;
+    if (q0 >= e1) continue;
+    const float* srow = src + (size_t)(y - o.oy) * g.tw + (o.x0 - o.ox);  // element e of the image: srow[e - e0]
+    if (q0 >= e0 && q0 + 4 <= e1) {
+      const float* s = srow + (q0 - e0);
+      *(float4*)(img + q0) = make_float4(clamp01(s[0]), clamp01(s[1]), clamp01(s[2]), clamp01(s[3]));
+    } else {
+      for (int64_t e = max(q0, e0); e < min(q0 + 4, e1); ++e) img[e] = clamp01(srow[e - e0]);
+    }
+  }
+}
+
+// tiles [n][C][th][tw] -> (uint8)(clamp(x,0,1) * 255) into the uint8 HWC image
+__global__ __launch_bounds__(256) void stitch_u8_kernel(const float* __restrict__ tiles, uint8_t* __restrict__ img,
+                                                        Grid g, int C, int first) {
+  const int t = first + blockIdx.y;
+  const Owned o = owned(g, t);
+  const int ya = o.y0 + blockIdx.x * kTileRows;
+  const int rows = min(kTileRows, o.y1 - ya);
+  if (rows <= 0) return;
+  const float* src = tiles + (size_t)blockIdx.y * C * g.th * g.tw;
+  const size_t cplane = (size_t)g.th * g.tw;
+  const int seg = (o.x1 - o.x0) * C;
+  const int cpr = seg / 16 + 2;  // 16-byte chunks a row segment can touch
+  for (int i = threadIdx.x; i < rows * cpr; i += blockDim.x) {
+    const int r = i / cpr, k = i - r * cpr;
+    const int y = ya + r;
+    const int64_t b0 = ((int64_t)y * g.W + o.x0) * C, b1 = b0 + seg;
+    const int64_t q0 = ((b0 >> 4) + k) << 4;
+    if (q0 >= b1) continue;
+    const int64_t lo = max(q0, b0), hi = min(q0 + 16, b1);
+    const float* srow = src + (size_t)(y - o.oy) * g.tw;
+    int px = (int)((lo - b0) / C), c = (int)((lo - b0) - (int64_t)px * C);
+    px += o.x0 - o.ox;  // column within the tile
+    uint8_t b[16];
+#pragma unroll
+    for (int e = 0; e < 16; ++e) {
+      b[e] = 0;
+      if (q0 + e >= lo && q0 + e < hi) {
+        b[e] = (uint8_t)(clamp01(srow[c * cplane + px]) * 255.0f);
+        if (++c == C) c = 0, ++px;
+      }
+    }
+    if (lo == q0 && hi == q0 + 16) {
+      uint4 v;
+      __builtin_memcpy(&v, b, 16);
+      *(uint4*)(img + q0) = v;
+    } else {
+      for (int64_t e = lo; e < hi; ++e) img[e] = b[e - q0];
+    }
+  }
+}
+
+// ---- DSIC2 container --------------------------------------------------------------------------------------
+// magic(6) | tag u32 | B,My,Hy,Wy,Nz,Hz,Wz u32 | B x (min_y,max_y,min_z,max_z i32, len_z,len_y u32) | strings
+constexpr int kHeadBytes = 38, kRecBytes = 24;
+
+__device__ __forceinline__ void put_u32(uint8_t* p, int byte, uint32_t v) { *p = (uint8_t)(v >> (8 * byte)); }
+__device__ __forceinline__ int64_t clamp_len(int v, int64_t cap) { return v < 0 ? 0 : (v > cap ? cap : v); }
+
+// one workgroup: header, records, exclusive scan of the 2B string lengths (z0, y0, z1, ...) into ws[2..2+2B];
+// ws[0] = container bytes, ws[1] = the coder's error word
+__global__ __launch_bounds__(256) void pack_head_kernel(const int* __restrict__ lengths, const int* __restrict__ meta,
+                                                        const int* __restrict__ err, int B, int64_t cap_z,
+                                                        int64_t cap_y, uint32_t tag, int My, int Hy, int Wy, int Nz,
+                                                        int Hz, int Wz, long long* __restrict__ ws,
+                                                        uint8_t* __restrict__ out) {
+  __shared__ long long lds4[4];
+  const int tid = threadIdx.x;
+  if (tid < kHeadBytes) {
+    const char magic[6] = {'D', 'S', 'I', 'C', '2', 0};
+    const uint32_t f[8] = {tag, (uint32_t)B, (uint32_t)My, (uint32_t)Hy, (uint32_t)Wy, (uint32_t)Nz, (uint32_t)Hz,
+                           (uint32_t)Wz};
+    if (tid < 6) out[tid] = (uint8_t)magic[tid];
+    else put_u32(out + tid, (tid - 6) & 3, f[(tid - 6) >> 2]);
+  }
+  for (int i = tid; i < kRecBytes * B; i += blockDim.x) {
+    const int b = i / kRecBytes, k = i - b * kRecBytes;
+    const int* m = meta + 4 * b;
+    uint32_t v;
+    switch (k >> 2) {
+      case 0: v = (uint32_t)m[0]; break;
+      case 1: v = (uint32_t)(m[0] + m[1] - 1); break;
+      case 2: v = (uint32_t)m[2]; break;
+      case 3: v = (uint32_t)(m[2] + m[3] - 1); break;
+      case 4: v = (uint32_t)clamp_len(lengths[2 * b], cap_z); break;
+      default: v = (uint32_t)clamp_len(lengths[2 * b + 1], cap_y); break;
+    }
+    put_u32(out + kHeadBytes + i, k & 3, v);
+  }
+  long long carry = 0;
+  for (int s0 = 0; s0 < 2 * B; s0 += blockDim.x) {
+    const int s = s0 + tid;
+    const long long v = s < 2 * B ? clamp_len(lengths[s], (s & 1) ? cap_y : cap_z) : 0;
+    long long tot;
+    const long long ex = block_exclusive_scan(v, lds4, &tot);
+    if (s < 2 * B) ws[2 + s] = carry + ex;
+    carry += tot;
+  }
+  if (tid == 0) {
+    ws[2 + 2 * B] = carry;
+    ws[0] = kHeadBytes + (long long)kRecBytes * B + carry;
+    ws[1] = err ? *err : 0;
+  }
+}
+
+// blockIdx.y = string s (image s/2, z if even, y if odd); blockIdx.x = slice of it
+__global__ __launch_bounds__(256) void pack_strings_kernel(const uint8_t* __restrict__ bytes,
+                                                           const int* __restrict__ lengths, int B, int64_t cap_z,
+                                                           int64_t cap_y, const long long* __restrict__ ws,
+                                                           uint8_t* __restrict__ out) {
+  const int s = blockIdx.y, b = s >> 1, which = s & 1;
+  const uint8_t* src = bytes + (size_t)b * (cap_z + cap_y) + (which ? cap_z : 0);
+  const int64_t n = clamp_len(lengths[s], which ? cap_y : cap_z);
+  copy_bytes(out + kHeadBytes + (int64_t)kRecBytes * B + ws[2 + s], src, n, blockIdx.x, gridDim.x);
+}
+
+__device__ __forceinline__ uint32_t get_u32(const uint8_t* p) {
+  return (uint32_t)p[0] | ((uint32_t)p[1] << 8) | ((uint32_t)p[2] << 16) | ((uint32_t)p[3] << 24);
+}
+
+// one workgroup: records -> meta [B,4] (ymin, Ly, zmin, Lz), lengths [B,2] (z, y), string offsets ws[2..2+2B]
+__global__ __launch_bounds__(256) void scatter_head_kernel(const uint8_t* __restrict__ blob, int B,
+                                                           int* __restrict__ lengths, int* __restrict__ meta,
+                                                           long long* __restrict__ ws) {
+  __shared__ long long lds4[4];
+  const int tid = threadIdx.x;
+  for (int b = tid; b < B; b += blockDim.x) {
+    const uint8_t* rec = blob + kHeadBytes + (size_t)kRecBytes * b;
+    const int min_y = (int)get_u32(rec), max_y = (int)get_u32(rec + 4);
+    const int min_z = (int)get_u32(rec + 8), max_z = (int)get_u32(rec + 12);
+    meta[4 * b] = min_y, meta[4 * b + 1] = max_y - min_y + 1;
+    meta[4 * b + 2] = min_z, meta[4 * b + 3] = max_z - min_z + 1;
+  }
+  long long carry = 0;
+  for (int s0 = 0; s0 < 2 * B; s0 += blockDim.x) {
+    const int s = s0 + tid;
+    const uint32_t len = s < 2 * B ? get_u32(blob + kHeadBytes + (size_t)kRecBytes * (s >> 1) + 16 + 4 * (s & 1)) : 0;
+    if (s < 2 * B) lengths[s] = (int)len;
+    long long tot;
+    const long long ex = block_exclusive_scan(len, lds4, &tot);
+    if (s < 2 * B) ws[2 + s] = carry + ex;
+    carry += tot;
+  }
+  if (tid == 0) ws[2 + 2 * B] = carry, ws[0] = kHeadBytes + (long long)kRecBytes * B + carry, ws[1] = 0;
+}
+
+__global__ __launch_bounds__(256) void scatter_strings_kernel(const uint8_t* __restrict__ blob, int64_t blob_bytes,
+                                                              int B, uint8_t* __restrict__ zbuf, int64_t zstride,
+                                                              uint8_t* __restrict__ ybuf, int64_t ystride,
+                                                              const int* __restrict__ lengths,
+                                                              const long long* __restrict__ ws) {
+  const int s = blockIdx.y, b = s >> 1, which = s & 1;
+  const int64_t stride = which ? ystride : zstride;
+  const int64_t off = kHeadBytes + (int64_t)kRecBytes * B + ws[2 + s];
+  int64_t n = clamp_len(lengths[s], stride);  // the host checked the records; a bad blob still stays in bounds
+  if (off + n > blob_bytes) n = blob_bytes - off;
+  copy_bytes((which ? ybuf : zbuf) + (size_t)b * stride, blob + off, n, blockIdx.x, gridDim.x);
+}
+
+static int string_parts(int64_t max_len) {
+  const int64_t p = (max_len + 16 * 256 - 1) / (16 * 256);
+  return (int)(p < 1 ? 1 : (p > 8 ? 8 : p));
+}
+
+static const char* grid_error(int H, int W, int th, int tw) {
+  if (H <= 0 || W <= 0) return "empty image";
+  if (th < 32 || tw < 32 || th % 16 || tw % 16) return "tile sides must be multiples of 16, at least 32";
+  if (round_up(H, 16) - H >= H || round_up(W, 16) - W >= W) return "padding must be smaller than the image";
+  if (th > round_up(H, 16) || tw > round_up(W, 16)) return "tile larger than the padded image";
+  return nullptr;
+}
+
+}  // namespace dsic
+
+using namespace dsic;
+
+#define DSIC_TILE_ARGS(what)                                                                                 \
+  const char* ge = grid_error(H, W, th, tw);                                                                 \
+  DSIC_REQUIRE(!ge, what ": %s (H=%d W=%d th=%d tw=%d)", ge ? ge : "", H, W, th, tw);                        \
+  const Grid g = make_grid(H, W, th, tw);                                                                    \
+  DSIC_REQUIRE(first_tile >= 0 && n_tiles > 0 && (int64_t)first_tile + n_tiles <= (int64_t)g.ny * g.nx,      \
+               what ": tiles [%d, %d) outside the grid of %d", first_tile, first_tile + n_tiles, g.ny * g.nx); \
+  DSIC_REQUIRE(n_tiles <= 65535, what ": at most 65535 tiles per call");                                   \
+  const dim3 grid(g.th / kTileRows, n_tiles, 1)
+
+extern "C" int dsic_tile_gather_u8(const uint8_t* img_hwc, uint8_t* tiles, int H, int W, int C, int th, int tw,
+                                   int first_tile, int n_tiles, void* stream) {
+  DSIC_REQUIRE(img_hwc && tiles, "tile_gather_u8: null pointer");
+  DSIC_REQUIRE(C == 3 || C == 4, "tile_gather_u8: C=%d must be 3 or 4", C);
+  DSIC_TILE_ARGS("tile_gather_u8");
+  DSIC_REQUIRE(((uintptr_t)tiles & 15) == 0, "tile_gather_u8: tiles must be 16-byte aligned");
+  hipLaunchKernelGGL(gather_u8_kernel, grid, dim3(256), 0, (hipStream_t)stream, img_hwc, tiles, g, C, first_tile);
+  return check_launch("tile_gather_u8");
+}
+
+extern "C" int dsic_tile_gather_f32(const float* img_chw, float* tiles, int H, int W, int C, int th, int tw,
+                                    int first_tile, int n_tiles, void* stream) {
+  DSIC_REQUIRE(img_chw && tiles, "tile_gather_f32: null pointer");
+  DSIC_REQUIRE(C >= 1 && C <= 8, "tile_gather_f32: C=%d must be in 1..8", C);
+  DSIC_TILE_ARGS("tile_gather_f32");
+  DSIC_REQUIRE(((uintptr_t)tiles & 15) == 0, "tile_gather_f32: tiles must be 16-byte aligned");
+  hipLaunchKernelGGL(gather_f32_kernel, dim3(grid.x, grid.y, C), dim3(256), 0, (hipStream_t)stream, img_chw, tiles,
+                     g, first_tile);
+  return check_launch("tile_gather_f32");
+}
+
+extern "C" int dsic_tile_stitch_f32(const float* tiles, float* img_chw, int H, int W, int C, int th, int tw,
+                                    int first_tile, int n_tiles, void* stream) {
+  DSIC_REQUIRE(tiles && img_chw, "tile_stitch_f32: null pointer");
+  DSIC_REQUIRE(C >= 1 && C <= 8, "tile_stitch_f32: C=%d must be in 1..8", C);
+  DSIC_TILE_ARGS("tile_stitch_f32");
+  DSIC_REQUIRE(((uintptr_t)img_chw & 15) == 0, "tile_stitch_f32: image must be 16-byte aligned");
+  hipLaunchKernelGGL(stitch_f32_kernel, dim3(grid.x, grid.y, C), dim3(256), 0, (hipStream_t)stream, tiles, img_chw,
+                     g, first_tile);
+  return check_launch("tile_stitch_f32");
+}
+
+extern "C" int dsic_tile_stitch_u8(const float* tiles, uint8_t* img_hwc, int H, int W, int C, int th, int tw,
+                                   int first_tile, int n_tiles, void* stream) {
+  DSIC_REQUIRE(tiles && img_hwc, "tile_stitch_u8: null pointer");
+  DSIC_REQUIRE(C == 3 || C == 4, "tile_stitch_u8: C=%d must be 3 or 4", C);
+  DSIC_TILE_ARGS("tile_stitch_u8");
+  DSIC_REQUIRE(((uintptr_t)img_hwc & 15) == 0, "tile_stitch_u8: image must be 16-byte aligned");
+  hipLaunchKernelGGL(stitch_u8_kernel, grid, dim3(256), 0, (hipStream_t)stream, tiles, img_hwc, g, C, first_tile);
+  return check_launch("tile_stitch_u8");
+}
+
+extern "C" int dsic_container_pack(const uint8_t* bytes, int64_t cap_z, int64_t cap_y, const int* lengths,
+                                   const int* meta, const int* err, int B, uint32_t tag, int My, int Hy, int Wy,
+                                   int Nz, int Hz, int Wz, int64_t* workspace, uint8_t* out, void* stream) {
+  DSIC_REQUIRE(bytes && lengths && meta && workspace && out, "container_pack: null pointer");
+  DSIC_REQUIRE(B > 0 && cap_z > 0 && cap_y > 0 && cap_z % 4 == 0 && cap_y % 4 == 0,
+               "container_pack: bad shape (B=%d cap_z=%lld cap_y=%lld)", B, (long long)cap_z, (long long)cap_y);
+  DSIC_REQUIRE(((uintptr_t)bytes & 3) == 0, "container_pack: bytes must be 4-byte aligned");
+  DSIC_REQUIRE(B <= 32767, "container_pack: at most 32767 images per container");
+  hipStream_t st = (hipStream_t)stream;
+  long long* ws = (long long*)workspace;
+  hipLaunchKernelGGL(pack_head_kernel, dim3(1), dim3(256), 0, st, lengths, meta, err, B, cap_z, cap_y, tag, My, Hy,
+                     Wy, Nz, Hz, Wz, ws, out);
+  const int rc = check_launch("container_pack(head)");
+  if (rc) return rc;
+  hipLaunchKernelGGL(pack_strings_kernel, dim3(string_parts(cap_z > cap_y ? cap_z : cap_y), 2 * B), dim3(256), 0,
+                     st, bytes, lengths, B, cap_z, cap_y, (const long long*)ws, out);
+  return check_launch("container_pack(strings)");
+}
+
+extern "C" int dsic_container_scatter(const uint8_t* blob, int64_t blob_bytes, int B, int64_t max_len, uint8_t* zbuf,
+                                      int64_t zstride, uint8_t* ybuf, int64_t ystride, int* lengths, int* meta,
+                                      int64_t* workspace, void* stream) {
+  DSIC_REQUIRE(blob && zbuf && ybuf && lengths && meta && workspace, "container_scatter: null pointer");
+  DSIC_REQUIRE(B > 0 && blob_bytes >= kHeadBytes + (int64_t)kRecBytes * B, "container_scatter: blob too short for B=%d",
+               B);
+  DSIC_REQUIRE(zstride > 0 && ystride > 0 && zstride % 4 == 0 && ystride % 4 == 0,
+               "container_scatter: strides must be positive multiples of 4");
+  DSIC_REQUIRE(B <= 32767, "container_scatter: at most 32767 images per container");
+  hipStream_t st = (hipStream_t)stream;
+  long long* ws = (long long*)workspace;
+  hipLaunchKernelGGL(scatter_head_kernel, dim3(1), dim3(256), 0, st, blob, B, lengths, meta, ws);
+  const int rc = check_launch("container_scatter(head)");
+  if (rc) return rc;
+  hipLaunchKernelGGL(scatter_strings_kernel, dim3(string_parts(max_len), 2 * B), dim3(256), 0, st, blob, blob_bytes,
+                     B, zbuf, zstride, ybuf, ystride, (const int*)lengths, (const long long*)ws);
+  return check_launch("container_scatter(strings)");
+}

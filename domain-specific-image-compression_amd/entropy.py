@@ -26,7 +26,10 @@ class EntropyError(RuntimeError):
 
 
 def _check_err(err, what):
-    code = int(err.item())
+    _raise_err(int(err.item()), what)
+
+
+def _raise_err(code, what):
     if code:
         reasons = [m for bit, m in ((1, "support wider than Lmax"), (2, "symbol outside its support"),
                                     (4, "output capacity exceeded")) if code & bit]
@@ -258,10 +261,9 @@ def numerics_tag() -> int:
             | ((int(_lib.load().dsic_abi_version()) & 0xFFFF) << 16))
 
 
-@torch.no_grad()
-def custom_compress(model, x, tail=10, Lmax=DEFAULT_LMAX):
-    """eval_selfcontained_entropy.py:26-74.  Returns the reference's dict:
-    strings [[z_bytes, y_bytes], ...], shape_y, shape_z, min_y, max_y, min_z, max_z."""
+def _coded_batch(model, x, tail, Lmax, what, pack=False):
+    """forward(round) and the range coder of custom_compress, with its Lmax retry.  pack=True also writes the DSIC2
+    container on the device (_pack_on_device) and learns the error word with the container's size, one copy."""
     out = model(x, quant_mode="round")
     sigma_z = sigma_z_of(model)                                        # :32 (no clamp)
     if getattr(model, "spatial_params", False):
@@ -271,13 +273,24 @@ def custom_compress(model, x, tail=10, Lmax=DEFAULT_LMAX):
     while True:
         c = compress_latents(out["y_tilde"], out["z_tilde"], _per_channel(out["sigma"]),
                              _per_channel(out["nu"]), sigma_z, tail, Lmax)
+        if pack:
+            c["container"], c["container_bytes"], code = _pack_on_device(c, numerics_tag())
+        else:
+            code = int(c["err"].item())
         try:
-            _check_err(c["err"], "custom_compress")
-            break
+            _raise_err(code, what)
+            return c
         except EntropyError:
-            if Lmax >= 1000 or not (int(c["err"].item()) & 1):
+            if Lmax >= 1000 or not (code & 1):
                 raise
             Lmax = min(1000, Lmax * 2)                                 # wider support than expected
+
+
+@torch.no_grad()
+def custom_compress(model, x, tail=10, Lmax=DEFAULT_LMAX):
+    """eval_selfcontained_entropy.py:26-74.  Returns the reference's dict:
+    strings [[z_bytes, y_bytes], ...], shape_y, shape_z, min_y, max_y, min_z, max_z."""
+    c = _coded_batch(model, x, tail, Lmax, "custom_compress")
     lengths = c["lengths"].cpu().numpy()
     meta = c["meta"].cpu().numpy()
     raw = c["bytes"].cpu().numpy()
@@ -304,35 +317,33 @@ def _upload_strings(strings, which, dev):
     return (torch.from_numpy(buf).to(dev), torch.tensor(lens, dtype=torch.int32, device=dev), stride)
 
 
-@torch.no_grad()
-def custom_decompress(model, compressed, Lmax=None):
-    """eval_selfcontained_entropy.py:76-123: decode z, re-run h_s, decode y, run g_s, clamp."""
-    dev = next(model.parameters()).device
-    tag = compressed.get("numerics")
+def _refuse_tag(tag, what):
     if tag is not None and int(tag) != numerics_tag():
-        raise EntropyError(f"custom_decompress: the stream was written with numerics tag {int(tag):#x}, this decoder "
+        raise EntropyError(f"{what}: the stream was written with numerics tag {int(tag):#x}, this decoder "
                            f"is {numerics_tag():#x} (table flow / kernel arithmetic differ: the coder tables would "
                            "not match and the latents would decode to garbage)")
-    strings = compressed["strings"]
-    B = len(strings)
-    _, M, Hy, Wy = compressed["shape_y"]
-    _, N, Hz, Wz = compressed["shape_z"]
-    meta_np = np.array([[compressed["min_y"][b], compressed["max_y"][b] - compressed["min_y"][b] + 1,
-                         compressed["min_z"][b], compressed["max_z"][b] - compressed["min_z"][b] + 1]
-                        for b in range(B)], dtype=np.int32)
-    if Lmax is None:
-        Lmax = int(meta_np[:, [1, 3]].max())
-        Lmax = (Lmax + 7) // 8 * 8 if getattr(model, "spatial_params", False) else max(DEFAULT_LMAX, Lmax)
-    meta = torch.from_numpy(meta_np).to(dev)
+
+
+def _default_lmax(model, meta_np):
+    Lmax = int(meta_np[:, [1, 3]].max())
+    return (Lmax + 7) // 8 * 8 if getattr(model, "spatial_params", False) else max(DEFAULT_LMAX, Lmax)
+
+
+def _decode_batch(model, shape_y, shape_z, meta, Lmax, z, y, what):
+    """:76-120 from strings already on the device: z / y = (buffer, stride, lengths, lstride, loff) as
+    dsic_range_decode takes them.  Returns g_s's output, not yet clamped."""
+    dev = meta.device
+    B, M, Hy, Wy = shape_y
+    _, N, Hz, Wz = shape_z
     err = torch.zeros(1, dtype=torch.int32, device=dev)
     L = _lib.load()
     sigma_z = sigma_z_of(model)
     tab_z = torch.zeros((B, N, Lmax), dtype=torch.uint16, device=dev)
     _lib.check(L.dsic_cdf_tables_gauss(_p(sigma_z), _p(meta), _p(tab_z), B, N, Lmax, _p(err), _stream()),
                "cdf_tables_gauss")
-    zbuf, zlen, zstride = _upload_strings(strings, 0, dev)
+    zbuf, zstride, zlen, zls, zlo = z
     z_hat = torch.empty((B, N, Hz, Wz), dtype=torch.float32, device=dev)
-    _lib.check(L.dsic_range_decode(_p(zbuf), zstride, _p(zlen), 1, 0, _p(meta), 2, _p(tab_z), Lmax, B, N,
+    _lib.check(L.dsic_range_decode(_p(zbuf), zstride, _p(zlen), zls, zlo, _p(meta), 2, _p(tab_z), Lmax, B, N,
                                    Hz * Wz, 0, _p(z_hat), _p(err), _stream()), "range_decode(z)")
     # :100-106: hyper-synthesis on the decoded z
     (_, _, sigma_y, nu_y), _ = model.h_s.params_nhwc(ops.nchw_to_nhwc(z_hat), model.min_nu, model.max_nu)
@@ -341,12 +352,31 @@ def custom_decompress(model, compressed, Lmax=None):
     tab_y = torch.zeros((B, rows, Lmax), dtype=torch.uint16, device=dev)
     _lib.check(L.dsic_cdf_tables_student(_p(sigma_y.contiguous()), _p(nu_y.contiguous()), _p(meta), _p(tab_y), B,
                                          rows, Lmax, _p(err), _stream()), "cdf_tables_student")
-    ybuf, ylen, ystride = _upload_strings(strings, 1, dev)
+    ybuf, ystride, ylen, yls, ylo = y
     y_hat = torch.empty((B, M, Hy, Wy), dtype=torch.float32, device=dev)
-    _lib.check(L.dsic_range_decode(_p(ybuf), ystride, _p(ylen), 1, 0, _p(meta), 0, _p(tab_y), Lmax, B, M,
+    _lib.check(L.dsic_range_decode(_p(ybuf), ystride, _p(ylen), yls, ylo, _p(meta), 0, _p(tab_y), Lmax, B, M,
                                    Hy * Wy, per_element, _p(y_hat), _p(err), _stream()), "range_decode(y)")
-    _check_err(err, "custom_decompress")
-    x_hat = model.g_s.forward_nhwc(ops.nchw_to_nhwc(y_hat))            # :120
+    _check_err(err, what)
+    return model.g_s.forward_nhwc(ops.nchw_to_nhwc(y_hat))            # :120
+
+
+@torch.no_grad()
+def custom_decompress(model, compressed, Lmax=None):
+    """eval_selfcontained_entropy.py:76-123: decode z, re-run h_s, decode y, run g_s, clamp."""
+    dev = next(model.parameters()).device
+    _refuse_tag(compressed.get("numerics"), "custom_decompress")
+    strings = compressed["strings"]
+    B = len(strings)
+    meta_np = np.array([[compressed["min_y"][b], compressed["max_y"][b] - compressed["min_y"][b] + 1,
+                         compressed["min_z"][b], compressed["max_z"][b] - compressed["min_z"][b] + 1]
+                        for b in range(B)], dtype=np.int32)
+    if Lmax is None:
+        Lmax = _default_lmax(model, meta_np)
+    meta = torch.from_numpy(meta_np).to(dev)
+    zbuf, zlen, zstride = _upload_strings(strings, 0, dev)
+    ybuf, ylen, ystride = _upload_strings(strings, 1, dev)
+    x_hat = _decode_batch(model, compressed["shape_y"], compressed["shape_z"], meta, Lmax,
+                          (zbuf, zstride, zlen, 1, 0), (ybuf, ystride, ylen, 1, 0), "custom_decompress")
     return x_hat.clamp(0, 1)                                           # :123
 
 
@@ -405,3 +435,84 @@ def unpack_container(blob: bytes):
     return {"strings": strings, "shape_y": [B, My, Hy, Wy], "shape_z": [B, Nz, Hz, Wz],
             "min_y": [m[0] for m in meta], "max_y": [m[1] for m in meta],
             "min_z": [m[2] for m in meta], "max_z": [m[3] for m in meta], "numerics": tag}
+
+
+# ---- the same container, written and read on the device (codec.py's batches) ----------------------------------
+_HEAD = 38          # magic, tag, 7 shape words
+_REC = 24           # per image: min_y, max_y, min_z, max_z, len_z, len_y
+
+
+def _pack_on_device(c, tag):
+    """compress_latents' outputs -> (DSIC2 container in a device buffer, its size, the coder's error word).  The size and
+    the error word come back in one 16-byte copy; nothing is sliced per image on the host."""
+    B = c["bytes"].shape[0]
+    _, My, Hy, Wy = c["shape_y"]
+    _, Nz, Hz, Wz = c["shape_z"]
+    dev = c["bytes"].device
+    out = torch.empty(_HEAD + _REC * B + B * (c["cap_z"] + c["cap_y"]), dtype=torch.uint8, device=dev)
+    ws = torch.empty(2 * B + 3, dtype=torch.int64, device=dev)
+    _lib.check(_lib.load().dsic_container_pack(_p(c["bytes"]), c["cap_z"], c["cap_y"], _p(c["lengths"]), _p(c["meta"]),
+                                               _p(c["err"]), B, tag & 0xFFFFFFFF, My, Hy, Wy, Nz, Hz, Wz, _p(ws),
+                                               _p(out), _stream()), "container_pack")
+    nbytes, code = (int(v) for v in ws[:2].cpu())
+    return out, nbytes, code
+
+
+@torch.no_grad()
+def compress_to_container(model, x, tail=10, Lmax=DEFAULT_LMAX) -> bytes:
+    """pack_container(custom_compress(model, x, tail, Lmax)), byte for byte, with the container assembled on the
+    device: one copy of exactly the container's bytes leaves the GPU."""
+    c = _coded_batch(model, x, tail, Lmax, "compress_to_container", pack=True)
+    return c["container"][:c["container_bytes"]].cpu().numpy().tobytes()
+
+
+def _container_records(blob):
+    """DSIC2 header and records -> (tag, shape_y, shape_z, records int64 [B,6]); the checks of unpack_container."""
+    import struct
+    if blob[:6] == _MAGIC_V1:
+        raise ValueError("DSIC1 container: written before the numerics tag existed (its coder tables may be the float64 "
+                         "ones of round 1); re-encode")
+    if len(blob) < _HEAD or blob[:6] != _MAGIC:
+        raise ValueError("not a DSIC container")
+    (tag,) = struct.unpack_from("<I", blob, 6)
+    B, My, Hy, Wy, Nz, Hz, Wz = struct.unpack_from("<7I", blob, 10)
+    if B < 1 or len(blob) < _HEAD + _REC * B:
+        raise ValueError("truncated or oversized DSIC container")
+    rec = np.frombuffer(blob, dtype="<i4", count=6 * B, offset=_HEAD).reshape(B, 6).astype(np.int64)
+    rec[:, 4:] &= 0xFFFFFFFF                                           # the lengths are unsigned
+    if _HEAD + _REC * B + int(rec[:, 4:].sum()) != len(blob):
+        raise ValueError("truncated or oversized DSIC container")
+    return tag, [B, My, Hy, Wy], [B, Nz, Hz, Wz], rec
+
+
+def _decompress_container_raw(model, blob, Lmax=None, what="decompress_container"):
+    dev = next(model.parameters()).device
+    tag, shape_y, shape_z, rec = _container_records(blob)
+    _refuse_tag(tag, what)
+    B = shape_y[0]
+    meta_np = np.stack([rec[:, 0], rec[:, 1] - rec[:, 0] + 1, rec[:, 2], rec[:, 3] - rec[:, 2] + 1], axis=1)
+    if Lmax is None:
+        Lmax = _default_lmax(model, meta_np)
+    # custom_decompress's strides (_upload_strings); the device copy of the blob is padded to whole 16-byte chunks
+    zstride = max(4, (int(rec[:, 4].max()) + 3) // 4 * 4)
+    ystride = max(4, (int(rec[:, 5].max()) + 3) // 4 * 4)
+    host = torch.empty((len(blob) + 31) // 16 * 16, dtype=torch.uint8)
+    host.numpy()[:len(blob)] = np.frombuffer(blob, dtype=np.uint8)
+    d_blob = host.to(dev)
+    zbuf = torch.empty(B * zstride, dtype=torch.uint8, device=dev)
+    ybuf = torch.empty(B * ystride, dtype=torch.uint8, device=dev)
+    lengths = torch.empty((B, 2), dtype=torch.int32, device=dev)
+    meta = torch.empty((B, 4), dtype=torch.int32, device=dev)
+    ws = torch.empty(2 * B + 3, dtype=torch.int64, device=dev)
+    _lib.check(_lib.load().dsic_container_scatter(_p(d_blob), len(blob), B, int(rec[:, 4:].max()), _p(zbuf), zstride,
+                                                  _p(ybuf), ystride, _p(lengths), _p(meta), _p(ws), _stream()),
+               "container_scatter")
+    return _decode_batch(model, shape_y, shape_z, meta, Lmax, (zbuf, zstride, lengths, 2, 0),
+                         (ybuf, ystride, lengths, 2, 1), what)
+
+
+@torch.no_grad()
+def decompress_container(model, blob, Lmax=None):
+    """custom_decompress(model, unpack_container(blob)), bit for bit: the blob is uploaded once and its strings are
+    moved into the decoder's buffers on the device; the host reads only the header and the 24-byte records."""
+    return _decompress_container_raw(model, bytes(blob), Lmax).clamp(0, 1)

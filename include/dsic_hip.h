@@ -361,6 +361,47 @@ int dsic_range_decode(const uint8_t* in, int64_t stride, const int* lengths,
                       const uint16_t* tables, int Lmax, int B, int C, int HW,
                       int per_element, float* out_nchw, int* err, void* stream);
 
+/* ---- whole-image codec (codec.py; no reference counterpart: its driver codes one
+ * image of sizes that are multiples of 16 in one pass, eval_selfcontained_entropy.py:126-159) --
+ * Tile grid of an H x W image and tiles th x tw (multiples of 16, >= 32, at most the padded
+ * size): Hp = ceil16(H), tiles_y = ceil(Hp/th), origin of tile row i = min(i*th, Hp-th), tile
+ * row i owns padded rows [i*th, min((i+1)*th, Hp)); columns likewise; tiles numbered row-major.
+ * Padding to Hp x Wp reflects bottom/right as dsic_reflect_pad_br does (Hp-H < H, Wp-W < W).
+ * The calls handle tiles [first_tile, first_tile+n_tiles) of the grid.
+ * gather: img uint8 [H][W][C] (C 3 or 4) -> tiles uint8 [n][th][tw][C], or img float32
+ *   [C][H][W] -> tiles float32 [n][C][th][tw]; tiles 16-byte aligned.
+ * stitch: decoded tiles float32 [n][C][th][tw] -> the pixels they own, cropped to H x W, into
+ *   img float32 [C][H][W] as clamp(x,0,1), or img uint8 [H][W][C] as (uint8)(clamp(x,0,1)*255)
+ *   (truncating, = torch x.clamp(0,1).mul(255).to(uint8)); img 16-byte aligned. */
+int dsic_tile_gather_u8(const uint8_t* img_hwc, uint8_t* tiles, int H, int W, int C,
+                        int th, int tw, int first_tile, int n_tiles, void* stream);
+int dsic_tile_gather_f32(const float* img_chw, float* tiles, int H, int W, int C,
+                         int th, int tw, int first_tile, int n_tiles, void* stream);
+int dsic_tile_stitch_f32(const float* tiles, float* img_chw, int H, int W, int C,
+                         int th, int tw, int first_tile, int n_tiles, void* stream);
+int dsic_tile_stitch_u8(const float* tiles, uint8_t* img_hwc, int H, int W, int C,
+                        int th, int tw, int first_tile, int n_tiles, void* stream);
+
+/* The DSIC2 container of entropy.pack_container, written on the device from the outputs of
+ * dsic_range_encode (bytes [B][cap_z+cap_y], lengths [B][2], meta [B][4] of
+ * dsic_latent_support; err may be NULL): magic "DSIC2\0" | tag u32 | B,My,Hy,Wy,Nz,Hz,Wz u32 |
+ * B x (min_y,max_y,min_z,max_z i32, len_z,len_y u32) | B x (z string, y string).
+ * out holds at least 38 + 24*B + B*(cap_z+cap_y) bytes.  workspace: 2*B+3 int64; on
+ * completion workspace[0] = container bytes, workspace[1] = *err (0 without err),
+ * workspace[2..2+2B] = offsets of the strings after the records (exclusive scan). */
+int dsic_container_pack(const uint8_t* bytes, int64_t cap_z, int64_t cap_y, const int* lengths,
+                        const int* meta, const int* err, int B, uint32_t tag, int My, int Hy,
+                        int Wy, int Nz, int Hz, int Wz, int64_t* workspace, uint8_t* out,
+                        void* stream);
+/* Inverse for the decoder: a DSIC2 container of B images (blob_bytes bytes on the device) ->
+ * z strings at zbuf + b*zstride, y strings at ybuf + b*ystride, lengths [B][2] (z, y) and
+ * meta [B][4] (ymin, Ly, zmin, Lz) as dsic_range_decode takes them (lstride 2).  The caller has
+ * checked the records on the host (max_len = the longest string, <= both strides); bytes past
+ * a string's length in zbuf / ybuf are left as they are.  workspace: 2*B+3 int64. */
+int dsic_container_scatter(const uint8_t* blob, int64_t blob_bytes, int B, int64_t max_len,
+                           uint8_t* zbuf, int64_t zstride, uint8_t* ybuf, int64_t ystride,
+                           int* lengths, int* meta, int64_t* workspace, void* stream);
+
 /* HIP stream limited to the CUs whose bit is set in mask_host[words] (bit i of
  * word i/32 = CU i).  Used to give the range coder its own few CUs beside the
  * conv kernels; there is no reference counterpart (the reference is
