@@ -41,7 +41,8 @@ template <int C, bool U8 = false, bool BF16 = false>
 __global__ __launch_bounds__(256, 2) void conv_first_kernel(
     const void* __restrict__ xv, const float* __restrict__ w, const float* __restrict__ bias,
     const float* __restrict__ beta, const float* __restrict__ gamma, float* __restrict__ out, int B,
-    int H, int W, int Cout, int act, int tiles_x, int tiles_y, int s2d) {
+    int H, int W, int Cout, int act, int tiles_x, int tiles_y, int layout) {
+  const int s2d = layout & 1, cm = layout & DSIC_LAYOUT_CM16;
   constexpr int K = 9 * C;
   constexpr int KP = (K + 1) / 2 * 2;  // even
   constexpr int NS = KP / 2;           // MFMA k-steps
@@ -218,9 +219,12 @@ __global__ __launch_bounds__(256, 2) void conv_first_kernel(
       const int ox = ox0 + r % TW, oy = oy0 + r / TW;
       if (oy < H && ox < W && nn < Cout) {
         // s2d: pixel (oy,ox) becomes channel block (oy&1)*2+(ox&1) of pixel (oy/2,ox/2)
-        const size_t o = s2d ? (((size_t)n * (H >> 1) + (oy >> 1)) * (W >> 1) + (ox >> 1)) * (4 * Cout) +
-                                   ((oy & 1) * 2 + (ox & 1)) * Cout + nn
-                             : (((size_t)n * H + oy) * W + ox) * Cout + nn;
+        const int64_t pix = s2d ? (int64_t)(oy >> 1) * (W >> 1) + (ox >> 1) : (int64_t)oy * W + ox;
+        const int64_t npix = s2d ? (int64_t)(H >> 1) * (W >> 1) : (int64_t)H * W;
+        const int Co = s2d ? 4 * Cout : Cout, ch = s2d ? ((oy & 1) * 2 + (ox & 1)) * Cout + nn : nn;
+        // chunk-major: [B][C/16][pixels][16] (Cout % 16 == 0: a quad never straddles a chunk)
+        const size_t o = cm ? (size_t)(((int64_t)n * Co + (ch & ~15)) * npix + pix * 16 + (ch & 15))
+                            : (size_t)(((int64_t)n * npix + pix) * Co + ch);
         __builtin_nontemporal_store(v, (floatx4*)(out + o));
       }
     }
@@ -263,7 +267,9 @@ static int conv_first_launch(const void* x, bool u8, const float* w_oihw, const 
   DSIC_REQUIRE(Cout > 0 && Cout <= 128 && Cout % 4 == 0, "conv_first: Cout=%d must be a multiple of 4, <= 128", Cout);
   DSIC_REQUIRE(act == DSIC_ACT_NONE || act == DSIC_ACT_GDN || act == DSIC_ACT_RELU, "conv_first: act=%d", act);
   DSIC_REQUIRE(act != DSIC_ACT_GDN || (beta && gamma), "conv_first: GDN needs beta and gamma");
-  DSIC_REQUIRE(!s2d || (H % 2 == 0 && W % 2 == 0), "conv_first: space-to-depth output needs even H and W");
+  DSIC_REQUIRE((s2d & ~(1 | DSIC_LAYOUT_CM16)) == 0, "conv_first: s2d=%d", s2d);
+  DSIC_REQUIRE(!(s2d & 1) || (H % 2 == 0 && W % 2 == 0), "conv_first: space-to-depth output needs even H and W");
+  DSIC_REQUIRE(!(s2d & DSIC_LAYOUT_CM16) || Cout % 16 == 0, "conv_first: a chunk-major output needs Cout %% 16 == 0");
   const int tx = ceil_div(W, 16), ty = ceil_div(H, 8);
   DSIC_REQUIRE((int64_t)tx * ty * B < ((int64_t)1 << 31), "conv_first: grid too large");
   dim3 grid(tx * ty * B), block(256);

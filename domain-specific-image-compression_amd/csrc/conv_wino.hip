@@ -737,6 +737,7 @@ extern "C" int dsic_conv3x3_wino_nhwc(const float* in, const float* u_packed, co
   DSIC_REQUIRE(Cout > 0 && Cout % 4 == 0 && Cout <= 128, "conv3x3_wino: Cout=%d must be a multiple of 4, <= 128", Cout);
   DSIC_REQUIRE(act >= 0 && act <= 3, "conv3x3_wino: act=%d", act);
   DSIC_REQUIRE(!(act == DSIC_ACT_GDN || act == DSIC_ACT_IGDN) || (beta && gamma), "conv3x3_wino: GDN needs beta and gamma");
+  DSIC_REQUIRE(!((s2d_out | s2d_in) & DSIC_LAYOUT_CM16), "conv3x3_wino: chunk-major activations are not supported");
   WinoArgs a{};
   a.in = in; a.u = u_packed; a.bias = bias; a.beta = beta; a.gamma = gamma; a.out = out;
   DSIC_REQUIRE(!s2d_out || (H % 2 == 0 && W % 2 == 0), "conv3x3_wino: space-to-depth output needs even H and W");

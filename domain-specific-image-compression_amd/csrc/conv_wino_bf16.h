@@ -61,6 +61,8 @@ struct Args {
   // un-biased, un-activated sums into out + ks*part_stride (same addressing); splitk_reduce_kernel finishes
   int ksplit, kchunks;
   int64_t part_stride;
+  // chunk-major (CM16) activations [B][C/16][H][W][16] on the input / output side (conv_wino_bf16m.hip only)
+  int cm_in, cm_out;
 };
 
 constexpr int P = WB_PLANES;

@@ -670,7 +670,12 @@ static int wb_launch(wb::Args& a, hipStream_t st) {
                    (int64_t)H * W * a.ostride * 4 * (a.nphase == 4 ? 4 : 1) < ((int64_t)1 << 31),
                "conv_wino_bf16: one image must stay below 2 GiB (32-bit offsets inside an image)");
   DSIC_REQUIRE(a.u_phase_bytes * a.nphase < ((int64_t)1 << 31), "conv_wino_bf16: transformed weights must stay below 2 GiB");
-  if (a.ksplit == 1 && dsic_wino_bf16_m64(H, W, a.Cin, a.nphase)) return dsic_wbm_launch(a, st);   // large layers: conv_wino_bf16m.hip
+  const bool m64 = a.ksplit == 1 && dsic_wino_bf16_m64(H, W, a.Cin, a.nphase);
+  DSIC_REQUIRE(m64 || !(a.cm_in || a.cm_out),
+               "conv_wino_bf16: chunk-major activations exist for the layers of the 64-tile kernel only (dsic_wino_bf16_m64)");
+  DSIC_REQUIRE(!a.cm_out || (a.ostride == a.Cout && a.ooff == 0 && a.Cout % 16 == 0),
+               "conv_wino_bf16: a chunk-major output is a dense tensor of whole 16-channel chunks (Cout=%d)", a.Cout);
+  if (m64) return dsic_wbm_launch(a, st);   // large layers: conv_wino_bf16m.hip
   a.ntiles = (int)nt;
   a.nt_out = a.ksplit == 1 && (int64_t)B * H * W * a.Cout * 4 * (a.nphase == 4 ? 4 : 1) > (300ll << 20);
   int dev = 0;
@@ -737,12 +742,13 @@ extern "C" int dsic_conv3x3_wino_bf16_nhwc(const float* in, const void* u_planes
   DSIC_REQUIRE(Cout > 0 && Cout % 4 == 0 && Cout <= 128, "conv3x3_wino_bf16: Cout=%d must be a multiple of 4, <= 128", Cout);
   DSIC_REQUIRE(act >= 0 && act <= 3, "conv3x3_wino_bf16: act=%d", act);
   DSIC_REQUIRE(!(act == DSIC_ACT_GDN || act == DSIC_ACT_IGDN) || (beta && gamma), "conv3x3_wino_bf16: GDN needs beta and gamma");
-  DSIC_REQUIRE(!s2d_out || (H % 2 == 0 && W % 2 == 0), "conv3x3_wino_bf16: space-to-depth output needs even H and W");
-  DSIC_REQUIRE(!s2d_in || Cin % 128 == 0, "conv3x3_wino_bf16: space-to-depth input needs Cin = 4*Cs with Cs %% 32 == 0");
+  DSIC_REQUIRE(!(s2d_out & 1) || (H % 2 == 0 && W % 2 == 0), "conv3x3_wino_bf16: space-to-depth output needs even H and W");
+  DSIC_REQUIRE(!(s2d_in & 1) || Cin % 128 == 0, "conv3x3_wino_bf16: space-to-depth input needs Cin = 4*Cs with Cs %% 32 == 0");
   wb::Args a{};
   a.in = in; a.u = u_planes; a.bias = bias; a.beta = beta; a.gamma = gamma; a.out = out;
   a.B = B; a.H = H; a.W = W; a.Cin = Cin; a.Cout = Cout; a.CoutP = round_up(Cout, 32); a.act = act;
-  a.s2d = s2d_out; a.s2d_in = s2d_in ? 1 : 0;
+  a.s2d = s2d_out & 1; a.s2d_in = s2d_in & 1;
+  a.cm_out = (s2d_out & DSIC_LAYOUT_CM16) ? 1 : 0; a.cm_in = (s2d_in & DSIC_LAYOUT_CM16) ? 1 : 0;
   a.ostride = out_cstride; a.ooff = out_coff;
   a.ticket = (unsigned long long*)ticket;
   a.nphase = 1; a.u_phase_bytes = dsic_wino_bf16_weight_bytes(Cout, Cin);
@@ -779,7 +785,8 @@ extern "C" int dsic_conv3x3_wino_bf16_splitk_nhwc(const float* in, const void* u
   wb::Args a{};
   a.in = in; a.u = u_planes; a.bias = nullptr; a.beta = nullptr; a.gamma = nullptr; a.out = partials;
   a.B = B; a.H = H; a.W = W; a.Cin = Cin; a.Cout = Cout; a.CoutP = round_up(Cout, 32); a.act = DSIC_ACT_NONE;
-  a.s2d = s2d_out; a.s2d_in = s2d_in ? 1 : 0;
+  DSIC_REQUIRE(!((s2d_out | s2d_in) & DSIC_LAYOUT_CM16), "conv3x3_wino_bf16_splitk: chunk-major activations are not supported");
+  a.s2d = s2d_out & 1; a.s2d_in = s2d_in & 1;
   a.ostride = out_cstride; a.ooff = out_coff;
   a.ticket = (unsigned long long*)ticket;
   a.nphase = 1; a.u_phase_bytes = dsic_wino_bf16_weight_bytes(Cout, Cin);
@@ -804,10 +811,26 @@ extern "C" int dsic_conv3x3_wino_bf16_splitk_nhwc(const float* in, const void* u
   return check_launch("conv3x3_wino_bf16_splitk");
 }
 
+extern "C" int dsic_conv_transpose2d_wino_bf16_layout(const float* in, const void* u_planes4, const float* bias,
+                                                      const float* beta, const float* gamma, float* out, int B,
+                                                      int H, int W, int Cin, int Cout, int act, int layout_in,
+                                                      int layout_out, void* ticket, void* stream);
+
 extern "C" int dsic_conv_transpose2d_wino_bf16_nhwc(const float* in, const void* u_planes4, const float* bias,
                                                     const float* beta, const float* gamma, float* out, int B,
                                                     int H, int W, int Cin, int Cout, int act, void* ticket,
                                                     void* stream) {
+  return dsic_conv_transpose2d_wino_bf16_layout(in, u_planes4, bias, beta, gamma, out, B, H, W, Cin, Cout, act, 0, 0,
+                                                ticket, stream);
+}
+
+// layout_in / layout_out: 0 = NHWC, DSIC_LAYOUT_CM16 = chunk-major [B][C/16][H][W][16] (64-tile kernel only)
+extern "C" int dsic_conv_transpose2d_wino_bf16_layout(const float* in, const void* u_planes4, const float* bias,
+                                                      const float* beta, const float* gamma, float* out, int B,
+                                                      int H, int W, int Cin, int Cout, int act, int layout_in,
+                                                      int layout_out, void* ticket, void* stream) {
+  DSIC_REQUIRE((layout_in == 0 || layout_in == DSIC_LAYOUT_CM16) && (layout_out == 0 || layout_out == DSIC_LAYOUT_CM16),
+               "convT_wino_bf16: layout_in=%d layout_out=%d", layout_in, layout_out);
   DSIC_REQUIRE(in && u_planes4 && bias && out && ticket, "convT_wino_bf16: null pointer");
   DSIC_REQUIRE(B > 0 && H > 0 && W > 0, "convT_wino_bf16: empty tensor");
   DSIC_REQUIRE(Cin >= 64 && Cin % 32 == 0, "convT_wino_bf16: Cin=%d must be a multiple of 32, >= 64", Cin);
@@ -819,5 +842,6 @@ extern "C" int dsic_conv_transpose2d_wino_bf16_nhwc(const float* in, const void*
   a.B = B; a.H = H; a.W = W; a.Cin = Cin; a.Cout = Cout; a.CoutP = round_up(Cout, 32); a.act = act;
   a.ticket = (unsigned long long*)ticket;
   a.s2d = 0; a.s2d_in = 0; a.nphase = 4; a.u_phase_bytes = dsic_wino_bf16_weight_bytes(Cout, Cin);
+  a.cm_in = layout_in ? 1 : 0; a.cm_out = layout_out ? 1 : 0;
   return wb_launch(a, (hipStream_t)stream);
 }

@@ -179,6 +179,12 @@ __global__ __launch_bounds__(THREADS) void conv_wino_bf16m_kernel(const Args a) 
     //   phase sg: issue the window of chunk-pass sg + 3; transform sg + 1; wait for the window of sg + 2 (all but
     //             this wave's newest NDMA loads); barrier.
     // A window has two phases to arrive; an out-of-image pixel is an out-of-range offset (the DMA writes zeros).
+    // Chunk-major input (a.cm_in, [B][Cin/16][H][W][16]): a pixel's 16 channels of the chunk are 64 contiguous bytes
+    // and the chunk is a plane of H*W pixels, so a window row is 18 x 64 contiguous bytes and every line a window
+    // fetches belongs to its own chunk (NHWC: 64-byte pieces Cin*4 bytes apart, two chunks per 128-byte line).  Only
+    // the pixel stride and the chunk stride differ; the LDS window is the same.
+    const int pix_f = a.cm_in ? CK : Cin;                                        // floats per pixel of the input
+    const unsigned chunk_in_b = a.cm_in ? (unsigned)(a.H * a.W * CK * 4) : (unsigned)(CK * 4);   // bytes per chunk
     struct WinAim {
       unsigned off[NLOAD];
       uintx4 rsrc;
@@ -198,7 +204,7 @@ __global__ __launch_bounds__(THREADS) void conv_wino_bf16m_kernel(const Args a) 
         const int wy = pix / WINW, wx = pix - wy * WINW;
         const int gy = t.ty * 16 - 1 + wy, gx = t.tx * 16 - 1 + wx;
         const bool ok = i < WINITEMS && gy >= 0 && gy < a.H && gx >= 0 && gx < a.W && !(WBM_ABL & 2);
-        m.off[j] = ok ? (unsigned)(((gy * a.W + gx) * Cin + 4 * q) * 4) : 0x80000000u;
+        m.off[j] = ok ? (unsigned)(((gy * a.W + gx) * pix_f + 4 * q) * 4) : 0x80000000u;
       }
     };
     auto aim_nowhere = [&](WinAim& m) {
@@ -208,7 +214,7 @@ __global__ __launch_bounds__(THREADS) void conv_wino_bf16m_kernel(const Args a) 
     auto dma = [&](int wbuf, int chunk) {
       const uintx4 rs = {(unsigned)__builtin_amdgcn_readfirstlane((int)am.rsrc[0]), (unsigned)__builtin_amdgcn_readfirstlane((int)am.rsrc[1]),
                          (unsigned)__builtin_amdgcn_readfirstlane((int)am.rsrc[2]), (unsigned)__builtin_amdgcn_readfirstlane((int)am.rsrc[3])};
-      const unsigned soff = (unsigned)(chunk * (CK * 4));
+      const unsigned soff = (unsigned)chunk * chunk_in_b;
 #pragma unroll
       for (int j = 0; j < NLOAD; ++j) {
         const unsigned m0v = lds_base + (unsigned)(STAGEOFF + wbuf * WINB + 16 * (hw * 64 + 256 * j));
@@ -429,20 +435,25 @@ __global__ __launch_bounds__(THREADS) void conv_wino_bf16m_kernel(const Args a) 
     return v;
   };
   // output addressing (bytes): pixel of Winograd tile (ty, tx) of the workgroup tile, output (i, j) of that tile
-  //   = tbase + ty*SY + tx*SX + i*SI + j*SJ + channel*4
+  //   = tbase + ty*SY + tx*SX + i*SI + j*SJ + channel offset (NHWC: channel*4)
+  // Chunk-major output (a.cm_out, [B][C/16][OH][OW][16]): a pixel is 64 bytes of its chunk's plane, the channel
+  // offset is (channel/16)*plane + (channel%16)*4, and the space-to-depth block (j, i) is a channel offset of
+  // Cout/16 (2 Cout/16) planes.
+  const int OHW = a.nphase == 4 ? 4 * a.H * a.W : a.s2d ? (a.H >> 1) * (a.W >> 1) : a.H * a.W;   // output pixels
+  const int PB = a.cm_out ? CK * 4 : a.ostride * 4;                    // bytes per output pixel (of a chunk's plane)
   int SJ, SI;
   if (a.nphase == 4) {
-    SJ = 2 * a.ostride * 4;
-    SI = 2 * (2 * a.W) * a.ostride * 4;
+    SJ = 2 * PB;
+    SI = 2 * (2 * a.W) * PB;
   } else if (a.s2d) {
-    SJ = a.Cout * 4;
-    SI = 2 * a.Cout * 4;
+    SJ = a.cm_out ? (a.Cout / CK) * OHW * (CK * 4) : a.Cout * 4;
+    SI = 2 * SJ;
   } else {
-    SJ = a.ostride * 4;
-    SI = a.W * a.ostride * 4;
+    SJ = PB;
+    SI = a.W * PB;
   }
-  const int SX = a.nphase == 4 ? 2 * SJ : a.s2d ? 4 * a.Cout * 4 : 2 * SJ;
-  const int SY = a.nphase == 4 ? 2 * SI : a.s2d ? (a.W >> 1) * 4 * a.Cout * 4 : 2 * SI;
+  const int SX = a.nphase == 4 ? 2 * SJ : a.s2d ? (a.cm_out ? PB : 4 * a.Cout * 4) : 2 * SJ;
+  const int SY = a.nphase == 4 ? 2 * SI : a.s2d ? (a.W >> 1) * SX : 2 * SI;
 
   auto mfma_waves = [&](auto pq_tag) {
   constexpr int PQ = decltype(pq_tag)::value;
@@ -597,9 +608,9 @@ __global__ __launch_bounds__(THREADS) void conv_wino_bf16m_kernel(const Args a) 
       const __amdgpu_buffer_rsrc_t ors = __builtin_amdgcn_make_buffer_rsrc(
           (void*)(a.out + (size_t)cur.n * OH * OW * a.ostride + a.ooff), 0, (OH * OW * a.ostride - a.ooff) * 4, 0x00020000);
       const unsigned tbase =
-          a.nphase == 4 ? (unsigned)(((32 * cur.ty + ppy) * OW + 32 * cur.tx + ppx) * a.ostride * 4)
-          : a.s2d       ? (unsigned)(((8 * cur.ty) * (a.W >> 1) + 8 * cur.tx) * 4 * a.Cout * 4)
-                        : (unsigned)((16 * cur.ty * a.W + 16 * cur.tx) * a.ostride * 4);
+          a.nphase == 4 ? (unsigned)(((32 * cur.ty + ppy) * OW + 32 * cur.tx + ppx) * PB)
+          : a.s2d       ? (unsigned)(((8 * cur.ty) * (a.W >> 1) + 8 * cur.tx) * SX)
+                        : (unsigned)((16 * cur.ty * a.W + 16 * cur.tx) * PB);
       constexpr int XB = PQ == 0 ? 0 : 3;
       constexpr int t0 = step_of<MODE, 1, PQ>(XB * 4 + 0), t1 = step_of<MODE, 1, PQ>(XB * 4 + 1);
       constexpr int t2 = step_of<MODE, 1, PQ>(XB * 4 + 2), t3 = step_of<MODE, 1, PQ>(XB * 4 + 3);
@@ -610,7 +621,8 @@ __global__ __launch_bounds__(THREADS) void conv_wino_bf16m_kernel(const Args a) 
       const float* const prm = (const float*)(lds_raw + PARAMOFF) + nt * 32 + (ln & 31);
       const float pbias = prm[0], pbeta = prm[128], pgamma = prm[256];
       const int cq = nt * 32 + (ln & 7) * 4;     // first channel of this lane's quad
-      const unsigned svoff = cq < a.Cout ? (unsigned)((ln >> 3) * SX + cq * 4) : 0x80000000u;
+      const int cqoff = a.cm_out ? (cq >> 4) * OHW * (CK * 4) + (cq & 15) * 4 : cq * 4;
+      const unsigned svoff = cq < a.Cout ? (unsigned)((ln >> 3) * SX + cqoff) : 0x80000000u;
       auto emit = [&](auto act_tag, int m, int j, floatx16 y) {
         constexpr int ACT = decltype(act_tag)::value;
 #pragma unroll

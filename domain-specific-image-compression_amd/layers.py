@@ -20,6 +20,11 @@ from . import ops
 
 # DSIC_WINOGRAD=0 forces the direct implicit-GEMM kernel for every layer (A/B runs)
 USE_WINOGRAD = os.environ.get("DSIC_WINOGRAD", "1") != "0"
+# Chunk-major activations (ops.LAYOUT_CM16) between layers (A/B runs): DSIC_CHUNK_MAJOR=0 keeps every activation
+# NHWC; 1 passes the first layer's output chunk-major when its consumer runs on the 64-tile Winograd kernel;
+# 2 (default) also every activation whose producer and consumer both run on that kernel
+CHUNK_MAJOR = int(os.environ.get("DSIC_CHUNK_MAJOR", "2"))
+USE_CHUNK_MAJOR = CHUNK_MAJOR > 0
 
 
 def wino_bf16() -> bool:
@@ -174,12 +179,33 @@ class Conv2d(_ConvBase):
             self._wino_key = key
         return self._wino
 
-    def run_nhwc(self, x, act=ops.ACT_NONE, gdn=None, x_is_s2d=False, s2d_out=False):
+    def m64(self, H, W, x_is_s2d=False):
+        """Does this layer run on the 64-tile Winograd kernel (conv_wino_bf16m.hip), the only reader and writer of
+        chunk-major activations, for an input of H x W pixels (the space-to-depth grid when x_is_s2d)?"""
+        if not wino_bf16():
+            return False
+        if x_is_s2d:
+            cin, ok = 4 * self.in_channels, self.use_winograd_s2 and self.out_channels <= 128
+        else:
+            cin, ok = self.in_channels, self.use_winograd
+        from . import lib as _lib
+        return ok and cin >= 64 and bool(_lib.load().dsic_wino_bf16_m64(H, W, cin, 1))
+
+    def run_nhwc(self, x, act=ops.ACT_NONE, gdn=None, x_is_s2d=False, s2d_out=False, cm_in=False, cm_out=False):
         """x_is_s2d: x is the space-to-depth image of this layer's input; s2d_out: write the
-        output space-to-depth (only the Winograd paths can)."""
+        output space-to-depth (only the Winograd paths can).  cm_in / cm_out: chunk-major input / output
+        (only where m64() holds)."""
         beta = gamma = None
         if gdn is not None:
             beta, gamma = gdn.effective()
+        if cm_in or cm_out:
+            B, H, W, _ = ops.cm16_shape(x) if cm_in else x.shape
+            assert self.m64(H, W, x_is_s2d), "chunk-major activations need the 64-tile Winograd kernel"
+            taps = 25 if x_is_s2d else 9
+            return ops.conv3x3_wino_nhwc(x, self.packed_wino(), self.bias, self.out_channels, act, beta, gamma,
+                                         s2d_out=s2d_out, s2d_in=x_is_s2d, split_k=self.split_k, cm_in=cm_in,
+                                         cm_out=cm_out,
+                                         algo_flops=2.0 * B * H * W * self.out_channels * self.in_channels * taps)
         if x_is_s2d and self.out_channels > 128:
             B, H2, W2, _ = x.shape
             assert not s2d_out
@@ -248,14 +274,26 @@ class ConvTranspose2d(_ConvBase):
             return u
         return ops.pack_convT_weight(self.weight)
 
-    def run_nhwc(self, x, act=ops.ACT_NONE, gdn=None):
+    def m64(self, H, W):
+        """Does this layer run on the 64-tile Winograd kernel for an H x W input (see Conv2d.m64)?"""
+        if not (self.use_winograd and wino_bf16() and self.in_channels >= 64):
+            return False
+        from . import lib as _lib
+        return bool(_lib.load().dsic_wino_bf16_m64(H, W, self.in_channels, 4))
+
+    def run_nhwc(self, x, act=ops.ACT_NONE, gdn=None, cm_in=False, cm_out=False):
         if self.to_image:   # returns NCHW image
+            assert not (cm_in or cm_out)
             return ops.conv_transpose2d_image(x, self.packed(), self.bias, self.out_channels)
         beta = gamma = None
         if gdn is not None:
             beta, gamma = gdn.effective()
+        if cm_in or cm_out:
+            _, H, W, _ = ops.cm16_shape(x) if cm_in else x.shape
+            assert self.m64(H, W), "chunk-major activations need the 64-tile Winograd kernel"
         if self.use_winograd:
-            return ops.conv_transpose2d_wino_nhwc(x, self.packed(), self.bias, self.out_channels, act, beta, gamma)
+            return ops.conv_transpose2d_wino_nhwc(x, self.packed(), self.bias, self.out_channels, act, beta, gamma,
+                                                  cm_in=cm_in, cm_out=cm_out)
         return ops.conv_transpose2d_nhwc(x, self.packed(), self.bias, self.out_channels, act, beta, gamma)
 
     @torch.no_grad()
@@ -292,6 +330,26 @@ class _Chain(nn.Sequential):
         nxt = mods[j] if j < len(mods) else None
         return isinstance(nxt, Conv2d) and nxt.use_winograd_s2 and H % 2 == 0 and W % 2 == 0
 
+    @staticmethod
+    def _wants_cm(mods, j, H, W, s2d):
+        """Does the module at index j, the consumer of an output of H x W pixels (space-to-depth when s2d: then the
+        grid is H/2 x W/2), read it chunk-major?  Only the 64-tile Winograd kernel does."""
+        if not USE_CHUNK_MAJOR or j >= len(mods):
+            return False
+        nxt = mods[j]
+        if s2d:
+            return isinstance(nxt, Conv2d) and nxt.m64(H // 2, W // 2, True)
+        if isinstance(nxt, Conv2d):
+            return nxt.kernel_size == 3 and nxt.stride == 1 and nxt.m64(H, W)
+        return isinstance(nxt, ConvTranspose2d) and nxt.m64(H, W)
+
+    @staticmethod
+    def _tap(x, s2d, cm):
+        """A tap in the layout the fixtures know: NHWC at the layer's own resolution."""
+        if cm:
+            x = ops.cm16_to_nhwc(x)
+        return ops.depth_to_space(x) if s2d else x
+
     def forward_from_image(self, x_nchw, taps=None):
         """Like forward_nhwc but from an NCHW image: a leading conv(3|4 -> <=128, 3, 1)
         runs as the dedicated first-layer kernel (K = 9*Cimg, no channel padding)."""
@@ -306,70 +364,76 @@ class _Chain(nn.Sequential):
         if first_ok:
             nxt = mods[1] if len(mods) > 1 else None
             H, W = (x_nchw.shape[1], x_nchw.shape[2]) if u8 else (x_nchw.shape[2], x_nchw.shape[3])
-            if isinstance(nxt, GDN) and not nxt.inverse:
+            j = 2 if isinstance(nxt, GDN) and not nxt.inverse or isinstance(nxt, nn.ReLU) else 1
+            s2d = self._wants_s2d(mods, j, H, W)
+            cm = m.out_channels % 16 == 0 and self._wants_cm(mods, j, H, W, s2d)
+            if j == 2 and isinstance(nxt, GDN):
                 beta, gamma = nxt.effective()
-                s2d = self._wants_s2d(mods, 2, H, W)
-                y = ops.conv_first_nchw(x_nchw, m.weight, m.bias, ops.ACT_GDN, beta, gamma, s2d_out=s2d)
-                start = 2
-            elif isinstance(nxt, nn.ReLU):
-                s2d = self._wants_s2d(mods, 2, H, W)
-                y = ops.conv_first_nchw(x_nchw, m.weight, m.bias, ops.ACT_RELU, s2d_out=s2d)
-                start = 2
+                y = ops.conv_first_nchw(x_nchw, m.weight, m.bias, ops.ACT_GDN, beta, gamma, s2d_out=s2d, cm_out=cm)
+            elif j == 2:
+                y = ops.conv_first_nchw(x_nchw, m.weight, m.bias, ops.ACT_RELU, s2d_out=s2d, cm_out=cm)
             else:
-                s2d = self._wants_s2d(mods, 1, H, W)
-                y = ops.conv_first_nchw(x_nchw, m.weight, m.bias, s2d_out=s2d)
-                start = 1
+                y = ops.conv_first_nchw(x_nchw, m.weight, m.bias, s2d_out=s2d, cm_out=cm)
             if taps is not None:
-                taps.append(ops.depth_to_space(y) if s2d else y)
-            return self.forward_nhwc(y, taps, start, x_is_s2d=s2d)
+                taps.append(self._tap(y, s2d, cm))
+            return self.forward_nhwc(y, taps, j, x_is_s2d=s2d, x_is_cm=cm)
         return self.forward_nhwc(_to_nhwc(x_nchw), taps)
 
-    def forward_nhwc(self, x, taps=None, start=0, x_is_s2d=False):
+    def forward_nhwc(self, x, taps=None, start=0, x_is_s2d=False, x_is_cm=False):
+        """x_is_cm: x is chunk-major (ops.cm16_to_nhwc); the returned tensor is NHWC (or the NCHW image)."""
         mods = list(self)
         i = start
         while i < len(mods):
             m = mods[i]
             nxt = mods[i + 1] if i + 1 < len(mods) else None
-            out_s2d = False
+            out_s2d = out_cm = False
+            # spatial size of the input
+            H, W = (x.shape[2], x.shape[3]) if x_is_cm else (x.shape[1], x.shape[2])
             if isinstance(m, Conv2d):
                 fused = isinstance(nxt, (GDN, nn.ReLU))
                 # spatial size of this layer's output
                 if x_is_s2d:
-                    Ho, Wo = x.shape[1], x.shape[2]
+                    Ho, Wo = H, W
                 else:
-                    Ho, Wo = -(-x.shape[1] // m.stride), -(-x.shape[2] // m.stride)
-                out_s2d = m.can_write_s2d(x_is_s2d) and self._wants_s2d(mods, i + (2 if fused else 1), Ho, Wo)
+                    Ho, Wo = -(-H // m.stride), -(-W // m.stride)
+                j = i + (2 if fused else 1)
+                out_s2d = m.can_write_s2d(x_is_s2d) and self._wants_s2d(mods, j, Ho, Wo)
+                out_cm = CHUNK_MAJOR > 1 and (x_is_s2d or m.kernel_size == 3) and m.m64(H, W, x_is_s2d) and \
+                    self._wants_cm(mods, j, Ho, Wo, out_s2d)
                 if isinstance(nxt, GDN):
-                    x = m.run_nhwc(x, ops.ACT_IGDN if nxt.inverse else ops.ACT_GDN, nxt, x_is_s2d, out_s2d)
+                    x = m.run_nhwc(x, ops.ACT_IGDN if nxt.inverse else ops.ACT_GDN, nxt, x_is_s2d, out_s2d,
+                                   x_is_cm, out_cm)
                 elif isinstance(nxt, nn.ReLU):
-                    x = m.run_nhwc(x, ops.ACT_RELU, None, x_is_s2d, out_s2d)
+                    x = m.run_nhwc(x, ops.ACT_RELU, None, x_is_s2d, out_s2d, x_is_cm, out_cm)
                 else:
-                    x = m.run_nhwc(x, ops.ACT_NONE, None, x_is_s2d, out_s2d)
-                i += 2 if fused else 1
+                    x = m.run_nhwc(x, ops.ACT_NONE, None, x_is_s2d, out_s2d, x_is_cm, out_cm)
+                i = j
             elif isinstance(m, ConvTranspose2d):
                 assert not x_is_s2d
+                fused = isinstance(nxt, (GDN, nn.ReLU))
+                j = i + (2 if fused else 1)
+                out_cm = CHUNK_MAJOR > 1 and m.m64(H, W) and self._wants_cm(mods, j, 2 * H, 2 * W, False)
                 if isinstance(nxt, GDN):
-                    x = m.run_nhwc(x, ops.ACT_IGDN if nxt.inverse else ops.ACT_GDN, nxt)
-                    i += 2
+                    x = m.run_nhwc(x, ops.ACT_IGDN if nxt.inverse else ops.ACT_GDN, nxt, x_is_cm, out_cm)
                 elif isinstance(nxt, nn.ReLU):
-                    x = m.run_nhwc(x, ops.ACT_RELU)
-                    i += 2
+                    x = m.run_nhwc(x, ops.ACT_RELU, None, x_is_cm, out_cm)
                 else:
-                    x = m.run_nhwc(x)
-                    i += 1
+                    x = m.run_nhwc(x, cm_in=x_is_cm, cm_out=out_cm)
+                i = j
             elif isinstance(m, GDN):
-                assert not x_is_s2d
+                assert not (x_is_s2d or x_is_cm)
                 x = ops.nchw_to_nhwc(m(ops.nhwc_to_nchw(x)))
                 i += 1
             elif isinstance(m, nn.ReLU):
+                assert not x_is_cm
                 x = torch.relu(x)
                 i += 1
             else:  # pragma: no cover
                 raise TypeError(f"unsupported module {type(m).__name__}")
-            x_is_s2d = out_s2d
+            x_is_s2d, x_is_cm = out_s2d, out_cm
             if taps is not None:
-                taps.append(ops.depth_to_space(x) if x_is_s2d else x)
-        assert not x_is_s2d
+                taps.append(self._tap(x, x_is_s2d, x_is_cm))
+        assert not (x_is_s2d or x_is_cm)
         return x
 
     @torch.no_grad()

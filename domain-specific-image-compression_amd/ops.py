@@ -217,27 +217,33 @@ def wino_bf16_planes() -> int:
     return int(_lib.load().dsic_wino_bf16_planes())
 
 
-def conv_transpose2d_wino_nhwc(x, u_packed4, bias, Cout, act=ACT_NONE, beta=None, gamma=None, out=None):
+def conv_transpose2d_wino_nhwc(x, u_packed4, bias, Cout, act=ACT_NONE, beta=None, gamma=None, out=None,
+                               cm_in=False, cm_out=False):
     """ConvTranspose2d(Cin,Cout,5,2,2,1) + fused activation: four Winograd 3x3 phase convs.
     u_packed4: fp32 transformed weights (fp32 MFMA kernel) or the uint8 bf16 planes of
-    split_wino_weight_bf16 (split-bf16 kernel)."""
+    split_wino_weight_bf16 (split-bf16 kernel).  cm_in / cm_out: the input / output is chunk-major
+    [B,C/16,H,W,16] (nhwc_to_cm16; layers of the 64-tile kernel only)."""
     x = _f32c(x, "conv_transpose2d_wino_nhwc")
-    B, H, W, Cin = x.shape
+    B, H, W, Cin = cm16_shape(x) if cm_in else x.shape
     if out is None:
-        out = torch.empty((B, 2 * H, 2 * W, Cout), dtype=torch.float32, device=x.device)
+        out = torch.empty(_act_shape(B, 2 * H, 2 * W, Cout, cm_out), dtype=torch.float32, device=x.device)
     L = _lib.load()
     wino_tiles = 4 * B * (-(-H // 8)) * (-(-W // 16)) * 32
     if u_packed4.dtype == torch.uint8:
         nprod = 3 if wino_bf16_planes() == 2 else 6
         # large layers run on the 64-tile two-pass kernel (conv_wino_bf16m.hip): the symbol the profiler will show
         m64 = bool(L.dsic_wino_bf16_m64(H, W, Cin, 4))
+        lay_in, lay_out = LAYOUT_CM16 if cm_in else 0, LAYOUT_CM16 if cm_out else 0
         _timed("conv_wino_bf16m_kernel<2>" if m64 else "conv_wino_bf16_kernel<2>", 2.0 * B * H * W * Cout * Cin * 25,
-               lambda: _lib.check(L.dsic_conv_transpose2d_wino_bf16_nhwc(_p(x), _p(u_packed4), _p(bias), _p(beta),
-                                                                         _p(gamma), _p(out), B, H, W, Cin, Cout, act,
-                                                                         _p(_ticket(x.device)), _stream()),
-                                  "conv_transpose2d_wino_bf16_nhwc"),
+               lambda: _lib.check(L.dsic_conv_transpose2d_wino_bf16_layout(_p(x), _p(u_packed4), _p(bias), _p(beta),
+                                                                           _p(gamma), _p(out), B, H, W, Cin, Cout, act,
+                                                                           lay_in, lay_out, _p(_ticket(x.device)),
+                                                                           _stream()),
+                                  "conv_transpose2d_wino_bf16_layout"),
                exec_flops=2.0 * nprod * wino_tiles * 12.25 * Cin * round_up(Cout, 32))
         return out
+    if cm_in or cm_out:
+        raise ValueError("conv_transpose2d_wino_nhwc: chunk-major activations need the split-bf16 kernel")
     _timed("conv_wino_kernel<2>", 2.0 * B * H * W * Cout * Cin * 25,
            lambda: _lib.check(L.dsic_conv_transpose2d_wino_nhwc(_p(x), _p(u_packed4), _p(bias), _p(beta), _p(gamma),
                                                                 _p(out), B, H, W, Cin, Cout, act, _p(_ticket(x.device)),
@@ -259,22 +265,53 @@ def depth_to_space(x_s2d):
     return x_s2d.view(B, H2, W2, 2, 2, C).permute(0, 1, 3, 2, 4, 5).reshape(B, 2 * H2, 2 * W2, C).contiguous()
 
 
+# Chunk-major activations (CM16, DSIC_LAYOUT_CM16 in include/dsic_hip.h): [B][C/16][H][W][16] fp32, the channel axis
+# of the NHWC tensor cut into 16-channel chunks, each a contiguous plane.  Written by a producer whose consumer runs
+# on the 64-tile Winograd kernel (layers._Chain decides); these conversions are layout plumbing for taps and tests.
+LAYOUT_CM16 = 2
+
+
+def cm16_shape(x_cm):
+    """(B, H, W, C) of a chunk-major tensor."""
+    B, CC, H, W, K = x_cm.shape
+    assert K == 16, tuple(x_cm.shape)
+    return B, H, W, 16 * CC
+
+
+def _act_shape(B, H, W, C, cm):
+    return (B, C // 16, H, W, 16) if cm else (B, H, W, C)
+
+
+def cm16_to_nhwc(x_cm):
+    B, H, W, C = cm16_shape(x_cm)
+    return x_cm.permute(0, 2, 3, 1, 4).reshape(B, H, W, C).contiguous()
+
+
+def nhwc_to_cm16(x_nhwc):
+    B, H, W, C = x_nhwc.shape
+    return x_nhwc.view(B, H, W, C // 16, 16).permute(0, 3, 1, 2, 4).contiguous()
+
+
 def conv3x3_wino_nhwc(x, u_packed, bias, Cout, act=ACT_NONE, beta=None, gamma=None, out=None, s2d_out=False,
-                      algo_flops=None, s2d_in=False, out_coff=0, split_k=True):
+                      algo_flops=None, s2d_in=False, out_coff=0, split_k=True, cm_in=False, cm_out=False):
     """conv(Cin,Cout,3,1) + fused activation by Winograd F(2x2,3x3) on NHWC activations.
 
-    s2d_out: write [B,H/2,W/2,4*Cout] (space-to-depth) for a following 5x5/s2 layer."""
+    s2d_out: write [B,H/2,W/2,4*Cout] (space-to-depth) for a following 5x5/s2 layer.
+    cm_in / cm_out: the input / output is chunk-major [B,C/16,H,W,16] (layers of the 64-tile kernel only)."""
     x = _f32c(x, "conv3x3_wino_nhwc")
-    B, H, W, Cin = x.shape
+    B, H, W, Cin = cm16_shape(x) if cm_in else x.shape
     if out is None:
-        shape = (B, H // 2, W // 2, 4 * Cout) if s2d_out else (B, H, W, Cout)
+        shape = _act_shape(B, H // 2, W // 2, 4 * Cout, cm_out) if s2d_out else _act_shape(B, H, W, Cout, cm_out)
         out = torch.empty(shape, dtype=torch.float32, device=x.device)
     L = _lib.load()
     wino_tiles = B * (-(-H // 8)) * (-(-W // 16)) * 32          # 2x2-output tiles incl. border padding
+    if (cm_in or cm_out) and u_packed.dtype != torch.uint8:
+        raise ValueError("conv3x3_wino_nhwc: chunk-major activations need the split-bf16 kernel")
+    lay_in, lay_out = LAYOUT_CM16 if cm_in else 0, LAYOUT_CM16 if cm_out else 0
     if u_packed.dtype == torch.uint8:                            # bf16 planes: split-bf16 kernel
         nprod = 3 if wino_bf16_planes() == 2 else 6
         ksplit = L.dsic_wino_bf16_ksplit(H, W, Cin) if (WINO_SPLITK and split_k) else 1
-        if ksplit > 1:
+        if ksplit > 1 and not (cm_in or cm_out):
             # few tiles per image: the input channels of a tile are shared by `ksplit` work items
             partials = torch.empty((ksplit,) + tuple(out.shape), dtype=torch.float32, device=x.device)
             _timed("conv_wino_bf16_kernel<1>" if s2d_in else "conv_wino_bf16_kernel<0>",
@@ -289,9 +326,10 @@ def conv3x3_wino_nhwc(x, u_packed, bias, Cout, act=ACT_NONE, beta=None, gamma=No
         _timed(f"conv_wino_bf16{m64}_kernel<1>" if s2d_in else f"conv_wino_bf16{m64}_kernel<0>",
                algo_flops if algo_flops is not None else 2.0 * B * H * W * Cout * Cin * 9,
                lambda: _lib.check(L.dsic_conv3x3_wino_bf16_nhwc(_p(x), _p(u_packed), _p(bias), _p(beta), _p(gamma),
-                                                                _p(out), B, H, W, Cin, Cout, act, int(bool(s2d_out)),
-                                                                int(bool(s2d_in)),
-                                                                0 if s2d_out else int(out.shape[-1]), int(out_coff),
+                                                                _p(out), B, H, W, Cin, Cout, act,
+                                                                int(bool(s2d_out)) | lay_out, int(bool(s2d_in)) | lay_in,
+                                                                0 if (s2d_out or cm_out) else int(out.shape[-1]),
+                                                                int(out_coff),
                                                                 _p(_ticket(x.device)), _stream()),
                                   "conv3x3_wino_bf16_nhwc"),
                exec_flops=2.0 * nprod * wino_tiles * (12.25 if s2d_in else 16) * Cin * round_up(Cout, 32))
@@ -317,33 +355,34 @@ def to_tensor_u8(x_u8_nhwc: torch.Tensor) -> torch.Tensor:
     return out
 
 
-def conv_first_nchw(x, w, bias, act=ACT_NONE, beta=None, gamma=None, s2d_out=False):
+def conv_first_nchw(x, w, bias, act=ACT_NONE, beta=None, gamma=None, s2d_out=False, cm_out=False):
     """conv(Cimg,Cout,3,1) + fused activation from the image to NHWC (layers.py:51).
     x: float32 NCHW in [0,1] (the reference's tensor contract), or uint8 NHWC image bytes
-    (to_tensor fused into the kernel)."""
+    (to_tensor fused into the kernel).  cm_out: write the output chunk-major [B,C/16,H',W',16]."""
     w = _f32c(w, "conv_first_nchw")
     Cout = w.shape[0]
+    flag = int(bool(s2d_out)) | (LAYOUT_CM16 if cm_out else 0)
     if x.dtype == torch.uint8:
         if not x.is_cuda:
             raise RuntimeError(f"conv_first_nchw: expected a tensor on the GPU (no CPU fallback), got {x.device}")
         x = x.contiguous()
         B, H, W, C = x.shape
-        shape = (B, H // 2, W // 2, 4 * Cout) if s2d_out else (B, H, W, Cout)
+        shape = _act_shape(B, H // 2, W // 2, 4 * Cout, cm_out) if s2d_out else _act_shape(B, H, W, Cout, cm_out)
         out = torch.empty(shape, dtype=torch.float32, device=x.device)
         L = _lib.load()
         _timed(f"conv_first_kernel<{C}>", 2.0 * B * H * W * Cout * C * 9,
                lambda: _lib.check(L.dsic_conv_first_u8hwc(_p(x), _p(w), _p(bias), _p(beta), _p(gamma), _p(out), B, C,
-                                                          H, W, Cout, act, int(bool(s2d_out)), _stream()),
+                                                          H, W, Cout, act, flag, _stream()),
                                   "conv_first_u8hwc"))
         return out
     x = _f32c(x, "conv_first_nchw")
     B, C, H, W = x.shape
-    shape = (B, H // 2, W // 2, 4 * Cout) if s2d_out else (B, H, W, Cout)
+    shape = _act_shape(B, H // 2, W // 2, 4 * Cout, cm_out) if s2d_out else _act_shape(B, H, W, Cout, cm_out)
     out = torch.empty(shape, dtype=torch.float32, device=x.device)
     L = _lib.load()
     _timed(f"conv_first_kernel<{C}>", 2.0 * B * H * W * Cout * C * 9,
            lambda: _lib.check(L.dsic_conv_first_nchw(_p(x), _p(w), _p(bias), _p(beta), _p(gamma), _p(out), B, C,
-                                                     H, W, Cout, act, int(bool(s2d_out)), _stream()),
+                                                     H, W, Cout, act, flag, _stream()),
                               "conv_first_nchw"))
     return out
 

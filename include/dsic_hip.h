@@ -36,6 +36,12 @@ extern "C" {
 #define DSIC_ACT_GDN 1   /* x / sqrt(beta + gamma*x^2)   layers.py:19-27 */
 #define DSIC_ACT_IGDN 2  /* x * sqrt(beta + gamma*x^2)   layers.py:24-25 */
 #define DSIC_ACT_RELU 3  /* nn.ReLU                      layers.py:108-111 */
+/* Activation layout flag, OR-ed into the s2d_in / s2d_out arguments of dsic_conv3x3_wino_bf16_nhwc and the s2d
+ * argument of dsic_conv_first_*: the tensor is chunk-major (CM16) [B][C/16][H][W][16] fp32 instead of NHWC, on the
+ * same channel axis (C = 4*Cs in the space-to-depth order for a space-to-depth map).  A 16-channel chunk's window row
+ * is then contiguous.  Only layers that dsic_wino_bf16_m64 assigns to the 64-tile kernel read or write it (anything
+ * else returns DSIC_EINVAL); Cout a multiple of 16 on the output side. */
+#define DSIC_LAYOUT_CM16 2
 
 const char* dsic_last_error(void);
 int dsic_abi_version(void);
@@ -188,12 +194,20 @@ int dsic_conv_transpose2d_wino_bf16_nhwc(const float* in, const void* u_planes4,
                                          const float* gamma, float* out, int B,
                                          int H, int W, int Cin, int Cout, int act,
                                          void* ticket, void* stream);
+/* The same with the input / output layout chosen: layout_in, layout_out 0 (NHWC) or DSIC_LAYOUT_CM16. */
+int dsic_conv_transpose2d_wino_bf16_layout(const float* in, const void* u_planes4,
+                                           const float* bias, const float* beta,
+                                           const float* gamma, float* out, int B,
+                                           int H, int W, int Cin, int Cout, int act,
+                                           int layout_in, int layout_out, void* ticket,
+                                           void* stream);
 
 /* First analysis layer conv(Cimg,Cout,3,1) + optional GDN/ReLU (layers.py:51)
  * read straight from the NCHW image [B,Cimg,H,W] (Cimg 3 or 4) with K = 9*Cimg;
  * w_oihw is the reference weight [Cout,Cimg,3,3] unpacked; out NHWC [B,H,W,Cout],
  * Cout a multiple of 4, <= 128.  s2d_out: store space-to-depth
- * [B,H/2,W/2,4*Cout] for a following 5x5/s2 layer run by Winograd. */
+ * [B,H/2,W/2,4*Cout] for a following 5x5/s2 layer run by Winograd; | DSIC_LAYOUT_CM16: store
+ * chunk-major [B,C/16,H',W',16] (Cout a multiple of 16). */
 int dsic_conv_first_nchw(const float* x_nchw, const float* w_oihw,
                          const float* bias, const float* beta,
                          const float* gamma, float* out_nhwc, int B, int Cimg,

@@ -1,30 +1,35 @@
 #!/usr/bin/env python3
 """Reads the in-kernel cycle stamps of a -DWBM_STAMP=1 build of conv_wino_bf16m.hip (diagnostic; third tile of every
-workgroup, medians over workgroups).  LAYER=3x3 (default, 8 chunks per pass) | s2 (32) | convT (8)."""
+workgroup, medians over workgroups).  LAYER=3x3 (default, 8 chunks per pass) | s2 (32) | convT (8).  CM=1: the
+input and the output chunk-major (ops.LAYOUT_CM16) instead of NHWC.  DSIC_LIB_ROOT: the repository tree whose package
+(and library) to load."""
 import ctypes, os, sys
-sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+sys.path.insert(0, os.environ.get("DSIC_LIB_ROOT") or os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np, torch
 from dsic_amd import ops, lib
 B, h = 64, 128
 layer = os.environ.get("LAYER", "3x3")
+cm = os.environ.get("CM", "0") == "1"
+kw = dict(cm_in=True, cm_out=True) if cm else {}
+cmx = (lambda t: ops.nhwc_to_cm16(t)) if cm else (lambda t: t)
 bias = torch.randn(128, device="cuda"); beta = torch.rand(128, device="cuda") + 0.5; gamma = torch.rand(128, device="cuda") * 0.2
 if layer == "s2":
-    x = torch.randn(B, h, h, 512, device="cuda")
+    x = cmx(torch.randn(B, h, h, 512, device="cuda"))
     w = ops.split_wino_weight_bf16(ops.pack_wino_s2_weight(torch.randn(128, 128, 5, 5, device="cuda") * 0.05), 128, 512)
-    n = 32; run = lambda: ops.conv3x3_wino_nhwc(x, w, bias, 128, ops.ACT_GDN, beta, gamma, s2d_in=True)
+    n = 32; run = lambda: ops.conv3x3_wino_nhwc(x, w, bias, 128, ops.ACT_GDN, beta, gamma, s2d_in=True, **kw)
 elif layer == "convT":
-    x = torch.randn(B, h // 2, h // 2, 128, device="cuda")
+    x = cmx(torch.randn(B, h // 2, h // 2, 128, device="cuda"))
     w = ops.split_wino_weight_bf16(ops.pack_wino_convT_weight(torch.randn(128, 128, 5, 5, device="cuda") * 0.05), 128, 128, 4)
-    n = 8; run = lambda: ops.conv_transpose2d_wino_nhwc(x, w, bias, 128, ops.ACT_IGDN, beta, gamma)
+    n = 8; run = lambda: ops.conv_transpose2d_wino_nhwc(x, w, bias, 128, ops.ACT_IGDN, beta, gamma, **kw)
 else:
-    x = torch.randn(B, h, h, 128, device="cuda")
+    x = cmx(torch.randn(B, h, h, 128, device="cuda"))
     w = ops.split_wino_weight_bf16(ops.pack_wino_weight(torch.randn(128, 128, 3, 3, device="cuda") * 0.05), 128, 128)
-    n = 8; run = lambda: ops.conv3x3_wino_nhwc(x, w, bias, 128, ops.ACT_GDN, beta, gamma)
+    n = 8; run = lambda: ops.conv3x3_wino_nhwc(x, w, bias, 128, ops.ACT_GDN, beta, gamma, **kw)
 for _ in range(3): run()
 torch.cuda.synchronize()
 e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
 e0.record(); run(); e1.record(); torch.cuda.synchronize()
-print(layer, "kernel ms", e0.elapsed_time(e1))
+print(layer, "CM16" if cm else "NHWC", "kernel ms", e0.elapsed_time(e1))
 L = lib.load()
 buf = np.zeros(256 * 256, dtype=np.int64)
 L.dsic_debug_wbm_stamps.restype = ctypes.c_int
