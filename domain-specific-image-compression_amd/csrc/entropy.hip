@@ -441,6 +441,277 @@ __global__ __launch_bounds__(1024) void range_encode_kernel(
   if (lane == 0) lengths[2 * b + which] = (int)((total_bits + 7) >> 3);
 }
 
+// ---- split encoder: pack -> chain -> place (dsic_range_encode_ws) -----------------------------------
+// The same coder in three launches on the coder's stream, so that the only long-running one is a wave small
+// enough to share a CU with a persistent conv workgroup (3 x 168 of a SIMD's 512 VGPRs leave 8).
+//  pack  (whole chip, short): every symbol's (c_low, c_high-1) pair, error bits 1 and 2.
+//  chain (one wave per string, <= 8 VGPRs, no LDS): enc_step on scalar registers, 64 pairs per global load
+//        (two groups ahead); per symbol the interval before renormalisation (low1, high1) leaves through two
+//        vector stores per 64 symbols; the final low per string.
+//  place (one workgroup per string): per symbol the E1/E2 bits and the E3 run from (low1, high1), the pending
+//        counts as a scan over the whole string, the bit offsets as a prefix sum, then the same put_bits calls,
+//        flush, lengths and error bit 4 as range_encode_kernel.
+// Workspace: pairs, rec_low, rec_high [B (M HWy + N HWz)] uint32, then final low [2B]; string s < B is y string
+// s at symbol s * ny, string B + b the z string b at B ny + b nz.
+struct SplitGeom {
+  int B, M, HWy, N, HWz, Lmax, per_element_y;
+  int64_t ny, nz;
+  __device__ __forceinline__ void stream(int s, int& which, int& b, int64_t& n, int64_t& base) const {
+    which = s < B ? 1 : 0;
+    b = which ? s : s - B;
+    n = which ? ny : nz;
+    base = which ? (int64_t)b * ny : (int64_t)B * ny + (int64_t)b * nz;
+  }
+};
+
+__global__ __launch_bounds__(256) void enc_pack_kernel(const float* __restrict__ y, const float* __restrict__ z,
+                                                       const int* __restrict__ meta, const uint16_t* __restrict__ tab_y,
+                                                       const uint16_t* __restrict__ tab_z, SplitGeom G,
+                                                       uint32_t* __restrict__ pairs, int* __restrict__ err) {
+  int which, b;
+  int64_t n, base;
+  G.stream(blockIdx.y, which, b, n, base);
+  const int HW = which ? G.HWy : G.HWz, Lmax = G.Lmax;
+  const bool per_element = which && G.per_element_y;
+  const float* sym = which ? y + (size_t)b * n : z + (size_t)b * n;
+  const uint16_t* tab = (which ? tab_y + (size_t)b * (per_element ? (size_t)G.M * G.HWy : (size_t)G.M) * Lmax
+                               : tab_z + (size_t)b * G.N * Lmax);
+  const int smin = meta[4 * b + (which ? 0 : 2)], L = meta[4 * b + (which ? 1 : 3)];
+  if (L > Lmax || L < 1) return;   // place_kernel reports it
+  for (int64_t g = (int64_t)blockIdx.x * 256 + threadIdx.x; g < n; g += (int64_t)gridDim.x * 256) {
+    const int c = (int)(g / HW);
+    int sc = (int)sym[g] - smin;
+    if (sc < 0 || sc >= L) {
+      atomicOr(err, 2);
+      sc = 0;
+    }
+    const uint16_t* t = tab + (size_t)(per_element ? g : (int64_t)c) * Lmax;
+    const uint32_t c_low = t[sc];
+    const uint32_t c_high = (sc == L - 1) ? 0x10000u : (uint32_t)t[sc + 1];
+    pairs[base + g] = c_low | ((c_high - 1u) << 16);
+  }
+}
+
+// enc_step with the bounds taken from the packed pair by scalar ops: cl = c_low << 16, ch = c_high << 16, which is
+// 0 for c_high = 65536; then hi_add = floor(span 2^16 / 2^16) = span (mod 2^32, as the general path's 64-bit product).
+template <int J>
+__device__ __forceinline__ void chain_step(uint32_t& low, uint32_t& lowm1, uint32_t& span, uint32_t& cl, uint32_t& ch,
+                                           uint32_t pv, uint32_t& rec_low, uint32_t& rec_high) {
+  const uint32_t pn = J < 63 ? rlane<(J < 63 ? J + 1 : 63)>(pv) : 0u;
+  const uint32_t ml = __umulhi(span, cl), mh = __umulhi(span, ch);
+  const uint32_t lo_add = span ? ml : cl;
+  const uint32_t hi_add = ch ? (span ? mh : ch) : span;
+  const uint32_t low1 = low + lo_add;
+  const uint32_t high1 = lowm1 + hi_add;
+  const uint32_t span1 = hi_add - lo_add;
+  wlane<J>(rec_low, low1);
+  wlane<J>(rec_high, high1);
+  const int nb = __builtin_clz(low1 ^ high1);
+  const uint32_t q2 = (high1 | ~low1) << 1;
+  const int m = __builtin_clz(q2 << nb);
+  const int sh = nb + m;
+  span = span1 << sh;
+  low = (low1 << sh) & 0x7FFFFFFFu;
+  lowm1 = low - 1u;
+  cl = pn << 16;
+  ch = (pn & 0xFFFF0000u) + 0x10000u;
+}
+
+template <int J0>
+__device__ __forceinline__ void chain_steps8(uint32_t& low, uint32_t& lowm1, uint32_t& span, uint32_t& cl,
+                                             uint32_t& ch, uint32_t pv, uint32_t& rl, uint32_t& rh) {
+  chain_step<J0 + 0>(low, lowm1, span, cl, ch, pv, rl, rh);
+  chain_step<J0 + 1>(low, lowm1, span, cl, ch, pv, rl, rh);
+  chain_step<J0 + 2>(low, lowm1, span, cl, ch, pv, rl, rh);
+  chain_step<J0 + 3>(low, lowm1, span, cl, ch, pv, rl, rh);
+  chain_step<J0 + 4>(low, lowm1, span, cl, ch, pv, rl, rh);
+  chain_step<J0 + 5>(low, lowm1, span, cl, ch, pv, rl, rh);
+  chain_step<J0 + 6>(low, lowm1, span, cl, ch, pv, rl, rh);
+  chain_step<J0 + 7>(low, lowm1, span, cl, ch, pv, rl, rh);
+}
+
+__global__ __launch_bounds__(64) __attribute__((amdgpu_num_vgpr(8))) void enc_chain_kernel(
+    const uint32_t* __restrict__ pairs, const int* __restrict__ meta, SplitGeom G, uint32_t* __restrict__ rec_low,
+    uint32_t* __restrict__ rec_high, uint32_t* __restrict__ final_low) {
+  const int s = blockIdx.x;
+  int which, b;
+  int64_t n, base;
+  G.stream(s, which, b, n, base);
+  const int L = meta[4 * b + (which ? 1 : 3)];
+  if (L > G.Lmax || L < 1) return;
+  // Buffer accesses: the string's base and size in an SGPR resource, one lane-offset VGPR, the group in the scalar
+  // offset.  Past the string end (n * 4 bytes, < 2 GiB: checked by the host) loads return 0 and stores are dropped.
+  const uint32_t voff = threadIdx.x * 4u;
+  const uint32_t nbytes = (uint32_t)n * 4u;
+  const __amdgpu_buffer_rsrc_t rp = __builtin_amdgcn_make_buffer_rsrc((void*)(pairs + base), 0, nbytes, 0x00020000);
+  const __amdgpu_buffer_rsrc_t rlo = __builtin_amdgcn_make_buffer_rsrc((void*)(rec_low + base), 0, nbytes, 0x00020000);
+  const __amdgpu_buffer_rsrc_t rhi = __builtin_amdgcn_make_buffer_rsrc((void*)(rec_high + base), 0, nbytes, 0x00020000);
+  auto ld = [&](uint32_t g) -> uint32_t { return __builtin_amdgcn_raw_buffer_load_b32(rp, voff, g * 4u, 0); };
+  uint32_t low = 0, span = 0, lowm1 = 0xFFFFFFFFu;   // span 0 = 2^32
+  uint32_t cur = ld(0), n1 = ld(64);
+  const uint32_t nfull = (uint32_t)n & ~63u;   // 32-bit scalar loop counter (n < 2^29)
+  uint32_t g = 0;
+  for (; g < nfull; g += 64) {
+    const uint32_t n2 = ld(g + 128);
+    uint32_t rl = 0, rh = 0;
+    const uint32_t p0 = rlane<0>(cur);
+    uint32_t cl = p0 << 16, ch = (p0 & 0xFFFF0000u) + 0x10000u;
+    chain_steps8<0>(low, lowm1, span, cl, ch, cur, rl, rh);
+    chain_steps8<8>(low, lowm1, span, cl, ch, cur, rl, rh);
+    chain_steps8<16>(low, lowm1, span, cl, ch, cur, rl, rh);
+    chain_steps8<24>(low, lowm1, span, cl, ch, cur, rl, rh);
+    chain_steps8<32>(low, lowm1, span, cl, ch, cur, rl, rh);
+    chain_steps8<40>(low, lowm1, span, cl, ch, cur, rl, rh);
+    chain_steps8<48>(low, lowm1, span, cl, ch, cur, rl, rh);
+    chain_steps8<56>(low, lowm1, span, cl, ch, cur, rl, rh);
+    __builtin_amdgcn_raw_buffer_store_b32(rl, rlo, voff, g * 4u, 0);
+    __builtin_amdgcn_raw_buffer_store_b32(rh, rhi, voff, g * 4u, 0);
+    cur = n1;
+    n1 = n2;
+  }
+  const int cnt = (int)((uint32_t)n - g);   // 0..63 symbols left
+  if (cnt > 0) {
+    uint32_t rl = 0, rh = 0;
+    for (int j = 0; j < cnt; ++j) {
+      const uint32_t pr = __builtin_amdgcn_readlane(cur, j);
+      const uint32_t cl = pr << 16, ch = (pr & 0xFFFF0000u) + 0x10000u;
+      const uint32_t lo_add = span ? __umulhi(span, cl) : cl;
+      const uint32_t hi_add = ch ? (span ? __umulhi(span, ch) : ch) : span;
+      const uint32_t low1 = low + lo_add, high1 = lowm1 + hi_add, span1 = hi_add - lo_add;
+      // lane select through M0, 4 wait states after the SALU write (see range_encode_kernel)
+      asm volatile("s_mov_b32 m0, %4\n\ts_nop 3\n\tv_writelane_b32 %0, %2, m0\n\tv_writelane_b32 %1, %3, m0"
+                   : "+v"(rl), "+v"(rh)
+                   : "s"(low1), "s"(high1), "s"(j));
+      const int nb = __builtin_clz(low1 ^ high1);
+      const int m = __builtin_clz(((high1 | ~low1) << 1) << nb);
+      const int sh = nb + m;
+      span = span1 << sh;
+      low = (low1 << sh) & 0x7FFFFFFFu;
+      lowm1 = low - 1u;
+    }
+    __builtin_amdgcn_raw_buffer_store_b32(rl, rlo, voff, g * 4u, 0);   // lanes >= cnt: out of range
+    __builtin_amdgcn_raw_buffer_store_b32(rh, rhi, voff, g * 4u, 0);
+  }
+  if (threadIdx.x == 0) final_low[s] = low;
+}
+
+constexpr int PLACE_THREADS = 1024;
+
+// Carry of the pending count across a slice of symbols: c -> (a ? c : 0) + t.  Composition (a1, t1) then (a2, t2)
+// = (a1 & a2, (a2 ? t1 : 0) + t2).
+__global__ __launch_bounds__(PLACE_THREADS) void enc_place_kernel(const int* __restrict__ meta, SplitGeom G,
+                                                                  const uint32_t* __restrict__ rec_low,
+                                                                  const uint32_t* __restrict__ rec_high,
+                                                                  const uint32_t* __restrict__ final_low,
+                                                                  uint8_t* __restrict__ out, int64_t cap_y,
+                                                                  int64_t cap_z, int* __restrict__ lengths,
+                                                                  int* __restrict__ err) {
+  __shared__ uint32_t sc_a[PLACE_THREADS], sc_t[PLACE_THREADS];
+  __shared__ uint64_t sc_l[PLACE_THREADS];
+  const int s = blockIdx.x, tid = threadIdx.x;
+  int which, b;
+  int64_t n, base;
+  G.stream(s, which, b, n, base);
+  const int L = meta[4 * b + (which ? 1 : 3)];
+  if (L > G.Lmax || L < 1) {
+    if (tid == 0) {
+      atomicOr(err, 1);
+      lengths[2 * b + which] = 0;
+    }
+    return;
+  }
+  const int64_t stride = cap_z + cap_y;
+  uint32_t* dst32 = (uint32_t*)(out + (size_t)b * stride + (which ? cap_z : 0));
+  const int64_t cap_bits = (which ? cap_y : cap_z) * 8;
+  const uint32_t* rlo = rec_low + base;
+  const uint32_t* rhi = rec_high + base;
+  const int64_t per = (n + PLACE_THREADS - 1) / PLACE_THREADS;
+  const int64_t j0 = (int64_t)tid * per < n ? (int64_t)tid * per : n;
+  const int64_t j1 = j0 + per < n ? j0 + per : n;
+
+  // pass 1: the slice's carry map and its bit count without the carry
+  uint32_t t = 0, head = 0;
+  uint64_t len = 0;
+  for (int64_t j = j0; j < j1; ++j) {
+    const uint32_t lo = rlo[j], hi = rhi[j];
+    const uint32_t nb = (uint32_t)__builtin_clz(lo ^ hi);
+    const uint32_t m = (uint32_t)__builtin_clz((((hi | ~lo) << nb) << 1) | 1u);
+    if (nb) {   // owed in front of it: the runs since the last head (the first head: + the carry-in, added below)
+      len += nb + t;
+      head = 1;
+      t = 0;
+    }
+    t += m;
+  }
+  // exclusive scan of the carry maps: pending count owed at the slice start (0 at the string start)
+  sc_a[tid] = head ? 0u : 1u;
+  sc_t[tid] = t;
+  __syncthreads();
+  for (int o = 1; o < PLACE_THREADS; o <<= 1) {
+    uint32_t pa = 1, pt = 0;
+    if (tid >= o) {
+      pa = sc_a[tid - o];
+      pt = sc_t[tid - o];
+    }
+    __syncthreads();
+    if (tid >= o) {   // (pa, pt) then (a, t)
+      const uint32_t a = sc_a[tid];
+      sc_t[tid] = (a ? pt : 0u) + sc_t[tid];
+      sc_a[tid] = pa & a;
+    }
+    __syncthreads();
+  }
+  const uint32_t carry_in = tid ? sc_t[tid - 1] : 0u;   // maps applied to 0: a does not matter
+  const uint32_t pend_final = sc_t[PLACE_THREADS - 1];
+  const uint64_t mylen = len + (head ? (uint64_t)carry_in : 0u);
+  __syncthreads();
+  sc_l[tid] = mylen;
+  __syncthreads();
+  for (int o = 1; o < PLACE_THREADS; o <<= 1) {
+    const uint64_t v = tid >= o ? sc_l[tid - o] : 0u;
+    __syncthreads();
+    sc_l[tid] += v;
+    __syncthreads();
+  }
+  const int64_t total = (int64_t)sc_l[PLACE_THREADS - 1];
+  int64_t off = (int64_t)(sc_l[tid] - mylen);
+
+  // pass 2: the same pieces range_encode_kernel writes, at the same offsets
+  int overflow = 0;
+  uint32_t pend = carry_in;
+  for (int64_t j = j0; j < j1; ++j) {
+    const uint32_t lo = rlo[j], hi = rhi[j];
+    const uint32_t nbv = (uint32_t)__builtin_clz(lo ^ hi);
+    const uint32_t m = (uint32_t)__builtin_clz((((hi | ~lo) << nbv) << 1) | 1u);
+    if (nbv) {
+      const uint32_t bitsv = lo >> (32u - nbv);
+      const uint32_t pendv = pend;
+      if (pendv == 0) {
+        put_bits(dst32, cap_bits, off, bitsv, (int)nbv, &overflow);
+      } else {
+        const uint32_t first = bitsv >> (nbv - 1);
+        put_bits(dst32, cap_bits, off, first, 1, &overflow);
+        if (!first) put_ones(dst32, cap_bits, off + 1, pendv, &overflow);
+        else if (off + 1 + (int64_t)pendv > cap_bits) overflow = 1;
+        if (nbv > 1)
+          put_bits(dst32, cap_bits, off + 1 + pendv, bitsv & ((1u << (nbv - 1)) - 1u), (int)nbv - 1, &overflow);
+      }
+      off += nbv + pendv;
+      pend = 0;
+    }
+    pend += m;
+  }
+  if (tid == 0) {   // flush (torchac): one more pending bit, then the deciding bit and the pending run
+    const uint32_t pending = pend_final + 1u;
+    const uint32_t bit = final_low[s] < 0x40000000u ? 0u : 1u;
+    put_bits(dst32, cap_bits, total, bit, 1, &overflow);
+    if (!bit) put_ones(dst32, cap_bits, total + 1, pending, &overflow);
+    else if (total + 1 + (int64_t)pending > cap_bits) overflow = 1;
+    lengths[2 * b + which] = (int)((total + 1 + (int64_t)pending + 7) >> 3);
+  }
+  if (overflow) atomicOr(err, 4);
+}
+
 // Range decoder, one wave per stream (torchac decode_float_cdf, call sites :96,116).
 //
 // The reference computes count = ((value-low+1)*2^16 - 1) / span and searches the table for
@@ -717,6 +988,51 @@ extern "C" int dsic_range_encode(const float* y_nchw, const float* z_nchw, const
                      y_nchw, z_nchw, meta, tab_y, tab_z, Lmax, M, HWy, N, HWz, out, cap_y, cap_z, lengths,
                      err, 2 * B, per_element_y ? 1 : 0);
   return check_launch("range_encode");
+}
+
+// Split encoder (pack -> chain -> place): the same bytes, lengths and error bits as dsic_range_encode.
+extern "C" int64_t dsic_range_encode_workspace_size(int B, int M, int HWy, int N, int HWz) {
+  if (B <= 0 || M <= 0 || HWy <= 0 || N <= 0 || HWz <= 0) return -1;
+  const int64_t total = (int64_t)B * ((int64_t)M * HWy + (int64_t)N * HWz);
+  return 12 * total + 8 * (int64_t)B;   // pairs, rec_low, rec_high: 4 B per symbol each; final low per string
+}
+
+extern "C" int dsic_range_encode_ws(const float* y_nchw, const float* z_nchw, const int* meta,
+                                    const uint16_t* tab_y, const uint16_t* tab_z, int Lmax, int B, int M,
+                                    int HWy, int N, int HWz, uint8_t* out, int64_t cap_y, int64_t cap_z,
+                                    int* lengths, int* err, int per_element_y, void* workspace,
+                                    int64_t workspace_bytes, void* stream) {
+  DSIC_REQUIRE(y_nchw && z_nchw && meta && tab_y && tab_z && out && lengths && err && workspace,
+               "range_encode_ws: null pointer");
+  DSIC_REQUIRE(B > 0 && M > 0 && N > 0 && HWy > 0 && HWz > 0, "range_encode_ws: empty latent");
+  DSIC_REQUIRE(cap_y % 4 == 0 && cap_z % 4 == 0 && cap_y >= 8 && cap_z >= 8,
+               "range_encode_ws: capacities must be multiples of 4 and >= 8");
+  DSIC_REQUIRE(workspace_bytes >= dsic_range_encode_workspace_size(B, M, HWy, N, HWz),
+               "range_encode_ws: workspace too small");
+  SplitGeom G;
+  G.B = B; G.M = M; G.HWy = HWy; G.N = N; G.HWz = HWz; G.Lmax = Lmax; G.per_element_y = per_element_y ? 1 : 0;
+  G.ny = (int64_t)M * HWy;
+  G.nz = (int64_t)N * HWz;
+  DSIC_REQUIRE(G.ny < ((int64_t)1 << 29) && G.nz < ((int64_t)1 << 29), "range_encode_ws: string too long");
+  const int64_t total = (int64_t)B * (G.ny + G.nz);
+  uint32_t* pairs = (uint32_t*)workspace;
+  uint32_t* rec_low = pairs + total;
+  uint32_t* rec_high = rec_low + total;
+  uint32_t* final_low = rec_high + total;
+  hipStream_t st = (hipStream_t)stream;
+  const int64_t nmax = G.ny > G.nz ? G.ny : G.nz;
+  const int gx = (int)((nmax + 255) / 256 < 256 ? (nmax + 255) / 256 : 256);
+  hipLaunchKernelGGL(enc_pack_kernel, dim3(gx, 2 * B), dim3(256), 0, st, y_nchw, z_nchw, meta, tab_y, tab_z, G, pairs,
+                     err);
+  int rc = check_launch("range_encode_ws: pack");
+  if (rc != DSIC_OK) return rc;
+  // strings 0..B-1 (the long y strings) first; one wave per workgroup
+  hipLaunchKernelGGL(enc_chain_kernel, dim3(2 * B), dim3(64), 0, st, pairs, meta, G, rec_low, rec_high, final_low);
+  rc = check_launch("range_encode_ws: chain");
+  if (rc != DSIC_OK) return rc;
+  hipLaunchKernelGGL(enc_place_kernel, dim3(2 * B), dim3(PLACE_THREADS), 0, st, meta, G, rec_low, rec_high,
+                     final_low, out, cap_y, cap_z, lengths, err);
+  return check_launch("range_encode_ws: place");
 }
 
 extern "C" int dsic_range_decode(const uint8_t* in, int64_t stride, const int* lengths, int lstride,

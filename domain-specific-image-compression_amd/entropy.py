@@ -10,6 +10,7 @@ interpretation frozen in DESIGN.md "Entropy path".
 from __future__ import annotations
 
 import ctypes
+import os
 
 import numpy as np
 import torch
@@ -19,6 +20,9 @@ from . import ops
 from .ops import _f32c, _p, _stream
 
 DEFAULT_LMAX = 256
+# The range encoder runs as pack -> chain -> place (dsic_range_encode_ws: the serial chain is a wave of 8 VGPRs that
+# shares its CU with a persistent conv workgroup); DSIC_SPLIT_CODER=0 keeps the single kernel (A/B runs).
+SPLIT_CODER = os.environ.get("DSIC_SPLIT_CODER", "1") != "0"
 
 
 class EntropyError(RuntimeError):
@@ -107,13 +111,15 @@ def _cap(n):
 
 
 @torch.no_grad()
-def compress_latents(y_tilde, z_tilde, sigma_y, nu_y, sigma_z, tail=10, Lmax=DEFAULT_LMAX, streams_per_wg=1):
+def compress_latents(y_tilde, z_tilde, sigma_y, nu_y, sigma_z, tail=10, Lmax=DEFAULT_LMAX, streams_per_wg=1,
+                     split=None):
     """Device-resident compress of already computed latents.
 
     y_tilde [B,M,Hy,Wy], z_tilde [B,N,Hz,Wz] integer-valued (quant_mode="round");
     sigma_y/nu_y [B,M]; sigma_z [N].  Returns dict with device tensors:
     bytes uint8 [B, cap_z+cap_y], lengths int32 [B,2] (z,y), meta int32 [B,4],
     cap_z, cap_y, tab_y, tab_z, err.  Nothing synchronises with the host.
+    split: the split encoder (default SPLIT_CODER; streams_per_wg > 1 always uses the single kernel).
     """
     y = _f32c(y_tilde, "compress")
     z = _f32c(z_tilde, "compress")
@@ -127,9 +133,19 @@ def compress_latents(y_tilde, z_tilde, sigma_y, nu_y, sigma_z, tail=10, Lmax=DEF
     # the coder ORs its bits in: zero-filled, as 32-bit words (a byte fill kernel takes 4x the elements)
     out = torch.zeros((B, (cap_z + cap_y) // 4), dtype=torch.int32, device=dev).view(torch.uint8)
     lengths = torch.zeros((B, 2), dtype=torch.int32, device=dev)
-    _lib.check(_lib.load().dsic_range_encode(_p(y), _p(z), _p(meta), _p(tab_y), _p(tab_z), Lmax, B, M, Hy * Wy,
-                                             N, Hz * Wz, _p(out), cap_y, cap_z, _p(lengths), _p(err),
-                                             int(streams_per_wg), int(per_element), _stream()), "range_encode")
+    L = _lib.load()
+    ws = None
+    if (SPLIT_CODER if split is None else split) and int(streams_per_wg) == 1:
+        nbytes = L.dsic_range_encode_workspace_size(B, M, Hy * Wy, N, Hz * Wz)
+        # the caching allocator on the coder's stream: every call in flight has its own
+        ws = torch.empty(((nbytes + 3) // 4,), dtype=torch.int32, device=dev)
+        _lib.check(L.dsic_range_encode_ws(_p(y), _p(z), _p(meta), _p(tab_y), _p(tab_z), Lmax, B, M, Hy * Wy,
+                                          N, Hz * Wz, _p(out), cap_y, cap_z, _p(lengths), _p(err), int(per_element),
+                                          _p(ws), ws.numel() * 4, _stream()), "range_encode_ws")
+    else:
+        _lib.check(L.dsic_range_encode(_p(y), _p(z), _p(meta), _p(tab_y), _p(tab_z), Lmax, B, M, Hy * Wy,
+                                       N, Hz * Wz, _p(out), cap_y, cap_z, _p(lengths), _p(err),
+                                       int(streams_per_wg), int(per_element), _stream()), "range_encode")
     return {"bytes": out, "lengths": lengths, "meta": meta, "cap_z": cap_z, "cap_y": cap_y,
             "tab_y": tab_y, "tab_z": tab_z, "err": err, "shape_y": list(y.shape), "shape_z": list(z.shape)}
 

@@ -367,6 +367,18 @@ int dsic_range_encode(const float* y_nchw, const float* z_nchw, const int* meta,
                       int64_t cap_y, int64_t cap_z, int* lengths, int* err,
                       int streams_per_wg, int per_element_y, void* stream);
 
+/* dsic_range_encode in three launches on `stream` (pack: every symbol's interval; chain: the serial interval
+ * recurrence, one small wave per string; place: bit offsets and bits in parallel).  Same arguments and the same
+ * out, lengths and err, without streams_per_wg; `workspace` is device memory of at least
+ * dsic_range_encode_workspace_size(B, M, HWy, N, HWz) bytes, private to this call until the stream passes it.
+ * The workspace size is -1 for a bad shape. */
+int64_t dsic_range_encode_workspace_size(int B, int M, int HWy, int N, int HWz);
+int dsic_range_encode_ws(const float* y_nchw, const float* z_nchw, const int* meta,
+                         const uint16_t* tab_y, const uint16_t* tab_z, int Lmax,
+                         int B, int M, int HWy, int N, int HWz, uint8_t* out,
+                         int64_t cap_y, int64_t cap_z, int* lengths, int* err,
+                         int per_element_y, void* workspace, int64_t workspace_bytes, void* stream);
+
 /* torchac.decode_float_cdf call sites :96,116: string b starts at
  * in + b*stride and has lengths[b*lstride + loff] bytes; meta_off 0 = y, 2 = z.
  * out: NCHW float latents [B][C][HW] (symbol + min). */
