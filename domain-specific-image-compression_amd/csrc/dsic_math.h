@@ -195,11 +195,16 @@ DM_HD double betainc(double a, double b, double x, double xc) {
   return 1.0 - front * betacf(b, a, xc) / b;
 }
 
-DM_HD double student_t_cdf(double t, double nu) {
+// P(T <= -|t|): a function of t^2 only, so t and -t share it exactly
+DM_HD double student_t_tail(double t, double nu) {
   const double t2 = t * t;
   const double den = nu + t2;
   const double x = nu / den, xc = t2 / den;
-  const double tail = 0.5 * betainc(0.5 * nu, 0.5, x, xc);
+  return 0.5 * betainc(0.5 * nu, 0.5, x, xc);
+}
+
+DM_HD double student_t_cdf(double t, double nu) {
+  const double tail = student_t_tail(t, nu);
   return t > 0 ? 1.0 - tail : tail;
 }
 

@@ -18,6 +18,8 @@
 #include "common.h"
 #include "dsic_math.h"
 
+#include <climits>
+
 namespace dsic {
 
 // meta[b] = {ymin - tail, Ly, zmin - tail, Lz}: :39-41, :52-54 (values are
@@ -115,6 +117,10 @@ __device__ __forceinline__ void finish_table_wave(float* F, int L, uint16_t* out
 }
 
 // One wave per table.  sigma/nu indexed [b*sb + c] (sb = 0 for the image-independent z prior).
+// Student-t: F at the boundaries b and -b comes from one evaluation of the tail, which depends on t^2 only (IEEE
+// division and squaring are sign-symmetric): on a support that straddles 0 the lanes walk the distinct |b| and each
+// writes F at both signs.  The boundary of u = smin + k is float(u) - 0.5f; |b| = float(w) - 0.5f with w = u for
+// u >= 1, w = 1 - u for u <= 0 (exact: a straddling support has |u| <= Lmax + 1).  Elsewhere every k is its own.
 template <bool STUDENT>
 __global__ __launch_bounds__(256) void tables_kernel(const float* __restrict__ sigma,
                                                      const float* __restrict__ nu, int sb,
@@ -135,11 +141,80 @@ __global__ __launch_bounds__(256) void tables_kernel(const float* __restrict__ s
   float* pmf = F + Lmax + 1;
   const float sg = sigma[(size_t)b * sb + c];
   const float nv = STUDENT ? nu[(size_t)b * sb + c] : 0.0f;
-  for (int k = lane; k <= L; k += 64)
-    F[k] = STUDENT ? dm::table_cdf_student(smin, k, sg, nv) : dm::table_cdf_gauss(smin, k, sg);
+  if (STUDENT && smin <= 0 && smin + L >= 1) {
+    const int whi = smin + L > 1 - smin ? smin + L : 1 - smin;   // w = 1 .. whi
+    for (int w = 1 + lane; w <= whi; w += 64) {
+      const double tail = dm::student_t_tail((double)((float)w - 0.5f) / (double)sg, (double)nv);
+      if (w <= smin + L) F[w - smin] = (float)(1.0 - tail);   // u = w
+      if (1 - w >= smin) F[1 - w - smin] = (float)tail;       // u = 1 - w
+    }
+  } else {
+    for (int k = lane; k <= L; k += 64)
+      F[k] = STUDENT ? dm::table_cdf_student(smin, k, sg, nv) : dm::table_cdf_gauss(smin, k, sg);
+  }
   __builtin_amdgcn_s_waitcnt(0xc07f);
   __builtin_amdgcn_wave_barrier();
   finish_table_wave(F, L, tables + ((size_t)b * C + c) * Lmax, pmf, lane);
+}
+
+// z tables: sigma is per channel (the same for every image) and a boundary's value depends on u = smin + k only,
+// so the tables of one channel evaluate the same CDF values for every image.  One workgroup per (channel, ZT_IMGS
+// images): the 256 threads evaluate the channel's CDF once over the union of those images' supports, then each wave
+// finishes the tables of ZT_IMGS / 4 images from their slices of that row.  A union wider than `rowmax` boundaries
+// (supports far apart) evaluates each table's own boundaries, as tables_kernel<false>.
+constexpr int ZT_IMGS = 16;
+
+__global__ __launch_bounds__(256) void gauss_tables_kernel(const float* __restrict__ sigma,
+                                                           const int* __restrict__ meta,
+                                                           uint16_t* __restrict__ tables, int B, int C, int Lmax,
+                                                           int rowmax, int* __restrict__ err) {
+  extern __shared__ float shm[];  // row[rowmax], then per wave F[Lmax+1], pmf[Lmax]
+  __shared__ int ulo, uhi;
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  const int c = blockIdx.x, b0 = blockIdx.y * ZT_IMGS;
+  const int b1 = B - b0 < ZT_IMGS ? B : b0 + ZT_IMGS;
+  const float sg = sigma[c];
+  if (wave == 0) {   // union [lo, hi] of the valid supports' u = smin .. smin + L
+    int lo = INT_MAX, hi = INT_MIN;
+    if (b0 + lane < b1 && lane < ZT_IMGS) {
+      const int smin = meta[4 * (b0 + lane) + 2], L = meta[4 * (b0 + lane) + 3];
+      if (L >= 1 && L <= Lmax) {
+        lo = smin;
+        hi = smin + L;
+      }
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+      lo = min(lo, __shfl_xor(lo, o, 64));
+      hi = max(hi, __shfl_xor(hi, o, 64));
+    }
+    if (lane == 0) {
+      ulo = lo;
+      uhi = hi;
+    }
+  }
+  __syncthreads();
+  const int lo = ulo, hi = uhi;
+  const bool shared_row = hi >= lo && (int64_t)hi - lo < (int64_t)rowmax;
+  float* row = shm;
+  if (shared_row)
+    for (int u = lo + (int)threadIdx.x; u <= hi; u += 256) row[u - lo] = dm::table_cdf_gauss(u, 0, sg);
+  __syncthreads();
+  float* F = shm + rowmax + (size_t)wave * (2 * Lmax + 1);
+  float* pmf = F + Lmax + 1;
+  for (int b = b0 + wave; b < b1; b += 4) {
+    const int smin = meta[4 * b + 2], L = meta[4 * b + 3];
+    if (L > Lmax || L < 1) {
+      if (lane == 0) atomicOr(err, 1);
+      continue;
+    }
+    for (int k = lane; k <= L; k += 64) F[k] = shared_row ? row[smin + k - lo] : dm::table_cdf_gauss(smin, k, sg);
+    __builtin_amdgcn_s_waitcnt(0xc07f);
+    __builtin_amdgcn_wave_barrier();
+    finish_table_wave(F, L, tables + ((size_t)b * C + c) * Lmax, pmf, lane);
+    __builtin_amdgcn_s_waitcnt(0xc07f);
+    __builtin_amdgcn_wave_barrier();
+  }
 }
 
 // Range encoder, one wave per (image, stream): stream ids 0..B-1 = y strings, B..2B-1 = z strings (which 0: z string,
@@ -178,6 +253,42 @@ __device__ __forceinline__ void put_ones(uint32_t* out32, int64_t cap_bits, int6
   while (count > 0) {
     const int len = count > 32 ? 32 : (int)count;
     put_bits(out32, cap_bits, off, len == 32 ? 0xFFFFFFFFu : ((1u << len) - 1u), len, overflow);
+    off += len;
+    count -= len;
+  }
+}
+
+// put_bits / put_ones through a window of LDS words: words wbase .. wbase + PLACE_WIN - 1 of the output are ORed in
+// LDS (flushed with one global atomic per word by place_flush), the rest straight into the output.
+constexpr int PLACE_WIN = 512;
+__device__ __forceinline__ void or_word(uint32_t* out32, uint32_t* win, int64_t wbase, int64_t w, uint32_t v) {
+  const int64_t i = w - wbase;
+  if (i >= 0 && i < PLACE_WIN) atomicOr(win + i, v);
+  else atomicOr(out32 + w, v);
+}
+
+__device__ __forceinline__ void put_bits_w(uint32_t* out32, uint32_t* win, int64_t wbase, int64_t cap_bits,
+                                           int64_t off, uint32_t v, int len, int* overflow) {
+  if (off + len > cap_bits) {
+    *overflow = 1;
+    return;
+  }
+  const int64_t w = off >> 5;
+  const int s = (int)(off & 31), space = 32 - s;
+  if (len <= space) {
+    or_word(out32, win, wbase, w, __builtin_bswap32(v << (space - len)));
+  } else {
+    const int rest = len - space;
+    or_word(out32, win, wbase, w, __builtin_bswap32(v >> rest));
+    or_word(out32, win, wbase, w + 1, __builtin_bswap32(v << (32 - rest)));
+  }
+}
+
+__device__ __forceinline__ void put_ones_w(uint32_t* out32, uint32_t* win, int64_t wbase, int64_t cap_bits,
+                                           int64_t off, uint32_t count, int* overflow) {
+  while (count > 0) {
+    const int len = count > 32 ? 32 : (int)count;
+    put_bits_w(out32, win, wbase, cap_bits, off, len == 32 ? 0xFFFFFFFFu : ((1u << len) - 1u), len, overflow);
     off += len;
     count -= len;
   }
@@ -448,21 +559,45 @@ __global__ __launch_bounds__(1024) void range_encode_kernel(
 //  chain (one wave per string, <= 8 VGPRs, no LDS): enc_step on scalar registers, 64 pairs per global load
 //        (two groups ahead); per symbol the interval before renormalisation (low1, high1) leaves through two
 //        vector stores per 64 symbols; the final low per string.
-//  place (one workgroup per string): per symbol the E1/E2 bits and the E3 run from (low1, high1), the pending
-//        counts as a scan over the whole string, the bit offsets as a prefix sum, then the same put_bits calls,
-//        flush, lengths and error bit 4 as range_encode_kernel.
-// Workspace: pairs, rec_low, rec_high [B (M HWy + N HWz)] uint32, then final low [2B]; string s < B is y string
-// s at symbol s * ny, string B + b the z string b at B ny + b nz.
+//  place (two whole-chip launches of short waves, one slice of a string each): per symbol the E1/E2 bits and the
+//        E3 run from (low1, high1); summarize writes each slice's carry map and bit count, emit composes the records
+//        in front of its slice and makes the same put_bits calls, flush, lengths and error bit 4 as
+//        range_encode_kernel.
+// Workspace: pairs, rec_low, rec_high [B (M HWy + N HWz)] uint32, then final low [2B], then (8-byte aligned) the
+// slice records [B (ky + kz)] uint2; string s < B is y string s at symbol s * ny, string B + b the z string b at
+// B ny + b nz.
 struct SplitGeom {
   int B, M, HWy, N, HWz, Lmax, per_element_y;
   int64_t ny, nz;
+  int gy, gz;   // place: 64-symbol groups per slice of a y / z string (place_slicing)
+  int ky, kz;   // place: slices per y / z string
   __device__ __forceinline__ void stream(int s, int& which, int& b, int64_t& n, int64_t& base) const {
     which = s < B ? 1 : 0;
     b = which ? s : s - B;
     n = which ? ny : nz;
     base = which ? (int64_t)b * ny : (int64_t)B * ny + (int64_t)b * nz;
   }
+  // place slice q (0 .. B (ky + kz) - 1; y strings first) -> string s, slice k of the string, its slice count and
+  // the index of the string's first slice record
+  __device__ __forceinline__ void slice(int q, int& s, int& k, int& ks, int& gs, int& q0) const {
+    const int qz = q - B * ky;
+    const bool y = qz < 0;
+    ks = y ? ky : kz;
+    gs = y ? gy : gz;
+    s = y ? q / ky : B + qz / kz;
+    k = y ? q % ky : qz % kz;
+    q0 = q - k;
+  }
 };
+
+// Groups of 64 symbols per place slice: at least 8 (one slice = one wave's short walk), more for long strings so
+// that a string has at most 256 slices (the records a wave composes before it emits).
+static inline void place_slicing(int64_t n, int& groups, int& slices) {
+  const int64_t ng = (n + 63) / 64;
+  const int64_t g = (ng + 255) / 256 > 8 ? (ng + 255) / 256 : 8;
+  groups = (int)g;
+  slices = (int)((ng + g - 1) / g);
+}
 
 __global__ __launch_bounds__(256) void enc_pack_kernel(const float* __restrict__ y, const float* __restrict__ z,
                                                        const int* __restrict__ meta, const uint16_t* __restrict__ tab_y,
@@ -595,121 +730,220 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_num_vgpr(8))) void enc_ch
   if (threadIdx.x == 0) final_low[s] = low;
 }
 
-constexpr int PLACE_THREADS = 1024;
+// ---- place: summarize -> emit ----------------------------------------------------------------------------------
+// A string is cut into slices of `gs` groups of 64 symbols (place_slicing); a wave walks one slice, and a 256-thread
+// workgroup holds four such waves that never wait for each other (no barrier; emit gives each wave an LDS window of
+// its own), so every workgroup lives for a few microseconds and none keeps a CU from the next conv launch for long.
+//  summarize: the slice's carry map of the pending count, c -> (a ? c : 0) + t (a = 1: no symbol of the slice emits
+//             a bit), and its bit count with carry-in 0; one record per slice.
+//  emit:      the records of the slices in front of it give the slice's carry-in and its bit offset; then the same
+//             put_bits / put_ones calls at the same offsets as range_encode_kernel, and the string's last slice
+//             writes the flush and the length.  Every record is written by the first launch before the second reads
+//             one: no wave waits for another, and the workspace may hold anything when the call starts.
+// Composition: (a1, t1) then (a2, t2) = (a1 & a2, (a2 ? t1 : 0) + t2).  A record is (t, len | head << 31), head = !a.
+#ifndef PLACE_WAVES
+#define PLACE_WAVES 4
+#endif
+constexpr int PLACE_CHUNK = 8;   // groups whose records one wave loads at once (a slice is >= 8 groups)
 
-// Carry of the pending count across a slice of symbols: c -> (a ? c : 0) + t.  Composition (a1, t1) then (a2, t2)
-// = (a1 & a2, (a2 ? t1 : 0) + t2).
-__global__ __launch_bounds__(PLACE_THREADS) void enc_place_kernel(const int* __restrict__ meta, SplitGeom G,
-                                                                  const uint32_t* __restrict__ rec_low,
-                                                                  const uint32_t* __restrict__ rec_high,
-                                                                  const uint32_t* __restrict__ final_low,
-                                                                  uint8_t* __restrict__ out, int64_t cap_y,
-                                                                  int64_t cap_z, int* __restrict__ lengths,
-                                                                  int* __restrict__ err) {
-  __shared__ uint32_t sc_a[PLACE_THREADS], sc_t[PLACE_THREADS];
-  __shared__ uint64_t sc_l[PLACE_THREADS];
-  const int s = blockIdx.x, tid = threadIdx.x;
+// records of the groups c0, c0 + 64, ... (PLACE_CHUNK of them) in one round of loads; past j1: (0, ~0)
+__device__ __forceinline__ void place_load(const uint32_t* __restrict__ rlo, const uint32_t* __restrict__ rhi,
+                                           int64_t c0, int64_t j1, int lane, uint32_t (&lo)[PLACE_CHUNK],
+                                           uint32_t (&hi)[PLACE_CHUNK]) {
+#pragma unroll
+  for (int i = 0; i < PLACE_CHUNK; ++i) {
+    const int64_t j = c0 + i * 64 + lane;
+    lo[i] = j < j1 ? rlo[j] : 0u;
+    hi[i] = j < j1 ? rhi[j] : ~0u;
+  }
+}
+
+// One group of 64 records; lane j: symbol j of the group, lanes past the slice end hold (0, ~0): no bit, no E3 run.
+// Per lane the final bits of the symbol (nbv of them) and the inverse bits owed in front of the first (pendv, 0
+// unless nbv > 0); `pending` (wave-uniform) goes from the count owed in front of the group to the count owed behind
+// it.  The scans of range_encode_kernel's fast path.
+__device__ __forceinline__ void place_group(uint32_t lo, uint32_t hi, int lane, uint32_t& pending, uint32_t& nbv,
+                                            uint32_t& pendv) {
+  nbv = (uint32_t)__builtin_clz(lo ^ hi);
+  const uint32_t mv = (uint32_t)__builtin_clz((((hi | ~lo) << nbv) << 1) | 1u);
+  uint32_t T = mv;
+#pragma unroll
+  for (int o = 1; o < 64; o <<= 1) {
+    const uint32_t up = __shfl_up(T, o, 64);
+    if (lane >= o) T += up;
+  }
+  const uint32_t Tex = T - mv;
+  const uint64_t heads = __ballot(nbv > 0);
+  const uint64_t before = heads & ((1ull << lane) - 1ull);
+  const int hb = 63 - __builtin_clzll(before | 1ull);
+  const uint32_t Tex_h = __shfl(Tex, hb, 64);
+  const uint32_t pend_in = before ? Tex - Tex_h : pending + Tex;
+  pendv = nbv ? pend_in : 0u;
+  const int hl = 63 - __builtin_clzll(heads | 1ull);
+  const uint32_t T63 = __builtin_amdgcn_readlane(T, 63);
+  const uint32_t Tex_hl = __builtin_amdgcn_readlane(Tex, hl);
+  pending = heads ? T63 - Tex_hl : pending + T63;
+}
+
+__global__ __launch_bounds__(64 * PLACE_WAVES) void enc_place_sum_kernel(const int* __restrict__ meta, SplitGeom G,
+                                                                         const uint32_t* __restrict__ rec_low,
+                                                                         const uint32_t* __restrict__ rec_high,
+                                                                         uint2* __restrict__ slices) {
+  const int lane = threadIdx.x & 63;
+  const int q = __builtin_amdgcn_readfirstlane(blockIdx.x * PLACE_WAVES + (threadIdx.x >> 6));
+  if (q >= G.B * (G.ky + G.kz)) return;
+  int s, k, ks, gs, q0;
+  G.slice(q, s, k, ks, gs, q0);
+  int which, b;
+  int64_t n, base;
+  G.stream(s, which, b, n, base);
+  const int L = meta[4 * b + (which ? 1 : 3)];
+  if (L > G.Lmax || L < 1) return;   // emit reports it; the chain wrote no records
+  const uint32_t* rlo = rec_low + base;
+  const uint32_t* rhi = rec_high + base;
+  const int64_t j0 = (int64_t)k * gs * 64;
+  const int64_t j1 = j0 + (int64_t)gs * 64 < n ? j0 + (int64_t)gs * 64 : n;
+  uint32_t pending = 0, bits = 0, head = 0;   // a slice emits < 2^27 bits besides its carry-in
+  for (int64_t c0 = j0; c0 < j1; c0 += PLACE_CHUNK * 64) {
+    uint32_t lo[PLACE_CHUNK], hi[PLACE_CHUNK];
+    place_load(rlo, rhi, c0, j1, lane, lo, hi);
+#pragma unroll
+    for (int i = 0; i < PLACE_CHUNK; ++i) {
+      if (c0 + i * 64 >= j1) break;
+      uint32_t nbv, pendv;
+      place_group(lo[i], hi[i], lane, pending, nbv, pendv);
+      head |= __ballot(nbv > 0) ? 1u : 0u;
+      uint32_t len = nbv + pendv;
+#pragma unroll
+      for (int o = 32; o > 0; o >>= 1) len += __shfl_xor(len, o, 64);
+      bits += len;
+    }
+  }
+  if (lane == 0) slices[q] = make_uint2(pending, bits | (head << 31));
+}
+
+__global__ __launch_bounds__(64 * PLACE_WAVES) void enc_place_emit_kernel(
+    const int* __restrict__ meta, SplitGeom G, const uint32_t* __restrict__ rec_low,
+    const uint32_t* __restrict__ rec_high, const uint2* __restrict__ slices, const uint32_t* __restrict__ final_low,
+    uint8_t* __restrict__ out, int64_t cap_y, int64_t cap_z, int* __restrict__ lengths, int* __restrict__ err) {
+  const int lane = threadIdx.x & 63;
+  const int q = __builtin_amdgcn_readfirstlane(blockIdx.x * PLACE_WAVES + (threadIdx.x >> 6));
+  if (q >= G.B * (G.ky + G.kz)) return;
+  int s, k, ks, gs, q0;
+  G.slice(q, s, k, ks, gs, q0);
   int which, b;
   int64_t n, base;
   G.stream(s, which, b, n, base);
   const int L = meta[4 * b + (which ? 1 : 3)];
   if (L > G.Lmax || L < 1) {
-    if (tid == 0) {
+    if (k == 0 && lane == 0) {
       atomicOr(err, 1);
       lengths[2 * b + which] = 0;
     }
     return;
   }
+  const uint32_t* rlo = rec_low + base;
+  const uint32_t* rhi = rec_high + base;
+  const int64_t j0 = (int64_t)k * gs * 64;
+  const int64_t j1 = j0 + (int64_t)gs * 64 < n ? j0 + (int64_t)gs * 64 : n;
+  uint32_t lo[PLACE_CHUNK], hi[PLACE_CHUNK];   // the first chunk's records travel while the slices are composed
+  place_load(rlo, rhi, j0, j1, lane, lo, hi);
+  // carry-in and bit offset of slice k: the maps of slices 0..k-1 composed, 64 records per step
+  uint32_t pending = 0;
+  uint64_t off = 0;
+  for (int i0 = 0; i0 < k; i0 += 64) {
+    const int i = i0 + lane;
+    uint32_t a = 1u, t = 0u, len = 0u;   // past k: the identity map, no bits
+    if (i < k) {
+      const uint2 r = slices[q0 + i];
+      t = r.x;
+      len = r.y & 0x7FFFFFFFu;
+      a = (r.y >> 31) ? 0u : 1u;
+    }
+    uint32_t A = a, Tm = t;   // slices i0..i composed
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+      const uint32_t pa = __shfl_up(A, o, 64), pt = __shfl_up(Tm, o, 64);
+      if (lane >= o) {   // (pa, pt) then (A, Tm)
+        Tm = (A ? pt : 0u) + Tm;
+        A = pa & A;
+      }
+    }
+    uint32_t Ae = __shfl_up(A, 1, 64), Te = __shfl_up(Tm, 1, 64);
+    if (lane == 0) {
+      Ae = 1u;
+      Te = 0u;
+    }
+    const uint32_t cin = (Ae ? pending : 0u) + Te;   // owed at the start of slice i
+    uint64_t bits = (uint64_t)len + (a ? 0u : cin);
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) bits += __shfl_xor(bits, o, 64);
+    off += bits;
+    const uint32_t A63 = __builtin_amdgcn_readlane(A, 63), T63 = __builtin_amdgcn_readlane(Tm, 63);
+    pending = (A63 ? pending : 0u) + T63;
+  }
+
   const int64_t stride = cap_z + cap_y;
   uint32_t* dst32 = (uint32_t*)(out + (size_t)b * stride + (which ? cap_z : 0));
   const int64_t cap_bits = (which ? cap_y : cap_z) * 8;
-  const uint32_t* rlo = rec_low + base;
-  const uint32_t* rhi = rec_high + base;
-  const int64_t per = (n + PLACE_THREADS - 1) / PLACE_THREADS;
-  const int64_t j0 = (int64_t)tid * per < n ? (int64_t)tid * per : n;
-  const int64_t j1 = j0 + per < n ? j0 + per : n;
-
-  // pass 1: the slice's carry map and its bit count without the carry
-  uint32_t t = 0, head = 0;
-  uint64_t len = 0;
-  for (int64_t j = j0; j < j1; ++j) {
-    const uint32_t lo = rlo[j], hi = rhi[j];
-    const uint32_t nb = (uint32_t)__builtin_clz(lo ^ hi);
-    const uint32_t m = (uint32_t)__builtin_clz((((hi | ~lo) << nb) << 1) | 1u);
-    if (nb) {   // owed in front of it: the runs since the last head (the first head: + the carry-in, added below)
-      len += nb + t;
-      head = 1;
-      t = 0;
-    }
-    t += m;
-  }
-  // exclusive scan of the carry maps: pending count owed at the slice start (0 at the string start)
-  sc_a[tid] = head ? 0u : 1u;
-  sc_t[tid] = t;
-  __syncthreads();
-  for (int o = 1; o < PLACE_THREADS; o <<= 1) {
-    uint32_t pa = 1, pt = 0;
-    if (tid >= o) {
-      pa = sc_a[tid - o];
-      pt = sc_t[tid - o];
-    }
-    __syncthreads();
-    if (tid >= o) {   // (pa, pt) then (a, t)
-      const uint32_t a = sc_a[tid];
-      sc_t[tid] = (a ? pt : 0u) + sc_t[tid];
-      sc_a[tid] = pa & a;
-    }
-    __syncthreads();
-  }
-  const uint32_t carry_in = tid ? sc_t[tid - 1] : 0u;   // maps applied to 0: a does not matter
-  const uint32_t pend_final = sc_t[PLACE_THREADS - 1];
-  const uint64_t mylen = len + (head ? (uint64_t)carry_in : 0u);
-  __syncthreads();
-  sc_l[tid] = mylen;
-  __syncthreads();
-  for (int o = 1; o < PLACE_THREADS; o <<= 1) {
-    const uint64_t v = tid >= o ? sc_l[tid - o] : 0u;
-    __syncthreads();
-    sc_l[tid] += v;
-    __syncthreads();
-  }
-  const int64_t total = (int64_t)sc_l[PLACE_THREADS - 1];
-  int64_t off = (int64_t)(sc_l[tid] - mylen);
-
-  // pass 2: the same pieces range_encode_kernel writes, at the same offsets
   int overflow = 0;
-  uint32_t pend = carry_in;
-  for (int64_t j = j0; j < j1; ++j) {
-    const uint32_t lo = rlo[j], hi = rhi[j];
-    const uint32_t nbv = (uint32_t)__builtin_clz(lo ^ hi);
-    const uint32_t m = (uint32_t)__builtin_clz((((hi | ~lo) << nbv) << 1) | 1u);
-    if (nbv) {
-      const uint32_t bitsv = lo >> (32u - nbv);
-      const uint32_t pendv = pend;
-      if (pendv == 0) {
-        put_bits(dst32, cap_bits, off, bitsv, (int)nbv, &overflow);
-      } else {
-        const uint32_t first = bitsv >> (nbv - 1);
-        put_bits(dst32, cap_bits, off, first, 1, &overflow);
-        if (!first) put_ones(dst32, cap_bits, off + 1, pendv, &overflow);
-        else if (off + 1 + (int64_t)pendv > cap_bits) overflow = 1;
-        if (nbv > 1)
-          put_bits(dst32, cap_bits, off + 1 + pendv, bitsv & ((1u << (nbv - 1)) - 1u), (int)nbv - 1, &overflow);
+  // the slice's bits are ORed into an LDS window first: one global atomic per output word instead of one per piece
+  __shared__ uint32_t win_all[PLACE_WAVES][PLACE_WIN];
+  uint32_t* win = win_all[threadIdx.x >> 6];
+#pragma unroll
+  for (int i = lane; i < PLACE_WIN; i += 64) win[i] = 0u;
+  const int64_t wbase = (int64_t)(off >> 5);
+  for (int64_t c0 = j0; c0 < j1; c0 += PLACE_CHUNK * 64) {
+    if (c0 != j0) place_load(rlo, rhi, c0, j1, lane, lo, hi);
+#pragma unroll
+    for (int i = 0; i < PLACE_CHUNK; ++i) {
+      if (c0 + i * 64 >= j1) break;
+      uint32_t nbv, pendv;
+      place_group(lo[i], hi[i], lane, pending, nbv, pendv);
+      const uint32_t len = nbv + pendv;
+      uint32_t incl = len;
+#pragma unroll
+      for (int o = 1; o < 64; o <<= 1) {
+        const uint32_t up = __shfl_up(incl, o, 64);
+        if (lane >= o) incl += up;
       }
-      off += nbv + pendv;
-      pend = 0;
+      const int64_t o = (int64_t)off + (int64_t)(incl - len);
+      if (nbv > 0) {   // the pieces of range_encode_kernel, at the same offsets
+        const uint32_t bitsv = lo[i] >> (32u - nbv);
+        if (pendv == 0) {
+          put_bits_w(dst32, win, wbase, cap_bits, o, bitsv, (int)nbv, &overflow);
+        } else {
+          const uint32_t first = bitsv >> (nbv - 1);
+          put_bits_w(dst32, win, wbase, cap_bits, o, first, 1, &overflow);
+          if (!first) put_ones_w(dst32, win, wbase, cap_bits, o + 1, pendv, &overflow);
+          else if (o + 1 + (int64_t)pendv > cap_bits) overflow = 1;
+          if (nbv > 1)
+            put_bits_w(dst32, win, wbase, cap_bits, o + 1 + pendv, bitsv & ((1u << (nbv - 1)) - 1u), (int)nbv - 1,
+                       &overflow);
+        }
+      }
+      off += (uint32_t)__builtin_amdgcn_readlane((int)incl, 63);
     }
-    pend += m;
   }
-  if (tid == 0) {   // flush (torchac): one more pending bit, then the deciding bit and the pending run
-    const uint32_t pending = pend_final + 1u;
+  // the window's words that received bits (all inside the capacity: put_bits_w checked each piece)
+  const int64_t wend = (int64_t)((off + 31) >> 5) - wbase;
+  const int nw = wend < PLACE_WIN ? (int)wend : PLACE_WIN;
+  __builtin_amdgcn_s_waitcnt(0xc07f);
+  __builtin_amdgcn_wave_barrier();
+  for (int i = lane; i < nw; i += 64) {
+    const uint32_t v = win[i];
+    if (v) atomicOr(dst32 + wbase + i, v);
+  }
+  if (k == ks - 1 && lane == 0) {   // flush (torchac): one more pending bit, then the deciding bit and the pending run
+    const int64_t total = (int64_t)off;
+    const uint32_t pend = pending + 1u;
     const uint32_t bit = final_low[s] < 0x40000000u ? 0u : 1u;
     put_bits(dst32, cap_bits, total, bit, 1, &overflow);
-    if (!bit) put_ones(dst32, cap_bits, total + 1, pending, &overflow);
-    else if (total + 1 + (int64_t)pending > cap_bits) overflow = 1;
-    lengths[2 * b + which] = (int)((total + 1 + (int64_t)pending + 7) >> 3);
+    if (!bit) put_ones(dst32, cap_bits, total + 1, pend, &overflow);
+    else if (total + 1 + (int64_t)pend > cap_bits) overflow = 1;
+    lengths[2 * b + which] = (int)((total + 1 + (int64_t)pend + 7) >> 3);
   }
-  if (overflow) atomicOr(err, 4);
+  if (__any(overflow) && lane == 0) atomicOr(err, 4);
 }
 
 // Range decoder, one wave per stream (torchac decode_float_cdf, call sites :96,116).
@@ -933,10 +1167,27 @@ __global__ __launch_bounds__(256) void range_decode_kernel(const uint8_t* __rest
 
 using namespace dsic;
 
+// ENC_ABL (diagnostic builds only, wrong results): skip the launches of 1 support, 2 tables, 4 pack, 8 place (both
+// launches), 16 chain; error bits then go to a sink of their own, so that a run is not stopped by them.
+#ifndef ENC_ABL
+#define ENC_ABL 0
+#endif
+#if ENC_ABL
+__device__ int enc_abl_err_sink;
+static int* abl_err(int* err) {
+  void* p = nullptr;
+  return hipGetSymbolAddress(&p, HIP_SYMBOL(enc_abl_err_sink)) == hipSuccess ? (int*)p : err;
+}
+#else
+static int* abl_err(int* err) { return err; }
+#endif
+
+
 extern "C" int dsic_latent_support(const float* y_nchw, const float* z_nchw, int* meta, int B,
                                    int64_t n_y, int64_t n_z, int tail, void* stream) {
   DSIC_REQUIRE(y_nchw && z_nchw && meta, "latent_support: null pointer");
   DSIC_REQUIRE(B > 0 && n_y > 0 && n_z > 0 && tail >= 0, "latent_support: bad argument");
+  if (ENC_ABL & 1) return DSIC_OK;
   hipLaunchKernelGGL(support_kernel, dim3(B), dim3(256), 0, (hipStream_t)stream, y_nchw, z_nchw, meta,
                      n_y, n_z, tail);
   return check_launch("latent_support");
@@ -949,15 +1200,22 @@ static int tables_launch(bool student, const float* sigma, const float* nu, int 
                          int* err, hipStream_t st) {
   DSIC_REQUIRE(sigma && meta && tables && err && (!student || nu), "cdf_tables: null pointer");
   DSIC_REQUIRE(B > 0 && C > 0 && Lmax >= 1 && Lmax <= 1000, "cdf_tables: Lmax=%d must be in [1,1000]", Lmax);
+  if (ENC_ABL & 2) return DSIC_OK;
+  err = abl_err(err);
   const int ntables = B * C;
   const size_t shm = (size_t)4 * (2 * Lmax + 1) * sizeof(float);
   const int sb = per_image ? C : 0;
-  if (student)
+  if (student) {
     hipLaunchKernelGGL(tables_kernel<true>, dim3(ceil_div(ntables, 4)), dim3(256), shm, st, sigma, nu, sb,
                        meta, meta_off, tables, C, Lmax, ntables, err);
-  else
+  } else if (sb == 0) {
+    const int rowmax = 4 * Lmax;
+    hipLaunchKernelGGL(gauss_tables_kernel, dim3(C, ceil_div(B, ZT_IMGS)), dim3(256), shm + rowmax * sizeof(float),
+                       st, sigma, meta, tables, B, C, Lmax, rowmax, err);
+  } else {
     hipLaunchKernelGGL(tables_kernel<false>, dim3(ceil_div(ntables, 4)), dim3(256), shm, st, sigma, nu, sb,
                        meta, meta_off, tables, C, Lmax, ntables, err);
+  }
   return check_launch("cdf_tables");
 }
 
@@ -991,10 +1249,19 @@ extern "C" int dsic_range_encode(const float* y_nchw, const float* z_nchw, const
 }
 
 // Split encoder (pack -> chain -> place): the same bytes, lengths and error bits as dsic_range_encode.
+static int64_t place_records(int B, int64_t ny, int64_t nz) {
+  int gy, ky, gz, kz;
+  place_slicing(ny, gy, ky);
+  place_slicing(nz, gz, kz);
+  return (int64_t)B * (ky + kz);
+}
+
 extern "C" int64_t dsic_range_encode_workspace_size(int B, int M, int HWy, int N, int HWz) {
   if (B <= 0 || M <= 0 || HWy <= 0 || N <= 0 || HWz <= 0) return -1;
-  const int64_t total = (int64_t)B * ((int64_t)M * HWy + (int64_t)N * HWz);
-  return 12 * total + 8 * (int64_t)B;   // pairs, rec_low, rec_high: 4 B per symbol each; final low per string
+  const int64_t ny = (int64_t)M * HWy, nz = (int64_t)N * HWz;
+  const int64_t total = (int64_t)B * (ny + nz);
+  // pairs, rec_low, rec_high: 4 B per symbol each; final low per string; 8-byte slice records (+ alignment)
+  return 12 * total + 8 * (int64_t)B + 8 + 8 * place_records(B, ny, nz);
 }
 
 extern "C" int dsic_range_encode_ws(const float* y_nchw, const float* z_nchw, const int* meta,
@@ -1009,30 +1276,49 @@ extern "C" int dsic_range_encode_ws(const float* y_nchw, const float* z_nchw, co
                "range_encode_ws: capacities must be multiples of 4 and >= 8");
   DSIC_REQUIRE(workspace_bytes >= dsic_range_encode_workspace_size(B, M, HWy, N, HWz),
                "range_encode_ws: workspace too small");
+  err = abl_err(err);
   SplitGeom G;
   G.B = B; G.M = M; G.HWy = HWy; G.N = N; G.HWz = HWz; G.Lmax = Lmax; G.per_element_y = per_element_y ? 1 : 0;
   G.ny = (int64_t)M * HWy;
   G.nz = (int64_t)N * HWz;
   DSIC_REQUIRE(G.ny < ((int64_t)1 << 29) && G.nz < ((int64_t)1 << 29), "range_encode_ws: string too long");
+  place_slicing(G.ny, G.gy, G.ky);
+  place_slicing(G.nz, G.gz, G.kz);
+  const int64_t nslices = (int64_t)B * (G.ky + G.kz);
+  DSIC_REQUIRE(nslices < ((int64_t)1 << 30), "range_encode_ws: too many strings");
   const int64_t total = (int64_t)B * (G.ny + G.nz);
   uint32_t* pairs = (uint32_t*)workspace;
   uint32_t* rec_low = pairs + total;
   uint32_t* rec_high = rec_low + total;
   uint32_t* final_low = rec_high + total;
+  uint2* slices = (uint2*)(((uintptr_t)(final_low + 2 * B) + 7) & ~(uintptr_t)7);
   hipStream_t st = (hipStream_t)stream;
-  const int64_t nmax = G.ny > G.nz ? G.ny : G.nz;
-  const int gx = (int)((nmax + 255) / 256 < 256 ? (nmax + 255) / 256 : 256);
-  hipLaunchKernelGGL(enc_pack_kernel, dim3(gx, 2 * B), dim3(256), 0, st, y_nchw, z_nchw, meta, tab_y, tab_z, G, pairs,
-                     err);
-  int rc = check_launch("range_encode_ws: pack");
-  if (rc != DSIC_OK) return rc;
-  // strings 0..B-1 (the long y strings) first; one wave per workgroup
-  hipLaunchKernelGGL(enc_chain_kernel, dim3(2 * B), dim3(64), 0, st, pairs, meta, G, rec_low, rec_high, final_low);
-  rc = check_launch("range_encode_ws: chain");
-  if (rc != DSIC_OK) return rc;
-  hipLaunchKernelGGL(enc_place_kernel, dim3(2 * B), dim3(PLACE_THREADS), 0, st, meta, G, rec_low, rec_high,
-                     final_low, out, cap_y, cap_z, lengths, err);
-  return check_launch("range_encode_ws: place");
+  int rc = DSIC_OK;
+  if (!(ENC_ABL & 4)) {
+    const int64_t nmax = G.ny > G.nz ? G.ny : G.nz;
+    const int gx = (int)((nmax + 255) / 256 < 256 ? (nmax + 255) / 256 : 256);
+    hipLaunchKernelGGL(enc_pack_kernel, dim3(gx, 2 * B), dim3(256), 0, st, y_nchw, z_nchw, meta, tab_y, tab_z, G,
+                       pairs, err);
+    rc = check_launch("range_encode_ws: pack");
+    if (rc != DSIC_OK) return rc;
+  }
+  if (!(ENC_ABL & 16)) {
+    // strings 0..B-1 (the long y strings) first; one wave per workgroup
+    hipLaunchKernelGGL(enc_chain_kernel, dim3(2 * B), dim3(64), 0, st, pairs, meta, G, rec_low, rec_high, final_low);
+    rc = check_launch("range_encode_ws: chain");
+    if (rc != DSIC_OK) return rc;
+  }
+  if (!(ENC_ABL & 8)) {
+    const int nwg = (int)((nslices + PLACE_WAVES - 1) / PLACE_WAVES);
+    hipLaunchKernelGGL(enc_place_sum_kernel, dim3(nwg), dim3(64 * PLACE_WAVES), 0, st, meta, G, rec_low, rec_high,
+                       slices);
+    rc = check_launch("range_encode_ws: place summarize");
+    if (rc != DSIC_OK) return rc;
+    hipLaunchKernelGGL(enc_place_emit_kernel, dim3(nwg), dim3(64 * PLACE_WAVES), 0, st, meta, G, rec_low, rec_high,
+                       slices, final_low, out, cap_y, cap_z, lengths, err);
+    rc = check_launch("range_encode_ws: place emit");
+  }
+  return rc;
 }
 
 extern "C" int dsic_range_decode(const uint8_t* in, int64_t stride, const int* lengths, int lstride,

@@ -11,7 +11,8 @@ import os
 from ctypes import c_int, c_int64, c_void_p
 
 HERE = os.path.dirname(os.path.abspath(__file__))
-LIB_PATH = os.path.join(HERE, "libdsic_hip.so")
+# DSIC_LIB: load another build (A/B and diagnostic builds) without touching the production library
+LIB_PATH = os.environ.get("DSIC_LIB") or os.path.join(HERE, "libdsic_hip.so")
 
 DSIC_OK, DSIC_EINVAL, DSIC_EHIP = 0, 1, 2
 ACT_NONE, ACT_GDN, ACT_IGDN, ACT_RELU = 0, 1, 2, 3
