@@ -12,6 +12,10 @@ kind 0 = uint8 [H,W,C] (PIL / numpy layout), 1 = float32 [C,H,W] in [0,1].  Tili
 reflect-padded bottom/right to multiples of 16 inside the gather kernel; the last row / column of tiles shifts inward
 (overlap, no extra padding) and every pixel is written back by the one tile that owns it.  Tiles are coded
 independently, as the reference's patch-trained model sees them; seams are not blended.
+
+Because tiles are independent and the DSIC2 heads hold every string's length, any window of a stream can be decoded
+from only the tiles that own its pixels: stream_index finds their bytes from the heads alone, decompress_region decodes
+them in dense batches and stitches them into the window, byte for byte the crop of decompress_image's result.
 """
 from __future__ import annotations
 
@@ -159,22 +163,20 @@ def compress_image(model, img, tile=256, batch=64, tail=10) -> bytes:
     return pack_image_stream(header, blobs)
 
 
-@torch.no_grad()
-def decompress_image(model, stream, out=None):
-    """DSICI stream -> the image on the model's device: uint8 [H,W,C] ((uint8)(clamp(x,0,1)*255), truncating, as
-    torchvision's to_pil_image) or float32 [C,H,W] (clamp(x,0,1)); by default the kind of the encoder's input,
-    out="u8" / "f32" overrides it.  Each decoded batch is stitched straight into the image."""
-    h = unpack_image_stream(stream)
-    if out not in (None, "u8", "f32"):
-        raise ValueError(f"decompress_image: out={out!r} (None, 'u8' or 'f32')")
+def _refuse_foreign(model, h, what):
+    """A stream this decoder cannot rebuild the coder tables of: another numerics tag, or another model shape."""
     if int(h["numerics"]) != entropy.numerics_tag():
-        raise EntropyError(f"decompress_image: the stream was written with numerics tag {h['numerics']:#x}, this "
+        raise EntropyError(f"{what}: the stream was written with numerics tag {h['numerics']:#x}, this "
                            f"decoder is {entropy.numerics_tag():#x}")
     mine = _model_shape(model)
     theirs = (h["N"], h["M"], h["in_ch"], h["spatial_params"])
     if mine != theirs:
-        raise EntropyError(f"decompress_image: the stream was written by a model with (N, M, in_ch, spatial_params) = "
+        raise EntropyError(f"{what}: the stream was written by a model with (N, M, in_ch, spatial_params) = "
                            f"{theirs}, this one is {mine}")
+
+
+def _stream_grid(h):
+    """The tile grid a DSICI header describes; ValueError where its fields contradict each other."""
     H, W, C, th, tw = h["H"], h["W"], h["C"], h["th"], h["tw"]
     if C != h["in_ch"] or h["kind"] not in (KIND_U8_HWC, KIND_F32_CHW) or h["batch"] < 1:
         raise ValueError("DSICI stream: inconsistent header")
@@ -184,24 +186,281 @@ def decompress_image(model, stream, out=None):
     g = _grid(H, W, th, tw)
     if h["batches"] != -(-g["n"] // h["batch"]):
         raise ValueError(f"DSICI stream: {h['batches']} batches for {g['n']} tiles in batches of {h['batch']}")
+    return g
+
+
+def _check_batch_shape(k, shape_y, n, th, tw):
+    if shape_y[0] != n or shape_y[2:] != [th // 16, tw // 16]:
+        raise ValueError(f"DSICI stream: batch {k} holds {shape_y[0]} latents of {shape_y[2]}x{shape_y[3]}, "
+                         f"expected {n} of {th // 16}x{tw // 16}")
+
+
+def _out_image(kind, C, h, w, dev, what):
+    """The empty output image of a decode and the stitch call's name stem: uint8 [h,w,C] or float32 [C,h,w]."""
+    if kind == KIND_U8_HWC:
+        if C not in (3, 4):
+            raise ValueError(f"{what}: uint8 output needs 3 or 4 channels, the stream has {C}")
+        return torch.empty((h, w, C), dtype=torch.uint8, device=dev), "u8"
+    return torch.empty((C, h, w), dtype=torch.float32, device=dev), "f32"
+
+
+@torch.no_grad()
+def decompress_image(model, stream, out=None):
+    """DSICI stream -> the image on the model's device: uint8 [H,W,C] ((uint8)(clamp(x,0,1)*255), truncating, as
+    torchvision's to_pil_image) or float32 [C,H,W] (clamp(x,0,1)); by default the kind of the encoder's input,
+    out="u8" / "f32" overrides it.  Each decoded batch is stitched straight into the image."""
+    h = unpack_image_stream(stream)
+    if out not in (None, "u8", "f32"):
+        raise ValueError(f"decompress_image: out={out!r} (None, 'u8' or 'f32')")
+    _refuse_foreign(model, h, "decompress_image")
+    g = _stream_grid(h)
+    H, W, C, th, tw = h["H"], h["W"], h["C"], h["th"], h["tw"]
     kind = {None: h["kind"], "u8": KIND_U8_HWC, "f32": KIND_F32_CHW}[out]
     dev = next(model.parameters()).device
     L = _lib.load()
-    if kind == KIND_U8_HWC:
-        if C not in (3, 4):
-            raise ValueError(f"decompress_image: uint8 output needs 3 or 4 channels, the stream has {C}")
-        img = torch.empty((H, W, C), dtype=torch.uint8, device=dev)
-        fn, what = L.dsic_tile_stitch_u8, "tile_stitch_u8"
-    else:
-        img = torch.empty((C, H, W), dtype=torch.float32, device=dev)
-        fn, what = L.dsic_tile_stitch_f32, "tile_stitch_f32"
+    img, suffix = _out_image(kind, C, H, W, dev, "decompress_image")
+    fn, what = getattr(L, "dsic_tile_stitch_" + suffix), "tile_stitch_" + suffix
     for k, blob in enumerate(h["blobs"]):
         first = k * h["batch"]
         n = min(h["batch"], g["n"] - first)
         _, shape_y, _, _ = entropy._container_records(blob)
-        if shape_y[0] != n or shape_y[2:] != [th // 16, tw // 16]:
-            raise ValueError(f"DSICI stream: batch {k} holds {shape_y[0]} latents of {shape_y[2]}x{shape_y[3]}, "
-                             f"expected {n} of {th // 16}x{tw // 16}")
+        _check_batch_shape(k, shape_y, n, th, tw)
         tiles = entropy._decompress_container_raw(model, blob, what="decompress_image").contiguous()
         _lib.check(fn(_p(tiles), _p(img), H, W, C, th, tw, first, n, _stream()), what)
+    return img
+
+
+# ---- region decode: any window of an image stream from only its tiles --------------------------------------------
+_DSIC2_HEAD = struct.Struct("<6sI7I")      # magic, numerics tag, B, My, Hy, Wy, Nz, Hz, Wz  (entropy.pack_container)
+_DSIC2_REC = struct.Struct("<4i2I")        # min_y, max_y, min_z, max_z, len_z, len_y
+
+
+class _Source:
+    """Random access to a stream held as bytes or behind a binary file object (seek + read); counts what it reads."""
+
+    def __init__(self, src):
+        if isinstance(src, (bytes, bytearray, memoryview)):
+            self.buf, self.f = memoryview(src).cast("B"), None
+            self.size = len(self.buf)
+        elif hasattr(src, "seek") and hasattr(src, "read"):
+            self.buf, self.f = None, src
+            self.size = src.seek(0, 2)
+            if self.size is None:                                          # a seek that returns nothing: ask tell
+                self.size = src.tell()
+        else:
+            raise TypeError(f"expected bytes or a binary file object with seek and read, got {type(src).__name__}")
+        self.bytes_read = 0
+
+    def read_at(self, off, n):
+        """Up to n bytes at off (fewer only at the end of the stream)."""
+        n = max(0, min(n, self.size - off))
+        if self.f is None:
+            out = self.buf[off:off + n]                                    # a view: copied once, into the upload
+        else:
+            self.f.seek(off)
+            out = self.f.read(n)
+            if len(out) != n:
+                raise ValueError("truncated DSICI stream")
+        self.bytes_read += len(out)
+        return out
+
+
+def _index_of(src):
+    """stream_index on an open _Source."""
+    head = src.read_at(0, _HEAD.size)
+    if len(head) < _HEAD.size:
+        raise ValueError("truncated DSICI stream" if head[:6] == MAGIC[:len(head)] else "not a DSICI image stream")
+    f = _HEAD.unpack(head)
+    if f[0] != MAGIC:
+        raise ValueError("not a DSICI image stream")
+    keys = ("version", "numerics", "H", "W", "C", "kind", "th", "tw", "N", "M", "in_ch", "spatial_params", "batch",
+            "batches")
+    ix = dict(zip(keys, f[1:]))
+    if ix["version"] != VERSION:
+        raise ValueError(f"DSICI stream version {ix['version']}, this reader knows {VERSION}")
+    g = _stream_grid(ix)
+    th, tw = ix["th"], ix["tw"]
+    off, tiles, containers = _HEAD.size, [], []
+    for k in range(ix["batches"]):
+        if off + _LEN.size > src.size:
+            raise ValueError("truncated DSICI stream")
+        (size,) = _LEN.unpack(src.read_at(off, _LEN.size))
+        off += _LEN.size
+        if off + size > src.size:
+            raise ValueError("truncated DSICI stream")
+        chead = src.read_at(off, min(size, _DSIC2_HEAD.size))
+        if chead[:6] == entropy._MAGIC_V1:
+            raise ValueError("DSIC1 container: written before the numerics tag existed (its coder tables may be the "
+                             "float64 ones of round 1); re-encode")
+        if len(chead) < _DSIC2_HEAD.size or chead[:6] != entropy._MAGIC:
+            raise ValueError("not a DSIC container")
+        _, tag, B, My, Hy, Wy, Nz, Hz, Wz = _DSIC2_HEAD.unpack(chead)
+        if tag != ix["numerics"]:
+            raise ValueError(f"DSICI stream: batch {k} carries numerics tag {tag:#x}, the stream's is "
+                             f"{ix['numerics']:#x}")
+        if B < 1 or size < _DSIC2_HEAD.size + _DSIC2_REC.size * B:
+            raise ValueError("truncated or oversized DSIC container")
+        first = k * ix["batch"]
+        _check_batch_shape(k, [B, My, Hy, Wy], min(ix["batch"], g["n"] - first), th, tw)
+        if (My, Nz) != (ix["M"], ix["N"]):
+            raise ValueError(f"DSICI stream: batch {k} holds latents of {My} and {Nz} channels, the header says "
+                             f"{ix['M']} and {ix['N']}")
+        if containers and (Hz, Wz) != tuple(containers[0]["shape_z"][2:]):
+            raise ValueError(f"DSICI stream: batch {k} holds hyper-latents of {Hz}x{Wz}, batch 0 of "
+                             f"{containers[0]['shape_z'][2]}x{containers[0]['shape_z'][3]}")
+        recs = src.read_at(off + _DSIC2_HEAD.size, _DSIC2_REC.size * B)
+        pos = off + _DSIC2_HEAD.size + _DSIC2_REC.size * B
+        for b, (min_y, max_y, min_z, max_z, len_z, len_y) in enumerate(_DSIC2_REC.iter_unpack(recs)):
+            tiles.append({"k": k, "b": b, "min_y": min_y, "max_y": max_y, "min_z": min_z, "max_z": max_z,
+                          "z_off": pos, "z_len": len_z, "y_off": pos + len_z, "y_len": len_y})
+            pos += len_z + len_y
+        if pos != off + size:
+            raise ValueError("truncated or oversized DSIC container")
+        containers.append({"offset": off, "bytes": size, "first": first, "tiles": B, "shape_y": [B, My, Hy, Wy],
+                           "shape_z": [B, Nz, Hz, Wz]})
+        off += size
+    if off != src.size:
+        raise ValueError(f"DSICI stream: {src.size - off} trailing bytes")
+    ix.update(grid=g, tiles=tiles, containers=containers, stream_bytes=src.size, index_bytes=src.bytes_read)
+    return ix
+
+
+def stream_index(src) -> dict:
+    """Where every tile of a DSICI stream lies, from its heads alone (pure Python).  src: bytes / bytearray /
+    memoryview, or a binary file object with seek and read.  Only the 60-byte header and, per batch, the 8-byte
+    length, the 38-byte DSIC2 header and the 24-byte records are read; the strings are skipped.  Returns the header
+    fields of unpack_image_stream (no "blobs") and
+      grid         tile_grid's dict for H, W, th, tw
+      tiles        per tile t (row-major, as the grid numbers them): k (batch), b (slot in it), min_y, max_y, min_z,
+                   max_z, z_off, z_len, y_off, y_len (absolute byte offsets and lengths of its two strings)
+      containers   per batch: offset, bytes, first (tile), tiles, shape_y, shape_z
+      stream_bytes, index_bytes (what this call read).
+    ValueError as unpack_image_stream, entropy.unpack_container and decompress_image raise it: wrong magic or version,
+    DSIC1 container, truncated stream or container, trailing bytes, batches that do not match the grid, latents that
+    do not match the tile size, a container whose numerics tag is not the stream's."""
+    return _index_of(_Source(src))
+
+
+def window_tiles(index_or_grid, y0, x0, h, w) -> list:
+    """The tiles whose owned rectangle, clipped to H x W, meets the window rows [y0, y0+h) x columns [x0, x0+w),
+    ascending (pure Python).  Owned ranges partition each axis, so these are tile rows y0 // th ... (y0+h-1) // th
+    and the columns likewise.  ValueError for an empty window or one that leaves the image."""
+    g = index_or_grid.get("grid", index_or_grid)
+    y0, x0, h, w = int(y0), int(x0), int(h), int(w)
+    if y0 < 0 or x0 < 0 or h < 1 or w < 1 or y0 + h > g["H"] or x0 + w > g["W"]:
+        raise ValueError(f"window {h}x{w} at ({y0}, {x0}) is empty or outside the {g['H']}x{g['W']} image")
+    rows = range(y0 // g["th"], (y0 + h - 1) // g["th"] + 1)
+    cols = range(x0 // g["tw"], (x0 + w - 1) // g["tw"] + 1)
+    return [i * g["nx"] + j for i in rows for j in cols]
+
+
+def tile_spans(index, tiles) -> list:
+    """Byte ranges (offset, length) of the stream that hold the strings of the given tiles: ascending, ranges that
+    touch merged into one, empty strings dropped (pure Python)."""
+    parts = []
+    for t in tiles:
+        r = index["tiles"][t]
+        if r["z_len"]:
+            parts.append((r["z_off"], r["z_len"]))
+        if r["y_len"]:
+            parts.append((r["y_off"], r["y_len"]))
+    parts.sort()
+    spans = []
+    for off, n in parts:
+        if spans and spans[-1][0] + spans[-1][1] >= off + n:               # a tile named twice
+            continue
+        if spans and spans[-1][0] + spans[-1][1] == off:
+            spans[-1][1] += n
+        else:
+            spans.append([off, n])
+    return [tuple(s) for s in spans]
+
+
+def _select_batch(index, tiles, spans):
+    """One int64 control block for a dense decode batch, which travels behind the strings in their copy: desc [n][4]
+    (z offset, z length, y offset, y length inside the back-to-back spans), then meta int32 [n][4] (ymin, Ly, zmin,
+    Lz), then the tile numbers int32 [n].  Returns (block, meta as numpy)."""
+    import bisect
+    import numpy as np
+    n = len(tiles)
+    starts = [s[0] for s in spans]
+    base, acc = [], 0
+    for _, length in spans:
+        base.append(acc)
+        acc += length
+
+    def inside(off, length):
+        if length == 0:
+            return 0
+        i = bisect.bisect_right(starts, off) - 1
+        return base[i] + off - starts[i]
+
+    rows, metas = [], []
+    for t in tiles:
+        r = index["tiles"][t]
+        rows.append((inside(r["z_off"], r["z_len"]), r["z_len"], inside(r["y_off"], r["y_len"]), r["y_len"]))
+        metas.append((r["min_y"], r["max_y"] - r["min_y"] + 1, r["min_z"], r["max_z"] - r["min_z"] + 1))
+    block = np.zeros(6 * n + (n + 1) // 2, dtype=np.int64)
+    block[:4 * n] = np.array(rows, dtype=np.int64).ravel()
+    meta = block[4 * n:6 * n].view(np.int32).reshape(n, 4)
+    meta[:] = np.array(metas, dtype=np.int32)
+    block[6 * n:].view(np.int32)[:n] = tiles
+    return block, meta
+
+
+@torch.no_grad()
+def decompress_region(model, src, y0, x0, h, w, out=None, batch=64, stats=None):
+    """The window rows [y0, y0+h) x columns [x0, x0+w) of a DSICI stream, decoded from only the tiles that own its
+    pixels: uint8 [h,w,C] or float32 [C,h,w] on the model's device, the same bytes decompress_image(...) gives there
+    (out as in decompress_image).  src: the stream as bytes, or a binary file object, of which only the heads
+    (stream_index) and the selected tiles' strings (tile_spans) are read.  The selected tiles are decoded in dense
+    batches of at most `batch`, in ascending tile order, whatever containers they come from; each batch is one
+    upload and is stitched into the window as soon as it is decoded.  stats (a dict) receives tiles, decode_batches,
+    bytes_read and bytes_uploaded (the padded string bytes; 52 bytes of descriptors per tile travel beside them)."""
+    if out not in (None, "u8", "f32"):
+        raise ValueError(f"decompress_region: out={out!r} (None, 'u8' or 'f32')")
+    batch = int(batch)
+    if batch < 1:
+        raise ValueError(f"decompress_region: batch={batch}")
+    source = _Source(src)
+    ix = _index_of(source)
+    _refuse_foreign(model, ix, "decompress_region")
+    tiles = window_tiles(ix, y0, x0, h, w)
+    y0, x0, h, w = int(y0), int(x0), int(h), int(w)
+    H, W, C, th, tw = ix["H"], ix["W"], ix["C"], ix["th"], ix["tw"]
+    kind = {None: ix["kind"], "u8": KIND_U8_HWC, "f32": KIND_F32_CHW}[out]
+    dev = next(model.parameters()).device
+    L = _lib.load()
+    img, suffix = _out_image(kind, C, h, w, dev, "decompress_region")
+    fn, what = getattr(L, "dsic_tile_stitch_window_" + suffix), "tile_stitch_window_" + suffix
+    _, N, Hz, Wz = ix["containers"][0]["shape_z"]
+    uploaded = decode_batches = 0
+    for first in range(0, len(tiles), batch):
+        sel = tiles[first:first + batch]
+        n = len(sel)
+        spans = tile_spans(ix, sel)
+        block, meta_np = _select_batch(ix, sel, spans)
+        d_blob, blob_bytes, d_block = entropy._upload_padded([source.read_at(off, length) for off, length in spans],
+                                                             dev, tail=block)
+        d_block = d_block.view(torch.int64)
+        desc, meta = d_block[:4 * n], d_block[4 * n:6 * n].view(torch.int32).view(n, 4)
+        ids = d_block[6 * n:].view(torch.int32)
+        zmax, ymax = int(block[1:4 * n:4].max()), int(block[3:4 * n:4].max())
+        # custom_decompress's strides (entropy._upload_strings), as decompress_container's
+        zstride, ystride = max(4, (zmax + 3) // 4 * 4), max(4, (ymax + 3) // 4 * 4)
+        zbuf = torch.empty(n * zstride, dtype=torch.uint8, device=dev)
+        ybuf = torch.empty(n * ystride, dtype=torch.uint8, device=dev)
+        lengths = torch.empty((n, 2), dtype=torch.int32, device=dev)
+        _lib.check(L.dsic_strings_scatter_select(_p(d_blob), blob_bytes, _p(desc), n, max(zmax, ymax), _p(zbuf),
+                                                 zstride, _p(ybuf), ystride, _p(lengths), _stream()),
+                   "strings_scatter_select")
+        x_hat = entropy._decode_batch(model, [n, ix["M"], th // 16, tw // 16], [n, N, Hz, Wz], meta,
+                                      entropy._default_lmax(model, meta_np), (zbuf, zstride, lengths, 2, 0),
+                                      (ybuf, ystride, lengths, 2, 1), "decompress_region").contiguous()
+        _lib.check(fn(_p(x_hat), _p(ids), n, _p(img), H, W, C, th, tw, y0, x0, h, w, _stream()), what)
+        uploaded += entropy._padded_bytes(blob_bytes)
+        decode_batches += 1
+    if stats is not None:
+        stats.update(tiles=tiles, decode_batches=decode_batches, bytes_read=source.bytes_read,
+                     bytes_uploaded=uploaded)
     return img

@@ -151,22 +151,41 @@ __device__ __forceinline__ Owned owned(const Grid& g, int t) {
           g.ox(j)};
 }
 
-// tiles [n][C][th][tw] -> clamp(0,1) into the float32 CHW image; blockIdx.z = channel
+// What a stitch call writes to: the window rows [y0,y1) x columns [x0,x1) of the image, stored as an image of its
+// own of (y1-y0) x (x1-x0) pixels.  The whole-image calls pass {0, H, 0, W}.
+struct Clip {
+  int y0, y1, x0, x1;
+};
+
+// The part of tile t that a stitch call writes: owned(t) cut to the window.  ids == nullptr: the tiles of the call
+// are first, first+1, ...; otherwise tile blockIdx.y is ids[blockIdx.y], and a number outside the grid owns nothing.
+__device__ __forceinline__ bool stitch_rect(const Grid& g, const int* ids, int first, const Clip& w, Owned* o) {
+  const int t = ids ? ids[blockIdx.y] : first + blockIdx.y;
+  if (t < 0 || t >= g.ny * g.nx) return false;
+  *o = owned(g, t);
+  o->y0 = max(o->y0, w.y0), o->y1 = min(o->y1, w.y1);
+  o->x0 = max(o->x0, w.x0), o->x1 = min(o->x1, w.x1);
+  return o->y0 < o->y1 && o->x0 < o->x1;
+}
+
+// tiles [n][C][th][tw] -> clamp(0,1) into the float32 CHW window image; blockIdx.z = channel
 __global__ __launch_bounds__(256) void stitch_f32_kernel(const float* __restrict__ tiles, float* __restrict__ img,
-                                                         Grid g, int first) {
-  const int t = first + blockIdx.y, c = blockIdx.z, C = gridDim.z;
-  const Owned o = owned(g, t);
+                                                         Grid g, int first, const int* __restrict__ ids, Clip w) {
+  const int c = blockIdx.z, C = gridDim.z;
+  Owned o;
+  if (!stitch_rect(g, ids, first, w, &o)) return;
   const int ya = o.y0 + blockIdx.x * kTileRows;
   const int rows = min(kTileRows, o.y1 - ya);
   if (rows <= 0) return;
   const float* src = tiles + ((size_t)blockIdx.y * C + c) * g.th * g.tw;
   // 4-float chunks aligned in the image (its base is 16-byte aligned): chunk q covers elements [4q, 4q+4)
-  const int64_t plane = (int64_t)c * g.H * g.W;
+  const int wW = w.x1 - w.x0;
+  const int64_t plane = (int64_t)c * (w.y1 - w.y0) * wW;
   const int cpr = (o.x1 - o.x0) / 4 + 2;  // chunks a row segment can touch
   for (int i = threadIdx.x; i < rows * cpr; i += blockDim.x) {
     const int r = i / cpr, k = i - r * cpr;
     const int y = ya + r;
-    const int64_t e0 = plane + (int64_t)y * g.W + o.x0, e1 = e0 + (o.x1 - o.x0);
+    const int64_t e0 = plane + (int64_t)(y - w.y0) * wW + (o.x0 - w.x0), e1 = e0 + (o.x1 - o.x0);
     const int64_t q0 = ((e0 >> 2) + k) << 2;
     if (q0 >= e1) continue;
     const float* srow = src + (size_t)(y - o.oy) * g.tw + (o.x0 - o.ox);  // element e of the image: srow[e - e0]
@@ -179,22 +198,24 @@ __global__ __launch_bounds__(256) void stitch_f32_kernel(const float* __restrict
   }
 }
 
-// tiles [n][C][th][tw] -> (uint8)(clamp(x,0,1) * 255) into the uint8 HWC image
+// tiles [n][C][th][tw] -> (uint8)(clamp(x,0,1) * 255) into the uint8 HWC window image
 __global__ __launch_bounds__(256) void stitch_u8_kernel(const float* __restrict__ tiles, uint8_t* __restrict__ img,
-                                                        Grid g, int C, int first) {
-  const int t = first + blockIdx.y;
-  const Owned o = owned(g, t);
+                                                        Grid g, int C, int first, const int* __restrict__ ids,
+                                                        Clip w) {
+  Owned o;
+  if (!stitch_rect(g, ids, first, w, &o)) return;
   const int ya = o.y0 + blockIdx.x * kTileRows;
   const int rows = min(kTileRows, o.y1 - ya);
   if (rows <= 0) return;
   const float* src = tiles + (size_t)blockIdx.y * C * g.th * g.tw;
   const size_t cplane = (size_t)g.th * g.tw;
+  const int wW = w.x1 - w.x0;
   const int seg = (o.x1 - o.x0) * C;
   const int cpr = seg / 16 + 2;  // 16-byte chunks a row segment can touch
   for (int i = threadIdx.x; i < rows * cpr; i += blockDim.x) {
     const int r = i / cpr, k = i - r * cpr;
     const int y = ya + r;
-    const int64_t b0 = ((int64_t)y * g.W + o.x0) * C, b1 = b0 + seg;
+    const int64_t b0 = ((int64_t)(y - w.y0) * wW + (o.x0 - w.x0)) * C, b1 = b0 + seg;
     const int64_t q0 = ((b0 >> 4) + k) << 4;
     if (q0 >= b1) continue;
     const int64_t lo = max(q0, b0), hi = min(q0 + 16, b1);
@@ -327,6 +348,24 @@ __global__ __launch_bounds__(256) void scatter_strings_kernel(const uint8_t* __r
   copy_bytes((which ? ybuf : zbuf) + (size_t)b * stride, blob + off, n, blockIdx.x, gridDim.x);
 }
 
+// The same for strings picked from several containers: blob holds the selected byte spans back to back, desc
+// [n][4] = (z offset, z length, y offset, y length) inside it.  blockIdx.y = string s (tile s/2 of the batch, z if
+// even, y if odd).  A descriptor that points outside the blob or past the row moves fewer bytes, never other ones.
+__global__ __launch_bounds__(256) void scatter_select_kernel(const uint8_t* __restrict__ blob, int64_t blob_bytes,
+                                                             const long long* __restrict__ desc,
+                                                             uint8_t* __restrict__ zbuf, int64_t zstride,
+                                                             uint8_t* __restrict__ ybuf, int64_t ystride,
+                                                             int* __restrict__ lengths) {
+  const int s = blockIdx.y, b = s >> 1, which = s & 1;
+  const int64_t stride = which ? ystride : zstride;
+  const int64_t off = desc[4 * b + 2 * which], len = desc[4 * b + 2 * which + 1];
+  int64_t n = len < 0 ? 0 : (len > stride ? stride : len);
+  if (off < 0 || off > blob_bytes) n = 0;
+  else if (n > blob_bytes - off) n = blob_bytes - off;
+  if (blockIdx.x == 0 && threadIdx.x == 0) lengths[s] = (int)n;
+  copy_bytes((which ? ybuf : zbuf) + (size_t)b * stride, blob + off, n, blockIdx.x, gridDim.x);
+}
+
 static int string_parts(int64_t max_len) {
   const int64_t p = (max_len + 16 * 256 - 1) / (16 * 256);
   return (int)(p < 1 ? 1 : (p > 8 ? 8 : p));
@@ -381,7 +420,7 @@ extern "C" int dsic_tile_stitch_f32(const float* tiles, float* img_chw, int H, i
   DSIC_TILE_ARGS("tile_stitch_f32");
   DSIC_REQUIRE(((uintptr_t)img_chw & 15) == 0, "tile_stitch_f32: image must be 16-byte aligned");
   hipLaunchKernelGGL(stitch_f32_kernel, dim3(grid.x, grid.y, C), dim3(256), 0, (hipStream_t)stream, tiles, img_chw,
-                     g, first_tile);
+                     g, first_tile, (const int*)nullptr, Clip{0, H, 0, W});
   return check_launch("tile_stitch_f32");
 }
 
@@ -391,8 +430,42 @@ extern "C" int dsic_tile_stitch_u8(const float* tiles, uint8_t* img_hwc, int H, 
   DSIC_REQUIRE(C == 3 || C == 4, "tile_stitch_u8: C=%d must be 3 or 4", C);
   DSIC_TILE_ARGS("tile_stitch_u8");
   DSIC_REQUIRE(((uintptr_t)img_hwc & 15) == 0, "tile_stitch_u8: image must be 16-byte aligned");
-  hipLaunchKernelGGL(stitch_u8_kernel, grid, dim3(256), 0, (hipStream_t)stream, tiles, img_hwc, g, C, first_tile);
+  hipLaunchKernelGGL(stitch_u8_kernel, grid, dim3(256), 0, (hipStream_t)stream, tiles, img_hwc, g, C, first_tile,
+                     (const int*)nullptr, Clip{0, H, 0, W});
   return check_launch("tile_stitch_u8");
+}
+
+#define DSIC_WINDOW_ARGS(what)                                                                                \
+  const char* ge = grid_error(H, W, th, tw);                                                                  \
+  DSIC_REQUIRE(!ge, what ": %s (H=%d W=%d th=%d tw=%d)", ge ? ge : "", H, W, th, tw);                         \
+  const Grid g = make_grid(H, W, th, tw);                                                                     \
+  DSIC_REQUIRE(wy0 >= 0 && wx0 >= 0 && wh >= 1 && ww >= 1 && (int64_t)wy0 + wh <= H && (int64_t)wx0 + ww <= W, \
+               what ": window %dx%d at (%d, %d) outside the %dx%d image", wh, ww, wy0, wx0, H, W);           \
+  DSIC_REQUIRE(n_tiles >= 1 && n_tiles <= 65535, what ": n=%d tiles per call (1..65535)", n_tiles);           \
+  const Clip clip = {wy0, wy0 + wh, wx0, wx0 + ww};                                                           \
+  const dim3 grid(g.th / kTileRows, n_tiles, 1)
+
+extern "C" int dsic_tile_stitch_window_f32(const float* tiles, const int* tile_ids, int n_tiles, float* out, int H,
+                                           int W, int C, int th, int tw, int wy0, int wx0, int wh, int ww,
+                                           void* stream) {
+  DSIC_REQUIRE(tiles && tile_ids && out, "tile_stitch_window_f32: null pointer");
+  DSIC_REQUIRE(C >= 1 && C <= 8, "tile_stitch_window_f32: C=%d must be in 1..8", C);
+  DSIC_WINDOW_ARGS("tile_stitch_window_f32");
+  DSIC_REQUIRE(((uintptr_t)out & 15) == 0, "tile_stitch_window_f32: out must be 16-byte aligned");
+  hipLaunchKernelGGL(stitch_f32_kernel, dim3(grid.x, grid.y, C), dim3(256), 0, (hipStream_t)stream, tiles, out, g, 0,
+                     tile_ids, clip);
+  return check_launch("tile_stitch_window_f32");
+}
+
+extern "C" int dsic_tile_stitch_window_u8(const float* tiles, const int* tile_ids, int n_tiles, uint8_t* out, int H,
+                                          int W, int C, int th, int tw, int wy0, int wx0, int wh, int ww,
+                                          void* stream) {
+  DSIC_REQUIRE(tiles && tile_ids && out, "tile_stitch_window_u8: null pointer");
+  DSIC_REQUIRE(C == 3 || C == 4, "tile_stitch_window_u8: C=%d must be 3 or 4", C);
+  DSIC_WINDOW_ARGS("tile_stitch_window_u8");
+  DSIC_REQUIRE(((uintptr_t)out & 15) == 0, "tile_stitch_window_u8: out must be 16-byte aligned");
+  hipLaunchKernelGGL(stitch_u8_kernel, grid, dim3(256), 0, (hipStream_t)stream, tiles, out, g, C, 0, tile_ids, clip);
+  return check_launch("tile_stitch_window_u8");
 }
 
 extern "C" int dsic_container_pack(const uint8_t* bytes, int64_t cap_z, int64_t cap_y, const int* lengths,
@@ -431,4 +504,18 @@ extern "C" int dsic_container_scatter(const uint8_t* blob, int64_t blob_bytes, i
   hipLaunchKernelGGL(scatter_strings_kernel, dim3(string_parts(max_len), 2 * B), dim3(256), 0, st, blob, blob_bytes,
                      B, zbuf, zstride, ybuf, ystride, (const int*)lengths, (const long long*)ws);
   return check_launch("container_scatter(strings)");
+}
+
+extern "C" int dsic_strings_scatter_select(const uint8_t* blob, int64_t blob_bytes, const int64_t* desc, int n,
+                                           int64_t max_len, uint8_t* zbuf, int64_t zstride, uint8_t* ybuf,
+                                           int64_t ystride, int* lengths, void* stream) {
+  DSIC_REQUIRE(blob && desc && zbuf && ybuf && lengths, "strings_scatter_select: null pointer");
+  DSIC_REQUIRE(n >= 1 && n <= 32767, "strings_scatter_select: n=%d tiles per call (1..32767)", n);
+  DSIC_REQUIRE(blob_bytes >= 0 && max_len >= 0, "strings_scatter_select: negative size");
+  DSIC_REQUIRE(zstride > 0 && ystride > 0 && zstride % 4 == 0 && ystride % 4 == 0,
+               "strings_scatter_select: strides must be positive multiples of 4");
+  DSIC_REQUIRE(((uintptr_t)blob & 15) == 0, "strings_scatter_select: blob must be 16-byte aligned");
+  hipLaunchKernelGGL(scatter_select_kernel, dim3(string_parts(max_len), 2 * n), dim3(256), 0, (hipStream_t)stream,
+                     blob, blob_bytes, (const long long*)desc, zbuf, zstride, ybuf, ystride, lengths);
+  return check_launch("strings_scatter_select");
 }

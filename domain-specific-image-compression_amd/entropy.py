@@ -501,6 +501,30 @@ def _container_records(blob):
     return tag, [B, My, Hy, Wy], [B, Nz, Hz, Wz], rec
 
 
+def _padded_bytes(n):
+    """Size of the device copy of n stream bytes: whole 16-byte chunks and at least one spare, so the 16-byte reads of
+    the string movers (image_codec.hip load16_any) stay inside the allocation."""
+    return (n + 31) // 16 * 16
+
+
+def _upload_padded(parts, dev, tail=None):
+    """Byte strings, back to back, in one host buffer and one copy -> (device uint8 [_padded_bytes(total)], total).
+    tail (a numpy array) rides in the same copy, after the padding (16-byte aligned): -> (..., total, its device
+    copy as uint8)."""
+    total = sum(len(p) for p in parts)
+    padded = _padded_bytes(total)
+    host = torch.empty(padded + (tail.nbytes if tail is not None else 0), dtype=torch.uint8)
+    a, off = host.numpy(), 0
+    for p in parts:
+        a[off:off + len(p)] = np.frombuffer(p, dtype=np.uint8)
+        off += len(p)
+    if tail is None:
+        return host.to(dev), total
+    a[padded:] = tail.view(np.uint8).ravel()
+    d = host.to(dev)
+    return d[:padded], total, d[padded:]
+
+
 def _decompress_container_raw(model, blob, Lmax=None, what="decompress_container"):
     dev = next(model.parameters()).device
     tag, shape_y, shape_z, rec = _container_records(blob)
@@ -512,9 +536,7 @@ def _decompress_container_raw(model, blob, Lmax=None, what="decompress_container
     # custom_decompress's strides (_upload_strings); the device copy of the blob is padded to whole 16-byte chunks
     zstride = max(4, (int(rec[:, 4].max()) + 3) // 4 * 4)
     ystride = max(4, (int(rec[:, 5].max()) + 3) // 4 * 4)
-    host = torch.empty((len(blob) + 31) // 16 * 16, dtype=torch.uint8)
-    host.numpy()[:len(blob)] = np.frombuffer(blob, dtype=np.uint8)
-    d_blob = host.to(dev)
+    d_blob, _ = _upload_padded([blob], dev)
     zbuf = torch.empty(B * zstride, dtype=torch.uint8, device=dev)
     ybuf = torch.empty(B * ystride, dtype=torch.uint8, device=dev)
     lengths = torch.empty((B, 2), dtype=torch.int32, device=dev)

@@ -96,7 +96,10 @@ SIGNATURES = {
     "dsic_container_pack": (c_int, [_P, c_int64, c_int64, _P, _P, _P, c_int, ctypes.c_uint32, c_int, c_int, c_int,
                                     c_int, c_int, c_int, _P, _P, _P]),
     "dsic_container_scatter": (c_int, [_P, c_int64, c_int, c_int64, _P, c_int64, _P, c_int64, _P, _P, _P, _P]),
-    "dsic_stream_create_masked": (c_int, [_P, c_int, _P]),
+    "dsic_strings_scatter_select": (c_int, [_P, c_int64, _P, c_int, c_int64, _P, c_int64, _P, c_int64, _P, _P]),
+    "dsic_tile_stitch_window_f32": (c_int, [_P, _P, c_int, _P] + [c_int] * 9 + [_P]),
+    "dsic_tile_stitch_window_u8": (c_int, [_P, _P, c_int, _P] + [c_int] * 9 + [_P]),
+    "dsic_stream_create_masked":(c_int, [_P, c_int, _P]),
     "dsic_stream_destroy": (c_int, [_P]),
     "dsic_range_decode": (c_int, [_P, c_int64, _P, c_int, c_int, _P, c_int, _P, c_int, c_int, c_int,
                                   c_int, c_int, _P, _P, _P]),

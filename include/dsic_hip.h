@@ -428,6 +428,33 @@ int dsic_container_scatter(const uint8_t* blob, int64_t blob_bytes, int B, int64
                            uint8_t* zbuf, int64_t zstride, uint8_t* ybuf, int64_t ystride,
                            int* lengths, int* meta, int64_t* workspace, void* stream);
 
+/* ---- region decode (codec.decompress_region): a window of an image from only its tiles ----
+ * The strings of n tiles picked from any containers of a stream, for one decode batch.  blob
+ * (on the device, 16-byte aligned, its allocation a whole number of 16-byte chunks) holds the
+ * selected byte spans back to back; desc is device int64 [n][4]: z offset, z length, y offset,
+ * y length inside blob (any alignment).  String i goes to zbuf + i*zstride / ybuf + i*ystride
+ * and lengths [n][2] (z, y) is written as dsic_range_decode takes it (lstride 2).  A length is
+ * cut to its stride and to blob_bytes, and an offset outside the blob moves nothing, so a
+ * forged descriptor cannot move a copy out of bounds.  max_len = the longest string;
+ * n in 1..32767.  meta [n][4] comes from the host, which has the records. */
+int dsic_strings_scatter_select(const uint8_t* blob, int64_t blob_bytes, const int64_t* desc,
+                                int n, int64_t max_len, uint8_t* zbuf, int64_t zstride,
+                                uint8_t* ybuf, int64_t ystride, int* lengths, void* stream);
+/* Stitch into a window image.  tiles float32 [n][C][th][tw]; tile_ids device int32 [n], the
+ * grid number of each (H, W, th, tw as for the calls above).  out is the window rows
+ * [wy0, wy0+wh) x columns [wx0, wx0+ww) of the image as an image of its own: float32
+ * [C][wh][ww] (C in 1..8) or uint8 [wh][ww][C] (C 3 or 4), 16-byte aligned.  Tile t writes the
+ * pixels it owns that lie in the window, with the values of the whole-image stitch calls bit
+ * for bit; every window pixel is written once when tile_ids holds every tile that meets the
+ * window.  A number outside the grid, or a tile that does not meet the window, writes
+ * nothing.  n in 1..65535. */
+int dsic_tile_stitch_window_f32(const float* tiles, const int* tile_ids, int n, float* out,
+                                int H, int W, int C, int th, int tw, int wy0, int wx0, int wh,
+                                int ww, void* stream);
+int dsic_tile_stitch_window_u8(const float* tiles, const int* tile_ids, int n, uint8_t* out,
+                               int H, int W, int C, int th, int tw, int wy0, int wx0, int wh,
+                               int ww, void* stream);
+
 /* HIP stream limited to the CUs whose bit is set in mask_host[words] (bit i of
  * word i/32 = CU i).  Used to give the range coder its own few CUs beside the
  * conv kernels; there is no reference counterpart (the reference is

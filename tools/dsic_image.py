@@ -1,7 +1,11 @@
 """Compress an image of any size to one DSICI stream, or decompress a stream back to an image.
 
     python tools/dsic_image.py compress   --weights CKPT.pt IN.png  OUT.dsic [--tile 256] [--batch 64]
-    python tools/dsic_image.py decompress --weights CKPT.pt IN.dsic OUT.png [--out u8|f32]
+    python tools/dsic_image.py decompress --weights CKPT.pt IN.dsic OUT.png [--out u8|f32] [--region Y0,X0,H,W]
+    python tools/dsic_image.py info       IN.dsic
+
+--region decodes only the tiles that own the window's pixels and reads only their bytes of the file; info prints the
+geometry, the tile grid and the bytes of every batch from the stream's heads, without a model or a GPU.
 
 The state dict is loaded plain or from under "model" (code/modelv2/eval_selfcontained_entropy.py:130-134); the model's
 N, M, input channels and spatial_params are read from its shapes.  Images are PNG through PIL when PIL is importable
@@ -69,20 +73,54 @@ def write_image(path, img):
     return path
 
 
+def print_info(ix):
+    """stream_index's dict as text: geometry, tile grid, and bytes / bpp of every batch (bpp over the pixels its tiles
+    own)."""
+    g = ix["grid"]
+    kind = {0: "uint8 HWC", 1: "float32 CHW"}.get(ix["kind"], f"kind {ix['kind']}")
+    print(f"[dsic_image] {ix['H']}x{ix['W']}x{ix['C']} {kind}, {ix['stream_bytes']} bytes, "
+          f"{8.0 * ix['stream_bytes'] / (ix['H'] * ix['W']):.4f} bpp, numerics tag {ix['numerics']:#x}")
+    print(f"[dsic_image] model N={ix['N']} M={ix['M']} in_ch={ix['in_ch']} spatial_params={ix['spatial_params']}")
+    print(f"[dsic_image] tile grid {g['ny']}x{g['nx']} = {g['n']} tiles of {g['th']}x{g['tw']}, "
+          f"{ix['batches']} batch(es) of up to {ix['batch']}; heads {ix['index_bytes']} bytes")
+    for k, c in enumerate(ix["containers"]):
+        pixels = 0
+        for t in range(c["first"], c["first"] + c["tiles"]):
+            (a, b), (l, r) = g["own_y"][t // g["nx"]], g["own_x"][t % g["nx"]]
+            pixels += max(0, min(b, g["H"]) - a) * max(0, min(r, g["W"]) - l)
+        print(f"[dsic_image]   batch {k}: tiles {c['first']}..{c['first'] + c['tiles'] - 1}, {c['bytes']} bytes, "
+              f"{8.0 * c['bytes'] / pixels:.4f} bpp over {pixels} pixels")
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser(description=__doc__.splitlines()[0])
-    ap.add_argument("mode", choices=("compress", "decompress"))
+    ap.add_argument("mode", choices=("compress", "decompress", "info"))
     ap.add_argument("src")
-    ap.add_argument("dst")
-    ap.add_argument("--weights", required=True)
+    ap.add_argument("dst", nargs="?")
+    ap.add_argument("--weights")
     ap.add_argument("--tile", type=int, default=256)
     ap.add_argument("--batch", type=int, default=64)
     ap.add_argument("--tail", type=int, default=10)
     ap.add_argument("--out", choices=("u8", "f32"), default=None, help="decoded kind (default: the encoder's input's)")
+    ap.add_argument("--region", default=None, metavar="Y0,X0,H,W", help="decompress: only this window of the image")
     ap.add_argument("--min-nu", type=float, default=2.0)
     ap.add_argument("--max-nu", type=float, default=100.0)
     a = ap.parse_args(argv)
     from dsic_amd import codec
+    if a.mode == "info":
+        with open(a.src, "rb") as f:
+            print_info(codec.stream_index(f))
+        return
+    if a.dst is None or a.weights is None:
+        ap.error(f"{a.mode} needs a destination and --weights")
+    region = None
+    if a.region is not None:
+        try:
+            region = [int(v) for v in a.region.split(",")]
+        except ValueError:
+            region = []
+        if a.mode != "decompress" or len(region) != 4:
+            ap.error("--region Y0,X0,H,W (four integers) goes with decompress")
     model = load_model(a.weights, a.min_nu, a.max_nu)
     if a.mode == "compress":
         img = read_image(a.src, codec._model_shape(model)[2])
@@ -92,6 +130,13 @@ def main(argv=None):
         h = codec.unpack_image_stream(stream)
         print(f"[dsic_image] {h['H']}x{h['W']}x{h['C']} -> {len(stream)} bytes, {codec.image_bpp(stream):.4f} bpp, "
               f"{h['batches']} batch(es) of {h['th']}x{h['tw']} tiles")
+    elif region is not None:
+        stats = {}
+        with open(a.src, "rb") as f:
+            img = codec.decompress_region(model, f, *region, out=a.out, batch=a.batch, stats=stats)
+        path = write_image(a.dst, img)
+        print(f"[dsic_image] window {region[2]}x{region[3]} at ({region[0]}, {region[1]}): {len(stats['tiles'])} "
+              f"tile(s), {stats['bytes_read']} of {os.path.getsize(a.src)} bytes read -> {path}")
     else:
         with open(a.src, "rb") as f:
             stream = f.read()

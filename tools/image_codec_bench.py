@@ -6,6 +6,12 @@ device path  compress_image (gather on the device, compress_to_container per bat
              (decompress_container per batch, stitched into a uint8 image);
 host path    the same tiles through custom_compress + pack_container, and unpack_container + custom_decompress.
 Every figure is the best of --reps full passes over the scene after one warm-up pass, wall clock, synchronised.
+
+    python tools/image_codec_bench.py --region [--json profiles/region_decode_bench.json]
+
+--region  decompress_region of the same stream for an aligned one-tile window, an unaligned 2 x 2-tile-sized window
+          (9 tiles), an unaligned half-scene window and the whole image, beside decompress_image before and after
+          them in the same run (the two readings show the run-to-run spread).  Records, not bars.
 """
 from __future__ import annotations
 
@@ -20,17 +26,57 @@ if ROOT not in sys.path:
     sys.path.insert(0, ROOT)
 
 
-def _best(fn, reps):
+def _times(fn, reps):
     import torch
     fn()
     torch.cuda.synchronize()
-    best = float("inf")
+    out = []
     for _ in range(reps):
         t0 = time.perf_counter()
         fn()
         torch.cuda.synchronize()
-        best = min(best, time.perf_counter() - t0)
-    return best
+        out.append(time.perf_counter() - t0)
+    return out
+
+
+def _best(fn, reps):
+    return min(_times(fn, reps))
+
+
+def region_records(model, stream, a):
+    """decompress_region on four windows of the scene beside decompress_image, one run."""
+    import torch
+    from dsic_amd import codec
+    t, size = a.tile, a.size
+    off = 4 * t - 24                                       # not a multiple of 16: ragged row ends on every tile
+    windows = [("tile_aligned", (4 * t, 4 * t, t, t)), ("unaligned_2x2", (off, off, 2 * t, 2 * t)),
+               ("unaligned_half", (off, off, size // 2, size // 2)), ("whole_image", (0, 0, size, size))]
+
+    def ms(ts):
+        return [round(1e3 * v, 3) for v in ts]
+
+    full = codec.decompress_image(model, stream)
+    before = _times(lambda: codec.decompress_image(model, stream), a.reps)
+    recs = {}
+    for name, win in windows:
+        stats = {}
+        got = codec.decompress_region(model, stream, *win, batch=a.batch, stats=stats)
+        y0, x0, h, w = win
+        assert torch.equal(got, full[y0:y0 + h, x0:x0 + w]), f"{name}: the window differs from the full decode"
+        ts = _times(lambda: codec.decompress_region(model, stream, *win, batch=a.batch), a.reps)
+        recs[name] = {"window_y0_x0_h_w": list(win), "ms": min(ms(ts)), "ms_all": ms(ts),
+                      "tiles_decoded": len(stats["tiles"]), "decode_batches": stats["decode_batches"],
+                      "bytes_uploaded": stats["bytes_uploaded"], "bytes_read": stats["bytes_read"]}
+    after = _times(lambda: codec.decompress_image(model, stream), a.reps)
+    best_full = min(before + after)
+    ix = codec.stream_index(stream)
+    return {"scene": f"{size}x{size}x3 uint8", "tiles": ix["grid"]["n"], "tile": t, "batch": a.batch,
+            "stream_bytes": len(stream), "reps": a.reps,
+            "decompress_image": {"ms": round(1e3 * best_full, 3), "ms_before": ms(before), "ms_after": ms(after),
+                                 "tiles_decoded": ix["grid"]["n"], "decode_batches": ix["batches"]},
+            "decompress_region": recs,
+            "whole_image_over_decompress_image": round(recs["whole_image"]["ms"] / (1e3 * best_full), 4),
+            "unaligned_2x2_over_decompress_image": round(recs["unaligned_2x2"]["ms"] / (1e3 * best_full), 4)}
 
 
 def main():
@@ -40,6 +86,7 @@ def main():
     ap.add_argument("--batch", type=int, default=64)
     ap.add_argument("--reps", type=int, default=3)
     ap.add_argument("--json", default=None)
+    ap.add_argument("--region", action="store_true", help="measure decompress_region windows instead")
     a = ap.parse_args()
 
     import numpy as np
@@ -61,6 +108,12 @@ def main():
     n = g["n"]
 
     stream = codec.compress_image(model, img, tile=a.tile, batch=a.batch)
+    if a.region:
+        res = region_records(model, stream, a)
+        print(json.dumps(res))
+        with open(a.json or os.path.join(ROOT, "profiles", "region_decode_bench.json"), "w") as f:
+            json.dump(res, f, indent=1)
+        return
     t_enc = _best(lambda: codec.compress_image(model, img, tile=a.tile, batch=a.batch), a.reps)
     t_dec = _best(lambda: codec.decompress_image(model, stream), a.reps)
 
