@@ -16,6 +16,7 @@ independently, as the reference's patch-trained model sees them; seams are not b
 Because tiles are independent and the DSIC2 heads hold every string's length, any window of a stream can be decoded
 from only the tiles that own its pixels: stream_index finds their bytes from the heads alone, decompress_region decodes
 them in dense batches and stitches them into the window, byte for byte the crop of decompress_image's result.
+decompress_image is the same decode (_decode_window) of the window (0, 0, H, W), one batch per container.
 """
 from __future__ import annotations
 
@@ -83,14 +84,43 @@ def pack_image_stream(header: dict, blobs) -> bytes:
     return b"".join([head] + [_LEN.pack(len(b)) + bytes(b) for b in blobs])
 
 
-def unpack_image_stream(stream) -> dict:
-    """stream -> header fields (version, numerics, H, W, C, kind, th, tw, N, M, in_ch, spatial_params, batch,
-    batches) and "blobs", the list of inner DSIC2 containers (pure Python).  ValueError on a wrong magic, a truncated
-    stream or trailing bytes."""
-    s = bytes(stream)
-    if len(s) < _HEAD.size:
-        raise ValueError("truncated DSICI stream" if s[:6] == MAGIC[:len(s)] else "not a DSICI image stream")
-    f = _HEAD.unpack_from(s, 0)
+class _Source:
+    """Random access to a stream held as bytes or behind a binary file object (seek + read); counts what it reads."""
+
+    def __init__(self, src):
+        if isinstance(src, (bytes, bytearray, memoryview)):
+            self.buf, self.f = memoryview(src).cast("B"), None
+            self.size = len(self.buf)
+        elif hasattr(src, "seek") and hasattr(src, "read"):
+            self.buf, self.f = None, src
+            self.size = src.seek(0, 2)
+            if self.size is None:                                          # a seek that returns nothing: ask tell
+                self.size = src.tell()
+        else:
+            raise TypeError(f"expected bytes or a binary file object with seek and read, got {type(src).__name__}")
+        self.bytes_read = 0
+
+    def read_at(self, off, n):
+        """Up to n bytes at off (fewer only at the end of the stream)."""
+        n = max(0, min(n, self.size - off))
+        if self.f is None:
+            out = self.buf[off:off + n]                                    # a view: copied once, into the upload
+        else:
+            self.f.seek(off)
+            out = self.f.read(n)
+            if len(out) != n:
+                raise ValueError("truncated DSICI stream")
+        self.bytes_read += len(out)
+        return out
+
+
+def _read_framing(src):
+    """The DSICI head and the length words of a _Source -> (header fields, (offset, bytes) of every batch); what
+    lies inside the batches is not read."""
+    head = src.read_at(0, _HEAD.size)
+    if len(head) < _HEAD.size:
+        raise ValueError("truncated DSICI stream" if head[:6] == MAGIC[:len(head)] else "not a DSICI image stream")
+    f = _HEAD.unpack(head)
     if f[0] != MAGIC:
         raise ValueError("not a DSICI image stream")
     keys = ("version", "numerics", "H", "W", "C", "kind", "th", "tw", "N", "M", "in_ch", "spatial_params", "batch",
@@ -98,19 +128,28 @@ def unpack_image_stream(stream) -> dict:
     h = dict(zip(keys, f[1:]))
     if h["version"] != VERSION:
         raise ValueError(f"DSICI stream version {h['version']}, this reader knows {VERSION}")
-    off, blobs = _HEAD.size, []
+    off, frames = _HEAD.size, []
     for _ in range(h["batches"]):
-        if off + _LEN.size > len(s):
+        if off + _LEN.size > src.size:
             raise ValueError("truncated DSICI stream")
-        (n,) = _LEN.unpack_from(s, off)
+        (size,) = _LEN.unpack(src.read_at(off, _LEN.size))
         off += _LEN.size
-        if off + n > len(s):
+        if off + size > src.size:
             raise ValueError("truncated DSICI stream")
-        blobs.append(s[off:off + n])
-        off += n
-    if off != len(s):
-        raise ValueError(f"DSICI stream: {len(s) - off} trailing bytes")
-    h["blobs"] = blobs
+        frames.append((off, size))
+        off += size
+    if off != src.size:
+        raise ValueError(f"DSICI stream: {src.size - off} trailing bytes")
+    return h, frames
+
+
+def unpack_image_stream(stream) -> dict:
+    """stream -> header fields (version, numerics, H, W, C, kind, th, tw, N, M, in_ch, spatial_params, batch,
+    batches) and "blobs", the list of inner DSIC2 containers (pure Python).  ValueError on a wrong magic, a truncated
+    stream or trailing bytes."""
+    s = bytes(stream)
+    h, frames = _read_framing(_Source(s))
+    h["blobs"] = [s[off:off + size] for off, size in frames]
     return h
 
 
@@ -204,123 +243,30 @@ def _out_image(kind, C, h, w, dev, what):
     return torch.empty((C, h, w), dtype=torch.float32, device=dev), "f32"
 
 
-@torch.no_grad()
-def decompress_image(model, stream, out=None):
-    """DSICI stream -> the image on the model's device: uint8 [H,W,C] ((uint8)(clamp(x,0,1)*255), truncating, as
-    torchvision's to_pil_image) or float32 [C,H,W] (clamp(x,0,1)); by default the kind of the encoder's input,
-    out="u8" / "f32" overrides it.  Each decoded batch is stitched straight into the image."""
-    h = unpack_image_stream(stream)
-    if out not in (None, "u8", "f32"):
-        raise ValueError(f"decompress_image: out={out!r} (None, 'u8' or 'f32')")
-    _refuse_foreign(model, h, "decompress_image")
-    g = _stream_grid(h)
-    H, W, C, th, tw = h["H"], h["W"], h["C"], h["th"], h["tw"]
-    kind = {None: h["kind"], "u8": KIND_U8_HWC, "f32": KIND_F32_CHW}[out]
-    dev = next(model.parameters()).device
-    L = _lib.load()
-    img, suffix = _out_image(kind, C, H, W, dev, "decompress_image")
-    fn, what = getattr(L, "dsic_tile_stitch_" + suffix), "tile_stitch_" + suffix
-    for k, blob in enumerate(h["blobs"]):
-        first = k * h["batch"]
-        n = min(h["batch"], g["n"] - first)
-        _, shape_y, _, _ = entropy._container_records(blob)
-        _check_batch_shape(k, shape_y, n, th, tw)
-        tiles = entropy._decompress_container_raw(model, blob, what="decompress_image").contiguous()
-        _lib.check(fn(_p(tiles), _p(img), H, W, C, th, tw, first, n, _stream()), what)
-    return img
-
-
-# ---- region decode: any window of an image stream from only its tiles --------------------------------------------
-_DSIC2_HEAD = struct.Struct("<6sI7I")      # magic, numerics tag, B, My, Hy, Wy, Nz, Hz, Wz  (entropy.pack_container)
-_DSIC2_REC = struct.Struct("<4i2I")        # min_y, max_y, min_z, max_z, len_z, len_y
-
-
-class _Source:
-    """Random access to a stream held as bytes or behind a binary file object (seek + read); counts what it reads."""
-
-    def __init__(self, src):
-        if isinstance(src, (bytes, bytearray, memoryview)):
-            self.buf, self.f = memoryview(src).cast("B"), None
-            self.size = len(self.buf)
-        elif hasattr(src, "seek") and hasattr(src, "read"):
-            self.buf, self.f = None, src
-            self.size = src.seek(0, 2)
-            if self.size is None:                                          # a seek that returns nothing: ask tell
-                self.size = src.tell()
-        else:
-            raise TypeError(f"expected bytes or a binary file object with seek and read, got {type(src).__name__}")
-        self.bytes_read = 0
-
-    def read_at(self, off, n):
-        """Up to n bytes at off (fewer only at the end of the stream)."""
-        n = max(0, min(n, self.size - off))
-        if self.f is None:
-            out = self.buf[off:off + n]                                    # a view: copied once, into the upload
-        else:
-            self.f.seek(off)
-            out = self.f.read(n)
-            if len(out) != n:
-                raise ValueError("truncated DSICI stream")
-        self.bytes_read += len(out)
-        return out
-
-
+# ---- decode: any window of an image stream from only its tiles; the whole image is the window (0, 0, H, W) ------
 def _index_of(src):
     """stream_index on an open _Source."""
-    head = src.read_at(0, _HEAD.size)
-    if len(head) < _HEAD.size:
-        raise ValueError("truncated DSICI stream" if head[:6] == MAGIC[:len(head)] else "not a DSICI image stream")
-    f = _HEAD.unpack(head)
-    if f[0] != MAGIC:
-        raise ValueError("not a DSICI image stream")
-    keys = ("version", "numerics", "H", "W", "C", "kind", "th", "tw", "N", "M", "in_ch", "spatial_params", "batch",
-            "batches")
-    ix = dict(zip(keys, f[1:]))
-    if ix["version"] != VERSION:
-        raise ValueError(f"DSICI stream version {ix['version']}, this reader knows {VERSION}")
+    ix, frames = _read_framing(src)
     g = _stream_grid(ix)
-    th, tw = ix["th"], ix["tw"]
-    off, tiles, containers = _HEAD.size, [], []
-    for k in range(ix["batches"]):
-        if off + _LEN.size > src.size:
-            raise ValueError("truncated DSICI stream")
-        (size,) = _LEN.unpack(src.read_at(off, _LEN.size))
-        off += _LEN.size
-        if off + size > src.size:
-            raise ValueError("truncated DSICI stream")
-        chead = src.read_at(off, min(size, _DSIC2_HEAD.size))
-        if chead[:6] == entropy._MAGIC_V1:
-            raise ValueError("DSIC1 container: written before the numerics tag existed (its coder tables may be the "
-                             "float64 ones of round 1); re-encode")
-        if len(chead) < _DSIC2_HEAD.size or chead[:6] != entropy._MAGIC:
-            raise ValueError("not a DSIC container")
-        _, tag, B, My, Hy, Wy, Nz, Hz, Wz = _DSIC2_HEAD.unpack(chead)
+    tiles, containers = [], []
+    for k, (off, size) in enumerate(frames):
+        tag, shape_y, shape_z, images = entropy.read_container_head(src.read_at, off, size)
         if tag != ix["numerics"]:
             raise ValueError(f"DSICI stream: batch {k} carries numerics tag {tag:#x}, the stream's is "
                              f"{ix['numerics']:#x}")
-        if B < 1 or size < _DSIC2_HEAD.size + _DSIC2_REC.size * B:
-            raise ValueError("truncated or oversized DSIC container")
         first = k * ix["batch"]
-        _check_batch_shape(k, [B, My, Hy, Wy], min(ix["batch"], g["n"] - first), th, tw)
-        if (My, Nz) != (ix["M"], ix["N"]):
-            raise ValueError(f"DSICI stream: batch {k} holds latents of {My} and {Nz} channels, the header says "
-                             f"{ix['M']} and {ix['N']}")
-        if containers and (Hz, Wz) != tuple(containers[0]["shape_z"][2:]):
-            raise ValueError(f"DSICI stream: batch {k} holds hyper-latents of {Hz}x{Wz}, batch 0 of "
+        _check_batch_shape(k, shape_y, min(ix["batch"], g["n"] - first), ix["th"], ix["tw"])
+        if (shape_y[1], shape_z[1]) != (ix["M"], ix["N"]):
+            raise ValueError(f"DSICI stream: batch {k} holds latents of {shape_y[1]} and {shape_z[1]} channels, the "
+                             f"header says {ix['M']} and {ix['N']}")
+        if containers and shape_z[2:] != containers[0]["shape_z"][2:]:
+            raise ValueError(f"DSICI stream: batch {k} holds hyper-latents of {shape_z[2]}x{shape_z[3]}, batch 0 of "
                              f"{containers[0]['shape_z'][2]}x{containers[0]['shape_z'][3]}")
-        recs = src.read_at(off + _DSIC2_HEAD.size, _DSIC2_REC.size * B)
-        pos = off + _DSIC2_HEAD.size + _DSIC2_REC.size * B
-        for b, (min_y, max_y, min_z, max_z, len_z, len_y) in enumerate(_DSIC2_REC.iter_unpack(recs)):
+        for b, (min_y, max_y, min_z, max_z, z_off, z_len, y_off, y_len) in enumerate(images):
             tiles.append({"k": k, "b": b, "min_y": min_y, "max_y": max_y, "min_z": min_z, "max_z": max_z,
-                          "z_off": pos, "z_len": len_z, "y_off": pos + len_z, "y_len": len_y})
-            pos += len_z + len_y
-        if pos != off + size:
-            raise ValueError("truncated or oversized DSIC container")
-        containers.append({"offset": off, "bytes": size, "first": first, "tiles": B, "shape_y": [B, My, Hy, Wy],
-                           "shape_z": [B, Nz, Hz, Wz]})
-        off += size
-    if off != src.size:
-        raise ValueError(f"DSICI stream: {src.size - off} trailing bytes")
+                          "z_off": z_off, "z_len": z_len, "y_off": y_off, "y_len": y_len})
+        containers.append({"offset": off, "bytes": size, "first": first, "tiles": len(images), "shape_y": shape_y,
+                           "shape_z": shape_z})
     ix.update(grid=g, tiles=tiles, containers=containers, stream_bytes=src.size, index_bytes=src.bytes_read)
     return ix
 
@@ -376,36 +322,53 @@ def tile_spans(index, tiles) -> list:
     return [tuple(s) for s in spans]
 
 
-def _select_batch(index, tiles, spans):
-    """One int64 control block for a dense decode batch, which travels behind the strings in their copy: desc [n][4]
-    (z offset, z length, y offset, y length inside the back-to-back spans), then meta int32 [n][4] (ymin, Ly, zmin,
-    Lz), then the tile numbers int32 [n].  Returns (block, meta as numpy)."""
-    import bisect
-    import numpy as np
-    n = len(tiles)
-    starts = [s[0] for s in spans]
-    base, acc = [], 0
-    for _, length in spans:
-        base.append(acc)
-        acc += length
+def _decode_window(model, src, window, out, batch, stats, what):
+    """decompress_region's work; window None = the whole image, batch None = the stream's tiles per container."""
+    if out not in (None, "u8", "f32"):
+        raise ValueError(f"{what}: out={out!r} (None, 'u8' or 'f32')")
+    source = _Source(src)
+    ix = _index_of(source)
+    _refuse_foreign(model, ix, what)
+    H, W, C, th, tw = ix["H"], ix["W"], ix["C"], ix["th"], ix["tw"]
+    y0, x0, h, w = (0, 0, H, W) if window is None else window
+    tiles = window_tiles(ix, y0, x0, h, w)
+    y0, x0, h, w = int(y0), int(x0), int(h), int(w)
+    batch = ix["batch"] if batch is None else batch
+    kind = {None: ix["kind"], "u8": KIND_U8_HWC, "f32": KIND_F32_CHW}[out]
+    img, suffix = _out_image(kind, C, h, w, next(model.parameters()).device, what)
+    fn = getattr(_lib.load(), "dsic_tile_stitch_window_" + suffix)
+    _, N, Hz, Wz = ix["containers"][0]["shape_z"]
+    uploaded = decode_batches = 0
+    for first in range(0, len(tiles), batch):
+        sel = tiles[first:first + batch]
+        n = len(sel)
+        # ascending tiles lie in ascending stream order, so back to back their strings are the spans back to back
+        images, pos = [], 0
+        for r in (ix["tiles"][t] for t in sel):
+            images.append((r["min_y"], r["max_y"], r["min_z"], r["max_z"], pos, r["z_len"], pos + r["z_len"],
+                           r["y_len"]))
+            pos += r["z_len"] + r["y_len"]
+        parts = [source.read_at(off, length) for off, length in tile_spans(ix, sel)]
+        x_hat, nbytes, ids = entropy._decode_selected(model, images, parts, [n, ix["M"], th // 16, tw // 16],
+                                                      [n, N, Hz, Wz], what, ride=sel)
+        x_hat = x_hat.contiguous()
+        _lib.check(fn(_p(x_hat), _p(ids), n, _p(img), H, W, C, th, tw, y0, x0, h, w, _stream()),
+                   "tile_stitch_window_" + suffix)
+        uploaded += nbytes
+        decode_batches += 1
+    if stats is not None:
+        stats.update(tiles=tiles, decode_batches=decode_batches, bytes_read=source.bytes_read,
+                     bytes_uploaded=uploaded)
+    return img
 
-    def inside(off, length):
-        if length == 0:
-            return 0
-        i = bisect.bisect_right(starts, off) - 1
-        return base[i] + off - starts[i]
 
-    rows, metas = [], []
-    for t in tiles:
-        r = index["tiles"][t]
-        rows.append((inside(r["z_off"], r["z_len"]), r["z_len"], inside(r["y_off"], r["y_len"]), r["y_len"]))
-        metas.append((r["min_y"], r["max_y"] - r["min_y"] + 1, r["min_z"], r["max_z"] - r["min_z"] + 1))
-    block = np.zeros(6 * n + (n + 1) // 2, dtype=np.int64)
-    block[:4 * n] = np.array(rows, dtype=np.int64).ravel()
-    meta = block[4 * n:6 * n].view(np.int32).reshape(n, 4)
-    meta[:] = np.array(metas, dtype=np.int32)
-    block[6 * n:].view(np.int32)[:n] = tiles
-    return block, meta
+@torch.no_grad()
+def decompress_image(model, stream, out=None):
+    """DSICI stream -> the image on the model's device: uint8 [H,W,C] ((uint8)(clamp(x,0,1)*255), truncating, as
+    torchvision's to_pil_image) or float32 [C,H,W] (clamp(x,0,1)); by default the kind of the encoder's input,
+    out="u8" / "f32" overrides it.  The whole image as a window, decoded container by container; each decoded batch
+    is stitched straight into the image."""
+    return _decode_window(model, stream, None, out, None, None, "decompress_image")
 
 
 @torch.no_grad()
@@ -417,50 +380,7 @@ def decompress_region(model, src, y0, x0, h, w, out=None, batch=64, stats=None):
     batches of at most `batch`, in ascending tile order, whatever containers they come from; each batch is one
     upload and is stitched into the window as soon as it is decoded.  stats (a dict) receives tiles, decode_batches,
     bytes_read and bytes_uploaded (the padded string bytes; 52 bytes of descriptors per tile travel beside them)."""
-    if out not in (None, "u8", "f32"):
-        raise ValueError(f"decompress_region: out={out!r} (None, 'u8' or 'f32')")
     batch = int(batch)
     if batch < 1:
         raise ValueError(f"decompress_region: batch={batch}")
-    source = _Source(src)
-    ix = _index_of(source)
-    _refuse_foreign(model, ix, "decompress_region")
-    tiles = window_tiles(ix, y0, x0, h, w)
-    y0, x0, h, w = int(y0), int(x0), int(h), int(w)
-    H, W, C, th, tw = ix["H"], ix["W"], ix["C"], ix["th"], ix["tw"]
-    kind = {None: ix["kind"], "u8": KIND_U8_HWC, "f32": KIND_F32_CHW}[out]
-    dev = next(model.parameters()).device
-    L = _lib.load()
-    img, suffix = _out_image(kind, C, h, w, dev, "decompress_region")
-    fn, what = getattr(L, "dsic_tile_stitch_window_" + suffix), "tile_stitch_window_" + suffix
-    _, N, Hz, Wz = ix["containers"][0]["shape_z"]
-    uploaded = decode_batches = 0
-    for first in range(0, len(tiles), batch):
-        sel = tiles[first:first + batch]
-        n = len(sel)
-        spans = tile_spans(ix, sel)
-        block, meta_np = _select_batch(ix, sel, spans)
-        d_blob, blob_bytes, d_block = entropy._upload_padded([source.read_at(off, length) for off, length in spans],
-                                                             dev, tail=block)
-        d_block = d_block.view(torch.int64)
-        desc, meta = d_block[:4 * n], d_block[4 * n:6 * n].view(torch.int32).view(n, 4)
-        ids = d_block[6 * n:].view(torch.int32)
-        zmax, ymax = int(block[1:4 * n:4].max()), int(block[3:4 * n:4].max())
-        # custom_decompress's strides (entropy._upload_strings), as decompress_container's
-        zstride, ystride = max(4, (zmax + 3) // 4 * 4), max(4, (ymax + 3) // 4 * 4)
-        zbuf = torch.empty(n * zstride, dtype=torch.uint8, device=dev)
-        ybuf = torch.empty(n * ystride, dtype=torch.uint8, device=dev)
-        lengths = torch.empty((n, 2), dtype=torch.int32, device=dev)
-        _lib.check(L.dsic_strings_scatter_select(_p(d_blob), blob_bytes, _p(desc), n, max(zmax, ymax), _p(zbuf),
-                                                 zstride, _p(ybuf), ystride, _p(lengths), _stream()),
-                   "strings_scatter_select")
-        x_hat = entropy._decode_batch(model, [n, ix["M"], th // 16, tw // 16], [n, N, Hz, Wz], meta,
-                                      entropy._default_lmax(model, meta_np), (zbuf, zstride, lengths, 2, 0),
-                                      (ybuf, ystride, lengths, 2, 1), "decompress_region").contiguous()
-        _lib.check(fn(_p(x_hat), _p(ids), n, _p(img), H, W, C, th, tw, y0, x0, h, w, _stream()), what)
-        uploaded += entropy._padded_bytes(blob_bytes)
-        decode_batches += 1
-    if stats is not None:
-        stats.update(tiles=tiles, decode_batches=decode_batches, bytes_read=source.bytes_read,
-                     bytes_uploaded=uploaded)
-    return img
+    return _decode_window(model, src, (y0, x0, h, w), out, batch, stats, "decompress_region")

@@ -11,6 +11,7 @@ from __future__ import annotations
 
 import ctypes
 import os
+import struct
 
 import numpy as np
 import torch
@@ -406,58 +407,64 @@ def real_bpp(compressed, H, W):
 # this is that dict as one byte string, so the strings can leave the process ------------------
 _MAGIC = b"DSIC2\x00"      # DSIC1: rounds 1-2, no numerics tag (float64 / float32 tables both wrote it: not decodable
 _MAGIC_V1 = b"DSIC1\x00"   # safely any more, refused)
+_HEAD = struct.Struct("<6sI7I")      # magic, numerics tag, B, My, Hy, Wy, Nz, Hz, Wz
+_REC = struct.Struct("<4i2I")        # per image: min_y, max_y, min_z, max_z, len_z, len_y
 
 
 def pack_container(compressed) -> bytes:
     """dict of custom_compress -> bytes.  Layout (little endian):
     magic(6) | numerics tag (uint32, numerics_tag()) | B,My,Hy,Wy,Nz,Hz,Wz (7 x uint32) | per image:
     min_y,max_y,min_z,max_z (4 x int32), len_z,len_y (2 x uint32) | per image: z bytes, y bytes."""
-    import struct
     B, My, Hy, Wy = compressed["shape_y"]
     _, Nz, Hz, Wz = compressed["shape_z"]
     tag = int(compressed.get("numerics", numerics_tag()))
-    head = [_MAGIC, struct.pack("<I", tag), struct.pack("<7I", B, My, Hy, Wy, Nz, Hz, Wz)]
+    head = [_HEAD.pack(_MAGIC, tag, B, My, Hy, Wy, Nz, Hz, Wz)]
     body = []
     for b in range(B):
         zs, ys = compressed["strings"][b]
-        head.append(struct.pack("<4i2I", compressed["min_y"][b], compressed["max_y"][b], compressed["min_z"][b],
-                                compressed["max_z"][b], len(zs), len(ys)))
+        head.append(_REC.pack(compressed["min_y"][b], compressed["max_y"][b], compressed["min_z"][b],
+                              compressed["max_z"][b], len(zs), len(ys)))
         body += [zs, ys]
     return b"".join(head + body)
 
 
-def unpack_container(blob: bytes):
-    """Inverse of pack_container."""
-    import struct
-    if blob[:6] == _MAGIC_V1:
+def read_container_head(read_at, off, size):
+    """The head and the records of the DSIC2 container that fills bytes [off, off + size) behind read_at(offset, n)
+    (n bytes at an offset: a slice of a blob, or codec._Source.read_at); the strings are not read.  Returns (tag,
+    shape_y, shape_z, per image (min_y, max_y, min_z, max_z, z_off, z_len, y_off, y_len)), offsets as read_at counts
+    them.  ValueError for a DSIC1 container, another magic, and records that do not add up to size."""
+    head = read_at(off, min(size, _HEAD.size))
+    if head[:6] == _MAGIC_V1:
         raise ValueError("DSIC1 container: written before the numerics tag existed (its coder tables may be the float64 "
                          "ones of round 1); re-encode")
-    if blob[:6] != _MAGIC:
+    if len(head) < _HEAD.size or head[:6] != _MAGIC:
         raise ValueError("not a DSIC container")
-    (tag,) = struct.unpack_from("<I", blob, 6)
-    B, My, Hy, Wy, Nz, Hz, Wz = struct.unpack_from("<7I", blob, 10)
-    off = 10 + 28
-    meta = [struct.unpack_from("<4i2I", blob, off + 24 * b) for b in range(B)]
-    off += 24 * B
-    strings = []
-    for m in meta:
-        zs = blob[off:off + m[4]]
-        off += m[4]
-        ys = blob[off:off + m[5]]
-        off += m[5]
-        strings.append([zs, ys])
-    if off != len(blob):
+    _, tag, B, My, Hy, Wy, Nz, Hz, Wz = _HEAD.unpack(head)
+    if B < 1 or size < _HEAD.size + _REC.size * B:
         raise ValueError("truncated or oversized DSIC container")
-    return {"strings": strings, "shape_y": [B, My, Hy, Wy], "shape_z": [B, Nz, Hz, Wz],
-            "min_y": [m[0] for m in meta], "max_y": [m[1] for m in meta],
-            "min_z": [m[2] for m in meta], "max_z": [m[3] for m in meta], "numerics": tag}
+    pos, images = off + _HEAD.size + _REC.size * B, []
+    for min_y, max_y, min_z, max_z, len_z, len_y in _REC.iter_unpack(read_at(off + _HEAD.size, _REC.size * B)):
+        images.append((min_y, max_y, min_z, max_z, pos, len_z, pos + len_z, len_y))
+        pos += len_z + len_y
+    if pos != off + size:
+        raise ValueError("truncated or oversized DSIC container")
+    return tag, [B, My, Hy, Wy], [B, Nz, Hz, Wz], images
+
+
+def _blob_head(blob):
+    return read_container_head(lambda off, n: blob[off:off + n], 0, len(blob))
+
+
+def unpack_container(blob: bytes):
+    """Inverse of pack_container."""
+    tag, shape_y, shape_z, images = _blob_head(blob)
+    return {"strings": [[blob[r[4]:r[4] + r[5]], blob[r[6]:r[6] + r[7]]] for r in images],
+            "shape_y": shape_y, "shape_z": shape_z,
+            "min_y": [r[0] for r in images], "max_y": [r[1] for r in images],
+            "min_z": [r[2] for r in images], "max_z": [r[3] for r in images], "numerics": tag}
 
 
 # ---- the same container, written and read on the device (codec.py's batches) ----------------------------------
-_HEAD = 38          # magic, tag, 7 shape words
-_REC = 24           # per image: min_y, max_y, min_z, max_z, len_z, len_y
-
-
 def _pack_on_device(c, tag):
     """compress_latents' outputs -> (DSIC2 container in a device buffer, its size, the coder's error word).  The size and
     the error word come back in one 16-byte copy; nothing is sliced per image on the host."""
@@ -465,7 +472,7 @@ def _pack_on_device(c, tag):
     _, My, Hy, Wy = c["shape_y"]
     _, Nz, Hz, Wz = c["shape_z"]
     dev = c["bytes"].device
-    out = torch.empty(_HEAD + _REC * B + B * (c["cap_z"] + c["cap_y"]), dtype=torch.uint8, device=dev)
+    out = torch.empty(_HEAD.size + _REC.size * B + B * (c["cap_z"] + c["cap_y"]), dtype=torch.uint8, device=dev)
     ws = torch.empty(2 * B + 3, dtype=torch.int64, device=dev)
     _lib.check(_lib.load().dsic_container_pack(_p(c["bytes"]), c["cap_z"], c["cap_y"], _p(c["lengths"]), _p(c["meta"]),
                                                _p(c["err"]), B, tag & 0xFFFFFFFF, My, Hy, Wy, Nz, Hz, Wz, _p(ws),
@@ -482,75 +489,72 @@ def compress_to_container(model, x, tail=10, Lmax=DEFAULT_LMAX) -> bytes:
     return c["container"][:c["container_bytes"]].cpu().numpy().tobytes()
 
 
-def _container_records(blob):
-    """DSIC2 header and records -> (tag, shape_y, shape_z, records int64 [B,6]); the checks of unpack_container."""
-    import struct
-    if blob[:6] == _MAGIC_V1:
-        raise ValueError("DSIC1 container: written before the numerics tag existed (its coder tables may be the float64 "
-                         "ones of round 1); re-encode")
-    if len(blob) < _HEAD or blob[:6] != _MAGIC:
-        raise ValueError("not a DSIC container")
-    (tag,) = struct.unpack_from("<I", blob, 6)
-    B, My, Hy, Wy, Nz, Hz, Wz = struct.unpack_from("<7I", blob, 10)
-    if B < 1 or len(blob) < _HEAD + _REC * B:
-        raise ValueError("truncated or oversized DSIC container")
-    rec = np.frombuffer(blob, dtype="<i4", count=6 * B, offset=_HEAD).reshape(B, 6).astype(np.int64)
-    rec[:, 4:] &= 0xFFFFFFFF                                           # the lengths are unsigned
-    if _HEAD + _REC * B + int(rec[:, 4:].sum()) != len(blob):
-        raise ValueError("truncated or oversized DSIC container")
-    return tag, [B, My, Hy, Wy], [B, Nz, Hz, Wz], rec
-
-
 def _padded_bytes(n):
     """Size of the device copy of n stream bytes: whole 16-byte chunks and at least one spare, so the 16-byte reads of
     the string movers (image_codec.hip load16_any) stay inside the allocation."""
     return (n + 31) // 16 * 16
 
 
-def _upload_padded(parts, dev, tail=None):
-    """Byte strings, back to back, in one host buffer and one copy -> (device uint8 [_padded_bytes(total)], total).
-    tail (a numpy array) rides in the same copy, after the padding (16-byte aligned): -> (..., total, its device
-    copy as uint8)."""
+def _upload_padded(parts, tail, dev):
+    """Byte strings, back to back, and behind their padding (16-byte aligned) the numpy array tail, in one host buffer
+    and one copy -> (device uint8 [_padded_bytes(total)], total, the device copy of tail as uint8)."""
     total = sum(len(p) for p in parts)
     padded = _padded_bytes(total)
-    host = torch.empty(padded + (tail.nbytes if tail is not None else 0), dtype=torch.uint8)
+    host = torch.empty(padded + tail.nbytes, dtype=torch.uint8)
     a, off = host.numpy(), 0
     for p in parts:
         a[off:off + len(p)] = np.frombuffer(p, dtype=np.uint8)
         off += len(p)
-    if tail is None:
-        return host.to(dev), total
     a[padded:] = tail.view(np.uint8).ravel()
     d = host.to(dev)
     return d[:padded], total, d[padded:]
 
 
-def _decompress_container_raw(model, blob, Lmax=None, what="decompress_container"):
+def _decode_selected(model, images, parts, shape_y, shape_z, what, Lmax=None, ride=None):
+    """One decode batch from the strings of n images picked anywhere: images as read_container_head gives them, with
+    z_off / y_off counted inside the byte strings `parts` laid back to back; shape_y / shape_z = [n, channels, h, w].
+    The strings travel in one padded copy with an int64 control block behind them: descriptors [n][4] (z offset, z
+    length, y offset, y length), meta int32 [n][4] (ymin, Ly, zmin, Lz), then the int32 array `ride` (codec's tile
+    numbers).  The device spreads the strings at custom_decompress's strides (_upload_strings) and decodes with Lmax
+    (default: _default_lmax over these images).  Returns (g_s's output, not yet clamped; the padded string bytes
+    uploaded; the device copy of ride)."""
     dev = next(model.parameters()).device
-    tag, shape_y, shape_z, rec = _container_records(blob)
-    _refuse_tag(tag, what)
-    B = shape_y[0]
-    meta_np = np.stack([rec[:, 0], rec[:, 1] - rec[:, 0] + 1, rec[:, 2], rec[:, 3] - rec[:, 2] + 1], axis=1)
+    n = len(images)
+    rec = np.array(images, dtype=np.int64).reshape(n, 8)
+    ride = np.zeros(0, dtype=np.int32) if ride is None else np.asarray(ride, dtype=np.int32)
+    block = np.zeros(6 * n + (ride.size + 1) // 2, dtype=np.int64)
+    block[:4 * n] = rec[:, 4:].ravel()
+    meta_np = block[4 * n:6 * n].view(np.int32).reshape(n, 4)
+    meta_np[:, 0::2] = rec[:, 0:4:2]
+    meta_np[:, 1::2] = rec[:, 1:4:2] - rec[:, 0:4:2] + 1
+    block[6 * n:].view(np.int32)[:ride.size] = ride
+    d_blob, total, d_block = _upload_padded(parts, block, dev)
+    d_block = d_block.view(torch.int64)
+    meta = d_block[4 * n:6 * n].view(torch.int32).view(n, 4)
+    zmax, ymax = int(rec[:, 5].max()), int(rec[:, 7].max())
+    zstride, ystride = max(4, (zmax + 3) // 4 * 4), max(4, (ymax + 3) // 4 * 4)
+    zbuf = torch.empty(n * zstride, dtype=torch.uint8, device=dev)
+    ybuf = torch.empty(n * ystride, dtype=torch.uint8, device=dev)
+    lengths = torch.empty((n, 2), dtype=torch.int32, device=dev)
+    _lib.check(_lib.load().dsic_strings_scatter_select(_p(d_blob), total, _p(d_block), n, max(zmax, ymax), _p(zbuf),
+                                                       zstride, _p(ybuf), ystride, _p(lengths), _stream()),
+               "strings_scatter_select")
     if Lmax is None:
         Lmax = _default_lmax(model, meta_np)
-    # custom_decompress's strides (_upload_strings); the device copy of the blob is padded to whole 16-byte chunks
-    zstride = max(4, (int(rec[:, 4].max()) + 3) // 4 * 4)
-    ystride = max(4, (int(rec[:, 5].max()) + 3) // 4 * 4)
-    d_blob, _ = _upload_padded([blob], dev)
-    zbuf = torch.empty(B * zstride, dtype=torch.uint8, device=dev)
-    ybuf = torch.empty(B * ystride, dtype=torch.uint8, device=dev)
-    lengths = torch.empty((B, 2), dtype=torch.int32, device=dev)
-    meta = torch.empty((B, 4), dtype=torch.int32, device=dev)
-    ws = torch.empty(2 * B + 3, dtype=torch.int64, device=dev)
-    _lib.check(_lib.load().dsic_container_scatter(_p(d_blob), len(blob), B, int(rec[:, 4:].max()), _p(zbuf), zstride,
-                                                  _p(ybuf), ystride, _p(lengths), _p(meta), _p(ws), _stream()),
-               "container_scatter")
-    return _decode_batch(model, shape_y, shape_z, meta, Lmax, (zbuf, zstride, lengths, 2, 0),
-                         (ybuf, ystride, lengths, 2, 1), what)
+    x_hat = _decode_batch(model, shape_y, shape_z, meta, Lmax, (zbuf, zstride, lengths, 2, 0),
+                          (ybuf, ystride, lengths, 2, 1), what)
+    return x_hat, _padded_bytes(total), d_block[6 * n:].view(torch.int32)[:ride.size]
 
 
 @torch.no_grad()
 def decompress_container(model, blob, Lmax=None):
-    """custom_decompress(model, unpack_container(blob)), bit for bit: the blob is uploaded once and its strings are
-    moved into the decoder's buffers on the device; the host reads only the header and the 24-byte records."""
-    return _decompress_container_raw(model, bytes(blob), Lmax).clamp(0, 1)
+    """custom_decompress(model, unpack_container(blob)), bit for bit: every image of the blob through
+    _decode_selected.  The host reads the header and the 24-byte records; the strings are uploaded once and moved
+    into the decoder's buffers on the device."""
+    blob = bytes(blob)
+    tag, shape_y, shape_z, images = _blob_head(blob)
+    _refuse_tag(tag, "decompress_container")
+    body = images[0][4]                                                # the strings follow the records
+    images = [r[:4] + (r[4] - body, r[5], r[6] - body, r[7]) for r in images]
+    return _decode_selected(model, images, [memoryview(blob)[body:]], shape_y, shape_z, "decompress_container",
+                            Lmax)[0].clamp(0, 1)

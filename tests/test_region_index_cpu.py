@@ -193,6 +193,11 @@ def test_refusals():
     odd, _, _, _ = _build(600, 1000, 256, 5, seed=5, container_tags=[TAG, TAG ^ 0x100, TAG])
     with pytest.raises(ValueError, match="batch 1 carries numerics tag"):
         codec.stream_index(odd)
+    # ... and both decoders refuse it the same way, from the index, before they touch the model
+    with pytest.raises(ValueError, match="batch 1 carries numerics tag"):
+        codec.decompress_image(None, odd)
+    with pytest.raises(ValueError, match="batch 1 carries numerics tag"):
+        codec.decompress_region(None, odd, 0, 0, 8, 8)
     # batches versus grid: a dropped batch, a batch size that needs four batches, batches in the wrong places
     u = codec.unpack_image_stream(stream)
     head = {k: u[k] for k in ("numerics", "H", "W", "C", "kind", "th", "tw", "N", "M", "in_ch", "spatial_params",
