@@ -99,6 +99,22 @@ def test_forward_vs_oracle_live():
         assert out[k].shape == ref[k].shape
         scale = float(ref[k].abs().mean())
         assert float((out[k].cpu() - ref[k]).abs().max()) < 1e-3 * scale + 1e-5, k
+    # nll_y element by element, where the latent is the oracle's: the kernel's envelope (tests/rate_ref.py) at the
+    # model's sigma, nu, plus what sigma and nu within rtol 1e-4 of the oracle's (the fixture test's tolerance) can
+    # move the bits by: the largest change over the four corners sigma (1 +- 1e-4), nu (1 +- 1e-4)
+    import rate_ref as R
+    sig, nu, xt = out["sigma"].cpu(), out["nu"].cpu(), out["y_tilde"].cpu()
+    np.testing.assert_allclose(sig.numpy(), ref["sigma"].numpy(), rtol=1e-4)
+    np.testing.assert_allclose(nu.numpy(), ref["nu"].numpy(), rtol=1e-4)
+    bits = R.student_bits64(xt, sig, nu)
+    moved = torch.zeros_like(bits)
+    for ds in (1 - 1e-4, 1 + 1e-4):
+        for dn in (1 - 1e-4, 1 + 1e-4):
+            moved = torch.maximum(moved, (R.student_bits64(xt, sig.double() * ds, nu.double() * dn) - bits).abs())
+    same = xt == ref["y_tilde"]
+    excess = (out["nll_y"].cpu().double() - ref["nll_y"].double()).abs() - (R.K_GPU * R.env_student(xt, sig, nu) + moved)
+    assert out["nll_y"].shape == ref["nll_y"].shape and int(same.sum()) >= same.numel() - 2
+    assert float(excess[same].max()) <= 0.0, float(excess[same].max())
 
 
 @pytest.mark.parametrize("N,M", [(80, 96), (96, 192)])
