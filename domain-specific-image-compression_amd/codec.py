@@ -8,6 +8,10 @@ and the containers travel in one stream with the image's geometry:
     magic "DSICI\\0" | version u16 | numerics tag u32 | H, W, C, kind, th, tw u32 | N, M, in_ch, spatial_params u32 |
     batch, batches u32 | per batch: u64 length, DSIC2 container            (little endian, fixed-size fields)
 
+A stream compressed with segments = K > 1 (entropy.compress_latents: every tile's y string as K independent strings,
+so that a decoder reads a tile on K waves) is version 2: the version-1 head, then segments u32, and every container
+is DSIC3 with that K.  Version 1 is written whenever K = 1.
+
 kind 0 = uint8 [H,W,C] (PIL / numpy layout), 1 = float32 [C,H,W] in [0,1].  Tiling (tile_grid): the image is
 reflect-padded bottom/right to multiples of 16 inside the gather kernel; the last row / column of tiles shifts inward
 (overlap, no extra padding) and every pixel is written back by the one tile that owns it.  Tiles are coded
@@ -31,8 +35,10 @@ from .ops import _p, _stream
 
 MAGIC = b"DSICI\x00"
 VERSION = 1
+VERSION_SEG = 2            # version 1 + the segments word; written only for segments > 1
 KIND_U8_HWC, KIND_F32_CHW = 0, 1
 _HEAD = struct.Struct("<6sHI6I4I2I")
+_SEGS = struct.Struct("<I")
 _LEN = struct.Struct("<Q")
 
 
@@ -77,10 +83,15 @@ def _model_shape(model):
 
 
 def pack_image_stream(header: dict, blobs) -> bytes:
-    """header (the fields unpack_image_stream returns) + the DSIC2 containers -> the stream (pure Python)."""
+    """header (the fields unpack_image_stream returns) + the DSIC2 containers -> the stream (pure Python).  A header
+    with "segments" = K > 1 writes version 2, whose containers are DSIC3 with that K."""
     h = header
-    head = _HEAD.pack(MAGIC, VERSION, h["numerics"] & 0xFFFFFFFF, h["H"], h["W"], h["C"], h["kind"], h["th"], h["tw"],
-                      h["N"], h["M"], h["in_ch"], h["spatial_params"], h["batch"], len(blobs))
+    K = entropy.check_segments(h.get("segments", 1), h["M"], "pack_image_stream")
+    head = _HEAD.pack(MAGIC, VERSION_SEG if K > 1 else VERSION, h["numerics"] & 0xFFFFFFFF, h["H"], h["W"], h["C"],
+                      h["kind"], h["th"], h["tw"], h["N"], h["M"], h["in_ch"], h["spatial_params"], h["batch"],
+                      len(blobs))
+    if K > 1:
+        head += _SEGS.pack(K)
     return b"".join([head] + [_LEN.pack(len(b)) + bytes(b) for b in blobs])
 
 
@@ -126,9 +137,19 @@ def _read_framing(src):
     keys = ("version", "numerics", "H", "W", "C", "kind", "th", "tw", "N", "M", "in_ch", "spatial_params", "batch",
             "batches")
     h = dict(zip(keys, f[1:]))
-    if h["version"] != VERSION:
-        raise ValueError(f"DSICI stream version {h['version']}, this reader knows {VERSION}")
-    off, frames = _HEAD.size, []
+    if h["version"] not in (VERSION, VERSION_SEG):
+        raise ValueError(f"DSICI stream version {h['version']}, this reader knows {VERSION} and {VERSION_SEG}")
+    off, h["segments"] = _HEAD.size, 1
+    if h["version"] == VERSION_SEG:
+        word = src.read_at(off, _SEGS.size)
+        if len(word) < _SEGS.size:
+            raise ValueError("truncated DSICI stream")
+        (h["segments"],) = _SEGS.unpack(word)
+        off += _SEGS.size
+        if h["segments"] not in entropy.SEGMENTS[1:] or h["M"] % h["segments"]:
+            raise ValueError(f"DSICI stream: segments={h['segments']} is not one of {entropy.SEGMENTS[1:]} dividing "
+                             f"M={h['M']}")
+    frames = []
     for _ in range(h["batches"]):
         if off + _LEN.size > src.size:
             raise ValueError("truncated DSICI stream")
@@ -145,7 +166,7 @@ def _read_framing(src):
 
 def unpack_image_stream(stream) -> dict:
     """stream -> header fields (version, numerics, H, W, C, kind, th, tw, N, M, in_ch, spatial_params, batch,
-    batches) and "blobs", the list of inner DSIC2 containers (pure Python).  ValueError on a wrong magic, a truncated
+    batches, segments: 1 for a version-1 stream) and "blobs", the list of inner DSIC2 containers (pure Python).  ValueError on a wrong magic, a truncated
     stream or trailing bytes."""
     s = bytes(stream)
     h, frames = _read_framing(_Source(s))
@@ -172,10 +193,11 @@ def _gather(img, kind, g, C, first, n):
 
 
 @torch.no_grad()
-def compress_image(model, img, tile=256, batch=64, tail=10) -> bytes:
+def compress_image(model, img, tile=256, batch=64, tail=10, segments=1) -> bytes:
     """img: uint8 [H,W,C] or float32 [C,H,W] in [0,1], on the CPU or the GPU -> one DSICI stream.  The image is
     uploaded once; each batch of `batch` tiles is gathered on the device (reflect padding included) and becomes one
-    DSIC2 container."""
+    DSIC2 container.  segments = K > 1 (1, 2, 4, 8 or 16, dividing M): every tile's y string is K independent strings
+    (DSIC3 containers, stream version 2), which the decoders read on K waves per tile; the decoded image is the same."""
     dev = next(model.parameters()).device
     if img.dim() != 3:
         raise ValueError(f"compress_image: expected uint8 [H,W,C] or float32 [C,H,W], got {tuple(img.shape)}")
@@ -186,6 +208,7 @@ def compress_image(model, img, tile=256, batch=64, tail=10) -> bytes:
     else:
         raise TypeError(f"compress_image: expected uint8 or float32, got {img.dtype}")
     N, M, in_ch, spatial = _model_shape(model)
+    segments = entropy.check_segments(segments, M, "compress_image")
     if C != in_ch:
         raise ValueError(f"compress_image: image has {C} channels, the model takes {in_ch}")
     batch = int(batch)
@@ -196,9 +219,9 @@ def compress_image(model, img, tile=256, batch=64, tail=10) -> bytes:
     blobs = []
     for first in range(0, g["n"], batch):
         tiles = _gather(x, kind, g, C, first, min(batch, g["n"] - first))
-        blobs.append(entropy.compress_to_container(model, tiles, tail))
+        blobs.append(entropy.compress_to_container(model, tiles, tail, segments=segments))
     header = {"numerics": entropy.numerics_tag(), "H": H, "W": W, "C": C, "kind": kind, "th": g["th"], "tw": g["tw"],
-              "N": N, "M": M, "in_ch": in_ch, "spatial_params": spatial, "batch": batch}
+              "N": N, "M": M, "in_ch": in_ch, "spatial_params": spatial, "batch": batch, "segments": segments}
     return pack_image_stream(header, blobs)
 
 
@@ -250,7 +273,10 @@ def _index_of(src):
     g = _stream_grid(ix)
     tiles, containers = [], []
     for k, (off, size) in enumerate(frames):
-        tag, shape_y, shape_z, images = entropy.read_container_head(src.read_at, off, size)
+        tag, shape_y, shape_z, images, segs, seg = entropy.read_container_segments(src.read_at, off, size)
+        if segs != ix["segments"]:
+            raise ValueError(f"DSICI stream: batch {k} holds {segs} segments per y string, the header says "
+                             f"{ix['segments']}")
         if tag != ix["numerics"]:
             raise ValueError(f"DSICI stream: batch {k} carries numerics tag {tag:#x}, the stream's is "
                              f"{ix['numerics']:#x}")
@@ -264,7 +290,7 @@ def _index_of(src):
                              f"{containers[0]['shape_z'][2]}x{containers[0]['shape_z'][3]}")
         for b, (min_y, max_y, min_z, max_z, z_off, z_len, y_off, y_len) in enumerate(images):
             tiles.append({"k": k, "b": b, "min_y": min_y, "max_y": max_y, "min_z": min_z, "max_z": max_z,
-                          "z_off": z_off, "z_len": z_len, "y_off": y_off, "y_len": y_len})
+                          "z_off": z_off, "z_len": z_len, "y_off": y_off, "y_len": y_len, "y_segs": seg[b]})
         containers.append({"offset": off, "bytes": size, "first": first, "tiles": len(images), "shape_y": shape_y,
                            "shape_z": shape_z})
     ix.update(grid=g, tiles=tiles, containers=containers, stream_bytes=src.size, index_bytes=src.bytes_read)
@@ -274,16 +300,19 @@ def _index_of(src):
 def stream_index(src) -> dict:
     """Where every tile of a DSICI stream lies, from its heads alone (pure Python).  src: bytes / bytearray /
     memoryview, or a binary file object with seek and read.  Only the 60-byte header and, per batch, the 8-byte
-    length, the 38-byte DSIC2 header and the 24-byte records are read; the strings are skipped.  Returns the header
-    fields of unpack_image_stream (no "blobs") and
+    length, the 38-byte DSIC2 header and the 24-byte records are read (version 2: 64 bytes, and per batch the 42-byte
+    DSIC3 header, the records and 4 bytes per y segment); the strings are skipped.  Returns the header fields of
+    unpack_image_stream (no "blobs"; segments = y segments per tile, 1 for version 1) and
       grid         tile_grid's dict for H, W, th, tw
       tiles        per tile t (row-major, as the grid numbers them): k (batch), b (slot in it), min_y, max_y, min_z,
-                   max_z, z_off, z_len, y_off, y_len (absolute byte offsets and lengths of its two strings)
+                   max_z, z_off, z_len, y_off, y_len (absolute byte offsets and lengths of its two strings), y_segs
+                   (the lengths of the y string's segments, back to back from y_off; [y_len] for segments = 1)
       containers   per batch: offset, bytes, first (tile), tiles, shape_y, shape_z
       stream_bytes, index_bytes (what this call read).
     ValueError as unpack_image_stream, entropy.unpack_container and decompress_image raise it: wrong magic or version,
     DSIC1 container, truncated stream or container, trailing bytes, batches that do not match the grid, latents that
-    do not match the tile size, a container whose numerics tag is not the stream's."""
+    do not match the tile size, a container whose numerics tag or segment count is not the stream's, segment lengths
+    that do not add up."""
     return _index_of(_Source(src))
 
 
@@ -350,7 +379,8 @@ def _decode_window(model, src, window, out, batch, stats, what):
             pos += r["z_len"] + r["y_len"]
         parts = [source.read_at(off, length) for off, length in tile_spans(ix, sel)]
         x_hat, nbytes, ids = entropy._decode_selected(model, images, parts, [n, ix["M"], th // 16, tw // 16],
-                                                      [n, N, Hz, Wz], what, ride=sel)
+                                                      [n, N, Hz, Wz], what, ride=sel, segments=ix["segments"],
+                                                      seg_lengths=[ix["tiles"][t]["y_segs"] for t in sel])
         x_hat = x_hat.contiguous()
         _lib.check(fn(_p(x_hat), _p(ids), n, _p(img), H, W, C, th, tw, y0, x0, h, w, _stream()),
                    "tile_stitch_window_" + suffix)

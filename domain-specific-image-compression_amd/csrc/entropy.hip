@@ -563,28 +563,43 @@ __global__ __launch_bounds__(1024) void range_encode_kernel(
 //        E3 run from (low1, high1); summarize writes each slice's carry map and bit count, emit composes the records
 //        in front of its slice and makes the same put_bits calls, flush, lengths and error bit 4 as
 //        range_encode_kernel.
-// Workspace: pairs, rec_low, rec_high [B (M HWy + N HWz)] uint32, then final low [2B], then (8-byte aligned) the
-// slice records [B (ky + kz)] uint2; string s < B is y string s at symbol s * ny, string B + b the z string b at
-// B ny + b nz.
+// Workspace: pairs, rec_low, rec_high [B (M HWy + N HWz)] uint32, then final low [B (K + 1)], then (8-byte aligned)
+// the slice records [B (K ky + kz)] uint2.
+// Segments (dsic_range_encode_seg_ws): the y string of an image is coded as K = 2^lk independent strings, segment k =
+// its symbols [k ns, (k + 1) ns) with ns = ny / K (M / K channels), so the pairs and records of the B K segment
+// strings lie back to back: string s < B K is segment s & (K - 1) of image s >> lk at symbol s * ns, string B K + b
+// the z string b at B ny + b nz.  K = 1 is the unsegmented coder.
 struct SplitGeom {
   int B, M, HWy, N, HWz, Lmax, per_element_y;
+  int K, lk;    // y segments per image and log2 of it
   int64_t ny, nz;
-  int gy, gz;   // place: 64-symbol groups per slice of a y / z string (place_slicing)
-  int ky, kz;   // place: slices per y / z string
-  __device__ __forceinline__ void stream(int s, int& which, int& b, int64_t& n, int64_t& base) const {
+  int64_t ns;   // symbols of one y segment
+  int gy, gz;   // place: 64-symbol groups per slice of a y segment / z string (place_slicing)
+  int ky, kz;   // place: slices per y segment / z string
+  // the whole strings of an image, as the pack kernel walks them: s < B is y string s, B + b the z string b
+  __device__ __forceinline__ void image(int s, int& which, int& b, int64_t& n, int64_t& base) const {
     which = s < B ? 1 : 0;
     b = which ? s : s - B;
     n = which ? ny : nz;
     base = which ? (int64_t)b * ny : (int64_t)B * ny + (int64_t)b * nz;
   }
-  // place slice q (0 .. B (ky + kz) - 1; y strings first) -> string s, slice k of the string, its slice count and
+  __device__ __forceinline__ void stream(int s, int& which, int& b, int64_t& n, int64_t& base) const {
+    const int BK = B << lk;
+    which = s < BK ? 1 : 0;
+    b = which ? s >> lk : s - BK;
+    n = which ? ns : nz;
+    base = which ? (int64_t)s * ns : (int64_t)B * ny + (int64_t)b * nz;
+  }
+  __device__ __forceinline__ int nslices() const { return (B << lk) * ky + B * kz; }
+  // place slice q (0 .. nslices() - 1; y segments first) -> string s, slice k of the string, its slice count and
   // the index of the string's first slice record
   __device__ __forceinline__ void slice(int q, int& s, int& k, int& ks, int& gs, int& q0) const {
-    const int qz = q - B * ky;
+    const int BK = B << lk;
+    const int qz = q - BK * ky;
     const bool y = qz < 0;
     ks = y ? ky : kz;
     gs = y ? gy : gz;
-    s = y ? q / ky : B + qz / kz;
+    s = y ? q / ky : BK + qz / kz;
     k = y ? q % ky : qz % kz;
     q0 = q - k;
   }
@@ -605,7 +620,7 @@ __global__ __launch_bounds__(256) void enc_pack_kernel(const float* __restrict__
                                                        uint32_t* __restrict__ pairs, int* __restrict__ err) {
   int which, b;
   int64_t n, base;
-  G.stream(blockIdx.y, which, b, n, base);
+  G.image(blockIdx.y, which, b, n, base);
   const int HW = which ? G.HWy : G.HWz, Lmax = G.Lmax;
   const bool per_element = which && G.per_element_y;
   const float* sym = which ? y + (size_t)b * n : z + (size_t)b * n;
@@ -791,7 +806,7 @@ __global__ __launch_bounds__(64 * PLACE_WAVES) void enc_place_sum_kernel(const i
                                                                          uint2* __restrict__ slices) {
   const int lane = threadIdx.x & 63;
   const int q = __builtin_amdgcn_readfirstlane(blockIdx.x * PLACE_WAVES + (threadIdx.x >> 6));
-  if (q >= G.B * (G.ky + G.kz)) return;
+  if (q >= G.nslices()) return;
   int s, k, ks, gs, q0;
   G.slice(q, s, k, ks, gs, q0);
   int which, b;
@@ -826,19 +841,22 @@ __global__ __launch_bounds__(64 * PLACE_WAVES) void enc_place_emit_kernel(
     const int* __restrict__ meta, SplitGeom G, const uint32_t* __restrict__ rec_low,
     const uint32_t* __restrict__ rec_high, const uint2* __restrict__ slices, const uint32_t* __restrict__ final_low,
     uint8_t* __restrict__ out, int64_t cap_y, int64_t cap_z, int* __restrict__ lengths, int* __restrict__ err) {
+  // cap_y: the capacity of one y segment; out [B][cap_z + K cap_y], lengths [B][1 + K] = {z, segment 0 .. K - 1}
   const int lane = threadIdx.x & 63;
   const int q = __builtin_amdgcn_readfirstlane(blockIdx.x * PLACE_WAVES + (threadIdx.x >> 6));
-  if (q >= G.B * (G.ky + G.kz)) return;
+  if (q >= G.nslices()) return;
   int s, k, ks, gs, q0;
   G.slice(q, s, k, ks, gs, q0);
   int which, b;
   int64_t n, base;
   G.stream(s, which, b, n, base);
+  const int seg = which ? s & (G.K - 1) : 0;
+  int* const length = lengths + (size_t)(1 + G.K) * b + (which ? 1 + seg : 0);
   const int L = meta[4 * b + (which ? 1 : 3)];
   if (L > G.Lmax || L < 1) {
     if (k == 0 && lane == 0) {
       atomicOr(err, 1);
-      lengths[2 * b + which] = 0;
+      *length = 0;
     }
     return;
   }
@@ -883,8 +901,8 @@ __global__ __launch_bounds__(64 * PLACE_WAVES) void enc_place_emit_kernel(
     pending = (A63 ? pending : 0u) + T63;
   }
 
-  const int64_t stride = cap_z + cap_y;
-  uint32_t* dst32 = (uint32_t*)(out + (size_t)b * stride + (which ? cap_z : 0));
+  const int64_t stride = cap_z + (int64_t)G.K * cap_y;
+  uint32_t* dst32 = (uint32_t*)(out + (size_t)b * stride + (which ? cap_z + (int64_t)seg * cap_y : 0));
   const int64_t cap_bits = (which ? cap_y : cap_z) * 8;
   int overflow = 0;
   // the slice's bits are ORed into an LDS window first: one global atomic per output word instead of one per piece
@@ -941,7 +959,7 @@ __global__ __launch_bounds__(64 * PLACE_WAVES) void enc_place_emit_kernel(
     put_bits(dst32, cap_bits, total, bit, 1, &overflow);
     if (!bit) put_ones(dst32, cap_bits, total + 1, pend, &overflow);
     else if (total + 1 + (int64_t)pend > cap_bits) overflow = 1;
-    lengths[2 * b + which] = (int)((total + 1 + (int64_t)pend + 7) >> 3);
+    *length = (int)((total + 1 + (int64_t)pend + 7) >> 3);
   }
   if (__any(overflow) && lane == 0) atomicOr(err, 4);
 }
@@ -955,6 +973,13 @@ __global__ __launch_bounds__(64 * PLACE_WAVES) void enc_place_emit_kernel(
 // encoder (bulk shifts by clz); `value` takes the same shifts with fresh stream bits, and the
 // m-step E3 correction  v <- 2(v - 2^30) + bit  collapses to flipping the top bit.  Stream
 // bytes are fetched 256 at a time by the wave (zero past the end, like torchac's reader).
+//
+// SEG (dsic_range_decode_seg): one wave per (string, segment).  The 2^lk segments of string b lie back to back from
+// in + b * stride, segment k at byte sum_{j<k} seg_lengths[b][j] (any alignment: the window's big-endian words are
+// funnelled from aligned dwords), and decode C / 2^lk channels each with the string's one support: table rows, symbols
+// and output from k C / 2^lk.  A segment's start and length are cut to what is left of lengths[b], so a forged
+// length reads zeros, never past the string.
+template <bool SEG>
 __global__ __launch_bounds__(256) void range_decode_kernel(const uint8_t* __restrict__ in,
                                                            int64_t stride,
                                                            const int* __restrict__ lengths, int lstride,
@@ -963,21 +988,44 @@ __global__ __launch_bounds__(256) void range_decode_kernel(const uint8_t* __rest
                                                            const uint16_t* __restrict__ tables, int Lmax,
                                                            int C, int HW, float* __restrict__ out,
                                                            int* __restrict__ err, int B,
-                                                           int per_element) {
+                                                           int per_element, const int* __restrict__ seg_lengths,
+                                                           int lk) {
   const int lane = threadIdx.x & 63;
-  const int b = __builtin_amdgcn_readfirstlane(blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6));
+  const int wid = __builtin_amdgcn_readfirstlane(blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6));
+  const int b = SEG ? wid >> lk : wid;
   if (b >= B) return;
   const int smin = meta[4 * b + meta_off], L = meta[4 * b + meta_off + 1];
   if (L > Lmax || L < 1) {
-    if (lane == 0) atomicOr(err, 1);
+    if (lane == 0 && (!SEG || (wid & ((1 << lk) - 1)) == 0)) atomicOr(err, 1);
     return;
   }
   const uint16_t* gt = tables + (size_t)b * (per_element ? (size_t)C * HW : (size_t)C) * Lmax;
   const uint32_t* src32 = (const uint32_t*)(in + (size_t)b * stride);  // stride is a multiple of 4
-  const int nbytes = lengths[b * lstride + loff];
+  int nbytes = lengths[b * lstride + loff];
+  float* dst = out + (size_t)b * C * HW;
+  int sh8 = 0, ndw_all = 0;   // SEG: 8 x the segment's byte offset inside its first dword; dwords of the whole string
+  if (SEG) {
+    const int k = wid & ((1 << lk) - 1);
+    const uint32_t total = nbytes < 0 ? 0u : (uint32_t)nbytes;
+    uint32_t soff = 0;
+    for (int j = 0; j < k; ++j) {
+      const int lj = seg_lengths[((size_t)b << lk) + j];
+      const uint32_t left = total - soff;
+      soff += lj < 0 ? 0u : ((uint32_t)lj < left ? (uint32_t)lj : left);
+    }
+    const int lkk = seg_lengths[((size_t)b << lk) + k];
+    const uint32_t left = total - soff;
+    nbytes = (int)(lkk < 0 ? 0u : ((uint32_t)lkk < left ? (uint32_t)lkk : left));
+    ndw_all = (int)((total + 3u) >> 2);
+    src32 += soff >> 2;
+    ndw_all -= (int)(soff >> 2);
+    sh8 = (int)(soff & 3u) * 8;
+    C >>= lk;
+    gt += (size_t)k * (per_element ? (size_t)C * HW : (size_t)C) * Lmax;
+    dst += (size_t)k * C * HW;
+  }
   const int ndw = (nbytes + 3) >> 2;
   const int64_t n = (int64_t)C * HW;
-  float* dst = out + (size_t)b * n;
 
   // 64-dword window of the stream, big-endian words, bytes >= nbytes read as zero
   auto load_window = [&](int w0) -> uint32_t {
@@ -985,6 +1033,10 @@ __global__ __launch_bounds__(256) void range_decode_kernel(const uint8_t* __rest
     uint32_t v = 0;
     if (k < ndw) {
       v = __builtin_bswap32(src32[k]);
+      if (SEG && sh8) {   // word k of the segment straddles dwords k and k + 1 of the string
+        const uint32_t nx = k + 1 < ndw_all ? __builtin_bswap32(src32[k + 1]) : 0u;
+        v = (v << sh8) | (nx >> (32 - sh8));
+      }
       const int valid = nbytes - 4 * k;  // 1..4 valid bytes in the last dword
       if (valid < 4) v &= 0xFFFFFFFFu << (8 * (4 - valid));
     }
@@ -1249,49 +1301,65 @@ extern "C" int dsic_range_encode(const float* y_nchw, const float* z_nchw, const
 }
 
 // Split encoder (pack -> chain -> place): the same bytes, lengths and error bits as dsic_range_encode.
-static int64_t place_records(int B, int64_t ny, int64_t nz) {
+static int64_t place_records(int B, int64_t ns, int64_t nz, int segs) {
   int gy, ky, gz, kz;
-  place_slicing(ny, gy, ky);
+  place_slicing(ns, gy, ky);
   place_slicing(nz, gz, kz);
-  return (int64_t)B * (ky + kz);
+  return (int64_t)B * ((int64_t)segs * ky + kz);
 }
 
-extern "C" int64_t dsic_range_encode_workspace_size(int B, int M, int HWy, int N, int HWz) {
-  if (B <= 0 || M <= 0 || HWy <= 0 || N <= 0 || HWz <= 0) return -1;
+// y segments per image: a power of two up to 16 that divides the channels
+static bool segs_ok(int segs, int M) {
+  return (segs == 1 || segs == 2 || segs == 4 || segs == 8 || segs == 16) && M % segs == 0;
+}
+
+extern "C" int64_t dsic_range_encode_seg_workspace_size(int B, int M, int HWy, int N, int HWz, int segs) {
+  if (B <= 0 || M <= 0 || HWy <= 0 || N <= 0 || HWz <= 0 || !segs_ok(segs, M)) return -1;
   const int64_t ny = (int64_t)M * HWy, nz = (int64_t)N * HWz;
   const int64_t total = (int64_t)B * (ny + nz);
   // pairs, rec_low, rec_high: 4 B per symbol each; final low per string; 8-byte slice records (+ alignment)
-  return 12 * total + 8 * (int64_t)B + 8 + 8 * place_records(B, ny, nz);
+  return 12 * total + 4 * (int64_t)B * (segs + 1) + 8 + 8 * place_records(B, ny / segs, nz, segs);
 }
 
-extern "C" int dsic_range_encode_ws(const float* y_nchw, const float* z_nchw, const int* meta,
-                                    const uint16_t* tab_y, const uint16_t* tab_z, int Lmax, int B, int M,
-                                    int HWy, int N, int HWz, uint8_t* out, int64_t cap_y, int64_t cap_z,
-                                    int* lengths, int* err, int per_element_y, void* workspace,
-                                    int64_t workspace_bytes, void* stream) {
+extern "C" int64_t dsic_range_encode_workspace_size(int B, int M, int HWy, int N, int HWz) {
+  return dsic_range_encode_seg_workspace_size(B, M, HWy, N, HWz, 1);
+}
+
+// cap_y: the capacity of one y segment (of the y string for segs = 1)
+extern "C" int dsic_range_encode_seg_ws(const float* y_nchw, const float* z_nchw, const int* meta,
+                                        const uint16_t* tab_y, const uint16_t* tab_z, int Lmax, int B, int M,
+                                        int HWy, int N, int HWz, uint8_t* out, int64_t cap_seg, int64_t cap_z,
+                                        int* lengths, int* err, int per_element_y, int segs, void* workspace,
+                                        int64_t workspace_bytes, void* stream) {
+  const int64_t cap_y = cap_seg;
   DSIC_REQUIRE(y_nchw && z_nchw && meta && tab_y && tab_z && out && lengths && err && workspace,
                "range_encode_ws: null pointer");
   DSIC_REQUIRE(B > 0 && M > 0 && N > 0 && HWy > 0 && HWz > 0, "range_encode_ws: empty latent");
+  DSIC_REQUIRE(segs_ok(segs, M), "range_encode_ws: segments=%d must be 1, 2, 4, 8 or 16 and divide M=%d", segs, M);
   DSIC_REQUIRE(cap_y % 4 == 0 && cap_z % 4 == 0 && cap_y >= 8 && cap_z >= 8,
                "range_encode_ws: capacities must be multiples of 4 and >= 8");
-  DSIC_REQUIRE(workspace_bytes >= dsic_range_encode_workspace_size(B, M, HWy, N, HWz),
+  DSIC_REQUIRE(workspace_bytes >= dsic_range_encode_seg_workspace_size(B, M, HWy, N, HWz, segs),
                "range_encode_ws: workspace too small");
   err = abl_err(err);
   SplitGeom G;
   G.B = B; G.M = M; G.HWy = HWy; G.N = N; G.HWz = HWz; G.Lmax = Lmax; G.per_element_y = per_element_y ? 1 : 0;
+  G.K = segs;
+  G.lk = __builtin_ctz((unsigned)segs);
   G.ny = (int64_t)M * HWy;
   G.nz = (int64_t)N * HWz;
+  G.ns = G.ny / segs;
   DSIC_REQUIRE(G.ny < ((int64_t)1 << 29) && G.nz < ((int64_t)1 << 29), "range_encode_ws: string too long");
-  place_slicing(G.ny, G.gy, G.ky);
+  place_slicing(G.ns, G.gy, G.ky);
   place_slicing(G.nz, G.gz, G.kz);
-  const int64_t nslices = (int64_t)B * (G.ky + G.kz);
-  DSIC_REQUIRE(nslices < ((int64_t)1 << 30), "range_encode_ws: too many strings");
+  const int64_t nstrings = (int64_t)B * (segs + 1);
+  const int64_t nslices = (int64_t)B * ((int64_t)segs * G.ky + G.kz);
+  DSIC_REQUIRE(nslices < ((int64_t)1 << 30) && nstrings < ((int64_t)1 << 30), "range_encode_ws: too many strings");
   const int64_t total = (int64_t)B * (G.ny + G.nz);
   uint32_t* pairs = (uint32_t*)workspace;
   uint32_t* rec_low = pairs + total;
   uint32_t* rec_high = rec_low + total;
   uint32_t* final_low = rec_high + total;
-  uint2* slices = (uint2*)(((uintptr_t)(final_low + 2 * B) + 7) & ~(uintptr_t)7);
+  uint2* slices = (uint2*)(((uintptr_t)(final_low + nstrings) + 7) & ~(uintptr_t)7);
   hipStream_t st = (hipStream_t)stream;
   int rc = DSIC_OK;
   if (!(ENC_ABL & 4)) {
@@ -1303,8 +1371,8 @@ extern "C" int dsic_range_encode_ws(const float* y_nchw, const float* z_nchw, co
     if (rc != DSIC_OK) return rc;
   }
   if (!(ENC_ABL & 16)) {
-    // strings 0..B-1 (the long y strings) first; one wave per workgroup
-    hipLaunchKernelGGL(enc_chain_kernel, dim3(2 * B), dim3(64), 0, st, pairs, meta, G, rec_low, rec_high, final_low);
+    // the y strings (the long ones) first; one wave per workgroup
+    hipLaunchKernelGGL(enc_chain_kernel, dim3((unsigned)nstrings), dim3(64), 0, st, pairs, meta, G, rec_low, rec_high, final_low);
     rc = check_launch("range_encode_ws: chain");
     if (rc != DSIC_OK) return rc;
   }
@@ -1321,6 +1389,15 @@ extern "C" int dsic_range_encode_ws(const float* y_nchw, const float* z_nchw, co
   return rc;
 }
 
+extern "C" int dsic_range_encode_ws(const float* y_nchw, const float* z_nchw, const int* meta,
+                                    const uint16_t* tab_y, const uint16_t* tab_z, int Lmax, int B, int M,
+                                    int HWy, int N, int HWz, uint8_t* out, int64_t cap_y, int64_t cap_z,
+                                    int* lengths, int* err, int per_element_y, void* workspace,
+                                    int64_t workspace_bytes, void* stream) {
+  return dsic_range_encode_seg_ws(y_nchw, z_nchw, meta, tab_y, tab_z, Lmax, B, M, HWy, N, HWz, out, cap_y, cap_z,
+                                  lengths, err, per_element_y, 1, workspace, workspace_bytes, stream);
+}
+
 extern "C" int dsic_range_decode(const uint8_t* in, int64_t stride, const int* lengths, int lstride,
                                  int loff, const int* meta, int meta_off, const uint16_t* tables,
                                  int Lmax, int B, int C, int HW, int per_element, float* out_nchw,
@@ -1330,9 +1407,27 @@ extern "C" int dsic_range_decode(const uint8_t* in, int64_t stride, const int* l
   DSIC_REQUIRE(meta_off == 0 || meta_off == 2, "range_decode: meta_off must be 0 (y) or 2 (z)");
   DSIC_REQUIRE(stride % 4 == 0, "range_decode: stride must be a multiple of 4");
   // one wave per workgroup: a decoder wave has its CU's scalar unit to itself (as the encoder's waves)
-  hipLaunchKernelGGL(range_decode_kernel, dim3(B), dim3(64), 0, (hipStream_t)stream, in, stride,
-                     lengths, lstride, loff, meta, meta_off, tables, Lmax, C, HW, out_nchw, err, B, per_element ? 1 : 0);
+  hipLaunchKernelGGL(range_decode_kernel<false>, dim3(B), dim3(64), 0, (hipStream_t)stream, in, stride,
+                     lengths, lstride, loff, meta, meta_off, tables, Lmax, C, HW, out_nchw, err, B, per_element ? 1 : 0,
+                     (const int*)nullptr, 0);
   return check_launch("range_decode");
+}
+
+extern "C" int dsic_range_decode_seg(const uint8_t* in, int64_t stride, const int* lengths, int lstride, int loff,
+                                     const int* seg_lengths, int segs, const int* meta, int meta_off,
+                                     const uint16_t* tables, int Lmax, int B, int C, int HW, int per_element,
+                                     float* out_nchw, int* err, void* stream) {
+  DSIC_REQUIRE(in && lengths && seg_lengths && meta && tables && out_nchw && err, "range_decode_seg: null pointer");
+  DSIC_REQUIRE(B > 0 && C > 0 && HW > 0 && Lmax >= 1, "range_decode_seg: bad argument");
+  DSIC_REQUIRE(segs_ok(segs, C), "range_decode_seg: segments=%d must be 1, 2, 4, 8 or 16 and divide C=%d", segs, C);
+  DSIC_REQUIRE((int64_t)B * segs < ((int64_t)1 << 30), "range_decode_seg: too many strings");
+  DSIC_REQUIRE(meta_off == 0 || meta_off == 2, "range_decode_seg: meta_off must be 0 (y) or 2 (z)");
+  DSIC_REQUIRE(stride % 4 == 0 && ((uintptr_t)in & 3) == 0, "range_decode_seg: in and stride must be multiples of 4");
+  // one wave per workgroup and per (string, segment)
+  hipLaunchKernelGGL(range_decode_kernel<true>, dim3(B * segs), dim3(64), 0, (hipStream_t)stream, in, stride, lengths,
+                     lstride, loff, meta, meta_off, tables, Lmax, C, HW, out_nchw, err, B, per_element ? 1 : 0,
+                     seg_lengths, __builtin_ctz((unsigned)segs));
+  return check_launch("range_decode_seg");
 }
 
 // A HIP stream restricted to a subset of the compute units (mask bit i = CU i

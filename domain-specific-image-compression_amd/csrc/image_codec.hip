@@ -243,24 +243,32 @@ __global__ __launch_bounds__(256) void stitch_u8_kernel(const float* __restrict_
 
 // ---- DSIC2 container --------------------------------------------------------------------------------------
 // magic(6) | tag u32 | B,My,Hy,Wy,Nz,Hz,Wz u32 | B x (min_y,max_y,min_z,max_z i32, len_z,len_y u32) | strings
+// DSIC3 (K > 1 segments per y string): magic "DSIC3\0" | the same fields | segs u32 | the same records (len_y = the sum
+// of the segments) | B x K u32 segment lengths | per image the z string, then the K segments
 constexpr int kHeadBytes = 38, kRecBytes = 24;
+__host__ __device__ inline int head_bytes(int K) { return K > 1 ? kHeadBytes + 4 : kHeadBytes; }
+__host__ __device__ inline int64_t body_offset(int B, int K) {
+  return head_bytes(K) + (int64_t)kRecBytes * B + (K > 1 ? (int64_t)4 * B * K : 0);
+}
 
 __device__ __forceinline__ void put_u32(uint8_t* p, int byte, uint32_t v) { *p = (uint8_t)(v >> (8 * byte)); }
 __device__ __forceinline__ int64_t clamp_len(int v, int64_t cap) { return v < 0 ? 0 : (v > cap ? cap : v); }
 
-// one workgroup: header, records, exclusive scan of the 2B string lengths (z0, y0, z1, ...) into ws[2..2+2B];
-// ws[0] = container bytes, ws[1] = the coder's error word
+// one workgroup: header, records, exclusive scan of the B (1 + K) string lengths (z0, y0 segments, z1, ...) into
+// ws[2..2+B(1+K)]; ws[0] = container bytes, ws[1] = the coder's error word.  lengths [B][1 + K], cap_y the capacity of
+// one y segment; K = 1 writes DSIC2.
 __global__ __launch_bounds__(256) void pack_head_kernel(const int* __restrict__ lengths, const int* __restrict__ meta,
-                                                        const int* __restrict__ err, int B, int64_t cap_z,
+                                                        const int* __restrict__ err, int B, int K, int64_t cap_z,
                                                         int64_t cap_y, uint32_t tag, int My, int Hy, int Wy, int Nz,
                                                         int Hz, int Wz, long long* __restrict__ ws,
                                                         uint8_t* __restrict__ out) {
   __shared__ long long lds4[4];
   const int tid = threadIdx.x;
-  if (tid < kHeadBytes) {
-    const char magic[6] = {'D', 'S', 'I', 'C', '2', 0};
-    const uint32_t f[8] = {tag, (uint32_t)B, (uint32_t)My, (uint32_t)Hy, (uint32_t)Wy, (uint32_t)Nz, (uint32_t)Hz,
-                           (uint32_t)Wz};
+  const int hb = head_bytes(K), S = 1 + K;
+  if (tid < hb) {
+    const char magic[6] = {'D', 'S', 'I', 'C', K > 1 ? '3' : '2', 0};
+    const uint32_t f[9] = {tag, (uint32_t)B, (uint32_t)My, (uint32_t)Hy, (uint32_t)Wy, (uint32_t)Nz, (uint32_t)Hz,
+                           (uint32_t)Wz, (uint32_t)K};
     if (tid < 6) out[tid] = (uint8_t)magic[tid];
     else put_u32(out + tid, (tid - 6) & 3, f[(tid - 6) >> 2]);
   }
@@ -273,36 +281,46 @@ __global__ __launch_bounds__(256) void pack_head_kernel(const int* __restrict__ 
       case 1: v = (uint32_t)(m[0] + m[1] - 1); break;
       case 2: v = (uint32_t)m[2]; break;
       case 3: v = (uint32_t)(m[2] + m[3] - 1); break;
-      case 4: v = (uint32_t)clamp_len(lengths[2 * b], cap_z); break;
-      default: v = (uint32_t)clamp_len(lengths[2 * b + 1], cap_y); break;
+      case 4: v = (uint32_t)clamp_len(lengths[S * b], cap_z); break;
+      default:
+        v = 0;
+        for (int j = 1; j <= K; ++j) v += (uint32_t)clamp_len(lengths[S * b + j], cap_y);
+        break;
     }
-    put_u32(out + kHeadBytes + i, k & 3, v);
+    put_u32(out + hb + i, k & 3, v);
+  }
+  if (K > 1) {
+    for (int i = tid; i < 4 * B * K; i += blockDim.x) {
+      const int e = i >> 2, b = e / K, j = e - b * K;
+      put_u32(out + hb + (int64_t)kRecBytes * B + i, i & 3, (uint32_t)clamp_len(lengths[S * b + 1 + j], cap_y));
+    }
   }
   long long carry = 0;
-  for (int s0 = 0; s0 < 2 * B; s0 += blockDim.x) {
+  for (int s0 = 0; s0 < S * B; s0 += blockDim.x) {
     const int s = s0 + tid;
-    const long long v = s < 2 * B ? clamp_len(lengths[s], (s & 1) ? cap_y : cap_z) : 0;
+    const long long v = s < S * B ? clamp_len(lengths[s], (s % S) ? cap_y : cap_z) : 0;
     long long tot;
     const long long ex = block_exclusive_scan(v, lds4, &tot);
-    if (s < 2 * B) ws[2 + s] = carry + ex;
+    if (s < S * B) ws[2 + s] = carry + ex;
     carry += tot;
   }
   if (tid == 0) {
-    ws[2 + 2 * B] = carry;
-    ws[0] = kHeadBytes + (long long)kRecBytes * B + carry;
+    ws[2 + S * B] = carry;
+    ws[0] = body_offset(B, K) + carry;
     ws[1] = err ? *err : 0;
   }
 }
 
-// blockIdx.y = string s (image s/2, z if even, y if odd); blockIdx.x = slice of it
+// blockIdx.y = string s (image s / (1 + K); the z string, then the K segments); blockIdx.x = slice of it
 __global__ __launch_bounds__(256) void pack_strings_kernel(const uint8_t* __restrict__ bytes,
-                                                           const int* __restrict__ lengths, int B, int64_t cap_z,
-                                                           int64_t cap_y, const long long* __restrict__ ws,
+                                                           const int* __restrict__ lengths, int B, int K,
+                                                           int64_t cap_z, int64_t cap_y,
+                                                           const long long* __restrict__ ws,
                                                            uint8_t* __restrict__ out) {
-  const int s = blockIdx.y, b = s >> 1, which = s & 1;
-  const uint8_t* src = bytes + (size_t)b * (cap_z + cap_y) + (which ? cap_z : 0);
-  const int64_t n = clamp_len(lengths[s], which ? cap_y : cap_z);
-  copy_bytes(out + kHeadBytes + (int64_t)kRecBytes * B + ws[2 + s], src, n, blockIdx.x, gridDim.x);
+  const int s = blockIdx.y, b = s / (1 + K), j = s - b * (1 + K);
+  const uint8_t* src = bytes + (size_t)b * (cap_z + K * cap_y) + (j ? cap_z + (int64_t)(j - 1) * cap_y : 0);
+  const int64_t n = clamp_len(lengths[s], j ? cap_y : cap_z);
+  copy_bytes(out + body_offset(B, K) + ws[2 + s], src, n, blockIdx.x, gridDim.x);
 }
 
 __device__ __forceinline__ uint32_t get_u32(const uint8_t* p) {
@@ -478,13 +496,35 @@ extern "C" int dsic_container_pack(const uint8_t* bytes, int64_t cap_z, int64_t 
   DSIC_REQUIRE(B <= 32767, "container_pack: at most 32767 images per container");
   hipStream_t st = (hipStream_t)stream;
   long long* ws = (long long*)workspace;
-  hipLaunchKernelGGL(pack_head_kernel, dim3(1), dim3(256), 0, st, lengths, meta, err, B, cap_z, cap_y, tag, My, Hy,
+  hipLaunchKernelGGL(pack_head_kernel, dim3(1), dim3(256), 0, st, lengths, meta, err, B, 1, cap_z, cap_y, tag, My, Hy,
                      Wy, Nz, Hz, Wz, ws, out);
   const int rc = check_launch("container_pack(head)");
   if (rc) return rc;
   hipLaunchKernelGGL(pack_strings_kernel, dim3(string_parts(cap_z > cap_y ? cap_z : cap_y), 2 * B), dim3(256), 0,
-                     st, bytes, lengths, B, cap_z, cap_y, (const long long*)ws, out);
+                     st, bytes, lengths, B, 1, cap_z, cap_y, (const long long*)ws, out);
   return check_launch("container_pack(strings)");
+}
+
+extern "C" int dsic_container_pack_seg(const uint8_t* bytes, int64_t cap_z, int64_t cap_seg, int segs,
+                                       const int* lengths, const int* meta, const int* err, int B, uint32_t tag,
+                                       int My, int Hy, int Wy, int Nz, int Hz, int Wz, int64_t* workspace,
+                                       uint8_t* out, void* stream) {
+  DSIC_REQUIRE(bytes && lengths && meta && workspace && out, "container_pack_seg: null pointer");
+  DSIC_REQUIRE(B > 0 && cap_z > 0 && cap_seg > 0 && cap_z % 4 == 0 && cap_seg % 4 == 0,
+               "container_pack_seg: bad shape (B=%d cap_z=%lld cap_seg=%lld)", B, (long long)cap_z, (long long)cap_seg);
+  DSIC_REQUIRE((segs == 2 || segs == 4 || segs == 8 || segs == 16) && My > 0 && My % segs == 0,
+               "container_pack_seg: segments=%d must be 2, 4, 8 or 16 and divide My=%d", segs, My);
+  DSIC_REQUIRE(((uintptr_t)bytes & 3) == 0, "container_pack_seg: bytes must be 4-byte aligned");
+  DSIC_REQUIRE((int64_t)B * (1 + segs) <= 65535, "container_pack_seg: at most 65535 strings per container");
+  hipStream_t st = (hipStream_t)stream;
+  long long* ws = (long long*)workspace;
+  hipLaunchKernelGGL(pack_head_kernel, dim3(1), dim3(256), 0, st, lengths, meta, err, B, segs, cap_z, cap_seg, tag, My,
+                     Hy, Wy, Nz, Hz, Wz, ws, out);
+  const int rc = check_launch("container_pack_seg(head)");
+  if (rc) return rc;
+  hipLaunchKernelGGL(pack_strings_kernel, dim3(string_parts(cap_z > cap_seg ? cap_z : cap_seg), (1 + segs) * B),
+                     dim3(256), 0, st, bytes, lengths, B, segs, cap_z, cap_seg, (const long long*)ws, out);
+  return check_launch("container_pack_seg(strings)");
 }
 
 extern "C" int dsic_container_scatter(const uint8_t* blob, int64_t blob_bytes, int B, int64_t max_len, uint8_t* zbuf,

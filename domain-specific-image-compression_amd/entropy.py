@@ -111,9 +111,23 @@ def _cap(n):
     return (2 * n + 16 + 3) // 4 * 4   # <= 16 bits per symbol + flush, multiple of 4
 
 
+SEGMENTS = (1, 2, 4, 8, 16)
+
+
+def check_segments(segments, M, what):
+    """segments as an int: one of SEGMENTS that divides the M channels of y, else ValueError."""
+    try:
+        K = int(segments)
+    except (TypeError, ValueError):
+        K = -1
+    if K != segments or K not in SEGMENTS or int(M) % K:
+        raise ValueError(f"{what}: segments={segments!r} must be one of {SEGMENTS} and divide M={M}")
+    return K
+
+
 @torch.no_grad()
 def compress_latents(y_tilde, z_tilde, sigma_y, nu_y, sigma_z, tail=10, Lmax=DEFAULT_LMAX, streams_per_wg=1,
-                     split=None):
+                     split=None, segments=1):
     """Device-resident compress of already computed latents.
 
     y_tilde [B,M,Hy,Wy], z_tilde [B,N,Hz,Wz] integer-valued (quant_mode="round");
@@ -121,22 +135,38 @@ def compress_latents(y_tilde, z_tilde, sigma_y, nu_y, sigma_z, tail=10, Lmax=DEF
     bytes uint8 [B, cap_z+cap_y], lengths int32 [B,2] (z,y), meta int32 [B,4],
     cap_z, cap_y, tab_y, tab_z, err.  Nothing synchronises with the host.
     split: the split encoder (default SPLIT_CODER; streams_per_wg > 1 always uses the single kernel).
+    segments = K > 1 (one of SEGMENTS, dividing M; the split encoder only): the y string of an image is coded as K
+    independent strings, one per group of M / K channels, with the same support and tables.  Then bytes is
+    [B, cap_z + K * cap_y] with segment k at cap_z + k * cap_y (cap_y the capacity of one segment) and lengths is
+    [B, 1 + K] (z, y segment 0 .. K - 1); the dict carries "segments" either way.
     """
     y = _f32c(y_tilde, "compress")
     z = _f32c(z_tilde, "compress")
     B, M, Hy, Wy = y.shape
     _, N, Hz, Wz = z.shape
     dev = y.device
+    K = check_segments(segments, M, "compress_latents")
+    use_split = bool(SPLIT_CODER if split is None else split) and int(streams_per_wg) == 1
+    if K > 1 and not use_split:
+        raise ValueError("compress_latents: segments > 1 needs the split encoder (split=False, DSIC_SPLIT_CODER=0 or "
+                         "streams_per_wg > 1 select the single kernel, which codes whole strings)")
     per_element = sigma_y.dim() == 4        # spatial_params: a table row per latent element
     meta = latent_support(y, z, tail)
     tab_y, tab_z, err = cdf_tables(sigma_y, nu_y, sigma_z, meta, Lmax)
-    cap_y, cap_z = _cap(M * Hy * Wy), _cap(N * Hz * Wz)
+    cap_y, cap_z = _cap(M * Hy * Wy // K), _cap(N * Hz * Wz)
     # the coder ORs its bits in: zero-filled, as 32-bit words (a byte fill kernel takes 4x the elements)
-    out = torch.zeros((B, (cap_z + cap_y) // 4), dtype=torch.int32, device=dev).view(torch.uint8)
-    lengths = torch.zeros((B, 2), dtype=torch.int32, device=dev)
+    out = torch.zeros((B, (cap_z + K * cap_y) // 4), dtype=torch.int32, device=dev).view(torch.uint8)
+    lengths = torch.zeros((B, 1 + K), dtype=torch.int32, device=dev)
     L = _lib.load()
     ws = None
-    if (SPLIT_CODER if split is None else split) and int(streams_per_wg) == 1:
+    if K > 1:
+        nbytes = L.dsic_range_encode_seg_workspace_size(B, M, Hy * Wy, N, Hz * Wz, K)
+        ws = torch.empty(((nbytes + 3) // 4,), dtype=torch.int32, device=dev)
+        _lib.check(L.dsic_range_encode_seg_ws(_p(y), _p(z), _p(meta), _p(tab_y), _p(tab_z), Lmax, B, M, Hy * Wy,
+                                              N, Hz * Wz, _p(out), cap_y, cap_z, _p(lengths), _p(err),
+                                              int(per_element), K, _p(ws), ws.numel() * 4, _stream()),
+                   "range_encode_seg_ws")
+    elif use_split:
         nbytes = L.dsic_range_encode_workspace_size(B, M, Hy * Wy, N, Hz * Wz)
         # the caching allocator on the coder's stream: every call in flight has its own
         ws = torch.empty(((nbytes + 3) // 4,), dtype=torch.int32, device=dev)
@@ -147,7 +177,7 @@ def compress_latents(y_tilde, z_tilde, sigma_y, nu_y, sigma_z, tail=10, Lmax=DEF
         _lib.check(L.dsic_range_encode(_p(y), _p(z), _p(meta), _p(tab_y), _p(tab_z), Lmax, B, M, Hy * Wy,
                                        N, Hz * Wz, _p(out), cap_y, cap_z, _p(lengths), _p(err),
                                        int(streams_per_wg), int(per_element), _stream()), "range_encode")
-    return {"bytes": out, "lengths": lengths, "meta": meta, "cap_z": cap_z, "cap_y": cap_y,
+    return {"bytes": out, "lengths": lengths, "meta": meta, "cap_z": cap_z, "cap_y": cap_y, "segments": K,
             "tab_y": tab_y, "tab_z": tab_z, "err": err, "shape_y": list(y.shape), "shape_z": list(z.shape)}
 
 
@@ -187,9 +217,10 @@ class AsyncCompressor:
     coder of batch i, so a coder that takes longer than one step (512x512 patches: 196 608 y symbols
     per string, a serial chain) still keeps up - its latency is hidden, its throughput doubles."""
 
-    def __init__(self, model, tail=10, Lmax=DEFAULT_LMAX, stream=None, streams_per_wg=1, depth=1):
+    def __init__(self, model, tail=10, Lmax=DEFAULT_LMAX, stream=None, streams_per_wg=1, depth=1, segments=1):
         self.model, self.tail, self.Lmax = model, tail, Lmax
         self.streams_per_wg = streams_per_wg
+        self.segments = check_segments(segments, model.M, "AsyncCompressor")   # y segments (compress_latents)
         self.streams = [stream if stream is not None else torch.cuda.Stream()]
         self.streams += [torch.cuda.Stream() for _ in range(max(1, int(depth)) - 1)]
         self.stream = self.streams[0]
@@ -238,7 +269,7 @@ class AsyncCompressor:
             else:
                 done = torch.cuda.Event()
             self.last = compress_latents(tensors[0], tensors[1], tensors[2], tensors[3], self._sigma_z,
-                                         self.tail, self.Lmax, self.streams_per_wg)
+                                         self.tail, self.Lmax, self.streams_per_wg, segments=self.segments)
             done.record(side)
             if self.timing:
                 self.times.append((e0, done))
@@ -278,9 +309,10 @@ def numerics_tag() -> int:
             | ((int(_lib.load().dsic_abi_version()) & 0xFFFF) << 16))
 
 
-def _coded_batch(model, x, tail, Lmax, what, pack=False):
+def _coded_batch(model, x, tail, Lmax, what, pack=False, segments=1):
     """forward(round) and the range coder of custom_compress, with its Lmax retry.  pack=True also writes the DSIC2
     container on the device (_pack_on_device) and learns the error word with the container's size, one copy."""
+    segments = check_segments(segments, model.M, what)
     out = model(x, quant_mode="round")
     sigma_z = sigma_z_of(model)                                        # :32 (no clamp)
     if getattr(model, "spatial_params", False):
@@ -289,7 +321,7 @@ def _coded_batch(model, x, tail, Lmax, what, pack=False):
         Lmax = min(1000, _tight_lmax(latent_support(out["y_tilde"], out["z_tilde"], tail)))
     while True:
         c = compress_latents(out["y_tilde"], out["z_tilde"], _per_channel(out["sigma"]),
-                             _per_channel(out["nu"]), sigma_z, tail, Lmax)
+                             _per_channel(out["nu"]), sigma_z, tail, Lmax, segments=segments)
         if pack:
             c["container"], c["container_bytes"], code = _pack_on_device(c, numerics_tag())
         else:
@@ -304,19 +336,25 @@ def _coded_batch(model, x, tail, Lmax, what, pack=False):
 
 
 @torch.no_grad()
-def custom_compress(model, x, tail=10, Lmax=DEFAULT_LMAX):
+def custom_compress(model, x, tail=10, Lmax=DEFAULT_LMAX, segments=1):
     """eval_selfcontained_entropy.py:26-74.  Returns the reference's dict:
-    strings [[z_bytes, y_bytes], ...], shape_y, shape_z, min_y, max_y, min_z, max_z."""
-    c = _coded_batch(model, x, tail, Lmax, "custom_compress")
+    strings [[z_bytes, y_bytes], ...], shape_y, shape_z, min_y, max_y, min_z, max_z.
+    segments = K > 1: y_bytes is the K segment strings of compress_latents joined, and the dict gains "segments" and
+    "seg_lengths_y" (per image the K lengths)."""
+    c = _coded_batch(model, x, tail, Lmax, "custom_compress", segments=segments)
+    K = c["segments"]
     lengths = c["lengths"].cpu().numpy()
     meta = c["meta"].cpu().numpy()
     raw = c["bytes"].cpu().numpy()
     strings = []
     for b in range(raw.shape[0]):
         zs = raw[b, :lengths[b, 0]].tobytes()
-        ys = raw[b, c["cap_z"]:c["cap_z"] + lengths[b, 1]].tobytes()
+        ys = b"".join(raw[b, c["cap_z"] + k * c["cap_y"]:c["cap_z"] + k * c["cap_y"] + lengths[b, 1 + k]].tobytes()
+                      for k in range(K))
         strings.append([zs, ys])
+    seg = {"segments": K, "seg_lengths_y": [[int(v) for v in lengths[b, 1:]] for b in range(raw.shape[0])]}
     return {
+        **(seg if K > 1 else {}),
         "strings": strings,
         "shape_y": c["shape_y"], "shape_z": c["shape_z"],
         "min_y": [int(m[0]) for m in meta], "max_y": [int(m[0] + m[1] - 1) for m in meta],
@@ -341,14 +379,27 @@ def _refuse_tag(tag, what):
                            "not match and the latents would decode to garbage)")
 
 
+def _dict_segments(compressed, what):
+    """(K, per image the K segment lengths) of a custom_compress dict; ValueError where they contradict its strings."""
+    K = check_segments(compressed.get("segments", 1), compressed["shape_y"][1], what)
+    if K == 1:
+        return 1, [[len(s[1])] for s in compressed["strings"]]
+    seg = [[int(v) for v in row] for row in compressed["seg_lengths_y"]]
+    if len(seg) != len(compressed["strings"]) or any(
+            len(row) != K or min(row) < 0 or sum(row) != len(s[1]) for row, s in zip(seg, compressed["strings"])):
+        raise ValueError(f"{what}: seg_lengths_y must hold {K} lengths per image that add up to its y string")
+    return K, seg
+
+
 def _default_lmax(model, meta_np):
     Lmax = int(meta_np[:, [1, 3]].max())
     return (Lmax + 7) // 8 * 8 if getattr(model, "spatial_params", False) else max(DEFAULT_LMAX, Lmax)
 
 
-def _decode_batch(model, shape_y, shape_z, meta, Lmax, z, y, what):
+def _decode_batch(model, shape_y, shape_z, meta, Lmax, z, y, what, segments=1, seg_lengths=None):
     """:76-120 from strings already on the device: z / y = (buffer, stride, lengths, lstride, loff) as
-    dsic_range_decode takes them.  Returns g_s's output, not yet clamped."""
+    dsic_range_decode takes them; segments = K > 1: every y string is K segments back to back, seg_lengths the device
+    int32 [B, K] of their lengths (dsic_range_decode_seg).  Returns g_s's output, not yet clamped."""
     dev = meta.device
     B, M, Hy, Wy = shape_y
     _, N, Hz, Wz = shape_z
@@ -371,8 +422,13 @@ def _decode_batch(model, shape_y, shape_z, meta, Lmax, z, y, what):
                                          rows, Lmax, _p(err), _stream()), "cdf_tables_student")
     ybuf, ystride, ylen, yls, ylo = y
     y_hat = torch.empty((B, M, Hy, Wy), dtype=torch.float32, device=dev)
-    _lib.check(L.dsic_range_decode(_p(ybuf), ystride, _p(ylen), yls, ylo, _p(meta), 0, _p(tab_y), Lmax, B, M,
-                                   Hy * Wy, per_element, _p(y_hat), _p(err), _stream()), "range_decode(y)")
+    if segments > 1:
+        _lib.check(L.dsic_range_decode_seg(_p(ybuf), ystride, _p(ylen), yls, ylo, _p(seg_lengths), segments, _p(meta),
+                                           0, _p(tab_y), Lmax, B, M, Hy * Wy, per_element, _p(y_hat), _p(err),
+                                           _stream()), "range_decode_seg(y)")
+    else:
+        _lib.check(L.dsic_range_decode(_p(ybuf), ystride, _p(ylen), yls, ylo, _p(meta), 0, _p(tab_y), Lmax, B, M,
+                                       Hy * Wy, per_element, _p(y_hat), _p(err), _stream()), "range_decode(y)")
     _check_err(err, what)
     return model.g_s.forward_nhwc(ops.nchw_to_nhwc(y_hat))            # :120
 
@@ -390,10 +446,13 @@ def custom_decompress(model, compressed, Lmax=None):
     if Lmax is None:
         Lmax = _default_lmax(model, meta_np)
     meta = torch.from_numpy(meta_np).to(dev)
+    K, seg = _dict_segments(compressed, "custom_decompress")
     zbuf, zlen, zstride = _upload_strings(strings, 0, dev)
     ybuf, ylen, ystride = _upload_strings(strings, 1, dev)
+    seg_lengths = torch.tensor(seg, dtype=torch.int32, device=dev) if K > 1 else None
     x_hat = _decode_batch(model, compressed["shape_y"], compressed["shape_z"], meta, Lmax,
-                          (zbuf, zstride, zlen, 1, 0), (ybuf, ystride, ylen, 1, 0), "custom_decompress")
+                          (zbuf, zstride, zlen, 1, 0), (ybuf, ystride, ylen, 1, 0), "custom_decompress", K,
+                          seg_lengths)
     return x_hat.clamp(0, 1)                                           # :123
 
 
@@ -407,58 +466,93 @@ def real_bpp(compressed, H, W):
 # this is that dict as one byte string, so the strings can leave the process ------------------
 _MAGIC = b"DSIC2\x00"      # DSIC1: rounds 1-2, no numerics tag (float64 / float32 tables both wrote it: not decodable
 _MAGIC_V1 = b"DSIC1\x00"   # safely any more, refused)
+_MAGIC_SEG = b"DSIC3\x00"  # DSIC3: segmented y strings (written only for segments > 1)
 _HEAD = struct.Struct("<6sI7I")      # magic, numerics tag, B, My, Hy, Wy, Nz, Hz, Wz
+_SEGS = struct.Struct("<I")          # DSIC3: segments per y string, behind the head
 _REC = struct.Struct("<4i2I")        # per image: min_y, max_y, min_z, max_z, len_z, len_y
 
 
 def pack_container(compressed) -> bytes:
     """dict of custom_compress -> bytes.  Layout (little endian):
     magic(6) | numerics tag (uint32, numerics_tag()) | B,My,Hy,Wy,Nz,Hz,Wz (7 x uint32) | per image:
-    min_y,max_y,min_z,max_z (4 x int32), len_z,len_y (2 x uint32) | per image: z bytes, y bytes."""
+    min_y,max_y,min_z,max_z (4 x int32), len_z,len_y (2 x uint32) | per image: z bytes, y bytes.
+    A dict with "segments" = K > 1 becomes a DSIC3 container: magic "DSIC3\\0", segs (uint32) behind the head's
+    fields, the same records (len_y = the sum of the image's segments), then B x K uint32 segment lengths in front of
+    the strings (the y bytes are the segments back to back)."""
     B, My, Hy, Wy = compressed["shape_y"]
     _, Nz, Hz, Wz = compressed["shape_z"]
     tag = int(compressed.get("numerics", numerics_tag()))
-    head = [_HEAD.pack(_MAGIC, tag, B, My, Hy, Wy, Nz, Hz, Wz)]
+    K, seg = _dict_segments(compressed, "pack_container")
+    head = [_HEAD.pack(_MAGIC_SEG if K > 1 else _MAGIC, tag, B, My, Hy, Wy, Nz, Hz, Wz)]
+    if K > 1:
+        head.append(_SEGS.pack(K))
     body = []
     for b in range(B):
         zs, ys = compressed["strings"][b]
         head.append(_REC.pack(compressed["min_y"][b], compressed["max_y"][b], compressed["min_z"][b],
                               compressed["max_z"][b], len(zs), len(ys)))
         body += [zs, ys]
+    if K > 1:
+        head.append(struct.pack(f"<{B * K}I", *[v for row in seg for v in row]))
     return b"".join(head + body)
 
 
-def read_container_head(read_at, off, size):
-    """The head and the records of the DSIC2 container that fills bytes [off, off + size) behind read_at(offset, n)
-    (n bytes at an offset: a slice of a blob, or codec._Source.read_at); the strings are not read.  Returns (tag,
-    shape_y, shape_z, per image (min_y, max_y, min_z, max_z, z_off, z_len, y_off, y_len)), offsets as read_at counts
-    them.  ValueError for a DSIC1 container, another magic, and records that do not add up to size."""
+def read_container_segments(read_at, off, size):
+    """The head, the records and (DSIC3) the segment lengths of the container that fills bytes [off, off + size) behind
+    read_at(offset, n) (n bytes at an offset: a slice of a blob, or codec._Source.read_at); the strings are not read.
+    Returns (tag, shape_y, shape_z, per image (min_y, max_y, min_z, max_z, z_off, z_len, y_off, y_len), segs, per
+    image the segs lengths of its y segments), offsets as read_at counts them; a DSIC2 container has segs = 1 and
+    [y_len] per image.  ValueError for a DSIC1 container, another magic, records that do not add up to size, a segs
+    that is not allowed for My, and segment lengths that do not add up to their record's len_y."""
     head = read_at(off, min(size, _HEAD.size))
     if head[:6] == _MAGIC_V1:
         raise ValueError("DSIC1 container: written before the numerics tag existed (its coder tables may be the float64 "
                          "ones of round 1); re-encode")
-    if len(head) < _HEAD.size or head[:6] != _MAGIC:
+    if len(head) < _HEAD.size or bytes(head[:6]) not in (_MAGIC, _MAGIC_SEG):
         raise ValueError("not a DSIC container")
     _, tag, B, My, Hy, Wy, Nz, Hz, Wz = _HEAD.unpack(head)
-    if B < 1 or size < _HEAD.size + _REC.size * B:
+    K, recs = 1, off + _HEAD.size
+    if bytes(head[:6]) == _MAGIC_SEG:
+        word = read_at(recs, min(max(size - _HEAD.size, 0), _SEGS.size))
+        if len(word) < _SEGS.size:
+            raise ValueError("truncated or oversized DSIC container")
+        (K,) = _SEGS.unpack(word)
+        recs += _SEGS.size
+        if K not in SEGMENTS[1:] or My % K:
+            raise ValueError(f"DSIC3 container: segs={K} is not one of {SEGMENTS[1:]} dividing My={My}")
+    table = 4 * B * K if K > 1 else 0
+    if B < 1 or off + size < recs + _REC.size * B + table:
         raise ValueError("truncated or oversized DSIC container")
-    pos, images = off + _HEAD.size + _REC.size * B, []
-    for min_y, max_y, min_z, max_z, len_z, len_y in _REC.iter_unpack(read_at(off + _HEAD.size, _REC.size * B)):
+    pos, images = recs + _REC.size * B + table, []
+    for min_y, max_y, min_z, max_z, len_z, len_y in _REC.iter_unpack(read_at(recs, _REC.size * B)):
         images.append((min_y, max_y, min_z, max_z, pos, len_z, pos + len_z, len_y))
         pos += len_z + len_y
     if pos != off + size:
         raise ValueError("truncated or oversized DSIC container")
-    return tag, [B, My, Hy, Wy], [B, Nz, Hz, Wz], images
+    if K > 1:
+        flat = struct.unpack(f"<{B * K}I", read_at(recs + _REC.size * B, table))
+        seg = [list(flat[b * K:(b + 1) * K]) for b in range(B)]
+        if any(sum(row) != r[7] for row, r in zip(seg, images)):
+            raise ValueError("DSIC3 container: segment lengths do not add up to their record's len_y")
+    else:
+        seg = [[r[7]] for r in images]
+    return tag, [B, My, Hy, Wy], [B, Nz, Hz, Wz], images, K, seg
+
+
+def read_container_head(read_at, off, size):
+    """read_container_segments without the segments: (tag, shape_y, shape_z, images) of a DSIC2 or DSIC3 container."""
+    return read_container_segments(read_at, off, size)[:4]
 
 
 def _blob_head(blob):
-    return read_container_head(lambda off, n: blob[off:off + n], 0, len(blob))
+    return read_container_segments(lambda off, n: blob[off:off + n], 0, len(blob))
 
 
 def unpack_container(blob: bytes):
-    """Inverse of pack_container."""
-    tag, shape_y, shape_z, images = _blob_head(blob)
-    return {"strings": [[blob[r[4]:r[4] + r[5]], blob[r[6]:r[6] + r[7]]] for r in images],
+    """Inverse of pack_container (DSIC2 and DSIC3)."""
+    tag, shape_y, shape_z, images, K, seg = _blob_head(blob)
+    return {**({"segments": K, "seg_lengths_y": seg} if K > 1 else {}),
+            "strings": [[blob[r[4]:r[4] + r[5]], blob[r[6]:r[6] + r[7]]] for r in images],
             "shape_y": shape_y, "shape_z": shape_z,
             "min_y": [r[0] for r in images], "max_y": [r[1] for r in images],
             "min_z": [r[2] for r in images], "max_z": [r[3] for r in images], "numerics": tag}
@@ -472,6 +566,16 @@ def _pack_on_device(c, tag):
     _, My, Hy, Wy = c["shape_y"]
     _, Nz, Hz, Wz = c["shape_z"]
     dev = c["bytes"].device
+    K = c["segments"]
+    if K > 1:                                                          # DSIC3
+        out = torch.empty(_HEAD.size + _SEGS.size + (_REC.size + 4 * K) * B + B * (c["cap_z"] + K * c["cap_y"]),
+                          dtype=torch.uint8, device=dev)
+        ws = torch.empty((1 + K) * B + 3, dtype=torch.int64, device=dev)
+        _lib.check(_lib.load().dsic_container_pack_seg(_p(c["bytes"]), c["cap_z"], c["cap_y"], K, _p(c["lengths"]),
+                                                       _p(c["meta"]), _p(c["err"]), B, tag & 0xFFFFFFFF, My, Hy, Wy,
+                                                       Nz, Hz, Wz, _p(ws), _p(out), _stream()), "container_pack_seg")
+        nbytes, code = (int(v) for v in ws[:2].cpu())
+        return out, nbytes, code
     out = torch.empty(_HEAD.size + _REC.size * B + B * (c["cap_z"] + c["cap_y"]), dtype=torch.uint8, device=dev)
     ws = torch.empty(2 * B + 3, dtype=torch.int64, device=dev)
     _lib.check(_lib.load().dsic_container_pack(_p(c["bytes"]), c["cap_z"], c["cap_y"], _p(c["lengths"]), _p(c["meta"]),
@@ -482,10 +586,10 @@ def _pack_on_device(c, tag):
 
 
 @torch.no_grad()
-def compress_to_container(model, x, tail=10, Lmax=DEFAULT_LMAX) -> bytes:
-    """pack_container(custom_compress(model, x, tail, Lmax)), byte for byte, with the container assembled on the
-    device: one copy of exactly the container's bytes leaves the GPU."""
-    c = _coded_batch(model, x, tail, Lmax, "compress_to_container", pack=True)
+def compress_to_container(model, x, tail=10, Lmax=DEFAULT_LMAX, segments=1) -> bytes:
+    """pack_container(custom_compress(model, x, tail, Lmax, segments)), byte for byte, with the container assembled on
+    the device: one copy of exactly the container's bytes leaves the GPU."""
+    c = _coded_batch(model, x, tail, Lmax, "compress_to_container", pack=True, segments=segments)
     return c["container"][:c["container_bytes"]].cpu().numpy().tobytes()
 
 
@@ -510,24 +614,28 @@ def _upload_padded(parts, tail, dev):
     return d[:padded], total, d[padded:]
 
 
-def _decode_selected(model, images, parts, shape_y, shape_z, what, Lmax=None, ride=None):
+def _decode_selected(model, images, parts, shape_y, shape_z, what, Lmax=None, ride=None, segments=1, seg_lengths=None):
     """One decode batch from the strings of n images picked anywhere: images as read_container_head gives them, with
     z_off / y_off counted inside the byte strings `parts` laid back to back; shape_y / shape_z = [n, channels, h, w].
     The strings travel in one padded copy with an int64 control block behind them: descriptors [n][4] (z offset, z
-    length, y offset, y length), meta int32 [n][4] (ymin, Ly, zmin, Lz), then the int32 array `ride` (codec's tile
-    numbers).  The device spreads the strings at custom_decompress's strides (_upload_strings) and decodes with Lmax
+    length, y offset, y length), meta int32 [n][4] (ymin, Ly, zmin, Lz), for segments = K > 1 the int32 [n][K]
+    seg_lengths (per image the lengths of its y segments, which lie back to back in its y string), then the int32
+    array `ride` (codec's tile numbers).  The device spreads the strings at custom_decompress's strides (_upload_strings) and decodes with Lmax
     (default: _default_lmax over these images).  Returns (g_s's output, not yet clamped; the padded string bytes
     uploaded; the device copy of ride)."""
     dev = next(model.parameters()).device
     n = len(images)
     rec = np.array(images, dtype=np.int64).reshape(n, 8)
     ride = np.zeros(0, dtype=np.int32) if ride is None else np.asarray(ride, dtype=np.int32)
-    block = np.zeros(6 * n + (ride.size + 1) // 2, dtype=np.int64)
+    nseg = n * segments if segments > 1 else 0
+    block = np.zeros(6 * n + (nseg + ride.size + 1) // 2, dtype=np.int64)
     block[:4 * n] = rec[:, 4:].ravel()
     meta_np = block[4 * n:6 * n].view(np.int32).reshape(n, 4)
     meta_np[:, 0::2] = rec[:, 0:4:2]
     meta_np[:, 1::2] = rec[:, 1:4:2] - rec[:, 0:4:2] + 1
-    block[6 * n:].view(np.int32)[:ride.size] = ride
+    if nseg:
+        block[6 * n:].view(np.int32)[:nseg] = np.asarray(seg_lengths, dtype=np.int32).reshape(nseg)
+    block[6 * n:].view(np.int32)[nseg:nseg + ride.size] = ride
     d_blob, total, d_block = _upload_padded(parts, block, dev)
     d_block = d_block.view(torch.int64)
     meta = d_block[4 * n:6 * n].view(torch.int32).view(n, 4)
@@ -541,9 +649,10 @@ def _decode_selected(model, images, parts, shape_y, shape_z, what, Lmax=None, ri
                "strings_scatter_select")
     if Lmax is None:
         Lmax = _default_lmax(model, meta_np)
+    tail32 = d_block[6 * n:].view(torch.int32)
     x_hat = _decode_batch(model, shape_y, shape_z, meta, Lmax, (zbuf, zstride, lengths, 2, 0),
-                          (ybuf, ystride, lengths, 2, 1), what)
-    return x_hat, _padded_bytes(total), d_block[6 * n:].view(torch.int32)[:ride.size]
+                          (ybuf, ystride, lengths, 2, 1), what, segments, tail32[:nseg] if nseg else None)
+    return x_hat, _padded_bytes(total), tail32[nseg:nseg + ride.size]
 
 
 @torch.no_grad()
@@ -552,9 +661,9 @@ def decompress_container(model, blob, Lmax=None):
     _decode_selected.  The host reads the header and the 24-byte records; the strings are uploaded once and moved
     into the decoder's buffers on the device."""
     blob = bytes(blob)
-    tag, shape_y, shape_z, images = _blob_head(blob)
+    tag, shape_y, shape_z, images, K, seg = _blob_head(blob)
     _refuse_tag(tag, "decompress_container")
     body = images[0][4]                                                # the strings follow the records
     images = [r[:4] + (r[4] - body, r[5], r[6] - body, r[7]) for r in images]
     return _decode_selected(model, images, [memoryview(blob)[body:]], shape_y, shape_z, "decompress_container",
-                            Lmax)[0].clamp(0, 1)
+                            Lmax, segments=K, seg_lengths=seg)[0].clamp(0, 1)

@@ -89,6 +89,13 @@ SIGNATURES = {
     "dsic_range_encode_workspace_size": (c_int64, [c_int, c_int, c_int, c_int, c_int]),
     "dsic_range_encode_ws": (c_int, [_P, _P, _P, _P, _P, c_int, c_int, c_int, c_int, c_int, c_int, _P,
                                      c_int64, c_int64, _P, _P, c_int, _P, c_int64, _P]),
+    "dsic_range_encode_seg_workspace_size": (c_int64, [c_int, c_int, c_int, c_int, c_int, c_int]),
+    "dsic_range_encode_seg_ws": (c_int, [_P, _P, _P, _P, _P, c_int, c_int, c_int, c_int, c_int, c_int, _P,
+                                         c_int64, c_int64, _P, _P, c_int, c_int, _P, c_int64, _P]),
+    "dsic_range_decode_seg": (c_int, [_P, c_int64, _P, c_int, c_int, _P, c_int, _P, c_int, _P, c_int, c_int, c_int,
+                                      c_int, c_int, _P, _P, _P]),
+    "dsic_container_pack_seg": (c_int, [_P, c_int64, c_int64, c_int, _P, _P, _P, c_int, ctypes.c_uint32, c_int, c_int,
+                                        c_int, c_int, c_int, c_int, _P, _P, _P]),
     "dsic_tile_gather_u8": (c_int, [_P, _P, c_int, c_int, c_int, c_int, c_int, c_int, c_int, _P]),
     "dsic_tile_gather_f32": (c_int, [_P, _P, c_int, c_int, c_int, c_int, c_int, c_int, c_int, _P]),
     "dsic_tile_stitch_f32": (c_int, [_P, _P, c_int, c_int, c_int, c_int, c_int, c_int, c_int, _P]),

@@ -379,6 +379,20 @@ int dsic_range_encode_ws(const float* y_nchw, const float* z_nchw, const int* me
                          int64_t cap_y, int64_t cap_z, int* lengths, int* err,
                          int per_element_y, void* workspace, int64_t workspace_bytes, void* stream);
 
+/* Segmented y strings: the y string of an image is coded as segs (1, 2, 4, 8 or 16, dividing M) independent
+ * range-coder strings, segment k = channels [k*M/segs, (k+1)*M/segs) (a contiguous symbol range and a contiguous
+ * block of table rows), all with the image's one support.  Arguments as dsic_range_encode_ws, with cap_seg (a multiple
+ * of 4, >= 8) the capacity of one segment: out [B][cap_z + segs*cap_seg] zero-initialised, the z string at 0,
+ * segment k at cap_z + k*cap_seg; lengths [B][1 + segs] = {len_z, len_y0 .. len_y(segs-1)}.  segs = 1 is
+ * dsic_range_encode_ws.  The z string is never segmented. */
+int64_t dsic_range_encode_seg_workspace_size(int B, int M, int HWy, int N, int HWz, int segs);
+int dsic_range_encode_seg_ws(const float* y_nchw, const float* z_nchw, const int* meta,
+                             const uint16_t* tab_y, const uint16_t* tab_z, int Lmax,
+                             int B, int M, int HWy, int N, int HWz, uint8_t* out,
+                             int64_t cap_seg, int64_t cap_z, int* lengths, int* err,
+                             int per_element_y, int segs, void* workspace, int64_t workspace_bytes,
+                             void* stream);
+
 /* torchac.decode_float_cdf call sites :96,116: string b starts at
  * in + b*stride and has lengths[b*lstride + loff] bytes; meta_off 0 = y, 2 = z.
  * out: NCHW float latents [B][C][HW] (symbol + min). */
@@ -386,6 +400,16 @@ int dsic_range_decode(const uint8_t* in, int64_t stride, const int* lengths,
                       int lstride, int loff, const int* meta, int meta_off,
                       const uint16_t* tables, int Lmax, int B, int C, int HW,
                       int per_element, float* out_nchw, int* err, void* stream);
+
+/* dsic_range_decode of segmented strings, one wave per (string, segment): the segs segments of string b lie back
+ * to back from in + b*stride (4-byte aligned), segment k at byte sum_{j<k} seg_lengths[b*segs + j] with
+ * seg_lengths[b*segs + k] bytes, at any alignment.  Starts and lengths are cut to what is left of
+ * lengths[b*lstride + loff]: a forged length reads zeros, never past the string.  Segment k decodes channels
+ * [k*C/segs, (k+1)*C/segs) with the rows of `tables` that belong to them. */
+int dsic_range_decode_seg(const uint8_t* in, int64_t stride, const int* lengths, int lstride,
+                          int loff, const int* seg_lengths, int segs, const int* meta,
+                          int meta_off, const uint16_t* tables, int Lmax, int B, int C, int HW,
+                          int per_element, float* out_nchw, int* err, void* stream);
 
 /* ---- whole-image codec (codec.py; no reference counterpart: its driver codes one
  * image of sizes that are multiples of 16 in one pass, eval_selfcontained_entropy.py:126-159) --
@@ -419,6 +443,15 @@ int dsic_container_pack(const uint8_t* bytes, int64_t cap_z, int64_t cap_y, cons
                         const int* meta, const int* err, int B, uint32_t tag, int My, int Hy,
                         int Wy, int Nz, int Hz, int Wz, int64_t* workspace, uint8_t* out,
                         void* stream);
+/* The DSIC3 container of segmented y strings, from the outputs of dsic_range_encode_seg_ws (bytes
+ * [B][cap_z + segs*cap_seg], lengths [B][1 + segs]; segs 2, 4, 8 or 16): magic "DSIC3\0" | the DSIC2 fields |
+ * segs u32 | B x the DSIC2 record (len_y = the sum of its segments) | B x segs u32 segment lengths |
+ * B x (z string, segment 0 .. segs-1).  out holds at least 42 + (24 + 4*segs)*B + B*(cap_z + segs*cap_seg)
+ * bytes; workspace: B*(1+segs)+3 int64, [0] and [1] as dsic_container_pack. */
+int dsic_container_pack_seg(const uint8_t* bytes, int64_t cap_z, int64_t cap_seg, int segs,
+                            const int* lengths, const int* meta, const int* err, int B,
+                            uint32_t tag, int My, int Hy, int Wy, int Nz, int Hz, int Wz,
+                            int64_t* workspace, uint8_t* out, void* stream);
 /* Inverse for the decoder: a DSIC2 container of B images (blob_bytes bytes on the device) ->
  * z strings at zbuf + b*zstride, y strings at ybuf + b*ystride, lengths [B][2] (z, y) and
  * meta [B][4] (ymin, Ly, zmin, Lz) as dsic_range_decode takes them (lstride 2).  The caller has

@@ -9,6 +9,10 @@ Every figure is the best of --reps full passes over the scene after one warm-up 
 
     python tools/image_codec_bench.py --region [--json profiles/region_decode_bench.json]
 
+--segments K  (with or without --region) the same figures for streams whose y strings are whole (K = 1) and in K
+          segments, read alternately in one run, each the median of --reps readings; "segments" in the result holds
+          them per K beside the stream-size ratio.  The K = 1 stream's figures stay where they were.
+
 --region  decompress_region of the same stream for an aligned one-tile window, an unaligned 2 x 2-tile-sized window
           (9 tiles), an unaligned half-scene window and the whole image, beside decompress_image before and after
           them in the same run (the two readings show the run-to-run spread).  Records, not bars.
@@ -79,6 +83,47 @@ def region_records(model, stream, a):
             "unaligned_2x2_over_decompress_image": round(recs["unaligned_2x2"]["ms"] / (1e3 * best_full), 4)}
 
 
+def segment_records(model, img, a, n):
+    """K = 1 and K = a.segments alternately: compress_image / decompress_image tiles per second and, with --region,
+    the one-tile and nine-tile windows; medians of a.reps readings."""
+    import statistics
+    import torch
+    from dsic_amd import codec
+    t = a.tile
+    off = 4 * t - 24
+    Ks = [1, a.segments]
+    streams = {K: codec.compress_image(model, img, tile=t, batch=a.batch, segments=K) for K in Ks}
+    full = codec.decompress_image(model, streams[1])
+    assert torch.equal(codec.decompress_image(model, streams[a.segments]), full), "segments decode to another image"
+    jobs = {"compress_image": lambda K: codec.compress_image(model, img, tile=t, batch=a.batch, segments=K),
+            "decompress_image": lambda K: codec.decompress_image(model, streams[K])}
+    if a.region:
+        jobs["region_one_tile"] = lambda K: codec.decompress_region(model, streams[K], 4 * t, 4 * t, t, t, batch=a.batch)
+        jobs["region_nine_tiles"] = lambda K: codec.decompress_region(model, streams[K], off, off, 2 * t, 2 * t,
+                                                                      batch=a.batch)
+    reads = {name: {K: [] for K in Ks} for name in jobs}
+    for name, job in jobs.items():
+        for K in Ks:
+            job(K)                                                     # warm-up
+        torch.cuda.synchronize()
+        for _ in range(a.reps):
+            for K in Ks:
+                t0 = time.perf_counter()
+                job(K)
+                torch.cuda.synchronize()
+                reads[name][K].append(1e3 * (time.perf_counter() - t0))
+    res = {"K": a.segments, "reps": a.reps, "stream_bytes": {str(K): len(streams[K]) for K in Ks},
+           "stream_size_ratio": round(len(streams[a.segments]) / len(streams[1]), 6)}
+    for name in jobs:
+        res[name] = {}
+        for K in Ks:
+            med = statistics.median(reads[name][K])
+            res[name][str(K)] = {"ms_median": round(med, 3), "ms_all": [round(v, 3) for v in reads[name][K]]}
+            if name in ("compress_image", "decompress_image"):
+                res[name][str(K)]["tiles_per_s"] = round(n / med * 1e3, 1)
+    return res
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--size", type=int, default=4096)
@@ -87,6 +132,7 @@ def main():
     ap.add_argument("--reps", type=int, default=3)
     ap.add_argument("--json", default=None)
     ap.add_argument("--region", action="store_true", help="measure decompress_region windows instead")
+    ap.add_argument("--segments", type=int, default=1, help="also measure streams of K y segments, alternately")
     a = ap.parse_args()
 
     import numpy as np
@@ -108,8 +154,11 @@ def main():
     n = g["n"]
 
     stream = codec.compress_image(model, img, tile=a.tile, batch=a.batch)
+    seg = segment_records(model, img, a, n) if a.segments > 1 else None
     if a.region:
         res = region_records(model, stream, a)
+        if seg:
+            res["segments"] = seg
         print(json.dumps(res))
         with open(a.json or os.path.join(ROOT, "profiles", "region_decode_bench.json"), "w") as f:
             json.dump(res, f, indent=1)
@@ -137,6 +186,8 @@ def main():
            "host_compress_tiles_per_s": round(n / t_henc, 1), "host_decompress_tiles_per_s": round(n / t_hdec, 1),
            "ms": {"compress_image": round(1e3 * t_enc, 2), "decompress_image": round(1e3 * t_dec, 2),
                   "host_compress": round(1e3 * t_henc, 2), "host_decompress": round(1e3 * t_hdec, 2)}}
+    if seg:
+        res["segments"] = seg
     print(json.dumps(res))
     if a.json:
         with open(a.json, "w") as f:
