@@ -7,13 +7,22 @@
 // resolution).  Interpretation choices are frozen in DESIGN.md "Entropy path".
 //
 // Parallel structure: tables are embarrassingly parallel (one wave per
-// (image, channel) table: 64 lanes evaluate the boundary CDFs, lane 0 does the
-// short sequential normalise/cumsum/quantise in the reference's float32 order).  The coder's interval
-// update is a serial dependency chain per stream, so there is one workgroup
-// (one wave) per (image, stream): all 64 lanes translate a chunk of symbols to
-// (c_low, c_high) pairs in LDS, then lane 0 walks the chunk.  Matching leading
-// bits and pending (E3) runs are shifted out in bulk with clz instead of bit
-// by bit; the emitted bytes are identical to the bit-serial reference loop.
+// (image, channel) table: the 64 lanes evaluate the boundary CDFs and finish the
+// table an entry each; its two order-sensitive sums keep the reference's serial
+// order, finish_table_wave).  The coder's interval
+// update is a serial dependency chain per string, so one wave per string runs it
+// on wave-uniform values (the scalar unit): the 64 lanes translate 64 symbols to
+// packed (c_low, c_high - 1) pairs in parallel, the chain reads them lane by lane
+// (v_readlane) and records per symbol only the interval before renormalisation.
+// Which bits a symbol emits, what is owed in front of them and where they go are
+// prefix sums over those records, 64 lanes at a time, ORed into the zero-filled
+// output.  Matching leading bits and pending (E3) runs are shifted out in bulk
+// with clz instead of bit by bit; the emitted bytes are identical to the
+// bit-serial reference loop.  The interval step (IntervalStep), the bit
+// bookkeeping (place_group), the bit placement (put_group, put_flush) and the
+// symbol lookup (pair_of) are each stated once: the split encoder runs them in
+// separate launches, the single kernel in one wave, the decoder's fast path
+// shares the interval step.
 // Integer work only after the tables: results are bit-exact by construction.
 #include "common.h"
 #include "dsic_math.h"
@@ -217,93 +226,54 @@ __global__ __launch_bounds__(256) void gauss_tables_kernel(const float* __restri
   }
 }
 
-// Range encoder, one wave per (image, stream): stream ids 0..B-1 = y strings, B..2B-1 = z strings (which 0: z string,
-// 1: y string); several streams (one per SIMD) share a workgroup.
+// ---- range encoder ----------------------------------------------------------------------------------------------
+// The coder is split along its only true dependency.  (1) The interval recurrence is a serial chain per string: it
+// runs branch-free on wave-uniform values (scalar unit), reading the (c_low, c_high - 1) pair of symbol j with
+// v_readlane from a register the 64 lanes filled in parallel, and records per symbol only (low1, high1), the interval
+// BEFORE renormalisation (v_writelane).  (2) WHAT a symbol emits - the leading bits of low1 that became final (E1/E2)
+// and the inverse bits owed from the E3 runs since the last such symbol - is recomputed from the records by the 64
+// lanes in parallel (place_group), and WHERE those bits go is a prefix sum of their counts (put_group).  Bytes are
+// identical to the bit-serial reference loop (torchac): E1/E2 shifts = clz(low ^ high) at once, E3 run = leading
+// ones of (low << 1) & ~(high << 1).
 //
-// The coder is split along its only true dependency.  (1) The interval recurrence
-// (low, high, pending) is a serial chain per stream: it runs branch-free on wave-uniform
-// values (scalar unit), reading the (c_low, c_high-1) pair of symbol j with v_readlane from a
-// register the 64 lanes filled in parallel (table gather, pipelined two groups ahead), and
-// records per symbol only WHAT is emitted: the nb leading bits of low that became final and
-// the pending count flushed behind the first of them (v_writelane).  (2) WHERE those bits go
-// is a prefix sum: every 64 symbols the lanes scan their bit counts and OR their pieces into
-// the zero-initialised output with atomics, in parallel.  Bytes are identical to the
-// bit-serial reference loop (torchac): E1/E2 shifts = clz(low^high) at once, E3 run = leading
-// ones of (low<<1)&~(high<<1).
-__device__ __forceinline__ void put_bits(uint32_t* out32, int64_t cap_bits, int64_t off, uint32_t v,
-                                         int len, int* overflow) {
-  // append the low `len` (1..32) bits of v at bit offset `off`, MSB first
-  if (off + len > cap_bits) {
-    *overflow = 1;
-    return;
+// Interval state (low, span, lowm1): span = high - low + 1 kept mod 2^32 (0 means 2^32), lowm1 = low - 1.  Bounds
+// (cl, ch) = (c_low << 16, c_high << 16), so floor(span c / 2^16) is ONE mul_hi; ch = 0 means c_high = 65536, whose
+// product is span itself, and span = 0 selects (2^32 c) >> 16 = c << 16 (a select: 4 % faster than a branch per
+// symbol).
+struct IntervalStep {
+  uint32_t low1, high1, span1;   // the symbol's interval before renormalisation; span1 >= 2^14 - 1
+  // nb: leading bits now final (E1/E2); m: (1, 0) bit pairs below the split bit (E3)
+  __device__ __forceinline__ void shifts(int& nb, int& m) const {
+    nb = __builtin_clz(low1 ^ high1);
+    const uint32_t q2 = (high1 | ~low1) << 1;   // 0 where (low, high) = (1, 0)
+    m = __builtin_clz(q2 << nb);                // != 0: an all-E3 tail would need span1 == 2
   }
-  const int64_t w = off >> 5;
-  const int s = (int)(off & 31), space = 32 - s;
-  if (len <= space) {
-    atomicOr(out32 + w, __builtin_bswap32(v << (space - len)));
-  } else {
-    const int rest = len - space;
-    atomicOr(out32 + w, __builtin_bswap32(v >> rest));
-    atomicOr(out32 + w + 1, __builtin_bswap32(v << (32 - rest)));
-  }
+  // after both renormalisation shifts at once (sh = nb + m <= 18, as span1 << sh <= 2^32)
+  __device__ __forceinline__ uint32_t low(int sh) const { return (low1 << sh) & 0x7FFFFFFFu; }
+  __device__ __forceinline__ uint32_t span(int sh) const { return span1 << sh; }   // exactly 2^32 -> 0
+};
+
+// One symbol in two halves, so that an encoder records (low1, high1) between them.  The chain span -> span of the next
+// symbol is ~9 dependent scalar operations (mul_hi, select, sub/add, xor | orn2, flbit | shift, shift, flbit, add,
+// shift); low - 1 and the record sit beside it.  TOP: ch = 0 (c_high = 65536) may occur.
+template <bool TOP>
+__device__ __forceinline__ IntervalStep interval_narrow(uint32_t low, uint32_t lowm1, uint32_t span, uint32_t cl,
+                                                        uint32_t ch) {
+  const uint32_t ml = __umulhi(span, cl), mh = __umulhi(span, ch);
+  const uint32_t lo_add = span ? ml : cl;
+  const uint32_t hi_add = TOP && !ch ? span : (span ? mh : ch);
+  return IntervalStep{low + lo_add, lowm1 + hi_add, hi_add - lo_add};   // low - 1 + floor(span c_high / 2^16)
 }
 
-__device__ __forceinline__ void put_ones(uint32_t* out32, int64_t cap_bits, int64_t off, uint32_t count,
-                                         int* overflow) {
-  while (count > 0) {
-    const int len = count > 32 ? 32 : (int)count;
-    put_bits(out32, cap_bits, off, len == 32 ? 0xFFFFFFFFu : ((1u << len) - 1u), len, overflow);
-    off += len;
-    count -= len;
-  }
+__device__ __forceinline__ void interval_renorm(const IntervalStep& s, uint32_t& low, uint32_t& lowm1,
+                                                uint32_t& span) {
+  int nb, m;
+  s.shifts(nb, m);
+  span = s.span(nb + m);
+  low = s.low(nb + m);
+  lowm1 = low - 1u;
 }
 
-// put_bits / put_ones through a window of LDS words: words wbase .. wbase + PLACE_WIN - 1 of the output are ORed in
-// LDS (flushed with one global atomic per word by place_flush), the rest straight into the output.
-constexpr int PLACE_WIN = 512;
-__device__ __forceinline__ void or_word(uint32_t* out32, uint32_t* win, int64_t wbase, int64_t w, uint32_t v) {
-  const int64_t i = w - wbase;
-  if (i >= 0 && i < PLACE_WIN) atomicOr(win + i, v);
-  else atomicOr(out32 + w, v);
-}
-
-__device__ __forceinline__ void put_bits_w(uint32_t* out32, uint32_t* win, int64_t wbase, int64_t cap_bits,
-                                           int64_t off, uint32_t v, int len, int* overflow) {
-  if (off + len > cap_bits) {
-    *overflow = 1;
-    return;
-  }
-  const int64_t w = off >> 5;
-  const int s = (int)(off & 31), space = 32 - s;
-  if (len <= space) {
-    or_word(out32, win, wbase, w, __builtin_bswap32(v << (space - len)));
-  } else {
-    const int rest = len - space;
-    or_word(out32, win, wbase, w, __builtin_bswap32(v >> rest));
-    or_word(out32, win, wbase, w + 1, __builtin_bswap32(v << (32 - rest)));
-  }
-}
-
-__device__ __forceinline__ void put_ones_w(uint32_t* out32, uint32_t* win, int64_t wbase, int64_t cap_bits,
-                                           int64_t off, uint32_t count, int* overflow) {
-  while (count > 0) {
-    const int len = count > 32 ? 32 : (int)count;
-    put_bits_w(out32, win, wbase, cap_bits, off, len == 32 ? 0xFFFFFFFFu : ((1u << len) - 1u), len, overflow);
-    off += len;
-    count -= len;
-  }
-}
-
-// ---- fast serial step (full groups of 64 symbols whose c_high < 65536) ------------------------
-// State (low, span) with span = high - low + 1 kept mod 2^32 (0 means 2^32).  The lanes hold
-// c << 16, so floor(span * c / 2^16) is ONE s_mul_hi_u32; the step is unrolled with immediate
-// lane selects (no M0 / wait-state padding), and only (low1, high1) — the interval BEFORE
-// renormalisation — are recorded: which bits became final (E1/E2), how long the E3 run is and
-// what is owed from earlier symbols is recomputed from them by the 64 lanes in parallel.
-// ~22 scalar instructions per symbol instead of ~55.
-#ifndef ENC_SELECT
-#define ENC_SELECT 1   // 1: s_cselect for the span = 2^32 case (4 % faster than a branch per symbol)
-#endif
 template <int J>
 __device__ __forceinline__ void wlane(uint32_t& rec, uint32_t v) {
   asm volatile("v_writelane_b32 %0, %1, %2" : "+v"(rec) : "s"(v), "n"(J));
@@ -316,255 +286,220 @@ __device__ __forceinline__ uint32_t rlane(uint32_t v) {
   return r;
 }
 
-// (cl, ch): the bounds of symbol J, read one step earlier; the step first reads those of symbol J+1,
-// so the VALU -> SGPR latency of v_readlane never sits on the serial chain.
-template <int J>
-__device__ __forceinline__ void enc_step(uint32_t& low, uint32_t& lowm1, uint32_t& span, uint32_t& cl,
-                                         uint32_t& ch, uint32_t clo16, uint32_t chi16, uint32_t& rec_low,
-                                         uint32_t& rec_high) {
-  // The chain span -> span of the next symbol is ~9 dependent scalar operations (mul_hi, select,
-  // sub/add, xor | orn2, flbit | shift, shift, flbit, add, shift); low - 1 and the record stores sit
-  // beside it.
-  const uint32_t cl_next = J < 63 ? rlane<(J < 63 ? J + 1 : 63)>(clo16) : 0u;
-  const uint32_t ch_next = J < 63 ? rlane<(J < 63 ? J + 1 : 63)>(chi16) : 0u;
-  uint32_t lo_add, hi_add;
-#if ENC_SELECT
-  {  // branch-free: span = 2^32 (kept as 0) selects (2^32 c) >> 16 = c << 16
-    const uint32_t ml = __umulhi(span, cl), mh = __umulhi(span, ch);
-    lo_add = span ? ml : cl;
-    hi_add = span ? mh : ch;
+// Where the steps of a full group of 64 take their bounds from: the only thing in which the two encoders' 64-step
+// blocks differ.
+//  PackedPairs: one register of packed pairs, unpacked by scalar operations; c_high = 65536 allowed.  One v_readlane
+//               per symbol and a register less: the chain kernel (8 VGPRs).
+//  LaneBounds:  (c_low << 16, c_high << 16) in two registers, every c_high < 65536.  Two v_readlane per symbol, no
+//               unpacking and no select on ch: 3 % faster where registers are free (the single kernel).
+struct PackedPairs {
+  static constexpr bool TOP = true;
+  template <int J>
+  static __device__ __forceinline__ void fetch(uint32_t pv, uint32_t, uint32_t& p, uint32_t&) { p = rlane<J>(pv); }
+  static __device__ __forceinline__ void bounds(uint32_t p, uint32_t, uint32_t& cl, uint32_t& ch) {
+    cl = p << 16;
+    ch = (p & 0xFFFF0000u) + 0x10000u;
   }
-#else
-  if (__builtin_expect(span == 0u, 0)) {  // span = 2^32: (2^32 c) >> 16
-    lo_add = cl;
-    hi_add = ch;
-  } else {
-    lo_add = __umulhi(span, cl);
-    hi_add = __umulhi(span, ch);
+};
+struct LaneBounds {
+  static constexpr bool TOP = false;
+  template <int J>
+  static __device__ __forceinline__ void fetch(uint32_t clo16, uint32_t chi16, uint32_t& l, uint32_t& h) {
+    l = rlane<J>(clo16);
+    h = rlane<J>(chi16);
   }
-#endif
-  const uint32_t low1 = low + lo_add;
-  const uint32_t high1 = lowm1 + hi_add;         // low - 1 + floor(span c_high / 2^16)
-  const uint32_t span1 = hi_add - lo_add;        // >= 2^14 - 1
-  wlane<J>(rec_low, low1);
-  wlane<J>(rec_high, high1);
-  const int nb = __builtin_clz(low1 ^ high1);    // E1/E2
-  const uint32_t q2 = (high1 | ~low1) << 1;      // 0 where (low, high) = (1, 0): E3 pairs below the split bit
-  const int m = __builtin_clz(q2 << nb);         // != 0: an all-E3 tail would need span1 == 2
-  const int sh = nb + m;
-  span = span1 << sh;                            // exactly 2^32 -> 0
-  low = (low1 << sh) & 0x7FFFFFFFu;
-  lowm1 = low - 1u;
-  cl = cl_next;
-  ch = ch_next;
+  static __device__ __forceinline__ void bounds(uint32_t l, uint32_t h, uint32_t& cl, uint32_t& ch) {
+    cl = l;
+    ch = h;
+  }
+};
+
+// Symbol J of a full group, unrolled with immediate lane selects (no M0 / wait-state padding).  (cl, ch): the bounds
+// of symbol J, fetched one step earlier; the step first reads those of symbol J + 1, so the VALU -> SGPR latency of
+// v_readlane never sits on the serial chain.  ~22 scalar instructions per symbol.
+template <class Src, int J>
+__device__ __forceinline__ void chain_step(uint32_t& low, uint32_t& lowm1, uint32_t& span, uint32_t& cl, uint32_t& ch,
+                                           uint32_t v0, uint32_t v1, uint32_t& rec_low, uint32_t& rec_high) {
+  uint32_t n0 = 0u, n1 = 0u;
+  if (J < 63) Src::template fetch<(J < 63 ? J + 1 : 63)>(v0, v1, n0, n1);
+  const IntervalStep s = interval_narrow<Src::TOP>(low, lowm1, span, cl, ch);
+  wlane<J>(rec_low, s.low1);
+  wlane<J>(rec_high, s.high1);
+  interval_renorm(s, low, lowm1, span);
+  Src::bounds(n0, n1, cl, ch);
 }
 
-template <int J0>
-__device__ __forceinline__ void enc_steps8(uint32_t& low, uint32_t& lowm1, uint32_t& span, uint32_t& cl,
-                                           uint32_t& ch, uint32_t clo16, uint32_t chi16, uint32_t& rec_low,
-                                           uint32_t& rec_high) {
-  enc_step<J0 + 0>(low, lowm1, span, cl, ch, clo16, chi16, rec_low, rec_high);
-  enc_step<J0 + 1>(low, lowm1, span, cl, ch, clo16, chi16, rec_low, rec_high);
-  enc_step<J0 + 2>(low, lowm1, span, cl, ch, clo16, chi16, rec_low, rec_high);
-  enc_step<J0 + 3>(low, lowm1, span, cl, ch, clo16, chi16, rec_low, rec_high);
-  enc_step<J0 + 4>(low, lowm1, span, cl, ch, clo16, chi16, rec_low, rec_high);
-  enc_step<J0 + 5>(low, lowm1, span, cl, ch, clo16, chi16, rec_low, rec_high);
-  enc_step<J0 + 6>(low, lowm1, span, cl, ch, clo16, chi16, rec_low, rec_high);
-  enc_step<J0 + 7>(low, lowm1, span, cl, ch, clo16, chi16, rec_low, rec_high);
+template <class Src, int J0>
+__device__ __forceinline__ void chain_steps8(uint32_t& low, uint32_t& lowm1, uint32_t& span, uint32_t& cl,
+                                             uint32_t& ch, uint32_t v0, uint32_t v1, uint32_t& rl, uint32_t& rh) {
+  chain_step<Src, J0 + 0>(low, lowm1, span, cl, ch, v0, v1, rl, rh);
+  chain_step<Src, J0 + 1>(low, lowm1, span, cl, ch, v0, v1, rl, rh);
+  chain_step<Src, J0 + 2>(low, lowm1, span, cl, ch, v0, v1, rl, rh);
+  chain_step<Src, J0 + 3>(low, lowm1, span, cl, ch, v0, v1, rl, rh);
+  chain_step<Src, J0 + 4>(low, lowm1, span, cl, ch, v0, v1, rl, rh);
+  chain_step<Src, J0 + 5>(low, lowm1, span, cl, ch, v0, v1, rl, rh);
+  chain_step<Src, J0 + 6>(low, lowm1, span, cl, ch, v0, v1, rl, rh);
+  chain_step<Src, J0 + 7>(low, lowm1, span, cl, ch, v0, v1, rl, rh);
 }
 
-__global__ __launch_bounds__(1024) void range_encode_kernel(
-    const float* __restrict__ y, const float* __restrict__ z, const int* __restrict__ meta,
-    const uint16_t* __restrict__ tab_y, const uint16_t* __restrict__ tab_z, int Lmax, int M, int HWy,
-    int N, int HWz, uint8_t* __restrict__ out, int64_t cap_y, int64_t cap_z,
-    int* __restrict__ lengths, int* __restrict__ err, int nstreams, int per_element_y) {
-  const int lane = threadIdx.x & 63;
-  const int sid = __builtin_amdgcn_readfirstlane(blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6));
-  if (sid >= nstreams) return;
-  // streams 0..B-1 are the long y strings, B..2B-1 the short z strings: the y waves share as few
-  // workgroups (= CUs, which a persistent conv workgroup cannot use meanwhile) as possible
-  const int nimg = nstreams >> 1;
-  const int which = sid < nimg ? 1 : 0, b = which ? sid : sid - nimg;
-  const int C = which ? M : N, HW = which ? HWy : HWz;
-  const int64_t n = (int64_t)C * HW;
-  const float* sym = which ? y + (size_t)b * n : z + (size_t)b * n;
-  const bool per_element = which && per_element_y;  // spatial_params: one table row per y symbol
-  const uint16_t* tab = (which ? tab_y + (size_t)b * (per_element ? (size_t)M * HWy : (size_t)M) * Lmax
-                               : tab_z + (size_t)b * N * Lmax);
-  const int smin = meta[4 * b + (which ? 0 : 2)], L = meta[4 * b + (which ? 1 : 3)];
-  const int64_t stride = cap_z + cap_y;  // per image: [z bytes | y bytes], zero-initialised by the caller
-  uint32_t* dst32 = (uint32_t*)(out + (size_t)b * stride + (which ? cap_z : 0));
-  const int64_t cap_bits = (which ? cap_y : cap_z) * 8;
-  if (L > Lmax || L < 1) {
-    if (lane == 0) {
-      atomicOr(err, 1);
-      lengths[2 * b + which] = 0;
-    }
+// a full group: the records of its 64 symbols in (rl, rh)
+template <class Src>
+__device__ __forceinline__ void chain_group(uint32_t v0, uint32_t v1, uint32_t& low, uint32_t& lowm1, uint32_t& span,
+                                            uint32_t& rl, uint32_t& rh) {
+  uint32_t n0 = 0u, n1 = 0u, cl, ch;
+  Src::template fetch<0>(v0, v1, n0, n1);
+  Src::bounds(n0, n1, cl, ch);
+  chain_steps8<Src, 0>(low, lowm1, span, cl, ch, v0, v1, rl, rh);
+  chain_steps8<Src, 8>(low, lowm1, span, cl, ch, v0, v1, rl, rh);
+  chain_steps8<Src, 16>(low, lowm1, span, cl, ch, v0, v1, rl, rh);
+  chain_steps8<Src, 24>(low, lowm1, span, cl, ch, v0, v1, rl, rh);
+  chain_steps8<Src, 32>(low, lowm1, span, cl, ch, v0, v1, rl, rh);
+  chain_steps8<Src, 40>(low, lowm1, span, cl, ch, v0, v1, rl, rh);
+  chain_steps8<Src, 48>(low, lowm1, span, cl, ch, v0, v1, rl, rh);
+  chain_steps8<Src, 56>(low, lowm1, span, cl, ch, v0, v1, rl, rh);
+}
+
+// cnt (1..64) symbols of a group of packed pairs, any c_high: the same step in a loop; lanes cnt.. of (rl, rh) are left as they were.
+// v_writelane has no clang builtin on this toolchain.  The lane select goes through M0 (an SGPR value plus an SGPR
+// lane select would exceed the constant-bus limit); s_nop 3: an SALU result needs 4 wait states before it is used as
+// a lane select, and hipcc pads nothing inside asm.  The encoders use no GWS or movrel, so M0 is otherwise unused.
+__device__ __forceinline__ void chain_tail(uint32_t pv, int cnt, uint32_t& low, uint32_t& lowm1, uint32_t& span,
+                                           uint32_t& rl, uint32_t& rh) {
+  for (int j = 0; j < cnt; ++j) {
+    const uint32_t pr = __builtin_amdgcn_readlane(pv, j);
+    const IntervalStep s = interval_narrow<true>(low, lowm1, span, pr << 16, (pr & 0xFFFF0000u) + 0x10000u);
+    asm volatile("s_mov_b32 m0, %4\n\ts_nop 3\n\tv_writelane_b32 %0, %2, m0\n\tv_writelane_b32 %1, %3, m0"
+                 : "+v"(rl), "+v"(rh)
+                 : "s"(s.low1), "s"(s.high1), "s"(j));
+    interval_renorm(s, low, lowm1, span);
+  }
+}
+
+// One group of 64 records; lane j: symbol j of the group, lanes past the end hold (0, ~0): no bit, no E3 run.
+// Per lane the number of final bits of the symbol (nbv, the top bits of lo) and the inverse bits owed behind the first
+// of them (pendv, 0 unless nbv > 0); `pending` (wave-uniform) goes from the count owed in front of the group to the
+// count owed behind it.
+__device__ __forceinline__ void place_group(uint32_t lo, uint32_t hi, int lane, uint32_t& pending, uint32_t& nbv,
+                                            uint32_t& pendv) {
+  nbv = (uint32_t)__builtin_clz(lo ^ hi);
+  const uint32_t mv = (uint32_t)__builtin_clz((((hi | ~lo) << nbv) << 1) | 1u);
+  // pending count in front of symbol j = sum of the E3 runs since the last symbol that emitted bits (its own run
+  // included), or since the carry-in: a segmented prefix sum
+  uint32_t T = mv;
+#pragma unroll
+  for (int o = 1; o < 64; o <<= 1) {
+    const uint32_t up = __shfl_up(T, o, 64);
+    if (lane >= o) T += up;
+  }
+  const uint32_t Tex = T - mv;
+  const uint64_t heads = __ballot(nbv > 0);
+  const uint64_t before = heads & ((1ull << lane) - 1ull);
+  const int hb = 63 - __builtin_clzll(before | 1ull);
+  const uint32_t Tex_h = __shfl(Tex, hb, 64);
+  const uint32_t pend_in = before ? Tex - Tex_h : pending + Tex;
+  pendv = nbv ? pend_in : 0u;
+  const int hl = 63 - __builtin_clzll(heads | 1ull);
+  const uint32_t T63 = __builtin_amdgcn_readlane(T, 63);
+  const uint32_t Tex_hl = __builtin_amdgcn_readlane(Tex, hl);
+  pending = heads ? T63 - Tex_hl : pending + T63;
+}
+
+// ---- bit placement ----------------------------------------------------------------------------------------------
+// A string's bits are ORed into its zero-initialised capacity as big-endian 32-bit words, in pieces of at most 32
+// bits at any bit offset, by any lane in any order.  WIN: the words wbase .. wbase + PLACE_WIN - 1 are ORed in an LDS
+// window (which its owner adds to the output later, one global atomic per word instead of one per piece), the rest
+// straight into the output; !WIN: every word goes straight to the output.  A piece that would end behind the capacity
+// is dropped whole and *overflow set (error bit 4).
+constexpr int PLACE_WIN = 512;
+struct BitSink {
+  uint32_t* out32;    // the string's capacity
+  int64_t cap_bits;
+  uint32_t* win;      // WIN only
+  int64_t wbase;
+};
+
+template <bool WIN>
+__device__ __forceinline__ void or_word(const BitSink& S, int64_t w, uint32_t v) {
+  const int64_t i = w - S.wbase;
+  if (WIN && i >= 0 && i < PLACE_WIN) atomicOr(S.win + i, v);
+  else atomicOr(S.out32 + w, v);
+}
+
+// append the low `len` (1..32) bits of v at bit offset `off`, MSB first
+template <bool WIN>
+__device__ __forceinline__ void put_bits(const BitSink& S, int64_t off, uint32_t v, int len, int* overflow) {
+  if (off + len > S.cap_bits) {
+    *overflow = 1;
     return;
   }
-
-  // Two-deep software pipeline for the operand gather: symbols are loaded two groups ahead,
-  // their table entries one group ahead, so neither dependent load round sits on the serial
-  // chain even when L2 latency is several microseconds under a co-running conv kernel.
-  auto sym_of = [&](int64_t g) -> float { return g < n ? sym[g] : 0.f; };
-  auto pair_of = [&](float v, int64_t g) -> uint32_t {
-    if (g >= n) return 0u;
-    const int c = (int)(g / HW);
-    int sc = (int)v - smin;
-    if (sc < 0 || sc >= L) {  // cannot happen when meta came from dsic_latent_support on the same latents
-      atomicOr(err, 2);
-      sc = 0;
-    }
-    const uint16_t* t = tab + (size_t)(per_element ? g : (int64_t)c) * Lmax;
-    const uint32_t c_low = t[sc];
-    const uint32_t c_high = (sc == L - 1) ? 0x10000u : (uint32_t)t[sc + 1];
-    return c_low | ((c_high - 1u) << 16);
-  };
-
-  uint32_t low = 0, high = 0xFFFFFFFFu, pending = 0;
-  int64_t base_bits = 0;  // bits emitted so far (wave-uniform)
-  int overflow = 0;
-
-  uint32_t cur = pair_of(sym_of(lane), lane);
-  float sym1 = sym_of(64 + lane);
-  for (int64_t base = 0; base < n; base += 64) {
-    const float sym2 = sym_of(base + 128 + lane);
-    const uint32_t nxt = pair_of(sym1, base + 64 + lane);
-    const int cnt = (int)((n - base) < 64 ? (n - base) : 64);
-    uint32_t nbv, bitsv, pendv;   // lane j: final bits of symbol j, their count, inverse bits owed behind the first
-    const uint32_t c_lo_v = cur & 0xFFFFu, c_hi_v = (cur >> 16) + 1u;
-    if (cnt == 64 && !__any(c_hi_v == 0x10000u)) {
-      // ---- fast path ----
-      uint32_t rec_low = 0, rec_high = 0;
-      uint32_t span = high - low + 1u, lowm1 = low - 1u;
-      const uint32_t clo16 = c_lo_v << 16, chi16 = c_hi_v << 16;
-      uint32_t cl = rlane<0>(clo16), ch = rlane<0>(chi16);
-      enc_steps8<0>(low, lowm1, span, cl, ch, clo16, chi16, rec_low, rec_high);
-      enc_steps8<8>(low, lowm1, span, cl, ch, clo16, chi16, rec_low, rec_high);
-      enc_steps8<16>(low, lowm1, span, cl, ch, clo16, chi16, rec_low, rec_high);
-      enc_steps8<24>(low, lowm1, span, cl, ch, clo16, chi16, rec_low, rec_high);
-      enc_steps8<32>(low, lowm1, span, cl, ch, clo16, chi16, rec_low, rec_high);
-      enc_steps8<40>(low, lowm1, span, cl, ch, clo16, chi16, rec_low, rec_high);
-      enc_steps8<48>(low, lowm1, span, cl, ch, clo16, chi16, rec_low, rec_high);
-      enc_steps8<56>(low, lowm1, span, cl, ch, clo16, chi16, rec_low, rec_high);
-      high = low + span - 1u;
-      // lanes: what symbol j emitted
-      nbv = (uint32_t)__builtin_clz(rec_low ^ rec_high);
-      bitsv = nbv ? rec_low >> (32u - nbv) : 0u;
-      const uint32_t mv = (uint32_t)__builtin_clz((((rec_high | ~rec_low) << nbv) << 1) | 1u);
-      // pending count in front of symbol j = sum of the E3 runs since the last symbol that
-      // emitted bits (its own run included), or since the carry-in: a segmented prefix sum
-      uint32_t T = mv;
-#pragma unroll
-      for (int o = 1; o < 64; o <<= 1) {
-        const uint32_t up = __shfl_up(T, o, 64);
-        if (lane >= o) T += up;
-      }
-      const uint32_t Tex = T - mv;
-      const uint64_t heads = __ballot(nbv > 0);
-      const uint64_t before = heads & ((1ull << lane) - 1ull);
-      const int hb = 63 - __builtin_clzll(before | 1ull);
-      const uint32_t Tex_h = __shfl(Tex, hb, 64);
-      const uint32_t pend_in = before ? Tex - Tex_h : pending + Tex;
-      pendv = nbv ? pend_in : 0u;
-      const int hl = 63 - __builtin_clzll(heads | 1ull);
-      const uint32_t T63 = __builtin_amdgcn_readlane(T, 63);
-      const uint32_t Tex_hl = __builtin_amdgcn_readlane(Tex, hl);
-      pending = heads ? T63 - Tex_hl : pending + T63;
-    } else {
-      // ---- general path (last partial group, or a symbol whose c_high is 65536) ----
-      uint32_t rec0 = 0, rec1 = 0;  // lane j: (nb << 24 | bits) and the pending count flushed at symbol j
-      for (int j = 0; j < cnt; ++j) {
-        const uint32_t pr = __builtin_amdgcn_readlane(cur, j);
-        const uint32_t c_low = pr & 0xFFFFu, c_high = (pr >> 16) + 1u;
-        // span = high - low + 1 (up to 2^32): (span*c) >> 16 == (r*c + c) >> 16 with r = high - low
-        const uint32_t r = high - low;
-        const uint32_t hi_add = (uint32_t)(((uint64_t)r * c_high + c_high) >> 16);
-        const uint32_t lo_add = (uint32_t)(((uint64_t)r * c_low + c_low) >> 16);
-        high = (low - 1u) + hi_add;
-        low = low + lo_add;
-        // Between symbols high - low >= 2^30 (MSBs differ, no E3 pending) and every table interval
-        // is >= 1/65536, so the new interval is >= 2^14 - 2 wide: low != high, nb <= 18.
-        const int nb = __builtin_clz(low ^ high);             // E1/E2: leading bits now final
-        const uint32_t bits = (low >> 1) >> (31 - nb);        // those nb bits (0 when nb == 0)
-        const uint32_t flush = nb ? pending : 0u;             // inverse bits owed behind the first one
-        pending = nb ? 0u : pending;
-        // v_writelane has no clang builtin on this toolchain.  The lane select goes through M0
-        // (an SGPR value plus an SGPR lane select would exceed the constant-bus limit); s_nop 3:
-        // an SALU result needs 4 wait states before it is used as a lane select, and hipcc pads
-        // nothing inside asm.  The kernel uses no LDS, GWS or movrel, so M0 is otherwise unused.
-        const uint32_t w0 = bits | ((uint32_t)nb << 24);
-        asm volatile("s_mov_b32 m0, %4\n\ts_nop 3\n\tv_writelane_b32 %0, %2, m0\n\tv_writelane_b32 %1, %3, m0"
-                     : "+v"(rec0), "+v"(rec1)
-                     : "s"(w0), "s"(flush), "s"(j));
-        low <<= nb;
-        high = (high << nb) | ((1u << nb) - 1u);
-        // E3: low = 01.., high = 10..: m consecutive (1,0) bit pairs below the MSB
-        const uint32_t e3 = (low << 1) & ~(high << 1);        // bit 0 is 0, so ~e3 != 0
-        const int m = __builtin_clz(~e3);
-        pending += (uint32_t)m;
-        low = (low << m) & 0x7FFFFFFFu;                       // MSB(low) is 0 here, so m == 0 is a no-op
-        high = (high << m) | 0x80000000u | ((1u << m) - 1u);
-      }
-      nbv = rec0 >> 24;
-      bitsv = rec0 & 0xFFFFFFu;
-      pendv = rec1;
-    }
-    // parallel placement of this group's bits
-    {
-      const uint32_t len = nbv + pendv;
-      uint32_t incl = len;
-#pragma unroll
-      for (int o = 1; o < 64; o <<= 1) {
-        const uint32_t up = __shfl_up(incl, o, 64);
-        if (lane >= o) incl += up;
-      }
-      const int64_t off = base_bits + (int64_t)(incl - len);
-      if (nbv > 0) {
-        if (pendv == 0) {
-          put_bits(dst32, cap_bits, off, bitsv, (int)nbv, &overflow);
-        } else {
-          const uint32_t first = bitsv >> (nbv - 1);
-          put_bits(dst32, cap_bits, off, first, 1, &overflow);
-          if (!first) put_ones(dst32, cap_bits, off + 1, pendv, &overflow);   // inverse bits are 1s
-          else if (off + 1 + (int64_t)pendv > cap_bits) overflow = 1;
-          if (nbv > 1)
-            put_bits(dst32, cap_bits, off + 1 + pendv, bitsv & ((1u << (nbv - 1)) - 1u), (int)nbv - 1, &overflow);
-        }
-      }
-      base_bits += (int64_t)__builtin_amdgcn_readlane((int)incl, 63);
-    }
-    cur = nxt;
-    sym1 = sym2;
+  const int64_t w = off >> 5;
+  const int s = (int)(off & 31), space = 32 - s;
+  if (len <= space) {
+    or_word<WIN>(S, w, __builtin_bswap32(v << (space - len)));
+  } else {
+    const int rest = len - space;
+    or_word<WIN>(S, w, __builtin_bswap32(v >> rest));
+    or_word<WIN>(S, w + 1, __builtin_bswap32(v << (32 - rest)));
   }
-  // flush (torchac): one more pending bit, then the deciding bit and the pending run, zero padded
-  pending += 1;
-  const uint32_t bit = low < 0x40000000u ? 0u : 1u;
-  if (lane == 0) {
-    put_bits(dst32, cap_bits, base_bits, bit, 1, &overflow);
-    if (!bit) put_ones(dst32, cap_bits, base_bits + 1, pending, &overflow);
-    else if (base_bits + 1 + (int64_t)pending > cap_bits) overflow = 1;
-  }
-  const int64_t total_bits = base_bits + 1 + (int64_t)pending;
-  if (__any(overflow)) {
-    if (lane == 0) atomicOr(err, 4);
-  }
-  if (lane == 0) lengths[2 * b + which] = (int)((total_bits + 7) >> 3);
 }
 
-// ---- split encoder: pack -> chain -> place (dsic_range_encode_ws) -----------------------------------
-// The same coder in three launches on the coder's stream, so that the only long-running one is a wave small
-// enough to share a CU with a persistent conv workgroup (3 x 168 of a SIMD's 512 VGPRs leave 8).
-//  pack  (whole chip, short): every symbol's (c_low, c_high-1) pair, error bits 1 and 2.
-//  chain (one wave per string, <= 8 VGPRs, no LDS): enc_step on scalar registers, 64 pairs per global load
-//        (two groups ahead); per symbol the interval before renormalisation (low1, high1) leaves through two
-//        vector stores per 64 symbols; the final low per string.
-//  place (two whole-chip launches of short waves, one slice of a string each): per symbol the E1/E2 bits and the
-//        E3 run from (low1, high1); summarize writes each slice's carry map and bit count, emit composes the records
-//        in front of its slice and makes the same put_bits calls, flush, lengths and error bit 4 as
-//        range_encode_kernel.
-// Workspace: pairs, rec_low, rec_high [B (M HWy + N HWz)] uint32, then final low [B (K + 1)], then (8-byte aligned)
-// the slice records [B (K ky + kz)] uint2.
+template <bool WIN>
+__device__ __forceinline__ void put_ones(const BitSink& S, int64_t off, uint32_t count, int* overflow) {
+  while (count > 0) {
+    const int len = count > 32 ? 32 : (int)count;
+    put_bits<WIN>(S, off, len == 32 ? 0xFFFFFFFFu : ((1u << len) - 1u), len, overflow);
+    off += len;
+    count -= len;
+  }
+}
+
+// a first bit and the `pend` inverse bits behind it: a run of ones after a 0; after a 1 the run is zeros, which are
+// there already but count against the capacity all the same
+template <bool WIN>
+__device__ __forceinline__ void put_resolved(const BitSink& S, int64_t off, uint32_t first, uint32_t pend,
+                                             int* overflow) {
+  put_bits<WIN>(S, off, first, 1, overflow);
+  if (!first) put_ones<WIN>(S, off + 1, pend, overflow);
+  else if (off + 1 + (int64_t)pend > S.cap_bits) *overflow = 1;
+}
+
+// The bits of one group (place_group's nbv, pendv; lo: the records' low1) from bit offset `off` on: lane j places
+// the pieces of symbol j behind those of the lanes before it - all its bits at once, or its first bit, the inverse
+// bits owed, the rest.  Returns the group's bit count.
+template <bool WIN>
+__device__ __forceinline__ uint32_t put_group(const BitSink& S, int64_t off, uint32_t lo, uint32_t nbv, uint32_t pendv,
+                                              int lane, int* overflow) {
+  const uint32_t len = nbv + pendv;
+  uint32_t incl = len;
+#pragma unroll
+  for (int o = 1; o < 64; o <<= 1) {
+    const uint32_t up = __shfl_up(incl, o, 64);
+    if (lane >= o) incl += up;
+  }
+  const int64_t o = off + (int64_t)(incl - len);
+  if (nbv > 0) {
+    const uint32_t bitsv = lo >> (32u - nbv);
+    if (pendv == 0) {
+      put_bits<WIN>(S, o, bitsv, (int)nbv, overflow);
+    } else {
+      put_resolved<WIN>(S, o, bitsv >> (nbv - 1), pendv, overflow);
+      if (nbv > 1) put_bits<WIN>(S, o + 1 + pendv, bitsv & ((1u << (nbv - 1)) - 1u), (int)nbv - 1, overflow);
+    }
+  }
+  return (uint32_t)__builtin_amdgcn_readlane((int)incl, 63);
+}
+
+// The end of a string of `total` bits (torchac's flush), by one lane and straight into the output: one more pending
+// bit, then the deciding bit and the pending run; the zero padding is there already.  Returns the length in bytes.
+__device__ __forceinline__ int put_flush(const BitSink& S, int64_t total, uint32_t pending, uint32_t low,
+                                         int* overflow) {
+  const uint32_t pend = pending + 1u;
+  put_resolved<false>(S, total, low < 0x40000000u ? 0u : 1u, pend, overflow);
+  return (int)((total + 1 + (int64_t)pend + 7) >> 3);
+}
+
+// ---- strings and symbols ----------------------------------------------------------------------------------------
+// Stream ids: s < B is the y string of image s (which = 1), B + b the z string of image b (which = 0).
 // Segments (dsic_range_encode_seg_ws): the y string of an image is coded as K = 2^lk independent strings, segment k =
 // its symbols [k ns, (k + 1) ns) with ns = ny / K (M / K channels), so the pairs and records of the B K segment
 // strings lie back to back: string s < B K is segment s & (K - 1) of image s >> lk at symbol s * ns, string B K + b
@@ -576,7 +511,7 @@ struct SplitGeom {
   int64_t ns;   // symbols of one y segment
   int gy, gz;   // place: 64-symbol groups per slice of a y segment / z string (place_slicing)
   int ky, kz;   // place: slices per y segment / z string
-  // the whole strings of an image, as the pack kernel walks them: s < B is y string s, B + b the z string b
+  // the whole strings of an image, as the symbols are looked up: s < B is y string s, B + b the z string b
   __device__ __forceinline__ void image(int s, int& which, int& b, int64_t& n, int64_t& base) const {
     which = s < B ? 1 : 0;
     b = which ? s : s - B;
@@ -614,6 +549,101 @@ static inline void place_slicing(int64_t n, int& groups, int& slices) {
   slices = (int)((ng + g - 1) / g);
 }
 
+// table row t, symbol sc of a support of L -> c_low | (c_high - 1) << 16.  A symbol outside the support (cannot happen
+// when meta came from dsic_latent_support on the same latents) raises error bit 2 and is coded as symbol 0.
+__device__ __forceinline__ uint32_t pair_of(const uint16_t* t, int sc, int L, int* err) {
+  if (sc < 0 || sc >= L) {
+    atomicOr(err, 2);
+    sc = 0;
+  }
+  const uint32_t c_low = t[sc];
+  const uint32_t c_high = (sc == L - 1) ? 0x10000u : (uint32_t)t[sc + 1];
+  return c_low | ((c_high - 1u) << 16);
+}
+
+// ---- single-kernel encoder (dsic_range_encode) --------------------------------------------------------------------
+// The split encoder's functions in one wave per (image, string): stream ids 0..B-1 = y strings, B..2B-1 = z strings;
+// several strings (one per SIMD) may share a workgroup.  Per group of 64 symbols: pair_of by the lanes, chain_group
+// (chain_tail for a partial group or one that holds the top symbol, c_high = 65536) on the scalar unit, place_group
+// and put_group by the lanes.  It has registers to spare, so its 64-step block takes LaneBounds.
+__global__ __launch_bounds__(1024) void range_encode_kernel(
+    const float* __restrict__ y, const float* __restrict__ z, const int* __restrict__ meta,
+    const uint16_t* __restrict__ tab_y, const uint16_t* __restrict__ tab_z, int Lmax, int M, int HWy,
+    int N, int HWz, uint8_t* __restrict__ out, int64_t cap_y, int64_t cap_z,
+    int* __restrict__ lengths, int* __restrict__ err, int nstreams, int per_element_y) {
+  const int lane = threadIdx.x & 63;
+  const int sid = __builtin_amdgcn_readfirstlane(blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6));
+  if (sid >= nstreams) return;
+  // streams 0..B-1 are the long y strings, B..2B-1 the short z strings: the y waves share as few
+  // workgroups (= CUs, which a persistent conv workgroup cannot use meanwhile) as possible
+  const int nimg = nstreams >> 1;
+  const int which = sid < nimg ? 1 : 0, b = which ? sid : sid - nimg;
+  const int C = which ? M : N, HW = which ? HWy : HWz;
+  const int64_t n = (int64_t)C * HW;
+  const float* sym = which ? y + (size_t)b * n : z + (size_t)b * n;
+  const bool per_element = which && per_element_y;  // spatial_params: one table row per y symbol
+  const uint16_t* tab = (which ? tab_y + (size_t)b * (per_element ? (size_t)M * HWy : (size_t)M) * Lmax
+                               : tab_z + (size_t)b * N * Lmax);
+  const int smin = meta[4 * b + (which ? 0 : 2)], L = meta[4 * b + (which ? 1 : 3)];
+  const int64_t stride = cap_z + cap_y;  // per image: [z bytes | y bytes], zero-initialised by the caller
+  const BitSink sink{(uint32_t*)(out + (size_t)b * stride + (which ? cap_z : 0)), (which ? cap_y : cap_z) * 8,
+                     nullptr, 0};
+  if (L > Lmax || L < 1) {
+    if (lane == 0) {
+      atomicOr(err, 1);
+      lengths[2 * b + which] = 0;
+    }
+    return;
+  }
+
+  // Two-deep software pipeline for the operand gather: symbols are loaded two groups ahead,
+  // their table entries one group ahead, so neither dependent load round sits on the serial
+  // chain even when L2 latency is several microseconds under a co-running conv kernel.
+  auto sym_of = [&](int64_t g) -> float { return g < n ? sym[g] : 0.f; };
+  auto pair_at = [&](float v, int64_t g) -> uint32_t {
+    if (g >= n) return 0u;
+    const int c = (int)(g / HW);
+    return pair_of(tab + (size_t)(per_element ? g : (int64_t)c) * Lmax, (int)v - smin, L, err);
+  };
+
+  uint32_t low = 0, span = 0, lowm1 = 0xFFFFFFFFu;   // span 0 = 2^32
+  uint32_t pending = 0;
+  int64_t base_bits = 0;  // bits emitted so far (wave-uniform)
+  int overflow = 0;
+
+  uint32_t cur = pair_at(sym_of(lane), lane);
+  float sym1 = sym_of(64 + lane);
+  for (int64_t base = 0; base < n; base += 64) {
+    const float sym2 = sym_of(base + 128 + lane);
+    const uint32_t nxt = pair_at(sym1, base + 64 + lane);
+    const int cnt = (int)((n - base) < 64 ? (n - base) : 64);
+    uint32_t rl = 0, rh = ~0u;   // lanes past cnt: no bit, no E3 run
+    // a full group without the top symbol: bounds in two registers (LaneBounds); else the loop
+    const uint32_t chv = (cur >> 16) + 1u;
+    if (cnt == 64 && !__any(chv == 0x10000u)) chain_group<LaneBounds>(cur << 16, chv << 16, low, lowm1, span, rl, rh);
+    else chain_tail(cur, cnt, low, lowm1, span, rl, rh);
+    uint32_t nbv, pendv;
+    place_group(rl, rh, lane, pending, nbv, pendv);
+    base_bits += (int64_t)put_group<false>(sink, base_bits, rl, nbv, pendv, lane, &overflow);
+    cur = nxt;
+    sym1 = sym2;
+  }
+  if (lane == 0) lengths[2 * b + which] = put_flush(sink, base_bits, pending, low, &overflow);
+  if (__any(overflow) && lane == 0) atomicOr(err, 4);
+}
+
+// ---- split encoder: pack -> chain -> place (dsic_range_encode_ws) -----------------------------------
+// The same coder in three launches on the coder's stream, so that the only long-running one is a wave small
+// enough to share a CU with a persistent conv workgroup (3 x 168 of a SIMD's 512 VGPRs leave 8).
+//  pack  (whole chip, short): every symbol's (c_low, c_high-1) pair, error bits 1 and 2.
+//  chain (one wave per string, <= 8 VGPRs, no LDS): chain_group on scalar registers, 64 pairs per global load
+//        (two groups ahead); per symbol the interval before renormalisation (low1, high1) leaves through two
+//        vector stores per 64 symbols; the final low per string.
+//  place (two whole-chip launches of short waves, one slice of a string each): per symbol the E1/E2 bits and the
+//        E3 run from (low1, high1); summarize writes each slice's carry map and bit count, emit composes the records
+//        in front of its slice and places the slice's bits; the string's last slice writes the flush and the length.
+// Workspace: pairs, rec_low, rec_high [B (M HWy + N HWz)] uint32, then final low [B (K + 1)], then (8-byte aligned)
+// the slice records [B (K ky + kz)] uint2.
 __global__ __launch_bounds__(256) void enc_pack_kernel(const float* __restrict__ y, const float* __restrict__ z,
                                                        const int* __restrict__ meta, const uint16_t* __restrict__ tab_y,
                                                        const uint16_t* __restrict__ tab_z, SplitGeom G,
@@ -627,57 +657,11 @@ __global__ __launch_bounds__(256) void enc_pack_kernel(const float* __restrict__
   const uint16_t* tab = (which ? tab_y + (size_t)b * (per_element ? (size_t)G.M * G.HWy : (size_t)G.M) * Lmax
                                : tab_z + (size_t)b * G.N * Lmax);
   const int smin = meta[4 * b + (which ? 0 : 2)], L = meta[4 * b + (which ? 1 : 3)];
-  if (L > Lmax || L < 1) return;   // place_kernel reports it
+  if (L > Lmax || L < 1) return;   // the place kernels report it
   for (int64_t g = (int64_t)blockIdx.x * 256 + threadIdx.x; g < n; g += (int64_t)gridDim.x * 256) {
     const int c = (int)(g / HW);
-    int sc = (int)sym[g] - smin;
-    if (sc < 0 || sc >= L) {
-      atomicOr(err, 2);
-      sc = 0;
-    }
-    const uint16_t* t = tab + (size_t)(per_element ? g : (int64_t)c) * Lmax;
-    const uint32_t c_low = t[sc];
-    const uint32_t c_high = (sc == L - 1) ? 0x10000u : (uint32_t)t[sc + 1];
-    pairs[base + g] = c_low | ((c_high - 1u) << 16);
+    pairs[base + g] = pair_of(tab + (size_t)(per_element ? g : (int64_t)c) * Lmax, (int)sym[g] - smin, L, err);
   }
-}
-
-// enc_step with the bounds taken from the packed pair by scalar ops: cl = c_low << 16, ch = c_high << 16, which is
-// 0 for c_high = 65536; then hi_add = floor(span 2^16 / 2^16) = span (mod 2^32, as the general path's 64-bit product).
-template <int J>
-__device__ __forceinline__ void chain_step(uint32_t& low, uint32_t& lowm1, uint32_t& span, uint32_t& cl, uint32_t& ch,
-                                           uint32_t pv, uint32_t& rec_low, uint32_t& rec_high) {
-  const uint32_t pn = J < 63 ? rlane<(J < 63 ? J + 1 : 63)>(pv) : 0u;
-  const uint32_t ml = __umulhi(span, cl), mh = __umulhi(span, ch);
-  const uint32_t lo_add = span ? ml : cl;
-  const uint32_t hi_add = ch ? (span ? mh : ch) : span;
-  const uint32_t low1 = low + lo_add;
-  const uint32_t high1 = lowm1 + hi_add;
-  const uint32_t span1 = hi_add - lo_add;
-  wlane<J>(rec_low, low1);
-  wlane<J>(rec_high, high1);
-  const int nb = __builtin_clz(low1 ^ high1);
-  const uint32_t q2 = (high1 | ~low1) << 1;
-  const int m = __builtin_clz(q2 << nb);
-  const int sh = nb + m;
-  span = span1 << sh;
-  low = (low1 << sh) & 0x7FFFFFFFu;
-  lowm1 = low - 1u;
-  cl = pn << 16;
-  ch = (pn & 0xFFFF0000u) + 0x10000u;
-}
-
-template <int J0>
-__device__ __forceinline__ void chain_steps8(uint32_t& low, uint32_t& lowm1, uint32_t& span, uint32_t& cl,
-                                             uint32_t& ch, uint32_t pv, uint32_t& rl, uint32_t& rh) {
-  chain_step<J0 + 0>(low, lowm1, span, cl, ch, pv, rl, rh);
-  chain_step<J0 + 1>(low, lowm1, span, cl, ch, pv, rl, rh);
-  chain_step<J0 + 2>(low, lowm1, span, cl, ch, pv, rl, rh);
-  chain_step<J0 + 3>(low, lowm1, span, cl, ch, pv, rl, rh);
-  chain_step<J0 + 4>(low, lowm1, span, cl, ch, pv, rl, rh);
-  chain_step<J0 + 5>(low, lowm1, span, cl, ch, pv, rl, rh);
-  chain_step<J0 + 6>(low, lowm1, span, cl, ch, pv, rl, rh);
-  chain_step<J0 + 7>(low, lowm1, span, cl, ch, pv, rl, rh);
 }
 
 __global__ __launch_bounds__(64) __attribute__((amdgpu_num_vgpr(8))) void enc_chain_kernel(
@@ -704,16 +688,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_num_vgpr(8))) void enc_ch
   for (; g < nfull; g += 64) {
     const uint32_t n2 = ld(g + 128);
     uint32_t rl = 0, rh = 0;
-    const uint32_t p0 = rlane<0>(cur);
-    uint32_t cl = p0 << 16, ch = (p0 & 0xFFFF0000u) + 0x10000u;
-    chain_steps8<0>(low, lowm1, span, cl, ch, cur, rl, rh);
-    chain_steps8<8>(low, lowm1, span, cl, ch, cur, rl, rh);
-    chain_steps8<16>(low, lowm1, span, cl, ch, cur, rl, rh);
-    chain_steps8<24>(low, lowm1, span, cl, ch, cur, rl, rh);
-    chain_steps8<32>(low, lowm1, span, cl, ch, cur, rl, rh);
-    chain_steps8<40>(low, lowm1, span, cl, ch, cur, rl, rh);
-    chain_steps8<48>(low, lowm1, span, cl, ch, cur, rl, rh);
-    chain_steps8<56>(low, lowm1, span, cl, ch, cur, rl, rh);
+    chain_group<PackedPairs>(cur, 0u, low, lowm1, span, rl, rh);
     __builtin_amdgcn_raw_buffer_store_b32(rl, rlo, voff, g * 4u, 0);
     __builtin_amdgcn_raw_buffer_store_b32(rh, rhi, voff, g * 4u, 0);
     cur = n1;
@@ -722,23 +697,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_num_vgpr(8))) void enc_ch
   const int cnt = (int)((uint32_t)n - g);   // 0..63 symbols left
   if (cnt > 0) {
     uint32_t rl = 0, rh = 0;
-    for (int j = 0; j < cnt; ++j) {
-      const uint32_t pr = __builtin_amdgcn_readlane(cur, j);
-      const uint32_t cl = pr << 16, ch = (pr & 0xFFFF0000u) + 0x10000u;
-      const uint32_t lo_add = span ? __umulhi(span, cl) : cl;
-      const uint32_t hi_add = ch ? (span ? __umulhi(span, ch) : ch) : span;
-      const uint32_t low1 = low + lo_add, high1 = lowm1 + hi_add, span1 = hi_add - lo_add;
-      // lane select through M0, 4 wait states after the SALU write (see range_encode_kernel)
-      asm volatile("s_mov_b32 m0, %4\n\ts_nop 3\n\tv_writelane_b32 %0, %2, m0\n\tv_writelane_b32 %1, %3, m0"
-                   : "+v"(rl), "+v"(rh)
-                   : "s"(low1), "s"(high1), "s"(j));
-      const int nb = __builtin_clz(low1 ^ high1);
-      const int m = __builtin_clz(((high1 | ~low1) << 1) << nb);
-      const int sh = nb + m;
-      span = span1 << sh;
-      low = (low1 << sh) & 0x7FFFFFFFu;
-      lowm1 = low - 1u;
-    }
+    chain_tail(cur, cnt, low, lowm1, span, rl, rh);
     __builtin_amdgcn_raw_buffer_store_b32(rl, rlo, voff, g * 4u, 0);   // lanes >= cnt: out of range
     __builtin_amdgcn_raw_buffer_store_b32(rh, rhi, voff, g * 4u, 0);
   }
@@ -751,10 +710,10 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_num_vgpr(8))) void enc_ch
 // its own), so every workgroup lives for a few microseconds and none keeps a CU from the next conv launch for long.
 //  summarize: the slice's carry map of the pending count, c -> (a ? c : 0) + t (a = 1: no symbol of the slice emits
 //             a bit), and its bit count with carry-in 0; one record per slice.
-//  emit:      the records of the slices in front of it give the slice's carry-in and its bit offset; then the same
-//             put_bits / put_ones calls at the same offsets as range_encode_kernel, and the string's last slice
-//             writes the flush and the length.  Every record is written by the first launch before the second reads
-//             one: no wave waits for another, and the workspace may hold anything when the call starts.
+//  emit:      the records of the slices in front of it give the slice's carry-in and its bit offset; then put_group
+//             per group through the wave's LDS window, and the string's last slice writes the flush and the length.
+//             Every record is written by the first launch before the second reads one: no wave waits for another,
+//             and the workspace may hold anything when the call starts.
 // Composition: (a1, t1) then (a2, t2) = (a1 & a2, (a2 ? t1 : 0) + t2).  A record is (t, len | head << 31), head = !a.
 #ifndef PLACE_WAVES
 #define PLACE_WAVES 4
@@ -771,33 +730,6 @@ __device__ __forceinline__ void place_load(const uint32_t* __restrict__ rlo, con
     lo[i] = j < j1 ? rlo[j] : 0u;
     hi[i] = j < j1 ? rhi[j] : ~0u;
   }
-}
-
-// One group of 64 records; lane j: symbol j of the group, lanes past the slice end hold (0, ~0): no bit, no E3 run.
-// Per lane the final bits of the symbol (nbv of them) and the inverse bits owed in front of the first (pendv, 0
-// unless nbv > 0); `pending` (wave-uniform) goes from the count owed in front of the group to the count owed behind
-// it.  The scans of range_encode_kernel's fast path.
-__device__ __forceinline__ void place_group(uint32_t lo, uint32_t hi, int lane, uint32_t& pending, uint32_t& nbv,
-                                            uint32_t& pendv) {
-  nbv = (uint32_t)__builtin_clz(lo ^ hi);
-  const uint32_t mv = (uint32_t)__builtin_clz((((hi | ~lo) << nbv) << 1) | 1u);
-  uint32_t T = mv;
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) {
-    const uint32_t up = __shfl_up(T, o, 64);
-    if (lane >= o) T += up;
-  }
-  const uint32_t Tex = T - mv;
-  const uint64_t heads = __ballot(nbv > 0);
-  const uint64_t before = heads & ((1ull << lane) - 1ull);
-  const int hb = 63 - __builtin_clzll(before | 1ull);
-  const uint32_t Tex_h = __shfl(Tex, hb, 64);
-  const uint32_t pend_in = before ? Tex - Tex_h : pending + Tex;
-  pendv = nbv ? pend_in : 0u;
-  const int hl = 63 - __builtin_clzll(heads | 1ull);
-  const uint32_t T63 = __builtin_amdgcn_readlane(T, 63);
-  const uint32_t Tex_hl = __builtin_amdgcn_readlane(Tex, hl);
-  pending = heads ? T63 - Tex_hl : pending + T63;
 }
 
 __global__ __launch_bounds__(64 * PLACE_WAVES) void enc_place_sum_kernel(const int* __restrict__ meta, SplitGeom G,
@@ -903,14 +835,13 @@ __global__ __launch_bounds__(64 * PLACE_WAVES) void enc_place_emit_kernel(
 
   const int64_t stride = cap_z + (int64_t)G.K * cap_y;
   uint32_t* dst32 = (uint32_t*)(out + (size_t)b * stride + (which ? cap_z + (int64_t)seg * cap_y : 0));
-  const int64_t cap_bits = (which ? cap_y : cap_z) * 8;
   int overflow = 0;
   // the slice's bits are ORed into an LDS window first: one global atomic per output word instead of one per piece
   __shared__ uint32_t win_all[PLACE_WAVES][PLACE_WIN];
   uint32_t* win = win_all[threadIdx.x >> 6];
 #pragma unroll
   for (int i = lane; i < PLACE_WIN; i += 64) win[i] = 0u;
-  const int64_t wbase = (int64_t)(off >> 5);
+  const BitSink sink{dst32, (which ? cap_y : cap_z) * 8, win, (int64_t)(off >> 5)};
   for (int64_t c0 = j0; c0 < j1; c0 += PLACE_CHUNK * 64) {
     if (c0 != j0) place_load(rlo, rhi, c0, j1, lane, lo, hi);
 #pragma unroll
@@ -918,49 +849,19 @@ __global__ __launch_bounds__(64 * PLACE_WAVES) void enc_place_emit_kernel(
       if (c0 + i * 64 >= j1) break;
       uint32_t nbv, pendv;
       place_group(lo[i], hi[i], lane, pending, nbv, pendv);
-      const uint32_t len = nbv + pendv;
-      uint32_t incl = len;
-#pragma unroll
-      for (int o = 1; o < 64; o <<= 1) {
-        const uint32_t up = __shfl_up(incl, o, 64);
-        if (lane >= o) incl += up;
-      }
-      const int64_t o = (int64_t)off + (int64_t)(incl - len);
-      if (nbv > 0) {   // the pieces of range_encode_kernel, at the same offsets
-        const uint32_t bitsv = lo[i] >> (32u - nbv);
-        if (pendv == 0) {
-          put_bits_w(dst32, win, wbase, cap_bits, o, bitsv, (int)nbv, &overflow);
-        } else {
-          const uint32_t first = bitsv >> (nbv - 1);
-          put_bits_w(dst32, win, wbase, cap_bits, o, first, 1, &overflow);
-          if (!first) put_ones_w(dst32, win, wbase, cap_bits, o + 1, pendv, &overflow);
-          else if (o + 1 + (int64_t)pendv > cap_bits) overflow = 1;
-          if (nbv > 1)
-            put_bits_w(dst32, win, wbase, cap_bits, o + 1 + pendv, bitsv & ((1u << (nbv - 1)) - 1u), (int)nbv - 1,
-                       &overflow);
-        }
-      }
-      off += (uint32_t)__builtin_amdgcn_readlane((int)incl, 63);
+      off += put_group<true>(sink, (int64_t)off, lo[i], nbv, pendv, lane, &overflow);
     }
   }
-  // the window's words that received bits (all inside the capacity: put_bits_w checked each piece)
-  const int64_t wend = (int64_t)((off + 31) >> 5) - wbase;
+  // the window's words that received bits (all inside the capacity: put_bits checked each piece)
+  const int64_t wend = (int64_t)((off + 31) >> 5) - sink.wbase;
   const int nw = wend < PLACE_WIN ? (int)wend : PLACE_WIN;
   __builtin_amdgcn_s_waitcnt(0xc07f);
   __builtin_amdgcn_wave_barrier();
   for (int i = lane; i < nw; i += 64) {
     const uint32_t v = win[i];
-    if (v) atomicOr(dst32 + wbase + i, v);
+    if (v) atomicOr(dst32 + sink.wbase + i, v);
   }
-  if (k == ks - 1 && lane == 0) {   // flush (torchac): one more pending bit, then the deciding bit and the pending run
-    const int64_t total = (int64_t)off;
-    const uint32_t pend = pending + 1u;
-    const uint32_t bit = final_low[s] < 0x40000000u ? 0u : 1u;
-    put_bits(dst32, cap_bits, total, bit, 1, &overflow);
-    if (!bit) put_ones(dst32, cap_bits, total + 1, pend, &overflow);
-    else if (total + 1 + (int64_t)pend > cap_bits) overflow = 1;
-    *length = (int)((total + 1 + (int64_t)pend + 7) >> 3);
-  }
+  if (k == ks - 1 && lane == 0) *length = put_flush(sink, (int64_t)off, pending, final_low[s], &overflow);
   if (__any(overflow) && lane == 0) atomicOr(err, 4);
 }
 
@@ -1074,10 +975,10 @@ __global__ __launch_bounds__(256) void range_decode_kernel(const uint8_t* __rest
   const int nseg = (L + 63) >> 6;  // table entries per row, 64 per register
   if (nseg == 1 && !per_element) {
     // ---- fast path: the whole table row in one register, rows per channel ---------------------------------
-    // Same arithmetic, shorter chain (round 3: 371 -> 188 ns per symbol at the bench shape): the state is (low, span) with span =
-    // high - low + 1 kept mod 2^32 (0 means 2^32) and the lanes hold c << 16, so floor(span c / 2^16) is ONE
-    // v_mul_hi_u32 per lane for the search and one s_mul_hi_u32 for each bound of the decoded symbol (the general
-    // path multiplies in 64 bits); c_high = 65536 (last symbol) is hi_add = span.  The two renormalisation shifts
+    // The encoder's IntervalStep, shorter chain (round 3: 371 -> 188 ns per symbol at the bench shape): the state is
+    // (low, span, lowm1) and the lanes hold c << 16, so floor(span c / 2^16) is ONE v_mul_hi_u32 per lane for the
+    // search, and the decoded symbol's bounds are two of those products (the general path multiplies in 64 bits);
+    // c_high = 65536 (last symbol) is hi_add = span.  The two renormalisation shifts
     // (E1/E2 by nb, E3 by m) are applied together and their stream bits taken together when nb + m < 32.  Decoded
     // symbols collect in a register (lane g & 63) and leave as one coalesced 256-byte store per 64 symbols
     // instead of a 4-byte store per symbol.  (Stream bits cut out of two window lanes by absolute bit position,
@@ -1105,20 +1006,17 @@ __global__ __launch_bounds__(256) void range_decode_kernel(const uint8_t* __rest
         asm volatile("s_mov_b32 m0, %2\n\ts_nop 3\n\tv_writelane_b32 %0, %1, m0" : "+v"(outv) : "s"(sv), "s"(ln));
         if (ln == 63) dst[g - 63 + lane] = (float)outv;
       }
-      const uint32_t low1 = low + lo_add;
-      const uint32_t high1 = lowm1 + hi_add;
-      const uint32_t span1 = hi_add - lo_add;
-      const int nb = __builtin_clz(low1 ^ high1);
-      const uint32_t q2 = (high1 | ~low1) << 1;
-      const int m = __builtin_clz(q2 << nb);
+      const IntervalStep st{low + lo_add, lowm1 + hi_add, hi_add - lo_add};
+      int nb, m;
+      st.shifts(nb, m);
       const int sh = nb + m;
       if (__builtin_expect(sh < 32, 1)) {
-        span = span1 << sh;
-        low = (low1 << sh) & 0x7FFFFFFFu;
+        span = st.span(sh);
+        low = st.low(sh);
         const uint32_t v2 = sh ? ((value << sh) | take(sh)) : value;
         value = m ? (v2 ^ 0x80000000u) : v2;
       } else {  // a long E3 run: the two shifts one after the other, as the general path
-        uint32_t lo2 = low1 << nb, hi2 = (high1 << nb) | ((1u << nb) - 1u);
+        uint32_t lo2 = st.low1 << nb, hi2 = (st.high1 << nb) | ((1u << nb) - 1u);
         value = nb ? ((value << nb) | take(nb)) : value;
         lo2 = (lo2 << m) & 0x7FFFFFFFu;
         hi2 = (hi2 << m) | 0x80000000u | ((1u << m) - 1u);
@@ -1140,6 +1038,10 @@ __global__ __launch_bounds__(256) void range_decode_kernel(const uint8_t* __rest
     }
     return;
   }
+  // ---- general path: rows wider than 64 entries, or a row per symbol -------------------------------------------
+  // Kept apart from IntervalStep on purpose: a step searches up to Lmax / 64 registers of table entries, so its bounds
+  // are plain 17-bit values (c_high up to 65536) multiplied in 64 bits against (low, high), not the c << 16 operands
+  // of the one-register paths; it shares no operand form with them.
   // Table row of the current symbol: per channel (row changes every HW symbols) or per element
   // (spatial_params: a row per symbol).  Segment 0 of the NEXT row is prefetched while the
   // current symbol is decoded, so the row load never sits on the serial chain.
@@ -1197,7 +1099,7 @@ __global__ __launch_bounds__(256) void range_decode_kernel(const uint8_t* __rest
       }
       const int sidx = cnt - 1;
       if (lane == 0) dst[g] = (float)(sidx + smin);
-      // interval update + renormalisation (same arithmetic as the encoder)
+      // interval update + renormalisation, E1/E2 then E3, on (low, high)
       const uint32_t hi_add = (uint32_t)(((uint64_t)r * c_high + c_high) >> 16);
       const uint32_t lo_add = (uint32_t)(((uint64_t)r * c_low + c_low) >> 16);
       high = (low - 1u) + hi_add;

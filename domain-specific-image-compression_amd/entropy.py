@@ -158,21 +158,15 @@ def compress_latents(y_tilde, z_tilde, sigma_y, nu_y, sigma_z, tail=10, Lmax=DEF
     out = torch.zeros((B, (cap_z + K * cap_y) // 4), dtype=torch.int32, device=dev).view(torch.uint8)
     lengths = torch.zeros((B, 1 + K), dtype=torch.int32, device=dev)
     L = _lib.load()
-    ws = None
-    if K > 1:
+    if use_split:
+        # K = 1 is dsic_range_encode_ws's launches.  The caching allocator on the coder's stream: every call in
+        # flight has its own workspace
         nbytes = L.dsic_range_encode_seg_workspace_size(B, M, Hy * Wy, N, Hz * Wz, K)
         ws = torch.empty(((nbytes + 3) // 4,), dtype=torch.int32, device=dev)
         _lib.check(L.dsic_range_encode_seg_ws(_p(y), _p(z), _p(meta), _p(tab_y), _p(tab_z), Lmax, B, M, Hy * Wy,
                                               N, Hz * Wz, _p(out), cap_y, cap_z, _p(lengths), _p(err),
                                               int(per_element), K, _p(ws), ws.numel() * 4, _stream()),
                    "range_encode_seg_ws")
-    elif use_split:
-        nbytes = L.dsic_range_encode_workspace_size(B, M, Hy * Wy, N, Hz * Wz)
-        # the caching allocator on the coder's stream: every call in flight has its own
-        ws = torch.empty(((nbytes + 3) // 4,), dtype=torch.int32, device=dev)
-        _lib.check(L.dsic_range_encode_ws(_p(y), _p(z), _p(meta), _p(tab_y), _p(tab_z), Lmax, B, M, Hy * Wy,
-                                          N, Hz * Wz, _p(out), cap_y, cap_z, _p(lengths), _p(err), int(per_element),
-                                          _p(ws), ws.numel() * 4, _stream()), "range_encode_ws")
     else:
         _lib.check(L.dsic_range_encode(_p(y), _p(z), _p(meta), _p(tab_y), _p(tab_z), Lmax, B, M, Hy * Wy,
                                        N, Hz * Wz, _p(out), cap_y, cap_z, _p(lengths), _p(err),

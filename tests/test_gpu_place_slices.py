@@ -1,9 +1,11 @@
 """The place step of the split encoder in slices (summarize -> emit), and the CDF tables that share evaluations:
-bytes, lengths and error bits equal to the single-kernel encoder, tables equal to the oracle's."""
+bytes, lengths and error bits equal to the single-kernel encoder and its strings to the bit-serial CPU oracle's on the
+run's tables, tables equal to the oracle's."""
 import numpy as np
 import pytest
 import torch
 
+import coder_oracle as O
 from oracle import entropy_ref as E
 
 pytestmark = pytest.mark.gpu
@@ -39,6 +41,8 @@ def test_slice_geometry(B, M, Hy, Wy, N, Hz, Wz):
     new, old = _encode(*args, split=True), _encode(*args, split=False)
     assert int(new["err"].item()) == 0
     _same(new, old)
+    O.assert_oracle_of(new, args[0], args[1])
+    O.assert_oracle_of(old, args[0], args[1])
 
 
 def test_e3_runs_across_many_slices():
@@ -57,6 +61,8 @@ def test_e3_runs_across_many_slices():
     new, old = _encode(*args, split=True), _encode(*args, split=False)
     assert int(new["err"].item()) == 0
     _same(new, old)
+    O.assert_oracle_of(new, args[0], args[1])
+    O.assert_oracle_of(old, args[0], args[1])
 
 
 def _ws_call(L, t, meta, tab_y, tab_z, Lmax, shape, ws, stream):
@@ -86,12 +92,17 @@ def test_garbage_workspace_and_two_streams():
                                             torch.from_numpy(sz).cuda(), meta, Lmax)
     assert int(err0.item()) == 0
     ref = _encode(y, z, sy, ny, sz, split=False, Lmax=Lmax)
+    assert int(ref["err"].item()) == 0
+    want = O.oracle_strings(y, z, meta, tab_y, tab_z)
+    O.assert_oracle(ref, want, ref["cap_z"])
     shape = (B, M, Hy * Wy, N, Hz * Wz)
     nbytes = L.dsic_range_encode_workspace_size(*shape)
     cur = torch.cuda.current_stream()
     ws = torch.full(((nbytes + 3) // 4,), -1, dtype=torch.int32, device="cuda")
     for _ in range(2):
-        _same(_ws_call(L, t, meta, tab_y, tab_z, Lmax, shape, ws, cur.cuda_stream), ref)
+        got = _ws_call(L, t, meta, tab_y, tab_z, Lmax, shape, ws, cur.cuda_stream)
+        _same(got, ref)
+        O.assert_oracle(got, want, ref["cap_z"])
     streams = [torch.cuda.Stream(), torch.cuda.Stream()]
     wss = [torch.full_like(ws, -1) for _ in streams]
     torch.cuda.synchronize()
@@ -101,6 +112,7 @@ def test_garbage_workspace_and_two_streams():
     torch.cuda.synchronize()
     for r in res:
         _same(r, ref)
+        O.assert_oracle(r, want, ref["cap_z"])
 
 
 def _tables(meta_rows, sigma_z, sigma_y, nu_y, Lmax):

@@ -1,9 +1,12 @@
 """The split range encoder (pack -> chain -> place, dsic_range_encode_ws) writes the same bytes, lengths and error
-bits as the single-kernel encoder (dsic_range_encode) for every input."""
+bits as the single-kernel encoder (dsic_range_encode) for every input, and where no error bit is set both write the
+strings of the bit-serial CPU oracle on the run's tables (the two encoders share their interval arithmetic, so their
+equality alone does not check it)."""
 import numpy as np
 import pytest
 import torch
 
+import coder_oracle as O
 from dsic_amd import synthetic as S
 
 pytestmark = pytest.mark.gpu
@@ -21,6 +24,14 @@ def _same(new, old):
     assert torch.equal(new["lengths"], old["lengths"])
     assert int(new["err"].item()) == int(old["err"].item())
     assert torch.equal(new["bytes"], old["bytes"])
+
+
+def _oracle(new, old, y, z):
+    """both encoders' strings are the oracle's (runs without an error bit)"""
+    assert int(new["err"].item()) == 0 and int(old["err"].item()) == 0
+    want = O.oracle_strings(y, z, new["meta"], new["tab_y"], new["tab_z"])
+    O.assert_oracle(new, want, new["cap_z"])
+    O.assert_oracle(old, want, old["cap_z"])
 
 
 def _stress(case, rng):
@@ -46,7 +57,10 @@ def _stress(case, rng):
 
 @pytest.mark.parametrize("case", ["random", "peaky", "runs", "single"])
 def test_stress_cases(case):
-    _same(*_both(*_stress(case, np.random.default_rng(11))))
+    args = _stress(case, np.random.default_rng(11))
+    new, old = _both(*args)
+    _same(new, old)
+    _oracle(new, old, args[0], args[1])
 
 
 def test_top_symbol_c_high_65536():
@@ -61,6 +75,7 @@ def test_top_symbol_c_high_65536():
     new, old = _both(*[a.astype(np.float32) for a in (y, z, sy, ny, sz)], tail=0)
     assert int(new["err"].item()) == 0
     _same(new, old)
+    _oracle(new, old, y, z)
 
 
 def test_long_pending_runs_across_place_slices():
@@ -78,6 +93,7 @@ def test_long_pending_runs_across_place_slices():
     new, old = _both(*[a.astype(np.float32) for a in (y, z, sy, ny, sz)])
     assert int(new["err"].item()) == 0
     _same(new, old)
+    _oracle(new, old, y, z)
 
 
 def test_non_finite_latents():
@@ -128,6 +144,10 @@ def test_symbol_outside_support_and_overflow():
         if cap_y == 32:
             assert int(res[0]["err"].item()) & 4
         _same(*res)
+        # the symbols outside the support coded as symbol 0: the oracle's strings, cut where the capacity ends
+        want = O.oracle_strings(y, z, meta, tab_y, tab_z)
+        for r in res:
+            O.assert_oracle_prefix(r, want, cap_z, cap_y)
 
 
 @pytest.fixture(scope="module")
@@ -150,6 +170,7 @@ def test_bench_batch_through_model(bench_latents):
     old = entropy.compress_latents(*args, split=False)
     assert int(new["err"].item()) == 0
     _same(new, old)
+    _oracle(new, old, out["y_tilde"], out["z_tilde"])
 
 
 def test_spatial_params():
@@ -169,3 +190,4 @@ def test_spatial_params():
     old = entropy.compress_latents(*args, split=False)
     assert int(new["err"].item()) == 0
     _same(new, old)
+    _oracle(new, old, out["y_tilde"], out["z_tilde"])
