@@ -120,7 +120,9 @@ __global__ __launch_bounds__(256, 2) void ssim_level_kernel(const float* __restr
   // 2x2 average of rows (r-1, r), r odd: same summation order as avgpool2_kernel
   auto pool_rows = [&](int r, const Row& r0, const Row& r1) {
     if (!(pool && (r & 1) && r < own_end && pvalid)) return;
-    if (col0 >= W || (strips > 1 && col0 >= (strip + 1) * SSIM_STRIP)) return;
+    // a strip pools the 244 input columns it owns; the last one pools through W (Wo = W - 10 decides the strip
+    // count, so up to 10 input columns lie beyond strips * 244)
+    if (col0 >= W || (strip + 1 < strips && col0 >= (strip + 1) * SSIM_STRIP)) return;
     const size_t o = ((size_t)plane * (H >> 1) + (r >> 1)) * (W >> 1) + (col0 >> 1);
     // both planes at once: lane [0] = X, lane [1] = Y
     const floatx2 q0 = (((r0.p[0] + r0.p[1]) + r1.p[0]) + r1.p[1]) * 0.25f;
