@@ -50,8 +50,10 @@ def set_kernel_timer(timer):
     _kernel_timer = timer
 
 
-def _conv_kernel_name(win, stride, Wo, Cin, CoutP):
-    """Template instantiation conv_igemm.hip dispatches to (for profile matching)."""
+def _conv_kernel_name(win, stride, Wo, Cin, CoutP, Ho=None, B=None, nphase=1):
+    """Template instantiation conv_igemm.hip dispatches to (for profile matching).  Ho, B, nphase (4 for the
+    transposed conv): the workgroup count that decides between two column tiles per wave and column blocks for
+    CoutP > 128 (run_conv_ck); without them the grid is taken to be large."""
     ck = (32 if Cin % 32 == 0 else 8) if win == 3 else (16 if Cin % 16 == 0 else 8)
     if Wo > 8:
         tile = (16, 8, 1)
@@ -63,6 +65,10 @@ def _conv_kernel_name(win, stride, Wo, Cin, CoutP):
             ck = 8
     nt = CoutP // 32
     ntw, narrow = (1, 1) if nt == 1 else ((1, 0) if nt <= 4 else (2, 0))
+    if ntw == 2 and Ho is not None and B is not None:
+        wgs = -(-Wo // tile[0]) * -(-Ho // tile[1]) * -(-B // tile[2]) * nphase
+        if wgs < 512:
+            ntw = 1                                     # columns split over blockIdx.z instead
     return f"conv_igemm_kernel<{win},{stride},{tile[0]},{tile[1]},{tile[2]},{ck},{ntw},{narrow}>"
 
 
@@ -148,7 +154,7 @@ def conv2d_nhwc(x, w_packed, bias, Cout, k, stride, act=ACT_NONE, beta=None, gam
     if out is None:
         out = torch.empty((B, Ho, Wo, Cout), dtype=torch.float32, device=x.device)
     L = _lib.load()
-    _timed(_conv_kernel_name(k, stride, Wo, CinP, round_up(Cout, 32)),
+    _timed(_conv_kernel_name(k, stride, Wo, CinP, round_up(Cout, 32), Ho, B),
            2.0 * B * Ho * Wo * Cout * (cin_real or CinP) * k * k,
            lambda: _lib.check(L.dsic_conv2d_nhwc(_p(x), _p(w_packed), _p(bias), _p(beta), _p(gamma),
                                                  _p(out), B, H, W, CinP, Cout, k, stride, act, _stream()),
@@ -394,7 +400,7 @@ def conv_transpose2d_nhwc(x, w_packed, bias, Cout, act=ACT_NONE, beta=None, gamm
     if out is None:
         out = torch.empty((B, 2 * H, 2 * W, Cout), dtype=torch.float32, device=x.device)
     L = _lib.load()
-    _timed(_conv_kernel_name(3, 1, W, Cin, round_up(Cout, 32)),
+    _timed(_conv_kernel_name(3, 1, W, Cin, round_up(Cout, 32), H, B, 4),
            2.0 * B * H * W * Cout * Cin * 25,
            lambda: _lib.check(L.dsic_conv_transpose2d_nhwc(_p(x), _p(w_packed), _p(bias), _p(beta),
                                                            _p(gamma), _p(out), B, H, W, Cin, Cout, act,

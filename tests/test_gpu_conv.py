@@ -35,6 +35,11 @@ def _pad8(x_nhwc):
     return torch.nn.functional.pad(x_nhwc, (0, 8 - c % 8))
 
 
+def _nan(*shape):
+    """An output buffer that is no other call's result: an element the kernel leaves unwritten stays NaN."""
+    return torch.full(shape, float("nan"), device="cuda")
+
+
 def _tol(ref, K):
     return 2e-6 * float(ref.abs().max()) * max(1.0, K ** 0.5 / 8) + 1e-6
 
@@ -86,7 +91,8 @@ CONV_CASES = [
     (2, 128, 128, 40, 24, 5, 2, "gdn"),      # g_a.2/6/10
     (1, 128, 128, 19, 37, 3, 1, "gdn"),      # odd sizes, tile borders
     (1, 128, 128, 17, 33, 5, 2, "none"),
-    (3, 128, 192, 10, 14, 5, 2, "none"),     # g_a.14 (two column tiles per wave)
+    (3, 128, 192, 10, 14, 5, 2, "none"),     # g_a.14: conv_igemm_kernel<5,2,8,8,2,16,1,0>, 2 column blocks (2 workgroups
+                                             # < 512, so not the two-column-tiles-per-wave instance)
     (3, 192, 128, 6, 8, 3, 1, "relu"),       # h_a.0, 8x8x2 tile
     (5, 128, 128, 6, 8, 5, 2, "relu"),       # h_a.4 -> 3x4 grid, 4x4x8 tile, ragged batch
     (9, 128, 128, 3, 4, 5, 2, "none"),       # h_a.6
@@ -250,7 +256,7 @@ def test_winograd_conv_vs_oracle(ops, B, Cin, Cout, H, W, act, variant):
         ref = torch.relu(ref)
     u = _wino_weights(ops, variant, ops.pack_wino_weight(w.cuda()), Cout, Cin)
     y = ops.conv3x3_wino_nhwc(_nhwc(x).cuda(), u, b.cuda(), Cout, code,
-                              (beta_p ** 2 - 2 ** -18).cuda(), (gam_p ** 2 - 2 ** -18).cuda())
+                              (beta_p ** 2 - 2 ** -18).cuda(), (gam_p ** 2 - 2 ** -18).cuda(), out=_nan(B, H, W, Cout))
     got = ops.nhwc_to_nchw(y).cpu()
     assert got.shape == ref.shape
     err = float((got - ref).abs().max())
@@ -286,7 +292,8 @@ def test_conv5x5_stride2_as_winograd_over_space_to_depth(ops, B, Cs, Cout, H, W,
     xs = ops.space_to_depth(_nhwc(x).cuda())
     u = _wino_weights(ops, variant, ops.pack_wino_s2_weight(w.cuda()), Cout, 4 * Cs)
     y = ops.conv3x3_wino_nhwc(xs, u, b.cuda(), Cout, code,
-                              (beta_p ** 2 - 2 ** -18).cuda(), (gam_p ** 2 - 2 ** -18).cuda(), s2d_in=True)
+                              (beta_p ** 2 - 2 ** -18).cuda(), (gam_p ** 2 - 2 ** -18).cuda(), s2d_in=True,
+                              out=_nan(B, H // 2, W // 2, Cout))
     got = ops.nhwc_to_nchw(y).cpu()
     assert got.shape == ref.shape
     err = float((got - ref).abs().max())
@@ -351,7 +358,8 @@ def test_conv_transpose_winograd_vs_oracle(ops, B, Cin, Cout, H, W, act, variant
         ref = torch.relu(ref)
     u = _wino_weights(ops, variant, ops.pack_wino_convT_weight(w.cuda()), Cout, Cin, 4)
     y = ops.conv_transpose2d_wino_nhwc(_nhwc(x).cuda(), u, b.cuda(), Cout, code,
-                                       (beta_p ** 2 - 2 ** -18).cuda(), (gam_p ** 2 - 2 ** -18).cuda())
+                                       (beta_p ** 2 - 2 ** -18).cuda(), (gam_p ** 2 - 2 ** -18).cuda(),
+                                       out=_nan(B, 2 * H, 2 * W, Cout))
     got = ops.nhwc_to_nchw(y).cpu()
     assert got.shape == ref.shape
     err = float((got - ref).abs().max())
