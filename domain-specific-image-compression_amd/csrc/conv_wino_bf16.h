@@ -63,6 +63,8 @@ struct Args {
   int64_t part_stride;
   // chunk-major (CM16) activations [B][C/16][H][W][16] on the input / output side (conv_wino_bf16m.hip only)
   int cm_in, cm_out;
+  // conv_wino_bf16m.hip: pass-B chunks with the same dead Winograd row run two to a chunk-pass (conv_wino_pair.h)
+  int pair_b;
 };
 
 constexpr int P = WB_PLANES;

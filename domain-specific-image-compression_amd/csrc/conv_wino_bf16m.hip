@@ -24,12 +24,20 @@
 // straight from the accumulator layout: lane = output channel, so 32 lanes write one pixel's 128 contiguous bytes.
 // No output staging in LDS, no copy-out by the helper waves (they are the longer pole of a phase here).
 //
+// Half-empty chunk-passes.  Where one of pass B's two rows is structurally zero (xi = 3 in the space-to-depth blocks 2
+// and 3, xi = 0 for the ConvTranspose phases 2 and 3) one wave half issues alone and is held by its U fetches; two such
+// chunks run as one chunk-pass (conv_wino_pair.h: tables, V slots, the shorter pass B), bit-identical to one each.
+//
 // Helper waves, window staging, tile tickets, U stream layout and the V layout in LDS are those of
 // conv_wino_bf16.hip with 64 tiles x 8 positions in place of 32 x 16; the same packed weights serve both kernels.
 #include "conv_wino_bf16.h"
+#include "conv_wino_pair.h"
 
 #ifndef WBM_STAMP
-#define WBM_STAMP 0
+#define WBM_STAMP 0   // diagnostic: cycle stamps of the MFMA waves 0 (PQ 0) and 4 (PQ 1) and of helper wave 8 (tools/wbm_stamps.py)
+#endif
+#ifndef WBM_STAMP_C0
+#define WBM_STAMP_C0 0   // first chunk-pass of the tile that gets stamps (32 chunk-passes fit)
 #endif
 #ifndef WBM_ABL
 #define WBM_ABL 0   // diagnostic, wrong results: 1 every window load from tile (0,0) of image 0 (cache hits), 2 no window loads
@@ -68,24 +76,37 @@ constexpr int NLOAD = (WINITEMS + 255) / 256;   // 6 window loads per helper thr
 constexpr int STAGEOFF = SLOTOFF + 64;
 constexpr int NWIN = 3;                          // window buffers: one being transformed, two in flight (LDS-DMA)
 constexpr int STAMPOFF = STAGEOFF + NWIN * WINB;
-constexpr int PARAMOFF = STAMPOFF + (WBM_STAMP ? 1024 : 0);   // bias, beta, gamma: [3][128] floats
+constexpr int PARAMOFF = STAMPOFF + (WBM_STAMP ? 1536 : 0);   // bias, beta, gamma: [3][128] floats
 constexpr int LDS_TOTAL = PARAMOFF + 3 * 128 * 4;
 constexpr int THREADS = 768;
 constexpr int RING = 2;
+// a paired window: nine rows of each of two chunks, the second chunk's behind the first's
+constexpr int PAIRITEMS = 9 * WINW * 4;          // float4 items of one chunk's half: 648
+constexpr int PAIRHALFB = PAIRITEMS * 16;        // 10368 bytes
 
 static_assert(LDS_TOTAL <= 160 * 1024, "LDS budget");
+static_assert(2 * PAIRITEMS == WINITEMS, "a paired window fills one window buffer, piece for piece");
 
 #if WBM_STAMP
-static __device__ long long wbm_stamps[256 * 256];   // low 32 bits of s_memtime (the LDS copy is 4 bytes per stamp)
+// per workgroup 384 stamps: [0, 128) MFMA wave 0, [128, 256) helper wave 8, [256, 384) MFMA wave 4.  An MFMA wave
+// has 3 stamps per chunk-pass at 3 (sigma - C0), its folds at 120..126 and the tile's item at 127; the helper 4 per
+// chunk-pass at 4 (sigma - C0).  Low 32 bits of s_memtime (the LDS copy is 4 bytes per stamp).
+static __device__ long long wbm_stamps[256 * 384];
 #define MSTAMP(w, i)                                                                                   \
   do {                                                                                                 \
     __builtin_amdgcn_sched_barrier(0);                                                                 \
     if (lane == 0 && wave == (w) && tile_count == 3 && (i) >= 0 && (i) < 128)                          \
-      ((unsigned*)(lds_raw + STAMPOFF))[((w) == 0 ? 0 : 128) + (i)] = (unsigned)__builtin_amdgcn_s_memtime();   \
+      ((unsigned*)(lds_raw + STAMPOFF))[((w) == 0 ? 0 : (w) == 8 ? 128 : 256) + (i)] = (unsigned)__builtin_amdgcn_s_memtime();   \
     __builtin_amdgcn_sched_barrier(0);                                                                 \
+  } while (0)
+// stamp k of chunk-pass sigma, PER stamps per chunk-pass, inside the window of 32 chunk-passes from WBM_STAMP_C0
+#define MSTAMPC(w, sigma, k, PER)                                                                      \
+  do {                                                                                                 \
+    if ((sigma) >= WBM_STAMP_C0 && (sigma) < WBM_STAMP_C0 + 32) MSTAMP(w, (PER) * ((sigma) - WBM_STAMP_C0) + (k)); \
   } while (0)
 #else
 #define MSTAMP(w, i)
+#define MSTAMPC(w, sigma, k, PER)
 #endif
 
 // The lane id, recomputed where it is used: volatile, so it is neither hoisted out of the tile loop nor kept in a
@@ -94,33 +115,6 @@ __device__ __forceinline__ int lane_now() {
   int l;
   asm volatile("v_mbcnt_lo_u32_b32 %0, -1, 0\n\tv_mbcnt_hi_u32_b32 %0, -1, %0" : "=v"(l));
   return l;
-}
-
-// Steps of a chunk for wave half PQ in pass PASS: 4 bits per step s, global position xi*4 + nu.  Positions that can
-// be structurally zero come last (MODE 1: xi = 3 / nu = 3; MODE 2: xi = 0 / nu = 0), so the two fragments
-// prefetched across a chunk boundary are live in (almost) every chunk.
-template <int MODE, int PASS, int PQ>
-struct Steps {
-  // pass A: row xi = 1 + PQ; pass B: row xi = 0 (PQ 0) / 3 (PQ 1); nu ascending (MODE 2: descending, nu = 0 can vanish)
-  static constexpr unsigned value =
-      PASS == 0 ? (PQ == 0 ? (MODE == 2 ? 0x4567u : 0x7654u) : (MODE == 2 ? 0x89ABu : 0xBA98u))
-                : (PQ == 0 ? (MODE == 2 ? 0x0123u : 0x3210u) : (MODE == 2 ? 0xCDEFu : 0xFEDCu));
-};
-template <int MODE, int PASS, int PQ>
-__device__ __forceinline__ constexpr int gpos(int s) {
-  return (int)((Steps<MODE, PASS, PQ>::value >> (4 * s)) & 15u);
-}
-// index of a global position inside the V buffer of its pass (8 positions: the pass's two xi rows x 4 nu)
-template <int PASS>
-__device__ __forceinline__ constexpr int lpos_of(int g) {
-  return PASS == 0 ? ((g >> 2) - 1) * 4 + (g & 3) : ((g >> 2) == 3 ? 4 : 0) + (g & 3);
-}
-// step that holds global position g
-template <int MODE, int PASS, int PQ>
-__device__ __forceinline__ constexpr int step_of(int g) {
-  for (int s = 0; s < 4; ++s)
-    if (gpos<MODE, PASS, PQ>(s) == g) return s;
-  return -1;
 }
 
 template <int MODE, bool NT_OUT>
@@ -141,7 +135,11 @@ __global__ __launch_bounds__(THREADS) void conv_wino_bf16m_kernel(const Args a) 
   };
   const int pshift = a.nphase == 4 ? 2 : 0;
   const int nchunks = a.Cin / CK;   // even, >= 4 (host)
-  const int L = 2 * nchunks;        // chunk-passes of a tile: sigma < nchunks is pass A, the rest pass B
+  // Chunk-passes of a tile: sigma < nchunks is pass A, the rest pass B, whose chunks run paired from chunk
+  // pfirst on (conv_wino_pair.h; a.pair_b = 0: never).  Helper and MFMA waves derive pfirst, and from it the length
+  // nchunks + pass_b_len of the tile, from the same slot record.
+  constexpr bool PAIR = MODE != 0;
+  auto pfirst_of = [&](const Tile& t) { return PAIR ? pair_first(MODE, nchunks, t.item & 3, a.pair_b != 0) : nchunks; };
   int tile_count = 0;
   (void)tile_count;
   // per-channel epilogue parameters live in LDS: the MFMA waves read them at the fold (an LDS read is not ordered
@@ -190,6 +188,7 @@ __global__ __launch_bounds__(THREADS) void conv_wino_bf16m_kernel(const Args a) 
       uintx4 rsrc;
     };
     WinAim am;
+    unsigned off2[NLOAD];   // a paired window's offsets (PAIR only); the descriptor is am's
     const int hw = wave - 8;
     const unsigned lds_base = (unsigned)(unsigned long long)(__attribute__((address_space(3))) unsigned char*)lds_raw;
     auto aim = [&](WinAim& m, const Tile& t0) {
@@ -211,7 +210,27 @@ __global__ __launch_bounds__(THREADS) void conv_wino_bf16m_kernel(const Args a) 
 #pragma unroll
       for (int j = 0; j < NLOAD; ++j) m.off[j] = 0x80000000u;
     };
-    auto dma = [&](int wbuf, int chunk) {
+    // A paired window (chunks c, c + 1 of pass B with the same dead row): item i < 648 is (stored row r = pixel / 18
+    // of 9, channel quad) of chunk c, item 648 + i the same of chunk c + 1; stored row r is the window row
+    // pair_window_row(r), the only rows the live Winograd row reads.  Same items per thread and per wave as a whole
+    // window, so the same count of loads; the second chunk is part of the vector offset (the halves do not split on
+    // a wave boundary).  Aimed only for a tile that has pairs; never used for a load past the tile's last chunk-pass.
+    auto aim2 = [&](const Tile& t0) {
+      Tile t = t0;
+      if (WBM_ABL & 1) { t.n = 0; t.tx = 0; t.ty = 0; }
+#pragma unroll
+      for (int j = 0; j < NLOAD; ++j) {
+        const int i = ht + 256 * j;
+        const int half = i >= PAIRITEMS ? 1 : 0;
+        const int ii = i - half * PAIRITEMS;
+        const int pix = ii >> 2, q = ii & 3;
+        const int r = pix / WINW, wx = pix - r * WINW;
+        const int gy = t.ty * 16 - 1 + pair_window_row(MODE, r), gx = t.tx * 16 - 1 + wx;
+        const bool ok = i < WINITEMS && gy >= 0 && gy < a.H && gx >= 0 && gx < a.W && !(WBM_ABL & 2);
+        off2[j] = ok ? (unsigned)(((gy * a.W + gx) * pix_f + 4 * q) * 4) + (unsigned)half * chunk_in_b : 0x80000000u;
+      }
+    };
+    auto dma = [&](int wbuf, int chunk, const unsigned (&off)[NLOAD]) {
       const uintx4 rs = {(unsigned)__builtin_amdgcn_readfirstlane((int)am.rsrc[0]), (unsigned)__builtin_amdgcn_readfirstlane((int)am.rsrc[1]),
                          (unsigned)__builtin_amdgcn_readfirstlane((int)am.rsrc[2]), (unsigned)__builtin_amdgcn_readfirstlane((int)am.rsrc[3])};
       const unsigned soff = (unsigned)chunk * chunk_in_b;
@@ -220,7 +239,7 @@ __global__ __launch_bounds__(THREADS) void conv_wino_bf16m_kernel(const Args a) 
         const unsigned m0v = lds_base + (unsigned)(STAGEOFF + wbuf * WINB + 16 * (hw * 64 + 256 * j));
         if (j < NLOAD - 1 || ht < WINITEMS - 256 * (NLOAD - 1))   // the last piece: lanes 0..15 of helper wave 0
           asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tbuffer_load_dwordx4 %1, %2, %3 offen lds"
-                       :: "s"(m0v), "v"(am.off[j]), "s"(rs), "s"(soff) : "memory");
+                       :: "s"(m0v), "v"(off[j]), "s"(rs), "s"(soff) : "memory");
       }
     };
     // number of loads one dma() adds to this wave's vector-memory counter
@@ -230,7 +249,8 @@ __global__ __launch_bounds__(THREADS) void conv_wino_bf16m_kernel(const Args a) 
       else if (groups == 1) { if (last_piece) asm volatile("s_waitcnt vmcnt(6)" ::: "memory"); else asm volatile("s_waitcnt vmcnt(5)" ::: "memory"); }
       else { if (last_piece) asm volatile("s_waitcnt vmcnt(12)" ::: "memory"); else asm volatile("s_waitcnt vmcnt(10)" ::: "memory"); }
     };
-    static_assert(NLOAD == 6, "the vmcnt immediates above count 6 (5) loads per window");
+    // A paired window is the same 1296 items in the same order (2 x 648), so it adds the same 6 (5) loads per wave.
+    static_assert(NLOAD == 6 && 2 * PAIRITEMS == WINITEMS, "the vmcnt immediates above count 6 (5) loads per window, whole or paired");
     // this thread's 4x4 patch inside a staged window: rows 2*pty .. +3, columns 2*ptx .. +3, quad pq
     const int patch0 = ((2 * pty) * WINW + 2 * ptx) * (CK * 4) + pq * 16;
     // a - b on a register pair: v_pk_add_f32 with the second operand negated (there is no v_pk_sub_f32, and the
@@ -270,16 +290,31 @@ __global__ __launch_bounds__(THREADS) void conv_wino_bf16m_kernel(const Args a) 
           xb[k] = sub4(r2, r1);
         }
       } else {
+        // a dead row (wave-uniform) is neither read nor differenced: all reads of the live rows first
         a_live = zxi != 0u;
         b_live = zxi != 3u;
+        floatx4 r0[4], r1[4], r2[4], r3[4];
+        if (a_live) {
 #pragma unroll
-        for (int k = 0; k < 4; ++k) {
-          const floatx4 r0 = *(const floatx4*)(src + (0 * WINW + k) * (CK * 4));
-          const floatx4 r1 = *(const floatx4*)(src + (1 * WINW + k) * (CK * 4));
-          const floatx4 r2 = *(const floatx4*)(src + (2 * WINW + k) * (CK * 4));
-          const floatx4 r3 = *(const floatx4*)(src + (3 * WINW + k) * (CK * 4));
-          xa[k] = sub4(r0, r2);
-          xb[k] = sub4(r1, r3);
+          for (int k = 0; k < 4; ++k) {
+            r0[k] = *(const floatx4*)(src + (0 * WINW + k) * (CK * 4));
+            r2[k] = *(const floatx4*)(src + (2 * WINW + k) * (CK * 4));
+          }
+        }
+        if (b_live) {
+#pragma unroll
+          for (int k = 0; k < 4; ++k) {
+            r1[k] = *(const floatx4*)(src + (1 * WINW + k) * (CK * 4));
+            r3[k] = *(const floatx4*)(src + (3 * WINW + k) * (CK * 4));
+          }
+        }
+        if (a_live) {
+#pragma unroll
+          for (int k = 0; k < 4; ++k) xa[k] = sub4(r0[k], r2[k]);
+        }
+        if (b_live) {
+#pragma unroll
+          for (int k = 0; k < 4; ++k) xb[k] = sub4(r1[k], r3[k]);
         }
       }
       // columns: nu 0: x0-x2, 1: x1+x2, 2: x2-x1, 3: x1-x3
@@ -297,16 +332,35 @@ __global__ __launch_bounds__(THREADS) void conv_wino_bf16m_kernel(const Args a) 
       }
     };
     auto zero_of = [&](const Tile& t, int k, unsigned& zxi, unsigned& znu) {
-      zxi = 4;
-      znu = 4;
-      if (MODE == 1) {
-        const int blk = k / (nchunks >> 2);
-        if (blk >> 1) zxi = 3;
-        if (blk & 1) znu = 3;
-      } else if (MODE == 2) {
-        const int phase = t.item & 3;
-        if (phase >> 1) zxi = 0;
-        if (phase & 1) znu = 0;
+      zxi = zero_xi_of(MODE, nchunks, t.item & 3, k);
+      znu = zero_nu_of(MODE, nchunks, t.item & 3, k);
+    };
+    // The live row of the chunks c and c + 1 of pass B from one paired window (aim2): stored rows pty, pty + 1 of
+    // each half are the two patch rows the live row reads (xi 0 = r0 - r2, xi 3 = r1 - r3, as in commit); chunk c
+    // goes to the row's own V slots, chunk c + 1 to the dead row's (pair_commit_slot).
+    auto commit_pair = [&](int wbuf, int vb, const Tile& t, int c) {
+      const unsigned char* src = lds_raw + STAGEOFF + wbuf * WINB + (pty * WINW + 2 * ptx) * (CK * 4) + pq * 16;
+      unsigned char* dst = vmine + vb * VBUFB;
+      floatx4 ra[2][4], rb[2][4];
+#pragma unroll
+      for (int hf = 0; hf < 2; ++hf) {
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+          ra[hf][k] = *(const floatx4*)(src + hf * PAIRHALFB + k * (CK * 4));
+          rb[hf][k] = *(const floatx4*)(src + hf * PAIRHALFB + (WINW + k) * (CK * 4));
+        }
+      }
+#pragma unroll
+      for (int hf = 0; hf < 2; ++hf) {
+        unsigned zxi, znu;
+        zero_of(t, c + hf, zxi, znu);
+        floatx4 x[4];
+#pragma unroll
+        for (int k = 0; k < 4; ++k) x[k] = sub4(ra[hf][k], rb[hf][k]);
+        if (znu != 0) split_store(sub4(x[0], x[2]), dst + pair_commit_slot(MODE, hf, 0) * POSB);
+        split_store(x[1] + x[2], dst + pair_commit_slot(MODE, hf, 1) * POSB);
+        split_store(sub4(x[2], x[1]), dst + pair_commit_slot(MODE, hf, 2) * POSB);
+        if (znu != 3) split_store(sub4(x[1], x[3]), dst + pair_commit_slot(MODE, hf, 3) * POSB);
       }
     };
     auto next_ticket = [&]() { return (int)(atomicAdd(a.ticket, 1ULL) + gridDim.x); };
@@ -319,9 +373,11 @@ __global__ __launch_bounds__(THREADS) void conv_wino_bf16m_kernel(const Args a) 
     Tile cur = read_slot(0);
     int ticket_pre = a.ntiles;
     aim(am, cur);
-    dma(0, 0);
-    dma(1, 1);
-    dma(2, 2);
+    const bool pair_on = PAIR && a.pair_b != 0;
+    if (pair_on && pfirst_of(cur) < nchunks) aim2(cur);
+    dma(0, 0, am.off);
+    dma(1, 1, am.off);
+    dma(2, 2, am.off);
     if (ht == 0 && read_slot(1).item < a.ntiles) ticket_pre = next_ticket();
     wait_all_but_newest(2);
     __syncthreads();  // P1: the window of chunk 0 has landed (every helper wave has waited for its pieces)
@@ -338,31 +394,45 @@ __global__ __launch_bounds__(THREADS) void conv_wino_bf16m_kernel(const Args a) 
       const Tile nxt = read_slot(s_nxt);
       const bool more = nxt.item < a.ntiles;
       tile_count++;
-      // One phase (chunk-pass sg of this tile; targets past the last one belong to the next tile).  Every phase
-      // issues the same memory operations whatever the tile: with no next tile the aim points nowhere.
+      // chunk-passes of this tile: pass A, then pass B with its chunks paired from chunk pfirst on (L is even: the
+      // V buffers alternate through the tile boundary, and the loop below runs two phases per turn)
+      const int pfirst = pfirst_of(cur);
+      const int L = nchunks + pass_b_len(nchunks, pfirst);
+      // One phase (chunk-pass sg of this tile; targets past the last one belong to the next tile, whose first three
+      // chunk-passes are of its pass A).  Every phase issues the same memory operations whatever the tile: with no
+      // next tile the aim points nowhere; a paired window is as many loads as a whole one.
       auto phase = [&](int sg) {
-        MSTAMP(8, 4 * sg);
+        MSTAMPC(8, sg, 0, 4);
         {
           const int k3 = sg + 3;                                         // window of chunk-pass sg + 3
           if (k3 == L) {   // from here on every load is for the next tile
             if (more) aim(am, nxt); else aim_nowhere(am);
+            if (pair_on && more && pfirst_of(nxt) < nchunks) aim2(nxt);
           }
-          const int k3w = k3 < L ? k3 : k3 - L;
-          dma(wq >= 1 ? wq - 1 : 2, k3w < nchunks ? k3w : k3w - nchunks);   // buffer (wq + 2) % 3
+          const int wb3 = wq >= 1 ? wq - 1 : 2;                          // buffer (wq + 2) % 3
+          const int jb = k3 - nchunks;                                   // chunk-pass of pass B, if 0 <= jb, k3 < L
+          if (PAIR && k3 < L && jb >= pfirst)
+            dma(wb3, pass_b_chunk(jb, pfirst), off2);
+          else
+            dma(wb3, k3 < nchunks ? k3 : k3 < L ? jb : k3 - L, am.off);
         }
-        MSTAMP(8, 4 * sg + 1);
+        MSTAMPC(8, sg, 1, 4);
         {
           unsigned zxi, znu;                                             // target sg + 1
           const int tg = sg + 1;
           const bool passB = tg >= nchunks && tg < L;
-          if (tg < L) zero_of(cur, passB ? tg - nchunks : tg, zxi, znu); else zero_of(nxt, 0, zxi, znu);
-          commit(wq, tg & 1, passB, zxi, znu);
+          if (PAIR && passB && tg - nchunks >= pfirst) {
+            commit_pair(wq, tg & 1, cur, pass_b_chunk(tg - nchunks, pfirst));
+          } else {
+            if (tg < L) zero_of(cur, passB ? tg - nchunks : tg, zxi, znu); else zero_of(nxt, 0, zxi, znu);
+            commit(wq, tg & 1, passB, zxi, znu);
+          }
         }
         wq = wq == 2 ? 0 : wq + 1;
         wait_all_but_newest(1);                                          // window of chunk-pass sg + 2
-        MSTAMP(8, 4 * sg + 2);
+        MSTAMPC(8, sg, 2, 4);
         __syncthreads();  // B_sg
-        MSTAMP(8, 4 * sg + 3);
+        MSTAMPC(8, sg, 3, 4);
       };
       if (ht == 0 && more) post(s_wr, ticket_pre);
       for (int sg = 0; sg < L; sg += 2) {
@@ -384,8 +454,8 @@ __global__ __launch_bounds__(THREADS) void conv_wino_bf16m_kernel(const Args a) 
     }
 #if WBM_STAMP
     if (wave == 8) {
-      wbm_stamps[blockIdx.x * 256 + 128 + lane] = (long long)((unsigned*)(lds_raw + STAMPOFF))[128 + lane];
-      wbm_stamps[blockIdx.x * 256 + 192 + lane] = (long long)((unsigned*)(lds_raw + STAMPOFF))[192 + lane];
+      wbm_stamps[blockIdx.x * 384 + 128 + lane] = (long long)((unsigned*)(lds_raw + STAMPOFF))[128 + lane];
+      wbm_stamps[blockIdx.x * 384 + 192 + lane] = (long long)((unsigned*)(lds_raw + STAMPOFF))[192 + lane];
     }
 #endif
     if (ht == 0) {
@@ -477,6 +547,9 @@ __global__ __launch_bounds__(THREADS) void conv_wino_bf16m_kernel(const Args a) 
   int s_nxt = 1;
   while (cur.item < a.ntiles) {
     tile_count++;
+#if WBM_STAMP
+    if (lane == 0 && wave == 4 * PQ && tile_count == 3) ((unsigned*)(lds_raw + STAMPOFF))[(PQ ? 256 : 0) + 127] = (unsigned)cur.item;
+#endif
     const Tile nxt = read_slot(s_nxt);
     const unsigned soff_phase_nxt = soff_item(nxt.item < a.ntiles ? nxt : cur);
     unsigned tzero_xi = 4, tzero_nu = 4;   // MODE 2: the phase's zero row / column, for the whole tile
@@ -490,12 +563,11 @@ __global__ __launch_bounds__(THREADS) void conv_wino_bf16m_kernel(const Args a) 
       constexpr int PASS = decltype(pass_tag)::value;
       constexpr bool FIRST = decltype(first_tag)::value;
       const bool last = chunk + 1 == nchunks;
-      MSTAMP(0, 3 * (PASS * nchunks + chunk));
+      MSTAMPC(4 * PQ, PASS * nchunks + chunk, 0, 3);
       unsigned zero_xi = tzero_xi, zero_nu = tzero_nu;
       if (MODE == 1) {
-        const int blk = chunk / (nchunks >> 2);
-        zero_xi = (blk >> 1) ? 3 : 4;
-        zero_nu = (blk & 1) ? 3 : 4;
+        zero_xi = zero_xi_of(MODE, nchunks, 0, chunk);
+        zero_nu = zero_nu_of(MODE, nchunks, 0, chunk);
       }
       auto is_zero = [&](int s) {
         const int g = gpos<MODE, PASS, PQ>(s);
@@ -540,9 +612,54 @@ __global__ __launch_bounds__(THREADS) void conv_wino_bf16m_kernel(const Args a) 
           if (f < 4 ? !(ZSKIP && is_zero(f)) : !last) fetch(Bq[s % RING], so);
         }
       }
-      MSTAMP(0, 3 * (PASS * nchunks + chunk) + 1);
+      MSTAMPC(4 * PQ, PASS * nchunks + chunk, 1, 3);
       __syncthreads();  // B_sigma
-      MSTAMP(0, 3 * (PASS * nchunks + chunk) + 2);
+      MSTAMPC(4 * PQ, PASS * nchunks + chunk, 2, 3);
+    };
+    // One paired chunk-pass of pass B (chunk-pass j: the chunks chunk, chunk + 1), for the wave half that owns the
+    // live row: eight steps into the four positions of the row - chunk's four, then those of chunk + 1, whose V
+    // lies in the dead row's slots (conv_wino_pair.h).  The ring runs on through both chunks and into the next pair.
+    auto pair_body = [&](int j, int chunk) {
+      const bool last = chunk + 2 == nchunks;
+      MSTAMPC(4 * PQ, nchunks + j, 0, 3);
+      auto is_zero = [&](int s) {   // the owner's row is live: the chunk's zero column only
+        return (unsigned)(pair_gpos<MODE, PQ>(s) & 3) == zero_nu_of(MODE, nchunks, cur.item & 3, chunk + pair_half(s));
+      };
+      const unsigned char* vb = lds_raw + (j & 1) * VBUFB + aread;
+      auto vaddr = [&](int sub, int q) {   // sub = 2*s + m
+        return vb + pair_vslot<MODE, PQ>(sub >> 1) * POSB + (sub & 1) * (32 * ROWB) + q * PLANEB;
+      };
+      bf16x8 Aq[P];
+#pragma unroll
+      for (int q = 0; q < P; ++q) Aq[q] = *(const bf16x8*)vaddr(0, q);
+#pragma unroll
+      for (int s = 0; s < 8; ++s) {
+        const bool live = !is_zero(s);  // wave-uniform
+#pragma unroll
+        for (int m = 0; m < 2; ++m) {
+          const int sub = 2 * s + m, ai = 2 * pair_acc(s) + m;
+          if (live) {
+            floatx16 c = acc[ai];
+            c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(Aq[0], Bq[s % RING][1], c, 0, 0, 0);
+            c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(Aq[1], Bq[s % RING][0], c, 0, 0, 0);
+            c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(Aq[0], Bq[s % RING][0], c, 0, 0, 0);
+            acc[ai] = c;
+          }
+          if (sub + 1 < 16) {
+#pragma unroll
+            for (int q = 0; q < P; ++q) Aq[q] = *(const bf16x8*)vaddr(sub + 1, q);
+          }
+        }
+        {
+          const int f = s + RING;   // steps 8, 9: the first two of the next pair
+          const unsigned so = soff_phase + (unsigned)pair_gpos<MODE, PQ>(f & 7) * pos_b +
+                              (unsigned)(chunk + (f < 8 ? pair_half(f) : 2)) * chunk_b;
+          if (f < 8 ? !is_zero(f) : !last) fetch(Bq[s % RING], so);
+        }
+      }
+      MSTAMPC(4 * PQ, nchunks + j, 1, 3);
+      __syncthreads();  // B_sigma
+      MSTAMPC(4 * PQ, nchunks + j, 2, 3);
     };
 
     // ---------------------------------- pass A ------------------------------------------------
@@ -570,9 +687,9 @@ __global__ __launch_bounds__(THREADS) void conv_wino_bf16m_kernel(const Args a) 
       for (int m = 0; m < 2; ++m) {
         xwrite(xa_mine, c0[m]);
         xwrite(xb_mine, c1[m]);
-        MSTAMP(0, 122 + 2 * m);
+        MSTAMP(4 * PQ, 122 + 2 * m);
         __syncthreads();  // M1 / M3
-        MSTAMP(0, 123 + 2 * m);
+        MSTAMP(4 * PQ, 123 + 2 * m);
         const floatx16 g0 = xread(xa_part), g1 = xread(xb_part);
         if (PQ == 0) {
           acc[2 * t0 + m] = c0[m] + g0;
@@ -588,19 +705,33 @@ __global__ __launch_bounds__(THREADS) void conv_wino_bf16m_kernel(const Args a) 
         }
         __syncthreads();  // M2 / M4: both regions have been read (M4: V buffer 1 belongs to the helpers again)
       }
-      MSTAMP(0, 126);
+      MSTAMP(4 * PQ, 126);
     }
 #pragma unroll
     for (int f = 0; f < RING; ++f) fetch(Bq[f], soff_phase + (unsigned)gpos<MODE, 1, PQ>(f) * pos_b);
     // ---------------------------------- pass B ------------------------------------------------
-    for (int chunk = 0; chunk < nchunks; ++chunk) chunk_body(std::integral_constant<int, 1>{}, std::false_type{}, chunk);
+    // single chunks up to pfirst, then pairs: the wave half that owns the dead row only joins their barriers
+    const int pfirst = pfirst_of(cur);
+    for (int chunk = 0; chunk < pfirst; ++chunk) chunk_body(std::integral_constant<int, 1>{}, std::false_type{}, chunk);
+    if constexpr (PAIR) {
+      for (int j = pfirst; j < pass_b_len(nchunks, pfirst); ++j) {
+        if constexpr (PQ == pair_owner(MODE)) {
+          pair_body(j, pass_b_chunk(j, pfirst));
+        } else {
+          MSTAMPC(4 * PQ, nchunks + j, 0, 3);
+          MSTAMPC(4 * PQ, nchunks + j, 1, 3);
+          __syncthreads();  // B_sigma
+          MSTAMPC(4 * PQ, nchunks + j, 2, 3);
+        }
+      }
+    }
     soff_phase = soff_phase_nxt;
 
     // ---- final fold: output row i = PQ from the wave's own row; bias + activation; stores --------
     // Y[0][0] = M00 + M01 + M02, Y[0][1] = M01 - M02 - M03 (row 0); Y[1][j] = -(the same of row 3).  No exchange and
     // no barrier: every wave transposes its outputs through its own 4 KB of region A (lane = channel -> lane = channel
     // quad of a tile) and stores 16 bytes per lane, 8 pixels x 128 bytes per instruction.
-    MSTAMP(0, 120);
+    MSTAMP(4 * PQ, 120);
     {
       const int phase = cur.item & (a.nphase - 1);
       const int ppy = phase >> 1, ppx = phase & 1;
@@ -674,16 +805,17 @@ __global__ __launch_bounds__(THREADS) void conv_wino_bf16m_kernel(const Args a) 
         emit_act(m, 1, PQ == 0 ? y1 : -y1);
       }
     }
-    MSTAMP(0, 121);
+    MSTAMP(4 * PQ, 121);
 #pragma unroll
     for (int f = 0; f < RING; ++f) fetch(Bq[f], soff_phase + (unsigned)gpos<MODE, 0, PQ>(f) * pos_b);
     cur = nxt;
     s_nxt = s_nxt == 2 ? 0 : s_nxt + 1;
   }
 #if WBM_STAMP
-  if (wave == 0) {
-    wbm_stamps[blockIdx.x * 256 + lane] = (long long)((unsigned*)(lds_raw + STAMPOFF))[lane];
-    wbm_stamps[blockIdx.x * 256 + 64 + lane] = (long long)((unsigned*)(lds_raw + STAMPOFF))[64 + lane];
+  if (wave == 0 || wave == 4) {   // slot 127: the item of the stamped tile
+    unsigned* const st = (unsigned*)(lds_raw + STAMPOFF) + (wave == 0 ? 0 : 256);
+    wbm_stamps[blockIdx.x * 384 + (wave == 0 ? 0 : 256) + lane] = (long long)st[lane];
+    wbm_stamps[blockIdx.x * 384 + (wave == 0 ? 0 : 256) + 64 + lane] = (long long)st[64 + lane];
   }
 #endif
   };
@@ -718,6 +850,80 @@ extern "C" int dsic_wino_bf16_m64(int H, int W, int Cin, int nphase) {
   return (H / 16) * (W / 16) * nphase >= min_items;
 }
 
+// Pairing of the half-empty pass-B chunks (conv_wino_pair.h): on unless DSIC_WINO_PAIR=0 (read once; A/B runs), or
+// switched by dsic_wino_pair_chunks (tests compare the two schedules in one process).
+static int wbm_pair_mode() {
+  static int mode = -1;
+  if (mode < 0) {
+    const char* e = getenv("DSIC_WINO_PAIR");
+    mode = e ? (atoi(e) != 0) : 1;
+  }
+  return mode;
+}
+static int wbm_pair_override = -1;
+extern "C" int dsic_wino_pair_chunks(int on) {
+  const int was = wbm_pair_override >= 0 ? wbm_pair_override : wbm_pair_mode();
+  if (on >= 0) wbm_pair_override = on != 0;
+  return was;
+}
+
+// Host restatement of a tile's schedule from the same tables the kernel reads: the (chunk, position xi*4 + nu)
+// pairs that accumulator acc (0..3) of wave half pq receives in pass B, in order, for the paired or the unpaired
+// schedule.  out: up to cap pairs of ints; returns their number (-1: bad arguments).
+namespace {
+template <int MODE, int PQ>
+int pass_b_sequence(int nchunks, int phase, bool paired, int acc, int* out, int cap) {
+  using namespace dsic::wbm;
+  int n = 0;
+  auto put = [&](int chunk, int g) {
+    if (n < cap) {
+      out[2 * n] = chunk;
+      out[2 * n + 1] = g;
+    }
+    ++n;
+  };
+  auto live = [&](int chunk, int g) {
+    return (unsigned)(g >> 2) != zero_xi_of(MODE, nchunks, phase, chunk) && (unsigned)(g & 3) != zero_nu_of(MODE, nchunks, phase, chunk);
+  };
+  const int pfirst = MODE == 0 ? nchunks : pair_first(MODE, nchunks, phase, paired);
+  for (int j = 0; j < pass_b_len(nchunks, pfirst); ++j) {
+    const int c = pass_b_chunk(j, pfirst);
+    if (j < pfirst) {
+      for (int s = 0; s < 4; ++s)
+        if (s == acc && live(c, gpos<MODE, 1, PQ>(s))) put(c, gpos<MODE, 1, PQ>(s));
+    } else if (PQ == pair_owner(MODE)) {
+      for (int s = 0; s < 8; ++s) {
+        const int g = pair_gpos<MODE, PQ>(s), cc = c + pair_half(s);
+        // the V slot the MFMA wave reads is the one the helpers commit this (chunk, position) to
+        if (pair_vslot<MODE, PQ>(s) != pair_commit_slot(MODE, pair_half(s), g & 3) || (g >> 2) != pair_live_xi(MODE)) return -2;
+        if (pair_acc(s) == acc && live(cc, g)) put(cc, g);
+      }
+    } else {
+      // the other half issues nothing in a paired chunk-pass: its row must be dead in both chunks
+      for (int h = 0; h < 2; ++h)
+        for (int s = 0; s < 4; ++s)
+          if (live(c + h, gpos<MODE, 1, PQ>(s))) return -3;
+    }
+  }
+  return n;
+}
+}  // namespace
+extern "C" int dsic_wino_pair_schedule(int mode, int nchunks, int phase, int paired, int pq, int acc, int* out, int cap) {
+  if (mode < 0 || mode > 2 || nchunks < 4 || nchunks % 2 || phase < 0 || phase > 3 || pq < 0 || pq > 1 || acc < 0 || acc > 3 ||
+      (cap > 0 && !out))
+    return -1;
+#define WBM_SEQ(M, Q) pass_b_sequence<M, Q>(nchunks, phase, paired != 0, acc, out, cap)
+  switch (mode * 2 + pq) {
+    case 0: return WBM_SEQ(0, 0);
+    case 1: return WBM_SEQ(0, 1);
+    case 2: return WBM_SEQ(1, 0);
+    case 3: return WBM_SEQ(1, 1);
+    case 4: return WBM_SEQ(2, 0);
+    default: return WBM_SEQ(2, 1);
+  }
+#undef WBM_SEQ
+}
+
 int dsic_wbm_launch(wb::Args& a, hipStream_t st) {
   a.tiles_x = a.W / 16;
   a.tiles_y = a.H / 16;
@@ -727,6 +933,7 @@ int dsic_wbm_launch(wb::Args& a, hipStream_t st) {
   if (a.ostride <= 0) a.ostride = a.Cout;
   a.ntiles = (int)nt;
   a.ksplit = 1;
+  a.pair_b = dsic_wino_pair_chunks(-1);
   a.nt_out = (int64_t)a.B * a.H * a.W * a.Cout * 4 * (a.nphase == 4 ? 4 : 1) > (300ll << 20);
   int dev = 0;
   if (hipGetDevice(&dev) != hipSuccess) dev = 0;
@@ -773,7 +980,7 @@ int dsic_wbm_launch(wb::Args& a, hipStream_t st) {
 }
 
 #if WBM_STAMP
-extern "C" int dsic_debug_wbm_stamps(long long* host_out) {
-  return hipMemcpyFromSymbol(host_out, HIP_SYMBOL(wbm::wbm_stamps), sizeof(long long) * 256 * 256) == hipSuccess ? 0 : 2;
+extern "C" int dsic_debug_wbm_stamps(long long* host_out) {   // [256 workgroups][384]
+  return hipMemcpyFromSymbol(host_out, HIP_SYMBOL(wbm::wbm_stamps), sizeof(long long) * 256 * 384) == hipSuccess ? 0 : 2;
 }
 #endif

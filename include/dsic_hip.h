@@ -183,6 +183,17 @@ int dsic_wino_bf16_ksplit(int H, int W, int Cin);
  * two-pass kernel (csrc/conv_wino_bf16m.hip: H and W multiples of 16, at least 4 work items per image; nphase = 4
  * for ConvTranspose2d, 1 otherwise) - a function of the layer geometry only, like the split-K rule. */
 int dsic_wino_bf16_m64(int H, int W, int Cin, int nphase);
+/* The 64-tile kernel runs two pass-B chunks whose Winograd row xi = 3 (5x5/s2 over space-to-depth) or xi = 0
+ * (ConvTranspose2d phases 2, 3) is structurally zero as one chunk-pass; results are bit-identical either way.
+ * dsic_wino_pair_chunks(on): 1 / 0 switches that on / off for later launches (default on; DSIC_WINO_PAIR=0 in the
+ * environment: off), a negative value only asks; returns the previous setting.
+ * dsic_wino_pair_schedule: host restatement of a tile's pass B from the kernel's own tables - the (chunk, position
+ * xi*4 + nu) pairs that accumulator acc (0..3) of wave half pq (0, 1) receives, in order, in the paired (1) or
+ * unpaired (0) schedule of mode 0 (3x3) / 1 (space-to-depth) / 2 (ConvTranspose2d item of `phase`) with nchunks =
+ * Cin/16; writes up to cap pairs of ints to out and returns their number (negative: bad arguments or a table
+ * that contradicts itself). */
+int dsic_wino_pair_chunks(int on);
+int dsic_wino_pair_schedule(int mode, int nchunks, int phase, int paired, int pq, int acc, int* out, int cap);
 int dsic_conv3x3_wino_bf16_splitk_nhwc(const float* in, const void* u_planes,
                                        const float* bias, const float* beta,
                                        const float* gamma, float* out, int B, int H, int W,

@@ -1,8 +1,14 @@
 #!/usr/bin/env python3
-"""Reads the in-kernel cycle stamps of a -DWBM_STAMP=1 build of conv_wino_bf16m.hip (diagnostic; third tile of every
-workgroup, medians over workgroups).  LAYER=3x3 (default, 8 chunks per pass) | s2 (32) | convT (8).  CM=1: the
-input and the output chunk-major (ops.LAYOUT_CM16) instead of NHWC.  DSIC_LIB_ROOT: the repository tree whose package
-(and library) to load."""
+"""Reads the in-kernel cycle stamps of a -DWBM_STAMP=1 [-DWBM_STAMP_C0=<first chunk-pass>] build of
+conv_wino_bf16m.hip (diagnostic; third tile of every workgroup, medians over workgroups): the MFMA waves 0 (PQ 0)
+and 4 (PQ 1) and helper wave 8, for the 32 chunk-passes from C0 on.
+
+  LAYER=3x3 (default, 8 chunks per pass) | s2 (5x5/s2 over space-to-depth, Cin = 512: 32 chunks) | convT (8)
+  CM=1     input and output chunk-major (ops.LAYOUT_CM16) instead of NHWC
+  PAIR=0   the unpaired schedule of pass B (dsic_wino_pair_chunks); default: the library's setting
+  C0=<n>   the WBM_STAMP_C0 the library was built with (labels only)
+  PHASES=23 | 01   convT: keep the workgroups whose stamped item has one of these phases (default 23: row xi = 0 dead)
+  DSIC_LIB_ROOT: the repository tree whose package (and library) to load; DSIC_LIB: the stamped library."""
 import ctypes, os, sys
 sys.path.insert(0, os.environ.get("DSIC_LIB_ROOT") or os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np, torch
@@ -10,6 +16,12 @@ from dsic_amd import ops, lib
 B, h = 64, 128
 layer = os.environ.get("LAYER", "3x3")
 cm = os.environ.get("CM", "0") == "1"
+c0 = int(os.environ.get("C0", "0"))
+phases = {int(c) for c in os.environ.get("PHASES", "23")}
+L = lib.load()
+if "PAIR" in os.environ:
+    L.dsic_wino_pair_chunks(int(os.environ["PAIR"]))
+pair = bool(L.dsic_wino_pair_chunks(-1))
 kw = dict(cm_in=True, cm_out=True) if cm else {}
 cmx = (lambda t: ops.nhwc_to_cm16(t)) if cm else (lambda t: t)
 bias = torch.randn(128, device="cuda"); beta = torch.rand(128, device="cuda") + 0.5; gamma = torch.rand(128, device="cuda") * 0.2
@@ -29,24 +41,54 @@ for _ in range(3): run()
 torch.cuda.synchronize()
 e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
 e0.record(); run(); e1.record(); torch.cuda.synchronize()
-print(layer, "CM16" if cm else "NHWC", "kernel ms", e0.elapsed_time(e1))
-L = lib.load()
-buf = np.zeros(256 * 256, dtype=np.int64)
+print(f"{layer} {'CM16' if cm else 'NHWC'} {'paired' if pair else 'unpaired'} pass B, stamps from chunk-pass {c0}: kernel ms {e0.elapsed_time(e1):.3f} (stamped build: shares, not length)")
+buf = np.zeros(256 * 384, dtype=np.int64)
 L.dsic_debug_wbm_stamps.restype = ctypes.c_int
 assert L.dsic_debug_wbm_stamps(buf.ctypes.data_as(ctypes.c_void_p)) == 0
-s = buf.reshape(256, 256).astype(np.float64)
+s = buf.reshape(256, 384).astype(np.float64)
 s = s[s[:, 0] > 0]
-m, hlp = s[:, :128], s[:, 128:]
-d = lambda arr, a, b: np.median(arr[:, b] - arr[:, a])
-ns = min(2 * n, 38)
-print("MFMA wave 0:  chunk-pass: mfma-phase | barrier wait | gap       helper wave 8: stage | commit | barrier wait | issue+gap")
-for c in range(ns):
-    hl = f"{d(hlp, 4*c, 4*c+1):6.0f} | {d(hlp, 4*c+1, 4*c+2):6.0f} | {d(hlp, 4*c+2, 4*c+3):6.0f} | {d(hlp, 4*c+3, 4*c+4) if 4*c+4 < 128 and c + 1 < 2 * n else 0:6.0f}" if 4 * c + 3 < 128 else ""
-    gap = d(m, 3*c+2, 3*c+3) if c + 1 < ns and c + 1 != n else 0
-    print(f"  {c:2d}{'B' if c >= n else 'A'}: {d(m, 3*c, 3*c+1):7.0f} | {d(m, 3*c+1, 3*c+2):7.0f} | {gap:7.0f}        {hl}")
-if 2 * n <= 38:
-    print(f"mid fold: compute+write m0 {d(m, 3*(n-1)+2, 122):6.0f} | M1 wait {d(m, 122, 123):6.0f} | read+init+M2+write m1 {d(m, 123, 124):6.0f} | M3 wait {d(m, 124, 125):6.0f} | read+init+M4 {d(m, 125, 126):6.0f}")
-    print(f"final fold (no barrier): {d(m, 120, 121):6.0f}")
-    print(f"tile: {d(m, 0, 121):.0f} cycles; chunk-pass period (pass A, MFMA wave): {d(m, 0, 3*(n-1)) / (n-1):.0f}; pass B: {d(m, 3*n, 3*(2*n-1)) / (n-1):.0f}")
-else:
-    print(f"chunk-pass period (pass A, first {ns} chunk-passes): {d(m, 0, 3*(ns-1)) / (ns-1):.0f}")
+if layer == "convT":
+    s = s[np.isin(s[:, 127].astype(np.int64) & 3, list(phases))]
+    print(f"  items of phase {sorted(phases)}: {len(s)} workgroups")
+# the tile's schedule (conv_wino_pair.h): pass B runs single chunks up to pfirst, then pairs
+dead = layer == "s2" or (layer == "convT" and min(phases) >= 2)
+pfirst = n
+if pair and layer == "s2" and n % 8 == 0: pfirst = n // 2
+if pair and layer == "convT" and min(phases) >= 2 and n % 4 == 0: pfirst = 0
+nb = pfirst + (n - pfirst) // 2
+total = n + nb
+def label(sig):
+    if sig < n: return f"A {sig:2d}     "
+    j = sig - n
+    if j < pfirst:
+        half = dead and (layer == "convT" or j >= n // 2)
+        return f"B {j:2d}{' half' if half else '     '}"
+    c = pfirst + 2 * (j - pfirst)
+    return f"B {c:2d}+{c + 1:<2d} "
+m0, hlp, m4 = s[:, :128], s[:, 128:256], s[:, 256:384]
+d = lambda arr, a, b: np.median((arr[:, b] - arr[:, a]) % 2.0 ** 32)
+print("chunk-pass    : PQ 0 wave 0: mfma-phase | barrier wait | gap    PQ 1 wave 4: mfma-phase | barrier wait | gap    "
+      "helper wave 8: stage | commit | barrier wait | gap    period")
+per = {}
+for sig in range(c0, min(total, c0 + 32)):
+    i = sig - c0
+    nxt = sig + 1 < min(total, c0 + 32) and sig + 1 != n   # the mid fold lies between chunk-pass n - 1 and n
+    row = f"  {sig:2d} {label(sig)}:"
+    for arr in (m0, m4):
+        row += f" {d(arr, 3*i, 3*i+1):7.0f} | {d(arr, 3*i+1, 3*i+2):7.0f} | {d(arr, 3*i+2, 3*i+3) if nxt else 0:7.0f}      "
+    row += f" {d(hlp, 4*i, 4*i+1):6.0f} | {d(hlp, 4*i+1, 4*i+2):6.0f} | {d(hlp, 4*i+2, 4*i+3):6.0f} | {d(hlp, 4*i+3, 4*i+4) if nxt else 0:6.0f}"
+    if nxt:
+        if sig: per[sig] = d(hlp, 4 * i, 4 * i + 4)   # chunk-pass 0 waits for the MFMA waves' final fold of the tile before
+        row += f"   {d(hlp, 4 * i, 4 * i + 4):6.0f}"
+    print(row)
+def mean_period(sel):
+    v = [per[k] for k in per if sel(k)]
+    return f"{np.mean(v):.0f} ({len(v)})" if v else "-"
+print(f"mean period (helper wave, chunk-passes stamped): pass A {mean_period(lambda k: k < n)}; "
+      f"pass B full {mean_period(lambda k: k >= n and 'half' not in label(k) and '+' not in label(k))}; "
+      f"pass B half-empty, single {mean_period(lambda k: 'half' in label(k))}; pass B paired {mean_period(lambda k: '+' in label(k))}")
+if c0 + 32 >= total:
+    print(f"final fold (no barrier): PQ 0 {d(m0, 120, 121):6.0f}  PQ 1 {d(m4, 120, 121):6.0f}")
+if c0 <= n - 1 < c0 + 32:
+    i = n - 1 - c0
+    print(f"mid fold (PQ 0): compute+write m0 {d(m0, 3*i+2, 122):6.0f} | M1 wait {d(m0, 122, 123):6.0f} | read+init+M2+write m1 {d(m0, 123, 124):6.0f} | M3 wait {d(m0, 124, 125):6.0f} | read+init+M4 {d(m0, 125, 126):6.0f}")
