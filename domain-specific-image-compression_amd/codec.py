@@ -15,7 +15,13 @@ is DSIC3 with that K.  Version 1 is written whenever K = 1.
 kind 0 = uint8 [H,W,C] (PIL / numpy layout), 1 = float32 [C,H,W] in [0,1].  Tiling (tile_grid): the image is
 reflect-padded bottom/right to multiples of 16 inside the gather kernel; the last row / column of tiles shifts inward
 (overlap, no extra padding) and every pixel is written back by the one tile that owns it.  Tiles are coded
-independently, as the reference's patch-trained model sees them; seams are not blended.
+independently, as the reference's patch-trained model sees them; at the default overlap = 0 seams are not blended.
+
+overlap = O > 0 (a multiple of 16, at most half a tile side) is stream version 3: the version-1 head, then segments
+u32 (1 allowed), then overlap u32.  Neighbouring tiles then share O pixels (tile_grid: stride t - O) and their
+reconstructions are cross-faded over them with linear ramps that sum to 1; the blend is a fixed float32 fold over a
+pixel's contributing tiles in ascending tile number (dsic_tile_blend_window_f32), so a window decodes to the same
+bits however its tiles are batched.
 
 Because tiles are independent and the DSIC2 heads hold every string's length, any window of a stream can be decoded
 from only the tiles that own its pixels: stream_index finds their bytes from the heads alone, decompress_region decodes
@@ -24,6 +30,7 @@ decompress_image is the same decode (_decode_window) of the window (0, 0, H, W),
 """
 from __future__ import annotations
 
+import operator
 import struct
 
 import torch
@@ -36,6 +43,8 @@ from .ops import _p, _stream
 MAGIC = b"DSICI\x00"
 VERSION = 1
 VERSION_SEG = 2            # version 1 + the segments word; written only for segments > 1
+VERSION_OV = 3             # version 1 + the segments word + the overlap word; written only for overlap > 0
+BLEND_IDS = 64             # tiles per dsic_tile_blend_window_f32 call
 KIND_U8_HWC, KIND_F32_CHW = 0, 1
 _HEAD = struct.Struct("<6sHI6I4I2I")
 _SEGS = struct.Struct("<I")
@@ -46,13 +55,37 @@ def _ceil16(n):
     return (n + 15) // 16 * 16
 
 
-def _grid(H, W, th, tw):
+def _axis(Lp, t, O):
+    """One axis of the grid: (stride, origins, nominal ranges, supports)."""
+    if Lp <= t:
+        return t, [0], [(0, Lp)], [(0, Lp)]
+    s = t - O
+    n = -(-(Lp - O) // s)
+    return (s, [min(i * s, Lp - t) for i in range(n)], [(i * s, min((i + 1) * s, Lp)) if i < n - 1 else (i * s, Lp)
+                                                        for i in range(n)],
+            [(i * s, (i + 1) * s + O) if i < n - 1 else (i * s, Lp) for i in range(n)])
+
+
+def _grid(H, W, th, tw, O=0):
     Hp, Wp = _ceil16(H), _ceil16(W)
-    ny, nx = -(-Hp // th), -(-Wp // tw)
+    sy, ys, own_y, sup_y = _axis(Hp, th, O)
+    sx, xs, own_x, sup_x = _axis(Wp, tw, O)
+    ny, nx = len(ys), len(xs)
     return {"H": H, "W": W, "Hp": Hp, "Wp": Wp, "th": th, "tw": tw, "ny": ny, "nx": nx, "n": ny * nx,
-            "ys": [min(i * th, Hp - th) for i in range(ny)], "xs": [min(j * tw, Wp - tw) for j in range(nx)],
-            "own_y": [(i * th, min((i + 1) * th, Hp)) for i in range(ny)],
-            "own_x": [(j * tw, min((j + 1) * tw, Wp)) for j in range(nx)]}
+            "ys": ys, "xs": xs, "own_y": own_y, "own_x": own_x,
+            "overlap": O, "sy": sy, "sx": sx, "sup_y": sup_y, "sup_x": sup_x}
+
+
+def _check_overlap(O, th, tw, what):
+    """overlap as a stream and the kernels take it: 0, or a multiple of 16 of at most half the smaller tile side."""
+    try:
+        O = operator.index(O)
+    except TypeError:
+        raise ValueError(f"{what}: overlap={O!r} is not an integer") from None
+    if O < 0 or O % 16 or 2 * O > min(th, tw):
+        raise ValueError(f"{what}: overlap={O!r} must be 0 or a multiple of 16 from 16 to half the smaller side of "
+                         f"the {th}x{tw} tiles")
+    return O
 
 
 def _check_image(H, W):
@@ -65,16 +98,25 @@ def _check_image(H, W):
         raise ValueError(f"image {H}x{W}: the reflect padding to {Hp}x{Wp} must be smaller than the image")
 
 
-def tile_grid(H, W, tile=256) -> dict:
+def tile_grid(H, W, tile=256, overlap=0) -> dict:
     """Tile geometry of an H x W image (pure Python).  Hp = ceil16(H), th = min(tile, Hp); tile row origins 0, th, 2th,
     ... with the last clamped to Hp - th; tile row i owns padded rows [i*th, min((i+1)*th, Hp)) (overlap rows belong
     to the earlier tile).  Columns likewise; tiles are numbered row-major.  Returns H, W, Hp, Wp, th, tw, ny, nx, n,
-    ys, xs (origins) and own_y, own_x (owned ranges)."""
+    ys, xs (origins) and own_y, own_x (owned ranges).
+
+    overlap = O (0, or a multiple of 16 with 16 <= O <= tile / 2): an axis of more than one tile has the stride
+    s = t - O, ceil((Lp - O) / s) tiles, nominal origins a(i) = i*s and real origins min(i*s, Lp - t) (only the last
+    shifts inward).  own_y / own_x are the nominal ranges [a(i), a(i+1)) (the last ends at Lp); sup_y / sup_x the
+    supports [a(i), a(i+1) + O) (the last ends at Lp), outside which the tile's blend weight is 0: it ramps up as
+    (2k+1)/(2O) over the first O positions of the support (i > 0), down as (2(O-1-k)+1)/(2O) over its last O
+    (i < n-1) and is 1 between, so the weights at a position sum to 1 and at most two tiles per axis contribute.
+    Also returns overlap, sy, sx (strides; t on an axis of one tile, which has no ramp)."""
     tile = int(tile)
     if tile % 16 or tile < 32:
         raise ValueError(f"tile={tile} must be a multiple of 16 and at least 32")
+    overlap = _check_overlap(overlap, tile, tile, "tile_grid")
     _check_image(H, W)
-    return _grid(H, W, min(tile, _ceil16(H)), min(tile, _ceil16(W)))
+    return _grid(H, W, min(tile, _ceil16(H)), min(tile, _ceil16(W)), overlap)
 
 
 def _model_shape(model):
@@ -84,13 +126,17 @@ def _model_shape(model):
 
 def pack_image_stream(header: dict, blobs) -> bytes:
     """header (the fields unpack_image_stream returns) + the DSIC2 containers -> the stream (pure Python).  A header
-    with "segments" = K > 1 writes version 2, whose containers are DSIC3 with that K."""
+    with "segments" = K > 1 writes version 2, whose containers are DSIC3 with that K; one with "overlap" = O > 0
+    writes version 3 (segments word, then overlap word), whose containers are DSIC2 for K = 1 and DSIC3 otherwise."""
     h = header
     K = entropy.check_segments(h.get("segments", 1), h["M"], "pack_image_stream")
-    head = _HEAD.pack(MAGIC, VERSION_SEG if K > 1 else VERSION, h["numerics"] & 0xFFFFFFFF, h["H"], h["W"], h["C"],
-                      h["kind"], h["th"], h["tw"], h["N"], h["M"], h["in_ch"], h["spatial_params"], h["batch"],
-                      len(blobs))
-    if K > 1:
+    O = _check_overlap(h.get("overlap", 0), h["th"], h["tw"], "pack_image_stream")
+    head = _HEAD.pack(MAGIC, VERSION_OV if O else (VERSION_SEG if K > 1 else VERSION), h["numerics"] & 0xFFFFFFFF,
+                      h["H"], h["W"], h["C"], h["kind"], h["th"], h["tw"], h["N"], h["M"], h["in_ch"],
+                      h["spatial_params"], h["batch"], len(blobs))
+    if O:
+        head += _SEGS.pack(K) + _SEGS.pack(O)
+    elif K > 1:
         head += _SEGS.pack(K)
     return b"".join([head] + [_LEN.pack(len(b)) + bytes(b) for b in blobs])
 
@@ -137,18 +183,26 @@ def _read_framing(src):
     keys = ("version", "numerics", "H", "W", "C", "kind", "th", "tw", "N", "M", "in_ch", "spatial_params", "batch",
             "batches")
     h = dict(zip(keys, f[1:]))
-    if h["version"] not in (VERSION, VERSION_SEG):
-        raise ValueError(f"DSICI stream version {h['version']}, this reader knows {VERSION} and {VERSION_SEG}")
-    off, h["segments"] = _HEAD.size, 1
-    if h["version"] == VERSION_SEG:
-        word = src.read_at(off, _SEGS.size)
-        if len(word) < _SEGS.size:
+    if h["version"] not in (VERSION, VERSION_SEG, VERSION_OV):
+        raise ValueError(f"DSICI stream version {h['version']}, this reader knows {VERSION}, {VERSION_SEG} and "
+                         f"{VERSION_OV}")
+    off, h["segments"], h["overlap"] = _HEAD.size, 1, 0
+    if h["version"] in (VERSION_SEG, VERSION_OV):
+        words = 2 if h["version"] == VERSION_OV else 1
+        word = src.read_at(off, words * _SEGS.size)
+        if len(word) < words * _SEGS.size:
             raise ValueError("truncated DSICI stream")
-        (h["segments"],) = _SEGS.unpack(word)
-        off += _SEGS.size
-        if h["segments"] not in entropy.SEGMENTS[1:] or h["M"] % h["segments"]:
-            raise ValueError(f"DSICI stream: segments={h['segments']} is not one of {entropy.SEGMENTS[1:]} dividing "
+        (h["segments"],) = _SEGS.unpack_from(word, 0)
+        off += words * _SEGS.size
+        allowed = entropy.SEGMENTS[1:] if h["version"] == VERSION_SEG else entropy.SEGMENTS
+        if h["segments"] not in allowed or h["M"] % h["segments"]:
+            raise ValueError(f"DSICI stream: segments={h['segments']} is not one of {allowed} dividing "
                              f"M={h['M']}")
+        if h["version"] == VERSION_OV:
+            (h["overlap"],) = _SEGS.unpack_from(word, _SEGS.size)
+            if h["overlap"] == 0:
+                raise ValueError("DSICI stream: version 3 with overlap=0")
+            _check_overlap(h["overlap"], h["th"], h["tw"], "DSICI stream")
     frames = []
     for _ in range(h["batches"]):
         if off + _LEN.size > src.size:
@@ -166,7 +220,7 @@ def _read_framing(src):
 
 def unpack_image_stream(stream) -> dict:
     """stream -> header fields (version, numerics, H, W, C, kind, th, tw, N, M, in_ch, spatial_params, batch,
-    batches, segments: 1 for a version-1 stream) and "blobs", the list of inner DSIC2 containers (pure Python).  ValueError on a wrong magic, a truncated
+    batches, segments: 1 for a version-1 stream, overlap: 0 for versions 1 and 2) and "blobs", the list of inner DSIC2 containers (pure Python).  ValueError on a wrong magic, a truncated
     stream or trailing bytes."""
     s = bytes(stream)
     h, frames = _read_framing(_Source(s))
@@ -184,20 +238,29 @@ def _gather(img, kind, g, C, first, n):
     L = _lib.load()
     if kind == KIND_U8_HWC:
         tiles = torch.empty((n, g["th"], g["tw"], C), dtype=torch.uint8, device=img.device)
-        fn, what = L.dsic_tile_gather_u8, "tile_gather_u8"
+        what = "tile_gather_u8"
     else:
         tiles = torch.empty((n, C, g["th"], g["tw"]), dtype=torch.float32, device=img.device)
-        fn, what = L.dsic_tile_gather_f32, "tile_gather_f32"
-    _lib.check(fn(_p(img), _p(tiles), g["H"], g["W"], C, g["th"], g["tw"], first, n, _stream()), what)
+        what = "tile_gather_f32"
+    if g["overlap"]:
+        what += "_ov"
+        status = getattr(L, "dsic_" + what)(_p(img), _p(tiles), g["H"], g["W"], C, g["th"], g["tw"], g["overlap"],
+                                            first, n, _stream())
+    else:
+        status = getattr(L, "dsic_" + what)(_p(img), _p(tiles), g["H"], g["W"], C, g["th"], g["tw"], first, n,
+                                            _stream())
+    _lib.check(status, what)
     return tiles
 
 
 @torch.no_grad()
-def compress_image(model, img, tile=256, batch=64, tail=10, segments=1) -> bytes:
+def compress_image(model, img, tile=256, batch=64, tail=10, segments=1, overlap=0) -> bytes:
     """img: uint8 [H,W,C] or float32 [C,H,W] in [0,1], on the CPU or the GPU -> one DSICI stream.  The image is
     uploaded once; each batch of `batch` tiles is gathered on the device (reflect padding included) and becomes one
     DSIC2 container.  segments = K > 1 (1, 2, 4, 8 or 16, dividing M): every tile's y string is K independent strings
-    (DSIC3 containers, stream version 2), which the decoders read on K waves per tile; the decoded image is the same."""
+    (DSIC3 containers, stream version 2), which the decoders read on K waves per tile; the decoded image is the same.
+    overlap = O > 0 (a multiple of 16, at most half a tile side): tiles share O pixels with their neighbours
+    (tile_grid) and the decoders cross-fade them over that band (stream version 3); 0 writes today's streams."""
     dev = next(model.parameters()).device
     if img.dim() != 3:
         raise ValueError(f"compress_image: expected uint8 [H,W,C] or float32 [C,H,W], got {tuple(img.shape)}")
@@ -214,14 +277,15 @@ def compress_image(model, img, tile=256, batch=64, tail=10, segments=1) -> bytes
     batch = int(batch)
     if batch < 1:
         raise ValueError(f"compress_image: batch={batch}")
-    g = tile_grid(H, W, tile)
+    g = tile_grid(H, W, tile, overlap)
+    overlap = _check_overlap(overlap, g["th"], g["tw"], "compress_image")
     x = img.to(dev).contiguous()
     blobs = []
     for first in range(0, g["n"], batch):
         tiles = _gather(x, kind, g, C, first, min(batch, g["n"] - first))
         blobs.append(entropy.compress_to_container(model, tiles, tail, segments=segments))
     header = {"numerics": entropy.numerics_tag(), "H": H, "W": W, "C": C, "kind": kind, "th": g["th"], "tw": g["tw"],
-              "N": N, "M": M, "in_ch": in_ch, "spatial_params": spatial, "batch": batch, "segments": segments}
+              "N": N, "M": M, "in_ch": in_ch, "spatial_params": spatial, "batch": batch, "segments": segments, "overlap": overlap}
     return pack_image_stream(header, blobs)
 
 
@@ -245,7 +309,7 @@ def _stream_grid(h):
     _check_image(H, W)
     if th % 16 or tw % 16 or th < 32 or tw < 32 or th > _ceil16(H) or tw > _ceil16(W):
         raise ValueError(f"DSICI stream: tile {th}x{tw} does not fit a {H}x{W} image")
-    g = _grid(H, W, th, tw)
+    g = _grid(H, W, th, tw, _check_overlap(h.get("overlap", 0), th, tw, "DSICI stream"))
     if h["batches"] != -(-g["n"] // h["batch"]):
         raise ValueError(f"DSICI stream: {h['batches']} batches for {g['n']} tiles in batches of {h['batch']}")
     return g
@@ -302,7 +366,8 @@ def stream_index(src) -> dict:
     memoryview, or a binary file object with seek and read.  Only the 60-byte header and, per batch, the 8-byte
     length, the 38-byte DSIC2 header and the 24-byte records are read (version 2: 64 bytes, and per batch the 42-byte
     DSIC3 header, the records and 4 bytes per y segment); the strings are skipped.  Returns the header fields of
-    unpack_image_stream (no "blobs"; segments = y segments per tile, 1 for version 1) and
+    unpack_image_stream (no "blobs"; segments = y segments per tile, 1 for version 1; overlap, 0 for versions 1
+    and 2, whose words add 8 bytes to a version-3 head) and
       grid         tile_grid's dict for H, W, th, tw
       tiles        per tile t (row-major, as the grid numbers them): k (batch), b (slot in it), min_y, max_y, min_z,
                    max_z, z_off, z_len, y_off, y_len (absolute byte offsets and lengths of its two strings), y_segs
@@ -319,13 +384,19 @@ def stream_index(src) -> dict:
 def window_tiles(index_or_grid, y0, x0, h, w) -> list:
     """The tiles whose owned rectangle, clipped to H x W, meets the window rows [y0, y0+h) x columns [x0, x0+w),
     ascending (pure Python).  Owned ranges partition each axis, so these are tile rows y0 // th ... (y0+h-1) // th
-    and the columns likewise.  ValueError for an empty window or one that leaves the image."""
+    and the columns likewise.  On a grid with overlap these are the tiles with a non-zero blend weight on some pixel
+    of the window: those whose support rectangle (sup_y x sup_x), clipped to H x W, meets it.  ValueError for an
+    empty window or one that leaves the image."""
     g = index_or_grid.get("grid", index_or_grid)
     y0, x0, h, w = int(y0), int(x0), int(h), int(w)
     if y0 < 0 or x0 < 0 or h < 1 or w < 1 or y0 + h > g["H"] or x0 + w > g["W"]:
         raise ValueError(f"window {h}x{w} at ({y0}, {x0}) is empty or outside the {g['H']}x{g['W']} image")
-    rows = range(y0 // g["th"], (y0 + h - 1) // g["th"] + 1)
-    cols = range(x0 // g["tw"], (x0 + w - 1) // g["tw"] + 1)
+    if g.get("overlap", 0):
+        rows = [i for i, (a, b) in enumerate(g["sup_y"]) if a < y0 + h and min(b, g["H"]) > y0]
+        cols = [j for j, (a, b) in enumerate(g["sup_x"]) if a < x0 + w and min(b, g["W"]) > x0]
+    else:
+        rows = range(y0 // g["th"], (y0 + h - 1) // g["th"] + 1)
+        cols = range(x0 // g["tw"], (x0 + w - 1) // g["tw"] + 1)
     return [i * g["nx"] + j for i in rows for j in cols]
 
 
@@ -365,7 +436,10 @@ def _decode_window(model, src, window, out, batch, stats, what):
     batch = ix["batch"] if batch is None else batch
     kind = {None: ix["kind"], "u8": KIND_U8_HWC, "f32": KIND_F32_CHW}[out]
     img, suffix = _out_image(kind, C, h, w, next(model.parameters()).device, what)
-    fn = getattr(_lib.load(), "dsic_tile_stitch_window_" + suffix)
+    L, O = _lib.load(), ix["overlap"]
+    fn = getattr(L, "dsic_tile_stitch_window_" + suffix)
+    if O:       # the window's float32 canvas, zeroed: the output itself, or a temporary that the finish turns to uint8
+        canvas = img.zero_() if kind == KIND_F32_CHW else torch.zeros((C, h, w), dtype=torch.float32, device=img.device)
     _, N, Hz, Wz = ix["containers"][0]["shape_z"]
     uploaded = decode_batches = 0
     for first in range(0, len(tiles), batch):
@@ -382,10 +456,20 @@ def _decode_window(model, src, window, out, batch, stats, what):
                                                       [n, N, Hz, Wz], what, ride=sel, segments=ix["segments"],
                                                       seg_lengths=[ix["tiles"][t]["y_segs"] for t in sel])
         x_hat = x_hat.contiguous()
-        _lib.check(fn(_p(x_hat), _p(ids), n, _p(img), H, W, C, th, tw, y0, x0, h, w, _stream()),
-                   "tile_stitch_window_" + suffix)
+        if O:
+            for c0 in range(0, n, BLEND_IDS):
+                _lib.check(L.dsic_tile_blend_window_f32(_p(x_hat[c0:]), _p(ids[c0:]), min(BLEND_IDS, n - c0),
+                                                        _p(canvas), H, W, C, th, tw, O, y0, x0, h, w, _stream()),
+                           "tile_blend_window_f32")
+        else:
+            _lib.check(fn(_p(x_hat), _p(ids), n, _p(img), H, W, C, th, tw, y0, x0, h, w, _stream()),
+                       "tile_stitch_window_" + suffix)
         uploaded += nbytes
         decode_batches += 1
+    if O and kind == KIND_F32_CHW:
+        _lib.check(L.dsic_tile_blend_finish_f32(_p(canvas), C, h, w, _stream()), "tile_blend_finish_f32")
+    elif O:
+        _lib.check(L.dsic_tile_blend_finish_u8(_p(canvas), _p(img), C, h, w, _stream()), "tile_blend_finish_u8")
     if stats is not None:
         stats.update(tiles=tiles, decode_batches=decode_batches, bytes_read=source.bytes_read,
                      bytes_uploaded=uploaded)
@@ -397,7 +481,9 @@ def decompress_image(model, stream, out=None):
     """DSICI stream -> the image on the model's device: uint8 [H,W,C] ((uint8)(clamp(x,0,1)*255), truncating, as
     torchvision's to_pil_image) or float32 [C,H,W] (clamp(x,0,1)); by default the kind of the encoder's input,
     out="u8" / "f32" overrides it.  The whole image as a window, decoded container by container; each decoded batch
-    is stitched straight into the image."""
+    is stitched straight into the image.  A stream with overlap (version 3) is blended instead: each decoded batch
+    is added into a zeroed float32 canvas (the output itself for float32) with the tiles' ramp weights, and a finishing
+    pass takes min(v, 1) and, for uint8, (uint8)(v*255)."""
     return _decode_window(model, stream, None, out, None, None, "decompress_image")
 
 
@@ -408,7 +494,8 @@ def decompress_region(model, src, y0, x0, h, w, out=None, batch=64, stats=None):
     (out as in decompress_image).  src: the stream as bytes, or a binary file object, of which only the heads
     (stream_index) and the selected tiles' strings (tile_spans) are read.  The selected tiles are decoded in dense
     batches of at most `batch`, in ascending tile order, whatever containers they come from; each batch is one
-    upload and is stitched into the window as soon as it is decoded.  stats (a dict) receives tiles, decode_batches,
+    upload and is stitched (blended, for a stream with overlap: then "own" reads "weigh on", and the bits do not
+    depend on `batch`) into the window as soon as it is decoded.  stats (a dict) receives tiles, decode_batches,
     bytes_read and bytes_uploaded (the padded string bytes; 52 bytes of descriptors per tile travel beside them)."""
     batch = int(batch)
     if batch < 1:

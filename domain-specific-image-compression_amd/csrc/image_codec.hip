@@ -7,6 +7,12 @@
 // Tile geometry (codec.tile_grid): Hp = ceil16(H), tiles_y = ceil(Hp / th), origin of tile row i =
 // min(i*th, Hp - th); tile row i owns padded rows [i*th, min((i+1)*th, Hp)) (the last row of tiles shifts
 // inward and its overlap rows belong to the earlier tile).  Columns likewise; tiles are numbered row-major.
+//
+// Overlapped tiles (overlap = O, a multiple of 16 with O <= min(th, tw) / 2): on an axis of more than one tile the
+// stride is s = t - O, tiles = ceil((P - O) / s), nominal origin a(i) = i*s, real origin min(i*s, P - t); tile i's
+// support is [a(i), a(i+1) + O), the last one's [a(n-1), P).  Over the first O positions of a support (i > 0) the
+// tile's weight ramps up as (2k+1)/(2O), over [a(i+1), a(i+1) + O) it ramps down as (2(O-1-k)+1)/(2O), elsewhere in
+// the support it is 1: at every position the weights of at most two tiles per axis sum to 1.  O = 0 is the grid above.
 #include "common.h"
 
 namespace dsic {
@@ -15,15 +21,17 @@ constexpr int kTileRows = 16;  // rows of one tile per workgroup (th, tw are mul
 
 struct Grid {
   int H, W, Hp, Wp, th, tw, ny, nx;
-  __host__ __device__ int oy(int i) const { return min(i * th, Hp - th); }
-  __host__ __device__ int ox(int j) const { return min(j * tw, Wp - tw); }
+  int O, sy, sx;  // overlap and the strides th - O, tw - O (th, tw on an axis of one tile)
+  __host__ __device__ int oy(int i) const { return min(i * sy, Hp - th); }
+  __host__ __device__ int ox(int j) const { return min(j * sx, Wp - tw); }
 };
 
-static Grid make_grid(int H, int W, int th, int tw) {
+static Grid make_grid(int H, int W, int th, int tw, int O = 0) {
   Grid g;
-  g.H = H, g.W = W, g.th = th, g.tw = tw;
+  g.H = H, g.W = W, g.th = th, g.tw = tw, g.O = O;
   g.Hp = round_up(H, 16), g.Wp = round_up(W, 16);
-  g.ny = ceil_div(g.Hp, th), g.nx = ceil_div(g.Wp, tw);
+  g.sy = g.Hp <= th ? th : th - O, g.sx = g.Wp <= tw ? tw : tw - O;
+  g.ny = g.Hp <= th ? 1 : ceil_div(g.Hp - O, g.sy), g.nx = g.Wp <= tw ? 1 : ceil_div(g.Wp - O, g.sx);
   return g;
 }
 
@@ -241,6 +249,162 @@ __global__ __launch_bounds__(256) void stitch_u8_kernel(const float* __restrict_
   }
 }
 
+// ---- tile blend (overlapped tiles) -------------------------------------------------------------------------
+// A pixel's value is the left fold ((0 + c_a) + c_b) + ... over its contributing tiles in ascending tile number,
+// c = (wy * wx) * clamp01(x_tile), all float32 and unfused.  The partial sum travels in the canvas: a call adds the
+// contributions of the tiles it holds, and one thread per pixel does so, that of the lowest-numbered contributor
+// present.  Calls arrive with ascending tiles, so the order of the additions is the same however the tiles are cut
+// into calls.
+
+constexpr int kBlendIds = 64;  // tiles per blend call: the id list is searched in LDS
+
+// The tiles that weigh on padded position p of one axis: lo <= hi (equal outside the ramps), with their weights.
+struct Contrib {
+  int lo, hi;
+  float wlo, whi;
+};
+__device__ __forceinline__ Contrib contrib(int p, int s, int n, int O, float rcp) {
+  const int j = min(p / s, n - 1), k = p - j * s;
+  if (j > 0 && k < O) return {j - 1, j, (float)(2 * (O - 1 - k) + 1) * rcp, (float)(2 * k + 1) * rcp};
+  return {j, j, 1.f, 1.f};
+}
+
+// tiles [n][C][th][tw], ids ascending -> accumulated into the float32 [C][wh][ww] canvas; blockIdx.z = channel
+__global__ __launch_bounds__(256) void blend_f32_kernel(const float* __restrict__ tiles, const int* __restrict__ ids,
+                                                        int n, float* __restrict__ canvas, Grid g, Clip w, float rcp) {
+  __shared__ int s_ids[kBlendIds];
+  __shared__ int s_slot[9];  // where the tiles (i-1..i+1, j-1..j+1) lie in this call, -1 = not in it
+  const int c = blockIdx.z, C = gridDim.z;
+  if ((int)threadIdx.x < n) s_ids[threadIdx.x] = ids[threadIdx.x];
+  __syncthreads();
+  const int t = s_ids[blockIdx.y];
+  if (t < 0 || t >= g.ny * g.nx) return;
+  const int i = t / g.nx, j = t % g.nx;
+  if (threadIdx.x < 9) {
+    const int ii = i + (int)threadIdx.x / 3 - 1, jj = j + (int)threadIdx.x % 3 - 1;
+    int slot = -1;
+    if (ii >= 0 && ii < g.ny && jj >= 0 && jj < g.nx) {
+      const int want = ii * g.nx + jj;
+      int lo = 0, hi = n;  // the first entry that is not below want
+      while (lo < hi) {
+        const int mid = (lo + hi) >> 1;
+        if (s_ids[mid] < want) lo = mid + 1;
+        else hi = mid;
+      }
+      if (lo < n && s_ids[lo] == want) slot = lo;
+    }
+    s_slot[threadIdx.x] = slot;
+  }
+  __syncthreads();
+  if (s_slot[4] != (int)blockIdx.y) return;  // a tile named twice is blended once, by its first entry
+  // the support of tile t, cut to the image and the window
+  const int sy0 = max(i * g.sy, w.y0), sy1 = min(min(i < g.ny - 1 ? (i + 1) * g.sy + g.O : g.Hp, g.H), w.y1);
+  const int sx0 = max(j * g.sx, w.x0), sx1 = min(min(j < g.nx - 1 ? (j + 1) * g.sx + g.O : g.Wp, g.W), w.x1);
+  if (sx0 >= sx1) return;
+  const int ya = sy0 + blockIdx.x * kTileRows;
+  const int rows = min(kTileRows, sy1 - ya);
+  if (rows <= 0) return;
+  const size_t cplane = (size_t)g.th * g.tw;
+  const float* src = tiles + (size_t)c * cplane;
+
+  // v + the contributions to pixel (y, x) of the tiles of this call, if tile t is the lowest of them
+  auto pixel = [&](const Contrib& ay, int y, int x, float* v) -> bool {
+    const Contrib ax = contrib(x, g.sx, g.nx, g.O, rcp);
+    bool mine = false;
+    float acc = *v;
+    for (int a = ay.lo == ay.hi ? 1 : 0; a < 2; ++a) {
+      const int iy = a ? ay.hi : ay.lo;
+      const float wy = a ? ay.whi : ay.wlo;
+      for (int b = ax.lo == ax.hi ? 1 : 0; b < 2; ++b) {
+        const int ix = b ? ax.hi : ax.lo;
+        const int slot = s_slot[(iy - i + 1) * 3 + (ix - j + 1)];
+        if (slot < 0) continue;
+        if (!mine) {
+          if (iy != i || ix != j) return false;
+          mine = true;
+        }
+        const float wgt = wy * (b ? ax.whi : ax.wlo);
+        const float x_hat = src[(size_t)slot * C * cplane + (size_t)(y - g.oy(iy)) * g.tw + (x - g.ox(ix))];
+        acc = acc + wgt * clamp01(x_hat);
+      }
+    }
+    *v = acc;
+    return mine;
+  };
+
+  const int wW = w.x1 - w.x0;
+  const int64_t plane = (int64_t)c * (w.y1 - w.y0) * wW;
+  const int cpr = (sx1 - sx0) / 4 + 2;  // 4-float chunks a row segment can touch
+  for (int idx = threadIdx.x; idx < rows * cpr; idx += blockDim.x) {
+    const int r = idx / cpr, k = idx - r * cpr;
+    const int y = ya + r;
+    const int64_t e0 = plane + (int64_t)(y - w.y0) * wW + (sx0 - w.x0), e1 = e0 + (sx1 - sx0);
+    const int64_t q0 = ((e0 >> 2) + k) << 2;
+    if (q0 >= e1) continue;
+    const Contrib ay = contrib(y, g.sy, g.ny, g.O, rcp);
+    const int xq = sx0 + (int)(q0 - e0);  // the image column of element q0
+    if (q0 >= e0 && q0 + 4 <= e1) {
+      float4 v = *(const float4*)(canvas + q0);
+      const bool m0 = pixel(ay, y, xq, &v.x), m1 = pixel(ay, y, xq + 1, &v.y), m2 = pixel(ay, y, xq + 2, &v.z),
+                 m3 = pixel(ay, y, xq + 3, &v.w);
+      if (m0 && m1 && m2 && m3) {
+        *(float4*)(canvas + q0) = v;
+      } else {  // a ramp begins or ends inside the chunk: the other elements belong to another tile's thread
+        if (m0) canvas[q0] = v.x;
+        if (m1) canvas[q0 + 1] = v.y;
+        if (m2) canvas[q0 + 2] = v.z;
+        if (m3) canvas[q0 + 3] = v.w;
+      }
+    } else {
+      for (int64_t e = max(q0, e0); e < min(q0 + 4, e1); ++e) {
+        float v = canvas[e];
+        if (pixel(ay, y, sx0 + (int)(e - e0), &v)) canvas[e] = v;
+      }
+    }
+  }
+}
+
+__device__ __forceinline__ float min1(float v) { return v > 1.f ? 1.f : v; }
+
+// min(v, 1) in place: in float32 the four weights of a pixel can sum to 1 + 2 ulp
+__global__ __launch_bounds__(256) void blend_finish_f32_kernel(float* __restrict__ canvas, int64_t n) {
+  const int64_t n4 = n >> 2, step = (int64_t)gridDim.x * blockDim.x;
+  const int64_t tid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  for (int64_t q = tid; q < n4; q += step) {
+    float4 v = ((const float4*)canvas)[q];
+    v.x = min1(v.x), v.y = min1(v.y), v.z = min1(v.z), v.w = min1(v.w);
+    ((float4*)canvas)[q] = v;
+  }
+  for (int64_t e = 4 * n4 + tid; e < n; e += step) canvas[e] = min1(canvas[e]);
+}
+
+// canvas float32 [C][hw] -> (uint8)(min(v, 1) * 255) into the uint8 [hw][C] image, 16 bytes per lane
+__global__ __launch_bounds__(256) void blend_finish_u8_kernel(const float* __restrict__ canvas,
+                                                              uint8_t* __restrict__ out, int C, int64_t hw) {
+  const int64_t n = hw * C, nq = (n + 15) >> 4, step = (int64_t)gridDim.x * blockDim.x;
+  for (int64_t q = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; q < nq; q += step) {
+    const int64_t q0 = q << 4, hi = min(q0 + 16, n);
+    int64_t px = q0 / C;
+    int c = (int)(q0 - px * C);
+    uint8_t b[16];
+#pragma unroll
+    for (int e = 0; e < 16; ++e) {
+      b[e] = 0;
+      if (q0 + e < hi) {
+        b[e] = (uint8_t)(min1(canvas[c * hw + px]) * 255.0f);
+        if (++c == C) c = 0, ++px;
+      }
+    }
+    if (hi == q0 + 16) {
+      uint4 v;
+      __builtin_memcpy(&v, b, 16);
+      *(uint4*)(out + q0) = v;
+    } else {
+      for (int64_t e = q0; e < hi; ++e) out[e] = b[e - q0];
+    }
+  }
+}
+
 // ---- DSIC2 container --------------------------------------------------------------------------------------
 // magic(6) | tag u32 | B,My,Hy,Wy,Nz,Hz,Wz u32 | B x (min_y,max_y,min_z,max_z i32, len_z,len_y u32) | strings
 // DSIC3 (K > 1 segments per y string): magic "DSIC3\0" | the same fields | segs u32 | the same records (len_y = the sum
@@ -397,18 +561,44 @@ static const char* grid_error(int H, int W, int th, int tw) {
   return nullptr;
 }
 
+static bool overlap_ok(int th, int tw, int O) { return O >= 0 && O % 16 == 0 && 2 * O <= (th < tw ? th : tw); }
+
 }  // namespace dsic
 
 using namespace dsic;
 
-#define DSIC_TILE_ARGS(what)                                                                                 \
+#define DSIC_TILE_ARGS_OV(what, overlap)                                                                     \
   const char* ge = grid_error(H, W, th, tw);                                                                 \
   DSIC_REQUIRE(!ge, what ": %s (H=%d W=%d th=%d tw=%d)", ge ? ge : "", H, W, th, tw);                        \
-  const Grid g = make_grid(H, W, th, tw);                                                                    \
+  DSIC_REQUIRE(overlap_ok(th, tw, overlap), what ": overlap=%d must be a multiple of 16 in 0..min(th, tw)/2", \
+               overlap);                                                                                     \
+  const Grid g = make_grid(H, W, th, tw, overlap);                                                           \
   DSIC_REQUIRE(first_tile >= 0 && n_tiles > 0 && (int64_t)first_tile + n_tiles <= (int64_t)g.ny * g.nx,      \
                what ": tiles [%d, %d) outside the grid of %d", first_tile, first_tile + n_tiles, g.ny * g.nx); \
   DSIC_REQUIRE(n_tiles <= 65535, what ": at most 65535 tiles per call");                                   \
   const dim3 grid(g.th / kTileRows, n_tiles, 1)
+#define DSIC_TILE_ARGS(what) DSIC_TILE_ARGS_OV(what, 0)
+
+extern "C" int dsic_tile_gather_u8_ov(const uint8_t* img_hwc, uint8_t* tiles, int H, int W, int C, int th, int tw,
+                                      int overlap, int first_tile, int n_tiles, void* stream) {
+  DSIC_REQUIRE(img_hwc && tiles, "tile_gather_u8_ov: null pointer");
+  DSIC_REQUIRE(C == 3 || C == 4, "tile_gather_u8_ov: C=%d must be 3 or 4", C);
+  DSIC_TILE_ARGS_OV("tile_gather_u8_ov", overlap);
+  DSIC_REQUIRE(((uintptr_t)tiles & 15) == 0, "tile_gather_u8_ov: tiles must be 16-byte aligned");
+  hipLaunchKernelGGL(gather_u8_kernel, grid, dim3(256), 0, (hipStream_t)stream, img_hwc, tiles, g, C, first_tile);
+  return check_launch("tile_gather_u8_ov");
+}
+
+extern "C" int dsic_tile_gather_f32_ov(const float* img_chw, float* tiles, int H, int W, int C, int th, int tw,
+                                       int overlap, int first_tile, int n_tiles, void* stream) {
+  DSIC_REQUIRE(img_chw && tiles, "tile_gather_f32_ov: null pointer");
+  DSIC_REQUIRE(C >= 1 && C <= 8, "tile_gather_f32_ov: C=%d must be in 1..8", C);
+  DSIC_TILE_ARGS_OV("tile_gather_f32_ov", overlap);
+  DSIC_REQUIRE(((uintptr_t)tiles & 15) == 0, "tile_gather_f32_ov: tiles must be 16-byte aligned");
+  hipLaunchKernelGGL(gather_f32_kernel, dim3(grid.x, grid.y, C), dim3(256), 0, (hipStream_t)stream, img_chw, tiles,
+                     g, first_tile);
+  return check_launch("tile_gather_f32_ov");
+}
 
 extern "C" int dsic_tile_gather_u8(const uint8_t* img_hwc, uint8_t* tiles, int H, int W, int C, int th, int tw,
                                    int first_tile, int n_tiles, void* stream) {
@@ -484,6 +674,54 @@ extern "C" int dsic_tile_stitch_window_u8(const float* tiles, const int* tile_id
   DSIC_REQUIRE(((uintptr_t)out & 15) == 0, "tile_stitch_window_u8: out must be 16-byte aligned");
   hipLaunchKernelGGL(stitch_u8_kernel, grid, dim3(256), 0, (hipStream_t)stream, tiles, out, g, C, 0, tile_ids, clip);
   return check_launch("tile_stitch_window_u8");
+}
+
+extern "C" int dsic_tile_blend_window_f32(const float* tiles, const int* tile_ids, int n_tiles, float* canvas, int H,
+                                          int W, int C, int th, int tw, int overlap, int wy0, int wx0, int wh, int ww,
+                                          void* stream) {
+  DSIC_REQUIRE(tiles && tile_ids && canvas, "tile_blend_window_f32: null pointer");
+  DSIC_REQUIRE(C >= 1 && C <= 8, "tile_blend_window_f32: C=%d must be in 1..8", C);
+  const char* ge = grid_error(H, W, th, tw);
+  DSIC_REQUIRE(!ge, "tile_blend_window_f32: %s (H=%d W=%d th=%d tw=%d)", ge ? ge : "", H, W, th, tw);
+  DSIC_REQUIRE(overlap_ok(th, tw, overlap),
+               "tile_blend_window_f32: overlap=%d must be a multiple of 16 in 0..min(th, tw)/2", overlap);
+  DSIC_REQUIRE(wy0 >= 0 && wx0 >= 0 && wh >= 1 && ww >= 1 && (int64_t)wy0 + wh <= H && (int64_t)wx0 + ww <= W,
+               "tile_blend_window_f32: window %dx%d at (%d, %d) outside the %dx%d image", wh, ww, wy0, wx0, H, W);
+  DSIC_REQUIRE(n_tiles >= 1 && n_tiles <= kBlendIds, "tile_blend_window_f32: n=%d tiles per call (1..%d)", n_tiles,
+               kBlendIds);
+  DSIC_REQUIRE(((uintptr_t)canvas & 15) == 0, "tile_blend_window_f32: canvas must be 16-byte aligned");
+  const Grid g = make_grid(H, W, th, tw, overlap);
+  const float rcp = overlap ? 1.0f / (float)(2 * overlap) : 0.f;
+  hipLaunchKernelGGL(blend_f32_kernel, dim3(g.th / kTileRows, n_tiles, C), dim3(256), 0, (hipStream_t)stream, tiles,
+                     tile_ids, n_tiles, canvas, g, Clip{wy0, wy0 + wh, wx0, wx0 + ww}, rcp);
+  return check_launch("tile_blend_window_f32");
+}
+
+static int finish_blocks(int64_t units) {
+  const int64_t b = (units + 255) / 256;
+  return (int)(b < 1 ? 1 : (b > 8192 ? 8192 : b));
+}
+
+extern "C" int dsic_tile_blend_finish_f32(float* canvas, int C, int h, int w, void* stream) {
+  DSIC_REQUIRE(canvas, "tile_blend_finish_f32: null pointer");
+  DSIC_REQUIRE(C >= 1 && C <= 8, "tile_blend_finish_f32: C=%d must be in 1..8", C);
+  DSIC_REQUIRE(h >= 1 && w >= 1, "tile_blend_finish_f32: empty window %dx%d", h, w);
+  DSIC_REQUIRE(((uintptr_t)canvas & 15) == 0, "tile_blend_finish_f32: canvas must be 16-byte aligned");
+  const int64_t n = (int64_t)C * h * w;
+  hipLaunchKernelGGL(blend_finish_f32_kernel, dim3(finish_blocks(n >> 2)), dim3(256), 0, (hipStream_t)stream, canvas,
+                     n);
+  return check_launch("tile_blend_finish_f32");
+}
+
+extern "C" int dsic_tile_blend_finish_u8(const float* canvas, uint8_t* out_hwc, int C, int h, int w, void* stream) {
+  DSIC_REQUIRE(canvas && out_hwc, "tile_blend_finish_u8: null pointer");
+  DSIC_REQUIRE(C == 3 || C == 4, "tile_blend_finish_u8: C=%d must be 3 or 4", C);
+  DSIC_REQUIRE(h >= 1 && w >= 1, "tile_blend_finish_u8: empty window %dx%d", h, w);
+  DSIC_REQUIRE(((uintptr_t)out_hwc & 15) == 0, "tile_blend_finish_u8: out must be 16-byte aligned");
+  const int64_t hw = (int64_t)h * w;
+  hipLaunchKernelGGL(blend_finish_u8_kernel, dim3(finish_blocks((hw * C + 15) >> 4)), dim3(256), 0,
+                     (hipStream_t)stream, canvas, out_hwc, C, hw);
+  return check_launch("tile_blend_finish_u8");
 }
 
 extern "C" int dsic_container_pack(const uint8_t* bytes, int64_t cap_z, int64_t cap_y, const int* lengths,

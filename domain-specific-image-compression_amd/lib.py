@@ -108,6 +108,11 @@ SIGNATURES = {
     "dsic_strings_scatter_select": (c_int, [_P, c_int64, _P, c_int, c_int64, _P, c_int64, _P, c_int64, _P, _P]),
     "dsic_tile_stitch_window_f32": (c_int, [_P, _P, c_int, _P] + [c_int] * 9 + [_P]),
     "dsic_tile_stitch_window_u8": (c_int, [_P, _P, c_int, _P] + [c_int] * 9 + [_P]),
+    "dsic_tile_gather_u8_ov": (c_int, [_P, _P] + [c_int] * 8 + [_P]),
+    "dsic_tile_gather_f32_ov": (c_int, [_P, _P] + [c_int] * 8 + [_P]),
+    "dsic_tile_blend_window_f32": (c_int, [_P, _P, c_int, _P] + [c_int] * 10 + [_P]),
+    "dsic_tile_blend_finish_f32": (c_int, [_P, c_int, c_int, c_int, _P]),
+    "dsic_tile_blend_finish_u8": (c_int, [_P, _P, c_int, c_int, c_int, _P]),
     "dsic_stream_create_masked":(c_int, [_P, c_int, _P]),
     "dsic_stream_destroy": (c_int, [_P]),
     "dsic_range_decode": (c_int, [_P, c_int64, _P, c_int, c_int, _P, c_int, _P, c_int, c_int, c_int,

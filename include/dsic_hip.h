@@ -499,6 +499,40 @@ int dsic_tile_stitch_window_u8(const float* tiles, const int* tile_ids, int n, u
                                int H, int W, int C, int th, int tw, int wy0, int wx0, int wh,
                                int ww, void* stream);
 
+/* Overlapped tiles with blended seams (codec.tile_grid with overlap = O, a multiple of 16 with
+ * O <= min(th, tw) / 2; O = 0 is the grid above).  On an axis of more than one tile the stride
+ * is s = t - O, tiles = ceil((P - O) / s), nominal origin a(i) = i*s, real origin
+ * min(i*s, P - t).  Tile i's support is [a(i), a(i+1) + O), the last one's [a(n-1), P); its
+ * weight is (2k+1)/(2O) over the first O positions of the support (i > 0, k counted from a(i)),
+ * (2(O-1-k)+1)/(2O) over [a(i+1), a(i+1) + O) (k counted from a(i+1)), 1 elsewhere in the
+ * support and 0 outside it, so at most two tiles per axis weigh on a position and their
+ * weights sum to 1.
+ * gather_*_ov: the gather calls above on this grid; overlap = 0 gives their tiles bit for bit.
+ * blend_window_f32: adds one decoded batch (tiles float32 [n][C][th][tw]; tile_ids device int32
+ *   [n], strictly ascending, n in 1..64) into canvas, the float32 [C][wh][ww] image of the
+ *   window rows [wy0, wy0+wh) x columns [wx0, wx0+ww), 16-byte aligned and zeroed by the caller
+ *   before the first batch.  All float32, unfused: rcp = 1.0f / (float)(2 O), a ramp weight
+ *   (float)(2k+1) * rcp, the weight of a tile w = wy * wx, its contribution w * clamp(x,0,1),
+ *   and a pixel the left fold ((0 + c_a) + c_b) + ... over its contributing tiles in ascending
+ *   number.  No atomics: a pixel is read, added to and stored by one thread per call, that of
+ *   the lowest-numbered contributing tile in the call, and the partial sum travels in the
+ *   canvas, so batches that arrive in ascending tile order give the same bits however the tiles
+ *   are cut into batches.  A number outside the grid, or a tile that misses the window, adds
+ *   nothing.
+ * blend_finish_f32: canvas = min(canvas, 1) in place (the float32 weights of a pixel can sum to
+ *   1 + 2 ulp).  blend_finish_u8: out uint8 [h][w][C] = (uint8)(min(canvas, 1) * 255),
+ *   truncating, C 3 or 4, out 16-byte aligned. */
+int dsic_tile_gather_u8_ov(const uint8_t* img_hwc, uint8_t* tiles, int H, int W, int C, int th,
+                           int tw, int overlap, int first_tile, int n_tiles, void* stream);
+int dsic_tile_gather_f32_ov(const float* img_chw, float* tiles, int H, int W, int C, int th,
+                            int tw, int overlap, int first_tile, int n_tiles, void* stream);
+int dsic_tile_blend_window_f32(const float* tiles, const int* tile_ids, int n, float* canvas,
+                               int H, int W, int C, int th, int tw, int overlap, int wy0,
+                               int wx0, int wh, int ww, void* stream);
+int dsic_tile_blend_finish_f32(float* canvas, int C, int h, int w, void* stream);
+int dsic_tile_blend_finish_u8(const float* canvas, uint8_t* out_hwc, int C, int h, int w,
+                              void* stream);
+
 /* HIP stream limited to the CUs whose bit is set in mask_host[words] (bit i of
  * word i/32 = CU i).  Used to give the range coder its own few CUs beside the
  * conv kernels; there is no reference counterpart (the reference is

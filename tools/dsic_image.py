@@ -1,11 +1,13 @@
 """Compress an image of any size to one DSICI stream, or decompress a stream back to an image.
 
-    python tools/dsic_image.py compress   --weights CKPT.pt IN.png  OUT.dsic [--tile 256] [--batch 64] [--segments K]
+    python tools/dsic_image.py compress   --weights CKPT.pt IN.png  OUT.dsic [--tile 256] [--batch 64] [--segments K] [--overlap O]
     python tools/dsic_image.py decompress --weights CKPT.pt IN.dsic OUT.png [--out u8|f32] [--region Y0,X0,H,W]
     python tools/dsic_image.py info       IN.dsic
 
 --segments K (2, 4, 8 or 16) codes every tile's y string as K independent strings, which a decoder reads on K waves per
-tile (a version-2 stream, a fraction of a percent larger; the decoded image is the same).  --region decodes only the tiles that own the window's pixels and reads only their bytes of the file; info prints the
+tile (a version-2 stream, a fraction of a percent larger; the decoded image is the same).  --overlap O (a multiple of
+16, at most half a tile side) makes neighbouring tiles share O pixels, which the decoder cross-fades (a version-3
+stream; more tiles, so more bytes).  --region decodes only the tiles that own the window's pixels and reads only their bytes of the file; info prints the
 geometry, the tile grid and the bytes of every batch from the stream's heads, without a model or a GPU.
 
 The state dict is loaded plain or from under "model" (code/modelv2/eval_selfcontained_entropy.py:130-134); the model's
@@ -84,7 +86,8 @@ def print_info(ix):
     print(f"[dsic_image] model N={ix['N']} M={ix['M']} in_ch={ix['in_ch']} spatial_params={ix['spatial_params']}")
     print(f"[dsic_image] tile grid {g['ny']}x{g['nx']} = {g['n']} tiles of {g['th']}x{g['tw']}, "
           f"{ix['batches']} batch(es) of up to {ix['batch']}; heads {ix['index_bytes']} bytes")
-    print(f"[dsic_image] stream version {ix['version']}, {ix['segments']} segment(s) per y string")
+    print(f"[dsic_image] stream version {ix['version']}, {ix['segments']} segment(s) per y string, "
+          f"overlap {ix['overlap']}, stride {g['sy']}x{g['sx']}")
     for k, c in enumerate(ix["containers"]):
         pixels = 0
         for t in range(c["first"], c["first"] + c["tiles"]):
@@ -104,6 +107,7 @@ def main(argv=None):
     ap.add_argument("--batch", type=int, default=64)
     ap.add_argument("--tail", type=int, default=10)
     ap.add_argument("--segments", type=int, default=1, help="compress: y segments per tile (1, 2, 4, 8 or 16)")
+    ap.add_argument("--overlap", type=int, default=0, help="compress: pixels neighbouring tiles share and cross-fade")
     ap.add_argument("--out", choices=("u8", "f32"), default=None, help="decoded kind (default: the encoder's input's)")
     ap.add_argument("--region", default=None, metavar="Y0,X0,H,W", help="decompress: only this window of the image")
     ap.add_argument("--min-nu", type=float, default=2.0)
@@ -127,12 +131,14 @@ def main(argv=None):
     model = load_model(a.weights, a.min_nu, a.max_nu)
     if a.mode == "compress":
         img = read_image(a.src, codec._model_shape(model)[2])
-        stream = codec.compress_image(model, img, tile=a.tile, batch=a.batch, tail=a.tail, segments=a.segments)
+        stream = codec.compress_image(model, img, tile=a.tile, batch=a.batch, tail=a.tail, segments=a.segments,
+                                      overlap=a.overlap)
         with open(a.dst, "wb") as f:
             f.write(stream)
         h = codec.unpack_image_stream(stream)
         print(f"[dsic_image] {h['H']}x{h['W']}x{h['C']} -> {len(stream)} bytes, {codec.image_bpp(stream):.4f} bpp, "
-              f"{h['batches']} batch(es) of {h['th']}x{h['tw']} tiles, {h['segments']} segment(s) per y string")
+              f"{h['batches']} batch(es) of {h['th']}x{h['tw']} tiles, {h['segments']} segment(s) per y string, "
+              f"overlap {h['overlap']}")
     elif region is not None:
         stats = {}
         with open(a.src, "rb") as f:

@@ -1,6 +1,7 @@
 """Tiles per second of the whole-image codec on a synthetic scene, against the host-packed path on the same tiles.
 
     python tools/image_codec_bench.py [--size 4096] [--tile 256] [--batch 64] [--reps 3] [--json OUT]
+    python tools/image_codec_bench.py --overlap 16,32 [--json profiles/overlap_bench.json]
 
 device path  compress_image (gather on the device, compress_to_container per batch) and decompress_image
              (decompress_container per batch, stitched into a uint8 image);
@@ -12,6 +13,14 @@ Every figure is the best of --reps full passes over the scene after one warm-up 
 --segments K  (with or without --region) the same figures for streams whose y strings are whole (K = 1) and in K
           segments, read alternately in one run, each the median of --reps readings; "segments" in the result holds
           them per K beside the stream-size ratio.  The K = 1 stream's figures stay where they were.
+
+--overlap O[,O2...]  overlapped tiles with blended seams: streams of overlap 0 and of every O given, read alternately
+          in one run (medians of --reps readings): stream bytes and tile counts against overlap 0, compress_image /
+          decompress_image in tiles per second, and a seam figure: the mean absolute step of the reconstruction error
+          x_hat - x across the nominal tile boundaries of each stream's own grid, relative to its mean step at all other
+          rows and columns (the error, not the image, because the synthetic scene has edges of its own every 256
+          pixels).  With synthetic weights the seam figure shows the mechanism, not a trained model's quality.
+          Written to profiles/overlap_bench.json (or --json).  Records, not bars.
 
 --region  decompress_region of the same stream for an aligned one-tile window, an unaligned 2 x 2-tile-sized window
           (9 tiles), an unaligned half-scene window and the whole image, beside decompress_image before and after
@@ -124,6 +133,66 @@ def segment_records(model, img, a, n):
     return res
 
 
+def _seam_figure(err, g):
+    """err float32 [C,H,W] (x_hat - x): mean |step| across the nominal tile boundaries over the mean |step| at all
+    other rows and columns."""
+    import torch
+    dy = (err[:, 1:, :] - err[:, :-1, :]).abs().mean(dim=(0, 2))       # step between rows r and r+1, at index r
+    dx = (err[:, :, 1:] - err[:, :, :-1]).abs().mean(dim=(0, 1))
+    at, off = [], []
+    for d, own in ((dy, g["own_y"]), (dx, g["own_x"])):
+        seam = torch.zeros(d.numel(), dtype=torch.bool, device=d.device)
+        for a, _ in own[1:]:
+            if a - 1 < d.numel():
+                seam[a - 1] = True
+        at.append(d[seam])
+        off.append(d[~seam])
+    at, off = torch.cat(at), torch.cat(off)
+    return {"mean_step_at_boundaries": float(at.mean()), "mean_step_elsewhere": float(off.mean()),
+            "ratio": round(float(at.mean() / off.mean()), 4), "boundaries": int(at.numel())}
+
+
+def overlap_records(model, img, a, overlaps):
+    """Overlap 0 and every O of `overlaps`, alternately."""
+    import statistics
+    import torch
+    from dsic_amd import codec
+    t = a.tile
+    Os = [0] + [o for o in overlaps if o]
+    streams = {O: codec.compress_image(model, img, tile=t, batch=a.batch, overlap=O) for O in Os}
+    grids = {O: codec.stream_index(streams[O])["grid"] for O in Os}
+    x = img.permute(2, 0, 1).to(torch.float32).div(255)
+    seams = {O: _seam_figure(codec.decompress_image(model, streams[O], out="f32") - x, grids[O]) for O in Os}
+    jobs = {"compress_image": lambda O: codec.compress_image(model, img, tile=t, batch=a.batch, overlap=O),
+            "decompress_image": lambda O: codec.decompress_image(model, streams[O])}
+    reads = {name: {O: [] for O in Os} for name in jobs}
+    for name, job in jobs.items():
+        for O in Os:
+            job(O)                                                     # warm-up
+        torch.cuda.synchronize()
+        for _ in range(a.reps):
+            for O in Os:
+                t0 = time.perf_counter()
+                job(O)
+                torch.cuda.synchronize()
+                reads[name][O].append(1e3 * (time.perf_counter() - t0))
+    res = {"what": "overlap 0 against overlapped tiles with blended seams, read alternately in one run on one MI355X; "
+                   "medians.  Synthetic weights: the seam figure shows the mechanism, not a trained model's quality",
+           "scene": f"{a.size}x{a.size}x3 uint8", "tile": t, "batch": a.batch, "reps": a.reps, "overlaps": {}}
+    for O in Os:
+        n = grids[O]["n"]
+        rec = {"tiles": n, "grid": f"{grids[O]['ny']}x{grids[O]['nx']}", "stride": grids[O]["sy"],
+               "tiles_over_overlap_0": round(n / grids[0]["n"], 4), "stream_bytes": len(streams[O]),
+               "bytes_over_overlap_0": round(len(streams[O]) / len(streams[0]), 4),
+               "bpp": round(codec.image_bpp(streams[O]), 4), "seam": seams[O]}
+        for name in jobs:
+            med = statistics.median(reads[name][O])
+            rec[name] = {"ms_median": round(med, 3), "ms_all": [round(v, 3) for v in reads[name][O]],
+                         "tiles_per_s": round(n / med * 1e3, 1)}
+        res["overlaps"][str(O)] = rec
+    return res
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--size", type=int, default=4096)
@@ -133,6 +202,8 @@ def main():
     ap.add_argument("--json", default=None)
     ap.add_argument("--region", action="store_true", help="measure decompress_region windows instead")
     ap.add_argument("--segments", type=int, default=1, help="also measure streams of K y segments, alternately")
+    ap.add_argument("--overlap", default=None, metavar="O[,O2...]",
+                    help="measure overlapped tiles with blended seams against overlap 0, alternately")
     a = ap.parse_args()
 
     import numpy as np
@@ -153,6 +224,12 @@ def main():
     img = torch.from_numpy(scene.astype(np.uint8)).cuda()
     n = g["n"]
 
+    if a.overlap is not None:
+        res = overlap_records(model, img, a, [int(v) for v in a.overlap.split(",")])
+        print(json.dumps(res))
+        with open(a.json or os.path.join(ROOT, "profiles", "overlap_bench.json"), "w") as f:
+            json.dump(res, f, indent=1)
+        return
     stream = codec.compress_image(model, img, tile=a.tile, batch=a.batch)
     seg = segment_records(model, img, a, n) if a.segments > 1 else None
     if a.region:
