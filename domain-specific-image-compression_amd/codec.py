@@ -23,6 +23,13 @@ reconstructions are cross-faded over them with linear ramps that sum to 1; the b
 pixel's contributing tiles in ascending tile number (dsic_tile_blend_window_f32), so a window decodes to the same
 bits however its tiles are batched.
 
+max_error = tau (an integer 0 .. 127; uint8 images, overlap = 0) is stream version 4, the near-lossless mode: the
+version-3 head with overlap word 0, then max_error u32 and res_bands u32 (16), and per batch, behind `u64 length,
+container` (the bytes the same call without max_error writes), `u64 length, residual block` (residual.py): per tile
+the quantized difference between the tile and the lossy uint8 reconstruction, coded with tables built from the tile's
+own histogram.  The decoders add it back in the stitch, and every decoded pixel lies within tau of the original;
+tau = 0 is lossless.  Tiles stay independent, so a region still decodes from its own tiles' bytes alone.
+
 Because tiles are independent and the DSIC2 heads hold every string's length, any window of a stream can be decoded
 from only the tiles that own its pixels: stream_index finds their bytes from the heads alone, decompress_region decodes
 them in dense batches and stitches them into the window, byte for byte the crop of decompress_image's result.
@@ -30,6 +37,7 @@ decompress_image is the same decode (_decode_window) of the window (0, 0, H, W),
 """
 from __future__ import annotations
 
+import bisect
 import operator
 import struct
 
@@ -37,6 +45,7 @@ import torch
 
 from . import entropy
 from . import lib as _lib
+from . import residual as _residual
 from .entropy import EntropyError
 from .ops import _p, _stream
 
@@ -44,10 +53,12 @@ MAGIC = b"DSICI\x00"
 VERSION = 1
 VERSION_SEG = 2            # version 1 + the segments word; written only for segments > 1
 VERSION_OV = 3             # version 1 + the segments word + the overlap word; written only for overlap > 0
+VERSION_RES = 4            # the version-3 head with overlap 0 + max_error u32 + res_bands u32; a residual block per batch
 BLEND_IDS = 64             # tiles per dsic_tile_blend_window_f32 call
 KIND_U8_HWC, KIND_F32_CHW = 0, 1
 _HEAD = struct.Struct("<6sHI6I4I2I")
 _SEGS = struct.Struct("<I")
+_RES = struct.Struct("<II")                                                # version 4: max_error, res_bands
 _LEN = struct.Struct("<Q")
 
 
@@ -124,13 +135,28 @@ def _model_shape(model):
     return int(model.N), int(model.M), int(in_ch), int(bool(getattr(model, "spatial_params", False)))
 
 
-def pack_image_stream(header: dict, blobs) -> bytes:
+def pack_image_stream(header: dict, blobs, residuals=None) -> bytes:
     """header (the fields unpack_image_stream returns) + the DSIC2 containers -> the stream (pure Python).  A header
     with "segments" = K > 1 writes version 2, whose containers are DSIC3 with that K; one with "overlap" = O > 0
-    writes version 3 (segments word, then overlap word), whose containers are DSIC2 for K = 1 and DSIC3 otherwise."""
+    writes version 3 (segments word, then overlap word), whose containers are DSIC2 for K = 1 and DSIC3 otherwise.
+    A header with "max_error" = tau (not None) writes version 4: segments word, overlap word 0, max_error, res_bands,
+    and behind every container its residual block from `residuals` (residual.pack_block)."""
     h = header
     K = entropy.check_segments(h.get("segments", 1), h["M"], "pack_image_stream")
     O = _check_overlap(h.get("overlap", 0), h["th"], h["tw"], "pack_image_stream")
+    if h.get("max_error") is not None:
+        tau = _residual.check_max_error(h["max_error"], "pack_image_stream")
+        if O:
+            raise ValueError("pack_image_stream: max_error together with overlap > 0 is not supported")
+        if residuals is None or len(residuals) != len(blobs):
+            raise ValueError("pack_image_stream: max_error needs one residual block per container")
+        head = _HEAD.pack(MAGIC, VERSION_RES, h["numerics"] & 0xFFFFFFFF, h["H"], h["W"], h["C"], h["kind"], h["th"],
+                          h["tw"], h["N"], h["M"], h["in_ch"], h["spatial_params"], h["batch"], len(blobs))
+        head += _SEGS.pack(K) + _SEGS.pack(0) + _RES.pack(tau, _residual.BANDS)
+        return b"".join([head] + [_LEN.pack(len(b)) + bytes(b) + _LEN.pack(len(r)) + bytes(r)
+                                  for b, r in zip(blobs, residuals)])
+    if residuals is not None:
+        raise ValueError("pack_image_stream: residual blocks without max_error in the header")
     head = _HEAD.pack(MAGIC, VERSION_OV if O else (VERSION_SEG if K > 1 else VERSION), h["numerics"] & 0xFFFFFFFF,
                       h["H"], h["W"], h["C"], h["kind"], h["th"], h["tw"], h["N"], h["M"], h["in_ch"],
                       h["spatial_params"], h["batch"], len(blobs))
@@ -172,8 +198,8 @@ class _Source:
 
 
 def _read_framing(src):
-    """The DSICI head and the length words of a _Source -> (header fields, (offset, bytes) of every batch); what
-    lies inside the batches is not read."""
+    """The DSICI head and the length words of a _Source -> (header fields, (offset, bytes) of every batch's container,
+    the same of every batch's residual block: empty below version 4); what lies inside them is not read."""
     head = src.read_at(0, _HEAD.size)
     if len(head) < _HEAD.size:
         raise ValueError("truncated DSICI stream" if head[:6] == MAGIC[:len(head)] else "not a DSICI image stream")
@@ -183,12 +209,12 @@ def _read_framing(src):
     keys = ("version", "numerics", "H", "W", "C", "kind", "th", "tw", "N", "M", "in_ch", "spatial_params", "batch",
             "batches")
     h = dict(zip(keys, f[1:]))
-    if h["version"] not in (VERSION, VERSION_SEG, VERSION_OV):
-        raise ValueError(f"DSICI stream version {h['version']}, this reader knows {VERSION}, {VERSION_SEG} and "
-                         f"{VERSION_OV}")
+    if h["version"] not in (VERSION, VERSION_SEG, VERSION_OV, VERSION_RES):
+        raise ValueError(f"DSICI stream version {h['version']}, this reader knows {VERSION}, {VERSION_SEG}, "
+                         f"{VERSION_OV} and {VERSION_RES}")
     off, h["segments"], h["overlap"] = _HEAD.size, 1, 0
-    if h["version"] in (VERSION_SEG, VERSION_OV):
-        words = 2 if h["version"] == VERSION_OV else 1
+    if h["version"] in (VERSION_SEG, VERSION_OV, VERSION_RES):
+        words = {VERSION_SEG: 1, VERSION_OV: 2, VERSION_RES: 4}[h["version"]]
         word = src.read_at(off, words * _SEGS.size)
         if len(word) < words * _SEGS.size:
             raise ValueError("truncated DSICI stream")
@@ -203,28 +229,41 @@ def _read_framing(src):
             if h["overlap"] == 0:
                 raise ValueError("DSICI stream: version 3 with overlap=0")
             _check_overlap(h["overlap"], h["th"], h["tw"], "DSICI stream")
-    frames = []
-    for _ in range(h["batches"]):
+        if h["version"] == VERSION_RES:
+            overlap, h["max_error"], bands = struct.unpack_from("<3I", word, _SEGS.size)
+            if overlap != 0:
+                raise ValueError(f"DSICI stream: version 4 with overlap={overlap} (a residual layer over blended "
+                                 "tiles is not supported)")
+            if bands != _residual.BANDS:
+                raise ValueError(f"DSICI stream: version 4 with res_bands={bands}, this reader knows "
+                                 f"{_residual.BANDS}")
+            if h["max_error"] > 127:
+                raise ValueError(f"DSICI stream: max_error={h['max_error']} (0 .. 127)")
+    frames, rframes = [], []
+    for k in range(h["batches"] * (2 if h["version"] == VERSION_RES else 1)):
         if off + _LEN.size > src.size:
             raise ValueError("truncated DSICI stream")
         (size,) = _LEN.unpack(src.read_at(off, _LEN.size))
         off += _LEN.size
         if off + size > src.size:
             raise ValueError("truncated DSICI stream")
-        frames.append((off, size))
+        (rframes if h["version"] == VERSION_RES and k % 2 else frames).append((off, size))
         off += size
     if off != src.size:
         raise ValueError(f"DSICI stream: {src.size - off} trailing bytes")
-    return h, frames
+    return h, frames, rframes
 
 
 def unpack_image_stream(stream) -> dict:
     """stream -> header fields (version, numerics, H, W, C, kind, th, tw, N, M, in_ch, spatial_params, batch,
     batches, segments: 1 for a version-1 stream, overlap: 0 for versions 1 and 2) and "blobs", the list of inner DSIC2 containers (pure Python).  ValueError on a wrong magic, a truncated
-    stream or trailing bytes."""
+    stream or trailing bytes.  A version-4 stream also gives "max_error" and "residuals", the list of its residual
+    blocks; the dicts of versions 1 to 3 have neither key."""
     s = bytes(stream)
-    h, frames = _read_framing(_Source(s))
+    h, frames, rframes = _read_framing(_Source(s))
     h["blobs"] = [s[off:off + size] for off, size in frames]
+    if h["version"] == VERSION_RES:
+        h["residuals"] = [s[off:off + size] for off, size in rframes]
     return h
 
 
@@ -254,14 +293,19 @@ def _gather(img, kind, g, C, first, n):
 
 
 @torch.no_grad()
-def compress_image(model, img, tile=256, batch=64, tail=10, segments=1, overlap=0) -> bytes:
+def compress_image(model, img, tile=256, batch=64, tail=10, segments=1, overlap=0, max_error=None) -> bytes:
     """img: uint8 [H,W,C] or float32 [C,H,W] in [0,1], on the CPU or the GPU -> one DSICI stream.  The image is
     uploaded once; each batch of `batch` tiles is gathered on the device (reflect padding included) and becomes one
     DSIC2 container.  segments = K > 1 (1, 2, 4, 8 or 16, dividing M): every tile's y string is K independent strings
     (DSIC3 containers, stream version 2), which the decoders read on K waves per tile; the decoded image is the same.
     overlap = O > 0 (a multiple of 16, at most half a tile side): tiles share O pixels with their neighbours
-    (tile_grid) and the decoders cross-fade them over that band (stream version 3); 0 writes today's streams."""
+    (tile_grid) and the decoders cross-fade them over that band (stream version 3); 0 writes today's streams.
+    max_error = tau (an integer 0 .. 127; uint8 images, overlap = 0): the near-lossless mode (stream version 4).
+    Behind every container, byte for byte the one written without max_error, goes a residual block (residual.py),
+    and the decoders return a uint8 image within tau of img on every pixel and channel; 0 is lossless.  None writes
+    today's streams."""
     dev = next(model.parameters()).device
+    tau = None if max_error is None else _residual.check_max_error(max_error, "compress_image")
     if img.dim() != 3:
         raise ValueError(f"compress_image: expected uint8 [H,W,C] or float32 [C,H,W], got {tuple(img.shape)}")
     if img.dtype == torch.uint8:
@@ -279,14 +323,39 @@ def compress_image(model, img, tile=256, batch=64, tail=10, segments=1, overlap=
         raise ValueError(f"compress_image: batch={batch}")
     g = tile_grid(H, W, tile, overlap)
     overlap = _check_overlap(overlap, g["th"], g["tw"], "compress_image")
+    if tau is not None:
+        if kind != KIND_U8_HWC:
+            raise ValueError("compress_image: max_error bounds the error of integer pixel values; pass the image as "
+                             "uint8 [H,W,C], not float32")
+        if overlap:
+            raise ValueError("compress_image: max_error together with overlap > 0 is not supported (the predictor "
+                             "would be the blended image)")
     x = img.to(dev).contiguous()
-    blobs = []
+    blobs, residuals = [], None if tau is None else []
     for first in range(0, g["n"], batch):
-        tiles = _gather(x, kind, g, C, first, min(batch, g["n"] - first))
-        blobs.append(entropy.compress_to_container(model, tiles, tail, segments=segments))
+        n = min(batch, g["n"] - first)
+        tiles = _gather(x, kind, g, C, first, n)
+        if tau is None:
+            blobs.append(entropy.compress_to_container(model, tiles, tail, segments=segments))
+            continue
+        # compress_to_container's work, keeping the forward x_hat: the predictor the decoder will have bit for bit
+        c = entropy._coded_batch(model, tiles, tail, entropy.DEFAULT_LMAX, "compress_image", pack=True,
+                                 segments=segments)
+        blobs.append(c["container"][:c["container_bytes"]].cpu().numpy().tobytes())
+        residuals.append(_residual.encode_block(tiles, c["x_hat"], [_owned_in_tile(g, t)
+                                                                   for t in range(first, first + n)], tau))
     header = {"numerics": entropy.numerics_tag(), "H": H, "W": W, "C": C, "kind": kind, "th": g["th"], "tw": g["tw"],
               "N": N, "M": M, "in_ch": in_ch, "spatial_params": spatial, "batch": batch, "segments": segments, "overlap": overlap}
-    return pack_image_stream(header, blobs)
+    if tau is not None:
+        header["max_error"] = tau
+    return pack_image_stream(header, blobs, residuals)
+
+
+def _owned_in_tile(g, t):
+    """(y0, y1, x0, x1): the rows and columns of tile t, counted from its origin, that it owns inside the H x W image."""
+    i, j = divmod(t, g["nx"])
+    (a, b), (c, d) = g["own_y"][i], g["own_x"][j]
+    return a - g["ys"][i], min(b, g["H"]) - g["ys"][i], c - g["xs"][j], min(d, g["W"]) - g["xs"][j]
 
 
 def _refuse_foreign(model, h, what):
@@ -333,7 +402,7 @@ def _out_image(kind, C, h, w, dev, what):
 # ---- decode: any window of an image stream from only its tiles; the whole image is the window (0, 0, H, W) ------
 def _index_of(src):
     """stream_index on an open _Source."""
-    ix, frames = _read_framing(src)
+    ix, frames, rframes = _read_framing(src)
     g = _stream_grid(ix)
     tiles, containers = [], []
     for k, (off, size) in enumerate(frames):
@@ -357,6 +426,12 @@ def _index_of(src):
                           "z_off": z_off, "z_len": z_len, "y_off": y_off, "y_len": y_len, "y_segs": seg[b]})
         containers.append({"offset": off, "bytes": size, "first": first, "tiles": len(images), "shape_y": shape_y,
                            "shape_z": shape_z})
+        if rframes:
+            recs = _residual.read_block_head(src.read_at, rframes[k][0], rframes[k][1], len(images), ix["C"],
+                                             ix["th"], ix["tw"], ix["max_error"])
+            for tile, rec in zip(tiles[first:], recs):
+                tile.update(rec)
+            containers[-1].update(r_offset=rframes[k][0], r_bytes=rframes[k][1])
     ix.update(grid=g, tiles=tiles, containers=containers, stream_bytes=src.size, index_bytes=src.bytes_read)
     return ix
 
@@ -373,6 +448,10 @@ def stream_index(src) -> dict:
                    max_z, z_off, z_len, y_off, y_len (absolute byte offsets and lengths of its two strings), y_segs
                    (the lengths of the y string's segments, back to back from y_off; [y_len] for segments = 1)
       containers   per batch: offset, bytes, first (tile), tiles, shape_y, shape_z
+    and for a version-4 stream (only then) max_error; per tile r_off, r_len (its span in the batch's residual block:
+    C x r_L table entries, then 16 strings), r_smin, r_L (the residual's support) and r_segs (the 16 string lengths);
+    per batch r_offset, r_bytes (the block).  Of a residual block the 30-byte head, the 12-byte records and the 64
+    bytes of segment lengths per tile are read.
       stream_bytes, index_bytes (what this call read).
     ValueError as unpack_image_stream, entropy.unpack_container and decompress_image raise it: wrong magic or version,
     DSIC1 container, truncated stream or container, trailing bytes, batches that do not match the grid, latents that
@@ -401,8 +480,9 @@ def window_tiles(index_or_grid, y0, x0, h, w) -> list:
 
 
 def tile_spans(index, tiles) -> list:
-    """Byte ranges (offset, length) of the stream that hold the strings of the given tiles: ascending, ranges that
-    touch merged into one, empty strings dropped (pure Python)."""
+    """Byte ranges (offset, length) of the stream that hold the strings of the given tiles (in a version-4
+    stream also their residual spans): ascending, ranges that touch merged into one, empty strings dropped (pure
+    Python)."""
     parts = []
     for t in tiles:
         r = index["tiles"][t]
@@ -410,6 +490,8 @@ def tile_spans(index, tiles) -> list:
             parts.append((r["z_off"], r["z_len"]))
         if r["y_len"]:
             parts.append((r["y_off"], r["y_len"]))
+        if r.get("r_len"):
+            parts.append((r["r_off"], r["r_len"]))
     parts.sort()
     spans = []
     for off, n in parts:
@@ -435,7 +517,8 @@ def _decode_window(model, src, window, out, batch, stats, what):
     y0, x0, h, w = int(y0), int(x0), int(h), int(w)
     batch = ix["batch"] if batch is None else batch
     kind = {None: ix["kind"], "u8": KIND_U8_HWC, "f32": KIND_F32_CHW}[out]
-    img, suffix = _out_image(kind, C, h, w, next(model.parameters()).device, what)
+    tau = ix.get("max_error")                  # a residual layer: the result is the uint8 image, converted for "f32"
+    img, suffix = _out_image(KIND_U8_HWC if tau is not None else kind, C, h, w, next(model.parameters()).device, what)
     L, O = _lib.load(), ix["overlap"]
     fn = getattr(L, "dsic_tile_stitch_window_" + suffix)
     if O:       # the window's float32 canvas, zeroed: the output itself, or a temporary that the finish turns to uint8
@@ -445,18 +528,37 @@ def _decode_window(model, src, window, out, batch, stats, what):
     for first in range(0, len(tiles), batch):
         sel = tiles[first:first + batch]
         n = len(sel)
-        # ascending tiles lie in ascending stream order, so back to back their strings are the spans back to back
-        images, pos = [], 0
-        for r in (ix["tiles"][t] for t in sel):
-            images.append((r["min_y"], r["max_y"], r["min_z"], r["max_z"], pos, r["z_len"], pos + r["z_len"],
-                           r["y_len"]))
-            pos += r["z_len"] + r["y_len"]
-        parts = [source.read_at(off, length) for off, length in tile_spans(ix, sel)]
-        x_hat, nbytes, ids = entropy._decode_selected(model, images, parts, [n, ix["M"], th // 16, tw // 16],
-                                                      [n, N, Hz, Wz], what, ride=sel, segments=ix["segments"],
-                                                      seg_lengths=[ix["tiles"][t]["y_segs"] for t in sel])
+        # the upload is the tiles' spans back to back: a string at stream offset o lies where its span does
+        spans = tile_spans(ix, sel)
+        starts, base = [off for off, _ in spans], [0]
+        for _, length in spans:
+            base.append(base[-1] + length)
+
+        def at(off, length):
+            i = bisect.bisect_right(starts, off) - 1
+            return base[i] + off - starts[i] if length else 0
+
+        recs = [ix["tiles"][t] for t in sel]
+        images = [(r["min_y"], r["max_y"], r["min_z"], r["max_z"], at(r["z_off"], r["z_len"]), r["z_len"],
+                   at(r["y_off"], r["y_len"]), r["y_len"]) for r in recs]
+        parts = [source.read_at(off, length) for off, length in spans]
+        spec = None
+        if tau is not None:
+            for r in recs:                     # the tables as they arrived, before anything is uploaded
+                i = bisect.bisect_right(starts, r["r_off"]) - 1
+                a = r["r_off"] - starts[i]
+                _residual.check_tables(parts[i][a:a + 2 * C * r["r_L"]], C, r["r_L"], tau)
+            spec = {"C": C, "th": th, "tw": tw, "tau": tau, "smin": [r["r_smin"] for r in recs],
+                    "L": [r["r_L"] for r in recs], "segs": [r["r_segs"] for r in recs],
+                    "desc": [(at(r["r_off"], r["r_len"]), 2 * C * r["r_L"],
+                              at(r["r_off"], r["r_len"]) + 2 * C * r["r_L"], sum(r["r_segs"])) for r in recs]}
+        x_hat, nbytes, ids, *q = entropy._decode_selected(model, images, parts, [n, ix["M"], th // 16, tw // 16],
+                                                          [n, N, Hz, Wz], what, ride=sel, segments=ix["segments"],
+                                                          seg_lengths=[r["y_segs"] for r in recs], residual=spec)
         x_hat = x_hat.contiguous()
-        if O:
+        if q:
+            _residual.stitch_window_u8(x_hat, q[0], tau, ids, img, H, W, C, th, tw, y0, x0, h, w)
+        elif O:
             for c0 in range(0, n, BLEND_IDS):
                 _lib.check(L.dsic_tile_blend_window_f32(_p(x_hat[c0:]), _p(ids[c0:]), min(BLEND_IDS, n - c0),
                                                         _p(canvas), H, W, C, th, tw, O, y0, x0, h, w, _stream()),
@@ -473,6 +575,8 @@ def _decode_window(model, src, window, out, batch, stats, what):
     if stats is not None:
         stats.update(tiles=tiles, decode_batches=decode_batches, bytes_read=source.bytes_read,
                      bytes_uploaded=uploaded)
+    if tau is not None and kind == KIND_F32_CHW:
+        return (img.permute(2, 0, 1).to(torch.float32) / 255).contiguous()
     return img
 
 
@@ -483,7 +587,8 @@ def decompress_image(model, stream, out=None):
     out="u8" / "f32" overrides it.  The whole image as a window, decoded container by container; each decoded batch
     is stitched straight into the image.  A stream with overlap (version 3) is blended instead: each decoded batch
     is added into a zeroed float32 canvas (the output itself for float32) with the tiles' ramp weights, and a finishing
-    pass takes min(v, 1) and, for uint8, (uint8)(v*255)."""
+    pass takes min(v, 1) and, for uint8, (uint8)(v*255).  A near-lossless stream (version 4) decodes to the uint8 image
+    clamp(p + q s, 0, 255) of residual.py, within max_error of the original; out="f32" returns that image / 255."""
     return _decode_window(model, stream, None, out, None, None, "decompress_image")
 
 

@@ -13,7 +13,7 @@
 // support is [a(i), a(i+1) + O), the last one's [a(n-1), P).  Over the first O positions of a support (i > 0) the
 // tile's weight ramps up as (2k+1)/(2O), over [a(i+1), a(i+1) + O) it ramps down as (2(O-1-k)+1)/(2O), elsewhere in
 // the support it is 1: at every position the weights of at most two tiles per axis sum to 1.  O = 0 is the grid above.
-#include "common.h"
+#include "byte_movers.h"
 
 namespace dsic {
 
@@ -37,60 +37,6 @@ static Grid make_grid(int H, int W, int th, int tw, int O = 0) {
 
 // reflect without repeating the edge (layout.hip reflect_pad_br_kernel); p < 2H-1 by the padding precondition
 __device__ __forceinline__ int reflect(int p, int n) { return p < n ? p : 2 * (n - 1) - p; }
-
-// 16 bytes from any address: aligned dword loads funnelled by __builtin_amdgcn_alignbyte.  The dwords read
-// start at the aligned-down address of p and end at the dword holding p[15], so no byte outside the
-// allocation's dwords is touched.
-__device__ __forceinline__ uint4 load16_any(const uint8_t* p) {
-  const uintptr_t a = (uintptr_t)p;
-  if ((a & 15) == 0) return *(const uint4*)p;
-  const int sh = a & 3;
-  const uint32_t* w = (const uint32_t*)(a - sh);
-  const uint32_t w0 = w[0], w1 = w[1], w2 = w[2], w3 = w[3];
-  if (sh == 0) return make_uint4(w0, w1, w2, w3);
-  const uint32_t w4 = w[4];
-  return make_uint4(__builtin_amdgcn_alignbyte(w1, w0, sh), __builtin_amdgcn_alignbyte(w2, w1, sh),
-                    __builtin_amdgcn_alignbyte(w3, w2, sh), __builtin_amdgcn_alignbyte(w4, w3, sh));
-}
-
-// n bytes src -> dst (any alignments), split over `parts` workgroups of blockDim.x threads: the destination's
-// aligned 16-byte chunks are whole dwordx4 stores, the ragged head and tail are byte stores (their neighbours
-// belong to another string or to the header and are written by another workgroup).
-__device__ void copy_bytes(uint8_t* dst, const uint8_t* src, int64_t n, int part, int parts) {
-  if (n <= 0) return;
-  int64_t head = (16 - ((uintptr_t)dst & 15)) & 15;
-  if (head > n) head = n;
-  const int64_t nfull = (n - head) >> 4;
-  const int64_t tail = head + 16 * nfull;
-  if (part == 0) {
-    for (int64_t i = threadIdx.x; i < head; i += blockDim.x) dst[i] = src[i];
-    for (int64_t i = tail + threadIdx.x; i < n; i += blockDim.x) dst[i] = src[i];
-  }
-  for (int64_t c = (int64_t)part * blockDim.x + threadIdx.x; c < nfull; c += (int64_t)parts * blockDim.x)
-    *(uint4*)(dst + head + 16 * c) = load16_any(src + head + 16 * c);
-}
-
-// exclusive prefix sum over a 256-thread workgroup; *total = sum of all v
-__device__ long long block_exclusive_scan(long long v, long long* lds4, long long* total) {
-  const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
-  long long s = v;
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) {
-    const long long t = __shfl_up(s, o, 64);
-    if (lane >= o) s += t;
-  }
-  if (lane == 63) lds4[wid] = s;
-  __syncthreads();
-  long long base = 0, tot = 0;
-#pragma unroll
-  for (int w = 0; w < 4; ++w) {
-    base += w < wid ? lds4[w] : 0;
-    tot += lds4[w];
-  }
-  __syncthreads();
-  *total = tot;
-  return base + s - v;
-}
 
 // ---- tile gather ------------------------------------------------------------------------------------------
 
@@ -146,8 +92,6 @@ __global__ __launch_bounds__(256) void gather_f32_kernel(const float* __restrict
 }
 
 // ---- tile stitch ------------------------------------------------------------------------------------------
-
-__device__ __forceinline__ float clamp01(float v) { return v < 0.f ? 0.f : (v > 1.f ? 1.f : v); }  // torch clamp(0,1)
 
 // the owned part of tile t in image coordinates: rows [y0,y1), columns [x0,x1); (oy, ox) its origin
 struct Owned {
@@ -206,10 +150,13 @@ __global__ __launch_bounds__(256) void stitch_f32_kernel(const float* __restrict
   }
 }
 
-// tiles [n][C][th][tw] -> (uint8)(clamp(x,0,1) * 255) into the uint8 HWC window image
+// tiles [n][C][th][tw] -> p = (uint8)(clamp(x,0,1) * 255) into the uint8 HWC window image.  RES (near-lossless
+// streams, residual.hip): q [n][C][th][tw] holds the tile's integer residual steps and the pixel is
+// clamp(p + q * s, 0, 255), s = 2 tau + 1.
+template <bool RES>
 __global__ __launch_bounds__(256) void stitch_u8_kernel(const float* __restrict__ tiles, uint8_t* __restrict__ img,
                                                         Grid g, int C, int first, const int* __restrict__ ids,
-                                                        Clip w) {
+                                                        Clip w, const float* __restrict__ q, int s) {
   Owned o;
   if (!stitch_rect(g, ids, first, w, &o)) return;
   const int ya = o.y0 + blockIdx.x * kTileRows;
@@ -228,6 +175,7 @@ __global__ __launch_bounds__(256) void stitch_u8_kernel(const float* __restrict_
     if (q0 >= b1) continue;
     const int64_t lo = max(q0, b0), hi = min(q0 + 16, b1);
     const float* srow = src + (size_t)(y - o.oy) * g.tw;
+    const float* qrow = RES ? q + (size_t)blockIdx.y * C * cplane + (size_t)(y - o.oy) * g.tw : nullptr;
     int px = (int)((lo - b0) / C), c = (int)((lo - b0) - (int64_t)px * C);
     px += o.x0 - o.ox;  // column within the tile
     uint8_t b[16];
@@ -236,6 +184,10 @@ __global__ __launch_bounds__(256) void stitch_u8_kernel(const float* __restrict_
       b[e] = 0;
       if (q0 + e >= lo && q0 + e < hi) {
         b[e] = (uint8_t)(clamp01(srow[c * cplane + px]) * 255.0f);
+        if (RES) {
+          const int v = (int)b[e] + (int)qrow[c * cplane + px] * s;
+          b[e] = (uint8_t)(v < 0 ? 0 : (v > 255 ? 255 : v));
+        }
         if (++c == C) c = 0, ++px;
       }
     }
@@ -415,9 +367,6 @@ __host__ __device__ inline int64_t body_offset(int B, int K) {
   return head_bytes(K) + (int64_t)kRecBytes * B + (K > 1 ? (int64_t)4 * B * K : 0);
 }
 
-__device__ __forceinline__ void put_u32(uint8_t* p, int byte, uint32_t v) { *p = (uint8_t)(v >> (8 * byte)); }
-__device__ __forceinline__ int64_t clamp_len(int v, int64_t cap) { return v < 0 ? 0 : (v > cap ? cap : v); }
-
 // one workgroup: header, records, exclusive scan of the B (1 + K) string lengths (z0, y0 segments, z1, ...) into
 // ws[2..2+B(1+K)]; ws[0] = container bytes, ws[1] = the coder's error word.  lengths [B][1 + K], cap_y the capacity of
 // one y segment; K = 1 writes DSIC2.
@@ -548,11 +497,6 @@ __global__ __launch_bounds__(256) void scatter_select_kernel(const uint8_t* __re
   copy_bytes((which ? ybuf : zbuf) + (size_t)b * stride, blob + off, n, blockIdx.x, gridDim.x);
 }
 
-static int string_parts(int64_t max_len) {
-  const int64_t p = (max_len + 16 * 256 - 1) / (16 * 256);
-  return (int)(p < 1 ? 1 : (p > 8 ? 8 : p));
-}
-
 static const char* grid_error(int H, int W, int th, int tw) {
   if (H <= 0 || W <= 0) return "empty image";
   if (th < 32 || tw < 32 || th % 16 || tw % 16) return "tile sides must be multiples of 16, at least 32";
@@ -638,8 +582,8 @@ extern "C" int dsic_tile_stitch_u8(const float* tiles, uint8_t* img_hwc, int H, 
   DSIC_REQUIRE(C == 3 || C == 4, "tile_stitch_u8: C=%d must be 3 or 4", C);
   DSIC_TILE_ARGS("tile_stitch_u8");
   DSIC_REQUIRE(((uintptr_t)img_hwc & 15) == 0, "tile_stitch_u8: image must be 16-byte aligned");
-  hipLaunchKernelGGL(stitch_u8_kernel, grid, dim3(256), 0, (hipStream_t)stream, tiles, img_hwc, g, C, first_tile,
-                     (const int*)nullptr, Clip{0, H, 0, W});
+  hipLaunchKernelGGL(stitch_u8_kernel<false>, grid, dim3(256), 0, (hipStream_t)stream, tiles, img_hwc, g, C,
+                     first_tile, (const int*)nullptr, Clip{0, H, 0, W}, (const float*)nullptr, 1);
   return check_launch("tile_stitch_u8");
 }
 
@@ -672,8 +616,22 @@ extern "C" int dsic_tile_stitch_window_u8(const float* tiles, const int* tile_id
   DSIC_REQUIRE(C == 3 || C == 4, "tile_stitch_window_u8: C=%d must be 3 or 4", C);
   DSIC_WINDOW_ARGS("tile_stitch_window_u8");
   DSIC_REQUIRE(((uintptr_t)out & 15) == 0, "tile_stitch_window_u8: out must be 16-byte aligned");
-  hipLaunchKernelGGL(stitch_u8_kernel, grid, dim3(256), 0, (hipStream_t)stream, tiles, out, g, C, 0, tile_ids, clip);
+  hipLaunchKernelGGL(stitch_u8_kernel<false>, grid, dim3(256), 0, (hipStream_t)stream, tiles, out, g, C, 0, tile_ids,
+                     clip, (const float*)nullptr, 1);
   return check_launch("tile_stitch_window_u8");
+}
+
+extern "C" int dsic_tile_stitch_window_u8_res(const float* tiles, const float* q, int tau, const int* tile_ids,
+                                              int n_tiles, uint8_t* out, int H, int W, int C, int th, int tw, int wy0,
+                                              int wx0, int wh, int ww, void* stream) {
+  DSIC_REQUIRE(tiles && q && tile_ids && out, "tile_stitch_window_u8_res: null pointer");
+  DSIC_REQUIRE(C == 3 || C == 4, "tile_stitch_window_u8_res: C=%d must be 3 or 4", C);
+  DSIC_REQUIRE(tau >= 0 && tau <= 127, "tile_stitch_window_u8_res: tau=%d must be in 0..127", tau);
+  DSIC_WINDOW_ARGS("tile_stitch_window_u8_res");
+  DSIC_REQUIRE(((uintptr_t)out & 15) == 0, "tile_stitch_window_u8_res: out must be 16-byte aligned");
+  hipLaunchKernelGGL(stitch_u8_kernel<true>, grid, dim3(256), 0, (hipStream_t)stream, tiles, out, g, C, 0, tile_ids,
+                     clip, q, 2 * tau + 1);
+  return check_launch("tile_stitch_window_u8_res");
 }
 
 extern "C" int dsic_tile_blend_window_f32(const float* tiles, const int* tile_ids, int n_tiles, float* canvas, int H,

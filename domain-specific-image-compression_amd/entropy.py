@@ -316,6 +316,7 @@ def _coded_batch(model, x, tail, Lmax, what, pack=False, segments=1):
     while True:
         c = compress_latents(out["y_tilde"], out["z_tilde"], _per_channel(out["sigma"]),
                              _per_channel(out["nu"]), sigma_z, tail, Lmax, segments=segments)
+        c["x_hat"] = out["x_hat"]                                      # the forward reconstruction (codec's residual layer)
         if pack:
             c["container"], c["container_bytes"], code = _pack_on_device(c, numerics_tag())
         else:
@@ -608,7 +609,8 @@ def _upload_padded(parts, tail, dev):
     return d[:padded], total, d[padded:]
 
 
-def _decode_selected(model, images, parts, shape_y, shape_z, what, Lmax=None, ride=None, segments=1, seg_lengths=None):
+def _decode_selected(model, images, parts, shape_y, shape_z, what, Lmax=None, ride=None, segments=1, seg_lengths=None,
+                     residual=None):
     """One decode batch from the strings of n images picked anywhere: images as read_container_head gives them, with
     z_off / y_off counted inside the byte strings `parts` laid back to back; shape_y / shape_z = [n, channels, h, w].
     The strings travel in one padded copy with an int64 control block behind them: descriptors [n][4] (z offset, z
@@ -616,13 +618,16 @@ def _decode_selected(model, images, parts, shape_y, shape_z, what, Lmax=None, ri
     seg_lengths (per image the lengths of its y segments, which lie back to back in its y string), then the int32
     array `ride` (codec's tile numbers).  The device spreads the strings at custom_decompress's strides (_upload_strings) and decodes with Lmax
     (default: _default_lmax over these images).  Returns (g_s's output, not yet clamped; the padded string bytes
-    uploaded; the device copy of ride)."""
+    uploaded; the device copy of ride).
+    residual (codec's near-lossless streams): the spec of residual.decode_q, whose spans lie in `parts` beside the
+    strings; its control words travel behind ride in the same copy, and the tuple gains the decoded q planes."""
     dev = next(model.parameters()).device
     n = len(images)
     rec = np.array(images, dtype=np.int64).reshape(n, 8)
     ride = np.zeros(0, dtype=np.int32) if ride is None else np.asarray(ride, dtype=np.int32)
     nseg = n * segments if segments > 1 else 0
-    block = np.zeros(6 * n + (nseg + ride.size + 1) // 2, dtype=np.int64)
+    tail_words = (nseg + ride.size + 1) // 2
+    block = np.zeros(6 * n + tail_words, dtype=np.int64)
     block[:4 * n] = rec[:, 4:].ravel()
     meta_np = block[4 * n:6 * n].view(np.int32).reshape(n, 4)
     meta_np[:, 0::2] = rec[:, 0:4:2]
@@ -630,6 +635,9 @@ def _decode_selected(model, images, parts, shape_y, shape_z, what, Lmax=None, ri
     if nseg:
         block[6 * n:].view(np.int32)[:nseg] = np.asarray(seg_lengths, dtype=np.int32).reshape(nseg)
     block[6 * n:].view(np.int32)[nseg:nseg + ride.size] = ride
+    if residual is not None:
+        from . import residual as _residual
+        block = np.concatenate([block, _residual.control_words(residual)])
     d_blob, total, d_block = _upload_padded(parts, block, dev)
     d_block = d_block.view(torch.int64)
     meta = d_block[4 * n:6 * n].view(torch.int32).view(n, 4)
@@ -643,9 +651,12 @@ def _decode_selected(model, images, parts, shape_y, shape_z, what, Lmax=None, ri
                "strings_scatter_select")
     if Lmax is None:
         Lmax = _default_lmax(model, meta_np)
-    tail32 = d_block[6 * n:].view(torch.int32)
+    tail32 = d_block[6 * n:6 * n + tail_words].view(torch.int32)
     x_hat = _decode_batch(model, shape_y, shape_z, meta, Lmax, (zbuf, zstride, lengths, 2, 0),
                           (ybuf, ystride, lengths, 2, 1), what, segments, tail32[:nseg] if nseg else None)
+    if residual is not None:
+        q = _residual.decode_q(d_blob, total, d_block[6 * n + tail_words:], residual)
+        return x_hat, _padded_bytes(total), tail32[nseg:nseg + ride.size], q
     return x_hat, _padded_bytes(total), tail32[nseg:nseg + ride.size]
 
 

@@ -533,6 +533,48 @@ int dsic_tile_blend_finish_f32(float* canvas, int C, int h, int w, void* stream)
 int dsic_tile_blend_finish_u8(const float* canvas, uint8_t* out_hwc, int C, int h, int w,
                               void* stream);
 
+/* ---- near-lossless residual layer (codec.compress_image with max_error = tau, 0..127) ----
+ * Per tile, with x the gathered uint8 tile [th][tw][C] (C 3 or 4) and x_hat the encoder's
+ * forward reconstruction float32 [C][th][tw]:
+ *   p = (uint8)(clamp(x_hat,0,1)*255)  (float32, truncating: the uint8 stitch's value),
+ *   r = x - p, s = 2 tau + 1, q = sign(r) * floor((|r| + tau) / s), |q| <= Q = (255 + tau) / s,
+ *   q = 0 outside the rectangle the tile owns; the decoder writes clamp(p + q s, 0, 255), which
+ *   lies within tau of x.  All integer.
+ * residual_quantize_u8: tiles uint8 [n][th][tw][C], x_hat float32 [n][C][th][tw], own int32
+ *   [n][4] = the owned rows [y0, y1) and columns [x0, x1) in tile coordinates -> q float32
+ *   [n][C][th][tw] and hist int32 [n][C][512], to which the count of every pixel of the tile is
+ *   ADDED at bin q + Q (the caller zeroes it).  tiles, x_hat, q 16-byte aligned; th, tw
+ *   multiples of 16; n in 1..3000.
+ * residual_tables: hist -> meta int32 [n][4] = (smin, L, 0, 1): the support [smin, smin + L) =
+ *   min .. max of q over all channels of the tile in the y slots of the coder's meta, and the
+ *   support of a one-symbol dummy string in the z slots; per (tile, channel) the table
+ *   c[k] = floor(cum[k] * (65536 - L) / (th*tw)) + k, k < L (64-bit integers, cum the exclusive
+ *   prefix sum of the channel's histogram over the support; c[L] = 65536 is implicit), entries
+ *   k >= L written as 0, as compact uint16 [n][C][Lmax] and replicated to the 16 row bands of
+ *   the channel in coder uint16 [n][C*16][Lmax]; both 16-byte aligned.  Lmax = ceil8(2 Q + 1).
+ *   The q planes are coded by dsic_range_encode_seg_ws as its y family: M = C*16 channels of
+ *   HWy = (th/16)*tw symbols, 16 segments, with a dummy z family of one symbol 0 (N = HWz = 1,
+ *   a one-entry table 0) whose string is dropped.
+ * residual_pack: the residual block of a batch from that call's outputs (bytes
+ *   [n][cap_z + 16*cap_seg], lengths [n][17]; err may be NULL): "DSICR\0" | n, C, th, tw, tau,
+ *   16 u32 | n x (smin i32, L u32, span_bytes u32) | n x 16 u32 segment lengths | per tile its
+ *   span: C x L uint16 table entries, then the 16 segment strings.  out holds at least
+ *   30 + 76*n + n*(2*C*Lmax + 16*cap_seg) bytes; workspace: (C+16)*n + 3 int64, [0] = block
+ *   bytes, [1] = *err.
+ * tile_stitch_window_u8_res: dsic_tile_stitch_window_u8 with q float32 [n][C][th][tw] (the decoded
+ *   residual steps) added: a pixel is clamp(p + (int)q * (2 tau + 1), 0, 255). */
+int dsic_residual_quantize_u8(const uint8_t* tiles, const float* x_hat, const int* own, int n,
+                              int C, int th, int tw, int tau, float* q, int* hist, void* stream);
+int dsic_residual_tables(const int* hist, int n, int C, int th, int tw, int tau, int Lmax,
+                         int* meta, uint16_t* compact, uint16_t* coder, void* stream);
+int dsic_residual_pack(const uint8_t* bytes, int64_t cap_z, int64_t cap_seg, const int* lengths,
+                       const int* meta, const uint16_t* compact, const int* err, int n, int C,
+                       int th, int tw, int tau, int Lmax, int64_t* workspace, uint8_t* out,
+                       void* stream);
+int dsic_tile_stitch_window_u8_res(const float* tiles, const float* q, int tau,
+                                   const int* tile_ids, int n, uint8_t* out, int H, int W, int C,
+                                   int th, int tw, int wy0, int wx0, int wh, int ww, void* stream);
+
 /* HIP stream limited to the CUs whose bit is set in mask_host[words] (bit i of
  * word i/32 = CU i).  Used to give the range coder its own few CUs beside the
  * conv kernels; there is no reference counterpart (the reference is

@@ -1,13 +1,15 @@
 """Compress an image of any size to one DSICI stream, or decompress a stream back to an image.
 
     python tools/dsic_image.py compress   --weights CKPT.pt IN.png  OUT.dsic [--tile 256] [--batch 64] [--segments K] [--overlap O]
+                                          [--max-error T]
     python tools/dsic_image.py decompress --weights CKPT.pt IN.dsic OUT.png [--out u8|f32] [--region Y0,X0,H,W]
     python tools/dsic_image.py info       IN.dsic
 
 --segments K (2, 4, 8 or 16) codes every tile's y string as K independent strings, which a decoder reads on K waves per
 tile (a version-2 stream, a fraction of a percent larger; the decoded image is the same).  --overlap O (a multiple of
 16, at most half a tile side) makes neighbouring tiles share O pixels, which the decoder cross-fades (a version-3
-stream; more tiles, so more bytes).  --region decodes only the tiles that own the window's pixels and reads only their bytes of the file; info prints the
+stream; more tiles, so more bytes).  --max-error T (0 .. 127, uint8 images) adds the near-lossless residual layer (a
+version-4 stream): every decoded pixel lies within T of the original, 0 is lossless.  --region decodes only the tiles that own the window's pixels and reads only their bytes of the file; info prints the
 geometry, the tile grid and the bytes of every batch from the stream's heads, without a model or a GPU.
 
 The state dict is loaded plain or from under "model" (code/modelv2/eval_selfcontained_entropy.py:130-134); the model's
@@ -88,6 +90,10 @@ def print_info(ix):
           f"{ix['batches']} batch(es) of up to {ix['batch']}; heads {ix['index_bytes']} bytes")
     print(f"[dsic_image] stream version {ix['version']}, {ix['segments']} segment(s) per y string, "
           f"overlap {ix['overlap']}, stride {g['sy']}x{g['sx']}")
+    if ix.get("max_error") is not None:
+        res = sum(c["r_bytes"] for c in ix["containers"])
+        print(f"[dsic_image] near-lossless: max_error {ix['max_error']}, residual layer {res} bytes "
+              f"({8.0 * res / (ix['H'] * ix['W']):.4f} bpp), lossy layer {sum(c['bytes'] for c in ix['containers'])} bytes")
     for k, c in enumerate(ix["containers"]):
         pixels = 0
         for t in range(c["first"], c["first"] + c["tiles"]):
@@ -108,6 +114,8 @@ def main(argv=None):
     ap.add_argument("--tail", type=int, default=10)
     ap.add_argument("--segments", type=int, default=1, help="compress: y segments per tile (1, 2, 4, 8 or 16)")
     ap.add_argument("--overlap", type=int, default=0, help="compress: pixels neighbouring tiles share and cross-fade")
+    ap.add_argument("--max-error", type=int, default=None, metavar="T",
+                    help="compress: near-lossless, every decoded pixel within T (0 .. 127) of the original; 0 = lossless")
     ap.add_argument("--out", choices=("u8", "f32"), default=None, help="decoded kind (default: the encoder's input's)")
     ap.add_argument("--region", default=None, metavar="Y0,X0,H,W", help="decompress: only this window of the image")
     ap.add_argument("--min-nu", type=float, default=2.0)
@@ -132,13 +140,13 @@ def main(argv=None):
     if a.mode == "compress":
         img = read_image(a.src, codec._model_shape(model)[2])
         stream = codec.compress_image(model, img, tile=a.tile, batch=a.batch, tail=a.tail, segments=a.segments,
-                                      overlap=a.overlap)
+                                      overlap=a.overlap, max_error=a.max_error)
         with open(a.dst, "wb") as f:
             f.write(stream)
         h = codec.unpack_image_stream(stream)
         print(f"[dsic_image] {h['H']}x{h['W']}x{h['C']} -> {len(stream)} bytes, {codec.image_bpp(stream):.4f} bpp, "
               f"{h['batches']} batch(es) of {h['th']}x{h['tw']} tiles, {h['segments']} segment(s) per y string, "
-              f"overlap {h['overlap']}")
+              f"overlap {h['overlap']}" + (f", max_error {h['max_error']}" if "max_error" in h else ""))
     elif region is not None:
         stats = {}
         with open(a.src, "rb") as f:

@@ -22,6 +22,11 @@ Every figure is the best of --reps full passes over the scene after one warm-up 
           pixels).  With synthetic weights the seam figure shows the mechanism, not a trained model's quality.
           Written to profiles/overlap_bench.json (or --json).  Records, not bars.
 
+--max-error T[,T2...]  the near-lossless mode: the lossy stream and a stream of every T given, read alternately in one
+          run (medians of --reps readings): stream bytes split into the lossy and the residual layer, the worst pixel
+          error of the decode, compress_image / decompress_image and a one-tile decompress_region in ms.  Written to
+          profiles/near_lossless_bench.json (or --json).  Records, not bars.
+
 --region  decompress_region of the same stream for an aligned one-tile window, an unaligned 2 x 2-tile-sized window
           (9 tiles), an unaligned half-scene window and the whole image, beside decompress_image before and after
           them in the same run (the two readings show the run-to-run spread).  Records, not bars.
@@ -193,6 +198,49 @@ def overlap_records(model, img, a, overlaps):
     return res
 
 
+def near_lossless_records(model, img, a, taus):
+    """The lossy stream (None) and max_error = every tau of `taus`, alternately."""
+    import statistics
+    import torch
+    from dsic_amd import codec
+    t = a.tile
+    modes = [None] + list(taus)
+    streams = {m: codec.compress_image(model, img, tile=t, batch=a.batch, max_error=m) for m in modes}
+    lossy = codec.unpack_image_stream(streams[None])["blobs"]
+    jobs = {"compress_image": lambda m: codec.compress_image(model, img, tile=t, batch=a.batch, max_error=m),
+            "decompress_image": lambda m: codec.decompress_image(model, streams[m]),
+            "region_one_tile": lambda m: codec.decompress_region(model, streams[m], 4 * t, 4 * t, t, t, batch=a.batch)}
+    reads = {name: {m: [] for m in modes} for name in jobs}
+    for name, job in jobs.items():
+        for m in modes:
+            job(m)                                                     # warm-up
+        torch.cuda.synchronize()
+        for _ in range(a.reps):
+            for m in modes:
+                t0 = time.perf_counter()
+                job(m)
+                torch.cuda.synchronize()
+                reads[name][m].append(1e3 * (time.perf_counter() - t0))
+    res = {"what": "the lossy stream against near-lossless streams (max_error = tau), read alternately in one run on "
+                   "one MI355X; medians.  Synthetic weights: the lossy layer predicts poorly, so the residual bytes "
+                   "are an upper end, not a trained model's",
+           "scene": f"{a.size}x{a.size}x3 uint8", "tile": t, "batch": a.batch, "reps": a.reps, "modes": {}}
+    for m in modes:
+        u = codec.unpack_image_stream(streams[m])
+        out = codec.decompress_image(model, streams[m])
+        worst = int((out.to(torch.int16) - img.to(torch.int16)).abs().max())
+        rec = {"stream_bytes": len(streams[m]), "lossy_bytes": sum(len(b) for b in u["blobs"]),
+               "residual_bytes": sum(len(b) for b in u.get("residuals", [])), "bpp": round(codec.image_bpp(streams[m]), 4),
+               "max_abs_error": worst}
+        if m is not None:
+            assert u["blobs"] == lossy and worst <= m, "the near-lossless stream broke its contract"
+        for name in jobs:
+            med = statistics.median(reads[name][m])
+            rec[name] = {"ms_median": round(med, 3), "ms_all": [round(v, 3) for v in reads[name][m]]}
+        res["modes"]["lossy" if m is None else str(m)] = rec
+    return res
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--size", type=int, default=4096)
@@ -204,6 +252,8 @@ def main():
     ap.add_argument("--segments", type=int, default=1, help="also measure streams of K y segments, alternately")
     ap.add_argument("--overlap", default=None, metavar="O[,O2...]",
                     help="measure overlapped tiles with blended seams against overlap 0, alternately")
+    ap.add_argument("--max-error", default=None, metavar="T[,T2...]",
+                    help="measure near-lossless streams (max_error = T) against the lossy stream, alternately")
     a = ap.parse_args()
 
     import numpy as np
@@ -224,6 +274,12 @@ def main():
     img = torch.from_numpy(scene.astype(np.uint8)).cuda()
     n = g["n"]
 
+    if a.max_error is not None:
+        res = near_lossless_records(model, img, a, [int(v) for v in a.max_error.split(",")])
+        print(json.dumps(res))
+        with open(a.json or os.path.join(ROOT, "profiles", "near_lossless_bench.json"), "w") as f:
+            json.dump(res, f, indent=1)
+        return
     if a.overlap is not None:
         res = overlap_records(model, img, a, [int(v) for v in a.overlap.split(",")])
         print(json.dumps(res))
