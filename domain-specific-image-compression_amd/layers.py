@@ -9,13 +9,16 @@ Inference only: parameters are plain tensors for the kernels, no autograd.
 """
 from __future__ import annotations
 
+import enum
 import math
+import os
+from collections import namedtuple
+from typing import NamedTuple
 
 import torch
 import torch.nn as nn
 
-import os
-
+from . import lib as _lib
 from . import ops
 
 # DSIC_WINOGRAD=0 forces the direct implicit-GEMM kernel for every layer (A/B runs)
@@ -24,21 +27,18 @@ USE_WINOGRAD = os.environ.get("DSIC_WINOGRAD", "1") != "0"
 # NHWC; 1 passes the first layer's output chunk-major when its consumer runs on the 64-tile Winograd kernel;
 # 2 (default) also every activation whose producer and consumer both run on that kernel
 CHUNK_MAJOR = int(os.environ.get("DSIC_CHUNK_MAJOR", "2"))
-USE_CHUNK_MAJOR = CHUNK_MAJOR > 0
 
 
 def wino_bf16() -> bool:
     """The library's arithmetic variant (dsic_split_bf16): True = every contraction on bf16 MFMAs with operands split
     into two bf16 planes (fp32-class results, csrc/conv_wino_bf16.hip; the default), False = fp32-input MFMAs.  One
     switch for the first layer, the Winograd layers and the image layer; DSIC_WINO_BF16=0 only sets its initial value."""
-    from . import lib as _lib
     return bool(_lib.load().dsic_split_bf16())
 
 
 def set_wino_bf16(on: bool) -> None:
     """Switches the variant at run time.  Packed weights are cached per variant (_ConvBase._key), so layers built
     before the switch follow it on their next call."""
-    from . import lib as _lib
     _lib.check(_lib.load().dsic_set_split_bf16(1 if on else 0), "set_split_bf16")
 
 
@@ -91,22 +91,60 @@ class GDN(nn.Module):
         return ops.gdn_nchw(x, beta, gamma, self.inverse)
 
 
+class Layout(NamedTuple):
+    """How an activation lies in memory.  s2d: the space-to-depth image [B,H/2,W/2,4C] of the tensor, which a 5x5/s2
+    layer reads as a 3x3 conv; cm: chunk-major [B,C/16,H,W,16] (ops.LAYOUT_CM16) instead of NHWC [B,H,W,C]."""
+    s2d: bool = False
+    cm: bool = False
+
+
+NHWC = Layout()
+
+
+class Kernel(enum.Enum):
+    FIRST = "first layer, from the image"
+    DIRECT = "direct implicit GEMM"
+    WINO_F32 = "Winograd on fp32 MFMAs"
+    BF16_32 = "split-bf16 Winograd, 32 tiles"    # also its split-K form (ops.conv3x3_wino_nhwc decides) and Cout slices
+    BF16_64 = "split-bf16 Winograd, 64 tiles"    # conv_wino_bf16m.hip
+    IMAGE = "last layer, to the image"
+
+
+class Choice(NamedTuple):
+    """The kernel a layer runs on for one input (Conv2d.kernel, ConvTranspose2d.kernel) and what that launch can do
+    beside plain NHWC: write its output space-to-depth; read and write chunk-major (the first layer only writes)."""
+    kernel: Kernel
+    s2d_out: bool = False
+    cm: bool = False
+
+
+def _gdn_params(gdn):
+    return gdn.effective() if gdn is not None else (None, None)
+
+
+_NEEDS_M64 = "chunk-major activations need the 64-tile Winograd kernel"
+
+
 class _ConvBase(nn.Module):
     def __init__(self):
         super().__init__()
-        self._packed = None
-        self._packed_key = None
+        self._cache, self._cache_key = {}, None
 
     def _key(self):
         w = self.weight
         return (w._version, w.data_ptr(), str(w.device), wino_bf16())
 
-    def packed(self):
+    def _cached(self, form, make):
+        """The packed forms of the weights, each made on first use and all dropped when _key() changes."""
         key = self._key()
-        if self._packed is None or self._packed_key != key:
-            self._packed = self._pack()
-            self._packed_key = key
-        return self._packed
+        if self._cache_key != key:
+            self._cache, self._cache_key = {}, key
+        if form not in self._cache:
+            self._cache[form] = make()
+        return self._cache[form]
+
+    def packed(self):
+        return self._cached("packed", self._pack)
 
 
 class Conv2d(_ConvBase):
@@ -116,10 +154,6 @@ class Conv2d(_ConvBase):
         super().__init__()
         self.in_channels, self.out_channels = in_ch, out_ch
         self.kernel_size, self.stride = k, stride
-        # layers on few tiles per image may share a tile's input channels between workgroups (ops.WINO_SPLITK);
-        # HyperAnalysis switches it off: its launches run on the side stream, where every extra launch waits for
-        # compute units at a kernel boundary of the main stream
-        self.split_k = True
         w = torch.empty(out_ch, in_ch, k, k)
         nn.init.kaiming_uniform_(w, a=math.sqrt(5))
         bound = 1.0 / math.sqrt(in_ch * k * k)
@@ -133,15 +167,9 @@ class Conv2d(_ConvBase):
         return ops.pack_conv_weight(self.weight)
 
     @property
-    def use_winograd(self):
-        """3x3 stride-1 layers with MFMA-friendly channel counts run as Winograd F(2x2,3x3)."""
-        return (USE_WINOGRAD and self.kernel_size == 3 and self.stride == 1 and self.in_channels % 32 == 0
-                and self.out_channels % 4 == 0 and 64 <= self.out_channels <= 128)
-
-    @property
     def use_winograd_s2(self):
         """5x5 stride-2 layers run as a 3x3 Winograd conv over the space-to-depth input (4*Cin
-        channels) when the producing layer can write that layout."""
+        channels) when the producing layer can write that layout: does this layer ask for it?"""
         # both Winograd kernels need 4*Cin as a multiple of 128 over the space-to-depth input (Cin % 32 == 0); other
         # widths (cfg.MODEL.N is configurable in the reference's train.py) take the direct implicit GEMM
         if not (USE_WINOGRAD and self.kernel_size == 5 and self.stride == 2 and self.in_channels % 32 == 0
@@ -151,85 +179,78 @@ class Conv2d(_ConvBase):
         # only the split-bf16 kernel can store a slice
         return self.out_channels <= 128 or (wino_bf16() and self.out_channels <= 256 and 4 * self.in_channels >= 64)
 
-    def _cout_slices(self):
-        """(lo, hi) output-channel slices of at most 128 (multiples of 32 except the last)."""
-        n = self.out_channels
-        return [(lo, min(lo + 128, n)) for lo in range(0, n, 128)]
+    def kernel(self, H, W, layout=NHWC, image_ch=None):
+        """Which kernel runs this layer on an input of H x W pixels in `layout` (the space-to-depth grid when
+        layout.s2d), and which layouts that launch can exchange.  image_ch: the input is still the image, with that
+        many channels.  The only place that decides either; run_nhwc and _Chain.plan follow it."""
+        cin, cout = self.in_channels, self.out_channels
+        if image_ch is not None and (self.kernel_size == 3 and self.stride == 1 and cin in (3, 4) and image_ch == cin
+                                     and cout <= 128 and cout % 4 == 0):
+            # conv(3|4 -> <=128, 3, 1) from the NCHW image or its uint8 bytes (K = 9*Cimg, no channel padding)
+            return Choice(Kernel.FIRST, s2d_out=True, cm=cout % 16 == 0)
+        if layout.s2d:
+            # only the Winograd kernels read space-to-depth; a layer is given it only after it asked (use_winograd_s2),
+            # and one that did not ask is never given chunk-major
+            cin, m64_ok = 4 * cin, self.use_winograd_s2
+            if cout > 128:
+                return Choice(Kernel.BF16_32)             # Cout slices of <= 128 into one NHWC tensor
+        elif (USE_WINOGRAD and self.kernel_size == 3 and self.stride == 1 and cin % 32 == 0 and cout % 4 == 0
+              and 64 <= cout <= 128):
+            m64_ok = True                                 # 3x3 stride-1, MFMA-friendly channel counts: F(2x2,3x3)
+        else:
+            return Choice(Kernel.DIRECT)
+        if not (wino_bf16() and cin >= 64):
+            return Choice(Kernel.WINO_F32, s2d_out=True)
+        if m64_ok and _lib.load().dsic_wino_bf16_m64(H, W, cin, 1):
+            return Choice(Kernel.BF16_64, s2d_out=True, cm=True)
+        return Choice(Kernel.BF16_32, s2d_out=True)
 
     def packed_wino_slices(self):
-        """per Cout slice: (lo, hi, bf16 planes, bias, ...) for out_channels > 128 (space-to-depth 5x5/s2 only)"""
-        key = self._key()
-        if getattr(self, "_wino_sl", None) is None or self._wino_sl_key != key:
+        """(lo, hi, bf16 planes, bias) per Cout slice of at most 128, for out_channels > 128 (space-to-depth 5x5/s2)"""
+        def make():
             sl = []
-            for lo, hi in self._cout_slices():
+            for lo in range(0, self.out_channels, 128):
+                hi = min(lo + 128, self.out_channels)
                 u = ops.pack_wino_s2_weight(self.weight[lo:hi].contiguous())
                 u = ops.split_wino_weight_bf16(u, hi - lo, 4 * self.in_channels, 1)
                 sl.append((lo, hi, u, self.bias[lo:hi].contiguous()))
-            self._wino_sl, self._wino_sl_key = sl, key
-        return self._wino_sl
+            return sl
+        return self._cached("wino_slices", make)
 
     def packed_wino(self):
-        key = self._key()
-        if getattr(self, "_wino", None) is None or self._wino_key != key:
-            self._wino = (ops.pack_wino_s2_weight(self.weight) if self.kernel_size == 5
-                          else ops.pack_wino_weight(self.weight))
+        def make():
+            u = ops.pack_wino_s2_weight(self.weight) if self.kernel_size == 5 else ops.pack_wino_weight(self.weight)
             cin = self.in_channels * (4 if self.kernel_size == 5 else 1)
             if wino_bf16() and cin >= 64:
-                self._wino = ops.split_wino_weight_bf16(self._wino, self.out_channels, cin, 1)
-            self._wino_key = key
-        return self._wino
+                u = ops.split_wino_weight_bf16(u, self.out_channels, cin, 1)
+            return u
+        return self._cached("wino", make)
 
-    def m64(self, H, W, x_is_s2d=False):
-        """Does this layer run on the 64-tile Winograd kernel (conv_wino_bf16m.hip), the only reader and writer of
-        chunk-major activations, for an input of H x W pixels (the space-to-depth grid when x_is_s2d)?"""
-        if not wino_bf16():
-            return False
-        if x_is_s2d:
-            cin, ok = 4 * self.in_channels, self.use_winograd_s2 and self.out_channels <= 128
-        else:
-            cin, ok = self.in_channels, self.use_winograd
-        from . import lib as _lib
-        return ok and cin >= 64 and bool(_lib.load().dsic_wino_bf16_m64(H, W, cin, 1))
-
-    def run_nhwc(self, x, act=ops.ACT_NONE, gdn=None, x_is_s2d=False, s2d_out=False, cm_in=False, cm_out=False):
-        """x_is_s2d: x is the space-to-depth image of this layer's input; s2d_out: write the
-        output space-to-depth (only the Winograd paths can).  cm_in / cm_out: chunk-major input / output
-        (only where m64() holds)."""
-        beta = gamma = None
-        if gdn is not None:
-            beta, gamma = gdn.effective()
-        if cm_in or cm_out:
-            B, H, W, _ = ops.cm16_shape(x) if cm_in else x.shape
-            assert self.m64(H, W, x_is_s2d), "chunk-major activations need the 64-tile Winograd kernel"
-            taps = 25 if x_is_s2d else 9
-            return ops.conv3x3_wino_nhwc(x, self.packed_wino(), self.bias, self.out_channels, act, beta, gamma,
-                                         s2d_out=s2d_out, s2d_in=x_is_s2d, split_k=self.split_k, cm_in=cm_in,
-                                         cm_out=cm_out,
-                                         algo_flops=2.0 * B * H * W * self.out_channels * self.in_channels * taps)
-        if x_is_s2d and self.out_channels > 128:
-            B, H2, W2, _ = x.shape
-            assert not s2d_out
-            out = torch.empty((B, H2, W2, self.out_channels), dtype=torch.float32, device=x.device)
+    def run_nhwc(self, x, act=ops.ACT_NONE, gdn=None, x_is_s2d=False, s2d_out=False, cm_in=False, cm_out=False,
+                 split_k=True):
+        """x_is_s2d: x is the space-to-depth image of this layer's input; s2d_out: write the output space-to-depth;
+        cm_in / cm_out: chunk-major input / output (each only where kernel() says the launch can).
+        split_k: on few tiles per image, workgroups may share a tile's input channels (ops.WINO_SPLITK)."""
+        B, H, W, _ = ops.cm16_shape(x) if cm_in else x.shape
+        c = self.kernel(H, W, Layout(x_is_s2d, cm_in))
+        assert c.cm or not (cm_in or cm_out), _NEEDS_M64
+        assert c.s2d_out or not s2d_out
+        beta, gamma = _gdn_params(gdn)
+        if c.kernel is Kernel.DIRECT:
+            return ops.conv2d_nhwc(x, self.packed(), self.bias, self.out_channels, self.kernel_size,
+                                   self.stride, act, beta, gamma, cin_real=self.in_channels)
+        # direct-convolution FLOPs per output channel (the space-to-depth 3x3 stands for 25 taps)
+        flops = 2.0 * B * H * W * self.in_channels * (25 if x_is_s2d else 9)
+        if self.out_channels > 128:
+            out = torch.empty((B, H, W, self.out_channels), dtype=torch.float32, device=x.device)
             for lo, hi, u, bias in self.packed_wino_slices():
                 ops.conv3x3_wino_nhwc(x, u, bias, hi - lo, act, None if beta is None else beta[lo:hi].contiguous(),
                                       None if gamma is None else gamma[lo:hi].contiguous(), out=out, s2d_in=True,
-                                      out_coff=lo, split_k=self.split_k,
-                                      algo_flops=2.0 * B * H2 * W2 * (hi - lo) * self.in_channels * 25)
+                                      out_coff=lo, split_k=split_k, algo_flops=flops * (hi - lo))
             return out
-        if x_is_s2d:
-            B, H2, W2, _ = x.shape
-            return ops.conv3x3_wino_nhwc(x, self.packed_wino(), self.bias, self.out_channels, act, beta, gamma,
-                                         s2d_out=s2d_out, s2d_in=True, split_k=self.split_k,
-                                         algo_flops=2.0 * B * H2 * W2 * self.out_channels * self.in_channels * 25)
-        if self.use_winograd and x.shape[-1] == self.in_channels:
-            return ops.conv3x3_wino_nhwc(x, self.packed_wino(), self.bias, self.out_channels, act, beta, gamma,
-                                         s2d_out=s2d_out, split_k=self.split_k)
-        assert not s2d_out
-        return ops.conv2d_nhwc(x, self.packed(), self.bias, self.out_channels, self.kernel_size,
-                               self.stride, act, beta, gamma, cin_real=self.in_channels)
-
-    def can_write_s2d(self, x_is_s2d):
-        return x_is_s2d or self.use_winograd
+        return ops.conv3x3_wino_nhwc(x, self.packed_wino(), self.bias, self.out_channels, act, beta, gamma,
+                                     s2d_out=s2d_out, s2d_in=x_is_s2d, split_k=split_k, cm_in=cm_in, cm_out=cm_out,
+                                     algo_flops=flops * self.out_channels)
 
     @torch.no_grad()
     def forward(self, x):
@@ -249,15 +270,12 @@ class ConvTranspose2d(_ConvBase):
         if (kernel_size, stride, padding, output_padding) != (5, 2, 2, 1):
             raise ValueError("only ConvTranspose2d(k=5, s=2, p=2, output_padding=1) is on the hot path")
         self.in_channels, self.out_channels = in_ch, out_ch
+        self.to_image = out_ch % 8 != 0         # the last synthesis layer: NHWC features -> NCHW image
         w = torch.empty(in_ch, out_ch, 5, 5)
         nn.init.kaiming_uniform_(w, a=math.sqrt(5))
         bound = 1.0 / math.sqrt(out_ch * 25)
         self.weight = nn.Parameter(w, requires_grad=False)
         self.bias = nn.Parameter(torch.empty(out_ch).uniform_(-bound, bound), requires_grad=False)
-
-    @property
-    def to_image(self):
-        return self.out_channels % 8 != 0
 
     @property
     def use_winograd(self):
@@ -274,27 +292,31 @@ class ConvTranspose2d(_ConvBase):
             return u
         return ops.pack_convT_weight(self.weight)
 
-    def m64(self, H, W):
-        """Does this layer run on the 64-tile Winograd kernel for an H x W input (see Conv2d.m64)?"""
-        if not (self.use_winograd and wino_bf16() and self.in_channels >= 64):
-            return False
-        from . import lib as _lib
-        return bool(_lib.load().dsic_wino_bf16_m64(H, W, self.in_channels, 4))
+    def kernel(self, H, W, layout=NHWC):
+        """Which kernel runs this layer on an H x W input, and which layouts that launch can exchange (see
+        Conv2d.kernel): no transposed form reads or writes space-to-depth, the image layer takes NHWC only."""
+        assert not layout.s2d
+        if self.to_image:
+            return Choice(Kernel.IMAGE)
+        if not self.use_winograd:
+            return Choice(Kernel.DIRECT)
+        if not (wino_bf16() and self.in_channels >= 64):
+            return Choice(Kernel.WINO_F32)
+        if _lib.load().dsic_wino_bf16_m64(H, W, self.in_channels, 4):
+            return Choice(Kernel.BF16_64, cm=True)
+        return Choice(Kernel.BF16_32)
 
     def run_nhwc(self, x, act=ops.ACT_NONE, gdn=None, cm_in=False, cm_out=False):
-        if self.to_image:   # returns NCHW image
-            assert not (cm_in or cm_out)
+        _, H, W, _ = ops.cm16_shape(x) if cm_in else x.shape
+        c = self.kernel(H, W, Layout(cm=cm_in))
+        assert c.cm or not (cm_in or cm_out), _NEEDS_M64
+        if c.kernel is Kernel.IMAGE:   # returns NCHW image
             return ops.conv_transpose2d_image(x, self.packed(), self.bias, self.out_channels)
-        beta = gamma = None
-        if gdn is not None:
-            beta, gamma = gdn.effective()
-        if cm_in or cm_out:
-            _, H, W, _ = ops.cm16_shape(x) if cm_in else x.shape
-            assert self.m64(H, W), "chunk-major activations need the 64-tile Winograd kernel"
-        if self.use_winograd:
-            return ops.conv_transpose2d_wino_nhwc(x, self.packed(), self.bias, self.out_channels, act, beta, gamma,
-                                                  cm_in=cm_in, cm_out=cm_out)
-        return ops.conv_transpose2d_nhwc(x, self.packed(), self.bias, self.out_channels, act, beta, gamma)
+        beta, gamma = _gdn_params(gdn)
+        if c.kernel is Kernel.DIRECT:
+            return ops.conv_transpose2d_nhwc(x, self.packed(), self.bias, self.out_channels, act, beta, gamma)
+        return ops.conv_transpose2d_wino_nhwc(x, self.packed(), self.bias, self.out_channels, act, beta, gamma,
+                                              cm_in=cm_in, cm_out=cm_out)
 
     @torch.no_grad()
     def forward(self, x):
@@ -320,129 +342,105 @@ def _to_nhwc(x):
     return ops.nchw_to_nhwc(x)
 
 
+# One launch of a chain's plan: the conv (or a GDN | nn.ReLU that no conv takes in: kernel None), the activation fused
+# into its kernel (ops.ACT_*) with its GDN or None, the Layouts it reads and writes, and the Kernel
+Step = namedtuple("Step", "conv act gdn lay_in lay_out kernel")
+
+
+def _fused(nxt, kernel):
+    """(act, gdn, modules consumed): the activation after a conv that its kernel applies itself."""
+    if isinstance(nxt, GDN) and not (nxt.inverse and kernel is Kernel.FIRST):
+        return (ops.ACT_IGDN if nxt.inverse else ops.ACT_GDN), nxt, 2
+    if isinstance(nxt, nn.ReLU):
+        return ops.ACT_RELU, None, 2
+    return ops.ACT_NONE, None, 1
+
+
 class _Chain(nn.Sequential):
-    """nn.Sequential whose (conv, GDN|ReLU) pairs run as one fused kernel."""
+    """nn.Sequential whose (conv, GDN|ReLU) pairs run as one fused kernel, in the layouts plan() chooses."""
 
-    @staticmethod
-    def _wants_s2d(mods, j, H, W):
-        """Does the conv that consumes the output of the layer ending before index j take
-        space-to-depth input?  (H, W: spatial size of that output.)"""
-        nxt = mods[j] if j < len(mods) else None
-        return isinstance(nxt, Conv2d) and nxt.use_winograd_s2 and H % 2 == 0 and W % 2 == 0
+    def __init__(self, *mods, split_k=True):
+        super().__init__(*mods)
+        # HyperAnalysis switches split-K off: its launches run on the side stream, where every extra launch waits for
+        # compute units at a kernel boundary of the main stream
+        self.split_k = split_k
 
-    @staticmethod
-    def _wants_cm(mods, j, H, W, s2d):
-        """Does the module at index j, the consumer of an output of H x W pixels (space-to-depth when s2d: then the
-        grid is H/2 x W/2), read it chunk-major?  Only the 64-tile Winograd kernel does."""
-        if not USE_CHUNK_MAJOR or j >= len(mods):
-            return False
-        nxt = mods[j]
-        if s2d:
-            return isinstance(nxt, Conv2d) and nxt.m64(H // 2, W // 2, True)
-        if isinstance(nxt, Conv2d):
-            return nxt.kernel_size == 3 and nxt.stride == 1 and nxt.m64(H, W)
-        return isinstance(nxt, ConvTranspose2d) and nxt.m64(H, W)
+    def plan(self, shape, dtype, from_image=False):
+        """The launches of this chain for an input of `shape` and `dtype`: NHWC activations, or with from_image the
+        NCHW float32 image or its uint8 [B,H,W,C] bytes.  Pure: no tensors, no launches, recomputed on every call.
 
-    @staticmethod
-    def _tap(x, s2d, cm):
-        """A tap in the layout the fixtures know: NHWC at the layer's own resolution."""
-        if cm:
-            x = ops.cm16_to_nhwc(x)
-        return ops.depth_to_space(x) if s2d else x
-
-    def forward_from_image(self, x_nchw, taps=None):
-        """Like forward_nhwc but from an NCHW image: a leading conv(3|4 -> <=128, 3, 1)
-        runs as the dedicated first-layer kernel (K = 9*Cimg, no channel padding)."""
+        An edge between two layers is space-to-depth when the consumer asks for it (Conv2d.use_winograd_s2, even
+        sizes) and the producer's launch can write it; chunk-major when the consumer then runs on the 64-tile
+        Winograd kernel and the producer is the first layer (CHUNK_MAJOR >= 1) or that kernel too (CHUNK_MAJOR >= 2).
+        The chain's input and output are always NHWC (or the image)."""
         mods = list(self)
-        m = mods[0] if mods else None
-        u8 = x_nchw.dtype == torch.uint8          # decoded image bytes [B,H,W,C]: to_tensor is fused into the kernel
-        cin = x_nchw.shape[3] if u8 else x_nchw.shape[1]
-        first_ok = (isinstance(m, Conv2d) and m.kernel_size == 3 and m.stride == 1 and m.in_channels in (3, 4)
-                    and m.out_channels <= 128 and m.out_channels % 4 == 0 and cin == m.in_channels)
-        if u8 and not first_ok:
-            x_nchw, u8 = ops.to_tensor_u8(x_nchw), False
-        if first_ok:
-            nxt = mods[1] if len(mods) > 1 else None
-            H, W = (x_nchw.shape[1], x_nchw.shape[2]) if u8 else (x_nchw.shape[2], x_nchw.shape[3])
-            j = 2 if isinstance(nxt, GDN) and not nxt.inverse or isinstance(nxt, nn.ReLU) else 1
-            s2d = self._wants_s2d(mods, j, H, W)
-            cm = m.out_channels % 16 == 0 and self._wants_cm(mods, j, H, W, s2d)
-            if j == 2 and isinstance(nxt, GDN):
-                beta, gamma = nxt.effective()
-                y = ops.conv_first_nchw(x_nchw, m.weight, m.bias, ops.ACT_GDN, beta, gamma, s2d_out=s2d, cm_out=cm)
-            elif j == 2:
-                y = ops.conv_first_nchw(x_nchw, m.weight, m.bias, ops.ACT_RELU, s2d_out=s2d, cm_out=cm)
-            else:
-                y = ops.conv_first_nchw(x_nchw, m.weight, m.bias, s2d_out=s2d, cm_out=cm)
-            if taps is not None:
-                taps.append(self._tap(y, s2d, cm))
-            return self.forward_nhwc(y, taps, j, x_is_s2d=s2d, x_is_cm=cm)
-        return self.forward_nhwc(_to_nhwc(x_nchw), taps)
-
-    def forward_nhwc(self, x, taps=None, start=0, x_is_s2d=False, x_is_cm=False):
-        """x_is_cm: x is chunk-major (ops.cm16_to_nhwc); the returned tensor is NHWC (or the NCHW image)."""
-        mods = list(self)
-        i = start
+        if from_image and dtype != torch.uint8:
+            shape = shape[0], shape[2], shape[3], shape[1]
+        (_, H, W, C), steps, lay, i = shape, [], NHWC, 0
         while i < len(mods):
             m = mods[i]
-            nxt = mods[i + 1] if i + 1 < len(mods) else None
-            out_s2d = out_cm = False
-            # spatial size of the input
-            H, W = (x.shape[2], x.shape[3]) if x_is_cm else (x.shape[1], x.shape[2])
+            if isinstance(m, (GDN, nn.ReLU)):            # no conv before it to be fused into
+                assert lay == NHWC
+                steps.append(Step(m, ops.ACT_NONE, None, NHWC, NHWC, None))
+                i += 1
+                continue
             if isinstance(m, Conv2d):
-                fused = isinstance(nxt, (GDN, nn.ReLU))
-                # spatial size of this layer's output
-                if x_is_s2d:
-                    Ho, Wo = H, W
-                else:
-                    Ho, Wo = -(-H // m.stride), -(-W // m.stride)
-                j = i + (2 if fused else 1)
-                out_s2d = m.can_write_s2d(x_is_s2d) and self._wants_s2d(mods, j, Ho, Wo)
-                out_cm = CHUNK_MAJOR > 1 and (x_is_s2d or m.kernel_size == 3) and m.m64(H, W, x_is_s2d) and \
-                    self._wants_cm(mods, j, Ho, Wo, out_s2d)
-                if isinstance(nxt, GDN):
-                    x = m.run_nhwc(x, ops.ACT_IGDN if nxt.inverse else ops.ACT_GDN, nxt, x_is_s2d, out_s2d,
-                                   x_is_cm, out_cm)
-                elif isinstance(nxt, nn.ReLU):
-                    x = m.run_nhwc(x, ops.ACT_RELU, None, x_is_s2d, out_s2d, x_is_cm, out_cm)
-                else:
-                    x = m.run_nhwc(x, ops.ACT_NONE, None, x_is_s2d, out_s2d, x_is_cm, out_cm)
-                i = j
+                c = m.kernel(H, W, lay, C if from_image and i == 0 else None)
+                Ho, Wo = (H, W) if lay.s2d else (-(-H // m.stride), -(-W // m.stride))
             elif isinstance(m, ConvTranspose2d):
-                assert not x_is_s2d
-                fused = isinstance(nxt, (GDN, nn.ReLU))
-                j = i + (2 if fused else 1)
-                out_cm = CHUNK_MAJOR > 1 and m.m64(H, W) and self._wants_cm(mods, j, 2 * H, 2 * W, False)
-                if isinstance(nxt, GDN):
-                    x = m.run_nhwc(x, ops.ACT_IGDN if nxt.inverse else ops.ACT_GDN, nxt, x_is_cm, out_cm)
-                elif isinstance(nxt, nn.ReLU):
-                    x = m.run_nhwc(x, ops.ACT_RELU, None, x_is_cm, out_cm)
-                else:
-                    x = m.run_nhwc(x, cm_in=x_is_cm, cm_out=out_cm)
-                i = j
-            elif isinstance(m, GDN):
-                assert not (x_is_s2d or x_is_cm)
-                x = ops.nchw_to_nhwc(m(ops.nhwc_to_nchw(x)))
-                i += 1
-            elif isinstance(m, nn.ReLU):
-                assert not x_is_cm
-                x = torch.relu(x)
-                i += 1
-            else:  # pragma: no cover
+                c = m.kernel(H, W, lay)
+                Ho, Wo = 2 * H, 2 * W
+            else:
                 raise TypeError(f"unsupported module {type(m).__name__}")
-            x_is_s2d, x_is_cm = out_s2d, out_cm
+            act, gdn, n = _fused(mods[i + 1] if i + 1 < len(mods) else None, c.kernel)
+            i += n
+            con = mods[i] if i < len(mods) else None     # the consumer of this launch's output
+            s2d = isinstance(con, Conv2d) and con.use_winograd_s2 and Ho % 2 == 0 and Wo % 2 == 0
+            # the Cout-slice form reads space-to-depth but cannot write it: such a chain is refused, not run NHWC
+            assert c.s2d_out or not (s2d and lay.s2d)
+            s2d = s2d and c.s2d_out
+            Ho, Wo = (Ho // 2, Wo // 2) if s2d else (Ho, Wo)
+            cm = (c.cm and CHUNK_MAJOR >= (1 if c.kernel is Kernel.FIRST else 2)
+                  and isinstance(con, (Conv2d, ConvTranspose2d)) and con.kernel(Ho, Wo, Layout(s2d)).cm)
+            steps.append(Step(m, act, gdn, lay, Layout(s2d, cm), c.kernel))
+            H, W, lay = Ho, Wo, Layout(s2d, cm)
+        assert lay == NHWC
+        return steps
+
+    def _run(self, steps, x, taps):
+        for st in steps:
+            m, i, o = st.conv, st.lay_in, st.lay_out
+            if st.kernel is None:
+                x = torch.relu(x) if isinstance(m, nn.ReLU) else ops.nchw_to_nhwc(m(ops.nhwc_to_nchw(x)))
+            elif st.kernel is Kernel.FIRST:
+                x = ops.conv_first_nchw(x, m.weight, m.bias, st.act, *_gdn_params(st.gdn), s2d_out=o.s2d, cm_out=o.cm)
+            elif isinstance(m, Conv2d):
+                x = m.run_nhwc(x, st.act, st.gdn, i.s2d, o.s2d, i.cm, o.cm, self.split_k)
+            else:
+                x = m.run_nhwc(x, st.act, st.gdn, i.cm, o.cm)
             if taps is not None:
-                taps.append(self._tap(x, x_is_s2d, x_is_cm))
-        assert not (x_is_s2d or x_is_cm)
+                # a tap in the layout the fixtures know: NHWC at the layer's own resolution
+                t = ops.cm16_to_nhwc(x) if o.cm else x
+                taps.append(ops.depth_to_space(t) if o.s2d else t)
         return x
+
+    def forward_from_image(self, x_nchw, taps=None):
+        """Like forward_nhwc but from an NCHW image, or from decoded image bytes (uint8 [B,H,W,C]: to_tensor is fused
+        into the first-layer kernel)."""
+        steps = self.plan(x_nchw.shape, x_nchw.dtype, from_image=True)
+        if not (steps and steps[0].kernel is Kernel.FIRST):
+            x_nchw = _to_nhwc(ops.to_tensor_u8(x_nchw) if x_nchw.dtype == torch.uint8 else x_nchw)
+        return self._run(steps, x_nchw, taps)
+
+    def forward_nhwc(self, x, taps=None):
+        """NHWC in, NHWC (or the NCHW image) out; taps: a list that receives every launch's output."""
+        return self._run(self.plan(x.shape, x.dtype), x, taps)
 
     @torch.no_grad()
     def forward(self, x):
         y = self.forward_nhwc(_to_nhwc(x))
         last = list(self)[-1]
-        if isinstance(last, ConvTranspose2d) and last.to_image:
-            return y
-        return ops.nhwc_to_nchw(y)
+        return y if isinstance(last, ConvTranspose2d) and last.to_image else ops.nhwc_to_nchw(y)
 
 
 class AnalysisTransform(nn.Module):
@@ -504,10 +502,8 @@ class HyperAnalysis(nn.Module):
             conv(N, N, 3, 1), nn.ReLU(inplace=True),
             conv(N, N, 5, 2), nn.ReLU(inplace=True),
             conv(N, N, 5, 2),
+            split_k=False,
         )
-        for m in self.h_a:
-            if isinstance(m, Conv2d):
-                m.split_k = False
 
     def forward_nhwc(self, y, taps=None):
         return self.h_a.forward_nhwc(y, taps)

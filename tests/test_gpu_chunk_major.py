@@ -116,30 +116,38 @@ def test_chunk_major_needs_the_64_tile_kernel(ops):
 
 
 def test_analysis_and_synthesis_chains_match_nhwc(ops, monkeypatch):
-    """g_a.0 -> g_a.2 and every 64-tile edge of g_a / g_s: same outputs and taps with and without CM16."""
+    """g_a.0 -> g_a.2 and every 64-tile edge of g_a / g_s: same outputs and taps at every level of layers.CHUNK_MAJOR.
+    128x128 is the smallest size with 64-tile edges in both chains, 48x80 the smallest whose bottom layers run on the
+    direct kernel."""
     from dsic_amd import layers, synthetic as S
     from dsic_amd.model import CompressionModel
     sd = S.make_state_dict(seed=3)
     m = CompressionModel(N=128, M=192, spatial_params=False, min_nu=2, max_nu=100.0)
     m.load_state_dict({k: torch.from_numpy(v) for k, v in sd.items()}, strict=True)
     m = m.cuda().eval()
-    x = torch.from_numpy(S.make_patches(0, 2, 128, 128)).cuda()
     firsts = []
     real_first = ops.conv_first_nchw
     monkeypatch.setattr(ops, "conv_first_nchw", lambda *a, **k: firsts.append(k.get("cm_out")) or real_first(*a, **k))
 
-    def run(cm):
-        monkeypatch.setattr(layers, "USE_CHUNK_MAJOR", cm)
+    def run(x, cm):
+        monkeypatch.setattr(layers, "CHUNK_MAJOR", cm)
         ta, ts = [], []
         y = m.g_a.forward_from_image(x, ta)
         xh = m.g_s.forward_nhwc(y[..., :192].contiguous(), ts)
         torch.cuda.synchronize()
         return y, xh, ta, ts
 
-    y0, xh0, ta0, ts0 = run(False)
-    y1, xh1, ta1, ts1 = run(True)
-    assert firsts == [False, True]
-    assert torch.equal(y0, y1) and torch.equal(xh0, xh1)
-    assert len(ta0) == len(ta1) and len(ts0) == len(ts1)
-    for a, b in zip(ta0 + ts0, ta1 + ts1):
-        assert torch.equal(a, b)
+    for H, W in ((128, 128), (48, 80)):
+        x = torch.from_numpy(S.make_patches(0, 2, H, W)).cuda()
+        del firsts[:]
+        y0, xh0, ta0, ts0 = run(x, 0)
+        # g_a.2 reads the first layer's output as a space-to-depth map of 512 channels: chunk-major where that is a
+        # 64-tile layer
+        first_cm = True if (H, W) == (128, 128) else bool(ops._lib.load().dsic_wino_bf16_m64(H // 2, W // 2, 512, 1))
+        for level in (1, 2):
+            y1, xh1, ta1, ts1 = run(x, level)
+            assert firsts == [False] + [first_cm] * level, (H, W, level)
+            assert torch.equal(y0, y1) and torch.equal(xh0, xh1)
+            assert len(ta0) == len(ta1) and len(ts0) == len(ts1)
+            for a, b in zip(ta0 + ts0, ta1 + ts1):
+                assert torch.equal(a, b)
