@@ -26,6 +26,7 @@
 #include <type_traits>
 
 #include "common.h"
+#include "wino_host.h"
 
 #ifndef WINO_STAMP
 #define WINO_STAMP 0
@@ -119,9 +120,6 @@ constexpr int WLDS_TOTAL = WLDS_BYTES + 64 + (WINO_STAMP ? 256 : 0);  // + three
 constexpr int WTHREADS = 768;              // 8 MFMA waves + 4 helper waves
 #ifndef WINO_RING
 #define WINO_RING 4                        // U fragments in flight per MFMA wave (2 or 4)
-#endif
-#ifndef WINO_NT_BYTES
-#define WINO_NT_BYTES (300ll << 20)  // outputs larger than this are stored non-temporal (they cannot stay in the 256 MB MALL)
 #endif
 #ifndef WINO_CPRIO
 #define WINO_CPRIO 1                       // wave priority of an MFMA wave inside an MFMA cluster
@@ -707,101 +705,43 @@ extern "C" int dsic_pack_wino_convT_weight(const float* w_iohw5, float* dst, int
   return check_launch("pack_wino_convT_weight");
 }
 
-static int wino_launch(WinoArgs& a, hipStream_t st);
+// One launch of the fp32 kernel: a 3x3 layer (nphase 1) or the four phases of a transposed one.  what, gdn: the
+// export's message prefix and its name for the activation.
+static int wino_launch(const char* what, const char* gdn, const wino_host::Layer& l, int nphase, void* stream) {
+  if (const int rc = wino_host::check_layer(what, gdn, 32, l)) return rc;
+  WinoArgs a{};
+  a.in = l.in; a.u = (const float*)l.u; a.bias = l.bias; a.beta = l.beta; a.gamma = l.gamma; a.out = l.out;
+  a.B = l.B; a.H = l.H; a.W = l.W; a.Cin = l.Cin; a.Cout = l.Cout; a.CoutP = round_up(l.Cout, 32); a.act = l.act;
+  a.ticket = (unsigned long long*)l.ticket;
+  a.s2d = l.s2d_out; a.s2d_in = l.s2d_in;
+  a.nphase = nphase; a.u_phase_stride = nphase == 4 ? dsic_wino_weight_floats(l.Cout, l.Cin) : 0;
+  a.tiles_x = ceil_div(a.W, 16); a.tiles_y = ceil_div(a.H, 8);
+  const int64_t nt = (int64_t)a.tiles_x * a.tiles_y * a.B * nphase;
+  if (const int rc = wino_host::check_limits("conv3x3_wino", nt, a.H, a.W, a.Cin, (int64_t)a.Cout * (nphase == 4 ? 4 : 1),
+                                             (int64_t)16 * (a.Cin / 8) * a.CoutP * 8 * 4 * nphase))
+    return rc;
+  a.ntiles = (int)nt;
+  a.nt_out = wino_host::streams_output(a.B, a.H, a.W, a.Cout, nphase);
+  static wino_host::Family<3> family = {"conv3x3_wino", WTHREADS, WLDS_TOTAL,   // by MODE
+                                        {(const void*)conv_wino_kernel<0>, (const void*)conv_wino_kernel<1>,
+                                         (const void*)conv_wino_kernel<2>}};
+  return wino_host::launch(family, a.s2d_in ? 1 : nphase == 4 ? 2 : 0, nt, a, (hipStream_t)stream);
+}
 
 extern "C" int dsic_conv_transpose2d_wino_nhwc(const float* in, const float* u_packed4, const float* bias,
                                                const float* beta, const float* gamma, float* out, int B,
                                                int H, int W, int Cin, int Cout, int act, void* ticket,
                                                void* stream) {
-  DSIC_REQUIRE(in && u_packed4 && bias && out && ticket, "convT_wino: null pointer");
-  DSIC_REQUIRE(B > 0 && H > 0 && W > 0, "convT_wino: empty tensor");
-  DSIC_REQUIRE(Cin > 0 && Cin % 32 == 0, "convT_wino: Cin=%d must be a positive multiple of 32", Cin);
-  DSIC_REQUIRE(Cout > 0 && Cout % 4 == 0 && Cout <= 128, "convT_wino: Cout=%d must be a multiple of 4, <= 128", Cout);
-  DSIC_REQUIRE(act >= 0 && act <= 3, "convT_wino: act=%d", act);
-  DSIC_REQUIRE(!(act == DSIC_ACT_GDN || act == DSIC_ACT_IGDN) || (beta && gamma), "convT_wino: IGDN needs beta and gamma");
-  WinoArgs a{};
-  a.in = in; a.u = u_packed4; a.bias = bias; a.beta = beta; a.gamma = gamma; a.out = out;
-  a.B = B; a.H = H; a.W = W; a.Cin = Cin; a.Cout = Cout; a.CoutP = round_up(Cout, 32); a.act = act;
-  a.ticket = (unsigned long long*)ticket;
-  a.s2d = 0; a.s2d_in = 0; a.nphase = 4; a.u_phase_stride = dsic_wino_weight_floats(Cout, Cin);
-  return wino_launch(a, (hipStream_t)stream);
+  return wino_launch("convT_wino", "IGDN", {in, u_packed4, bias, beta, gamma, out, ticket, B, H, W, Cin, Cout, act, 0, 0},
+                     4, stream);
 }
 
 extern "C" int dsic_conv3x3_wino_nhwc(const float* in, const float* u_packed, const float* bias,
                                       const float* beta, const float* gamma, float* out, int B, int H,
                                       int W, int Cin, int Cout, int act, int s2d_out, int s2d_in,
                                       void* ticket, void* stream) {
-  DSIC_REQUIRE(in && u_packed && bias && out && ticket, "conv3x3_wino: null pointer");
-  DSIC_REQUIRE(B > 0 && H > 0 && W > 0, "conv3x3_wino: empty tensor");
-  DSIC_REQUIRE(Cin > 0 && Cin % 32 == 0, "conv3x3_wino: Cin=%d must be a positive multiple of 32", Cin);
-  DSIC_REQUIRE(Cout > 0 && Cout % 4 == 0 && Cout <= 128, "conv3x3_wino: Cout=%d must be a multiple of 4, <= 128", Cout);
-  DSIC_REQUIRE(act >= 0 && act <= 3, "conv3x3_wino: act=%d", act);
-  DSIC_REQUIRE(!(act == DSIC_ACT_GDN || act == DSIC_ACT_IGDN) || (beta && gamma), "conv3x3_wino: GDN needs beta and gamma");
   DSIC_REQUIRE(!((s2d_out | s2d_in) & DSIC_LAYOUT_CM16), "conv3x3_wino: chunk-major activations are not supported");
-  WinoArgs a{};
-  a.in = in; a.u = u_packed; a.bias = bias; a.beta = beta; a.gamma = gamma; a.out = out;
-  DSIC_REQUIRE(!s2d_out || (H % 2 == 0 && W % 2 == 0), "conv3x3_wino: space-to-depth output needs even H and W");
-  a.B = B; a.H = H; a.W = W; a.Cin = Cin; a.Cout = Cout; a.CoutP = round_up(Cout, 32); a.act = act;
-  a.s2d = s2d_out;
-  a.ticket = (unsigned long long*)ticket;
-  DSIC_REQUIRE(!s2d_in || Cin % 128 == 0, "conv3x3_wino: space-to-depth input needs Cin = 4*Cs with Cs %% 32 == 0");
-  a.s2d_in = s2d_in ? 1 : 0;
-  a.nphase = 1; a.u_phase_stride = 0;
-  return wino_launch(a, (hipStream_t)stream);
-}
-
-static int wino_launch(WinoArgs& a, hipStream_t st) {
-  const int B = a.B, H = a.H, W = a.W;
-  a.tiles_x = ceil_div(W, 16); a.tiles_y = ceil_div(H, 8);
-  const int64_t nt = (int64_t)a.tiles_x * a.tiles_y * B * a.nphase;
-  DSIC_REQUIRE(nt < ((int64_t)1 << 31), "conv3x3_wino: too many tiles");
-  DSIC_REQUIRE((int64_t)H * W * a.Cin * 4 < ((int64_t)1 << 31) &&
-                   (int64_t)H * W * a.Cout * 4 * (a.nphase == 4 ? 4 : 1) < ((int64_t)1 << 31),
-               "conv3x3_wino: one image must stay below 2 GiB (32-bit offsets inside an image)");
-  DSIC_REQUIRE((int64_t)16 * (a.Cin / 8) * a.CoutP * 8 * 4 * a.nphase < ((int64_t)1 << 31),
-               "conv3x3_wino: transformed weights must stay below 2 GiB");
-  a.ntiles = (int)nt;
-  // Small outputs are read back by the next layer from L2/MALL (cached stores measured 1-3 % faster per
-  // step); an output that cannot stay there anyway is streamed (1 % faster per layer).
-  a.nt_out = (int64_t)B * H * W * a.Cout * 4 * (a.nphase == 4 ? 4 : 1) > WINO_NT_BYTES;
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) dev = 0;
-  static bool attr_set_dev[64] = {};
-  bool& attr_set = attr_set_dev[dev];  // per device: the attribute belongs to the device's code object
-  if (!attr_set) {
-    hipError_t e = hipFuncSetAttribute((const void*)conv_wino_kernel<0>,
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, WLDS_TOTAL);
-    if (e == hipSuccess)
-      e = hipFuncSetAttribute((const void*)conv_wino_kernel<1>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                              WLDS_TOTAL);
-    if (e == hipSuccess)
-      e = hipFuncSetAttribute((const void*)conv_wino_kernel<2>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                              WLDS_TOTAL);
-    if (e != hipSuccess) {
-      set_error("conv3x3_wino: hipFuncSetAttribute: %s", hipGetErrorString(e));
-      return DSIC_EHIP;
-    }
-    attr_set = true;
-  }
-  // persistent: one workgroup per CU.  DSIC_WINO_GRID lowers the count when the launching stream
-  // owns fewer CUs (CU-masked streams, dsic_stream_create_masked).
-  // one persistent workgroup per compute unit of THIS device (DSIC_WINO_GRID overrides it for experiments)
-  static int max_grid_dev[64] = {};
-  if (max_grid_dev[dev] == 0) {
-    const char* g = getenv("DSIC_WINO_GRID");
-    int n = g ? atoi(g) : 0;
-    if (n < 1 || n > 1024) {
-      if (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n < 1) n = 256;
-    }
-    max_grid_dev[dev] = n;
-  }
-  const int max_grid = max_grid_dev[dev];
-  const int grid = a.ntiles < max_grid ? a.ntiles : max_grid;
-  if (a.s2d_in)
-    hipLaunchKernelGGL(conv_wino_kernel<1>, dim3(grid), dim3(WTHREADS), WLDS_TOTAL, st, a);
-  else if (a.nphase == 4)
-    hipLaunchKernelGGL(conv_wino_kernel<2>, dim3(grid), dim3(WTHREADS), WLDS_TOTAL, st, a);
-  else
-    hipLaunchKernelGGL(conv_wino_kernel<0>, dim3(grid), dim3(WTHREADS), WLDS_TOTAL, st, a);
-  return check_launch("conv3x3_wino");
+  return wino_launch("conv3x3_wino", "GDN",
+                     {in, u_packed, bias, beta, gamma, out, ticket, B, H, W, Cin, Cout, act, s2d_out, s2d_in ? 1 : 0}, 1,
+                     stream);
 }

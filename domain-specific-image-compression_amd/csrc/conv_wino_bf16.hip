@@ -27,6 +27,7 @@
 //     buffer the MFMA waves are not reading.
 // Tile hand-out, the fold through LDS and the fused epilogue follow conv_wino.hip.
 #include "conv_wino_bf16.h"
+#include "wino_host.h"
 
 namespace dsic {
 namespace wb {
@@ -651,107 +652,62 @@ extern "C" int dsic_split_wino_weight_bf16(const float* u_f32, void* dst, int Co
 
 int dsic_wbm_launch(wb::Args& a, hipStream_t st);   // conv_wino_bf16m.hip
 
+// wb::Args of a layer that check_layer has passed: a dense NHWC output, no split-K
+static wb::Args wb_args(const wino_host::Layer& l, int nphase) {
+  wb::Args a{};
+  a.in = l.in; a.u = l.u; a.bias = l.bias; a.beta = l.beta; a.gamma = l.gamma; a.out = l.out;
+  a.B = l.B; a.H = l.H; a.W = l.W; a.Cin = l.Cin; a.Cout = l.Cout; a.CoutP = round_up(l.Cout, 32); a.act = l.act;
+  a.s2d = l.s2d_out; a.s2d_in = l.s2d_in;
+  a.ticket = (unsigned long long*)l.ticket;
+  a.nphase = nphase; a.u_phase_bytes = dsic_wino_bf16_weight_bytes(l.Cout, l.Cin);
+  return a;
+}
+
 static int wb_launch(wb::Args& a, hipStream_t st) {
-  const int B = a.B, H = a.H, W = a.W;
-  a.tiles_x = ceil_div(W, 16);
-  a.tiles_y = ceil_div(H, 8);
-  const int64_t nt = (int64_t)a.tiles_x * a.tiles_y * B * a.nphase;
+  a.tiles_x = ceil_div(a.W, 16);
+  a.tiles_y = ceil_div(a.H, 8);
+  const int64_t nt = (int64_t)a.tiles_x * a.tiles_y * a.B * a.nphase;
   if (a.ksplit < 1) a.ksplit = 1;
   a.kchunks = a.Cin / wb::CK / a.ksplit;
   DSIC_REQUIRE(a.kchunks * a.ksplit * wb::CK == a.Cin && a.kchunks >= 4 && a.kchunks % 2 == 0 && a.ksplit < 256,
                "conv_wino_bf16: ksplit=%d does not divide Cin=%d into even runs of >= 4 chunks", a.ksplit, a.Cin);
-  DSIC_REQUIRE(nt * a.ksplit < ((int64_t)1 << 31), "conv_wino_bf16: too many tiles");
   if (a.ostride <= 0) a.ostride = a.Cout;
   DSIC_REQUIRE(a.ooff >= 0 && a.ooff % 4 == 0 && a.ostride % 4 == 0 && a.ooff + a.Cout <= a.ostride,
                "conv_wino_bf16: output slice [%d, %d) does not fit a pixel stride of %d channels", a.ooff,
                a.ooff + a.Cout, a.ostride);
   DSIC_REQUIRE(a.ostride == a.Cout || !a.s2d, "conv_wino_bf16: a Cout slice cannot be stored space-to-depth");
-  DSIC_REQUIRE((int64_t)H * W * a.Cin * 4 < ((int64_t)1 << 31) &&
-                   (int64_t)H * W * a.ostride * 4 * (a.nphase == 4 ? 4 : 1) < ((int64_t)1 << 31),
-               "conv_wino_bf16: one image must stay below 2 GiB (32-bit offsets inside an image)");
-  DSIC_REQUIRE(a.u_phase_bytes * a.nphase < ((int64_t)1 << 31), "conv_wino_bf16: transformed weights must stay below 2 GiB");
-  const bool m64 = a.ksplit == 1 && dsic_wino_bf16_m64(H, W, a.Cin, a.nphase);
+  if (const int rc = wino_host::check_limits("conv_wino_bf16", nt * a.ksplit, a.H, a.W, a.Cin,
+                                             (int64_t)a.ostride * (a.nphase == 4 ? 4 : 1), a.u_phase_bytes * a.nphase))
+    return rc;
+  const bool m64 = a.ksplit == 1 && dsic_wino_bf16_m64(a.H, a.W, a.Cin, a.nphase);
   DSIC_REQUIRE(m64 || !(a.cm_in || a.cm_out),
                "conv_wino_bf16: chunk-major activations exist for the layers of the 64-tile kernel only (dsic_wino_bf16_m64)");
   DSIC_REQUIRE(!a.cm_out || (a.ostride == a.Cout && a.ooff == 0 && a.Cout % 16 == 0),
                "conv_wino_bf16: a chunk-major output is a dense tensor of whole 16-channel chunks (Cout=%d)", a.Cout);
+  // split-K partial sums are read back at once by the reduce kernel: never streamed
+  a.nt_out = a.ksplit == 1 && wino_host::streams_output(a.B, a.H, a.W, a.Cout, a.nphase);
   if (m64) return dsic_wbm_launch(a, st);   // large layers: conv_wino_bf16m.hip
   a.ntiles = (int)nt;
-  a.nt_out = a.ksplit == 1 && (int64_t)B * H * W * a.Cout * 4 * (a.nphase == 4 ? 4 : 1) > (300ll << 20);
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess) dev = 0;
-  static bool attr_set[64] = {};
-  if (dev < 0 || dev >= 64) dev = 0;
-  if (!attr_set[dev]) {
-    const void* fns[8] = {(const void*)wb::conv_wino_bf16_kernel<0, false, false>, (const void*)wb::conv_wino_bf16_kernel<1, false, false>,
-                          (const void*)wb::conv_wino_bf16_kernel<2, false, false>, (const void*)wb::conv_wino_bf16_kernel<0, true, false>,
-                          (const void*)wb::conv_wino_bf16_kernel<1, true, false>,  (const void*)wb::conv_wino_bf16_kernel<2, true, false>,
-                          (const void*)wb::conv_wino_bf16_kernel<0, false, true>,  (const void*)wb::conv_wino_bf16_kernel<1, false, true>};
-    for (int i = 0; i < 8; ++i) {
-      const hipError_t e = hipFuncSetAttribute(fns[i], hipFuncAttributeMaxDynamicSharedMemorySize, wb::LDS_TOTAL);
-      if (e != hipSuccess) {
-        set_error("conv_wino_bf16: hipFuncSetAttribute: %s", hipGetErrorString(e));
-        return DSIC_EHIP;
-      }
-    }
-    attr_set[dev] = true;
-  }
-  // one persistent workgroup per compute unit of THIS device (DSIC_WINO_GRID overrides it for experiments)
-  static int max_grid_dev[64] = {};
-  if (max_grid_dev[dev] == 0) {
-    const char* g = getenv("DSIC_WINO_GRID");
-    int n = g ? atoi(g) : 0;
-    if (n < 1 || n > 1024) {
-      if (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n < 1) n = 256;
-    }
-    max_grid_dev[dev] = n;
-  }
-  const int max_grid = max_grid_dev[dev];
-  const int64_t nwork = (int64_t)a.ntiles * a.ksplit;
-  const int grid = nwork < max_grid ? (int)nwork : max_grid;
-#define WB_LAUNCH(M)                                                                                          \
-  do {                                                                                                        \
-    if (a.nt_out)                                                                                             \
-      hipLaunchKernelGGL((wb::conv_wino_bf16_kernel<M, true, false>), dim3(grid), dim3(wb::THREADS), wb::LDS_TOTAL, st, a);  \
-    else                                                                                                      \
-      hipLaunchKernelGGL((wb::conv_wino_bf16_kernel<M, false, false>), dim3(grid), dim3(wb::THREADS), wb::LDS_TOTAL, st, a); \
-  } while (0)
-  if (a.ksplit > 1) {
-    DSIC_REQUIRE(a.nphase == 1, "conv_wino_bf16: split-K exists for the 3x3 layers only");
-    if (a.s2d_in)
-      hipLaunchKernelGGL((wb::conv_wino_bf16_kernel<1, false, true>), dim3(grid), dim3(wb::THREADS), wb::LDS_TOTAL, st, a);
-    else
-      hipLaunchKernelGGL((wb::conv_wino_bf16_kernel<0, false, true>), dim3(grid), dim3(wb::THREADS), wb::LDS_TOTAL, st, a);
-  } else if (a.s2d_in)
-    WB_LAUNCH(1);
-  else if (a.nphase == 4)
-    WB_LAUNCH(2);
-  else
-    WB_LAUNCH(0);
-#undef WB_LAUNCH
-  return check_launch("conv_wino_bf16");
+  using wb::conv_wino_bf16_kernel;
+  static wino_host::Family<8> family = {
+      "conv_wino_bf16", wb::THREADS, wb::LDS_TOTAL,   // MODE + 3 * NT_OUT; split-K (3x3 layers only): 6 + MODE
+      {(const void*)conv_wino_bf16_kernel<0, false, false>, (const void*)conv_wino_bf16_kernel<1, false, false>,
+       (const void*)conv_wino_bf16_kernel<2, false, false>, (const void*)conv_wino_bf16_kernel<0, true, false>,
+       (const void*)conv_wino_bf16_kernel<1, true, false>, (const void*)conv_wino_bf16_kernel<2, true, false>,
+       (const void*)conv_wino_bf16_kernel<0, false, true>, (const void*)conv_wino_bf16_kernel<1, false, true>}};
+  const int mode = a.s2d_in ? 1 : a.nphase == 4 ? 2 : 0;
+  return wino_host::launch(family, a.ksplit > 1 ? 6 + mode : 3 * a.nt_out + mode, nt * a.ksplit, a, st);
 }
 
 extern "C" int dsic_conv3x3_wino_bf16_nhwc(const float* in, const void* u_planes, const float* bias,
                                            const float* beta, const float* gamma, float* out, int B, int H,
                                            int W, int Cin, int Cout, int act, int s2d_out, int s2d_in,
                                            int out_cstride, int out_coff, void* ticket, void* stream) {
-  DSIC_REQUIRE(in && u_planes && bias && out && ticket, "conv3x3_wino_bf16: null pointer");
-  DSIC_REQUIRE(B > 0 && H > 0 && W > 0, "conv3x3_wino_bf16: empty tensor");
-  DSIC_REQUIRE(Cin >= 64 && Cin % 32 == 0, "conv3x3_wino_bf16: Cin=%d must be a multiple of 32, >= 64", Cin);
-  DSIC_REQUIRE(Cout > 0 && Cout % 4 == 0 && Cout <= 128, "conv3x3_wino_bf16: Cout=%d must be a multiple of 4, <= 128", Cout);
-  DSIC_REQUIRE(act >= 0 && act <= 3, "conv3x3_wino_bf16: act=%d", act);
-  DSIC_REQUIRE(!(act == DSIC_ACT_GDN || act == DSIC_ACT_IGDN) || (beta && gamma), "conv3x3_wino_bf16: GDN needs beta and gamma");
-  DSIC_REQUIRE(!(s2d_out & 1) || (H % 2 == 0 && W % 2 == 0), "conv3x3_wino_bf16: space-to-depth output needs even H and W");
-  DSIC_REQUIRE(!(s2d_in & 1) || Cin % 128 == 0, "conv3x3_wino_bf16: space-to-depth input needs Cin = 4*Cs with Cs %% 32 == 0");
-  wb::Args a{};
-  a.in = in; a.u = u_planes; a.bias = bias; a.beta = beta; a.gamma = gamma; a.out = out;
-  a.B = B; a.H = H; a.W = W; a.Cin = Cin; a.Cout = Cout; a.CoutP = round_up(Cout, 32); a.act = act;
-  a.s2d = s2d_out & 1; a.s2d_in = s2d_in & 1;
+  const wino_host::Layer l{in, u_planes, bias, beta, gamma, out, ticket, B, H, W, Cin, Cout, act, s2d_out & 1, s2d_in & 1};
+  if (const int rc = wino_host::check_layer("conv3x3_wino_bf16", "GDN", 64, l)) return rc;
+  wb::Args a = wb_args(l, 1);
   a.cm_out = (s2d_out & DSIC_LAYOUT_CM16) ? 1 : 0; a.cm_in = (s2d_in & DSIC_LAYOUT_CM16) ? 1 : 0;
   a.ostride = out_cstride; a.ooff = out_coff;
-  a.ticket = (unsigned long long*)ticket;
-  a.nphase = 1; a.u_phase_bytes = dsic_wino_bf16_weight_bytes(Cout, Cin);
   return wb_launch(a, (hipStream_t)stream);
 }
 
@@ -773,28 +729,20 @@ extern "C" int dsic_conv3x3_wino_bf16_splitk_nhwc(const float* in, const void* u
                                                   int W, int Cin, int Cout, int act, int s2d_out, int s2d_in,
                                                   int out_cstride, int out_coff, int ksplit, float* partials,
                                                   void* ticket, void* stream) {
-  DSIC_REQUIRE(in && u_planes && bias && out && ticket && partials, "conv3x3_wino_bf16_splitk: null pointer");
-  DSIC_REQUIRE(B > 0 && H > 0 && W > 0, "conv3x3_wino_bf16_splitk: empty tensor");
-  DSIC_REQUIRE(Cin >= 64 && Cin % 32 == 0, "conv3x3_wino_bf16_splitk: Cin=%d must be a multiple of 32, >= 64", Cin);
-  DSIC_REQUIRE(Cout > 0 && Cout % 4 == 0 && Cout <= 128, "conv3x3_wino_bf16_splitk: Cout=%d must be a multiple of 4, <= 128", Cout);
-  DSIC_REQUIRE(act >= 0 && act <= 3, "conv3x3_wino_bf16_splitk: act=%d", act);
-  DSIC_REQUIRE(!(act == DSIC_ACT_GDN || act == DSIC_ACT_IGDN) || (beta && gamma), "conv3x3_wino_bf16_splitk: GDN needs beta and gamma");
-  DSIC_REQUIRE(!s2d_out || (H % 2 == 0 && W % 2 == 0), "conv3x3_wino_bf16_splitk: space-to-depth output needs even H and W");
-  DSIC_REQUIRE(!s2d_in || Cin % 128 == 0, "conv3x3_wino_bf16_splitk: space-to-depth input needs Cin = 4*Cs with Cs %% 32 == 0");
-  DSIC_REQUIRE(ksplit >= 2, "conv3x3_wino_bf16_splitk: ksplit=%d", ksplit);
-  wb::Args a{};
-  a.in = in; a.u = u_planes; a.bias = nullptr; a.beta = nullptr; a.gamma = nullptr; a.out = partials;
-  a.B = B; a.H = H; a.W = W; a.Cin = Cin; a.Cout = Cout; a.CoutP = round_up(Cout, 32); a.act = DSIC_ACT_NONE;
-  DSIC_REQUIRE(!((s2d_out | s2d_in) & DSIC_LAYOUT_CM16), "conv3x3_wino_bf16_splitk: chunk-major activations are not supported");
-  a.s2d = s2d_out & 1; a.s2d_in = s2d_in & 1;
+  const char* what = "conv3x3_wino_bf16_splitk";
+  const wino_host::Layer l{in, u_planes, bias, beta, gamma, out, ticket, B, H, W, Cin, Cout, act, s2d_out & 1, s2d_in & 1};
+  if (const int rc = wino_host::check_layer(what, "GDN", 64, l)) return rc;
+  DSIC_REQUIRE(partials, "%s: null pointer", what);
+  DSIC_REQUIRE(ksplit >= 2, "%s: ksplit=%d", what, ksplit);
+  DSIC_REQUIRE(!((s2d_out | s2d_in) & DSIC_LAYOUT_CM16), "%s: chunk-major activations are not supported", what);
+  // the kernel writes un-biased, un-activated partial sums; splitk_reduce_kernel finishes them
+  wb::Args a = wb_args(l, 1);
+  a.bias = nullptr; a.beta = nullptr; a.gamma = nullptr; a.out = partials; a.act = DSIC_ACT_NONE;
   a.ostride = out_cstride; a.ooff = out_coff;
-  a.ticket = (unsigned long long*)ticket;
-  a.nphase = 1; a.u_phase_bytes = dsic_wino_bf16_weight_bytes(Cout, Cin);
   a.ksplit = ksplit;
   const int ostride = out_cstride > 0 ? out_cstride : Cout;
   a.part_stride = (int64_t)B * H * W * ostride;
-  const int rc = wb_launch(a, (hipStream_t)stream);
-  if (rc != DSIC_OK) return rc;
+  if (const int rc = wb_launch(a, (hipStream_t)stream)) return rc;
   // the space-to-depth output is a [B, H/2, W/2, 4*Cout] tensor: channel of the bias = index mod Cout
   const int64_t npix = s2d_out ? (int64_t)B * (H / 2) * (W / 2) : (int64_t)B * H * W;
   const int C = s2d_out ? 4 * Cout : Cout, rstride = s2d_out ? 4 * Cout : ostride;
@@ -808,20 +756,7 @@ extern "C" int dsic_conv3x3_wino_bf16_splitk_nhwc(const float* in, const void* u
   else if (act == DSIC_ACT_RELU) WB_REDUCE(DSIC_ACT_RELU);
   else WB_REDUCE(DSIC_ACT_NONE);
 #undef WB_REDUCE
-  return check_launch("conv3x3_wino_bf16_splitk");
-}
-
-extern "C" int dsic_conv_transpose2d_wino_bf16_layout(const float* in, const void* u_planes4, const float* bias,
-                                                      const float* beta, const float* gamma, float* out, int B,
-                                                      int H, int W, int Cin, int Cout, int act, int layout_in,
-                                                      int layout_out, void* ticket, void* stream);
-
-extern "C" int dsic_conv_transpose2d_wino_bf16_nhwc(const float* in, const void* u_planes4, const float* bias,
-                                                    const float* beta, const float* gamma, float* out, int B,
-                                                    int H, int W, int Cin, int Cout, int act, void* ticket,
-                                                    void* stream) {
-  return dsic_conv_transpose2d_wino_bf16_layout(in, u_planes4, bias, beta, gamma, out, B, H, W, Cin, Cout, act, 0, 0,
-                                                ticket, stream);
+  return check_launch(what);
 }
 
 // layout_in / layout_out: 0 = NHWC, DSIC_LAYOUT_CM16 = chunk-major [B][C/16][H][W][16] (64-tile kernel only)
@@ -831,17 +766,17 @@ extern "C" int dsic_conv_transpose2d_wino_bf16_layout(const float* in, const voi
                                                       int layout_out, void* ticket, void* stream) {
   DSIC_REQUIRE((layout_in == 0 || layout_in == DSIC_LAYOUT_CM16) && (layout_out == 0 || layout_out == DSIC_LAYOUT_CM16),
                "convT_wino_bf16: layout_in=%d layout_out=%d", layout_in, layout_out);
-  DSIC_REQUIRE(in && u_planes4 && bias && out && ticket, "convT_wino_bf16: null pointer");
-  DSIC_REQUIRE(B > 0 && H > 0 && W > 0, "convT_wino_bf16: empty tensor");
-  DSIC_REQUIRE(Cin >= 64 && Cin % 32 == 0, "convT_wino_bf16: Cin=%d must be a multiple of 32, >= 64", Cin);
-  DSIC_REQUIRE(Cout > 0 && Cout % 4 == 0 && Cout <= 128, "convT_wino_bf16: Cout=%d must be a multiple of 4, <= 128", Cout);
-  DSIC_REQUIRE(act >= 0 && act <= 3, "convT_wino_bf16: act=%d", act);
-  DSIC_REQUIRE(!(act == DSIC_ACT_GDN || act == DSIC_ACT_IGDN) || (beta && gamma), "convT_wino_bf16: IGDN needs beta and gamma");
-  wb::Args a{};
-  a.in = in; a.u = u_planes4; a.bias = bias; a.beta = beta; a.gamma = gamma; a.out = out;
-  a.B = B; a.H = H; a.W = W; a.Cin = Cin; a.Cout = Cout; a.CoutP = round_up(Cout, 32); a.act = act;
-  a.ticket = (unsigned long long*)ticket;
-  a.s2d = 0; a.s2d_in = 0; a.nphase = 4; a.u_phase_bytes = dsic_wino_bf16_weight_bytes(Cout, Cin);
+  const wino_host::Layer l{in, u_planes4, bias, beta, gamma, out, ticket, B, H, W, Cin, Cout, act, 0, 0};
+  if (const int rc = wino_host::check_layer("convT_wino_bf16", "IGDN", 64, l)) return rc;
+  wb::Args a = wb_args(l, 4);
   a.cm_in = layout_in ? 1 : 0; a.cm_out = layout_out ? 1 : 0;
   return wb_launch(a, (hipStream_t)stream);
+}
+
+extern "C" int dsic_conv_transpose2d_wino_bf16_nhwc(const float* in, const void* u_planes4, const float* bias,
+                                                    const float* beta, const float* gamma, float* out, int B,
+                                                    int H, int W, int Cin, int Cout, int act, void* ticket,
+                                                    void* stream) {
+  return dsic_conv_transpose2d_wino_bf16_layout(in, u_planes4, bias, beta, gamma, out, B, H, W, Cin, Cout, act, 0, 0,
+                                                ticket, stream);
 }

@@ -32,6 +32,7 @@
 // conv_wino_bf16.hip with 64 tiles x 8 positions in place of 32 x 16; the same packed weights serve both kernels.
 #include "conv_wino_bf16.h"
 #include "conv_wino_pair.h"
+#include "wino_host.h"
 
 #ifndef WBM_STAMP
 #define WBM_STAMP 0   // diagnostic: cycle stamps of the MFMA waves 0 (PQ 0) and 4 (PQ 1) and of helper wave 8 (tools/wbm_stamps.py)
@@ -924,59 +925,20 @@ extern "C" int dsic_wino_pair_schedule(int mode, int nchunks, int phase, int pai
 #undef WBM_SEQ
 }
 
+// wb_launch (conv_wino_bf16.hip) has checked the layer and chosen this kernel for it; what is left is the 64-tile
+// kernel's own: 16x16-pixel tiles, the pass-B pairing, its instances and its launch.
 int dsic_wbm_launch(wb::Args& a, hipStream_t st) {
   a.tiles_x = a.W / 16;
   a.tiles_y = a.H / 16;
-  const int64_t nt = (int64_t)a.tiles_x * a.tiles_y * a.B * a.nphase;
-  DSIC_REQUIRE(nt < ((int64_t)1 << 31), "conv_wino_bf16m: too many tiles");
-  DSIC_REQUIRE((a.Cin / wbm::CK) % 2 == 0 && a.Cin / wbm::CK >= 4, "conv_wino_bf16m: Cin=%d", a.Cin);
-  if (a.ostride <= 0) a.ostride = a.Cout;
-  a.ntiles = (int)nt;
-  a.ksplit = 1;
+  a.ntiles = a.tiles_x * a.tiles_y * a.B * a.nphase;   // no more than the 16x8-pixel tiles wb_launch has counted
   a.pair_b = dsic_wino_pair_chunks(-1);
-  a.nt_out = (int64_t)a.B * a.H * a.W * a.Cout * 4 * (a.nphase == 4 ? 4 : 1) > (300ll << 20);
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess) dev = 0;
-  if (dev < 0 || dev >= 64) dev = 0;
-  static bool attr_set[64] = {};
-  if (!attr_set[dev]) {
-    const void* fns[6] = {(const void*)wbm::conv_wino_bf16m_kernel<0, false>, (const void*)wbm::conv_wino_bf16m_kernel<1, false>,
-                          (const void*)wbm::conv_wino_bf16m_kernel<2, false>, (const void*)wbm::conv_wino_bf16m_kernel<0, true>,
-                          (const void*)wbm::conv_wino_bf16m_kernel<1, true>,  (const void*)wbm::conv_wino_bf16m_kernel<2, true>};
-    for (int i = 0; i < 6; ++i) {
-      const hipError_t e = hipFuncSetAttribute(fns[i], hipFuncAttributeMaxDynamicSharedMemorySize, wbm::LDS_TOTAL);
-      if (e != hipSuccess) {
-        set_error("conv_wino_bf16m: hipFuncSetAttribute: %s", hipGetErrorString(e));
-        return DSIC_EHIP;
-      }
-    }
-    attr_set[dev] = true;
-  }
-  static int max_grid_dev[64] = {};
-  if (max_grid_dev[dev] == 0) {   // one persistent workgroup per compute unit (DSIC_WINO_GRID: experiments)
-    const char* g = getenv("DSIC_WINO_GRID");
-    int n = g ? atoi(g) : 0;
-    if (n < 1 || n > 1024) {
-      if (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n < 1) n = 256;
-    }
-    max_grid_dev[dev] = n;
-  }
-  const int grid = nt < max_grid_dev[dev] ? (int)nt : max_grid_dev[dev];
-#define WBM_LAUNCH(M)                                                                                            \
-  do {                                                                                                           \
-    if (a.nt_out)                                                                                                \
-      hipLaunchKernelGGL((wbm::conv_wino_bf16m_kernel<M, true>), dim3(grid), dim3(wbm::THREADS), wbm::LDS_TOTAL, st, a);  \
-    else                                                                                                         \
-      hipLaunchKernelGGL((wbm::conv_wino_bf16m_kernel<M, false>), dim3(grid), dim3(wbm::THREADS), wbm::LDS_TOTAL, st, a); \
-  } while (0)
-  if (a.s2d_in)
-    WBM_LAUNCH(1);
-  else if (a.nphase == 4)
-    WBM_LAUNCH(2);
-  else
-    WBM_LAUNCH(0);
-#undef WBM_LAUNCH
-  return check_launch("conv_wino_bf16m");
+  using wbm::conv_wino_bf16m_kernel;
+  static wino_host::Family<6> family = {
+      "conv_wino_bf16m", wbm::THREADS, wbm::LDS_TOTAL,   // MODE + 3 * NT_OUT
+      {(const void*)conv_wino_bf16m_kernel<0, false>, (const void*)conv_wino_bf16m_kernel<1, false>,
+       (const void*)conv_wino_bf16m_kernel<2, false>, (const void*)conv_wino_bf16m_kernel<0, true>,
+       (const void*)conv_wino_bf16m_kernel<1, true>, (const void*)conv_wino_bf16m_kernel<2, true>}};
+  return wino_host::launch(family, 3 * a.nt_out + (a.s2d_in ? 1 : a.nphase == 4 ? 2 : 0), a.ntiles, a, st);
 }
 
 #if WBM_STAMP

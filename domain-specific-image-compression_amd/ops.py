@@ -84,41 +84,40 @@ def round_up(a: int, b: int) -> int:
     return (a + b - 1) // b * b
 
 
+def _pack(name, w, k, size, call, dtype=torch.float32):
+    """One weight packer: w [C0,C1,k,k] (k None: any square kernel) -> size(L, C0, C1, k) elements of dtype on w's
+    device, written by call(L, pointer to w, pointer to them, C0, C1, k)."""
+    w = _f32c(w, name)
+    C0, C1, kh, kw = w.shape
+    if k is None:
+        assert kh == kw
+    elif (kh, kw) != (k, k):
+        raise ValueError(f"{name}: kernel must be {k}x{k}")
+    L = _lib.load()
+    dst = torch.empty(size(L, C0, C1, kh), dtype=dtype, device=w.device)
+    _lib.check(call(L, _p(w), _p(dst), C0, C1, kh), name)
+    return dst
+
+
 def pack_conv_weight(w: torch.Tensor) -> torch.Tensor:
     """nn.Conv2d weight [Cout,Cin,k,k] -> [k*k][CinP/8][CoutP][8]."""
-    w = _f32c(w, "pack_conv_weight")
-    Cout, Cin, k, k2 = w.shape
-    assert k == k2
-    L = _lib.load()
-    n = L.dsic_packed_conv_weight_floats(Cout, Cin, k)
-    dst = torch.empty(n, dtype=torch.float32, device=w.device)
-    _lib.check(L.dsic_pack_conv_weight(_p(w), _p(dst), Cout, Cin, k, _stream()), "pack_conv_weight")
-    return dst
+    return _pack("pack_conv_weight", w, None, lambda L, Cout, Cin, k: L.dsic_packed_conv_weight_floats(Cout, Cin, k),
+                 lambda L, w, dst, Cout, Cin, k: L.dsic_pack_conv_weight(w, dst, Cout, Cin, k, _stream()))
 
 
 def pack_convT_weight(w: torch.Tensor) -> torch.Tensor:
     """nn.ConvTranspose2d weight [Cin,Cout,5,5] -> four phase kernels, 25 taps."""
-    w = _f32c(w, "pack_convT_weight")
-    Cin, Cout, k, k2 = w.shape
-    if (k, k2) != (5, 5):
-        raise ValueError("pack_convT_weight: kernel must be 5x5")
-    dst = torch.empty(25 * (Cin // 8) * round_up(Cout, 32) * 8, dtype=torch.float32, device=w.device)
-    _lib.check(_lib.load().dsic_pack_convT_weight(_p(w), _p(dst), Cin, Cout, _stream()),
-               "pack_convT_weight")
-    return dst
+    return _pack("pack_convT_weight", w, 5, lambda L, Cin, Cout, k: 25 * (Cin // 8) * round_up(Cout, 32) * 8,
+                 lambda L, w, dst, Cin, Cout, k: L.dsic_pack_convT_weight(w, dst, Cin, Cout, _stream()))
 
 
 def pack_convT_image_weight(w: torch.Tensor) -> torch.Tensor:
-    w = _f32c(w, "pack_convT_image_weight")
-    Cin, Cimg, k, k2 = w.shape
-    if (k, k2) != (5, 5):
-        raise ValueError("pack_convT_image_weight: kernel must be 5x5")
-    if Cin % 16 or not 1 <= Cimg <= 4:
-        raise ValueError("pack_convT_image_weight: Cin must be a multiple of 16 and Cimg in [1,4]")
-    dst = torch.empty(_lib.load().dsic_convT_image_weight_floats(Cin), dtype=torch.float32, device=w.device)
-    _lib.check(_lib.load().dsic_pack_convT_image_weight(_p(w), _p(dst), Cin, Cimg, _stream()),
-               "pack_convT_image_weight")
-    return dst
+    def size(L, Cin, Cimg, k):
+        if Cin % 16 or not 1 <= Cimg <= 4:
+            raise ValueError("pack_convT_image_weight: Cin must be a multiple of 16 and Cimg in [1,4]")
+        return L.dsic_convT_image_weight_floats(Cin)
+    return _pack("pack_convT_image_weight", w, 5, size,
+                 lambda L, w, dst, Cin, Cimg, k: L.dsic_pack_convT_image_weight(w, dst, Cin, Cimg, _stream()))
 
 
 def image_to_nhwc8(x: torch.Tensor) -> torch.Tensor:
@@ -164,26 +163,14 @@ def conv2d_nhwc(x, w_packed, bias, Cout, k, stride, act=ACT_NONE, beta=None, gam
 
 def pack_wino_weight(w: torch.Tensor) -> torch.Tensor:
     """nn.Conv2d 3x3 weight [Cout,Cin,3,3] -> Winograd-domain U = G g G^T, [16][Cin/8][CoutP][8]."""
-    w = _f32c(w, "pack_wino_weight")
-    Cout, Cin, k, k2 = w.shape
-    if (k, k2) != (3, 3):
-        raise ValueError("pack_wino_weight: kernel must be 3x3")
-    L = _lib.load()
-    dst = torch.empty(L.dsic_wino_weight_floats(Cout, Cin), dtype=torch.float32, device=w.device)
-    _lib.check(L.dsic_pack_wino_weight(_p(w), _p(dst), Cout, Cin, _stream()), "pack_wino_weight")
-    return dst
+    return _pack("pack_wino_weight", w, 3, lambda L, Cout, Cin, k: L.dsic_wino_weight_floats(Cout, Cin),
+                 lambda L, w, dst, Cout, Cin, k: L.dsic_pack_wino_weight(w, dst, Cout, Cin, _stream()))
 
 
 def pack_wino_s2_weight(w: torch.Tensor) -> torch.Tensor:
     """5x5 stride-2 weight [Cout,Cs,5,5] -> Winograd U of the equivalent 3x3 conv over 4*Cs s2d channels."""
-    w = _f32c(w, "pack_wino_s2_weight")
-    Cout, Cs, k, k2 = w.shape
-    if (k, k2) != (5, 5):
-        raise ValueError("pack_wino_s2_weight: kernel must be 5x5")
-    L = _lib.load()
-    dst = torch.empty(L.dsic_wino_weight_floats(Cout, 4 * Cs), dtype=torch.float32, device=w.device)
-    _lib.check(L.dsic_pack_wino_s2_weight(_p(w), _p(dst), Cout, Cs, _stream()), "pack_wino_s2_weight")
-    return dst
+    return _pack("pack_wino_s2_weight", w, 5, lambda L, Cout, Cs, k: L.dsic_wino_weight_floats(Cout, 4 * Cs),
+                 lambda L, w, dst, Cout, Cs, k: L.dsic_pack_wino_s2_weight(w, dst, Cout, Cs, _stream()))
 
 
 _tickets = {}
@@ -201,14 +188,8 @@ def _ticket(device):
 
 def pack_wino_convT_weight(w: torch.Tensor) -> torch.Tensor:
     """ConvTranspose2d weight [Cin,Cout,5,5] -> Winograd U of its four 3x3 sub-pixel phase convs."""
-    w = _f32c(w, "pack_wino_convT_weight")
-    Cin, Cout, k, k2 = w.shape
-    if (k, k2) != (5, 5):
-        raise ValueError("pack_wino_convT_weight: kernel must be 5x5")
-    L = _lib.load()
-    dst = torch.empty(4 * L.dsic_wino_weight_floats(Cout, Cin), dtype=torch.float32, device=w.device)
-    _lib.check(L.dsic_pack_wino_convT_weight(_p(w), _p(dst), Cin, Cout, _stream()), "pack_wino_convT_weight")
-    return dst
+    return _pack("pack_wino_convT_weight", w, 5, lambda L, Cin, Cout, k: 4 * L.dsic_wino_weight_floats(Cout, Cin),
+                 lambda L, w, dst, Cin, Cout, k: L.dsic_pack_wino_convT_weight(w, dst, Cin, Cout, _stream()))
 
 
 def split_wino_weight_bf16(u_f32: torch.Tensor, Cout: int, Cin: int, nphase: int = 1) -> torch.Tensor:
@@ -223,6 +204,17 @@ def wino_bf16_planes() -> int:
     return int(_lib.load().dsic_wino_bf16_planes())
 
 
+def _wino_exec_flops(tiles, positions, nprod, Cin, CoutP):
+    """FLOPs the MFMA pipe executes in a Winograd launch: `tiles` 2x2-output tiles (border padding included) of
+    `positions` live Winograd positions (16; 12.25 on average with a space-to-depth input or the phases of a
+    transposed layer), `nprod` bf16 products per position (1: the fp32 kernel), Cin x CoutP each."""
+    return 2.0 * nprod * tiles * positions * Cin * CoutP
+
+
+def _wino_bf16_products():
+    return 3 if wino_bf16_planes() == 2 else 6
+
+
 def conv_transpose2d_wino_nhwc(x, u_packed4, bias, Cout, act=ACT_NONE, beta=None, gamma=None, out=None,
                                cm_in=False, cm_out=False):
     """ConvTranspose2d(Cin,Cout,5,2,2,1) + fused activation: four Winograd 3x3 phase convs.
@@ -235,27 +227,23 @@ def conv_transpose2d_wino_nhwc(x, u_packed4, bias, Cout, act=ACT_NONE, beta=None
         out = torch.empty(_act_shape(B, 2 * H, 2 * W, Cout, cm_out), dtype=torch.float32, device=x.device)
     L = _lib.load()
     wino_tiles = 4 * B * (-(-H // 8)) * (-(-W // 16)) * 32
+
+    def args(*layouts):
+        return (_p(x), _p(u_packed4), _p(bias), _p(beta), _p(gamma), _p(out), B, H, W, Cin, Cout, act, *layouts,
+                _p(_ticket(x.device)), _stream())
     if u_packed4.dtype == torch.uint8:
-        nprod = 3 if wino_bf16_planes() == 2 else 6
+        nprod = _wino_bf16_products()
         # large layers run on the 64-tile two-pass kernel (conv_wino_bf16m.hip): the symbol the profiler will show
-        m64 = bool(L.dsic_wino_bf16_m64(H, W, Cin, 4))
-        lay_in, lay_out = LAYOUT_CM16 if cm_in else 0, LAYOUT_CM16 if cm_out else 0
-        _timed("conv_wino_bf16m_kernel<2>" if m64 else "conv_wino_bf16_kernel<2>", 2.0 * B * H * W * Cout * Cin * 25,
-               lambda: _lib.check(L.dsic_conv_transpose2d_wino_bf16_layout(_p(x), _p(u_packed4), _p(bias), _p(beta),
-                                                                           _p(gamma), _p(out), B, H, W, Cin, Cout, act,
-                                                                           lay_in, lay_out, _p(_ticket(x.device)),
-                                                                           _stream()),
-                                  "conv_transpose2d_wino_bf16_layout"),
-               exec_flops=2.0 * nprod * wino_tiles * 12.25 * Cin * round_up(Cout, 32))
-        return out
-    if cm_in or cm_out:
+        name = "conv_wino_bf16m_kernel<2>" if L.dsic_wino_bf16_m64(H, W, Cin, 4) else "conv_wino_bf16_kernel<2>"
+        what, call = "conv_transpose2d_wino_bf16_layout", lambda: L.dsic_conv_transpose2d_wino_bf16_layout(
+            *args(LAYOUT_CM16 if cm_in else 0, LAYOUT_CM16 if cm_out else 0))
+    elif cm_in or cm_out:
         raise ValueError("conv_transpose2d_wino_nhwc: chunk-major activations need the split-bf16 kernel")
-    _timed("conv_wino_kernel<2>", 2.0 * B * H * W * Cout * Cin * 25,
-           lambda: _lib.check(L.dsic_conv_transpose2d_wino_nhwc(_p(x), _p(u_packed4), _p(bias), _p(beta), _p(gamma),
-                                                                _p(out), B, H, W, Cin, Cout, act, _p(_ticket(x.device)),
-                                                                _stream()),
-                              "conv_transpose2d_wino_nhwc"),
-           exec_flops=2.0 * wino_tiles * 12.25 * Cin * round_up(Cout, 32))
+    else:
+        nprod, name = 1, "conv_wino_kernel<2>"
+        what, call = "conv_transpose2d_wino_nhwc", lambda: L.dsic_conv_transpose2d_wino_nhwc(*args())
+    _timed(name, 2.0 * B * H * W * Cout * Cin * 25, lambda: _lib.check(call(), what),
+           exec_flops=_wino_exec_flops(wino_tiles, 12.25, nprod, Cin, round_up(Cout, 32)))
     return out
 
 
@@ -288,6 +276,11 @@ def _act_shape(B, H, W, C, cm):
     return (B, C // 16, H, W, 16) if cm else (B, H, W, C)
 
 
+def _out_shape(B, H, W, Cout, s2d_out, cm_out):
+    """Output of a stride-1 layer over [B,H,W,.]: stored space-to-depth it is [B,H/2,W/2,4*Cout]."""
+    return _act_shape(B, H // 2, W // 2, 4 * Cout, cm_out) if s2d_out else _act_shape(B, H, W, Cout, cm_out)
+
+
 def cm16_to_nhwc(x_cm):
     B, H, W, C = cm16_shape(x_cm)
     return x_cm.permute(0, 2, 3, 1, 4).reshape(B, H, W, C).contiguous()
@@ -307,46 +300,37 @@ def conv3x3_wino_nhwc(x, u_packed, bias, Cout, act=ACT_NONE, beta=None, gamma=No
     x = _f32c(x, "conv3x3_wino_nhwc")
     B, H, W, Cin = cm16_shape(x) if cm_in else x.shape
     if out is None:
-        shape = _act_shape(B, H // 2, W // 2, 4 * Cout, cm_out) if s2d_out else _act_shape(B, H, W, Cout, cm_out)
-        out = torch.empty(shape, dtype=torch.float32, device=x.device)
+        out = torch.empty(_out_shape(B, H, W, Cout, s2d_out, cm_out), dtype=torch.float32, device=x.device)
     L = _lib.load()
     wino_tiles = B * (-(-H // 8)) * (-(-W // 16)) * 32          # 2x2-output tiles incl. border padding
-    if (cm_in or cm_out) and u_packed.dtype != torch.uint8:
+    bf16 = u_packed.dtype == torch.uint8                         # bf16 planes: split-bf16 kernel
+    if (cm_in or cm_out) and not bf16:
         raise ValueError("conv3x3_wino_nhwc: chunk-major activations need the split-bf16 kernel")
-    lay_in, lay_out = LAYOUT_CM16 if cm_in else 0, LAYOUT_CM16 if cm_out else 0
-    if u_packed.dtype == torch.uint8:                            # bf16 planes: split-bf16 kernel
-        nprod = 3 if wino_bf16_planes() == 2 else 6
-        ksplit = L.dsic_wino_bf16_ksplit(H, W, Cin) if (WINO_SPLITK and split_k) else 1
-        if ksplit > 1 and not (cm_in or cm_out):
-            # few tiles per image: the input channels of a tile are shared by `ksplit` work items
-            partials = torch.empty((ksplit,) + tuple(out.shape), dtype=torch.float32, device=x.device)
-            _timed("conv_wino_bf16_kernel<1>" if s2d_in else "conv_wino_bf16_kernel<0>",
-                   algo_flops if algo_flops is not None else 2.0 * B * H * W * Cout * Cin * 9,
-                   lambda: _lib.check(L.dsic_conv3x3_wino_bf16_splitk_nhwc(
-                       _p(x), _p(u_packed), _p(bias), _p(beta), _p(gamma), _p(out), B, H, W, Cin, Cout, act,
-                       int(bool(s2d_out)), int(bool(s2d_in)), 0 if s2d_out else int(out.shape[-1]), int(out_coff),
-                       ksplit, _p(partials), _p(_ticket(x.device)), _stream()), "conv3x3_wino_bf16_splitk_nhwc"),
-                   exec_flops=2.0 * nprod * wino_tiles * (12.25 if s2d_in else 16) * Cin * round_up(Cout, 32))
-            return out
+    mode, s2d_o, s2d_i = (1 if s2d_in else 0), int(bool(s2d_out)), int(bool(s2d_in))
+
+    def args(*rest):
+        return (_p(x), _p(u_packed), _p(bias), _p(beta), _p(gamma), _p(out), B, H, W, Cin, Cout, act, *rest,
+                _p(_ticket(x.device)), _stream())
+    ksplit = L.dsic_wino_bf16_ksplit(H, W, Cin) if (bf16 and WINO_SPLITK and split_k) else 1
+    if not bf16:
+        name = f"conv_wino_kernel<{mode}>"
+        what, call = "conv3x3_wino_nhwc", lambda: L.dsic_conv3x3_wino_nhwc(*args(s2d_o, s2d_i))
+    elif ksplit > 1 and not (cm_in or cm_out):
+        # few tiles per image: the input channels of a tile are shared by `ksplit` work items
+        partials = torch.empty((ksplit,) + tuple(out.shape), dtype=torch.float32, device=x.device)
+        name = f"conv_wino_bf16_kernel<{mode}>"
+        what, call = "conv3x3_wino_bf16_splitk_nhwc", lambda: L.dsic_conv3x3_wino_bf16_splitk_nhwc(*args(
+            s2d_o, s2d_i, 0 if s2d_out else int(out.shape[-1]), int(out_coff), ksplit, _p(partials)))
+    else:
         m64 = "m" if L.dsic_wino_bf16_m64(H, W, Cin, 1) else ""   # 64-tile two-pass kernel (conv_wino_bf16m.hip)
-        _timed(f"conv_wino_bf16{m64}_kernel<1>" if s2d_in else f"conv_wino_bf16{m64}_kernel<0>",
-               algo_flops if algo_flops is not None else 2.0 * B * H * W * Cout * Cin * 9,
-               lambda: _lib.check(L.dsic_conv3x3_wino_bf16_nhwc(_p(x), _p(u_packed), _p(bias), _p(beta), _p(gamma),
-                                                                _p(out), B, H, W, Cin, Cout, act,
-                                                                int(bool(s2d_out)) | lay_out, int(bool(s2d_in)) | lay_in,
-                                                                0 if (s2d_out or cm_out) else int(out.shape[-1]),
-                                                                int(out_coff),
-                                                                _p(_ticket(x.device)), _stream()),
-                                  "conv3x3_wino_bf16_nhwc"),
-               exec_flops=2.0 * nprod * wino_tiles * (12.25 if s2d_in else 16) * Cin * round_up(Cout, 32))
-        return out
-    _timed("conv_wino_kernel<1>" if s2d_in else "conv_wino_kernel<0>",
-           algo_flops if algo_flops is not None else 2.0 * B * H * W * Cout * Cin * 9,
-           lambda: _lib.check(L.dsic_conv3x3_wino_nhwc(_p(x), _p(u_packed), _p(bias), _p(beta), _p(gamma), _p(out),
-                                                       B, H, W, Cin, Cout, act, int(bool(s2d_out)), int(bool(s2d_in)),
-                                                       _p(_ticket(x.device)), _stream()),
-                              "conv3x3_wino_nhwc"),
-           exec_flops=2.0 * wino_tiles * (12.25 if s2d_in else 16) * Cin * round_up(Cout, 32))
+        name = f"conv_wino_bf16{m64}_kernel<{mode}>"
+        what, call = "conv3x3_wino_bf16_nhwc", lambda: L.dsic_conv3x3_wino_bf16_nhwc(*args(
+            s2d_o | (LAYOUT_CM16 if cm_out else 0), s2d_i | (LAYOUT_CM16 if cm_in else 0),
+            0 if (s2d_out or cm_out) else int(out.shape[-1]), int(out_coff)))
+    _timed(name, algo_flops if algo_flops is not None else 2.0 * B * H * W * Cout * Cin * 9,
+           lambda: _lib.check(call(), what),
+           exec_flops=_wino_exec_flops(wino_tiles, 12.25 if s2d_in else 16, _wino_bf16_products() if bf16 else 1, Cin,
+                                       round_up(Cout, 32)))
     return out
 
 
@@ -371,25 +355,16 @@ def conv_first_nchw(x, w, bias, act=ACT_NONE, beta=None, gamma=None, s2d_out=Fal
     if x.dtype == torch.uint8:
         if not x.is_cuda:
             raise RuntimeError(f"conv_first_nchw: expected a tensor on the GPU (no CPU fallback), got {x.device}")
-        x = x.contiguous()
+        x, what = x.contiguous(), "conv_first_u8hwc"
         B, H, W, C = x.shape
-        shape = _act_shape(B, H // 2, W // 2, 4 * Cout, cm_out) if s2d_out else _act_shape(B, H, W, Cout, cm_out)
-        out = torch.empty(shape, dtype=torch.float32, device=x.device)
-        L = _lib.load()
-        _timed(f"conv_first_kernel<{C}>", 2.0 * B * H * W * Cout * C * 9,
-               lambda: _lib.check(L.dsic_conv_first_u8hwc(_p(x), _p(w), _p(bias), _p(beta), _p(gamma), _p(out), B, C,
-                                                          H, W, Cout, act, flag, _stream()),
-                                  "conv_first_u8hwc"))
-        return out
-    x = _f32c(x, "conv_first_nchw")
-    B, C, H, W = x.shape
-    shape = _act_shape(B, H // 2, W // 2, 4 * Cout, cm_out) if s2d_out else _act_shape(B, H, W, Cout, cm_out)
-    out = torch.empty(shape, dtype=torch.float32, device=x.device)
-    L = _lib.load()
+    else:
+        x, what = _f32c(x, "conv_first_nchw"), "conv_first_nchw"
+        B, C, H, W = x.shape
+    out = torch.empty(_out_shape(B, H, W, Cout, s2d_out, cm_out), dtype=torch.float32, device=x.device)
+    fn = getattr(_lib.load(), "dsic_" + what)
     _timed(f"conv_first_kernel<{C}>", 2.0 * B * H * W * Cout * C * 9,
-           lambda: _lib.check(L.dsic_conv_first_nchw(_p(x), _p(w), _p(bias), _p(beta), _p(gamma), _p(out), B, C,
-                                                     H, W, Cout, act, flag, _stream()),
-                              "conv_first_nchw"))
+           lambda: _lib.check(fn(_p(x), _p(w), _p(bias), _p(beta), _p(gamma), _p(out), B, C, H, W, Cout, act, flag,
+                                 _stream()), what))
     return out
 
 

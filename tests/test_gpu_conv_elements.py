@@ -430,6 +430,31 @@ def test_refusals_leave_the_output_untouched(ops, L):
             assert out.untouched(), match
 
 
+# ---------------------------------------------------------------------------------------------------- streamed stores
+
+def test_streamed_output_of_the_32_tile_kernel_equals_the_cached_one(ops):
+    """Outputs above 300 MiB leave the 32-tile split-bf16 kernel through its streaming-store instance (NT_OUT), which
+    only a layer the 64-tile kernel does not take can reach: 280 is no multiple of 16, and 8 x 280 x 280 x 128 floats
+    are 321 MB.  The same images four at a time are 160 MB per call and take the cached-store instance; a patch's
+    bits do not depend on its batch, so all 8 images agree bit for bit."""
+    B, H, W, Cin, Cout = 8, 280, 280, 64, 128
+    g = torch.Generator(device="cuda").manual_seed(280)
+    x = torch.randn((B, H, W, Cin), device="cuda", generator=g)
+    w = torch.randn((Cout, Cin, 3, 3), device="cuda", generator=g) / 24
+    bias = torch.randn(Cout, device="cuda", generator=g)
+    u = ops.split_wino_weight_bf16(ops.pack_wino_weight(w), Cout, Cin)
+    whole = ops.conv3x3_wino_nhwc(x, u, bias, Cout, split_k=False)
+    assert 4 * whole.numel() > 300 << 20 > 2 * whole.numel() and tuple(whole.shape) == (B, H, W, Cout)
+    halves = [ops.conv3x3_wino_nhwc(x[i:i + 4], u, bias, Cout, split_k=False) for i in (0, 4)]
+    torch.cuda.synchronize()
+    _seen.add("conv_wino_bf16_kernel<0> split-bf16 streamed stores")
+    assert not bool(ops._ticket(x.device).any())
+    assert bool(torch.isfinite(whole).all()) and float(whole.abs().max()) > 1.0
+    for b in range(B):
+        assert torch.equal(whole[b].view(torch.int32), halves[b // 4][b % 4].view(torch.int32)), \
+            f"image {b}: the streamed and the cached stores give other bits"
+
+
 # ---------------------------------------------------------------------------------------------------- the report
 
 def test_worst_ratios_reported():
