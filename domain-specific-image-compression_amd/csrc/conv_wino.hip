@@ -728,6 +728,9 @@ static int wino_launch(const char* what, const char* gdn, const wino_host::Layer
   return wino_host::launch(family, a.s2d_in ? 1 : nphase == 4 ? 2 : 0, nt, a, (hipStream_t)stream);
 }
 
+// The cap of every Winograd kernel's persistent grid (wino_host::persistent_grid), for all three translation units.
+extern "C" int dsic_wino_grid(int n) { return wino_host::set_grid_override(n); }
+
 extern "C" int dsic_conv_transpose2d_wino_nhwc(const float* in, const float* u_packed4, const float* bias,
                                                const float* beta, const float* gamma, float* out, int B,
                                                int H, int W, int Cin, int Cout, int act, void* ticket,

@@ -65,7 +65,18 @@ inline int device_slot() {
 
 // Workgroups of a persistent launch over nwork work items: one per compute unit of the device (256 if it cannot be
 // asked), read once per device.  DSIC_WINO_GRID = 1..1024 takes the place of the CU count: for a stream that owns
-// fewer CUs (dsic_stream_create_masked), and for experiments.
+// fewer CUs (dsic_stream_create_masked), and for experiments.  grid_override() = 1..1024 (dsic_wino_grid; 0: none)
+// caps the grid of every device in place of both: tests walk a workgroup through many work items at small shapes.
+inline int& grid_override() {
+  static int n = 0;
+  return n;
+}
+inline int set_grid_override(int n) {
+  const int was = grid_override();
+  if (n > 1024) return -1;
+  if (n >= 0) grid_override() = n;
+  return was;
+}
 inline int persistent_grid(int dev, int64_t nwork) {
   static int max_grid_dev[64] = {};
   if (max_grid_dev[dev] == 0) {
@@ -76,7 +87,8 @@ inline int persistent_grid(int dev, int64_t nwork) {
     }
     max_grid_dev[dev] = n;
   }
-  return nwork < max_grid_dev[dev] ? (int)nwork : max_grid_dev[dev];
+  const int cap = grid_override() > 0 ? grid_override() : max_grid_dev[dev];
+  return nwork < cap ? (int)nwork : cap;
 }
 
 // A kernel family: every instance of one persistent kernel, in the order its translation unit indexes them.

@@ -52,6 +52,7 @@ SIGNATURES = {
     "dsic_wino_bf16_ksplit": (c_int, [c_int, c_int, c_int]),
     "dsic_wino_bf16_m64": (c_int, [c_int, c_int, c_int, c_int]),
     "dsic_wino_pair_chunks": (c_int, [c_int]),
+    "dsic_wino_grid": (c_int, [c_int]),
     "dsic_wino_pair_schedule": (c_int, [c_int, c_int, c_int, c_int, c_int, c_int, _P, c_int]),
     "dsic_conv3x3_wino_bf16_splitk_nhwc": (c_int, [_P, _P, _P, _P, _P, _P, c_int, c_int, c_int, c_int, c_int, c_int,
                                                    c_int, c_int, c_int, c_int, c_int, _P, _P, _P]),

@@ -193,6 +193,13 @@ int dsic_wino_bf16_m64(int H, int W, int Cin, int nphase);
  * Cin/16; writes up to cap pairs of ints to out and returns their number (negative: bad arguments or a table
  * that contradicts itself). */
 int dsic_wino_pair_chunks(int on);
+/* The Winograd kernels are persistent: a launch has one workgroup per compute unit of the device (DSIC_WINO_GRID =
+ * 1..1024 in the environment: that many), at most one per work item, and each takes work items from the ticket
+ * until none is left; an output element is the work of one item, so results are bit-identical at every grid.
+ * dsic_wino_grid(n): n = 1..1024 caps the grid of later launches at n workgroups on every device (tests walk a
+ * workgroup through many items at small shapes), 0 returns to the default, a negative value only asks, a value
+ * above 1024 changes nothing and returns -1; otherwise returns the previous cap (0: none). */
+int dsic_wino_grid(int n);
 int dsic_wino_pair_schedule(int mode, int nchunks, int phase, int paired, int pq, int acc, int* out, int cap);
 int dsic_conv3x3_wino_bf16_splitk_nhwc(const float* in, const void* u_planes,
                                        const float* bias, const float* beta,

@@ -278,7 +278,10 @@ def _c(fam, op, H, W, Cin, Cout, act, *opt):
 
 
 WINO32_CASES = [
-    # 3x3: every H x W, Cin (4, 6, 8, 12 chunks: both copy-out schedules) and Cout once, the four activations
+    # 3x3: every H x W, Cin (4, 6, 8, 12 chunks) and Cout once, the four activations.  The two copy-out schedules of
+    # the loop (nchunks >= 8, < 8) carry outputs only where a workgroup takes a second item: at the device's grid
+    # every workgroup takes one of these cases' <= 27 items, its in-loop stores are dropped offsets and the judged
+    # outputs leave through the epilogue.  test_winograd_elements_through_the_ticket_loop caps the grid at 1, 2, 3.
     _c("wino32", "c3", 1, 1, 64, 4, "none"),
     _c("wino32", "c3", 2, 3, 96, 36, "relu"),
     _c("wino32", "c3", 8, 16, 128, 100, "gdn"),

@@ -115,16 +115,21 @@ def test_chunk_major_needs_the_64_tile_kernel(ops):
         ops.conv3x3_wino_nhwc(x, u, _rand((128,), 42), 128, cm_in=True)
 
 
+def _chain_model():
+    from dsic_amd import synthetic as S
+    from dsic_amd.model import CompressionModel
+    sd = S.make_state_dict(seed=3)
+    m = CompressionModel(N=128, M=192, spatial_params=False, min_nu=2, max_nu=100.0)
+    m.load_state_dict({k: torch.from_numpy(v) for k, v in sd.items()}, strict=True)
+    return m.cuda().eval()
+
+
 def test_analysis_and_synthesis_chains_match_nhwc(ops, monkeypatch):
     """g_a.0 -> g_a.2 and every 64-tile edge of g_a / g_s: same outputs and taps at every level of layers.CHUNK_MAJOR.
     128x128 is the smallest size with 64-tile edges in both chains, 48x80 the smallest whose bottom layers run on the
     direct kernel."""
     from dsic_amd import layers, synthetic as S
-    from dsic_amd.model import CompressionModel
-    sd = S.make_state_dict(seed=3)
-    m = CompressionModel(N=128, M=192, spatial_params=False, min_nu=2, max_nu=100.0)
-    m.load_state_dict({k: torch.from_numpy(v) for k, v in sd.items()}, strict=True)
-    m = m.cuda().eval()
+    m = _chain_model()
     firsts = []
     real_first = ops.conv_first_nchw
     monkeypatch.setattr(ops, "conv_first_nchw", lambda *a, **k: firsts.append(k.get("cm_out")) or real_first(*a, **k))
@@ -151,3 +156,39 @@ def test_analysis_and_synthesis_chains_match_nhwc(ops, monkeypatch):
             assert len(ta0) == len(ta1) and len(ts0) == len(ts1)
             for a, b in zip(ta0 + ts0, ta1 + ts1):
                 assert torch.equal(a, b)
+
+
+def test_chains_give_the_same_bits_at_every_grid(ops):
+    """The same chains with the Winograd kernels' persistent grid capped at 1 and at 3 workgroups
+    (dsic_wino_grid), where a workgroup walks from work item to work item through every layer: the outputs of one
+    tile leave during the next one's phases.  At the device's grid these sizes give a workgroup one item, two at
+    the most.  Every edge of the plan in that state: the space-to-depth first edge, chunk-major in and out, the
+    Cout slices of g_a.14, split-K.  Outputs and every tap equal the default grid's bit for bit."""
+    from dsic_amd import synthetic as S
+    m = _chain_model()
+    L = ops._lib.load()
+
+    def run(x):
+        ta, ts = [], []
+        y = m.g_a.forward_from_image(x, ta)
+        xh = m.g_s.forward_nhwc(y[..., :192].contiguous(), ts)
+        torch.cuda.synchronize()
+        assert not bool(ops._ticket(x.device).any())
+        return [y, xh] + ta + ts
+
+    was = L.dsic_wino_grid(-1)
+    try:
+        for H, W in ((128, 128), (48, 80)):
+            x = torch.from_numpy(S.make_patches(0, 2, H, W)).cuda()
+            L.dsic_wino_grid(0)
+            ref = run(x)
+            assert len(ref) > 10 and all(bool(torch.isfinite(t).all()) for t in ref)
+            for grid in (1, 3):
+                assert L.dsic_wino_grid(grid) in (0, 1) and L.dsic_wino_grid(-1) == grid
+                got = run(x)
+                assert len(got) == len(ref)
+                for i, (a, b) in enumerate(zip(got, ref)):
+                    assert torch.equal(a, b), f"{H}x{W}, grid {grid}: tensor {i} of {len(ref)} (outputs, then taps) " \
+                                              f"differs from the default grid's"
+    finally:
+        L.dsic_wino_grid(was)

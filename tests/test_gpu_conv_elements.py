@@ -8,7 +8,9 @@ shape per branch of the dispatch.  Every buffer the kernel sees sits between gua
 sentinels (an element never written or a store outside the tensor fails), inputs, weights, bias, beta and gamma sit
 between NaN guards (a read past a tensor poisons the result), and the judged image is the only finite image of its
 batch (a read from a neighbouring image poisons it).  A second call and the judged image alone (B = 1) give the same
-bits; after each Winograd call the ticket is zero.
+bits; after each Winograd call the ticket is zero.  The Winograd cases run once more with the persistent grid capped
+at 1, 2 and 3 workgroups (dsic_wino_grid), where a workgroup takes item after item and the outputs of one tile leave
+during the next one's phases: the bits must be those of the device's grid.
 """
 import contextlib
 import math
@@ -256,9 +258,68 @@ def test_winograd_elements(ops, L, c):
             _check_run(c, kind, contraction, what, _wino_run(ops, L, c, kind, contraction), R.batches_of(c))
 
 
+@pytest.fixture
+def wino_grid(L):
+    """dsic_wino_grid, with the cap that was set before the test back in place afterwards (after a failure too)."""
+    was = L.dsic_wino_grid(-1)
+    yield L.dsic_wino_grid
+    L.dsic_wino_grid(was)
+
+
+def _wino_items(L, c, B):
+    """Work items of a launch over B images, as the launch code counts them (wino_launch in conv_wino.hip and
+    wb_launch in conv_wino_bf16.hip: 16x8-pixel tiles, times the split-K factor; dsic_wbm_launch in
+    conv_wino_bf16m.hip: 16x16-pixel tiles; a transposed layer has four phase items per tile)."""
+    nphase = 4 if c.op == "ct" else 1
+    if c.fam == "wino64":
+        assert c.H % 16 == 0 and c.W % 16 == 0
+        return (c.H // 16) * (c.W // 16) * B * nphase
+    S = L.dsic_wino_bf16_ksplit(c.H, c.W, c.Cin) if "splitk" in c.opt else 1
+    return -(-c.H // 8) * (-(-c.W // 16)) * B * nphase * S
+
+
+# test_winograd_elements runs every case at the device's grid, min(items, CUs): with at most 27 items each workgroup
+# takes one, copies nothing out inside its loop and leaves through the epilogue behind a prologue that no item
+# precedes.  Here the grid is capped at 1, 2 and 3 workgroups, so that a workgroup walks from item to item: the judged
+# image is the first item a workgroup ever takes (7, 0: the prologue, then its outputs leave during a NaN successor's
+# phases), the last (7, 6: a NaN predecessor, the epilogue) and one in the middle (3, 1).  An output element is the
+# work of one item (of S partial sums added in fixed order by the second launch), so the bits are those of the
+# default grid, which are judged against float64 once.
+@pytest.mark.parametrize("grid", [1, 2, 3])
+@pytest.mark.parametrize("c", R.WINO32_CASES + R.WINO64_CASES, ids=R.case_id)
+def test_winograd_elements_through_the_ticket_loop(ops, L, wino_grid, c, grid):
+    items = _wino_items(L, c, 7)                                         # of the batches (7, 0) and (7, 6)
+    assert items >= 2 * grid + 1, f"{items} items on {grid} workgroups: none takes a third item"
+    for kind in R.kinds_of(c):
+        for contraction in R.contractions(c):
+            what = f"{R.case_id(c)} {kind} {contraction}"
+            run = _wino_run(ops, L, c, kind, contraction)
+            wino_grid(0)
+            ref, _ = _judged_chw(c, run(3, 1)[0].take(what), 1)
+            _judge(c, kind, contraction, ref, f"{what} default grid")
+            assert wino_grid(grid) == 0 and wino_grid(-1) == grid
+            for B, j in ((3, 1), (7, 0), (7, 6)):
+                where = f"{what} grid {grid} B={B} image {j}"
+                out, launch = run(B, j)                                  # the launch checks the ticket
+                got, outside = _judged_chw(c, out.take(where), j)         # take checks the guards
+                if outside is not None:
+                    assert bool((outside == OUTSIDE).all()), f"{where}: a store outside the channel slice"
+                bad = torch.isnan(got).nonzero()
+                assert bad.numel() == 0, f"{where}: {bad.shape[0]} of {got.numel()} elements never written or " \
+                                         f"poisoned, first at (channel, row, col) {tuple(bad[0].tolist())}"
+                diff = (got.view(torch.int32) != ref.view(torch.int32)).nonzero()
+                assert _same_bits(got, ref), f"{where}: {diff.shape[0]} of {got.numel()} elements differ from the " \
+                                             f"default grid's, first at (channel, row, col) {tuple(diff[0].tolist())}"
+                launch()
+                again, outside = _judged_chw(c, out.take(where), j)
+                assert _same_bits(again, got), f"{where}: a second call on the same buffers gives other bits"
+                if outside is not None:
+                    assert bool((outside == OUTSIDE).all()), f"{where}: a store outside the channel slice"
+
+
 # ---------------------------------------------------------------------------------------------------- implicit GEMM
 
-_tile_places = {}    # tile shape -> places of the judged image inside a tile group, over all cases
+_tile_places = {}   # tile shape -> places of the judged image inside a tile group, over all cases
 
 
 @pytest.mark.parametrize("c", R.IGEMM_CASES, ids=R.case_id)

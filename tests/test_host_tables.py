@@ -29,6 +29,24 @@ def test_library_exports_every_declared_symbol(L):
     assert L.dsic_abi_version() == 4
 
 
+def test_wino_grid_setter_without_gpu(L):
+    """dsic_wino_grid (include/dsic_hip.h): 1..1024 sets the cap and returns the previous one, a negative value only
+    asks, a value above 1024 is refused with -1 and changes nothing, 0 returns to the default."""
+    g = L.dsic_wino_grid
+    was = g(-1)
+    try:
+        assert g(0) == was and g(-1) == 0 and g(-7) == 0           # no cap: the default grid
+        assert g(3) == 0 and g(-1) == 3                            # set, ask
+        assert g(1024) == 3 and g(-1) == 1024                      # the largest cap
+        assert g(1025) == -1 and g(1 << 30) == -1 and g(-1) == 1024   # refused: nothing changes
+        assert g(1) == 1024 and g(-1) == 1 and g(-1) == 1          # asking changes nothing
+        assert g(0) == 1 and g(-1) == 0                            # 0 restores the default
+        assert g(5) == 0 and g(g(-1)) == 5 and g(-1) == 5          # restore idiom: set what was asked
+    finally:
+        g(was)
+    assert g(-1) == was
+
+
 def test_argument_validation_without_gpu(L):
     # NULL pointers / bad shapes are rejected before anything touches the device
     assert L.dsic_conv2d_nhwc(None, None, None, None, None, None, 1, 8, 8, 8, 8, 3, 1, 0, None) == 1
