@@ -23,9 +23,7 @@
 // See DESIGN.md section 3 for the reasons (in-order vmcnt, VALU issue under MFMA) and the numbers.
 #include <stdlib.h>
 
-#include <type_traits>
-
-#include "common.h"
+#include "wino_device.h"
 #include "wino_host.h"
 
 #ifndef WINO_STAMP
@@ -43,37 +41,9 @@
 
 namespace dsic {
 
-typedef float floatx16 __attribute__((ext_vector_type(16)));
-typedef float floatx4 __attribute__((ext_vector_type(4)));
-typedef int intx4 __attribute__((ext_vector_type(4)));
-typedef float floatx2 __attribute__((ext_vector_type(2)));
-typedef unsigned uintx4 __attribute__((ext_vector_type(4)));
-
-// a - b on two / four / sixteen floats with packed fp32 instructions.  The compiler packs fp32
-// additions (v_pk_add_f32) but leaves subtractions scalar; the negation is an operand modifier of
-// the same instruction, so a - b costs the same single issue slot.  Every VALU issue slot matters
-// here: a SIMD cannot issue VALU work of any wave while an MFMA is waiting for the matrix pipe.
-__device__ __forceinline__ floatx2 pk_sub(floatx2 a, floatx2 b) {
-  floatx2 r;
-  asm("v_pk_add_f32 %0, %1, %2 neg_lo:[0,1] neg_hi:[0,1]" : "=v"(r) : "v"(a), "v"(b));
-  return r;
-}
-__device__ __forceinline__ floatx4 sub4(floatx4 a, floatx4 b) {
-  const floatx2 lo = pk_sub(__builtin_shufflevector(a, a, 0, 1), __builtin_shufflevector(b, b, 0, 1));
-  const floatx2 hi = pk_sub(__builtin_shufflevector(a, a, 2, 3), __builtin_shufflevector(b, b, 2, 3));
-  return __builtin_shufflevector(lo, hi, 0, 1, 2, 3);
-}
-__device__ __forceinline__ floatx16 sub16(floatx16 a, floatx16 b) {
-  floatx16 r;
-#pragma unroll
-  for (int i = 0; i < 16; i += 2) {
-    const floatx2 x = {a[i], a[i + 1]}, y = {b[i], b[i + 1]};
-    const floatx2 d = pk_sub(x, y);
-    r[i] = d[0];
-    r[i + 1] = d[1];
-  }
-  return r;
-}
+using wino::sub16;
+using wino::sub4;
+using wino::Tile;  // a work item (tile*nphase + phase) and its 16x8-pixel tile coordinates
 
 struct WinoArgs {
   const float* in;
@@ -84,8 +54,7 @@ struct WinoArgs {
   float* out;
   int B, H, W, Cin, Cout, CoutP;
   int act;
-  unsigned long long* ticket;  // [0] tiles handed out beyond the first round, [1] finished workgroups (zeroed
-                               // once by the caller; the last workgroup of a launch zeroes it again)
+  unsigned long long* ticket;  // two counters, zeroed once by the caller (wino_device.h)
   int nphase;  // 1, or 4: ConvTranspose2d(5,2,2,1) as four 3x3 sub-pixel phase convs sharing the input;
                // work item w = spatial tile*4 + phase, U of phase p at u + p*u_phase_stride, output pixel
                // (2*oy+py, 2*ox+px) of a [B,2H,2W,Cout] tensor
@@ -130,10 +99,6 @@ constexpr int WTHREADS = 768;              // 8 MFMA waves + 4 helper waves
 
 __device__ __forceinline__ void wg_barrier() { __syncthreads(); }
 
-struct WinoTile {
-  int item, tx, ty, n;  // work item (tile*nphase + phase) and its 16x8-pixel tile coordinates
-};
-
 // MODE 0: plain 3x3 layer.  MODE 1 (space-to-depth input) and MODE 2 (ConvTranspose2d phases) have
 // structurally zero Winograd positions whose MFMA clusters are skipped; MODE 0 carries no test in
 // the loop.  Steps run position-major (all four 8-channel groups of a position, then the next
@@ -152,26 +117,14 @@ struct WinoTile {
 // finished outputs to HBM from there, behind the next chunk's input loads.
 // Every wave executes the same barrier sequence: P0, P, then per tile B_0..B_{n-1}, E1, E2.
 //
-// Tiles are handed out dynamically (first round = blockIdx.x, then a global ticket): a CU that is
-// slowed down - e.g. by co-resident waves of another stream - simply takes fewer tiles.  Helper
-// thread 0 fetches the ticket one tile ahead, splits it into (tx, ty, n) (the only integer
-// divisions of the kernel) and posts the descriptor in a 3-slot LDS ring: slot k%3 = the k-th
-// tile of this workgroup.
+// Tiles are handed out dynamically through a 3-slot LDS ring: wino_device.h.
 template <int MODE>
 __global__ __launch_bounds__(WTHREADS) void conv_wino_kernel(const WinoArgs a) {
   extern __shared__ __attribute__((aligned(16))) float lds[];
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   float* slots = lds + 2 * WBUF;  // written before a workgroup barrier, read after it
-  auto read_slot = [&](int s) {
-    const intx4 v = *(const intx4*)(slots + 4 * s);
-    WinoTile t;
-    t.item = __builtin_amdgcn_readfirstlane(v[0]);
-    t.tx = __builtin_amdgcn_readfirstlane(v[1]);
-    t.ty = __builtin_amdgcn_readfirstlane(v[2]);
-    t.n = __builtin_amdgcn_readfirstlane(v[3]);
-    return t;
-  };
+  auto read_slot = [&](int s) { return wino::read_tile<false>(slots, s); };
   const int pshift = a.nphase == 4 ? 2 : 0;
 
   if (wave >= 8) {
@@ -185,12 +138,7 @@ __global__ __launch_bounds__(WTHREADS) void conv_wino_kernel(const WinoArgs a) {
     const int pt = ht >> 3, pq = ht & 7;
     const int ptx = pt & 7, pty = pt >> 3;
     const int vwrite = pt * WP + 4 * pq;  // + pos*32*WP
-    auto post = [&](int s, int item) {  // helper thread 0 only
-      const int tile = item >> pshift;
-      const int row = tile / a.tiles_x;
-      const intx4 v = {item, tile - row * a.tiles_x, row % a.tiles_y, row / a.tiles_y};
-      *(intx4*)(slots + 4 * s) = v;
-    };
+    auto post = [&](int s, int item) { wino::post_tile(slots, s, item, 0, pshift, a.tiles_x, a.tiles_y); };
     // Input side, in three steps so that the loads of the next chunk can be put in flight before
     // the helper waits at a barrier (a helper only gets issue slots while the MFMA waves idle: the
     // SIMD issues one VALU-class instruction at a time and a pending MFMA holds the port):
@@ -204,7 +152,7 @@ __global__ __launch_bounds__(WTHREADS) void conv_wino_kernel(const WinoArgs a) {
       unsigned off[16];  // byte offsets of the 16 patch pixels inside the image (+ this thread's channel quad)
       __amdgpu_buffer_rsrc_t rsrc;  // uniform
     };
-    auto aim = [&](Aim& m, const WinoTile& t) {
+    auto aim = [&](Aim& m, const Tile& t) {
       const int gy0 = t.ty * 8 + 2 * pty - 1, gx0 = t.tx * 16 + 2 * ptx - 1;
       m.rsrc = __builtin_amdgcn_make_buffer_rsrc((void*)(a.in + (size_t)t.n * a.H * a.W * Cin), 0,
                                                  a.H * a.W * Cin * 4, 0x00020000);
@@ -260,8 +208,8 @@ __global__ __launch_bounds__(WTHREADS) void conv_wino_kernel(const WinoArgs a) {
       unsigned po[4];
       __amdgpu_buffer_rsrc_t rs;
     };
-    auto next_ticket = [&]() { return (int)(atomicAdd(a.ticket, 1ULL) + gridDim.x); };
-    auto aim_out = [&](OutAim& o, const WinoTile& t) {
+    auto next_ticket = [&]() { return wino::take_ticket(a.ticket); };
+    auto aim_out = [&](OutAim& o, const Tile& t) {
       const int phase = t.item & (a.nphase - 1);
       const int ppy = phase >> 1, ppx = phase & 1;  // sub-pixel phase placement (ConvTranspose2d)
       const int OH = a.nphase == 4 ? 2 * a.H : a.H, OW = a.nphase == 4 ? 2 * a.W : a.W;
@@ -302,7 +250,7 @@ __global__ __launch_bounds__(WTHREADS) void conv_wino_kernel(const WinoArgs a) {
       post(1, next_ticket());
     }
     wg_barrier();  // P0: the first two descriptors are posted
-    WinoTile cur = read_slot(0);
+    Tile cur = read_slot(0);
     // The patch in flight and its aim live across tiles: the aim moves on to the next tile two
     // chunks before the current one ends, and (layers with more than one chunk) the loads of the next
     // tile's target 0 are issued before the fold barriers of the current one, so their latency and
@@ -325,7 +273,7 @@ __global__ __launch_bounds__(WTHREADS) void conv_wino_kernel(const WinoArgs a) {
     for (int ij = 0; ij < 4; ++ij) oa.po[ij] = 0x80000000u;
     bool have_y = false;  // finished outputs of the previous tile wait in V[buf^1], aimed by oa
     while (cur.item < a.ntiles) {
-      const WinoTile nxt = read_slot(s_nxt);
+      const Tile nxt = read_slot(s_nxt);
       const bool more = nxt.item < a.ntiles;
       tile_count++;
       // chunk c: the MFMA waves consume V[buf]; the helpers fill V[buf^1] with target c =
@@ -380,21 +328,16 @@ __global__ __launch_bounds__(WTHREADS) void conv_wino_kernel(const WinoArgs a) {
       wg_barrier();  // E2: the finished outputs of this tile lie in V[buf^1]
       have_y = true;
       cur = nxt;
+      // wino::rotate_ring, kept local: through the shared one this kernel's SGPR allocation and spill code move
       const int s_old = s_nxt;
       s_nxt = s_wr;
-      s_wr = s_old == 0 ? 2 : s_old - 1;  // ring 0,1,2: cur slot of the finished tile becomes writable
+      s_wr = s_old == 0 ? 2 : s_old - 1;
     }
     if (have_y) store_outputs(oa, lds + (buf ^ 1) * WBUF);  // outputs of the last tile
 #if WINO_STAMP
     if (wave == 8 && lane < 32) wino_stamps[blockIdx.x * 32 + lane] = ((long long*)(lds + 2 * WBUF + 16))[lane];
 #endif
-    if (ht == 0) {  // last workgroup out re-arms the ticket for the next launch on this stream
-      const unsigned long long done = atomicAdd(a.ticket + 1, 1ULL);
-      if (done == (unsigned long long)gridDim.x - 1) {
-        a.ticket[0] = 0ULL;
-        a.ticket[1] = 0ULL;
-      }
-    }
+    if (ht == 0) wino::rearm_ticket(a.ticket);
     return;
   }
 
@@ -442,7 +385,7 @@ __global__ __launch_bounds__(WTHREADS) void conv_wino_kernel(const WinoArgs a) {
   floatx4 Bq[R];
   wg_barrier();  // P0
   wg_barrier();  // P
-  WinoTile cur = read_slot(0);
+  Tile cur = read_slot(0);
   const __amdgpu_buffer_rsrc_t urs = __builtin_amdgcn_make_buffer_rsrc(
       (void*)a.u, 0, (int)(16u * step_p * (unsigned)a.nphase), 0x00020000);  // all phases' U (host checks < 2 GiB)
   const unsigned phase_bytes = (unsigned)a.u_phase_stride * 4u;
@@ -460,7 +403,7 @@ __global__ __launch_bounds__(WTHREADS) void conv_wino_kernel(const WinoArgs a) {
   for (int f = 0; f < R - 1; ++f) Bq[f] = fetch(f);
   int buf = 0, s_nxt = 1;
   while (cur.item < a.ntiles) {
-    const WinoTile nxt = read_slot(s_nxt);
+    const Tile nxt = read_slot(s_nxt);
     const unsigned soff_nxt = soff0 + (unsigned)((nxt.item < a.ntiles ? nxt.item : cur.item) & (a.nphase - 1)) * phase_bytes;
     tile_count++;
     // FIRST: chunk 0 of a tile starts every accumulator from a zero C operand (inline constant), so
@@ -560,7 +503,7 @@ __global__ __launch_bounds__(WTHREADS) void conv_wino_kernel(const WinoArgs a) {
       // The wave that adds the second term holds the finished sum in registers, so bias and
       // activation are applied right here (this lane = one output channel: its three parameters
       // live in registers) and the helpers only copy the result out.
-      auto finish_rows = [&](auto act_tag) {
+      wino::for_act(a.act, [&](auto act_tag) {
         constexpr int ACT = decltype(act_tag)::value;
 #pragma unroll
         for (int j = 0; j < 2; ++j) {
@@ -570,33 +513,18 @@ __global__ __launch_bounds__(WTHREADS) void conv_wino_kernel(const WinoArgs a) {
 #pragma unroll
           for (int e = 0; e < 16; e += 2) {
             floatx2 v = {got[e], got[e + 1]};
-            v = v + floatx2{send[j][e], send[j][e + 1]};
-            v = v + floatx2{pbias, pbias};
-            if (ACT == DSIC_ACT_GDN || ACT == DSIC_ACT_IGDN) {
-              v = gdn_pair<ACT == DSIC_ACT_IGDN>(v, floatx2{pbeta, pbeta}, floatx2{pgamma, pgamma});
-            } else if (ACT == DSIC_ACT_RELU) {
-              v[0] = v[0] > 0.f ? v[0] : 0.f;
-              v[1] = v[1] > 0.f ? v[1] : 0.f;
-            }
+            v = wino::bias_act<ACT>(v + floatx2{send[j][e], send[j][e + 1]}, pbias, pbeta, pgamma);
             yoth[(4 * j * 32 + (e & 3) + 8 * (e >> 2)) * WP] = v[0];
             yoth[(4 * j * 32 + ((e + 1) & 3) + 8 * ((e + 1) >> 2)) * WP] = v[1];
           }
         }
-      };
-      if (a.act == DSIC_ACT_GDN)
-        finish_rows(std::integral_constant<int, DSIC_ACT_GDN>{});
-      else if (a.act == DSIC_ACT_IGDN)
-        finish_rows(std::integral_constant<int, DSIC_ACT_IGDN>{});
-      else if (a.act == DSIC_ACT_RELU)
-        finish_rows(std::integral_constant<int, DSIC_ACT_RELU>{});
-      else
-        finish_rows(std::integral_constant<int, DSIC_ACT_NONE>{});
+      });
     }
     STAMP(26);
     wg_barrier();  // E2: the helpers copy the finished outputs from here and refill the buffer
     STAMP(27);
     cur = nxt;
-    s_nxt = s_nxt == 2 ? 0 : s_nxt + 1;
+    s_nxt = wino::step_ring(s_nxt);
   }
 }
 

@@ -1,11 +1,10 @@
-// Launch arguments, LDS layout, position tables and the fold of the split-bf16 Winograd kernel (conv_wino_bf16.hip).
+// Launch arguments, LDS layout, bf16 conversions, U-fragment fetch, position tables and the fold of the split-bf16
+// Winograd kernels (conv_wino_bf16.hip; conv_wino_bf16m.hip shares arguments, conversions and fetch).
 // (A header since the fused-role experiment of round 2, commit 5f523cb: a second kernel built on the same pieces.)
 #pragma once
 #include <stdlib.h>
 
-#include <type_traits>
-
-#include "common.h"
+#include "wino_device.h"
 
 #ifndef WB_PLANES
 #define WB_PLANES 2
@@ -33,12 +32,7 @@
 namespace dsic {
 namespace wb {
 
-typedef float floatx16 __attribute__((ext_vector_type(16)));
-typedef float floatx4 __attribute__((ext_vector_type(4)));
-typedef float floatx2 __attribute__((ext_vector_type(2)));
-typedef int intx4 __attribute__((ext_vector_type(4)));
-typedef unsigned uintx4 __attribute__((ext_vector_type(4)));
-typedef unsigned uintx2 __attribute__((ext_vector_type(2)));
+using wino::Tile;
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 
 struct Args {
@@ -105,24 +99,6 @@ static __device__ long long wb_stamps[256 * 128];
 #define WSTAMPC(w, i, lim)
 #endif
 
-__device__ __forceinline__ floatx2 pk_sub(floatx2 a, floatx2 b) {
-  floatx2 r;
-  asm("v_pk_add_f32 %0, %1, %2 neg_lo:[0,1] neg_hi:[0,1]" : "=v"(r) : "v"(a), "v"(b));
-  return r;
-}
-__device__ __forceinline__ floatx4 sub4(floatx4 a, floatx4 b) { return a - b; }
-__device__ __forceinline__ floatx16 sub16(floatx16 a, floatx16 b) {
-  floatx16 r;
-#pragma unroll
-  for (int i = 0; i < 16; i += 2) {
-    const floatx2 x = {a[i], a[i + 1]}, y = {b[i], b[i + 1]};
-    const floatx2 d = pk_sub(x, y);
-    r[i] = d[0];
-    r[i + 1] = d[1];
-  }
-  return r;
-}
-
 // two floats -> packed bf16 pair (round to nearest even), and the pair back as two floats
 typedef __bf16 wb_bf16x2 __attribute__((ext_vector_type(2)));
 __device__ __forceinline__ unsigned cvt_pk_bf16(float a, float b) {
@@ -133,9 +109,20 @@ __device__ __forceinline__ unsigned cvt_pk_bf16(float a, float b) {
 __device__ __forceinline__ float bf16_lo(unsigned pk) { return __builtin_bit_cast(float, pk << 16); }
 __device__ __forceinline__ float bf16_hi(unsigned pk) { return __builtin_bit_cast(float, pk & 0xFFFF0000u); }
 
-struct Tile {
-  int item, tx, ty, n, ks;
-};
+// U stream [phase][pos 16][chunk][plane][CoutP][16 bf16]: the scalar byte offset at which a work item's fragments
+// start (its phase's weights, from its first chunk on: ks runs of nchunks chunks of chunk_b bytes), and the planes
+// of one fragment (64 lanes x 16 bytes at lane offset ulane, plane_b bytes apart) from scalar offset so.
+__device__ __forceinline__ unsigned soff_item(const Tile& t, int nphase, int64_t u_phase_bytes, int nchunks,
+                                               unsigned chunk_b) {
+  return (unsigned)(t.item & (nphase - 1)) * (unsigned)u_phase_bytes + (unsigned)(t.ks * nchunks) * chunk_b;
+}
+template <int NP>
+__device__ __forceinline__ void fetch_u(bf16x8 (&dst)[NP], __amdgpu_buffer_rsrc_t urs, unsigned ulane, unsigned so,
+                                        unsigned plane_b) {
+#pragma unroll
+  for (int q = 0; q < NP; ++q)
+    dst[q] = __builtin_bit_cast(bf16x8, __builtin_amdgcn_raw_buffer_load_b128(urs, ulane, so + (unsigned)q * plane_b, 0));
+}
 
 // Which 8 of the 16 Winograd positions (xi, nu) an MFMA wave of position half ph owns: the checkerboard
 // (xi + nu) & 1 == ph.  A structurally zero row (xi) or column (nu) of a chunk - space-to-depth blocks, ConvTranspose

@@ -25,7 +25,7 @@
 //     (Winograd tile, channel quad, half of the positions) then reads three rows of its 4x4 patch
 //     from there, applies B^T d B in fp32, splits into the bf16 planes and stores them into the V
 //     buffer the MFMA waves are not reading.
-// Tile hand-out, the fold through LDS and the fused epilogue follow conv_wino.hip.
+// Tile hand-out and fused epilogue are those of wino_device.h; the fold through LDS follows conv_wino.hip.
 #include "conv_wino_bf16.h"
 #include "wino_host.h"
 
@@ -41,20 +41,27 @@ __global__ __launch_bounds__(THREADS) void conv_wino_bf16_kernel(const Args a) {
   float* const slots = (float*)(lds_raw + SLOTOFF);
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  auto read_slot = [&](int s) {
-    const intx4 v = *(const intx4*)(slots + 4 * s);
-    Tile t;
-    t.item = __builtin_amdgcn_readfirstlane(v[0]);
-    t.tx = __builtin_amdgcn_readfirstlane(v[1]);
-    t.ty = SPLITK ? __builtin_amdgcn_readfirstlane(v[2]) & 0xFFFF : __builtin_amdgcn_readfirstlane(v[2]);
-    t.ks = SPLITK ? __builtin_amdgcn_readfirstlane(v[2]) >> 16 : 0;
-    t.n = __builtin_amdgcn_readfirstlane(v[3]);
-    return t;
-  };
+  auto read_slot = [&](int s) { return wino::read_tile<SPLITK>(slots, s); };
   const int pshift = a.nphase == 4 ? 2 : 0;
   const int tchunks = a.Cin / CK;                    // = nchunks * ksplit
   const int nchunks = SPLITK ? a.kchunks : tchunks;  // chunks of one work item: even, >= 4 (host)
   const int ksplit = SPLITK ? a.ksplit : 1;
+  // The structurally zero Winograd row / column (4 = none) of tile-local chunk k of a work item: MODE 1 by the
+  // channel block of the chunk, MODE 2 by the item's phase.  The helpers neither transform nor store those positions,
+  // the MFMA waves neither fetch nor multiply them.
+  auto zero_of = [&](const Tile& t, int k, unsigned& zxi, unsigned& znu) {
+    zxi = 4;
+    znu = 4;
+    if (MODE == 1) {
+      const int blk = (t.ks * nchunks + k) / (tchunks >> 2);
+      if (blk >> 1) zxi = 3;
+      if (blk & 1) znu = 3;
+    } else if (MODE == 2) {
+      const int phase = t.item & 3;
+      if (phase >> 1) zxi = 0;
+      if (phase & 1) znu = 0;
+    }
+  };
 
   if (wave >= 8) {
     // =================================== helper waves ===========================================
@@ -80,10 +87,7 @@ __global__ __launch_bounds__(THREADS) void conv_wino_bf16_kernel(const Args a) {
     const int yread = ot * WP + 4 * oq;
     auto post = [&](int s, int t) {  // helper thread 0 only; ticket t = item * ksplit + ks
       const int item = SPLITK ? t / ksplit : t, ks = SPLITK ? t - item * ksplit : 0;
-      const int tile = item >> pshift;
-      const int row = tile / a.tiles_x;
-      const intx4 v = {item, tile - row * a.tiles_x, (row % a.tiles_y) | (ks << 16), row / a.tiles_y};
-      *(intx4*)(slots + 4 * s) = v;
+      wino::post_tile(slots, s, item, ks, pshift, a.tiles_x, a.tiles_y);
     };
     // Input side.  The 18x10-pixel window of the tile (halo 1; 16 channels of the chunk, fp32) is
     // loaded ONCE from global memory - 720 float4 for 256 threads - and staged in LDS; every
@@ -152,8 +156,8 @@ __global__ __launch_bounds__(THREADS) void conv_wino_bf16_kernel(const Args a) {
       }
     };
     // B^T d B for this thread's two xi rows: window buffer wbuf -> V buffer vb.  zxi / znu: the
-    // structurally zero Winograd row / column of this chunk (4 = none; see the MFMA waves): those
-    // positions are never read, so they are neither transformed nor split nor stored.
+    // structurally zero Winograd row / column of this chunk (zero_of): those positions are never
+    // read, so they are neither transformed nor split nor stored.
     auto commit = [&](int wbuf, int vb, unsigned zxi, unsigned znu) {
       if (WB_ABL & 4) return;
       const unsigned char* src = lds_raw + STAGEOFF + wbuf * WINB + patch0;
@@ -187,25 +191,11 @@ __global__ __launch_bounds__(THREADS) void conv_wino_bf16_kernel(const Args a) {
         if (znu != 3) split_store(xhi[1] - xhi[3], dst + 7 * POSB);
       }
     };
-    // zero row / column of tile-local chunk k of work item `item` (MODE 1: by channel block; MODE 2: by phase)
-    auto zero_of = [&](const Tile& t, int k, unsigned& zxi, unsigned& znu) {
-      zxi = 4;
-      znu = 4;
-      if (MODE == 1) {
-        const int blk = (t.ks * nchunks + k) / (tchunks >> 2);
-        if (blk >> 1) zxi = 3;
-        if (blk & 1) znu = 3;
-      } else if (MODE == 2) {
-        const int phase = t.item & 3;
-        if (phase >> 1) zxi = 0;
-        if (phase & 1) znu = 0;
-      }
-    };
     struct OutAim {
       unsigned po[4];
       __amdgpu_buffer_rsrc_t rs;
     };
-    auto next_ticket = [&]() { return (int)(atomicAdd(a.ticket, 1ULL) + gridDim.x); };
+    auto next_ticket = [&]() { return wino::take_ticket(a.ticket); };
     auto aim_out = [&](OutAim& o, const Tile& t) {
       const int phase = t.item & (a.nphase - 1);
       const int ppy = phase >> 1, ppx = phase & 1;
@@ -320,9 +310,7 @@ __global__ __launch_bounds__(THREADS) void conv_wino_bf16_kernel(const Args a) {
       __syncthreads();  // E1
       __syncthreads();  // E2
       cur = nxt;
-      const int s_old = s_nxt;
-      s_nxt = s_wr;
-      s_wr = s_old == 0 ? 2 : s_old - 1;
+      wino::rotate_ring(s_nxt, s_wr);
     }
     for (int g = 0; g < 4; ++g) store_group(oa, g);   // outputs of the last tile (dropped offsets if there was none)
 #if WB_STAMP
@@ -331,13 +319,7 @@ __global__ __launch_bounds__(THREADS) void conv_wino_bf16_kernel(const Args a) {
       wb_stamps[blockIdx.x * 128 + 64 + lane] = ((long long*)(lds_raw + STAMPOFF))[64 + lane];
     }
 #endif
-    if (ht == 0) {
-      const unsigned long long done = atomicAdd(a.ticket + 1, 1ULL);
-      if (done == (unsigned long long)gridDim.x - 1) {
-        a.ticket[0] = 0ULL;
-        a.ticket[1] = 0ULL;
-      }
-    }
+    if (ht == 0) wino::rearm_ticket(a.ticket);
     return;
   }
 
@@ -377,21 +359,13 @@ __global__ __launch_bounds__(THREADS) void conv_wino_bf16_kernel(const Args a) {
   Tile cur = read_slot(0);
   const __amdgpu_buffer_rsrc_t urs = __builtin_amdgcn_make_buffer_rsrc(
       (void*)a.u, 0, (int)(16u * pos_b * (unsigned)a.nphase), 0x00020000);
-  // fetch stream position: (tile's phase, chunk, position index pi) -> scalar byte offset
-  // (+ the work item's first chunk)
-  auto soff_item = [&](const Tile& t) {
-    return (unsigned)(t.item & (a.nphase - 1)) * (unsigned)a.u_phase_bytes + (unsigned)(t.ks * nchunks) * chunk_b;
-  };
+  // fetch stream position: (work item, chunk, position index pi) -> scalar byte offset
+  auto soff_item = [&](const Tile& t) { return wb::soff_item(t, a.nphase, a.u_phase_bytes, nchunks, chunk_b); };
   unsigned soff_phase = soff_item(cur);
   auto soff_of = [&](unsigned phase_off, int chunk, int pi) {
     return phase_off + (unsigned)pos_of(pi) * pos_b + (unsigned)chunk * chunk_b;
   };
-  auto fetch = [&](bf16x8 (&dst)[P], unsigned so) {
-    if (WB_ABL & 1) so = 0;
-#pragma unroll
-    for (int q = 0; q < P; ++q)
-      dst[q] = __builtin_bit_cast(bf16x8, __builtin_amdgcn_raw_buffer_load_b128(urs, ulane, so + (unsigned)q * plane_b, 0));
-  };
+  auto fetch = [&](bf16x8 (&dst)[P], unsigned so) { fetch_u(dst, urs, ulane, (WB_ABL & 1) ? 0u : so, plane_b); };
 #pragma unroll
   for (int f = 0; f < RING; ++f) fetch(Bq[f], soff_of(soff_phase, 0, f));
   int s_nxt = 1;
@@ -405,16 +379,8 @@ __global__ __launch_bounds__(THREADS) void conv_wino_bf16_kernel(const Args a) {
       constexpr bool FIRST = decltype(first_tag)::value;
       const bool last = chunk + 1 == nchunks;
       WSTAMPC(0, 3 * (chunk - WB_STAMP_C0), 60);
-      unsigned zero_xi = 4, zero_nu = 4;
-      if (MODE == 1) {
-        const int blk = (cur.ks * nchunks + chunk) / (tchunks >> 2);
-        if (blk >> 1) zero_xi = 3;
-        if (blk & 1) zero_nu = 3;
-      } else if (MODE == 2) {
-        const int phase = cur.item & 3;
-        if (phase >> 1) zero_xi = 0;
-        if (phase & 1) zero_nu = 0;
-      }
+      unsigned zero_xi, zero_nu;
+      zero_of(cur, chunk, zero_xi, zero_nu);
       auto is_zero = [&](int pi) {
         const int p = pos_of(pi);
         const unsigned xi = (unsigned)(p >> 2), nu = (unsigned)(p & 3);
@@ -520,7 +486,7 @@ __global__ __launch_bounds__(THREADS) void conv_wino_bf16_kernel(const Args a) {
       send[1] = fold_partial<MODE, PH, PH ^ 1, 1>(acc);
       WSTAMP(0, 61);
       __syncthreads();  // E1
-      auto finish_rows = [&](auto act_tag) {
+      wino::for_act(a.act, [&](auto act_tag) {
         constexpr int ACT = decltype(act_tag)::value;
 #pragma unroll
         for (int j = 0; j < 2; ++j) {
@@ -530,33 +496,18 @@ __global__ __launch_bounds__(THREADS) void conv_wino_bf16_kernel(const Args a) {
 #pragma unroll
           for (int e = 0; e < 16; e += 2) {
             floatx2 v = {got[e], got[e + 1]};
-            v = v + floatx2{send[j][e], send[j][e + 1]};
-            v = v + floatx2{pbias, pbias};
-            if (ACT == DSIC_ACT_GDN || ACT == DSIC_ACT_IGDN) {
-              v = gdn_pair<ACT == DSIC_ACT_IGDN>(v, floatx2{pbeta, pbeta}, floatx2{pgamma, pgamma});
-            } else if (ACT == DSIC_ACT_RELU) {
-              v[0] = v[0] > 0.f ? v[0] : 0.f;
-              v[1] = v[1] > 0.f ? v[1] : 0.f;
-            }
+            v = wino::bias_act<ACT>(v + floatx2{send[j][e], send[j][e + 1]}, pbias, pbeta, pgamma);
             yoth[(4 * j * 32 + (e & 3) + 8 * (e >> 2)) * WP] = v[0];
             yoth[(4 * j * 32 + ((e + 1) & 3) + 8 * ((e + 1) >> 2)) * WP] = v[1];
           }
         }
-      };
-      if (a.act == DSIC_ACT_GDN)
-        finish_rows(std::integral_constant<int, DSIC_ACT_GDN>{});
-      else if (a.act == DSIC_ACT_IGDN)
-        finish_rows(std::integral_constant<int, DSIC_ACT_IGDN>{});
-      else if (a.act == DSIC_ACT_RELU)
-        finish_rows(std::integral_constant<int, DSIC_ACT_RELU>{});
-      else
-        finish_rows(std::integral_constant<int, DSIC_ACT_NONE>{});
+      });
     }
     WSTAMP(0, 62);
     __syncthreads();  // E2
     WSTAMP(0, 63);
     cur = nxt;
-    s_nxt = s_nxt == 2 ? 0 : s_nxt + 1;
+    s_nxt = wino::step_ring(s_nxt);
   }
   };
   if (ph == 0)

@@ -28,8 +28,9 @@
 // and 3, xi = 0 for the ConvTranspose phases 2 and 3) one wave half issues alone and is held by its U fetches; two such
 // chunks run as one chunk-pass (conv_wino_pair.h: tables, V slots, the shorter pass B), bit-identical to one each.
 //
-// Helper waves, window staging, tile tickets, U stream layout and the V layout in LDS are those of
-// conv_wino_bf16.hip with 64 tiles x 8 positions in place of 32 x 16; the same packed weights serve both kernels.
+// Helper waves, window staging, U stream layout and the V layout in LDS are those of conv_wino_bf16.hip with
+// 64 tiles x 8 positions in place of 32 x 16; the same packed weights serve both kernels.  Tile hand-out, epilogue
+// and packed subtraction: wino_device.h.
 #include "conv_wino_bf16.h"
 #include "conv_wino_pair.h"
 #include "wino_host.h"
@@ -52,13 +53,8 @@ using wb::bf16_hi;
 using wb::bf16_lo;
 using wb::bf16x8;
 using wb::cvt_pk_bf16;
-using wb::floatx16;
-using wb::floatx2;
-using wb::floatx4;
-using wb::intx4;
-using wb::Tile;
-using wb::uintx2;
-using wb::uintx4;
+using wino::sub4;
+using wino::Tile;
 
 constexpr int P = 2;                            // bf16 planes
 constexpr int CK = 16;                          // channels per chunk = one MFMA k-step
@@ -124,16 +120,7 @@ __global__ __launch_bounds__(THREADS) void conv_wino_bf16m_kernel(const Args a) 
   float* const slots = (float*)(lds_raw + SLOTOFF);
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  auto read_slot = [&](int s) {
-    const intx4 v = *(const intx4*)(slots + 4 * s);
-    Tile t;
-    t.item = __builtin_amdgcn_readfirstlane(v[0]);
-    t.tx = __builtin_amdgcn_readfirstlane(v[1]);
-    t.ty = __builtin_amdgcn_readfirstlane(v[2]);
-    t.n = __builtin_amdgcn_readfirstlane(v[3]);
-    t.ks = 0;
-    return t;
-  };
+  auto read_slot = [&](int s) { return wino::read_tile<false>(slots, s); };
   const int pshift = a.nphase == 4 ? 2 : 0;
   const int nchunks = a.Cin / CK;   // even, >= 4 (host)
   // Chunk-passes of a tile: sigma < nchunks is pass A, the rest pass B, whose chunks run paired from chunk
@@ -163,12 +150,7 @@ __global__ __launch_bounds__(THREADS) void conv_wino_bf16m_kernel(const Args a) 
     const int ptx = pt & 7, pty = pt >> 3;
     const int vwrite = pt * ROWB + ((((pq >> 1) ^ ((pt >> 3) & 1))) << 4) + ((pq & 1) << 3);
     unsigned char* const vmine = lds_raw + vwrite;
-    auto post = [&](int s, int item) {  // helper thread 0 only
-      const int tile = item >> pshift;
-      const int row = tile / a.tiles_x;
-      const intx4 v = {item, tile - row * a.tiles_x, row % a.tiles_y, row / a.tiles_y};
-      *(intx4*)(slots + 4 * s) = v;
-    };
+    auto post = [&](int s, int item) { wino::post_tile(slots, s, item, 0, pshift, a.tiles_x, a.tiles_y); };
     // Input side.  The 18x18-pixel window of the tile (halo 1; 16 channels of the chunk, fp32) goes from global
     // memory straight into one of three LDS window buffers (buffer_load_dwordx4 ... lds: no registers, no staging
     // stores): item i = (pixel i >> 2, channel quad i & 3) lies at byte 16 i of the buffer, i.e. the 64 lanes of a
@@ -254,24 +236,12 @@ __global__ __launch_bounds__(THREADS) void conv_wino_bf16m_kernel(const Args a) 
     static_assert(NLOAD == 6 && 2 * PAIRITEMS == WINITEMS, "the vmcnt immediates above count 6 (5) loads per window, whole or paired");
     // this thread's 4x4 patch inside a staged window: rows 2*pty .. +3, columns 2*ptx .. +3, quad pq
     const int patch0 = ((2 * pty) * WINW + 2 * ptx) * (CK * 4) + pq * 16;
-    // a - b on a register pair: v_pk_add_f32 with the second operand negated (there is no v_pk_sub_f32, and the
-    // compiler scalarises a vector fsub into v_sub_f32).  Every VALU instruction of a helper wave is paid in MFMA
-    // time: other waves' vector instructions do not issue while an MFMA wave of the SIMD has MFMAs queued
-    // (tools/coissue3.hip), so the transform's 72 subtractions per pass are issued as 36 packed ones.
-    auto psub = [](floatx2 x, floatx2 y) {
-      floatx2 r;
-      asm("v_pk_add_f32 %0, %1, %2 neg_lo:[0,1] neg_hi:[0,1]" : "=v"(r) : "v"(x), "v"(y));
-      return r;
-    };
-    auto sub4 = [&](floatx4 x, floatx4 y) {
-      const floatx2 l = psub(floatx2{x[0], x[1]}, floatx2{y[0], y[1]}), h = psub(floatx2{x[2], x[3]}, floatx2{y[2], y[3]});
-      return floatx4{l[0], l[1], h[0], h[1]};
-    };
+    // Every subtraction of the transform is packed (wino::sub4, wino::pk_sub): 36 issue slots per pass instead of 72.
     auto split_store = [&](floatx4 v, unsigned char* dst) {
       const unsigned h0 = cvt_pk_bf16(v[0], v[1]), h1 = cvt_pk_bf16(v[2], v[3]);
       *(uintx2*)dst = uintx2{h0, h1};
-      const floatx2 r01 = psub(floatx2{v[0], v[1]}, floatx2{bf16_lo(h0), bf16_hi(h0)});
-      const floatx2 r23 = psub(floatx2{v[2], v[3]}, floatx2{bf16_lo(h1), bf16_hi(h1)});
+      const floatx2 r01 = wino::pk_sub(floatx2{v[0], v[1]}, floatx2{bf16_lo(h0), bf16_hi(h0)});
+      const floatx2 r23 = wino::pk_sub(floatx2{v[2], v[3]}, floatx2{bf16_lo(h1), bf16_hi(h1)});
       *(uintx2*)(dst + PLANEB) = uintx2{cvt_pk_bf16(r01[0], r01[1]), cvt_pk_bf16(r23[0], r23[1])};
     };
     // B^T d B for the two xi rows of a pass: window buffer wbuf -> V buffer vb.  pass A: xi 1 = r1 + r2, xi 2 = r2 - r1
@@ -364,7 +334,7 @@ __global__ __launch_bounds__(THREADS) void conv_wino_bf16m_kernel(const Args a) 
         if (znu != 3) split_store(sub4(x[1], x[3]), dst + pair_commit_slot(MODE, hf, 3) * POSB);
       }
     };
-    auto next_ticket = [&]() { return (int)(atomicAdd(a.ticket, 1ULL) + gridDim.x); };
+    auto next_ticket = [&]() { return wino::take_ticket(a.ticket); };
 
     if (ht == 0) {
       post(0, (int)blockIdx.x);
@@ -449,9 +419,7 @@ __global__ __launch_bounds__(THREADS) void conv_wino_bf16m_kernel(const Args a) 
       }
       if (ht == 0 && more && read_slot(s_wr).item < a.ntiles) ticket_pre = next_ticket();
       cur = nxt;
-      const int s_old = s_nxt;
-      s_nxt = s_wr;
-      s_wr = s_old == 0 ? 2 : s_old - 1;
+      wino::rotate_ring(s_nxt, s_wr);
     }
 #if WBM_STAMP
     if (wave == 8) {
@@ -459,13 +427,7 @@ __global__ __launch_bounds__(THREADS) void conv_wino_bf16m_kernel(const Args a) 
       wbm_stamps[blockIdx.x * 384 + 192 + lane] = (long long)((unsigned*)(lds_raw + STAMPOFF))[192 + lane];
     }
 #endif
-    if (ht == 0) {
-      const unsigned long long done = atomicAdd(a.ticket + 1, 1ULL);
-      if (done == (unsigned long long)gridDim.x - 1) {
-        a.ticket[0] = 0ULL;
-        a.ticket[1] = 0ULL;
-      }
-    }
+    if (ht == 0) wino::rearm_ticket(a.ticket);
     return;
   }
 
@@ -536,13 +498,9 @@ __global__ __launch_bounds__(THREADS) void conv_wino_bf16m_kernel(const Args a) 
   Tile cur = read_slot(0);
   const __amdgpu_buffer_rsrc_t urs = __builtin_amdgcn_make_buffer_rsrc(
       (void*)a.u, 0, (int)(16u * pos_b * (unsigned)a.nphase), 0x00020000);
-  auto soff_item = [&](const Tile& t) { return (unsigned)(t.item & (a.nphase - 1)) * (unsigned)a.u_phase_bytes; };
+  auto soff_item = [&](const Tile& t) { return wb::soff_item(t, a.nphase, a.u_phase_bytes, nchunks, chunk_b); };
   unsigned soff_phase = soff_item(cur);
-  auto fetch = [&](bf16x8 (&dst)[P], unsigned so) {
-#pragma unroll
-    for (int q = 0; q < P; ++q)
-      dst[q] = __builtin_bit_cast(bf16x8, __builtin_amdgcn_raw_buffer_load_b128(urs, ulane, so + (unsigned)q * plane_b, 0));
-  };
+  auto fetch = [&](bf16x8 (&dst)[P], unsigned so) { wb::fetch_u(dst, urs, ulane, so, plane_b); };
 #pragma unroll
   for (int f = 0; f < RING; ++f) fetch(Bq[f], soff_phase + (unsigned)gpos<MODE, 0, PQ>(f) * pos_b);
   int s_nxt = 1;
@@ -553,7 +511,9 @@ __global__ __launch_bounds__(THREADS) void conv_wino_bf16m_kernel(const Args a) 
 #endif
     const Tile nxt = read_slot(s_nxt);
     const unsigned soff_phase_nxt = soff_item(nxt.item < a.ntiles ? nxt : cur);
-    unsigned tzero_xi = 4, tzero_nu = 4;   // MODE 2: the phase's zero row / column, for the whole tile
+    // MODE 2: the phase's zero row / column, for the whole tile.  zero_xi_of / zero_nu_of (conv_wino_pair.h), kept
+    // local: read from there, the MFMA schedule of the MODE 2 instances and operand orders in the others move.
+    unsigned tzero_xi = 4, tzero_nu = 4;
     if (MODE == 2) {
       const int phase = cur.item & 3;
       if (phase >> 1) tzero_xi = 0;
@@ -759,14 +719,7 @@ __global__ __launch_bounds__(THREADS) void conv_wino_bf16m_kernel(const Args a) 
         constexpr int ACT = decltype(act_tag)::value;
 #pragma unroll
         for (int e = 0; e < 16; e += 2) {
-          floatx2 v = {y[e], y[e + 1]};
-          v = v + floatx2{pbias, pbias};
-          if (ACT == DSIC_ACT_GDN || ACT == DSIC_ACT_IGDN) {
-            v = gdn_pair<ACT == DSIC_ACT_IGDN>(v, floatx2{pbeta, pbeta}, floatx2{pgamma, pgamma});
-          } else if (ACT == DSIC_ACT_RELU) {
-            v[0] = v[0] > 0.f ? v[0] : 0.f;
-            v[1] = v[1] > 0.f ? v[1] : 0.f;
-          }
+          const floatx2 v = wino::bias_act<ACT>(floatx2{y[e], y[e + 1]}, pbias, pbeta, pgamma);
           const float v0 = v[0], v1 = v[1];
           tw[((e & 3) + 8 * (e >> 2)) * 32] = v0;
           tw[(((e + 1) & 3) + 8 * ((e + 1) >> 2)) * 32] = v1;
@@ -789,14 +742,7 @@ __global__ __launch_bounds__(THREADS) void conv_wino_bf16m_kernel(const Args a) 
         asm volatile("s_nop 15\n\ts_nop 15\n\ts_nop 15\n\ts_nop 15" ::: "memory");
       };
       auto emit_act = [&](int m, int j, const floatx16& y) {
-        if (a.act == DSIC_ACT_GDN)
-          emit(std::integral_constant<int, DSIC_ACT_GDN>{}, m, j, y);
-        else if (a.act == DSIC_ACT_IGDN)
-          emit(std::integral_constant<int, DSIC_ACT_IGDN>{}, m, j, y);
-        else if (a.act == DSIC_ACT_RELU)
-          emit(std::integral_constant<int, DSIC_ACT_RELU>{}, m, j, y);
-        else
-          emit(std::integral_constant<int, DSIC_ACT_NONE>{}, m, j, y);
+        wino::for_act(a.act, [&](auto act_tag) { emit(act_tag, m, j, y); });
       };
 #pragma unroll
       for (int m = 0; m < 2; ++m) {
@@ -810,7 +756,7 @@ __global__ __launch_bounds__(THREADS) void conv_wino_bf16m_kernel(const Args a) 
 #pragma unroll
     for (int f = 0; f < RING; ++f) fetch(Bq[f], soff_phase + (unsigned)gpos<MODE, 0, PQ>(f) * pos_b);
     cur = nxt;
-    s_nxt = s_nxt == 2 ? 0 : s_nxt + 1;
+    s_nxt = wino::step_ring(s_nxt);
   }
 #if WBM_STAMP
   if (wave == 0 || wave == 4) {   // slot 127: the item of the stamped tile
