@@ -34,6 +34,16 @@ Because tiles are independent and the DSIC2 heads hold every string's length, an
 from only the tiles that own its pixels: stream_index finds their bytes from the heads alone, decompress_region decodes
 them in dense batches and stitches them into the window, byte for byte the crop of decompress_image's result.
 decompress_image is the same decode (_decode_window) of the window (0, 0, H, W), one batch per container.
+
+overviews = n > 0 writes a pyramid, the image at full, 1/2, 1/4, ... 1/2^n resolution in one DSICP stream:
+
+    magic "DSICP\\0" | version u16 = 1 | levels u32 (n + 1 >= 2) | levels x (H u32, W u32, offset u64, length u64) |
+    the level streams back to back, level 0 first                 (little endian; offsets count from the magic)
+
+Level l + 1 is level l halved on the device (build_overviews: ceil(H/2) x ceil(W/2), the mean of each 2 x 2 block with
+the last row or column of an odd side counted twice; uint8 (a + b + c + d + 2) >> 2, float32 ((a + b) + (c + d)) *
+0.25f), and every level's bytes are the DSICI stream compress_image writes for that level's image, so a level is
+read, indexed and decoded on its own (level=l of the decoders and of stream_index) through a view of its byte range.
 """
 from __future__ import annotations
 
@@ -60,6 +70,11 @@ _HEAD = struct.Struct("<6sHI6I4I2I")
 _SEGS = struct.Struct("<I")
 _RES = struct.Struct("<II")                                                # version 4: max_error, res_bands
 _LEN = struct.Struct("<Q")
+PMAGIC = b"DSICP\x00"
+PVERSION = 1
+_PHEAD = struct.Struct("<6sHI")                                            # magic, version, levels
+_PLEVEL = struct.Struct("<IIQQ")                                           # H, W, offset, length
+_SAME_IN_LEVELS = ("C", "kind", "N", "M", "in_ch", "spatial_params", "numerics")
 
 
 def _ceil16(n):
@@ -197,10 +212,12 @@ class _Source:
         return out
 
 
-def _read_framing(src):
+def _read_framing(src, head=None):
     """The DSICI head and the length words of a _Source -> (header fields, (offset, bytes) of every batch's container,
-    the same of every batch's residual block: empty below version 4); what lies inside them is not read."""
-    head = src.read_at(0, _HEAD.size)
+    the same of every batch's residual block: empty below version 4); what lies inside them is not read.  head: the
+    first _HEAD.size bytes, where the caller has read them already."""
+    if head is None:
+        head = src.read_at(0, _HEAD.size)
     if len(head) < _HEAD.size:
         raise ValueError("truncated DSICI stream" if head[:6] == MAGIC[:len(head)] else "not a DSICI image stream")
     f = _HEAD.unpack(head)
@@ -268,9 +285,227 @@ def unpack_image_stream(stream) -> dict:
 
 
 def image_bpp(stream) -> float:
-    """8 * stream bytes / (H * W): the whole stream, headers included."""
+    """8 * stream bytes / (H * W): the whole stream, headers included.  A DSICP stream: all its levels over the pixels
+    of level 0."""
+    if bytes(stream[:6]) == PMAGIC:
+        H, W, _, _ = _PLEVEL.unpack_from(bytes(stream[_PHEAD.size:_PHEAD.size + _PLEVEL.size]), 0)
+        return 8.0 * len(stream) / (H * W)
     h = _HEAD.unpack_from(bytes(stream[:_HEAD.size]), 0)
     return 8.0 * len(stream) / (h[3] * h[4])
+
+
+# ---- overviews: the image at 1/2, 1/4, ... resolution beside it, each level a stream of its own ------------------
+def _halved(n):
+    return (n + 1) // 2
+
+
+def overview_shapes(H, W, n) -> list:
+    """[(H, W), (ceil(H/2), ceil(W/2)), ...]: the sizes of an H x W image and its n overview levels, each the one
+    before it halved and rounded up (pure Python).  ValueError if n is not an integer >= 0, or if a level is not an
+    image the codec takes (its padded side under 32, or its reflect padding not smaller than the level); the message
+    names the first such level."""
+    try:
+        n = operator.index(n)
+    except TypeError:
+        raise ValueError(f"overviews={n!r} is not an integer") from None
+    if n < 0:
+        raise ValueError(f"overviews={n} must be at least 0")
+    shapes = [(int(H), int(W))]
+    for _ in range(n):
+        shapes.append((_halved(shapes[-1][0]), _halved(shapes[-1][1])))
+    for level, (h, w) in enumerate(shapes):
+        try:
+            _check_image(h, w)
+        except ValueError as e:
+            raise ValueError(f"overview level {level} of a {H}x{W} image: {e}") from None
+    return shapes
+
+
+def level_window(level, y0, x0, h, w) -> tuple:
+    """The smallest window (y0', x0', h', w') of overview level `level` that covers the level-0 window rows
+    [y0, y0+h) x columns [x0, x0+w) (pure Python): a pixel of level l covers the 2^l x 2^l block of level 0 at
+    (y << l, x << l), so y0' = y0 >> l and h' = ceil((y0 + h) / 2^l) - y0'; columns likewise."""
+    level, y0, x0, h, w = (operator.index(v) for v in (level, y0, x0, h, w))
+    if level < 0 or y0 < 0 or x0 < 0 or h < 1 or w < 1:
+        raise ValueError(f"level_window: level {level}, window {h}x{w} at ({y0}, {x0})")
+    s = (1 << level) - 1
+    return y0 >> level, x0 >> level, ((y0 + h + s) >> level) - (y0 >> level), ((x0 + w + s) >> level) - (x0 >> level)
+
+
+def level_for(index, max_side) -> int:
+    """The coarsest level of a stream_index dict whose longer side is still >= max_side, or 0 if none is (always 0 for
+    a DSICI stream): the level to decode for a view of max_side pixels without magnifying (pure Python)."""
+    levels = index.get("levels") or [{"H": index["H"], "W": index["W"]}]
+    fit = [l for l, lv in enumerate(levels) if max(lv["H"], lv["W"]) >= max_side]
+    return max(fit) if fit else 0
+
+
+def _image_kind(img, what):
+    """(kind, H, W, C) of a uint8 [H,W,C] or float32 [C,H,W] tensor."""
+    if img.dim() != 3:
+        raise ValueError(f"{what}: expected uint8 [H,W,C] or float32 [C,H,W], got {tuple(img.shape)}")
+    if img.dtype == torch.uint8:
+        H, W, C = img.shape
+        return KIND_U8_HWC, H, W, C
+    if img.dtype == torch.float32:
+        C, H, W = img.shape
+        return KIND_F32_CHW, H, W, C
+    raise TypeError(f"{what}: expected uint8 or float32, got {img.dtype}")
+
+
+@torch.no_grad()
+def build_overviews(img, n) -> list:
+    """[img, level 1, ..., level n] on the device: img uint8 [H,W,C] or float32 [C,H,W] on the GPU, each level the one
+    before it halved by dsic_image_halve_u8 / dsic_image_halve_f32 (one launch per level): ceil(H/2) x ceil(W/2), a
+    pixel the mean of its 2 x 2 block, the last row or column of an odd side counted twice; uint8 rounds half up,
+    (a + b + c + d + 2) >> 2, float32 is ((a + b) + (c + d)) * 0.25f.  The sizes are overview_shapes(H, W, n)."""
+    kind, H, W, C = _image_kind(img, "build_overviews")
+    if not img.is_cuda:
+        raise RuntimeError(f"build_overviews: expected a tensor on the GPU (no CPU fallback), got {img.device}")
+    shapes = overview_shapes(H, W, n)
+    L = _lib.load()
+    levels = [img.contiguous()]
+    for (h, w), (h2, w2) in zip(shapes, shapes[1:]):
+        src = levels[-1]
+        if kind == KIND_U8_HWC:
+            dst = torch.empty((h2, w2, C), dtype=torch.uint8, device=src.device)
+            _lib.check(L.dsic_image_halve_u8(_p(src), _p(dst), h, w, C, _stream()), "image_halve_u8")
+        else:
+            dst = torch.empty((C, h2, w2), dtype=torch.float32, device=src.device)
+            _lib.check(L.dsic_image_halve_f32(_p(src), _p(dst), C, h, w, _stream()), "image_halve_f32")
+        levels.append(dst)
+    return levels
+
+
+def pack_pyramid_stream(level_streams) -> bytes:
+    """DSICI streams of an image and its overviews, level 0 first -> one DSICP stream (pure Python): the directory
+    (H, W from each stream's own head; absolute offset and length of its bytes), then the streams back to back.
+    ValueError for fewer than two levels, sizes that are not the halving chain of level 0, or levels that disagree on
+    C, kind, the model's shape or the numerics tag."""
+    streams = [bytes(s) for s in level_streams]
+    if len(streams) < 2:
+        raise ValueError(f"pack_pyramid_stream: {len(streams)} level(s); a pyramid has at least two")
+    heads = [_read_framing(_Source(s))[0] for s in streams]
+    _check_levels([(h["H"], h["W"]) for h in heads], heads)
+    off = _PHEAD.size + _PLEVEL.size * len(streams)
+    parts = [_PHEAD.pack(PMAGIC, PVERSION, len(streams))]
+    for h, s in zip(heads, streams):
+        parts.append(_PLEVEL.pack(h["H"], h["W"], off, len(s)))
+        off += len(s)
+    return b"".join(parts + streams)
+
+
+def _check_levels(sizes, heads):
+    """sizes: (H, W) per level as the directory has them; heads: the DSICI header fields of the levels that were read
+    (None for the others)."""
+    for l in range(1, len(sizes)):
+        want = (_halved(sizes[l - 1][0]), _halved(sizes[l - 1][1]))
+        if tuple(sizes[l]) != want:
+            raise ValueError(f"DSICP stream: level {l} is {sizes[l][0]}x{sizes[l][1]}, level {l - 1} "
+                             f"({sizes[l - 1][0]}x{sizes[l - 1][1]}) halves to {want[0]}x{want[1]}")
+    first = None
+    for l, h in enumerate(heads):
+        if h is None:
+            continue
+        if (h["H"], h["W"]) != tuple(sizes[l]):
+            raise ValueError(f"DSICP stream: the directory gives level {l} as {sizes[l][0]}x{sizes[l][1]}, its own "
+                             f"head says {h['H']}x{h['W']}")
+        if first is None:
+            first = l
+        for key in _SAME_IN_LEVELS:
+            if h[key] != heads[first][key]:
+                raise ValueError(f"DSICP stream: levels {first} and {l} disagree on {key} ({heads[first][key]} and "
+                                 f"{h[key]})")
+
+
+def _read_directory(src, head):
+    """The directory of a DSICP _Source whose first _HEAD.size bytes are `head` (the directory of two levels is just
+    as long) -> [{"H", "W", "offset", "length"}]; the level streams are not read."""
+    if len(head) < _PHEAD.size:
+        raise ValueError("truncated DSICP stream")
+    _, version, levels = _PHEAD.unpack_from(head, 0)
+    if version != PVERSION:
+        raise ValueError(f"DSICP stream version {version}, this reader knows {PVERSION}")
+    if levels < 2:
+        raise ValueError(f"DSICP stream: {levels} level(s); a pyramid has at least two")
+    end = _PHEAD.size + _PLEVEL.size * levels
+    if end > src.size:
+        raise ValueError("truncated DSICP stream")
+    table = bytes(head[:end])
+    if end > len(table):
+        table += bytes(src.read_at(len(table), end - len(table)))
+    out, off = [], end
+    for l in range(levels):
+        H, W, offset, length = _PLEVEL.unpack_from(table, _PHEAD.size + _PLEVEL.size * l)
+        if offset != off:
+            raise ValueError(f"DSICP stream: level {l} at offset {offset}, expected {off} (the directory's end, then "
+                             "the levels back to back)")
+        off += length
+        if off > src.size:
+            raise ValueError("truncated DSICP stream")
+        out.append({"H": H, "W": W, "offset": offset, "length": length})
+    if off != src.size:
+        raise ValueError(f"DSICP stream: {src.size - off} trailing bytes")
+    _check_levels([(d["H"], d["W"]) for d in out], [])
+    return out
+
+
+class _Level:
+    """One level's bytes of a DSICP _Source as a source of its own: offsets count from the level's first byte, and
+    nothing outside its `size` bytes is read, so the DSICI checks for truncated and trailing bytes hold per level."""
+
+    def __init__(self, source, base, size):
+        self.source, self.base, self.size = source, base, size
+
+    @property
+    def bytes_read(self):
+        return self.source.bytes_read
+
+    def read_at(self, off, n):
+        return self.source.read_at(self.base + off, max(0, min(n, self.size - off)))
+
+
+def _open_level(src, level):
+    """src (bytes or a file object) -> (the source the chosen level's DSICI stream is read from, its index with
+    offsets inside that source, the level's first byte in src, the DSICP directory or None for a DSICI src)."""
+    source = _Source(src)
+    head = source.read_at(0, _HEAD.size)
+    try:
+        level = 0 if level is None else operator.index(level)
+    except TypeError:
+        raise ValueError(f"level={level!r} is not an integer") from None
+    if bytes(head[:len(PMAGIC)]) != PMAGIC:
+        if level != 0:
+            raise ValueError(f"level={level}: a DSICI stream holds one image, level 0")
+        return source, _index_of(source, head), 0, None
+    levels = _read_directory(source, head)
+    if not 0 <= level < len(levels):
+        raise ValueError(f"level={level}: the DSICP stream holds levels 0 .. {len(levels) - 1}")
+    d = levels[level]
+    view = _Level(source, d["offset"], d["length"])
+    ix = _index_of(view)
+    _check_levels([(v["H"], v["W"]) for v in levels], [None] * level + [ix])
+    ix.update(level=level, levels=levels)
+    return view, ix, d["offset"], levels
+
+
+def unpack_pyramid_stream(stream) -> dict:
+    """DSICP stream -> {"version", "levels": [{"H", "W", "offset", "length", "stream"}]}, stream the level's DSICI
+    bytes (pure Python).  ValueError on a wrong magic or version, fewer than two levels, a truncated directory or
+    stream, offsets that are not the directory's end and then back to back, trailing bytes, sizes that are not the
+    halving chain of level 0, a level whose own head gives another H or W than the directory, and levels that
+    disagree on C, kind, N, M, in_ch, spatial_params or the numerics tag."""
+    s = bytes(stream)
+    src = _Source(s)
+    head = src.read_at(0, _HEAD.size)
+    if bytes(head[:len(PMAGIC)]) != PMAGIC:
+        raise ValueError("truncated DSICP stream" if len(head) < len(PMAGIC) and bytes(head) == PMAGIC[:len(head)]
+                         else "not a DSICP pyramid stream")
+    levels = _read_directory(src, head)
+    for d in levels:
+        d["stream"] = s[d["offset"]:d["offset"] + d["length"]]
+    _check_levels([(d["H"], d["W"]) for d in levels], [_read_framing(_Source(d["stream"]))[0] for d in levels])
+    return {"version": PVERSION, "levels": levels}
 
 
 def _gather(img, kind, g, C, first, n):
@@ -292,35 +527,8 @@ def _gather(img, kind, g, C, first, n):
     return tiles
 
 
-@torch.no_grad()
-def compress_image(model, img, tile=256, batch=64, tail=10, segments=1, overlap=0, max_error=None) -> bytes:
-    """img: uint8 [H,W,C] or float32 [C,H,W] in [0,1], on the CPU or the GPU -> one DSICI stream.  The image is
-    uploaded once; each batch of `batch` tiles is gathered on the device (reflect padding included) and becomes one
-    DSIC2 container.  segments = K > 1 (1, 2, 4, 8 or 16, dividing M): every tile's y string is K independent strings
-    (DSIC3 containers, stream version 2), which the decoders read on K waves per tile; the decoded image is the same.
-    overlap = O > 0 (a multiple of 16, at most half a tile side): tiles share O pixels with their neighbours
-    (tile_grid) and the decoders cross-fade them over that band (stream version 3); 0 writes today's streams.
-    max_error = tau (an integer 0 .. 127; uint8 images, overlap = 0): the near-lossless mode (stream version 4).
-    Behind every container, byte for byte the one written without max_error, goes a residual block (residual.py),
-    and the decoders return a uint8 image within tau of img on every pixel and channel; 0 is lossless.  None writes
-    today's streams."""
-    dev = next(model.parameters()).device
-    tau = None if max_error is None else _residual.check_max_error(max_error, "compress_image")
-    if img.dim() != 3:
-        raise ValueError(f"compress_image: expected uint8 [H,W,C] or float32 [C,H,W], got {tuple(img.shape)}")
-    if img.dtype == torch.uint8:
-        kind, (H, W, C) = KIND_U8_HWC, img.shape
-    elif img.dtype == torch.float32:
-        kind, (C, H, W) = KIND_F32_CHW, img.shape
-    else:
-        raise TypeError(f"compress_image: expected uint8 or float32, got {img.dtype}")
-    N, M, in_ch, spatial = _model_shape(model)
-    segments = entropy.check_segments(segments, M, "compress_image")
-    if C != in_ch:
-        raise ValueError(f"compress_image: image has {C} channels, the model takes {in_ch}")
-    batch = int(batch)
-    if batch < 1:
-        raise ValueError(f"compress_image: batch={batch}")
+def _level_grid(H, W, kind, tile, overlap, tau):
+    """tile_grid of one image as compress_image codes it, and its overlap; ValueError where it cannot."""
     g = tile_grid(H, W, tile, overlap)
     overlap = _check_overlap(overlap, g["th"], g["tw"], "compress_image")
     if tau is not None:
@@ -330,7 +538,15 @@ def compress_image(model, img, tile=256, batch=64, tail=10, segments=1, overlap=
         if overlap:
             raise ValueError("compress_image: max_error together with overlap > 0 is not supported (the predictor "
                              "would be the blended image)")
-    x = img.to(dev).contiguous()
+    return g, overlap
+
+
+def _compress_device_image(model, x, tile, batch, tail, segments, overlap, tau) -> bytes:
+    """compress_image's work on one image that lies contiguous on the model's device, after the argument checks that
+    do not depend on its size -> its DSICI stream."""
+    kind, H, W, C = _image_kind(x, "compress_image")
+    N, M, in_ch, spatial = _model_shape(model)
+    g, overlap = _level_grid(H, W, kind, tile, overlap, tau)
     blobs, residuals = [], None if tau is None else []
     for first in range(0, g["n"], batch):
         n = min(batch, g["n"] - first)
@@ -349,6 +565,51 @@ def compress_image(model, img, tile=256, batch=64, tail=10, segments=1, overlap=
     if tau is not None:
         header["max_error"] = tau
     return pack_image_stream(header, blobs, residuals)
+
+
+@torch.no_grad()
+def compress_image(model, img, tile=256, batch=64, tail=10, segments=1, overlap=0, max_error=None,
+                   overviews=0) -> bytes:
+    """img: uint8 [H,W,C] or float32 [C,H,W] in [0,1], on the CPU or the GPU -> one DSICI stream.  The image is
+    uploaded once; each batch of `batch` tiles is gathered on the device (reflect padding included) and becomes one
+    DSIC2 container.  segments = K > 1 (1, 2, 4, 8 or 16, dividing M): every tile's y string is K independent strings
+    (DSIC3 containers, stream version 2), which the decoders read on K waves per tile; the decoded image is the same.
+    overlap = O > 0 (a multiple of 16, at most half a tile side): tiles share O pixels with their neighbours
+    (tile_grid) and the decoders cross-fade them over that band (stream version 3); 0 writes today's streams.
+    max_error = tau (an integer 0 .. 127; uint8 images, overlap = 0): the near-lossless mode (stream version 4).
+    Behind every container, byte for byte the one written without max_error, goes a residual block (residual.py),
+    and the decoders return a uint8 image within tau of img on every pixel and channel; 0 is lossless.  None writes
+    today's streams.
+    overviews = n > 0 writes a DSICP stream instead (pack_pyramid_stream): the image and its n overview levels
+    (build_overviews, made on the device from the one upload), every level coded with the same tile, batch, tail,
+    segments and overlap, its bytes the DSICI stream this call returns for that level's image alone; a level smaller
+    than a tile is one smaller tile (tile_grid), and a level the codec does not take (overview_shapes), or whose
+    tiles are too small for the overlap, is a ValueError before anything is coded.  max_error applies to level 0
+    only, which is then the version-4 stream of the call without overviews; the overview levels are the lossy
+    streams: an overview is a preview, and a residual layer there would add bytes to bound an error against an image
+    the caller never supplied.  0 writes today's streams."""
+    dev = next(model.parameters()).device
+    tau = None if max_error is None else _residual.check_max_error(max_error, "compress_image")
+    kind, H, W, C = _image_kind(img, "compress_image")
+    N, M, in_ch, spatial = _model_shape(model)
+    segments = entropy.check_segments(segments, M, "compress_image")
+    if C != in_ch:
+        raise ValueError(f"compress_image: image has {C} channels, the model takes {in_ch}")
+    batch = int(batch)
+    if batch < 1:
+        raise ValueError(f"compress_image: batch={batch}")
+    shapes = overview_shapes(H, W, overviews) if overviews != 0 else [(H, W)]
+    for level, (h, w) in enumerate(shapes):
+        try:
+            _level_grid(h, w, kind, tile, overlap, tau if level == 0 else None)
+        except ValueError as e:
+            raise ValueError(f"{e} (overview level {level}, {h}x{w})" if level else str(e)) from None
+    x = img.to(dev).contiguous()
+    if len(shapes) == 1:
+        return _compress_device_image(model, x, tile, batch, tail, segments, overlap, tau)
+    return pack_pyramid_stream([_compress_device_image(model, lv, tile, batch, tail, segments, overlap,
+                                                       tau if level == 0 else None)
+                                for level, lv in enumerate(build_overviews(x, overviews))])
 
 
 def _owned_in_tile(g, t):
@@ -400,9 +661,9 @@ def _out_image(kind, C, h, w, dev, what):
 
 
 # ---- decode: any window of an image stream from only its tiles; the whole image is the window (0, 0, H, W) ------
-def _index_of(src):
-    """stream_index on an open _Source."""
-    ix, frames, rframes = _read_framing(src)
+def _index_of(src, head=None):
+    """stream_index on an open _Source (head: as _read_framing takes it)."""
+    ix, frames, rframes = _read_framing(src, head)
     g = _stream_grid(ix)
     tiles, containers = [], []
     for k, (off, size) in enumerate(frames):
@@ -436,7 +697,7 @@ def _index_of(src):
     return ix
 
 
-def stream_index(src) -> dict:
+def stream_index(src, level=None) -> dict:
     """Where every tile of a DSICI stream lies, from its heads alone (pure Python).  src: bytes / bytearray /
     memoryview, or a binary file object with seek and read.  Only the 60-byte header and, per batch, the 8-byte
     length, the 38-byte DSIC2 header and the 24-byte records are read (version 2: 64 bytes, and per batch the 42-byte
@@ -456,8 +717,25 @@ def stream_index(src) -> dict:
     ValueError as unpack_image_stream, entropy.unpack_container and decompress_image raise it: wrong magic or version,
     DSIC1 container, truncated stream or container, trailing bytes, batches that do not match the grid, latents that
     do not match the tile size, a container whose numerics tag or segment count is not the stream's, segment lengths
-    that do not add up."""
-    return _index_of(_Source(src))
+    that do not add up.
+
+    On a DSICP stream: the index of level 0, or of `level`, read from the directory and that level's heads alone.
+    Every offset (offset, r_offset, z_off, y_off, r_off) counts from the start of src, so tile_spans gives byte ranges
+    of src; beside the keys above the dict has level, levels (the directory: H, W, offset, length per level),
+    stream_bytes (the whole pyramid) and index_bytes (what this call read).  ValueError as unpack_pyramid_stream,
+    for a level the stream does not hold, and for a level other than 0 of a DSICI stream."""
+    _, ix, base, levels = _open_level(src, level)
+    if levels is not None:
+        for c in ix["containers"]:
+            c["offset"] += base
+            if "r_offset" in c:
+                c["r_offset"] += base
+        for t in ix["tiles"]:
+            for key in ("z_off", "y_off", "r_off"):
+                if key in t:
+                    t[key] += base
+        ix.update(stream_bytes=levels[-1]["offset"] + levels[-1]["length"])
+    return ix
 
 
 def window_tiles(index_or_grid, y0, x0, h, w) -> list:
@@ -504,12 +782,12 @@ def tile_spans(index, tiles) -> list:
     return [tuple(s) for s in spans]
 
 
-def _decode_window(model, src, window, out, batch, stats, what):
-    """decompress_region's work; window None = the whole image, batch None = the stream's tiles per container."""
+def _decode_window(model, src, window, out, batch, stats, what, level=0):
+    """decompress_region's work; window None = the whole image, batch None = the stream's tiles per container.  Of a
+    DSICP stream the chosen level is decoded, through a view of its bytes."""
     if out not in (None, "u8", "f32"):
         raise ValueError(f"{what}: out={out!r} (None, 'u8' or 'f32')")
-    source = _Source(src)
-    ix = _index_of(source)
+    source, ix, _, _ = _open_level(src, level)
     _refuse_foreign(model, ix, what)
     H, W, C, th, tw = ix["H"], ix["W"], ix["C"], ix["th"], ix["tw"]
     y0, x0, h, w = (0, 0, H, W) if window is None else window
@@ -581,19 +859,21 @@ def _decode_window(model, src, window, out, batch, stats, what):
 
 
 @torch.no_grad()
-def decompress_image(model, stream, out=None):
+def decompress_image(model, stream, out=None, level=0):
     """DSICI stream -> the image on the model's device: uint8 [H,W,C] ((uint8)(clamp(x,0,1)*255), truncating, as
     torchvision's to_pil_image) or float32 [C,H,W] (clamp(x,0,1)); by default the kind of the encoder's input,
     out="u8" / "f32" overrides it.  The whole image as a window, decoded container by container; each decoded batch
     is stitched straight into the image.  A stream with overlap (version 3) is blended instead: each decoded batch
     is added into a zeroed float32 canvas (the output itself for float32) with the tiles' ramp weights, and a finishing
     pass takes min(v, 1) and, for uint8, (uint8)(v*255).  A near-lossless stream (version 4) decodes to the uint8 image
-    clamp(p + q s, 0, 255) of residual.py, within max_error of the original; out="f32" returns that image / 255."""
-    return _decode_window(model, stream, None, out, None, None, "decompress_image")
+    clamp(p + q s, 0, 255) of residual.py, within max_error of the original; out="f32" returns that image / 255.  A DSICP stream (compress_image with
+    overviews) decodes to its level `level`, 0 the full image, as that level's own DSICI stream does; any other level
+    than 0 of a DSICI stream, or a level the pyramid does not hold, is a ValueError."""
+    return _decode_window(model, stream, None, out, None, None, "decompress_image", level)
 
 
 @torch.no_grad()
-def decompress_region(model, src, y0, x0, h, w, out=None, batch=64, stats=None):
+def decompress_region(model, src, y0, x0, h, w, out=None, batch=64, stats=None, level=0):
     """The window rows [y0, y0+h) x columns [x0, x0+w) of a DSICI stream, decoded from only the tiles that own its
     pixels: uint8 [h,w,C] or float32 [C,h,w] on the model's device, the same bytes decompress_image(...) gives there
     (out as in decompress_image).  src: the stream as bytes, or a binary file object, of which only the heads
@@ -601,8 +881,11 @@ def decompress_region(model, src, y0, x0, h, w, out=None, batch=64, stats=None):
     batches of at most `batch`, in ascending tile order, whatever containers they come from; each batch is one
     upload and is stitched (blended, for a stream with overlap: then "own" reads "weigh on", and the bits do not
     depend on `batch`) into the window as soon as it is decoded.  stats (a dict) receives tiles, decode_batches,
-    bytes_read and bytes_uploaded (the padded string bytes; 52 bytes of descriptors per tile travel beside them)."""
+    bytes_read and bytes_uploaded (the padded string bytes; 52 bytes of descriptors per tile travel beside them).
+    level: of a DSICP stream, the overview level to decode; the window is in that level's own pixel grid
+    (level_window maps a level-0 window to it), and only the directory, that level's heads and its selected tiles'
+    strings are read."""
     batch = int(batch)
     if batch < 1:
         raise ValueError(f"decompress_region: batch={batch}")
-    return _decode_window(model, src, (y0, x0, h, w), out, batch, stats, "decompress_region")
+    return _decode_window(model, src, (y0, x0, h, w), out, batch, stats, "decompress_region", level)

@@ -582,6 +582,19 @@ int dsic_tile_stitch_window_u8_res(const float* tiles, const float* q, int tau,
                                    const int* tile_ids, int n, uint8_t* out, int H, int W, int C,
                                    int th, int tw, int wy0, int wx0, int wh, int ww, void* stream);
 
+/* ---- image overviews (codec.build_overviews, compress_image with overviews = n) ----
+ * One level of the pyramid from the one before it: dst is H2 x W2, H2 = ceil(H/2), W2 = ceil(W/2),
+ * and output pixel (y, x) is taken from source rows 2y and min(2y+1, H-1) and columns 2x and
+ * min(2x+1, W-1): on an odd side the last row or column counts twice, and nothing outside
+ * H x W is read.  With a = top-left, b = top-right, c = bottom-left, d = bottom-right:
+ * halve_u8: uint8 [H][W][C] -> uint8 [H2][W2][C], (a + b + c + d + 2) >> 2 per channel.
+ * halve_f32: float32 [C][H][W] -> float32 [C][H2][W2], ((a + b) + (c + d)) * 0.25f, unfused.
+ * C, H, W >= 1; src and dst at any (element) alignment, and they must not overlap. */
+int dsic_image_halve_u8(const uint8_t* src_hwc, uint8_t* dst_hwc, int H, int W, int C,
+                        void* stream);
+int dsic_image_halve_f32(const float* src_chw, float* dst_chw, int C, int H, int W,
+                         void* stream);
+
 /* HIP stream limited to the CUs whose bit is set in mask_host[words] (bit i of
  * word i/32 = CU i).  Used to give the range coder its own few CUs beside the
  * conv kernels; there is no reference counterpart (the reference is

@@ -1,8 +1,10 @@
-"""Compress an image of any size to one DSICI stream, or decompress a stream back to an image.
+"""Compress an image of any size to one DSICI stream (with overviews: one DSICP stream), or decompress a stream back to
+an image.
 
     python tools/dsic_image.py compress   --weights CKPT.pt IN.png  OUT.dsic [--tile 256] [--batch 64] [--segments K] [--overlap O]
-                                          [--max-error T]
+                                          [--max-error T] [--overviews N]
     python tools/dsic_image.py decompress --weights CKPT.pt IN.dsic OUT.png [--out u8|f32] [--region Y0,X0,H,W]
+                                          [--level L]
     python tools/dsic_image.py info       IN.dsic
 
 --segments K (2, 4, 8 or 16) codes every tile's y string as K independent strings, which a decoder reads on K waves per
@@ -11,6 +13,10 @@ tile (a version-2 stream, a fraction of a percent larger; the decoded image is t
 stream; more tiles, so more bytes).  --max-error T (0 .. 127, uint8 images) adds the near-lossless residual layer (a
 version-4 stream): every decoded pixel lies within T of the original, 0 is lossless.  --region decodes only the tiles that own the window's pixels and reads only their bytes of the file; info prints the
 geometry, the tile grid and the bytes of every batch from the stream's heads, without a model or a GPU.
+--overviews N stores the image at 1/2 ... 1/2^N resolution beside it (a DSICP stream: every level a stream of its own,
+coded with the same options; --max-error bounds level 0 only).  --level L decodes level L of such a stream (0 = the
+full image) from that level's bytes alone; with --region the window is in level L's own pixels.  info prints the
+levels of a DSICP stream (size, bytes, tiles), then level 0.
 
 The state dict is loaded plain or from under "model" (code/modelv2/eval_selfcontained_entropy.py:130-134); the model's
 N, M, input channels and spatial_params are read from its shapes.  Images are PNG through PIL when PIL is importable
@@ -80,7 +86,8 @@ def write_image(path, img):
 
 def print_info(ix):
     """stream_index's dict as text: geometry, tile grid, and bytes / bpp of every batch (bpp over the pixels its tiles
-    own)."""
+    own).  For a level of a DSICP stream the bytes and bpp of the first line are the whole pyramid's over the pixels
+    of that level."""
     g = ix["grid"]
     kind = {0: "uint8 HWC", 1: "float32 CHW"}.get(ix["kind"], f"kind {ix['kind']}")
     print(f"[dsic_image] {ix['H']}x{ix['W']}x{ix['C']} {kind}, {ix['stream_bytes']} bytes, "
@@ -118,13 +125,22 @@ def main(argv=None):
                     help="compress: near-lossless, every decoded pixel within T (0 .. 127) of the original; 0 = lossless")
     ap.add_argument("--out", choices=("u8", "f32"), default=None, help="decoded kind (default: the encoder's input's)")
     ap.add_argument("--region", default=None, metavar="Y0,X0,H,W", help="decompress: only this window of the image")
+    ap.add_argument("--overviews", type=int, default=0, metavar="N",
+                    help="compress: store N halved levels beside the image (a DSICP stream)")
+    ap.add_argument("--level", type=int, default=0, metavar="L",
+                    help="decompress: the overview level of a DSICP stream (0 = the full image); --region counts in it")
     ap.add_argument("--min-nu", type=float, default=2.0)
     ap.add_argument("--max-nu", type=float, default=100.0)
     a = ap.parse_args(argv)
     from dsic_amd import codec
     if a.mode == "info":
         with open(a.src, "rb") as f:
-            print_info(codec.stream_index(f))
+            ix = codec.stream_index(f)
+            for l, lv in enumerate(ix.get("levels", ())):
+                tiles = ix["grid"]["n"] if l == 0 else codec.stream_index(f, level=l)["grid"]["n"]
+                print(f"[dsic_image] level {l}: {lv['H']}x{lv['W']}, {lv['length']} bytes at {lv['offset']}, "
+                      f"{tiles} tile(s)")
+            print_info(ix)
         return
     if a.dst is None or a.weights is None:
         ap.error(f"{a.mode} needs a destination and --weights")
@@ -140,24 +156,31 @@ def main(argv=None):
     if a.mode == "compress":
         img = read_image(a.src, codec._model_shape(model)[2])
         stream = codec.compress_image(model, img, tile=a.tile, batch=a.batch, tail=a.tail, segments=a.segments,
-                                      overlap=a.overlap, max_error=a.max_error)
+                                      overlap=a.overlap, max_error=a.max_error, overviews=a.overviews)
         with open(a.dst, "wb") as f:
             f.write(stream)
-        h = codec.unpack_image_stream(stream)
+        if a.overviews:
+            levels = codec.unpack_pyramid_stream(stream)["levels"]
+            print(f"[dsic_image] {len(levels)} levels: " + ", ".join(f"{lv['H']}x{lv['W']} {lv['length']} bytes"
+                                                                       for lv in levels))
+            h = codec.unpack_image_stream(levels[0]["stream"])
+        else:
+            h = codec.unpack_image_stream(stream)
         print(f"[dsic_image] {h['H']}x{h['W']}x{h['C']} -> {len(stream)} bytes, {codec.image_bpp(stream):.4f} bpp, "
               f"{h['batches']} batch(es) of {h['th']}x{h['tw']} tiles, {h['segments']} segment(s) per y string, "
               f"overlap {h['overlap']}" + (f", max_error {h['max_error']}" if "max_error" in h else ""))
     elif region is not None:
         stats = {}
         with open(a.src, "rb") as f:
-            img = codec.decompress_region(model, f, *region, out=a.out, batch=a.batch, stats=stats)
+            img = codec.decompress_region(model, f, *region, out=a.out, batch=a.batch, stats=stats, level=a.level)
         path = write_image(a.dst, img)
-        print(f"[dsic_image] window {region[2]}x{region[3]} at ({region[0]}, {region[1]}): {len(stats['tiles'])} "
-              f"tile(s), {stats['bytes_read']} of {os.path.getsize(a.src)} bytes read -> {path}")
+        print(f"[dsic_image] window {region[2]}x{region[3]} at ({region[0]}, {region[1]})"
+              + (f" of level {a.level}" if a.level else "") + f": {len(stats['tiles'])} tile(s), "
+              f"{stats['bytes_read']} of {os.path.getsize(a.src)} bytes read -> {path}")
     else:
         with open(a.src, "rb") as f:
             stream = f.read()
-        path = write_image(a.dst, codec.decompress_image(model, stream, out=a.out))
+        path = write_image(a.dst, codec.decompress_image(model, stream, out=a.out, level=a.level))
         print(f"[dsic_image] {len(stream)} bytes -> {path}")
 
 
