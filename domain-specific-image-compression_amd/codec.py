@@ -30,6 +30,16 @@ the quantized difference between the tile and the lossy uint8 reconstruction, co
 own histogram.  The decoders add it back in the stitch, and every decoded pixel lies within tau of the original;
 tau = 0 is lossless.  Tiles stay independent, so a region still decodes from its own tiles' bytes alone.
 
+nodata = v (an integer 0 .. 255; uint8 images, overlap = 0, no max_error, no overviews) is stream version 5: the
+version-3 head with overlap word 0, then nodata u32 and coded u32 (nc), then `u64 length, mask block` (mask.py) and
+ceil(nc / batch) times `u64 length, container`; 0 containers are allowed.  A pixel is nodata iff all its channels
+equal v.  Per tile, over the pixels it owns inside H x W, the block holds a state: 0 empty (all nodata), 1 full (none),
+2 mixed.  The coded tiles are those of state 1 and 2 in ascending tile number, container k holds coded tiles k batch
+... ; their strings are byte for byte those of the stream without nodata.  A mixed tile's mask travels in the block
+as the vertical delta of its bit plane, raw or as a list of positions.  The decoders skip empty tiles altogether and
+write v at every nodata pixel after the stitch (dsic_mask_apply_u8 / _f32, which write only pixels a tile owns, so
+stray set bits outside a tile's owned rectangle are harmless).
+
 Because tiles are independent and the DSIC2 heads hold every string's length, any window of a stream can be decoded
 from only the tiles that own its pixels: stream_index finds their bytes from the heads alone, decompress_region decodes
 them in dense batches and stitches them into the window, byte for byte the crop of decompress_image's result.
@@ -51,10 +61,12 @@ import bisect
 import operator
 import struct
 
+import numpy as np
 import torch
 
 from . import entropy
 from . import lib as _lib
+from . import mask as _mask
 from . import residual as _residual
 from .entropy import EntropyError
 from .ops import _p, _stream
@@ -64,11 +76,13 @@ VERSION = 1
 VERSION_SEG = 2            # version 1 + the segments word; written only for segments > 1
 VERSION_OV = 3             # version 1 + the segments word + the overlap word; written only for overlap > 0
 VERSION_RES = 4            # the version-3 head with overlap 0 + max_error u32 + res_bands u32; a residual block per batch
+VERSION_MASK = 5           # the version-3 head with overlap 0 + nodata u32 + coded u32; a mask block, then the coded tiles' batches
 BLEND_IDS = 64             # tiles per dsic_tile_blend_window_f32 call
 KIND_U8_HWC, KIND_F32_CHW = 0, 1
 _HEAD = struct.Struct("<6sHI6I4I2I")
 _SEGS = struct.Struct("<I")
 _RES = struct.Struct("<II")                                                # version 4: max_error, res_bands
+_MASK = struct.Struct("<II")                                               # version 5: nodata, coded
 _LEN = struct.Struct("<Q")
 PMAGIC = b"DSICP\x00"
 PVERSION = 1
@@ -150,15 +164,38 @@ def _model_shape(model):
     return int(model.N), int(model.M), int(in_ch), int(bool(getattr(model, "spatial_params", False)))
 
 
-def pack_image_stream(header: dict, blobs, residuals=None) -> bytes:
+def pack_image_stream(header: dict, blobs, residuals=None, mask=None) -> bytes:
     """header (the fields unpack_image_stream returns) + the DSIC2 containers -> the stream (pure Python).  A header
     with "segments" = K > 1 writes version 2, whose containers are DSIC3 with that K; one with "overlap" = O > 0
     writes version 3 (segments word, then overlap word), whose containers are DSIC2 for K = 1 and DSIC3 otherwise.
     A header with "max_error" = tau (not None) writes version 4: segments word, overlap word 0, max_error, res_bands,
-    and behind every container its residual block from `residuals` (residual.pack_block)."""
+    and behind every container its residual block from `residuals` (residual.pack_block).
+    A header with "nodata" = v (not None) writes version 5: segments word, overlap word 0, nodata, coded (the number
+    of tiles that are not empty, counted from the block's states), then `u64 length, mask` with `mask` the mask block
+    (mask.pack_block), then the containers of the coded tiles, `batch` to a container; there may be none."""
     h = header
     K = entropy.check_segments(h.get("segments", 1), h["M"], "pack_image_stream")
     O = _check_overlap(h.get("overlap", 0), h["th"], h["tw"], "pack_image_stream")
+    if h.get("nodata") is not None:
+        v = _mask.check_nodata(h["nodata"], "pack_image_stream")
+        if O or h.get("max_error") is not None or residuals is not None:
+            raise ValueError("pack_image_stream: nodata together with overlap > 0 or max_error is not supported")
+        if mask is None:
+            raise ValueError("pack_image_stream: nodata needs the mask block")
+        mask = bytes(mask)
+        n = _grid(h["H"], h["W"], h["th"], h["tw"])["n"]
+        states, _ = _mask.read_block_head(lambda o, c: mask[o:o + c], 0, len(mask), n, h["th"], h["tw"], v,
+                                          "pack_image_stream")
+        coded = sum(1 for s in states if s != _mask.EMPTY)
+        if len(blobs) != -(-coded // h["batch"]):
+            raise ValueError(f"pack_image_stream: {len(blobs)} containers for {coded} coded tiles in batches of "
+                             f"{h['batch']}")
+        head = _HEAD.pack(MAGIC, VERSION_MASK, h["numerics"] & 0xFFFFFFFF, h["H"], h["W"], h["C"], h["kind"], h["th"],
+                          h["tw"], h["N"], h["M"], h["in_ch"], h["spatial_params"], h["batch"], len(blobs))
+        head += _SEGS.pack(K) + _SEGS.pack(0) + _MASK.pack(v, coded)
+        return b"".join([head, _LEN.pack(len(mask)), mask] + [_LEN.pack(len(b)) + bytes(b) for b in blobs])
+    if mask is not None:
+        raise ValueError("pack_image_stream: a mask block without nodata in the header")
     if h.get("max_error") is not None:
         tau = _residual.check_max_error(h["max_error"], "pack_image_stream")
         if O:
@@ -226,12 +263,12 @@ def _read_framing(src, head=None):
     keys = ("version", "numerics", "H", "W", "C", "kind", "th", "tw", "N", "M", "in_ch", "spatial_params", "batch",
             "batches")
     h = dict(zip(keys, f[1:]))
-    if h["version"] not in (VERSION, VERSION_SEG, VERSION_OV, VERSION_RES):
+    if h["version"] not in (VERSION, VERSION_SEG, VERSION_OV, VERSION_RES, VERSION_MASK):
         raise ValueError(f"DSICI stream version {h['version']}, this reader knows {VERSION}, {VERSION_SEG}, "
-                         f"{VERSION_OV} and {VERSION_RES}")
+                         f"{VERSION_OV}, {VERSION_RES} and {VERSION_MASK}")
     off, h["segments"], h["overlap"] = _HEAD.size, 1, 0
-    if h["version"] in (VERSION_SEG, VERSION_OV, VERSION_RES):
-        words = {VERSION_SEG: 1, VERSION_OV: 2, VERSION_RES: 4}[h["version"]]
+    if h["version"] in (VERSION_SEG, VERSION_OV, VERSION_RES, VERSION_MASK):
+        words = {VERSION_SEG: 1, VERSION_OV: 2, VERSION_RES: 4, VERSION_MASK: 4}[h["version"]]
         word = src.read_at(off, words * _SEGS.size)
         if len(word) < words * _SEGS.size:
             raise ValueError("truncated DSICI stream")
@@ -256,6 +293,21 @@ def _read_framing(src, head=None):
                                  f"{_residual.BANDS}")
             if h["max_error"] > 127:
                 raise ValueError(f"DSICI stream: max_error={h['max_error']} (0 .. 127)")
+        if h["version"] == VERSION_MASK:
+            overlap, h["nodata"], h["coded"] = struct.unpack_from("<3I", word, _SEGS.size)
+            if overlap != 0:
+                raise ValueError(f"DSICI stream: version 5 with overlap={overlap} (a mask over blended tiles is not "
+                                 "supported)")
+            if h["nodata"] > 255:
+                raise ValueError(f"DSICI stream: nodata={h['nodata']} (0 .. 255)")
+            if off + _LEN.size > src.size:
+                raise ValueError("truncated DSICI stream")
+            (size,) = _LEN.unpack(src.read_at(off, _LEN.size))
+            off += _LEN.size
+            if off + size > src.size:
+                raise ValueError("truncated DSICI stream")
+            h["mask_offset"], h["mask_bytes"] = off, size
+            off += size
     frames, rframes = [], []
     for k in range(h["batches"] * (2 if h["version"] == VERSION_RES else 1)):
         if off + _LEN.size > src.size:
@@ -275,12 +327,16 @@ def unpack_image_stream(stream) -> dict:
     """stream -> header fields (version, numerics, H, W, C, kind, th, tw, N, M, in_ch, spatial_params, batch,
     batches, segments: 1 for a version-1 stream, overlap: 0 for versions 1 and 2) and "blobs", the list of inner DSIC2 containers (pure Python).  ValueError on a wrong magic, a truncated
     stream or trailing bytes.  A version-4 stream also gives "max_error" and "residuals", the list of its residual
-    blocks; the dicts of versions 1 to 3 have neither key."""
+    blocks; the dicts of versions 1 to 3 have neither key.  A version-5 stream gives "nodata", "coded" (the tiles that
+    are not empty: the containers hold these, in ascending tile number), "mask_offset", "mask_bytes" and "mask", its
+    mask block (mask.py); no other version has these keys."""
     s = bytes(stream)
     h, frames, rframes = _read_framing(_Source(s))
     h["blobs"] = [s[off:off + size] for off, size in frames]
     if h["version"] == VERSION_RES:
         h["residuals"] = [s[off:off + size] for off, size in rframes]
+    if h["version"] == VERSION_MASK:
+        h["mask"] = s[h["mask_offset"]:h["mask_offset"] + h["mask_bytes"]]
     return h
 
 
@@ -541,12 +597,41 @@ def _level_grid(H, W, kind, tile, overlap, tau):
     return g, overlap
 
 
-def _compress_device_image(model, x, tile, batch, tail, segments, overlap, tau) -> bytes:
+def _compress_masked(model, x, g, C, batch, tail, segments, nodata, header) -> bytes:
+    """The version-5 stream of a uint8 image on the device: classify the tiles, code those that are not empty (a
+    batch is gathered run by run of consecutive tile numbers into slices of one tensor, so every tile's strings are
+    those of the stream without nodata), and put the mixed tiles' masks into the mask block."""
+    owned = [_owned_in_tile(g, t) for t in range(g["n"])]
+    states = _mask.tile_states(_mask.classify(x, g, C, nodata), [(b - a) * (d - c) for a, b, c, d in owned])
+    ids = [t for t, s in enumerate(states) if s != _mask.EMPTY]
+    L, blobs = _lib.load(), []
+    for first in range(0, len(ids), batch):
+        sel = ids[first:first + batch]
+        tiles = torch.empty((len(sel), g["th"], g["tw"], C), dtype=torch.uint8, device=x.device)
+        a = 0
+        while a < len(sel):
+            b = a + 1
+            while b < len(sel) and sel[b] == sel[b - 1] + 1:
+                b += 1
+            _lib.check(L.dsic_tile_gather_u8(_p(x), _p(tiles[a:b]), g["H"], g["W"], C, g["th"], g["tw"], sel[a], b - a,
+                                             _stream()), "tile_gather_u8")
+            a = b
+        blobs.append(entropy.compress_to_container(model, tiles, tail, segments=segments))
+    header["nodata"] = nodata
+    return pack_image_stream(header, blobs, mask=_mask.encode_block(x, g, C, nodata, states))
+
+
+def _compress_device_image(model, x, tile, batch, tail, segments, overlap, tau, nodata=None) -> bytes:
     """compress_image's work on one image that lies contiguous on the model's device, after the argument checks that
     do not depend on its size -> its DSICI stream."""
     kind, H, W, C = _image_kind(x, "compress_image")
     N, M, in_ch, spatial = _model_shape(model)
     g, overlap = _level_grid(H, W, kind, tile, overlap, tau)
+    if nodata is not None:
+        return _compress_masked(model, x, g, C, batch, tail, segments, nodata,
+                                {"numerics": entropy.numerics_tag(), "H": H, "W": W, "C": C, "kind": kind,
+                                 "th": g["th"], "tw": g["tw"], "N": N, "M": M, "in_ch": in_ch,
+                                 "spatial_params": spatial, "batch": batch, "segments": segments, "overlap": 0})
     blobs, residuals = [], None if tau is None else []
     for first in range(0, g["n"], batch):
         n = min(batch, g["n"] - first)
@@ -569,7 +654,7 @@ def _compress_device_image(model, x, tile, batch, tail, segments, overlap, tau) 
 
 @torch.no_grad()
 def compress_image(model, img, tile=256, batch=64, tail=10, segments=1, overlap=0, max_error=None,
-                   overviews=0) -> bytes:
+                   overviews=0, nodata=None) -> bytes:
     """img: uint8 [H,W,C] or float32 [C,H,W] in [0,1], on the CPU or the GPU -> one DSICI stream.  The image is
     uploaded once; each batch of `batch` tiles is gathered on the device (reflect padding included) and becomes one
     DSIC2 container.  segments = K > 1 (1, 2, 4, 8 or 16, dividing M): every tile's y string is K independent strings
@@ -587,10 +672,27 @@ def compress_image(model, img, tile=256, batch=64, tail=10, segments=1, overlap=
     tiles are too small for the overlap, is a ValueError before anything is coded.  max_error applies to level 0
     only, which is then the version-4 stream of the call without overviews; the overview levels are the lossy
     streams: an overview is a preview, and a residual layer there would add bytes to bound an error against an image
-    the caller never supplied.  0 writes today's streams."""
+    the caller never supplied.  0 writes today's streams.
+    nodata = v (an integer 0 .. 255; uint8 images): a pixel whose C channels all equal v is nodata, and the stream
+    (version 5) keeps that mask exactly (mask.py).  Tiles whose owned pixels inside the image are all nodata are
+    neither gathered, coded nor decoded; the other tiles' strings are byte for byte those of the stream without
+    nodata, and a tile that holds both kinds of pixel carries its mask beside them.  The decoders return v on all
+    channels (v / 255.0f for out="f32") at every nodata pixel of img, and at every other pixel the bits the stream
+    without nodata decodes to.  Not promised: a valid pixel may happen to decode to (v, ..., v), as it can today.
+    A float32 image, overlap > 0, max_error and overviews > 0 are refused with nodata: each would need a masked
+    variant of its own (predictor, blend, halving over valid pixels only).  None writes today's streams."""
     dev = next(model.parameters()).device
     tau = None if max_error is None else _residual.check_max_error(max_error, "compress_image")
     kind, H, W, C = _image_kind(img, "compress_image")
+    if nodata is not None:
+        nodata = _mask.check_nodata(nodata, "compress_image")
+        if kind != KIND_U8_HWC:
+            raise ValueError("compress_image: nodata compares integer pixel values; pass the image as uint8 [H,W,C], "
+                             "not float32")
+        for name, on in (("overlap > 0", overlap != 0), ("max_error", tau is not None),
+                         ("overviews > 0", overviews != 0)):
+            if on:
+                raise ValueError(f"compress_image: nodata together with {name} is not supported")
     N, M, in_ch, spatial = _model_shape(model)
     segments = entropy.check_segments(segments, M, "compress_image")
     if C != in_ch:
@@ -606,7 +708,7 @@ def compress_image(model, img, tile=256, batch=64, tail=10, segments=1, overlap=
             raise ValueError(f"{e} (overview level {level}, {h}x{w})" if level else str(e)) from None
     x = img.to(dev).contiguous()
     if len(shapes) == 1:
-        return _compress_device_image(model, x, tile, batch, tail, segments, overlap, tau)
+        return _compress_device_image(model, x, tile, batch, tail, segments, overlap, tau, nodata)
     return pack_pyramid_stream([_compress_device_image(model, lv, tile, batch, tail, segments, overlap,
                                                        tau if level == 0 else None)
                                 for level, lv in enumerate(build_overviews(x, overviews))])
@@ -640,8 +742,10 @@ def _stream_grid(h):
     if th % 16 or tw % 16 or th < 32 or tw < 32 or th > _ceil16(H) or tw > _ceil16(W):
         raise ValueError(f"DSICI stream: tile {th}x{tw} does not fit a {H}x{W} image")
     g = _grid(H, W, th, tw, _check_overlap(h.get("overlap", 0), th, tw, "DSICI stream"))
-    if h["batches"] != -(-g["n"] // h["batch"]):
-        raise ValueError(f"DSICI stream: {h['batches']} batches for {g['n']} tiles in batches of {h['batch']}")
+    coded = h.get("coded", g["n"])
+    if coded > g["n"] or h["batches"] != -(-coded // h["batch"]):
+        raise ValueError(f"DSICI stream: {h['batches']} batches for {coded} of {g['n']} tiles in batches of "
+                         f"{h['batch']}")
     return g
 
 
@@ -666,6 +770,15 @@ def _index_of(src, head=None):
     ix, frames, rframes = _read_framing(src, head)
     g = _stream_grid(ix)
     tiles, containers = [], []
+    ids = None                                 # version 5: the grid numbers of the coded tiles, ascending
+    if ix["version"] == VERSION_MASK:
+        states, mrecs = _mask.read_block_head(src.read_at, ix["mask_offset"], ix["mask_bytes"], g["n"], ix["th"],
+                                              ix["tw"], ix["nodata"])
+        ids = [t for t, s in enumerate(states) if s != _mask.EMPTY]
+        if len(ids) != ix["coded"]:
+            raise ValueError(f"DSICI stream: the head says {ix['coded']} coded tiles, the mask block's states "
+                             f"{len(ids)}")
+    n_coded = g["n"] if ids is None else len(ids)
     for k, (off, size) in enumerate(frames):
         tag, shape_y, shape_z, images, segs, seg = entropy.read_container_segments(src.read_at, off, size)
         if segs != ix["segments"]:
@@ -675,7 +788,7 @@ def _index_of(src, head=None):
             raise ValueError(f"DSICI stream: batch {k} carries numerics tag {tag:#x}, the stream's is "
                              f"{ix['numerics']:#x}")
         first = k * ix["batch"]
-        _check_batch_shape(k, shape_y, min(ix["batch"], g["n"] - first), ix["th"], ix["tw"])
+        _check_batch_shape(k, shape_y, min(ix["batch"], n_coded - first), ix["th"], ix["tw"])
         if (shape_y[1], shape_z[1]) != (ix["M"], ix["N"]):
             raise ValueError(f"DSICI stream: batch {k} holds latents of {shape_y[1]} and {shape_z[1]} channels, the "
                              f"header says {ix['M']} and {ix['N']}")
@@ -687,12 +800,22 @@ def _index_of(src, head=None):
                           "z_off": z_off, "z_len": z_len, "y_off": y_off, "y_len": y_len, "y_segs": seg[b]})
         containers.append({"offset": off, "bytes": size, "first": first, "tiles": len(images), "shape_y": shape_y,
                            "shape_z": shape_z})
+        if ids is not None:
+            containers[-1]["ids"] = ids[first:first + len(images)]
         if rframes:
             recs = _residual.read_block_head(src.read_at, rframes[k][0], rframes[k][1], len(images), ix["C"],
                                              ix["th"], ix["tw"], ix["max_error"])
             for tile, rec in zip(tiles[first:], recs):
                 tile.update(rec)
             containers[-1].update(r_offset=rframes[k][0], r_bytes=rframes[k][1])
+    if ids is not None:                        # the coded tiles' records, spread over the grid
+        coded, tiles = dict(zip(ids, tiles)), []
+        for t, state in enumerate(states):
+            rec = coded.get(t) or {"k": None, "b": None, "min_y": 0, "max_y": 0, "min_z": 0, "max_z": 0, "z_off": 0,
+                                   "z_len": 0, "y_off": 0, "y_len": 0, "y_segs": [0] * ix["segments"]}
+            rec["state"] = state
+            rec.update(mrecs.get(t, {}))
+            tiles.append(rec)
     ix.update(grid=g, tiles=tiles, containers=containers, stream_bytes=src.size, index_bytes=src.bytes_read)
     return ix
 
@@ -713,6 +836,10 @@ def stream_index(src, level=None) -> dict:
     C x r_L table entries, then 16 strings), r_smin, r_L (the residual's support) and r_segs (the 16 string lengths);
     per batch r_offset, r_bytes (the block).  Of a residual block the 30-byte head, the 12-byte records and the 64
     bytes of segment lengths per tile are read.
+    and for a version-5 stream (only then) nodata, coded, mask_offset, mask_bytes (the mask block); per tile state (0
+    empty, 1 full, 2 mixed), for an empty tile k = b = None and zero lengths, for a mixed tile m_off, m_len, m_mode (its
+    mask payload, which tile_spans includes); per container ids, the grid numbers of its tiles.  Of the mask block the
+    26-byte head, the state bytes and the 12-byte records are read.
       stream_bytes, index_bytes (what this call read).
     ValueError as unpack_image_stream, entropy.unpack_container and decompress_image raise it: wrong magic or version,
     DSIC1 container, truncated stream or container, trailing bytes, batches that do not match the grid, latents that
@@ -726,12 +853,14 @@ def stream_index(src, level=None) -> dict:
     for a level the stream does not hold, and for a level other than 0 of a DSICI stream."""
     _, ix, base, levels = _open_level(src, level)
     if levels is not None:
+        if "mask_offset" in ix:
+            ix["mask_offset"] += base
         for c in ix["containers"]:
             c["offset"] += base
             if "r_offset" in c:
                 c["r_offset"] += base
         for t in ix["tiles"]:
-            for key in ("z_off", "y_off", "r_off"):
+            for key in ("z_off", "y_off", "r_off", "m_off"):
                 if key in t:
                     t[key] += base
         ix.update(stream_bytes=levels[-1]["offset"] + levels[-1]["length"])
@@ -757,10 +886,10 @@ def window_tiles(index_or_grid, y0, x0, h, w) -> list:
     return [i * g["nx"] + j for i in rows for j in cols]
 
 
-def tile_spans(index, tiles) -> list:
+def tile_spans(index, tiles, masks=True) -> list:
     """Byte ranges (offset, length) of the stream that hold the strings of the given tiles (in a version-4
-    stream also their residual spans): ascending, ranges that touch merged into one, empty strings dropped (pure
-    Python)."""
+    stream also their residual spans; in a version-5 stream also the mask payloads of mixed tiles, unless masks is
+    False): ascending, ranges that touch merged into one, empty strings dropped (pure Python)."""
     parts = []
     for t in tiles:
         r = index["tiles"][t]
@@ -770,6 +899,8 @@ def tile_spans(index, tiles) -> list:
             parts.append((r["y_off"], r["y_len"]))
         if r.get("r_len"):
             parts.append((r["r_off"], r["r_len"]))
+        if masks and r.get("m_len"):
+            parts.append((r["m_off"], r["m_len"]))
     parts.sort()
     spans = []
     for off, n in parts:
@@ -780,6 +911,37 @@ def tile_spans(index, tiles) -> list:
         else:
             spans.append([off, n])
     return [tuple(s) for s in spans]
+
+
+def _apply_mask(source, ix, tiles, img, kind, window) -> int:
+    """The nodata pixels of a window of a version-5 stream, after its coded tiles have been stitched: the payloads of
+    the window's mixed tiles are read, checked (mask.check_payload) and uploaded in one small copy with their
+    descriptors, unpacked to m planes (dsic_mask_unpack), and one pass (dsic_mask_apply_u8 / _f32) writes nodata at the
+    set bits of the mixed tiles and over the whole owned rectangle of the empty ones; mask.MAX_TILES tiles at a time.
+    Returns the padded payload bytes uploaded."""
+    H, W, C, th, tw, v = ix["H"], ix["W"], ix["C"], ix["th"], ix["tw"], ix["nodata"]
+    masked = [t for t in tiles if ix["tiles"][t]["state"] != _mask.FULL]
+    uploaded = 0
+    for c0 in range(0, len(masked), _mask.MAX_TILES):
+        sel = masked[c0:c0 + _mask.MAX_TILES]
+        mixed = [t for t in sel if ix["tiles"][t]["state"] == _mask.MIXED]
+        slot = {t: i for i, t in enumerate(mixed)}
+        words = np.zeros(3 * len(mixed) + 2 * len(sel), dtype=np.int32)
+        parts, off = [], 0
+        for i, t in enumerate(mixed):
+            r = ix["tiles"][t]
+            parts.append(source.read_at(r["m_off"], r["m_len"]))
+            _mask.check_payload(parts[-1], r["m_mode"], th, tw)
+            words[3 * i:3 * i + 3] = (r["m_mode"], off, r["m_len"])
+            off += r["m_len"]
+        words[3 * len(mixed):] = np.array([(t, slot.get(t, -1)) for t in sel], dtype=np.int32).ravel()
+        d_blob, total, d_words = entropy._upload_padded(parts, words, img.device)
+        d_words = d_words.view(torch.int32)
+        planes = _mask.unpack_planes(d_blob, total, d_words, len(mixed), th, tw) if mixed else None
+        _mask.apply_window(planes, len(mixed), d_words[3 * len(mixed):], len(sel), v, img, kind == KIND_U8_HWC, H, W, C,
+                           th, tw, *window)
+        uploaded += entropy._padded_bytes(total) if mixed else 0
+    return uploaded
 
 
 def _decode_window(model, src, window, out, batch, stats, what, level=0):
@@ -801,13 +963,15 @@ def _decode_window(model, src, window, out, batch, stats, what, level=0):
     fn = getattr(L, "dsic_tile_stitch_window_" + suffix)
     if O:       # the window's float32 canvas, zeroed: the output itself, or a temporary that the finish turns to uint8
         canvas = img.zero_() if kind == KIND_F32_CHW else torch.zeros((C, h, w), dtype=torch.float32, device=img.device)
-    _, N, Hz, Wz = ix["containers"][0]["shape_z"]
+    v = ix.get("nodata")                       # a mask: empty tiles hold no strings, and are filled in _apply_mask
+    coded = tiles if v is None else [t for t in tiles if ix["tiles"][t]["state"] != _mask.EMPTY]
+    N, Hz, Wz = ix["containers"][0]["shape_z"][1:] if ix["containers"] else (ix["N"], 0, 0)
     uploaded = decode_batches = 0
-    for first in range(0, len(tiles), batch):
-        sel = tiles[first:first + batch]
+    for first in range(0, len(coded), batch):
+        sel = coded[first:first + batch]
         n = len(sel)
         # the upload is the tiles' spans back to back: a string at stream offset o lies where its span does
-        spans = tile_spans(ix, sel)
+        spans = tile_spans(ix, sel, masks=False)           # the mask payloads travel with _apply_mask
         starts, base = [off for off, _ in spans], [0]
         for _, length in spans:
             base.append(base[-1] + length)
@@ -846,6 +1010,8 @@ def _decode_window(model, src, window, out, batch, stats, what, level=0):
                        "tile_stitch_window_" + suffix)
         uploaded += nbytes
         decode_batches += 1
+    if v is not None:
+        uploaded += _apply_mask(source, ix, tiles, img, kind, (y0, x0, h, w))
     if O and kind == KIND_F32_CHW:
         _lib.check(L.dsic_tile_blend_finish_f32(_p(canvas), C, h, w, _stream()), "tile_blend_finish_f32")
     elif O:

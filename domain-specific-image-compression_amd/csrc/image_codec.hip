@@ -14,26 +14,11 @@
 // tile's weight ramps up as (2k+1)/(2O), over [a(i+1), a(i+1) + O) it ramps down as (2(O-1-k)+1)/(2O), elsewhere in
 // the support it is 1: at every position the weights of at most two tiles per axis sum to 1.  O = 0 is the grid above.
 #include "byte_movers.h"
+#include "tile_grid.h"
 
 namespace dsic {
 
 constexpr int kTileRows = 16;  // rows of one tile per workgroup (th, tw are multiples of 16)
-
-struct Grid {
-  int H, W, Hp, Wp, th, tw, ny, nx;
-  int O, sy, sx;  // overlap and the strides th - O, tw - O (th, tw on an axis of one tile)
-  __host__ __device__ int oy(int i) const { return min(i * sy, Hp - th); }
-  __host__ __device__ int ox(int j) const { return min(j * sx, Wp - tw); }
-};
-
-static Grid make_grid(int H, int W, int th, int tw, int O = 0) {
-  Grid g;
-  g.H = H, g.W = W, g.th = th, g.tw = tw, g.O = O;
-  g.Hp = round_up(H, 16), g.Wp = round_up(W, 16);
-  g.sy = g.Hp <= th ? th : th - O, g.sx = g.Wp <= tw ? tw : tw - O;
-  g.ny = g.Hp <= th ? 1 : ceil_div(g.Hp - O, g.sy), g.nx = g.Wp <= tw ? 1 : ceil_div(g.Wp - O, g.sx);
-  return g;
-}
 
 // reflect without repeating the edge (layout.hip reflect_pad_br_kernel); p < 2H-1 by the padding precondition
 __device__ __forceinline__ int reflect(int p, int n) { return p < n ? p : 2 * (n - 1) - p; }
@@ -92,22 +77,6 @@ __global__ __launch_bounds__(256) void gather_f32_kernel(const float* __restrict
 }
 
 // ---- tile stitch ------------------------------------------------------------------------------------------
-
-// the owned part of tile t in image coordinates: rows [y0,y1), columns [x0,x1); (oy, ox) its origin
-struct Owned {
-  int y0, y1, x0, x1, oy, ox;
-};
-__device__ __forceinline__ Owned owned(const Grid& g, int t) {
-  const int i = t / g.nx, j = t % g.nx;
-  return {i * g.th, min(min((i + 1) * g.th, g.Hp), g.H), j * g.tw, min(min((j + 1) * g.tw, g.Wp), g.W), g.oy(i),
-          g.ox(j)};
-}
-
-// What a stitch call writes to: the window rows [y0,y1) x columns [x0,x1) of the image, stored as an image of its
-// own of (y1-y0) x (x1-x0) pixels.  The whole-image calls pass {0, H, 0, W}.
-struct Clip {
-  int y0, y1, x0, x1;
-};
 
 // The part of tile t that a stitch call writes: owned(t) cut to the window.  ids == nullptr: the tiles of the call
 // are first, first+1, ...; otherwise tile blockIdx.y is ids[blockIdx.y], and a number outside the grid owns nothing.
@@ -495,14 +464,6 @@ __global__ __launch_bounds__(256) void scatter_select_kernel(const uint8_t* __re
   else if (n > blob_bytes - off) n = blob_bytes - off;
   if (blockIdx.x == 0 && threadIdx.x == 0) lengths[s] = (int)n;
   copy_bytes((which ? ybuf : zbuf) + (size_t)b * stride, blob + off, n, blockIdx.x, gridDim.x);
-}
-
-static const char* grid_error(int H, int W, int th, int tw) {
-  if (H <= 0 || W <= 0) return "empty image";
-  if (th < 32 || tw < 32 || th % 16 || tw % 16) return "tile sides must be multiples of 16, at least 32";
-  if (round_up(H, 16) - H >= H || round_up(W, 16) - W >= W) return "padding must be smaller than the image";
-  if (th > round_up(H, 16) || tw > round_up(W, 16)) return "tile larger than the padded image";
-  return nullptr;
 }
 
 static bool overlap_ok(int th, int tw, int O) { return O >= 0 && O % 16 == 0 && 2 * O <= (th < tw ? th : tw); }

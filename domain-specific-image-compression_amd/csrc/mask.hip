@@ -1,0 +1,468 @@
+// Nodata masks of the whole-image codec (codec.compress_image with nodata = v, stream version 5).  A pixel of a uint8
+// HWC image is nodata iff all its C channels equal v.  Per tile, over the pixels it owns inside H x W (tile_grid.h
+// owned()), the mask m is a bit plane in tile coordinates: th*tw bits, row-major, bit y*tw + x in byte (y*tw + x) / 8,
+// LSB first; 1 iff the pixel is owned, inside the image and nodata.  What travels is the vertical delta plane
+// d[y][x] = m[y][x] ^ m[y-1][x] (m[-1] = 0), raw (mode 0, th*tw/8 bytes) or as the ascending positions of its set
+// bits (mode 1; u16 if th*tw <= 65536, else u32), whichever is shorter, raw on a tie.
+//
+// Byte movers as image_codec.hip's.  The image is read 16 pixels per lane, C 16-byte loads (load16_any: the image
+// is aligned as it happens to be) that become one 16-bit half of a plane dword; a run of 16 pixels that the tile does
+// not own whole goes pixel by pixel.  tw is a multiple of 16, not of 32, so a plane row is a whole number of halves and
+// a dword may hold the end of one row and the start of the next.
+//
+//   classify      image -> per tile the count of nodata pixels among its owned pixels: one read of the image
+//   delta planes  image, tile ids -> d planes as dwords [th*tw/32] and their popcounts: the tiles' pixels read twice
+//                 (a half needs its row and the row above), the second time from cache
+//   pack          planes, popcounts -> records (tile, mode, bytes) and the payloads back to back in one buffer;
+//                 mode 1 is an ordered compaction (workgroup scan over the dwords' popcounts)
+//   unpack        payloads, (mode, offset, bytes) per tile -> m planes: every dword gathers the positions of its 32
+//                 bits from the ascending list by bisection (no atomics, the result does not depend on any order), or
+//                 copies its raw bytes; then the XOR prefix down every 16-bit column strip
+//   apply         m planes, (tile, plane or -1 = all set) per tile -> v (uint8 HWC) or v / 255.0f (float32 CHW) at the
+//                 tile's owned pixels inside the window whose bit is set; nothing else is written
+#include <limits.h>
+
+#include "byte_movers.h"
+#include "tile_grid.h"
+
+namespace dsic {
+
+constexpr int kMaskRows = 16;  // rows of one tile per workgroup of classify and apply
+
+// bit e = pixel e of the 16 at p is nodata; all 16 C bytes are read
+template <int C>
+__device__ __forceinline__ uint32_t nodata16_full(const uint8_t* __restrict__ p, uint32_t v) {
+  uint32_t m = 0;
+  if (C == 4) {
+    const uint32_t vv = v * 0x01010101u;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      const uint4 q = load16_any(p + 16 * k);
+      m |= ((uint32_t)(q.x == vv) | ((uint32_t)(q.y == vv) << 1) | ((uint32_t)(q.z == vv) << 2) |
+            ((uint32_t)(q.w == vv) << 3))
+           << (4 * k);
+    }
+  } else {
+    const uint4 q[3] = {load16_any(p), load16_any(p + 16), load16_any(p + 32)};
+    uint8_t b[48];
+    __builtin_memcpy(b, q, 48);
+#pragma unroll
+    for (int e = 0; e < 16; ++e)
+      m |= (uint32_t)(b[3 * e] == v && b[3 * e + 1] == v && b[3 * e + 2] == v) << e;
+  }
+  return m;
+}
+
+// The 16 mask bits of row y, columns [16 s, 16 s + 16) of the tile that owns `o`, in tile coordinates: a bit is set
+// iff the pixel is owned, inside H x W (o is cut to it) and nodata.
+template <int C>
+__device__ __forceinline__ uint32_t mask16(const uint8_t* __restrict__ img, int W, const Owned& o, uint32_t v, int y,
+                                           int s) {
+  const int iy = o.oy + y, ix0 = o.ox + 16 * s;
+  if (iy < o.y0 || iy >= o.y1) return 0;
+  const int lo = max(o.x0, ix0), hi = min(o.x1, ix0 + 16);
+  if (lo >= hi) return 0;
+  const uint8_t* row = img + ((int64_t)iy * W + ix0) * C;
+  if (hi - lo == 16) return nodata16_full<C>(row, v);
+  uint32_t m = 0;
+  for (int x = lo; x < hi; ++x) {
+    const uint8_t* p = row + (x - ix0) * C;
+    bool e = true;
+#pragma unroll
+    for (int c = 0; c < C; ++c) e = e && p[c] == v;
+    m |= (uint32_t)e << (x - ix0);
+  }
+  return m;
+}
+
+__device__ __forceinline__ int wave_sum(int v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
+  return v;  // in lane 0
+}
+
+// blockIdx.y = tile first + blockIdx.y, blockIdx.x = a block of kMaskRows of its rows; counts[blockIdx.y] += nodata
+template <int C>
+__global__ __launch_bounds__(256) void mask_classify_kernel(const uint8_t* __restrict__ img, Grid g, uint32_t v,
+                                                            int first, int* __restrict__ counts) {
+  const Owned o = owned(g, first + blockIdx.y);
+  const int S = g.tw >> 4, r0 = blockIdx.x * kMaskRows;
+  int cnt = 0;
+  for (int i = threadIdx.x; i < kMaskRows * S; i += blockDim.x) {
+    const int r = i / S;
+    cnt += __popc(mask16<C>(img, g.W, o, v, r0 + r, i - r * S));
+  }
+  cnt = wave_sum(cnt);
+  if ((threadIdx.x & 63) == 0 && cnt) atomicAdd(counts + blockIdx.y, cnt);
+}
+
+// blockIdx.y = tile ids[blockIdx.y]; a thread makes one dword of its d plane: halves 2w and 2w + 1, half h = row
+// h / S, strip h % S (S = tw / 16)
+template <int C>
+__global__ __launch_bounds__(256) void mask_delta_kernel(const uint8_t* __restrict__ img, Grid g, uint32_t v,
+                                                         const int* __restrict__ ids, uint32_t* __restrict__ planes,
+                                                         int* __restrict__ pop) {
+  const int t = ids[blockIdx.y];
+  const int D = (g.th * g.tw) >> 5, S = g.tw >> 4;
+  const int w = blockIdx.x * blockDim.x + threadIdx.x;
+  uint32_t d = 0;
+  if (w < D && t >= 0 && t < g.ny * g.nx) {
+    const Owned o = owned(g, t);
+#pragma unroll
+    for (int k = 0; k < 2; ++k) {
+      const int h = 2 * w + k, y = h / S, s = h - y * S;
+      const uint32_t m = mask16<C>(img, g.W, o, v, y, s) ^ (y ? mask16<C>(img, g.W, o, v, y - 1, s) : 0u);
+      d |= m << (16 * k);
+    }
+  }
+  if (w < D) planes[(size_t)blockIdx.y * D + w] = d;
+  const int cnt = wave_sum(__popc(d));
+  if ((threadIdx.x & 63) == 0 && cnt) atomicAdd(pop + blockIdx.y, cnt);
+}
+
+// ---- pack: records and payloads of the mixed tiles in one buffer ----------------------------------------------------
+// out: n x (tile u32, mode u32, bytes u32) | the n payloads back to back.  ws[0] = bytes of all that, ws[1] = 0,
+// ws[2 + t] = offset of payload t behind the records.
+constexpr int kMaskRec = 12;
+__host__ __device__ inline int pos_bytes(int64_t bits) { return bits <= 65536 ? 2 : 4; }
+__device__ __forceinline__ int64_t list_bytes(const int* pop, int t, int64_t bits) {
+  const int64_t p = pop[t] < 0 ? 0 : (pop[t] > bits ? bits : pop[t]);
+  return p * pos_bytes(bits);
+}
+__device__ __forceinline__ int64_t payload_bytes(const int* pop, int t, int64_t bits, int* mode) {
+  const int64_t raw = bits >> 3, list = list_bytes(pop, t, bits);
+  *mode = list < raw;
+  return *mode ? list : raw;
+}
+
+__global__ __launch_bounds__(256) void mask_pack_head_kernel(const int* __restrict__ pop, const int* __restrict__ ids,
+                                                             int n, int64_t bits, long long* __restrict__ ws,
+                                                             uint8_t* __restrict__ out) {
+  __shared__ long long lds4[4];
+  const int tid = threadIdx.x;
+  for (int i = tid; i < kMaskRec * n; i += blockDim.x) {
+    const int t = i / kMaskRec, k = i - t * kMaskRec;
+    int mode;
+    const int64_t bytes = payload_bytes(pop, t, bits, &mode);
+    const uint32_t f[3] = {(uint32_t)ids[t], (uint32_t)mode, (uint32_t)bytes};
+    put_u32(out + i, k & 3, f[k >> 2]);
+  }
+  long long carry = 0;
+  for (int t0 = 0; t0 < n; t0 += blockDim.x) {
+    const int t = t0 + tid;
+    int mode;
+    const long long v = t < n ? payload_bytes(pop, t, bits, &mode) : 0;
+    long long tot;
+    const long long ex = block_exclusive_scan(v, lds4, &tot);
+    if (t < n) ws[2 + t] = carry + ex;
+    carry += tot;
+  }
+  if (tid == 0) ws[0] = (long long)kMaskRec * n + carry, ws[1] = 0;
+}
+
+// blockIdx.y = tile, blockIdx.x = slice of a raw plane; a list is written by slice 0 alone, in order: the scan gives
+// every dword the rank of its first set bit
+__global__ __launch_bounds__(256) void mask_pack_payload_kernel(const uint32_t* __restrict__ planes,
+                                                                const int* __restrict__ pop, int n, int64_t bits,
+                                                                const long long* __restrict__ ws,
+                                                                uint8_t* __restrict__ out) {
+  __shared__ long long lds4[4];
+  const int t = blockIdx.y, D = (int)(bits >> 5);
+  int mode;
+  const int64_t bytes = payload_bytes(pop, t, bits, &mode);
+  const uint32_t* plane = planes + (size_t)t * D;
+  uint8_t* dst = out + (int64_t)kMaskRec * n + ws[2 + t];
+  if (!mode) {
+    copy_bytes(dst, (const uint8_t*)plane, bytes, blockIdx.x, gridDim.x);
+    return;
+  }
+  if (blockIdx.x) return;
+  const int ps = pos_bytes(bits);
+  const long long count = bytes / ps;
+  long long carry = 0;
+  for (int w0 = 0; w0 < D; w0 += blockDim.x) {
+    const int w = w0 + threadIdx.x;
+    uint32_t v = w < D ? plane[w] : 0u;
+    long long tot;
+    long long idx = carry + block_exclusive_scan(__popc(v), lds4, &tot);
+    carry += tot;
+    for (; v && idx < count; v &= v - 1, ++idx) {  // payload offsets are multiples of the position size
+      const uint32_t pos = 32u * (uint32_t)w + (uint32_t)(__ffs((int)v) - 1);
+      if (ps == 2) *(uint16_t*)(dst + 2 * idx) = (uint16_t)pos;
+      else *(uint32_t*)(dst + 4 * idx) = pos;
+    }
+  }
+}
+
+// ---- unpack: payloads -> m planes ---------------------------------------------------------------------------------
+__device__ __forceinline__ uint32_t get_pos(const uint8_t* p, int ps) {
+  uint32_t v = (uint32_t)p[0] | ((uint32_t)p[1] << 8);
+  if (ps == 4) v |= ((uint32_t)p[2] << 16) | ((uint32_t)p[3] << 24);
+  return v;
+}
+
+// One workgroup per tile.  desc [n][3] = (mode, offset of the payload in blob, its bytes).  A payload that cannot be
+// a tile's (the host has checked: a bad mode or length, or one that leaves the blob) gives the empty plane, and a
+// position outside the plane sets nothing.
+__global__ __launch_bounds__(256) void mask_unpack_kernel(const uint8_t* __restrict__ blob, int64_t blob_bytes,
+                                                          const int* __restrict__ desc, int th, int tw,
+                                                          uint32_t* __restrict__ planes) {
+  __shared__ uint16_t part[256];
+  const int t = blockIdx.x, tid = threadIdx.x;
+  const int64_t bits = (int64_t)th * tw, raw = bits >> 3;
+  const int D = (int)(bits >> 5), S = tw >> 4, ps = pos_bytes(bits);
+  const int mode = desc[3 * t];
+  const int64_t off = desc[3 * t + 1], bytes = desc[3 * t + 2];
+  const bool in_blob = off >= 0 && bytes >= 0 && off + bytes <= blob_bytes;
+  uint32_t* plane = planes + (size_t)t * D;
+  const uint8_t* src = blob + off;
+  if (in_blob && mode == 0 && bytes == raw) {
+    copy_bytes((uint8_t*)plane, src, raw, 0, 1);
+  } else {
+    const int count = in_blob && mode == 1 && bytes % ps == 0 && bytes < raw ? (int)(bytes / ps) : 0;
+    for (int w = tid; w < D; w += blockDim.x) {
+      int lo = 0, hi = count;  // the first position that is not below 32 w
+      while (lo < hi) {
+        const int mid = (lo + hi) >> 1;
+        if (get_pos(src + (int64_t)mid * ps, ps) < 32u * (uint32_t)w) lo = mid + 1;
+        else hi = mid;
+      }
+      uint32_t v = 0;
+      for (int k = 0; k < 32 && lo < count; ++k, ++lo) {
+        const uint32_t pos = get_pos(src + (int64_t)lo * ps, ps);
+        if (pos >= 32u * (uint32_t)w + 32u) break;
+        v |= 1u << (pos & 31);
+      }
+      plane[w] = v;
+    }
+  }
+  __syncthreads();
+  // m[y] = m[y-1] ^ d[y] down every strip of 16 columns: thread (r, s) folds the rows of group r of strip s, the
+  // groups' folds meet in LDS, and the second pass writes m over d
+  uint16_t* h = (uint16_t*)plane;
+  const int G = min(256 / S, th), R = (th + G - 1) / G;
+  const int s = tid % S, r = tid / S;
+  const int ya = min(r * R, th), yb = r < G ? min(ya + R, th) : ya;
+  uint16_t x = 0;
+  for (int y = ya; y < yb; ++y) x ^= h[(size_t)y * S + s];
+  part[tid] = x;
+  __syncthreads();
+  uint16_t acc = 0;
+  for (int k = 0; k < r && k < G; ++k) acc ^= part[k * S + s];
+  for (int y = ya; y < yb; ++y) {
+    acc ^= h[(size_t)y * S + s];
+    h[(size_t)y * S + s] = acc;
+  }
+}
+
+// ---- apply: v at the pixels whose bit is set ------------------------------------------------------------------------
+// desc [n][2] = (tile, plane index or -1 for "all set").  The part of tile t the call writes is owned(t) cut to the
+// window, as stitch_rect of image_codec.hip has it: a number outside the grid owns nothing.
+__device__ __forceinline__ bool apply_rect(const Grid& g, const int* desc, int n_planes, const Clip& w, Owned* o,
+                                           int* plane) {
+  const int t = desc[2 * blockIdx.y];
+  *plane = desc[2 * blockIdx.y + 1];
+  if (t < 0 || t >= g.ny * g.nx || *plane >= n_planes) return false;
+  *o = owned(g, t);
+  o->y0 = max(o->y0, w.y0), o->y1 = min(o->y1, w.y1);
+  o->x0 = max(o->x0, w.x0), o->x1 = min(o->x1, w.x1);
+  return o->y0 < o->y1 && o->x0 < o->x1;
+}
+
+__device__ __forceinline__ bool mask_bit(const uint32_t* plane, int idx) {
+  return !plane || ((plane[idx >> 5] >> (idx & 31)) & 1u);
+}
+
+__global__ __launch_bounds__(256) void mask_apply_u8_kernel(const uint32_t* __restrict__ planes,
+                                                            const int* __restrict__ desc, int n_planes, Grid g, int C,
+                                                            Clip w, uint8_t* __restrict__ img, uint32_t v) {
+  Owned o;
+  int pi;
+  if (!apply_rect(g, desc, n_planes, w, &o, &pi)) return;
+  const int ya = o.y0 + blockIdx.x * kMaskRows;
+  const int rows = min(kMaskRows, o.y1 - ya);
+  if (rows <= 0) return;
+  const uint32_t* plane = pi < 0 ? nullptr : planes + (size_t)pi * ((g.th * g.tw) >> 5);
+  const int wW = w.x1 - w.x0;
+  const int seg = (o.x1 - o.x0) * C;
+  const int cpr = seg / 16 + 2;  // 16-byte chunks a row segment can touch
+  const uint32_t vv = v * 0x01010101u;
+  for (int i = threadIdx.x; i < rows * cpr; i += blockDim.x) {
+    const int r = i / cpr, k = i - r * cpr;
+    const int y = ya + r;
+    const int64_t b0 = ((int64_t)(y - w.y0) * wW + (o.x0 - w.x0)) * C, b1 = b0 + seg;
+    const int64_t q0 = ((b0 >> 4) + k) << 4;
+    if (q0 >= b1) continue;
+    const int64_t lo = max(q0, b0), hi = min(q0 + 16, b1);
+    int px = (int)((lo - b0) / C), c = (int)((lo - b0) - (int64_t)px * C);
+    px += o.x0 - o.ox;  // column within the tile
+    const int row_bit = (y - o.oy) * g.tw;
+    uint32_t sel = 0;
+#pragma unroll
+    for (int e = 0; e < 16; ++e) {
+      if (q0 + e >= lo && q0 + e < hi) {
+        sel |= (uint32_t)mask_bit(plane, row_bit + px) << e;
+        if (++c == C) c = 0, ++px;
+      }
+    }
+    if (sel == 0xFFFFu) {
+      *(uint4*)(img + q0) = make_uint4(vv, vv, vv, vv);
+    } else {
+#pragma unroll
+      for (int e = 0; e < 16; ++e)
+        if ((sel >> e) & 1u) img[q0 + e] = (uint8_t)v;
+    }
+  }
+}
+
+// float32 CHW window; blockIdx.z = channel
+__global__ __launch_bounds__(256) void mask_apply_f32_kernel(const uint32_t* __restrict__ planes,
+                                                             const int* __restrict__ desc, int n_planes, Grid g,
+                                                             Clip w, float* __restrict__ img, float fv) {
+  Owned o;
+  int pi;
+  if (!apply_rect(g, desc, n_planes, w, &o, &pi)) return;
+  const int ya = o.y0 + blockIdx.x * kMaskRows;
+  const int rows = min(kMaskRows, o.y1 - ya);
+  if (rows <= 0) return;
+  const uint32_t* plane = pi < 0 ? nullptr : planes + (size_t)pi * ((g.th * g.tw) >> 5);
+  const int wW = w.x1 - w.x0;
+  const int64_t cplane = (int64_t)blockIdx.z * (w.y1 - w.y0) * wW;
+  const int cpr = (o.x1 - o.x0) / 4 + 2;  // 4-float chunks a row segment can touch
+  for (int i = threadIdx.x; i < rows * cpr; i += blockDim.x) {
+    const int r = i / cpr, k = i - r * cpr;
+    const int y = ya + r;
+    const int64_t e0 = cplane + (int64_t)(y - w.y0) * wW + (o.x0 - w.x0), e1 = e0 + (o.x1 - o.x0);
+    const int64_t q0 = ((e0 >> 2) + k) << 2;
+    if (q0 >= e1) continue;
+    const int64_t lo = max(q0, e0), hi = min(q0 + 4, e1);
+    const int bit0 = (y - o.oy) * g.tw + (o.x0 - o.ox) + (int)(lo - e0);
+    uint32_t sel = 0;
+    for (int64_t e = lo; e < hi; ++e) sel |= (uint32_t)mask_bit(plane, bit0 + (int)(e - lo)) << (int)(e - q0);
+    if (sel == 0xFu) {
+      *(float4*)(img + q0) = make_float4(fv, fv, fv, fv);
+    } else {
+#pragma unroll
+      for (int e = 0; e < 4; ++e)
+        if ((sel >> e) & 1u) img[q0 + e] = fv;
+    }
+  }
+}
+
+}  // namespace dsic
+
+using namespace dsic;
+
+#define DSIC_MASK_IMAGE(what)                                                                          \
+  DSIC_REQUIRE(C == 3 || C == 4, what ": C=%d must be 3 or 4", C);                                     \
+  DSIC_REQUIRE(nodata >= 0 && nodata <= 255, what ": nodata=%d must be in 0..255", nodata);            \
+  const char* ge = grid_error(H, W, th, tw);                                                           \
+  DSIC_REQUIRE(!ge, what ": %s (H=%d W=%d th=%d tw=%d)", ge ? ge : "", H, W, th, tw);                  \
+  DSIC_REQUIRE((int64_t)th * tw <= INT_MAX / 2, what ": a tile of %dx%d has over 2^30 pixels", th, tw); \
+  const Grid g = make_grid(H, W, th, tw)
+
+extern "C" int dsic_mask_classify_u8(const uint8_t* img_hwc, int H, int W, int C, int th, int tw, int nodata,
+                                     int first_tile, int n_tiles, int* counts, void* stream) {
+  DSIC_REQUIRE(img_hwc && counts, "mask_classify_u8: null pointer");
+  DSIC_MASK_IMAGE("mask_classify_u8");
+  DSIC_REQUIRE(first_tile >= 0 && n_tiles > 0 && (int64_t)first_tile + n_tiles <= (int64_t)g.ny * g.nx,
+               "mask_classify_u8: tiles [%d, %d) outside the grid of %d", first_tile, first_tile + n_tiles,
+               g.ny * g.nx);
+  DSIC_REQUIRE(n_tiles <= 65535, "mask_classify_u8: at most 65535 tiles per call");
+  const dim3 grid(g.th / kMaskRows, n_tiles);
+  if (C == 3)
+    hipLaunchKernelGGL(mask_classify_kernel<3>, grid, dim3(256), 0, (hipStream_t)stream, img_hwc, g, (uint32_t)nodata,
+                       first_tile, counts);
+  else
+    hipLaunchKernelGGL(mask_classify_kernel<4>, grid, dim3(256), 0, (hipStream_t)stream, img_hwc, g, (uint32_t)nodata,
+                       first_tile, counts);
+  return check_launch("mask_classify_u8");
+}
+
+extern "C" int dsic_mask_delta_planes_u8(const uint8_t* img_hwc, int H, int W, int C, int th, int tw, int nodata,
+                                         const int* tile_ids, int n_tiles, uint32_t* planes, int* popcounts,
+                                         void* stream) {
+  DSIC_REQUIRE(img_hwc && tile_ids && planes && popcounts, "mask_delta_planes_u8: null pointer");
+  DSIC_MASK_IMAGE("mask_delta_planes_u8");
+  DSIC_REQUIRE(n_tiles >= 1 && n_tiles <= 65535, "mask_delta_planes_u8: n=%d tiles per call (1..65535)", n_tiles);
+  DSIC_REQUIRE(((uintptr_t)planes & 3) == 0, "mask_delta_planes_u8: planes must be 4-byte aligned");
+  const dim3 grid(ceil_div((g.th * g.tw) >> 5, 256), n_tiles);
+  if (C == 3)
+    hipLaunchKernelGGL(mask_delta_kernel<3>, grid, dim3(256), 0, (hipStream_t)stream, img_hwc, g, (uint32_t)nodata,
+                       tile_ids, planes, popcounts);
+  else
+    hipLaunchKernelGGL(mask_delta_kernel<4>, grid, dim3(256), 0, (hipStream_t)stream, img_hwc, g, (uint32_t)nodata,
+                       tile_ids, planes, popcounts);
+  return check_launch("mask_delta_planes_u8");
+}
+
+#define DSIC_MASK_TILE(what)                                                                                     \
+  DSIC_REQUIRE(th >= 32 && tw >= 32 && th % 16 == 0 && tw % 16 == 0 && tw <= 4096 &&                             \
+                   (int64_t)th * tw <= INT_MAX / 2,                                                              \
+               what ": tile %dx%d: sides must be multiples of 16 from 32, tw at most 4096, under 2^30 pixels", th, \
+               tw);                                                                                              \
+  DSIC_REQUIRE(n_tiles >= 1 && n_tiles <= 65535, what ": n=%d tiles per call (1..65535)", n_tiles)
+
+extern "C" int dsic_mask_pack(const uint32_t* planes, const int* popcounts, const int* tile_ids, int n_tiles, int th,
+                              int tw, int64_t* workspace, uint8_t* out, void* stream) {
+  DSIC_REQUIRE(planes && popcounts && tile_ids && workspace && out, "mask_pack: null pointer");
+  DSIC_MASK_TILE("mask_pack");
+  DSIC_REQUIRE((((uintptr_t)planes | (uintptr_t)out) & 3) == 0, "mask_pack: planes and out must be 4-byte aligned");
+  hipStream_t st = (hipStream_t)stream;
+  long long* ws = (long long*)workspace;
+  const int64_t bits = (int64_t)th * tw;
+  hipLaunchKernelGGL(mask_pack_head_kernel, dim3(1), dim3(256), 0, st, popcounts, tile_ids, n_tiles, bits, ws, out);
+  const int rc = check_launch("mask_pack(head)");
+  if (rc) return rc;
+  hipLaunchKernelGGL(mask_pack_payload_kernel, dim3(string_parts(bits >> 3), n_tiles), dim3(256), 0, st, planes,
+                     popcounts, n_tiles, bits, (const long long*)ws, out);
+  return check_launch("mask_pack(payloads)");
+}
+
+extern "C" int dsic_mask_unpack(const uint8_t* blob, int64_t blob_bytes, const int* desc, int n_tiles, int th, int tw,
+                                uint32_t* planes, void* stream) {
+  DSIC_REQUIRE(blob && desc && planes, "mask_unpack: null pointer");
+  DSIC_MASK_TILE("mask_unpack");
+  DSIC_REQUIRE(blob_bytes >= 0, "mask_unpack: negative size");
+  DSIC_REQUIRE(((uintptr_t)planes & 15) == 0, "mask_unpack: planes must be 16-byte aligned");
+  hipLaunchKernelGGL(mask_unpack_kernel, dim3(n_tiles), dim3(256), 0, (hipStream_t)stream, blob, blob_bytes, desc, th,
+                     tw, planes);
+  return check_launch("mask_unpack");
+}
+
+#define DSIC_MASK_WINDOW(what)                                                                                 \
+  DSIC_REQUIRE(nodata >= 0 && nodata <= 255, what ": nodata=%d must be in 0..255", nodata);                    \
+  const char* ge = grid_error(H, W, th, tw);                                                                   \
+  DSIC_REQUIRE(!ge, what ": %s (H=%d W=%d th=%d tw=%d)", ge ? ge : "", H, W, th, tw);                          \
+  DSIC_REQUIRE((int64_t)th * tw <= INT_MAX / 2, what ": a tile of %dx%d has over 2^30 pixels", th, tw);        \
+  const Grid g = make_grid(H, W, th, tw);                                                                      \
+  DSIC_REQUIRE(wy0 >= 0 && wx0 >= 0 && wh >= 1 && ww >= 1 && (int64_t)wy0 + wh <= H && (int64_t)wx0 + ww <= W, \
+               what ": window %dx%d at (%d, %d) outside the %dx%d image", wh, ww, wy0, wx0, H, W);             \
+  DSIC_REQUIRE(n_tiles >= 1 && n_tiles <= 65535, what ": n=%d tiles per call (1..65535)", n_tiles);            \
+  DSIC_REQUIRE(n_planes >= 0 && (planes || n_planes == 0), what ": %d planes at a null pointer", n_planes);    \
+  DSIC_REQUIRE(((uintptr_t)out & 15) == 0, what ": out must be 16-byte aligned");                              \
+  const Clip clip = {wy0, wy0 + wh, wx0, wx0 + ww};                                                            \
+  const dim3 grid(g.th / kMaskRows, n_tiles, 1)
+
+extern "C" int dsic_mask_apply_u8(const uint32_t* planes, int n_planes, const int* desc, int n_tiles, int nodata,
+                                  uint8_t* out, int H, int W, int C, int th, int tw, int wy0, int wx0, int wh, int ww,
+                                  void* stream) {
+  DSIC_REQUIRE(desc && out, "mask_apply_u8: null pointer");
+  DSIC_REQUIRE(C == 3 || C == 4, "mask_apply_u8: C=%d must be 3 or 4", C);
+  DSIC_MASK_WINDOW("mask_apply_u8");
+  hipLaunchKernelGGL(mask_apply_u8_kernel, grid, dim3(256), 0, (hipStream_t)stream, planes, desc, n_planes, g, C, clip,
+                     out, (uint32_t)nodata);
+  return check_launch("mask_apply_u8");
+}
+
+extern "C" int dsic_mask_apply_f32(const uint32_t* planes, int n_planes, const int* desc, int n_tiles, int nodata,
+                                   float* out, int H, int W, int C, int th, int tw, int wy0, int wx0, int wh, int ww,
+                                   void* stream) {
+  DSIC_REQUIRE(desc && out, "mask_apply_f32: null pointer");
+  DSIC_REQUIRE(C >= 1 && C <= 8, "mask_apply_f32: C=%d must be in 1..8", C);
+  DSIC_MASK_WINDOW("mask_apply_f32");
+  const float fv = (float)nodata / 255.0f;  // on the host, correctly rounded: NumPy's float32(v) / float32(255)
+  hipLaunchKernelGGL(mask_apply_f32_kernel, dim3(grid.x, grid.y, C), dim3(256), 0, (hipStream_t)stream, planes, desc,
+                     n_planes, g, clip, out, fv);
+  return check_launch("mask_apply_f32");
+}

@@ -120,6 +120,12 @@ SIGNATURES = {
     "dsic_tile_stitch_window_u8_res": (c_int, [_P, _P, c_int, _P, c_int, _P] + [c_int] * 9 + [_P]),
     "dsic_image_halve_u8": (c_int, [_P, _P, c_int, c_int, c_int, _P]),
     "dsic_image_halve_f32": (c_int, [_P, _P, c_int, c_int, c_int, _P]),
+    "dsic_mask_classify_u8": (c_int, [_P] + [c_int] * 8 + [_P, _P]),
+    "dsic_mask_delta_planes_u8": (c_int, [_P] + [c_int] * 6 + [_P, c_int, _P, _P, _P]),
+    "dsic_mask_pack": (c_int, [_P, _P, _P, c_int, c_int, c_int, _P, _P, _P]),
+    "dsic_mask_unpack": (c_int, [_P, c_int64, _P, c_int, c_int, c_int, _P, _P]),
+    "dsic_mask_apply_u8": (c_int, [_P, c_int, _P, c_int, c_int, _P] + [c_int] * 9 + [_P]),
+    "dsic_mask_apply_f32": (c_int, [_P, c_int, _P, c_int, c_int, _P] + [c_int] * 9 + [_P]),
     "dsic_stream_create_masked":(c_int, [_P, c_int, _P]),
     "dsic_stream_destroy": (c_int, [_P]),
     "dsic_range_decode": (c_int, [_P, c_int64, _P, c_int, c_int, _P, c_int, _P, c_int, c_int, c_int,

@@ -595,6 +595,49 @@ int dsic_image_halve_u8(const uint8_t* src_hwc, uint8_t* dst_hwc, int H, int W, 
 int dsic_image_halve_f32(const float* src_chw, float* dst_chw, int C, int H, int W,
                          void* stream);
 
+/* ---- nodata masks (codec.compress_image with nodata = v, 0..255; stream version 5) ----
+ * A pixel of a uint8 [H][W][C] image (C 3 or 4) is nodata iff all its C channels equal v.  Per
+ * tile of the grid (th, tw multiples of 16, no overlap) the mask m is a bit plane in tile
+ * coordinates: th*tw bits, row-major, bit y*tw + x in byte (y*tw + x) / 8, LSB first, held as
+ * uint32 [th*tw/32]; the bit is 1 iff the pixel is owned by the tile, inside H x W and nodata.
+ * The delta plane is d[y][x] = m[y][x] ^ m[y-1][x], m[-1] = 0.  A payload is d in one of two
+ * modes: 0 = the plane, th*tw/8 bytes; 1 = the positions y*tw + x of its set bits, ascending,
+ * u16 little endian if th*tw <= 65536, else u32; mode 1 iff it is strictly shorter.
+ * mask_classify_u8: counts int32 [n_tiles], to which the number of nodata pixels among the
+ *   owned pixels inside H x W of tiles first_tile .. first_tile + n_tiles - 1 is ADDED (the
+ *   caller zeroes it); n_tiles <= 65535 per call.  The image at any alignment.
+ * mask_delta_planes_u8: tile_ids int32 [n] -> planes uint32 [n][th*tw/32] = the tiles' d
+ *   planes, and popcounts int32 [n], to which their set bits are ADDED.  A number outside the
+ *   grid gives the empty plane.
+ * mask_pack: planes, popcounts, tile_ids [n] -> out = n x (tile u32, mode u32, bytes u32), then
+ *   the n payloads back to back; out holds at least n * (12 + th*tw/8) bytes, 4-byte aligned.
+ *   workspace: n + 2 int64, [0] = bytes written, [1] = 0.
+ * mask_unpack: blob (the payloads, anywhere in it and at any alignment; readable in whole
+ *   dwords) and desc int32 [n][3] = (mode, offset in blob, bytes) -> planes uint32
+ *   [n][th*tw/32] = the m planes, 16-byte aligned.  Positions must ascend (the host checks);
+ *   a payload that leaves the blob, or whose mode or length no tile can have, gives the empty
+ *   plane, and a position >= th*tw sets nothing.
+ * mask_apply_u8 / mask_apply_f32: desc int32 [n][2] = (tile, index into planes or -1 for "all
+ *   set") -> v (uint8 [wh][ww][C]) or (float)v / 255.0f (float32 [C][wh][ww]) at those pixels
+ *   of the window rows [wy0, wy0+wh) x columns [wx0, wx0+ww) that the tile owns and whose bit is
+ *   set; nothing else is written, so set bits outside a tile's owned rectangle are harmless.
+ *   A tile outside the grid, or a plane index >= n_planes, writes nothing.  out 16-byte aligned. */
+int dsic_mask_classify_u8(const uint8_t* img_hwc, int H, int W, int C, int th, int tw, int nodata,
+                          int first_tile, int n_tiles, int* counts, void* stream);
+int dsic_mask_delta_planes_u8(const uint8_t* img_hwc, int H, int W, int C, int th, int tw,
+                              int nodata, const int* tile_ids, int n, uint32_t* planes,
+                              int* popcounts, void* stream);
+int dsic_mask_pack(const uint32_t* planes, const int* popcounts, const int* tile_ids, int n,
+                   int th, int tw, int64_t* workspace, uint8_t* out, void* stream);
+int dsic_mask_unpack(const uint8_t* blob, int64_t blob_bytes, const int* desc, int n, int th,
+                     int tw, uint32_t* planes, void* stream);
+int dsic_mask_apply_u8(const uint32_t* planes, int n_planes, const int* desc, int n, int nodata,
+                       uint8_t* out, int H, int W, int C, int th, int tw, int wy0, int wx0,
+                       int wh, int ww, void* stream);
+int dsic_mask_apply_f32(const uint32_t* planes, int n_planes, const int* desc, int n, int nodata,
+                        float* out, int H, int W, int C, int th, int tw, int wy0, int wx0, int wh,
+                        int ww, void* stream);
+
 /* HIP stream limited to the CUs whose bit is set in mask_host[words] (bit i of
  * word i/32 = CU i).  Used to give the range coder its own few CUs beside the
  * conv kernels; there is no reference counterpart (the reference is

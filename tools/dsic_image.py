@@ -2,7 +2,7 @@
 an image.
 
     python tools/dsic_image.py compress   --weights CKPT.pt IN.png  OUT.dsic [--tile 256] [--batch 64] [--segments K] [--overlap O]
-                                          [--max-error T] [--overviews N]
+                                          [--max-error T] [--overviews N] [--nodata V]
     python tools/dsic_image.py decompress --weights CKPT.pt IN.dsic OUT.png [--out u8|f32] [--region Y0,X0,H,W]
                                           [--level L]
     python tools/dsic_image.py info       IN.dsic
@@ -17,6 +17,9 @@ geometry, the tile grid and the bytes of every batch from the stream's heads, wi
 coded with the same options; --max-error bounds level 0 only).  --level L decodes level L of such a stream (0 = the
 full image) from that level's bytes alone; with --region the window is in level L's own pixels.  info prints the
 levels of a DSICP stream (size, bytes, tiles), then level 0.
+--nodata V (0 .. 255, uint8 images; not with --overlap, --max-error or --overviews) keeps the mask of the pixels whose
+channels all equal V exactly (a version-5 stream): tiles that hold nothing else are not coded at all, and every such
+pixel decodes to V again.  info prints the value, the counts of empty, full and mixed tiles and the mask block's bytes.
 
 The state dict is loaded plain or from under "model" (code/modelv2/eval_selfcontained_entropy.py:130-134); the model's
 N, M, input channels and spatial_params are read from its shapes.  Images are PNG through PIL when PIL is importable
@@ -101,12 +104,17 @@ def print_info(ix):
         res = sum(c["r_bytes"] for c in ix["containers"])
         print(f"[dsic_image] near-lossless: max_error {ix['max_error']}, residual layer {res} bytes "
               f"({8.0 * res / (ix['H'] * ix['W']):.4f} bpp), lossy layer {sum(c['bytes'] for c in ix['containers'])} bytes")
+    if ix.get("nodata") is not None:
+        states = [t["state"] for t in ix["tiles"]]
+        print(f"[dsic_image] nodata {ix['nodata']}: {states.count(0)} empty, {states.count(1)} full, "
+              f"{states.count(2)} mixed tile(s), {ix['coded']} coded; mask block {ix['mask_bytes']} bytes")
     for k, c in enumerate(ix["containers"]):
         pixels = 0
-        for t in range(c["first"], c["first"] + c["tiles"]):
+        held = c.get("ids", range(c["first"], c["first"] + c["tiles"]))   # the tiles the batch really holds
+        for t in held:
             (a, b), (l, r) = g["own_y"][t // g["nx"]], g["own_x"][t % g["nx"]]
             pixels += max(0, min(b, g["H"]) - a) * max(0, min(r, g["W"]) - l)
-        print(f"[dsic_image]   batch {k}: tiles {c['first']}..{c['first'] + c['tiles'] - 1}, {c['bytes']} bytes, "
+        print(f"[dsic_image]   batch {k}: tiles {held[0]}..{held[-1]}, {c['bytes']} bytes, "
               f"{8.0 * c['bytes'] / pixels:.4f} bpp over {pixels} pixels")
 
 
@@ -127,6 +135,8 @@ def main(argv=None):
     ap.add_argument("--region", default=None, metavar="Y0,X0,H,W", help="decompress: only this window of the image")
     ap.add_argument("--overviews", type=int, default=0, metavar="N",
                     help="compress: store N halved levels beside the image (a DSICP stream)")
+    ap.add_argument("--nodata", type=int, default=None, metavar="V",
+                    help="compress: keep the mask of the pixels whose channels all equal V (0 .. 255) exactly")
     ap.add_argument("--level", type=int, default=0, metavar="L",
                     help="decompress: the overview level of a DSICP stream (0 = the full image); --region counts in it")
     ap.add_argument("--min-nu", type=float, default=2.0)
@@ -156,7 +166,7 @@ def main(argv=None):
     if a.mode == "compress":
         img = read_image(a.src, codec._model_shape(model)[2])
         stream = codec.compress_image(model, img, tile=a.tile, batch=a.batch, tail=a.tail, segments=a.segments,
-                                      overlap=a.overlap, max_error=a.max_error, overviews=a.overviews)
+                                      overlap=a.overlap, max_error=a.max_error, overviews=a.overviews, nodata=a.nodata)
         with open(a.dst, "wb") as f:
             f.write(stream)
         if a.overviews:
@@ -168,7 +178,8 @@ def main(argv=None):
             h = codec.unpack_image_stream(stream)
         print(f"[dsic_image] {h['H']}x{h['W']}x{h['C']} -> {len(stream)} bytes, {codec.image_bpp(stream):.4f} bpp, "
               f"{h['batches']} batch(es) of {h['th']}x{h['tw']} tiles, {h['segments']} segment(s) per y string, "
-              f"overlap {h['overlap']}" + (f", max_error {h['max_error']}" if "max_error" in h else ""))
+              f"overlap {h['overlap']}" + (f", max_error {h['max_error']}" if "max_error" in h else "")
+              + (f", nodata {h['nodata']}: {h['coded']} coded tile(s)" if "nodata" in h else ""))
     elif region is not None:
         stats = {}
         with open(a.src, "rb") as f:

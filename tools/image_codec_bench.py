@@ -27,6 +27,12 @@ Every figure is the best of --reps full passes over the scene after one warm-up 
           error of the decode, compress_image / decompress_image and a one-tile decompress_region in ms.  Written to
           profiles/near_lossless_bench.json (or --json).  Records, not bars.
 
+--nodata  nodata masks: the scene with a wedge of fill pixels (value 0) that empties about a third of its tiles, coded
+          without nodata and with nodata=0, read alternately in one run (medians of --reps readings): stream bytes, the
+          mask block's bytes, tile states, compress_image / decompress_image and decompress_region of one empty and of
+          one full tile in ms, and the classify pass alone.  Written to profiles/nodata_bench.json (or --json).
+          Records, not bars.
+
 --region  decompress_region of the same stream for an aligned one-tile window, an unaligned 2 x 2-tile-sized window
           (9 tiles), an unaligned half-scene window and the whole image, beside decompress_image before and after
           them in the same run (the two readings show the run-to-run spread).  Records, not bars.
@@ -241,6 +247,70 @@ def near_lossless_records(model, img, a, taus):
     return res
 
 
+def nodata_records(model, img, a):
+    """The scene with a wedge of nodata, coded without (None) and with nodata = 0, alternately."""
+    import statistics
+    import torch
+    from dsic_amd import codec
+    from dsic_amd import mask as _mask
+    t, size = a.tile, a.size
+    yy = torch.arange(size, device=img.device).view(size, 1)
+    xx = torch.arange(size, device=img.device).view(1, size)
+    img = img.clone()
+    img[(10 * xx < 8 * (size - yy))] = 0                               # 40 % of the pixels, along the top-left edge
+    modes = [None, 0]
+    streams = {m: codec.compress_image(model, img, tile=t, batch=a.batch, nodata=m) for m in modes}
+    ix = codec.stream_index(streams[0])
+    states = [r["state"] for r in ix["tiles"]]
+    empty, full = states.index(0), len(states) - 1 - states[::-1].index(1)
+    g = ix["grid"]
+    wins = {"region_empty_tile": (g["own_y"][empty // g["nx"]][0], g["own_x"][empty % g["nx"]][0], t, t),
+            "region_full_tile": (g["own_y"][full // g["nx"]][0], g["own_x"][full % g["nx"]][0], t, t)}
+    plain = codec.decompress_image(model, streams[None])
+    nod = (img == 0).all(dim=2)
+    want = torch.where(nod.unsqueeze(2), torch.zeros_like(plain), plain)
+    assert torch.equal(codec.decompress_image(model, streams[0]), want), "the masked stream broke its contract"
+    jobs = {"compress_image": lambda m: codec.compress_image(model, img, tile=t, batch=a.batch, nodata=m),
+            "decompress_image": lambda m: codec.decompress_image(model, streams[m])}
+    for name, win in wins.items():
+        jobs[name] = lambda m, win=win: codec.decompress_region(model, streams[m], *win, batch=a.batch)
+    reads = {name: {m: [] for m in modes} for name in jobs}
+    for name, job in jobs.items():
+        for m in modes:
+            job(m)                                                     # warm-up
+        torch.cuda.synchronize()
+        for _ in range(a.reps):
+            for m in modes:
+                t0 = time.perf_counter()
+                job(m)
+                torch.cuda.synchronize()
+                reads[name][m].append(1e3 * (time.perf_counter() - t0))
+    cls = [1e3 * v for v in _times(lambda: _mask.classify(img, g, 3, 0), a.reps)]
+    res = {"what": "the scene with a wedge of nodata, coded without and with nodata=0, read alternately in one run on "
+                   "one MI355X; medians",
+           "scene": f"{size}x{size}x3 uint8", "tile": t, "batch": a.batch, "reps": a.reps, "tiles": g["n"],
+           "nodata_pixels": int(nod.sum()), "states": {"empty": states.count(0), "full": states.count(1),
+                                                       "mixed": states.count(2)},
+           "coded_tiles": ix["coded"], "mask_block_bytes": ix["mask_bytes"],
+           "mask_modes": {"raw": sum(1 for r in ix["tiles"] if r.get("m_mode") == 0),
+                          "list": sum(1 for r in ix["tiles"] if r.get("m_mode") == 1)},
+           "windows_y0_x0_h_w": {k: list(v) for k, v in wins.items()},
+           "classify": {"ms_median": round(statistics.median(cls), 3), "ms_all": [round(v, 3) for v in cls],
+                        "what": "dsic_mask_classify_u8 and the copy of the counts, wall clock",
+                        "image_GB_per_s": round(img.numel() / statistics.median(cls) / 1e6, 1)},
+           "modes": {}}
+    for m in modes:
+        rec = {"stream_bytes": len(streams[m]), "bpp": round(codec.image_bpp(streams[m]), 4)}
+        for name in jobs:
+            med = statistics.median(reads[name][m])
+            rec[name] = {"ms_median": round(med, 3), "ms_all": [round(v, 3) for v in reads[name][m]]}
+        coded = ix["coded"] if m is not None else g["n"]
+        for name in ("compress_image", "decompress_image"):
+            rec[name]["ms_per_coded_tile"] = round(rec[name]["ms_median"] / coded, 4)
+        res["modes"]["plain" if m is None else f"nodata={m}"] = rec
+    return res
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--size", type=int, default=4096)
@@ -254,6 +324,8 @@ def main():
                     help="measure overlapped tiles with blended seams against overlap 0, alternately")
     ap.add_argument("--max-error", default=None, metavar="T[,T2...]",
                     help="measure near-lossless streams (max_error = T) against the lossy stream, alternately")
+    ap.add_argument("--nodata", action="store_true",
+                    help="measure a scene with a wedge of nodata, coded without and with nodata=0, alternately")
     a = ap.parse_args()
 
     import numpy as np
@@ -274,6 +346,12 @@ def main():
     img = torch.from_numpy(scene.astype(np.uint8)).cuda()
     n = g["n"]
 
+    if a.nodata:
+        res = nodata_records(model, img, a)
+        print(json.dumps(res))
+        with open(a.json or os.path.join(ROOT, "profiles", "nodata_bench.json"), "w") as f:
+            json.dump(res, f, indent=1)
+        return
     if a.max_error is not None:
         res = near_lossless_records(model, img, a, [int(v) for v in a.max_error.split(",")])
         print(json.dumps(res))
