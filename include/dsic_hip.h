@@ -413,7 +413,11 @@ int dsic_range_encode_seg_ws(const float* y_nchw, const float* z_nchw, const int
 
 /* torchac.decode_float_cdf call sites :96,116: string b starts at
  * in + b*stride and has lengths[b*lstride + loff] bytes; meta_off 0 = y, 2 = z.
- * out: NCHW float latents [B][C][HW] (symbol + min). */
+ * out: NCHW float latents [B][C][HW] (symbol + min).
+ * The bytes at and behind lengths[...] (zeros stand in for them) and the table entries k >= L_b of a
+ * row (c[L_b] = 65536 is implicit) are never interpreted: both may hold anything.  Any bytes decode
+ * to symbols inside the support.  An image whose L_b is < 1 or > Lmax raises err bit 1 and keeps its
+ * part of out untouched; the other images decode. */
 int dsic_range_decode(const uint8_t* in, int64_t stride, const int* lengths,
                       int lstride, int loff, const int* meta, int meta_off,
                       const uint16_t* tables, int Lmax, int B, int C, int HW,
