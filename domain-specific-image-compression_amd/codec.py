@@ -45,19 +45,29 @@ from only the tiles that own its pixels: stream_index finds their bytes from the
 them in dense batches and stitches them into the window, byte for byte the crop of decompress_image's result.
 decompress_image is the same decode (_decode_window) of the window (0, 0, H, W), one batch per container.
 
+A uint16 [H,W,C] image (kind 2: 16-bit imagery such as Sentinel-2 reflectances, C at most 4) is stream version 6: the
+version-3 head (segments word, overlap word, 0 allowed), then per band `lo u32, hi u32` with lo <= hi <= 65535, the
+scale: by default the band's own minimum and maximum (dsic_band_range_u16), or the caller's.  With R = hi - lo the model
+sees norm(v) = R == 0 ? 0 : float32(min(max(v, lo), hi) - lo) / float32(R), the arithmetic of the reference's
+code/combinebandsall.py:7-12, computed in the tile gather (dsic_tile_gather_u16), so every container is byte for byte
+that of the float32 image norm(img); the decoders return denorm(x) = lo + uint32(clamp(x, 0, 1) * float32(R) + 0.5f),
+rounded to nearest (stitch and blend finish), and denorm(norm(v)) == v inside [lo, hi].  Version 6 and kind 2 occur only
+together.  max_error and nodata are refused with uint16 images: the residual tables and the mask classifier are 8-bit.
+
 overviews = n > 0 writes a pyramid, the image at full, 1/2, 1/4, ... 1/2^n resolution in one DSICP stream:
 
     magic "DSICP\\0" | version u16 = 1 | levels u32 (n + 1 >= 2) | levels x (H u32, W u32, offset u64, length u64) |
     the level streams back to back, level 0 first                 (little endian; offsets count from the magic)
 
 Level l + 1 is level l halved on the device (build_overviews: ceil(H/2) x ceil(W/2), the mean of each 2 x 2 block with
-the last row or column of an odd side counted twice; uint8 (a + b + c + d + 2) >> 2, float32 ((a + b) + (c + d)) *
-0.25f), and every level's bytes are the DSICI stream compress_image writes for that level's image, so a level is
+the last row or column of an odd side counted twice; uint8 and uint16 (a + b + c + d + 2) >> 2, float32 ((a + b) +
+(c + d)) * 0.25f), and every level's bytes are the DSICI stream compress_image writes for that level's image, so a level is
 read, indexed and decoded on its own (level=l of the decoders and of stream_index) through a view of its byte range.
 """
 from __future__ import annotations
 
 import bisect
+import ctypes
 import operator
 import struct
 
@@ -77,18 +87,20 @@ VERSION_SEG = 2            # version 1 + the segments word; written only for seg
 VERSION_OV = 3             # version 1 + the segments word + the overlap word; written only for overlap > 0
 VERSION_RES = 4            # the version-3 head with overlap 0 + max_error u32 + res_bands u32; a residual block per batch
 VERSION_MASK = 5           # the version-3 head with overlap 0 + nodata u32 + coded u32; a mask block, then the coded tiles' batches
+VERSION_U16 = 6            # the version-3 head (overlap 0 allowed) + C x (lo u32, hi u32), the per-band scale; kind 2 only
 BLEND_IDS = 64             # tiles per dsic_tile_blend_window_f32 call
-KIND_U8_HWC, KIND_F32_CHW = 0, 1
+KIND_U8_HWC, KIND_F32_CHW, KIND_U16_HWC = 0, 1, 2
 _HEAD = struct.Struct("<6sHI6I4I2I")
 _SEGS = struct.Struct("<I")
 _RES = struct.Struct("<II")                                                # version 4: max_error, res_bands
 _MASK = struct.Struct("<II")                                               # version 5: nodata, coded
+_SCALE = struct.Struct("<II")                                              # version 6, per band: lo, hi
 _LEN = struct.Struct("<Q")
 PMAGIC = b"DSICP\x00"
 PVERSION = 1
 _PHEAD = struct.Struct("<6sHI")                                            # magic, version, levels
 _PLEVEL = struct.Struct("<IIQQ")                                           # H, W, offset, length
-_SAME_IN_LEVELS = ("C", "kind", "N", "M", "in_ch", "spatial_params", "numerics")
+_SAME_IN_LEVELS = ("C", "kind", "N", "M", "in_ch", "spatial_params", "numerics", "scale")
 
 
 def _ceil16(n):
@@ -126,6 +138,26 @@ def _check_overlap(O, th, tw, what):
         raise ValueError(f"{what}: overlap={O!r} must be 0 or a multiple of 16 from 16 to half the smaller side of "
                          f"the {th}x{tw} tiles")
     return O
+
+
+def check_scale(scale, C, what) -> list:
+    """scale as a stream holds it: C pairs of integers (lo, hi), 0 <= lo <= hi <= 65535 -> [(lo, hi), ...]."""
+    try:
+        pairs = [tuple(operator.index(v) for v in pair) for pair in scale]
+    except TypeError:
+        raise ValueError(f"{what}: scale={scale!r} is not a sequence of integer pairs (lo, hi)") from None
+    if len(pairs) != C or any(len(pair) != 2 for pair in pairs):
+        raise ValueError(f"{what}: scale={scale!r} must hold one pair (lo, hi) for each of the {C} bands")
+    for lo, hi in pairs:
+        if not 0 <= lo <= hi <= 65535:
+            raise ValueError(f"{what}: scale pair ({lo}, {hi}) must have 0 <= lo <= hi <= 65535")
+    return pairs
+
+
+def _lohi(scale):
+    """The scale as the uint16 kernels take it: a host array of 2 C uint32 (lo0, hi0, lo1, hi1, ...)."""
+    flat = [v for pair in scale for v in pair]
+    return (ctypes.c_uint32 * len(flat))(*flat)
 
 
 def _check_image(H, W):
@@ -172,10 +204,22 @@ def pack_image_stream(header: dict, blobs, residuals=None, mask=None) -> bytes:
     and behind every container its residual block from `residuals` (residual.pack_block).
     A header with "nodata" = v (not None) writes version 5: segments word, overlap word 0, nodata, coded (the number
     of tiles that are not empty, counted from the block's states), then `u64 length, mask` with `mask` the mask block
-    (mask.pack_block), then the containers of the coded tiles, `batch` to a container; there may be none."""
+    (mask.pack_block), then the containers of the coded tiles, `batch` to a container; there may be none.
+    A header with "scale" = [(lo, hi)] * C (not None) writes version 6, the uint16 image: kind must be 2 (and kind 2
+    needs a scale); segments word, overlap word (0 allowed), then lo, hi per band; no max_error, no nodata."""
     h = header
     K = entropy.check_segments(h.get("segments", 1), h["M"], "pack_image_stream")
     O = _check_overlap(h.get("overlap", 0), h["th"], h["tw"], "pack_image_stream")
+    if (h.get("scale") is not None) != (h["kind"] == KIND_U16_HWC):
+        raise ValueError("pack_image_stream: a scale goes with kind 2 (uint16 [H,W,C]), and only with it")
+    if h.get("scale") is not None:
+        scale = check_scale(h["scale"], h["C"], "pack_image_stream")
+        if h.get("nodata") is not None or h.get("max_error") is not None or residuals is not None or mask is not None:
+            raise ValueError("pack_image_stream: a uint16 image together with max_error or nodata is not supported")
+        head = _HEAD.pack(MAGIC, VERSION_U16, h["numerics"] & 0xFFFFFFFF, h["H"], h["W"], h["C"], h["kind"], h["th"],
+                          h["tw"], h["N"], h["M"], h["in_ch"], h["spatial_params"], h["batch"], len(blobs))
+        head += _SEGS.pack(K) + _SEGS.pack(O) + b"".join(_SCALE.pack(lo, hi) for lo, hi in scale)
+        return b"".join([head] + [_LEN.pack(len(b)) + bytes(b) for b in blobs])
     if h.get("nodata") is not None:
         v = _mask.check_nodata(h["nodata"], "pack_image_stream")
         if O or h.get("max_error") is not None or residuals is not None:
@@ -263,12 +307,18 @@ def _read_framing(src, head=None):
     keys = ("version", "numerics", "H", "W", "C", "kind", "th", "tw", "N", "M", "in_ch", "spatial_params", "batch",
             "batches")
     h = dict(zip(keys, f[1:]))
-    if h["version"] not in (VERSION, VERSION_SEG, VERSION_OV, VERSION_RES, VERSION_MASK):
+    if h["version"] not in (VERSION, VERSION_SEG, VERSION_OV, VERSION_RES, VERSION_MASK, VERSION_U16):
         raise ValueError(f"DSICI stream version {h['version']}, this reader knows {VERSION}, {VERSION_SEG}, "
-                         f"{VERSION_OV}, {VERSION_RES} and {VERSION_MASK}")
+                         f"{VERSION_OV}, {VERSION_RES}, {VERSION_MASK} and {VERSION_U16}")
+    if (h["version"] == VERSION_U16) != (h["kind"] == KIND_U16_HWC):
+        raise ValueError(f"DSICI stream: version {h['version']} with kind {h['kind']} (version {VERSION_U16} and kind "
+                         f"{KIND_U16_HWC}, the uint16 image, go together)")
+    if h["version"] == VERSION_U16 and not 1 <= h["C"] <= 4:
+        raise ValueError(f"DSICI stream: a uint16 image of {h['C']} bands (1 .. 4)")
     off, h["segments"], h["overlap"] = _HEAD.size, 1, 0
-    if h["version"] in (VERSION_SEG, VERSION_OV, VERSION_RES, VERSION_MASK):
-        words = {VERSION_SEG: 1, VERSION_OV: 2, VERSION_RES: 4, VERSION_MASK: 4}[h["version"]]
+    if h["version"] in (VERSION_SEG, VERSION_OV, VERSION_RES, VERSION_MASK, VERSION_U16):
+        words = {VERSION_SEG: 1, VERSION_OV: 2, VERSION_RES: 4, VERSION_MASK: 4,
+                 VERSION_U16: 2 + 2 * h["C"]}[h["version"]]
         word = src.read_at(off, words * _SEGS.size)
         if len(word) < words * _SEGS.size:
             raise ValueError("truncated DSICI stream")
@@ -283,6 +333,13 @@ def _read_framing(src, head=None):
             if h["overlap"] == 0:
                 raise ValueError("DSICI stream: version 3 with overlap=0")
             _check_overlap(h["overlap"], h["th"], h["tw"], "DSICI stream")
+        if h["version"] == VERSION_U16:
+            (h["overlap"],) = _SEGS.unpack_from(word, _SEGS.size)
+            _check_overlap(h["overlap"], h["th"], h["tw"], "DSICI stream")
+            h["scale"] = [_SCALE.unpack_from(word, 2 * _SEGS.size + _SCALE.size * c) for c in range(h["C"])]
+            for lo, hi in h["scale"]:
+                if lo > hi or hi > 65535:
+                    raise ValueError(f"DSICI stream: scale pair ({lo}, {hi}) must have lo <= hi <= 65535")
         if h["version"] == VERSION_RES:
             overlap, h["max_error"], bands = struct.unpack_from("<3I", word, _SEGS.size)
             if overlap != 0:
@@ -329,7 +386,8 @@ def unpack_image_stream(stream) -> dict:
     stream or trailing bytes.  A version-4 stream also gives "max_error" and "residuals", the list of its residual
     blocks; the dicts of versions 1 to 3 have neither key.  A version-5 stream gives "nodata", "coded" (the tiles that
     are not empty: the containers hold these, in ascending tile number), "mask_offset", "mask_bytes" and "mask", its
-    mask block (mask.py); no other version has these keys."""
+    mask block (mask.py); no other version has these keys.  A version-6 stream (kind 2, the uint16 image) gives
+    "scale", the list of its C pairs (lo, hi); no other version has that key."""
     s = bytes(stream)
     h, frames, rframes = _read_framing(_Source(s))
     h["blobs"] = [s[off:off + size] for off, size in frames]
@@ -397,24 +455,25 @@ def level_for(index, max_side) -> int:
 
 
 def _image_kind(img, what):
-    """(kind, H, W, C) of a uint8 [H,W,C] or float32 [C,H,W] tensor."""
+    """(kind, H, W, C) of a uint8 [H,W,C], uint16 [H,W,C] or float32 [C,H,W] tensor."""
     if img.dim() != 3:
-        raise ValueError(f"{what}: expected uint8 [H,W,C] or float32 [C,H,W], got {tuple(img.shape)}")
-    if img.dtype == torch.uint8:
+        raise ValueError(f"{what}: expected uint8 or uint16 [H,W,C] or float32 [C,H,W], got {tuple(img.shape)}")
+    if img.dtype in (torch.uint8, torch.uint16):
         H, W, C = img.shape
-        return KIND_U8_HWC, H, W, C
+        return (KIND_U8_HWC if img.dtype == torch.uint8 else KIND_U16_HWC), H, W, C
     if img.dtype == torch.float32:
         C, H, W = img.shape
         return KIND_F32_CHW, H, W, C
-    raise TypeError(f"{what}: expected uint8 or float32, got {img.dtype}")
+    raise TypeError(f"{what}: expected uint8, uint16 or float32, got {img.dtype}")
 
 
 @torch.no_grad()
 def build_overviews(img, n) -> list:
-    """[img, level 1, ..., level n] on the device: img uint8 [H,W,C] or float32 [C,H,W] on the GPU, each level the one
-    before it halved by dsic_image_halve_u8 / dsic_image_halve_f32 (one launch per level): ceil(H/2) x ceil(W/2), a
-    pixel the mean of its 2 x 2 block, the last row or column of an odd side counted twice; uint8 rounds half up,
-    (a + b + c + d + 2) >> 2, float32 is ((a + b) + (c + d)) * 0.25f.  The sizes are overview_shapes(H, W, n)."""
+    """[img, level 1, ..., level n] on the device: img uint8 or uint16 [H,W,C] or float32 [C,H,W] on the GPU, each
+    level the one before it halved by dsic_image_halve_u8 / _u16 / _f32 (one launch per level): ceil(H/2) x ceil(W/2),
+    a pixel the mean of its 2 x 2 block, the last row or column of an odd side counted twice; uint8 and uint16 round
+    half up, (a + b + c + d + 2) >> 2, float32 is ((a + b) + (c + d)) * 0.25f.  The sizes are
+    overview_shapes(H, W, n)."""
     kind, H, W, C = _image_kind(img, "build_overviews")
     if not img.is_cuda:
         raise RuntimeError(f"build_overviews: expected a tensor on the GPU (no CPU fallback), got {img.device}")
@@ -426,6 +485,9 @@ def build_overviews(img, n) -> list:
         if kind == KIND_U8_HWC:
             dst = torch.empty((h2, w2, C), dtype=torch.uint8, device=src.device)
             _lib.check(L.dsic_image_halve_u8(_p(src), _p(dst), h, w, C, _stream()), "image_halve_u8")
+        elif kind == KIND_U16_HWC:
+            dst = torch.empty((h2, w2, C), dtype=torch.uint16, device=src.device)
+            _lib.check(L.dsic_image_halve_u16(_p(src), _p(dst), h, w, C, _stream()), "image_halve_u16")
         else:
             dst = torch.empty((C, h2, w2), dtype=torch.float32, device=src.device)
             _lib.check(L.dsic_image_halve_f32(_p(src), _p(dst), C, h, w, _stream()), "image_halve_f32")
@@ -469,9 +531,9 @@ def _check_levels(sizes, heads):
         if first is None:
             first = l
         for key in _SAME_IN_LEVELS:
-            if h[key] != heads[first][key]:
-                raise ValueError(f"DSICP stream: levels {first} and {l} disagree on {key} ({heads[first][key]} and "
-                                 f"{h[key]})")
+            if h.get(key) != heads[first].get(key):                        # scale: version 6 only
+                raise ValueError(f"DSICP stream: levels {first} and {l} disagree on {key} ({heads[first].get(key)} "
+                                 f"and {h.get(key)})")
 
 
 def _read_directory(src, head):
@@ -564,8 +626,34 @@ def unpack_pyramid_stream(stream) -> dict:
     return {"version": PVERSION, "levels": levels}
 
 
-def _gather(img, kind, g, C, first, n):
+def band_range(img) -> list:
+    """[(lo, hi), ...]: per band the minimum and maximum of a uint16 [H,W,C] image on the GPU (dsic_band_range_u16:
+    one pass over the image on many workgroups, then one small copy to the host).  The default scale of
+    compress_image."""
+    kind, H, W, C = _image_kind(img, "band_range")
+    if kind != KIND_U16_HWC:
+        raise TypeError(f"band_range: expected uint16 [H,W,C], got {img.dtype}")
+    if not img.is_cuda:
+        raise RuntimeError(f"band_range: expected a tensor on the GPU (no CPU fallback), got {img.device}")
+    img = img.contiguous()
+    out = torch.empty(2 * C, dtype=torch.int32, device=img.device)
+    _lib.check(_lib.load().dsic_band_range_u16(_p(img), H, W, C, _p(out), _stream()), "band_range_u16")
+    v = [int(x) & 0xFFFFFFFF for x in out.cpu().tolist()]
+    return list(zip(v[0::2], v[1::2]))
+
+
+def _gather(img, kind, g, C, first, n, scale=None):
     L = _lib.load()
+    if kind == KIND_U16_HWC:               # normalised on the way: the tiles gather_f32 cuts from norm(img)
+        tiles = torch.empty((n, C, g["th"], g["tw"]), dtype=torch.float32, device=img.device)
+        if g["overlap"]:
+            status = L.dsic_tile_gather_u16_ov(_p(img), _p(tiles), g["H"], g["W"], C, g["th"], g["tw"], g["overlap"],
+                                               _lohi(scale), first, n, _stream())
+        else:
+            status = L.dsic_tile_gather_u16(_p(img), _p(tiles), g["H"], g["W"], C, g["th"], g["tw"], _lohi(scale),
+                                            first, n, _stream())
+        _lib.check(status, "tile_gather_u16_ov" if g["overlap"] else "tile_gather_u16")
+        return tiles
     if kind == KIND_U8_HWC:
         tiles = torch.empty((n, g["th"], g["tw"], C), dtype=torch.uint8, device=img.device)
         what = "tile_gather_u8"
@@ -621,9 +709,9 @@ def _compress_masked(model, x, g, C, batch, tail, segments, nodata, header) -> b
     return pack_image_stream(header, blobs, mask=_mask.encode_block(x, g, C, nodata, states))
 
 
-def _compress_device_image(model, x, tile, batch, tail, segments, overlap, tau, nodata=None) -> bytes:
+def _compress_device_image(model, x, tile, batch, tail, segments, overlap, tau, nodata=None, scale=None) -> bytes:
     """compress_image's work on one image that lies contiguous on the model's device, after the argument checks that
-    do not depend on its size -> its DSICI stream."""
+    do not depend on its size -> its DSICI stream.  scale: the checked pairs of a uint16 image."""
     kind, H, W, C = _image_kind(x, "compress_image")
     N, M, in_ch, spatial = _model_shape(model)
     g, overlap = _level_grid(H, W, kind, tile, overlap, tau)
@@ -635,7 +723,7 @@ def _compress_device_image(model, x, tile, batch, tail, segments, overlap, tau, 
     blobs, residuals = [], None if tau is None else []
     for first in range(0, g["n"], batch):
         n = min(batch, g["n"] - first)
-        tiles = _gather(x, kind, g, C, first, n)
+        tiles = _gather(x, kind, g, C, first, n, scale)
         if tau is None:
             blobs.append(entropy.compress_to_container(model, tiles, tail, segments=segments))
             continue
@@ -649,14 +737,16 @@ def _compress_device_image(model, x, tile, batch, tail, segments, overlap, tau, 
               "N": N, "M": M, "in_ch": in_ch, "spatial_params": spatial, "batch": batch, "segments": segments, "overlap": overlap}
     if tau is not None:
         header["max_error"] = tau
+    if scale is not None:
+        header["scale"] = scale
     return pack_image_stream(header, blobs, residuals)
 
 
 @torch.no_grad()
 def compress_image(model, img, tile=256, batch=64, tail=10, segments=1, overlap=0, max_error=None,
-                   overviews=0, nodata=None) -> bytes:
-    """img: uint8 [H,W,C] or float32 [C,H,W] in [0,1], on the CPU or the GPU -> one DSICI stream.  The image is
-    uploaded once; each batch of `batch` tiles is gathered on the device (reflect padding included) and becomes one
+                   overviews=0, nodata=None, scale=None) -> bytes:
+    """img: uint8 [H,W,C], uint16 [H,W,C] or float32 [C,H,W] in [0,1], on the CPU or the GPU -> one DSICI stream.  The
+    image is uploaded once; each batch of `batch` tiles is gathered on the device (reflect padding included) and becomes one
     DSIC2 container.  segments = K > 1 (1, 2, 4, 8 or 16, dividing M): every tile's y string is K independent strings
     (DSIC3 containers, stream version 2), which the decoders read on K waves per tile; the decoded image is the same.
     overlap = O > 0 (a multiple of 16, at most half a tile side): tiles share O pixels with their neighbours
@@ -680,10 +770,29 @@ def compress_image(model, img, tile=256, batch=64, tail=10, segments=1, overlap=
     channels (v / 255.0f for out="f32") at every nodata pixel of img, and at every other pixel the bits the stream
     without nodata decodes to.  Not promised: a valid pixel may happen to decode to (v, ..., v), as it can today.
     A float32 image, overlap > 0, max_error and overviews > 0 are refused with nodata: each would need a masked
-    variant of its own (predictor, blend, halving over valid pixels only).  None writes today's streams."""
+    variant of its own (predictor, blend, halving over valid pixels only).  None writes today's streams.
+    A uint16 image (1 to 4 bands) writes stream version 6, which carries a per-band scale (lo, hi): scale = None takes
+    each band's own minimum and maximum (band_range, on the device), otherwise scale is a sequence of C integer pairs
+    with 0 <= lo <= hi <= 65535, e.g. [(0, 10000)] * C, and values outside a pair clip to it.  The model codes
+    norm(img) (module docstring), so every container is byte for byte that of the float32 image norm(img) compressed
+    with the same arguments; segments and overlap work unchanged, and the decoders return uint16 by default.  With
+    overviews the scale is decided once, at level 0, and every level is written with it (halved values stay inside
+    [lo, hi]).  scale with a uint8 or float32 image is a ValueError.  max_error and nodata are refused with a uint16
+    image: the residual tables and the mask classifier are 8-bit, and 16-bit variants are separate work."""
     dev = next(model.parameters()).device
     tau = None if max_error is None else _residual.check_max_error(max_error, "compress_image")
     kind, H, W, C = _image_kind(img, "compress_image")
+    if kind == KIND_U16_HWC:
+        for name, on in (("max_error", max_error is not None), ("nodata", nodata is not None)):
+            if on:
+                raise ValueError(f"compress_image: {name} together with a uint16 image is not supported (the residual "
+                                 "tables and the mask classifier are 8-bit)")
+        if not 1 <= C <= 4:
+            raise ValueError(f"compress_image: a uint16 image has 1 to 4 bands, got {C}")
+        if scale is not None:
+            scale = check_scale(scale, C, "compress_image")
+    elif scale is not None:
+        raise ValueError("compress_image: scale goes with a uint16 [H,W,C] image, not with uint8 or float32")
     if nodata is not None:
         nodata = _mask.check_nodata(nodata, "compress_image")
         if kind != KIND_U8_HWC:
@@ -707,10 +816,12 @@ def compress_image(model, img, tile=256, batch=64, tail=10, segments=1, overlap=
         except ValueError as e:
             raise ValueError(f"{e} (overview level {level}, {h}x{w})" if level else str(e)) from None
     x = img.to(dev).contiguous()
+    if kind == KIND_U16_HWC and scale is None:
+        scale = band_range(x)
     if len(shapes) == 1:
-        return _compress_device_image(model, x, tile, batch, tail, segments, overlap, tau, nodata)
+        return _compress_device_image(model, x, tile, batch, tail, segments, overlap, tau, nodata, scale)
     return pack_pyramid_stream([_compress_device_image(model, lv, tile, batch, tail, segments, overlap,
-                                                       tau if level == 0 else None)
+                                                       tau if level == 0 else None, scale=scale)
                                 for level, lv in enumerate(build_overviews(x, overviews))])
 
 
@@ -736,7 +847,8 @@ def _refuse_foreign(model, h, what):
 def _stream_grid(h):
     """The tile grid a DSICI header describes; ValueError where its fields contradict each other."""
     H, W, C, th, tw = h["H"], h["W"], h["C"], h["th"], h["tw"]
-    if C != h["in_ch"] or h["kind"] not in (KIND_U8_HWC, KIND_F32_CHW) or h["batch"] < 1:
+    kinds = (KIND_U16_HWC,) if h["version"] == VERSION_U16 else (KIND_U8_HWC, KIND_F32_CHW)
+    if C != h["in_ch"] or h["kind"] not in kinds or h["batch"] < 1:
         raise ValueError("DSICI stream: inconsistent header")
     _check_image(H, W)
     if th % 16 or tw % 16 or th < 32 or tw < 32 or th > _ceil16(H) or tw > _ceil16(W):
@@ -756,7 +868,10 @@ def _check_batch_shape(k, shape_y, n, th, tw):
 
 
 def _out_image(kind, C, h, w, dev, what):
-    """The empty output image of a decode and the stitch call's name stem: uint8 [h,w,C] or float32 [C,h,w]."""
+    """The empty output image of a decode and the stitch call's name stem: uint8 [h,w,C], uint16 [h,w,C] or float32
+    [C,h,w]."""
+    if kind == KIND_U16_HWC:
+        return torch.empty((h, w, C), dtype=torch.uint16, device=dev), "u16"
     if kind == KIND_U8_HWC:
         if C not in (3, 4):
             raise ValueError(f"{what}: uint8 output needs 3 or 4 channels, the stream has {C}")
@@ -840,6 +955,8 @@ def stream_index(src, level=None) -> dict:
     empty, 1 full, 2 mixed), for an empty tile k = b = None and zero lengths, for a mixed tile m_off, m_len, m_mode (its
     mask payload, which tile_spans includes); per container ids, the grid numbers of its tiles.  Of the mask block the
     26-byte head, the state bytes and the 12-byte records are read.
+    and for a version-6 stream (only then) scale, the C pairs (lo, hi) of the uint16 image; they add 8 C bytes to the
+    version-3 head, which index_bytes counts.
       stream_bytes, index_bytes (what this call read).
     ValueError as unpack_image_stream, entropy.unpack_container and decompress_image raise it: wrong magic or version,
     DSIC1 container, truncated stream or container, trailing bytes, batches that do not match the grid, latents that
@@ -947,16 +1064,20 @@ def _apply_mask(source, ix, tiles, img, kind, window) -> int:
 def _decode_window(model, src, window, out, batch, stats, what, level=0):
     """decompress_region's work; window None = the whole image, batch None = the stream's tiles per container.  Of a
     DSICP stream the chosen level is decoded, through a view of its bytes."""
-    if out not in (None, "u8", "f32"):
-        raise ValueError(f"{what}: out={out!r} (None, 'u8' or 'f32')")
+    if out not in (None, "u8", "f32", "u16"):
+        raise ValueError(f"{what}: out={out!r} (None, 'u8', 'f32' or 'u16')")
     source, ix, _, _ = _open_level(src, level)
+    if out == "u16" and "scale" not in ix:
+        raise ValueError(f"{what}: out='u16' needs the scale of a uint16 stream (version {VERSION_U16}); this one is "
+                         f"version {ix['version']}")
     _refuse_foreign(model, ix, what)
     H, W, C, th, tw = ix["H"], ix["W"], ix["C"], ix["th"], ix["tw"]
     y0, x0, h, w = (0, 0, H, W) if window is None else window
     tiles = window_tiles(ix, y0, x0, h, w)
     y0, x0, h, w = int(y0), int(x0), int(h), int(w)
     batch = ix["batch"] if batch is None else batch
-    kind = {None: ix["kind"], "u8": KIND_U8_HWC, "f32": KIND_F32_CHW}[out]
+    kind = {None: ix["kind"], "u8": KIND_U8_HWC, "f32": KIND_F32_CHW, "u16": KIND_U16_HWC}[out]
+    lohi = (_lohi(ix["scale"]),) if kind == KIND_U16_HWC else ()        # the uint16 calls take the scale last
     tau = ix.get("max_error")                  # a residual layer: the result is the uint8 image, converted for "f32"
     img, suffix = _out_image(KIND_U8_HWC if tau is not None else kind, C, h, w, next(model.parameters()).device, what)
     L, O = _lib.load(), ix["overlap"]
@@ -1006,7 +1127,7 @@ def _decode_window(model, src, window, out, batch, stats, what, level=0):
                                                         _p(canvas), H, W, C, th, tw, O, y0, x0, h, w, _stream()),
                            "tile_blend_window_f32")
         else:
-            _lib.check(fn(_p(x_hat), _p(ids), n, _p(img), H, W, C, th, tw, y0, x0, h, w, _stream()),
+            _lib.check(fn(_p(x_hat), _p(ids), n, _p(img), H, W, C, th, tw, y0, x0, h, w, *lohi, _stream()),
                        "tile_stitch_window_" + suffix)
         uploaded += nbytes
         decode_batches += 1
@@ -1014,6 +1135,8 @@ def _decode_window(model, src, window, out, batch, stats, what, level=0):
         uploaded += _apply_mask(source, ix, tiles, img, kind, (y0, x0, h, w))
     if O and kind == KIND_F32_CHW:
         _lib.check(L.dsic_tile_blend_finish_f32(_p(canvas), C, h, w, _stream()), "tile_blend_finish_f32")
+    elif O and kind == KIND_U16_HWC:
+        _lib.check(L.dsic_tile_blend_finish_u16(_p(canvas), _p(img), C, h, w, *lohi, _stream()), "tile_blend_finish_u16")
     elif O:
         _lib.check(L.dsic_tile_blend_finish_u8(_p(canvas), _p(img), C, h, w, _stream()), "tile_blend_finish_u8")
     if stats is not None:
@@ -1034,7 +1157,11 @@ def decompress_image(model, stream, out=None, level=0):
     pass takes min(v, 1) and, for uint8, (uint8)(v*255).  A near-lossless stream (version 4) decodes to the uint8 image
     clamp(p + q s, 0, 255) of residual.py, within max_error of the original; out="f32" returns that image / 255.  A DSICP stream (compress_image with
     overviews) decodes to its level `level`, 0 the full image, as that level's own DSICI stream does; any other level
-    than 0 of a DSICI stream, or a level the pyramid does not hold, is a ValueError."""
+    than 0 of a DSICI stream, or a level the pyramid does not hold, is a ValueError.  A uint16 stream (version 6)
+    decodes by default, or with out="u16", to uint16 [H,W,C]: lo + uint32(clamp(x,0,1) * float32(hi - lo) + 0.5f) per
+    band with the stream's own scale, rounded to nearest (with overlap: of the blended canvas); out="u8" / "f32" give
+    the normalised image as for any other stream, the uint8 one being what the reference's (rgb*255).astype(uint8)
+    saves.  out="u16" on a stream of another version is a ValueError: it has no scale."""
     return _decode_window(model, stream, None, out, None, None, "decompress_image", level)
 
 

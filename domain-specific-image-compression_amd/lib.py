@@ -126,6 +126,12 @@ SIGNATURES = {
     "dsic_mask_unpack": (c_int, [_P, c_int64, _P, c_int, c_int, c_int, _P, _P]),
     "dsic_mask_apply_u8": (c_int, [_P, c_int, _P, c_int, c_int, _P] + [c_int] * 9 + [_P]),
     "dsic_mask_apply_f32": (c_int, [_P, c_int, _P, c_int, c_int, _P] + [c_int] * 9 + [_P]),
+    "dsic_band_range_u16": (c_int, [_P, c_int, c_int, c_int, _P, _P]),
+    "dsic_tile_gather_u16": (c_int, [_P, _P] + [c_int] * 5 + [_P, c_int, c_int, _P]),
+    "dsic_tile_gather_u16_ov": (c_int, [_P, _P] + [c_int] * 6 + [_P, c_int, c_int, _P]),
+    "dsic_tile_stitch_window_u16": (c_int, [_P, _P, c_int, _P] + [c_int] * 9 + [_P, _P]),
+    "dsic_tile_blend_finish_u16": (c_int, [_P, _P, c_int, c_int, c_int, _P, _P]),
+    "dsic_image_halve_u16": (c_int, [_P, _P, c_int, c_int, c_int, _P]),
     "dsic_stream_create_masked":(c_int, [_P, c_int, _P]),
     "dsic_stream_destroy": (c_int, [_P]),
     "dsic_range_decode": (c_int, [_P, c_int64, _P, c_int, c_int, _P, c_int, _P, c_int, c_int, c_int,

@@ -642,6 +642,40 @@ int dsic_mask_apply_f32(const uint32_t* planes, int n_planes, const int* desc, i
                         float* out, int H, int W, int C, int th, int tw, int wy0, int wx0, int wh,
                         int ww, void* stream);
 
+/* ---- 16-bit imagery (codec.compress_image of a uint16 [H][W][C] image; stream version 6) ----
+ * Per band c the scale is a pair of integers lo_c <= hi_c in 0..65535, R = hi - lo.  Every call
+ * that takes one reads it from the HOST pointer lohi: 2*C uint32 (lo0, hi0, lo1, hi1, ...),
+ * copied by value into the kernel's arguments, hence 1 <= C <= 4.
+ *   norm(v)   = R == 0 ? 0.0f : (float)(min(max(v, lo), hi) - lo) / (float)R   (one IEEE division)
+ *   denorm(x) = lo + (uint32)(clamp(x, 0, 1) * (float)R + 0.5f)               (unfused; NaN -> lo)
+ * denorm(norm(v)) == v for lo <= v <= hi, also with norm(v) one ulp off either way.
+ * Images are uint16 at any 2-byte alignment; a row of W*C*2 bytes must not exceed 2^31 - 1.
+ * band_range_u16: out_lohi_dev (DEVICE, uint32 [2*C]) = per band the minimum and maximum of the
+ *   whole image; the call initialises it, and the result does not depend on the launch shape.
+ * tile_gather_u16 / _ov: uint16 [H][W][C] -> float32 tiles [n][C][th][tw] = norm of the
+ *   reflect-padded tiles, grid, padding and (first_tile, n_tiles) as tile_gather_f32 / _ov; the
+ *   result is tile_gather_f32 of the float32 [C][H][W] image norm(img), bit for bit.
+ * tile_stitch_window_u16: tiles float32 [n][C][th][tw] + tile_ids -> denorm into the uint16
+ *   [wh][ww][C] window image, owned rectangles and window as tile_stitch_window_u8.
+ * tile_blend_finish_u16: canvas float32 [C][h][w] (tile_blend_window_f32) -> denorm(min(v, 1))
+ *   into uint16 [h][w][C].
+ * image_halve_u16: uint16 [H][W][C] -> [ceil(H/2)][ceil(W/2)][C], (a + b + c + d + 2) >> 2 in 32
+ *   bits, the last row or column of an odd side counted twice; src and dst must not overlap. */
+int dsic_band_range_u16(const uint16_t* img_hwc, int H, int W, int C, uint32_t* out_lohi_dev,
+                        void* stream);
+int dsic_tile_gather_u16(const uint16_t* img_hwc, float* tiles, int H, int W, int C, int th,
+                         int tw, const uint32_t* lohi, int first_tile, int n_tiles, void* stream);
+int dsic_tile_gather_u16_ov(const uint16_t* img_hwc, float* tiles, int H, int W, int C, int th,
+                            int tw, int overlap, const uint32_t* lohi, int first_tile, int n_tiles,
+                            void* stream);
+int dsic_tile_stitch_window_u16(const float* tiles, const int* tile_ids, int n_tiles,
+                                uint16_t* out, int H, int W, int C, int th, int tw, int wy0,
+                                int wx0, int wh, int ww, const uint32_t* lohi, void* stream);
+int dsic_tile_blend_finish_u16(const float* canvas, uint16_t* out_hwc, int C, int h, int w,
+                               const uint32_t* lohi, void* stream);
+int dsic_image_halve_u16(const uint16_t* src_hwc, uint16_t* dst_hwc, int H, int W, int C,
+                         void* stream);
+
 /* HIP stream limited to the CUs whose bit is set in mask_host[words] (bit i of
  * word i/32 = CU i).  Used to give the range coder its own few CUs beside the
  * conv kernels; there is no reference counterpart (the reference is

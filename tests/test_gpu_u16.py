@@ -1,0 +1,422 @@
+"""16-bit imagery on the GPU.  The kernels of csrc/image_u16.hip alone (band range, gather, stitch, blend finish,
+halving), bit for bit against the NumPy restatement of tests/u16_ref.py, outputs between guards and inputs inside a
+larger allocation at byte offsets 0 and 2 past a 16-byte boundary as in test_gpu_mask.py; then the version-6 stream of
+codec.py on the 330 x 530 scene of test_gpu_pyramid.py with the same synthetic model (tile 128, batch 5, 15 tiles),
+mapped to uint16 with another offset and span per band: its containers are those of the float32 stream of norm(img),
+and it decodes, whole, by window and level by level, to denorm of what that stream decodes to.  Every comparison is
+exact."""
+import ctypes
+import io
+import os
+import subprocess
+import sys
+
+import numpy as np
+import pytest
+import torch
+
+import blend_ref
+import codec_ref
+import u16_ref as R
+from dsic_amd import codec, evaluate, lib
+from dsic_amd import synthetic as S
+from dsic_amd.ops import _p, _stream
+from test_gpu_pyramid import BATCH, H0, SIZES, TILE, W0, _model
+
+pytestmark = pytest.mark.gpu
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+GUARD = 64                                   # bytes on either side of an output and around an input
+U8_GUARD, U8_FILL, U8_PAD = 0xCD, 0x5A, 0xEE
+_CACHE = {}
+
+
+class Out:
+    """n bytes between guards inside one device allocation, `offset` bytes past a 16-byte aligned point, the interior
+    pre-filled with `fill` (0xCD guards)."""
+
+    def __init__(self, n, fill=U8_FILL, offset=0):
+        self.n, self.lo = int(n), GUARD + offset
+        host = np.full(self.lo + self.n + GUARD, U8_GUARD, dtype=np.uint8)
+        host[self.lo:self.lo + self.n] = fill
+        self.buf = torch.from_numpy(host).cuda()
+        self.view = self.buf[self.lo:self.lo + self.n]
+
+    def host(self, what):
+        """The interior on the host, after the guards have been checked."""
+        a = self.buf.cpu().numpy()
+        g = np.concatenate([a[:self.lo], a[self.lo + self.n:]])
+        assert (g == U8_GUARD).all(), f"{what}: guard overwritten"
+        return a[self.lo:self.lo + self.n]
+
+
+def _inside(arr, offset):
+    """The array's bytes on the device, `offset` bytes past an aligned point of a larger allocation."""
+    flat = np.ascontiguousarray(arr).view(np.uint8).ravel()
+    host = np.full(GUARD + offset + flat.size + GUARD, U8_PAD, dtype=np.uint8)
+    host[GUARD + offset:GUARD + offset + flat.size] = flat
+    return torch.from_numpy(host).cuda()[GUARD + offset:GUARD + offset + flat.size]
+
+
+def _same(got, want, what, item=1):
+    """bit for bit; `item` bytes to an element in the message"""
+    got, want = np.ascontiguousarray(got).view(np.uint8).ravel(), np.ascontiguousarray(want).view(np.uint8).ravel()
+    assert got.size == want.size, (what, got.size, want.size)
+    if got.tobytes() != want.tobytes():
+        bad = np.flatnonzero((got != want).reshape(-1, item).any(axis=1))
+        i = int(bad[0])
+        raise AssertionError(f"{what}: {bad.size} of {got.size // item} elements differ, first at {i}: got "
+                             f"{got[i * item:(i + 1) * item].tolist()}, want {want[i * item:(i + 1) * item].tolist()}")
+
+
+def _lohi(scale):
+    flat = [v for pair in scale for v in pair]
+    return (ctypes.c_uint32 * len(flat))(*flat)
+
+
+def _eq(a, b):
+    """torch.equal with the dtype and the shape; uint16 tensors are compared through their int16 views"""
+    if a.dtype != b.dtype or a.shape != b.shape:
+        return False
+    return torch.equal(a.view(torch.int16), b.view(torch.int16)) if a.dtype == torch.uint16 else torch.equal(a, b)
+
+
+def _i32(values):
+    return torch.tensor(np.asarray(values, dtype=np.int32).ravel(), dtype=torch.int32, device="cuda")
+
+
+# ---- the kernels ----------------------------------------------------------------------------------------------------
+SHAPES = [(32, 32, 32), (40, 70, 32), (64, 100, 48), (300, 280, 272)]
+
+
+def _scales(C):
+    """the full range; a narrow pair per band that clips both ways; R == 0 on band 1"""
+    narrow = [(20000, 40000), (1, 65534), (30000, 30001), (12345, 12400)][:C]
+    flat = [(0, 65535), (7000, 7000), (100, 60000), (0, 1)][:C]
+    return {"full": [(0, 65535)] * C, "narrow": narrow, "flat": flat}
+
+
+def _kernel_image(H, W, C):
+    rng = np.random.default_rng(H * 1009 + W * 17 + C)
+    img = rng.integers(0, 65536, size=(H, W, C), dtype=np.uint16)
+    img[0, 0] = 0
+    img[-1, -1] = 65535
+    img[H // 2, W // 2] = [30000, 30001, 12345, 7000][:C]
+    return img
+
+
+def _tiles_for_stitch(n, C, th, tw, rng):
+    """float32 [n][C][th][tw] in [-0.2, 1.2] with a NaN, a -0.0, a 1.0 and values a hair off 0.5 in every tile"""
+    x = rng.uniform(-0.2, 1.2, size=(n, C, th, tw)).astype(np.float32)
+    x[:, :, 0, 0] = np.nan
+    x[:, :, 0, 1] = -0.0
+    x[:, :, 1, 0] = 1.0
+    x[:, :, 1, 1] = np.nextafter(np.float32(0.5), np.float32(0))
+    x[:, :, -1, -1] = np.nextafter(np.float32(0.5), np.float32(1))
+    return x
+
+
+@pytest.mark.parametrize("H,W,tile", SHAPES)
+@pytest.mark.parametrize("C", [3, 4])
+def test_gather_stitch_and_finish_equal_the_restatement(H, W, tile, C):
+    L = lib.load()
+    th, tw = min(tile, codec_ref.ceil16(H)), min(tile, codec_ref.ceil16(W))
+    img = _kernel_image(H, W, C)
+    rng = np.random.default_rng(H + W + C)
+    g = codec_ref.grid(H, W, th, tw)
+    n = g["n"]
+    run = 0
+    for name, scale in _scales(C).items():
+        off = 2 * (run % 2)                                              # the input 0 and 2 bytes past a 16-byte boundary
+        run += 1
+        what = f"{H}x{W}x{C} tile {tile} scale {name}, input offset {off}"
+        d_img, lohi = _inside(img, off), _lohi(scale)
+        # 1. gather, all tiles and a (first, n) slice of them: the tiles gather_f32 cuts from norm(img)
+        want = R.gather(img, th, tw, scale)
+        _same(want, codec_ref.gather_f32(R.norm_image(img, scale), th, tw), what + " restatement", 4)
+        out = Out(want.nbytes)
+        lib.check(L.dsic_tile_gather_u16(_p(d_img), _p(out.view), H, W, C, th, tw, lohi, 0, n, _stream()), what)
+        _same(out.host(what + " gather"), want, what + " gather", 4)
+        if n > 1:
+            out = Out(want[1:].nbytes)
+            lib.check(L.dsic_tile_gather_u16(_p(d_img), _p(out.view), H, W, C, th, tw, lohi, 1, n - 1, _stream()), what)
+            _same(out.host(what + " gather from tile 1"), want[1:], what + " gather from tile 1", 4)
+            # overlap 16: more tiles, other origins
+            ay, ax = blend_ref.axis(H, th, 16), blend_ref.axis(W, tw, 16)
+            n_ov = ay["n"] * ax["n"]
+            want_ov = R.gather(img, th, tw, scale, 16)
+            assert want_ov.shape[0] == n_ov >= n
+            out = Out(want_ov.nbytes)
+            lib.check(L.dsic_tile_gather_u16_ov(_p(d_img), _p(out.view), H, W, C, th, tw, 16, lohi, 0, n_ov, _stream()),
+                      what)
+            _same(out.host(what + " gather_ov"), want_ov, what + " gather_ov", 4)
+            out = Out(want_ov[n_ov - 1:].nbytes)
+            lib.check(L.dsic_tile_gather_u16_ov(_p(d_img), _p(out.view), H, W, C, th, tw, 16, lohi, n_ov - 1, 1,
+                                                _stream()), what)
+            _same(out.host(what + " gather_ov last"), want_ov[n_ov - 1:], what + " gather_ov last", 4)
+        # 2. stitch: the whole image and a window that cuts tiles; two numbers outside the grid; the output at
+        # offsets that move its ragged ends
+        tiles = _tiles_for_stitch(n + 2, C, th, tw, rng)
+        ids = list(range(n)) + [n, -1]
+        order = rng.permutation(n + 2)
+        tiles, ids = tiles[order], [ids[k] for k in order]
+        d_tiles, d_ids = torch.from_numpy(tiles).cuda(), _i32(ids)
+        windows = [(0, 0, H, W), (H // 3, W // 4, H // 2 + 1, W // 2 + 3), (H - 1, W - 1, 1, 1)]
+        for win, out_off in zip(windows, (off, 6, 14)):
+            wy, wx, wh, ww = win
+            o = Out(2 * wh * ww * C, offset=out_off)
+            lib.check(L.dsic_tile_stitch_window_u16(_p(d_tiles), _p(d_ids), n + 2, _p(o.view), H, W, C, th, tw, wy, wx,
+                                                    wh, ww, lohi, _stream()), what)
+            want = R.stitch(tiles, ids, H, W, th, tw, win, scale, U8_FILL * 0x0101)
+            _same(o.host(f"{what} stitch {win}"), want, f"{what} stitch {win}, output offset {out_off}", 2)
+        # a call that holds only some tiles leaves the others' pixels alone
+        if n > 1:
+            o = Out(2 * H * W * C)
+            lib.check(L.dsic_tile_stitch_window_u16(_p(d_tiles[:2]), _p(d_ids[:2]), 2, _p(o.view), H, W, C, th, tw, 0, 0,
+                                                    H, W, lohi, _stream()), what)
+            _same(o.host(what + " stitch two"), R.stitch(tiles[:2], ids[:2], H, W, th, tw, (0, 0, H, W), scale,
+                                                         U8_FILL * 0x0101), what + " stitch two", 2)
+        # 3. blend finish over a canvas of the partial window's size
+        _, _, wh, ww = windows[1]
+        canvas = rng.uniform(-0.1, 1.3, size=(C, wh, ww)).astype(np.float32)
+        canvas[:, 0, 0] = np.nan
+        canvas[:, -1, -1] = 1.0
+        canvas[:, 0, -1] = np.nextafter(np.float32(1), np.float32(2))
+        d_canvas = torch.from_numpy(canvas).cuda()
+        for out_off in (0, 2, 10):
+            o = Out(2 * wh * ww * C, offset=out_off)
+            lib.check(L.dsic_tile_blend_finish_u16(_p(d_canvas), _p(o.view), C, wh, ww, lohi, _stream()), what)
+            _same(o.host(what + " finish"), R.blend_finish(canvas, scale), f"{what} finish, output offset {out_off}", 2)
+    # 4. gather, then stitch, with no model between: the image itself when it lies inside the scale
+    for scale in ([(0, 65535)] * C, R.band_range(img)):
+        lohi = _lohi(scale)
+        d_img = _inside(img, 2)
+        tiles = torch.empty((n, C, th, tw), dtype=torch.float32, device="cuda")
+        lib.check(L.dsic_tile_gather_u16(_p(d_img), _p(tiles), H, W, C, th, tw, lohi, 0, n, _stream()), "gather")
+        o = Out(2 * H * W * C, offset=2)
+        lib.check(L.dsic_tile_stitch_window_u16(_p(tiles), _p(_i32(range(n))), n, _p(o.view), H, W, C, th, tw, 0, 0, H, W,
+                                                lohi, _stream()), "stitch")
+        _same(o.host("round trip"), img, f"{H}x{W}x{C} gather then stitch, scale {scale}", 2)
+
+
+@pytest.mark.parametrize("H,W", SIZES)
+@pytest.mark.parametrize("C", [1, 3, 4])
+def test_halving_equals_the_restatement(H, W, C):
+    L = lib.load()
+    rng = np.random.default_rng(H * 100003 + W * 101 + C)
+    img = rng.integers(0, 65536, size=(H, W, C), dtype=np.uint16)
+    img[:2, :2] = 65535                                                  # four times 65535 + 2 needs more than 16 bits
+    img[-1:, -2:] = 0
+    want = R.halve(img)
+    assert want.shape == ((H + 1) // 2, (W + 1) // 2, C)
+    for off, out_off in zip((0, 2, 0, 2), (0, 2, 6, 14)):
+        src = _inside(img, off)
+        out = Out(want.nbytes, offset=out_off)
+        lib.check(L.dsic_image_halve_u16(_p(src), _p(out.view), H, W, C, _stream()), "image_halve_u16")
+        what = f"image_halve_u16 {H}x{W}x{C}, input offset {off}, output offset {out_off}"
+        _same(out.host(what), want, what, 2)
+
+
+def test_halving_refuses_overlapping_images():
+    L = lib.load()
+    buf = torch.zeros(4096, dtype=torch.uint8, device="cuda")
+    assert L.dsic_image_halve_u16(_p(buf), _p(buf[80:]), 4, 4, 3, _stream()) == lib.DSIC_EINVAL
+    with pytest.raises(ValueError, match="overlap"):
+        lib.check(L.dsic_image_halve_u16(_p(buf[16:]), _p(buf), 4, 4, 3, _stream()), "image_halve_u16")
+    assert not bool(buf.any())
+
+
+@pytest.mark.parametrize("H,W", [(1, 1), (1, 7), (33, 65), (300, 280)])
+@pytest.mark.parametrize("C", [1, 3, 4])
+def test_band_range_equals_numpy_and_normalize_bands(H, W, C):
+    L = lib.load()
+    rng = np.random.default_rng(H * 31 + W * 7 + C)
+    for plant in ("first", "last", "mid"):
+        img = rng.integers(1000, 60000, size=(H, W, C), dtype=np.uint16)
+        y, x = {"first": (0, 0), "last": (H - 1, W - 1), "mid": (H // 2, W // 2)}[plant]
+        for c in range(C):                                               # the minimum there in even bands, the maximum in odd
+            img[y, x, c] = 3 + c if c % 2 == 0 else 65535 - c
+        if H * W > 1:
+            yy, xx = {"first": (H - 1, W - 1), "last": (0, 0), "mid": (H // 2, (W // 2 + 1) % W)}[plant]
+            if (yy, xx) != (y, x):
+                for c in range(C):
+                    img[yy, xx, c] = 65535 - c if c % 2 == 0 else 3 + c
+        want = R.band_range(img)
+        for off in (0, 2):
+            what = f"band_range {H}x{W}x{C} {plant}, input offset {off}"
+            out = Out(8 * C, fill=0x77)
+            lib.check(L.dsic_band_range_u16(_p(_inside(img, off)), H, W, C, _p(out.view), _stream()), what)
+            got = out.host(what).view("<u4").tolist()
+            assert list(zip(got[0::2], got[1::2])) == want, what
+        assert codec.band_range(torch.from_numpy(img).cuda()) == want
+        # the reference's own normalisation (dsic_normalize_bands) takes the same minimum and maximum
+        planes = torch.from_numpy(np.ascontiguousarray(img.transpose(2, 0, 1)).astype(np.float32)[None]).cuda()
+        _same(evaluate.combine_bands(planes)[0].cpu().numpy(), R.norm_image(img, want), f"normalize_bands {H}x{W}x{C}", 4)
+
+
+# ---- the codec --------------------------------------------------------------------------------------------------------
+ARGS = {"tile": TILE, "batch": BATCH}
+OFFSETS, SPANS = (100, 1000, 0), (9900, 30000, 65535)
+EXPLICIT = [(0, 10000), (5000, 25000), (0, 65535)]                      # band 1 clips at both ends
+
+
+def _scene():
+    """(the 330 x 530 scene as uint16 [H,W,3], its own scale), read-only"""
+    if "scene" not in _CACHE:
+        x = S.make_patches(21, 1, H0, W0, 3)[0].astype(np.float64)       # [3, H, W] in [0, 1]
+        img = np.stack([(o + x[c] * s + 0.5).astype(np.uint16) for c, (o, s) in enumerate(zip(OFFSETS, SPANS))], axis=2)
+        img = np.ascontiguousarray(img)
+        img.setflags(write=False)
+        _CACHE["scene"] = (img, R.band_range(img))
+    return _CACHE["scene"]
+
+
+def _dev(a):
+    return torch.from_numpy(np.array(a)).cuda()
+
+
+def _u16_stream(scale=None, **kw):
+    key = ("u16", None if scale is None else tuple(scale), tuple(sorted(kw.items())))
+    if key not in _CACHE:
+        _CACHE[key] = codec.compress_image(_model(), _dev(_scene()[0]), scale=scale, **ARGS, **kw)
+    return _CACHE[key]
+
+
+def _f32_stream(scale=None, **kw):
+    """the float32 [C,H,W] image norm(img) compressed with the same arguments"""
+    key = ("f32", None if scale is None else tuple(scale), tuple(sorted(kw.items())))
+    if key not in _CACHE:
+        img, own = _scene()
+        _CACHE[key] = codec.compress_image(_model(), _dev(R.norm_image(img, scale or own)), **ARGS, **kw)
+    return _CACHE[key]
+
+
+def _decoded(which, scale=None, out=None, **kw):
+    key = ("decoded", which, None if scale is None else tuple(scale), out, tuple(sorted(kw.items())))
+    if key not in _CACHE:
+        stream = _u16_stream(scale, **kw) if which == "u16" else _f32_stream(scale, **kw)
+        _CACHE[key] = codec.decompress_image(_model(), stream, out=out)
+    return _CACHE[key]
+
+
+@pytest.mark.parametrize("scale,kw", [(None, {}), (EXPLICIT, {}), (None, {"segments": 4}), (None, {"overlap": 16})])
+def test_the_containers_are_those_of_the_float32_stream_of_the_normalised_image(scale, kw):
+    img, own = _scene()
+    u, f = codec.unpack_image_stream(_u16_stream(scale, **kw)), codec.unpack_image_stream(_f32_stream(scale, **kw))
+    assert u["version"] == 6 and u["kind"] == 2 and u["scale"] == [tuple(p) for p in (scale or own)]
+    assert f["kind"] == 1 and f["version"] == (3 if kw.get("overlap") else 2 if kw.get("segments") else 1)
+    assert len(u["blobs"]) == len(f["blobs"]) == -(-codec.tile_grid(H0, W0, TILE, kw.get("overlap", 0))["n"] // BATCH)
+    assert u["blobs"] == f["blobs"]
+    for key in ("H", "W", "C", "th", "tw", "N", "M", "batch", "batches", "segments", "overlap", "numerics"):
+        assert u[key] == f[key], key
+    if scale is None and not kw:                                         # the image may come from the host
+        assert codec.compress_image(_model(), torch.from_numpy(np.array(img)), **ARGS) == _u16_stream()
+        assert codec.compress_image(_model(), _dev(img), scale=own, **ARGS) == _u16_stream()
+
+
+@pytest.mark.parametrize("scale,kw", [(None, {}), (EXPLICIT, {}), (None, {"overlap": 16}), (EXPLICIT, {"overlap": 16})])
+def test_the_decode_is_denorm_of_the_float32_streams_decode(scale, kw):
+    img, own = _scene()
+    got = _decoded("u16", scale, **kw)
+    assert got.dtype == torch.uint16 and tuple(got.shape) == (H0, W0, 3) and got.is_cuda
+    x = _decoded("f32", scale, out="f32", **kw).cpu().numpy()
+    _same(got.cpu().numpy(), R.denorm_image(x, scale or own), f"decode {scale} {kw}", 2)
+    assert _eq(codec.decompress_image(_model(), _u16_stream(scale, **kw), out="u16"), got)
+    for out in ("u8", "f32"):                                           # the normalised image, through the existing paths
+        assert _eq(_decoded("u16", scale, out=out, **kw), _decoded("f32", scale, out=out, **kw)), out
+    lo = np.array([p[0] for p in (scale or own)])
+    hi = np.array([p[1] for p in (scale or own)])
+    a = got.cpu().numpy()
+    assert (a >= lo).all() and (a <= hi).all()
+    with pytest.raises(ValueError, match="out='u16' needs the scale"):
+        codec.decompress_image(_model(), _f32_stream(scale, **kw), out="u16")
+
+
+def _crop(full, win):
+    y0, x0, h, w = win
+    return full[y0:y0 + h, x0:x0 + w] if full.dtype == torch.uint16 else full[:, y0:y0 + h, x0:x0 + w]
+
+
+WINDOWS = [(0, 0, 1, 1), (H0 - 1, W0 - 1, 1, 1), (0, 0, H0, W0), (10, 20, 100, 150), (120, 250, 140, 200),
+           (300, 3, 30, 520), (127, 127, 2, 2)]
+
+
+@pytest.mark.parametrize("kw", [{}, {"overlap": 16}])
+def test_a_region_is_the_crop_of_the_whole_image(kw):
+    model, stream = _model(), _u16_stream(**kw)
+    full = {out: _decoded("u16", out=out, **kw) for out in (None, "f32")}
+    for win in WINDOWS:
+        for batch in (1, 3, 64):
+            stats = {}
+            got = codec.decompress_region(model, stream, *win, batch=batch, stats=stats)
+            assert got.dtype == torch.uint16 and _eq(got, _crop(full[None], win)), (win, batch)
+        assert _eq(codec.decompress_region(model, stream, *win, out="f32"), _crop(full["f32"], win)), win
+        f = io.BytesIO(stream)
+        stats = {}
+        assert _eq(codec.decompress_region(model, f, *win, out="u16", stats=stats), _crop(full[None], win))
+        ix = codec.stream_index(stream)
+        assert stats["bytes_read"] == ix["index_bytes"] + sum(n for _, n in codec.tile_spans(ix, stats["tiles"]))
+        if len(stats["tiles"]) < ix["grid"]["n"]:
+            assert stats["bytes_read"] < len(stream), win
+
+
+def test_overviews_share_the_scale_of_level_0():
+    model = _model()
+    img, own = _scene()
+    want = R.chain(img, 2)
+    got = codec.build_overviews(_dev(img), 2)
+    assert [tuple(g.shape) for g in got] == [w.shape for w in want]
+    for l, (g, w) in enumerate(zip(got, want)):
+        assert g.dtype == torch.uint16 and g.is_cuda and g.is_contiguous()
+        _same(g.cpu().numpy(), w, f"level {l}", 2)
+    for scale in (None, EXPLICIT):
+        stream = codec.compress_image(model, _dev(img), overviews=2, scale=scale, **ARGS)
+        levels = codec.unpack_pyramid_stream(stream)["levels"]
+        assert stream[:6] == b"DSICP\0" and len(levels) == 3
+        for l, lv in enumerate(levels):
+            alone = codec.compress_image(model, _dev(want[l]), scale=scale or own, **ARGS)
+            assert lv["stream"] == alone, f"level {l}"
+            h = codec.unpack_image_stream(lv["stream"])
+            assert h["version"] == 6 and h["scale"] == [tuple(p) for p in (scale or own)]
+            dec = codec.decompress_image(model, stream, level=l)
+            assert dec.dtype == torch.uint16 and tuple(dec.shape) == want[l].shape
+            assert _eq(dec, codec.decompress_image(model, alone))
+            assert codec.stream_index(stream, level=l)["scale"] == h["scale"]
+        assert levels[0]["stream"] == _u16_stream(scale)
+        win = codec.level_window(1, 100, 200, 64, 64)
+        assert _eq(codec.decompress_region(model, stream, *win, level=1),
+                           _crop(codec.decompress_image(model, stream, level=1), win))
+
+
+def test_command_line_round_trip(tmp_path):
+    import test_gpu_pyramid as TP
+    model = _model()
+    sd = TP._CACHE[("model", 3, 128, 192)][1]
+    torch.save({"model": {k: torch.from_numpy(v) for k, v in sd.items()}}, tmp_path / "ckpt.pt")
+    x = S.make_patches(71, 1, 150, 170, 3)[0].astype(np.float64)
+    u16 = np.ascontiguousarray((200 + x * 9000.0 + 0.5).astype(np.uint16).transpose(1, 2, 0))
+    np.save(tmp_path / "in.npy", u16)
+    tool = os.path.join(ROOT, "tools", "dsic_image.py")
+    w = ["--weights", str(tmp_path / "ckpt.pt")]
+    region = (5, 6, 20, 30)
+    runs = (["compress", str(tmp_path / "in.npy"), str(tmp_path / "s.dsic"), "--tile", "64", "--batch", "4",
+             "--scale", "0,10000"] + w,
+            ["info", str(tmp_path / "s.dsic")],
+            ["decompress", str(tmp_path / "s.dsic"), str(tmp_path / "win.npy"), "--out", "u16", "--region",
+             ",".join(str(v) for v in region)] + w)
+    outs = []
+    for args in runs:
+        r = subprocess.run([sys.executable, tool, *args], cwd=ROOT, capture_output=True, text=True, timeout=600)
+        assert r.returncode == 0, r.stdout + r.stderr
+        outs.append(r.stdout)
+    stream = codec.compress_image(model, torch.from_numpy(u16), tile=64, batch=4, scale=[(0, 10000)] * 3)
+    assert (tmp_path / "s.dsic").read_bytes() == stream
+    full = codec.decompress_image(model, stream).cpu().numpy()
+    win = np.load(tmp_path / "win.npy")
+    assert win.dtype == np.uint16 and np.array_equal(win, full[5:25, 6:36])
+    assert "uint16 HWC" in outs[1] and "scale (lo, hi) per band: (0, 10000), (0, 10000), (0, 10000)" in outs[1], outs[1]
+    assert "stream version 6" in outs[1]
+    # a uint16 result goes to .npy only: refused from the stream's head, before the model is loaded
+    r = subprocess.run([sys.executable, tool, "decompress", str(tmp_path / "s.dsic"), str(tmp_path / "x.png")] + w,
+                       cwd=ROOT, capture_output=True, text=True, timeout=600)
+    assert r.returncode != 0 and "uint16 image is written as .npy only" in r.stderr and not (tmp_path / "x.png").exists()

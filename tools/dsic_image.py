@@ -2,8 +2,8 @@
 an image.
 
     python tools/dsic_image.py compress   --weights CKPT.pt IN.png  OUT.dsic [--tile 256] [--batch 64] [--segments K] [--overlap O]
-                                          [--max-error T] [--overviews N] [--nodata V]
-    python tools/dsic_image.py decompress --weights CKPT.pt IN.dsic OUT.png [--out u8|f32] [--region Y0,X0,H,W]
+                                          [--max-error T] [--overviews N] [--nodata V] [--scale LO,HI[,LO,HI...]]
+    python tools/dsic_image.py decompress --weights CKPT.pt IN.dsic OUT.png [--out u8|f32|u16] [--region Y0,X0,H,W]
                                           [--level L]
     python tools/dsic_image.py info       IN.dsic
 
@@ -20,10 +20,15 @@ levels of a DSICP stream (size, bytes, tiles), then level 0.
 --nodata V (0 .. 255, uint8 images; not with --overlap, --max-error or --overviews) keeps the mask of the pixels whose
 channels all equal V exactly (a version-5 stream): tiles that hold nothing else are not coded at all, and every such
 pixel decodes to V again.  info prints the value, the counts of empty, full and mixed tiles and the mask block's bytes.
+A .npy of dtype uint16 [H,W,C] (16-bit imagery, up to 4 bands; not with --max-error or --nodata) is a version-6 stream
+that carries a per-band scale: --scale LO,HI for all bands or LO,HI,LO,HI,... one pair per band, by default each band's
+own minimum and maximum; values outside a pair clip.  Such a stream decodes to uint16 again (--out u16 says so
+explicitly and is refused for any other stream; --out u8 / f32 give the normalised image), written as .npy only; info
+prints the scale.
 
 The state dict is loaded plain or from under "model" (code/modelv2/eval_selfcontained_entropy.py:130-134); the model's
 N, M, input channels and spatial_params are read from its shapes.  Images are PNG through PIL when PIL is importable
-(RGB, or RGBA for 4-channel models), .npy otherwise: uint8 [H,W,C], or float32 [C,H,W] in [0,1].  A decoded uint8
+(RGB, or RGBA for 4-channel models), .npy otherwise: uint8 or uint16 [H,W,C], or float32 [C,H,W] in [0,1].  A decoded uint8
 image is (uint8)(clamp(x,0,1)*255), as torchvision's to_pil_image writes the reference's reconstruction (:157).
 """
 from __future__ import annotations
@@ -77,6 +82,8 @@ def read_image(path, channels):
 def write_image(path, img):
     import numpy as np
     a = img.cpu().numpy()
+    if a.dtype == np.uint16 and not path.endswith(".npy"):
+        raise SystemExit(f"{path}: a uint16 image is written as .npy only")
     if path.endswith(".npy") or not _has_pil() or a.dtype != np.uint8:
         if not path.endswith(".npy"):
             path += ".npy"
@@ -87,12 +94,23 @@ def write_image(path, img):
     return path
 
 
+def scale_pairs(text, channels):
+    """--scale's text -> [(lo, hi)] * channels: "LO,HI" for all bands, or one pair per band; ValueError otherwise."""
+    values = [int(v) for v in text.split(",")]
+    if len(values) == 2:
+        return [tuple(values)] * channels
+    if len(values) != 2 * channels:
+        raise ValueError(f"--scale {text}: one pair LO,HI for all bands, or {channels} pairs for the model's "
+                         f"{channels} bands")
+    return list(zip(values[0::2], values[1::2]))
+
+
 def print_info(ix):
     """stream_index's dict as text: geometry, tile grid, and bytes / bpp of every batch (bpp over the pixels its tiles
     own).  For a level of a DSICP stream the bytes and bpp of the first line are the whole pyramid's over the pixels
     of that level."""
     g = ix["grid"]
-    kind = {0: "uint8 HWC", 1: "float32 CHW"}.get(ix["kind"], f"kind {ix['kind']}")
+    kind = {0: "uint8 HWC", 1: "float32 CHW", 2: "uint16 HWC"}.get(ix["kind"], f"kind {ix['kind']}")
     print(f"[dsic_image] {ix['H']}x{ix['W']}x{ix['C']} {kind}, {ix['stream_bytes']} bytes, "
           f"{8.0 * ix['stream_bytes'] / (ix['H'] * ix['W']):.4f} bpp, numerics tag {ix['numerics']:#x}")
     print(f"[dsic_image] model N={ix['N']} M={ix['M']} in_ch={ix['in_ch']} spatial_params={ix['spatial_params']}")
@@ -108,6 +126,8 @@ def print_info(ix):
         states = [t["state"] for t in ix["tiles"]]
         print(f"[dsic_image] nodata {ix['nodata']}: {states.count(0)} empty, {states.count(1)} full, "
               f"{states.count(2)} mixed tile(s), {ix['coded']} coded; mask block {ix['mask_bytes']} bytes")
+    if ix.get("scale") is not None:
+        print("[dsic_image] scale (lo, hi) per band: " + ", ".join(f"({lo}, {hi})" for lo, hi in ix["scale"]))
     for k, c in enumerate(ix["containers"]):
         pixels = 0
         held = c.get("ids", range(c["first"], c["first"] + c["tiles"]))   # the tiles the batch really holds
@@ -131,7 +151,11 @@ def main(argv=None):
     ap.add_argument("--overlap", type=int, default=0, help="compress: pixels neighbouring tiles share and cross-fade")
     ap.add_argument("--max-error", type=int, default=None, metavar="T",
                     help="compress: near-lossless, every decoded pixel within T (0 .. 127) of the original; 0 = lossless")
-    ap.add_argument("--out", choices=("u8", "f32"), default=None, help="decoded kind (default: the encoder's input's)")
+    ap.add_argument("--out", choices=("u8", "f32", "u16"), default=None,
+                    help="decoded kind (default: the encoder's input's; u16 only for a uint16 stream)")
+    ap.add_argument("--scale", default=None, metavar="LO,HI[,LO,HI...]",
+                    help="compress, uint16 images: the (lo, hi) that map to 0 and 1, one pair for all bands or one per "
+                         "band (default: each band's minimum and maximum)")
     ap.add_argument("--region", default=None, metavar="Y0,X0,H,W", help="decompress: only this window of the image")
     ap.add_argument("--overviews", type=int, default=0, metavar="N",
                     help="compress: store N halved levels beside the image (a DSICP stream)")
@@ -162,11 +186,23 @@ def main(argv=None):
             region = []
         if a.mode != "decompress" or len(region) != 4:
             ap.error("--region Y0,X0,H,W (four integers) goes with decompress")
+    if a.scale is not None and a.mode != "compress":
+        ap.error("--scale goes with compress")
+    if a.mode == "decompress" and not a.dst.endswith(".npy"):
+        with open(a.src, "rb") as f:                                       # the heads only: no model, no GPU
+            if a.out == "u16" or (a.out is None and codec.stream_index(f, level=a.level)["kind"] == codec.KIND_U16_HWC):
+                ap.error(f"{a.dst}: a uint16 image is written as .npy only")
     model = load_model(a.weights, a.min_nu, a.max_nu)
     if a.mode == "compress":
-        img = read_image(a.src, codec._model_shape(model)[2])
+        in_ch = codec._model_shape(model)[2]
+        img = read_image(a.src, in_ch)
+        try:
+            scale = None if a.scale is None else scale_pairs(a.scale, in_ch)
+        except ValueError as e:
+            ap.error(str(e) if "--scale" in str(e) else f"--scale {a.scale}: integers LO,HI[,LO,HI...]")
         stream = codec.compress_image(model, img, tile=a.tile, batch=a.batch, tail=a.tail, segments=a.segments,
-                                      overlap=a.overlap, max_error=a.max_error, overviews=a.overviews, nodata=a.nodata)
+                                      overlap=a.overlap, max_error=a.max_error, overviews=a.overviews, nodata=a.nodata,
+                                      scale=scale)
         with open(a.dst, "wb") as f:
             f.write(stream)
         if a.overviews:
@@ -179,7 +215,8 @@ def main(argv=None):
         print(f"[dsic_image] {h['H']}x{h['W']}x{h['C']} -> {len(stream)} bytes, {codec.image_bpp(stream):.4f} bpp, "
               f"{h['batches']} batch(es) of {h['th']}x{h['tw']} tiles, {h['segments']} segment(s) per y string, "
               f"overlap {h['overlap']}" + (f", max_error {h['max_error']}" if "max_error" in h else "")
-              + (f", nodata {h['nodata']}: {h['coded']} coded tile(s)" if "nodata" in h else ""))
+              + (f", nodata {h['nodata']}: {h['coded']} coded tile(s)" if "nodata" in h else "")
+              + (f", scale {h['scale']}" if "scale" in h else ""))
     elif region is not None:
         stats = {}
         with open(a.src, "rb") as f:

@@ -33,6 +33,12 @@ Every figure is the best of --reps full passes over the scene after one warm-up 
           one full tile in ms, and the classify pass alone.  Written to profiles/nodata_bench.json (or --json).
           Records, not bars.
 
+--u16     16-bit imagery: the scene as uint8 and as uint16 [H,W,3] (another offset and span per band; stream version 6),
+          once with scale=None (one more pass over the scene, dsic_band_range_u16) and once with the scale given, read
+          alternately in one run (medians of --reps readings): stream bytes, compress_image / decompress_image and a
+          four-tile decompress_region in ms, and the band-range pass alone.  Written to profiles/u16_bench.json (or
+          --json).  Records, not bars.
+
 --region  decompress_region of the same stream for an aligned one-tile window, an unaligned 2 x 2-tile-sized window
           (9 tiles), an unaligned half-scene window and the whole image, beside decompress_image before and after
           them in the same run (the two readings show the run-to-run spread).  Records, not bars.
@@ -311,6 +317,53 @@ def nodata_records(model, img, a):
     return res
 
 
+def u16_records(model, scene01, img_u8, a):
+    """The scene as uint8 and as uint16 (another offset and span per band), coded and decoded alternately; uint16 with
+    the bands' own range (one more pass over the scene, dsic_band_range_u16) and with the caller's scale."""
+    import statistics
+    import numpy as np
+    import torch
+    from dsic_amd import codec
+    t, size = a.tile, a.size
+    offs, spans = (100.0, 1000.0, 0.0), (9900.0, 30000.0, 65535.0)
+    img16 = torch.from_numpy(np.stack([(o + scene01[..., c].astype(np.float64) * s + 0.5).astype(np.uint16)
+                                       for c, (o, s) in enumerate(zip(offs, spans))], axis=2)).cuda()
+    own = codec.band_range(img16)
+    modes = {"uint8": (img_u8, {}), "uint16, scale=None": (img16, {}), "uint16, scale given": (img16, {"scale": own})}
+    streams = {m: codec.compress_image(model, x, tile=t, batch=a.batch, **kw) for m, (x, kw) in modes.items()}
+    assert streams["uint16, scale=None"] == streams["uint16, scale given"], "the band range is not the scale written"
+    win = (size // 2 - t // 2, size // 2 - t // 2, t, t)                # meets four tiles
+    jobs = {"compress_image": lambda m: codec.compress_image(model, modes[m][0], tile=t, batch=a.batch, **modes[m][1]),
+            "decompress_image": lambda m: codec.decompress_image(model, streams[m]),
+            "decompress_region": lambda m: codec.decompress_region(model, streams[m], *win, batch=a.batch)}
+    reads = {name: {m: [] for m in modes} for name in jobs}
+    for name, job in jobs.items():
+        for m in modes:
+            job(m)                                                     # warm-up
+        torch.cuda.synchronize()
+        for _ in range(a.reps):
+            for m in modes:
+                t0 = time.perf_counter()
+                job(m)
+                torch.cuda.synchronize()
+                reads[name][m].append(1e3 * (time.perf_counter() - t0))
+    rng = [1e3 * v for v in _times(lambda: codec.band_range(img16), a.reps)]
+    res = {"what": "the scene as uint8 and as uint16, read alternately in one run on one MI355X; medians",
+           "scene": f"{size}x{size}x3", "tile": t, "batch": a.batch, "reps": a.reps, "scale": [list(p) for p in own],
+           "window_y0_x0_h_w": list(win),
+           "band_range": {"ms_median": round(statistics.median(rng), 3), "ms_all": [round(v, 3) for v in rng],
+                          "what": "dsic_band_range_u16 and the copy of the 2 C words, wall clock",
+                          "image_GB_per_s": round(2 * img16.numel() / statistics.median(rng) / 1e6, 1)},
+           "modes": {}}
+    for m in modes:
+        rec = {"stream_bytes": len(streams[m]), "bpp": round(codec.image_bpp(streams[m]), 4)}
+        for name in jobs:
+            rec[name] = {"ms_median": round(statistics.median(reads[name][m]), 3),
+                         "ms_all": [round(v, 3) for v in reads[name][m]]}
+        res["modes"][m] = rec
+    return res
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--size", type=int, default=4096)
@@ -326,6 +379,8 @@ def main():
                     help="measure near-lossless streams (max_error = T) against the lossy stream, alternately")
     ap.add_argument("--nodata", action="store_true",
                     help="measure a scene with a wedge of nodata, coded without and with nodata=0, alternately")
+    ap.add_argument("--u16", action="store_true",
+                    help="measure the scene as uint16 (stream version 6) against the uint8 scene, alternately")
     a = ap.parse_args()
 
     import numpy as np
@@ -346,6 +401,12 @@ def main():
     img = torch.from_numpy(scene.astype(np.uint8)).cuda()
     n = g["n"]
 
+    if a.u16:
+        res = u16_records(model, scene / 255, img, a)
+        print(json.dumps(res))
+        with open(a.json or os.path.join(ROOT, "profiles", "u16_bench.json"), "w") as f:
+            json.dump(res, f, indent=1)
+        return
     if a.nodata:
         res = nodata_records(model, img, a)
         print(json.dumps(res))
