@@ -63,6 +63,10 @@ Level l + 1 is level l halved on the device (build_overviews: ceil(H/2) x ceil(W
 the last row or column of an odd side counted twice; uint8 and uint16 (a + b + c + d + 2) >> 2, float32 ((a + b) +
 (c + d)) * 0.25f), and every level's bytes are the DSICI stream compress_image writes for that level's image, so a level is
 read, indexed and decoded on its own (level=l of the decoders and of stream_index) through a view of its byte range.
+
+ImageReader (view.py) keeps a stream open for pan and zoom: levels opened once, decoded tiles cached on the device and
+assembled by the calls decompress_region makes (_assemble_window), requests decoded together (read_many), and windows
+resampled to a size asked for from the level view_level picks (csrc/view.hip).
 """
 from __future__ import annotations
 
@@ -970,18 +974,23 @@ def stream_index(src, level=None) -> dict:
     for a level the stream does not hold, and for a level other than 0 of a DSICI stream."""
     _, ix, base, levels = _open_level(src, level)
     if levels is not None:
-        if "mask_offset" in ix:
-            ix["mask_offset"] += base
-        for c in ix["containers"]:
-            c["offset"] += base
-            if "r_offset" in c:
-                c["r_offset"] += base
-        for t in ix["tiles"]:
-            for key in ("z_off", "y_off", "r_off", "m_off"):
-                if key in t:
-                    t[key] += base
-        ix.update(stream_bytes=levels[-1]["offset"] + levels[-1]["length"])
+        _absolute_offsets(ix, base, levels)
     return ix
+
+
+def _absolute_offsets(ix, base, levels):
+    """The index of a DSICP level, its offsets counted inside the level's bytes -> counted from the pyramid's start."""
+    if "mask_offset" in ix:
+        ix["mask_offset"] += base
+    for c in ix["containers"]:
+        c["offset"] += base
+        if "r_offset" in c:
+            c["r_offset"] += base
+    for t in ix["tiles"]:
+        for key in ("z_off", "y_off", "r_off", "m_off"):
+            if key in t:
+                t[key] += base
+    ix.update(stream_bytes=levels[-1]["offset"] + levels[-1]["length"])
 
 
 def window_tiles(index_or_grid, y0, x0, h, w) -> list:
@@ -1061,22 +1070,67 @@ def _apply_mask(source, ix, tiles, img, kind, window) -> int:
     return uploaded
 
 
-def _decode_window(model, src, window, out, batch, stats, what, level=0):
-    """decompress_region's work; window None = the whole image, batch None = the stream's tiles per container.  Of a
-    DSICP stream the chosen level is decoded, through a view of its bytes."""
+def _check_out(out, ix, what):
+    """out as the decoders take it -> the kind of the result; ix None: only whether out is a known word."""
     if out not in (None, "u8", "f32", "u16"):
         raise ValueError(f"{what}: out={out!r} (None, 'u8', 'f32' or 'u16')")
-    source, ix, _, _ = _open_level(src, level)
+    if ix is None:
+        return None
     if out == "u16" and "scale" not in ix:
         raise ValueError(f"{what}: out='u16' needs the scale of a uint16 stream (version {VERSION_U16}); this one is "
                          f"version {ix['version']}")
-    _refuse_foreign(model, ix, what)
+    return {None: ix["kind"], "u8": KIND_U8_HWC, "f32": KIND_F32_CHW, "u16": KIND_U16_HWC}[out]
+
+
+def _coded_tiles(ix, tiles):
+    """Of a window's tiles those that hold strings: all, or in a version-5 stream those that are not empty."""
+    return tiles if ix.get("nodata") is None else [t for t in tiles if ix["tiles"][t]["state"] != _mask.EMPTY]
+
+
+def _decode_tiles(model, source, ix, sel, what):
+    """One dense decode batch: the tiles `sel` (ascending) of an indexed level, their strings read from `source` in
+    one upload -> (g_s's output [n,C,th,tw], contiguous and not clamped; the padded string bytes uploaded; the device
+    copy of sel; the q planes of a version-4 stream, else None)."""
+    C, th, tw, tau = ix["C"], ix["th"], ix["tw"], ix.get("max_error")
+    N, Hz, Wz = ix["containers"][0]["shape_z"][1:] if ix["containers"] else (ix["N"], 0, 0)
+    n = len(sel)
+    # the upload is the tiles' spans back to back: a string at stream offset o lies where its span does
+    spans = tile_spans(ix, sel, masks=False)               # the mask payloads travel with _apply_mask
+    starts, base = [off for off, _ in spans], [0]
+    for _, length in spans:
+        base.append(base[-1] + length)
+
+    def at(off, length):
+        i = bisect.bisect_right(starts, off) - 1
+        return base[i] + off - starts[i] if length else 0
+
+    recs = [ix["tiles"][t] for t in sel]
+    images = [(r["min_y"], r["max_y"], r["min_z"], r["max_z"], at(r["z_off"], r["z_len"]), r["z_len"],
+               at(r["y_off"], r["y_len"]), r["y_len"]) for r in recs]
+    parts = [source.read_at(off, length) for off, length in spans]
+    spec = None
+    if tau is not None:
+        for r in recs:                         # the tables as they arrived, before anything is uploaded
+            i = bisect.bisect_right(starts, r["r_off"]) - 1
+            a = r["r_off"] - starts[i]
+            _residual.check_tables(parts[i][a:a + 2 * C * r["r_L"]], C, r["r_L"], tau)
+        spec = {"C": C, "th": th, "tw": tw, "tau": tau, "smin": [r["r_smin"] for r in recs],
+                "L": [r["r_L"] for r in recs], "segs": [r["r_segs"] for r in recs],
+                "desc": [(at(r["r_off"], r["r_len"]), 2 * C * r["r_L"],
+                          at(r["r_off"], r["r_len"]) + 2 * C * r["r_L"], sum(r["r_segs"])) for r in recs]}
+    x_hat, nbytes, ids, *q = entropy._decode_selected(model, images, parts, [n, ix["M"], th // 16, tw // 16],
+                                                      [n, N, Hz, Wz], what, ride=sel, segments=ix["segments"],
+                                                      seg_lengths=[r["y_segs"] for r in recs], residual=spec)
+    return x_hat.contiguous(), nbytes, ids, (q[0] if q else None)
+
+
+def _assemble_window(model, source, ix, tiles, window, kind, batches, what):
+    """The window image from its tiles' decoded batches.  batches yields (x_hat, padded bytes uploaded, ids, q or
+    None) as _decode_tiles returns them, the window's coded tiles in ascending order; each is stitched (blended) into
+    the window as it arrives.  Then the nodata pixels (_apply_mask) and the blend's finish.  Returns (the image, the
+    bytes uploaded, the batches taken)."""
     H, W, C, th, tw = ix["H"], ix["W"], ix["C"], ix["th"], ix["tw"]
-    y0, x0, h, w = (0, 0, H, W) if window is None else window
-    tiles = window_tiles(ix, y0, x0, h, w)
-    y0, x0, h, w = int(y0), int(x0), int(h), int(w)
-    batch = ix["batch"] if batch is None else batch
-    kind = {None: ix["kind"], "u8": KIND_U8_HWC, "f32": KIND_F32_CHW, "u16": KIND_U16_HWC}[out]
+    y0, x0, h, w = window
     lohi = (_lohi(ix["scale"]),) if kind == KIND_U16_HWC else ()        # the uint16 calls take the scale last
     tau = ix.get("max_error")                  # a residual layer: the result is the uint8 image, converted for "f32"
     img, suffix = _out_image(KIND_U8_HWC if tau is not None else kind, C, h, w, next(model.parameters()).device, what)
@@ -1084,43 +1138,11 @@ def _decode_window(model, src, window, out, batch, stats, what, level=0):
     fn = getattr(L, "dsic_tile_stitch_window_" + suffix)
     if O:       # the window's float32 canvas, zeroed: the output itself, or a temporary that the finish turns to uint8
         canvas = img.zero_() if kind == KIND_F32_CHW else torch.zeros((C, h, w), dtype=torch.float32, device=img.device)
-    v = ix.get("nodata")                       # a mask: empty tiles hold no strings, and are filled in _apply_mask
-    coded = tiles if v is None else [t for t in tiles if ix["tiles"][t]["state"] != _mask.EMPTY]
-    N, Hz, Wz = ix["containers"][0]["shape_z"][1:] if ix["containers"] else (ix["N"], 0, 0)
-    uploaded = decode_batches = 0
-    for first in range(0, len(coded), batch):
-        sel = coded[first:first + batch]
-        n = len(sel)
-        # the upload is the tiles' spans back to back: a string at stream offset o lies where its span does
-        spans = tile_spans(ix, sel, masks=False)           # the mask payloads travel with _apply_mask
-        starts, base = [off for off, _ in spans], [0]
-        for _, length in spans:
-            base.append(base[-1] + length)
-
-        def at(off, length):
-            i = bisect.bisect_right(starts, off) - 1
-            return base[i] + off - starts[i] if length else 0
-
-        recs = [ix["tiles"][t] for t in sel]
-        images = [(r["min_y"], r["max_y"], r["min_z"], r["max_z"], at(r["z_off"], r["z_len"]), r["z_len"],
-                   at(r["y_off"], r["y_len"]), r["y_len"]) for r in recs]
-        parts = [source.read_at(off, length) for off, length in spans]
-        spec = None
-        if tau is not None:
-            for r in recs:                     # the tables as they arrived, before anything is uploaded
-                i = bisect.bisect_right(starts, r["r_off"]) - 1
-                a = r["r_off"] - starts[i]
-                _residual.check_tables(parts[i][a:a + 2 * C * r["r_L"]], C, r["r_L"], tau)
-            spec = {"C": C, "th": th, "tw": tw, "tau": tau, "smin": [r["r_smin"] for r in recs],
-                    "L": [r["r_L"] for r in recs], "segs": [r["r_segs"] for r in recs],
-                    "desc": [(at(r["r_off"], r["r_len"]), 2 * C * r["r_L"],
-                              at(r["r_off"], r["r_len"]) + 2 * C * r["r_L"], sum(r["r_segs"])) for r in recs]}
-        x_hat, nbytes, ids, *q = entropy._decode_selected(model, images, parts, [n, ix["M"], th // 16, tw // 16],
-                                                          [n, N, Hz, Wz], what, ride=sel, segments=ix["segments"],
-                                                          seg_lengths=[r["y_segs"] for r in recs], residual=spec)
-        x_hat = x_hat.contiguous()
-        if q:
-            _residual.stitch_window_u8(x_hat, q[0], tau, ids, img, H, W, C, th, tw, y0, x0, h, w)
+    uploaded = taken = 0
+    for x_hat, nbytes, ids, q in batches:
+        n = x_hat.shape[0]
+        if q is not None:
+            _residual.stitch_window_u8(x_hat, q, tau, ids, img, H, W, C, th, tw, y0, x0, h, w)
         elif O:
             for c0 in range(0, n, BLEND_IDS):
                 _lib.check(L.dsic_tile_blend_window_f32(_p(x_hat[c0:]), _p(ids[c0:]), min(BLEND_IDS, n - c0),
@@ -1130,8 +1152,8 @@ def _decode_window(model, src, window, out, batch, stats, what, level=0):
             _lib.check(fn(_p(x_hat), _p(ids), n, _p(img), H, W, C, th, tw, y0, x0, h, w, *lohi, _stream()),
                        "tile_stitch_window_" + suffix)
         uploaded += nbytes
-        decode_batches += 1
-    if v is not None:
+        taken += 1
+    if ix.get("nodata") is not None:           # a mask: empty tiles hold no strings, and are filled here
         uploaded += _apply_mask(source, ix, tiles, img, kind, (y0, x0, h, w))
     if O and kind == KIND_F32_CHW:
         _lib.check(L.dsic_tile_blend_finish_f32(_p(canvas), C, h, w, _stream()), "tile_blend_finish_f32")
@@ -1139,11 +1161,32 @@ def _decode_window(model, src, window, out, batch, stats, what, level=0):
         _lib.check(L.dsic_tile_blend_finish_u16(_p(canvas), _p(img), C, h, w, *lohi, _stream()), "tile_blend_finish_u16")
     elif O:
         _lib.check(L.dsic_tile_blend_finish_u8(_p(canvas), _p(img), C, h, w, _stream()), "tile_blend_finish_u8")
-    if stats is not None:
-        stats.update(tiles=tiles, decode_batches=decode_batches, bytes_read=source.bytes_read,
-                     bytes_uploaded=uploaded)
     if tau is not None and kind == KIND_F32_CHW:
-        return (img.permute(2, 0, 1).to(torch.float32) / 255).contiguous()
+        img = (img.permute(2, 0, 1).to(torch.float32) / 255).contiguous()
+    return img, uploaded, taken
+
+
+def _decode_window(model, src, window, out, batch, stats, what, level=0, opened=None):
+    """decompress_region's work; window None = the whole image, batch None = the stream's tiles per container.  Of a
+    DSICP stream the chosen level is decoded, through a view of its bytes.  opened: (source, index) of a level that
+    an ImageReader has opened and checked against the model already; then bytes_read counts from this call on."""
+    _check_out(out, None, what)
+    source, ix = opened if opened is not None else _open_level(src, level)[:2]
+    read0 = source.bytes_read if opened is not None else 0
+    kind = _check_out(out, ix, what)
+    if opened is None:
+        _refuse_foreign(model, ix, what)
+    y0, x0, h, w = (0, 0, ix["H"], ix["W"]) if window is None else window
+    tiles = window_tiles(ix, y0, x0, h, w)
+    window = (int(y0), int(x0), int(h), int(w))
+    batch = ix["batch"] if batch is None else batch
+    coded = _coded_tiles(ix, tiles)
+    batches = (_decode_tiles(model, source, ix, coded[first:first + batch], what)
+               for first in range(0, len(coded), batch))
+    img, uploaded, decode_batches = _assemble_window(model, source, ix, tiles, window, kind, batches, what)
+    if stats is not None:
+        stats.update(tiles=tiles, decode_batches=decode_batches, bytes_read=source.bytes_read - read0,
+                     bytes_uploaded=uploaded)
     return img
 
 
@@ -1182,3 +1225,6 @@ def decompress_region(model, src, y0, x0, h, w, out=None, batch=64, stats=None, 
     if batch < 1:
         raise ValueError(f"decompress_region: batch={batch}")
     return _decode_window(model, src, (y0, x0, h, w), out, batch, stats, "decompress_region", level)
+
+
+from .view import ImageReader, view_level  # noqa: E402  (view.py builds on the functions above)

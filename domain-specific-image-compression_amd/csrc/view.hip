@@ -1,0 +1,253 @@
+// Resampled reads (codec.ImageReader.read with size=(oh, ow)): a region of level 0, given through a window of overview
+// level l that covers it, resampled to oh x ow.  One launch; a thread owns one output pixel with all its channels.
+//
+// The geometry is integer.  On the row axis, scaled by oh, output row i covers [i h, (i+1) h) of the region and source
+// row Y (a row of level l, counted in that level's own grid) covers [(Y << l) oh - y0 oh, ((Y+1) << l) oh - y0 oh);
+// wy(i, Y) is the length of their intersection, which over Y sums to h.  The rows with wy > 0 are
+// (y0 + i h / oh) >> l ... (y0 + ((i+1) h - 1) / oh) >> l (floor divisions), all inside the covering window
+// codec.level_window(l, y0, x0, h, w).  Columns likewise with ow, x0 and w.
+//
+// average, uint8 / uint16 [sh][sw][C]: per channel S = sum wy wx v and T = sum wy wx in 64 bits, output
+// (2 S + T) / (2 T): the weighted mean rounded half up, exact.  h w <= 2^46 keeps 2 S + T under 2^64.
+// average, float32 [C][sh][sw]: acc = the float32 left fold over Y ascending, then X ascending, of
+// float32(wy wx) * v (built with -ffp-contract=off: NumPy folds to the same bits), output acc / float32(T).
+// nodata: a source pixel whose C channels all equal the value stays out of S (acc) and T; T = 0 gives the value.
+// nearest: source row (y0 2 oh + (2 i + 1) h) / (2 oh) >> l = (y0 + (2 i + 1) h / (2 oh)) >> l, columns likewise; a copy.
+//
+// A wave covers 64 consecutive pixels of an output row, so its loads walk the source rows in step and its stores are
+// one run of 64 C elements; each source pixel is needed by at most two output rows and two output columns when the
+// level fits the scale (codec.view_level), which the caches absorb.
+#include <limits.h>
+
+#include "common.h"
+
+namespace dsic {
+
+struct View {
+  int sh, sw, sy0, sx0, shift, y0, x0, h, w, oh, ow;
+  int hn, hd, wn, wd;  // h / oh and w / ow in lowest terms: the integer kinds' weights (view_reduce)
+};
+
+struct Span {
+  int a, b;
+};
+
+// output index i of n over the region [o, o + len): the first and last source index of level `shift` that it meets
+__device__ __forceinline__ Span axis_span(int i, int len, int n, int o, int shift) {
+  const int64_t lo = (int64_t)i * len / n, hi = ((int64_t)(i + 1) * len - 1) / n;
+  return {(int)((o + lo) >> shift), (int)((o + hi) >> shift)};
+}
+
+// the length, scaled by n, that output index i and source index Y share: positive for Y inside axis_span
+__device__ __forceinline__ int64_t axis_weight(int i, int len, int n, int o, int shift, int Y) {
+  const int64_t a = ((int64_t)Y << shift) * n - (int64_t)o * n, b = a + ((int64_t)n << shift);
+  return min(b, (int64_t)(i + 1) * len) - max(a, (int64_t)i * len);
+}
+
+__device__ __forceinline__ int axis_nearest(int i, int len, int n, int o, int shift) {
+  return (int)((o + (2 * (int64_t)i + 1) * len / (2 * (int64_t)n)) >> shift);
+}
+
+constexpr int VIEW_BX = 64, VIEW_BY = 4;  // output pixels of a workgroup: 4 rows of 64
+
+// T = uint8_t or uint16_t, [.][.][C] with C <= 4; nodata < 0 = none.  The weights are taken with h / oh and w / ow in
+// lowest terms: every interval end is a multiple of gcd(h, oh), so this divides all wy by it, S and T alike, and
+// (2 S + T) / (2 T) is the same integer while S and T stay small (halving: T = 4).
+template <typename T>
+__global__ __launch_bounds__(VIEW_BX * VIEW_BY) void resample_int_kernel(const T* __restrict__ src,
+                                                                         T* __restrict__ dst, View v, int C, int mode,
+                                                                         int nodata, int bx, int64_t nblocks) {
+  for (int64_t blk = blockIdx.x; blk < nblocks; blk += gridDim.x) {
+    const int64_t by = blk / bx;
+    const int j = (int)(blk - by * bx) * VIEW_BX + threadIdx.x;
+    const int64_t i64 = by * VIEW_BY + threadIdx.y;
+    if (i64 >= v.oh || j >= v.ow) continue;
+    const int i = (int)i64;
+    T* o = dst + ((int64_t)i * v.ow + j) * C;
+    if (mode == 1) {
+      const int Y = axis_nearest(i, v.hn, v.hd, v.y0, v.shift), X = axis_nearest(j, v.wn, v.wd, v.x0, v.shift);
+      const T* p = src + ((int64_t)(Y - v.sy0) * v.sw + (X - v.sx0)) * C;
+      for (int c = 0; c < C; ++c) o[c] = p[c];
+      continue;
+    }
+    const Span ry = axis_span(i, v.hn, v.hd, v.y0, v.shift), rx = axis_span(j, v.wn, v.wd, v.x0, v.shift);
+    uint64_t S[4] = {0, 0, 0, 0}, Tw = 0;
+    for (int Y = ry.a; Y <= ry.b; ++Y) {
+      const uint64_t wy = (uint64_t)axis_weight(i, v.hn, v.hd, v.y0, v.shift, Y);
+      const T* row = src + (int64_t)(Y - v.sy0) * v.sw * C;
+      for (int X = rx.a; X <= rx.b; ++X) {
+        const uint64_t wgt = wy * (uint64_t)axis_weight(j, v.wn, v.wd, v.x0, v.shift, X);
+        const T* p = row + (int64_t)(X - v.sx0) * C;
+        uint32_t val[4];
+        bool nd = nodata >= 0;
+#pragma unroll
+        for (int c = 0; c < 4; ++c) {
+          val[c] = c < C ? (uint32_t)p[c] : 0u;
+          if (c < C) nd = nd && val[c] == (uint32_t)nodata;
+        }
+        if (nd) continue;
+        Tw += wgt;
+#pragma unroll
+        for (int c = 0; c < 4; ++c) S[c] += wgt * val[c];
+      }
+    }
+    // (2 S + T) / (2 T): in 32 bits where both fit, which reduced weights nearly always allow
+    const bool narrow = ((2 * (S[0] | S[1] | S[2] | S[3]) + Tw) >> 32) == 0 && (Tw >> 31) == 0;
+#pragma unroll
+    for (int c = 0; c < 4; ++c) {
+      if (c >= C) continue;
+      const uint64_t num = 2 * S[c] + Tw, den = 2 * Tw;
+      o[c] = !Tw ? (T)nodata : narrow ? (T)((uint32_t)num / (uint32_t)den) : (T)(num / den);
+    }
+  }
+}
+
+// float32 [C][.][.], C <= 8
+__global__ __launch_bounds__(VIEW_BX * VIEW_BY) void resample_f32_kernel(const float* __restrict__ src,
+                                                                         float* __restrict__ dst, View v, int C,
+                                                                         int mode, float nodata, int has_nodata, int bx,
+                                                                         int64_t nblocks) {
+  const int64_t splane = (int64_t)v.sh * v.sw, dplane = (int64_t)v.oh * v.ow;
+  for (int64_t blk = blockIdx.x; blk < nblocks; blk += gridDim.x) {
+    const int64_t by = blk / bx;
+    const int j = (int)(blk - by * bx) * VIEW_BX + threadIdx.x;
+    const int64_t i64 = by * VIEW_BY + threadIdx.y;
+    if (i64 >= v.oh || j >= v.ow) continue;
+    const int i = (int)i64;
+    float* o = dst + (int64_t)i * v.ow + j;
+    if (mode == 1) {
+      const int Y = axis_nearest(i, v.h, v.oh, v.y0, v.shift), X = axis_nearest(j, v.w, v.ow, v.x0, v.shift);
+      const float* p = src + (int64_t)(Y - v.sy0) * v.sw + (X - v.sx0);
+      for (int c = 0; c < C; ++c) o[c * dplane] = p[c * splane];
+      continue;
+    }
+    const Span ry = axis_span(i, v.h, v.oh, v.y0, v.shift), rx = axis_span(j, v.w, v.ow, v.x0, v.shift);
+    float acc[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+    int64_t Tw = 0;
+    for (int Y = ry.a; Y <= ry.b; ++Y) {
+      const int64_t wy = axis_weight(i, v.h, v.oh, v.y0, v.shift, Y);
+      const float* row = src + (int64_t)(Y - v.sy0) * v.sw;
+      for (int X = rx.a; X <= rx.b; ++X) {
+        const int64_t wgt = wy * axis_weight(j, v.w, v.ow, v.x0, v.shift, X);
+        const float* p = row + (X - v.sx0);
+        float val[8];
+        bool nd = has_nodata != 0;
+#pragma unroll
+        for (int c = 0; c < 8; ++c) {
+          val[c] = c < C ? p[c * splane] : 0.f;
+          if (c < C) nd = nd && val[c] == nodata;
+        }
+        if (nd) continue;
+        Tw += wgt;
+        const float wf = (float)wgt;
+#pragma unroll
+        for (int c = 0; c < 8; ++c) acc[c] = acc[c] + wf * val[c];
+      }
+    }
+    const float tf = (float)Tw;
+#pragma unroll
+    for (int c = 0; c < 8; ++c)
+      if (c < C) o[c * dplane] = Tw ? acc[c] / tf : nodata;
+  }
+}
+
+static bool view_apart(const void* a, int64_t a_bytes, const void* b, int64_t b_bytes) {
+  const uintptr_t pa = (uintptr_t)a, pb = (uintptr_t)b;
+  return pa + (uintptr_t)a_bytes <= pb || pb + (uintptr_t)b_bytes <= pa;
+}
+
+// the checks every kind shares; on success the launch shape
+static int view_check(const char* what, const void* src, const void* dst, const View& v, int C, int cmin, int cmax,
+                      int elem, int mode, int* bx, int64_t* nblocks) {
+  DSIC_REQUIRE(src && dst, "%s: null pointer", what);
+  DSIC_REQUIRE(C >= cmin && C <= cmax, "%s: C=%d must be in %d..%d", what, C, cmin, cmax);
+  DSIC_REQUIRE(mode == 0 || mode == 1, "%s: mode=%d (0 average, 1 nearest)", what, mode);
+  DSIC_REQUIRE(v.shift >= 0 && v.shift <= 15, "%s: shift=%d must be in 0..15", what, v.shift);
+  DSIC_REQUIRE(v.sh >= 1 && v.sw >= 1 && v.sy0 >= 0 && v.sx0 >= 0, "%s: source window %dx%d at (%d, %d)", what, v.sh, v.sw,
+               v.sy0, v.sx0);
+  DSIC_REQUIRE(v.h >= 1 && v.w >= 1 && v.y0 >= 0 && v.x0 >= 0 && (int64_t)v.y0 + v.h <= INT_MAX &&
+                   (int64_t)v.x0 + v.w <= INT_MAX,
+               "%s: region %dx%d at (%d, %d)", what, v.h, v.w, v.y0, v.x0);
+  DSIC_REQUIRE(v.oh >= 1 && v.ow >= 1, "%s: output %dx%d must be at least 1x1", what, v.oh, v.ow);
+  DSIC_REQUIRE((int64_t)v.sh * v.sw <= ((int64_t)1 << 48) && (int64_t)v.oh * v.ow <= ((int64_t)1 << 48),
+               "%s: a source window of %dx%d or an output of %dx%d pixels is over 2^48", what, v.sh, v.sw, v.oh, v.ow);
+  DSIC_REQUIRE((int64_t)v.h * v.w <= ((int64_t)1 << 46), "%s: a region of %dx%d pixels is over 2^46", what, v.h, v.w);
+  const int64_t ya = v.y0 >> v.shift, yb = ((int64_t)v.y0 + v.h - 1) >> v.shift;
+  const int64_t xa = v.x0 >> v.shift, xb = ((int64_t)v.x0 + v.w - 1) >> v.shift;
+  DSIC_REQUIRE(ya >= v.sy0 && yb < (int64_t)v.sy0 + v.sh && xa >= v.sx0 && xb < (int64_t)v.sx0 + v.sw,
+               "%s: the region %dx%d at (%d, %d) covers rows %lld..%lld, columns %lld..%lld of level %d, outside the "
+               "source window %dx%d at (%d, %d)",
+               what, v.h, v.w, v.y0, v.x0, (long long)ya, (long long)yb, (long long)xa, (long long)xb, v.shift, v.sh,
+               v.sw, v.sy0, v.sx0);
+  DSIC_REQUIRE((((uintptr_t)src | (uintptr_t)dst) & (uintptr_t)(elem - 1)) == 0, "%s: src and dst must be %d-byte aligned",
+               what, elem);
+  DSIC_REQUIRE(view_apart(src, (int64_t)elem * C * v.sh * v.sw, dst, (int64_t)elem * C * v.oh * v.ow),
+               "%s: src and dst overlap", what);
+  *bx = (v.ow + VIEW_BX - 1) / VIEW_BX;
+  *nblocks = (int64_t)*bx * ((v.oh + VIEW_BY - 1) / VIEW_BY);
+  return DSIC_OK;
+}
+
+static int view_gcd(int a, int b) {
+  while (b) {
+    const int t = a % b;
+    a = b;
+    b = t;
+  }
+  return a;
+}
+
+static View view_of(int sh, int sw, int sy0, int sx0, int shift, int y0, int x0, int h, int w, int oh, int ow) {
+  View v = {sh, sw, sy0, sx0, shift, y0, x0, h, w, oh, ow, h, oh, w, ow};
+  if (h >= 1 && oh >= 1 && w >= 1 && ow >= 1) {
+    const int gy = view_gcd(h, oh), gx = view_gcd(w, ow);
+    v.hn = h / gy, v.hd = oh / gy, v.wn = w / gx, v.wd = ow / gx;
+  }
+  return v;
+}
+
+static dim3 view_grid(int64_t nblocks) { return dim3((unsigned)(nblocks > (1 << 20) ? (1 << 20) : nblocks)); }
+
+template <typename T>
+static int resample_int(const char* what, const T* src, const View& v, int C, int cmin, T* dst, int mode, int nodata,
+                        void* stream) {
+  int bx;
+  int64_t nblocks;
+  const int status = view_check(what, src, dst, v, C, cmin, 4, (int)sizeof(T), mode, &bx, &nblocks);
+  if (status != DSIC_OK) return status;
+  DSIC_REQUIRE(nodata >= -1 && nodata <= (int)(T)~(T)0, "%s: nodata=%d (-1 for none, or a pixel value)", what, nodata);
+  hipLaunchKernelGGL(resample_int_kernel<T>, view_grid(nblocks), dim3(VIEW_BX, VIEW_BY), 0, (hipStream_t)stream, src, dst,
+                     v, C, mode, nodata, bx, nblocks);
+  return check_launch(what);
+}
+
+}  // namespace dsic
+
+using namespace dsic;
+
+extern "C" int dsic_window_resample_u8(const uint8_t* src_hwc, int sh, int sw, int sy0, int sx0, int C, int shift, int y0,
+                                       int x0, int h, int w, uint8_t* dst_hwc, int oh, int ow, int mode, int nodata,
+                                       void* stream) {
+  const View v = view_of(sh, sw, sy0, sx0, shift, y0, x0, h, w, oh, ow);
+  return resample_int<uint8_t>("window_resample_u8", src_hwc, v, C, 3, dst_hwc, mode, nodata, stream);
+}
+
+extern "C" int dsic_window_resample_u16(const uint16_t* src_hwc, int sh, int sw, int sy0, int sx0, int C, int shift,
+                                        int y0, int x0, int h, int w, uint16_t* dst_hwc, int oh, int ow, int mode,
+                                        int nodata, void* stream) {
+  const View v = view_of(sh, sw, sy0, sx0, shift, y0, x0, h, w, oh, ow);
+  return resample_int<uint16_t>("window_resample_u16", src_hwc, v, C, 1, dst_hwc, mode, nodata, stream);
+}
+
+extern "C" int dsic_window_resample_f32(const float* src_chw, int sh, int sw, int sy0, int sx0, int C, int shift, int y0,
+                                        int x0, int h, int w, float* dst_chw, int oh, int ow, int mode, float nodata,
+                                        int has_nodata, void* stream) {
+  const View v = view_of(sh, sw, sy0, sx0, shift, y0, x0, h, w, oh, ow);
+  int bx;
+  int64_t nblocks;
+  const int status = view_check("window_resample_f32", src_chw, dst_chw, v, C, 1, 8, 4, mode, &bx, &nblocks);
+  if (status != DSIC_OK) return status;
+  hipLaunchKernelGGL(resample_f32_kernel, view_grid(nblocks), dim3(VIEW_BX, VIEW_BY), 0, (hipStream_t)stream, src_chw,
+                     dst_chw, v, C, mode, nodata, has_nodata, bx, nblocks);
+  return check_launch("window_resample_f32");
+}

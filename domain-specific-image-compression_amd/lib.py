@@ -132,6 +132,9 @@ SIGNATURES = {
     "dsic_tile_stitch_window_u16": (c_int, [_P, _P, c_int, _P] + [c_int] * 9 + [_P, _P]),
     "dsic_tile_blend_finish_u16": (c_int, [_P, _P, c_int, c_int, c_int, _P, _P]),
     "dsic_image_halve_u16": (c_int, [_P, _P, c_int, c_int, c_int, _P]),
+    "dsic_window_resample_u8": (c_int, [_P] + [c_int] * 10 + [_P] + [c_int] * 4 + [_P]),
+    "dsic_window_resample_u16": (c_int, [_P] + [c_int] * 10 + [_P] + [c_int] * 4 + [_P]),
+    "dsic_window_resample_f32": (c_int, [_P] + [c_int] * 10 + [_P] + [c_int] * 3 + [ctypes.c_float, c_int, _P]),
     "dsic_stream_create_masked":(c_int, [_P, c_int, _P]),
     "dsic_stream_destroy": (c_int, [_P]),
     "dsic_range_decode": (c_int, [_P, c_int64, _P, c_int, c_int, _P, c_int, _P, c_int, c_int, c_int,

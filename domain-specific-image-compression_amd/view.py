@@ -1,0 +1,379 @@
+"""Pan and zoom over an image stream: codec.ImageReader, a reader that stays open.
+
+decompress_region starts from nothing on every call: it reads and checks the stream's heads again and decodes every
+tile the window touches.  A reader opens each level of a DSICI / DSICP stream once (source view, index, the check
+against the model), keeps decoded tiles on the device, decodes the tiles that several requests miss in shared dense
+batches (read_many), and resamples a window of the best-fitting overview to the size asked for (csrc/view.hip).
+
+The cache holds what the stitch and blend calls consume: per (level, tile) the tile's g_s output, float32
+[C, th, tw], not clamped, and for a near-lossless level its q plane.  A window is served by collecting its tiles, in
+ascending tile order, into one dense batch and making the calls decompress_region makes on a freshly decoded batch
+(codec._assemble_window), so the result is that function's, bit for bit: a decoded tile does not depend on the batch it
+was decoded in, the stitch writes every pixel from the one tile that owns it, and the blend folds a pixel's tiles in
+ascending tile number however they are cut into calls.
+"""
+from __future__ import annotations
+
+import collections
+import copy
+import ctypes
+import operator
+
+import numpy as np
+import torch
+
+from . import codec as _c
+from . import lib as _lib
+from .ops import _p, _stream
+
+RESAMPLING = {"average": 0, "nearest": 1}
+_COUNTERS = ("hits", "decoded", "decode_batches", "bytes_read", "bytes_uploaded")
+
+
+def view_level(n_levels, h, w, oh, ow) -> int:
+    """The overview level to read a level-0 window of h x w pixels from for a view of oh x ow (pure Python): the
+    largest l < n_levels with (oh << l) <= h and (ow << l) <= w, else 0, so that a coarser level is never magnified
+    while a finer one exists."""
+    n_levels, h, w, oh, ow = (operator.index(v) for v in (n_levels, h, w, oh, ow))
+    if n_levels < 1 or h < 1 or w < 1 or oh < 1 or ow < 1:
+        raise ValueError(f"view_level: {n_levels} level(s), window {h}x{w}, view {oh}x{ow}")
+    for l in range(n_levels - 1, 0, -1):
+        if (oh << l) <= h and (ow << l) <= w:
+            return l
+    return 0
+
+
+def _tile_bytes(ix):
+    """What a cached tile of an indexed level costs: float32 [C, th, tw], and as much again for its q plane."""
+    return 4 * ix["C"] * ix["th"] * ix["tw"] * (2 if ix.get("max_error") is not None else 1)
+
+
+def _new_stats():
+    return {"tiles": [], "hits": 0, "decoded": 0, "decode_batches": 0, "bytes_read": 0, "bytes_uploaded": 0}
+
+
+class _Slab:
+    """The cached tiles of one level: row `slot` of x (and of q, for a near-lossless level) is a decoded tile, ids
+    its tile number on the device, as the stitch calls take it."""
+
+    def __init__(self, ix, dev):
+        self.shape = (ix["C"], ix["th"], ix["tw"])
+        self.has_q = ix.get("max_error") is not None
+        self.tile_bytes = _tile_bytes(ix)
+        self.dev, self.slots, self.free, self.cap = dev, {}, [], 0
+        self.x = self.q = self.ids = None
+
+    def reserve(self, cap, limit):
+        """Room for `cap` rows: the slab grows to twice its size, to `cap` if that is more, and not past `limit`."""
+        if cap <= self.cap:
+            return
+        new = max(cap, min(2 * self.cap, limit))
+        for name, shape, dtype in (("x", self.shape, torch.float32), ("q", self.shape, torch.float32),
+                                   ("ids", (), torch.int32)):
+            if name == "q" and not self.has_q:
+                continue
+            grown = torch.empty((new,) + shape, dtype=dtype, device=self.dev)
+            if self.cap:
+                grown[:self.cap] = getattr(self, name)
+            setattr(self, name, grown)
+        self.free.extend(range(new - 1, self.cap - 1, -1))       # popped from the end: the lowest row first
+        self.cap = new
+
+    def rows(self, tiles):
+        """The rows of `tiles` as an index for index_select / index_copy_."""
+        return torch.tensor([self.slots[t] for t in tiles], dtype=torch.int64).to(self.dev)
+
+
+class ImageReader:
+    """An open DSICI or DSICP stream for repeated window reads: ImageReader(model, src, cache_bytes=1 << 30,
+    batch=64), a context manager; close() drops the cache.  src: bytes or a binary file object, as decompress_region
+    takes it.  Every level is opened at most once, on first use: its source view and index are kept, and the stream
+    is checked against the model (numerics tag, model shape) once per level.
+
+    Decoded tiles are cached on the device, at most cache_bytes of them (float32 [C, th, tw] per tile, twice that for
+    a near-lossless level), one slab per level that grows on demand, one least-recently-used order over all levels;
+    the tiles of the running call are never evicted by it.  A request whose tiles exceed cache_bytes is decoded as
+    decompress_region decodes it and leaves the cache as it was; cache_bytes = 0 makes the reader an index-caching
+    front of decompress_region.  Missing tiles are decoded in ascending tile order in dense batches of at most
+    `batch`.  A slab's rows are handed back when the last tile of its level is evicted.
+
+    stats: the counters of all calls so far, with the keys of a call's dict (`tiles` as a count; bytes_read is all the
+    reader has read from src, the heads included)."""
+
+    def __init__(self, model, src, cache_bytes=1 << 30, batch=64):
+        self.model, self.batch, self.cache_bytes = model, int(batch), int(cache_bytes)
+        if self.batch < 1:
+            raise ValueError(f"ImageReader: batch={batch}")
+        if self.cache_bytes < 0:
+            raise ValueError(f"ImageReader: cache_bytes={cache_bytes}")
+        self._dev = next(model.parameters()).device
+        self._source = _c._Source(src)
+        self._head = self._source.read_at(0, _c._HEAD.size)
+        self._dir = None
+        if bytes(self._head[:len(_c.PMAGIC)]) == _c.PMAGIC:
+            self._dir = _c._read_directory(self._source, self._head)
+        self._open, self._slabs = {}, {}
+        self._lru, self._used = collections.OrderedDict(), 0       # (level, tile) -> None, oldest first
+        self._stats = dict(_new_stats(), tiles=0)
+        self._closed = False
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def close(self):
+        self._slabs.clear()
+        self._lru.clear()
+        self._open.clear()
+        self._used, self._closed = 0, True
+
+    # ---- the stream ---------------------------------------------------------------------------------------------
+    def _level(self, level):
+        """(source view, index with offsets inside that view) of a level, opened on first use."""
+        if self._closed:
+            raise ValueError("ImageReader: the reader is closed")
+        try:
+            level = 0 if level is None else operator.index(level)
+        except TypeError:
+            raise ValueError(f"level={level!r} is not an integer") from None
+        if level not in self._open:
+            if self._dir is None:
+                if level != 0:
+                    raise ValueError(f"level={level}: a DSICI stream holds one image, level 0")
+                view, base = self._source, 0
+                ix = _c._index_of(view, self._head)
+            else:
+                if not 0 <= level < len(self._dir):
+                    raise ValueError(f"level={level}: the DSICP stream holds levels 0 .. {len(self._dir) - 1}")
+                d = self._dir[level]
+                view, base = _c._Level(self._source, d["offset"], d["length"]), d["offset"]
+                before = self._source.bytes_read
+                ix = _c._index_of(view)
+                _c._check_levels([(v["H"], v["W"]) for v in self._dir], [None] * level + [ix])
+                ix.update(level=level, levels=self._dir, index_bytes=self._source.bytes_read - before)
+            _c._refuse_foreign(self.model, ix, "ImageReader")
+            self._open[level] = (view, ix, base)
+        return level, self._open[level][0], self._open[level][1]
+
+    @property
+    def stats(self):
+        return dict(self._stats, bytes_read=self._source.bytes_read)       # whatever opened the levels included
+
+    @property
+    def shape(self):
+        ix = self._level(0)[2]
+        return ix["H"], ix["W"], ix["C"]
+
+    @property
+    def kind(self):
+        return self._level(0)[2]["kind"]
+
+    @property
+    def levels(self):
+        if self._dir is None:
+            return [self.shape[:2]]
+        return [(d["H"], d["W"]) for d in self._dir]
+
+    def index(self, level=0):
+        """stream_index(src, level), from the reader's own copy: offsets count from the start of src."""
+        level = self._level(level)[0]
+        _, ix, base = self._open[level]
+        ix = copy.deepcopy(ix)
+        if self._dir is not None:
+            _c._absolute_offsets(ix, base, ix["levels"])
+        return ix
+
+    # ---- the cache ----------------------------------------------------------------------------------------------
+    def _slab(self, level, ix):
+        if level not in self._slabs:
+            self._slabs[level] = _Slab(ix, self._dev)
+        return self._slabs[level]
+
+    def _evict_for(self, need, pinned):
+        """Evict the least recently used tiles that the running call does not need until `need` more bytes fit."""
+        if self._used + need <= self.cache_bytes:
+            return
+        for key in [k for k in self._lru if k not in pinned]:
+            level, tile = key
+            slab = self._slabs[level]
+            slab.free.append(slab.slots.pop(tile))
+            del self._lru[key]
+            self._used -= slab.tile_bytes
+            if not slab.slots:
+                del self._slabs[level]
+            if self._used + need <= self.cache_bytes:
+                return
+        raise RuntimeError("ImageReader: the running call's tiles do not fit the cache")   # the callers check the size
+
+    def _ensure(self, level, view, ix, coded, pinned, st):
+        """The tiles `coded` (ascending) of a level into the cache: those already there become the most recently used,
+        the others are decoded in dense batches and stored."""
+        slab = self._slab(level, ix)
+        missing = [t for t in coded if t not in slab.slots]
+        st["hits"] += len(coded) - len(missing)
+        for t in coded:
+            if t in slab.slots:
+                self._lru.move_to_end((level, t))
+        for first in range(0, len(missing), self.batch):
+            sel = missing[first:first + self.batch]
+            x_hat, nbytes, ids, q = _c._decode_tiles(self.model, view, ix, sel, "ImageReader")
+            self._evict_for(len(sel) * slab.tile_bytes, pinned)
+            slab = self._slab(level, ix)                   # the eviction may have dropped the level's empty slab
+            held = len(slab.slots)
+            slab.reserve(held + len(sel), max(held + len(sel), min(ix["grid"]["n"], self.cache_bytes // slab.tile_bytes)))
+            for t in sel:
+                slab.slots[t] = slab.free.pop()
+                self._lru[(level, t)] = None
+            rows = slab.rows(sel)
+            slab.x.index_copy_(0, rows, x_hat)
+            slab.ids.index_copy_(0, rows, ids)
+            if slab.has_q:
+                slab.q.index_copy_(0, rows, q)
+            self._used += len(sel) * slab.tile_bytes
+            st["decoded"] += len(sel)
+            st["decode_batches"] += 1
+            st["bytes_uploaded"] += nbytes
+
+    def _window(self, level, window, out, st, ensured=False):
+        """decompress_region(model, src, *window, out=out, level=level), through the cache.  ensured: read_many has
+        brought the window's tiles into the cache and counted them."""
+        level, view, ix = self._level(level)
+        kind = _c._check_out(out, ix, "ImageReader.read")
+        tiles = _c.window_tiles(ix, *window)
+        window = tuple(int(v) for v in window)
+        coded = _c._coded_tiles(ix, tiles)
+        if not ensured:
+            st["tiles"] += [(level, t) for t in tiles]
+            if len(coded) * _tile_bytes(ix) > self.cache_bytes:
+                inner = {}
+                img = _c._decode_window(self.model, None, window, out, self.batch, inner, "ImageReader.read",
+                                        opened=(view, ix))
+                st["decoded"] += len(coded)
+                st["decode_batches"] += inner["decode_batches"]
+                st["bytes_uploaded"] += inner["bytes_uploaded"]
+                return img
+            self._ensure(level, view, ix, coded, {(level, t) for t in coded}, st)
+        batches = []
+        if coded:
+            slab = self._slabs[level]
+            rows = slab.rows(coded)
+            batches.append((slab.x.index_select(0, rows), 0, slab.ids.index_select(0, rows),
+                            slab.q.index_select(0, rows) if slab.has_q else None))
+        img, uploaded, _ = _c._assemble_window(self.model, view, ix, tiles, window, kind, batches, "ImageReader.read")
+        st["bytes_uploaded"] += uploaded
+        return img
+
+    # ---- requests -----------------------------------------------------------------------------------------------
+    def _plan(self, window, size, level, resampling):
+        """A request -> (level, that level's window, None or (region, size, mode))."""
+        if resampling not in RESAMPLING:
+            raise ValueError(f"ImageReader: resampling={resampling!r} ({', '.join(RESAMPLING)})")
+        y0, x0, h, w = window
+        if size is None:
+            return self._level(level)[0], (y0, x0, h, w), None
+        try:
+            oh, ow = (operator.index(v) for v in size)
+        except (TypeError, ValueError):
+            raise ValueError(f"ImageReader: size={size!r} is not a pair of integers (oh, ow)") from None
+        if oh < 1 or ow < 1:
+            raise ValueError(f"ImageReader: size={size!r} must be at least (1, 1)")
+        y0, x0, h, w = (int(v) for v in window)
+        H, W = self.levels[0]
+        if y0 < 0 or x0 < 0 or h < 1 or w < 1 or y0 + h > H or x0 + w > W:
+            raise ValueError(f"window {h}x{w} at ({y0}, {x0}) is empty or outside the {H}x{W} image")
+        if level is None:
+            level = view_level(len(self.levels), h, w, oh, ow)
+        level = self._level(level)[0]
+        if level == 0 and (oh, ow) == (h, w):
+            return 0, (y0, x0, h, w), None
+        return level, _c.level_window(level, y0, x0, h, w), ((y0, x0, h, w), (oh, ow), RESAMPLING[resampling])
+
+    def _resample(self, img, level, lw, view):
+        """A level's window `lw`, as _window returns it, resampled to the view (csrc/view.hip)."""
+        (y0, x0, h, w), (oh, ow), mode = view
+        ix = self._open[level][1]
+        v = ix.get("nodata") if mode == 0 else None
+        L = _lib.load()
+        geo = (lw[2], lw[3], lw[0], lw[1], ix["C"], level, y0, x0, h, w)
+        if img.dtype == torch.float32:
+            dst = torch.empty((ix["C"], oh, ow), dtype=torch.float32, device=img.device)
+            value = 0.0 if v is None else float(np.float32(v) / np.float32(255.0))     # what _apply_mask wrote
+            status = L.dsic_window_resample_f32(_p(img), *geo, _p(dst), oh, ow, mode, ctypes.c_float(value),
+                                                int(v is not None), _stream())
+            what = "window_resample_f32"
+        else:
+            what = "window_resample_u8" if img.dtype == torch.uint8 else "window_resample_u16"
+            dst = torch.empty((oh, ow, ix["C"]), dtype=img.dtype, device=img.device)
+            status = getattr(L, "dsic_" + what)(_p(img), *geo, _p(dst), oh, ow, mode, -1 if v is None else v, _stream())
+        _lib.check(status, what)
+        return dst
+
+    def _finish(self, st, before, stats):
+        st["bytes_read"] = self._source.bytes_read - before
+        for key in _COUNTERS:
+            self._stats[key] += st[key]
+        self._stats["tiles"] += len(st["tiles"])
+        if stats is not None:
+            stats.update(st)
+
+    @torch.no_grad()
+    def read(self, y0, x0, h, w, size=None, level=None, out=None, resampling="average", stats=None):
+        """size = None: the window rows [y0, y0+h) x columns [x0, x0+w) of level `level` (default 0), in that level's
+        own pixel grid: decompress_region(model, src, y0, x0, h, w, out=out, level=level), bit for bit, whatever the
+        cache held before.
+        size = (oh, ow): the window is in level-0 pixels and the result has oh x ow pixels.  The level read is `level`,
+        or view_level(number of levels, h, w, oh, ow); its covering window level_window(l, y0, x0, h, w) is produced
+        as above and resampled (dsic_window_resample_u8 / _u16 / _f32): resampling = "average" is the area-weighted
+        mean over each output pixel's footprint (integer kinds exact and rounded half up, float32 a fixed float32
+        fold), "nearest" copies the pixel under the output pixel's centre.  Averaging a nodata stream (version 5)
+        leaves nodata pixels out, and an output pixel with nothing else under it is nodata.  size == (h, w) at level
+        0 is the plain window.  The result has the kind `out` gives the window.
+        stats (a dict) receives tiles ((level, tile) pairs), hits, decoded, decode_batches, bytes_read and
+        bytes_uploaded, and for a read with a size level and level_window.
+        ValueError as decompress_region raises it, and for an unknown resampling, a size whose entries are not
+        integers >= 1, and a level the stream does not hold."""
+        _c._check_out(out, None, "ImageReader.read")
+        before, st = self._source.bytes_read, _new_stats()
+        level, lw, view = self._plan((y0, x0, h, w), size, level, resampling)
+        img = self._window(level, lw, out, st)
+        if view is not None:
+            img = self._resample(img, level, lw, view)
+        if size is not None:
+            st.update(level=level, level_window=tuple(lw))
+        self._finish(st, before, stats)
+        return img
+
+    @torch.no_grad()
+    def read_many(self, requests, out=None, resampling="average", stats=None):
+        """requests: dicts with `window` = (y0, x0, h, w) and optionally `size` and `level`, as read takes them ->
+        the list [read(*window, size, level, out, resampling) for each], bit for bit.  The tiles that the cache lacks
+        are decoded once over the union of all requests: per level, in ascending tile order, in dense batches of at
+        most `batch`, so many small requests share their decode batches.  If the union does not fit the cache the
+        requests are read one by one.  stats: as read's, over the whole call; tiles is the union."""
+        _c._check_out(out, None, "ImageReader.read_many")
+        before, st = self._source.bytes_read, _new_stats()
+        plans = [self._plan(r["window"], r.get("size"), r.get("level"), resampling) for r in requests]
+        union, used = {}, 0
+        for level, lw, _ in plans:
+            _, _, ix = self._level(level)
+            _c._check_out(out, ix, "ImageReader.read_many")
+            union.setdefault(level, set()).update(_c.window_tiles(ix, *lw))
+        for level in union:
+            ix = self._open[level][1]
+            union[level] = sorted(union[level])
+            used += len(_c._coded_tiles(ix, union[level])) * _tile_bytes(ix)
+        shared = used <= self.cache_bytes
+        if shared:
+            pinned = {(level, t) for level, tiles in union.items() for t in tiles}
+            for level in sorted(union):
+                _, view, ix = self._level(level)
+                st["tiles"] += [(level, t) for t in union[level]]
+                self._ensure(level, view, ix, _c._coded_tiles(ix, union[level]), pinned, st)
+        imgs = []
+        for level, lw, view in plans:
+            img = self._window(level, lw, out, st, ensured=shared)
+            imgs.append(img if view is None else self._resample(img, level, lw, view))
+        self._finish(st, before, stats)
+        return imgs

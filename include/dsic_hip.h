@@ -676,6 +676,35 @@ int dsic_tile_blend_finish_u16(const float* canvas, uint16_t* out_hwc, int C, in
 int dsic_image_halve_u16(const uint16_t* src_hwc, uint16_t* dst_hwc, int H, int W, int C,
                          void* stream);
 
+/* ---- resampled reads (codec.ImageReader.read with size = (oh, ow)) ----
+ * The level-0 region rows [y0, y0+h) x columns [x0, x0+w), resampled to oh x ow from a window of
+ * overview level `shift` (0 = the image itself): src holds sh x sw pixels of that level, its first
+ * pixel being the level's pixel (sy0, sx0), and must contain the region's covering window, rows
+ * y0 >> shift ... (y0+h-1) >> shift and the columns likewise (codec.level_window).  src and dst
+ * are uint8 / uint16 [.][.][C] or float32 [C][.][.].  All geometry is integer: on the row axis,
+ * scaled by oh, output row i covers [i h, (i+1) h) and level row Y covers
+ * [(Y << shift) oh - y0 oh, ((Y+1) << shift) oh - y0 oh); wy(i, Y) is the length they share
+ * (summed over Y: h); columns likewise with ow, x0, w.
+ * mode 0, average.  u8 / u16: S = sum wy wx v, T = sum wy wx in 64 bits, output
+ *   (2 S + T) / (2 T), the exact weighted mean rounded half up.  f32: the float32 left fold over
+ *   Y ascending, then X ascending, of (float)(wy wx) * v, unfused, divided by (float)T.
+ *   nodata (u8 / u16: a pixel value, -1 = none; f32: the value, used if has_nodata != 0): a source
+ *   pixel whose C channels all equal it stays out of S and T; T = 0 gives it in every channel.
+ * mode 1, nearest: level row (y0 + (2 i + 1) h / (2 oh)) >> shift, columns likewise; copied, and
+ *   nodata has no effect.
+ * DSIC_EINVAL: null pointers; C outside 3..4 (u8), 1..4 (u16), 1..8 (f32); shift outside 0..15;
+ * a region whose covering window leaves the source window; h w > 2^46; sizes under 1 or origins
+ * under 0; u16 / f32 pointers not aligned to their element; src and dst overlapping. */
+int dsic_window_resample_u8(const uint8_t* src_hwc, int sh, int sw, int sy0, int sx0, int C,
+                            int shift, int y0, int x0, int h, int w, uint8_t* dst_hwc, int oh,
+                            int ow, int mode, int nodata, void* stream);
+int dsic_window_resample_u16(const uint16_t* src_hwc, int sh, int sw, int sy0, int sx0, int C,
+                             int shift, int y0, int x0, int h, int w, uint16_t* dst_hwc, int oh,
+                             int ow, int mode, int nodata, void* stream);
+int dsic_window_resample_f32(const float* src_chw, int sh, int sw, int sy0, int sx0, int C,
+                             int shift, int y0, int x0, int h, int w, float* dst_chw, int oh,
+                             int ow, int mode, float nodata, int has_nodata, void* stream);
+
 /* HIP stream limited to the CUs whose bit is set in mask_host[words] (bit i of
  * word i/32 = CU i).  Used to give the range coder its own few CUs beside the
  * conv kernels; there is no reference counterpart (the reference is

@@ -4,7 +4,7 @@ an image.
     python tools/dsic_image.py compress   --weights CKPT.pt IN.png  OUT.dsic [--tile 256] [--batch 64] [--segments K] [--overlap O]
                                           [--max-error T] [--overviews N] [--nodata V] [--scale LO,HI[,LO,HI...]]
     python tools/dsic_image.py decompress --weights CKPT.pt IN.dsic OUT.png [--out u8|f32|u16] [--region Y0,X0,H,W]
-                                          [--level L]
+                                          [--level L] [--size OH,OW] [--resampling average|nearest]
     python tools/dsic_image.py info       IN.dsic
 
 --segments K (2, 4, 8 or 16) codes every tile's y string as K independent strings, which a decoder reads on K waves per
@@ -17,6 +17,9 @@ geometry, the tile grid and the bytes of every batch from the stream's heads, wi
 coded with the same options; --max-error bounds level 0 only).  --level L decodes level L of such a stream (0 = the
 full image) from that level's bytes alone; with --region the window is in level L's own pixels.  info prints the
 levels of a DSICP stream (size, bytes, tiles), then level 0.
+--region with --size OH,OW reads the window, given in level-0 pixels, resampled to OH x OW (codec.ImageReader.read):
+from the coarsest level that need not be magnified, or from --level L if given; --resampling average (the default) is
+the area-weighted mean that leaves nodata pixels out, nearest copies the pixel under each output pixel's centre.
 --nodata V (0 .. 255, uint8 images; not with --overlap, --max-error or --overviews) keeps the mask of the pixels whose
 channels all equal V exactly (a version-5 stream): tiles that hold nothing else are not coded at all, and every such
 pixel decodes to V again.  info prints the value, the counts of empty, full and mixed tiles and the mask block's bytes.
@@ -163,6 +166,10 @@ def main(argv=None):
                     help="compress: keep the mask of the pixels whose channels all equal V (0 .. 255) exactly")
     ap.add_argument("--level", type=int, default=0, metavar="L",
                     help="decompress: the overview level of a DSICP stream (0 = the full image); --region counts in it")
+    ap.add_argument("--size", default=None, metavar="OH,OW",
+                    help="decompress --region: the window, in level-0 pixels, resampled to OH x OW")
+    ap.add_argument("--resampling", choices=("average", "nearest"), default="average",
+                    help="decompress --region --size: how the window is resampled")
     ap.add_argument("--min-nu", type=float, default=2.0)
     ap.add_argument("--max-nu", type=float, default=100.0)
     a = ap.parse_args(argv)
@@ -186,6 +193,14 @@ def main(argv=None):
             region = []
         if a.mode != "decompress" or len(region) != 4:
             ap.error("--region Y0,X0,H,W (four integers) goes with decompress")
+    size = None
+    if a.size is not None:
+        try:
+            size = [int(v) for v in a.size.split(",")]
+        except ValueError:
+            size = []
+        if region is None or len(size) != 2:
+            ap.error("--size OH,OW (two integers) goes with decompress --region")
     if a.scale is not None and a.mode != "compress":
         ap.error("--scale goes with compress")
     if a.mode == "decompress" and not a.dst.endswith(".npy"):
@@ -217,6 +232,17 @@ def main(argv=None):
               f"overlap {h['overlap']}" + (f", max_error {h['max_error']}" if "max_error" in h else "")
               + (f", nodata {h['nodata']}: {h['coded']} coded tile(s)" if "nodata" in h else "")
               + (f", scale {h['scale']}" if "scale" in h else ""))
+    elif size is not None:
+        given = any(s == "--level" or s.startswith("--level=") for s in (sys.argv[1:] if argv is None else argv))
+        stats = {}
+        with open(a.src, "rb") as f, codec.ImageReader(model, f, batch=a.batch) as reader:
+            img = reader.read(*region, size=tuple(size), level=a.level if given else None, out=a.out,
+                              resampling=a.resampling, stats=stats)
+            stats["bytes_read"] = reader.stats["bytes_read"]                  # the heads included
+        path = write_image(a.dst, img)
+        print(f"[dsic_image] window {region[2]}x{region[3]} at ({region[0]}, {region[1]}) as {size[0]}x{size[1]} "
+              f"({a.resampling}) from level {stats['level']}: {len(stats['tiles'])} tile(s), "
+              f"{stats['bytes_read']} of {os.path.getsize(a.src)} bytes read -> {path}")
     elif region is not None:
         stats = {}
         with open(a.src, "rb") as f:

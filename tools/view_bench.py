@@ -1,0 +1,141 @@
+"""Pan and zoom: codec.ImageReader against one decompress_region call per frame, and the resampling kernel alone.
+
+    python tools/view_bench.py [--size 4096] [--tile 256] [--reps 3] [--json profiles/view_bench.json]
+
+The scene of image_codec_bench.py (synthetic patches side by side, uint8) is coded once with overviews=3.  A viewport
+of 768 rows x 1024 columns pans right in 32 steps of 64 pixels (33 frames).  Per frame, alternately in one process:
+  reader   ImageReader.read of the window (one reader per pass, so frame 0 starts with an empty cache)
+  region   decompress_region of the window, which is unchanged by the reader's arrival and so is the way without it
+then the same frames as a 384 x 512 view: the reader's read(..., size=(384, 512)) (level 1, resampled) against
+decompress_region of that level's covering window (what a caller could do before: no resampling, a grid of its own).
+Every frame is wall clock around the call and a device synchronise; one untimed pass warms every shape, then --reps
+passes, and a frame's figure is the median over the passes.  Last, dsic_window_resample_u8 alone on three shapes,
+device events around 50 launches after 5 warm-up launches, with the bytes it must move (source window + output).
+Records, not bars."""
+from __future__ import annotations
+
+import argparse
+import json
+import os
+import statistics
+import sys
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+if ROOT not in sys.path:
+    sys.path.insert(0, ROOT)
+
+VIEW_H, VIEW_W, STEP, STEPS, SIZE = 768, 1024, 64, 32, (384, 512)
+
+
+def _frame_ms(fn):
+    import torch
+    t0 = time.perf_counter()
+    fn()
+    torch.cuda.synchronize()
+    return (time.perf_counter() - t0) * 1e3
+
+
+def _summary(per_pass):
+    """per_pass[p][k] = ms of frame k in pass p -> the medians over the passes, summarised"""
+    frames = [statistics.median(col) for col in zip(*per_pass)]
+    return {"first_frame_ms": round(frames[0], 3), "later_frames_median_ms": round(statistics.median(frames[1:]), 3),
+            "later_frames_max_ms": round(max(frames[1:]), 3), "sequence_ms": round(sum(frames), 2),
+            "frames_ms": [round(f, 3) for f in frames]}
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--size", type=int, default=4096)
+    ap.add_argument("--tile", type=int, default=256)
+    ap.add_argument("--batch", type=int, default=64)
+    ap.add_argument("--reps", type=int, default=3)
+    ap.add_argument("--json", default=os.path.join(ROOT, "profiles", "view_bench.json"))
+    a = ap.parse_args()
+
+    import numpy as np
+    import torch
+    from dsic_amd import codec, lib
+    from dsic_amd import synthetic as S
+    from dsic_amd.model import CompressionModel
+    from dsic_amd.ops import _p, _stream
+
+    if not torch.cuda.is_available():
+        raise SystemExit("view_bench: no GPU; nothing is measured without one")
+    sd = S.make_state_dict(seed=1)
+    model = CompressionModel(N=128, M=192, spatial_params=False, min_nu=2, max_nu=100.0)
+    model.load_state_dict({k: torch.from_numpy(v) for k, v in sd.items()}, strict=True)
+    model = model.cuda().eval()
+    per = a.size // a.tile
+    p = S.make_patches(0, per * per, a.tile, a.tile)
+    scene = (p.reshape(per, per, 3, a.tile, a.tile).transpose(0, 3, 1, 4, 2).reshape(a.size, a.size, 3) * 255 + 0.5)
+    img = torch.from_numpy(scene.astype(np.uint8)).cuda()
+    stream = codec.compress_image(model, img, tile=a.tile, batch=a.batch, overviews=3)
+    y0, x_first = 1000, 500
+    frames = [(y0, x_first + STEP * k, VIEW_H, VIEW_W) for k in range(STEPS + 1)]
+    assert frames[-1][1] + VIEW_W <= a.size and y0 + VIEW_H <= a.size
+    level = codec.view_level(4, VIEW_H, VIEW_W, *SIZE)
+
+    def one_pass(timed):
+        rows = {"reader": [], "region": [], "reader_view": [], "region_level": []}
+        with codec.ImageReader(model, stream, batch=a.batch) as r:
+            for win in frames:
+                rows["reader"].append(_frame_ms(lambda: r.read(*win)))
+                rows["region"].append(_frame_ms(lambda: codec.decompress_region(model, stream, *win, batch=a.batch)))
+            stats = r.stats
+        with codec.ImageReader(model, stream, batch=a.batch) as r:
+            for win in frames:
+                lw = codec.level_window(level, *win)
+                rows["reader_view"].append(_frame_ms(lambda: r.read(*win, size=SIZE)))
+                rows["region_level"].append(_frame_ms(lambda: codec.decompress_region(model, stream, *lw, level=level,
+                                                                                      batch=a.batch)))
+        return rows, stats
+
+    # the results are the same pixels: checked once, outside the timed passes
+    with codec.ImageReader(model, stream, batch=a.batch) as r:
+        for win in (frames[0], frames[7], frames[-1]):
+            assert torch.equal(r.read(*win), codec.decompress_region(model, stream, *win, batch=a.batch))
+    one_pass(False)                                                        # warm-up: every shape of the timed passes
+    passes = [one_pass(True) for _ in range(a.reps)]
+    res = {"scene": f"{a.size}x{a.size} uint8, tile {a.tile}, overviews 3, {len(stream)} bytes",
+           "viewport": [VIEW_H, VIEW_W], "step": STEP, "frames": len(frames), "view_size": list(SIZE),
+           "view_level": level, "reps": a.reps,
+           "reader_counters_of_one_pan": {k: v for k, v in passes[0][1].items()}}
+    for key in ("reader", "region", "reader_view", "region_level"):
+        res[key] = _summary([rows[key] for rows, _ in passes])
+
+    # the kernel alone
+    L = lib.load()
+    kernel = []
+    for name, (sh, sw, shift, region, size) in {
+            "viewport 768x1024 of level 0 -> 384x512": (768, 1024, 0, (0, 0, 768, 1024), SIZE),
+            "its covering window of level 1 -> 384x512": (385, 513, 1, (1000, 501, 768, 1024), SIZE),
+            "whole level 0 -> 2048x2048": (a.size, a.size, 0, (0, 0, a.size, a.size), (a.size // 2, a.size // 2))}.items():
+        src = torch.randint(0, 256, (sh, sw, 3), dtype=torch.uint8, device="cuda")
+        dst = torch.empty((size[0], size[1], 3), dtype=torch.uint8, device="cuda")
+        sy0, sx0 = region[0] >> shift, region[1] >> shift
+
+        def launch():
+            lib.check(L.dsic_window_resample_u8(_p(src), sh, sw, sy0, sx0, 3, shift, *region, _p(dst), size[0], size[1],
+                                                0, -1, _stream()), "window_resample_u8")
+        for _ in range(5):
+            launch()
+        start, end = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        n = 50
+        start.record()
+        for _ in range(n):
+            launch()
+        end.record()
+        torch.cuda.synchronize()
+        us = start.elapsed_time(end) * 1e3 / n
+        moved = sh * sw * 3 + size[0] * size[1] * 3
+        kernel.append({"case": name, "us_per_launch": round(us, 2), "bytes_moved": moved,
+                       "GB_per_s": round(moved / us / 1e3, 1)})
+    res["resample_kernel_u8"] = kernel
+    print(json.dumps(res))
+    with open(a.json, "w") as f:
+        json.dump(res, f, indent=1)
+
+
+if __name__ == "__main__":
+    main()
