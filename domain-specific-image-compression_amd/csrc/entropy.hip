@@ -31,7 +31,7 @@
 
 namespace dsic {
 
-// meta[b] = {ymin - tail, Ly, zmin - tail, Lz}: :39-41, :52-54 (values are
+// meta[b] = {ymin - tail, Ly, zmin - tail, Lz}: :39-41, :52-54 (the model's values are
 // integers already, so floor/ceil are the identity).
 __global__ __launch_bounds__(256) void support_kernel(const float* __restrict__ y,
                                                       const float* __restrict__ z,
@@ -85,8 +85,9 @@ __global__ __launch_bounds__(256) void support_kernel(const float* __restrict__ 
 // truncation, spreading) runs one entry per lane; the two order-sensitive reductions keep the serial order of the
 // host function - the float32 sum (torch's cascade) is evaluated by every lane alike, the float64 running sum walks
 // the entries through v_readlane.  Same operations on the same operands: the tables are bit-identical to
-// dm::finish_table (tests/test_gpu_entropy.py compares them with the host entry point).  F[0..L] is overwritten
-// with the rounded prefixes.
+// dm::finish_table (tests/test_gpu_entropy.py compares them with the host entry point, tests/test_gpu_table_elements.py
+// with the oracle over the whole parameter domain).  F[0..L] is overwritten with the rounded prefixes; the last one
+// (and with it the `c < 1.0f` select) feeds only raw[L] of the host function: out[k] reads prefix k - 1.
 __device__ __forceinline__ void finish_table_wave(float* F, int L, uint16_t* out, float* pmf, int lane) {
   for (int k = lane; k < L; k += 64) {
     float p = F[k + 1] - F[k];

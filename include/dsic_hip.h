@@ -353,17 +353,25 @@ int dsic_sqerr_per_image(const float* a, const float* b, double* out, int B,
  * code/modelv2/eval_selfcontained_entropy.py:26-123 and the torchac 0.9.3
  * calls inside them (third-party; :48,62,96,116).  The script cannot execute
  * as written; the frozen interpretation is in DESIGN.md.
- * err: device int, OR-ed with 1 (support wider than Lmax), 2 (symbol outside
- * its support), 4 (output capacity exceeded); callers zero it first. */
+ * err: device int, OR-ed with 1 (a support with L < 1 or L > Lmax), 2 (symbol
+ * outside its support), 4 (output capacity exceeded); callers zero it first. */
 
-/* :39-41,52-54: meta[b] = {min(y)-tail, Ly, min(z)-tail, Lz}, L = max-min+2*tail+1.
- * y_nchw/z_nchw: integer-valued float latents (y_tilde, z_tilde), n_* per image. */
+/* :39-41,52-54: meta[b] = {floor(min(y))-tail, Ly, floor(min(z))-tail, Lz},
+ * L = ceil(max)-floor(min)+2*tail+1, tail >= 0.
+ * y_nchw/z_nchw: float latents (y_tilde, z_tilde: integer-valued), n_* >= 1 per image.
+ * Only |v| < 1e9 is admitted: a NaN, an infinity or a larger magnitude anywhere in y (z)
+ * of an image sets that half of meta[b] to (0, 0), which every consumer refuses with err
+ * bit 1; the other half and the other images are unaffected. */
 int dsic_latent_support(const float* y_nchw, const float* z_nchw, int* meta,
                         int B, int64_t n_y, int64_t n_z, int tail, void* stream);
 
 /* :43-47 gaussian PMF -> pmf_to_uint16_cdf (:17-23) -> spread table.
  * sigma_z [N] = exp(z_prior.log_sigma) (:32, no clamp); tables [B][N][Lmax]
- * uint16, entry k = c[k] for k < L_b (c[L_b] = 65536 implicit). */
+ * uint16, entry k = c[k] for k < L_b (c[L_b] = 65536 implicit).
+ * Both table calls: any sigma >= 0 is accepted, 0 and inf included (NaN is undefined),
+ * and any nu > 0; nothing is clamped.  Exactly the entries [0, L_b) of a row are written;
+ * an image whose support has L_b < 1 or L_b > Lmax raises err bit 1 and none of its rows
+ * is touched, while the other images of the call get their tables.  1 <= Lmax <= 1000. */
 int dsic_cdf_tables_gauss(const float* sigma_z, const int* meta,
                           uint16_t* tables, int B, int N, int Lmax, int* err,
                           void* stream);
