@@ -64,6 +64,17 @@ the last row or column of an odd side counted twice; uint8 and uint16 (a + b + c
 (c + d)) * 0.25f), and every level's bytes are the DSICI stream compress_image writes for that level's image, so a level is
 read, indexed and decoded on its own (level=l of the decoders and of stream_index) through a view of its byte range.
 
+valid = mask (a torch.bool [H,W] plane beside a uint8 or uint16 image, True = the pixel holds data) with fill = f is
+stream version 8, the general form of the nodata mask: nothing is guessed from pixel values.  Layout: the version-1
+head | segments u32 | overlap u32 = 0 | fill u32 | coded u32 | kind 2 only: C x (lo u32, hi u32) | u64 length, mask
+block | ceil(coded / batch) x (u64 length, container).  Kind is 0 or 2; the mask block is mask.py's, a set bit meaning
+owned, inside the image and invalid, its nodata field carrying fill; states, coded tiles and containers are as in
+version 5, and the coded tiles' strings are those of the stream without the mask (version 1 / 2, or version 6 with the
+same scale).  The decoders write fill at every invalid pixel and can return the mask (with_valid, decompress_valid).
+With overviews the levels come from the masked halving (build_overviews with valid): of the four taps k are valid with
+the sum S, the output is valid iff k > 0 and is (2 S + k) // (2 k), and for k = 0 the unmasked mean; every level is the
+version-8 stream of its own image and mask, with level 0's fill and scale.  Version 7 is unassigned.
+
 ImageReader (view.py) keeps a stream open for pan and zoom: levels opened once, decoded tiles cached on the device and
 assembled by the calls decompress_region makes (_assemble_window), requests decoded together (read_many), and windows
 resampled to a size asked for from the level view_level picks (csrc/view.hip).
@@ -92,6 +103,7 @@ VERSION_OV = 3             # version 1 + the segments word + the overlap word; w
 VERSION_RES = 4            # the version-3 head with overlap 0 + max_error u32 + res_bands u32; a residual block per batch
 VERSION_MASK = 5           # the version-3 head with overlap 0 + nodata u32 + coded u32; a mask block, then the coded tiles' batches
 VERSION_U16 = 6            # the version-3 head (overlap 0 allowed) + C x (lo u32, hi u32), the per-band scale; kind 2 only
+VERSION_VALID = 8          # the version-3 head with overlap 0 + fill u32 + coded u32 (+ the scale for kind 2); a mask block, then the coded tiles' batches
 BLEND_IDS = 64             # tiles per dsic_tile_blend_window_f32 call
 KIND_U8_HWC, KIND_F32_CHW, KIND_U16_HWC = 0, 1, 2
 _HEAD = struct.Struct("<6sHI6I4I2I")
@@ -104,7 +116,7 @@ PMAGIC = b"DSICP\x00"
 PVERSION = 1
 _PHEAD = struct.Struct("<6sHI")                                            # magic, version, levels
 _PLEVEL = struct.Struct("<IIQQ")                                           # H, W, offset, length
-_SAME_IN_LEVELS = ("C", "kind", "N", "M", "in_ch", "spatial_params", "numerics", "scale")
+_SAME_IN_LEVELS = ("C", "kind", "N", "M", "in_ch", "spatial_params", "numerics", "scale", "fill")
 
 
 def _ceil16(n):
@@ -210,12 +222,43 @@ def pack_image_stream(header: dict, blobs, residuals=None, mask=None) -> bytes:
     of tiles that are not empty, counted from the block's states), then `u64 length, mask` with `mask` the mask block
     (mask.pack_block), then the containers of the coded tiles, `batch` to a container; there may be none.
     A header with "scale" = [(lo, hi)] * C (not None) writes version 6, the uint16 image: kind must be 2 (and kind 2
-    needs a scale); segments word, overlap word (0 allowed), then lo, hi per band; no max_error, no nodata."""
+    needs a scale); segments word, overlap word (0 allowed), then lo, hi per band; no max_error, no nodata.
+    A header with "fill" = f (not None) writes version 8, the validity mask: kind 0 or 2; segments word, overlap word
+    0, fill, coded (counted from the block's states; a "coded" in the header must agree), for kind 2 the scale, then
+    `u64 length, mask` with `mask` the mask block whose nodata field is f, then the coded tiles' containers; no
+    overlap, max_error or nodata."""
     h = header
     K = entropy.check_segments(h.get("segments", 1), h["M"], "pack_image_stream")
     O = _check_overlap(h.get("overlap", 0), h["th"], h["tw"], "pack_image_stream")
     if (h.get("scale") is not None) != (h["kind"] == KIND_U16_HWC):
         raise ValueError("pack_image_stream: a scale goes with kind 2 (uint16 [H,W,C]), and only with it")
+    if h.get("fill") is not None:
+        if h["kind"] not in (KIND_U8_HWC, KIND_U16_HWC):
+            raise ValueError(f"pack_image_stream: a validity mask goes with kind {KIND_U8_HWC} or {KIND_U16_HWC}, not "
+                             f"kind {h['kind']}")
+        v = _mask.check_fill(h["fill"], 65535 if h["kind"] == KIND_U16_HWC else 255, "pack_image_stream")
+        if O or h.get("max_error") is not None or residuals is not None or h.get("nodata") is not None:
+            raise ValueError("pack_image_stream: a validity mask together with overlap > 0, max_error or nodata is not "
+                             "supported")
+        if mask is None:
+            raise ValueError("pack_image_stream: fill needs the mask block")
+        mask = bytes(mask)
+        n = _grid(h["H"], h["W"], h["th"], h["tw"])["n"]
+        states, _ = _mask.read_block_head(lambda o, c: mask[o:o + c], 0, len(mask), n, h["th"], h["tw"], v,
+                                          "pack_image_stream")
+        coded = sum(1 for s in states if s != _mask.EMPTY)
+        if h.get("coded", coded) != coded:
+            raise ValueError(f"pack_image_stream: the header says {h['coded']} coded tiles, the mask block's states "
+                             f"{coded}")
+        if len(blobs) != -(-coded // h["batch"]):
+            raise ValueError(f"pack_image_stream: {len(blobs)} containers for {coded} coded tiles in batches of "
+                             f"{h['batch']}")
+        head = _HEAD.pack(MAGIC, VERSION_VALID, h["numerics"] & 0xFFFFFFFF, h["H"], h["W"], h["C"], h["kind"], h["th"],
+                          h["tw"], h["N"], h["M"], h["in_ch"], h["spatial_params"], h["batch"], len(blobs))
+        head += _SEGS.pack(K) + _SEGS.pack(0) + _MASK.pack(v, coded)
+        if h["kind"] == KIND_U16_HWC:
+            head += b"".join(_SCALE.pack(lo, hi) for lo, hi in check_scale(h["scale"], h["C"], "pack_image_stream"))
+        return b"".join([head, _LEN.pack(len(mask)), mask] + [_LEN.pack(len(b)) + bytes(b) for b in blobs])
     if h.get("scale") is not None:
         scale = check_scale(h["scale"], h["C"], "pack_image_stream")
         if h.get("nodata") is not None or h.get("max_error") is not None or residuals is not None or mask is not None:
@@ -311,18 +354,22 @@ def _read_framing(src, head=None):
     keys = ("version", "numerics", "H", "W", "C", "kind", "th", "tw", "N", "M", "in_ch", "spatial_params", "batch",
             "batches")
     h = dict(zip(keys, f[1:]))
-    if h["version"] not in (VERSION, VERSION_SEG, VERSION_OV, VERSION_RES, VERSION_MASK, VERSION_U16):
+    if h["version"] not in (VERSION, VERSION_SEG, VERSION_OV, VERSION_RES, VERSION_MASK, VERSION_U16, VERSION_VALID):
         raise ValueError(f"DSICI stream version {h['version']}, this reader knows {VERSION}, {VERSION_SEG}, "
-                         f"{VERSION_OV}, {VERSION_RES}, {VERSION_MASK} and {VERSION_U16}")
-    if (h["version"] == VERSION_U16) != (h["kind"] == KIND_U16_HWC):
+                         f"{VERSION_OV}, {VERSION_RES}, {VERSION_MASK}, {VERSION_U16} and {VERSION_VALID}")
+    if h["version"] == VERSION_VALID:
+        if h["kind"] not in (KIND_U8_HWC, KIND_U16_HWC):
+            raise ValueError(f"DSICI stream: version {VERSION_VALID} with kind {h['kind']} (a validity mask goes with "
+                             f"kind {KIND_U8_HWC} or {KIND_U16_HWC})")
+    elif (h["version"] == VERSION_U16) != (h["kind"] == KIND_U16_HWC):
         raise ValueError(f"DSICI stream: version {h['version']} with kind {h['kind']} (version {VERSION_U16} and kind "
                          f"{KIND_U16_HWC}, the uint16 image, go together)")
-    if h["version"] == VERSION_U16 and not 1 <= h["C"] <= 4:
+    if h["kind"] == KIND_U16_HWC and not 1 <= h["C"] <= 4:
         raise ValueError(f"DSICI stream: a uint16 image of {h['C']} bands (1 .. 4)")
     off, h["segments"], h["overlap"] = _HEAD.size, 1, 0
-    if h["version"] in (VERSION_SEG, VERSION_OV, VERSION_RES, VERSION_MASK, VERSION_U16):
-        words = {VERSION_SEG: 1, VERSION_OV: 2, VERSION_RES: 4, VERSION_MASK: 4,
-                 VERSION_U16: 2 + 2 * h["C"]}[h["version"]]
+    if h["version"] in (VERSION_SEG, VERSION_OV, VERSION_RES, VERSION_MASK, VERSION_U16, VERSION_VALID):
+        words = {VERSION_SEG: 1, VERSION_OV: 2, VERSION_RES: 4, VERSION_MASK: 4, VERSION_U16: 2 + 2 * h["C"],
+                 VERSION_VALID: 4 + (2 * h["C"] if h["kind"] == KIND_U16_HWC else 0)}[h["version"]]
         word = src.read_at(off, words * _SEGS.size)
         if len(word) < words * _SEGS.size:
             raise ValueError("truncated DSICI stream")
@@ -361,6 +408,20 @@ def _read_framing(src, head=None):
                                  "supported)")
             if h["nodata"] > 255:
                 raise ValueError(f"DSICI stream: nodata={h['nodata']} (0 .. 255)")
+        if h["version"] == VERSION_VALID:
+            overlap, h["fill"], h["coded"] = struct.unpack_from("<3I", word, _SEGS.size)
+            if overlap != 0:
+                raise ValueError(f"DSICI stream: version 8 with overlap={overlap} (a mask over blended tiles is not "
+                                 "supported)")
+            top = 65535 if h["kind"] == KIND_U16_HWC else 255
+            if h["fill"] > top:
+                raise ValueError(f"DSICI stream: fill={h['fill']} (0 .. {top} for kind {h['kind']})")
+            if h["kind"] == KIND_U16_HWC:
+                h["scale"] = [_SCALE.unpack_from(word, 4 * _SEGS.size + _SCALE.size * c) for c in range(h["C"])]
+                for lo, hi in h["scale"]:
+                    if lo > hi or hi > 65535:
+                        raise ValueError(f"DSICI stream: scale pair ({lo}, {hi}) must have lo <= hi <= 65535")
+        if h["version"] in (VERSION_MASK, VERSION_VALID):
             if off + _LEN.size > src.size:
                 raise ValueError("truncated DSICI stream")
             (size,) = _LEN.unpack(src.read_at(off, _LEN.size))
@@ -391,13 +452,16 @@ def unpack_image_stream(stream) -> dict:
     blocks; the dicts of versions 1 to 3 have neither key.  A version-5 stream gives "nodata", "coded" (the tiles that
     are not empty: the containers hold these, in ascending tile number), "mask_offset", "mask_bytes" and "mask", its
     mask block (mask.py); no other version has these keys.  A version-6 stream (kind 2, the uint16 image) gives
-    "scale", the list of its C pairs (lo, hi); no other version has that key."""
+    "scale", the list of its C pairs (lo, hi); no other version has that key.  A version-8 stream (a validity mask;
+    kind 0 or 2) gives "fill", "coded", "mask_offset", "mask_bytes", "mask" and, for kind 2, "scale"; it has no "nodata"
+    key.  ValueError also for a version-8 head with kind 1, overlap != 0, a fill beyond the kind's range or a bad
+    scale pair."""
     s = bytes(stream)
     h, frames, rframes = _read_framing(_Source(s))
     h["blobs"] = [s[off:off + size] for off, size in frames]
     if h["version"] == VERSION_RES:
         h["residuals"] = [s[off:off + size] for off, size in rframes]
-    if h["version"] == VERSION_MASK:
+    if h["version"] in (VERSION_MASK, VERSION_VALID):
         h["mask"] = s[h["mask_offset"]:h["mask_offset"] + h["mask_bytes"]]
     return h
 
@@ -471,19 +535,47 @@ def _image_kind(img, what):
     raise TypeError(f"{what}: expected uint8, uint16 or float32, got {img.dtype}")
 
 
+def _check_valid(valid, H, W, what):
+    """valid as compress_image takes it: a torch.bool [H,W] tensor, else ValueError."""
+    if not isinstance(valid, torch.Tensor) or valid.dtype != torch.bool or tuple(valid.shape) != (H, W):
+        got = f"{valid.dtype} {tuple(valid.shape)}" if isinstance(valid, torch.Tensor) else type(valid).__name__
+        raise ValueError(f"{what}: valid must be a torch.bool [{H}, {W}] tensor (True = the pixel holds data), got {got}")
+
+
 @torch.no_grad()
-def build_overviews(img, n) -> list:
+def build_overviews(img, n, valid=None):
     """[img, level 1, ..., level n] on the device: img uint8 or uint16 [H,W,C] or float32 [C,H,W] on the GPU, each
     level the one before it halved by dsic_image_halve_u8 / _u16 / _f32 (one launch per level): ceil(H/2) x ceil(W/2),
     a pixel the mean of its 2 x 2 block, the last row or column of an odd side counted twice; uint8 and uint16 round
     half up, (a + b + c + d + 2) >> 2, float32 is ((a + b) + (c + d)) * 0.25f.  The sizes are
-    overview_shapes(H, W, n)."""
+    overview_shapes(H, W, n).
+    valid: a torch.bool [H,W] mask on the GPU beside a uint8 or uint16 image (True = the pixel holds data) -> (levels,
+    masks), the masked halving (dsic_image_halve_valid_u8 / _u16, one launch per level): of the same four taps k are
+    valid, with the sum S per channel; the output pixel is valid iff k > 0 and is (2 S + k) // (2 k), the mean over the
+    valid taps rounded half up, and for k = 0 the unmasked mean of the four taps.  With an all-True mask every level
+    is the level without a mask, bit for bit."""
     kind, H, W, C = _image_kind(img, "build_overviews")
     if not img.is_cuda:
         raise RuntimeError(f"build_overviews: expected a tensor on the GPU (no CPU fallback), got {img.device}")
     shapes = overview_shapes(H, W, n)
     L = _lib.load()
     levels = [img.contiguous()]
+    if valid is not None:
+        if kind == KIND_F32_CHW:
+            raise ValueError("build_overviews: a validity mask goes with a uint8 or uint16 [H,W,C] image, not float32")
+        _check_valid(valid, H, W, "build_overviews")
+        if not valid.is_cuda:
+            raise RuntimeError(f"build_overviews: expected the mask on the GPU (no CPU fallback), got {valid.device}")
+        masks = [valid.to(torch.uint8).contiguous()]
+        suffix, dtype = ("u8", torch.uint8) if kind == KIND_U8_HWC else ("u16", torch.uint16)
+        for (h, w), (h2, w2) in zip(shapes, shapes[1:]):
+            dst = torch.empty((h2, w2, C), dtype=dtype, device=img.device)
+            dval = torch.empty((h2, w2), dtype=torch.uint8, device=img.device)
+            _lib.check(getattr(L, "dsic_image_halve_valid_" + suffix)(_p(levels[-1]), _p(masks[-1]), _p(dst), _p(dval), h,
+                                                                      w, C, _stream()), "image_halve_valid_" + suffix)
+            levels.append(dst)
+            masks.append(dval)
+        return levels, [m.bool() for m in masks]
     for (h, w), (h2, w2) in zip(shapes, shapes[1:]):
         src = levels[-1]
         if kind == KIND_U8_HWC:
@@ -630,10 +722,11 @@ def unpack_pyramid_stream(stream) -> dict:
     return {"version": PVERSION, "levels": levels}
 
 
-def band_range(img) -> list:
+def band_range(img, valid=None) -> list:
     """[(lo, hi), ...]: per band the minimum and maximum of a uint16 [H,W,C] image on the GPU (dsic_band_range_u16:
     one pass over the image on many workgroups, then one small copy to the host).  The default scale of
-    compress_image."""
+    compress_image.  valid: a torch.bool or uint8 [H,W] mask on the GPU; then over the valid pixels only
+    (dsic_band_range_valid_u16), and a band without a valid pixel is (0, 0)."""
     kind, H, W, C = _image_kind(img, "band_range")
     if kind != KIND_U16_HWC:
         raise TypeError(f"band_range: expected uint16 [H,W,C], got {img.dtype}")
@@ -641,7 +734,14 @@ def band_range(img) -> list:
         raise RuntimeError(f"band_range: expected a tensor on the GPU (no CPU fallback), got {img.device}")
     img = img.contiguous()
     out = torch.empty(2 * C, dtype=torch.int32, device=img.device)
-    _lib.check(_lib.load().dsic_band_range_u16(_p(img), H, W, C, _p(out), _stream()), "band_range_u16")
+    if valid is not None:
+        if tuple(valid.shape) != (H, W) or valid.dtype not in (torch.bool, torch.uint8) or valid.device != img.device:
+            raise ValueError(f"band_range: valid must be a bool or uint8 [{H}, {W}] tensor on {img.device}")
+        valid = valid.to(torch.uint8).contiguous()
+        _lib.check(_lib.load().dsic_band_range_valid_u16(_p(img), _p(valid), H, W, C, _p(out), _stream()),
+                   "band_range_valid_u16")
+    else:
+        _lib.check(_lib.load().dsic_band_range_u16(_p(img), H, W, C, _p(out), _stream()), "band_range_u16")
     v = [int(x) & 0xFFFFFFFF for x in out.cpu().tolist()]
     return list(zip(v[0::2], v[1::2]))
 
@@ -689,41 +789,58 @@ def _level_grid(H, W, kind, tile, overlap, tau):
     return g, overlap
 
 
-def _compress_masked(model, x, g, C, batch, tail, segments, nodata, header) -> bytes:
+def _compress_masked(model, x, g, C, batch, tail, segments, nodata, header, valid=None, fill=0, scale=None) -> bytes:
     """The version-5 stream of a uint8 image on the device: classify the tiles, code those that are not empty (a
     batch is gathered run by run of consecutive tile numbers into slices of one tensor, so every tile's strings are
-    those of the stream without nodata), and put the mixed tiles' masks into the mask block."""
+    those of the stream without nodata), and put the mixed tiles' masks into the mask block.
+    valid (uint8 [H,W] on the device, 0 = invalid): the version-8 stream of a uint8 or uint16 image instead; the states
+    and the planes come from the mask itself (dsic_valid_classify, dsic_valid_delta_planes), and a uint16 image is
+    gathered with its scale, as the version-6 stream's tiles are."""
     owned = [_owned_in_tile(g, t) for t in range(g["n"])]
-    states = _mask.tile_states(_mask.classify(x, g, C, nodata), [(b - a) * (d - c) for a, b, c, d in owned])
+    counts = _mask.classify(x, g, C, nodata) if valid is None else _mask.classify_valid(valid, g)
+    states = _mask.tile_states(counts, [(b - a) * (d - c) for a, b, c, d in owned])
     ids = [t for t, s in enumerate(states) if s != _mask.EMPTY]
     L, blobs = _lib.load(), []
+    u16 = x.dtype == torch.uint16
     for first in range(0, len(ids), batch):
         sel = ids[first:first + batch]
-        tiles = torch.empty((len(sel), g["th"], g["tw"], C), dtype=torch.uint8, device=x.device)
+        tiles = (torch.empty((len(sel), C, g["th"], g["tw"]), dtype=torch.float32, device=x.device) if u16 else
+                 torch.empty((len(sel), g["th"], g["tw"], C), dtype=torch.uint8, device=x.device))
         a = 0
         while a < len(sel):
             b = a + 1
             while b < len(sel) and sel[b] == sel[b - 1] + 1:
                 b += 1
-            _lib.check(L.dsic_tile_gather_u8(_p(x), _p(tiles[a:b]), g["H"], g["W"], C, g["th"], g["tw"], sel[a], b - a,
-                                             _stream()), "tile_gather_u8")
+            if u16:
+                _lib.check(L.dsic_tile_gather_u16(_p(x), _p(tiles[a:b]), g["H"], g["W"], C, g["th"], g["tw"], _lohi(scale),
+                                                  sel[a], b - a, _stream()), "tile_gather_u16")
+            else:
+                _lib.check(L.dsic_tile_gather_u8(_p(x), _p(tiles[a:b]), g["H"], g["W"], C, g["th"], g["tw"], sel[a], b - a,
+                                                 _stream()), "tile_gather_u8")
             a = b
         blobs.append(entropy.compress_to_container(model, tiles, tail, segments=segments))
-    header["nodata"] = nodata
-    return pack_image_stream(header, blobs, mask=_mask.encode_block(x, g, C, nodata, states))
+    if valid is None:
+        header["nodata"] = nodata
+        return pack_image_stream(header, blobs, mask=_mask.encode_block(x, g, C, nodata, states))
+    header["fill"] = fill
+    if u16:
+        header["scale"] = scale
+    return pack_image_stream(header, blobs, mask=_mask.encode_block(valid, g, None, fill, states))
 
 
-def _compress_device_image(model, x, tile, batch, tail, segments, overlap, tau, nodata=None, scale=None) -> bytes:
+def _compress_device_image(model, x, tile, batch, tail, segments, overlap, tau, nodata=None, scale=None, valid=None,
+                           fill=0) -> bytes:
     """compress_image's work on one image that lies contiguous on the model's device, after the argument checks that
     do not depend on its size -> its DSICI stream.  scale: the checked pairs of a uint16 image."""
     kind, H, W, C = _image_kind(x, "compress_image")
     N, M, in_ch, spatial = _model_shape(model)
     g, overlap = _level_grid(H, W, kind, tile, overlap, tau)
-    if nodata is not None:
+    if nodata is not None or valid is not None:
         return _compress_masked(model, x, g, C, batch, tail, segments, nodata,
                                 {"numerics": entropy.numerics_tag(), "H": H, "W": W, "C": C, "kind": kind,
                                  "th": g["th"], "tw": g["tw"], "N": N, "M": M, "in_ch": in_ch,
-                                 "spatial_params": spatial, "batch": batch, "segments": segments, "overlap": 0})
+                                 "spatial_params": spatial, "batch": batch, "segments": segments, "overlap": 0},
+                                valid, fill, scale)
     blobs, residuals = [], None if tau is None else []
     for first in range(0, g["n"], batch):
         n = min(batch, g["n"] - first)
@@ -748,7 +865,7 @@ def _compress_device_image(model, x, tile, batch, tail, segments, overlap, tau, 
 
 @torch.no_grad()
 def compress_image(model, img, tile=256, batch=64, tail=10, segments=1, overlap=0, max_error=None,
-                   overviews=0, nodata=None, scale=None) -> bytes:
+                   overviews=0, nodata=None, scale=None, valid=None, fill=0) -> bytes:
     """img: uint8 [H,W,C], uint16 [H,W,C] or float32 [C,H,W] in [0,1], on the CPU or the GPU -> one DSICI stream.  The
     image is uploaded once; each batch of `batch` tiles is gathered on the device (reflect padding included) and becomes one
     DSIC2 container.  segments = K > 1 (1, 2, 4, 8 or 16, dividing M): every tile's y string is K independent strings
@@ -782,10 +899,41 @@ def compress_image(model, img, tile=256, batch=64, tail=10, segments=1, overlap=
     with the same arguments; segments and overlap work unchanged, and the decoders return uint16 by default.  With
     overviews the scale is decided once, at level 0, and every level is written with it (halved values stay inside
     [lo, hi]).  scale with a uint8 or float32 image is a ValueError.  max_error and nodata are refused with a uint16
-    image: the residual tables and the mask classifier are 8-bit, and 16-bit variants are separate work."""
+    image: the residual tables and the mask classifier are 8-bit, and 16-bit variants are separate work.
+    valid = mask (a torch.bool [H,W] tensor on the CPU or the GPU, True = the pixel holds data; uint8 and uint16
+    images, with segments and with overviews) with fill = f (an integer 0 .. 255 for uint8, 0 .. 65535 for uint16, the
+    value the decoders write at invalid pixels): the stream (version 8) keeps that mask exactly (mask.py; the block's
+    nodata field carries fill).  Tiles whose owned pixels inside the image are all invalid are neither gathered, coded
+    nor decoded; the other tiles' strings are byte for byte those of the same call without valid (for uint16: the
+    version-6 stream written with the same scale), and a tile that holds both kinds of pixel carries its mask beside
+    them.  With a uint16 image and scale = None the scale is each band's minimum and maximum over the valid pixels only
+    (band_range(img, valid)); a band without a valid pixel gets (0, 0).  The decoders return f on all channels at every
+    invalid pixel of img (f / 255.0f for a uint8 stream with out="f32"; out="u8" / "f32" on a uint16 stream is a
+    ValueError: the normalised image has no value that means fill), and at every other pixel the bits the stream
+    without valid decodes to; with_valid=True of the decoders and decompress_valid return the mask itself.  With
+    overviews every level is the version-8 stream of that level's image and mask alone (build_overviews(img, n, valid),
+    the masked halving), with level 0's fill and scale.  Out of scope, each a ValueError before anything touches the
+    device: a float32 image; overlap > 0 (blending across skipped tiles needs renormalised ramps); max_error; nodata at
+    the same time (nodata itself is unchanged); a mask of another shape or dtype; fill out of range, or given without
+    valid.  Invalid pixels inside coded tiles are coded as the caller left them: filling them with something smoother
+    is a bit-rate optimisation that would give up the "same strings as the stream without valid" property.  None writes
+    today's streams."""
     dev = next(model.parameters()).device
     tau = None if max_error is None else _residual.check_max_error(max_error, "compress_image")
     kind, H, W, C = _image_kind(img, "compress_image")
+    if valid is None:
+        if not (isinstance(fill, int) and not isinstance(fill, bool) and fill == 0):
+            raise ValueError(f"compress_image: fill={fill!r} goes with valid, the mask it fills")
+    else:
+        if kind == KIND_F32_CHW:
+            raise ValueError("compress_image: a validity mask goes with integer pixel values; pass the image as uint8 or "
+                             "uint16 [H,W,C], not float32")
+        for name, on in (("overlap > 0", overlap != 0), ("max_error", max_error is not None),
+                         ("nodata", nodata is not None)):
+            if on:
+                raise ValueError(f"compress_image: valid together with {name} is not supported")
+        _check_valid(valid, H, W, "compress_image")
+        fill = _mask.check_fill(fill, 65535 if kind == KIND_U16_HWC else 255, "compress_image")
     if kind == KIND_U16_HWC:
         for name, on in (("max_error", max_error is not None), ("nodata", nodata is not None)):
             if on:
@@ -820,6 +968,15 @@ def compress_image(model, img, tile=256, batch=64, tail=10, segments=1, overlap=
         except ValueError as e:
             raise ValueError(f"{e} (overview level {level}, {h}x{w})" if level else str(e)) from None
     x = img.to(dev).contiguous()
+    if valid is not None:
+        v8 = valid.to(dev).to(torch.uint8).contiguous()
+        if kind == KIND_U16_HWC and scale is None:
+            scale = band_range(x, v8)
+        if len(shapes) == 1:
+            return _compress_device_image(model, x, tile, batch, tail, segments, 0, None, None, scale, v8, fill)
+        levels, masks = build_overviews(x, overviews, v8.bool())
+        return pack_pyramid_stream([_compress_device_image(model, lv, tile, batch, tail, segments, 0, None, None, scale,
+                                                           m.to(torch.uint8), fill) for lv, m in zip(levels, masks)])
     if kind == KIND_U16_HWC and scale is None:
         scale = band_range(x)
     if len(shapes) == 1:
@@ -851,7 +1008,8 @@ def _refuse_foreign(model, h, what):
 def _stream_grid(h):
     """The tile grid a DSICI header describes; ValueError where its fields contradict each other."""
     H, W, C, th, tw = h["H"], h["W"], h["C"], h["th"], h["tw"]
-    kinds = (KIND_U16_HWC,) if h["version"] == VERSION_U16 else (KIND_U8_HWC, KIND_F32_CHW)
+    kinds = {VERSION_U16: (KIND_U16_HWC,), VERSION_VALID: (KIND_U8_HWC, KIND_U16_HWC)}.get(h["version"],
+                                                                                           (KIND_U8_HWC, KIND_F32_CHW))
     if C != h["in_ch"] or h["kind"] not in kinds or h["batch"] < 1:
         raise ValueError("DSICI stream: inconsistent header")
     _check_image(H, W)
@@ -890,9 +1048,9 @@ def _index_of(src, head=None):
     g = _stream_grid(ix)
     tiles, containers = [], []
     ids = None                                 # version 5: the grid numbers of the coded tiles, ascending
-    if ix["version"] == VERSION_MASK:
+    if ix["version"] in (VERSION_MASK, VERSION_VALID):
         states, mrecs = _mask.read_block_head(src.read_at, ix["mask_offset"], ix["mask_bytes"], g["n"], ix["th"],
-                                              ix["tw"], ix["nodata"])
+                                              ix["tw"], ix["nodata"] if ix["version"] == VERSION_MASK else ix["fill"])
         ids = [t for t, s in enumerate(states) if s != _mask.EMPTY]
         if len(ids) != ix["coded"]:
             raise ValueError(f"DSICI stream: the head says {ix['coded']} coded tiles, the mask block's states "
@@ -959,6 +1117,8 @@ def stream_index(src, level=None) -> dict:
     empty, 1 full, 2 mixed), for an empty tile k = b = None and zero lengths, for a mixed tile m_off, m_len, m_mode (its
     mask payload, which tile_spans includes); per container ids, the grid numbers of its tiles.  Of the mask block the
     26-byte head, the state bytes and the 12-byte records are read.
+    and for a version-8 stream (a validity mask) fill, coded, mask_offset, mask_bytes, per tile state and m_off, m_len,
+    m_mode, per container ids, exactly as for version 5, and scale for kind 2; the nodata key is not set.
     and for a version-6 stream (only then) scale, the C pairs (lo, hi) of the uint16 image; they add 8 C bytes to the
     version-3 head, which index_bytes counts.
       stream_bytes, index_bytes (what this call read).
@@ -1039,14 +1199,19 @@ def tile_spans(index, tiles, masks=True) -> list:
     return [tuple(s) for s in spans]
 
 
-def _apply_mask(source, ix, tiles, img, kind, window) -> int:
+def _apply_mask(source, ix, tiles, img, kind, window, valid_out=None) -> int:
     """The nodata pixels of a window of a version-5 stream, after its coded tiles have been stitched: the payloads of
     the window's mixed tiles are read, checked (mask.check_payload) and uploaded in one small copy with their
     descriptors, unpacked to m planes (dsic_mask_unpack), and one pass (dsic_mask_apply_u8 / _f32) writes nodata at the
     set bits of the mixed tiles and over the whole owned rectangle of the empty ones; mask.MAX_TILES tiles at a time.
-    Returns the padded payload bytes uploaded."""
-    H, W, C, th, tw, v = ix["H"], ix["W"], ix["C"], ix["th"], ix["tw"], ix["nodata"]
+    Returns the padded payload bytes uploaded.
+    A version-8 stream (a validity mask) goes the same way with its fill in the place of nodata, dsic_mask_apply_u16
+    for a uint16 window.  valid_out: a uint8 [h,w] tensor of ones on the device, or None; the same planes then also
+    give the window's validity (dsic_mask_window_u8).  img None: only that."""
+    H, W, C, th, tw = ix["H"], ix["W"], ix["C"], ix["th"], ix["tw"]
+    v = ix["nodata"] if "nodata" in ix else ix["fill"]
     masked = [t for t in tiles if ix["tiles"][t]["state"] != _mask.FULL]
+    dev = img.device if img is not None else valid_out.device
     uploaded = 0
     for c0 in range(0, len(masked), _mask.MAX_TILES):
         sel = masked[c0:c0 + _mask.MAX_TILES]
@@ -1061,11 +1226,14 @@ def _apply_mask(source, ix, tiles, img, kind, window) -> int:
             words[3 * i:3 * i + 3] = (r["m_mode"], off, r["m_len"])
             off += r["m_len"]
         words[3 * len(mixed):] = np.array([(t, slot.get(t, -1)) for t in sel], dtype=np.int32).ravel()
-        d_blob, total, d_words = entropy._upload_padded(parts, words, img.device)
+        d_blob, total, d_words = entropy._upload_padded(parts, words, dev)
         d_words = d_words.view(torch.int32)
         planes = _mask.unpack_planes(d_blob, total, d_words, len(mixed), th, tw) if mixed else None
-        _mask.apply_window(planes, len(mixed), d_words[3 * len(mixed):], len(sel), v, img, kind == KIND_U8_HWC, H, W, C,
-                           th, tw, *window)
+        if img is not None:
+            _mask.apply_window(planes, len(mixed), d_words[3 * len(mixed):], len(sel), v, img, kind == KIND_U8_HWC, H,
+                               W, C, th, tw, *window)
+        if valid_out is not None:
+            _mask.window_valid(planes, len(mixed), d_words[3 * len(mixed):], len(sel), valid_out, H, W, th, tw, *window)
         uploaded += entropy._padded_bytes(total) if mixed else 0
     return uploaded
 
@@ -1079,12 +1247,16 @@ def _check_out(out, ix, what):
     if out == "u16" and "scale" not in ix:
         raise ValueError(f"{what}: out='u16' needs the scale of a uint16 stream (version {VERSION_U16}); this one is "
                          f"version {ix['version']}")
+    if out in ("u8", "f32") and "fill" in ix and ix["kind"] == KIND_U16_HWC:
+        raise ValueError(f"{what}: out={out!r} on a uint16 stream with a validity mask (version {VERSION_VALID}): the "
+                         "normalised image has no value that means fill")
     return {None: ix["kind"], "u8": KIND_U8_HWC, "f32": KIND_F32_CHW, "u16": KIND_U16_HWC}[out]
 
 
 def _coded_tiles(ix, tiles):
-    """Of a window's tiles those that hold strings: all, or in a version-5 stream those that are not empty."""
-    return tiles if ix.get("nodata") is None else [t for t in tiles if ix["tiles"][t]["state"] != _mask.EMPTY]
+    """Of a window's tiles those that hold strings: all, or in a masked stream (version 5 or 8) those that are not
+    empty."""
+    return tiles if "coded" not in ix else [t for t in tiles if ix["tiles"][t]["state"] != _mask.EMPTY]
 
 
 def _decode_tiles(model, source, ix, sel, what):
@@ -1124,11 +1296,12 @@ def _decode_tiles(model, source, ix, sel, what):
     return x_hat.contiguous(), nbytes, ids, (q[0] if q else None)
 
 
-def _assemble_window(model, source, ix, tiles, window, kind, batches, what):
+def _assemble_window(model, source, ix, tiles, window, kind, batches, what, valid_out=None):
     """The window image from its tiles' decoded batches.  batches yields (x_hat, padded bytes uploaded, ids, q or
     None) as _decode_tiles returns them, the window's coded tiles in ascending order; each is stitched (blended) into
-    the window as it arrives.  Then the nodata pixels (_apply_mask) and the blend's finish.  Returns (the image, the
-    bytes uploaded, the batches taken)."""
+    the window as it arrives.  Then the nodata or invalid pixels (_apply_mask) and the blend's finish.  Returns (the
+    image, the bytes uploaded, the batches taken).  valid_out: None, or a uint8 [h,w] tensor of ones on the device that
+    receives the window's validity (left all ones by a stream without a mask)."""
     H, W, C, th, tw = ix["H"], ix["W"], ix["C"], ix["th"], ix["tw"]
     y0, x0, h, w = window
     lohi = (_lohi(ix["scale"]),) if kind == KIND_U16_HWC else ()        # the uint16 calls take the scale last
@@ -1153,8 +1326,8 @@ def _assemble_window(model, source, ix, tiles, window, kind, batches, what):
                        "tile_stitch_window_" + suffix)
         uploaded += nbytes
         taken += 1
-    if ix.get("nodata") is not None:           # a mask: empty tiles hold no strings, and are filled here
-        uploaded += _apply_mask(source, ix, tiles, img, kind, (y0, x0, h, w))
+    if "coded" in ix:                          # a mask: empty tiles hold no strings, and are filled here
+        uploaded += _apply_mask(source, ix, tiles, img, kind, (y0, x0, h, w), valid_out)
     if O and kind == KIND_F32_CHW:
         _lib.check(L.dsic_tile_blend_finish_f32(_p(canvas), C, h, w, _stream()), "tile_blend_finish_f32")
     elif O and kind == KIND_U16_HWC:
@@ -1166,7 +1339,7 @@ def _assemble_window(model, source, ix, tiles, window, kind, batches, what):
     return img, uploaded, taken
 
 
-def _decode_window(model, src, window, out, batch, stats, what, level=0, opened=None):
+def _decode_window(model, src, window, out, batch, stats, what, level=0, opened=None, with_valid=False):
     """decompress_region's work; window None = the whole image, batch None = the stream's tiles per container.  Of a
     DSICP stream the chosen level is decoded, through a view of its bytes.  opened: (source, index) of a level that
     an ImageReader has opened and checked against the model already; then bytes_read counts from this call on."""
@@ -1183,15 +1356,16 @@ def _decode_window(model, src, window, out, batch, stats, what, level=0, opened=
     coded = _coded_tiles(ix, tiles)
     batches = (_decode_tiles(model, source, ix, coded[first:first + batch], what)
                for first in range(0, len(coded), batch))
-    img, uploaded, decode_batches = _assemble_window(model, source, ix, tiles, window, kind, batches, what)
+    valid = torch.ones(window[2:], dtype=torch.uint8, device=next(model.parameters()).device) if with_valid else None
+    img, uploaded, decode_batches = _assemble_window(model, source, ix, tiles, window, kind, batches, what, valid)
     if stats is not None:
         stats.update(tiles=tiles, decode_batches=decode_batches, bytes_read=source.bytes_read - read0,
                      bytes_uploaded=uploaded)
-    return img
+    return (img, valid.bool()) if with_valid else img
 
 
 @torch.no_grad()
-def decompress_image(model, stream, out=None, level=0):
+def decompress_image(model, stream, out=None, level=0, with_valid=False):
     """DSICI stream -> the image on the model's device: uint8 [H,W,C] ((uint8)(clamp(x,0,1)*255), truncating, as
     torchvision's to_pil_image) or float32 [C,H,W] (clamp(x,0,1)); by default the kind of the encoder's input,
     out="u8" / "f32" overrides it.  The whole image as a window, decoded container by container; each decoded batch
@@ -1204,12 +1378,17 @@ def decompress_image(model, stream, out=None, level=0):
     decodes by default, or with out="u16", to uint16 [H,W,C]: lo + uint32(clamp(x,0,1) * float32(hi - lo) + 0.5f) per
     band with the stream's own scale, rounded to nearest (with overlap: of the blended canvas); out="u8" / "f32" give
     the normalised image as for any other stream, the uint8 one being what the reference's (rgb*255).astype(uint8)
-    saves.  out="u16" on a stream of another version is a ValueError: it has no scale."""
-    return _decode_window(model, stream, None, out, None, None, "decompress_image", level)
+    saves.  out="u16" on a stream of another version is a ValueError: it has no scale.
+    A stream with a validity mask (version 8, compress_image with valid) decodes to fill on all channels at every
+    invalid pixel (fill / 255.0f for a uint8 stream with out="f32") and at every other pixel to the bits the stream
+    without the mask decodes to; out="u8" / "f32" on a uint16 stream with a mask is a ValueError.  with_valid = True
+    returns (image, valid), valid a torch.bool [H,W] on the device: the stream's mask, all True for a stream without
+    one (a version-5 stream gives its nodata mask, inverted)."""
+    return _decode_window(model, stream, None, out, None, None, "decompress_image", level, with_valid=with_valid)
 
 
 @torch.no_grad()
-def decompress_region(model, src, y0, x0, h, w, out=None, batch=64, stats=None, level=0):
+def decompress_region(model, src, y0, x0, h, w, out=None, batch=64, stats=None, level=0, with_valid=False):
     """The window rows [y0, y0+h) x columns [x0, x0+w) of a DSICI stream, decoded from only the tiles that own its
     pixels: uint8 [h,w,C] or float32 [C,h,w] on the model's device, the same bytes decompress_image(...) gives there
     (out as in decompress_image).  src: the stream as bytes, or a binary file object, of which only the heads
@@ -1220,11 +1399,28 @@ def decompress_region(model, src, y0, x0, h, w, out=None, batch=64, stats=None, 
     bytes_read and bytes_uploaded (the padded string bytes; 52 bytes of descriptors per tile travel beside them).
     level: of a DSICP stream, the overview level to decode; the window is in that level's own pixel grid
     (level_window maps a level-0 window to it), and only the directory, that level's heads and its selected tiles'
-    strings are read."""
+    strings are read.  with_valid = True returns (image, valid) as decompress_image does, valid a torch.bool [h,w]."""
     batch = int(batch)
     if batch < 1:
         raise ValueError(f"decompress_region: batch={batch}")
-    return _decode_window(model, src, (y0, x0, h, w), out, batch, stats, "decompress_region", level)
+    return _decode_window(model, src, (y0, x0, h, w), out, batch, stats, "decompress_region", level,
+                          with_valid=with_valid)
+
+
+@torch.no_grad()
+def decompress_valid(src, y0=0, x0=0, h=None, w=None, level=0, device="cuda"):
+    """The validity of the window rows [y0, y0+h) x columns [x0, x0+w) (h, w None: to the image's end) of a stream's
+    level, torch.bool [h,w] on `device`, as decompress_region(..., with_valid=True) returns it.  No model is needed and
+    nothing is decoded: only the heads and the mask payloads of the window's mixed tiles are read, and the planes are
+    unpacked and written on the device (dsic_mask_unpack, dsic_mask_window_u8).  All True for a stream without a mask."""
+    source, ix = _open_level(src, level)[:2]
+    y0, x0 = int(y0), int(x0)
+    h, w = ix["H"] - y0 if h is None else int(h), ix["W"] - x0 if w is None else int(w)
+    tiles = window_tiles(ix, y0, x0, h, w)
+    valid = torch.ones((h, w), dtype=torch.uint8, device=device)
+    if "coded" in ix:
+        _apply_mask(source, ix, tiles, None, None, (y0, x0, h, w), valid)
+    return valid.bool()
 
 
 from .view import ImageReader, view_level  # noqa: E402  (view.py builds on the functions above)

@@ -33,7 +33,13 @@ constexpr int kMaskRows = 16;  // rows of one tile per workgroup of classify and
 template <int C>
 __device__ __forceinline__ uint32_t nodata16_full(const uint8_t* __restrict__ p, uint32_t v) {
   uint32_t m = 0;
-  if (C == 4) {
+  if (C == 1) {  // a validity image (csrc/mask.hip, the valid exports): one load gives the 16 plane bits
+    const uint4 q = load16_any(p);
+    uint8_t b[16];
+    __builtin_memcpy(b, &q, 16);
+#pragma unroll
+    for (int e = 0; e < 16; ++e) m |= (uint32_t)(b[e] == v) << e;
+  } else if (C == 4) {
     const uint32_t vv = v * 0x01010101u;
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
@@ -349,6 +355,88 @@ __global__ __launch_bounds__(256) void mask_apply_f32_kernel(const uint32_t* __r
   }
 }
 
+// uint16 HWC window at any 2-byte alignment, C 1 .. 4.  Positions count uint16 elements; `mis` is the window
+// image's offset behind a 16-byte boundary in elements (stitch_u16_kernel of image_u16.hip), so that chunk q0 is an
+// aligned 16 bytes of memory.
+__global__ __launch_bounds__(256) void mask_apply_u16_kernel(const uint32_t* __restrict__ planes,
+                                                             const int* __restrict__ desc, int n_planes, Grid g, int C,
+                                                             Clip w, uint16_t* __restrict__ img, uint32_t v, int mis) {
+  Owned o;
+  int pi;
+  if (!apply_rect(g, desc, n_planes, w, &o, &pi)) return;
+  const int ya = o.y0 + blockIdx.x * kMaskRows;
+  const int rows = min(kMaskRows, o.y1 - ya);
+  if (rows <= 0) return;
+  const uint32_t* plane = pi < 0 ? nullptr : planes + (size_t)pi * ((g.th * g.tw) >> 5);
+  const int wW = w.x1 - w.x0;
+  const int seg = (o.x1 - o.x0) * C;
+  const int cpr = seg / 8 + 2;  // 16-byte chunks a row segment can touch
+  const uint32_t vv = v * 0x00010001u;
+  for (int i = threadIdx.x; i < rows * cpr; i += blockDim.x) {
+    const int r = i / cpr, k = i - r * cpr;
+    const int y = ya + r;
+    const int64_t b0 = ((int64_t)(y - w.y0) * wW + (o.x0 - w.x0)) * C + mis, b1 = b0 + seg;
+    const int64_t q0 = ((b0 >> 3) + k) << 3;
+    if (q0 >= b1) continue;
+    const int64_t lo = max(q0, b0), hi = min(q0 + 8, b1);
+    int px = (int)((lo - b0) / C), c = (int)((lo - b0) - (int64_t)px * C);
+    px += o.x0 - o.ox;  // column within the tile
+    const int row_bit = (y - o.oy) * g.tw;
+    uint32_t sel = 0;
+#pragma unroll
+    for (int e = 0; e < 8; ++e) {
+      if (q0 + e >= lo && q0 + e < hi) {
+        sel |= (uint32_t)mask_bit(plane, row_bit + px) << e;
+        if (++c == C) c = 0, ++px;
+      }
+    }
+    if (sel == 0xFFu) {
+      *(uint4*)(img + (q0 - mis)) = make_uint4(vv, vv, vv, vv);
+    } else {
+#pragma unroll
+      for (int e = 0; e < 8; ++e)
+        if ((sel >> e) & 1u) img[q0 + e - mis] = (uint16_t)v;
+    }
+  }
+}
+
+// The validity window, uint8 [h][w] at any alignment (`mis` in bytes): every owned pixel of the listed tiles inside
+// the window gets 0 where its bit is set (or the plane is -1, all set) and 1 elsewhere; no other byte is written.
+__global__ __launch_bounds__(256) void mask_window_u8_kernel(const uint32_t* __restrict__ planes,
+                                                             const int* __restrict__ desc, int n_planes, Grid g, Clip w,
+                                                             uint8_t* __restrict__ out, int mis) {
+  Owned o;
+  int pi;
+  if (!apply_rect(g, desc, n_planes, w, &o, &pi)) return;
+  const int ya = o.y0 + blockIdx.x * kMaskRows;
+  const int rows = min(kMaskRows, o.y1 - ya);
+  if (rows <= 0) return;
+  const uint32_t* plane = pi < 0 ? nullptr : planes + (size_t)pi * ((g.th * g.tw) >> 5);
+  const int wW = w.x1 - w.x0;
+  const int seg = o.x1 - o.x0;
+  const int cpr = seg / 16 + 2;  // 16-byte chunks a row segment can touch
+  for (int i = threadIdx.x; i < rows * cpr; i += blockDim.x) {
+    const int r = i / cpr, k = i - r * cpr;
+    const int y = ya + r;
+    const int64_t b0 = (int64_t)(y - w.y0) * wW + (o.x0 - w.x0) + mis, b1 = b0 + seg;
+    const int64_t q0 = ((b0 >> 4) + k) << 4;
+    if (q0 >= b1) continue;
+    const int64_t lo = max(q0, b0), hi = min(q0 + 16, b1);
+    const int bit0 = (y - o.oy) * g.tw + (o.x0 - o.ox) + (int)(lo - b0);
+    uint8_t b[16];
+#pragma unroll
+    for (int e = 0; e < 16; ++e)
+      b[e] = q0 + e >= lo && q0 + e < hi ? (uint8_t)!mask_bit(plane, bit0 + (int)(q0 + e - lo)) : (uint8_t)0;
+    if (lo == q0 && hi == q0 + 16) {
+      uint4 v;
+      __builtin_memcpy(&v, b, 16);
+      *(uint4*)(out + (q0 - mis)) = v;
+    } else {
+      for (int64_t e = lo; e < hi; ++e) out[e - mis] = b[e - q0];
+    }
+  }
+}
+
 }  // namespace dsic
 
 using namespace dsic;
@@ -465,4 +553,75 @@ extern "C" int dsic_mask_apply_f32(const uint32_t* planes, int n_planes, const i
   hipLaunchKernelGGL(mask_apply_f32_kernel, dim3(grid.x, grid.y, C), dim3(256), 0, (hipStream_t)stream, planes, desc,
                      n_planes, g, clip, out, fv);
   return check_launch("mask_apply_f32");
+}
+
+// ---- validity masks (codec.compress_image with valid = mask, stream version 8) --------------------------------------
+// The mask travels as a uint8 [H][W] image, 0 = invalid: a one-channel image whose "nodata value" is 0, so classify and
+// the d planes are the C = 1 instantiation of the kernels above, with their grid, ownership and plane layout.
+#define DSIC_VALID_IMAGE(what)                                                                          \
+  const char* ge = grid_error(H, W, th, tw);                                                           \
+  DSIC_REQUIRE(!ge, what ": %s (H=%d W=%d th=%d tw=%d)", ge ? ge : "", H, W, th, tw);                  \
+  DSIC_REQUIRE((int64_t)th * tw <= INT_MAX / 2, what ": a tile of %dx%d has over 2^30 pixels", th, tw); \
+  const Grid g = make_grid(H, W, th, tw)
+
+extern "C" int dsic_valid_classify(const uint8_t* valid_hw, int H, int W, int th, int tw, int first_tile, int n_tiles,
+                                   int* counts, void* stream) {
+  DSIC_REQUIRE(valid_hw && counts, "valid_classify: null pointer");
+  DSIC_VALID_IMAGE("valid_classify");
+  DSIC_REQUIRE(first_tile >= 0 && n_tiles > 0 && (int64_t)first_tile + n_tiles <= (int64_t)g.ny * g.nx,
+               "valid_classify: tiles [%d, %d) outside the grid of %d", first_tile, first_tile + n_tiles, g.ny * g.nx);
+  DSIC_REQUIRE(n_tiles <= 65535, "valid_classify: at most 65535 tiles per call");
+  DSIC_REQUIRE(((uintptr_t)counts & 3) == 0, "valid_classify: counts must be 4-byte aligned");
+  hipLaunchKernelGGL(mask_classify_kernel<1>, dim3(g.th / kMaskRows, n_tiles), dim3(256), 0, (hipStream_t)stream,
+                     valid_hw, g, 0u, first_tile, counts);
+  return check_launch("valid_classify");
+}
+
+extern "C" int dsic_valid_delta_planes(const uint8_t* valid_hw, int H, int W, int th, int tw, const int* tile_ids,
+                                       int n_tiles, uint32_t* planes, int* popcounts, void* stream) {
+  DSIC_REQUIRE(valid_hw && tile_ids && planes && popcounts, "valid_delta_planes: null pointer");
+  DSIC_VALID_IMAGE("valid_delta_planes");
+  DSIC_REQUIRE(n_tiles >= 1 && n_tiles <= 65535, "valid_delta_planes: n=%d tiles per call (1..65535)", n_tiles);
+  DSIC_REQUIRE((((uintptr_t)planes | (uintptr_t)popcounts | (uintptr_t)tile_ids) & 3) == 0,
+               "valid_delta_planes: planes, popcounts and tile ids must be 4-byte aligned");
+  hipLaunchKernelGGL(mask_delta_kernel<1>, dim3(ceil_div((g.th * g.tw) >> 5, 256), n_tiles), dim3(256), 0,
+                     (hipStream_t)stream, valid_hw, g, 0u, tile_ids, planes, popcounts);
+  return check_launch("valid_delta_planes");
+}
+
+#define DSIC_VALID_WINDOW(what)                                                                                \
+  const char* ge = grid_error(H, W, th, tw);                                                                   \
+  DSIC_REQUIRE(!ge, what ": %s (H=%d W=%d th=%d tw=%d)", ge ? ge : "", H, W, th, tw);                          \
+  DSIC_REQUIRE((int64_t)th * tw <= INT_MAX / 2, what ": a tile of %dx%d has over 2^30 pixels", th, tw);        \
+  const Grid g = make_grid(H, W, th, tw);                                                                      \
+  DSIC_REQUIRE(wy0 >= 0 && wx0 >= 0 && wh >= 1 && ww >= 1 && (int64_t)wy0 + wh <= H && (int64_t)wx0 + ww <= W, \
+               what ": window %dx%d at (%d, %d) outside the %dx%d image", wh, ww, wy0, wx0, H, W);             \
+  DSIC_REQUIRE(n_tiles >= 1 && n_tiles <= 65535, what ": n=%d tiles per call (1..65535)", n_tiles);            \
+  DSIC_REQUIRE(n_planes >= 0 && (planes || n_planes == 0), what ": %d planes at a null pointer", n_planes);    \
+  DSIC_REQUIRE((((uintptr_t)planes | (uintptr_t)desc) & 3) == 0, what ": planes and desc must be 4-byte aligned"); \
+  const Clip clip = {wy0, wy0 + wh, wx0, wx0 + ww};                                                            \
+  const dim3 grid(g.th / kMaskRows, n_tiles, 1)
+
+extern "C" int dsic_mask_apply_u16(const uint32_t* planes, int n_planes, const int* desc, int n_tiles, int fill,
+                                   uint16_t* out, int H, int W, int C, int th, int tw, int wy0, int wx0, int wh, int ww,
+                                   void* stream) {
+  DSIC_REQUIRE(desc && out, "mask_apply_u16: null pointer");
+  DSIC_REQUIRE(C >= 1 && C <= 4, "mask_apply_u16: C=%d must be in 1..4", C);
+  DSIC_REQUIRE(fill >= 0 && fill <= 65535, "mask_apply_u16: fill=%d must be in 0..65535", fill);
+  DSIC_REQUIRE(((uintptr_t)out & 1) == 0, "mask_apply_u16: the uint16 window must be 2-byte aligned");
+  DSIC_VALID_WINDOW("mask_apply_u16");
+  DSIC_REQUIRE((int64_t)ww * C * 2 <= INT_MAX, "mask_apply_u16: a row of ww=%d pixels of C=%d uint16 is over 2^31 - 1 bytes",
+               ww, C);
+  hipLaunchKernelGGL(mask_apply_u16_kernel, grid, dim3(256), 0, (hipStream_t)stream, planes, desc, n_planes, g, C, clip,
+                     out, (uint32_t)fill, (int)(((uintptr_t)out & 15) >> 1));
+  return check_launch("mask_apply_u16");
+}
+
+extern "C" int dsic_mask_window_u8(const uint32_t* planes, int n_planes, const int* desc, int n_tiles, uint8_t* out_hw,
+                                   int H, int W, int th, int tw, int wy0, int wx0, int wh, int ww, void* stream) {
+  DSIC_REQUIRE(desc && out_hw, "mask_window_u8: null pointer");
+  DSIC_VALID_WINDOW("mask_window_u8");
+  hipLaunchKernelGGL(mask_window_u8_kernel, grid, dim3(256), 0, (hipStream_t)stream, planes, desc, n_planes, g, clip,
+                     out_hw, (int)((uintptr_t)out_hw & 15));
+  return check_launch("mask_window_u8");
 }

@@ -12,6 +12,9 @@
 // average, float32 [C][sh][sw]: acc = the float32 left fold over Y ascending, then X ascending, of
 // float32(wy wx) * v (built with -ffp-contract=off: NumPy folds to the same bits), output acc / float32(T).
 // nodata: a source pixel whose C channels all equal the value stays out of S (acc) and T; T = 0 gives the value.
+// validity (the _valid exports, a stream with a validity mask): a byte window [sh][sw] beside the source says which
+// pixels stay out of S and T (0 = invalid; no value is compared), T = 0 gives the fill and validity 0 in the optional
+// output validity [oh][ow], and nearest copies pixel and validity.
 // nearest: source row (y0 2 oh + (2 i + 1) h) / (2 oh) >> l = (y0 + (2 i + 1) h / (2 oh)) >> l, columns likewise; a copy.
 //
 // A wave covers 64 consecutive pixels of an output row, so its loads walk the source rows in step and its stores are
@@ -53,10 +56,15 @@ constexpr int VIEW_BX = 64, VIEW_BY = 4;  // output pixels of a workgroup: 4 row
 // T = uint8_t or uint16_t, [.][.][C] with C <= 4; nodata < 0 = none.  The weights are taken with h / oh and w / ow in
 // lowest terms: every interval end is a multiple of gcd(h, oh), so this divides all wy by it, S and T alike, and
 // (2 S + T) / (2 T) is the same integer while S and T stay small (halving: T = 4).
-template <typename T>
+// V: the validity window sval [sh][sw] (0 = invalid) decides what stays out of S and T instead of a comparison with
+// nodata, T = 0 writes nodata (the fill) and, where oval is not null, oval [oh][ow] receives 1 or 0; nearest copies
+// the pixel and its validity.
+template <typename T, bool V>
 __global__ __launch_bounds__(VIEW_BX * VIEW_BY) void resample_int_kernel(const T* __restrict__ src,
                                                                          T* __restrict__ dst, View v, int C, int mode,
-                                                                         int nodata, int bx, int64_t nblocks) {
+                                                                         int nodata, int bx, int64_t nblocks,
+                                                                         const uint8_t* __restrict__ sval,
+                                                                         uint8_t* __restrict__ oval) {
   for (int64_t blk = blockIdx.x; blk < nblocks; blk += gridDim.x) {
     const int64_t by = blk / bx;
     const int j = (int)(blk - by * bx) * VIEW_BX + threadIdx.x;
@@ -68,6 +76,7 @@ __global__ __launch_bounds__(VIEW_BX * VIEW_BY) void resample_int_kernel(const T
       const int Y = axis_nearest(i, v.hn, v.hd, v.y0, v.shift), X = axis_nearest(j, v.wn, v.wd, v.x0, v.shift);
       const T* p = src + ((int64_t)(Y - v.sy0) * v.sw + (X - v.sx0)) * C;
       for (int c = 0; c < C; ++c) o[c] = p[c];
+      if (V && oval) oval[(int64_t)i * v.ow + j] = (uint8_t)(sval[(int64_t)(Y - v.sy0) * v.sw + (X - v.sx0)] != 0);
       continue;
     }
     const Span ry = axis_span(i, v.hn, v.hd, v.y0, v.shift), rx = axis_span(j, v.wn, v.wd, v.x0, v.shift);
@@ -79,11 +88,11 @@ __global__ __launch_bounds__(VIEW_BX * VIEW_BY) void resample_int_kernel(const T
         const uint64_t wgt = wy * (uint64_t)axis_weight(j, v.wn, v.wd, v.x0, v.shift, X);
         const T* p = row + (int64_t)(X - v.sx0) * C;
         uint32_t val[4];
-        bool nd = nodata >= 0;
+        bool nd = V ? sval[(int64_t)(Y - v.sy0) * v.sw + (X - v.sx0)] == 0 : nodata >= 0;
 #pragma unroll
         for (int c = 0; c < 4; ++c) {
           val[c] = c < C ? (uint32_t)p[c] : 0u;
-          if (c < C) nd = nd && val[c] == (uint32_t)nodata;
+          if (!V && c < C) nd = nd && val[c] == (uint32_t)nodata;
         }
         if (nd) continue;
         Tw += wgt;
@@ -99,6 +108,7 @@ __global__ __launch_bounds__(VIEW_BX * VIEW_BY) void resample_int_kernel(const T
       const uint64_t num = 2 * S[c] + Tw, den = 2 * Tw;
       o[c] = !Tw ? (T)nodata : narrow ? (T)((uint32_t)num / (uint32_t)den) : (T)(num / den);
     }
+    if (V && oval) oval[(int64_t)i * v.ow + j] = (uint8_t)(Tw != 0);
   }
 }
 
@@ -216,8 +226,28 @@ static int resample_int(const char* what, const T* src, const View& v, int C, in
   const int status = view_check(what, src, dst, v, C, cmin, 4, (int)sizeof(T), mode, &bx, &nblocks);
   if (status != DSIC_OK) return status;
   DSIC_REQUIRE(nodata >= -1 && nodata <= (int)(T)~(T)0, "%s: nodata=%d (-1 for none, or a pixel value)", what, nodata);
-  hipLaunchKernelGGL(resample_int_kernel<T>, view_grid(nblocks), dim3(VIEW_BX, VIEW_BY), 0, (hipStream_t)stream, src, dst,
-                     v, C, mode, nodata, bx, nblocks);
+  hipLaunchKernelGGL((resample_int_kernel<T, false>), view_grid(nblocks), dim3(VIEW_BX, VIEW_BY), 0, (hipStream_t)stream,
+                     src, dst, v, C, mode, nodata, bx, nblocks, (const uint8_t*)nullptr, (uint8_t*)nullptr);
+  return check_launch(what);
+}
+
+template <typename T>
+static int resample_valid(const char* what, const T* src, const uint8_t* sval, const View& v, int C, int cmin, T* dst,
+                          uint8_t* oval, int mode, int fill, void* stream) {
+  int bx;
+  int64_t nblocks;
+  const int status = view_check(what, src, dst, v, C, cmin, 4, (int)sizeof(T), mode, &bx, &nblocks);
+  if (status != DSIC_OK) return status;
+  DSIC_REQUIRE(sval, "%s: null pointer", what);
+  DSIC_REQUIRE(fill >= 0 && fill <= (int)(T)~(T)0, "%s: fill=%d must be a pixel value", what, fill);
+  const int64_t sb = (int64_t)sizeof(T) * C * v.sh * v.sw, db = (int64_t)sizeof(T) * C * v.oh * v.ow;
+  const int64_t svb = (int64_t)v.sh * v.sw, ovb = (int64_t)v.oh * v.ow;
+  DSIC_REQUIRE(view_apart(sval, svb, dst, db) &&
+                   (!oval || (view_apart(oval, ovb, src, sb) && view_apart(oval, ovb, sval, svb) &&
+                              view_apart(oval, ovb, dst, db))),
+               "%s: src and dst overlap", what);
+  hipLaunchKernelGGL((resample_int_kernel<T, true>), view_grid(nblocks), dim3(VIEW_BX, VIEW_BY), 0, (hipStream_t)stream,
+                     src, dst, v, C, mode, fill, bx, nblocks, sval, oval);
   return check_launch(what);
 }
 
@@ -250,4 +280,20 @@ extern "C" int dsic_window_resample_f32(const float* src_chw, int sh, int sw, in
   hipLaunchKernelGGL(resample_f32_kernel, view_grid(nblocks), dim3(VIEW_BX, VIEW_BY), 0, (hipStream_t)stream, src_chw,
                      dst_chw, v, C, mode, nodata, has_nodata, bx, nblocks);
   return check_launch("window_resample_f32");
+}
+
+extern "C" int dsic_window_resample_valid_u8(const uint8_t* src_hwc, const uint8_t* src_valid, int sh, int sw, int sy0,
+                                             int sx0, int C, int shift, int y0, int x0, int h, int w, uint8_t* dst_hwc,
+                                             uint8_t* dst_valid, int oh, int ow, int mode, int fill, void* stream) {
+  const View v = view_of(sh, sw, sy0, sx0, shift, y0, x0, h, w, oh, ow);
+  return resample_valid<uint8_t>("window_resample_valid_u8", src_hwc, src_valid, v, C, 3, dst_hwc, dst_valid, mode, fill,
+                                 stream);
+}
+
+extern "C" int dsic_window_resample_valid_u16(const uint16_t* src_hwc, const uint8_t* src_valid, int sh, int sw, int sy0,
+                                              int sx0, int C, int shift, int y0, int x0, int h, int w, uint16_t* dst_hwc,
+                                              uint8_t* dst_valid, int oh, int ow, int mode, int fill, void* stream) {
+  const View v = view_of(sh, sw, sy0, sx0, shift, y0, x0, h, w, oh, ow);
+  return resample_valid<uint16_t>("window_resample_valid_u16", src_hwc, src_valid, v, C, 1, dst_hwc, dst_valid, mode, fill,
+                                  stream);
 }

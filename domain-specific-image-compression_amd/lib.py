@@ -135,6 +135,15 @@ SIGNATURES = {
     "dsic_window_resample_u8": (c_int, [_P] + [c_int] * 10 + [_P] + [c_int] * 4 + [_P]),
     "dsic_window_resample_u16": (c_int, [_P] + [c_int] * 10 + [_P] + [c_int] * 4 + [_P]),
     "dsic_window_resample_f32": (c_int, [_P] + [c_int] * 10 + [_P] + [c_int] * 3 + [ctypes.c_float, c_int, _P]),
+    "dsic_valid_classify": (c_int, [_P] + [c_int] * 6 + [_P, _P]),
+    "dsic_valid_delta_planes": (c_int, [_P] + [c_int] * 4 + [_P, c_int, _P, _P, _P]),
+    "dsic_mask_apply_u16": (c_int, [_P, c_int, _P, c_int, c_int, _P] + [c_int] * 9 + [_P]),
+    "dsic_mask_window_u8": (c_int, [_P, c_int, _P, c_int, _P] + [c_int] * 8 + [_P]),
+    "dsic_image_halve_valid_u8": (c_int, [_P, _P, _P, _P, c_int, c_int, c_int, _P]),
+    "dsic_image_halve_valid_u16": (c_int, [_P, _P, _P, _P, c_int, c_int, c_int, _P]),
+    "dsic_band_range_valid_u16": (c_int, [_P, _P, c_int, c_int, c_int, _P, _P]),
+    "dsic_window_resample_valid_u8": (c_int, [_P, _P] + [c_int] * 10 + [_P, _P] + [c_int] * 4 + [_P]),
+    "dsic_window_resample_valid_u16": (c_int, [_P, _P] + [c_int] * 10 + [_P, _P] + [c_int] * 4 + [_P]),
     "dsic_stream_create_masked":(c_int, [_P, c_int, _P]),
     "dsic_stream_destroy": (c_int, [_P]),
     "dsic_range_decode": (c_int, [_P, c_int64, _P, c_int, c_int, _P, c_int, _P, c_int, c_int, c_int,

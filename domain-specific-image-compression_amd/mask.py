@@ -18,6 +18,11 @@ The mask block of a stream (little endian):
     nm x (tile u32, mode u32, bytes u32), ascending tile | the nm payloads back to back
 
 Set bits outside a tile's owned rectangle are harmless: the apply kernel writes only pixels the tile owns.
+
+A validity mask (codec.compress_image with valid = mask, stream version 8) uses the same states, planes, payloads and
+block with "invalid" in the place of "nodata": the mask arrives as a uint8 [H,W] image, 0 = invalid (classify_valid,
+delta_planes_valid: the kernels above on a one-channel image whose nodata value is 0), the block's nodata field
+carries the fill, apply_window also fills uint16 windows, and window_valid writes a window's validity.
 """
 from __future__ import annotations
 
@@ -165,16 +170,50 @@ def pack_on_device(planes, pop, ids, th, tw):
     return out, int(ws[0].cpu())
 
 
+def check_fill(fill, top, what) -> int:
+    """fill as an int in 0 .. top (255 for uint8 images, 65535 for uint16), else ValueError."""
+    try:
+        v = -1 if isinstance(fill, (bool, np.bool_)) else operator.index(fill)
+    except TypeError:
+        v = -1
+    if not 0 <= v <= top:
+        raise ValueError(f"{what}: fill={fill!r} must be an integer from 0 to {top}")
+    return v
+
+
+def classify_valid(valid, g) -> np.ndarray:
+    """uint8 [H,W] on the device, 0 = invalid -> int64 [n]: per grid tile the invalid pixels among its owned pixels
+    inside H x W (dsic_valid_classify: classify of a one-channel image whose nodata value is 0)."""
+    L = _lib.load()
+    counts = torch.zeros(g["n"], dtype=torch.int32, device=valid.device)
+    for first in range(0, g["n"], 65535):
+        n = min(65535, g["n"] - first)
+        _lib.check(L.dsic_valid_classify(_p(valid), g["H"], g["W"], g["th"], g["tw"], first, n, _p(counts[first:]),
+                                         _stream()), "valid_classify")
+    return counts.cpu().numpy().astype(np.int64)
+
+
+def delta_planes_valid(valid, g, ids):
+    """delta_planes of a validity image (dsic_valid_delta_planes)."""
+    n = ids.numel()
+    planes = torch.empty((n, g["th"] * g["tw"] // 32), dtype=torch.int32, device=valid.device)
+    pop = torch.zeros(n, dtype=torch.int32, device=valid.device)
+    _lib.check(_lib.load().dsic_valid_delta_planes(_p(valid), g["H"], g["W"], g["th"], g["tw"], _p(ids), n, _p(planes),
+                                                   _p(pop), _stream()), "valid_delta_planes")
+    return planes, pop
+
+
 @torch.no_grad()
 def encode_block(img, g, C, nodata, states) -> bytes:
-    """The mask block of an image on the device from its tile states; only the block's bytes leave the device."""
+    """The mask block of an image on the device from its tile states; only the block's bytes leave the device.
+    C = None: img is a validity image (uint8 [H,W], 0 = invalid) and nodata the fill the block's field carries."""
     th, tw = g["th"], g["tw"]
     mixed = [t for t, s in enumerate(states) if s == MIXED]
     records, payloads = [], []
     for c0 in range(0, len(mixed), MAX_TILES):
         sel = mixed[c0:c0 + MAX_TILES]
         ids = torch.tensor(sel, dtype=torch.int32).to(img.device)
-        planes, pop = delta_planes(img, g, C, nodata, ids)
+        planes, pop = delta_planes_valid(img, g, ids) if C is None else delta_planes(img, g, C, nodata, ids)
         out, nbytes = pack_on_device(planes, pop, ids, th, tw)
         host = out[:nbytes].cpu().numpy().tobytes()
         records += list(_REC.iter_unpack(host[:_REC.size * len(sel)]))
@@ -196,5 +235,14 @@ def apply_window(planes, n_planes, desc, n, nodata, img, kind_u8, H, W, C, th, t
     nodata / 255.0f (float32 [C,h,w]) at the tiles' owned pixels inside the window whose bit is set."""
     L = _lib.load()
     fn, what = (L.dsic_mask_apply_u8, "mask_apply_u8") if kind_u8 else (L.dsic_mask_apply_f32, "mask_apply_f32")
+    if img.dtype == torch.uint16:                                  # a version-8 stream of a uint16 image: the fill
+        fn, what = L.dsic_mask_apply_u16, "mask_apply_u16"
     _lib.check(fn(_p(planes) if planes is not None else None, n_planes, _p(desc), n, nodata, _p(img), H, W, C, th, tw,
                   y0, x0, h, w, _stream()), what)
+
+
+def window_valid(planes, n_planes, desc, n, out, H, W, th, tw, y0, x0, h, w):
+    """desc as apply_window takes it: 1 or 0 into the uint8 [h,w] validity window `out` at every owned pixel of the
+    listed tiles inside the window (dsic_mask_window_u8); the pixels of other tiles keep the caller's pre-fill."""
+    _lib.check(_lib.load().dsic_mask_window_u8(_p(planes) if planes is not None else None, n_planes, _p(desc), n,
+                                               _p(out), H, W, th, tw, y0, x0, h, w, _stream()), "mask_window_u8")

@@ -236,9 +236,10 @@ class ImageReader:
             st["decode_batches"] += 1
             st["bytes_uploaded"] += nbytes
 
-    def _window(self, level, window, out, st, ensured=False):
+    def _window(self, level, window, out, st, ensured=False, valid_out=None):
         """decompress_region(model, src, *window, out=out, level=level), through the cache.  ensured: read_many has
-        brought the window's tiles into the cache and counted them."""
+        brought the window's tiles into the cache and counted them.  valid_out: None, or a uint8 tensor of ones of the
+        window's size that receives its validity."""
         level, view, ix = self._level(level)
         kind = _c._check_out(out, ix, "ImageReader.read")
         tiles = _c.window_tiles(ix, *window)
@@ -249,7 +250,10 @@ class ImageReader:
             if len(coded) * _tile_bytes(ix) > self.cache_bytes:
                 inner = {}
                 img = _c._decode_window(self.model, None, window, out, self.batch, inner, "ImageReader.read",
-                                        opened=(view, ix))
+                                        opened=(view, ix), with_valid=valid_out is not None)
+                if valid_out is not None:
+                    valid_out.copy_(img[1])
+                    img = img[0]
                 st["decoded"] += len(coded)
                 st["decode_batches"] += inner["decode_batches"]
                 st["bytes_uploaded"] += inner["bytes_uploaded"]
@@ -261,7 +265,8 @@ class ImageReader:
             rows = slab.rows(coded)
             batches.append((slab.x.index_select(0, rows), 0, slab.ids.index_select(0, rows),
                             slab.q.index_select(0, rows) if slab.has_q else None))
-        img, uploaded, _ = _c._assemble_window(self.model, view, ix, tiles, window, kind, batches, "ImageReader.read")
+        img, uploaded, _ = _c._assemble_window(self.model, view, ix, tiles, window, kind, batches, "ImageReader.read",
+                                               valid_out)
         st["bytes_uploaded"] += uploaded
         return img
 
@@ -290,13 +295,25 @@ class ImageReader:
             return 0, (y0, x0, h, w), None
         return level, _c.level_window(level, y0, x0, h, w), ((y0, x0, h, w), (oh, ow), RESAMPLING[resampling])
 
-    def _resample(self, img, level, lw, view):
-        """A level's window `lw`, as _window returns it, resampled to the view (csrc/view.hip)."""
+    def _masked(self, level):
+        """Whether a level carries a validity mask (stream version 8): its sized reads resample with the mask."""
+        return "fill" in self._open[level][1]
+
+    def _resample(self, img, level, lw, view, valid=None, want_valid=False):
+        """A level's window `lw`, as _window returns it, resampled to the view (csrc/view.hip).  valid: the window's
+        validity, uint8, for a level with a validity mask; then the result is (image, its validity or None)."""
         (y0, x0, h, w), (oh, ow), mode = view
         ix = self._open[level][1]
         v = ix.get("nodata") if mode == 0 else None
         L = _lib.load()
         geo = (lw[2], lw[3], lw[0], lw[1], ix["C"], level, y0, x0, h, w)
+        if valid is not None:
+            what = "window_resample_valid_u8" if img.dtype == torch.uint8 else "window_resample_valid_u16"
+            dst = torch.empty((oh, ow, ix["C"]), dtype=img.dtype, device=img.device)
+            oval = torch.empty((oh, ow), dtype=torch.uint8, device=img.device) if want_valid else None
+            _lib.check(getattr(L, "dsic_" + what)(_p(img), _p(valid), *geo, _p(dst), None if oval is None else _p(oval),
+                                                  oh, ow, mode, ix["fill"], _stream()), what)
+            return dst, oval
         if img.dtype == torch.float32:
             dst = torch.empty((ix["C"], oh, ow), dtype=torch.float32, device=img.device)
             value = 0.0 if v is None else float(np.float32(v) / np.float32(255.0))     # what _apply_mask wrote
@@ -319,7 +336,8 @@ class ImageReader:
             stats.update(st)
 
     @torch.no_grad()
-    def read(self, y0, x0, h, w, size=None, level=None, out=None, resampling="average", stats=None):
+    def read(self, y0, x0, h, w, size=None, level=None, out=None, resampling="average", stats=None,
+             with_valid=False):
         """size = None: the window rows [y0, y0+h) x columns [x0, x0+w) of level `level` (default 0), in that level's
         own pixel grid: decompress_region(model, src, y0, x0, h, w, out=out, level=level), bit for bit, whatever the
         cache held before.
@@ -330,6 +348,13 @@ class ImageReader:
         fold), "nearest" copies the pixel under the output pixel's centre.  Averaging a nodata stream (version 5)
         leaves nodata pixels out, and an output pixel with nothing else under it is nodata.  size == (h, w) at level
         0 is the plain window.  The result has the kind `out` gives the window.
+        A stream with a validity mask (version 8) is resampled with the mask itself, no value is compared
+        (dsic_window_resample_valid_u8 / _u16): averaging leaves invalid pixels out, an output pixel with nothing valid
+        under it is fill and invalid, and "nearest" copies pixel and validity; a sized, averaged read of it with
+        out="f32" is a ValueError (the float image has no mask-aware resampler).
+        with_valid = True returns (image, valid), valid a torch.bool tensor of the image's height and width: the
+        output validity, all True for a stream without a mask.  With a size it needs a version-8 mask or none at all,
+        and an integer kind.
         stats (a dict) receives tiles ((level, tile) pairs), hits, decoded, decode_batches, bytes_read and
         bytes_uploaded, and for a read with a size level and level_window.
         ValueError as decompress_region raises it, and for an unknown resampling, a size whose entries are not
@@ -337,13 +362,36 @@ class ImageReader:
         _c._check_out(out, None, "ImageReader.read")
         before, st = self._source.bytes_read, _new_stats()
         level, lw, view = self._plan((y0, x0, h, w), size, level, resampling)
-        img = self._window(level, lw, out, st)
+        masked = self._masked(level)
+        self._check_view(level, view, out, with_valid)
+        valid = None
+        if with_valid or (masked and view is not None):
+            valid = torch.ones((int(lw[2]), int(lw[3])), dtype=torch.uint8, device=self._dev)
+        img = self._window(level, lw, out, st, valid_out=valid)
         if view is not None:
-            img = self._resample(img, level, lw, view)
+            if masked and img.dtype != torch.float32:
+                img, valid = self._resample(img, level, lw, view, valid, with_valid)
+            else:
+                img = self._resample(img, level, lw, view)
+                if with_valid:                                     # no mask: every output pixel is valid
+                    valid = torch.ones(view[1], dtype=torch.uint8, device=self._dev)
         if size is not None:
             st.update(level=level, level_window=tuple(lw))
         self._finish(st, before, stats)
-        return img
+        return (img, valid.bool()) if with_valid else img
+
+    def _check_view(self, level, view, out, with_valid):
+        """The sized reads a masked level cannot serve."""
+        if view is None:
+            return
+        ix = self._open[level][1]
+        f32 = _c._check_out(out, ix, "ImageReader.read") == _c.KIND_F32_CHW
+        if "fill" in ix and f32 and (view[2] == 0 or with_valid):
+            raise ValueError("ImageReader.read: a sized read with out='f32' of a stream with a validity mask: the float "
+                             "image has no mask-aware resampler; read the native kind")
+        if with_valid and "nodata" in ix:
+            raise ValueError("ImageReader.read: with_valid together with a size needs a validity mask (stream version "
+                             f"{_c.VERSION_VALID}); a nodata stream is resampled by value")
 
     @torch.no_grad()
     def read_many(self, requests, out=None, resampling="average", stats=None):
@@ -373,7 +421,14 @@ class ImageReader:
                 self._ensure(level, view, ix, _c._coded_tiles(ix, union[level]), pinned, st)
         imgs = []
         for level, lw, view in plans:
-            img = self._window(level, lw, out, st, ensured=shared)
-            imgs.append(img if view is None else self._resample(img, level, lw, view))
+            self._check_view(level, view, out, False)
+            masked = view is not None and self._masked(level)
+            valid = torch.ones((int(lw[2]), int(lw[3])), dtype=torch.uint8, device=self._dev) if masked else None
+            img = self._window(level, lw, out, st, ensured=shared, valid_out=valid)
+            if masked and img.dtype != torch.float32:
+                img = self._resample(img, level, lw, view, valid)[0]
+            elif view is not None:
+                img = self._resample(img, level, lw, view)
+            imgs.append(img)
         self._finish(st, before, stats)
         return imgs

@@ -713,6 +713,62 @@ int dsic_window_resample_f32(const float* src_chw, int sh, int sw, int sy0, int 
                              int shift, int y0, int x0, int h, int w, float* dst_chw, int oh,
                              int ow, int mode, float nodata, int has_nodata, void* stream);
 
+/* ---- validity masks (codec.compress_image with valid = mask, stream version 8) ----
+ * A validity image is uint8 [H][W] at any address, 0 = invalid: a one-channel image whose "nodata
+ * value" is 0.  The mask block, the planes, pack and unpack are those of the nodata masks above; a
+ * set plane bit means the pixel is owned, inside the image and invalid.
+ * dsic_valid_classify / dsic_valid_delta_planes: dsic_mask_classify_u8 / dsic_mask_delta_planes_u8
+ *   on the validity image: per tile the invalid pixels among its owned pixels (counts is added
+ *   to: zero it first), and the d planes and popcounts of the listed tiles, same grid, ownership
+ *   and plane layout.
+ * dsic_mask_apply_u16: dsic_mask_apply_u8 for a uint16 [wh][ww][C] window at any 2-byte alignment,
+ *   C 1..4, fill 0..65535: fill at the set bits of the listed tiles (plane -1: over the whole
+ *   owned rectangle) inside the window, nothing else.
+ * dsic_mask_window_u8: the validity of a window, uint8 [wh][ww] at any address: every owned pixel
+ *   of the listed tiles (desc as for apply) inside the window gets 0 where its bit is set and 1
+ *   elsewhere; pixels of tiles that are not listed (full tiles) keep what the caller put there.
+ * dsic_image_halve_valid_u8 / _u16: one overview level of a masked image, C 1..4.  The four taps
+ *   of dsic_image_halve_u8 (a repeated tap counts twice); k = the valid taps, S = their sum per
+ *   channel: the output is (2 S + k) / (2 k) (k = 4: (a + b + c + d + 2) >> 2) and is valid iff
+ *   k > 0; for k = 0 it is the unmasked mean of the four taps.  dst_valid is uint8 [H2][W2] of 0
+ *   and 1.  Outputs at any element alignment; src, src_valid, dst and dst_valid must not overlap.
+ * dsic_band_range_valid_u16: dsic_band_range_u16 over the pixels whose validity byte is not 0; a
+ *   band without a valid pixel gives (0, 0).  Atomic min and max: no dependence on any order.
+ * dsic_window_resample_valid_u8 / _u16: dsic_window_resample_u8 / _u16 with a validity window
+ *   src_valid [sh][sw] beside the source and an optional output validity dst_valid [oh][ow] (NULL:
+ *   none).  A source pixel stays out of S and T iff its validity byte is 0 (no value is compared);
+ *   T = 0 writes fill in every channel and validity 0, else validity 1.  Nearest copies the pixel
+ *   and its validity (as 0 or 1).  Geometry, reduced weights and (2 S + T) / (2 T) are unchanged.
+ * DSIC_EINVAL: as their siblings' (null pointers, C, the grid, more than 65535 tiles per call, a
+ *   window outside the image, misaligned pointers, overlapping buffers) and a fill beyond the
+ *   element type. */
+int dsic_valid_classify(const uint8_t* valid_hw, int H, int W, int th, int tw, int first_tile,
+                        int n_tiles, int* counts, void* stream);
+int dsic_valid_delta_planes(const uint8_t* valid_hw, int H, int W, int th, int tw,
+                            const int* tile_ids, int n_tiles, uint32_t* planes, int* popcounts,
+                            void* stream);
+int dsic_mask_apply_u16(const uint32_t* planes, int n_planes, const int* desc, int n, int fill,
+                        uint16_t* out, int H, int W, int C, int th, int tw, int wy0, int wx0,
+                        int wh, int ww, void* stream);
+int dsic_mask_window_u8(const uint32_t* planes, int n_planes, const int* desc, int n,
+                        uint8_t* out_hw, int H, int W, int th, int tw, int wy0, int wx0, int wh,
+                        int ww, void* stream);
+int dsic_image_halve_valid_u8(const uint8_t* src_hwc, const uint8_t* src_valid, uint8_t* dst_hwc,
+                              uint8_t* dst_valid, int H, int W, int C, void* stream);
+int dsic_image_halve_valid_u16(const uint16_t* src_hwc, const uint8_t* src_valid,
+                               uint16_t* dst_hwc, uint8_t* dst_valid, int H, int W, int C,
+                               void* stream);
+int dsic_band_range_valid_u16(const uint16_t* img_hwc, const uint8_t* valid_hw, int H, int W,
+                              int C, uint32_t* out_lohi_dev, void* stream);
+int dsic_window_resample_valid_u8(const uint8_t* src_hwc, const uint8_t* src_valid, int sh, int sw,
+                                  int sy0, int sx0, int C, int shift, int y0, int x0, int h,
+                                  int w, uint8_t* dst_hwc, uint8_t* dst_valid, int oh, int ow,
+                                  int mode, int fill, void* stream);
+int dsic_window_resample_valid_u16(const uint16_t* src_hwc, const uint8_t* src_valid, int sh,
+                                   int sw, int sy0, int sx0, int C, int shift, int y0, int x0,
+                                   int h, int w, uint16_t* dst_hwc, uint8_t* dst_valid, int oh,
+                                   int ow, int mode, int fill, void* stream);
+
 /* HIP stream limited to the CUs whose bit is set in mask_host[words] (bit i of
  * word i/32 = CU i).  Used to give the range coder its own few CUs beside the
  * conv kernels; there is no reference counterpart (the reference is

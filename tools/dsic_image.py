@@ -3,8 +3,10 @@ an image.
 
     python tools/dsic_image.py compress   --weights CKPT.pt IN.png  OUT.dsic [--tile 256] [--batch 64] [--segments K] [--overlap O]
                                           [--max-error T] [--overviews N] [--nodata V] [--scale LO,HI[,LO,HI...]]
+                                          [--valid MASK [--fill V]]
     python tools/dsic_image.py decompress --weights CKPT.pt IN.dsic OUT.png [--out u8|f32|u16] [--region Y0,X0,H,W]
                                           [--level L] [--size OH,OW] [--resampling average|nearest]
+                                          [--valid-out FILE.npy]
     python tools/dsic_image.py info       IN.dsic
 
 --segments K (2, 4, 8 or 16) codes every tile's y string as K independent strings, which a decoder reads on K waves per
@@ -33,6 +35,10 @@ The state dict is loaded plain or from under "model" (code/modelv2/eval_selfcont
 N, M, input channels and spatial_params are read from its shapes.  Images are PNG through PIL when PIL is importable
 (RGB, or RGBA for 4-channel models), .npy otherwise: uint8 or uint16 [H,W,C], or float32 [C,H,W] in [0,1].  A decoded uint8
 image is (uint8)(clamp(x,0,1)*255), as torchvision's to_pil_image writes the reference's reconstruction (:157).
+--valid MASK (a .npy of bool or uint8 [H,W], or an image file; non-zero = the pixel holds data) with --fill V keeps that
+mask exactly beside a uint8 or uint16 image (a version-8 stream; works with --segments and --overviews): tiles without
+a valid pixel are not coded, the decoder writes V at invalid pixels, decompress --valid-out FILE.npy writes the decoded
+window's mask, and info prints fill and the coded, empty and mixed tile counts, per level.
 """
 from __future__ import annotations
 
@@ -82,6 +88,24 @@ def read_image(path, channels):
     return torch.from_numpy(np.array(Image.open(path).convert(mode), dtype=np.uint8))
 
 
+def read_valid(path):
+    """--valid's file -> torch.bool [H,W]: a .npy of bool or uint8, or an image file; non-zero means valid."""
+    import numpy as np
+    import torch
+    if path.endswith(".npy"):
+        m = np.load(path)
+    else:
+        if not _has_pil():
+            raise SystemExit(f"{path}: PIL is not importable here; give the mask as .npy")
+        from PIL import Image
+        m = np.array(Image.open(path))
+    if m.ndim == 3:
+        m = m.any(axis=2)
+    if m.ndim != 2 or m.dtype not in (np.bool_, np.uint8):
+        raise SystemExit(f"{path}: the mask must be a bool or uint8 [H,W] array, got {m.dtype} {m.shape}")
+    return torch.from_numpy(np.ascontiguousarray(m != 0))
+
+
 def write_image(path, img):
     import numpy as np
     a = img.cpu().numpy()
@@ -129,6 +153,10 @@ def print_info(ix):
         states = [t["state"] for t in ix["tiles"]]
         print(f"[dsic_image] nodata {ix['nodata']}: {states.count(0)} empty, {states.count(1)} full, "
               f"{states.count(2)} mixed tile(s), {ix['coded']} coded; mask block {ix['mask_bytes']} bytes")
+    if ix.get("fill") is not None:
+        states = [t["state"] for t in ix["tiles"]]
+        print(f"[dsic_image] valid mask, fill {ix['fill']}: {ix['coded']} coded, {states.count(0)} empty, "
+              f"{states.count(2)} mixed tile(s); mask block {ix['mask_bytes']} bytes")
     if ix.get("scale") is not None:
         print("[dsic_image] scale (lo, hi) per band: " + ", ".join(f"({lo}, {hi})" for lo, hi in ix["scale"]))
     for k, c in enumerate(ix["containers"]):
@@ -164,6 +192,13 @@ def main(argv=None):
                     help="compress: store N halved levels beside the image (a DSICP stream)")
     ap.add_argument("--nodata", type=int, default=None, metavar="V",
                     help="compress: keep the mask of the pixels whose channels all equal V (0 .. 255) exactly")
+    ap.add_argument("--valid", default=None, metavar="MASK",
+                    help="compress: a validity mask beside the image, a .npy of bool or uint8 [H,W] or an image file; "
+                         "non-zero means the pixel holds data")
+    ap.add_argument("--fill", type=int, default=None, metavar="V",
+                    help="compress --valid: the value the decoders write at invalid pixels (default 0)")
+    ap.add_argument("--valid-out", default=None, metavar="FILE.npy",
+                    help="decompress: also write the decoded window's validity mask, bool [h,w]")
     ap.add_argument("--level", type=int, default=0, metavar="L",
                     help="decompress: the overview level of a DSICP stream (0 = the full image); --region counts in it")
     ap.add_argument("--size", default=None, metavar="OH,OW",
@@ -179,8 +214,14 @@ def main(argv=None):
             ix = codec.stream_index(f)
             for l, lv in enumerate(ix.get("levels", ())):
                 tiles = ix["grid"]["n"] if l == 0 else codec.stream_index(f, level=l)["grid"]["n"]
+                lx = ix if l == 0 else codec.stream_index(f, level=l)
+                masked = ""
+                if lx.get("fill") is not None:
+                    states = [t["state"] for t in lx["tiles"]]
+                    masked = (f"; fill {lx['fill']}: {lx['coded']} coded, {states.count(0)} empty, {states.count(2)} "
+                              "mixed")
                 print(f"[dsic_image] level {l}: {lv['H']}x{lv['W']}, {lv['length']} bytes at {lv['offset']}, "
-                      f"{tiles} tile(s)")
+                      f"{tiles} tile(s)" + masked)
             print_info(ix)
         return
     if a.dst is None or a.weights is None:
@@ -203,6 +244,12 @@ def main(argv=None):
             ap.error("--size OH,OW (two integers) goes with decompress --region")
     if a.scale is not None and a.mode != "compress":
         ap.error("--scale goes with compress")
+    if (a.valid is not None or a.fill is not None) and a.mode != "compress":
+        ap.error("--valid and --fill go with compress")
+    if a.fill is not None and a.valid is None:
+        ap.error("--fill goes with --valid")
+    if a.valid_out is not None and (a.mode != "decompress" or not a.valid_out.endswith(".npy")):
+        ap.error("--valid-out FILE.npy goes with decompress")
     if a.mode == "decompress" and not a.dst.endswith(".npy"):
         with open(a.src, "rb") as f:                                       # the heads only: no model, no GPU
             if a.out == "u16" or (a.out is None and codec.stream_index(f, level=a.level)["kind"] == codec.KIND_U16_HWC):
@@ -217,7 +264,8 @@ def main(argv=None):
             ap.error(str(e) if "--scale" in str(e) else f"--scale {a.scale}: integers LO,HI[,LO,HI...]")
         stream = codec.compress_image(model, img, tile=a.tile, batch=a.batch, tail=a.tail, segments=a.segments,
                                       overlap=a.overlap, max_error=a.max_error, overviews=a.overviews, nodata=a.nodata,
-                                      scale=scale)
+                                      scale=scale, **({} if a.valid is None else
+                                                      {"valid": read_valid(a.valid), "fill": a.fill or 0}))
         with open(a.dst, "wb") as f:
             f.write(stream)
         if a.overviews:
@@ -231,13 +279,16 @@ def main(argv=None):
               f"{h['batches']} batch(es) of {h['th']}x{h['tw']} tiles, {h['segments']} segment(s) per y string, "
               f"overlap {h['overlap']}" + (f", max_error {h['max_error']}" if "max_error" in h else "")
               + (f", nodata {h['nodata']}: {h['coded']} coded tile(s)" if "nodata" in h else "")
+              + (f", fill {h['fill']}: {h['coded']} coded tile(s)" if "fill" in h else "")
               + (f", scale {h['scale']}" if "scale" in h else ""))
     elif size is not None:
         given = any(s == "--level" or s.startswith("--level=") for s in (sys.argv[1:] if argv is None else argv))
         stats = {}
         with open(a.src, "rb") as f, codec.ImageReader(model, f, batch=a.batch) as reader:
             img = reader.read(*region, size=tuple(size), level=a.level if given else None, out=a.out,
-                              resampling=a.resampling, stats=stats)
+                              resampling=a.resampling, stats=stats, with_valid=a.valid_out is not None)
+            if a.valid_out is not None:
+                img, valid = img
             stats["bytes_read"] = reader.stats["bytes_read"]                  # the heads included
         path = write_image(a.dst, img)
         print(f"[dsic_image] window {region[2]}x{region[3]} at ({region[0]}, {region[1]}) as {size[0]}x{size[1]} "
@@ -246,7 +297,10 @@ def main(argv=None):
     elif region is not None:
         stats = {}
         with open(a.src, "rb") as f:
-            img = codec.decompress_region(model, f, *region, out=a.out, batch=a.batch, stats=stats, level=a.level)
+            img = codec.decompress_region(model, f, *region, out=a.out, batch=a.batch, stats=stats, level=a.level,
+                                          with_valid=a.valid_out is not None)
+        if a.valid_out is not None:
+            img, valid = img
         path = write_image(a.dst, img)
         print(f"[dsic_image] window {region[2]}x{region[3]} at ({region[0]}, {region[1]})"
               + (f" of level {a.level}" if a.level else "") + f": {len(stats['tiles'])} tile(s), "
@@ -254,8 +308,15 @@ def main(argv=None):
     else:
         with open(a.src, "rb") as f:
             stream = f.read()
-        path = write_image(a.dst, codec.decompress_image(model, stream, out=a.out, level=a.level))
+        img = codec.decompress_image(model, stream, out=a.out, level=a.level, with_valid=a.valid_out is not None)
+        if a.valid_out is not None:
+            img, valid = img
+        path = write_image(a.dst, img)
         print(f"[dsic_image] {len(stream)} bytes -> {path}")
+    if a.mode == "decompress" and a.valid_out is not None:
+        import numpy as np
+        np.save(a.valid_out, valid.cpu().numpy())
+        print(f"[dsic_image] validity {tuple(valid.shape)}, {int(valid.sum())} valid pixel(s) -> {a.valid_out}")
 
 
 if __name__ == "__main__":
