@@ -52,7 +52,17 @@ sees norm(v) = R == 0 ? 0 : float32(min(max(v, lo), hi) - lo) / float32(R), the 
 code/combinebandsall.py:7-12, computed in the tile gather (dsic_tile_gather_u16), so every container is byte for byte
 that of the float32 image norm(img); the decoders return denorm(x) = lo + uint32(clamp(x, 0, 1) * float32(R) + 0.5f),
 rounded to nearest (stitch and blend finish), and denorm(norm(v)) == v inside [lo, hi].  Version 6 and kind 2 occur only
-together.  max_error and nodata are refused with uint16 images: the residual tables and the mask classifier are 8-bit.
+together.  max_error and nodata are refused with uint16 images: the residual tables and the mask classifier are 8-bit;
+max_error stays the uint8 mode, and a uint16 image takes tolerance instead.
+
+tolerance = tau (an integer 0 .. 32767; uint16 images, overlap = 0) is stream version 9, the bounded-error mode of
+16-bit imagery: the version-3 head with overlap word 0, then C x (lo u32, hi u32), tolerance u32 and res_bands u32
+(16), and per batch, behind `u64 length, container` (the bytes of the version-6 stream of the same call without
+tolerance), `u64 length, wide residual block` (residual16.py): per tile the quantized difference between the image and
+the lossy uint16 reconstruction, split into a high part of at most 511 values, coded as the version-4 residual is,
+and k raw bit planes.  Every decoded value lies within tau of the original and tau = 0 returns it, also outside the
+scale.  Version 9 goes with kind 2 only; the decoders return uint16.  k follows each tile's largest step, so one outlier
+in a quiet tile costs k raw bits on every sample of the tile (escape coding is not done).
 
 overviews = n > 0 writes a pyramid, the image at full, 1/2, 1/4, ... 1/2^n resolution in one DSICP stream:
 
@@ -93,6 +103,7 @@ from . import entropy
 from . import lib as _lib
 from . import mask as _mask
 from . import residual as _residual
+from . import residual16 as _residual16
 from .entropy import EntropyError
 from .ops import _p, _stream
 
@@ -104,6 +115,7 @@ VERSION_RES = 4            # the version-3 head with overlap 0 + max_error u32 +
 VERSION_MASK = 5           # the version-3 head with overlap 0 + nodata u32 + coded u32; a mask block, then the coded tiles' batches
 VERSION_U16 = 6            # the version-3 head (overlap 0 allowed) + C x (lo u32, hi u32), the per-band scale; kind 2 only
 VERSION_VALID = 8          # the version-3 head with overlap 0 + fill u32 + coded u32 (+ the scale for kind 2); a mask block, then the coded tiles' batches
+VERSION_TOL = 9            # the version-3 head with overlap 0 + the scale + tolerance u32 + res_bands u32; a wide residual block per batch; kind 2 only
 BLEND_IDS = 64             # tiles per dsic_tile_blend_window_f32 call
 KIND_U8_HWC, KIND_F32_CHW, KIND_U16_HWC = 0, 1, 2
 _HEAD = struct.Struct("<6sHI6I4I2I")
@@ -226,12 +238,33 @@ def pack_image_stream(header: dict, blobs, residuals=None, mask=None) -> bytes:
     A header with "fill" = f (not None) writes version 8, the validity mask: kind 0 or 2; segments word, overlap word
     0, fill, coded (counted from the block's states; a "coded" in the header must agree), for kind 2 the scale, then
     `u64 length, mask` with `mask` the mask block whose nodata field is f, then the coded tiles' containers; no
-    overlap, max_error or nodata."""
+    overlap, max_error or nodata.
+    A header with "tolerance" = tau (not None) writes version 9, the bounded-error uint16 image: kind 2 with its
+    scale; segments word, overlap word 0, the scale, tolerance, res_bands, and behind every container its wide
+    residual block from `residuals` (residual16.pack_block); no overlap, max_error, nodata or fill."""
     h = header
     K = entropy.check_segments(h.get("segments", 1), h["M"], "pack_image_stream")
     O = _check_overlap(h.get("overlap", 0), h["th"], h["tw"], "pack_image_stream")
     if (h.get("scale") is not None) != (h["kind"] == KIND_U16_HWC):
         raise ValueError("pack_image_stream: a scale goes with kind 2 (uint16 [H,W,C]), and only with it")
+    if h.get("tolerance") is not None:
+        tau = _residual16.check_tolerance(h["tolerance"], "pack_image_stream")
+        if h["kind"] != KIND_U16_HWC:
+            raise ValueError("pack_image_stream: tolerance goes with kind 2 (uint16 [H,W,C]); max_error is the uint8 "
+                             "mode")
+        if O or h.get("max_error") is not None or h.get("nodata") is not None or h.get("fill") is not None or \
+                mask is not None:
+            raise ValueError("pack_image_stream: tolerance together with overlap > 0, max_error, nodata or a validity "
+                             "mask is not supported")
+        if residuals is None or len(residuals) != len(blobs):
+            raise ValueError("pack_image_stream: tolerance needs one wide residual block per container")
+        scale = check_scale(h["scale"], h["C"], "pack_image_stream")
+        head = _HEAD.pack(MAGIC, VERSION_TOL, h["numerics"] & 0xFFFFFFFF, h["H"], h["W"], h["C"], h["kind"], h["th"],
+                          h["tw"], h["N"], h["M"], h["in_ch"], h["spatial_params"], h["batch"], len(blobs))
+        head += _SEGS.pack(K) + _SEGS.pack(0) + b"".join(_SCALE.pack(lo, hi) for lo, hi in scale)
+        head += _RES.pack(tau, _residual16.BANDS)
+        return b"".join([head] + [_LEN.pack(len(b)) + bytes(b) + _LEN.pack(len(r)) + bytes(r)
+                                  for b, r in zip(blobs, residuals)])
     if h.get("fill") is not None:
         if h["kind"] not in (KIND_U8_HWC, KIND_U16_HWC):
             raise ValueError(f"pack_image_stream: a validity mask goes with kind {KIND_U8_HWC} or {KIND_U16_HWC}, not "
@@ -342,7 +375,7 @@ class _Source:
 
 def _read_framing(src, head=None):
     """The DSICI head and the length words of a _Source -> (header fields, (offset, bytes) of every batch's container,
-    the same of every batch's residual block: empty below version 4); what lies inside them is not read.  head: the
+    the same of every batch's residual block: empty but for versions 4 and 9); what lies inside them is not read.  head: the
     first _HEAD.size bytes, where the caller has read them already."""
     if head is None:
         head = src.read_at(0, _HEAD.size)
@@ -354,10 +387,16 @@ def _read_framing(src, head=None):
     keys = ("version", "numerics", "H", "W", "C", "kind", "th", "tw", "N", "M", "in_ch", "spatial_params", "batch",
             "batches")
     h = dict(zip(keys, f[1:]))
-    if h["version"] not in (VERSION, VERSION_SEG, VERSION_OV, VERSION_RES, VERSION_MASK, VERSION_U16, VERSION_VALID):
+    if h["version"] not in (VERSION, VERSION_SEG, VERSION_OV, VERSION_RES, VERSION_MASK, VERSION_U16, VERSION_VALID,
+                            VERSION_TOL):
         raise ValueError(f"DSICI stream version {h['version']}, this reader knows {VERSION}, {VERSION_SEG}, "
-                         f"{VERSION_OV}, {VERSION_RES}, {VERSION_MASK}, {VERSION_U16} and {VERSION_VALID}")
-    if h["version"] == VERSION_VALID:
+                         f"{VERSION_OV}, {VERSION_RES}, {VERSION_MASK}, {VERSION_U16}, {VERSION_VALID} and "
+                         f"{VERSION_TOL}")
+    if h["version"] == VERSION_TOL:
+        if h["kind"] != KIND_U16_HWC:
+            raise ValueError(f"DSICI stream: version {VERSION_TOL} with kind {h['kind']} (a tolerance goes with kind "
+                             f"{KIND_U16_HWC}, the uint16 image)")
+    elif h["version"] == VERSION_VALID:
         if h["kind"] not in (KIND_U8_HWC, KIND_U16_HWC):
             raise ValueError(f"DSICI stream: version {VERSION_VALID} with kind {h['kind']} (a validity mask goes with "
                              f"kind {KIND_U8_HWC} or {KIND_U16_HWC})")
@@ -367,9 +406,10 @@ def _read_framing(src, head=None):
     if h["kind"] == KIND_U16_HWC and not 1 <= h["C"] <= 4:
         raise ValueError(f"DSICI stream: a uint16 image of {h['C']} bands (1 .. 4)")
     off, h["segments"], h["overlap"] = _HEAD.size, 1, 0
-    if h["version"] in (VERSION_SEG, VERSION_OV, VERSION_RES, VERSION_MASK, VERSION_U16, VERSION_VALID):
+    if h["version"] in (VERSION_SEG, VERSION_OV, VERSION_RES, VERSION_MASK, VERSION_U16, VERSION_VALID, VERSION_TOL):
         words = {VERSION_SEG: 1, VERSION_OV: 2, VERSION_RES: 4, VERSION_MASK: 4, VERSION_U16: 2 + 2 * h["C"],
-                 VERSION_VALID: 4 + (2 * h["C"] if h["kind"] == KIND_U16_HWC else 0)}[h["version"]]
+                 VERSION_VALID: 4 + (2 * h["C"] if h["kind"] == KIND_U16_HWC else 0),
+                 VERSION_TOL: 4 + 2 * h["C"]}[h["version"]]
         word = src.read_at(off, words * _SEGS.size)
         if len(word) < words * _SEGS.size:
             raise ValueError("truncated DSICI stream")
@@ -391,6 +431,21 @@ def _read_framing(src, head=None):
             for lo, hi in h["scale"]:
                 if lo > hi or hi > 65535:
                     raise ValueError(f"DSICI stream: scale pair ({lo}, {hi}) must have lo <= hi <= 65535")
+        if h["version"] == VERSION_TOL:
+            (overlap,) = _SEGS.unpack_from(word, _SEGS.size)
+            if overlap != 0:
+                raise ValueError(f"DSICI stream: version {VERSION_TOL} with overlap={overlap} (a residual layer over "
+                                 "blended tiles is not supported)")
+            h["scale"] = [_SCALE.unpack_from(word, 2 * _SEGS.size + _SCALE.size * c) for c in range(h["C"])]
+            for lo, hi in h["scale"]:
+                if lo > hi or hi > 65535:
+                    raise ValueError(f"DSICI stream: scale pair ({lo}, {hi}) must have lo <= hi <= 65535")
+            h["tolerance"], bands = _RES.unpack_from(word, 2 * _SEGS.size + _SCALE.size * h["C"])
+            if bands != _residual16.BANDS:
+                raise ValueError(f"DSICI stream: version {VERSION_TOL} with res_bands={bands}, this reader knows "
+                                 f"{_residual16.BANDS}")
+            if h["tolerance"] > _residual16.MAX_TOLERANCE:
+                raise ValueError(f"DSICI stream: tolerance={h['tolerance']} (0 .. {_residual16.MAX_TOLERANCE})")
         if h["version"] == VERSION_RES:
             overlap, h["max_error"], bands = struct.unpack_from("<3I", word, _SEGS.size)
             if overlap != 0:
@@ -431,14 +486,15 @@ def _read_framing(src, head=None):
             h["mask_offset"], h["mask_bytes"] = off, size
             off += size
     frames, rframes = [], []
-    for k in range(h["batches"] * (2 if h["version"] == VERSION_RES else 1)):
+    layered = h["version"] in (VERSION_RES, VERSION_TOL)                   # a residual block behind every container
+    for k in range(h["batches"] * (2 if layered else 1)):
         if off + _LEN.size > src.size:
             raise ValueError("truncated DSICI stream")
         (size,) = _LEN.unpack(src.read_at(off, _LEN.size))
         off += _LEN.size
         if off + size > src.size:
             raise ValueError("truncated DSICI stream")
-        (rframes if h["version"] == VERSION_RES and k % 2 else frames).append((off, size))
+        (rframes if layered and k % 2 else frames).append((off, size))
         off += size
     if off != src.size:
         raise ValueError(f"DSICI stream: {src.size - off} trailing bytes")
@@ -455,11 +511,13 @@ def unpack_image_stream(stream) -> dict:
     "scale", the list of its C pairs (lo, hi); no other version has that key.  A version-8 stream (a validity mask;
     kind 0 or 2) gives "fill", "coded", "mask_offset", "mask_bytes", "mask" and, for kind 2, "scale"; it has no "nodata"
     key.  ValueError also for a version-8 head with kind 1, overlap != 0, a fill beyond the kind's range or a bad
-    scale pair."""
+    scale pair.  A version-9 stream (kind 2 with a tolerance) gives "scale", "tolerance" and "residuals", the list of
+    its wide residual blocks (residual16.py); ValueError for a version-9 head with another kind, overlap != 0, a
+    tolerance over 32767 or res_bands other than 16."""
     s = bytes(stream)
     h, frames, rframes = _read_framing(_Source(s))
     h["blobs"] = [s[off:off + size] for off, size in frames]
-    if h["version"] == VERSION_RES:
+    if h["version"] in (VERSION_RES, VERSION_TOL):
         h["residuals"] = [s[off:off + size] for off, size in rframes]
     if h["version"] in (VERSION_MASK, VERSION_VALID):
         h["mask"] = s[h["mask_offset"]:h["mask_offset"] + h["mask_bytes"]]
@@ -829,9 +887,10 @@ def _compress_masked(model, x, g, C, batch, tail, segments, nodata, header, vali
 
 
 def _compress_device_image(model, x, tile, batch, tail, segments, overlap, tau, nodata=None, scale=None, valid=None,
-                           fill=0) -> bytes:
+                           fill=0, tol=None) -> bytes:
     """compress_image's work on one image that lies contiguous on the model's device, after the argument checks that
-    do not depend on its size -> its DSICI stream.  scale: the checked pairs of a uint16 image."""
+    do not depend on its size -> its DSICI stream.  scale: the checked pairs of a uint16 image; tol: its checked
+    tolerance, or None."""
     kind, H, W, C = _image_kind(x, "compress_image")
     N, M, in_ch, spatial = _model_shape(model)
     g, overlap = _level_grid(H, W, kind, tile, overlap, tau)
@@ -841,17 +900,20 @@ def _compress_device_image(model, x, tile, batch, tail, segments, overlap, tau, 
                                  "th": g["th"], "tw": g["tw"], "N": N, "M": M, "in_ch": in_ch,
                                  "spatial_params": spatial, "batch": batch, "segments": segments, "overlap": 0},
                                 valid, fill, scale)
-    blobs, residuals = [], None if tau is None else []
+    blobs, residuals = [], None if tau is None and tol is None else []
     for first in range(0, g["n"], batch):
         n = min(batch, g["n"] - first)
         tiles = _gather(x, kind, g, C, first, n, scale)
-        if tau is None:
+        if tau is None and tol is None:
             blobs.append(entropy.compress_to_container(model, tiles, tail, segments=segments))
             continue
         # compress_to_container's work, keeping the forward x_hat: the predictor the decoder will have bit for bit
         c = entropy._coded_batch(model, tiles, tail, entropy.DEFAULT_LMAX, "compress_image", pack=True,
                                  segments=segments)
         blobs.append(c["container"][:c["container_bytes"]].cpu().numpy().tobytes())
+        if tol is not None:                    # the gathered tiles are normalised float32: the image is read in place
+            residuals.append(_residual16.encode_block(x, c["x_hat"], H, W, g["th"], g["tw"], _lohi(scale), tol, first))
+            continue
         residuals.append(_residual.encode_block(tiles, c["x_hat"], [_owned_in_tile(g, t)
                                                                    for t in range(first, first + n)], tau))
     header = {"numerics": entropy.numerics_tag(), "H": H, "W": W, "C": C, "kind": kind, "th": g["th"], "tw": g["tw"],
@@ -860,12 +922,14 @@ def _compress_device_image(model, x, tile, batch, tail, segments, overlap, tau, 
         header["max_error"] = tau
     if scale is not None:
         header["scale"] = scale
+    if tol is not None:
+        header["tolerance"] = tol
     return pack_image_stream(header, blobs, residuals)
 
 
 @torch.no_grad()
 def compress_image(model, img, tile=256, batch=64, tail=10, segments=1, overlap=0, max_error=None,
-                   overviews=0, nodata=None, scale=None, valid=None, fill=0) -> bytes:
+                   overviews=0, nodata=None, scale=None, valid=None, fill=0, tolerance=None) -> bytes:
     """img: uint8 [H,W,C], uint16 [H,W,C] or float32 [C,H,W] in [0,1], on the CPU or the GPU -> one DSICI stream.  The
     image is uploaded once; each batch of `batch` tiles is gathered on the device (reflect padding included) and becomes one
     DSIC2 container.  segments = K > 1 (1, 2, 4, 8 or 16, dividing M): every tile's y string is K independent strings
@@ -899,7 +963,17 @@ def compress_image(model, img, tile=256, batch=64, tail=10, segments=1, overlap=
     with the same arguments; segments and overlap work unchanged, and the decoders return uint16 by default.  With
     overviews the scale is decided once, at level 0, and every level is written with it (halved values stay inside
     [lo, hi]).  scale with a uint8 or float32 image is a ValueError.  max_error and nodata are refused with a uint16
-    image: the residual tables and the mask classifier are 8-bit, and 16-bit variants are separate work.
+    image: the residual tables and the mask classifier are 8-bit; max_error stays the uint8 mode, and the bounded-error
+    mode of a uint16 image is tolerance.
+    tolerance = tau (an integer 0 .. 32767; uint16 images, overlap = 0): the bounded-error mode of 16-bit imagery
+    (stream version 9).  Behind every container, byte for byte the one the version-6 stream of the same call without
+    tolerance holds, goes a wide residual block (residual16.py), and the decoders return a uint16 image within tau of
+    img on every pixel and band; 0 returns img itself, also where its values leave the scale (lo, hi), which then only
+    affects the rate.  With overviews it applies to level 0 only, as max_error does; the overview levels are the
+    version-6 streams.  The decoders take out=None or "u16" on such a stream; "u8" and "f32" are a ValueError.  A uint8
+    or float32 image (use max_error), overlap > 0, valid, nodata and max_error at the same time are each a ValueError
+    before anything touches the device.  The split of the residual follows each tile's largest step, so one outlier in
+    a quiet tile costs raw bits on every sample of that tile (residual16.py).  None writes today's streams.
     valid = mask (a torch.bool [H,W] tensor on the CPU or the GPU, True = the pixel holds data; uint8 and uint16
     images, with segments and with overviews) with fill = f (an integer 0 .. 255 for uint8, 0 .. 65535 for uint16, the
     value the decoders write at invalid pixels): the stream (version 8) keeps that mask exactly (mask.py; the block's
@@ -921,6 +995,16 @@ def compress_image(model, img, tile=256, batch=64, tail=10, segments=1, overlap=
     dev = next(model.parameters()).device
     tau = None if max_error is None else _residual.check_max_error(max_error, "compress_image")
     kind, H, W, C = _image_kind(img, "compress_image")
+    tol = None
+    if tolerance is not None:
+        tol = _residual16.check_tolerance(tolerance, "compress_image")
+        if kind != KIND_U16_HWC:
+            raise ValueError("compress_image: tolerance bounds the error of a uint16 [H,W,C] image; for a uint8 image "
+                             "use max_error (float32 has neither)")
+        for name, on in (("overlap > 0", overlap != 0), ("valid", valid is not None), ("nodata", nodata is not None),
+                         ("max_error", max_error is not None)):
+            if on:
+                raise ValueError(f"compress_image: tolerance together with {name} is not supported")
     if valid is None:
         if not (isinstance(fill, int) and not isinstance(fill, bool) and fill == 0):
             raise ValueError(f"compress_image: fill={fill!r} goes with valid, the mask it fills")
@@ -980,9 +1064,10 @@ def compress_image(model, img, tile=256, batch=64, tail=10, segments=1, overlap=
     if kind == KIND_U16_HWC and scale is None:
         scale = band_range(x)
     if len(shapes) == 1:
-        return _compress_device_image(model, x, tile, batch, tail, segments, overlap, tau, nodata, scale)
+        return _compress_device_image(model, x, tile, batch, tail, segments, overlap, tau, nodata, scale, tol=tol)
     return pack_pyramid_stream([_compress_device_image(model, lv, tile, batch, tail, segments, overlap,
-                                                       tau if level == 0 else None, scale=scale)
+                                                       tau if level == 0 else None, scale=scale,
+                                                       tol=tol if level == 0 else None)
                                 for level, lv in enumerate(build_overviews(x, overviews))])
 
 
@@ -1008,8 +1093,8 @@ def _refuse_foreign(model, h, what):
 def _stream_grid(h):
     """The tile grid a DSICI header describes; ValueError where its fields contradict each other."""
     H, W, C, th, tw = h["H"], h["W"], h["C"], h["th"], h["tw"]
-    kinds = {VERSION_U16: (KIND_U16_HWC,), VERSION_VALID: (KIND_U8_HWC, KIND_U16_HWC)}.get(h["version"],
-                                                                                           (KIND_U8_HWC, KIND_F32_CHW))
+    kinds = {VERSION_U16: (KIND_U16_HWC,), VERSION_TOL: (KIND_U16_HWC,),
+             VERSION_VALID: (KIND_U8_HWC, KIND_U16_HWC)}.get(h["version"], (KIND_U8_HWC, KIND_F32_CHW))
     if C != h["in_ch"] or h["kind"] not in kinds or h["batch"] < 1:
         raise ValueError("DSICI stream: inconsistent header")
     _check_image(H, W)
@@ -1080,8 +1165,12 @@ def _index_of(src, head=None):
         if ids is not None:
             containers[-1]["ids"] = ids[first:first + len(images)]
         if rframes:
-            recs = _residual.read_block_head(src.read_at, rframes[k][0], rframes[k][1], len(images), ix["C"],
-                                             ix["th"], ix["tw"], ix["max_error"])
+            if ix["version"] == VERSION_TOL:
+                recs = _residual16.read_block_head(src.read_at, rframes[k][0], rframes[k][1], len(images), ix["C"],
+                                                   ix["th"], ix["tw"], ix["tolerance"])
+            else:
+                recs = _residual.read_block_head(src.read_at, rframes[k][0], rframes[k][1], len(images), ix["C"],
+                                                 ix["th"], ix["tw"], ix["max_error"])
             for tile, rec in zip(tiles[first:], recs):
                 tile.update(rec)
             containers[-1].update(r_offset=rframes[k][0], r_bytes=rframes[k][1])
@@ -1112,6 +1201,10 @@ def stream_index(src, level=None) -> dict:
     and for a version-4 stream (only then) max_error; per tile r_off, r_len (its span in the batch's residual block:
     C x r_L table entries, then 16 strings), r_smin, r_L (the residual's support) and r_segs (the 16 string lengths);
     per batch r_offset, r_bytes (the block).  Of a residual block the 30-byte head, the 12-byte records and the 64
+    bytes of segment lengths per tile are read.
+    and for a version-9 stream (only then) tolerance and scale; per tile r_off, r_len (its span in the batch's wide
+    residual block: C x r_L table entries, r_k bit planes of C th tw / 8 bytes, then 16 strings), r_smin, r_L, r_k and
+    r_segs; per batch r_offset, r_bytes.  Of a wide residual block the 30-byte head, the 16-byte records and the 64
     bytes of segment lengths per tile are read.
     and for a version-5 stream (only then) nodata, coded, mask_offset, mask_bytes (the mask block); per tile state (0
     empty, 1 full, 2 mixed), for an empty tile k = b = None and zero lengths, for a mixed tile m_off, m_len, m_mode (its
@@ -1247,6 +1340,9 @@ def _check_out(out, ix, what):
     if out == "u16" and "scale" not in ix:
         raise ValueError(f"{what}: out='u16' needs the scale of a uint16 stream (version {VERSION_U16}); this one is "
                          f"version {ix['version']}")
+    if out in ("u8", "f32") and "tolerance" in ix:
+        raise ValueError(f"{what}: out={out!r} on a uint16 stream with a tolerance (version {VERSION_TOL}): the bound "
+                         "is on the uint16 values; take out=None or 'u16'")
     if out in ("u8", "f32") and "fill" in ix and ix["kind"] == KIND_U16_HWC:
         raise ValueError(f"{what}: out={out!r} on a uint16 stream with a validity mask (version {VERSION_VALID}): the "
                          "normalised image has no value that means fill")
@@ -1262,8 +1358,8 @@ def _coded_tiles(ix, tiles):
 def _decode_tiles(model, source, ix, sel, what):
     """One dense decode batch: the tiles `sel` (ascending) of an indexed level, their strings read from `source` in
     one upload -> (g_s's output [n,C,th,tw], contiguous and not clamped; the padded string bytes uploaded; the device
-    copy of sel; the q planes of a version-4 stream, else None)."""
-    C, th, tw, tau = ix["C"], ix["th"], ix["tw"], ix.get("max_error")
+    copy of sel; the q planes of a version-4 or version-9 stream, else None)."""
+    C, th, tw, tau, tol = ix["C"], ix["th"], ix["tw"], ix.get("max_error"), ix.get("tolerance")
     N, Hz, Wz = ix["containers"][0]["shape_z"][1:] if ix["containers"] else (ix["N"], 0, 0)
     n = len(sel)
     # the upload is the tiles' spans back to back: a string at stream offset o lies where its span does
@@ -1290,6 +1386,18 @@ def _decode_tiles(model, source, ix, sel, what):
                 "L": [r["r_L"] for r in recs], "segs": [r["r_segs"] for r in recs],
                 "desc": [(at(r["r_off"], r["r_len"]), 2 * C * r["r_L"],
                           at(r["r_off"], r["r_len"]) + 2 * C * r["r_L"], sum(r["r_segs"])) for r in recs]}
+    if tol is not None:                        # the same, with the tile's bit planes between tables and strings
+        pb = _residual16.plane_bytes(C, th, tw)
+        for r in recs:
+            i = bisect.bisect_right(starts, r["r_off"]) - 1
+            a = r["r_off"] - starts[i]
+            _residual16.check_tables(parts[i][a:a + 2 * C * r["r_L"]], C, r["r_L"])
+        spans_at = [at(r["r_off"], r["r_len"]) for r in recs]
+        spec = {"C": C, "th": th, "tw": tw, "tau": tol, "smin": [r["r_smin"] for r in recs],
+                "L": [r["r_L"] for r in recs], "segs": [r["r_segs"] for r in recs], "k": [r["r_k"] for r in recs],
+                "plane_off": [a + 2 * C * r["r_L"] for a, r in zip(spans_at, recs)],
+                "desc": [(a, 2 * C * r["r_L"], a + 2 * C * r["r_L"] + r["r_k"] * pb, sum(r["r_segs"]))
+                         for a, r in zip(spans_at, recs)]}
     x_hat, nbytes, ids, *q = entropy._decode_selected(model, images, parts, [n, ix["M"], th // 16, tw // 16],
                                                       [n, N, Hz, Wz], what, ride=sel, segments=ix["segments"],
                                                       seg_lengths=[r["y_segs"] for r in recs], residual=spec)
@@ -1307,6 +1415,7 @@ def _assemble_window(model, source, ix, tiles, window, kind, batches, what, vali
     lohi = (_lohi(ix["scale"]),) if kind == KIND_U16_HWC else ()        # the uint16 calls take the scale last
     tau = ix.get("max_error")                  # a residual layer: the result is the uint8 image, converted for "f32"
     img, suffix = _out_image(KIND_U8_HWC if tau is not None else kind, C, h, w, next(model.parameters()).device, what)
+    tol = ix.get("tolerance")                  # its uint16 sibling: the result is the uint16 image
     L, O = _lib.load(), ix["overlap"]
     fn = getattr(L, "dsic_tile_stitch_window_" + suffix)
     if O:       # the window's float32 canvas, zeroed: the output itself, or a temporary that the finish turns to uint8
@@ -1314,7 +1423,9 @@ def _assemble_window(model, source, ix, tiles, window, kind, batches, what, vali
     uploaded = taken = 0
     for x_hat, nbytes, ids, q in batches:
         n = x_hat.shape[0]
-        if q is not None:
+        if q is not None and tol is not None:
+            _residual16.stitch_window_u16(x_hat, q, tol, ids, img, H, W, C, th, tw, y0, x0, h, w, *lohi)
+        elif q is not None:
             _residual.stitch_window_u8(x_hat, q, tau, ids, img, H, W, C, th, tw, y0, x0, h, w)
         elif O:
             for c0 in range(0, n, BLEND_IDS):

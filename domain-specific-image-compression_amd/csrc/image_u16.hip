@@ -11,66 +11,11 @@
 // aligned 16-byte chunks (8 pixels' values) with element stores only at the ragged ends.  The gather reads the image
 // once: a lane takes 4 consecutive pixels of a row (8 C bytes), consecutive lanes consecutive runs, and stores one
 // float4 per plane.
-#include <limits.h>
-
 #include "byte_movers.h"
 #include "tile_grid.h"
+#include "u16_scale.h"
 
 namespace dsic {
-
-struct Scale {
-  uint32_t lo[4], R[4];
-};
-
-__device__ __forceinline__ uint32_t pick(const uint32_t (&a)[4], int c) {
-  return c == 0 ? a[0] : (c == 1 ? a[1] : (c == 2 ? a[2] : a[3]));
-}
-
-__device__ __forceinline__ float norm_u16(uint32_t v, uint32_t lo, uint32_t R) {
-  v = min(max(v, lo), lo + R) - lo;
-  return R ? __fdiv_rn((float)v, (float)R) : 0.f;
-}
-
-__device__ __forceinline__ uint16_t denorm_u16(float x, uint32_t lo, uint32_t R) {
-  x = x > 0.f ? (x > 1.f ? 1.f : x) : 0.f;  // clamp(x, 0, 1); a NaN becomes 0
-  return (uint16_t)(lo + (uint32_t)__fadd_rn(__fmul_rn(x, (float)R), 0.5f));
-}
-
-// 2 ND uint16 from any 2-byte aligned address.  Off a dword boundary the dwords read are those that hold the run's
-// first and last value, so no dword outside the allocation is touched.
-template <int ND>
-__device__ __forceinline__ void load_run(const uint16_t* p, uint16_t* out) {
-  uint32_t d[ND];
-  const uintptr_t a = (uintptr_t)p;
-  if ((a & 3) == 0) {
-    if (ND % 4 == 0 && (a & 15) == 0) {
-#pragma unroll
-      for (int k = 0; k < ND / 4; ++k) {
-        const uint4 v = ((const uint4*)p)[k];
-        d[4 * k] = v.x, d[4 * k + 1] = v.y, d[4 * k + 2] = v.z, d[4 * k + 3] = v.w;
-      }
-    } else if ((a & 7) == 0) {  // ND is even
-#pragma unroll
-      for (int k = 0; k < ND / 2; ++k) {
-        const uint2 v = ((const uint2*)p)[k];
-        d[2 * k] = v.x, d[2 * k + 1] = v.y;
-      }
-    } else {
-#pragma unroll
-      for (int k = 0; k < ND; ++k) d[k] = ((const uint32_t*)p)[k];
-    }
-  } else {
-    const uint32_t* w = (const uint32_t*)(a - 2);
-    uint32_t prev = w[0];
-#pragma unroll
-    for (int k = 0; k < ND; ++k) {
-      const uint32_t next = w[k + 1];
-      d[k] = __builtin_amdgcn_alignbyte(next, prev, 2);
-      prev = next;
-    }
-  }
-  __builtin_memcpy(out, d, 4 * ND);
-}
 
 // ---- band range -------------------------------------------------------------------------------------------
 
@@ -165,9 +110,13 @@ __global__ __launch_bounds__(256) void gather_u16_kernel(const uint16_t* __restr
 // tiles [n][C][th][tw] -> denorm into the uint16 HWC window image; the rectangles of stitch_u8_kernel.  Positions
 // count uint16 elements; `mis` is the window image's offset behind a 16-byte boundary in elements, so that chunk q0
 // (in elements shifted by mis) is an aligned 16 bytes of memory.
-__global__ __launch_bounds__(256) void stitch_u16_kernel(const float* __restrict__ tiles, uint16_t* __restrict__ img,
-                                                         Grid g, int C, const int* __restrict__ ids, Clip w, Scale s,
-                                                         int mis) {
+// RES (codec.py, tolerance = tau): the decoded residual steps q float32 [n][C][th][tw] (residual_u16.hip) are added,
+// a value is clamp(denorm(x_hat) + (int)q * step, 0, 65535) with step = 2 tau + 1; |q| <= (65535 + tau) / step as the
+// join kernel leaves it, so the sum stays inside int32.
+template <bool RES>
+__global__ __launch_bounds__(256) void stitch_u16_kernel(const float* __restrict__ tiles, const float* __restrict__ qres,
+                                                         int step, uint16_t* __restrict__ img, Grid g, int C,
+                                                         const int* __restrict__ ids, Clip w, Scale s, int mis) {
   Owned o;
   if (!stitch_rect(g, ids, 0, w, &o)) return;
   const int ya = o.y0 + blockIdx.x * kTileRows;
@@ -175,6 +124,7 @@ __global__ __launch_bounds__(256) void stitch_u16_kernel(const float* __restrict
   if (rows <= 0) return;
   const size_t cplane = (size_t)g.th * g.tw;
   const float* src = tiles + (size_t)blockIdx.y * C * cplane;
+  const float* qsrc = RES ? qres + (size_t)blockIdx.y * C * cplane : nullptr;
   const int wW = w.x1 - w.x0;
   const int seg = (o.x1 - o.x0) * C;
   const int cpr = seg / 8 + 2;  // 16-byte chunks a row segment can touch
@@ -194,6 +144,10 @@ __global__ __launch_bounds__(256) void stitch_u16_kernel(const float* __restrict
       b[e] = 0;
       if (q0 + e >= lo && q0 + e < hi) {
         b[e] = denorm_u16(srow[c * cplane + px], pick(s.lo, c), pick(s.R, c));
+        if constexpr (RES) {
+          const int v = (int)b[e] + (int)qsrc[(size_t)(y - o.oy) * g.tw + c * cplane + px] * step;
+          b[e] = (uint16_t)(v < 0 ? 0 : (v > 65535 ? 65535 : v));
+        }
         if (++c == C) c = 0, ++px;
       }
     }
@@ -332,38 +286,9 @@ static bool apart16(const void* a, int64_t a_bytes, const void* b, int64_t b_byt
   return pa + (uintptr_t)a_bytes <= pb || pb + (uintptr_t)b_bytes <= pa;
 }
 
-// the host's 2 C words (lo0, hi0, ...) as the kernels take them; nullptr where they are no scale
-static const char* scale_error(const uint32_t* lohi, int C, Scale* s) {
-  for (int c = 0; c < 4; ++c) s->lo[c] = s->R[c] = 0;
-  for (int c = 0; c < C; ++c) {
-    if (lohi[2 * c + 1] > 65535u) return "hi must be at most 65535";
-    if (lohi[2 * c] > lohi[2 * c + 1]) return "lo must not exceed hi";
-    s->lo[c] = lohi[2 * c], s->R[c] = lohi[2 * c + 1] - lohi[2 * c];
-  }
-  return nullptr;
-}
-
 }  // namespace dsic
 
 using namespace dsic;
-
-#define DSIC_U16_COMMON(what, img)                                                                                  \
-  DSIC_REQUIRE(C >= 1 && C <= 4, what ": C=%d must be in 1..4", C);                                                 \
-  DSIC_REQUIRE(((uintptr_t)(img) & 1) == 0, what ": the uint16 image must be 2-byte aligned")
-#define DSIC_U16_SCALE(what)                                                          \
-  Scale sc;                                                                           \
-  const char* se = scale_error(lohi, C, &sc);                                         \
-  DSIC_REQUIRE(!se, what ": scale: %s", se ? se : "")
-#define DSIC_U16_ROW(what, W)                                                                                       \
-  DSIC_REQUIRE((int64_t)(W) * C * 2 <= INT_MAX, what ": a row of W=%d pixels of C=%d uint16 is over 2^31 - 1 bytes", \
-               (W), C)
-#define DSIC_U16_BY_C(kernel, ...)                                                    \
-  switch (C) {                                                                        \
-    case 1: hipLaunchKernelGGL(kernel<1>, __VA_ARGS__); break;                        \
-    case 2: hipLaunchKernelGGL(kernel<2>, __VA_ARGS__); break;                        \
-    case 3: hipLaunchKernelGGL(kernel<3>, __VA_ARGS__); break;                        \
-    default: hipLaunchKernelGGL(kernel<4>, __VA_ARGS__); break;                       \
-  }
 
 extern "C" int dsic_band_range_u16(const uint16_t* img_hwc, int H, int W, int C, uint32_t* out_lohi_dev,
                                    void* stream) {
@@ -412,9 +337,23 @@ extern "C" int dsic_tile_stitch_window_u16(const float* tiles, const int* tile_i
   DSIC_U16_SCALE("tile_stitch_window_u16");
   DSIC_WINDOW_ARGS("tile_stitch_window_u16");
   DSIC_U16_ROW("tile_stitch_window_u16", ww);
-  hipLaunchKernelGGL(stitch_u16_kernel, grid, dim3(256), 0, (hipStream_t)stream, tiles, out, g, C, tile_ids, clip, sc,
-                     (int)(((uintptr_t)out & 15) >> 1));
+  hipLaunchKernelGGL(stitch_u16_kernel<false>, grid, dim3(256), 0, (hipStream_t)stream, tiles, (const float*)nullptr, 0,
+                     out, g, C, tile_ids, clip, sc, (int)(((uintptr_t)out & 15) >> 1));
   return check_launch("tile_stitch_window_u16");
+}
+
+extern "C" int dsic_tile_stitch_window_u16_res(const float* tiles, const float* q, int tau, const int* tile_ids,
+                                               int n_tiles, uint16_t* out, int H, int W, int C, int th, int tw, int wy0,
+                                               int wx0, int wh, int ww, const uint32_t* lohi, void* stream) {
+  DSIC_REQUIRE(tiles && q && tile_ids && out && lohi, "tile_stitch_window_u16_res: null pointer");
+  DSIC_U16_COMMON("tile_stitch_window_u16_res", out);
+  DSIC_REQUIRE(tau >= 0 && tau <= 32767, "tile_stitch_window_u16_res: tau=%d must be in 0..32767", tau);
+  DSIC_U16_SCALE("tile_stitch_window_u16_res");
+  DSIC_WINDOW_ARGS("tile_stitch_window_u16_res");
+  DSIC_U16_ROW("tile_stitch_window_u16_res", ww);
+  hipLaunchKernelGGL(stitch_u16_kernel<true>, grid, dim3(256), 0, (hipStream_t)stream, tiles, q, 2 * tau + 1, out, g, C,
+                     tile_ids, clip, sc, (int)(((uintptr_t)out & 15) >> 1));
+  return check_launch("tile_stitch_window_u16_res");
 }
 
 extern "C" int dsic_tile_blend_finish_u16(const float* canvas, uint16_t* out_hwc, int C, int h, int w,

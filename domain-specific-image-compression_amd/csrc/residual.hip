@@ -296,6 +296,23 @@ extern "C" int dsic_residual_tables(const int* hist, int n, int C, int th, int t
   return check_launch("residual_tables");
 }
 
+// The tables of the wide residual's high part (residual_u16.hip): the same kernel at Q = 255, rows of res_lmax(0) =
+// 512, for the 1 to 4 bands of a uint16 image.
+extern "C" int dsic_residual_tables_u16(const int* hist, int n, int C, int th, int tw, int* meta, uint16_t* compact,
+                                        uint16_t* coder, void* stream) {
+  DSIC_REQUIRE(hist && meta && compact && coder, "residual_tables_u16: null pointer");
+  DSIC_REQUIRE(C >= 1 && C <= 4, "residual_tables_u16: C=%d must be in 1..4", C);
+  DSIC_REQUIRE(n >= 1 && n <= 3000, "residual_tables_u16: n=%d tiles per call (1..3000)", n);
+  DSIC_REQUIRE(th >= 16 && tw >= 16 && th % 16 == 0 && tw % 16 == 0 && (int64_t)th * tw < ((int64_t)1 << 30),
+               "residual_tables_u16: tile %dx%d: sides must be multiples of 16 (th %% 16)", th, tw);
+  DSIC_REQUIRE(((uintptr_t)hist & 3) == 0 && ((uintptr_t)meta & 3) == 0 &&
+                   (((uintptr_t)compact | (uintptr_t)coder) & 15) == 0,
+               "residual_tables_u16: hist and meta must be 4-byte, compact and coder 16-byte aligned");
+  hipLaunchKernelGGL(residual_tables_kernel, dim3(C, n), dim3(64), 0, (hipStream_t)stream, hist, C, th * tw, 0,
+                     res_lmax(0), meta, compact, coder);
+  return check_launch("residual_tables_u16");
+}
+
 extern "C" int dsic_residual_pack(const uint8_t* bytes, int64_t cap_z, int64_t cap_seg, const int* lengths,
                                   const int* meta, const uint16_t* compact, const int* err, int n, int C, int th, int tw,
                                   int tau, int Lmax, int64_t* workspace, uint8_t* out, void* stream) {

@@ -619,7 +619,7 @@ def _decode_selected(model, images, parts, shape_y, shape_z, what, Lmax=None, ri
     array `ride` (codec's tile numbers).  The device spreads the strings at custom_decompress's strides (_upload_strings) and decodes with Lmax
     (default: _default_lmax over these images).  Returns (g_s's output, not yet clamped; the padded string bytes
     uploaded; the device copy of ride).
-    residual (codec's near-lossless streams): the spec of residual.decode_q, whose spans lie in `parts` beside the
+    residual (codec's near-lossless streams): the spec of residual.decode_q or residual16.decode_q, whose spans lie in `parts` beside the
     strings; its control words travel behind ride in the same copy, and the tuple gains the decoded q planes."""
     dev = next(model.parameters()).device
     n = len(images)
@@ -635,9 +635,10 @@ def _decode_selected(model, images, parts, shape_y, shape_z, what, Lmax=None, ri
     if nseg:
         block[6 * n:].view(np.int32)[:nseg] = np.asarray(seg_lengths, dtype=np.int32).reshape(nseg)
     block[6 * n:].view(np.int32)[nseg:nseg + ride.size] = ride
-    if residual is not None:
-        from . import residual as _residual
-        block = np.concatenate([block, _residual.control_words(residual)])
+    if residual is not None:                       # a spec with shifts "k" is the wide residual of a uint16 stream
+        from . import residual as _residual, residual16 as _residual16
+        layer = _residual16 if "k" in residual else _residual
+        block = np.concatenate([block, layer.control_words(residual)])
     d_blob, total, d_block = _upload_padded(parts, block, dev)
     d_block = d_block.view(torch.int64)
     meta = d_block[4 * n:6 * n].view(torch.int32).view(n, 4)
@@ -655,7 +656,7 @@ def _decode_selected(model, images, parts, shape_y, shape_z, what, Lmax=None, ri
     x_hat = _decode_batch(model, shape_y, shape_z, meta, Lmax, (zbuf, zstride, lengths, 2, 0),
                           (ybuf, ystride, lengths, 2, 1), what, segments, tail32[:nseg] if nseg else None)
     if residual is not None:
-        q = _residual.decode_q(d_blob, total, d_block[6 * n + tail_words:], residual)
+        q = layer.decode_q(d_blob, total, d_block[6 * n + tail_words:], residual)
         return x_hat, _padded_bytes(total), tail32[nseg:nseg + ride.size], q
     return x_hat, _padded_bytes(total), tail32[nseg:nseg + ride.size]
 

@@ -118,6 +118,12 @@ SIGNATURES = {
     "dsic_residual_tables": (c_int, [_P] + [c_int] * 6 + [_P, _P, _P, _P]),
     "dsic_residual_pack": (c_int, [_P, c_int64, c_int64, _P, _P, _P, _P] + [c_int] * 6 + [_P, _P, _P]),
     "dsic_tile_stitch_window_u8_res": (c_int, [_P, _P, c_int, _P, c_int, _P] + [c_int] * 9 + [_P]),
+    "dsic_residual_quantize_u16": (c_int, [_P, _P] + [c_int] * 5 + [_P] + [c_int] * 3 + [_P, _P, _P]),
+    "dsic_residual_split_u16": (c_int, [_P, _P] + [c_int] * 4 + [_P, _P, _P, _P, _P]),
+    "dsic_residual_tables_u16": (c_int, [_P] + [c_int] * 4 + [_P, _P, _P, _P]),
+    "dsic_residual_pack_u16": (c_int, [_P, c_int64, c_int64, _P, _P, _P, _P, _P, _P] + [c_int] * 5 + [_P, _P, _P]),
+    "dsic_residual_join_u16": (c_int, [_P, _P, c_int64, _P, _P] + [c_int] * 5 + [_P, _P]),
+    "dsic_tile_stitch_window_u16_res": (c_int, [_P, _P, c_int, _P, c_int, _P] + [c_int] * 9 + [_P, _P]),
     "dsic_image_halve_u8": (c_int, [_P, _P, c_int, c_int, c_int, _P]),
     "dsic_image_halve_f32": (c_int, [_P, _P, c_int, c_int, c_int, _P]),
     "dsic_mask_classify_u8": (c_int, [_P] + [c_int] * 8 + [_P, _P]),

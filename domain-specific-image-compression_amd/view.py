@@ -43,9 +43,14 @@ def view_level(n_levels, h, w, oh, ow) -> int:
     return 0
 
 
+def _has_q(ix):
+    """Whether a level carries a residual layer: max_error (version 4) or tolerance (version 9)."""
+    return ix.get("max_error") is not None or ix.get("tolerance") is not None
+
+
 def _tile_bytes(ix):
     """What a cached tile of an indexed level costs: float32 [C, th, tw], and as much again for its q plane."""
-    return 4 * ix["C"] * ix["th"] * ix["tw"] * (2 if ix.get("max_error") is not None else 1)
+    return 4 * ix["C"] * ix["th"] * ix["tw"] * (2 if _has_q(ix) else 1)
 
 
 def _new_stats():
@@ -58,7 +63,7 @@ class _Slab:
 
     def __init__(self, ix, dev):
         self.shape = (ix["C"], ix["th"], ix["tw"])
-        self.has_q = ix.get("max_error") is not None
+        self.has_q = _has_q(ix)
         self.tile_bytes = _tile_bytes(ix)
         self.dev, self.slots, self.free, self.cap = dev, {}, [], 0
         self.x = self.q = self.ids = None

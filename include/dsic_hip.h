@@ -594,6 +594,60 @@ int dsic_tile_stitch_window_u8_res(const float* tiles, const float* q, int tau,
                                    const int* tile_ids, int n, uint8_t* out, int H, int W, int C,
                                    int th, int tw, int wy0, int wx0, int wh, int ww, void* stream);
 
+/* ---- bounded-error residual layer for uint16 images (codec.compress_image with tolerance = tau,
+ * 0..32767; stream version 9).  max_error above stays the uint8 mode; this is its uint16 sibling.
+ * Per tile, with x the uint16 image [H][W][C] (C 1..4, any 2-byte alignment), the scale lohi (host,
+ * 2*C words) and x_hat the encoder's forward reconstruction float32 [C][th][tw]:
+ *   p = denorm(x_hat) = lo + (uint32)(clamp(x_hat,0,1)*(float)R + 0.5f)  (the uint16 stitch's value),
+ *   r = x - p, s = 2 tau + 1, q = sign(r) * floor((|r| + tau) / s), |q| <= Q16 = (65535 + tau) / s,
+ *   q = 0 outside the rectangle the tile owns; the decoder writes clamp(p + q s, 0, 65535), within
+ *   tau of x.  Per tile q is split with m = max |q| and k the least shift with m <= 255 << k (0..9):
+ *   hi = q >> k (arithmetic) in [-255, 255], lo = q & (2^k - 1).  hi is coded as the uint8 layer's q
+ *   at tau = 0 (bin hi + 255 of 512, Lmax = 512, 16 row bands as 16 segments); lo travels raw as k
+ *   bit planes of C*th*tw/8 bytes: bit b of byte i of plane j is bit j of lo of sample 8 i + b in
+ *   [C][th][tw] order.  All integer.
+ * residual_quantize_u16: tiles first_tile .. first_tile + n_tiles - 1 of the grid (H, W, th, tw),
+ *   x_hat float32 [n][C][th][tw] -> q int32 [n][C][th][tw] and maxabs int32 [n], to which max |q| is
+ *   applied by an integer atomic max (the caller zeroes it).  Only owned pixels are read.  x_hat, q
+ *   16-byte aligned; n_tiles in 1..3000.
+ * residual_split_u16: q, maxabs -> k int32 [n], hi float32 [n][C][th][tw] (clamped to +-255), hist
+ *   int32 [n][C][512] (ADDED at bin hi + 255; the caller zeroes it) and planes uint64
+ *   [n][9][C*th*tw/64], of which the first k[t] of tile t are written: word w of plane j is the
+ *   64-bit ballot of bit j of lo over samples 64 w .. 64 w + 63.
+ * residual_tables_u16: dsic_residual_tables at Q = 255 and Lmax = 512 for C 1..4: meta int32 [n][4]
+ *   = (smin, L, 0, 1), compact uint16 [n][C][512], coder uint16 [n][C*16][512].
+ * residual_pack_u16: the wide residual block of a batch: "DSICW\0" | n, C, th, tw, tau, 16 u32 |
+ *   n x (smin i32, L u32, k u32, span_bytes u32) | n x 16 u32 segment lengths | per tile its span:
+ *   C x L uint16 table entries, k planes, then the 16 segment strings (bytes, lengths, cap_z,
+ *   cap_seg as dsic_residual_pack takes them).  out holds at least 30 + 80*n + n*(2*C*512 +
+ *   9*C*th*tw/8 + 16*cap_seg) bytes; workspace: (C+17)*n + 3 int64, [0] = block bytes, [1] = *err.
+ * residual_join_u16: hi float32 [n][C][th][tw] (decoded), blob the uploaded bytes (`total` of
+ *   them) in which tile t's k[t] planes lie back to back from byte plane_off[t] (int64, any
+ *   alignment; planes that would leave the blob read as 0; k clamped to 0..9) -> q float32
+ *   [n][C][th][tw] = hi * 2^k + lo, clamped to +-Q16.  hi, q 16-byte aligned.
+ * tile_stitch_window_u16_res: dsic_tile_stitch_window_u16 with q added: a value is
+ *   clamp(denorm(x_hat) + (int)q * (2 tau + 1), 0, 65535).
+ * DSIC_EINVAL: null pointers, C outside 1..4, tau outside 0..32767, n outside 1..3000, tile sides
+ * that are no multiples of 16, misaligned buffers, a bad scale or grid. */
+int dsic_residual_quantize_u16(const uint16_t* img_hwc, const float* x_hat, int H, int W, int C,
+                               int th, int tw, const uint32_t* lohi, int tau, int first_tile,
+                               int n_tiles, int* q, int* maxabs, void* stream);
+int dsic_residual_split_u16(const int* q, const int* maxabs, int n, int C, int th, int tw,
+                            float* hi, int* hist, int* k, uint64_t* planes, void* stream);
+int dsic_residual_tables_u16(const int* hist, int n, int C, int th, int tw, int* meta,
+                             uint16_t* compact, uint16_t* coder, void* stream);
+int dsic_residual_pack_u16(const uint8_t* bytes, int64_t cap_z, int64_t cap_seg, const int* lengths,
+                           const int* meta, const int* k, const uint16_t* compact,
+                           const uint64_t* planes, const int* err, int n, int C, int th, int tw,
+                           int tau, int64_t* workspace, uint8_t* out, void* stream);
+int dsic_residual_join_u16(const float* hi, const uint8_t* blob, int64_t total,
+                           const int64_t* plane_off, const int* k, int n, int C, int th, int tw,
+                           int tau, float* q, void* stream);
+int dsic_tile_stitch_window_u16_res(const float* tiles, const float* q, int tau,
+                                    const int* tile_ids, int n_tiles, uint16_t* out, int H, int W,
+                                    int C, int th, int tw, int wy0, int wx0, int wh, int ww,
+                                    const uint32_t* lohi, void* stream);
+
 /* ---- image overviews (codec.build_overviews, compress_image with overviews = n) ----
  * One level of the pyramid from the one before it: dst is H2 x W2, H2 = ceil(H/2), W2 = ceil(W/2),
  * and output pixel (y, x) is taken from source rows 2y and min(2y+1, H-1) and columns 2x and

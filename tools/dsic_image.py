@@ -3,7 +3,7 @@ an image.
 
     python tools/dsic_image.py compress   --weights CKPT.pt IN.png  OUT.dsic [--tile 256] [--batch 64] [--segments K] [--overlap O]
                                           [--max-error T] [--overviews N] [--nodata V] [--scale LO,HI[,LO,HI...]]
-                                          [--valid MASK [--fill V]]
+                                          [--valid MASK [--fill V]] [--tolerance T]
     python tools/dsic_image.py decompress --weights CKPT.pt IN.dsic OUT.png [--out u8|f32|u16] [--region Y0,X0,H,W]
                                           [--level L] [--size OH,OW] [--resampling average|nearest]
                                           [--valid-out FILE.npy]
@@ -30,6 +30,11 @@ that carries a per-band scale: --scale LO,HI for all bands or LO,HI,LO,HI,... on
 own minimum and maximum; values outside a pair clip.  Such a stream decodes to uint16 again (--out u16 says so
 explicitly and is refused for any other stream; --out u8 / f32 give the normalised image), written as .npy only; info
 prints the scale.
+--tolerance T (0 .. 32767, uint16 images only; --max-error stays the uint8 mode; not with --overlap, --valid, --nodata
+or --max-error) adds the bounded-error residual layer of 16-bit imagery (a version-9 stream): every decoded value lies
+within T of the original, 0 returns the image itself.  With --overviews it bounds level 0 only.  Such a stream decodes
+to uint16 only; info prints the tolerance, the residual layer's bytes and how many tiles took which shift k (the raw
+bit planes per sample).
 
 The state dict is loaded plain or from under "model" (code/modelv2/eval_selfcontained_entropy.py:130-134); the model's
 N, M, input channels and spatial_params are read from its shapes.  Images are PNG through PIL when PIL is importable
@@ -149,6 +154,12 @@ def print_info(ix):
         res = sum(c["r_bytes"] for c in ix["containers"])
         print(f"[dsic_image] near-lossless: max_error {ix['max_error']}, residual layer {res} bytes "
               f"({8.0 * res / (ix['H'] * ix['W']):.4f} bpp), lossy layer {sum(c['bytes'] for c in ix['containers'])} bytes")
+    if ix.get("tolerance") is not None:
+        res = sum(c["r_bytes"] for c in ix["containers"])
+        ks = [t["r_k"] for t in ix["tiles"]]
+        print(f"[dsic_image] bounded error: tolerance {ix['tolerance']}, residual layer {res} bytes "
+              f"({8.0 * res / (ix['H'] * ix['W']):.4f} bpp), lossy layer {sum(c['bytes'] for c in ix['containers'])} bytes; "
+              "tiles per shift k: " + ", ".join(f"k={k}: {ks.count(k)}" for k in sorted(set(ks))))
     if ix.get("nodata") is not None:
         states = [t["state"] for t in ix["tiles"]]
         print(f"[dsic_image] nodata {ix['nodata']}: {states.count(0)} empty, {states.count(1)} full, "
@@ -182,6 +193,9 @@ def main(argv=None):
     ap.add_argument("--overlap", type=int, default=0, help="compress: pixels neighbouring tiles share and cross-fade")
     ap.add_argument("--max-error", type=int, default=None, metavar="T",
                     help="compress: near-lossless, every decoded pixel within T (0 .. 127) of the original; 0 = lossless")
+    ap.add_argument("--tolerance", type=int, default=None, metavar="T",
+                    help="compress, uint16 images: every decoded value within T (0 .. 32767) of the original; 0 = "
+                         "lossless")
     ap.add_argument("--out", choices=("u8", "f32", "u16"), default=None,
                     help="decoded kind (default: the encoder's input's; u16 only for a uint16 stream)")
     ap.add_argument("--scale", default=None, metavar="LO,HI[,LO,HI...]",
@@ -264,7 +278,7 @@ def main(argv=None):
             ap.error(str(e) if "--scale" in str(e) else f"--scale {a.scale}: integers LO,HI[,LO,HI...]")
         stream = codec.compress_image(model, img, tile=a.tile, batch=a.batch, tail=a.tail, segments=a.segments,
                                       overlap=a.overlap, max_error=a.max_error, overviews=a.overviews, nodata=a.nodata,
-                                      scale=scale, **({} if a.valid is None else
+                                      scale=scale, tolerance=a.tolerance, **({} if a.valid is None else
                                                       {"valid": read_valid(a.valid), "fill": a.fill or 0}))
         with open(a.dst, "wb") as f:
             f.write(stream)
@@ -278,6 +292,7 @@ def main(argv=None):
         print(f"[dsic_image] {h['H']}x{h['W']}x{h['C']} -> {len(stream)} bytes, {codec.image_bpp(stream):.4f} bpp, "
               f"{h['batches']} batch(es) of {h['th']}x{h['tw']} tiles, {h['segments']} segment(s) per y string, "
               f"overlap {h['overlap']}" + (f", max_error {h['max_error']}" if "max_error" in h else "")
+              + (f", tolerance {h['tolerance']}" if "tolerance" in h else "")
               + (f", nodata {h['nodata']}: {h['coded']} coded tile(s)" if "nodata" in h else "")
               + (f", fill {h['fill']}: {h['coded']} coded tile(s)" if "fill" in h else "")
               + (f", scale {h['scale']}" if "scale" in h else ""))

@@ -39,6 +39,13 @@ Every figure is the best of --reps full passes over the scene after one warm-up 
           four-tile decompress_region in ms, and the band-range pass alone.  Written to profiles/u16_bench.json (or
           --json).  Records, not bars.
 
+--tolerance T[,T2...]  the bounded-error mode of 16-bit imagery: a four-band uint16 scene over (0, 10000), its
+          version-6 stream and a version-9 stream of every T given, read alternately in one run (medians of --reps
+          readings): stream bytes split into the lossy and the residual layer, residual bits per sample beside the
+          empirical entropy of q (so that the overhead of the per-tile split shows), the tiles per shift k, the worst
+          error of the decode, compress_image / decompress_image and a one-tile decompress_region in ms.  Written to
+          profiles/tolerance_u16_bench.json (or --json).  Records, not bars.
+
 --region  decompress_region of the same stream for an aligned one-tile window, an unaligned 2 x 2-tile-sized window
           (9 tiles), an unaligned half-scene window and the whole image, beside decompress_image before and after
           them in the same run (the two readings show the run-to-run spread).  Records, not bars.
@@ -364,6 +371,73 @@ def u16_records(model, scene01, img_u8, a):
     return res
 
 
+def tolerance_records(a, taus):
+    """A four-band uint16 scene over (0, 10000): the version-6 stream (None) and tolerance = every tau of `taus`,
+    alternately."""
+    import statistics
+    import numpy as np
+    import torch
+    from dsic_amd import codec
+    from dsic_amd import synthetic as S
+    from dsic_amd.model import CompressionModel
+    t, size, C = a.tile, a.size, 4
+    sd = S.make_state_dict(seed=1, in_ch=C)
+    model = CompressionModel(N=128, M=192, spatial_params=False, min_nu=2, max_nu=100.0, in_ch=C)
+    model.load_state_dict({k: torch.from_numpy(v) for k, v in sd.items()}, strict=True)
+    model = model.cuda().eval()
+    per = size // t
+    p = S.make_patches(0, per * per, t, t, C)
+    scene = p.reshape(per, per, C, t, t).transpose(0, 3, 1, 4, 2).reshape(size, size, C).astype(np.float64)
+    img = torch.from_numpy((scene * 10000.0 + 0.5).astype(np.uint16)).cuda()
+    scale = [(0, 10000)] * C
+    modes = [None] + list(taus)
+    streams = {m: codec.compress_image(model, img, tile=t, batch=a.batch, scale=scale, tolerance=m) for m in modes}
+    lossy = codec.unpack_image_stream(streams[None])["blobs"]
+    x = img.to(torch.int32)
+    pred = codec.decompress_image(model, streams[None]).to(torch.int32)
+    jobs = {"compress_image": lambda m: codec.compress_image(model, img, tile=t, batch=a.batch, scale=scale, tolerance=m),
+            "decompress_image": lambda m: codec.decompress_image(model, streams[m]),
+            "region_one_tile": lambda m: codec.decompress_region(model, streams[m], 4 * t, 4 * t, t, t, batch=a.batch)}
+    reads = {name: {m: [] for m in modes} for name in jobs}
+    for name, job in jobs.items():
+        for m in modes:
+            job(m)                                                     # warm-up
+        torch.cuda.synchronize()
+        for _ in range(a.reps):
+            for m in modes:
+                t0 = time.perf_counter()
+                job(m)
+                torch.cuda.synchronize()
+                reads[name][m].append(1e3 * (time.perf_counter() - t0))
+    res = {"what": "the version-6 stream of a uint16 scene against bounded-error streams (tolerance = tau), read "
+                   "alternately in one run on one MI355X; medians.  Synthetic weights: the lossy layer predicts poorly, "
+                   "so the residual bytes are an upper end, not a trained model's",
+           "scene": f"{size}x{size}x{C} uint16 over (0, 10000)", "tile": t, "batch": a.batch, "reps": a.reps,
+           "samples": size * size * C, "modes": {}}
+    for m in modes:
+        u = codec.unpack_image_stream(streams[m])
+        out = codec.decompress_image(model, streams[m]).to(torch.int32)
+        worst = int((out - x).abs().max())
+        rbytes = sum(len(b) for b in u.get("residuals", []))
+        rec = {"stream_bytes": len(streams[m]), "lossy_bytes": sum(len(b) for b in u["blobs"]), "residual_bytes": rbytes,
+               "bpp": round(codec.image_bpp(streams[m]), 4), "max_abs_error": worst}
+        if m is not None:
+            assert u["blobs"] == lossy and worst <= m, "the bounded-error stream broke its contract"
+            r = x - pred
+            q = torch.sign(r) * ((r.abs() + m) // (2 * m + 1))         # the arithmetic of residual16.py, on every sample
+            counts = torch.unique(q, return_counts=True)[1].to(torch.float64)
+            pr = counts / counts.sum()
+            ks = [tile["r_k"] for tile in codec.stream_index(streams[m])["tiles"]]
+            rec.update(residual_bits_per_sample=round(8.0 * rbytes / (size * size * C), 4),
+                       entropy_of_q_bits_per_sample=round(float(-(pr * torch.log2(pr)).sum()), 4),
+                       max_abs_q=int(q.abs().max()), tiles_per_k={str(k): ks.count(k) for k in sorted(set(ks))})
+        for name in jobs:
+            med = statistics.median(reads[name][m])
+            rec[name] = {"ms_median": round(med, 3), "ms_all": [round(v, 3) for v in reads[name][m]]}
+        res["modes"]["version 6" if m is None else str(m)] = rec
+    return res
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--size", type=int, default=4096)
@@ -381,7 +455,15 @@ def main():
                     help="measure a scene with a wedge of nodata, coded without and with nodata=0, alternately")
     ap.add_argument("--u16", action="store_true",
                     help="measure the scene as uint16 (stream version 6) against the uint8 scene, alternately")
+    ap.add_argument("--tolerance", default=None, metavar="T[,T2...]",
+                    help="measure bounded-error uint16 streams (tolerance = T) against the version-6 stream, alternately")
     a = ap.parse_args()
+    if a.tolerance is not None:
+        res = tolerance_records(a, [int(v) for v in a.tolerance.split(",")])
+        print(json.dumps(res))
+        with open(a.json or os.path.join(ROOT, "profiles", "tolerance_u16_bench.json"), "w") as f:
+            json.dump(res, f, indent=1)
+        return
 
     import numpy as np
     import torch
