@@ -1534,4 +1534,4 @@ def decompress_valid(src, y0=0, x0=0, h=None, w=None, level=0, device="cuda"):
     return valid.bool()
 
 
-from .view import ImageReader, view_level  # noqa: E402  (view.py builds on the functions above)
+from .view import ImageReader, stretch_from_histogram, view_level  # noqa: E402  (view.py builds on the functions above)

@@ -28,6 +28,12 @@ inline int check_launch(const char* what) {
     }                                    \
   } while (0)
 
+// whether the byte ranges [a, a + a_bytes) and [b, b + b_bytes) do not meet
+inline bool buffers_apart(const void* a, int64_t a_bytes, const void* b, int64_t b_bytes) {
+  const uintptr_t pa = (uintptr_t)a, pb = (uintptr_t)b;
+  return pa + (uintptr_t)a_bytes <= pb || pb + (uintptr_t)b_bytes <= pa;
+}
+
 inline int ceil_div(int a, int b) { return (a + b - 1) / b; }
 inline int round_up(int a, int b) { return ceil_div(a, b) * b; }
 

@@ -16,6 +16,8 @@
 // pixels stay out of S and T (0 = invalid; no value is compared), T = 0 gives the fill and validity 0 in the optional
 // output validity [oh][ow], and nearest copies pixel and validity.
 // nearest: source row (y0 2 oh + (2 i + 1) h) / (2 oh) >> l = (y0 + (2 i + 1) h / (2 oh)) >> l, columns likewise; a copy.
+// render (codec.ImageReader.render, the _render exports): the same pixel, of which chosen channels are stretched to
+// bytes between two values per channel, with the validity as alpha; the resampled samples never reach memory.
 //
 // A wave covers 64 consecutive pixels of an output row, so its loads walk the source rows in step and its stores are
 // one run of 64 C elements; each source pixel is needed by at most two output rows and two output columns when the
@@ -53,12 +55,57 @@ __device__ __forceinline__ int axis_nearest(int i, int len, int n, int o, int sh
 
 constexpr int VIEW_BX = 64, VIEW_BY = 4;  // output pixels of a workgroup: 4 rows of 64
 
+// One output pixel (i, j) of the integer kinds: its C resampled samples into m, and whether anything counted under it.
 // T = uint8_t or uint16_t, [.][.][C] with C <= 4; nodata < 0 = none.  The weights are taken with h / oh and w / ow in
 // lowest terms: every interval end is a multiple of gcd(h, oh), so this divides all wy by it, S and T alike, and
 // (2 S + T) / (2 T) is the same integer while S and T stay small (halving: T = 4).
 // V: the validity window sval [sh][sw] (0 = invalid) decides what stays out of S and T instead of a comparison with
-// nodata, T = 0 writes nodata (the fill) and, where oval is not null, oval [oh][ow] receives 1 or 0; nearest copies
-// the pixel and its validity.
+// nodata, and the result says whether the pixel is valid (nearest: its source pixel's validity); T = 0 gives nodata
+// (the fill) in every channel.  Without V the result is true.
+// need: bit c set = channel c is wanted; the others' divisions are skipped and their m is not defined.
+template <typename T, bool V>
+__device__ __forceinline__ bool resample_pixel(const T* __restrict__ src, const uint8_t* __restrict__ sval, const View& v,
+                                               int C, int mode, int nodata, int i, int j, int need, uint32_t m[4]) {
+  if (mode == 1) {
+    const int Y = axis_nearest(i, v.hn, v.hd, v.y0, v.shift), X = axis_nearest(j, v.wn, v.wd, v.x0, v.shift);
+    const T* p = src + ((int64_t)(Y - v.sy0) * v.sw + (X - v.sx0)) * C;
+#pragma unroll
+    for (int c = 0; c < 4; ++c) m[c] = c < C ? (uint32_t)p[c] : 0u;
+    return V ? sval[(int64_t)(Y - v.sy0) * v.sw + (X - v.sx0)] != 0 : true;
+  }
+  const Span ry = axis_span(i, v.hn, v.hd, v.y0, v.shift), rx = axis_span(j, v.wn, v.wd, v.x0, v.shift);
+  uint64_t S[4] = {0, 0, 0, 0}, Tw = 0;
+  for (int Y = ry.a; Y <= ry.b; ++Y) {
+    const uint64_t wy = (uint64_t)axis_weight(i, v.hn, v.hd, v.y0, v.shift, Y);
+    const T* row = src + (int64_t)(Y - v.sy0) * v.sw * C;
+    for (int X = rx.a; X <= rx.b; ++X) {
+      const uint64_t wgt = wy * (uint64_t)axis_weight(j, v.wn, v.wd, v.x0, v.shift, X);
+      const T* p = row + (int64_t)(X - v.sx0) * C;
+      uint32_t val[4];
+      bool nd = V ? sval[(int64_t)(Y - v.sy0) * v.sw + (X - v.sx0)] == 0 : nodata >= 0;
+#pragma unroll
+      for (int c = 0; c < 4; ++c) {
+        val[c] = c < C ? (uint32_t)p[c] : 0u;
+        if (!V && c < C) nd = nd && val[c] == (uint32_t)nodata;
+      }
+      if (nd) continue;
+      Tw += wgt;
+#pragma unroll
+      for (int c = 0; c < 4; ++c) S[c] += wgt * val[c];
+    }
+  }
+  // (2 S + T) / (2 T): in 32 bits where both fit, which reduced weights nearly always allow
+  const bool narrow = ((2 * (S[0] | S[1] | S[2] | S[3]) + Tw) >> 32) == 0 && (Tw >> 31) == 0;
+#pragma unroll
+  for (int c = 0; c < 4; ++c) {
+    if (c >= C || !((need >> c) & 1)) continue;
+    const uint64_t num = 2 * S[c] + Tw, den = 2 * Tw;
+    m[c] = !Tw ? (uint32_t)(T)nodata : narrow ? (uint32_t)num / (uint32_t)den : (uint32_t)(num / den);
+  }
+  return V ? Tw != 0 : true;
+}
+
+// The resampled window itself: dst [oh][ow][C] and, with V and oval not null, oval [oh][ow] = 1 or 0.
 template <typename T, bool V>
 __global__ __launch_bounds__(VIEW_BX * VIEW_BY) void resample_int_kernel(const T* __restrict__ src,
                                                                          T* __restrict__ dst, View v, int C, int mode,
@@ -72,43 +119,59 @@ __global__ __launch_bounds__(VIEW_BX * VIEW_BY) void resample_int_kernel(const T
     if (i64 >= v.oh || j >= v.ow) continue;
     const int i = (int)i64;
     T* o = dst + ((int64_t)i * v.ow + j) * C;
-    if (mode == 1) {
-      const int Y = axis_nearest(i, v.hn, v.hd, v.y0, v.shift), X = axis_nearest(j, v.wn, v.wd, v.x0, v.shift);
-      const T* p = src + ((int64_t)(Y - v.sy0) * v.sw + (X - v.sx0)) * C;
-      for (int c = 0; c < C; ++c) o[c] = p[c];
-      if (V && oval) oval[(int64_t)i * v.ow + j] = (uint8_t)(sval[(int64_t)(Y - v.sy0) * v.sw + (X - v.sx0)] != 0);
-      continue;
-    }
-    const Span ry = axis_span(i, v.hn, v.hd, v.y0, v.shift), rx = axis_span(j, v.wn, v.wd, v.x0, v.shift);
-    uint64_t S[4] = {0, 0, 0, 0}, Tw = 0;
-    for (int Y = ry.a; Y <= ry.b; ++Y) {
-      const uint64_t wy = (uint64_t)axis_weight(i, v.hn, v.hd, v.y0, v.shift, Y);
-      const T* row = src + (int64_t)(Y - v.sy0) * v.sw * C;
-      for (int X = rx.a; X <= rx.b; ++X) {
-        const uint64_t wgt = wy * (uint64_t)axis_weight(j, v.wn, v.wd, v.x0, v.shift, X);
-        const T* p = row + (int64_t)(X - v.sx0) * C;
-        uint32_t val[4];
-        bool nd = V ? sval[(int64_t)(Y - v.sy0) * v.sw + (X - v.sx0)] == 0 : nodata >= 0;
+    uint32_t m[4];
+    const bool ok = resample_pixel<T, V>(src, sval, v, C, mode, nodata, i, j, 15, m);
 #pragma unroll
-        for (int c = 0; c < 4; ++c) {
-          val[c] = c < C ? (uint32_t)p[c] : 0u;
-          if (!V && c < C) nd = nd && val[c] == (uint32_t)nodata;
-        }
-        if (nd) continue;
-        Tw += wgt;
+    for (int c = 0; c < 4; ++c)
+      if (c < C) o[c] = (T)m[c];
+    if (V && oval) oval[(int64_t)i * v.ow + j] = (uint8_t)ok;
+  }
+}
+
+// The rendered window (dsic_window_render_u8 / _u16): resample_pixel, then output band b = channel r.band[b] of it
+// stretched to a byte with r.lo[b], r.hi[b], then alpha.  A thread packs its nb + alpha bytes into one word: a wave
+// stores one run of 64 (nb + alpha) bytes, a dword per lane where that is 4 bytes at an aligned address.
+struct Render {
+  int nb, alpha, background, need;
+  int band[3];
+  uint32_t lo[3], hi[3];
+};
+
+__device__ __forceinline__ uint32_t stretch_byte(uint32_t m, uint32_t lo, uint32_t hi) {
+  const uint32_t R = hi - lo, d = min(max(m, lo), hi) - lo;
+  return R ? (510u * d + R) / (2u * R) : 0u;  // 255 d / R rounded half up; 510 * 65535 + 65535 < 2^32
+}
+
+template <typename T, bool V>
+__global__ __launch_bounds__(VIEW_BX * VIEW_BY) void render_kernel(const T* __restrict__ src,
+                                                                   const uint8_t* __restrict__ sval,
+                                                                   uint8_t* __restrict__ dst, View v, int C, int mode,
+                                                                   int nodata, Render r, int bx, int64_t nblocks) {
+  const int n = r.nb + r.alpha;
+  const bool dwords = n == 4 && ((uintptr_t)dst & 3) == 0;
+  for (int64_t blk = blockIdx.x; blk < nblocks; blk += gridDim.x) {
+    const int64_t by = blk / bx;
+    const int j = (int)(blk - by * bx) * VIEW_BX + threadIdx.x;
+    const int64_t i64 = by * VIEW_BY + threadIdx.y;
+    if (i64 >= v.oh || j >= v.ow) continue;
+    const int i = (int)i64;
+    uint32_t m[4] = {0u, 0u, 0u, 0u};
+    const bool ok = resample_pixel<T, V>(src, sval, v, C, mode, nodata, i, j, r.need, m);
+    uint32_t word = 0;
 #pragma unroll
-        for (int c = 0; c < 4; ++c) S[c] += wgt * val[c];
-      }
+    for (int b = 0; b < 3; ++b) {
+      if (b >= r.nb) continue;
+      const int k = r.band[b];
+      const uint32_t s = k == 0 ? m[0] : k == 1 ? m[1] : k == 2 ? m[2] : m[3];
+      word |= (ok ? stretch_byte(s, r.lo[b], r.hi[b]) : (uint32_t)r.background) << (8 * b);
     }
-    // (2 S + T) / (2 T): in 32 bits where both fit, which reduced weights nearly always allow
-    const bool narrow = ((2 * (S[0] | S[1] | S[2] | S[3]) + Tw) >> 32) == 0 && (Tw >> 31) == 0;
-#pragma unroll
-    for (int c = 0; c < 4; ++c) {
-      if (c >= C) continue;
-      const uint64_t num = 2 * S[c] + Tw, den = 2 * Tw;
-      o[c] = !Tw ? (T)nodata : narrow ? (T)((uint32_t)num / (uint32_t)den) : (T)(num / den);
+    if (r.alpha) word |= (ok ? 255u : 0u) << (8 * r.nb);
+    uint8_t* o = dst + ((int64_t)i * v.ow + j) * n;
+    if (dwords) {
+      *(uint32_t*)o = word;
+    } else {
+      for (int b = 0; b < n; ++b) o[b] = (uint8_t)(word >> (8 * b));
     }
-    if (V && oval) oval[(int64_t)i * v.ow + j] = (uint8_t)(Tw != 0);
   }
 }
 
@@ -161,14 +224,9 @@ __global__ __launch_bounds__(VIEW_BX * VIEW_BY) void resample_f32_kernel(const f
   }
 }
 
-static bool view_apart(const void* a, int64_t a_bytes, const void* b, int64_t b_bytes) {
-  const uintptr_t pa = (uintptr_t)a, pb = (uintptr_t)b;
-  return pa + (uintptr_t)a_bytes <= pb || pb + (uintptr_t)b_bytes <= pa;
-}
-
-// the checks every kind shares; on success the launch shape
+// the checks every kind shares; on success the launch shape.  dst holds dch elements of delem bytes per output pixel
 static int view_check(const char* what, const void* src, const void* dst, const View& v, int C, int cmin, int cmax,
-                      int elem, int mode, int* bx, int64_t* nblocks) {
+                      int elem, int delem, int dch, int mode, int* bx, int64_t* nblocks) {
   DSIC_REQUIRE(src && dst, "%s: null pointer", what);
   DSIC_REQUIRE(C >= cmin && C <= cmax, "%s: C=%d must be in %d..%d", what, C, cmin, cmax);
   DSIC_REQUIRE(mode == 0 || mode == 1, "%s: mode=%d (0 average, 1 nearest)", what, mode);
@@ -189,9 +247,9 @@ static int view_check(const char* what, const void* src, const void* dst, const 
                "source window %dx%d at (%d, %d)",
                what, v.h, v.w, v.y0, v.x0, (long long)ya, (long long)yb, (long long)xa, (long long)xb, v.shift, v.sh,
                v.sw, v.sy0, v.sx0);
-  DSIC_REQUIRE((((uintptr_t)src | (uintptr_t)dst) & (uintptr_t)(elem - 1)) == 0, "%s: src and dst must be %d-byte aligned",
-               what, elem);
-  DSIC_REQUIRE(view_apart(src, (int64_t)elem * C * v.sh * v.sw, dst, (int64_t)elem * C * v.oh * v.ow),
+  DSIC_REQUIRE(((uintptr_t)src & (uintptr_t)(elem - 1)) == 0 && ((uintptr_t)dst & (uintptr_t)(delem - 1)) == 0,
+               "%s: src must be %d-byte aligned and dst %d-byte aligned", what, elem, delem);
+  DSIC_REQUIRE(buffers_apart(src, (int64_t)elem * C * v.sh * v.sw, dst, (int64_t)delem * dch * v.oh * v.ow),
                "%s: src and dst overlap", what);
   *bx = (v.ow + VIEW_BX - 1) / VIEW_BX;
   *nblocks = (int64_t)*bx * ((v.oh + VIEW_BY - 1) / VIEW_BY);
@@ -223,7 +281,7 @@ static int resample_int(const char* what, const T* src, const View& v, int C, in
                         void* stream) {
   int bx;
   int64_t nblocks;
-  const int status = view_check(what, src, dst, v, C, cmin, 4, (int)sizeof(T), mode, &bx, &nblocks);
+  const int status = view_check(what, src, dst, v, C, cmin, 4, (int)sizeof(T), (int)sizeof(T), C, mode, &bx, &nblocks);
   if (status != DSIC_OK) return status;
   DSIC_REQUIRE(nodata >= -1 && nodata <= (int)(T)~(T)0, "%s: nodata=%d (-1 for none, or a pixel value)", what, nodata);
   hipLaunchKernelGGL((resample_int_kernel<T, false>), view_grid(nblocks), dim3(VIEW_BX, VIEW_BY), 0, (hipStream_t)stream,
@@ -236,18 +294,53 @@ static int resample_valid(const char* what, const T* src, const uint8_t* sval, c
                           uint8_t* oval, int mode, int fill, void* stream) {
   int bx;
   int64_t nblocks;
-  const int status = view_check(what, src, dst, v, C, cmin, 4, (int)sizeof(T), mode, &bx, &nblocks);
+  const int status = view_check(what, src, dst, v, C, cmin, 4, (int)sizeof(T), (int)sizeof(T), C, mode, &bx, &nblocks);
   if (status != DSIC_OK) return status;
   DSIC_REQUIRE(sval, "%s: null pointer", what);
   DSIC_REQUIRE(fill >= 0 && fill <= (int)(T)~(T)0, "%s: fill=%d must be a pixel value", what, fill);
   const int64_t sb = (int64_t)sizeof(T) * C * v.sh * v.sw, db = (int64_t)sizeof(T) * C * v.oh * v.ow;
   const int64_t svb = (int64_t)v.sh * v.sw, ovb = (int64_t)v.oh * v.ow;
-  DSIC_REQUIRE(view_apart(sval, svb, dst, db) &&
-                   (!oval || (view_apart(oval, ovb, src, sb) && view_apart(oval, ovb, sval, svb) &&
-                              view_apart(oval, ovb, dst, db))),
+  DSIC_REQUIRE(buffers_apart(sval, svb, dst, db) &&
+                   (!oval || (buffers_apart(oval, ovb, src, sb) && buffers_apart(oval, ovb, sval, svb) &&
+                              buffers_apart(oval, ovb, dst, db))),
                "%s: src and dst overlap", what);
   hipLaunchKernelGGL((resample_int_kernel<T, true>), view_grid(nblocks), dim3(VIEW_BX, VIEW_BY), 0, (hipStream_t)stream,
                      src, dst, v, C, mode, fill, bx, nblocks, sval, oval);
+  return check_launch(what);
+}
+
+template <typename T>
+static int render(const char* what, const T* src, const uint8_t* sval, const View& v, int C, const int* bands, int nb,
+                  const uint32_t* lohi, uint8_t* dst, int mode, int nodata, int alpha, int background, void* stream) {
+  DSIC_REQUIRE(nb == 1 || nb == 3, "%s: nb=%d output bands (1 or 3)", what, nb);
+  DSIC_REQUIRE(alpha == 0 || alpha == 1, "%s: alpha=%d (0 or 1)", what, alpha);
+  DSIC_REQUIRE(background >= 0 && background <= 255, "%s: background=%d must be in 0..255", what, background);
+  int bx;
+  int64_t nblocks;
+  const int n = nb + alpha;
+  const int status = view_check(what, src, dst, v, C, 1, 4, (int)sizeof(T), 1, n, mode, &bx, &nblocks);
+  if (status != DSIC_OK) return status;
+  DSIC_REQUIRE(bands && lohi, "%s: null pointer", what);
+  const int top = (int)(T)~(T)0;
+  DSIC_REQUIRE(nodata >= -1 && nodata <= top, "%s: nodata=%d (-1 for none, or a pixel value)", what, nodata);
+  for (int c = 0; c < C; ++c)
+    DSIC_REQUIRE(lohi[2 * c] <= lohi[2 * c + 1] && lohi[2 * c + 1] <= (uint32_t)top,
+                 "%s: stretch pair (%u, %u) of band %d must have 0 <= lo <= hi <= %d", what, lohi[2 * c], lohi[2 * c + 1], c,
+                 top);
+  Render r = {nb, alpha, background, 0, {0, 0, 0}, {0, 0, 0}, {0, 0, 0}};
+  for (int b = 0; b < nb; ++b) {
+    DSIC_REQUIRE(bands[b] >= 0 && bands[b] < C, "%s: band %d is outside 0..%d", what, bands[b], C - 1);
+    r.band[b] = bands[b], r.lo[b] = lohi[2 * bands[b]], r.hi[b] = lohi[2 * bands[b] + 1];
+    r.need |= 1 << bands[b];
+  }
+  if (sval)
+    DSIC_REQUIRE(buffers_apart(sval, (int64_t)v.sh * v.sw, dst, (int64_t)n * v.oh * v.ow), "%s: src and dst overlap", what);
+  if (sval)
+    hipLaunchKernelGGL((render_kernel<T, true>), view_grid(nblocks), dim3(VIEW_BX, VIEW_BY), 0, (hipStream_t)stream, src,
+                       sval, dst, v, C, mode, 0, r, bx, nblocks);
+  else
+    hipLaunchKernelGGL((render_kernel<T, false>), view_grid(nblocks), dim3(VIEW_BX, VIEW_BY), 0, (hipStream_t)stream, src,
+                       sval, dst, v, C, mode, nodata, r, bx, nblocks);
   return check_launch(what);
 }
 
@@ -275,7 +368,7 @@ extern "C" int dsic_window_resample_f32(const float* src_chw, int sh, int sw, in
   const View v = view_of(sh, sw, sy0, sx0, shift, y0, x0, h, w, oh, ow);
   int bx;
   int64_t nblocks;
-  const int status = view_check("window_resample_f32", src_chw, dst_chw, v, C, 1, 8, 4, mode, &bx, &nblocks);
+  const int status = view_check("window_resample_f32", src_chw, dst_chw, v, C, 1, 8, 4, 4, C, mode, &bx, &nblocks);
   if (status != DSIC_OK) return status;
   hipLaunchKernelGGL(resample_f32_kernel, view_grid(nblocks), dim3(VIEW_BX, VIEW_BY), 0, (hipStream_t)stream, src_chw,
                      dst_chw, v, C, mode, nodata, has_nodata, bx, nblocks);
@@ -296,4 +389,22 @@ extern "C" int dsic_window_resample_valid_u16(const uint16_t* src_hwc, const uin
   const View v = view_of(sh, sw, sy0, sx0, shift, y0, x0, h, w, oh, ow);
   return resample_valid<uint16_t>("window_resample_valid_u16", src_hwc, src_valid, v, C, 1, dst_hwc, dst_valid, mode, fill,
                                   stream);
+}
+
+extern "C" int dsic_window_render_u8(const uint8_t* src_hwc, const uint8_t* src_valid, int sh, int sw, int sy0, int sx0,
+                                     int C, int shift, int y0, int x0, int h, int w, const int* bands, int nb,
+                                     const uint32_t* lohi, uint8_t* dst, int oh, int ow, int mode, int nodata, int alpha,
+                                     int background, void* stream) {
+  const View v = view_of(sh, sw, sy0, sx0, shift, y0, x0, h, w, oh, ow);
+  return render<uint8_t>("window_render_u8", src_hwc, src_valid, v, C, bands, nb, lohi, dst, mode, nodata, alpha,
+                         background, stream);
+}
+
+extern "C" int dsic_window_render_u16(const uint16_t* src_hwc, const uint8_t* src_valid, int sh, int sw, int sy0, int sx0,
+                                      int C, int shift, int y0, int x0, int h, int w, const int* bands, int nb,
+                                      const uint32_t* lohi, uint8_t* dst, int oh, int ow, int mode, int nodata, int alpha,
+                                      int background, void* stream) {
+  const View v = view_of(sh, sw, sy0, sx0, shift, y0, x0, h, w, oh, ow);
+  return render<uint16_t>("window_render_u16", src_hwc, src_valid, v, C, bands, nb, lohi, dst, mode, nodata, alpha,
+                          background, stream);
 }

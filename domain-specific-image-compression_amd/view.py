@@ -4,6 +4,9 @@ decompress_region starts from nothing on every call: it reads and checks the str
 tile the window touches.  A reader opens each level of a DSICI / DSICP stream once (source view, index, the check
 against the model), keeps decoded tiles on the device, decodes the tiles that several requests miss in shared dense
 batches (read_many), and resamples a window of the best-fitting overview to the size asked for (csrc/view.hip).
+render turns such a window into display pixels in the same launch: chosen bands, stretched to 8 bits between two
+values per band, with the validity as an alpha channel; histogram and stretch derive those values from the data
+(csrc/histogram.hip, stretch_from_histogram).
 
 The cache holds what the stitch and blend calls consume: per (level, tile) the tile's g_s output, float32
 [C, th, tw], not clamped, and for a near-lossless level its q plane.  A window is served by collecting its tiles, in
@@ -41,6 +44,39 @@ def view_level(n_levels, h, w, oh, ow) -> int:
         if (oh << l) <= h and (ow << l) <= w:
             return l
     return 0
+
+
+def _check_percent(percent):
+    """percent as stretch_from_histogram takes it -> (p0, p1) as floats"""
+    try:
+        p0, p1 = (float(v) for v in percent)
+    except (TypeError, ValueError):
+        raise ValueError(f"stretch_from_histogram: percent={percent!r} is not a pair of numbers (p0, p1)") from None
+    if not 0 <= p0 <= p1 <= 100:
+        raise ValueError(f"stretch_from_histogram: percent={percent!r} must have 0 <= p0 <= p1 <= 100")
+    return p0, p1
+
+
+def stretch_from_histogram(hist, percent=(2, 98)) -> list:
+    """A percentile stretch from band histograms (pure Python / NumPy): hist [C][bins] of counts, percent = (p0, p1)
+    with 0 <= p0 <= p1 <= 100 -> [(lo, hi)] per band.  With q = round(100 p) (basis points), n = sum(hist[c]) and
+    cum(v) = sum(hist[c][:v + 1]): lo is the least v with cum(v) >= 1 and 10000 cum(v) >= q0 n, hi the same with q1;
+    n = 0 gives (0, 0).  So p = 0 is the minimum, p = 100 the maximum, and lo <= hi."""
+    p0, p1 = _check_percent(percent)
+    hist = np.asarray(hist)
+    if hist.ndim != 2 or hist.dtype.kind not in "iu" or (hist < 0).any():
+        raise ValueError("stretch_from_histogram: hist must be an integer array [C][bins] of counts")
+    out = []
+    for row in hist:
+        cum = np.cumsum(row.astype(np.int64))
+        n = int(cum[-1]) if cum.size else 0
+        if n == 0:
+            out.append((0, 0))
+            continue
+        # cum(v) >= 1 and 10000 cum(v) >= q n  <=>  cum(v) >= max(1, ceil(q n / 10000)), in Python's integers
+        out.append(tuple(int(np.searchsorted(cum, max(1, -(-int(round(100 * p)) * n // 10000)), side="left"))
+                         for p in (p0, p1)))
+    return out
 
 
 def _has_q(ix):
@@ -120,6 +156,7 @@ class ImageReader:
         self._open, self._slabs = {}, {}
         self._lru, self._used = collections.OrderedDict(), 0       # (level, tile) -> None, oldest first
         self._stats = dict(_new_stats(), tiles=0)
+        self._hists = {}                                           # level -> its histogram, counted once
         self._closed = False
 
     def __enter__(self):
@@ -132,6 +169,7 @@ class ImageReader:
         self._slabs.clear()
         self._lru.clear()
         self._open.clear()
+        self._hists.clear()
         self._used, self._closed = 0, True
 
     # ---- the stream ---------------------------------------------------------------------------------------------
@@ -408,10 +446,29 @@ class ImageReader:
         _c._check_out(out, None, "ImageReader.read_many")
         before, st = self._source.bytes_read, _new_stats()
         plans = [self._plan(r["window"], r.get("size"), r.get("level"), resampling) for r in requests]
+        for level, _, _ in plans:
+            _c._check_out(out, self._level(level)[2], "ImageReader.read_many")
+        shared = self._ensure_union(plans, st)
+        imgs = []
+        for level, lw, view in plans:
+            self._check_view(level, view, out, False)
+            masked = view is not None and self._masked(level)
+            valid = torch.ones((int(lw[2]), int(lw[3])), dtype=torch.uint8, device=self._dev) if masked else None
+            img = self._window(level, lw, out, st, ensured=shared, valid_out=valid)
+            if masked and img.dtype != torch.float32:
+                img = self._resample(img, level, lw, view, valid)[0]
+            elif view is not None:
+                img = self._resample(img, level, lw, view)
+            imgs.append(img)
+        self._finish(st, before, stats)
+        return imgs
+
+    def _ensure_union(self, plans, st):
+        """The tiles that the plans' windows need and the cache lacks, decoded once over their union: per level, in
+        ascending tile order, in dense batches.  False, and nothing done, if the union does not fit the cache."""
         union, used = {}, 0
         for level, lw, _ in plans:
-            _, _, ix = self._level(level)
-            _c._check_out(out, ix, "ImageReader.read_many")
+            ix = self._level(level)[2]
             union.setdefault(level, set()).update(_c.window_tiles(ix, *lw))
         for level in union:
             ix = self._open[level][1]
@@ -424,16 +481,160 @@ class ImageReader:
                 _, view, ix = self._level(level)
                 st["tiles"] += [(level, t) for t in union[level]]
                 self._ensure(level, view, ix, _c._coded_tiles(ix, union[level]), pinned, st)
-        imgs = []
-        for level, lw, view in plans:
-            self._check_view(level, view, out, False)
-            masked = view is not None and self._masked(level)
-            valid = torch.ones((int(lw[2]), int(lw[3])), dtype=torch.uint8, device=self._dev) if masked else None
-            img = self._window(level, lw, out, st, ensured=shared, valid_out=valid)
-            if masked and img.dtype != torch.float32:
-                img = self._resample(img, level, lw, view, valid)[0]
-            elif view is not None:
-                img = self._resample(img, level, lw, view)
-            imgs.append(img)
+        return shared
+
+    # ---- display ------------------------------------------------------------------------------------------------
+    def _display_out(self, ix):
+        """(out, top) of the integer image a level is counted and rendered from: its native uint8 or uint16, a
+        float32-kind stream in its out="u8" form."""
+        out = "u8" if ix["kind"] == _c.KIND_F32_CHW else None
+        kind = _c._check_out(out, ix, "ImageReader.render")
+        return out, 65535 if kind == _c.KIND_U16_HWC else 255
+
+    @torch.no_grad()
+    def histogram(self, level=None):
+        """hist[c][v] = the number of pixels of `level` (default: the coarsest level the stream holds) that count and
+        whose band c equals v: NumPy int64 [C, 256], or [C, 65536] for a uint16 stream.  The valid pixels of a stream
+        with a validity mask count, of a nodata stream (version 5) those that are not nodata, else all; a
+        float32-kind stream is counted in its out="u8" form.  The level is read in strips of whole tile rows through
+        the reader's own window path, so the cache and its limits apply (dsic_band_histogram_u8 / _u16 per strip,
+        summed on the device in int64).  The result is kept per level: a second call decodes nothing.  What the
+        first call decodes is counted in the reader's stats."""
+        before, st = self._source.bytes_read, _new_stats()
+        hist = self._histogram(level, st)
+        self._finish(st, before, None)
+        return hist
+
+    def _histogram(self, level, st):
+        """histogram(level); the tiles it reads are counted in st, the running call's counters."""
+        level, _, ix = self._level(len(self.levels) - 1 if level is None else level)
+        if level not in self._hists:
+            out, top = self._display_out(ix)
+            H, W, C, g = ix["H"], ix["W"], ix["C"], ix["grid"]
+            what = "band_histogram_u16" if top == 65535 else "band_histogram_u8"
+            fn = getattr(_lib.load(), "dsic_" + what)
+            total = torch.zeros((C, top + 1), dtype=torch.int64, device=self._dev)
+            part = torch.empty((C, top + 1), dtype=torch.int32, device=self._dev)      # the kernel's uint32 counters
+            rows = g["th"] * max(1, self.batch // g["nx"])         # tile rows that fill about one decode batch
+            for y in range(0, H, rows):
+                h = min(rows, H - y)
+                valid = torch.ones((h, W), dtype=torch.uint8, device=self._dev) if "fill" in ix else None
+                img = self._window(level, (y, 0, h, W), out, st, valid_out=valid)
+                part.zero_()
+                _lib.check(fn(_p(img), None if valid is None else _p(valid), h, W, C, ix.get("nodata", -1), _p(part),
+                              _stream()), what)
+                total += part.to(torch.int64) & 0xFFFFFFFF
+            self._hists[level] = total.cpu().numpy()
+        return self._hists[level].copy()
+
+    def stretch(self, percent=(2, 98), level=None):
+        """stretch_from_histogram(self.histogram(level), percent): one (lo, hi) per band."""
+        _check_percent(percent)                                    # before anything is decoded
+        return stretch_from_histogram(self.histogram(level), percent)
+
+    def _display(self, level, bands, stretch, alpha, background):
+        """render's arguments checked against a level -> (bands, None or the stretch pairs, alpha, background)."""
+        ix = self._open[level][1]
+        C, top = ix["C"], self._display_out(ix)[1]
+        try:
+            bands = ((0, 1, 2) if C >= 3 else (0,)) if bands is None else tuple(operator.index(b) for b in bands)
+        except TypeError:
+            raise ValueError(f"ImageReader.render: bands={bands!r} is not a sequence of band numbers") from None
+        if len(bands) not in (1, 3) or not all(0 <= b < C for b in bands):
+            raise ValueError(f"ImageReader.render: bands={bands!r} must be 1 or 3 of the bands 0 .. {C - 1}")
+        if stretch is not None:
+            try:
+                stretch = [tuple(operator.index(v) for v in pair) for pair in stretch]
+            except TypeError:
+                raise ValueError(f"ImageReader.render: stretch={stretch!r} is not a sequence of integer pairs "
+                                 "(lo, hi)") from None
+            if len(stretch) != C or any(len(pair) != 2 for pair in stretch):
+                raise ValueError(f"ImageReader.render: stretch={stretch!r} must hold one pair (lo, hi) for each of the "
+                                 f"{C} bands of the stream")
+            for lo, hi in stretch:
+                if not 0 <= lo <= hi <= top:
+                    raise ValueError(f"ImageReader.render: stretch pair ({lo}, {hi}) must have 0 <= lo <= hi <= {top}")
+        try:
+            background = operator.index(background)
+        except TypeError:
+            raise ValueError(f"ImageReader.render: background={background!r} is not an integer") from None
+        if not 0 <= background <= 255:
+            raise ValueError(f"ImageReader.render: background={background} must be in 0 .. 255")
+        if alpha and "nodata" in ix:
+            raise ValueError("ImageReader.render: alpha=True needs a validity mask (compress_image with valid=, stream "
+                             f"version {_c.VERSION_VALID}); a nodata stream marks its pixels by value")
+        return bands, stretch, int(bool(alpha)), background
+
+    def _default_stretch(self, level, stretch, st):
+        """stretch = None: (0, 255) per band for a uint8 or float32-kind stream, self.stretch() for a uint16 one, whose
+        histogram, if this call is the first to need it, is counted in st with the call's own tiles."""
+        if stretch is not None:
+            return stretch
+        ix = self._open[level][1]
+        if self._display_out(ix)[1] != 65535:
+            return [(0, 255)] * ix["C"]
+        return stretch_from_histogram(self._histogram(None, st))
+
+    def _render(self, level, lw, view, display, resampling, st, ensured):
+        """One planned request through the render kernel (dsic_window_render_u8 / _u16)."""
+        bands, stretch, alpha, background = display
+        ix = self._open[level][1]
+        if view is None:                                           # the window itself: every pixel under itself
+            view = (tuple(int(v) for v in lw), (int(lw[2]), int(lw[3])), RESAMPLING[resampling])
+            shift = 0
+        else:
+            shift = level
+        (y0, x0, h, w), (oh, ow), mode = view
+        valid = torch.ones((int(lw[2]), int(lw[3])), dtype=torch.uint8, device=self._dev) if self._masked(level) else None
+        img = self._window(level, lw, self._display_out(ix)[0], st, ensured=ensured, valid_out=valid)
+        nodata = ix.get("nodata") if mode == 0 else None
+        dst = torch.empty((oh, ow, len(bands) + alpha), dtype=torch.uint8, device=self._dev)
+        what = "window_render_u8" if img.dtype == torch.uint8 else "window_render_u16"
+        status = getattr(_lib.load(), "dsic_" + what)(
+            _p(img), None if valid is None else _p(valid), lw[2], lw[3], lw[0], lw[1], ix["C"], shift, y0, x0, h, w,
+            (ctypes.c_int * len(bands))(*bands), len(bands), _c._lohi(stretch), _p(dst), oh, ow, mode,
+            -1 if nodata is None else nodata, alpha, background, _stream())
+        _lib.check(status, what)
+        return dst
+
+    @torch.no_grad()
+    def render(self, y0, x0, h, w, size=None, level=None, bands=None, stretch=None, alpha=False, background=0,
+               resampling="average", stats=None):
+        """The window as display pixels: torch.uint8 [oh, ow, nb (+ 1)] on the device, in one launch over the window
+        that read would resample.  Window, size, level, resampling and stats mean what they mean for read; size =
+        None renders the window of `level` at its own resolution.
+        bands: 1 or 3 band numbers of the stream, repeats allowed; None = (0, 1, 2) for C >= 3, else (0,).
+        stretch: one (lo, hi) per band of the stream, 0 <= lo <= hi <= 255 (65535 for a uint16 stream); a sample m
+        becomes 255 (clip(m, lo, hi) - lo) / (hi - lo) rounded half up, 0 where lo == hi.  None = (0, 255) per band
+        for a uint8 or float32-kind stream (which is rendered from its out="u8" form), self.stretch() for a uint16
+        one; the first such call of a reader decodes the coarsest level for its histogram, and stats counts those
+        tiles with the window's.
+        For every valid pixel the result is that stretch of read(..., size, resampling)[..., bands], bit for bit.  A
+        stream with a validity mask gives `background` in every band where the output pixel is invalid; alpha = True
+        adds a last channel, 255 where valid and 0 where not (all 255 without a mask).
+        ValueError before any launch for bands, stretch, background or resampling out of these bounds, and for
+        alpha = True on a nodata stream (version 5), whose mask is by value."""
+        before, st = self._source.bytes_read, _new_stats()
+        level, lw, view = self._plan((y0, x0, h, w), size, level, resampling)
+        display = self._display(level, bands, stretch, alpha, background)
+        display = (display[0], self._default_stretch(level, display[1], st)) + display[2:]
+        img = self._render(level, lw, view, display, resampling, st, False)
+        if size is not None:
+            st.update(level=level, level_window=tuple(lw))
+        self._finish(st, before, stats)
+        return img
+
+    @torch.no_grad()
+    def render_many(self, requests, alpha=False, background=0, resampling="average", stats=None):
+        """requests: dicts with `window` and optionally `size`, `level`, `bands` and `stretch`, as render takes them
+        -> the list [render(*window, size, level, bands, stretch, alpha, background, resampling) for each], bit for
+        bit.  Missing tiles are decoded once over the union of the requests, as read_many does it."""
+        before, st = self._source.bytes_read, _new_stats()
+        plans = [self._plan(r["window"], r.get("size"), r.get("level"), resampling) for r in requests]
+        displays = [self._display(p[0], r.get("bands"), r.get("stretch"), alpha, background)
+                    for p, r in zip(plans, requests)]
+        displays = [(d[0], self._default_stretch(p[0], d[1], st)) + d[2:] for p, d in zip(plans, displays)]
+        shared = self._ensure_union(plans, st)
+        imgs = [self._render(level, lw, view, d, resampling, st, shared) for (level, lw, view), d in zip(plans, displays)]
         self._finish(st, before, stats)
         return imgs

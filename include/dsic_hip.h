@@ -823,6 +823,43 @@ int dsic_window_resample_valid_u16(const uint16_t* src_hwc, const uint8_t* src_v
                                    int h, int w, uint16_t* dst_hwc, uint8_t* dst_valid, int oh,
                                    int ow, int mode, int fill, void* stream);
 
+/* ---- rendered views (codec.ImageReader.render, .histogram) ----
+ * dsic_window_render_u8 / _u16: a display image of a resampled window in one launch.  Per output
+ *   pixel first exactly what dsic_window_resample_u8 / _u16 compute for it (src_valid = NULL;
+ *   nodata as there, -1 = none) or, with a validity window src_valid [sh][sw], what
+ *   dsic_window_resample_valid_u8 / _u16 compute (nodata is ignored): same geometry, reduced
+ *   weights, (2 S + T) / (2 T) and nearest rule; the resampled sample m stays in registers.
+ *   Output band b then takes channel bands[b] of it, stretched with the pair (lo, hi) =
+ *   lohi[2 bands[b]], lohi[2 bands[b] + 1]: R = hi - lo, d = min(max(m, lo), hi) - lo, the byte is
+ *   R == 0 ? 0 : (510 d + R) / (2 R), which is 255 d / R rounded half up.  dst is uint8
+ *   [oh][ow][nb + alpha].  With src_valid an output pixel with nothing valid under it (nearest:
+ *   whose source pixel is invalid) gets background in every band and, for alpha = 1, alpha 0;
+ *   every other pixel gets alpha 255.  Without src_valid every pixel is valid, and a nodata result
+ *   (T = 0) is stretched like any value.  bands (nb ints) and lohi (2 C words) are host arrays,
+ *   read before the call returns.
+ *   DSIC_EINVAL, nothing written: what the resample calls refuse, with C 1..4 for both kinds; nb
+ *   other than 1 or 3; a band outside 0..C-1; a pair that is not lo <= hi <= 255 (65535); alpha
+ *   outside 0..1; background outside 0..255; dst overlapping src or src_valid.
+ * dsic_band_histogram_u8 / _u16: hist [C][256] ([C][65536]) uint32 on the device; hist[c][v] += the
+ *   number of counted pixels of img [H][W][C] whose channel c equals v.  valid_hw (NULL: none),
+ *   uint8 [H][W], leaves out its zeros; nodata (-1: none) leaves out the pixels whose C channels
+ *   all equal it.  The caller zeroes hist; several calls sum into it.  Integer atomic adds: no
+ *   dependence on any order.  img at any element alignment, hist 4-byte aligned.
+ *   DSIC_EINVAL: null img or hist; C outside 1..4; H or W under 1 or H W >= 2^32; nodata beyond the
+ *   element type; hist overlapping img or valid_hw. */
+int dsic_window_render_u8(const uint8_t* src_hwc, const uint8_t* src_valid, int sh, int sw, int sy0,
+                          int sx0, int C, int shift, int y0, int x0, int h, int w,
+                          const int* bands, int nb, const uint32_t* lohi, uint8_t* dst, int oh,
+                          int ow, int mode, int nodata, int alpha, int background, void* stream);
+int dsic_window_render_u16(const uint16_t* src_hwc, const uint8_t* src_valid, int sh, int sw,
+                           int sy0, int sx0, int C, int shift, int y0, int x0, int h, int w,
+                           const int* bands, int nb, const uint32_t* lohi, uint8_t* dst, int oh,
+                           int ow, int mode, int nodata, int alpha, int background, void* stream);
+int dsic_band_histogram_u8(const uint8_t* img_hwc, const uint8_t* valid_hw, int H, int W, int C,
+                           int nodata, uint32_t* hist, void* stream);
+int dsic_band_histogram_u16(const uint16_t* img_hwc, const uint8_t* valid_hw, int H, int W, int C,
+                            int nodata, uint32_t* hist, void* stream);
+
 /* HIP stream limited to the CUs whose bit is set in mask_host[words] (bit i of
  * word i/32 = CU i).  Used to give the range coder its own few CUs beside the
  * conv kernels; there is no reference counterpart (the reference is

@@ -7,6 +7,9 @@ an image.
     python tools/dsic_image.py decompress --weights CKPT.pt IN.dsic OUT.png [--out u8|f32|u16] [--region Y0,X0,H,W]
                                           [--level L] [--size OH,OW] [--resampling average|nearest]
                                           [--valid-out FILE.npy]
+    python tools/dsic_image.py render     --weights CKPT.pt IN.dsic OUT [--region Y0,X0,H,W] [--size OH,OW] [--level L]
+                                          [--bands B | B,B,B] [--stretch LO,HI[,LO,HI...]] [--percent P0,P1] [--alpha]
+                                          [--background V] [--resampling average|nearest]
     python tools/dsic_image.py info       IN.dsic
 
 --segments K (2, 4, 8 or 16) codes every tile's y string as K independent strings, which a decoder reads on K waves per
@@ -35,6 +38,15 @@ or --max-error) adds the bounded-error residual layer of 16-bit imagery (a versi
 within T of the original, 0 returns the image itself.  With --overviews it bounds level 0 only.  Such a stream decodes
 to uint16 only; info prints the tolerance, the residual layer's bytes and how many tiles took which shift k (the raw
 bit planes per sample).
+render writes a window as display pixels (codec.ImageReader.render): --bands picks one band (grey) or three of the
+stream's bands (default 0,1,2, or 0 for fewer than three), --stretch LO,HI (one pair for all bands, or one per band of
+the stream) maps LO to 0 and HI to 255, clipping outside; without it a uint16 stream is stretched between the 2 % and
+98 % percentiles of its coarsest level's valid pixels and a uint8 stream not at all; --percent P0,P1 asks for that
+percentile stretch with other bounds, on any stream.  --alpha adds the
+validity mask of a version-8 stream as an alpha channel, --background V (0 .. 255) is what invalid pixels show.  The
+region (default: the whole image) is in level-0 pixels with --size, else in --level's own.  OUT is .npy, a binary .ppm
+(three bands) or .pgm (one band), both without alpha, or .png where PIL is importable.  The level read and the stretch
+used are printed.
 
 The state dict is loaded plain or from under "model" (code/modelv2/eval_selfcontained_entropy.py:130-134); the model's
 N, M, input channels and spatial_params are read from its shapes.  Images are PNG through PIL when PIL is importable
@@ -126,15 +138,92 @@ def write_image(path, img):
     return path
 
 
-def scale_pairs(text, channels):
+def scale_pairs(text, channels, name="--scale"):
     """--scale's text -> [(lo, hi)] * channels: "LO,HI" for all bands, or one pair per band; ValueError otherwise."""
     values = [int(v) for v in text.split(",")]
     if len(values) == 2:
         return [tuple(values)] * channels
     if len(values) != 2 * channels:
-        raise ValueError(f"--scale {text}: one pair LO,HI for all bands, or {channels} pairs for the model's "
+        raise ValueError(f"{name} {text}: one pair LO,HI for all bands, or {channels} pairs for the model's "
                          f"{channels} bands")
     return list(zip(values[0::2], values[1::2]))
+
+
+def write_display(path, a):
+    """A rendered window, uint8 [h][w][n]: .npy, binary .ppm (n = 3) / .pgm (n = 1), or .png through PIL."""
+    import numpy as np
+    if path.endswith(".npy"):
+        np.save(path, a)
+    elif path.endswith((".ppm", ".pgm")):
+        with open(path, "wb") as f:
+            f.write(b"P%d\n%d %d\n255\n" % (6 if a.shape[2] == 3 else 5, a.shape[1], a.shape[0]))
+            f.write(np.ascontiguousarray(a).tobytes())
+    else:
+        from PIL import Image
+        Image.fromarray(a[:, :, 0] if a.shape[2] == 1 else a, {1: "L", 2: "LA", 3: "RGB", 4: "RGBA"}[a.shape[2]]).save(path)
+    return path
+
+
+def render_main(a, ap, region, size, level_given):
+    """The render mode: every argument error before the model is loaded."""
+    from dsic_amd import codec
+
+    def numbers(text, cast, name, counts, what):
+        try:
+            values = [cast(v) for v in text.split(",")]
+        except ValueError:
+            values = []
+        if len(values) not in counts:
+            ap.error(f"{name} {text}: {what}")
+        return values
+
+    bands = None if a.bands is None else tuple(numbers(a.bands, int, "--bands", (1, 3), "one band B or three B,B,B"))
+    if a.stretch is not None and a.percent is not None:
+        ap.error("--stretch and --percent exclude each other")
+    percent = (2.0, 98.0) if a.percent is None else tuple(numbers(a.percent, float, "--percent", (2,),
+                                                                  "two numbers P0,P1 with 0 <= P0 <= P1 <= 100"))
+    if not 0 <= percent[0] <= percent[1] <= 100:
+        ap.error(f"--percent {a.percent}: two numbers P0,P1 with 0 <= P0 <= P1 <= 100")
+    if not 0 <= a.background <= 255:
+        ap.error(f"--background {a.background} must be in 0 .. 255")
+    ext = os.path.splitext(a.dst)[1].lower()
+    if ext not in (".npy", ".ppm", ".pgm", ".png"):
+        ap.error(f"{a.dst}: render writes .npy, .ppm, .pgm or .png")
+    if ext == ".png" and not _has_pil():
+        ap.error(f"{a.dst}: PIL is not importable here; write .npy, .ppm or .pgm")
+    if a.alpha and ext in (".ppm", ".pgm"):
+        ap.error(f"{a.dst}: a .ppm or .pgm holds no alpha channel; write .npy or .png")
+    with open(a.src, "rb") as f:                                           # the heads only: no model, no GPU
+        ix = codec.stream_index(f, level=a.level if level_given and size is None else 0)
+    C = ix["C"]
+    if bands is None:
+        bands = (0, 1, 2) if C >= 3 else (0,)
+    if not all(0 <= b < C for b in bands):
+        ap.error(f"--bands {a.bands}: the stream holds bands 0 .. {C - 1}")
+    if ext in (".ppm", ".pgm") and (ext == ".ppm") != (len(bands) == 3):
+        ap.error(f"{a.dst}: {len(bands)} band(s) go into a {'.ppm' if len(bands) == 3 else '.pgm'}")
+    stretch = None
+    if a.stretch is not None:
+        try:
+            stretch = scale_pairs(a.stretch, C, "--stretch")
+        except ValueError as e:
+            ap.error(str(e) if "--stretch" in str(e) else f"--stretch {a.stretch}: integers LO,HI[,LO,HI...]")
+    if region is None:
+        region = [0, 0, ix["H"], ix["W"]]
+    model = load_model(a.weights, a.min_nu, a.max_nu)
+    stats = {}
+    with open(a.src, "rb") as f, codec.ImageReader(model, f, batch=a.batch) as reader:
+        if stretch is None:                                                # --percent asks for the percentiles on any stream
+            wanted = a.percent is not None or reader.kind == codec.KIND_U16_HWC
+            stretch = reader.stretch(percent) if wanted else [(0, 255)] * C
+        img = reader.render(*region, size=None if size is None else tuple(size), level=a.level if level_given else None,
+                            bands=bands, stretch=stretch, alpha=a.alpha, background=a.background,
+                            resampling=a.resampling, stats=stats)
+    path = write_display(a.dst, img.cpu().numpy())
+    print(f"[dsic_image] window {region[2]}x{region[3]} at ({region[0]}, {region[1]}) as {img.shape[0]}x{img.shape[1]} "
+          f"({a.resampling}) from level {stats.get('level', a.level)}, bands {','.join(str(b) for b in bands)}"
+          + (" + alpha" if a.alpha else "") + ", stretch " + ", ".join(f"({lo}, {hi})" for lo, hi in stretch)
+          + f": {len(stats['tiles'])} tile(s) -> {path}")
 
 
 def print_info(ix):
@@ -182,7 +271,7 @@ def print_info(ix):
 
 def main(argv=None):
     ap = argparse.ArgumentParser(description=__doc__.splitlines()[0])
-    ap.add_argument("mode", choices=("compress", "decompress", "info"))
+    ap.add_argument("mode", choices=("compress", "decompress", "render", "info"))
     ap.add_argument("src")
     ap.add_argument("dst", nargs="?")
     ap.add_argument("--weights")
@@ -219,6 +308,14 @@ def main(argv=None):
                     help="decompress --region: the window, in level-0 pixels, resampled to OH x OW")
     ap.add_argument("--resampling", choices=("average", "nearest"), default="average",
                     help="decompress --region --size: how the window is resampled")
+    ap.add_argument("--bands", default=None, metavar="B[,B,B]", help="render: one band (grey) or three of the stream's")
+    ap.add_argument("--stretch", default=None, metavar="LO,HI[,LO,HI...]",
+                    help="render: the values shown as 0 and 255, one pair for all bands or one per band of the stream")
+    ap.add_argument("--percent", default=None, metavar="P0,P1",
+                    help="render without --stretch: stretch between these percentiles of the coarsest level (uint16 streams: "
+                         "by default 2,98; other streams: only when given)")
+    ap.add_argument("--alpha", action="store_true", help="render: add the validity mask as an alpha channel")
+    ap.add_argument("--background", type=int, default=0, metavar="V", help="render: what invalid pixels show (0 .. 255)")
     ap.add_argument("--min-nu", type=float, default=2.0)
     ap.add_argument("--max-nu", type=float, default=100.0)
     a = ap.parse_args(argv)
@@ -246,16 +343,16 @@ def main(argv=None):
             region = [int(v) for v in a.region.split(",")]
         except ValueError:
             region = []
-        if a.mode != "decompress" or len(region) != 4:
-            ap.error("--region Y0,X0,H,W (four integers) goes with decompress")
+        if a.mode not in ("decompress", "render") or len(region) != 4:
+            ap.error("--region Y0,X0,H,W (four integers) goes with decompress or render")
     size = None
     if a.size is not None:
         try:
             size = [int(v) for v in a.size.split(",")]
         except ValueError:
             size = []
-        if region is None or len(size) != 2:
-            ap.error("--size OH,OW (two integers) goes with decompress --region")
+        if (region is None and a.mode != "render") or len(size) != 2:
+            ap.error("--size OH,OW (two integers) goes with decompress --region or with render")
     if a.scale is not None and a.mode != "compress":
         ap.error("--scale goes with compress")
     if (a.valid is not None or a.fill is not None) and a.mode != "compress":
@@ -264,6 +361,13 @@ def main(argv=None):
         ap.error("--fill goes with --valid")
     if a.valid_out is not None and (a.mode != "decompress" or not a.valid_out.endswith(".npy")):
         ap.error("--valid-out FILE.npy goes with decompress")
+    given = any(s == "--level" or s.startswith("--level=") for s in (sys.argv[1:] if argv is None else argv))
+    if a.mode == "render":
+        if a.out is not None:
+            ap.error("--out goes with decompress")
+        return render_main(a, ap, region, size, given)
+    if a.bands is not None or a.stretch is not None or a.percent is not None or a.alpha or a.background:
+        ap.error("--bands, --stretch, --percent, --alpha and --background go with render")
     if a.mode == "decompress" and not a.dst.endswith(".npy"):
         with open(a.src, "rb") as f:                                       # the heads only: no model, no GPU
             if a.out == "u16" or (a.out is None and codec.stream_index(f, level=a.level)["kind"] == codec.KIND_U16_HWC):
@@ -297,7 +401,6 @@ def main(argv=None):
               + (f", fill {h['fill']}: {h['coded']} coded tile(s)" if "fill" in h else "")
               + (f", scale {h['scale']}" if "scale" in h else ""))
     elif size is not None:
-        given = any(s == "--level" or s.startswith("--level=") for s in (sys.argv[1:] if argv is None else argv))
         stats = {}
         with open(a.src, "rb") as f, codec.ImageReader(model, f, batch=a.batch) as reader:
             img = reader.read(*region, size=tuple(size), level=a.level if given else None, out=a.out,

@@ -8,13 +8,21 @@ of 768 rows x 1024 columns pans right in 32 steps of 64 pixels (33 frames).  Per
   region   decompress_region of the window, which is unchanged by the reader's arrival and so is the way without it
 then the same frames as a 384 x 512 view: the reader's read(..., size=(384, 512)) (level 1, resampled) against
 decompress_region of that level's covering window (what a caller could do before: no resampling, a grid of its own).
+render(..., size=(384, 512), alpha=True), the display path, is timed twice against that read.  render_view: a reader
+of its own over the same frames with the same decompress_region call between every two frames, so under reader_view's
+conditions.  view_cached: one reader whose cache an untimed pan has filled, read and render of every frame one after
+the other, the order swapping from frame to frame: the cost of a frame that decodes nothing, side by side.
 Every frame is wall clock around the call and a device synchronise; one untimed pass warms every shape, then --reps
 passes, and a frame's figure is the median over the passes.  Last, dsic_window_resample_u8 alone on three shapes,
-device events around 50 launches after 5 warm-up launches, with the bytes it must move (source window + output).
+device events around 50 launches after 5 warm-up launches, with the bytes it must move (source window + output), and
+dsic_window_render_u8 (three bands + alpha) on the same shapes.  The histogram behind a percentile stretch: a fresh
+reader's histogram() of the coarsest and of the full level (wall clock, the decode included), and the kernels alone on
+the full level as uint8 and as uint16, once on the scene and once on a constant image.
 Records, not bars."""
 from __future__ import annotations
 
 import argparse
+import ctypes
 import json
 import os
 import statistics
@@ -77,7 +85,8 @@ def main():
     level = codec.view_level(4, VIEW_H, VIEW_W, *SIZE)
 
     def one_pass(timed):
-        rows = {"reader": [], "region": [], "reader_view": [], "region_level": []}
+        rows = {"reader": [], "region": [], "reader_view": [], "region_level": [], "render_view": [],
+                "view_cached_read": [], "view_cached_render": []}
         with codec.ImageReader(model, stream, batch=a.batch) as r:
             for win in frames:
                 rows["reader"].append(_frame_ms(lambda: r.read(*win)))
@@ -89,6 +98,19 @@ def main():
                 rows["reader_view"].append(_frame_ms(lambda: r.read(*win, size=SIZE)))
                 rows["region_level"].append(_frame_ms(lambda: codec.decompress_region(model, stream, *lw, level=level,
                                                                                       batch=a.batch)))
+        with codec.ImageReader(model, stream, batch=a.batch) as r:
+            for win in frames:
+                lw = codec.level_window(level, *win)
+                rows["render_view"].append(_frame_ms(lambda: r.render(*win, size=SIZE, alpha=True)))
+                _frame_ms(lambda: codec.decompress_region(model, stream, *lw, level=level, batch=a.batch))
+        with codec.ImageReader(model, stream, batch=a.batch) as r:
+            for win in frames:                                             # untimed: every tile of the pan into the cache
+                r.read(*win, size=SIZE)
+            for k, win in enumerate(frames):
+                calls = [("view_cached_read", lambda: r.read(*win, size=SIZE)),
+                         ("view_cached_render", lambda: r.render(*win, size=SIZE, alpha=True))]
+                for key, fn in calls[::-1] if k % 2 else calls:
+                    rows[key].append(_frame_ms(fn))
         return rows, stats
 
     # the results are the same pixels: checked once, outside the timed passes
@@ -101,12 +123,29 @@ def main():
            "viewport": [VIEW_H, VIEW_W], "step": STEP, "frames": len(frames), "view_size": list(SIZE),
            "view_level": level, "reps": a.reps,
            "reader_counters_of_one_pan": {k: v for k, v in passes[0][1].items()}}
-    for key in ("reader", "region", "reader_view", "region_level"):
+    for key in ("reader", "region", "reader_view", "region_level", "render_view"):
         res[key] = _summary([rows[key] for rows, _ in passes])
+    for key in ("view_cached_read", "view_cached_render"):                 # no frame differs from another here
+        full = _summary([rows[key] for rows, _ in passes])
+        res[key] = {"frames_median_ms": round(statistics.median(full["frames_ms"]), 3),
+                    "frames_max_ms": round(max(full["frames_ms"]), 3), "sequence_ms": full["sequence_ms"],
+                    "frames_ms": full["frames_ms"]}
 
-    # the kernel alone
+    # the kernels alone
     L = lib.load()
-    kernel = []
+
+    def per_launch_us(launch, n=50):
+        for _ in range(5):
+            launch()
+        start, end = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        start.record()
+        for _ in range(n):
+            launch()
+        end.record()
+        torch.cuda.synchronize()
+        return start.elapsed_time(end) * 1e3 / n
+
+    kernel, render = [], []
     for name, (sh, sw, shift, region, size) in {
             "viewport 768x1024 of level 0 -> 384x512": (768, 1024, 0, (0, 0, 768, 1024), SIZE),
             "its covering window of level 1 -> 384x512": (385, 513, 1, (1000, 501, 768, 1024), SIZE),
@@ -118,20 +157,40 @@ def main():
         def launch():
             lib.check(L.dsic_window_resample_u8(_p(src), sh, sw, sy0, sx0, 3, shift, *region, _p(dst), size[0], size[1],
                                                 0, -1, _stream()), "window_resample_u8")
-        for _ in range(5):
-            launch()
-        start, end = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        n = 50
-        start.record()
-        for _ in range(n):
-            launch()
-        end.record()
-        torch.cuda.synchronize()
-        us = start.elapsed_time(end) * 1e3 / n
+        us = per_launch_us(launch)
         moved = sh * sw * 3 + size[0] * size[1] * 3
         kernel.append({"case": name, "us_per_launch": round(us, 2), "bytes_moved": moved,
                        "GB_per_s": round(moved / us / 1e3, 1)})
+        rgba = torch.empty((size[0], size[1], 4), dtype=torch.uint8, device="cuda")
+        bands, lohi = (ctypes.c_int * 3)(0, 1, 2), codec._lohi([(10, 240)] * 3)
+
+        def launch_render():
+            lib.check(L.dsic_window_render_u8(_p(src), None, sh, sw, sy0, sx0, 3, shift, *region, bands, 3, lohi, _p(rgba),
+                                              size[0], size[1], 0, -1, 1, 0, _stream()), "window_render_u8")
+        us = per_launch_us(launch_render)
+        moved = sh * sw * 3 + size[0] * size[1] * 4
+        render.append({"case": name, "us_per_launch": round(us, 2), "bytes_moved": moved,
+                       "GB_per_s": round(moved / us / 1e3, 1)})
     res["resample_kernel_u8"] = kernel
+    res["render_kernel_u8"] = render
+
+    # the histogram: through a fresh reader, and the kernels alone on the full level
+    hist = {}
+    with codec.ImageReader(model, stream, batch=a.batch) as r:            # untimed: the first call of either shape
+        r.histogram(None), r.histogram(0)
+    for name, lv in (("coarsest_level", None), ("full_level", 0)):
+        with codec.ImageReader(model, stream, batch=a.batch) as r:
+            hist[name + "_reader_ms"] = round(_frame_ms(lambda: r.histogram(lv)), 2)
+    for name, image in (("scene", img), ("constant", torch.full_like(img, 77))):
+        wide = torch.from_numpy(image.cpu().numpy().astype(np.uint16) * 257).cuda()
+        for kind, dev in (("u8", image), ("u16", wide)):
+            counts = torch.zeros((3, 256 if kind == "u8" else 65536), dtype=torch.int32, device="cuda")
+            fn = getattr(L, "dsic_band_histogram_" + kind)
+
+            def launch_hist():
+                lib.check(fn(_p(dev), None, a.size, a.size, 3, -1, _p(counts), _stream()), "band_histogram_" + kind)
+            hist[f"kernel_{kind}_{name}_us"] = round(per_launch_us(launch_hist, n=10), 1)
+    res["histogram"] = hist
     print(json.dumps(res))
     with open(a.json, "w") as f:
         json.dump(res, f, indent=1)
