@@ -3,66 +3,70 @@
 The reference's driver (code/modelv2/eval_selfcontained_entropy.py:126-159) codes one PNG in one forward pass and
 needs no size bookkeeping because its images are multiples of 16.  Here an image is cut into tiles of the size the
 codec is tuned for (256 x 256, batches of 64), each batch becomes one DSIC2 container (entropy.compress_to_container),
-and the containers travel in one stream with the image's geometry:
+and the containers travel in one DSICI stream with the image's geometry:
 
     magic "DSICI\\0" | version u16 | numerics tag u32 | H, W, C, kind, th, tw u32 | N, M, in_ch, spatial_params u32 |
-    batch, batches u32 | per batch: u64 length, DSIC2 container            (little endian, fixed-size fields)
+    batch, batches u32 | the version's fields, u32 words | [u64 length, mask block] |
+    per batch: u64 length, container [, u64 length, residual block]          (little endian, fixed-size fields)
 
-A stream compressed with segments = K > 1 (entropy.compress_latents: every tile's y string as K independent strings,
-so that a decoder reads a tile on K waves) is version 2: the version-1 head, then segments u32, and every container
-is DSIC3 with that K.  Version 1 is written whenever K = 1.
+What follows the 60 fixed bytes is stated once, in the table FORMATS below: per version the kinds it goes with, its
+fields in order with their constraints, and whether a mask block precedes the containers or a residual block follows
+each.  In one line each:
 
-kind 0 = uint8 [H,W,C] (PIL / numpy layout), 1 = float32 [C,H,W] in [0,1].  Tiling (tile_grid): the image is
-reflect-padded bottom/right to multiples of 16 inside the gather kernel; the last row / column of tiles shifts inward
-(overlap, no extra padding) and every pixel is written back by the one tile that owns it.  Tiles are coded
+    1  the plain stream                          5  nodata: a mask block, only the tiles that are not empty are coded
+    2  segments = K > 1: DSIC3 containers        6  a uint16 image (kind 2) with its per-band scale
+    3  overlap = O > 0: blended seams            8  a validity mask with its fill (kind 0 or 2); 7 is unassigned
+    4  max_error: a residual block per batch     9  tolerance: a uint16 image with a wide residual block per batch
+
+kind 0 = uint8 [H,W,C] (PIL / numpy layout), 1 = float32 [C,H,W] in [0,1], 2 = uint16 [H,W,C].  Tiling (tile_grid): the
+image is reflect-padded bottom/right to multiples of 16 inside the gather kernel; the last row / column of tiles shifts
+inward (overlap, no extra padding) and every pixel is written back by the one tile that owns it.  Tiles are coded
 independently, as the reference's patch-trained model sees them; at the default overlap = 0 seams are not blended.
 
-overlap = O > 0 (a multiple of 16, at most half a tile side) is stream version 3: the version-1 head, then segments
-u32 (1 allowed), then overlap u32.  Neighbouring tiles then share O pixels (tile_grid: stride t - O) and their
-reconstructions are cross-faded over them with linear ramps that sum to 1; the blend is a fixed float32 fold over a
-pixel's contributing tiles in ascending tile number (dsic_tile_blend_window_f32), so a window decodes to the same
-bits however its tiles are batched.
+segments = K > 1 (entropy.compress_latents): every tile's y string is K independent strings, so that a decoder reads a
+tile on K waves; version 1 is written whenever K = 1 and nothing else asks for more.
 
-max_error = tau (an integer 0 .. 127; uint8 images, overlap = 0) is stream version 4, the near-lossless mode: the
-version-3 head with overlap word 0, then max_error u32 and res_bands u32 (16), and per batch, behind `u64 length,
-container` (the bytes the same call without max_error writes), `u64 length, residual block` (residual.py): per tile
-the quantized difference between the tile and the lossy uint8 reconstruction, coded with tables built from the tile's
-own histogram.  The decoders add it back in the stitch, and every decoded pixel lies within tau of the original;
-tau = 0 is lossless.  Tiles stay independent, so a region still decodes from its own tiles' bytes alone.
+overlap = O > 0 (a multiple of 16, at most half a tile side): neighbouring tiles share O pixels (tile_grid: stride
+t - O) and their reconstructions are cross-faded over them with linear ramps that sum to 1; the blend is a fixed float32
+fold over a pixel's contributing tiles in ascending tile number (dsic_tile_blend_window_f32), so a window decodes to the
+same bits however its tiles are batched.
 
-nodata = v (an integer 0 .. 255; uint8 images, overlap = 0, no max_error, no overviews) is stream version 5: the
-version-3 head with overlap word 0, then nodata u32 and coded u32 (nc), then `u64 length, mask block` (mask.py) and
-ceil(nc / batch) times `u64 length, container`; 0 containers are allowed.  A pixel is nodata iff all its channels
-equal v.  Per tile, over the pixels it owns inside H x W, the block holds a state: 0 empty (all nodata), 1 full (none),
-2 mixed.  The coded tiles are those of state 1 and 2 in ascending tile number, container k holds coded tiles k batch
-... ; their strings are byte for byte those of the stream without nodata.  A mixed tile's mask travels in the block
-as the vertical delta of its bit plane, raw or as a list of positions.  The decoders skip empty tiles altogether and
-write v at every nodata pixel after the stitch (dsic_mask_apply_u8 / _f32, which write only pixels a tile owns, so
-stray set bits outside a tile's owned rectangle are harmless).
+max_error = tau (an integer 0 .. 127; uint8 images, overlap = 0), the near-lossless mode: behind every container (the
+bytes the same call without max_error writes) goes a residual block (residual.py): per tile the quantized difference
+between the tile and the lossy uint8 reconstruction, coded with tables built from the tile's own histogram.  The
+decoders add it back in the stitch, and every decoded pixel lies within tau of the original; tau = 0 is lossless.
+Tiles stay independent, so a region still decodes from its own tiles' bytes alone.
+
+nodata = v (an integer 0 .. 255; uint8 images, overlap = 0, no max_error, no overviews): a pixel is nodata iff all its
+channels equal v.  Per tile, over the pixels it owns inside H x W, the mask block (mask.py) holds a state: 0 empty (all
+nodata), 1 full (none), 2 mixed.  The coded tiles are those of state 1 and 2 in ascending tile number, container k
+holds coded tiles k batch ... (0 containers are allowed); their strings are byte for byte those of the stream without
+nodata.  A mixed tile's mask travels in the block as the vertical delta of its bit plane, raw or as a list of
+positions.  The decoders skip empty tiles altogether and write v at every nodata pixel after the stitch
+(dsic_mask_apply_u8 / _f32, which write only pixels a tile owns, so stray set bits outside a tile's owned rectangle are
+harmless).
 
 Because tiles are independent and the DSIC2 heads hold every string's length, any window of a stream can be decoded
 from only the tiles that own its pixels: stream_index finds their bytes from the heads alone, decompress_region decodes
 them in dense batches and stitches them into the window, byte for byte the crop of decompress_image's result.
 decompress_image is the same decode (_decode_window) of the window (0, 0, H, W), one batch per container.
 
-A uint16 [H,W,C] image (kind 2: 16-bit imagery such as Sentinel-2 reflectances, C at most 4) is stream version 6: the
-version-3 head (segments word, overlap word, 0 allowed), then per band `lo u32, hi u32` with lo <= hi <= 65535, the
-scale: by default the band's own minimum and maximum (dsic_band_range_u16), or the caller's.  With R = hi - lo the model
-sees norm(v) = R == 0 ? 0 : float32(min(max(v, lo), hi) - lo) / float32(R), the arithmetic of the reference's
+A uint16 [H,W,C] image (kind 2: 16-bit imagery such as Sentinel-2 reflectances, C at most 4) carries a per-band scale
+(lo, hi): by default the band's own minimum and maximum (dsic_band_range_u16), or the caller's.  With R = hi - lo the
+model sees norm(v) = R == 0 ? 0 : float32(min(max(v, lo), hi) - lo) / float32(R), the arithmetic of the reference's
 code/combinebandsall.py:7-12, computed in the tile gather (dsic_tile_gather_u16), so every container is byte for byte
 that of the float32 image norm(img); the decoders return denorm(x) = lo + uint32(clamp(x, 0, 1) * float32(R) + 0.5f),
-rounded to nearest (stitch and blend finish), and denorm(norm(v)) == v inside [lo, hi].  Version 6 and kind 2 occur only
-together.  max_error and nodata are refused with uint16 images: the residual tables and the mask classifier are 8-bit;
-max_error stays the uint8 mode, and a uint16 image takes tolerance instead.
+rounded to nearest (stitch and blend finish), and denorm(norm(v)) == v inside [lo, hi].  max_error and nodata are
+refused with uint16 images: the residual tables and the mask classifier are 8-bit; max_error stays the uint8 mode, and
+a uint16 image takes tolerance instead.
 
-tolerance = tau (an integer 0 .. 32767; uint16 images, overlap = 0) is stream version 9, the bounded-error mode of
-16-bit imagery: the version-3 head with overlap word 0, then C x (lo u32, hi u32), tolerance u32 and res_bands u32
-(16), and per batch, behind `u64 length, container` (the bytes of the version-6 stream of the same call without
-tolerance), `u64 length, wide residual block` (residual16.py): per tile the quantized difference between the image and
-the lossy uint16 reconstruction, split into a high part of at most 511 values, coded as the version-4 residual is,
-and k raw bit planes.  Every decoded value lies within tau of the original and tau = 0 returns it, also outside the
-scale.  Version 9 goes with kind 2 only; the decoders return uint16.  k follows each tile's largest step, so one outlier
-in a quiet tile costs k raw bits on every sample of the tile (escape coding is not done).
+tolerance = tau (an integer 0 .. 32767; uint16 images, overlap = 0), the bounded-error mode of 16-bit imagery: behind
+every container (the bytes of the version-6 stream of the same call without tolerance) goes a wide residual block
+(residual16.py): per tile the quantized difference between the image and the lossy uint16 reconstruction, split into a
+high part of at most 511 values, coded as the version-4 residual is, and k raw bit planes.  Every decoded value lies
+within tau of the original and tau = 0 returns it, also outside the scale; the decoders return uint16.  k follows each
+tile's largest step, so one outlier in a quiet tile costs k raw bits on every sample of the tile (escape coding is not
+done).
 
 overviews = n > 0 writes a pyramid, the image at full, 1/2, 1/4, ... 1/2^n resolution in one DSICP stream:
 
@@ -74,16 +78,14 @@ the last row or column of an odd side counted twice; uint8 and uint16 (a + b + c
 (c + d)) * 0.25f), and every level's bytes are the DSICI stream compress_image writes for that level's image, so a level is
 read, indexed and decoded on its own (level=l of the decoders and of stream_index) through a view of its byte range.
 
-valid = mask (a torch.bool [H,W] plane beside a uint8 or uint16 image, True = the pixel holds data) with fill = f is
-stream version 8, the general form of the nodata mask: nothing is guessed from pixel values.  Layout: the version-1
-head | segments u32 | overlap u32 = 0 | fill u32 | coded u32 | kind 2 only: C x (lo u32, hi u32) | u64 length, mask
-block | ceil(coded / batch) x (u64 length, container).  Kind is 0 or 2; the mask block is mask.py's, a set bit meaning
-owned, inside the image and invalid, its nodata field carrying fill; states, coded tiles and containers are as in
-version 5, and the coded tiles' strings are those of the stream without the mask (version 1 / 2, or version 6 with the
+valid = mask (a torch.bool [H,W] plane beside a uint8 or uint16 image, True = the pixel holds data) with fill = f is the
+general form of the nodata mask: nothing is guessed from pixel values.  The mask block is mask.py's, a set bit meaning
+owned, inside the image and invalid, its nodata field carrying fill; states, coded tiles and containers are as with
+nodata, and the coded tiles' strings are those of the stream without the mask (version 1 / 2, or version 6 with the
 same scale).  The decoders write fill at every invalid pixel and can return the mask (with_valid, decompress_valid).
 With overviews the levels come from the masked halving (build_overviews with valid): of the four taps k are valid with
 the sum S, the output is valid iff k > 0 and is (2 S + k) // (2 k), and for k = 0 the unmasked mean; every level is the
-version-8 stream of its own image and mask, with level 0's fill and scale.  Version 7 is unassigned.
+version-8 stream of its own image and mask, with level 0's fill and scale.
 
 ImageReader (view.py) keeps a stream open for pan and zoom: levels opened once, decoded tiles cached on the device and
 assembled by the calls decompress_region makes (_assemble_window), requests decoded together (read_many), and windows
@@ -92,6 +94,7 @@ resampled to a size asked for from the level view_level picks (csrc/view.hip).
 from __future__ import annotations
 
 import bisect
+import collections
 import ctypes
 import operator
 import struct
@@ -109,20 +112,19 @@ from .ops import _p, _stream
 
 MAGIC = b"DSICI\x00"
 VERSION = 1
-VERSION_SEG = 2            # version 1 + the segments word; written only for segments > 1
-VERSION_OV = 3             # version 1 + the segments word + the overlap word; written only for overlap > 0
-VERSION_RES = 4            # the version-3 head with overlap 0 + max_error u32 + res_bands u32; a residual block per batch
-VERSION_MASK = 5           # the version-3 head with overlap 0 + nodata u32 + coded u32; a mask block, then the coded tiles' batches
-VERSION_U16 = 6            # the version-3 head (overlap 0 allowed) + C x (lo u32, hi u32), the per-band scale; kind 2 only
-VERSION_VALID = 8          # the version-3 head with overlap 0 + fill u32 + coded u32 (+ the scale for kind 2); a mask block, then the coded tiles' batches
-VERSION_TOL = 9            # the version-3 head with overlap 0 + the scale + tolerance u32 + res_bands u32; a wide residual block per batch; kind 2 only
+VERSION_SEG = 2            # segments > 1
+VERSION_OV = 3             # overlap > 0
+VERSION_RES = 4            # max_error: a residual block per batch
+VERSION_MASK = 5           # nodata: a mask block, then the coded tiles' batches
+VERSION_U16 = 6            # a uint16 image with its per-band scale
+VERSION_VALID = 8          # a validity mask with its fill; 7 is unassigned
+VERSION_TOL = 9            # tolerance: a uint16 image with a wide residual block per batch
 BLEND_IDS = 64             # tiles per dsic_tile_blend_window_f32 call
 KIND_U8_HWC, KIND_F32_CHW, KIND_U16_HWC = 0, 1, 2
+_OUT_KINDS = {"u8": KIND_U8_HWC, "f32": KIND_F32_CHW, "u16": KIND_U16_HWC}
 _HEAD = struct.Struct("<6sHI6I4I2I")
-_SEGS = struct.Struct("<I")
-_RES = struct.Struct("<II")                                                # version 4: max_error, res_bands
-_MASK = struct.Struct("<II")                                               # version 5: nodata, coded
-_SCALE = struct.Struct("<II")                                              # version 6, per band: lo, hi
+_HEAD_KEYS = ("version", "numerics", "H", "W", "C", "kind", "th", "tw", "N", "M", "in_ch", "spatial_params", "batch",
+              "batches")
 _LEN = struct.Struct("<Q")
 PMAGIC = b"DSICP\x00"
 PVERSION = 1
@@ -224,123 +226,178 @@ def _model_shape(model):
     return int(model.N), int(model.M), int(in_ch), int(bool(getattr(model, "spatial_params", False)))
 
 
+# ---- the DSICI head: the fixed 60 bytes (_HEAD), then the version's fields, each a run of u32 words ----------------------
+# A field, stated once.  count(e, h): its words in a stream of entry e whose fixed head is h; load(e, h, w): the reader's
+# check of its words w, and what it keeps of them in h; dump(e, h, what): the words a writer emits for a header h whose
+# segments, overlap and coded it has settled, checking a caller's value as compress_image does.
+_Field = collections.namedtuple("_Field", "count load dump")
+
+
+def _one(e, h):
+    return 1
+
+
+def _load_segments(e, h, w):
+    h["segments"] = w[0]
+    allowed = entropy.SEGMENTS[1:] if e.segments == "many" else entropy.SEGMENTS
+    if w[0] not in allowed or h["M"] % w[0]:
+        raise ValueError(f"DSICI stream: segments={w[0]} is not one of {allowed} dividing M={h['M']}")
+
+
+def _load_overlap(e, h, w):
+    if e.overlap == "zero":
+        if w[0] != 0:
+            raise ValueError(f"DSICI stream: version {h['version']} with overlap={w[0]} "
+                             f"({'a mask' if e.mask else 'a residual layer'} over blended tiles is not supported)")
+        return
+    if e.overlap == "positive" and w[0] == 0:
+        raise ValueError(f"DSICI stream: version {h['version']} with overlap=0")
+    h["overlap"] = _check_overlap(w[0], h["th"], h["tw"], "DSICI stream")
+
+
+def _ranged(key, top, check, note=""):
+    """The field key = v with 0 <= v <= top(h); check(value, top, what): the writer's test of a caller's value."""
+    def load(e, h, w):
+        h[key] = w[0]
+        if w[0] > top(h):
+            raise ValueError(f"DSICI stream: {key}={w[0]} (0 .. {top(h)}{note.format(**h)})")
+    return _Field(_one, load, lambda e, h, what: [check(h[key], top(h), what)])
+
+
+def _load_bands(e, h, w):
+    if w[0] != e.layer.BANDS:
+        raise ValueError(f"DSICI stream: version {h['version']} with res_bands={w[0]}, this reader knows {e.layer.BANDS}")
+
+
+def _load_scale(e, h, w):
+    if w:
+        h["scale"] = list(zip(w[0::2], w[1::2]))
+    for lo, hi in zip(w[0::2], w[1::2]):
+        if lo > hi or hi > 65535:
+            raise ValueError(f"DSICI stream: scale pair ({lo}, {hi}) must have lo <= hi <= 65535")
+
+
+def _dump_scale(e, h, what):
+    return [v for pair in check_scale(h["scale"], h["C"], what) for v in pair] if h["kind"] == KIND_U16_HWC else []
+
+
+_FIELDS = {
+    "segments": _Field(_one, _load_segments, lambda e, h, what: [h["segments"]]),
+    "overlap": _Field(_one, _load_overlap, lambda e, h, what: [h["overlap"]]),
+    "max_error": _ranged("max_error", lambda h: 127, lambda v, top, what: _residual.check_max_error(v, what)),
+    "res_bands": _Field(_one, _load_bands, lambda e, h, what: [e.layer.BANDS]),
+    "nodata": _ranged("nodata", lambda h: 255, lambda v, top, what: _mask.check_nodata(v, what)),
+    "coded": _Field(_one, lambda e, h, w: h.update(coded=w[0]), lambda e, h, what: [h["coded"]]),
+    "fill": _ranged("fill", lambda h: 65535 if h["kind"] == KIND_U16_HWC else 255, _mask.check_fill, " for kind {kind}"),
+    # C pairs (lo, hi) of a uint16 image; a version that also takes kind 0 (8) has none there
+    "scale": _Field(lambda e, h: 2 * h["C"] if h["kind"] == KIND_U16_HWC else 0, _load_scale, _dump_scale),
+    "tolerance": _ranged("tolerance", lambda h: _residual16.MAX_TOLERANCE,
+                         lambda v, top, what: _residual16.check_tolerance(v, what)),
+}
+
+# A version, stated once.  kinds: the image kinds it goes with; fields: what follows the fixed head, in order; segments:
+# "many" (K > 1) or "any"; overlap: "positive", "free" (0 allowed) or "zero"; key: the header key that makes a writer
+# choose the version, name: what messages call it; mask: a mask block (mask.py) precedes the containers, its fill value
+# being h[key]; layer: the module (residual or residual16) of the residual block that follows every container, its
+# bound being h[key].
+_Version = collections.namedtuple("_Version", "kinds fields segments overlap key name mask layer",
+                                  defaults=((), None, None, None, None, False, None))
+_U8_F32, _U16 = (KIND_U8_HWC, KIND_F32_CHW), (KIND_U16_HWC,)
+FORMATS = {
+    VERSION: _Version(_U8_F32),
+    VERSION_SEG: _Version(_U8_F32, ("segments",), "many"),
+    VERSION_OV: _Version(_U8_F32, ("segments", "overlap"), "any", "positive"),
+    VERSION_RES: _Version(_U8_F32, ("segments", "overlap", "max_error", "res_bands"), "any", "zero", "max_error",
+                          "max_error", layer=_residual),
+    VERSION_MASK: _Version(_U8_F32, ("segments", "overlap", "nodata", "coded"), "any", "zero", "nodata", "nodata",
+                           mask=True),
+    VERSION_U16: _Version(_U16, ("segments", "overlap", "scale"), "any", "free", "scale", "a uint16 image"),
+    VERSION_VALID: _Version((KIND_U8_HWC, KIND_U16_HWC), ("segments", "overlap", "fill", "coded", "scale"), "any", "zero",
+                            "fill", "a validity mask", mask=True),
+    VERSION_TOL: _Version(_U16, ("segments", "overlap", "scale", "tolerance", "res_bands"), "any", "zero", "tolerance",
+                          "tolerance", layer=_residual16),
+}
+
+
+def _format_of(h) -> _Version:
+    """The table entry of a header that a reader has accepted."""
+    return FORMATS[h["version"]]
+
+
+def _listed(names, last) -> str:
+    """["a", "b", "c"], "or" -> "a, b or c"."""
+    names = [str(n) for n in names]
+    return f"{', '.join(names[:-1])} {last} {names[-1]}" if len(names) > 1 else names[0]
+
+
+def _version_for(h) -> int:
+    """The version a header is written as: the highest whose key it holds (tolerance, fill, scale, nodata, max_error),
+    else 3 for overlap > 0, 2 for segments > 1, else 1."""
+    return next((v for v in sorted(FORMATS, reverse=True) if h.get(FORMATS[v].key) is not None),
+                VERSION_OV if h.get("overlap", 0) else VERSION_SEG if h.get("segments", 1) > 1 else VERSION)
+
+
+def _check_kind(e, version, kind, what):
+    """The kind against the version, where the head's layout hangs on it: a uint16 image has a scale, so kind 2 and the
+    versions that take it are held to each other here; another kind nobody knows is left to _stream_grid."""
+    if kind not in e.kinds and KIND_U16_HWC in e.kinds + (kind,):
+        raise ValueError(f"{what}: version {version} with kind {kind} ({e.name or 'it'} goes with kind "
+                         f"{_listed(e.kinds, 'or')}; kind {KIND_U16_HWC}, the uint16 image, and the versions "
+                         "that carry a scale go together)")
+
+
 def pack_image_stream(header: dict, blobs, residuals=None, mask=None) -> bytes:
-    """header (the fields unpack_image_stream returns) + the DSIC2 containers -> the stream (pure Python).  A header
-    with "segments" = K > 1 writes version 2, whose containers are DSIC3 with that K; one with "overlap" = O > 0
-    writes version 3 (segments word, then overlap word), whose containers are DSIC2 for K = 1 and DSIC3 otherwise.
-    A header with "max_error" = tau (not None) writes version 4: segments word, overlap word 0, max_error, res_bands,
-    and behind every container its residual block from `residuals` (residual.pack_block).
-    A header with "nodata" = v (not None) writes version 5: segments word, overlap word 0, nodata, coded (the number
-    of tiles that are not empty, counted from the block's states), then `u64 length, mask` with `mask` the mask block
-    (mask.pack_block), then the containers of the coded tiles, `batch` to a container; there may be none.
-    A header with "scale" = [(lo, hi)] * C (not None) writes version 6, the uint16 image: kind must be 2 (and kind 2
-    needs a scale); segments word, overlap word (0 allowed), then lo, hi per band; no max_error, no nodata.
-    A header with "fill" = f (not None) writes version 8, the validity mask: kind 0 or 2; segments word, overlap word
-    0, fill, coded (counted from the block's states; a "coded" in the header must agree), for kind 2 the scale, then
-    `u64 length, mask` with `mask` the mask block whose nodata field is f, then the coded tiles' containers; no
-    overlap, max_error or nodata.
-    A header with "tolerance" = tau (not None) writes version 9, the bounded-error uint16 image: kind 2 with its
-    scale; segments word, overlap word 0, the scale, tolerance, res_bands, and behind every container its wide
-    residual block from `residuals` (residual16.pack_block); no overlap, max_error, nodata or fill."""
-    h = header
-    K = entropy.check_segments(h.get("segments", 1), h["M"], "pack_image_stream")
-    O = _check_overlap(h.get("overlap", 0), h["th"], h["tw"], "pack_image_stream")
+    """header (the fields unpack_image_stream returns) + the DSIC2 containers -> the stream (pure Python).  The version
+    is the highest one whose key (FORMATS) the header holds: tolerance, fill, scale, nodata, max_error; else 3 for
+    "overlap" > 0, 2 for "segments" > 1, else 1.  ValueError for a key, an overlap > 0 or a block the version does not
+    take, and for a value a field refuses.  residuals: behind every container its residual block (residual.pack_block
+    for max_error, residual16.pack_block for tolerance); mask: the mask block (mask.pack_block) of a header with nodata
+    or fill, whose nodata field is that value; the containers then hold the tiles that are not empty, counted from the
+    block's states, `batch` to a container, and there may be none."""
+    what = "pack_image_stream"
+    h = dict(header)
+    K = h["segments"] = entropy.check_segments(h.get("segments", 1), h["M"], what)
+    O = h["overlap"] = _check_overlap(h.get("overlap", 0), h["th"], h["tw"], what)
     if (h.get("scale") is not None) != (h["kind"] == KIND_U16_HWC):
         raise ValueError("pack_image_stream: a scale goes with kind 2 (uint16 [H,W,C]), and only with it")
-    if h.get("tolerance") is not None:
-        tau = _residual16.check_tolerance(h["tolerance"], "pack_image_stream")
-        if h["kind"] != KIND_U16_HWC:
-            raise ValueError("pack_image_stream: tolerance goes with kind 2 (uint16 [H,W,C]); max_error is the uint8 "
-                             "mode")
-        if O or h.get("max_error") is not None or h.get("nodata") is not None or h.get("fill") is not None or \
-                mask is not None:
-            raise ValueError("pack_image_stream: tolerance together with overlap > 0, max_error, nodata or a validity "
-                             "mask is not supported")
-        if residuals is None or len(residuals) != len(blobs):
-            raise ValueError("pack_image_stream: tolerance needs one wide residual block per container")
-        scale = check_scale(h["scale"], h["C"], "pack_image_stream")
-        head = _HEAD.pack(MAGIC, VERSION_TOL, h["numerics"] & 0xFFFFFFFF, h["H"], h["W"], h["C"], h["kind"], h["th"],
-                          h["tw"], h["N"], h["M"], h["in_ch"], h["spatial_params"], h["batch"], len(blobs))
-        head += _SEGS.pack(K) + _SEGS.pack(0) + b"".join(_SCALE.pack(lo, hi) for lo, hi in scale)
-        head += _RES.pack(tau, _residual16.BANDS)
-        return b"".join([head] + [_LEN.pack(len(b)) + bytes(b) + _LEN.pack(len(r)) + bytes(r)
-                                  for b, r in zip(blobs, residuals)])
-    if h.get("fill") is not None:
-        if h["kind"] not in (KIND_U8_HWC, KIND_U16_HWC):
-            raise ValueError(f"pack_image_stream: a validity mask goes with kind {KIND_U8_HWC} or {KIND_U16_HWC}, not "
-                             f"kind {h['kind']}")
-        v = _mask.check_fill(h["fill"], 65535 if h["kind"] == KIND_U16_HWC else 255, "pack_image_stream")
-        if O or h.get("max_error") is not None or residuals is not None or h.get("nodata") is not None:
-            raise ValueError("pack_image_stream: a validity mask together with overlap > 0, max_error or nodata is not "
-                             "supported")
+    version = _version_for(h)
+    e = FORMATS[version]
+    _check_kind(e, version, h["kind"], what)
+    # what the version does not take: overlap > 0, and the keys of the versions it ranks above
+    rivals = [r for r in (FORMATS[v] for v in sorted(FORMATS) if v < version) if r.key and r.key not in e.fields]
+    if (O and e.overlap == "zero") or any(h.get(r.key) is not None for r in rivals):
+        names = ["overlap > 0"] * (e.overlap == "zero") + [r.name for r in rivals]
+        raise ValueError(f"pack_image_stream: {e.name} together with {_listed(names, 'or')} is not supported")
+    if not e.mask and mask is not None:
+        raise ValueError("pack_image_stream: a mask block without nodata in the header")
+    if e.layer is None and residuals is not None:
+        raise ValueError("pack_image_stream: residual blocks without max_error in the header")
+    if e.layer is not None and (residuals is None or len(residuals) != len(blobs)):
+        raise ValueError(f"pack_image_stream: {e.key} needs one {e.layer.FORMAT.name} block per container")
+    parts = []
+    if e.mask:
         if mask is None:
-            raise ValueError("pack_image_stream: fill needs the mask block")
+            raise ValueError(f"pack_image_stream: {e.key} needs the mask block")
         mask = bytes(mask)
+        (v,) = _FIELDS[e.key].dump(e, h, what)
         n = _grid(h["H"], h["W"], h["th"], h["tw"])["n"]
-        states, _ = _mask.read_block_head(lambda o, c: mask[o:o + c], 0, len(mask), n, h["th"], h["tw"], v,
-                                          "pack_image_stream")
+        states, _ = _mask.read_block_head(lambda o, c: mask[o:o + c], 0, len(mask), n, h["th"], h["tw"], v, what)
         coded = sum(1 for s in states if s != _mask.EMPTY)
-        if h.get("coded", coded) != coded:
+        if e.key == "fill" and h.get("coded", coded) != coded:         # a nodata header's count was never read
             raise ValueError(f"pack_image_stream: the header says {h['coded']} coded tiles, the mask block's states "
                              f"{coded}")
         if len(blobs) != -(-coded // h["batch"]):
             raise ValueError(f"pack_image_stream: {len(blobs)} containers for {coded} coded tiles in batches of "
                              f"{h['batch']}")
-        head = _HEAD.pack(MAGIC, VERSION_VALID, h["numerics"] & 0xFFFFFFFF, h["H"], h["W"], h["C"], h["kind"], h["th"],
-                          h["tw"], h["N"], h["M"], h["in_ch"], h["spatial_params"], h["batch"], len(blobs))
-        head += _SEGS.pack(K) + _SEGS.pack(0) + _MASK.pack(v, coded)
-        if h["kind"] == KIND_U16_HWC:
-            head += b"".join(_SCALE.pack(lo, hi) for lo, hi in check_scale(h["scale"], h["C"], "pack_image_stream"))
-        return b"".join([head, _LEN.pack(len(mask)), mask] + [_LEN.pack(len(b)) + bytes(b) for b in blobs])
-    if h.get("scale") is not None:
-        scale = check_scale(h["scale"], h["C"], "pack_image_stream")
-        if h.get("nodata") is not None or h.get("max_error") is not None or residuals is not None or mask is not None:
-            raise ValueError("pack_image_stream: a uint16 image together with max_error or nodata is not supported")
-        head = _HEAD.pack(MAGIC, VERSION_U16, h["numerics"] & 0xFFFFFFFF, h["H"], h["W"], h["C"], h["kind"], h["th"],
-                          h["tw"], h["N"], h["M"], h["in_ch"], h["spatial_params"], h["batch"], len(blobs))
-        head += _SEGS.pack(K) + _SEGS.pack(O) + b"".join(_SCALE.pack(lo, hi) for lo, hi in scale)
-        return b"".join([head] + [_LEN.pack(len(b)) + bytes(b) for b in blobs])
-    if h.get("nodata") is not None:
-        v = _mask.check_nodata(h["nodata"], "pack_image_stream")
-        if O or h.get("max_error") is not None or residuals is not None:
-            raise ValueError("pack_image_stream: nodata together with overlap > 0 or max_error is not supported")
-        if mask is None:
-            raise ValueError("pack_image_stream: nodata needs the mask block")
-        mask = bytes(mask)
-        n = _grid(h["H"], h["W"], h["th"], h["tw"])["n"]
-        states, _ = _mask.read_block_head(lambda o, c: mask[o:o + c], 0, len(mask), n, h["th"], h["tw"], v,
-                                          "pack_image_stream")
-        coded = sum(1 for s in states if s != _mask.EMPTY)
-        if len(blobs) != -(-coded // h["batch"]):
-            raise ValueError(f"pack_image_stream: {len(blobs)} containers for {coded} coded tiles in batches of "
-                             f"{h['batch']}")
-        head = _HEAD.pack(MAGIC, VERSION_MASK, h["numerics"] & 0xFFFFFFFF, h["H"], h["W"], h["C"], h["kind"], h["th"],
-                          h["tw"], h["N"], h["M"], h["in_ch"], h["spatial_params"], h["batch"], len(blobs))
-        head += _SEGS.pack(K) + _SEGS.pack(0) + _MASK.pack(v, coded)
-        return b"".join([head, _LEN.pack(len(mask)), mask] + [_LEN.pack(len(b)) + bytes(b) for b in blobs])
-    if mask is not None:
-        raise ValueError("pack_image_stream: a mask block without nodata in the header")
-    if h.get("max_error") is not None:
-        tau = _residual.check_max_error(h["max_error"], "pack_image_stream")
-        if O:
-            raise ValueError("pack_image_stream: max_error together with overlap > 0 is not supported")
-        if residuals is None or len(residuals) != len(blobs):
-            raise ValueError("pack_image_stream: max_error needs one residual block per container")
-        head = _HEAD.pack(MAGIC, VERSION_RES, h["numerics"] & 0xFFFFFFFF, h["H"], h["W"], h["C"], h["kind"], h["th"],
-                          h["tw"], h["N"], h["M"], h["in_ch"], h["spatial_params"], h["batch"], len(blobs))
-        head += _SEGS.pack(K) + _SEGS.pack(0) + _RES.pack(tau, _residual.BANDS)
-        return b"".join([head] + [_LEN.pack(len(b)) + bytes(b) + _LEN.pack(len(r)) + bytes(r)
-                                  for b, r in zip(blobs, residuals)])
-    if residuals is not None:
-        raise ValueError("pack_image_stream: residual blocks without max_error in the header")
-    head = _HEAD.pack(MAGIC, VERSION_OV if O else (VERSION_SEG if K > 1 else VERSION), h["numerics"] & 0xFFFFFFFF,
-                      h["H"], h["W"], h["C"], h["kind"], h["th"], h["tw"], h["N"], h["M"], h["in_ch"],
-                      h["spatial_params"], h["batch"], len(blobs))
-    if O:
-        head += _SEGS.pack(K) + _SEGS.pack(O)
-    elif K > 1:
-        head += _SEGS.pack(K)
-    return b"".join([head] + [_LEN.pack(len(b)) + bytes(b) for b in blobs])
+        h["coded"] = coded
+        parts = [_LEN.pack(len(mask)), mask]
+    words = [w for name in e.fields for w in _FIELDS[name].dump(e, h, what)]
+    head = _HEAD.pack(MAGIC, version, h["numerics"] & 0xFFFFFFFF, *(h[k] for k in _HEAD_KEYS[2:-1]), len(blobs))
+    for i, b in enumerate(blobs):
+        parts += [_LEN.pack(len(b)), bytes(b)]
+        if e.layer is not None:
+            parts += [_LEN.pack(len(residuals[i])), bytes(residuals[i])]
+    return b"".join([head, struct.pack(f"<{len(words)}I", *words)] + parts)
 
 
 class _Source:
@@ -373,10 +430,20 @@ class _Source:
         return out
 
 
+def _read_frame(src, off):
+    """`u64 length, bytes` at off -> (where the bytes begin, the length)."""
+    if off + _LEN.size > src.size:
+        raise ValueError("truncated DSICI stream")
+    (size,) = _LEN.unpack(src.read_at(off, _LEN.size))
+    if off + _LEN.size + size > src.size:
+        raise ValueError("truncated DSICI stream")
+    return off + _LEN.size, size
+
+
 def _read_framing(src, head=None):
     """The DSICI head and the length words of a _Source -> (header fields, (offset, bytes) of every batch's container,
-    the same of every batch's residual block: empty but for versions 4 and 9); what lies inside them is not read.  head: the
-    first _HEAD.size bytes, where the caller has read them already."""
+    the same of every batch's residual block: empty unless the version has a residual layer); what lies inside them is
+    not read.  head: the first _HEAD.size bytes, where the caller has read them already."""
     if head is None:
         head = src.read_at(0, _HEAD.size)
     if len(head) < _HEAD.size:
@@ -384,118 +451,32 @@ def _read_framing(src, head=None):
     f = _HEAD.unpack(head)
     if f[0] != MAGIC:
         raise ValueError("not a DSICI image stream")
-    keys = ("version", "numerics", "H", "W", "C", "kind", "th", "tw", "N", "M", "in_ch", "spatial_params", "batch",
-            "batches")
-    h = dict(zip(keys, f[1:]))
-    if h["version"] not in (VERSION, VERSION_SEG, VERSION_OV, VERSION_RES, VERSION_MASK, VERSION_U16, VERSION_VALID,
-                            VERSION_TOL):
-        raise ValueError(f"DSICI stream version {h['version']}, this reader knows {VERSION}, {VERSION_SEG}, "
-                         f"{VERSION_OV}, {VERSION_RES}, {VERSION_MASK}, {VERSION_U16}, {VERSION_VALID} and "
-                         f"{VERSION_TOL}")
-    if h["version"] == VERSION_TOL:
-        if h["kind"] != KIND_U16_HWC:
-            raise ValueError(f"DSICI stream: version {VERSION_TOL} with kind {h['kind']} (a tolerance goes with kind "
-                             f"{KIND_U16_HWC}, the uint16 image)")
-    elif h["version"] == VERSION_VALID:
-        if h["kind"] not in (KIND_U8_HWC, KIND_U16_HWC):
-            raise ValueError(f"DSICI stream: version {VERSION_VALID} with kind {h['kind']} (a validity mask goes with "
-                             f"kind {KIND_U8_HWC} or {KIND_U16_HWC})")
-    elif (h["version"] == VERSION_U16) != (h["kind"] == KIND_U16_HWC):
-        raise ValueError(f"DSICI stream: version {h['version']} with kind {h['kind']} (version {VERSION_U16} and kind "
-                         f"{KIND_U16_HWC}, the uint16 image, go together)")
+    h = dict(zip(_HEAD_KEYS, f[1:]))
+    if h["version"] not in FORMATS:
+        raise ValueError(f"DSICI stream version {h['version']}, this reader knows {_listed(sorted(FORMATS), 'and')}")
+    e = _format_of(h)
+    _check_kind(e, h["version"], h["kind"], "DSICI stream")
     if h["kind"] == KIND_U16_HWC and not 1 <= h["C"] <= 4:
         raise ValueError(f"DSICI stream: a uint16 image of {h['C']} bands (1 .. 4)")
     off, h["segments"], h["overlap"] = _HEAD.size, 1, 0
-    if h["version"] in (VERSION_SEG, VERSION_OV, VERSION_RES, VERSION_MASK, VERSION_U16, VERSION_VALID, VERSION_TOL):
-        words = {VERSION_SEG: 1, VERSION_OV: 2, VERSION_RES: 4, VERSION_MASK: 4, VERSION_U16: 2 + 2 * h["C"],
-                 VERSION_VALID: 4 + (2 * h["C"] if h["kind"] == KIND_U16_HWC else 0),
-                 VERSION_TOL: 4 + 2 * h["C"]}[h["version"]]
-        word = src.read_at(off, words * _SEGS.size)
-        if len(word) < words * _SEGS.size:
+    counts = [_FIELDS[name].count(e, h) for name in e.fields]
+    if counts:
+        words = src.read_at(off, 4 * sum(counts))
+        if len(words) < 4 * sum(counts):
             raise ValueError("truncated DSICI stream")
-        (h["segments"],) = _SEGS.unpack_from(word, 0)
-        off += words * _SEGS.size
-        allowed = entropy.SEGMENTS[1:] if h["version"] == VERSION_SEG else entropy.SEGMENTS
-        if h["segments"] not in allowed or h["M"] % h["segments"]:
-            raise ValueError(f"DSICI stream: segments={h['segments']} is not one of {allowed} dividing "
-                             f"M={h['M']}")
-        if h["version"] == VERSION_OV:
-            (h["overlap"],) = _SEGS.unpack_from(word, _SEGS.size)
-            if h["overlap"] == 0:
-                raise ValueError("DSICI stream: version 3 with overlap=0")
-            _check_overlap(h["overlap"], h["th"], h["tw"], "DSICI stream")
-        if h["version"] == VERSION_U16:
-            (h["overlap"],) = _SEGS.unpack_from(word, _SEGS.size)
-            _check_overlap(h["overlap"], h["th"], h["tw"], "DSICI stream")
-            h["scale"] = [_SCALE.unpack_from(word, 2 * _SEGS.size + _SCALE.size * c) for c in range(h["C"])]
-            for lo, hi in h["scale"]:
-                if lo > hi or hi > 65535:
-                    raise ValueError(f"DSICI stream: scale pair ({lo}, {hi}) must have lo <= hi <= 65535")
-        if h["version"] == VERSION_TOL:
-            (overlap,) = _SEGS.unpack_from(word, _SEGS.size)
-            if overlap != 0:
-                raise ValueError(f"DSICI stream: version {VERSION_TOL} with overlap={overlap} (a residual layer over "
-                                 "blended tiles is not supported)")
-            h["scale"] = [_SCALE.unpack_from(word, 2 * _SEGS.size + _SCALE.size * c) for c in range(h["C"])]
-            for lo, hi in h["scale"]:
-                if lo > hi or hi > 65535:
-                    raise ValueError(f"DSICI stream: scale pair ({lo}, {hi}) must have lo <= hi <= 65535")
-            h["tolerance"], bands = _RES.unpack_from(word, 2 * _SEGS.size + _SCALE.size * h["C"])
-            if bands != _residual16.BANDS:
-                raise ValueError(f"DSICI stream: version {VERSION_TOL} with res_bands={bands}, this reader knows "
-                                 f"{_residual16.BANDS}")
-            if h["tolerance"] > _residual16.MAX_TOLERANCE:
-                raise ValueError(f"DSICI stream: tolerance={h['tolerance']} (0 .. {_residual16.MAX_TOLERANCE})")
-        if h["version"] == VERSION_RES:
-            overlap, h["max_error"], bands = struct.unpack_from("<3I", word, _SEGS.size)
-            if overlap != 0:
-                raise ValueError(f"DSICI stream: version 4 with overlap={overlap} (a residual layer over blended "
-                                 "tiles is not supported)")
-            if bands != _residual.BANDS:
-                raise ValueError(f"DSICI stream: version 4 with res_bands={bands}, this reader knows "
-                                 f"{_residual.BANDS}")
-            if h["max_error"] > 127:
-                raise ValueError(f"DSICI stream: max_error={h['max_error']} (0 .. 127)")
-        if h["version"] == VERSION_MASK:
-            overlap, h["nodata"], h["coded"] = struct.unpack_from("<3I", word, _SEGS.size)
-            if overlap != 0:
-                raise ValueError(f"DSICI stream: version 5 with overlap={overlap} (a mask over blended tiles is not "
-                                 "supported)")
-            if h["nodata"] > 255:
-                raise ValueError(f"DSICI stream: nodata={h['nodata']} (0 .. 255)")
-        if h["version"] == VERSION_VALID:
-            overlap, h["fill"], h["coded"] = struct.unpack_from("<3I", word, _SEGS.size)
-            if overlap != 0:
-                raise ValueError(f"DSICI stream: version 8 with overlap={overlap} (a mask over blended tiles is not "
-                                 "supported)")
-            top = 65535 if h["kind"] == KIND_U16_HWC else 255
-            if h["fill"] > top:
-                raise ValueError(f"DSICI stream: fill={h['fill']} (0 .. {top} for kind {h['kind']})")
-            if h["kind"] == KIND_U16_HWC:
-                h["scale"] = [_SCALE.unpack_from(word, 4 * _SEGS.size + _SCALE.size * c) for c in range(h["C"])]
-                for lo, hi in h["scale"]:
-                    if lo > hi or hi > 65535:
-                        raise ValueError(f"DSICI stream: scale pair ({lo}, {hi}) must have lo <= hi <= 65535")
-        if h["version"] in (VERSION_MASK, VERSION_VALID):
-            if off + _LEN.size > src.size:
-                raise ValueError("truncated DSICI stream")
-            (size,) = _LEN.unpack(src.read_at(off, _LEN.size))
-            off += _LEN.size
-            if off + size > src.size:
-                raise ValueError("truncated DSICI stream")
-            h["mask_offset"], h["mask_bytes"] = off, size
-            off += size
+        words = struct.unpack(f"<{sum(counts)}I", words)
+        off += 4 * len(words)
+        for name, n in zip(e.fields, counts):
+            _FIELDS[name].load(e, h, words[:n])
+            words = words[n:]
+    if e.mask:
+        h["mask_offset"], h["mask_bytes"] = _read_frame(src, off)
+        off = h["mask_offset"] + h["mask_bytes"]
     frames, rframes = [], []
-    layered = h["version"] in (VERSION_RES, VERSION_TOL)                   # a residual block behind every container
-    for k in range(h["batches"] * (2 if layered else 1)):
-        if off + _LEN.size > src.size:
-            raise ValueError("truncated DSICI stream")
-        (size,) = _LEN.unpack(src.read_at(off, _LEN.size))
-        off += _LEN.size
-        if off + size > src.size:
-            raise ValueError("truncated DSICI stream")
-        (rframes if layered and k % 2 else frames).append((off, size))
-        off += size
+    for _ in range(h["batches"]):
+        for into in (frames, rframes) if e.layer is not None else (frames,):
+            into.append(_read_frame(src, off))
+            off = sum(into[-1])
     if off != src.size:
         raise ValueError(f"DSICI stream: {src.size - off} trailing bytes")
     return h, frames, rframes
@@ -517,9 +498,9 @@ def unpack_image_stream(stream) -> dict:
     s = bytes(stream)
     h, frames, rframes = _read_framing(_Source(s))
     h["blobs"] = [s[off:off + size] for off, size in frames]
-    if h["version"] in (VERSION_RES, VERSION_TOL):
+    if _format_of(h).layer is not None:
         h["residuals"] = [s[off:off + size] for off, size in rframes]
-    if h["version"] in (VERSION_MASK, VERSION_VALID):
+    if _format_of(h).mask:
         h["mask"] = s[h["mask_offset"]:h["mask_offset"] + h["mask_bytes"]]
     return h
 
@@ -847,15 +828,16 @@ def _level_grid(H, W, kind, tile, overlap, tau):
     return g, overlap
 
 
-def _compress_masked(model, x, g, C, batch, tail, segments, nodata, header, valid=None, fill=0, scale=None) -> bytes:
-    """The version-5 stream of a uint8 image on the device: classify the tiles, code those that are not empty (a
-    batch is gathered run by run of consecutive tile numbers into slices of one tensor, so every tile's strings are
-    those of the stream without nodata), and put the mixed tiles' masks into the mask block.
-    valid (uint8 [H,W] on the device, 0 = invalid): the version-8 stream of a uint8 or uint16 image instead; the states
-    and the planes come from the mask itself (dsic_valid_classify, dsic_valid_delta_planes), and a uint16 image is
-    gathered with its scale, as the version-6 stream's tiles are."""
+def _compress_masked(model, x, g, C, batch, tail, header, valid=None) -> bytes:
+    """The stream of an image on the device whose header's version has a mask block: classify the tiles, code those that
+    are not empty (a batch is gathered run by run of consecutive tile numbers into slices of one tensor, so every
+    tile's strings are those of the stream without the mask), and put the mixed tiles' masks into the mask block.
+    valid None: the nodata mask of a uint8 image, read off its pixels.  valid (uint8 [H,W] on the device, 0 = invalid):
+    the states and the planes come from the mask itself (dsic_valid_classify, dsic_valid_delta_planes), and a uint16
+    image is gathered with its scale, as the stream's tiles without the mask are."""
+    v = header[FORMATS[_version_for(header)].key]
     owned = [_owned_in_tile(g, t) for t in range(g["n"])]
-    counts = _mask.classify(x, g, C, nodata) if valid is None else _mask.classify_valid(valid, g)
+    counts = _mask.classify(x, g, C, v) if valid is None else _mask.classify_valid(valid, g)
     states = _mask.tile_states(counts, [(b - a) * (d - c) for a, b, c, d in owned])
     ids = [t for t, s in enumerate(states) if s != _mask.EMPTY]
     L, blobs = _lib.load(), []
@@ -870,60 +852,50 @@ def _compress_masked(model, x, g, C, batch, tail, segments, nodata, header, vali
             while b < len(sel) and sel[b] == sel[b - 1] + 1:
                 b += 1
             if u16:
-                _lib.check(L.dsic_tile_gather_u16(_p(x), _p(tiles[a:b]), g["H"], g["W"], C, g["th"], g["tw"], _lohi(scale),
-                                                  sel[a], b - a, _stream()), "tile_gather_u16")
+                _lib.check(L.dsic_tile_gather_u16(_p(x), _p(tiles[a:b]), g["H"], g["W"], C, g["th"], g["tw"],
+                                                  _lohi(header["scale"]), sel[a], b - a, _stream()), "tile_gather_u16")
             else:
                 _lib.check(L.dsic_tile_gather_u8(_p(x), _p(tiles[a:b]), g["H"], g["W"], C, g["th"], g["tw"], sel[a], b - a,
                                                  _stream()), "tile_gather_u8")
             a = b
-        blobs.append(entropy.compress_to_container(model, tiles, tail, segments=segments))
-    if valid is None:
-        header["nodata"] = nodata
-        return pack_image_stream(header, blobs, mask=_mask.encode_block(x, g, C, nodata, states))
-    header["fill"] = fill
-    if u16:
-        header["scale"] = scale
-    return pack_image_stream(header, blobs, mask=_mask.encode_block(valid, g, None, fill, states))
+        blobs.append(entropy.compress_to_container(model, tiles, tail, segments=header["segments"]))
+    block = _mask.encode_block(x, g, C, v, states) if valid is None else _mask.encode_block(valid, g, None, v, states)
+    return pack_image_stream(header, blobs, mask=block)
 
 
 def _compress_device_image(model, x, tile, batch, tail, segments, overlap, tau, nodata=None, scale=None, valid=None,
                            fill=0, tol=None) -> bytes:
     """compress_image's work on one image that lies contiguous on the model's device, after the argument checks that
     do not depend on its size -> its DSICI stream.  scale: the checked pairs of a uint16 image; tol: its checked
-    tolerance, or None."""
+    tolerance, or None.  The header is made first; the version it will be written as says what travels beside the
+    containers."""
     kind, H, W, C = _image_kind(x, "compress_image")
     N, M, in_ch, spatial = _model_shape(model)
     g, overlap = _level_grid(H, W, kind, tile, overlap, tau)
-    if nodata is not None or valid is not None:
-        return _compress_masked(model, x, g, C, batch, tail, segments, nodata,
-                                {"numerics": entropy.numerics_tag(), "H": H, "W": W, "C": C, "kind": kind,
-                                 "th": g["th"], "tw": g["tw"], "N": N, "M": M, "in_ch": in_ch,
-                                 "spatial_params": spatial, "batch": batch, "segments": segments, "overlap": 0},
-                                valid, fill, scale)
-    blobs, residuals = [], None if tau is None and tol is None else []
+    header = {"numerics": entropy.numerics_tag(), "H": H, "W": W, "C": C, "kind": kind, "th": g["th"], "tw": g["tw"],
+              "N": N, "M": M, "in_ch": in_ch, "spatial_params": spatial, "batch": batch, "segments": segments, "overlap": overlap}
+    header.update({key: value for key, value in (("max_error", tau), ("nodata", nodata), ("scale", scale),
+                                                 ("fill", None if valid is None else fill), ("tolerance", tol))
+                   if value is not None})
+    e = FORMATS[_version_for(header)]
+    if e.mask:
+        return _compress_masked(model, x, g, C, batch, tail, dict(header, overlap=0), valid)
+    blobs, residuals = [], None if e.layer is None else []
     for first in range(0, g["n"], batch):
         n = min(batch, g["n"] - first)
         tiles = _gather(x, kind, g, C, first, n, scale)
-        if tau is None and tol is None:
+        if e.layer is None:
             blobs.append(entropy.compress_to_container(model, tiles, tail, segments=segments))
             continue
         # compress_to_container's work, keeping the forward x_hat: the predictor the decoder will have bit for bit
         c = entropy._coded_batch(model, tiles, tail, entropy.DEFAULT_LMAX, "compress_image", pack=True,
                                  segments=segments)
         blobs.append(c["container"][:c["container_bytes"]].cpu().numpy().tobytes())
-        if tol is not None:                    # the gathered tiles are normalised float32: the image is read in place
+        if e.layer is _residual16:             # the gathered tiles are normalised float32: the image is read in place
             residuals.append(_residual16.encode_block(x, c["x_hat"], H, W, g["th"], g["tw"], _lohi(scale), tol, first))
-            continue
-        residuals.append(_residual.encode_block(tiles, c["x_hat"], [_owned_in_tile(g, t)
-                                                                   for t in range(first, first + n)], tau))
-    header = {"numerics": entropy.numerics_tag(), "H": H, "W": W, "C": C, "kind": kind, "th": g["th"], "tw": g["tw"],
-              "N": N, "M": M, "in_ch": in_ch, "spatial_params": spatial, "batch": batch, "segments": segments, "overlap": overlap}
-    if tau is not None:
-        header["max_error"] = tau
-    if scale is not None:
-        header["scale"] = scale
-    if tol is not None:
-        header["tolerance"] = tol
+        else:
+            residuals.append(_residual.encode_block(tiles, c["x_hat"], [_owned_in_tile(g, t)
+                                                                       for t in range(first, first + n)], tau))
     return pack_image_stream(header, blobs, residuals)
 
 
@@ -1093,9 +1065,7 @@ def _refuse_foreign(model, h, what):
 def _stream_grid(h):
     """The tile grid a DSICI header describes; ValueError where its fields contradict each other."""
     H, W, C, th, tw = h["H"], h["W"], h["C"], h["th"], h["tw"]
-    kinds = {VERSION_U16: (KIND_U16_HWC,), VERSION_TOL: (KIND_U16_HWC,),
-             VERSION_VALID: (KIND_U8_HWC, KIND_U16_HWC)}.get(h["version"], (KIND_U8_HWC, KIND_F32_CHW))
-    if C != h["in_ch"] or h["kind"] not in kinds or h["batch"] < 1:
+    if C != h["in_ch"] or h["kind"] not in _format_of(h).kinds or h["batch"] < 1:
         raise ValueError("DSICI stream: inconsistent header")
     _check_image(H, W)
     if th % 16 or tw % 16 or th < 32 or tw < 32 or th > _ceil16(H) or tw > _ceil16(W):
@@ -1130,12 +1100,12 @@ def _out_image(kind, C, h, w, dev, what):
 def _index_of(src, head=None):
     """stream_index on an open _Source (head: as _read_framing takes it)."""
     ix, frames, rframes = _read_framing(src, head)
-    g = _stream_grid(ix)
+    g, e = _stream_grid(ix), _format_of(ix)
     tiles, containers = [], []
-    ids = None                                 # version 5: the grid numbers of the coded tiles, ascending
-    if ix["version"] in (VERSION_MASK, VERSION_VALID):
+    ids = None                                 # a mask: the grid numbers of the coded tiles, ascending
+    if e.mask:
         states, mrecs = _mask.read_block_head(src.read_at, ix["mask_offset"], ix["mask_bytes"], g["n"], ix["th"],
-                                              ix["tw"], ix["nodata"] if ix["version"] == VERSION_MASK else ix["fill"])
+                                              ix["tw"], ix[e.key])
         ids = [t for t, s in enumerate(states) if s != _mask.EMPTY]
         if len(ids) != ix["coded"]:
             raise ValueError(f"DSICI stream: the head says {ix['coded']} coded tiles, the mask block's states "
@@ -1165,12 +1135,8 @@ def _index_of(src, head=None):
         if ids is not None:
             containers[-1]["ids"] = ids[first:first + len(images)]
         if rframes:
-            if ix["version"] == VERSION_TOL:
-                recs = _residual16.read_block_head(src.read_at, rframes[k][0], rframes[k][1], len(images), ix["C"],
-                                                   ix["th"], ix["tw"], ix["tolerance"])
-            else:
-                recs = _residual.read_block_head(src.read_at, rframes[k][0], rframes[k][1], len(images), ix["C"],
-                                                 ix["th"], ix["tw"], ix["max_error"])
+            recs = e.layer.read_block_head(src.read_at, rframes[k][0], rframes[k][1], len(images), ix["C"], ix["th"],
+                                           ix["tw"], ix[e.key])
             for tile, rec in zip(tiles[first:], recs):
                 tile.update(rec)
             containers[-1].update(r_offset=rframes[k][0], r_bytes=rframes[k][1])
@@ -1302,7 +1268,7 @@ def _apply_mask(source, ix, tiles, img, kind, window, valid_out=None) -> int:
     for a uint16 window.  valid_out: a uint8 [h,w] tensor of ones on the device, or None; the same planes then also
     give the window's validity (dsic_mask_window_u8).  img None: only that."""
     H, W, C, th, tw = ix["H"], ix["W"], ix["C"], ix["th"], ix["tw"]
-    v = ix["nodata"] if "nodata" in ix else ix["fill"]
+    v = ix[_format_of(ix).key]
     masked = [t for t in tiles if ix["tiles"][t]["state"] != _mask.FULL]
     dev = img.device if img is not None else valid_out.device
     uploaded = 0
@@ -1337,29 +1303,30 @@ def _check_out(out, ix, what):
         raise ValueError(f"{what}: out={out!r} (None, 'u8', 'f32' or 'u16')")
     if ix is None:
         return None
-    if out == "u16" and "scale" not in ix:
+    e, u16 = _format_of(ix), ix["kind"] == KIND_U16_HWC                 # a uint16 stream, of any version, has a scale
+    if out == "u16" and not u16:
         raise ValueError(f"{what}: out='u16' needs the scale of a uint16 stream (version {VERSION_U16}); this one is "
                          f"version {ix['version']}")
-    if out in ("u8", "f32") and "tolerance" in ix:
+    if out in ("u8", "f32") and u16 and e.layer is not None:
         raise ValueError(f"{what}: out={out!r} on a uint16 stream with a tolerance (version {VERSION_TOL}): the bound "
                          "is on the uint16 values; take out=None or 'u16'")
-    if out in ("u8", "f32") and "fill" in ix and ix["kind"] == KIND_U16_HWC:
+    if out in ("u8", "f32") and u16 and e.mask:
         raise ValueError(f"{what}: out={out!r} on a uint16 stream with a validity mask (version {VERSION_VALID}): the "
                          "normalised image has no value that means fill")
-    return {None: ix["kind"], "u8": KIND_U8_HWC, "f32": KIND_F32_CHW, "u16": KIND_U16_HWC}[out]
+    return ix["kind"] if out is None else _OUT_KINDS[out]
 
 
 def _coded_tiles(ix, tiles):
     """Of a window's tiles those that hold strings: all, or in a masked stream (version 5 or 8) those that are not
     empty."""
-    return tiles if "coded" not in ix else [t for t in tiles if ix["tiles"][t]["state"] != _mask.EMPTY]
+    return tiles if not _format_of(ix).mask else [t for t in tiles if ix["tiles"][t]["state"] != _mask.EMPTY]
 
 
 def _decode_tiles(model, source, ix, sel, what):
     """One dense decode batch: the tiles `sel` (ascending) of an indexed level, their strings read from `source` in
     one upload -> (g_s's output [n,C,th,tw], contiguous and not clamped; the padded string bytes uploaded; the device
-    copy of sel; the q planes of a version-4 or version-9 stream, else None)."""
-    C, th, tw, tau, tol = ix["C"], ix["th"], ix["tw"], ix.get("max_error"), ix.get("tolerance")
+    copy of sel; the q planes of a stream with a residual layer, else None)."""
+    C, th, tw, e = ix["C"], ix["th"], ix["tw"], _format_of(ix)
     N, Hz, Wz = ix["containers"][0]["shape_z"][1:] if ix["containers"] else (ix["N"], 0, 0)
     n = len(sel)
     # the upload is the tiles' spans back to back: a string at stream offset o lies where its span does
@@ -1376,28 +1343,13 @@ def _decode_tiles(model, source, ix, sel, what):
     images = [(r["min_y"], r["max_y"], r["min_z"], r["max_z"], at(r["z_off"], r["z_len"]), r["z_len"],
                at(r["y_off"], r["y_len"]), r["y_len"]) for r in recs]
     parts = [source.read_at(off, length) for off, length in spans]
-    spec = None
-    if tau is not None:
-        for r in recs:                         # the tables as they arrived, before anything is uploaded
-            i = bisect.bisect_right(starts, r["r_off"]) - 1
-            a = r["r_off"] - starts[i]
-            _residual.check_tables(parts[i][a:a + 2 * C * r["r_L"]], C, r["r_L"], tau)
-        spec = {"C": C, "th": th, "tw": tw, "tau": tau, "smin": [r["r_smin"] for r in recs],
-                "L": [r["r_L"] for r in recs], "segs": [r["r_segs"] for r in recs],
-                "desc": [(at(r["r_off"], r["r_len"]), 2 * C * r["r_L"],
-                          at(r["r_off"], r["r_len"]) + 2 * C * r["r_L"], sum(r["r_segs"])) for r in recs]}
-    if tol is not None:                        # the same, with the tile's bit planes between tables and strings
-        pb = _residual16.plane_bytes(C, th, tw)
-        for r in recs:
-            i = bisect.bisect_right(starts, r["r_off"]) - 1
-            a = r["r_off"] - starts[i]
-            _residual16.check_tables(parts[i][a:a + 2 * C * r["r_L"]], C, r["r_L"])
-        spans_at = [at(r["r_off"], r["r_len"]) for r in recs]
-        spec = {"C": C, "th": th, "tw": tw, "tau": tol, "smin": [r["r_smin"] for r in recs],
-                "L": [r["r_L"] for r in recs], "segs": [r["r_segs"] for r in recs], "k": [r["r_k"] for r in recs],
-                "plane_off": [a + 2 * C * r["r_L"] for a, r in zip(spans_at, recs)],
-                "desc": [(a, 2 * C * r["r_L"], a + 2 * C * r["r_L"] + r["r_k"] * pb, sum(r["r_segs"]))
-                         for a, r in zip(spans_at, recs)]}
+
+    def tables_of(r):                          # a span begins with its tables
+        i = bisect.bisect_right(starts, r["r_off"]) - 1
+        a = r["r_off"] - starts[i]
+        return parts[i][a:a + 2 * C * r["r_L"]]
+
+    spec = None if e.layer is None else _residual.decode_spec(e.layer, recs, C, th, tw, ix[e.key], at, tables_of)
     x_hat, nbytes, ids, *q = entropy._decode_selected(model, images, parts, [n, ix["M"], th // 16, tw // 16],
                                                       [n, N, Hz, Wz], what, ride=sel, segments=ix["segments"],
                                                       seg_lengths=[r["y_segs"] for r in recs], residual=spec)
@@ -1413,9 +1365,9 @@ def _assemble_window(model, source, ix, tiles, window, kind, batches, what, vali
     H, W, C, th, tw = ix["H"], ix["W"], ix["C"], ix["th"], ix["tw"]
     y0, x0, h, w = window
     lohi = (_lohi(ix["scale"]),) if kind == KIND_U16_HWC else ()        # the uint16 calls take the scale last
-    tau = ix.get("max_error")                  # a residual layer: the result is the uint8 image, converted for "f32"
-    img, suffix = _out_image(KIND_U8_HWC if tau is not None else kind, C, h, w, next(model.parameters()).device, what)
-    tol = ix.get("tolerance")                  # its uint16 sibling: the result is the uint16 image
+    layer = _format_of(ix).layer               # a residual layer: the result is its integer image, converted for "f32"
+    img, suffix = _out_image(kind if layer is None else _OUT_KINDS[layer.OUT], C, h, w,
+                             next(model.parameters()).device, what)
     L, O = _lib.load(), ix["overlap"]
     fn = getattr(L, "dsic_tile_stitch_window_" + suffix)
     if O:       # the window's float32 canvas, zeroed: the output itself, or a temporary that the finish turns to uint8
@@ -1423,10 +1375,8 @@ def _assemble_window(model, source, ix, tiles, window, kind, batches, what, vali
     uploaded = taken = 0
     for x_hat, nbytes, ids, q in batches:
         n = x_hat.shape[0]
-        if q is not None and tol is not None:
-            _residual16.stitch_window_u16(x_hat, q, tol, ids, img, H, W, C, th, tw, y0, x0, h, w, *lohi)
-        elif q is not None:
-            _residual.stitch_window_u8(x_hat, q, tau, ids, img, H, W, C, th, tw, y0, x0, h, w)
+        if q is not None:
+            layer.stitch_window(x_hat, q, ix[_format_of(ix).key], ids, img, H, W, C, th, tw, y0, x0, h, w, *lohi)
         elif O:
             for c0 in range(0, n, BLEND_IDS):
                 _lib.check(L.dsic_tile_blend_window_f32(_p(x_hat[c0:]), _p(ids[c0:]), min(BLEND_IDS, n - c0),
@@ -1437,7 +1387,7 @@ def _assemble_window(model, source, ix, tiles, window, kind, batches, what, vali
                        "tile_stitch_window_" + suffix)
         uploaded += nbytes
         taken += 1
-    if "coded" in ix:                          # a mask: empty tiles hold no strings, and are filled here
+    if _format_of(ix).mask:                    # empty tiles hold no strings, and are filled here
         uploaded += _apply_mask(source, ix, tiles, img, kind, (y0, x0, h, w), valid_out)
     if O and kind == KIND_F32_CHW:
         _lib.check(L.dsic_tile_blend_finish_f32(_p(canvas), C, h, w, _stream()), "tile_blend_finish_f32")
@@ -1445,7 +1395,7 @@ def _assemble_window(model, source, ix, tiles, window, kind, batches, what, vali
         _lib.check(L.dsic_tile_blend_finish_u16(_p(canvas), _p(img), C, h, w, *lohi, _stream()), "tile_blend_finish_u16")
     elif O:
         _lib.check(L.dsic_tile_blend_finish_u8(_p(canvas), _p(img), C, h, w, _stream()), "tile_blend_finish_u8")
-    if tau is not None and kind == KIND_F32_CHW:
+    if layer is not None and kind == KIND_F32_CHW:
         img = (img.permute(2, 0, 1).to(torch.float32) / 255).contiguous()
     return img, uploaded, taken
 
@@ -1529,7 +1479,7 @@ def decompress_valid(src, y0=0, x0=0, h=None, w=None, level=0, device="cuda"):
     h, w = ix["H"] - y0 if h is None else int(h), ix["W"] - x0 if w is None else int(w)
     tiles = window_tiles(ix, y0, x0, h, w)
     valid = torch.ones((h, w), dtype=torch.uint8, device=device)
-    if "coded" in ix:
+    if _format_of(ix).mask:
         _apply_mask(source, ix, tiles, None, None, (y0, x0, h, w), valid)
     return valid.bool()
 

@@ -10,15 +10,12 @@
 // The q plane of a tile, float32 [C][th][tw], is read by the coder as the latent [C 16][(th / 16) tw]: 16 row bands
 // per colour plane, coded as 16 segments.  Everything here is integer arithmetic or byte movement; the kernels are
 // memory-bound and move 16 bytes per lane where the layout allows.
-#include "byte_movers.h"
+#include "residual_block.h"
 
 namespace dsic {
 
 constexpr int kResRows = 16;     // rows of one tile per quantize workgroup (th is a multiple of 16)
 constexpr int kResBins = 512;    // histogram bins per (tile, channel): bin q + Q, 2 Q + 1 <= 511 of them used
-constexpr int kResBands = 16;    // row bands per colour plane = segments per tile
-constexpr int kResHead = 30;     // "DSICR\0" | n, C, th, tw, tau, bands u32
-constexpr int kResRec = 12;      // smin i32, L u32, span_bytes u32
 
 __host__ __device__ inline int res_Q(int tau) { return (255 + tau) / (2 * tau + 1); }
 __host__ __device__ inline int res_lmax(int tau) { return (2 * res_Q(tau) + 1 + 7) / 8 * 8; }
@@ -99,17 +96,6 @@ __global__ __launch_bounds__(256) void residual_quantize_kernel(const uint8_t* _
   }
 }
 
-__device__ __forceinline__ int wave_min(int v) {
-#pragma unroll
-  for (int o = 32; o >= 1; o >>= 1) v = min(v, __shfl_xor(v, o, 64));
-  return v;
-}
-__device__ __forceinline__ int wave_max(int v) {
-#pragma unroll
-  for (int o = 32; o >= 1; o >>= 1) v = max(v, __shfl_xor(v, o, 64));
-  return v;
-}
-
 // One wave per (tile, channel): blockIdx.x = channel, blockIdx.y = tile.  hist [n][C][512] -> the tile's support
 // [smin, smin + L) = min .. max of q over all its channels, meta [n][4] = (smin, L, 0, 1) (the residual in the y
 // slots; the z slots describe the one-symbol dummy string of the encode call), and the channel's table
@@ -167,92 +153,6 @@ __global__ __launch_bounds__(64) void residual_tables_kernel(const int* __restri
 #pragma unroll
     for (int b = 0; b < kResBands; ++b) *(uint4*)(rows + (size_t)b * Lmax) = w;
   }
-}
-
-// ---- the residual block of a batch ------------------------------------------------------------------------------
-// "DSICR\0" | n, C, th, tw, tau, bands u32 | n x (smin i32, L u32, span_bytes u32) | n x bands u32 segment lengths |
-// per tile its span: C x L uint16 tables, then the 16 segment strings.
-// A tile's span is P = C + 16 pieces: table row c (2 L bytes of compact row c), then segment k (lengths[t][1 + k]
-// bytes at bytes + t (cap_z + 16 cap_seg) + cap_z + k cap_seg: the output of dsic_range_encode_seg_ws, whose z string
-// is the dummy and is dropped).
-__device__ __forceinline__ int64_t piece_len(int j, int C, int L, const int* lengths_t, int64_t cap_seg) {
-  return j < C ? 2 * (int64_t)L : clamp_len(lengths_t[1 + j - C], cap_seg);
-}
-__device__ __forceinline__ int table_width(const int* meta, int t, int Lmax) {
-  const int L = meta[4 * t + 1];
-  return L < 1 ? 0 : (L > Lmax ? Lmax : L);
-}
-
-__host__ __device__ inline int64_t res_body_offset(int n) {
-  return kResHead + (int64_t)kResRec * n + (int64_t)4 * kResBands * n;
-}
-
-// one workgroup: head, records, segment lengths, and the exclusive scan of the n P piece lengths into ws[2 ..];
-// ws[0] = block bytes, ws[1] = the coder's error word
-__global__ __launch_bounds__(256) void residual_pack_head_kernel(const int* __restrict__ lengths,
-                                                                 const int* __restrict__ meta,
-                                                                 const int* __restrict__ err, int n, int C, int th,
-                                                                 int tw, int tau, int Lmax, int64_t cap_seg,
-                                                                 long long* __restrict__ ws,
-                                                                 uint8_t* __restrict__ out) {
-  __shared__ long long lds4[4];
-  const int tid = threadIdx.x;
-  const int P = C + kResBands, S = 1 + kResBands;
-  if (tid < kResHead) {
-    const char magic[6] = {'D', 'S', 'I', 'C', 'R', 0};
-    const uint32_t f[6] = {(uint32_t)n, (uint32_t)C, (uint32_t)th, (uint32_t)tw, (uint32_t)tau, (uint32_t)kResBands};
-    if (tid < 6) out[tid] = (uint8_t)magic[tid];
-    else put_u32(out + tid, (tid - 6) & 3, f[(tid - 6) >> 2]);
-  }
-  for (int i = tid; i < kResRec * n; i += blockDim.x) {
-    const int t = i / kResRec, k = i - t * kResRec;
-    const int L = table_width(meta, t, Lmax);
-    uint32_t v;
-    switch (k >> 2) {
-      case 0: v = (uint32_t)meta[4 * t]; break;
-      case 1: v = (uint32_t)L; break;
-      default:
-        v = 0;
-        for (int j = 0; j < P; ++j) v += (uint32_t)piece_len(j, C, L, lengths + S * t, cap_seg);
-        break;
-    }
-    put_u32(out + kResHead + i, k & 3, v);
-  }
-  for (int i = tid; i < 4 * kResBands * n; i += blockDim.x) {
-    const int e = i >> 2, t = e / kResBands, j = e - t * kResBands;
-    put_u32(out + kResHead + (int64_t)kResRec * n + i, i & 3, (uint32_t)clamp_len(lengths[S * t + 1 + j], cap_seg));
-  }
-  long long carry = 0;
-  for (int s0 = 0; s0 < P * n; s0 += blockDim.x) {
-    const int s = s0 + tid, t = s / P;
-    const long long v = s < P * n ? piece_len(s - t * P, C, table_width(meta, t, Lmax), lengths + S * t, cap_seg) : 0;
-    long long tot;
-    const long long ex = block_exclusive_scan(v, lds4, &tot);
-    if (s < P * n) ws[2 + s] = carry + ex;
-    carry += tot;
-  }
-  if (tid == 0) {
-    ws[2 + P * n] = carry;
-    ws[0] = res_body_offset(n) + carry;
-    ws[1] = err ? *err : 0;
-  }
-}
-
-// blockIdx.y = piece (tile s / P), blockIdx.x = slice of it
-__global__ __launch_bounds__(256) void residual_pack_pieces_kernel(const uint8_t* __restrict__ bytes,
-                                                                   const int* __restrict__ lengths,
-                                                                   const int* __restrict__ meta,
-                                                                   const uint16_t* __restrict__ compact, int n, int C,
-                                                                   int Lmax, int64_t cap_z, int64_t cap_seg,
-                                                                   const long long* __restrict__ ws,
-                                                                   uint8_t* __restrict__ out) {
-  const int P = C + kResBands, S = 1 + kResBands;
-  const int s = blockIdx.y, t = s / P, j = s - t * P;
-  const int L = table_width(meta, t, Lmax);
-  const uint8_t* src = j < C ? (const uint8_t*)(compact + ((size_t)t * C + j) * Lmax)
-                             : bytes + (size_t)t * (cap_z + kResBands * cap_seg) + cap_z + (int64_t)(j - C) * cap_seg;
-  copy_bytes(out + res_body_offset(n) + ws[2 + s], src, piece_len(j, C, L, lengths + S * t, cap_seg), blockIdx.x,
-             gridDim.x);
 }
 
 }  // namespace dsic
@@ -325,13 +225,7 @@ extern "C" int dsic_residual_pack(const uint8_t* bytes, int64_t cap_z, int64_t c
                "residual_pack: bad capacities (cap_z=%lld cap_seg=%lld)", (long long)cap_z, (long long)cap_seg);
   DSIC_REQUIRE(((uintptr_t)bytes & 3) == 0 && ((uintptr_t)compact & 3) == 0,
                "residual_pack: bytes and compact must be 4-byte aligned");
-  hipStream_t st = (hipStream_t)stream;
-  long long* ws = (long long*)workspace;
-  hipLaunchKernelGGL(residual_pack_head_kernel, dim3(1), dim3(256), 0, st, lengths, meta, err, n, C, th, tw, tau, Lmax,
-                     cap_seg, ws, out);
-  const int rc = check_launch("residual_pack(head)");
-  if (rc) return rc;
-  hipLaunchKernelGGL(residual_pack_pieces_kernel, dim3(string_parts(cap_seg), (C + kResBands) * n), dim3(256), 0, st,
-                     bytes, lengths, meta, compact, n, C, Lmax, cap_z, cap_seg, (const long long*)ws, out);
-  return check_launch("residual_pack(pieces)");
+  return launch_pack<NarrowBlock>("residual_pack(head)", "residual_pack(pieces)", bytes, cap_z, cap_seg, lengths, meta,
+                                  nullptr, compact, nullptr, err, n, C, th, tw, tau, Lmax, cap_seg, workspace, out,
+                                  (hipStream_t)stream);
 }

@@ -14,7 +14,7 @@
 // (tile, band), 16 row bands as 16 segments); lo travels raw as k bit planes of C th tw / 8 bytes, bit b of byte i of
 // plane j being bit j of lo of sample 8 i + b in [C][th][tw] order: the 64-bit ballot of 64 consecutive samples,
 // little endian.  Everything here is integer arithmetic or byte movement and memory-bound.
-#include "byte_movers.h"
+#include "residual_block.h"
 #include "tile_grid.h"
 #include "u16_scale.h"
 
@@ -23,11 +23,7 @@ namespace dsic {
 constexpr int kW16Rows = 16;    // rows of one tile per workgroup (th is a multiple of 16)
 constexpr int kW16Bins = 512;   // histogram bins per (tile, band): bin hi + 255
 constexpr int kW16Top = 255;    // |hi| <= 255
-constexpr int kW16Bands = 16;   // row bands per plane = segments per tile
-constexpr int kW16Planes = 9;   // the largest shift: Q16(0) = 65535 <= 255 << 9
-constexpr int kW16Lmax = 512;   // rows of the coder tables: residual.hip res_lmax(0)
-constexpr int kW16Head = 30;    // "DSICW\0" | n, C, th, tw, tau, bands u32
-constexpr int kW16Rec = 16;     // smin i32, L u32, k u32, span_bytes u32
+constexpr int kW16Planes = WideBlock::slots;  // the largest shift: Q16(0) = 65535 <= 255 << 9
 
 __host__ __device__ inline int w16_Q(int tau) { return (65535 + tau) / (2 * tau + 1); }
 __host__ __device__ inline int w16_shift(int m) {
@@ -35,14 +31,6 @@ __host__ __device__ inline int w16_shift(int m) {
   while (k < kW16Planes && m > (kW16Top << k)) ++k;
   return k;
 }
-__device__ __forceinline__ int w16_planes(int k) { return k < 0 ? 0 : (k > kW16Planes ? kW16Planes : k); }
-
-__device__ __forceinline__ int wave_max_i32(int v) {
-#pragma unroll
-  for (int o = 32; o >= 1; o >>= 1) v = max(v, __shfl_xor(v, o, 64));
-  return v;
-}
-
 // img uint16 [H][W][C] at any 2-byte alignment, x_hat float32 [n][C][th][tw] of tiles first .. first + n - 1 of the
 // grid -> q int32 [n][C][th][tw] and maxabs int32 [n] (max= |q|: an integer maximum, so no order shows; the caller
 // zeroes it).  A lane takes 4 pixels of a tile row as the gather does, but reads only pixels the tile owns, which lie
@@ -100,7 +88,7 @@ __global__ __launch_bounds__(256) void quantize_u16_kernel(const uint16_t* __res
       *(int4*)(qt + c * cplane + e) = make_int4(qv[0], qv[1], qv[2], qv[3]);
     }
   }
-  m = wave_max_i32(m);
+  m = wave_max(m);
   if ((threadIdx.x & 63) == 0 && m > 0) atomicMax(maxabs + blockIdx.y, m);
 }
 
@@ -152,97 +140,6 @@ __global__ __launch_bounds__(256) void split_u16_kernel(const int* __restrict__ 
   }
 }
 
-// ---- the wide residual block of a batch ---------------------------------------------------------------------------
-// "DSICW\0" | n, C, th, tw, tau, bands u32 | n x (smin i32, L u32, k u32, span_bytes u32) | n x 16 u32 segment lengths |
-// per tile its span: C x L uint16 tables | k planes of C th tw / 8 bytes | the 16 segment strings.
-// A tile's span is P = C + 1 + 16 pieces: table row c (2 L bytes of compact row c), the planes (k pb bytes, the first
-// k of the tile's 9 plane slots, which lie back to back), then segment j as residual.hip's pack takes it from the
-// output of dsic_range_encode_seg_ws.
-__device__ __forceinline__ int64_t w16_piece_len(int j, int C, int L, int k, int64_t pb, const int* lengths_t,
-                                                 int64_t cap_seg) {
-  return j < C ? 2 * (int64_t)L : (j == C ? k * pb : clamp_len(lengths_t[j - C], cap_seg));
-}
-__device__ __forceinline__ int w16_width(const int* meta, int t) {
-  const int L = meta[4 * t + 1];
-  return L < 1 ? 0 : (L > kW16Lmax ? kW16Lmax : L);
-}
-__host__ __device__ inline int64_t w16_body_offset(int n) {
-  return kW16Head + (int64_t)kW16Rec * n + (int64_t)4 * kW16Bands * n;
-}
-
-// one workgroup: head, records, segment lengths, and the exclusive scan of the n P piece lengths into ws[2 ..];
-// ws[0] = block bytes, ws[1] = the coder's error word
-__global__ __launch_bounds__(256) void pack_u16_head_kernel(const int* __restrict__ lengths, const int* __restrict__ meta,
-                                                            const int* __restrict__ kk, const int* __restrict__ err,
-                                                            int n, int C, int th, int tw, int tau, int64_t cap_seg,
-                                                            long long* __restrict__ ws, uint8_t* __restrict__ out) {
-  __shared__ long long lds4[4];
-  const int tid = threadIdx.x;
-  const int P = C + 1 + kW16Bands, S = 1 + kW16Bands;
-  const int64_t pb = (int64_t)C * th * tw / 8;
-  if (tid < kW16Head) {
-    const char magic[6] = {'D', 'S', 'I', 'C', 'W', 0};
-    const uint32_t f[6] = {(uint32_t)n, (uint32_t)C, (uint32_t)th, (uint32_t)tw, (uint32_t)tau, (uint32_t)kW16Bands};
-    if (tid < 6) out[tid] = (uint8_t)magic[tid];
-    else put_u32(out + tid, (tid - 6) & 3, f[(tid - 6) >> 2]);
-  }
-  for (int i = tid; i < kW16Rec * n; i += blockDim.x) {
-    const int t = i / kW16Rec, b = i - t * kW16Rec;
-    const int L = w16_width(meta, t), k = w16_planes(kk[t]);
-    uint32_t v;
-    switch (b >> 2) {
-      case 0: v = (uint32_t)meta[4 * t]; break;
-      case 1: v = (uint32_t)L; break;
-      case 2: v = (uint32_t)k; break;
-      default:
-        v = 0;
-        for (int j = 0; j < P; ++j) v += (uint32_t)w16_piece_len(j, C, L, k, pb, lengths + S * t, cap_seg);
-        break;
-    }
-    put_u32(out + kW16Head + i, b & 3, v);
-  }
-  for (int i = tid; i < 4 * kW16Bands * n; i += blockDim.x) {
-    const int e = i >> 2, t = e / kW16Bands, j = e - t * kW16Bands;
-    put_u32(out + kW16Head + (int64_t)kW16Rec * n + i, i & 3, (uint32_t)clamp_len(lengths[S * t + 1 + j], cap_seg));
-  }
-  long long carry = 0;
-  for (int s0 = 0; s0 < P * n; s0 += blockDim.x) {
-    const int s = s0 + tid, t = s / P;
-    const long long v =
-        s < P * n ? w16_piece_len(s - t * P, C, w16_width(meta, t), w16_planes(kk[t]), pb, lengths + S * t, cap_seg) : 0;
-    long long tot;
-    const long long ex = block_exclusive_scan(v, lds4, &tot);
-    if (s < P * n) ws[2 + s] = carry + ex;
-    carry += tot;
-  }
-  if (tid == 0) {
-    ws[2 + P * n] = carry;
-    ws[0] = w16_body_offset(n) + carry;
-    ws[1] = err ? *err : 0;
-  }
-}
-
-// blockIdx.y = piece (tile s / P), blockIdx.x = slice of it
-__global__ __launch_bounds__(256) void pack_u16_pieces_kernel(const uint8_t* __restrict__ bytes,
-                                                              const int* __restrict__ lengths,
-                                                              const int* __restrict__ meta, const int* __restrict__ kk,
-                                                              const uint16_t* __restrict__ compact,
-                                                              const uint8_t* __restrict__ planes, int n, int C, int th,
-                                                              int tw, int64_t cap_z, int64_t cap_seg,
-                                                              const long long* __restrict__ ws,
-                                                              uint8_t* __restrict__ out) {
-  const int P = C + 1 + kW16Bands, S = 1 + kW16Bands;
-  const int s = blockIdx.y, t = s / P, j = s - t * P;
-  const int64_t pb = (int64_t)C * th * tw / 8;
-  const uint8_t* src =
-      j < C ? (const uint8_t*)(compact + ((size_t)t * C + j) * kW16Lmax)
-            : (j == C ? planes + (size_t)t * kW16Planes * pb
-                      : bytes + (size_t)t * (cap_z + kW16Bands * cap_seg) + cap_z + (int64_t)(j - C - 1) * cap_seg);
-  copy_bytes(out + w16_body_offset(n) + ws[2 + s], src,
-             w16_piece_len(j, C, w16_width(meta, t), w16_planes(kk[t]), pb, lengths + S * t, cap_seg), blockIdx.x,
-             gridDim.x);
-}
-
 // hi float32 [n][C][th][tw] (the decoded high parts), the uploaded stream bytes `blob` of `total` bytes in which tile
 // t's k[t] planes lie back to back from byte plane_off[t] (any alignment: read in place, a byte per lane and plane) ->
 // q float32 [n][C][th][tw] = hi 2^k + lo, exact since |q| < 2^24, clamped to +-Q16: a forged record can join to 131 071,
@@ -253,7 +150,7 @@ __global__ __launch_bounds__(256) void join_u16_kernel(const float* __restrict__
                                                        const int* __restrict__ kk, int64_t pb, int Q16,
                                                        float* __restrict__ q) {
   const int t = blockIdx.y;
-  const int k = w16_planes(kk[t]);
+  const int k = tile_planes<WideBlock>(kk, t);
   const long long off = plane_off[t];
   const bool inside = off >= 0 && off + (long long)k * pb <= total;
   const float* ht = hi + (size_t)t * pb * 8;
@@ -334,18 +231,10 @@ extern "C" int dsic_residual_pack_u16(const uint8_t* bytes, int64_t cap_z, int64
   DSIC_REQUIRE(((uintptr_t)bytes & 3) == 0 && ((uintptr_t)compact & 3) == 0 && ((uintptr_t)planes & 7) == 0 &&
                    ((uintptr_t)workspace & 7) == 0,
                "residual_pack_u16: bytes and compact must be 4-byte, planes and workspace 8-byte aligned");
-  hipStream_t st = (hipStream_t)stream;
-  long long* ws = (long long*)workspace;
-  hipLaunchKernelGGL(pack_u16_head_kernel, dim3(1), dim3(256), 0, st, lengths, meta, k, err, n, C, th, tw, tau, cap_seg,
-                     ws, out);
-  const int rc = check_launch("residual_pack_u16(head)");
-  if (rc) return rc;
-  const int64_t longest = (int64_t)kW16Planes * C * th * tw / 8;
-  hipLaunchKernelGGL(pack_u16_pieces_kernel, dim3(string_parts(cap_seg > longest ? cap_seg : longest),
-                                                  (C + 1 + kW16Bands) * n),
-                     dim3(256), 0, st, bytes, lengths, meta, k, compact, (const uint8_t*)planes, n, C, th, tw, cap_z,
-                     cap_seg, (const long long*)ws, out);
-  return check_launch("residual_pack_u16(pieces)");
+  const int64_t longest = (int64_t)WideBlock::slots * C * th * tw / 8;
+  return launch_pack<WideBlock>("residual_pack_u16(head)", "residual_pack_u16(pieces)", bytes, cap_z, cap_seg, lengths,
+                                meta, k, compact, (const uint8_t*)planes, err, n, C, th, tw, tau, WideBlock::lmax,
+                                cap_seg > longest ? cap_seg : longest, workspace, out, (hipStream_t)stream);
 }
 
 extern "C" int dsic_residual_join_u16(const float* hi, const uint8_t* blob, int64_t total, const int64_t* plane_off,

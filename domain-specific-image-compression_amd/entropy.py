@@ -619,7 +619,7 @@ def _decode_selected(model, images, parts, shape_y, shape_z, what, Lmax=None, ri
     array `ride` (codec's tile numbers).  The device spreads the strings at custom_decompress's strides (_upload_strings) and decodes with Lmax
     (default: _default_lmax over these images).  Returns (g_s's output, not yet clamped; the padded string bytes
     uploaded; the device copy of ride).
-    residual (codec's near-lossless streams): the spec of residual.decode_q or residual16.decode_q, whose spans lie in `parts` beside the
+    residual (codec's near-lossless streams): residual.decode_spec's dict, whose spans lie in `parts` beside the
     strings; its control words travel behind ride in the same copy, and the tuple gains the decoded q planes."""
     dev = next(model.parameters()).device
     n = len(images)
@@ -635,9 +635,8 @@ def _decode_selected(model, images, parts, shape_y, shape_z, what, Lmax=None, ri
     if nseg:
         block[6 * n:].view(np.int32)[:nseg] = np.asarray(seg_lengths, dtype=np.int32).reshape(nseg)
     block[6 * n:].view(np.int32)[nseg:nseg + ride.size] = ride
-    if residual is not None:                       # a spec with shifts "k" is the wide residual of a uint16 stream
-        from . import residual as _residual, residual16 as _residual16
-        layer = _residual16 if "k" in residual else _residual
+    if residual is not None:
+        layer = residual["layer"]                  # the module the spec names: residual or residual16
         block = np.concatenate([block, layer.control_words(residual)])
     d_blob, total, d_block = _upload_padded(parts, block, dev)
     d_block = d_block.view(torch.int64)

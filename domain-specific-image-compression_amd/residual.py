@@ -22,6 +22,7 @@ The residual block of a batch (little endian):
 """
 from __future__ import annotations
 
+import collections
 import operator
 import struct
 
@@ -60,68 +61,130 @@ def table_lmax(tau) -> int:
     return (2 * q_max(tau) + 1 + 7) // 8 * 8
 
 
+# ---- one block format, two widths: this module's DSICR block and residual16's DSICW block -------------------------
+# magic | n, C, th, tw, tau, bands u32 | n x (smin i32, L u32, [k u32,] span_bytes u32) | n x 16 u32 segment lengths |
+# per tile its span: C x L uint16 tables | [k planes of C th tw / 8 bytes] | the 16 segment strings
+# rec: the record's struct; name: the block in messages; top(tau): the bound on the support, |symbol| <= top; planes:
+# the largest k, 0 for a block whose records carry no k and whose spans no planes
+BlockFormat = collections.namedtuple("BlockFormat", "magic rec name top planes")
+FORMAT = BlockFormat(MAGIC, _REC, "residual", q_max, 0)
+
+
+def _bytes_of(v, dtype):
+    return v if isinstance(v, (bytes, bytearray, memoryview)) else np.ascontiguousarray(v, dtype=dtype).tobytes()
+
+
+def format_head_bytes(fmt, n) -> int:
+    return _HEAD.size + (fmt.rec.size + 4 * BANDS) * n
+
+
+def format_pack_block(fmt, C, th, tw, tau, tiles) -> bytes:
+    """A block of a batch (pure Python).  tiles: per tile (smin, tables, strings), with planes (smin, tables, k, planes,
+    strings)."""
+    recs, segs, spans = [], [], []
+    pb = C * th * tw // 8
+    for smin, tables, *kp, strings in tiles:
+        tb, (k, pl) = _bytes_of(tables, "<u2"), (kp[0], _bytes_of(kp[1], np.uint8)) if fmt.planes else (0, b"")
+        if len(strings) != BANDS or len(tb) % (2 * C) or len(pl) != k * pb:
+            raise ValueError(f"pack_block: a tile takes {C} tables of one width" +
+                             (f", k planes of {pb} bytes" if fmt.planes else "") + f" and {BANDS} strings")
+        span = bytes(tb) + bytes(pl) + b"".join(bytes(s) for s in strings)
+        recs.append(fmt.rec.pack(int(smin), len(tb) // (2 * C), *([int(k)] if fmt.planes else []), len(span)))
+        segs.append(struct.pack(f"<{BANDS}I", *[len(s) for s in strings]))
+        spans.append(span)
+    return b"".join([_HEAD.pack(fmt.magic, len(tiles), C, th, tw, tau, BANDS)] + recs + segs + spans)
+
+
+def format_read_block_head(fmt, read_at, off, size, n, C, th, tw, tau, what):
+    """The head, records and segment lengths of the block that fills bytes [off, off + size) behind read_at(offset,
+    count); the spans are not read.  n, C, th, tw, tau: what the stream's head says the block must hold.  Returns per
+    tile {"r_off", "r_len", "r_smin", "r_L", "r_segs"} and, with planes, "r_k": the absolute offset and length of its
+    span, its support, its shift, and the lengths of its 16 strings, which follow the span's C * r_L table entries and
+    r_k planes back to back.  ValueError where the block contradicts the head, is truncated, or a record cannot be a
+    tile's."""
+    name = fmt.name
+    head = read_at(off, min(size, _HEAD.size))
+    if len(head) < _HEAD.size or bytes(head[:6]) != fmt.magic:
+        raise ValueError(f"{what}: not a {name} block" if bytes(head[:6]) != fmt.magic[:len(head)]
+                         else f"{what}: truncated {name} block")
+    _, bn, bC, bth, btw, btau, bands = _HEAD.unpack(head)
+    if bands != BANDS:
+        raise ValueError(f"{what}: {name} block with {bands} bands, this reader knows {BANDS}")
+    if (bn, bC, bth, btw, btau) != (n, C, th, tw, tau):
+        raise ValueError(f"{what}: {name} block of (n, C, th, tw, tau) = {(bn, bC, bth, btw, btau)}, the stream's "
+                         f"head says {(n, C, th, tw, tau)}")
+    if size < format_head_bytes(fmt, n):
+        raise ValueError(f"{what}: truncated {name} block")
+    recs = list(fmt.rec.iter_unpack(read_at(off + _HEAD.size, fmt.rec.size * n)))
+    flat = struct.unpack(f"<{BANDS * n}I", read_at(off + _HEAD.size + fmt.rec.size * n, 4 * BANDS * n))
+    Q, pb, pos, out = fmt.top(tau), C * th * tw // 8, off + format_head_bytes(fmt, n), []
+    for t, rec in enumerate(recs):
+        smin, L, k, span = rec if fmt.planes else (rec[0], rec[1], 0, rec[2])
+        segs = list(flat[t * BANDS:(t + 1) * BANDS])
+        if k > fmt.planes:
+            raise ValueError(f"{what}: residual shift k={k} of tile {t} (0 .. {fmt.planes})")
+        if fmt.planes and (L < 1 or L > 2 * Q + 1):
+            raise ValueError(f"{what}: residual table width L={L} of tile {t} (1 .. {2 * Q + 1})")
+        if L < 1 or L > 2 * Q + 1 or smin < -Q or smin + L - 1 > Q:
+            raise ValueError(f"{what}: residual support [{smin}, {smin + L}) of tile {t} leaves [-{Q}, {Q}]")
+        if span != 2 * C * L + k * pb + sum(segs):
+            raise ValueError(f"{what}: residual tile {t}: tables{', planes' if fmt.planes else ''} and segment lengths "
+                             "do not add up to its span")
+        out.append({"r_off": pos, "r_len": span, "r_smin": smin, "r_L": L, "r_segs": segs})
+        if fmt.planes:
+            out[-1]["r_k"] = k
+        pos += span
+    if pos != off + size:
+        raise ValueError(f"{what}: truncated or oversized {name} block")
+    return out
+
+
+def format_check_tables(fmt, buf, C, L, tau, what):
+    """The C tables of a span (2 C L bytes): c[0] = 0, strictly increasing, L <= 2 top + 1; else ValueError."""
+    if L < 1 or L > 2 * fmt.top(tau) + 1 or len(buf) != 2 * C * L:
+        raise ValueError(f"{what}: residual tables of width {L}" + ("" if fmt.planes else f" for max_error={tau}"))
+    t = np.frombuffer(buf, dtype="<u2").reshape(C, L).astype(np.int64)
+    if (t[:, 0] != 0).any() or (np.diff(t, axis=1) <= 0).any():
+        raise ValueError(f"{what}: a residual table does not start at 0 or is not strictly increasing")
+
+
+def decode_spec(layer, recs, C, th, tw, tau, at, tables_of) -> dict:
+    """What layer.control_words and layer.decode_q take for one decode batch (layer: this module or residual16).  recs:
+    the tiles' index records; at(offset, length): where a stream range lies in the upload; tables_of(rec): the tables
+    of its span as they arrived, which are checked here, before anything is uploaded."""
+    fmt = layer.FORMAT
+    for r in recs:
+        format_check_tables(fmt, tables_of(r), C, r["r_L"], tau, "DSICI stream")
+    pb = C * th * tw // 8
+    tables = [(at(r["r_off"], r["r_len"]), 2 * C * r["r_L"]) for r in recs]
+    ks = [r.get("r_k", 0) for r in recs]
+    spec = {"layer": layer, "C": C, "th": th, "tw": tw, "tau": tau, "smin": [r["r_smin"] for r in recs],
+            "L": [r["r_L"] for r in recs], "segs": [r["r_segs"] for r in recs],
+            "desc": [(a, tb, a + tb + k * pb, sum(r["r_segs"])) for (a, tb), k, r in zip(tables, ks, recs)]}
+    if fmt.planes:
+        spec.update(k=ks, plane_off=[a + tb for a, tb in tables])
+    return spec
+
+
 def head_bytes(n) -> int:
     """Bytes of a block in front of its first span: head, records, segment lengths."""
-    return _HEAD.size + (_REC.size + 4 * BANDS) * n
+    return format_head_bytes(FORMAT, n)
 
 
 def pack_block(C, th, tw, tau, tiles) -> bytes:
     """The residual block of a batch (pure Python).  tiles: per tile (smin, tables, strings): tables a uint16 array
     [C][L] (or its bytes), strings the 16 segment strings."""
-    recs, segs, spans = [], [], []
-    for smin, tables, strings in tiles:
-        tb = tables if isinstance(tables, (bytes, bytearray, memoryview)) else np.ascontiguousarray(
-            tables, dtype="<u2").tobytes()
-        if len(strings) != BANDS or len(tb) % (2 * C):
-            raise ValueError(f"pack_block: a tile takes {C} tables of one width and {BANDS} strings")
-        span = bytes(tb) + b"".join(bytes(s) for s in strings)
-        recs.append(_REC.pack(int(smin), len(tb) // (2 * C), len(span)))
-        segs.append(struct.pack(f"<{BANDS}I", *[len(s) for s in strings]))
-        spans.append(span)
-    return b"".join([_HEAD.pack(MAGIC, len(tiles), C, th, tw, tau, BANDS)] + recs + segs + spans)
+    return format_pack_block(FORMAT, C, th, tw, tau, tiles)
 
 
 def read_block_head(read_at, off, size, n, C, th, tw, tau, what="DSICI stream"):
-    """The head, records and segment lengths of the residual block that fills bytes [off, off + size) behind
-    read_at(offset, count); the spans are not read.  n, C, th, tw, tau: what the stream's head says the block must
-    hold.  Returns per tile {"r_off", "r_len", "r_smin", "r_L", "r_segs"}: the absolute offset and length of its span,
-    its support, and the lengths of its 16 strings, which follow the span's C * r_L table entries back to back.
-    ValueError where the block contradicts the head, is truncated, or a record cannot be a tile's."""
-    head = read_at(off, min(size, _HEAD.size))
-    if len(head) < _HEAD.size or bytes(head[:6]) != MAGIC:
-        raise ValueError(f"{what}: not a residual block" if bytes(head[:6]) != MAGIC[:len(head)]
-                         else f"{what}: truncated residual block")
-    _, bn, bC, bth, btw, btau, bands = _HEAD.unpack(head)
-    if bands != BANDS:
-        raise ValueError(f"{what}: residual block with {bands} bands, this reader knows {BANDS}")
-    if (bn, bC, bth, btw, btau) != (n, C, th, tw, tau):
-        raise ValueError(f"{what}: residual block of (n, C, th, tw, tau) = {(bn, bC, bth, btw, btau)}, the stream's "
-                         f"head says {(n, C, th, tw, tau)}")
-    if size < head_bytes(n):
-        raise ValueError(f"{what}: truncated residual block")
-    recs = list(_REC.iter_unpack(read_at(off + _HEAD.size, _REC.size * n)))
-    flat = struct.unpack(f"<{BANDS * n}I", read_at(off + _HEAD.size + _REC.size * n, 4 * BANDS * n))
-    Q, pos, out = q_max(tau), off + head_bytes(n), []
-    for t, (smin, L, span) in enumerate(recs):
-        segs = list(flat[t * BANDS:(t + 1) * BANDS])
-        if L < 1 or L > 2 * Q + 1 or smin < -Q or smin + L - 1 > Q:
-            raise ValueError(f"{what}: residual support [{smin}, {smin + L}) of tile {t} leaves [-{Q}, {Q}]")
-        if span != 2 * C * L + sum(segs):
-            raise ValueError(f"{what}: residual tile {t}: tables and segment lengths do not add up to its span")
-        out.append({"r_off": pos, "r_len": span, "r_smin": smin, "r_L": L, "r_segs": segs})
-        pos += span
-    if pos != off + size:
-        raise ValueError(f"{what}: truncated or oversized residual block")
-    return out
+    """format_read_block_head for the residual block: per tile {"r_off", "r_len", "r_smin", "r_L", "r_segs"}."""
+    return format_read_block_head(FORMAT, read_at, off, size, n, C, th, tw, tau, what)
 
 
 def check_tables(buf, C, L, tau, what="DSICI stream"):
     """The C tables of a span (2 C L bytes): c[0] = 0, strictly increasing, L <= 2 Q + 1; else ValueError."""
-    if L < 1 or L > 2 * q_max(tau) + 1 or len(buf) != 2 * C * L:
-        raise ValueError(f"{what}: residual tables of width {L} for max_error={tau}")
-    t = np.frombuffer(buf, dtype="<u2").reshape(C, L).astype(np.int64)
-    if (t[:, 0] != 0).any() or (np.diff(t, axis=1) <= 0).any():
-        raise ValueError(f"{what}: a residual table does not start at 0 or is not strictly increasing")
+    format_check_tables(FORMAT, buf, C, L, tau, what)
 
 
 def _shape(tiles, what):
@@ -260,3 +323,6 @@ def stitch_window_u8(x_hat, q, tau, ids, img, H, W, C, th, tw, y0, x0, h, w):
     _lib.check(_lib.load().dsic_tile_stitch_window_u8_res(_p(x_hat), _p(q), tau, _p(ids), x_hat.shape[0], _p(img), H,
                                                           W, C, th, tw, y0, x0, h, w, _stream()),
                "tile_stitch_window_u8_res")
+
+
+OUT, stitch_window = "u8", stitch_window_u8    # what codec._assemble_window asks of a layer: its image, and its stitch

@@ -44,8 +44,8 @@ LMAX = 512                         # rows of the coder tables: residual.table_lm
 PLANES = 9                         # the largest shift
 MAX_TOLERANCE = 32767
 MAX_TILES = _residual.MAX_TILES
-_HEAD = struct.Struct("<6s6I")     # magic, n, C, th, tw, tau, bands
 _REC = struct.Struct("<iIII")      # per tile: smin, L, k, span_bytes
+FORMAT = _residual.BlockFormat(MAGIC, _REC, "wide residual", lambda tau: TOP, PLANES)
 
 
 def check_tolerance(tolerance, what) -> int:
@@ -78,76 +78,25 @@ def plane_bytes(C, th, tw) -> int:
 
 def head_bytes(n) -> int:
     """Bytes of a block in front of its first span: head, records, segment lengths."""
-    return _HEAD.size + (_REC.size + 4 * BANDS) * n
+    return _residual.format_head_bytes(FORMAT, n)
 
 
 def pack_block(C, th, tw, tau, tiles) -> bytes:
     """The wide residual block of a batch (pure Python).  tiles: per tile (smin, tables, k, planes, strings): tables a
     uint16 array [C][L] (or its bytes), planes the k bit planes back to back (bytes, or a uint8 array), strings the 16
     segment strings."""
-    recs, segs, spans = [], [], []
-    pb = plane_bytes(C, th, tw)
-    for smin, tables, k, planes, strings in tiles:
-        tb = tables if isinstance(tables, (bytes, bytearray, memoryview)) else np.ascontiguousarray(
-            tables, dtype="<u2").tobytes()
-        pl = planes if isinstance(planes, (bytes, bytearray, memoryview)) else np.ascontiguousarray(
-            planes, dtype=np.uint8).tobytes()
-        if len(strings) != BANDS or len(tb) % (2 * C) or len(pl) != k * pb:
-            raise ValueError(f"pack_block: a tile takes {C} tables of one width, k planes of {pb} bytes and {BANDS} "
-                             "strings")
-        span = bytes(tb) + bytes(pl) + b"".join(bytes(s) for s in strings)
-        recs.append(_REC.pack(int(smin), len(tb) // (2 * C), int(k), len(span)))
-        segs.append(struct.pack(f"<{BANDS}I", *[len(s) for s in strings]))
-        spans.append(span)
-    return b"".join([_HEAD.pack(MAGIC, len(tiles), C, th, tw, tau, BANDS)] + recs + segs + spans)
+    return _residual.format_pack_block(FORMAT, C, th, tw, tau, tiles)
 
 
 def read_block_head(read_at, off, size, n, C, th, tw, tau, what="DSICI stream"):
-    """The head, records and segment lengths of the wide residual block that fills bytes [off, off + size) behind
-    read_at(offset, count); the spans are not read.  n, C, th, tw, tau: what the stream's head says the block must
-    hold.  Returns per tile {"r_off", "r_len", "r_smin", "r_L", "r_k", "r_segs"}: the absolute offset and length of its
-    span, the support of hi, its shift, and the lengths of its 16 strings, which follow the span's C * r_L table entries
-    and r_k planes back to back.  ValueError where the block contradicts the head, is truncated, or a record cannot be a
-    tile's."""
-    head = read_at(off, min(size, _HEAD.size))
-    if len(head) < _HEAD.size or bytes(head[:6]) != MAGIC:
-        raise ValueError(f"{what}: not a wide residual block" if bytes(head[:6]) != MAGIC[:len(head)]
-                         else f"{what}: truncated wide residual block")
-    _, bn, bC, bth, btw, btau, bands = _HEAD.unpack(head)
-    if bands != BANDS:
-        raise ValueError(f"{what}: wide residual block with {bands} bands, this reader knows {BANDS}")
-    if (bn, bC, bth, btw, btau) != (n, C, th, tw, tau):
-        raise ValueError(f"{what}: wide residual block of (n, C, th, tw, tau) = {(bn, bC, bth, btw, btau)}, the "
-                         f"stream's head says {(n, C, th, tw, tau)}")
-    if size < head_bytes(n):
-        raise ValueError(f"{what}: truncated wide residual block")
-    recs = list(_REC.iter_unpack(read_at(off + _HEAD.size, _REC.size * n)))
-    flat = struct.unpack(f"<{BANDS * n}I", read_at(off + _HEAD.size + _REC.size * n, 4 * BANDS * n))
-    pb, pos, out = plane_bytes(C, th, tw), off + head_bytes(n), []
-    for t, (smin, L, k, span) in enumerate(recs):
-        segs = list(flat[t * BANDS:(t + 1) * BANDS])
-        if k > PLANES:
-            raise ValueError(f"{what}: residual shift k={k} of tile {t} (0 .. {PLANES})")
-        if L < 1 or L > 2 * TOP + 1:
-            raise ValueError(f"{what}: residual table width L={L} of tile {t} (1 .. {2 * TOP + 1})")
-        if smin < -TOP or smin + L - 1 > TOP:
-            raise ValueError(f"{what}: residual support [{smin}, {smin + L}) of tile {t} leaves [-{TOP}, {TOP}]")
-        if span != 2 * C * L + k * pb + sum(segs):
-            raise ValueError(f"{what}: residual tile {t}: tables, planes and segment lengths do not add up to its span")
-        out.append({"r_off": pos, "r_len": span, "r_smin": smin, "r_L": L, "r_k": k, "r_segs": segs})
-        pos += span
-    if pos != off + size:
-        raise ValueError(f"{what}: truncated or oversized wide residual block")
-    return out
+    """residual.format_read_block_head for the wide residual block: per tile {"r_off", "r_len", "r_smin", "r_L", "r_k",
+    "r_segs"}, the support being that of hi and r_k the tile's shift."""
+    return _residual.format_read_block_head(FORMAT, read_at, off, size, n, C, th, tw, tau, what)
 
 
 def check_tables(buf, C, L, what="DSICI stream"):
     """The C tables of a span (2 C L bytes): c[0] = 0, strictly increasing, L <= 511; else ValueError."""
-    if L < 1 or L > 2 * TOP + 1 or len(buf) != 2 * C * L:
-        raise ValueError(f"{what}: residual tables of width {L}")
-    t = np.frombuffer(buf, dtype="<u2").reshape(C, L).astype(np.int64)
-    if (t[:, 0] != 0).any() or (np.diff(t, axis=1) <= 0).any():
-        raise ValueError(f"{what}: a residual table does not start at 0 or is not strictly increasing")
+    _residual.format_check_tables(FORMAT, buf, C, L, None, what)
 
 
 def quantize(img, x_hat, H, W, th, tw, lohi, tau, first):
@@ -249,3 +198,6 @@ def stitch_window_u16(x_hat, q, tau, ids, img, H, W, C, th, tw, y0, x0, h, w, lo
     _lib.check(_lib.load().dsic_tile_stitch_window_u16_res(_p(x_hat), _p(q), tau, _p(ids), x_hat.shape[0], _p(img), H,
                                                            W, C, th, tw, y0, x0, h, w, lohi, _stream()),
                "tile_stitch_window_u16_res")
+
+
+OUT, stitch_window = "u16", stitch_window_u16
