@@ -1,6 +1,7 @@
 // Device helpers shared by the byte movers of image_codec.hip and residual.hip: 16-byte loads from any address, a
 // string copy split over workgroups, the workgroup prefix sum that turns string lengths into offsets, and the
-// little-endian field writers of the container heads.
+// little-endian field writers of the container heads; and the workgroup counts of their launches.  The chunk walk of
+// the HWC outputs is hwc_chunks.h.  Whether two buffers meet is buffers_apart of common.h.
 #pragma once
 #include "common.h"
 
@@ -69,6 +70,12 @@ __device__ __forceinline__ int64_t clamp_len(int v, int64_t cap) { return v < 0 
 static inline int string_parts(int64_t max_len) {
   const int64_t p = (max_len + 16 * 256 - 1) / (16 * 256);
   return (int)(p < 1 ? 1 : (p > 8 ? 8 : p));
+}
+
+// workgroups of a flat grid-stride pass over `units` 16-byte units, one unit per thread and pass
+static inline int flat_blocks(int64_t units) {
+  const int64_t b = (units + 255) / 256;
+  return (int)(b < 1 ? 1 : (b > 8192 ? 8192 : b));
 }
 
 }  // namespace dsic

@@ -2,7 +2,9 @@
 // batch of coder outputs to one DSIC2 container and back.  All of it is byte movement: every kernel is
 // memory-bound and works in 16-byte units (dwordx4 loads where the source is aligned, alignbyte funnels of
 // dword loads where it is not, dwordx4 stores on aligned destination chunks, byte stores only at the ragged
-// ends of a segment).  One workgroup covers a block of rows of one tile, or a slice of one string.
+// ends of a segment).  One workgroup covers a block of rows of one tile, or a slice of one string.  The stitch and
+// the blend finish into an HWC image stand here once for uint8 and uint16 (stitch_hwc_kernel, blend_finish_hwc_kernel
+// over the chunk walk of hwc_chunks.h and a value policy per width); image_u16.hip's exports launch them.
 //
 // Tile geometry (codec.tile_grid): Hp = ceil16(H), tiles_y = ceil(Hp / th), origin of tile row i =
 // min(i*th, Hp - th); tile row i owns padded rows [i*th, min((i+1)*th, Hp)) (the last row of tiles shifts
@@ -14,7 +16,8 @@
 // tile's weight ramps up as (2k+1)/(2O), over [a(i+1), a(i+1) + O) it ramps down as (2(O-1-k)+1)/(2O), elsewhere in
 // the support it is 1: at every position the weights of at most two tiles per axis sum to 1.  O = 0 is the grid above.
 #include "byte_movers.h"
-#include "tile_grid.h"
+#include "hwc_chunks.h"
+#include "hwc_launch.h"
 
 namespace dsic {
 
@@ -103,54 +106,75 @@ __global__ __launch_bounds__(256) void stitch_f32_kernel(const float* __restrict
   }
 }
 
-// tiles [n][C][th][tw] -> p = (uint8)(clamp(x,0,1) * 255) into the uint8 HWC window image.  RES (near-lossless
-// streams, residual.hip): q [n][C][th][tw] holds the tile's integer residual steps and the pixel is
-// clamp(p + q * s, 0, 255), s = 2 tau + 1.
-template <bool RES>
-__global__ __launch_bounds__(256) void stitch_u8_kernel(const float* __restrict__ tiles, uint8_t* __restrict__ img,
-                                                        Grid g, int C, int first, const int* __restrict__ ids,
-                                                        Clip w, const float* __restrict__ q, int s) {
+__device__ __forceinline__ float min1(float v) { return v > 1.f ? 1.f : v; }
+
+// What the width of an HWC output decides: the value of a decoded sample x of channel c (stitch), that of a blended
+// canvas sum v (finish), and the range a value with its residual is clamped to.  Passed to the kernels by value.
+template <typename T>
+struct HwcValue;
+template <>
+struct HwcValue<uint8_t> {  // p = (uint8)(clamp(x, 0, 1) * 255)
+  static constexpr int kMax = 255;
+  __device__ __forceinline__ uint8_t stitch(float x, int) const { return (uint8_t)(clamp01(x) * 255.0f); }
+  __device__ __forceinline__ uint8_t finish(float v, int) const { return (uint8_t)(min1(v) * 255.0f); }
+};
+template <>
+struct HwcValue<uint16_t> {  // denorm of u16_scale.h with the band's (lo, R); its clamp is the min(v, 1) of the finish
+  static constexpr int kMax = 65535;
+  Scale s;
+  __device__ __forceinline__ uint16_t stitch(float x, int c) const {
+    return denorm_u16(x, pick(s.lo, c), pick(s.R, c));
+  }
+  __device__ __forceinline__ uint16_t finish(float v, int c) const {
+    return denorm_u16(v, pick(s.lo, c), pick(s.R, c));
+  }
+};
+
+// tiles [n][C][th][tw] -> val.stitch(x) into the HWC window image of T, which lies mis elements behind a 16-byte
+// boundary (hwc_chunks.h).  RES (near-lossless streams, residual.hip and residual_u16.hip): q [n][C][th][tw] holds the
+// tile's integer residual steps and the value is clamp(p + (int)q * step, 0, kMax), step = 2 tau + 1; |q| is at most
+// (kMax + tau) / step as the join kernels leave it, so the sum stays inside int32.
+template <typename T, bool RES>
+__global__ __launch_bounds__(256) void stitch_hwc_kernel(const float* __restrict__ tiles, const float* __restrict__ q,
+                                                         int step, T* __restrict__ img, Grid g, int C, int first,
+                                                         const int* __restrict__ ids, Clip w, HwcValue<T> val,
+                                                         int mis) {
+  constexpr int E = 16 / (int)sizeof(T);
   Owned o;
   if (!stitch_rect(g, ids, first, w, &o)) return;
   const int ya = o.y0 + blockIdx.x * kTileRows;
   const int rows = min(kTileRows, o.y1 - ya);
   if (rows <= 0) return;
-  const float* src = tiles + (size_t)blockIdx.y * C * g.th * g.tw;
   const size_t cplane = (size_t)g.th * g.tw;
+  const float* src = tiles + (size_t)blockIdx.y * C * cplane;
+  const float* qsrc = RES ? q + (size_t)blockIdx.y * C * cplane : nullptr;
   const int wW = w.x1 - w.x0;
   const int seg = (o.x1 - o.x0) * C;
-  const int cpr = seg / 16 + 2;  // 16-byte chunks a row segment can touch
+  const int cpr = seg / E + 2;  // 16-byte chunks a row segment can touch
   for (int i = threadIdx.x; i < rows * cpr; i += blockDim.x) {
     const int r = i / cpr, k = i - r * cpr;
     const int y = ya + r;
-    const int64_t b0 = ((int64_t)(y - w.y0) * wW + (o.x0 - w.x0)) * C, b1 = b0 + seg;
-    const int64_t q0 = ((b0 >> 4) + k) << 4;
-    if (q0 >= b1) continue;
-    const int64_t lo = max(q0, b0), hi = min(q0 + 16, b1);
-    const float* srow = src + (size_t)(y - o.oy) * g.tw;
-    const float* qrow = RES ? q + (size_t)blockIdx.y * C * cplane + (size_t)(y - o.oy) * g.tw : nullptr;
-    int px = (int)((lo - b0) / C), c = (int)((lo - b0) - (int64_t)px * C);
-    px += o.x0 - o.ox;  // column within the tile
-    uint8_t b[16];
+    const int64_t b0 = ((int64_t)(y - w.y0) * wW + (o.x0 - w.x0)) * C + mis;
+    Chunk ch;
+    if (!row_chunk<T>(b0, seg, k, &ch)) continue;
+    const size_t row = (size_t)(y - o.oy) * g.tw;
+    HwcCursor u = hwc_cursor(ch.lo() - b0, C);
+    u.px += o.x0 - o.ox;  // column within the tile
+    T b[E];
 #pragma unroll
-    for (int e = 0; e < 16; ++e) {
+    for (int e = 0; e < E; ++e) {
       b[e] = 0;
-      if (q0 + e >= lo && q0 + e < hi) {
-        b[e] = (uint8_t)(clamp01(srow[c * cplane + px]) * 255.0f);
-        if (RES) {
-          const int v = (int)b[e] + (int)qrow[c * cplane + px] * s;
-          b[e] = (uint8_t)(v < 0 ? 0 : (v > 255 ? 255 : v));
+      if (ch.has(e)) {
+        const size_t at = u.c * cplane + row + u.px;
+        b[e] = val.stitch(src[at], u.c);
+        if constexpr (RES) {
+          const int v = (int)b[e] + (int)qsrc[at] * step;
+          b[e] = (T)(v < 0 ? 0 : (v > val.kMax ? val.kMax : v));
         }
-        if (++c == C) c = 0, ++px;
+        u.step(C);
       }
     }
-    if (lo == q0 && hi == q0 + 16) {
-      uint4 v;
-      __builtin_memcpy(&v, b, 16);
-      *(uint4*)(img + q0) = v;
-    } else {
-      for (int64_t e = lo; e < hi; ++e) img[e] = b[e - q0];
-    }
+    store_chunk<T>(img, mis, ch.q0, ch.lo(), ch.hi(), b);
   }
 }
 
@@ -269,8 +293,6 @@ __global__ __launch_bounds__(256) void blend_f32_kernel(const float* __restrict_
   }
 }
 
-__device__ __forceinline__ float min1(float v) { return v > 1.f ? 1.f : v; }
-
 // min(v, 1) in place: in float32 the four weights of a pixel can sum to 1 + 2 ulp
 __global__ __launch_bounds__(256) void blend_finish_f32_kernel(float* __restrict__ canvas, int64_t n) {
   const int64_t n4 = n >> 2, step = (int64_t)gridDim.x * blockDim.x;
@@ -283,31 +305,56 @@ __global__ __launch_bounds__(256) void blend_finish_f32_kernel(float* __restrict
   for (int64_t e = 4 * n4 + tid; e < n; e += step) canvas[e] = min1(canvas[e]);
 }
 
-// canvas float32 [C][hw] -> (uint8)(min(v, 1) * 255) into the uint8 [hw][C] image, 16 bytes per lane
-__global__ __launch_bounds__(256) void blend_finish_u8_kernel(const float* __restrict__ canvas,
-                                                              uint8_t* __restrict__ out, int C, int64_t hw) {
-  const int64_t n = hw * C, nq = (n + 15) >> 4, step = (int64_t)gridDim.x * blockDim.x;
+// canvas float32 [C][hw] -> val.finish(v) into the [hw][C] image of T, mis elements behind a 16-byte boundary
+template <typename T>
+__global__ __launch_bounds__(256) void blend_finish_hwc_kernel(const float* __restrict__ canvas, T* __restrict__ out,
+                                                               int C, int64_t hw, HwcValue<T> val, int mis) {
+  constexpr int E = 16 / (int)sizeof(T);
+  const int64_t n = hw * C, nq = flat_chunks<T>(mis, n), step = (int64_t)gridDim.x * blockDim.x;
   for (int64_t q = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; q < nq; q += step) {
-    const int64_t q0 = q << 4, hi = min(q0 + 16, n);
-    int64_t px = q0 / C;
-    int c = (int)(q0 - px * C);
-    uint8_t b[16];
+    Chunk ch;
+    flat_chunk<T>(mis, n, q, &ch);
+    HwcCursor u = hwc_cursor(ch.lo() - mis, C);
+    T b[E];
 #pragma unroll
-    for (int e = 0; e < 16; ++e) {
+    for (int e = 0; e < E; ++e) {
       b[e] = 0;
-      if (q0 + e < hi) {
-        b[e] = (uint8_t)(min1(canvas[c * hw + px]) * 255.0f);
-        if (++c == C) c = 0, ++px;
+      if (ch.has(e)) {
+        b[e] = val.finish(canvas[u.c * hw + u.px], u.c);
+        u.step(C);
       }
     }
-    if (hi == q0 + 16) {
-      uint4 v;
-      __builtin_memcpy(&v, b, 16);
-      *(uint4*)(out + q0) = v;
-    } else {
-      for (int64_t e = q0; e < hi; ++e) out[e] = b[e - q0];
-    }
+    store_chunk<T>(out, mis, ch.q0, ch.lo(), ch.hi(), b);
   }
+}
+
+// The launches of the two kernels above, after the export's own checks; mis follows from the output's address.
+template <typename T>
+static void launch_stitch(bool res, dim3 grid, hipStream_t st, const float* tiles, const float* q, int step, T* out,
+                          const Grid& g, int C, int first, const int* ids, const Clip& clip, HwcValue<T> val) {
+  const int mis = (int)(((uintptr_t)out & 15) / sizeof(T));
+  if (res)
+    hipLaunchKernelGGL((stitch_hwc_kernel<T, true>), grid, dim3(256), 0, st, tiles, q, step, out, g, C, first, ids,
+                       clip, val, mis);
+  else
+    hipLaunchKernelGGL((stitch_hwc_kernel<T, false>), grid, dim3(256), 0, st, tiles, q, step, out, g, C, first, ids,
+                       clip, val, mis);
+}
+
+template <typename T>
+static void launch_blend_finish(hipStream_t st, const float* canvas, T* out, int C, int64_t hw, HwcValue<T> val) {
+  const int mis = (int)(((uintptr_t)out & 15) / sizeof(T));
+  hipLaunchKernelGGL(blend_finish_hwc_kernel<T>, dim3(flat_blocks(flat_chunks<T>(mis, hw * C))), dim3(256), 0, st,
+                     canvas, out, C, hw, val, mis);
+}
+
+// for image_u16.hip's exports (declared in hwc_launch.h)
+void launch_stitch_u16(bool res, dim3 grid, hipStream_t st, const float* tiles, const float* q, int step, uint16_t* out,
+                       const Grid& g, int C, const int* ids, const Clip& clip, const Scale& sc) {
+  launch_stitch<uint16_t>(res, grid, st, tiles, q, step, out, g, C, 0, ids, clip, {sc});
+}
+void launch_blend_finish_u16(hipStream_t st, const float* canvas, uint16_t* out, int C, int64_t hw, const Scale& sc) {
+  launch_blend_finish<uint16_t>(st, canvas, out, C, hw, {sc});
 }
 
 // ---- DSIC2 container --------------------------------------------------------------------------------------
@@ -452,48 +499,66 @@ __global__ __launch_bounds__(256) void scatter_select_kernel(const uint8_t* __re
 
 }  // namespace dsic
 
+// ---- exports ----------------------------------------------------------------------------------------------
+// An export with and without _ov, or with and without _res, is one body; `what` is the export's name in its messages.
+namespace dsic {
+
+static int gather_u8(const char* what, const uint8_t* img_hwc, uint8_t* tiles, int H, int W, int C, int th, int tw,
+                     int overlap, int first_tile, int n_tiles, void* stream) {
+  DSIC_REQUIRE(img_hwc && tiles, "%s: null pointer", what);
+  DSIC_REQUIRE(C == 3 || C == 4, "%s: C=%d must be 3 or 4", what, C);
+  DSIC_TILE_ARGS_OV(what, overlap);
+  DSIC_REQUIRE(((uintptr_t)tiles & 15) == 0, "%s: tiles must be 16-byte aligned", what);
+  hipLaunchKernelGGL(gather_u8_kernel, grid, dim3(256), 0, (hipStream_t)stream, img_hwc, tiles, g, C, first_tile);
+  return check_launch(what);
+}
+
+static int gather_f32(const char* what, const float* img_chw, float* tiles, int H, int W, int C, int th, int tw,
+                      int overlap, int first_tile, int n_tiles, void* stream) {
+  DSIC_REQUIRE(img_chw && tiles, "%s: null pointer", what);
+  DSIC_REQUIRE(C >= 1 && C <= 8, "%s: C=%d must be in 1..8", what, C);
+  DSIC_TILE_ARGS_OV(what, overlap);
+  DSIC_REQUIRE(((uintptr_t)tiles & 15) == 0, "%s: tiles must be 16-byte aligned", what);
+  hipLaunchKernelGGL(gather_f32_kernel, dim3(grid.x, grid.y, C), dim3(256), 0, (hipStream_t)stream, img_chw, tiles,
+                     g, first_tile);
+  return check_launch(what);
+}
+
+// q == nullptr stands for "no residual" only where res is false
+static int stitch_window_u8(const char* what, bool res, const float* tiles, const float* q, int tau,
+                            const int* tile_ids, int n_tiles, uint8_t* out, int H, int W, int C, int th, int tw,
+                            int wy0, int wx0, int wh, int ww, void* stream) {
+  DSIC_REQUIRE(tiles && (q || !res) && tile_ids && out, "%s: null pointer", what);
+  DSIC_REQUIRE(C == 3 || C == 4, "%s: C=%d must be 3 or 4", what, C);
+  DSIC_REQUIRE(!res || (tau >= 0 && tau <= 127), "%s: tau=%d must be in 0..127", what, tau);
+  DSIC_WINDOW_ARGS(what);
+  DSIC_REQUIRE(((uintptr_t)out & 15) == 0, "%s: out must be 16-byte aligned", what);
+  launch_stitch<uint8_t>(res, grid, (hipStream_t)stream, tiles, q, 2 * tau + 1, out, g, C, 0, tile_ids, clip, {});
+  return check_launch(what);
+}
+
+}  // namespace dsic
+
 using namespace dsic;
 
 extern "C" int dsic_tile_gather_u8_ov(const uint8_t* img_hwc, uint8_t* tiles, int H, int W, int C, int th, int tw,
                                       int overlap, int first_tile, int n_tiles, void* stream) {
-  DSIC_REQUIRE(img_hwc && tiles, "tile_gather_u8_ov: null pointer");
-  DSIC_REQUIRE(C == 3 || C == 4, "tile_gather_u8_ov: C=%d must be 3 or 4", C);
-  DSIC_TILE_ARGS_OV("tile_gather_u8_ov", overlap);
-  DSIC_REQUIRE(((uintptr_t)tiles & 15) == 0, "tile_gather_u8_ov: tiles must be 16-byte aligned");
-  hipLaunchKernelGGL(gather_u8_kernel, grid, dim3(256), 0, (hipStream_t)stream, img_hwc, tiles, g, C, first_tile);
-  return check_launch("tile_gather_u8_ov");
+  return gather_u8("tile_gather_u8_ov", img_hwc, tiles, H, W, C, th, tw, overlap, first_tile, n_tiles, stream);
 }
 
 extern "C" int dsic_tile_gather_f32_ov(const float* img_chw, float* tiles, int H, int W, int C, int th, int tw,
                                        int overlap, int first_tile, int n_tiles, void* stream) {
-  DSIC_REQUIRE(img_chw && tiles, "tile_gather_f32_ov: null pointer");
-  DSIC_REQUIRE(C >= 1 && C <= 8, "tile_gather_f32_ov: C=%d must be in 1..8", C);
-  DSIC_TILE_ARGS_OV("tile_gather_f32_ov", overlap);
-  DSIC_REQUIRE(((uintptr_t)tiles & 15) == 0, "tile_gather_f32_ov: tiles must be 16-byte aligned");
-  hipLaunchKernelGGL(gather_f32_kernel, dim3(grid.x, grid.y, C), dim3(256), 0, (hipStream_t)stream, img_chw, tiles,
-                     g, first_tile);
-  return check_launch("tile_gather_f32_ov");
+  return gather_f32("tile_gather_f32_ov", img_chw, tiles, H, W, C, th, tw, overlap, first_tile, n_tiles, stream);
 }
 
 extern "C" int dsic_tile_gather_u8(const uint8_t* img_hwc, uint8_t* tiles, int H, int W, int C, int th, int tw,
                                    int first_tile, int n_tiles, void* stream) {
-  DSIC_REQUIRE(img_hwc && tiles, "tile_gather_u8: null pointer");
-  DSIC_REQUIRE(C == 3 || C == 4, "tile_gather_u8: C=%d must be 3 or 4", C);
-  DSIC_TILE_ARGS("tile_gather_u8");
-  DSIC_REQUIRE(((uintptr_t)tiles & 15) == 0, "tile_gather_u8: tiles must be 16-byte aligned");
-  hipLaunchKernelGGL(gather_u8_kernel, grid, dim3(256), 0, (hipStream_t)stream, img_hwc, tiles, g, C, first_tile);
-  return check_launch("tile_gather_u8");
+  return gather_u8("tile_gather_u8", img_hwc, tiles, H, W, C, th, tw, 0, first_tile, n_tiles, stream);
 }
 
 extern "C" int dsic_tile_gather_f32(const float* img_chw, float* tiles, int H, int W, int C, int th, int tw,
                                     int first_tile, int n_tiles, void* stream) {
-  DSIC_REQUIRE(img_chw && tiles, "tile_gather_f32: null pointer");
-  DSIC_REQUIRE(C >= 1 && C <= 8, "tile_gather_f32: C=%d must be in 1..8", C);
-  DSIC_TILE_ARGS("tile_gather_f32");
-  DSIC_REQUIRE(((uintptr_t)tiles & 15) == 0, "tile_gather_f32: tiles must be 16-byte aligned");
-  hipLaunchKernelGGL(gather_f32_kernel, dim3(grid.x, grid.y, C), dim3(256), 0, (hipStream_t)stream, img_chw, tiles,
-                     g, first_tile);
-  return check_launch("tile_gather_f32");
+  return gather_f32("tile_gather_f32", img_chw, tiles, H, W, C, th, tw, 0, first_tile, n_tiles, stream);
 }
 
 extern "C" int dsic_tile_stitch_f32(const float* tiles, float* img_chw, int H, int W, int C, int th, int tw,
@@ -513,8 +578,8 @@ extern "C" int dsic_tile_stitch_u8(const float* tiles, uint8_t* img_hwc, int H, 
   DSIC_REQUIRE(C == 3 || C == 4, "tile_stitch_u8: C=%d must be 3 or 4", C);
   DSIC_TILE_ARGS("tile_stitch_u8");
   DSIC_REQUIRE(((uintptr_t)img_hwc & 15) == 0, "tile_stitch_u8: image must be 16-byte aligned");
-  hipLaunchKernelGGL(stitch_u8_kernel<false>, grid, dim3(256), 0, (hipStream_t)stream, tiles, img_hwc, g, C,
-                     first_tile, (const int*)nullptr, Clip{0, H, 0, W}, (const float*)nullptr, 1);
+  launch_stitch<uint8_t>(false, grid, (hipStream_t)stream, tiles, nullptr, 1, img_hwc, g, C, first_tile, nullptr,
+                         Clip{0, H, 0, W}, {});
   return check_launch("tile_stitch_u8");
 }
 
@@ -533,26 +598,15 @@ extern "C" int dsic_tile_stitch_window_f32(const float* tiles, const int* tile_i
 extern "C" int dsic_tile_stitch_window_u8(const float* tiles, const int* tile_ids, int n_tiles, uint8_t* out, int H,
                                           int W, int C, int th, int tw, int wy0, int wx0, int wh, int ww,
                                           void* stream) {
-  DSIC_REQUIRE(tiles && tile_ids && out, "tile_stitch_window_u8: null pointer");
-  DSIC_REQUIRE(C == 3 || C == 4, "tile_stitch_window_u8: C=%d must be 3 or 4", C);
-  DSIC_WINDOW_ARGS("tile_stitch_window_u8");
-  DSIC_REQUIRE(((uintptr_t)out & 15) == 0, "tile_stitch_window_u8: out must be 16-byte aligned");
-  hipLaunchKernelGGL(stitch_u8_kernel<false>, grid, dim3(256), 0, (hipStream_t)stream, tiles, out, g, C, 0, tile_ids,
-                     clip, (const float*)nullptr, 1);
-  return check_launch("tile_stitch_window_u8");
+  return stitch_window_u8("tile_stitch_window_u8", false, tiles, nullptr, 0, tile_ids, n_tiles, out, H, W, C, th, tw,
+                          wy0, wx0, wh, ww, stream);
 }
 
 extern "C" int dsic_tile_stitch_window_u8_res(const float* tiles, const float* q, int tau, const int* tile_ids,
                                               int n_tiles, uint8_t* out, int H, int W, int C, int th, int tw, int wy0,
                                               int wx0, int wh, int ww, void* stream) {
-  DSIC_REQUIRE(tiles && q && tile_ids && out, "tile_stitch_window_u8_res: null pointer");
-  DSIC_REQUIRE(C == 3 || C == 4, "tile_stitch_window_u8_res: C=%d must be 3 or 4", C);
-  DSIC_REQUIRE(tau >= 0 && tau <= 127, "tile_stitch_window_u8_res: tau=%d must be in 0..127", tau);
-  DSIC_WINDOW_ARGS("tile_stitch_window_u8_res");
-  DSIC_REQUIRE(((uintptr_t)out & 15) == 0, "tile_stitch_window_u8_res: out must be 16-byte aligned");
-  hipLaunchKernelGGL(stitch_u8_kernel<true>, grid, dim3(256), 0, (hipStream_t)stream, tiles, out, g, C, 0, tile_ids,
-                     clip, q, 2 * tau + 1);
-  return check_launch("tile_stitch_window_u8_res");
+  return stitch_window_u8("tile_stitch_window_u8_res", true, tiles, q, tau, tile_ids, n_tiles, out, H, W, C, th, tw,
+                          wy0, wx0, wh, ww, stream);
 }
 
 extern "C" int dsic_tile_blend_window_f32(const float* tiles, const int* tile_ids, int n_tiles, float* canvas, int H,
@@ -582,7 +636,7 @@ extern "C" int dsic_tile_blend_finish_f32(float* canvas, int C, int h, int w, vo
   DSIC_REQUIRE(h >= 1 && w >= 1, "tile_blend_finish_f32: empty window %dx%d", h, w);
   DSIC_REQUIRE(((uintptr_t)canvas & 15) == 0, "tile_blend_finish_f32: canvas must be 16-byte aligned");
   const int64_t n = (int64_t)C * h * w;
-  hipLaunchKernelGGL(blend_finish_f32_kernel, dim3(finish_blocks(n >> 2)), dim3(256), 0, (hipStream_t)stream, canvas,
+  hipLaunchKernelGGL(blend_finish_f32_kernel, dim3(flat_blocks(n >> 2)), dim3(256), 0, (hipStream_t)stream, canvas,
                      n);
   return check_launch("tile_blend_finish_f32");
 }
@@ -592,9 +646,7 @@ extern "C" int dsic_tile_blend_finish_u8(const float* canvas, uint8_t* out_hwc, 
   DSIC_REQUIRE(C == 3 || C == 4, "tile_blend_finish_u8: C=%d must be 3 or 4", C);
   DSIC_REQUIRE(h >= 1 && w >= 1, "tile_blend_finish_u8: empty window %dx%d", h, w);
   DSIC_REQUIRE(((uintptr_t)out_hwc & 15) == 0, "tile_blend_finish_u8: out must be 16-byte aligned");
-  const int64_t hw = (int64_t)h * w;
-  hipLaunchKernelGGL(blend_finish_u8_kernel, dim3(finish_blocks((hw * C + 15) >> 4)), dim3(256), 0,
-                     (hipStream_t)stream, canvas, out_hwc, C, hw);
+  launch_blend_finish<uint8_t>((hipStream_t)stream, canvas, out_hwc, C, (int64_t)h * w, {});
   return check_launch("tile_blend_finish_u8");
 }
 

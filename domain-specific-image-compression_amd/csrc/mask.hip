@@ -18,11 +18,13 @@
 //   unpack        payloads, (mode, offset, bytes) per tile -> m planes: every dword gathers the positions of its 32
 //                 bits from the ascending list by bisection (no atomics, the result does not depend on any order), or
 //                 copies its raw bytes; then the XOR prefix down every 16-bit column strip
-//   apply         m planes, (tile, plane or -1 = all set) per tile -> v (uint8 HWC) or v / 255.0f (float32 CHW) at the
-//                 tile's owned pixels inside the window whose bit is set; nothing else is written
+//   apply         m planes, (tile, plane or -1 = all set) per tile -> v (uint8 or uint16 HWC, one kernel over the
+//                 element type) or v / 255.0f (float32 CHW) at the tile's owned pixels inside the window whose bit is
+//                 set; nothing else is written.  The HWC outputs are walked in the chunks of hwc_chunks.h.
 #include <limits.h>
 
 #include "byte_movers.h"
+#include "hwc_chunks.h"
 #include "tile_grid.h"
 
 namespace dsic {
@@ -279,9 +281,14 @@ __device__ __forceinline__ bool mask_bit(const uint32_t* plane, int idx) {
   return !plane || ((plane[idx >> 5] >> (idx & 31)) & 1u);
 }
 
-__global__ __launch_bounds__(256) void mask_apply_u8_kernel(const uint32_t* __restrict__ planes,
-                                                            const int* __restrict__ desc, int n_planes, Grid g, int C,
-                                                            Clip w, uint8_t* __restrict__ img, uint32_t v) {
+// HWC window of T (uint8_t or uint16_t) at any element alignment: `mis` is the window image's offset behind a 16-byte
+// boundary in elements (hwc_chunks.h).  A chunk whose every element is selected is one dwordx4 store of v, any other
+// stores v at its selected elements.
+template <typename T>
+__global__ __launch_bounds__(256) void mask_apply_hwc_kernel(const uint32_t* __restrict__ planes,
+                                                             const int* __restrict__ desc, int n_planes, Grid g, int C,
+                                                             Clip w, T* __restrict__ img, uint32_t v, int mis) {
+  constexpr int E = 16 / (int)sizeof(T);
   Owned o;
   int pi;
   if (!apply_rect(g, desc, n_planes, w, &o, &pi)) return;
@@ -291,32 +298,31 @@ __global__ __launch_bounds__(256) void mask_apply_u8_kernel(const uint32_t* __re
   const uint32_t* plane = pi < 0 ? nullptr : planes + (size_t)pi * ((g.th * g.tw) >> 5);
   const int wW = w.x1 - w.x0;
   const int seg = (o.x1 - o.x0) * C;
-  const int cpr = seg / 16 + 2;  // 16-byte chunks a row segment can touch
-  const uint32_t vv = v * 0x01010101u;
+  const int cpr = seg / E + 2;  // 16-byte chunks a row segment can touch
+  const uint32_t vv = v * (sizeof(T) == 1 ? 0x01010101u : 0x00010001u);
   for (int i = threadIdx.x; i < rows * cpr; i += blockDim.x) {
     const int r = i / cpr, k = i - r * cpr;
     const int y = ya + r;
-    const int64_t b0 = ((int64_t)(y - w.y0) * wW + (o.x0 - w.x0)) * C, b1 = b0 + seg;
-    const int64_t q0 = ((b0 >> 4) + k) << 4;
-    if (q0 >= b1) continue;
-    const int64_t lo = max(q0, b0), hi = min(q0 + 16, b1);
-    int px = (int)((lo - b0) / C), c = (int)((lo - b0) - (int64_t)px * C);
-    px += o.x0 - o.ox;  // column within the tile
+    const int64_t b0 = ((int64_t)(y - w.y0) * wW + (o.x0 - w.x0)) * C + mis;
+    Chunk ch;
+    if (!row_chunk<T>(b0, seg, k, &ch)) continue;
+    HwcCursor u = hwc_cursor(ch.lo() - b0, C);
+    u.px += o.x0 - o.ox;  // column within the tile
     const int row_bit = (y - o.oy) * g.tw;
     uint32_t sel = 0;
 #pragma unroll
-    for (int e = 0; e < 16; ++e) {
-      if (q0 + e >= lo && q0 + e < hi) {
-        sel |= (uint32_t)mask_bit(plane, row_bit + px) << e;
-        if (++c == C) c = 0, ++px;
+    for (int e = 0; e < E; ++e) {
+      if (ch.has(e)) {
+        sel |= (uint32_t)mask_bit(plane, row_bit + (int)u.px) << e;
+        u.step(C);
       }
     }
-    if (sel == 0xFFFFu) {
-      *(uint4*)(img + q0) = make_uint4(vv, vv, vv, vv);
+    if (sel == (1u << E) - 1u) {
+      *(uint4*)(img + (ch.q0 - mis)) = make_uint4(vv, vv, vv, vv);
     } else {
 #pragma unroll
-      for (int e = 0; e < 16; ++e)
-        if ((sel >> e) & 1u) img[q0 + e] = (uint8_t)v;
+      for (int e = 0; e < E; ++e)
+        if ((sel >> e) & 1u) img[ch.q0 + e - mis] = (T)v;
     }
   }
 }
@@ -355,51 +361,6 @@ __global__ __launch_bounds__(256) void mask_apply_f32_kernel(const uint32_t* __r
   }
 }
 
-// uint16 HWC window at any 2-byte alignment, C 1 .. 4.  Positions count uint16 elements; `mis` is the window
-// image's offset behind a 16-byte boundary in elements (stitch_u16_kernel of image_u16.hip), so that chunk q0 is an
-// aligned 16 bytes of memory.
-__global__ __launch_bounds__(256) void mask_apply_u16_kernel(const uint32_t* __restrict__ planes,
-                                                             const int* __restrict__ desc, int n_planes, Grid g, int C,
-                                                             Clip w, uint16_t* __restrict__ img, uint32_t v, int mis) {
-  Owned o;
-  int pi;
-  if (!apply_rect(g, desc, n_planes, w, &o, &pi)) return;
-  const int ya = o.y0 + blockIdx.x * kMaskRows;
-  const int rows = min(kMaskRows, o.y1 - ya);
-  if (rows <= 0) return;
-  const uint32_t* plane = pi < 0 ? nullptr : planes + (size_t)pi * ((g.th * g.tw) >> 5);
-  const int wW = w.x1 - w.x0;
-  const int seg = (o.x1 - o.x0) * C;
-  const int cpr = seg / 8 + 2;  // 16-byte chunks a row segment can touch
-  const uint32_t vv = v * 0x00010001u;
-  for (int i = threadIdx.x; i < rows * cpr; i += blockDim.x) {
-    const int r = i / cpr, k = i - r * cpr;
-    const int y = ya + r;
-    const int64_t b0 = ((int64_t)(y - w.y0) * wW + (o.x0 - w.x0)) * C + mis, b1 = b0 + seg;
-    const int64_t q0 = ((b0 >> 3) + k) << 3;
-    if (q0 >= b1) continue;
-    const int64_t lo = max(q0, b0), hi = min(q0 + 8, b1);
-    int px = (int)((lo - b0) / C), c = (int)((lo - b0) - (int64_t)px * C);
-    px += o.x0 - o.ox;  // column within the tile
-    const int row_bit = (y - o.oy) * g.tw;
-    uint32_t sel = 0;
-#pragma unroll
-    for (int e = 0; e < 8; ++e) {
-      if (q0 + e >= lo && q0 + e < hi) {
-        sel |= (uint32_t)mask_bit(plane, row_bit + px) << e;
-        if (++c == C) c = 0, ++px;
-      }
-    }
-    if (sel == 0xFFu) {
-      *(uint4*)(img + (q0 - mis)) = make_uint4(vv, vv, vv, vv);
-    } else {
-#pragma unroll
-      for (int e = 0; e < 8; ++e)
-        if ((sel >> e) & 1u) img[q0 + e - mis] = (uint16_t)v;
-    }
-  }
-}
-
 // The validity window, uint8 [h][w] at any alignment (`mis` in bytes): every owned pixel of the listed tiles inside
 // the window gets 0 where its bit is set (or the plane is -1, all set) and 1 elsewhere; no other byte is written.
 __global__ __launch_bounds__(256) void mask_window_u8_kernel(const uint32_t* __restrict__ planes,
@@ -418,22 +379,15 @@ __global__ __launch_bounds__(256) void mask_window_u8_kernel(const uint32_t* __r
   for (int i = threadIdx.x; i < rows * cpr; i += blockDim.x) {
     const int r = i / cpr, k = i - r * cpr;
     const int y = ya + r;
-    const int64_t b0 = (int64_t)(y - w.y0) * wW + (o.x0 - w.x0) + mis, b1 = b0 + seg;
-    const int64_t q0 = ((b0 >> 4) + k) << 4;
-    if (q0 >= b1) continue;
-    const int64_t lo = max(q0, b0), hi = min(q0 + 16, b1);
-    const int bit0 = (y - o.oy) * g.tw + (o.x0 - o.ox) + (int)(lo - b0);
+    const int64_t b0 = (int64_t)(y - w.y0) * wW + (o.x0 - w.x0) + mis;
+    Chunk ch;
+    if (!row_chunk<uint8_t>(b0, seg, k, &ch)) continue;
+    const int bit0 = (y - o.oy) * g.tw + (o.x0 - o.ox) + (int)(ch.lo() - b0);
     uint8_t b[16];
 #pragma unroll
     for (int e = 0; e < 16; ++e)
-      b[e] = q0 + e >= lo && q0 + e < hi ? (uint8_t)!mask_bit(plane, bit0 + (int)(q0 + e - lo)) : (uint8_t)0;
-    if (lo == q0 && hi == q0 + 16) {
-      uint4 v;
-      __builtin_memcpy(&v, b, 16);
-      *(uint4*)(out + (q0 - mis)) = v;
-    } else {
-      for (int64_t e = lo; e < hi; ++e) out[e - mis] = b[e - q0];
-    }
+      b[e] = ch.has(e) ? (uint8_t)!mask_bit(plane, bit0 + e - ch.first) : (uint8_t)0;
+    store_chunk<uint8_t>(out, mis, ch.q0, ch.lo(), ch.hi(), b);
   }
 }
 
@@ -518,18 +472,19 @@ extern "C" int dsic_mask_unpack(const uint8_t* blob, int64_t blob_bytes, const i
   return check_launch("mask_unpack");
 }
 
-#define DSIC_MASK_WINDOW(what)                                                                                 \
-  DSIC_REQUIRE(nodata >= 0 && nodata <= 255, what ": nodata=%d must be in 0..255", nodata);                    \
-  const char* ge = grid_error(H, W, th, tw);                                                                   \
-  DSIC_REQUIRE(!ge, what ": %s (H=%d W=%d th=%d tw=%d)", ge ? ge : "", H, W, th, tw);                          \
-  DSIC_REQUIRE((int64_t)th * tw <= INT_MAX / 2, what ": a tile of %dx%d has over 2^30 pixels", th, tw);        \
-  const Grid g = make_grid(H, W, th, tw);                                                                      \
-  DSIC_REQUIRE(wy0 >= 0 && wx0 >= 0 && wh >= 1 && ww >= 1 && (int64_t)wy0 + wh <= H && (int64_t)wx0 + ww <= W, \
-               what ": window %dx%d at (%d, %d) outside the %dx%d image", wh, ww, wy0, wx0, H, W);             \
-  DSIC_REQUIRE(n_tiles >= 1 && n_tiles <= 65535, what ": n=%d tiles per call (1..65535)", n_tiles);            \
-  DSIC_REQUIRE(n_planes >= 0 && (planes || n_planes == 0), what ": %d planes at a null pointer", n_planes);    \
-  DSIC_REQUIRE(((uintptr_t)out & 15) == 0, what ": out must be 16-byte aligned");                              \
-  const Clip clip = {wy0, wy0 + wh, wx0, wx0 + ww};                                                            \
+// The argument checks that the calls which write a window share (names as in the exports; `what` is a string),
+// leaving the grid `g`, the window `clip` and the launch grid `grid`.  The range of the fill value stands before it
+// at the call, the alignments of out, planes and desc behind it.
+#define DSIC_MASK_WINDOW(what)                                                                                     \
+  const char* ge = grid_error(H, W, th, tw);                                                                       \
+  DSIC_REQUIRE(!ge, "%s: %s (H=%d W=%d th=%d tw=%d)", what, ge ? ge : "", H, W, th, tw);                           \
+  DSIC_REQUIRE((int64_t)th * tw <= INT_MAX / 2, "%s: a tile of %dx%d has over 2^30 pixels", what, th, tw);         \
+  const Grid g = make_grid(H, W, th, tw);                                                                          \
+  DSIC_REQUIRE(wy0 >= 0 && wx0 >= 0 && wh >= 1 && ww >= 1 && (int64_t)wy0 + wh <= H && (int64_t)wx0 + ww <= W,     \
+               "%s: window %dx%d at (%d, %d) outside the %dx%d image", what, wh, ww, wy0, wx0, H, W);              \
+  DSIC_REQUIRE(n_tiles >= 1 && n_tiles <= 65535, "%s: n=%d tiles per call (1..65535)", what, n_tiles);             \
+  DSIC_REQUIRE(n_planes >= 0 && (planes || n_planes == 0), "%s: %d planes at a null pointer", what, n_planes);     \
+  const Clip clip = {wy0, wy0 + wh, wx0, wx0 + ww};                                                                \
   const dim3 grid(g.th / kMaskRows, n_tiles, 1)
 
 extern "C" int dsic_mask_apply_u8(const uint32_t* planes, int n_planes, const int* desc, int n_tiles, int nodata,
@@ -537,9 +492,11 @@ extern "C" int dsic_mask_apply_u8(const uint32_t* planes, int n_planes, const in
                                   void* stream) {
   DSIC_REQUIRE(desc && out, "mask_apply_u8: null pointer");
   DSIC_REQUIRE(C == 3 || C == 4, "mask_apply_u8: C=%d must be 3 or 4", C);
+  DSIC_REQUIRE(nodata >= 0 && nodata <= 255, "mask_apply_u8: nodata=%d must be in 0..255", nodata);
   DSIC_MASK_WINDOW("mask_apply_u8");
-  hipLaunchKernelGGL(mask_apply_u8_kernel, grid, dim3(256), 0, (hipStream_t)stream, planes, desc, n_planes, g, C, clip,
-                     out, (uint32_t)nodata);
+  DSIC_REQUIRE(((uintptr_t)out & 15) == 0, "mask_apply_u8: out must be 16-byte aligned");
+  hipLaunchKernelGGL(mask_apply_hwc_kernel<uint8_t>, grid, dim3(256), 0, (hipStream_t)stream, planes, desc, n_planes,
+                     g, C, clip, out, (uint32_t)nodata, 0);
   return check_launch("mask_apply_u8");
 }
 
@@ -548,7 +505,9 @@ extern "C" int dsic_mask_apply_f32(const uint32_t* planes, int n_planes, const i
                                    void* stream) {
   DSIC_REQUIRE(desc && out, "mask_apply_f32: null pointer");
   DSIC_REQUIRE(C >= 1 && C <= 8, "mask_apply_f32: C=%d must be in 1..8", C);
+  DSIC_REQUIRE(nodata >= 0 && nodata <= 255, "mask_apply_f32: nodata=%d must be in 0..255", nodata);
   DSIC_MASK_WINDOW("mask_apply_f32");
+  DSIC_REQUIRE(((uintptr_t)out & 15) == 0, "mask_apply_f32: out must be 16-byte aligned");
   const float fv = (float)nodata / 255.0f;  // on the host, correctly rounded: NumPy's float32(v) / float32(255)
   hipLaunchKernelGGL(mask_apply_f32_kernel, dim3(grid.x, grid.y, C), dim3(256), 0, (hipStream_t)stream, planes, desc,
                      n_planes, g, clip, out, fv);
@@ -589,19 +548,6 @@ extern "C" int dsic_valid_delta_planes(const uint8_t* valid_hw, int H, int W, in
   return check_launch("valid_delta_planes");
 }
 
-#define DSIC_VALID_WINDOW(what)                                                                                \
-  const char* ge = grid_error(H, W, th, tw);                                                                   \
-  DSIC_REQUIRE(!ge, what ": %s (H=%d W=%d th=%d tw=%d)", ge ? ge : "", H, W, th, tw);                          \
-  DSIC_REQUIRE((int64_t)th * tw <= INT_MAX / 2, what ": a tile of %dx%d has over 2^30 pixels", th, tw);        \
-  const Grid g = make_grid(H, W, th, tw);                                                                      \
-  DSIC_REQUIRE(wy0 >= 0 && wx0 >= 0 && wh >= 1 && ww >= 1 && (int64_t)wy0 + wh <= H && (int64_t)wx0 + ww <= W, \
-               what ": window %dx%d at (%d, %d) outside the %dx%d image", wh, ww, wy0, wx0, H, W);             \
-  DSIC_REQUIRE(n_tiles >= 1 && n_tiles <= 65535, what ": n=%d tiles per call (1..65535)", n_tiles);            \
-  DSIC_REQUIRE(n_planes >= 0 && (planes || n_planes == 0), what ": %d planes at a null pointer", n_planes);    \
-  DSIC_REQUIRE((((uintptr_t)planes | (uintptr_t)desc) & 3) == 0, what ": planes and desc must be 4-byte aligned"); \
-  const Clip clip = {wy0, wy0 + wh, wx0, wx0 + ww};                                                            \
-  const dim3 grid(g.th / kMaskRows, n_tiles, 1)
-
 extern "C" int dsic_mask_apply_u16(const uint32_t* planes, int n_planes, const int* desc, int n_tiles, int fill,
                                    uint16_t* out, int H, int W, int C, int th, int tw, int wy0, int wx0, int wh, int ww,
                                    void* stream) {
@@ -609,18 +555,22 @@ extern "C" int dsic_mask_apply_u16(const uint32_t* planes, int n_planes, const i
   DSIC_REQUIRE(C >= 1 && C <= 4, "mask_apply_u16: C=%d must be in 1..4", C);
   DSIC_REQUIRE(fill >= 0 && fill <= 65535, "mask_apply_u16: fill=%d must be in 0..65535", fill);
   DSIC_REQUIRE(((uintptr_t)out & 1) == 0, "mask_apply_u16: the uint16 window must be 2-byte aligned");
-  DSIC_VALID_WINDOW("mask_apply_u16");
+  DSIC_MASK_WINDOW("mask_apply_u16");
+  DSIC_REQUIRE((((uintptr_t)planes | (uintptr_t)desc) & 3) == 0,
+               "mask_apply_u16: planes and desc must be 4-byte aligned");
   DSIC_REQUIRE((int64_t)ww * C * 2 <= INT_MAX, "mask_apply_u16: a row of ww=%d pixels of C=%d uint16 is over 2^31 - 1 bytes",
                ww, C);
-  hipLaunchKernelGGL(mask_apply_u16_kernel, grid, dim3(256), 0, (hipStream_t)stream, planes, desc, n_planes, g, C, clip,
-                     out, (uint32_t)fill, (int)(((uintptr_t)out & 15) >> 1));
+  hipLaunchKernelGGL(mask_apply_hwc_kernel<uint16_t>, grid, dim3(256), 0, (hipStream_t)stream, planes, desc, n_planes,
+                     g, C, clip, out, (uint32_t)fill, (int)(((uintptr_t)out & 15) >> 1));
   return check_launch("mask_apply_u16");
 }
 
 extern "C" int dsic_mask_window_u8(const uint32_t* planes, int n_planes, const int* desc, int n_tiles, uint8_t* out_hw,
                                    int H, int W, int th, int tw, int wy0, int wx0, int wh, int ww, void* stream) {
   DSIC_REQUIRE(desc && out_hw, "mask_window_u8: null pointer");
-  DSIC_VALID_WINDOW("mask_window_u8");
+  DSIC_MASK_WINDOW("mask_window_u8");
+  DSIC_REQUIRE((((uintptr_t)planes | (uintptr_t)desc) & 3) == 0,
+               "mask_window_u8: planes and desc must be 4-byte aligned");
   hipLaunchKernelGGL(mask_window_u8_kernel, grid, dim3(256), 0, (hipStream_t)stream, planes, desc, n_planes, g, clip,
                      out_hw, (int)((uintptr_t)out_hw & 15));
   return check_launch("mask_window_u8");

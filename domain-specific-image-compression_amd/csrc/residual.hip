@@ -2,10 +2,10 @@
 // difference between the gathered uint8 tile x and the uint8 image p of the encoder's own x_hat, quantized with step
 // s = 2 tau + 1, coded with one static table per (tile, colour channel) by the range coder of entropy.hip.
 //
-//   p = (uint8)(clamp(x_hat, 0, 1) * 255)      float32, truncating: what stitch_u8_kernel writes
+//   p = (uint8)(clamp(x_hat, 0, 1) * 255)      float32, truncating: what stitch_hwc_kernel writes
 //   r = x - p,  q = sign(r) * floor((|r| + tau) / s),  |q| <= Q = floor((255 + tau) / s)
 //   q = 0 at every pixel the tile does not own (the decoder never writes it)
-//   decoder: x' = clamp(p + q s, 0, 255), |x' - x| <= tau           (image_codec.hip stitch_u8_kernel<true>)
+//   decoder: x' = clamp(p + q s, 0, 255), |x' - x| <= tau           (image_codec.hip stitch_hwc_kernel<uint8_t, true>)
 //
 // The q plane of a tile, float32 [C][th][tw], is read by the coder as the latent [C 16][(th / 16) tw]: 16 row bands
 // per colour plane, coded as 16 segments.  Everything here is integer arithmetic or byte movement; the kernels are

@@ -2,10 +2,10 @@
 // difference between the uint16 image x and the uint16 image p of the encoder's own x_hat, quantized with step
 // s = 2 tau + 1.
 //
-//   p = denorm(x_hat) = lo + (uint32)(clamp(x_hat, 0, 1) * (float)R + 0.5f)      what stitch_u16_kernel writes
+//   p = denorm(x_hat) = lo + (uint32)(clamp(x_hat, 0, 1) * (float)R + 0.5f)      what stitch_hwc_kernel writes
 //   r = x - p,  q = sign(r) * floor((|r| + tau) / s),  |q| <= Q16 = floor((65535 + tau) / s)
 //   q = 0 at every pixel the tile does not own
-//   decoder: x' = clamp(p + q s, 0, 65535), |x' - x| <= tau                       (image_u16.hip stitch_u16_kernel<true>)
+//   decoder: x' = clamp(p + q s, 0, 65535), |x' - x| <= tau                       (image_codec.hip stitch_hwc_kernel<uint16_t, true>)
 //
 // q has up to 131 071 values, far past the 511 symbols of the 16-bit coder tables, so it is split per tile: with
 // m = max |q| over the tile and k the least shift with m <= 255 << k (0 .. 9),

@@ -55,12 +55,6 @@ __device__ __forceinline__ bool stitch_rect(const Grid& g, const int* ids, int f
 
 static bool overlap_ok(int th, int tw, int O) { return O >= 0 && O % 16 == 0 && 2 * O <= (th < tw ? th : tw); }
 
-// workgroups of a flat finishing pass over `units` 16-byte units
-static int finish_blocks(int64_t units) {
-  const int64_t b = (units + 255) / 256;
-  return (int)(b < 1 ? 1 : (b > 8192 ? 8192 : b));
-}
-
 static const char* grid_error(int H, int W, int th, int tw) {
   if (H <= 0 || W <= 0) return "empty image";
   if (th < 32 || tw < 32 || th % 16 || tw % 16) return "tile sides must be multiples of 16, at least 32";
@@ -72,25 +66,26 @@ static const char* grid_error(int H, int W, int th, int tw) {
 }  // namespace dsic
 
 // The argument checks of a gather / stitch call over tiles first_tile .. first_tile + n_tiles - 1 (names as in the
-// exports), leaving the grid `g` and the launch grid `grid`; and those of a call that writes a window.
-#define DSIC_TILE_ARGS_OV(what, overlap)                                                                     \
-  const char* ge = grid_error(H, W, th, tw);                                                                 \
-  DSIC_REQUIRE(!ge, what ": %s (H=%d W=%d th=%d tw=%d)", ge ? ge : "", H, W, th, tw);                        \
-  DSIC_REQUIRE(overlap_ok(th, tw, overlap), what ": overlap=%d must be a multiple of 16 in 0..min(th, tw)/2", \
-               overlap);                                                                                     \
-  const Grid g = make_grid(H, W, th, tw, overlap);                                                           \
-  DSIC_REQUIRE(first_tile >= 0 && n_tiles > 0 && (int64_t)first_tile + n_tiles <= (int64_t)g.ny * g.nx,      \
-               what ": tiles [%d, %d) outside the grid of %d", first_tile, first_tile + n_tiles, g.ny * g.nx); \
-  DSIC_REQUIRE(n_tiles <= 65535, what ": at most 65535 tiles per call");                                   \
+// exports; `what` is a string, not only a literal), leaving the grid `g` and the launch grid `grid`; and those of a
+// call that writes a window.
+#define DSIC_TILE_ARGS_OV(what, overlap)                                                                           \
+  const char* ge = grid_error(H, W, th, tw);                                                                       \
+  DSIC_REQUIRE(!ge, "%s: %s (H=%d W=%d th=%d tw=%d)", what, ge ? ge : "", H, W, th, tw);                           \
+  DSIC_REQUIRE(overlap_ok(th, tw, overlap), "%s: overlap=%d must be a multiple of 16 in 0..min(th, tw)/2", what,   \
+               overlap);                                                                                           \
+  const Grid g = make_grid(H, W, th, tw, overlap);                                                                 \
+  DSIC_REQUIRE(first_tile >= 0 && n_tiles > 0 && (int64_t)first_tile + n_tiles <= (int64_t)g.ny * g.nx,            \
+               "%s: tiles [%d, %d) outside the grid of %d", what, first_tile, first_tile + n_tiles, g.ny * g.nx);  \
+  DSIC_REQUIRE(n_tiles <= 65535, "%s: at most 65535 tiles per call", what);                                        \
   const dim3 grid(g.th / kTileRows, n_tiles, 1)
 #define DSIC_TILE_ARGS(what) DSIC_TILE_ARGS_OV(what, 0)
 
-#define DSIC_WINDOW_ARGS(what)                                                                                \
-  const char* ge = grid_error(H, W, th, tw);                                                                  \
-  DSIC_REQUIRE(!ge, what ": %s (H=%d W=%d th=%d tw=%d)", ge ? ge : "", H, W, th, tw);                         \
-  const Grid g = make_grid(H, W, th, tw);                                                                     \
-  DSIC_REQUIRE(wy0 >= 0 && wx0 >= 0 && wh >= 1 && ww >= 1 && (int64_t)wy0 + wh <= H && (int64_t)wx0 + ww <= W, \
-               what ": window %dx%d at (%d, %d) outside the %dx%d image", wh, ww, wy0, wx0, H, W);           \
-  DSIC_REQUIRE(n_tiles >= 1 && n_tiles <= 65535, what ": n=%d tiles per call (1..65535)", n_tiles);           \
-  const Clip clip = {wy0, wy0 + wh, wx0, wx0 + ww};                                                           \
+#define DSIC_WINDOW_ARGS(what)                                                                                     \
+  const char* ge = grid_error(H, W, th, tw);                                                                       \
+  DSIC_REQUIRE(!ge, "%s: %s (H=%d W=%d th=%d tw=%d)", what, ge ? ge : "", H, W, th, tw);                           \
+  const Grid g = make_grid(H, W, th, tw);                                                                          \
+  DSIC_REQUIRE(wy0 >= 0 && wx0 >= 0 && wh >= 1 && ww >= 1 && (int64_t)wy0 + wh <= H && (int64_t)wx0 + ww <= W,     \
+               "%s: window %dx%d at (%d, %d) outside the %dx%d image", what, wh, ww, wy0, wx0, H, W);              \
+  DSIC_REQUIRE(n_tiles >= 1 && n_tiles <= 65535, "%s: n=%d tiles per call (1..65535)", what, n_tiles);             \
+  const Clip clip = {wy0, wy0 + wh, wx0, wx0 + ww};                                                                \
   const dim3 grid(g.th / kTileRows, n_tiles, 1)

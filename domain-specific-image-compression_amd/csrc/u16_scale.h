@@ -75,16 +75,17 @@ static const char* scale_error(const uint32_t* lohi, int C, Scale* s) {
 
 }  // namespace dsic
 
+// `what` is a string, not only a literal
 #define DSIC_U16_COMMON(what, img)                                                                                  \
-  DSIC_REQUIRE(C >= 1 && C <= 4, what ": C=%d must be in 1..4", C);                                                 \
-  DSIC_REQUIRE(((uintptr_t)(img) & 1) == 0, what ": the uint16 image must be 2-byte aligned")
+  DSIC_REQUIRE(C >= 1 && C <= 4, "%s: C=%d must be in 1..4", what, C);                                              \
+  DSIC_REQUIRE(((uintptr_t)(img) & 1) == 0, "%s: the uint16 image must be 2-byte aligned", what)
 #define DSIC_U16_SCALE(what)                                                          \
   Scale sc;                                                                           \
   const char* se = scale_error(lohi, C, &sc);                                         \
-  DSIC_REQUIRE(!se, what ": scale: %s", se ? se : "")
-#define DSIC_U16_ROW(what, W)                                                                                       \
-  DSIC_REQUIRE((int64_t)(W) * C * 2 <= INT_MAX, what ": a row of W=%d pixels of C=%d uint16 is over 2^31 - 1 bytes", \
-               (W), C)
+  DSIC_REQUIRE(!se, "%s: scale: %s", what, se ? se : "")
+#define DSIC_U16_ROW(what, W)                                                                                         \
+  DSIC_REQUIRE((int64_t)(W) * C * 2 <= INT_MAX, "%s: a row of W=%d pixels of C=%d uint16 is over 2^31 - 1 bytes", \
+               what, (W), C)
 #define DSIC_U16_BY_C(kernel, ...)                                                    \
   switch (C) {                                                                        \
     case 1: hipLaunchKernelGGL(kernel<1>, __VA_ARGS__); break;                        \

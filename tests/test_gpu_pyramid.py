@@ -30,7 +30,8 @@ GUARD = 64                                   # elements on either side of an out
 U8_GUARD, U8_FILL, U8_PAD = 0xCD, 0x5A, 0xEE
 F32_FILL, F32_PAD = -7.0, 1e30
 SIZES = [(1, 1), (1, 2), (2, 1), (2, 2), (3, 5), (17, 33), (33, 35), (40, 34), (64, 36), (50, 100), (70, 1030)]
-KINDS = [("u8", 3), ("u8", 4), ("f32", 1), ("f32", 3), ("f32", 4)]
+# uint8: 1 .. 4 channels are the instantiations with a window path, 5 goes tap by tap with C at run time
+KINDS = [("u8", 1), ("u8", 2), ("u8", 3), ("u8", 4), ("u8", 5), ("f32", 1), ("f32", 3), ("f32", 4)]
 _CACHE = {}
 
 

@@ -200,7 +200,7 @@ def test_gather_stitch_and_finish_equal_the_restatement(H, W, tile, C):
 
 
 @pytest.mark.parametrize("H,W", SIZES)
-@pytest.mark.parametrize("C", [1, 3, 4])
+@pytest.mark.parametrize("C", [1, 2, 3, 4])
 def test_halving_equals_the_restatement(H, W, C):
     L = lib.load()
     rng = np.random.default_rng(H * 100003 + W * 101 + C)

@@ -5,7 +5,9 @@
     python tools/pyramid_bench.py pyramid [--size 2048] [--overviews 3] [--reps 10]
     python tools/pyramid_bench.py levels  [--size 2048] [--overviews 3] [--reps 10]
 
-halve: one dsic_image_halve_u8 / _f32 launch on a size x size x 3 image, device events around back-to-back launches
+halve: one dsic_image_halve_u8 / _u16 / _f32 / _valid_u8 / _valid_u16 launch on a size x size x 3 image (the masked
+ones with a size x size validity image beside it, about one pixel in eight invalid), device events around back-to-back
+launches
 that walk through enough distinct images (over 512 MB) that no launch finds its source in the last-level cache; beside
 it the bytes the launch moves (source read once, destination written once) over the copy bandwidth of tools/hbm_bw.py's
 probe (2.1 GB read and written), taken in the same process.
@@ -81,19 +83,34 @@ def halve(a):
     copy_tbs = 2 * x.numel() * 4 / 1e9 / copy_ms
     del x, y
     res = {"size": n, "probe_copy_TBps": round(copy_tbs, 3), "kinds": {}}
-    for kind in ("u8", "f32"):
-        if kind == "u8":
-            src_bytes, dst_bytes = n * n * 3, h * h * 3
-            k = -(-512 * 2 ** 20 // src_bytes)
-            srcs = [torch.randint(0, 256, (n, n, 3), dtype=torch.uint8, device="cuda") for _ in range(k)]
-            dsts = [torch.empty((h, h, 3), dtype=torch.uint8, device="cuda") for _ in range(k)]
-            fn = lambda i: L.dsic_image_halve_u8(_p(srcs[i % k]), _p(dsts[i % k]), n, n, 3, _stream())
-        else:
+    for kind in ("u8", "u16", "f32", "valid_u8", "valid_u16"):
+        if kind == "f32":
             src_bytes, dst_bytes = 4 * n * n * 3, 4 * h * h * 3
             k = -(-512 * 2 ** 20 // src_bytes)
             srcs = [torch.rand((3, n, n), dtype=torch.float32, device="cuda") for _ in range(k)]
             dsts = [torch.empty((3, h, h), dtype=torch.float32, device="cuda") for _ in range(k)]
             fn = lambda i: L.dsic_image_halve_f32(_p(srcs[i % k]), _p(dsts[i % k]), 3, n, n, _stream())
+        else:
+            wide, masked = kind.endswith("u16"), kind.startswith("valid")
+            es = 2 if wide else 1
+            src_bytes, dst_bytes = (3 * es + masked) * n * n, (3 * es + masked) * h * h
+            k = -(-512 * 2 ** 20 // src_bytes)
+            dt = torch.uint16 if wide else torch.uint8
+            if wide:                                                     # random bits, seen as uint16
+                srcs = [torch.randint(-32768, 32768, (n, n, 3), dtype=torch.int16, device="cuda").view(dt)
+                        for _ in range(k)]
+            else:
+                srcs = [torch.randint(0, 256, (n, n, 3), dtype=dt, device="cuda") for _ in range(k)]
+            dsts = [torch.empty((h, h, 3), dtype=dt, device="cuda") for _ in range(k)]
+            if masked:
+                svals = [(torch.randint(0, 8, (n, n), device="cuda") != 0).to(torch.uint8) for _ in range(k)]
+                dvals = [torch.empty((h, h), dtype=torch.uint8, device="cuda") for _ in range(k)]
+                call = L.dsic_image_halve_valid_u16 if wide else L.dsic_image_halve_valid_u8
+                fn = lambda i: call(_p(srcs[i % k]), _p(svals[i % k]), _p(dsts[i % k]), _p(dvals[i % k]), n, n, 3,
+                                    _stream())
+            else:
+                call = L.dsic_image_halve_u16 if wide else L.dsic_image_halve_u8
+                fn = lambda i: call(_p(srcs[i % k]), _p(dsts[i % k]), n, n, 3, _stream())
         lib.check(fn(0), "image_halve_" + kind)
         _event_ms(fn, 2 * k)
         runs = [_event_ms(fn, 10 * k) for _ in range(5)]
@@ -103,7 +120,8 @@ def halve(a):
                               "ms_runs": [round(r, 5) for r in runs], "bytes_moved": moved,
                               "TBps": round(moved / 1e9 / ms, 3),
                               "floor_ms_at_probe": round(moved / 1e9 / copy_tbs, 5)}
-        del srcs, dsts
+        del srcs, dsts, fn
+        svals = dvals = None
     return res
 
 
