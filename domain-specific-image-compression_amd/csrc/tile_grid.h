@@ -1,6 +1,8 @@
 // The tile grid of the whole-image codec (codec.tile_grid) as the kernels of image_codec.hip and mask.hip see it:
 // the geometry, the part of the image a tile owns, the window a call writes to, and the argument check of a grid.
 #pragma once
+#include <limits.h>
+
 #include "common.h"
 
 namespace dsic {
@@ -57,6 +59,12 @@ static bool overlap_ok(int th, int tw, int O) { return O >= 0 && O % 16 == 0 && 
 
 static const char* grid_error(int H, int W, int th, int tw) {
   if (H <= 0 || W <= 0) return "empty image";
+  // Hp, Wp, row and column numbers and every tile number are ints.  A side of at most 2^30 keeps (i + 1) * th and
+  // (i + 1) * sy + O of owned() and the blend, which pass Hp by less than a tile, under 2^31; a tile has at least
+  // 16 x 16 pixels of stride at any overlap, so with at most 2^31 - 1 blocks of 16 x 16 in the padded image ny * nx
+  // (the kernels' product) stays inside int
+  if (H > (1 << 30) || W > (1 << 30) || ((int64_t)H + 15) / 16 * (((int64_t)W + 15) / 16) > INT_MAX)
+    return "a side is over 2^30 pixels or the padded image has over 2^31 - 1 blocks of 16 x 16 pixels";
   if (th < 32 || tw < 32 || th % 16 || tw % 16) return "tile sides must be multiples of 16, at least 32";
   if (round_up(H, 16) - H >= H || round_up(W, 16) - W >= W) return "padding must be smaller than the image";
   if (th > round_up(H, 16) || tw > round_up(W, 16)) return "tile larger than the padded image";

@@ -447,6 +447,10 @@ int dsic_range_decode_seg(const uint8_t* in, int64_t stride, const int* lengths,
  * size): Hp = ceil16(H), tiles_y = ceil(Hp/th), origin of tile row i = min(i*th, Hp-th), tile
  * row i owns padded rows [i*th, min((i+1)*th, Hp)); columns likewise; tiles numbered row-major.
  * Padding to Hp x Wp reflects bottom/right as dsic_reflect_pad_br does (Hp-H < H, Wp-W < W).
+ * Every call that takes a tile grid (gather, stitch, blend, the mask and validity calls, the
+ * residual calls) refuses an image with a side over 2^30 pixels or whose padded size holds over
+ * 2^31 - 1 blocks of 16 x 16 pixels (about 2^39 pixels): row, column and tile numbers are ints.
+ * Below that, offsets into the image are 64-bit.
  * The calls handle tiles [first_tile, first_tile+n_tiles) of the grid.
  * gather: img uint8 [H][W][C] (C 3 or 4) -> tiles uint8 [n][th][tw][C], or img float32
  *   [C][H][W] -> tiles float32 [n][C][th][tw]; tiles 16-byte aligned.

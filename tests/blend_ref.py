@@ -56,10 +56,14 @@ def axis(L, tile, O):
             "sup": [(a[i], a[i + 1] + O) if i < n - 1 else (a[i], Lp) for i in range(n)]}
 
 
-def _ramps(ax, O, up, down, one, zero):
-    """[n][Lp] weights; up(k) / down(k) give the ramp values."""
+def _ramps(ax, O, up, down, one, zero, only=None):
+    """[n][Lp] weights; up(k) / down(k) give the ramp values.  only: the tiles whose rows are wanted; the others' rows
+    are left empty (an axis of thousands of tiles)."""
     out = []
     for i in range(ax["n"]):
+        if only is not None and i not in only:
+            out.append(None)
+            continue
         lo, hi = ax["sup"][i]
         w = [zero] * ax["Lp"]
         for p in range(lo, hi):
@@ -79,12 +83,14 @@ def weights_exact(ax, O):
                   Fraction(1), Fraction(0))
 
 
-def weights_f32(ax, O):
-    """[n][Lp] float32, as the kernel computes them."""
+def weights_f32(ax, O, only=None):
+    """[n][Lp] float32, as the kernel computes them; with `only`, a dict of the rows of those tiles."""
     rcp = np.float32(1.0) / np.float32(2 * O) if O else np.float32(0)
-    return np.array(_ramps(ax, O, lambda k: np.float32(2 * k + 1) * rcp,
-                           lambda k: np.float32(2 * (O - 1 - k) + 1) * rcp, np.float32(1), np.float32(0)),
-                    dtype=np.float32)
+    rows = _ramps(ax, O, lambda k: np.float32(2 * k + 1) * rcp, lambda k: np.float32(2 * (O - 1 - k) + 1) * rcp,
+                  np.float32(1), np.float32(0), only)
+    if only is not None:
+        return {i: np.array(r, dtype=np.float32) for i, r in enumerate(rows) if r is not None}
+    return np.array(rows, dtype=np.float32)
 
 
 def weights_f64(ax, O):
@@ -114,11 +120,17 @@ def make_tiles(case, C, seed=0):
     return rng.uniform(-0.2, 1.2, size=(ay["n"] * ax["n"], C, ay["t"], ax["t"])).astype(np.float32)
 
 
-def _blend(batches, H, W, C, th, tw, O, wfun, dtype):
+def _blend(batches, H, W, C, th, tw, O, wfun, dtype, rows=None):
+    """rows = (y0, y1): only the rows [y0, y1) of the canvas, as [C][y1 - y0][W]; the weights of the listed tiles only"""
     ay, ax = grid(H, W, th, tw, O)
-    wy, wx = wfun(ay, O), wfun(ax, O)
-    canvas = np.zeros((C, H, W), dtype=dtype)
-    mass = np.zeros((C, H, W), dtype=dtype)
+    y0, y1 = (0, H) if rows is None else rows
+    if rows is None:
+        wy, wx = wfun(ay, O), wfun(ax, O)
+    else:
+        ids = [t for batch in batches for t, _ in batch]
+        wy, wx = wfun(ay, O, {t // ax["n"] for t in ids}), wfun(ax, O, {t % ax["n"] for t in ids})
+    canvas = np.zeros((C, y1 - y0, W), dtype=dtype)
+    mass = np.zeros((C, y1 - y0, W), dtype=dtype)
     last = -1
     for batch in batches:
         for t, x in batch:
@@ -126,20 +138,23 @@ def _blend(batches, H, W, C, th, tw, O, wfun, dtype):
             last = t
             i, j = divmod(t, ax["n"])
             (ya, yb), (xa, xb) = ay["sup"][i], ax["sup"][j]
-            yb, xb = min(yb, H), min(xb, W)
+            ya, yb, xb = max(ya, y0), min(yb, H, y1), min(xb, W)
+            if ya >= yb:
+                continue
             oy, ox = ay["o"][i], ax["o"][j]
             wgt = (wy[i][ya:yb, None] * wx[j][None, xa:xb]).astype(dtype)
             v = np.clip(np.asarray(x, dtype=np.float32)[:, ya - oy:yb - oy, xa - ox:xb - ox], 0, 1).astype(dtype)
             c = (wgt[None] * v).astype(dtype)
-            canvas[:, ya:yb, xa:xb] = canvas[:, ya:yb, xa:xb] + c
-            mass[:, ya:yb, xa:xb] += np.abs(c)
+            canvas[:, ya - y0:yb - y0, xa:xb] = canvas[:, ya - y0:yb - y0, xa:xb] + c
+            mass[:, ya - y0:yb - y0, xa:xb] += np.abs(c)
     return canvas, mass
 
 
-def blend_f32(batches, H, W, C, th, tw, O):
+def blend_f32(batches, H, W, C, th, tw, O, rows=None):
     """The float32 fold over batches (lists of (tile id, float32 [C][th][tw])), ascending: the unfinished canvas
-    [C][H][W].  How the tiles are cut into batches does not enter: the fold runs in tile order."""
-    return _blend(batches, H, W, C, th, tw, O, weights_f32, np.float32)[0]
+    [C][H][W], or its rows [y0, y1) for rows = (y0, y1).  How the tiles are cut into batches does not enter: the fold
+    runs in tile order."""
+    return _blend(batches, H, W, C, th, tw, O, weights_f32, np.float32, rows)[0]
 
 
 def blend_f64(batches, H, W, C, th, tw, O):

@@ -51,18 +51,29 @@ def _reflect(L, P):
     return np.where(p < L, p, 2 * (L - 1) - p)
 
 
-def gather_u8(img_hwc, th, tw):
+def _origins(H, W, th, tw, overlap):
+    """(row origins, column origins) of the tiles; with an overlap they are blend_ref.axis' (the grid of the seams)"""
+    if not overlap:
+        g = grid(H, W, th, tw)
+        return g["ys"], g["xs"]
+    import blend_ref
+    ay, ax = blend_ref.axis(H, th, overlap), blend_ref.axis(W, tw, overlap)
+    assert ay["t"] == th and ax["t"] == tw
+    return ay["o"], ax["o"]
+
+
+def gather_u8(img_hwc, th, tw, overlap=0):
     H, W = img_hwc.shape[:2]
-    g = grid(H, W, th, tw)
-    ry, rx = _reflect(H, g["Hp"]), _reflect(W, g["Wp"])
-    return np.stack([img_hwc[ry[y:y + th]][:, rx[x:x + tw]] for y in g["ys"] for x in g["xs"]])
+    ys, xs = _origins(H, W, th, tw, overlap)
+    ry, rx = _reflect(H, ceil16(H)), _reflect(W, ceil16(W))
+    return np.stack([img_hwc[ry[y:y + th]][:, rx[x:x + tw]] for y in ys for x in xs])
 
 
-def gather_f32(img_chw, th, tw):
+def gather_f32(img_chw, th, tw, overlap=0):
     H, W = img_chw.shape[1:]
-    g = grid(H, W, th, tw)
-    ry, rx = _reflect(H, g["Hp"]), _reflect(W, g["Wp"])
-    return np.stack([img_chw[:, ry[y:y + th]][:, :, rx[x:x + tw]] for y in g["ys"] for x in g["xs"]])
+    ys, xs = _origins(H, W, th, tw, overlap)
+    ry, rx = _reflect(H, ceil16(H)), _reflect(W, ceil16(W))
+    return np.stack([img_chw[:, ry[y:y + th]][:, :, rx[x:x + tw]] for y in ys for x in xs])
 
 
 def clamp01(x):

@@ -42,8 +42,19 @@ def m_plane(mask, tile, th, tw):
     return m
 
 
+def tile_row(H, W, th, tw, i):
+    """the tiles of tile row i, as tiles() lists them"""
+    oy, y0, y1 = axis(H, th)[i]
+    return [(oy, ox, y0, y1, x0, x1) for ox, x0, x1 in axis(W, tw)]
+
+
+def counts_in(mask, rects):
+    """per tile of rects (entries of tiles()) the set pixels of the mask among its owned pixels"""
+    return [int(mask[y0:y1, x0:x1].sum()) for _, _, y0, y1, x0, x1 in rects]
+
+
 def counts(mask, H, W, th, tw):
-    return [int(mask[y0:y1, x0:x1].sum()) for _, _, y0, y1, x0, x1 in tiles(H, W, th, tw)]
+    return counts_in(mask, tiles(H, W, th, tw))
 
 
 def states(mask, H, W, th, tw):
