@@ -25,6 +25,7 @@
 #include <limits.h>
 
 #include "common.h"
+#include "render.h"
 
 namespace dsic {
 
@@ -131,17 +132,7 @@ __global__ __launch_bounds__(VIEW_BX * VIEW_BY) void resample_int_kernel(const T
 // The rendered window (dsic_window_render_u8 / _u16): resample_pixel, then output band b = channel r.band[b] of it
 // stretched to a byte with r.lo[b], r.hi[b], then alpha.  A thread packs its nb + alpha bytes into one word: a wave
 // stores one run of 64 (nb + alpha) bytes, a dword per lane where that is 4 bytes at an aligned address.
-struct Render {
-  int nb, alpha, background, need;
-  int band[3];
-  uint32_t lo[3], hi[3];
-};
-
-__device__ __forceinline__ uint32_t stretch_byte(uint32_t m, uint32_t lo, uint32_t hi) {
-  const uint32_t R = hi - lo, d = min(max(m, lo), hi) - lo;
-  return R ? (510u * d + R) / (2u * R) : 0u;  // 255 d / R rounded half up; 510 * 65535 + 65535 < 2^32
-}
-
+// Render and stretch_byte: render.h, shared with warp.hip.
 template <typename T, bool V>
 __global__ __launch_bounds__(VIEW_BX * VIEW_BY) void render_kernel(const T* __restrict__ src,
                                                                    const uint8_t* __restrict__ sval,

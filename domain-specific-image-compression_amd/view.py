@@ -6,7 +6,9 @@ against the model), keeps decoded tiles on the device, decodes the tiles that se
 batches (read_many), and resamples a window of the best-fitting overview to the size asked for (csrc/view.hip).
 render turns such a window into display pixels in the same launch: chosen bands, stretched to 8 bits between two
 values per band, with the validity as an alpha channel; histogram and stretch derive those values from the data
-(csrc/histogram.hip, stretch_from_histogram).
+(csrc/histogram.hip, stretch_from_histogram).  read_warped and render_warped do both for an affine view: a 2 x 3
+matrix quantised once to Q16 (affine_q16), the level its scale asks for (warp_level), the window of that level which
+holds every tap (warp_window), and one launch of the bilinear, cubic or nearest sampler (csrc/warp.hip).
 
 The cache holds what the stitch and blend calls consume: per (level, tile) the tile's g_s output, float32
 [C, th, tw], not clamped, and for a near-lossless level its q plane.  A window is served by collecting its tiles, in
@@ -20,6 +22,7 @@ from __future__ import annotations
 import collections
 import copy
 import ctypes
+import math
 import operator
 
 import numpy as np
@@ -44,6 +47,115 @@ def view_level(n_levels, h, w, oh, ow) -> int:
         if (oh << l) <= h and (ow << l) <= w:
             return l
     return 0
+
+
+# ---- warped reads: an affine view, csrc/warp.hip ---------------------------------------------------------------------
+WARP_RESAMPLING = {"bilinear": 0, "nearest": 1, "cubic": 2}
+WARP_COEF, WARP_SHIFT, WARP_SIDE = 1 << 26, 1 << 47, 1 << 20     # Q16 bounds of a matrix, and the largest output side
+
+
+def affine_q16(matrix) -> tuple:
+    """A 2 x 3 matrix [[m00, m01, m02], [m10, m11, m12]] in (row, column) order, level-0 pixels per output pixel
+    (output pixel (i, j) samples y = m00 (i + 1/2) + m01 (j + 1/2) + m02, x likewise) -> its six entries as Q16
+    integers, round(v * 65536) with Python's round (pure Python).  Everything downstream works on these six integers.
+    ValueError for anything that is not six finite numbers, |m00|, |m01|, |m10|, |m11| over 2^26 or |m02|, |m12| >=
+    2^47 in Q16 (1024 and 2^31 pixels): the bounds keep every product of the geometry under 2^63."""
+    try:
+        rows = [list(row) for row in matrix]
+        if len(rows) != 2 or any(len(row) != 3 for row in rows):
+            raise TypeError
+        q = tuple(int(round(v * 65536)) for row in rows for v in row)
+    except (TypeError, ValueError, OverflowError):
+        raise ValueError(f"affine_q16: matrix={matrix!r} is not two rows of three finite numbers") from None
+    return check_q16(q)
+
+
+def check_q16(m) -> tuple:
+    """Six Q16 integers within affine_q16's bounds, as a tuple."""
+    try:
+        m = tuple(operator.index(v) for v in m)
+    except TypeError:
+        raise ValueError(f"matrix_q16={m!r} is not six integers") from None
+    if len(m) != 6:
+        raise ValueError(f"matrix_q16={m!r} is not six integers")
+    for k, v in enumerate(m):
+        if k % 3 == 2 and abs(v) >= WARP_SHIFT:
+            raise ValueError(f"affine matrix: the offset {v} / 65536 must be under 2^31 pixels in size")
+        if k % 3 != 2 and abs(v) > WARP_COEF:
+            raise ValueError(f"affine matrix: the coefficient {v} / 65536 must be at most 1024 in size")
+    return m
+
+
+def window_affine(y0, x0, h, w, oh, ow) -> list:
+    """The matrix of the crop of the level-0 window (y0, x0, h, w) to oh x ow pixels: [[h/oh, 0, y0], [0, w/ow, x0]]."""
+    if oh < 1 or ow < 1:
+        raise ValueError(f"window_affine: size ({oh}, {ow}) must be at least (1, 1)")
+    return [[h / oh, 0, y0], [0, w / ow, x0]]
+
+
+def rotation_affine(cy, cx, degrees, scale, oh, ow) -> list:
+    """The matrix of a view of oh x ow pixels centred on the level-0 position (cy, cx), at `scale` level-0 pixels per
+    output pixel, the image turned counter-clockwise by `degrees` (90: the view is np.rot90 of the axis-aligned one).
+    Multiples of 90 degrees take exact sines and cosines."""
+    if oh < 1 or ow < 1:
+        raise ValueError(f"rotation_affine: size ({oh}, {ow}) must be at least (1, 1)")
+    quarter, rest = divmod(degrees, 90)
+    if rest == 0:
+        c, s = ((1, 0), (0, 1), (-1, 0), (0, -1))[int(quarter) % 4]
+    else:
+        c, s = math.cos(math.radians(degrees)), math.sin(math.radians(degrees))
+    a, b = scale * c, scale * s
+    return [[a, b, cy - (a * oh + b * ow) / 2], [-b, a, cx - (-b * oh + a * ow) / 2]]
+
+
+def warp_level(n_levels, m) -> int:
+    """The overview level to sample a view with the Q16 matrix m from (pure Python integers): the largest
+    l < n_levels with 4^l 2^32 <= min(m00^2 + m10^2, m01^2 + m11^2), else 0: the coarsest level that the shorter of
+    the two output steps does not magnify.  A view minified past the coarsest level is sampled sparsely: the samplers
+    interpolate between the 2 x 2 or 4 x 4 pixels around each position and average nothing beyond them."""
+    n_levels, m = operator.index(n_levels), check_q16(m)
+    if n_levels < 1:
+        raise ValueError(f"warp_level: {n_levels} level(s)")
+    step = min(m[0] * m[0] + m[3] * m[3], m[1] * m[1] + m[4] * m[4])
+    for l in range(n_levels - 1, 0, -1):
+        if (1 << (2 * l + 32)) <= step:
+            return l
+    return 0
+
+
+def _warp_axis(m3, oh, ow, N, L, l, mode):
+    """One axis of warp_window: the level indices (first, last) that the taps of all inside samples can take, from the
+    positions of the four corner pixels, or None if no sample is inside on this axis."""
+    P = [m3[0] * (2 * i + 1) + m3[1] * (2 * j + 1) + 2 * m3[2] for i in (0, oh - 1) for j in (0, ow - 1)]
+    lo, hi = min(P), max(P)
+    if hi < 0 or lo >= N << 17:
+        return None
+    lo, hi = max(lo, 0), min(hi, (N << 17) - 1)
+    if mode == 1:
+        a, b = lo >> (17 + l), hi >> (17 + l)
+    else:
+        before, after = (1, 2) if mode == 2 else (0, 1)
+        a, b = ((lo - (1 << (16 + l))) >> (17 + l)) - before, ((hi - (1 << (16 + l))) >> (17 + l)) + after
+    return min(max(a, 0), L - 1), min(max(b, 0), L - 1)
+
+
+def warp_window(level, LH, LW, H, W, m, oh, ow, mode):
+    """The window (y0, x0, h, w) of overview level `level` (LH x LW, of an H x W image) that holds every tap of the
+    view with the Q16 matrix m and oh x ow pixels, mode 0 bilinear, 1 nearest, 2 cubic (pure Python integers): the
+    positions are affine in (i, j) and the floor is monotone, so per axis the range is exact at the four corner
+    pixels; it is cut to the image, widened by the mode's taps and clamped to the level.  None when the corner
+    positions' bounding box misses the image entirely: every pixel is fill.  dsic_window_warp_u8 / _u16 refuse a source
+    window that does not contain this one."""
+    m = check_q16(m)
+    level, LH, LW, H, W, oh, ow, mode = (operator.index(v) for v in (level, LH, LW, H, W, oh, ow, mode))
+    if not (1 <= oh <= WARP_SIDE and 1 <= ow <= WARP_SIDE):
+        raise ValueError(f"warp_window: size ({oh}, {ow}) must be (1, 1) .. (2^20, 2^20)")
+    if mode not in (0, 1, 2) or level < 0 or min(LH, LW, H, W) < 1:
+        raise ValueError(f"warp_window: mode {mode}, level {level}, {LH}x{LW} of {H}x{W}")
+    ys, xs = _warp_axis(m[:3], oh, ow, H, LH, level, mode), _warp_axis(m[3:], oh, ow, W, LW, level, mode)
+    if ys is None or xs is None:
+        return None
+    return ys[0], xs[0], ys[1] - ys[0] + 1, xs[1] - xs[0] + 1
 
 
 def _check_percent(percent):
@@ -638,3 +750,110 @@ class ImageReader:
         imgs = [self._render(level, lw, view, d, resampling, st, shared) for (level, lw, view), d in zip(plans, displays)]
         self._finish(st, before, stats)
         return imgs
+
+    # ---- warped views -------------------------------------------------------------------------------------------
+    def _plan_warp(self, matrix, size, level, resampling, what):
+        """A warped request -> (level, the Q16 matrix, (oh, ow), mode, the level's window or None)."""
+        if resampling not in WARP_RESAMPLING:
+            raise ValueError(f"{what}: resampling={resampling!r} ({', '.join(WARP_RESAMPLING)})")
+        m = affine_q16(matrix)
+        try:
+            oh, ow = (operator.index(v) for v in size)
+        except (TypeError, ValueError):
+            raise ValueError(f"{what}: size={size!r} is not a pair of integers (oh, ow)") from None
+        if not (1 <= oh <= WARP_SIDE and 1 <= ow <= WARP_SIDE):
+            raise ValueError(f"{what}: size={size!r} must be (1, 1) .. (2^20, 2^20)")
+        if level is None:
+            level = warp_level(len(self.levels), m)
+        level = self._level(level)[0]
+        mode = WARP_RESAMPLING[resampling]
+        return level, m, (oh, ow), mode, warp_window(level, *self.levels[level], *self.levels[0], m, oh, ow, mode)
+
+    def _warp_source(self, level, lw, out, st):
+        """The planned window and, for a level with a validity mask, its validity: (image, validity or None)."""
+        valid = torch.ones((lw[2], lw[3]), dtype=torch.uint8, device=self._dev) if self._masked(level) else None
+        return self._window(level, lw, out, st, valid_out=valid), valid
+
+    @torch.no_grad()
+    def read_warped(self, matrix, size, level=None, resampling="bilinear", out=None, stats=None, with_valid=False):
+        """An affine view of the image: uint8 or uint16 [oh, ow, C] on the device, size = (oh, ow), in one launch
+        (dsic_window_warp_u8 / _u16).  matrix: 2 x 3 in (row, column) order, level-0 pixels per output pixel: output
+        pixel (i, j) samples the level-0 position y = m00 (i + 1/2) + m01 (j + 1/2) + m02, x likewise, so that
+        window_affine(y0, x0, h, w, oh, ow) is the crop read(y0, x0, h, w, size=(oh, ow)) resamples and
+        rotation_affine(...) a turned view.  It is quantised once to Q16 (affine_q16); all geometry after that is
+        integer and the result is defined bit for bit (include/dsic_hip.h).
+        resampling: "bilinear" (2 x 2 taps, 7 phase bits per axis), "cubic" (Keys a = -1/2 over 4 x 4 taps, clamped to
+        the sample range; the bilinear pixel where a tap does not count) or "nearest".  A sample position outside the
+        image gives fill in every channel: the stream's fill, its nodata value, or 0.  Taps that a validity mask
+        (version 8) or a nodata value (version 5) excludes stay out of the interpolation; nothing left gives fill.
+        The level sampled is `level`, or warp_level(number of levels, the Q16 matrix); the window of it that holds
+        every tap (warp_window) comes in as read brings a window in, through the cache.  A view wholly beside the
+        image decodes nothing and launches nothing.
+        with_valid = True returns (image, valid), valid torch.bool [oh, ow]: False outside the image and where nothing
+        counted under the pixel.
+        stats: as read's, with level, level_window (None beside the image) and matrix_q16.
+        ValueError for a matrix or size out of bounds, an unknown resampling, a level the stream does not hold, and a
+        result that would be float32 (a float32-kind stream with out=None, or out="f32"): take out="u8"."""
+        what = "ImageReader.read_warped"
+        _c._check_out(out, None, what)
+        before, st = self._source.bytes_read, _new_stats()
+        level, m, (oh, ow), mode, lw = self._plan_warp(matrix, size, level, resampling, what)
+        ix = self._open[level][1]
+        kind = _c._check_out(out, ix, what)
+        if kind == _c.KIND_F32_CHW:
+            raise ValueError(f"{what}: the result would be float32; the warped samplers are integer, take out='u8'")
+        fill = ix.get("fill", ix.get("nodata", 0))
+        dtype = torch.uint16 if kind == _c.KIND_U16_HWC else torch.uint8
+        if lw is None:
+            host = np.full((oh, ow, ix["C"]), fill, dtype=np.uint16 if dtype == torch.uint16 else np.uint8)
+            img = torch.from_numpy(host).to(self._dev)
+            oval = torch.zeros((oh, ow), dtype=torch.uint8, device=self._dev)
+        else:
+            src, valid = self._warp_source(level, lw, out, st)
+            img = torch.empty((oh, ow, ix["C"]), dtype=dtype, device=self._dev)
+            oval = torch.empty((oh, ow), dtype=torch.uint8, device=self._dev) if with_valid else None
+            fn = "window_warp_u16" if dtype == torch.uint16 else "window_warp_u8"
+            H, W = self.levels[0]
+            status = getattr(_lib.load(), "dsic_" + fn)(
+                _p(src), None if valid is None else _p(valid), lw[2], lw[3], lw[0], lw[1], ix["C"], level,
+                *self.levels[level], H, W, (ctypes.c_int64 * 6)(*m), _p(img), None if oval is None else _p(oval), oh, ow,
+                mode, ix.get("nodata", -1), fill, _stream())
+            _lib.check(status, fn)
+        st.update(level=level, level_window=lw, matrix_q16=m)
+        self._finish(st, before, stats)
+        return (img, oval.bool()) if with_valid else img
+
+    @torch.no_grad()
+    def render_warped(self, matrix, size, level=None, bands=None, stretch=None, alpha=False, background=0,
+                      resampling="bilinear", stats=None):
+        """The affine view read_warped(matrix, size, level, resampling) as display pixels: torch.uint8
+        [oh, ow, nb (+ 1)] in one launch (dsic_window_warp_render_u8 / _u16); the samples never reach memory.  bands,
+        stretch, alpha and background are render's, with its default stretch.  Every valid pixel is the stretch of
+        read_warped's pixel, bit for bit; a pixel outside the image, or with nothing counting under it, is
+        `background` in every band and, with alpha = True, alpha 0.  So a view inside an image without a mask is the
+        stretch of read_warped throughout.  A float32-kind stream is rendered from its out="u8" form.
+        ValueError as read_warped and render raise it."""
+        what = "ImageReader.render_warped"
+        before, st = self._source.bytes_read, _new_stats()
+        level, m, (oh, ow), mode, lw = self._plan_warp(matrix, size, level, resampling, what)
+        bands, stretch, alpha, background = self._display(level, bands, stretch, alpha, background)
+        ix = self._open[level][1]
+        n = len(bands) + alpha
+        if lw is None:                                             # beside the image: no stretch needed, nothing decoded
+            img = torch.full((oh, ow, n), background, dtype=torch.uint8, device=self._dev)
+            if alpha:
+                img[:, :, n - 1] = 0
+        else:
+            stretch = self._default_stretch(level, stretch, st)
+            src, valid = self._warp_source(level, lw, self._display_out(ix)[0], st)
+            img = torch.empty((oh, ow, n), dtype=torch.uint8, device=self._dev)
+            fn = "window_warp_render_u16" if src.dtype == torch.uint16 else "window_warp_render_u8"
+            H, W = self.levels[0]
+            status = getattr(_lib.load(), "dsic_" + fn)(
+                _p(src), None if valid is None else _p(valid), lw[2], lw[3], lw[0], lw[1], ix["C"], level,
+                *self.levels[level], H, W, (ctypes.c_int64 * 6)(*m), (ctypes.c_int * len(bands))(*bands), len(bands),
+                _c._lohi(stretch), _p(img), oh, ow, mode, ix.get("nodata", -1), alpha, background, _stream())
+            _lib.check(status, fn)
+        st.update(level=level, level_window=lw, matrix_q16=m)
+        self._finish(st, before, stats)
+        return img

@@ -864,6 +864,55 @@ int dsic_band_histogram_u8(const uint8_t* img_hwc, const uint8_t* valid_hw, int 
 int dsic_band_histogram_u16(const uint16_t* img_hwc, const uint8_t* valid_hw, int H, int W, int C,
                             int nodata, uint32_t* hist, void* stream);
 
+/* ---- warped reads (codec.ImageReader.read_warped, .render_warped) ----
+ * An affine view of level 0 (H x W), sampled from a window of overview level `shift` (LH x LW, LH =
+ * ceil(H / 2^shift)): src holds sh x sw pixels of that level from its pixel (sy0, sx0), src_valid
+ * (NULL: none) their validity bytes.  m: six int64 on the host, the 2 x 3 matrix in (row, column)
+ * order in Q16, level-0 pixels per output pixel, read before the call returns.  All geometry is
+ * integer: output pixel (i, j) of oh x ow samples the level-0 position P / 2^17,
+ *   Py = m[0] (2 i + 1) + m[1] (2 j + 1) + 2 m[2],  Px = m[3] (2 i + 1) + m[4] (2 j + 1) + 2 m[5],
+ * and is inside iff 0 <= Py < H 2^17 and 0 <= Px < W 2^17; an outside pixel is fill in every
+ * channel and validity 0.  With q = P - 2^(16+shift), Y0 = q >> (17 + shift) and the phase p =
+ * (q >> (10 + shift)) & 127, tap indices clamped to the level:
+ * mode 1, nearest: pixel (min(Py >> (17 + shift), LH - 1), ...), a copy of pixel and validity.
+ * mode 0, bilinear: taps Y0, Y0 + 1 with weights (128 - p, p) per axis; S = sum wy wx v and T =
+ *   sum wy wx over the taps that count; (2 S + T) / (2 T); T = 0 gives fill and validity 0.
+ * mode 2, cubic: Keys a = -1/2, taps Y0 - 1 ... Y0 + 2, per-axis weights scaled by 2^22:
+ *   -p^3 + 256 p^2 - 16384 p, 3 p^3 - 640 p^2 + 2^22, -3 p^3 + 512 p^2 + 16384 p, p^3 - 128 p^2.
+ *   If all 16 clamped taps count: clamp((S + 2^43) >> 44, 0, 255 or 65535), S in int64;
+ *   otherwise the bilinear pixel.
+ * A tap counts iff its validity byte is not 0 (src_valid; nodata is then ignored), else iff its C
+ * channels do not all equal nodata (-1: none), else always.  dst_valid (NULL: none) is uint8
+ * [oh][ow] of 0 and 1.
+ * dsic_window_warp_render_u8 / _u16: the same sample, never stored, through the band choice,
+ *   stretch, alpha and background of dsic_window_render_u8 / _u16; a pixel whose validity would
+ *   be 0 gets background in every band and alpha 0.
+ * DSIC_EINVAL, nothing written: null pointers; C outside 3..4 (u8), 1..4 (u16; render: 1..4 for
+ *   both); mode outside 0..2; shift outside 0..15; LH or LW that is not the level's size; a source
+ *   window outside the level; oh or ow outside 1..2^20; |m[0]|, |m[1]|, |m[3]|, |m[4]| over 2^26 or
+ *   |m[2]|, |m[5]| >= 2^47; a source window that does not contain every tap of every inside sample
+ *   (the range is exact at the four corner pixels, widened by the mode's taps and clamped to the
+ *   level); nodata or fill beyond the element type; misaligned pointers; overlapping buffers; and
+ *   what dsic_window_render_u8 refuses of its display arguments. */
+int dsic_window_warp_u8(const uint8_t* src_hwc, const uint8_t* src_valid, int sh, int sw, int sy0,
+                        int sx0, int C, int shift, int LH, int LW, int H, int W, const int64_t* m,
+                        uint8_t* dst_hwc, uint8_t* dst_valid, int oh, int ow, int mode, int nodata,
+                        int fill, void* stream);
+int dsic_window_warp_u16(const uint16_t* src_hwc, const uint8_t* src_valid, int sh, int sw,
+                         int sy0, int sx0, int C, int shift, int LH, int LW, int H, int W,
+                         const int64_t* m, uint16_t* dst_hwc, uint8_t* dst_valid, int oh, int ow,
+                         int mode, int nodata, int fill, void* stream);
+int dsic_window_warp_render_u8(const uint8_t* src_hwc, const uint8_t* src_valid, int sh, int sw,
+                               int sy0, int sx0, int C, int shift, int LH, int LW, int H, int W,
+                               const int64_t* m, const int* bands, int nb, const uint32_t* lohi,
+                               uint8_t* dst, int oh, int ow, int mode, int nodata, int alpha,
+                               int background, void* stream);
+int dsic_window_warp_render_u16(const uint16_t* src_hwc, const uint8_t* src_valid, int sh, int sw,
+                                int sy0, int sx0, int C, int shift, int LH, int LW, int H, int W,
+                                const int64_t* m, const int* bands, int nb, const uint32_t* lohi,
+                                uint8_t* dst, int oh, int ow, int mode, int nodata, int alpha,
+                                int background, void* stream);
+
 /* HIP stream limited to the CUs whose bit is set in mask_host[words] (bit i of
  * word i/32 = CU i).  Used to give the range coder its own few CUs beside the
  * conv kernels; there is no reference counterpart (the reference is

@@ -7,9 +7,13 @@ an image.
     python tools/dsic_image.py decompress --weights CKPT.pt IN.dsic OUT.png [--out u8|f32|u16] [--region Y0,X0,H,W]
                                           [--level L] [--size OH,OW] [--resampling average|nearest]
                                           [--valid-out FILE.npy]
+                                          [--rotate DEG [--center Y,X] [--scale S] | --affine M00,M01,M02,M10,M11,M12]
+                                          [--resampling bilinear|cubic|nearest]
     python tools/dsic_image.py render     --weights CKPT.pt IN.dsic OUT [--region Y0,X0,H,W] [--size OH,OW] [--level L]
                                           [--bands B | B,B,B] [--stretch LO,HI[,LO,HI...]] [--percent P0,P1] [--alpha]
                                           [--background V] [--resampling average|nearest]
+                                          [--rotate DEG [--center Y,X] [--scale S] | --affine M00,M01,M02,M10,M11,M12]
+                                          [--resampling bilinear|cubic|nearest]
     python tools/dsic_image.py info       IN.dsic
 
 --segments K (2, 4, 8 or 16) codes every tile's y string as K independent strings, which a decoder reads on K waves per
@@ -47,6 +51,13 @@ validity mask of a version-8 stream as an alpha channel, --background V (0 .. 25
 region (default: the whole image) is in level-0 pixels with --size, else in --level's own.  OUT is .npy, a binary .ppm
 (three bands) or .pgm (one band), both without alpha, or .png where PIL is importable.  The level read and the stretch
 used are printed.
+--rotate DEG with --size OH,OW (decompress and render) reads an affine view instead of a window
+(codec.ImageReader.read_warped / render_warped): OH x OW pixels centred on the level-0 position --center Y,X (default:
+the image's centre), the image turned counter-clockwise by DEG degrees, at --scale S level-0 pixels per output pixel
+(default 1; codec.rotation_affine).  --affine M00,M01,M02,M10,M11,M12 gives the 2 x 3 matrix itself, in (row, column)
+order, level-0 pixels per output pixel.  Such a view is sampled with --resampling bilinear (the default), cubic or
+nearest from the level its scale asks for (or --level L); pixels outside the image are fill (render: --background, and
+alpha 0).  --region does not go with it.
 
 The state dict is loaded plain or from under "model" (code/modelv2/eval_selfcontained_entropy.py:130-134); the model's
 N, M, input channels and spatial_params are read from its shapes.  Images are PNG through PIL when PIL is importable
@@ -164,7 +175,68 @@ def write_display(path, a):
     return path
 
 
-def render_main(a, ap, region, size, level_given):
+def warp_matrix(a, ap, region, size):
+    """--rotate / --center / --scale / --affine -> the view's 2 x 3 matrix, or None for a plain window; every argument
+    error before the model is loaded.  Settles a.resampling for either kind of read."""
+    from dsic_amd import codec
+
+    def floats(text, n, name, what):
+        try:
+            values = [float(v) for v in text.split(",")]
+        except ValueError:
+            values = []
+        if len(values) != n:
+            ap.error(f"{name} {text}: {what}")
+        return values
+
+    warped = a.rotate is not None or a.affine is not None
+    if not warped:
+        if a.center is not None or (a.scale is not None and a.mode != "compress"):
+            ap.error("--center and --scale S go with --rotate" if a.mode != "compress" else "--center goes with --rotate")
+        if a.resampling in ("bilinear", "cubic"):
+            ap.error(f"--resampling {a.resampling} goes with --rotate or --affine")
+        a.resampling = a.resampling or "average"
+        return None
+    if a.mode not in ("decompress", "render"):
+        ap.error("--rotate and --affine go with decompress or render")
+    if a.rotate is not None and a.affine is not None:
+        ap.error("--rotate and --affine exclude each other")
+    if region is not None:
+        ap.error("--region does not go with --rotate or --affine: the matrix says where the view lies")
+    if size is None:
+        ap.error("--rotate and --affine need --size OH,OW")
+    if a.resampling == "average":
+        ap.error("--resampling average goes with --region; a warped view takes bilinear, cubic or nearest")
+    a.resampling = a.resampling or "bilinear"
+    if a.valid_out is not None:
+        ap.error("--valid-out does not go with --rotate or --affine")
+    if a.affine is not None:
+        if a.center is not None or a.scale is not None:
+            ap.error("--center and --scale go with --rotate")
+        values = floats(a.affine, 6, "--affine", "six numbers M00,M01,M02,M10,M11,M12")
+        matrix = [values[:3], values[3:]]
+    else:
+        scale = 1.0 if a.scale is None else floats(a.scale, 1, "--scale", "one number S, level-0 pixels per output pixel")[0]
+        if a.center is None:
+            with open(a.src, "rb") as f:                                   # the heads only: no model, no GPU
+                ix = codec.stream_index(f)
+            center = [ix["H"] / 2, ix["W"] / 2]
+        else:
+            center = floats(a.center, 2, "--center", "two numbers Y,X")
+        try:
+            matrix = codec.rotation_affine(center[0], center[1], a.rotate, scale, size[0], size[1])
+        except ValueError as e:
+            ap.error(str(e))
+    try:
+        codec.affine_q16(matrix)
+    except ValueError as e:
+        ap.error(str(e))
+    if not (1 <= size[0] <= 1 << 20 and 1 <= size[1] <= 1 << 20):
+        ap.error(f"--size {a.size}: a warped view has 1 .. 2^20 pixels a side")
+    return matrix
+
+
+def render_main(a, ap, region, size, level_given, matrix=None):
     """The render mode: every argument error before the model is loaded."""
     from dsic_amd import codec
 
@@ -195,6 +267,8 @@ def render_main(a, ap, region, size, level_given):
         ap.error(f"{a.dst}: a .ppm or .pgm holds no alpha channel; write .npy or .png")
     with open(a.src, "rb") as f:                                           # the heads only: no model, no GPU
         ix = codec.stream_index(f, level=a.level if level_given and size is None else 0)
+        if matrix is not None and level_given:
+            codec.stream_index(f, level=a.level)                           # a level the stream does not hold
     C = ix["C"]
     if bands is None:
         bands = (0, 1, 2) if C >= 3 else (0,)
@@ -216,6 +290,16 @@ def render_main(a, ap, region, size, level_given):
         if stretch is None:                                                # --percent asks for the percentiles on any stream
             wanted = a.percent is not None or reader.kind == codec.KIND_U16_HWC
             stretch = reader.stretch(percent) if wanted else [(0, 255)] * C
+        if matrix is not None:
+            img = reader.render_warped(matrix, tuple(size), level=a.level if level_given else None, bands=bands,
+                                       stretch=stretch, alpha=a.alpha, background=a.background, resampling=a.resampling,
+                                       stats=stats)
+            path = write_display(a.dst, img.cpu().numpy())
+            print(f"[dsic_image] affine view {', '.join(f'{v / 65536:g}' for v in stats['matrix_q16'])} as "
+                  f"{img.shape[0]}x{img.shape[1]} ({a.resampling}) from level {stats['level']}, bands "
+                  f"{','.join(str(b) for b in bands)}" + (" + alpha" if a.alpha else "") + ", stretch "
+                  + ", ".join(f"({lo}, {hi})" for lo, hi in stretch) + f": {len(stats['tiles'])} tile(s) -> {path}")
+            return
         img = reader.render(*region, size=None if size is None else tuple(size), level=a.level if level_given else None,
                             bands=bands, stretch=stretch, alpha=a.alpha, background=a.background,
                             resampling=a.resampling, stats=stats)
@@ -287,9 +371,10 @@ def main(argv=None):
                          "lossless")
     ap.add_argument("--out", choices=("u8", "f32", "u16"), default=None,
                     help="decoded kind (default: the encoder's input's; u16 only for a uint16 stream)")
-    ap.add_argument("--scale", default=None, metavar="LO,HI[,LO,HI...]",
+    ap.add_argument("--scale", default=None, metavar="LO,HI[,LO,HI...] | S",
                     help="compress, uint16 images: the (lo, hi) that map to 0 and 1, one pair for all bands or one per "
-                         "band (default: each band's minimum and maximum)")
+                         "band (default: each band's minimum and maximum); with --rotate: level-0 pixels per output "
+                         "pixel (default 1)")
     ap.add_argument("--region", default=None, metavar="Y0,X0,H,W", help="decompress: only this window of the image")
     ap.add_argument("--overviews", type=int, default=0, metavar="N",
                     help="compress: store N halved levels beside the image (a DSICP stream)")
@@ -306,8 +391,15 @@ def main(argv=None):
                     help="decompress: the overview level of a DSICP stream (0 = the full image); --region counts in it")
     ap.add_argument("--size", default=None, metavar="OH,OW",
                     help="decompress --region: the window, in level-0 pixels, resampled to OH x OW")
-    ap.add_argument("--resampling", choices=("average", "nearest"), default="average",
-                    help="decompress --region --size: how the window is resampled")
+    ap.add_argument("--resampling", choices=("average", "nearest", "bilinear", "cubic"), default=None,
+                    help="decompress --region --size: how the window is resampled, average (the default) or nearest; "
+                         "with --rotate or --affine: bilinear (the default), cubic or nearest")
+    ap.add_argument("--rotate", type=float, default=None, metavar="DEG",
+                    help="decompress, render: with --size, a view turned counter-clockwise by DEG degrees")
+    ap.add_argument("--center", default=None, metavar="Y,X",
+                    help="--rotate: the level-0 position under the view's centre (default: the image's centre)")
+    ap.add_argument("--affine", default=None, metavar="M00,M01,M02,M10,M11,M12",
+                    help="decompress, render: with --size, the view's 2 x 3 matrix, level-0 pixels per output pixel")
     ap.add_argument("--bands", default=None, metavar="B[,B,B]", help="render: one band (grey) or three of the stream's")
     ap.add_argument("--stretch", default=None, metavar="LO,HI[,LO,HI...]",
                     help="render: the values shown as 0 and 255, one pair for all bands or one per band of the stream")
@@ -351,10 +443,12 @@ def main(argv=None):
             size = [int(v) for v in a.size.split(",")]
         except ValueError:
             size = []
-        if (region is None and a.mode != "render") or len(size) != 2:
-            ap.error("--size OH,OW (two integers) goes with decompress --region or with render")
-    if a.scale is not None and a.mode != "compress":
-        ap.error("--scale goes with compress")
+        warped = a.rotate is not None or a.affine is not None
+        if (region is None and a.mode != "render" and not warped) or len(size) != 2:
+            ap.error("--size OH,OW (two integers) goes with decompress --region, --rotate or --affine, or with render")
+    if a.scale is not None and a.mode != "compress" and a.rotate is None:
+        ap.error("--scale goes with compress, or with --rotate")
+    matrix = warp_matrix(a, ap, region, size)
     if (a.valid is not None or a.fill is not None) and a.mode != "compress":
         ap.error("--valid and --fill go with compress")
     if a.fill is not None and a.valid is None:
@@ -365,7 +459,7 @@ def main(argv=None):
     if a.mode == "render":
         if a.out is not None:
             ap.error("--out goes with decompress")
-        return render_main(a, ap, region, size, given)
+        return render_main(a, ap, region, size, given, matrix)
     if a.bands is not None or a.stretch is not None or a.percent is not None or a.alpha or a.background:
         ap.error("--bands, --stretch, --percent, --alpha and --background go with render")
     if a.mode == "decompress" and not a.dst.endswith(".npy"):
@@ -400,6 +494,16 @@ def main(argv=None):
               + (f", nodata {h['nodata']}: {h['coded']} coded tile(s)" if "nodata" in h else "")
               + (f", fill {h['fill']}: {h['coded']} coded tile(s)" if "fill" in h else "")
               + (f", scale {h['scale']}" if "scale" in h else ""))
+    elif matrix is not None:
+        stats = {}
+        with open(a.src, "rb") as f, codec.ImageReader(model, f, batch=a.batch) as reader:
+            img = reader.read_warped(matrix, tuple(size), level=a.level if given else None, out=a.out,
+                                     resampling=a.resampling, stats=stats)
+            stats["bytes_read"] = reader.stats["bytes_read"]                  # the heads included
+        path = write_image(a.dst, img)
+        print(f"[dsic_image] affine view {', '.join(f'{v / 65536:g}' for v in stats['matrix_q16'])} as {size[0]}x{size[1]} "
+              f"({a.resampling}) from level {stats['level']}: {len(stats['tiles'])} tile(s), "
+              f"{stats['bytes_read']} of {os.path.getsize(a.src)} bytes read -> {path}")
     elif size is not None:
         stats = {}
         with open(a.src, "rb") as f, codec.ImageReader(model, f, batch=a.batch) as reader:

@@ -1,6 +1,6 @@
 """Pan and zoom: codec.ImageReader against one decompress_region call per frame, and the resampling kernel alone.
 
-    python tools/view_bench.py [--size 4096] [--tile 256] [--reps 3] [--json profiles/view_bench.json]
+    python tools/view_bench.py [--size 4096] [--tile 256] [--reps 3] [--json profiles/view_bench.json] [--only warp]
 
 The scene of image_codec_bench.py (synthetic patches side by side, uint8) is coded once with overviews=3.  A viewport
 of 768 rows x 1024 columns pans right in 32 steps of 64 pixels (33 frames).  Per frame, alternately in one process:
@@ -18,6 +18,11 @@ device events around 50 launches after 5 warm-up launches, with the bytes it mus
 dsic_window_render_u8 (three bands + alpha) on the same shapes.  The histogram behind a percentile stretch: a fresh
 reader's histogram() of the coarsest and of the full level (wall clock, the decode included), and the kernels alone on
 the full level as uint8 and as uint16, once on the scene and once on a constant image.
+warp: the 384 x 512 view of the middle frame from a reader whose cache holds its tiles, rendered axis-aligned with
+render(..., alpha=True) and with render_warped at 0 and at 30 degrees about the frame's centre, the same 2 level-0 pixels
+per output pixel, bilinear and cubic: the median wall clock of 30 calls each, the order rotating from round to round,
+and each call's kernel alone on the window it planned (device events, as above).  --only warp measures that record
+alone and puts it into the --json file beside the records already there.
 Records, not bars."""
 from __future__ import annotations
 
@@ -52,6 +57,69 @@ def _summary(per_pass):
             "frames_ms": [round(f, 3) for f in frames]}
 
 
+def _per_launch_us(launch, n=50):
+    import torch
+    for _ in range(5):
+        launch()
+    start, end = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    start.record()
+    for _ in range(n):
+        launch()
+    end.record()
+    torch.cuda.synchronize()
+    return start.elapsed_time(end) * 1e3 / n
+
+
+def _warp_record(model, stream, win, batch, rounds=30):
+    """The `warp` record: see the module's docstring."""
+    import torch
+    from dsic_amd import codec, lib
+    from dsic_amd.ops import _p, _stream
+    L = lib.load()
+    cy, cx, scale = win[0] + win[2] / 2, win[1] + win[3] / 2, win[2] / SIZE[0]
+    views = {f"render_warped {deg} deg {res}": (codec.rotation_affine(cy, cx, deg, scale, *SIZE), res)
+             for deg in (0, 30) for res in ("bilinear", "cubic")}
+    rec = {"view_size": list(SIZE), "level0_pixels_per_output_pixel": scale, "centre": [cy, cx], "rounds": rounds}
+    bands, lohi = (ctypes.c_int * 3)(0, 1, 2), codec._lohi([(0, 255)] * 3)
+    rgba = torch.empty(SIZE + (4,), dtype=torch.uint8, device="cuda")
+    with codec.ImageReader(model, stream, batch=batch) as r:
+        calls = {"render axis-aligned average": lambda: r.render(*win, size=SIZE, alpha=True)}
+        for name, (matrix, res) in views.items():
+            calls[name] = lambda matrix=matrix, res=res: r.render_warped(matrix, SIZE, alpha=True, resampling=res)
+        for fn in calls.values():                                          # untimed: the tiles into the cache, every shape
+            fn(), fn()
+        torch.cuda.synchronize()
+        times, names = {name: [] for name in calls}, list(calls)
+        for k in range(rounds):
+            for name in names[k % len(names):] + names[:k % len(names)]:
+                times[name].append(_frame_ms(calls[name]))
+        H, W = r.levels[0]
+        for name in names:
+            st = {}
+            if name in views:
+                r.render_warped(views[name][0], SIZE, alpha=True, resampling=views[name][1], stats=st)
+            else:
+                r.render(*win, size=SIZE, alpha=True, stats=st)
+            level, lw = st["level"], st["level_window"]
+            src = torch.randint(0, 256, (lw[2], lw[3], 3), dtype=torch.uint8, device="cuda")
+            if name in views:
+                m = (ctypes.c_int64 * 6)(*st["matrix_q16"])
+                mode = {"bilinear": 0, "cubic": 2}[views[name][1]]
+
+                def launch():
+                    lib.check(L.dsic_window_warp_render_u8(_p(src), None, lw[2], lw[3], lw[0], lw[1], 3, level,
+                                                           *r.levels[level], H, W, m, bands, 3, lohi, _p(rgba), *SIZE, mode,
+                                                           -1, 1, 0, _stream()), "window_warp_render_u8")
+            else:
+                def launch():
+                    lib.check(L.dsic_window_render_u8(_p(src), None, lw[2], lw[3], lw[0], lw[1], 3, level, *win, bands, 3,
+                                                      lohi, _p(rgba), *SIZE, 0, -1, 1, 0, _stream()), "window_render_u8")
+            rec[name] = {"call_median_ms": round(statistics.median(times[name]), 4),
+                         "call_max_ms": round(max(times[name]), 4), "level": level, "level_window": list(lw),
+                         "kernel_us_per_launch": round(_per_launch_us(launch), 2)}
+    return rec
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--size", type=int, default=4096)
@@ -59,6 +127,8 @@ def main():
     ap.add_argument("--batch", type=int, default=64)
     ap.add_argument("--reps", type=int, default=3)
     ap.add_argument("--json", default=os.path.join(ROOT, "profiles", "view_bench.json"))
+    ap.add_argument("--only", choices=("warp",), default=None,
+                    help="measure this record alone and put it into the --json file beside the others")
     a = ap.parse_args()
 
     import numpy as np
@@ -83,6 +153,14 @@ def main():
     frames = [(y0, x_first + STEP * k, VIEW_H, VIEW_W) for k in range(STEPS + 1)]
     assert frames[-1][1] + VIEW_W <= a.size and y0 + VIEW_H <= a.size
     level = codec.view_level(4, VIEW_H, VIEW_W, *SIZE)
+    if a.only == "warp":
+        with open(a.json) as f:
+            res = json.load(f)
+        res["warp"] = _warp_record(model, stream, frames[STEPS // 2], a.batch)
+        print(json.dumps(res["warp"]))
+        with open(a.json, "w") as f:
+            json.dump(res, f, indent=1)
+        return
 
     def one_pass(timed):
         rows = {"reader": [], "region": [], "reader_view": [], "region_level": [], "render_view": [],
@@ -134,16 +212,7 @@ def main():
     # the kernels alone
     L = lib.load()
 
-    def per_launch_us(launch, n=50):
-        for _ in range(5):
-            launch()
-        start, end = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        start.record()
-        for _ in range(n):
-            launch()
-        end.record()
-        torch.cuda.synchronize()
-        return start.elapsed_time(end) * 1e3 / n
+    per_launch_us = _per_launch_us
 
     kernel, render = [], []
     for name, (sh, sw, shift, region, size) in {
@@ -191,6 +260,7 @@ def main():
                 lib.check(fn(_p(dev), None, a.size, a.size, 3, -1, _p(counts), _stream()), "band_histogram_" + kind)
             hist[f"kernel_{kind}_{name}_us"] = round(per_launch_us(launch_hist, n=10), 1)
     res["histogram"] = hist
+    res["warp"] = _warp_record(model, stream, frames[STEPS // 2], a.batch)
     print(json.dumps(res))
     with open(a.json, "w") as f:
         json.dump(res, f, indent=1)
