@@ -9,9 +9,17 @@
  *
  * Conventions
  *   - every pointer is a DEVICE pointer unless the name ends in _host;
- *   - `stream` is a hipStream_t passed as void* (NULL = default stream);
+ *   - `stream` is a hipStream_t passed as void* (NULL = default stream).  All
+ *     device work of a call, every launch of a call that makes several, is
+ *     enqueued on `stream`, in order: it starts after what the caller enqueued
+ *     there before the call and is complete before what the caller enqueues
+ *     there after it.  The call returns without waiting for the device, so a
+ *     result is read behind `stream` like any other work on it;
  *   - the library allocates nothing and keeps no state; callers own all
- *     buffers including workspaces;
+ *     buffers including workspaces.  Calls on different streams whose
+ *     buffers (workspaces and the Winograd ticket included) are disjoint do
+ *     not affect each other, at whatever time they run;
+ *     (tests/test_gpu_stream_order.py holds every export to these three)
  *   - activations are NHWC float32 with a channel count that is a multiple
  *     of 8; image tensors at the boundary are NCHW float32 like the
  *     reference's (eval_selfcontained.py:58-59);
