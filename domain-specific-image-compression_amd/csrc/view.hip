@@ -22,6 +22,9 @@
 // A wave covers 64 consecutive pixels of an output row, so its loads walk the source rows in step and its stores are
 // one run of 64 C elements; each source pixel is needed by at most two output rows and two output columns when the
 // level fits the scale (codec.view_level), which the caches absorb.
+//
+// Here: the geometry (View, view_check), the samplers and the kernels.  In render.h, shared with warp.hip: Render and
+// stretch_byte, the display check (display_options, display_of) and the small host checks.
 #include <limits.h>
 
 #include "common.h"
@@ -265,72 +268,43 @@ static View view_of(int sh, int sw, int sy0, int sx0, int shift, int y0, int x0,
   return v;
 }
 
-static dim3 view_grid(int64_t nblocks) { return dim3((unsigned)(nblocks > (1 << 20) ? (1 << 20) : nblocks)); }
-
-template <typename T>
-static int resample_int(const char* what, const T* src, const View& v, int C, int cmin, T* dst, int mode, int nodata,
-                        void* stream) {
+// V: with a validity window; value is then the fill, else nodata (-1 for none)
+template <typename T, bool V>
+static int resample_int(const char* what, const T* src, const uint8_t* sval, const View& v, int C, int cmin, T* dst,
+                        uint8_t* oval, int mode, int value, void* stream) {
   int bx;
   int64_t nblocks;
   const int status = view_check(what, src, dst, v, C, cmin, 4, (int)sizeof(T), (int)sizeof(T), C, mode, &bx, &nblocks);
   if (status != DSIC_OK) return status;
-  DSIC_REQUIRE(nodata >= -1 && nodata <= (int)(T)~(T)0, "%s: nodata=%d (-1 for none, or a pixel value)", what, nodata);
-  hipLaunchKernelGGL((resample_int_kernel<T, false>), view_grid(nblocks), dim3(VIEW_BX, VIEW_BY), 0, (hipStream_t)stream,
-                     src, dst, v, C, mode, nodata, bx, nblocks, (const uint8_t*)nullptr, (uint8_t*)nullptr);
-  return check_launch(what);
-}
-
-template <typename T>
-static int resample_valid(const char* what, const T* src, const uint8_t* sval, const View& v, int C, int cmin, T* dst,
-                          uint8_t* oval, int mode, int fill, void* stream) {
-  int bx;
-  int64_t nblocks;
-  const int status = view_check(what, src, dst, v, C, cmin, 4, (int)sizeof(T), (int)sizeof(T), C, mode, &bx, &nblocks);
-  if (status != DSIC_OK) return status;
-  DSIC_REQUIRE(sval, "%s: null pointer", what);
-  DSIC_REQUIRE(fill >= 0 && fill <= (int)(T)~(T)0, "%s: fill=%d must be a pixel value", what, fill);
-  const int64_t sb = (int64_t)sizeof(T) * C * v.sh * v.sw, db = (int64_t)sizeof(T) * C * v.oh * v.ow;
-  const int64_t svb = (int64_t)v.sh * v.sw, ovb = (int64_t)v.oh * v.ow;
-  DSIC_REQUIRE(buffers_apart(sval, svb, dst, db) &&
-                   (!oval || (buffers_apart(oval, ovb, src, sb) && buffers_apart(oval, ovb, sval, svb) &&
-                              buffers_apart(oval, ovb, dst, db))),
-               "%s: src and dst overlap", what);
-  hipLaunchKernelGGL((resample_int_kernel<T, true>), view_grid(nblocks), dim3(VIEW_BX, VIEW_BY), 0, (hipStream_t)stream,
-                     src, dst, v, C, mode, fill, bx, nblocks, sval, oval);
+  if (!V) DSIC_REQUIRE(pixel_value<T>(value, -1), "%s: nodata=%d (-1 for none, or a pixel value)", what, value);
+  if (V) DSIC_REQUIRE(sval, "%s: null pointer", what);
+  if (V) DSIC_REQUIRE(pixel_value<T>(value, 0), "%s: fill=%d must be a pixel value", what, value);
+  const int64_t spix = (int64_t)v.sh * v.sw, opix = (int64_t)v.oh * v.ow, px = (int64_t)sizeof(T) * C;
+  DSIC_REQUIRE(windows_apart(src, px * spix, sval, spix, dst, px * opix, oval, opix), "%s: src and dst overlap", what);
+  hipLaunchKernelGGL((resample_int_kernel<T, V>), launch_grid(nblocks), dim3(VIEW_BX, VIEW_BY), 0, (hipStream_t)stream, src,
+                     dst, v, C, mode, value, bx, nblocks, sval, oval);
   return check_launch(what);
 }
 
 template <typename T>
 static int render(const char* what, const T* src, const uint8_t* sval, const View& v, int C, const int* bands, int nb,
                   const uint32_t* lohi, uint8_t* dst, int mode, int nodata, int alpha, int background, void* stream) {
-  DSIC_REQUIRE(nb == 1 || nb == 3, "%s: nb=%d output bands (1 or 3)", what, nb);
-  DSIC_REQUIRE(alpha == 0 || alpha == 1, "%s: alpha=%d (0 or 1)", what, alpha);
-  DSIC_REQUIRE(background >= 0 && background <= 255, "%s: background=%d must be in 0..255", what, background);
   int bx;
   int64_t nblocks;
+  Render r;
   const int n = nb + alpha;
-  const int status = view_check(what, src, dst, v, C, 1, 4, (int)sizeof(T), 1, n, mode, &bx, &nblocks);
+  int status = display_options(what, nb, alpha, background);
+  if (status == DSIC_OK) status = view_check(what, src, dst, v, C, 1, 4, (int)sizeof(T), 1, n, mode, &bx, &nblocks);
+  if (status == DSIC_OK) status = display_of<T>(what, C, bands, nb, lohi, nodata, alpha, background, &r);
   if (status != DSIC_OK) return status;
-  DSIC_REQUIRE(bands && lohi, "%s: null pointer", what);
-  const int top = (int)(T)~(T)0;
-  DSIC_REQUIRE(nodata >= -1 && nodata <= top, "%s: nodata=%d (-1 for none, or a pixel value)", what, nodata);
-  for (int c = 0; c < C; ++c)
-    DSIC_REQUIRE(lohi[2 * c] <= lohi[2 * c + 1] && lohi[2 * c + 1] <= (uint32_t)top,
-                 "%s: stretch pair (%u, %u) of band %d must have 0 <= lo <= hi <= %d", what, lohi[2 * c], lohi[2 * c + 1], c,
-                 top);
-  Render r = {nb, alpha, background, 0, {0, 0, 0}, {0, 0, 0}, {0, 0, 0}};
-  for (int b = 0; b < nb; ++b) {
-    DSIC_REQUIRE(bands[b] >= 0 && bands[b] < C, "%s: band %d is outside 0..%d", what, bands[b], C - 1);
-    r.band[b] = bands[b], r.lo[b] = lohi[2 * bands[b]], r.hi[b] = lohi[2 * bands[b] + 1];
-    r.need |= 1 << bands[b];
-  }
+  const int64_t spix = (int64_t)v.sh * v.sw, opix = (int64_t)v.oh * v.ow;
+  DSIC_REQUIRE(windows_apart(src, (int64_t)sizeof(T) * C * spix, sval, spix, dst, n * opix, nullptr, 0),
+               "%s: src and dst overlap", what);
   if (sval)
-    DSIC_REQUIRE(buffers_apart(sval, (int64_t)v.sh * v.sw, dst, (int64_t)n * v.oh * v.ow), "%s: src and dst overlap", what);
-  if (sval)
-    hipLaunchKernelGGL((render_kernel<T, true>), view_grid(nblocks), dim3(VIEW_BX, VIEW_BY), 0, (hipStream_t)stream, src,
+    hipLaunchKernelGGL((render_kernel<T, true>), launch_grid(nblocks), dim3(VIEW_BX, VIEW_BY), 0, (hipStream_t)stream, src,
                        sval, dst, v, C, mode, 0, r, bx, nblocks);
   else
-    hipLaunchKernelGGL((render_kernel<T, false>), view_grid(nblocks), dim3(VIEW_BX, VIEW_BY), 0, (hipStream_t)stream, src,
+    hipLaunchKernelGGL((render_kernel<T, false>), launch_grid(nblocks), dim3(VIEW_BX, VIEW_BY), 0, (hipStream_t)stream, src,
                        sval, dst, v, C, mode, nodata, r, bx, nblocks);
   return check_launch(what);
 }
@@ -343,14 +317,15 @@ extern "C" int dsic_window_resample_u8(const uint8_t* src_hwc, int sh, int sw, i
                                        int x0, int h, int w, uint8_t* dst_hwc, int oh, int ow, int mode, int nodata,
                                        void* stream) {
   const View v = view_of(sh, sw, sy0, sx0, shift, y0, x0, h, w, oh, ow);
-  return resample_int<uint8_t>("window_resample_u8", src_hwc, v, C, 3, dst_hwc, mode, nodata, stream);
+  return resample_int<uint8_t, false>("window_resample_u8", src_hwc, nullptr, v, C, 3, dst_hwc, nullptr, mode, nodata, stream);
 }
 
 extern "C" int dsic_window_resample_u16(const uint16_t* src_hwc, int sh, int sw, int sy0, int sx0, int C, int shift,
                                         int y0, int x0, int h, int w, uint16_t* dst_hwc, int oh, int ow, int mode,
                                         int nodata, void* stream) {
   const View v = view_of(sh, sw, sy0, sx0, shift, y0, x0, h, w, oh, ow);
-  return resample_int<uint16_t>("window_resample_u16", src_hwc, v, C, 1, dst_hwc, mode, nodata, stream);
+  return resample_int<uint16_t, false>("window_resample_u16", src_hwc, nullptr, v, C, 1, dst_hwc, nullptr, mode, nodata,
+                                       stream);
 }
 
 extern "C" int dsic_window_resample_f32(const float* src_chw, int sh, int sw, int sy0, int sx0, int C, int shift, int y0,
@@ -361,7 +336,7 @@ extern "C" int dsic_window_resample_f32(const float* src_chw, int sh, int sw, in
   int64_t nblocks;
   const int status = view_check("window_resample_f32", src_chw, dst_chw, v, C, 1, 8, 4, 4, C, mode, &bx, &nblocks);
   if (status != DSIC_OK) return status;
-  hipLaunchKernelGGL(resample_f32_kernel, view_grid(nblocks), dim3(VIEW_BX, VIEW_BY), 0, (hipStream_t)stream, src_chw,
+  hipLaunchKernelGGL(resample_f32_kernel, launch_grid(nblocks), dim3(VIEW_BX, VIEW_BY), 0, (hipStream_t)stream, src_chw,
                      dst_chw, v, C, mode, nodata, has_nodata, bx, nblocks);
   return check_launch("window_resample_f32");
 }
@@ -370,16 +345,16 @@ extern "C" int dsic_window_resample_valid_u8(const uint8_t* src_hwc, const uint8
                                              int sx0, int C, int shift, int y0, int x0, int h, int w, uint8_t* dst_hwc,
                                              uint8_t* dst_valid, int oh, int ow, int mode, int fill, void* stream) {
   const View v = view_of(sh, sw, sy0, sx0, shift, y0, x0, h, w, oh, ow);
-  return resample_valid<uint8_t>("window_resample_valid_u8", src_hwc, src_valid, v, C, 3, dst_hwc, dst_valid, mode, fill,
-                                 stream);
+  return resample_int<uint8_t, true>("window_resample_valid_u8", src_hwc, src_valid, v, C, 3, dst_hwc, dst_valid, mode,
+                                     fill, stream);
 }
 
 extern "C" int dsic_window_resample_valid_u16(const uint16_t* src_hwc, const uint8_t* src_valid, int sh, int sw, int sy0,
                                               int sx0, int C, int shift, int y0, int x0, int h, int w, uint16_t* dst_hwc,
                                               uint8_t* dst_valid, int oh, int ow, int mode, int fill, void* stream) {
   const View v = view_of(sh, sw, sy0, sx0, shift, y0, x0, h, w, oh, ow);
-  return resample_valid<uint16_t>("window_resample_valid_u16", src_hwc, src_valid, v, C, 1, dst_hwc, dst_valid, mode, fill,
-                                  stream);
+  return resample_int<uint16_t, true>("window_resample_valid_u16", src_hwc, src_valid, v, C, 1, dst_hwc, dst_valid, mode,
+                                      fill, stream);
 }
 
 extern "C" int dsic_window_render_u8(const uint8_t* src_hwc, const uint8_t* src_valid, int sh, int sw, int sy0, int sx0,

@@ -20,6 +20,9 @@
 // taps lie in a box of about 12 x 12 level pixels, a dozen cache lines, where 64 pixels of one output row walk up to 45
 // source rows at 45 degrees, one line each (DESIGN.md section 3 has the count).  A lane row of the patch stores 8 C
 // contiguous elements.  Taps are also clamped to the source window, so a wrong plan cannot read outside the allocation.
+//
+// Here: the geometry (Warp, warp_check, warp_axis), the sampler and the kernels.  In render.h, shared with view.hip:
+// Render and stretch_byte, the display check (display_options, display_of) and the small host checks.
 #include <limits.h>
 
 #include "common.h"
@@ -263,11 +266,8 @@ static int warp_check(const char* what, const void* src, const uint8_t* sval, co
                  what, (long long)ya, (long long)yb, (long long)xa, (long long)xb, g.shift, g.sh, g.sw, g.sy0, g.sx0);
   DSIC_REQUIRE(((uintptr_t)src & (uintptr_t)(elem - 1)) == 0 && ((uintptr_t)dst & (uintptr_t)(delem - 1)) == 0,
                "%s: src must be %d-byte aligned and dst %d-byte aligned", what, elem, delem);
-  const int64_t sb = (int64_t)elem * C * g.sh * g.sw, db = (int64_t)delem * dch * g.oh * g.ow;
-  const int64_t svb = (int64_t)g.sh * g.sw, ovb = (int64_t)g.oh * g.ow;
-  DSIC_REQUIRE(buffers_apart(src, sb, dst, db) && (!sval || buffers_apart(sval, svb, dst, db)) &&
-                   (!oval || (buffers_apart(oval, ovb, src, sb) && buffers_apart(oval, ovb, dst, db) &&
-                              (!sval || buffers_apart(oval, ovb, sval, svb)))),
+  const int64_t spix = (int64_t)g.sh * g.sw, opix = (int64_t)g.oh * g.ow;
+  DSIC_REQUIRE(windows_apart(src, elem * C * spix, sval, spix, dst, delem * dch * opix, oval, opix),
                "%s: src and dst overlap", what);
   *bx = (g.ow + WARP_TILE - 1) / WARP_TILE;
   *nblocks = (int64_t)*bx * ((g.oh + WARP_TILE - 1) / WARP_TILE);
@@ -281,8 +281,6 @@ static Warp warp_of(int sh, int sw, int sy0, int sx0, int shift, int LH, int LW,
   return g;
 }
 
-static dim3 warp_grid(int64_t nblocks) { return dim3((unsigned)(nblocks > (1 << 20) ? (1 << 20) : nblocks)); }
-
 template <typename T>
 static int warp(const char* what, const T* src, const uint8_t* sval, const Warp& g, int H, int W, const int64_t* m, int C,
                 int cmin, T* dst, uint8_t* oval, int mode, int nodata, int fill, void* stream) {
@@ -291,14 +289,13 @@ static int warp(const char* what, const T* src, const uint8_t* sval, const Warp&
   const int status = warp_check(what, src, sval, dst, oval, g, H, W, m, C, cmin, (int)sizeof(T), (int)sizeof(T), C, mode,
                                 &bx, &nblocks);
   if (status != DSIC_OK) return status;
-  const int top = (int)(T)~(T)0;
-  DSIC_REQUIRE(nodata >= -1 && nodata <= top, "%s: nodata=%d (-1 for none, or a pixel value)", what, nodata);
-  DSIC_REQUIRE(fill >= 0 && fill <= top, "%s: fill=%d must be a pixel value", what, fill);
+  DSIC_REQUIRE(pixel_value<T>(nodata, -1), "%s: nodata=%d (-1 for none, or a pixel value)", what, nodata);
+  DSIC_REQUIRE(pixel_value<T>(fill, 0), "%s: fill=%d must be a pixel value", what, fill);
   if (sval)
-    hipLaunchKernelGGL((warp_kernel<T, true>), warp_grid(nblocks), dim3(WARP_TILE * WARP_TILE), 0, (hipStream_t)stream, src,
+    hipLaunchKernelGGL((warp_kernel<T, true>), launch_grid(nblocks), dim3(WARP_TILE * WARP_TILE), 0, (hipStream_t)stream, src,
                        sval, dst, oval, g, C, mode, -1, fill, bx, nblocks);
   else
-    hipLaunchKernelGGL((warp_kernel<T, false>), warp_grid(nblocks), dim3(WARP_TILE * WARP_TILE), 0, (hipStream_t)stream, src,
+    hipLaunchKernelGGL((warp_kernel<T, false>), launch_grid(nblocks), dim3(WARP_TILE * WARP_TILE), 0, (hipStream_t)stream, src,
                        sval, dst, oval, g, C, mode, nodata, fill, bx, nblocks);
   return check_launch(what);
 }
@@ -307,32 +304,19 @@ template <typename T>
 static int warp_render(const char* what, const T* src, const uint8_t* sval, const Warp& g, int H, int W, const int64_t* m,
                        int C, const int* bands, int nb, const uint32_t* lohi, uint8_t* dst, int mode, int nodata, int alpha,
                        int background, void* stream) {
-  DSIC_REQUIRE(nb == 1 || nb == 3, "%s: nb=%d output bands (1 or 3)", what, nb);
-  DSIC_REQUIRE(alpha == 0 || alpha == 1, "%s: alpha=%d (0 or 1)", what, alpha);
-  DSIC_REQUIRE(background >= 0 && background <= 255, "%s: background=%d must be in 0..255", what, background);
   int bx;
   int64_t nblocks;
-  const int n = nb + alpha;
-  const int status = warp_check(what, src, sval, dst, nullptr, g, H, W, m, C, 1, (int)sizeof(T), 1, n, mode, &bx, &nblocks);
+  Render r;
+  int status = display_options(what, nb, alpha, background);
+  if (status == DSIC_OK)
+    status = warp_check(what, src, sval, dst, nullptr, g, H, W, m, C, 1, (int)sizeof(T), 1, nb + alpha, mode, &bx, &nblocks);
+  if (status == DSIC_OK) status = display_of<T>(what, C, bands, nb, lohi, nodata, alpha, background, &r);
   if (status != DSIC_OK) return status;
-  DSIC_REQUIRE(bands && lohi, "%s: null pointer", what);
-  const int top = (int)(T)~(T)0;
-  DSIC_REQUIRE(nodata >= -1 && nodata <= top, "%s: nodata=%d (-1 for none, or a pixel value)", what, nodata);
-  for (int c = 0; c < C; ++c)
-    DSIC_REQUIRE(lohi[2 * c] <= lohi[2 * c + 1] && lohi[2 * c + 1] <= (uint32_t)top,
-                 "%s: stretch pair (%u, %u) of band %d must have 0 <= lo <= hi <= %d", what, lohi[2 * c], lohi[2 * c + 1], c,
-                 top);
-  Render r = {nb, alpha, background, 0, {0, 0, 0}, {0, 0, 0}, {0, 0, 0}};
-  for (int b = 0; b < nb; ++b) {
-    DSIC_REQUIRE(bands[b] >= 0 && bands[b] < C, "%s: band %d is outside 0..%d", what, bands[b], C - 1);
-    r.band[b] = bands[b], r.lo[b] = lohi[2 * bands[b]], r.hi[b] = lohi[2 * bands[b] + 1];
-    r.need |= 1 << bands[b];
-  }
   if (sval)
-    hipLaunchKernelGGL((warp_render_kernel<T, true>), warp_grid(nblocks), dim3(WARP_TILE * WARP_TILE), 0,
+    hipLaunchKernelGGL((warp_render_kernel<T, true>), launch_grid(nblocks), dim3(WARP_TILE * WARP_TILE), 0,
                        (hipStream_t)stream, src, sval, dst, g, C, mode, -1, r, bx, nblocks);
   else
-    hipLaunchKernelGGL((warp_render_kernel<T, false>), warp_grid(nblocks), dim3(WARP_TILE * WARP_TILE), 0,
+    hipLaunchKernelGGL((warp_render_kernel<T, false>), launch_grid(nblocks), dim3(WARP_TILE * WARP_TILE), 0,
                        (hipStream_t)stream, src, sval, dst, g, C, mode, nodata, r, bx, nblocks);
   return check_launch(what);
 }

@@ -205,6 +205,28 @@ def _new_stats():
     return {"tiles": [], "hits": 0, "decoded": 0, "decode_batches": 0, "bytes_read": 0, "bytes_uploaded": 0}
 
 
+def _check_size(size, what, top=None, bound="at least (1, 1)"):
+    """size = (oh, ow) as the sized and warped reads take it -> two integers >= 1, and <= top if given; bound says so"""
+    try:
+        oh, ow = (operator.index(v) for v in size)
+    except (TypeError, ValueError):
+        raise ValueError(f"{what}: size={size!r} is not a pair of integers (oh, ow)") from None
+    if min(oh, ow) < 1 or (top is not None and max(oh, ow) > top):
+        raise ValueError(f"{what}: size={size!r} must be {bound}")
+    return oh, ow
+
+
+def _opt(t):
+    """The device pointer of an optional tensor."""
+    return None if t is None else _p(t)
+
+
+def _call_by_width(stem, img, *args):
+    """dsic_<stem>_u8 or dsic_<stem>_u16, as the image's dtype says, on the image and args; an error names the export."""
+    what = stem + ("_u16" if img.dtype == torch.uint16 else "_u8")
+    _lib.check(getattr(_lib.load(), "dsic_" + what)(_p(img), *args), what)
+
+
 class _Slab:
     """The cached tiles of one level: row `slot` of x (and of q, for a near-lossless level) is a decoded tile, ids
     its tile number on the device, as the stitch calls take it."""
@@ -433,12 +455,7 @@ class ImageReader:
         y0, x0, h, w = window
         if size is None:
             return self._level(level)[0], (y0, x0, h, w), None
-        try:
-            oh, ow = (operator.index(v) for v in size)
-        except (TypeError, ValueError):
-            raise ValueError(f"ImageReader: size={size!r} is not a pair of integers (oh, ow)") from None
-        if oh < 1 or ow < 1:
-            raise ValueError(f"ImageReader: size={size!r} must be at least (1, 1)")
+        oh, ow = _check_size(size, "ImageReader")
         y0, x0, h, w = (int(v) for v in window)
         H, W = self.levels[0]
         if y0 < 0 or x0 < 0 or h < 1 or w < 1 or y0 + h > H or x0 + w > W:
@@ -454,36 +471,48 @@ class ImageReader:
         """Whether a level carries a validity mask (stream version 8): its sized reads resample with the mask."""
         return "fill" in self._open[level][1]
 
+    def _source_window(self, level, window, out, st, ensured=False, want_valid=None):
+        """(image, validity or None) of a level's window, as _window brings it in.  The validity, uint8, comes with a
+        level that has a validity mask; want_valid = True or False asks for it, or declines it, whatever the level."""
+        want = self._masked(level) if want_valid is None else want_valid
+        valid = torch.ones((int(window[2]), int(window[3])), dtype=torch.uint8, device=self._dev) if want else None
+        return self._window(level, window, out, st, ensured, valid), valid
+
     def _resample(self, img, level, lw, view, valid=None, want_valid=False):
-        """A level's window `lw`, as _window returns it, resampled to the view (csrc/view.hip).  valid: the window's
-        validity, uint8, for a level with a validity mask; then the result is (image, its validity or None)."""
+        """A level's window `lw`, as _window returns it, resampled to the view (csrc/view.hip) -> (image, its validity if
+        wanted, else None).  valid: the window's validity, uint8, of a masked level; without it every pixel is valid."""
         (y0, x0, h, w), (oh, ow), mode = view
         ix = self._open[level][1]
-        v = ix.get("nodata") if mode == 0 else None
-        L = _lib.load()
-        geo = (lw[2], lw[3], lw[0], lw[1], ix["C"], level, y0, x0, h, w)
-        if valid is not None:
-            what = "window_resample_valid_u8" if img.dtype == torch.uint8 else "window_resample_valid_u16"
-            dst = torch.empty((oh, ow, ix["C"]), dtype=img.dtype, device=img.device)
-            oval = torch.empty((oh, ow), dtype=torch.uint8, device=img.device) if want_valid else None
-            _lib.check(getattr(L, "dsic_" + what)(_p(img), _p(valid), *geo, _p(dst), None if oval is None else _p(oval),
-                                                  oh, ow, mode, ix["fill"], _stream()), what)
-            return dst, oval
+        C, nodata = ix["C"], ix.get("nodata", -1) if mode == 0 else -1
+        geo = (lw[2], lw[3], lw[0], lw[1], C, level, y0, x0, h, w)
+        make = torch.ones if valid is None else torch.empty
+        oval = make((oh, ow), dtype=torch.uint8, device=img.device) if want_valid else None
         if img.dtype == torch.float32:
-            dst = torch.empty((ix["C"], oh, ow), dtype=torch.float32, device=img.device)
-            value = 0.0 if v is None else float(np.float32(v) / np.float32(255.0))     # what _apply_mask wrote
-            status = L.dsic_window_resample_f32(_p(img), *geo, _p(dst), oh, ow, mode, ctypes.c_float(value),
-                                                int(v is not None), _stream())
-            what = "window_resample_f32"
+            dst = torch.empty((C, oh, ow), dtype=torch.float32, device=img.device)
+            value = float(np.float32(nodata) / np.float32(255.0)) if nodata >= 0 else 0.0      # what _apply_mask wrote
+            _lib.check(_lib.load().dsic_window_resample_f32(_p(img), *geo, _p(dst), oh, ow, mode, ctypes.c_float(value),
+                                                            int(nodata >= 0), _stream()), "window_resample_f32")
+            return dst, oval
+        dst = torch.empty((oh, ow, C), dtype=img.dtype, device=img.device)
+        if valid is not None:
+            _call_by_width("window_resample_valid", img, _p(valid), *geo, _p(dst), _opt(oval), oh, ow, mode, ix["fill"],
+                           _stream())
         else:
-            what = "window_resample_u8" if img.dtype == torch.uint8 else "window_resample_u16"
-            dst = torch.empty((oh, ow, ix["C"]), dtype=img.dtype, device=img.device)
-            status = getattr(L, "dsic_" + what)(_p(img), *geo, _p(dst), oh, ow, mode, -1 if v is None else v, _stream())
-        _lib.check(status, what)
-        return dst
+            _call_by_width("window_resample", img, *geo, _p(dst), oh, ow, mode, nodata, _stream())
+        return dst, oval
 
-    def _finish(self, st, before, stats):
-        st["bytes_read"] = self._source.bytes_read - before
+    def _read_planned(self, level, lw, view, out, st, ensured, with_valid):
+        """One planned request, as read answers it -> (image, its uint8 validity if wanted, else None)."""
+        self._check_view(level, view, out, with_valid)
+        masked = view is not None and self._masked(level)
+        img, valid = self._source_window(level, lw, out, st, ensured, with_valid or masked)
+        if view is not None:
+            mask = valid if masked and img.dtype != torch.float32 else None
+            img, valid = self._resample(img, level, lw, view, mask, with_valid)
+        return img, valid
+
+    def _finish(self, st, before, stats, **more):
+        st.update(more, bytes_read=self._source.bytes_read - before)
         for key in _COUNTERS:
             self._stats[key] += st[key]
         self._stats["tiles"] += len(st["tiles"])
@@ -517,19 +546,7 @@ class ImageReader:
         _c._check_out(out, None, "ImageReader.read")
         before, st = self._source.bytes_read, _new_stats()
         level, lw, view = self._plan((y0, x0, h, w), size, level, resampling)
-        masked = self._masked(level)
-        self._check_view(level, view, out, with_valid)
-        valid = None
-        if with_valid or (masked and view is not None):
-            valid = torch.ones((int(lw[2]), int(lw[3])), dtype=torch.uint8, device=self._dev)
-        img = self._window(level, lw, out, st, valid_out=valid)
-        if view is not None:
-            if masked and img.dtype != torch.float32:
-                img, valid = self._resample(img, level, lw, view, valid, with_valid)
-            else:
-                img = self._resample(img, level, lw, view)
-                if with_valid:                                     # no mask: every output pixel is valid
-                    valid = torch.ones(view[1], dtype=torch.uint8, device=self._dev)
+        img, valid = self._read_planned(level, lw, view, out, st, False, with_valid)
         if size is not None:
             st.update(level=level, level_window=tuple(lw))
         self._finish(st, before, stats)
@@ -561,17 +578,7 @@ class ImageReader:
         for level, _, _ in plans:
             _c._check_out(out, self._level(level)[2], "ImageReader.read_many")
         shared = self._ensure_union(plans, st)
-        imgs = []
-        for level, lw, view in plans:
-            self._check_view(level, view, out, False)
-            masked = view is not None and self._masked(level)
-            valid = torch.ones((int(lw[2]), int(lw[3])), dtype=torch.uint8, device=self._dev) if masked else None
-            img = self._window(level, lw, out, st, ensured=shared, valid_out=valid)
-            if masked and img.dtype != torch.float32:
-                img = self._resample(img, level, lw, view, valid)[0]
-            elif view is not None:
-                img = self._resample(img, level, lw, view)
-            imgs.append(img)
+        imgs = [self._read_planned(level, lw, view, out, st, shared, False)[0] for level, lw, view in plans]
         self._finish(st, before, stats)
         return imgs
 
@@ -623,18 +630,14 @@ class ImageReader:
         if level not in self._hists:
             out, top = self._display_out(ix)
             H, W, C, g = ix["H"], ix["W"], ix["C"], ix["grid"]
-            what = "band_histogram_u16" if top == 65535 else "band_histogram_u8"
-            fn = getattr(_lib.load(), "dsic_" + what)
             total = torch.zeros((C, top + 1), dtype=torch.int64, device=self._dev)
             part = torch.empty((C, top + 1), dtype=torch.int32, device=self._dev)      # the kernel's uint32 counters
             rows = g["th"] * max(1, self.batch // g["nx"])         # tile rows that fill about one decode batch
             for y in range(0, H, rows):
                 h = min(rows, H - y)
-                valid = torch.ones((h, W), dtype=torch.uint8, device=self._dev) if "fill" in ix else None
-                img = self._window(level, (y, 0, h, W), out, st, valid_out=valid)
+                img, valid = self._source_window(level, (y, 0, h, W), out, st)
                 part.zero_()
-                _lib.check(fn(_p(img), None if valid is None else _p(valid), h, W, C, ix.get("nodata", -1), _p(part),
-                              _stream()), what)
+                _call_by_width("band_histogram", img, _opt(valid), h, W, C, ix.get("nodata", -1), _p(part), _stream())
                 total += part.to(torch.int64) & 0xFFFFFFFF
             self._hists[level] = total.cpu().numpy()
         return self._hists[level].copy()
@@ -691,22 +694,15 @@ class ImageReader:
         """One planned request through the render kernel (dsic_window_render_u8 / _u16)."""
         bands, stretch, alpha, background = display
         ix = self._open[level][1]
+        shift = 0 if view is None else level
         if view is None:                                           # the window itself: every pixel under itself
             view = (tuple(int(v) for v in lw), (int(lw[2]), int(lw[3])), RESAMPLING[resampling])
-            shift = 0
-        else:
-            shift = level
         (y0, x0, h, w), (oh, ow), mode = view
-        valid = torch.ones((int(lw[2]), int(lw[3])), dtype=torch.uint8, device=self._dev) if self._masked(level) else None
-        img = self._window(level, lw, self._display_out(ix)[0], st, ensured=ensured, valid_out=valid)
-        nodata = ix.get("nodata") if mode == 0 else None
+        img, valid = self._source_window(level, lw, self._display_out(ix)[0], st, ensured)
         dst = torch.empty((oh, ow, len(bands) + alpha), dtype=torch.uint8, device=self._dev)
-        what = "window_render_u8" if img.dtype == torch.uint8 else "window_render_u16"
-        status = getattr(_lib.load(), "dsic_" + what)(
-            _p(img), None if valid is None else _p(valid), lw[2], lw[3], lw[0], lw[1], ix["C"], shift, y0, x0, h, w,
-            (ctypes.c_int * len(bands))(*bands), len(bands), _c._lohi(stretch), _p(dst), oh, ow, mode,
-            -1 if nodata is None else nodata, alpha, background, _stream())
-        _lib.check(status, what)
+        _call_by_width("window_render", img, _opt(valid), lw[2], lw[3], lw[0], lw[1], ix["C"], shift, y0, x0, h, w,
+                       (ctypes.c_int * len(bands))(*bands), len(bands), _c._lohi(stretch), _p(dst), oh, ow, mode,
+                       ix.get("nodata", -1) if mode == 0 else -1, alpha, background, _stream())
         return dst
 
     @torch.no_grad()
@@ -757,22 +753,12 @@ class ImageReader:
         if resampling not in WARP_RESAMPLING:
             raise ValueError(f"{what}: resampling={resampling!r} ({', '.join(WARP_RESAMPLING)})")
         m = affine_q16(matrix)
-        try:
-            oh, ow = (operator.index(v) for v in size)
-        except (TypeError, ValueError):
-            raise ValueError(f"{what}: size={size!r} is not a pair of integers (oh, ow)") from None
-        if not (1 <= oh <= WARP_SIDE and 1 <= ow <= WARP_SIDE):
-            raise ValueError(f"{what}: size={size!r} must be (1, 1) .. (2^20, 2^20)")
+        oh, ow = _check_size(size, what, WARP_SIDE, "(1, 1) .. (2^20, 2^20)")
         if level is None:
             level = warp_level(len(self.levels), m)
         level = self._level(level)[0]
         mode = WARP_RESAMPLING[resampling]
         return level, m, (oh, ow), mode, warp_window(level, *self.levels[level], *self.levels[0], m, oh, ow, mode)
-
-    def _warp_source(self, level, lw, out, st):
-        """The planned window and, for a level with a validity mask, its validity: (image, validity or None)."""
-        valid = torch.ones((lw[2], lw[3]), dtype=torch.uint8, device=self._dev) if self._masked(level) else None
-        return self._window(level, lw, out, st, valid_out=valid), valid
 
     @torch.no_grad()
     def read_warped(self, matrix, size, level=None, resampling="bilinear", out=None, stats=None, with_valid=False):
@@ -809,18 +795,13 @@ class ImageReader:
             img = torch.from_numpy(host).to(self._dev)
             oval = torch.zeros((oh, ow), dtype=torch.uint8, device=self._dev)
         else:
-            src, valid = self._warp_source(level, lw, out, st)
+            src, valid = self._source_window(level, lw, out, st)
             img = torch.empty((oh, ow, ix["C"]), dtype=dtype, device=self._dev)
             oval = torch.empty((oh, ow), dtype=torch.uint8, device=self._dev) if with_valid else None
-            fn = "window_warp_u16" if dtype == torch.uint16 else "window_warp_u8"
-            H, W = self.levels[0]
-            status = getattr(_lib.load(), "dsic_" + fn)(
-                _p(src), None if valid is None else _p(valid), lw[2], lw[3], lw[0], lw[1], ix["C"], level,
-                *self.levels[level], H, W, (ctypes.c_int64 * 6)(*m), _p(img), None if oval is None else _p(oval), oh, ow,
-                mode, ix.get("nodata", -1), fill, _stream())
-            _lib.check(status, fn)
-        st.update(level=level, level_window=lw, matrix_q16=m)
-        self._finish(st, before, stats)
+            _call_by_width("window_warp", src, _opt(valid), lw[2], lw[3], lw[0], lw[1], ix["C"], level, *self.levels[level],
+                           *self.levels[0], (ctypes.c_int64 * 6)(*m), _p(img), _opt(oval), oh, ow, mode,
+                           ix.get("nodata", -1), fill, _stream())
+        self._finish(st, before, stats, level=level, level_window=lw, matrix_q16=m)
         return (img, oval.bool()) if with_valid else img
 
     @torch.no_grad()
@@ -845,15 +826,11 @@ class ImageReader:
                 img[:, :, n - 1] = 0
         else:
             stretch = self._default_stretch(level, stretch, st)
-            src, valid = self._warp_source(level, lw, self._display_out(ix)[0], st)
+            src, valid = self._source_window(level, lw, self._display_out(ix)[0], st)
             img = torch.empty((oh, ow, n), dtype=torch.uint8, device=self._dev)
-            fn = "window_warp_render_u16" if src.dtype == torch.uint16 else "window_warp_render_u8"
-            H, W = self.levels[0]
-            status = getattr(_lib.load(), "dsic_" + fn)(
-                _p(src), None if valid is None else _p(valid), lw[2], lw[3], lw[0], lw[1], ix["C"], level,
-                *self.levels[level], H, W, (ctypes.c_int64 * 6)(*m), (ctypes.c_int * len(bands))(*bands), len(bands),
-                _c._lohi(stretch), _p(img), oh, ow, mode, ix.get("nodata", -1), alpha, background, _stream())
-            _lib.check(status, fn)
-        st.update(level=level, level_window=lw, matrix_q16=m)
-        self._finish(st, before, stats)
+            _call_by_width("window_warp_render", src, _opt(valid), lw[2], lw[3], lw[0], lw[1], ix["C"], level,
+                           *self.levels[level], *self.levels[0], (ctypes.c_int64 * 6)(*m),
+                           (ctypes.c_int * len(bands))(*bands), len(bands), _c._lohi(stretch), _p(img), oh, ow, mode,
+                           ix.get("nodata", -1), alpha, background, _stream())
+        self._finish(st, before, stats, level=level, level_window=lw, matrix_q16=m)
         return img

@@ -901,7 +901,8 @@ int dsic_band_histogram_u16(const uint16_t* img_hwc, const uint8_t* valid_hw, in
  *   |m[2]|, |m[5]| >= 2^47; a source window that does not contain every tap of every inside sample
  *   (the range is exact at the four corner pixels, widened by the mode's taps and clamped to the
  *   level); nodata or fill beyond the element type; misaligned pointers; overlapping buffers; and
- *   what dsic_window_render_u8 refuses of its display arguments. */
+ *   what dsic_window_render_u8 refuses of its display arguments, in the same words and the same
+ *   order (one check serves both, csrc/render.h). */
 int dsic_window_warp_u8(const uint8_t* src_hwc, const uint8_t* src_valid, int sh, int sw, int sy0,
                         int sx0, int C, int shift, int LH, int LW, int H, int W, const int64_t* m,
                         uint8_t* dst_hwc, uint8_t* dst_valid, int oh, int ow, int mode, int nodata,

@@ -215,6 +215,30 @@ def test_the_histogram_calls_check_their_arguments_without_a_gpu():
     assert L.dsic_band_histogram_u16(a + 1, None, 4, 4, 3, -1, b, None) == E and b"aligned" in err()
 
 
+def test_both_render_exports_refuse_faulty_display_arguments_in_the_same_words():
+    """One display check behind dsic_window_render_* and dsic_window_warp_render_*: each fault alone, nothing launched."""
+    L = lib.load()
+    a, b = 1 << 20, 1 << 24
+    for name, top in (("u8", 255), ("u16", 65535)):
+        good = dict(bands=(0, 1, 2), nb=3, lohi=[(0, top)] * 3, alpha=1, background=0)
+        for fault, word in ((dict(nb=2), "nb=2"), (dict(alpha=2), "alpha=2"), (dict(background=256), "background=256"),
+                            (dict(bands=None), "null pointer"), (dict(lohi=[(0, top), (9, 8), (0, top)]), "stretch pair (9, 8)"),
+                            (dict(lohi=[(0, top + 1)] + [(0, top)] * 2), f"stretch pair (0, {top + 1})"),
+                            (dict(bands=(0, 3, 1)), "band 3"), (dict(bands=(-1, 0, 0)), "band -1")):
+            p = dict(good, **fault)
+            bands = None if p["bands"] is None else (ctypes.c_int * 3)(*p["bands"])
+            display = (bands, p["nb"], codec._lohi(p["lohi"]), b, 8, 8, 0, -1, p["alpha"], p["background"], None)
+            said = []
+            for export, geometry in (("window_render_", (8, 8, 0, 0, 3, 0, 0, 0, 8, 8)),
+                                     ("window_warp_render_", (8, 8, 0, 0, 3, 0, 8, 8, 8, 8,
+                                                              (ctypes.c_int64 * 6)(65536, 0, 0, 0, 65536, 0)))):
+                assert getattr(L, "dsic_" + export + name)(a, None, *geometry, *display) == lib.DSIC_EINVAL, (export, fault)
+                head, _, rest = L.dsic_last_error().decode().partition(": ")
+                assert head == export + name and rest
+                said.append(rest)
+            assert said[0] == said[1] and said[0].startswith(word), (name, fault, said)
+
+
 # ---- the reader's and the tool's argument errors ----------------------------------------------------------------------
 def _reader(C, kind, **extra):
     """A reader over nothing, one level open: every refusal below comes before the first read of a tile"""
