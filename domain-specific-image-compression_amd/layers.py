@@ -48,6 +48,15 @@ def __getattr__(name):   # layers.WINO_BF16: the current variant (read-only view
     raise AttributeError(name)
 
 
+def _written(param):
+    """Before a derived form of `param` (packed weights, GDN's effective beta / gamma) goes into its cache: the packers
+    run on the current stream, and the cache is read from every stream the model is later called on (bench.py's lanes,
+    each with a hyperprior side stream of its own) with nothing that orders those streams behind this one.  Once per
+    weight version, so the host wait costs the first call only."""
+    if param.is_cuda:
+        torch.cuda.current_stream(param.device).synchronize()
+
+
 class _GammaConv(nn.Module):
     """Holder for `gamma_conv.weight` [C,1,1,1] (layers.py:15-17)."""
 
@@ -82,6 +91,7 @@ class GDN(nn.Module):
             beta = self.beta ** 2 - self.reparam_offset
             gamma = (w ** 2 - self.reparam_offset).reshape(-1)
             self._eff = (beta.contiguous(), gamma.contiguous())
+            _written(w)
             self._eff_key = key
         return self._eff
 
@@ -140,7 +150,9 @@ class _ConvBase(nn.Module):
         if self._cache_key != key:
             self._cache, self._cache_key = {}, key
         if form not in self._cache:
-            self._cache[form] = make()
+            packed = make()
+            _written(self.weight)
+            self._cache[form] = packed
         return self._cache[form]
 
     def packed(self):
