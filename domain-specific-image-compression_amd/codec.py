@@ -785,118 +785,167 @@ def band_range(img, valid=None) -> list:
     return list(zip(v[0::2], v[1::2]))
 
 
-def _gather(img, kind, g, C, first, n, scale=None):
-    L = _lib.load()
-    if kind == KIND_U16_HWC:               # normalised on the way: the tiles gather_f32 cuts from norm(img)
-        tiles = torch.empty((n, C, g["th"], g["tw"]), dtype=torch.float32, device=img.device)
-        if g["overlap"]:
-            status = L.dsic_tile_gather_u16_ov(_p(img), _p(tiles), g["H"], g["W"], C, g["th"], g["tw"], g["overlap"],
-                                               _lohi(scale), first, n, _stream())
-        else:
-            status = L.dsic_tile_gather_u16(_p(img), _p(tiles), g["H"], g["W"], C, g["th"], g["tw"], _lohi(scale),
-                                            first, n, _stream())
-        _lib.check(status, "tile_gather_u16_ov" if g["overlap"] else "tile_gather_u16")
-        return tiles
-    if kind == KIND_U8_HWC:
-        tiles = torch.empty((n, g["th"], g["tw"], C), dtype=torch.uint8, device=img.device)
-        what = "tile_gather_u8"
-    else:
-        tiles = torch.empty((n, C, g["th"], g["tw"]), dtype=torch.float32, device=img.device)
-        what = "tile_gather_f32"
-    if g["overlap"]:
-        what += "_ov"
-        status = getattr(L, "dsic_" + what)(_p(img), _p(tiles), g["H"], g["W"], C, g["th"], g["tw"], g["overlap"],
-                                            first, n, _stream())
-    else:
-        status = getattr(L, "dsic_" + what)(_p(img), _p(tiles), g["H"], g["W"], C, g["th"], g["tw"], first, n,
-                                            _stream())
-    _lib.check(status, what)
+# What gathers the tiles of a kind: the export, whether the tiles are planar ([n,C,th,tw]; else [n,th,tw,C]), their dtype,
+# and whether the export takes the scale (a uint16 image is normalised on the way: the tiles gather_f32 cuts from norm(img)).
+_Gather = collections.namedtuple("_Gather", "export planar dtype lohi")
+_GATHERS = {KIND_U8_HWC: _Gather("tile_gather_u8", False, torch.uint8, False),
+            KIND_F32_CHW: _Gather("tile_gather_f32", True, torch.float32, False),
+            KIND_U16_HWC: _Gather("tile_gather_u16", True, torch.float32, True)}
+
+
+def _gather(img, kind, g, C, ids, scale=None):
+    """The tiles `ids` (ascending tile numbers) of an image on the device as one batch tensor: one library call per run
+    of consecutive numbers, into that run's slice, so a batch of consecutive tiles is one call."""
+    e = _GATHERS[kind]
+    what = e.export + ("_ov" if g["overlap"] else "")
+    export = getattr(_lib.load(), "dsic_" + what)
+    tiles = torch.empty((len(ids), C, g["th"], g["tw"]) if e.planar else (len(ids), g["th"], g["tw"], C), dtype=e.dtype,
+                        device=img.device)
+    args = ((g["H"], g["W"], C, g["th"], g["tw"]) + ((g["overlap"],) if g["overlap"] else ())
+            + ((_lohi(scale),) if e.lohi else ()))
+    a = 0
+    while a < len(ids):
+        b = a + 1
+        while b < len(ids) and ids[b] == ids[b - 1] + 1:
+            b += 1
+        _lib.check(export(_p(img), _p(tiles[a:b]), *args, ids[a], b - a, _stream()), what)
+        a = b
     return tiles
 
 
-def _level_grid(H, W, kind, tile, overlap, tau):
-    """tile_grid of one image as compress_image codes it, and its overlap; ValueError where it cannot."""
-    g = tile_grid(H, W, tile, overlap)
-    overlap = _check_overlap(overlap, g["th"], g["tw"], "compress_image")
-    if tau is not None:
-        if kind != KIND_U8_HWC:
-            raise ValueError("compress_image: max_error bounds the error of integer pixel values; pass the image as "
-                             "uint8 [H,W,C], not float32")
-        if overlap:
-            raise ValueError("compress_image: max_error together with overlap > 0 is not supported (the predictor "
-                             "would be the blended image)")
-    return g, overlap
+# ---- compress_image's options: what each goes with, stated once -----------------------------------------------------------
+# _REFUSALS: (an option, what it meets, the refusal), in the order a caller meets them: the first row that applies is the
+# message.  "value": the option's own check (_checked_options), which for an option that FORMATS knows is the check of
+# its field (_FIELDS); "kind": an image kind its version of FORMATS does not list; any other name is a flag of
+# _checked_options.  Beyond FORMATS the writer refuses float32 with max_error and nodata, nodata with overviews, fill
+# without valid; and max_error's own rows stand behind level 0's geometry, which they are checked against.
+def _with(a, b, note=""):
+    return a, b, f"compress_image: {a} together with {b} is not supported{note}"
 
 
-def _compress_masked(model, x, g, C, batch, tail, header, valid=None) -> bytes:
-    """The stream of an image on the device whose header's version has a mask block: classify the tiles, code those that
-    are not empty (a batch is gathered run by run of consecutive tile numbers into slices of one tensor, so every
-    tile's strings are those of the stream without the mask), and put the mixed tiles' masks into the mask block.
-    valid None: the nodata mask of a uint8 image, read off its pixels.  valid (uint8 [H,W] on the device, 0 = invalid):
-    the states and the planes come from the mask itself (dsic_valid_classify, dsic_valid_delta_planes), and a uint16
-    image is gathered with its scale, as the stream's tiles without the mask are."""
-    v = header[FORMATS[_version_for(header)].key]
-    owned = [_owned_in_tile(g, t) for t in range(g["n"])]
-    counts = _mask.classify(x, g, C, v) if valid is None else _mask.classify_valid(valid, g)
-    states = _mask.tile_states(counts, [(b - a) * (d - c) for a, b, c, d in owned])
-    ids = [t for t, s in enumerate(states) if s != _mask.EMPTY]
-    L, blobs = _lib.load(), []
-    u16 = x.dtype == torch.uint16
-    for first in range(0, len(ids), batch):
-        sel = ids[first:first + batch]
-        tiles = (torch.empty((len(sel), C, g["th"], g["tw"]), dtype=torch.float32, device=x.device) if u16 else
-                 torch.empty((len(sel), g["th"], g["tw"], C), dtype=torch.uint8, device=x.device))
-        a = 0
-        while a < len(sel):
-            b = a + 1
-            while b < len(sel) and sel[b] == sel[b - 1] + 1:
-                b += 1
-            if u16:
-                _lib.check(L.dsic_tile_gather_u16(_p(x), _p(tiles[a:b]), g["H"], g["W"], C, g["th"], g["tw"],
-                                                  _lohi(header["scale"]), sel[a], b - a, _stream()), "tile_gather_u16")
-            else:
-                _lib.check(L.dsic_tile_gather_u8(_p(x), _p(tiles[a:b]), g["H"], g["W"], C, g["th"], g["tw"], sel[a], b - a,
-                                                 _stream()), "tile_gather_u8")
-            a = b
-        blobs.append(entropy.compress_to_container(model, tiles, tail, segments=header["segments"]))
-    block = _mask.encode_block(x, g, C, v, states) if valid is None else _mask.encode_block(valid, g, None, v, states)
-    return pack_image_stream(header, blobs, mask=block)
+_8BIT = " (the residual tables and the mask classifier are 8-bit)"
+_OPTION_KINDS = {"valid" if e.key == "fill" else e.key: e.kinds for e in FORMATS.values() if e.key}
+_REFUSALS = (
+    ("max_error", "value", None), ("tolerance", "value", None),
+    ("tolerance", "kind", "compress_image: tolerance bounds the error of a uint16 [H,W,C] image; for a uint8 image use "
+                          "max_error (float32 has neither)"),
+    _with("tolerance", "overlap > 0"), _with("tolerance", "valid"), _with("tolerance", "nodata"),
+    _with("tolerance", "max_error"),
+    ("fill", "no valid", "compress_image: fill={fill!r} goes with valid, the mask it fills"),
+    ("valid", "kind", "compress_image: a validity mask goes with integer pixel values; pass the image as uint8 or uint16 "
+                      "[H,W,C], not float32"),
+    _with("valid", "overlap > 0"), _with("valid", "max_error"), _with("valid", "nodata"),
+    ("valid", "value", None), ("fill", "value", None),
+    ("max_error", "kind", _with("max_error", "a uint16 image", _8BIT)[2]),
+    ("nodata", "kind", _with("nodata", "a uint16 image", _8BIT)[2]),
+    ("a uint16 image", "value", None),
+    ("scale", "kind", "compress_image: scale goes with a uint16 [H,W,C] image, not with uint8 or float32"),
+    ("scale", "value", None), ("nodata", "value", None),
+    ("nodata", "float32", "compress_image: nodata compares integer pixel values; pass the image as uint8 [H,W,C], not "
+                          "float32"),
+    _with("nodata", "overlap > 0"), _with("nodata", "max_error"), _with("nodata", "overviews > 0"),
+    ("segments", "value", None), ("channels", "value", None), ("batch", "value", None), ("level 0", "value", None),
+    ("max_error", "float32", "compress_image: max_error bounds the error of integer pixel values; pass the image as uint8 "
+                             "[H,W,C], not float32"),
+    _with("max_error", "overlap > 0", " (the predictor would be the blended image)"),
+    ("overviews > 0", "value", None),
+)
+_Options = collections.namedtuple("_Options", "tile batch tail segments overlap tau nodata scale fill tol masked")
 
 
-def _compress_device_image(model, x, tile, batch, tail, segments, overlap, tau, nodata=None, scale=None, valid=None,
-                           fill=0, tol=None) -> bytes:
-    """compress_image's work on one image that lies contiguous on the model's device, after the argument checks that
-    do not depend on its size -> its DSICI stream.  scale: the checked pairs of a uint16 image; tol: its checked
-    tolerance, or None.  The header is made first; the version it will be written as says what travels beside the
-    containers."""
+def _checked_options(model, kind, H, W, C, tile, batch, tail, segments, overlap, max_error, overviews, nodata, scale, valid,
+                     fill, tolerance) -> _Options:
+    """compress_image's arguments, checked against each other and the image before anything touches the device (the
+    rows of _REFUSALS, in order) -> the options as the levels take them; scale is None where band_range decides it."""
+    what = "compress_image"
+    N, M, in_ch, spatial = _model_shape(model)
+    v = {"max_error": max_error, "tolerance": tolerance, "nodata": nodata, "scale": scale, "fill": fill}
+    on = {"max_error": max_error is not None, "tolerance": tolerance is not None, "nodata": nodata is not None,
+          "scale": scale is not None, "valid": valid is not None, "no valid": valid is None, "overlap > 0": overlap != 0,
+          "fill": not (isinstance(fill, int) and not isinstance(fill, bool) and fill == 0), "overviews > 0": overviews != 0,
+          "a uint16 image": kind == KIND_U16_HWC, "float32": kind == KIND_F32_CHW}
+    shapes = [(H, W)]
+
+    def need(ok, text):
+        if not ok:
+            raise ValueError(f"{what}: {text}")
+
+    def field(key):                        # the check of a caller's value that the stream's field table holds
+        return lambda: _FIELDS[key].dump(None, {key: v[key], "kind": kind}, what)[0]
+
+    def level(l):                          # the geometry of one level -> the overlap as a stream holds it
+        if l == 0 and on["overviews > 0"]:
+            shapes[:] = overview_shapes(H, W, overviews)
+        try:
+            g = tile_grid(*shapes[l], tile, overlap)
+            return _check_overlap(overlap, g["th"], g["tw"], what)
+        except ValueError as e:
+            raise ValueError(f"{e} (overview level {l}, {shapes[l][0]}x{shapes[l][1]})" if l else str(e)) from None
+
+    checks = {"max_error": field("max_error"), "tolerance": field("tolerance"), "nodata": field("nodata"),
+              "fill": field("fill"), "scale": lambda: check_scale(scale, C, what),
+              "valid": lambda: _check_valid(valid, H, W, what),
+              "a uint16 image": lambda: need(1 <= C <= 4, f"a uint16 image has 1 to 4 bands, got {C}"),
+              "segments": lambda: entropy.check_segments(segments, M, what),
+              "channels": lambda: need(C == in_ch, f"image has {C} channels, the model takes {in_ch}"),
+              "batch": lambda: need(int(batch) >= 1, f"batch={int(batch)}") or int(batch),
+              "level 0": lambda: level(0), "overviews > 0": lambda: [level(l) for l in range(1, len(shapes))]}
+    for option, other, text in _REFUSALS:
+        if not on.get(option, True):       # segments, channels, batch and level 0 are always there
+            continue
+        if other == "value":
+            v[option] = checks[option]()
+        elif kind not in _OPTION_KINDS[option] if other == "kind" else on[other]:
+            raise ValueError(text.format(fill=fill))
+    return _Options(tile, v["batch"], tail, v["segments"], v["level 0"], v["max_error"], v["nodata"], v["scale"],
+                    v["fill"] if on["valid"] else None, v["tolerance"], on["valid"])
+
+
+def _at_level(o, level) -> _Options:
+    """The options of one level of the pyramid: level 0 alone carries the error bounds (an overview is a preview)."""
+    return o if level == 0 else o._replace(tau=None, tol=None)
+
+
+def _compress_level(model, x, o, valid=None) -> bytes:
+    """One image that lies contiguous on the model's device, with its level's checked options (and its validity image:
+    uint8 [H,W], 0 = invalid) -> its DSICI stream.  The header is made first; the version it will be written as says
+    what travels beside the containers.  With a mask block only the tiles that are not empty are coded, in ascending
+    tile number, `batch` to a container; gathered run by run, every tile's strings are those of the stream without the
+    mask.  With a residual layer compress_to_container's work is done here, keeping the forward x_hat: the predictor
+    the decoder will have bit for bit."""
     kind, H, W, C = _image_kind(x, "compress_image")
     N, M, in_ch, spatial = _model_shape(model)
-    g, overlap = _level_grid(H, W, kind, tile, overlap, tau)
+    g = tile_grid(H, W, o.tile, o.overlap)
     header = {"numerics": entropy.numerics_tag(), "H": H, "W": W, "C": C, "kind": kind, "th": g["th"], "tw": g["tw"],
-              "N": N, "M": M, "in_ch": in_ch, "spatial_params": spatial, "batch": batch, "segments": segments, "overlap": overlap}
-    header.update({key: value for key, value in (("max_error", tau), ("nodata", nodata), ("scale", scale),
-                                                 ("fill", None if valid is None else fill), ("tolerance", tol))
-                   if value is not None})
+              "N": N, "M": M, "in_ch": in_ch, "spatial_params": spatial, "batch": o.batch, "segments": o.segments,
+              "overlap": o.overlap}
+    header.update({key: value for key, value in (("max_error", o.tau), ("nodata", o.nodata), ("scale", o.scale),
+                                                 ("fill", o.fill), ("tolerance", o.tol)) if value is not None})
     e = FORMATS[_version_for(header)]
-    if e.mask:
-        return _compress_masked(model, x, g, C, batch, tail, dict(header, overlap=0), valid)
-    blobs, residuals = [], None if e.layer is None else []
-    for first in range(0, g["n"], batch):
-        n = min(batch, g["n"] - first)
-        tiles = _gather(x, kind, g, C, first, n, scale)
+    ids = range(g["n"])
+    if e.mask:                             # nodata: the mask is read off the pixels; valid: it comes from the mask itself
+        owned = [_owned_in_tile(g, t) for t in ids]
+        counts = _mask.classify(x, g, C, header[e.key]) if valid is None else _mask.classify_valid(valid, g)
+        states = _mask.tile_states(counts, [(b - a) * (d - c) for a, b, c, d in owned])
+        ids = [t for t, s in enumerate(states) if s != _mask.EMPTY]
+    blobs, residuals, block = [], None if e.layer is None else [], None
+    for first in range(0, len(ids), o.batch):
+        sel = ids[first:first + o.batch]
+        tiles = _gather(x, kind, g, C, sel, o.scale)
         if e.layer is None:
-            blobs.append(entropy.compress_to_container(model, tiles, tail, segments=segments))
+            blobs.append(entropy.compress_to_container(model, tiles, o.tail, segments=o.segments))
             continue
-        # compress_to_container's work, keeping the forward x_hat: the predictor the decoder will have bit for bit
-        c = entropy._coded_batch(model, tiles, tail, entropy.DEFAULT_LMAX, "compress_image", pack=True,
-                                 segments=segments)
+        c = entropy._coded_batch(model, tiles, o.tail, entropy.DEFAULT_LMAX, "compress_image", pack=True,
+                                 segments=o.segments)
         blobs.append(c["container"][:c["container_bytes"]].cpu().numpy().tobytes())
         if e.layer is _residual16:             # the gathered tiles are normalised float32: the image is read in place
-            residuals.append(_residual16.encode_block(x, c["x_hat"], H, W, g["th"], g["tw"], _lohi(scale), tol, first))
+            residuals.append(_residual16.encode_block(x, c["x_hat"], H, W, g["th"], g["tw"], _lohi(o.scale), o.tol, sel[0]))
         else:
-            residuals.append(_residual.encode_block(tiles, c["x_hat"], [_owned_in_tile(g, t)
-                                                                       for t in range(first, first + n)], tau))
-    return pack_image_stream(header, blobs, residuals)
+            residuals.append(_residual.encode_block(tiles, c["x_hat"], [_owned_in_tile(g, t) for t in sel], o.tau))
+    if e.mask:
+        block = (_mask.encode_block(x, g, C, header[e.key], states) if valid is None else
+                 _mask.encode_block(valid, g, None, header[e.key], states))
+    return pack_image_stream(header, blobs, residuals, block)
 
 
 @torch.no_grad()
@@ -907,11 +956,10 @@ def compress_image(model, img, tile=256, batch=64, tail=10, segments=1, overlap=
     DSIC2 container.  segments = K > 1 (1, 2, 4, 8 or 16, dividing M): every tile's y string is K independent strings
     (DSIC3 containers, stream version 2), which the decoders read on K waves per tile; the decoded image is the same.
     overlap = O > 0 (a multiple of 16, at most half a tile side): tiles share O pixels with their neighbours
-    (tile_grid) and the decoders cross-fade them over that band (stream version 3); 0 writes today's streams.
+    (tile_grid) and the decoders cross-fade them over that band (stream version 3).
     max_error = tau (an integer 0 .. 127; uint8 images, overlap = 0): the near-lossless mode (stream version 4).
     Behind every container, byte for byte the one written without max_error, goes a residual block (residual.py),
-    and the decoders return a uint8 image within tau of img on every pixel and channel; 0 is lossless.  None writes
-    today's streams.
+    and the decoders return a uint8 image within tau of img on every pixel and channel; 0 is lossless.
     overviews = n > 0 writes a DSICP stream instead (pack_pyramid_stream): the image and its n overview levels
     (build_overviews, made on the device from the one upload), every level coded with the same tile, batch, tail,
     segments and overlap, its bytes the DSICI stream this call returns for that level's image alone; a level smaller
@@ -919,33 +967,28 @@ def compress_image(model, img, tile=256, batch=64, tail=10, segments=1, overlap=
     tiles are too small for the overlap, is a ValueError before anything is coded.  max_error applies to level 0
     only, which is then the version-4 stream of the call without overviews; the overview levels are the lossy
     streams: an overview is a preview, and a residual layer there would add bytes to bound an error against an image
-    the caller never supplied.  0 writes today's streams.
+    the caller never supplied.
     nodata = v (an integer 0 .. 255; uint8 images): a pixel whose C channels all equal v is nodata, and the stream
     (version 5) keeps that mask exactly (mask.py).  Tiles whose owned pixels inside the image are all nodata are
     neither gathered, coded nor decoded; the other tiles' strings are byte for byte those of the stream without
     nodata, and a tile that holds both kinds of pixel carries its mask beside them.  The decoders return v on all
     channels (v / 255.0f for out="f32") at every nodata pixel of img, and at every other pixel the bits the stream
     without nodata decodes to.  Not promised: a valid pixel may happen to decode to (v, ..., v), as it can today.
-    A float32 image, overlap > 0, max_error and overviews > 0 are refused with nodata: each would need a masked
-    variant of its own (predictor, blend, halving over valid pixels only).  None writes today's streams.
     A uint16 image (1 to 4 bands) writes stream version 6, which carries a per-band scale (lo, hi): scale = None takes
     each band's own minimum and maximum (band_range, on the device), otherwise scale is a sequence of C integer pairs
     with 0 <= lo <= hi <= 65535, e.g. [(0, 10000)] * C, and values outside a pair clip to it.  The model codes
     norm(img) (module docstring), so every container is byte for byte that of the float32 image norm(img) compressed
     with the same arguments; segments and overlap work unchanged, and the decoders return uint16 by default.  With
     overviews the scale is decided once, at level 0, and every level is written with it (halved values stay inside
-    [lo, hi]).  scale with a uint8 or float32 image is a ValueError.  max_error and nodata are refused with a uint16
-    image: the residual tables and the mask classifier are 8-bit; max_error stays the uint8 mode, and the bounded-error
-    mode of a uint16 image is tolerance.
+    [lo, hi]).  max_error stays the uint8 mode; the bounded-error mode of a uint16 image is tolerance.
     tolerance = tau (an integer 0 .. 32767; uint16 images, overlap = 0): the bounded-error mode of 16-bit imagery
     (stream version 9).  Behind every container, byte for byte the one the version-6 stream of the same call without
     tolerance holds, goes a wide residual block (residual16.py), and the decoders return a uint16 image within tau of
     img on every pixel and band; 0 returns img itself, also where its values leave the scale (lo, hi), which then only
     affects the rate.  With overviews it applies to level 0 only, as max_error does; the overview levels are the
-    version-6 streams.  The decoders take out=None or "u16" on such a stream; "u8" and "f32" are a ValueError.  A uint8
-    or float32 image (use max_error), overlap > 0, valid, nodata and max_error at the same time are each a ValueError
-    before anything touches the device.  The split of the residual follows each tile's largest step, so one outlier in
-    a quiet tile costs raw bits on every sample of that tile (residual16.py).  None writes today's streams.
+    version-6 streams.  The decoders take out=None or "u16" on such a stream; "u8" and "f32" are a ValueError.  The
+    split of the residual follows each tile's largest step, so one outlier in a quiet tile costs raw bits on every
+    sample of that tile (residual16.py).
     valid = mask (a torch.bool [H,W] tensor on the CPU or the GPU, True = the pixel holds data; uint8 and uint16
     images, with segments and with overviews) with fill = f (an integer 0 .. 255 for uint8, 0 .. 65535 for uint16, the
     value the decoders write at invalid pixels): the stream (version 8) keeps that mask exactly (mask.py; the block's
@@ -958,89 +1001,33 @@ def compress_image(model, img, tile=256, batch=64, tail=10, segments=1, overlap=
     ValueError: the normalised image has no value that means fill), and at every other pixel the bits the stream
     without valid decodes to; with_valid=True of the decoders and decompress_valid return the mask itself.  With
     overviews every level is the version-8 stream of that level's image and mask alone (build_overviews(img, n, valid),
-    the masked halving), with level 0's fill and scale.  Out of scope, each a ValueError before anything touches the
-    device: a float32 image; overlap > 0 (blending across skipped tiles needs renormalised ramps); max_error; nodata at
-    the same time (nodata itself is unchanged); a mask of another shape or dtype; fill out of range, or given without
-    valid.  Invalid pixels inside coded tiles are coded as the caller left them: filling them with something smoother
-    is a bit-rate optimisation that would give up the "same strings as the stream without valid" property.  None writes
-    today's streams."""
-    dev = next(model.parameters()).device
-    tau = None if max_error is None else _residual.check_max_error(max_error, "compress_image")
+    the masked halving), with level 0's fill and scale.  Invalid pixels inside coded tiles are coded as the caller left
+    them: filling them with something smoother is a bit-rate optimisation that would give up the "same strings as the
+    stream without valid" property.
+    Every option's default (0 or None) writes the stream the call wrote before the option existed.  What does not go
+    together is a ValueError before anything touches the device (_REFUSALS, in the order reported): max_error, nodata,
+    valid and tolerance exclude each other and overlap > 0 (the predictor, the blend across skipped tiles and the
+    halving would each need a masked variant of its own), nodata also overviews > 0; max_error and nodata go with uint8
+    images only (the residual tables and the mask classifier are 8-bit, and float32 has no integer pixel values), valid
+    with uint8 or uint16, tolerance and scale with uint16; fill goes with valid; and a value outside its range, or a
+    mask of another shape or dtype."""
     kind, H, W, C = _image_kind(img, "compress_image")
-    tol = None
-    if tolerance is not None:
-        tol = _residual16.check_tolerance(tolerance, "compress_image")
-        if kind != KIND_U16_HWC:
-            raise ValueError("compress_image: tolerance bounds the error of a uint16 [H,W,C] image; for a uint8 image "
-                             "use max_error (float32 has neither)")
-        for name, on in (("overlap > 0", overlap != 0), ("valid", valid is not None), ("nodata", nodata is not None),
-                         ("max_error", max_error is not None)):
-            if on:
-                raise ValueError(f"compress_image: tolerance together with {name} is not supported")
-    if valid is None:
-        if not (isinstance(fill, int) and not isinstance(fill, bool) and fill == 0):
-            raise ValueError(f"compress_image: fill={fill!r} goes with valid, the mask it fills")
-    else:
-        if kind == KIND_F32_CHW:
-            raise ValueError("compress_image: a validity mask goes with integer pixel values; pass the image as uint8 or "
-                             "uint16 [H,W,C], not float32")
-        for name, on in (("overlap > 0", overlap != 0), ("max_error", max_error is not None),
-                         ("nodata", nodata is not None)):
-            if on:
-                raise ValueError(f"compress_image: valid together with {name} is not supported")
-        _check_valid(valid, H, W, "compress_image")
-        fill = _mask.check_fill(fill, 65535 if kind == KIND_U16_HWC else 255, "compress_image")
-    if kind == KIND_U16_HWC:
-        for name, on in (("max_error", max_error is not None), ("nodata", nodata is not None)):
-            if on:
-                raise ValueError(f"compress_image: {name} together with a uint16 image is not supported (the residual "
-                                 "tables and the mask classifier are 8-bit)")
-        if not 1 <= C <= 4:
-            raise ValueError(f"compress_image: a uint16 image has 1 to 4 bands, got {C}")
-        if scale is not None:
-            scale = check_scale(scale, C, "compress_image")
-    elif scale is not None:
-        raise ValueError("compress_image: scale goes with a uint16 [H,W,C] image, not with uint8 or float32")
-    if nodata is not None:
-        nodata = _mask.check_nodata(nodata, "compress_image")
-        if kind != KIND_U8_HWC:
-            raise ValueError("compress_image: nodata compares integer pixel values; pass the image as uint8 [H,W,C], "
-                             "not float32")
-        for name, on in (("overlap > 0", overlap != 0), ("max_error", tau is not None),
-                         ("overviews > 0", overviews != 0)):
-            if on:
-                raise ValueError(f"compress_image: nodata together with {name} is not supported")
-    N, M, in_ch, spatial = _model_shape(model)
-    segments = entropy.check_segments(segments, M, "compress_image")
-    if C != in_ch:
-        raise ValueError(f"compress_image: image has {C} channels, the model takes {in_ch}")
-    batch = int(batch)
-    if batch < 1:
-        raise ValueError(f"compress_image: batch={batch}")
-    shapes = overview_shapes(H, W, overviews) if overviews != 0 else [(H, W)]
-    for level, (h, w) in enumerate(shapes):
-        try:
-            _level_grid(h, w, kind, tile, overlap, tau if level == 0 else None)
-        except ValueError as e:
-            raise ValueError(f"{e} (overview level {level}, {h}x{w})" if level else str(e)) from None
+    o = _checked_options(model, kind, H, W, C, tile, batch, tail, segments, overlap, max_error, overviews, nodata, scale,
+                         valid, fill, tolerance)
+    dev = next(model.parameters()).device
     x = img.to(dev).contiguous()
-    if valid is not None:
-        v8 = valid.to(dev).to(torch.uint8).contiguous()
-        if kind == KIND_U16_HWC and scale is None:
-            scale = band_range(x, v8)
-        if len(shapes) == 1:
-            return _compress_device_image(model, x, tile, batch, tail, segments, 0, None, None, scale, v8, fill)
+    v8 = valid.to(dev).to(torch.uint8).contiguous() if o.masked else None
+    if kind == KIND_U16_HWC and o.scale is None:
+        o = o._replace(scale=band_range(x, v8))
+    levels, masks = [x], [v8]
+    if overviews != 0 and o.masked:
         levels, masks = build_overviews(x, overviews, v8.bool())
-        return pack_pyramid_stream([_compress_device_image(model, lv, tile, batch, tail, segments, 0, None, None, scale,
-                                                           m.to(torch.uint8), fill) for lv, m in zip(levels, masks)])
-    if kind == KIND_U16_HWC and scale is None:
-        scale = band_range(x)
-    if len(shapes) == 1:
-        return _compress_device_image(model, x, tile, batch, tail, segments, overlap, tau, nodata, scale, tol=tol)
-    return pack_pyramid_stream([_compress_device_image(model, lv, tile, batch, tail, segments, overlap,
-                                                       tau if level == 0 else None, scale=scale,
-                                                       tol=tol if level == 0 else None)
-                                for level, lv in enumerate(build_overviews(x, overviews))])
+        masks = [m.to(torch.uint8) for m in masks]
+    elif overviews != 0:
+        levels = build_overviews(x, overviews)
+        masks = [None] * len(levels)
+    streams = [_compress_level(model, lv, _at_level(o, level), m) for level, (lv, m) in enumerate(zip(levels, masks))]
+    return streams[0] if overviews == 0 else pack_pyramid_stream(streams)
 
 
 def _owned_in_tile(g, t):
