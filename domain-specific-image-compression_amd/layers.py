@@ -218,14 +218,15 @@ class Conv2d(_ConvBase):
         return Choice(Kernel.BF16_32, s2d_out=True)
 
     def packed_wino_slices(self):
-        """(lo, hi, bf16 planes, bias) per Cout slice of at most 128, for out_channels > 128 (space-to-depth 5x5/s2)"""
+        """(lo, hi, bf16 planes) per Cout slice of at most 128, for out_channels > 128 (space-to-depth 5x5/s2).  Only
+        what is made from the weight: the cache is keyed on the weight alone, so the bias is sliced at the launch."""
         def make():
             sl = []
             for lo in range(0, self.out_channels, 128):
                 hi = min(lo + 128, self.out_channels)
                 u = ops.pack_wino_s2_weight(self.weight[lo:hi].contiguous())
                 u = ops.split_wino_weight_bf16(u, hi - lo, 4 * self.in_channels, 1)
-                sl.append((lo, hi, u, self.bias[lo:hi].contiguous()))
+                sl.append((lo, hi, u))
             return sl
         return self._cached("wino_slices", make)
 
@@ -255,8 +256,9 @@ class Conv2d(_ConvBase):
         flops = 2.0 * B * H * W * self.in_channels * (25 if x_is_s2d else 9)
         if self.out_channels > 128:
             out = torch.empty((B, H, W, self.out_channels), dtype=torch.float32, device=x.device)
-            for lo, hi, u, bias in self.packed_wino_slices():
-                ops.conv3x3_wino_nhwc(x, u, bias, hi - lo, act, None if beta is None else beta[lo:hi].contiguous(),
+            for lo, hi, u in self.packed_wino_slices():
+                ops.conv3x3_wino_nhwc(x, u, self.bias[lo:hi], hi - lo, act,
+                                      None if beta is None else beta[lo:hi].contiguous(),
                                       None if gamma is None else gamma[lo:hi].contiguous(), out=out, s2d_in=True,
                                       out_coff=lo, split_k=split_k, algo_flops=flops * (hi - lo))
             return out

@@ -73,7 +73,11 @@ int dsic_pack_conv_weight(const float* w_oihw, float* dst, int Cout, int Cin,
 
 /* nn.ConvTranspose2d(Cin,Cout,5,2,2,output_padding=1) weight [Cin,Cout,5,5]
  * (layers.py:83,89,93,123,124) -> the four sub-pixel phase kernels
- * (3x3,3x2,2x3,2x2 taps = all 25 taps) packed [25][Cin/8][CoutP][8]. */
+ * (3x3,3x2,2x3,2x2 taps = all 25 taps) packed [25][Cin/8][CoutP][8], zero
+ * padded: phase py*2+px owns (3-py)(3-px) taps (ty,tx), tx fastest; tap (ty,tx)
+ * of output (2i+py,2j+px) reads input (i-1+ty+py, j-1+tx+px) through
+ * w[py+4-2(ty+py)][px+4-2(tx+px)].  Cin % 8 == 0; dst holds
+ * dsic_packed_conv_weight_floats(Cout, Cin, 5) floats. */
 int dsic_pack_convT_weight(const float* w_iohw, float* dst, int Cin, int Cout,
                            void* stream);
 
@@ -82,7 +86,9 @@ int dsic_pack_convT_weight(const float* w_iohw, float* dst, int Cin, int Cout,
  * contraction over the input grid; packed [9][Cin/16][16][16] fp32, followed
  * by the same values as two bf16 planes [Cin/16][9][hi,mid][half][16][8]
  * (the B operands of the split-bf16 kernel) = together
- * dsic_convT_image_weight_floats(Cin) floats.  Cin % 16 == 0, Cimg in [1,4]. */
+ * dsic_convT_image_weight_floats(Cin) floats.  Column ph*Cimg+c is phase
+ * ph = py*2+px of image channel c; columns >= 4*Cimg are zero; hi = bf16(v) and
+ * mid = bf16(v - hi), both round-to-nearest-even.  Cin % 16 == 0, Cimg in [1,4]. */
 int64_t dsic_convT_image_weight_floats(int Cin);
 int dsic_pack_convT_image_weight(const float* w_iohw, float* dst, int Cin,
                                  int Cimg, void* stream);
@@ -125,7 +131,9 @@ int dsic_conv2d_nhwc(const float* in, const float* w_packed, const float* bias,
 /* 3x3 stride-1 conv() + optional GDN/IGDN/ReLU by Winograd F(2x2,3x3) on the
  * fp32 MFMA (layers.py:56,62,67,86,90,94,108,109): 2.25x fewer multiplies than
  * dsic_conv2d_nhwc, same fp32 operands.  u_packed from dsic_pack_wino_weight
- * (G g G^T per (cout,cin), [16][Cin/8][CoutP][8]).  Cin % 32 == 0, Cout % 4 == 0,
+ * (G g G^T per (cout,cin), [16 positions xi*4+nu][CinP/8][CoutP][8], CinP = ceil8(Cin),
+ * CoutP = ceil32(Cout), zero padded, dsic_wino_weight_floats() floats; the packer takes
+ * any Cin, the kernels below do not).  Cin % 32 == 0, Cout % 4 == 0,
  * Cout <= 128.  in NHWC [B,H,W,Cin] -> out NHWC [B,H,W,Cout].  ticket: 16 bytes of device
  * memory zeroed ONCE by the caller (dynamic tile hand-out of the persistent kernel; each launch
  * leaves it zeroed again; launches sharing a ticket must be ordered on one stream). */
@@ -165,7 +173,8 @@ int dsic_conv_transpose2d_wino_nhwc(const float* in, const float* u_packed4,
  * accumulated in fp32.  dsic_wino_bf16_planes(): planes the library was built with (2: products
  * hh, hm, mh; 3: + mm, hl, lh).  u_f32: transformed weights as written by dsic_pack_wino_weight /
  * dsic_pack_wino_s2_weight (nphase 1) or dsic_pack_wino_convT_weight (nphase 4); dst:
- * nphase * dsic_wino_bf16_weight_bytes(Cout, Cin) bytes, [phase][16][Cin/16][planes][CoutP][16] bf16.
+ * nphase * dsic_wino_bf16_weight_bytes(Cout, Cin) bytes, [phase][16][Cin/16][planes][CoutP][16] bf16;
+ * plane q = bf16(rem_q) round-to-nearest-even, rem_0 = u, rem_q+1 = rem_q - plane_q.  Cin % 32 == 0.
  * The two conv entry points mirror dsic_conv3x3_wino_nhwc / dsic_conv_transpose2d_wino_nhwc
  * (same layers of code/modelv2/layers.py:54-72, 83-97, 108-124; Cin a multiple of 32, >= 64).
  * out_cstride / out_coff (floats; 0 / 0 = a dense [B,H,W,Cout] output): the Cout <= 128 channels of this
