@@ -108,7 +108,7 @@ from . import mask as _mask
 from . import residual as _residual
 from . import residual16 as _residual16
 from .entropy import EntropyError
-from .ops import _p, _stream
+from .ops import _int_option, _p, _stream
 
 MAGIC = b"DSICI\x00"
 VERSION = 1
@@ -255,13 +255,14 @@ def _load_overlap(e, h, w):
     h["overlap"] = _check_overlap(w[0], h["th"], h["tw"], "DSICI stream")
 
 
-def _ranged(key, top, check, note=""):
-    """The field key = v with 0 <= v <= top(h); check(value, top, what): the writer's test of a caller's value."""
+def _ranged(key, top, note="", hint=""):
+    """The field key = v with 0 <= v <= top(h); the writer's test of a caller's value is ops._int_option, whose message
+    says `hint` behind the 0."""
     def load(e, h, w):
         h[key] = w[0]
         if w[0] > top(h):
             raise ValueError(f"DSICI stream: {key}={w[0]} (0 .. {top(h)}{note.format(**h)})")
-    return _Field(_one, load, lambda e, h, what: [check(h[key], top(h), what)])
+    return _Field(_one, load, lambda e, h, what: [_int_option(h[key], key, top(h), what, hint)])
 
 
 def _load_bands(e, h, w):
@@ -284,15 +285,14 @@ def _dump_scale(e, h, what):
 _FIELDS = {
     "segments": _Field(_one, _load_segments, lambda e, h, what: [h["segments"]]),
     "overlap": _Field(_one, _load_overlap, lambda e, h, what: [h["overlap"]]),
-    "max_error": _ranged("max_error", lambda h: 127, lambda v, top, what: _residual.check_max_error(v, what)),
+    "max_error": _ranged("max_error", lambda h: 127, hint=" (lossless)"),
     "res_bands": _Field(_one, _load_bands, lambda e, h, what: [e.layer.BANDS]),
-    "nodata": _ranged("nodata", lambda h: 255, lambda v, top, what: _mask.check_nodata(v, what)),
+    "nodata": _ranged("nodata", lambda h: 255),
     "coded": _Field(_one, lambda e, h, w: h.update(coded=w[0]), lambda e, h, what: [h["coded"]]),
-    "fill": _ranged("fill", lambda h: 65535 if h["kind"] == KIND_U16_HWC else 255, _mask.check_fill, " for kind {kind}"),
+    "fill": _ranged("fill", lambda h: 65535 if h["kind"] == KIND_U16_HWC else 255, " for kind {kind}"),
     # C pairs (lo, hi) of a uint16 image; a version that also takes kind 0 (8) has none there
     "scale": _Field(lambda e, h: 2 * h["C"] if h["kind"] == KIND_U16_HWC else 0, _load_scale, _dump_scale),
-    "tolerance": _ranged("tolerance", lambda h: _residual16.MAX_TOLERANCE,
-                         lambda v, top, what: _residual16.check_tolerance(v, what)),
+    "tolerance": _ranged("tolerance", lambda h: _residual16.MAX_TOLERANCE, hint=" (lossless)"),
 }
 
 # A version, stated once.  kinds: the image kinds it goes with; fields: what follows the fixed head, in order; segments:

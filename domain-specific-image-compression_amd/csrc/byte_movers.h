@@ -1,6 +1,7 @@
-// Device helpers shared by the byte movers of image_codec.hip and residual.hip: 16-byte loads from any address, a
-// string copy split over workgroups, the workgroup prefix sum that turns string lengths into offsets, and the
-// little-endian field writers of the container heads; and the workgroup counts of their launches.  The chunk walk of
+// Device helpers shared by the byte movers of image_codec.hip, residual_block.h and mask.hip: 16-byte loads from any
+// address, a string copy split over workgroups, the workgroup prefix sum and the one loop over it that turns n string
+// lengths into offsets (scan_offsets), and the little-endian field writers of the container heads; and the workgroup
+// counts of their launches.  The chunk walk of
 // the HWC outputs is hwc_chunks.h.  Whether two buffers meet is buffers_apart of common.h.
 #pragma once
 #include "common.h"
@@ -59,6 +60,22 @@ __device__ inline long long block_exclusive_scan(long long v, long long* lds4, l
   __syncthreads();
   *total = tot;
   return base + s - v;
+}
+
+// n lengths -> offsets, by one 256-thread workgroup: out[s] = len(0) + ... + len(s - 1) for s < n, 256 lengths per pass
+// with the carry of the passes before; returns the sum of all n (in every thread).  len(s) is called once, by the
+// thread that writes out[s].  The head kernels of the container, the residual block and the mask records use it.
+template <class F>
+__device__ inline long long scan_offsets(int n, F len, long long* lds4, long long* out) {
+  long long carry = 0;
+  for (int s0 = 0; s0 < n; s0 += blockDim.x) {
+    const int s = s0 + threadIdx.x;
+    long long tot;
+    const long long ex = block_exclusive_scan(s < n ? (long long)len(s) : 0, lds4, &tot);
+    if (s < n) out[s] = carry + ex;
+    carry += tot;
+  }
+  return carry;
 }
 
 __device__ __forceinline__ float clamp01(float v) { return v < 0.f ? 0.f : (v > 1.f ? 1.f : v); }  // torch clamp(0,1)

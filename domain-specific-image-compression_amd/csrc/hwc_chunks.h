@@ -1,5 +1,6 @@
 // The chunk walk of the HWC byte movers (image_codec.hip, image_u16.hip, mask.hip, halve.h), stated once over the
-// element type T (uint8_t or uint16_t).  An output is written as aligned 16-byte chunks of E = 16 / sizeof(T) elements,
+// element type T (uint8_t or uint16_t; float for the one-channel rows of mask.hip's float32 window, whose base is
+// 16-byte aligned, mis = 0).  An output is written as aligned 16-byte chunks of E = 16 / sizeof(T) elements,
 // one thread per chunk.  The output may begin `mis` elements behind a 16-byte boundary: positions then count elements
 // shifted by mis, so that position q0, a multiple of E, is an aligned 16 bytes of memory at img + (q0 - mis).  A chunk
 // that lies whole inside its row segment (or flat array) is one dwordx4 store; a ragged chunk at either end is element

@@ -408,18 +408,11 @@ __global__ __launch_bounds__(256) void pack_head_kernel(const int* __restrict__ 
       put_u32(out + hb + (int64_t)kRecBytes * B + i, i & 3, (uint32_t)clamp_len(lengths[S * b + 1 + j], cap_y));
     }
   }
-  long long carry = 0;
-  for (int s0 = 0; s0 < S * B; s0 += blockDim.x) {
-    const int s = s0 + tid;
-    const long long v = s < S * B ? clamp_len(lengths[s], (s % S) ? cap_y : cap_z) : 0;
-    long long tot;
-    const long long ex = block_exclusive_scan(v, lds4, &tot);
-    if (s < S * B) ws[2 + s] = carry + ex;
-    carry += tot;
-  }
+  const long long total =
+      scan_offsets(S * B, [&](int s) { return clamp_len(lengths[s], (s % S) ? cap_y : cap_z); }, lds4, ws + 2);
   if (tid == 0) {
-    ws[2 + S * B] = carry;
-    ws[0] = body_offset(B, K) + carry;
+    ws[2 + S * B] = total;
+    ws[0] = body_offset(B, K) + total;
     ws[1] = err ? *err : 0;
   }
 }
@@ -453,17 +446,15 @@ __global__ __launch_bounds__(256) void scatter_head_kernel(const uint8_t* __rest
     meta[4 * b] = min_y, meta[4 * b + 1] = max_y - min_y + 1;
     meta[4 * b + 2] = min_z, meta[4 * b + 3] = max_z - min_z + 1;
   }
-  long long carry = 0;
-  for (int s0 = 0; s0 < 2 * B; s0 += blockDim.x) {
-    const int s = s0 + tid;
-    const uint32_t len = s < 2 * B ? get_u32(blob + kHeadBytes + (size_t)kRecBytes * (s >> 1) + 16 + 4 * (s & 1)) : 0;
-    if (s < 2 * B) lengths[s] = (int)len;
-    long long tot;
-    const long long ex = block_exclusive_scan(len, lds4, &tot);
-    if (s < 2 * B) ws[2 + s] = carry + ex;
-    carry += tot;
-  }
-  if (tid == 0) ws[2 + 2 * B] = carry, ws[0] = kHeadBytes + (long long)kRecBytes * B + carry, ws[1] = 0;
+  const long long total = scan_offsets(  // a length is stored as it is read: the thread of string s keeps lengths[s]
+      2 * B,
+      [&](int s) {
+        const uint32_t len = get_u32(blob + kHeadBytes + (size_t)kRecBytes * (s >> 1) + 16 + 4 * (s & 1));
+        lengths[s] = (int)len;
+        return len;
+      },
+      lds4, ws + 2);
+  if (tid == 0) ws[2 + 2 * B] = total, ws[0] = kHeadBytes + (long long)kRecBytes * B + total, ws[1] = 0;
 }
 
 __global__ __launch_bounds__(256) void scatter_strings_kernel(const uint8_t* __restrict__ blob, int64_t blob_bytes,
@@ -614,16 +605,12 @@ extern "C" int dsic_tile_blend_window_f32(const float* tiles, const int* tile_id
                                           void* stream) {
   DSIC_REQUIRE(tiles && tile_ids && canvas, "tile_blend_window_f32: null pointer");
   DSIC_REQUIRE(C >= 1 && C <= 8, "tile_blend_window_f32: C=%d must be in 1..8", C);
-  const char* ge = grid_error(H, W, th, tw);
-  DSIC_REQUIRE(!ge, "tile_blend_window_f32: %s (H=%d W=%d th=%d tw=%d)", ge ? ge : "", H, W, th, tw);
-  DSIC_REQUIRE(overlap_ok(th, tw, overlap),
-               "tile_blend_window_f32: overlap=%d must be a multiple of 16 in 0..min(th, tw)/2", overlap);
+  DSIC_GRID_OV("tile_blend_window_f32", overlap);
   DSIC_REQUIRE(wy0 >= 0 && wx0 >= 0 && wh >= 1 && ww >= 1 && (int64_t)wy0 + wh <= H && (int64_t)wx0 + ww <= W,
                "tile_blend_window_f32: window %dx%d at (%d, %d) outside the %dx%d image", wh, ww, wy0, wx0, H, W);
   DSIC_REQUIRE(n_tiles >= 1 && n_tiles <= kBlendIds, "tile_blend_window_f32: n=%d tiles per call (1..%d)", n_tiles,
                kBlendIds);
   DSIC_REQUIRE(((uintptr_t)canvas & 15) == 0, "tile_blend_window_f32: canvas must be 16-byte aligned");
-  const Grid g = make_grid(H, W, th, tw, overlap);
   const float rcp = overlap ? 1.0f / (float)(2 * overlap) : 0.f;
   hipLaunchKernelGGL(blend_f32_kernel, dim3(g.th / kTileRows, n_tiles, C), dim3(256), 0, (hipStream_t)stream, tiles,
                      tile_ids, n_tiles, canvas, g, Clip{wy0, wy0 + wh, wx0, wx0 + ww}, rcp);

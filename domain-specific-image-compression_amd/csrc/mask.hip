@@ -20,7 +20,12 @@
 //                 copies its raw bytes; then the XOR prefix down every 16-bit column strip
 //   apply         m planes, (tile, plane or -1 = all set) per tile -> v (uint8 or uint16 HWC, one kernel over the
 //                 element type) or v / 255.0f (float32 CHW) at the tile's owned pixels inside the window whose bit is
-//                 set; nothing else is written.  The HWC outputs are walked in the chunks of hwc_chunks.h.
+//                 set; nothing else is written.  All three window writers (and the validity window) open with
+//                 window_rows and walk their rows in the chunks of hwc_chunks.h.
+//
+// What this file shares is stated elsewhere: the grid, its argument checks, kTileRows and a tile's part of a window in
+// tile_grid.h; the offsets scan of the pack head in byte_movers.h.  The nodata exports (C = 3, 4) and the validity
+// exports (C = 1) are one launcher each, at the end of the file.
 #include <limits.h>
 
 #include "byte_movers.h"
@@ -28,8 +33,6 @@
 #include "tile_grid.h"
 
 namespace dsic {
-
-constexpr int kMaskRows = 16;  // rows of one tile per workgroup of classify and apply
 
 // bit e = pixel e of the 16 at p is nodata; all 16 C bytes are read
 template <int C>
@@ -89,14 +92,14 @@ __device__ __forceinline__ int wave_sum(int v) {
   return v;  // in lane 0
 }
 
-// blockIdx.y = tile first + blockIdx.y, blockIdx.x = a block of kMaskRows of its rows; counts[blockIdx.y] += nodata
+// blockIdx.y = tile first + blockIdx.y, blockIdx.x = a block of kTileRows of its rows; counts[blockIdx.y] += nodata
 template <int C>
 __global__ __launch_bounds__(256) void mask_classify_kernel(const uint8_t* __restrict__ img, Grid g, uint32_t v,
                                                             int first, int* __restrict__ counts) {
   const Owned o = owned(g, first + blockIdx.y);
-  const int S = g.tw >> 4, r0 = blockIdx.x * kMaskRows;
+  const int S = g.tw >> 4, r0 = blockIdx.x * kTileRows;
   int cnt = 0;
-  for (int i = threadIdx.x; i < kMaskRows * S; i += blockDim.x) {
+  for (int i = threadIdx.x; i < kTileRows * S; i += blockDim.x) {
     const int r = i / S;
     cnt += __popc(mask16<C>(img, g.W, o, v, r0 + r, i - r * S));
   }
@@ -155,17 +158,14 @@ __global__ __launch_bounds__(256) void mask_pack_head_kernel(const int* __restri
     const uint32_t f[3] = {(uint32_t)ids[t], (uint32_t)mode, (uint32_t)bytes};
     put_u32(out + i, k & 3, f[k >> 2]);
   }
-  long long carry = 0;
-  for (int t0 = 0; t0 < n; t0 += blockDim.x) {
-    const int t = t0 + tid;
-    int mode;
-    const long long v = t < n ? payload_bytes(pop, t, bits, &mode) : 0;
-    long long tot;
-    const long long ex = block_exclusive_scan(v, lds4, &tot);
-    if (t < n) ws[2 + t] = carry + ex;
-    carry += tot;
-  }
-  if (tid == 0) ws[0] = (long long)kMaskRec * n + carry, ws[1] = 0;
+  const long long total = scan_offsets(
+      n,
+      [&](int t) {
+        int mode;
+        return payload_bytes(pop, t, bits, &mode);
+      },
+      lds4, ws + 2);
+  if (tid == 0) ws[0] = (long long)kMaskRec * n + total, ws[1] = 0;
 }
 
 // blockIdx.y = tile, blockIdx.x = slice of a raw plane; a list is written by slice 0 alone, in order: the scan gives
@@ -264,17 +264,24 @@ __global__ __launch_bounds__(256) void mask_unpack_kernel(const uint8_t* __restr
 }
 
 // ---- apply: v at the pixels whose bit is set ------------------------------------------------------------------------
-// desc [n][2] = (tile, plane index or -1 for "all set").  The part of tile t the call writes is owned(t) cut to the
-// window, as stitch_rect of image_codec.hip has it: a number outside the grid owns nothing.
-__device__ __forceinline__ bool apply_rect(const Grid& g, const int* desc, int n_planes, const Clip& w, Owned* o,
-                                           int* plane) {
-  const int t = desc[2 * blockIdx.y];
-  *plane = desc[2 * blockIdx.y + 1];
-  if (t < 0 || t >= g.ny * g.nx || *plane >= n_planes) return false;
-  *o = owned(g, t);
-  o->y0 = max(o->y0, w.y0), o->y1 = min(o->y1, w.y1);
-  o->x0 = max(o->x0, w.x0), o->x1 = min(o->x1, w.x1);
-  return o->y0 < o->y1 && o->x0 < o->x1;
+// desc [n][2] = (tile, plane index or -1 for "all set").  What workgroup (blockIdx.x, blockIdx.y) of a window writer
+// works on: o, the part of tile desc[blockIdx.y][0] the call writes (owned_in_window of tile_grid.h); its rows
+// [ya, ya + rows) of that part; the tile's m plane, null for "all set"; and wW, the window's width in pixels.  False
+// where there is nothing to write: a tile outside the grid, a plane index >= n_planes, an empty part, no rows.
+struct WindowRows {
+  Owned o;
+  int ya, rows, wW;
+  const uint32_t* plane;
+};
+__device__ __forceinline__ bool window_rows(const uint32_t* planes, const int* desc, int n_planes, const Grid& g,
+                                            const Clip& w, WindowRows* r) {
+  const int pi = desc[2 * blockIdx.y + 1];
+  if (pi >= n_planes || !owned_in_window(g, desc[2 * blockIdx.y], w, &r->o)) return false;
+  r->ya = r->o.y0 + blockIdx.x * kTileRows;
+  r->rows = min(kTileRows, r->o.y1 - r->ya);
+  r->wW = w.x1 - w.x0;
+  r->plane = pi < 0 ? nullptr : planes + (size_t)pi * ((g.th * g.tw) >> 5);
+  return r->rows > 0;
 }
 
 __device__ __forceinline__ bool mask_bit(const uint32_t* plane, int idx) {
@@ -289,21 +296,16 @@ __global__ __launch_bounds__(256) void mask_apply_hwc_kernel(const uint32_t* __r
                                                              const int* __restrict__ desc, int n_planes, Grid g, int C,
                                                              Clip w, T* __restrict__ img, uint32_t v, int mis) {
   constexpr int E = 16 / (int)sizeof(T);
-  Owned o;
-  int pi;
-  if (!apply_rect(g, desc, n_planes, w, &o, &pi)) return;
-  const int ya = o.y0 + blockIdx.x * kMaskRows;
-  const int rows = min(kMaskRows, o.y1 - ya);
-  if (rows <= 0) return;
-  const uint32_t* plane = pi < 0 ? nullptr : planes + (size_t)pi * ((g.th * g.tw) >> 5);
-  const int wW = w.x1 - w.x0;
+  WindowRows R;
+  if (!window_rows(planes, desc, n_planes, g, w, &R)) return;
+  const Owned& o = R.o;
   const int seg = (o.x1 - o.x0) * C;
   const int cpr = seg / E + 2;  // 16-byte chunks a row segment can touch
   const uint32_t vv = v * (sizeof(T) == 1 ? 0x01010101u : 0x00010001u);
-  for (int i = threadIdx.x; i < rows * cpr; i += blockDim.x) {
+  for (int i = threadIdx.x; i < R.rows * cpr; i += blockDim.x) {
     const int r = i / cpr, k = i - r * cpr;
-    const int y = ya + r;
-    const int64_t b0 = ((int64_t)(y - w.y0) * wW + (o.x0 - w.x0)) * C + mis;
+    const int y = R.ya + r;
+    const int64_t b0 = ((int64_t)(y - w.y0) * R.wW + (o.x0 - w.x0)) * C + mis;
     Chunk ch;
     if (!row_chunk<T>(b0, seg, k, &ch)) continue;
     HwcCursor u = hwc_cursor(ch.lo() - b0, C);
@@ -313,7 +315,7 @@ __global__ __launch_bounds__(256) void mask_apply_hwc_kernel(const uint32_t* __r
 #pragma unroll
     for (int e = 0; e < E; ++e) {
       if (ch.has(e)) {
-        sel |= (uint32_t)mask_bit(plane, row_bit + (int)u.px) << e;
+        sel |= (uint32_t)mask_bit(R.plane, row_bit + (int)u.px) << e;
         u.step(C);
       }
     }
@@ -331,32 +333,29 @@ __global__ __launch_bounds__(256) void mask_apply_hwc_kernel(const uint32_t* __r
 __global__ __launch_bounds__(256) void mask_apply_f32_kernel(const uint32_t* __restrict__ planes,
                                                              const int* __restrict__ desc, int n_planes, Grid g,
                                                              Clip w, float* __restrict__ img, float fv) {
-  Owned o;
-  int pi;
-  if (!apply_rect(g, desc, n_planes, w, &o, &pi)) return;
-  const int ya = o.y0 + blockIdx.x * kMaskRows;
-  const int rows = min(kMaskRows, o.y1 - ya);
-  if (rows <= 0) return;
-  const uint32_t* plane = pi < 0 ? nullptr : planes + (size_t)pi * ((g.th * g.tw) >> 5);
-  const int wW = w.x1 - w.x0;
-  const int64_t cplane = (int64_t)blockIdx.z * (w.y1 - w.y0) * wW;
-  const int cpr = (o.x1 - o.x0) / 4 + 2;  // 4-float chunks a row segment can touch
-  for (int i = threadIdx.x; i < rows * cpr; i += blockDim.x) {
+  WindowRows R;
+  if (!window_rows(planes, desc, n_planes, g, w, &R)) return;
+  const Owned& o = R.o;
+  const int64_t cplane = (int64_t)blockIdx.z * (w.y1 - w.y0) * R.wW;
+  const int seg = o.x1 - o.x0;
+  const int cpr = seg / 4 + 2;  // 4-float chunks a row segment can touch; the window is 16-byte aligned, mis = 0
+  for (int i = threadIdx.x; i < R.rows * cpr; i += blockDim.x) {
     const int r = i / cpr, k = i - r * cpr;
-    const int y = ya + r;
-    const int64_t e0 = cplane + (int64_t)(y - w.y0) * wW + (o.x0 - w.x0), e1 = e0 + (o.x1 - o.x0);
-    const int64_t q0 = ((e0 >> 2) + k) << 2;
-    if (q0 >= e1) continue;
-    const int64_t lo = max(q0, e0), hi = min(q0 + 4, e1);
-    const int bit0 = (y - o.oy) * g.tw + (o.x0 - o.ox) + (int)(lo - e0);
+    const int y = R.ya + r;
+    const int64_t b0 = cplane + (int64_t)(y - w.y0) * R.wW + (o.x0 - w.x0);
+    Chunk ch;
+    if (!row_chunk<float>(b0, seg, k, &ch)) continue;
+    const int bit0 = (y - o.oy) * g.tw + (o.x0 - o.ox) + (int)(ch.lo() - b0);
     uint32_t sel = 0;
-    for (int64_t e = lo; e < hi; ++e) sel |= (uint32_t)mask_bit(plane, bit0 + (int)(e - lo)) << (int)(e - q0);
+#pragma unroll
+    for (int e = 0; e < 4; ++e)
+      if (ch.has(e)) sel |= (uint32_t)mask_bit(R.plane, bit0 + e - ch.first) << e;
     if (sel == 0xFu) {
-      *(float4*)(img + q0) = make_float4(fv, fv, fv, fv);
+      *(float4*)(img + ch.q0) = make_float4(fv, fv, fv, fv);
     } else {
 #pragma unroll
       for (int e = 0; e < 4; ++e)
-        if ((sel >> e) & 1u) img[q0 + e] = fv;
+        if ((sel >> e) & 1u) img[ch.q0 + e] = fv;
     }
   }
 }
@@ -366,76 +365,103 @@ __global__ __launch_bounds__(256) void mask_apply_f32_kernel(const uint32_t* __r
 __global__ __launch_bounds__(256) void mask_window_u8_kernel(const uint32_t* __restrict__ planes,
                                                              const int* __restrict__ desc, int n_planes, Grid g, Clip w,
                                                              uint8_t* __restrict__ out, int mis) {
-  Owned o;
-  int pi;
-  if (!apply_rect(g, desc, n_planes, w, &o, &pi)) return;
-  const int ya = o.y0 + blockIdx.x * kMaskRows;
-  const int rows = min(kMaskRows, o.y1 - ya);
-  if (rows <= 0) return;
-  const uint32_t* plane = pi < 0 ? nullptr : planes + (size_t)pi * ((g.th * g.tw) >> 5);
-  const int wW = w.x1 - w.x0;
+  WindowRows R;
+  if (!window_rows(planes, desc, n_planes, g, w, &R)) return;
+  const Owned& o = R.o;
   const int seg = o.x1 - o.x0;
   const int cpr = seg / 16 + 2;  // 16-byte chunks a row segment can touch
-  for (int i = threadIdx.x; i < rows * cpr; i += blockDim.x) {
+  for (int i = threadIdx.x; i < R.rows * cpr; i += blockDim.x) {
     const int r = i / cpr, k = i - r * cpr;
-    const int y = ya + r;
-    const int64_t b0 = (int64_t)(y - w.y0) * wW + (o.x0 - w.x0) + mis;
+    const int y = R.ya + r;
+    const int64_t b0 = (int64_t)(y - w.y0) * R.wW + (o.x0 - w.x0) + mis;
     Chunk ch;
     if (!row_chunk<uint8_t>(b0, seg, k, &ch)) continue;
     const int bit0 = (y - o.oy) * g.tw + (o.x0 - o.ox) + (int)(ch.lo() - b0);
     uint8_t b[16];
 #pragma unroll
     for (int e = 0; e < 16; ++e)
-      b[e] = ch.has(e) ? (uint8_t)!mask_bit(plane, bit0 + e - ch.first) : (uint8_t)0;
+      b[e] = ch.has(e) ? (uint8_t)!mask_bit(R.plane, bit0 + e - ch.first) : (uint8_t)0;
     store_chunk<uint8_t>(out, mis, ch.q0, ch.lo(), ch.hi(), b);
   }
 }
 
 }  // namespace dsic
 
-using namespace dsic;
+// ---- exports --------------------------------------------------------------------------------------------------------
+// The grid, tile-range and window checks are tile_grid.h's (DSIC_GRID, DSIC_TILE_ARGS, DSIC_WINDOW_ARGS).  What is the
+// mask calls' alone stands here once: a tile's bit positions are ints, so a tile has at most 2^30 pixels, and a window
+// writer takes n_planes >= 0 planes, at a non-null pointer unless there are none.
+namespace dsic {
 
-#define DSIC_MASK_IMAGE(what)                                                                          \
-  DSIC_REQUIRE(C == 3 || C == 4, what ": C=%d must be 3 or 4", C);                                     \
-  DSIC_REQUIRE(nodata >= 0 && nodata <= 255, what ": nodata=%d must be in 0..255", nodata);            \
-  const char* ge = grid_error(H, W, th, tw);                                                           \
-  DSIC_REQUIRE(!ge, what ": %s (H=%d W=%d th=%d tw=%d)", ge ? ge : "", H, W, th, tw);                  \
-  DSIC_REQUIRE((int64_t)th * tw <= INT_MAX / 2, what ": a tile of %dx%d has over 2^30 pixels", th, tw); \
-  const Grid g = make_grid(H, W, th, tw)
+static int tile_pixels_ok(const char* what, int th, int tw) {
+  DSIC_REQUIRE((int64_t)th * tw <= INT_MAX / 2, "%s: a tile of %dx%d has over 2^30 pixels", what, th, tw);
+  return DSIC_OK;
+}
+
+static int window_planes_ok(const char* what, int th, int tw, const uint32_t* planes, int n_planes) {
+  DSIC_REQUIRE(n_planes >= 0 && (planes || n_planes == 0), "%s: %d planes at a null pointer", what, n_planes);
+  return tile_pixels_ok(what, th, tw);
+}
+
+// classify and delta planes of a C-channel image (C = 3, 4: a uint8 HWC image and its nodata value v; C = 1: a validity
+// image, v = 0): every check the nodata and the validity exports share, and the one dispatch on C
+static int classify(const char* what, const uint8_t* img, int H, int W, int C, int th, int tw, uint32_t v,
+                    int first_tile, int n_tiles, int* counts, void* stream) {
+  DSIC_REQUIRE(img && counts, "%s: null pointer", what);
+  DSIC_TILE_ARGS(what);
+  if (const int rc = tile_pixels_ok(what, th, tw)) return rc;
+  DSIC_REQUIRE(((uintptr_t)counts & 3) == 0, "%s: counts must be 4-byte aligned", what);
+  const auto kernel = C == 1 ? mask_classify_kernel<1> : (C == 3 ? mask_classify_kernel<3> : mask_classify_kernel<4>);
+  hipLaunchKernelGGL(kernel, grid, dim3(256), 0, (hipStream_t)stream, img, g, v, first_tile, counts);
+  return check_launch(what);
+}
+
+static int delta_planes(const char* what, const uint8_t* img, int H, int W, int C, int th, int tw, uint32_t v,
+                        const int* tile_ids, int n_tiles, uint32_t* planes, int* popcounts, void* stream) {
+  DSIC_REQUIRE(img && tile_ids && planes && popcounts, "%s: null pointer", what);
+  DSIC_GRID(what);
+  if (const int rc = tile_pixels_ok(what, th, tw)) return rc;
+  DSIC_REQUIRE(n_tiles >= 1 && n_tiles <= 65535, "%s: n=%d tiles per call (1..65535)", what, n_tiles);
+  DSIC_REQUIRE((((uintptr_t)planes | (uintptr_t)popcounts | (uintptr_t)tile_ids) & 3) == 0,
+               "%s: planes, popcounts and tile ids must be 4-byte aligned", what);
+  const auto kernel = C == 1 ? mask_delta_kernel<1> : (C == 3 ? mask_delta_kernel<3> : mask_delta_kernel<4>);
+  hipLaunchKernelGGL(kernel, dim3(ceil_div((g.th * g.tw) >> 5, 256), n_tiles), dim3(256), 0, (hipStream_t)stream, img,
+                     g, v, tile_ids, planes, popcounts);
+  return check_launch(what);
+}
+
+}  // namespace dsic
+
+using namespace dsic;
 
 extern "C" int dsic_mask_classify_u8(const uint8_t* img_hwc, int H, int W, int C, int th, int tw, int nodata,
                                      int first_tile, int n_tiles, int* counts, void* stream) {
-  DSIC_REQUIRE(img_hwc && counts, "mask_classify_u8: null pointer");
-  DSIC_MASK_IMAGE("mask_classify_u8");
-  DSIC_REQUIRE(first_tile >= 0 && n_tiles > 0 && (int64_t)first_tile + n_tiles <= (int64_t)g.ny * g.nx,
-               "mask_classify_u8: tiles [%d, %d) outside the grid of %d", first_tile, first_tile + n_tiles,
-               g.ny * g.nx);
-  DSIC_REQUIRE(n_tiles <= 65535, "mask_classify_u8: at most 65535 tiles per call");
-  const dim3 grid(g.th / kMaskRows, n_tiles);
-  if (C == 3)
-    hipLaunchKernelGGL(mask_classify_kernel<3>, grid, dim3(256), 0, (hipStream_t)stream, img_hwc, g, (uint32_t)nodata,
-                       first_tile, counts);
-  else
-    hipLaunchKernelGGL(mask_classify_kernel<4>, grid, dim3(256), 0, (hipStream_t)stream, img_hwc, g, (uint32_t)nodata,
-                       first_tile, counts);
-  return check_launch("mask_classify_u8");
+  DSIC_REQUIRE(C == 3 || C == 4, "mask_classify_u8: C=%d must be 3 or 4", C);
+  DSIC_REQUIRE(nodata >= 0 && nodata <= 255, "mask_classify_u8: nodata=%d must be in 0..255", nodata);
+  return classify("mask_classify_u8", img_hwc, H, W, C, th, tw, (uint32_t)nodata, first_tile, n_tiles, counts, stream);
 }
 
 extern "C" int dsic_mask_delta_planes_u8(const uint8_t* img_hwc, int H, int W, int C, int th, int tw, int nodata,
                                          const int* tile_ids, int n_tiles, uint32_t* planes, int* popcounts,
                                          void* stream) {
-  DSIC_REQUIRE(img_hwc && tile_ids && planes && popcounts, "mask_delta_planes_u8: null pointer");
-  DSIC_MASK_IMAGE("mask_delta_planes_u8");
-  DSIC_REQUIRE(n_tiles >= 1 && n_tiles <= 65535, "mask_delta_planes_u8: n=%d tiles per call (1..65535)", n_tiles);
-  DSIC_REQUIRE(((uintptr_t)planes & 3) == 0, "mask_delta_planes_u8: planes must be 4-byte aligned");
-  const dim3 grid(ceil_div((g.th * g.tw) >> 5, 256), n_tiles);
-  if (C == 3)
-    hipLaunchKernelGGL(mask_delta_kernel<3>, grid, dim3(256), 0, (hipStream_t)stream, img_hwc, g, (uint32_t)nodata,
-                       tile_ids, planes, popcounts);
-  else
-    hipLaunchKernelGGL(mask_delta_kernel<4>, grid, dim3(256), 0, (hipStream_t)stream, img_hwc, g, (uint32_t)nodata,
-                       tile_ids, planes, popcounts);
-  return check_launch("mask_delta_planes_u8");
+  DSIC_REQUIRE(C == 3 || C == 4, "mask_delta_planes_u8: C=%d must be 3 or 4", C);
+  DSIC_REQUIRE(nodata >= 0 && nodata <= 255, "mask_delta_planes_u8: nodata=%d must be in 0..255", nodata);
+  return delta_planes("mask_delta_planes_u8", img_hwc, H, W, C, th, tw, (uint32_t)nodata, tile_ids, n_tiles, planes,
+                      popcounts, stream);
+}
+
+// Validity masks (codec.compress_image with valid = mask, stream version 8).  The mask travels as a uint8 [H][W] image,
+// 0 = invalid: a one-channel image whose "nodata value" is 0, so classify and the d planes are the C = 1 instantiation
+// of the kernels above, with their grid, ownership and plane layout.
+extern "C" int dsic_valid_classify(const uint8_t* valid_hw, int H, int W, int th, int tw, int first_tile, int n_tiles,
+                                   int* counts, void* stream) {
+  return classify("valid_classify", valid_hw, H, W, 1, th, tw, 0u, first_tile, n_tiles, counts, stream);
+}
+
+extern "C" int dsic_valid_delta_planes(const uint8_t* valid_hw, int H, int W, int th, int tw, const int* tile_ids,
+                                       int n_tiles, uint32_t* planes, int* popcounts, void* stream) {
+  return delta_planes("valid_delta_planes", valid_hw, H, W, 1, th, tw, 0u, tile_ids, n_tiles, planes, popcounts,
+                      stream);
 }
 
 #define DSIC_MASK_TILE(what)                                                                                     \
@@ -472,28 +498,16 @@ extern "C" int dsic_mask_unpack(const uint8_t* blob, int64_t blob_bytes, const i
   return check_launch("mask_unpack");
 }
 
-// The argument checks that the calls which write a window share (names as in the exports; `what` is a string),
-// leaving the grid `g`, the window `clip` and the launch grid `grid`.  The range of the fill value stands before it
-// at the call, the alignments of out, planes and desc behind it.
-#define DSIC_MASK_WINDOW(what)                                                                                     \
-  const char* ge = grid_error(H, W, th, tw);                                                                       \
-  DSIC_REQUIRE(!ge, "%s: %s (H=%d W=%d th=%d tw=%d)", what, ge ? ge : "", H, W, th, tw);                           \
-  DSIC_REQUIRE((int64_t)th * tw <= INT_MAX / 2, "%s: a tile of %dx%d has over 2^30 pixels", what, th, tw);         \
-  const Grid g = make_grid(H, W, th, tw);                                                                          \
-  DSIC_REQUIRE(wy0 >= 0 && wx0 >= 0 && wh >= 1 && ww >= 1 && (int64_t)wy0 + wh <= H && (int64_t)wx0 + ww <= W,     \
-               "%s: window %dx%d at (%d, %d) outside the %dx%d image", what, wh, ww, wy0, wx0, H, W);              \
-  DSIC_REQUIRE(n_tiles >= 1 && n_tiles <= 65535, "%s: n=%d tiles per call (1..65535)", what, n_tiles);             \
-  DSIC_REQUIRE(n_planes >= 0 && (planes || n_planes == 0), "%s: %d planes at a null pointer", what, n_planes);     \
-  const Clip clip = {wy0, wy0 + wh, wx0, wx0 + ww};                                                                \
-  const dim3 grid(g.th / kMaskRows, n_tiles, 1)
-
+// The window writers: the range of the fill value and of C, the window (leaving g, clip and grid), the planes, then the
+// alignments each writer needs.
 extern "C" int dsic_mask_apply_u8(const uint32_t* planes, int n_planes, const int* desc, int n_tiles, int nodata,
                                   uint8_t* out, int H, int W, int C, int th, int tw, int wy0, int wx0, int wh, int ww,
                                   void* stream) {
   DSIC_REQUIRE(desc && out, "mask_apply_u8: null pointer");
   DSIC_REQUIRE(C == 3 || C == 4, "mask_apply_u8: C=%d must be 3 or 4", C);
   DSIC_REQUIRE(nodata >= 0 && nodata <= 255, "mask_apply_u8: nodata=%d must be in 0..255", nodata);
-  DSIC_MASK_WINDOW("mask_apply_u8");
+  DSIC_WINDOW_ARGS("mask_apply_u8");
+  if (const int rc = window_planes_ok("mask_apply_u8", th, tw, planes, n_planes)) return rc;
   DSIC_REQUIRE(((uintptr_t)out & 15) == 0, "mask_apply_u8: out must be 16-byte aligned");
   hipLaunchKernelGGL(mask_apply_hwc_kernel<uint8_t>, grid, dim3(256), 0, (hipStream_t)stream, planes, desc, n_planes,
                      g, C, clip, out, (uint32_t)nodata, 0);
@@ -506,46 +520,13 @@ extern "C" int dsic_mask_apply_f32(const uint32_t* planes, int n_planes, const i
   DSIC_REQUIRE(desc && out, "mask_apply_f32: null pointer");
   DSIC_REQUIRE(C >= 1 && C <= 8, "mask_apply_f32: C=%d must be in 1..8", C);
   DSIC_REQUIRE(nodata >= 0 && nodata <= 255, "mask_apply_f32: nodata=%d must be in 0..255", nodata);
-  DSIC_MASK_WINDOW("mask_apply_f32");
+  DSIC_WINDOW_ARGS("mask_apply_f32");
+  if (const int rc = window_planes_ok("mask_apply_f32", th, tw, planes, n_planes)) return rc;
   DSIC_REQUIRE(((uintptr_t)out & 15) == 0, "mask_apply_f32: out must be 16-byte aligned");
   const float fv = (float)nodata / 255.0f;  // on the host, correctly rounded: NumPy's float32(v) / float32(255)
   hipLaunchKernelGGL(mask_apply_f32_kernel, dim3(grid.x, grid.y, C), dim3(256), 0, (hipStream_t)stream, planes, desc,
                      n_planes, g, clip, out, fv);
   return check_launch("mask_apply_f32");
-}
-
-// ---- validity masks (codec.compress_image with valid = mask, stream version 8) --------------------------------------
-// The mask travels as a uint8 [H][W] image, 0 = invalid: a one-channel image whose "nodata value" is 0, so classify and
-// the d planes are the C = 1 instantiation of the kernels above, with their grid, ownership and plane layout.
-#define DSIC_VALID_IMAGE(what)                                                                          \
-  const char* ge = grid_error(H, W, th, tw);                                                           \
-  DSIC_REQUIRE(!ge, what ": %s (H=%d W=%d th=%d tw=%d)", ge ? ge : "", H, W, th, tw);                  \
-  DSIC_REQUIRE((int64_t)th * tw <= INT_MAX / 2, what ": a tile of %dx%d has over 2^30 pixels", th, tw); \
-  const Grid g = make_grid(H, W, th, tw)
-
-extern "C" int dsic_valid_classify(const uint8_t* valid_hw, int H, int W, int th, int tw, int first_tile, int n_tiles,
-                                   int* counts, void* stream) {
-  DSIC_REQUIRE(valid_hw && counts, "valid_classify: null pointer");
-  DSIC_VALID_IMAGE("valid_classify");
-  DSIC_REQUIRE(first_tile >= 0 && n_tiles > 0 && (int64_t)first_tile + n_tiles <= (int64_t)g.ny * g.nx,
-               "valid_classify: tiles [%d, %d) outside the grid of %d", first_tile, first_tile + n_tiles, g.ny * g.nx);
-  DSIC_REQUIRE(n_tiles <= 65535, "valid_classify: at most 65535 tiles per call");
-  DSIC_REQUIRE(((uintptr_t)counts & 3) == 0, "valid_classify: counts must be 4-byte aligned");
-  hipLaunchKernelGGL(mask_classify_kernel<1>, dim3(g.th / kMaskRows, n_tiles), dim3(256), 0, (hipStream_t)stream,
-                     valid_hw, g, 0u, first_tile, counts);
-  return check_launch("valid_classify");
-}
-
-extern "C" int dsic_valid_delta_planes(const uint8_t* valid_hw, int H, int W, int th, int tw, const int* tile_ids,
-                                       int n_tiles, uint32_t* planes, int* popcounts, void* stream) {
-  DSIC_REQUIRE(valid_hw && tile_ids && planes && popcounts, "valid_delta_planes: null pointer");
-  DSIC_VALID_IMAGE("valid_delta_planes");
-  DSIC_REQUIRE(n_tiles >= 1 && n_tiles <= 65535, "valid_delta_planes: n=%d tiles per call (1..65535)", n_tiles);
-  DSIC_REQUIRE((((uintptr_t)planes | (uintptr_t)popcounts | (uintptr_t)tile_ids) & 3) == 0,
-               "valid_delta_planes: planes, popcounts and tile ids must be 4-byte aligned");
-  hipLaunchKernelGGL(mask_delta_kernel<1>, dim3(ceil_div((g.th * g.tw) >> 5, 256), n_tiles), dim3(256), 0,
-                     (hipStream_t)stream, valid_hw, g, 0u, tile_ids, planes, popcounts);
-  return check_launch("valid_delta_planes");
 }
 
 extern "C" int dsic_mask_apply_u16(const uint32_t* planes, int n_planes, const int* desc, int n_tiles, int fill,
@@ -555,7 +536,8 @@ extern "C" int dsic_mask_apply_u16(const uint32_t* planes, int n_planes, const i
   DSIC_REQUIRE(C >= 1 && C <= 4, "mask_apply_u16: C=%d must be in 1..4", C);
   DSIC_REQUIRE(fill >= 0 && fill <= 65535, "mask_apply_u16: fill=%d must be in 0..65535", fill);
   DSIC_REQUIRE(((uintptr_t)out & 1) == 0, "mask_apply_u16: the uint16 window must be 2-byte aligned");
-  DSIC_MASK_WINDOW("mask_apply_u16");
+  DSIC_WINDOW_ARGS("mask_apply_u16");
+  if (const int rc = window_planes_ok("mask_apply_u16", th, tw, planes, n_planes)) return rc;
   DSIC_REQUIRE((((uintptr_t)planes | (uintptr_t)desc) & 3) == 0,
                "mask_apply_u16: planes and desc must be 4-byte aligned");
   DSIC_REQUIRE((int64_t)ww * C * 2 <= INT_MAX, "mask_apply_u16: a row of ww=%d pixels of C=%d uint16 is over 2^31 - 1 bytes",
@@ -568,7 +550,8 @@ extern "C" int dsic_mask_apply_u16(const uint32_t* planes, int n_planes, const i
 extern "C" int dsic_mask_window_u8(const uint32_t* planes, int n_planes, const int* desc, int n_tiles, uint8_t* out_hw,
                                    int H, int W, int th, int tw, int wy0, int wx0, int wh, int ww, void* stream) {
   DSIC_REQUIRE(desc && out_hw, "mask_window_u8: null pointer");
-  DSIC_MASK_WINDOW("mask_window_u8");
+  DSIC_WINDOW_ARGS("mask_window_u8");
+  if (const int rc = window_planes_ok("mask_window_u8", th, tw, planes, n_planes)) return rc;
   DSIC_REQUIRE((((uintptr_t)planes | (uintptr_t)desc) & 3) == 0,
                "mask_window_u8: planes and desc must be 4-byte aligned");
   hipLaunchKernelGGL(mask_window_u8_kernel, grid, dim3(256), 0, (hipStream_t)stream, planes, desc, n_planes, g, clip,

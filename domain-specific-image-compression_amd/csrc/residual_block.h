@@ -106,20 +106,17 @@ __global__ __launch_bounds__(256) void residual_pack_head_kernel(const int* __re
     const int e = i >> 2, t = e / kResBands, j = e - t * kResBands;
     put_u32(out + kResHead + (int64_t)S::rec * n + i, i & 3, (uint32_t)clamp_len(lengths[Sl * t + 1 + j], cap_seg));
   }
-  long long carry = 0;
-  for (int s0 = 0; s0 < P * n; s0 += blockDim.x) {
-    const int s = s0 + tid, t = s / P;
-    const long long v = s < P * n ? piece_len<S>(s - t * P, C, table_width<S>(meta, t, Lmax), tile_planes<S>(kk, t), pb,
-                                                 lengths + Sl * t, cap_seg)
-                                  : 0;
-    long long tot;
-    const long long ex = block_exclusive_scan(v, lds4, &tot);
-    if (s < P * n) ws[2 + s] = carry + ex;
-    carry += tot;
-  }
+  const long long total = scan_offsets(
+      P * n,
+      [&](int s) {
+        const int t = s / P;
+        return piece_len<S>(s - t * P, C, table_width<S>(meta, t, Lmax), tile_planes<S>(kk, t), pb, lengths + Sl * t,
+                            cap_seg);
+      },
+      lds4, ws + 2);
   if (tid == 0) {
-    ws[2 + P * n] = carry;
-    ws[0] = body_offset<S>(n) + carry;
+    ws[2 + P * n] = total;
+    ws[0] = body_offset<S>(n) + total;
     ws[1] = err ? *err : 0;
   }
 }

@@ -21,19 +21,20 @@ Set bits outside a tile's owned rectangle are harmless: the apply kernel writes 
 
 A validity mask (codec.compress_image with valid = mask, stream version 8) uses the same states, planes, payloads and
 block with "invalid" in the place of "nodata": the mask arrives as a uint8 [H,W] image, 0 = invalid (classify_valid,
-delta_planes_valid: the kernels above on a one-channel image whose nodata value is 0), the block's nodata field
-carries the fill, apply_window also fills uint16 windows, and window_valid writes a window's validity.
+delta_planes_valid: the kernels above on a one-channel image whose nodata value is 0; each shares its body with its
+nodata twin, _classify and _delta_planes), the block's nodata field carries the fill, apply_window also fills uint16
+windows, and window_valid writes a window's validity.  check_nodata and check_fill are ops._int_option, the one
+integer-option check of the codec.
 """
 from __future__ import annotations
 
-import operator
 import struct
 
 import numpy as np
 import torch
 
 from . import lib as _lib
-from .ops import _p, _stream
+from .ops import _int_option, _p, _stream
 
 MAGIC = b"DSICM\x00"
 EMPTY, FULL, MIXED = 0, 1, 2
@@ -44,13 +45,7 @@ _REC = struct.Struct("<3I")        # per mixed tile: tile, mode, bytes
 
 def check_nodata(nodata, what) -> int:
     """nodata as an int in 0 .. 255, else ValueError."""
-    try:
-        v = -1 if isinstance(nodata, (bool, np.bool_)) else operator.index(nodata)
-    except TypeError:
-        v = -1
-    if not 0 <= v <= 255:
-        raise ValueError(f"{what}: nodata={nodata!r} must be an integer from 0 to 255")
-    return v
+    return _int_option(nodata, "nodata", 255, what)
 
 
 def raw_bytes(th, tw) -> int:
@@ -138,26 +133,36 @@ def check_payload(buf, mode, th, tw, what="DSICI stream"):
 
 
 # ---- the device side ------------------------------------------------------------------------------------------------
-def classify(img, g, C, nodata) -> np.ndarray:
-    """uint8 [H,W,C] on the device -> int64 [n]: per grid tile the nodata pixels among its owned pixels inside H x W.
-    One pass over the image (dsic_mask_classify_u8) and one small copy."""
-    L = _lib.load()
+# The nodata calls (dsic_mask_*_u8) and the validity calls (dsic_valid_*) are one body each: `what` names the export,
+# channels and value are (C,) and (nodata,) where the export takes them, () where it does not.
+def _classify(what, img, g, channels, value) -> np.ndarray:
+    fn = getattr(_lib.load(), "dsic_" + what)
     counts = torch.zeros(g["n"], dtype=torch.int32, device=img.device)
     for first in range(0, g["n"], 65535):
         n = min(65535, g["n"] - first)
-        _lib.check(L.dsic_mask_classify_u8(_p(img), g["H"], g["W"], C, g["th"], g["tw"], nodata, first, n,
-                                           _p(counts[first:]), _stream()), "mask_classify_u8")
+        _lib.check(fn(_p(img), g["H"], g["W"], *channels, g["th"], g["tw"], *value, first, n, _p(counts[first:]),
+                      _stream()), what)
     return counts.cpu().numpy().astype(np.int64)
+
+
+def _delta_planes(what, img, g, channels, value, ids):
+    n = ids.numel()
+    planes = torch.empty((n, g["th"] * g["tw"] // 32), dtype=torch.int32, device=img.device)
+    pop = torch.zeros(n, dtype=torch.int32, device=img.device)
+    _lib.check(getattr(_lib.load(), "dsic_" + what)(_p(img), g["H"], g["W"], *channels, g["th"], g["tw"], *value,
+                                                    _p(ids), n, _p(planes), _p(pop), _stream()), what)
+    return planes, pop
+
+
+def classify(img, g, C, nodata) -> np.ndarray:
+    """uint8 [H,W,C] on the device -> int64 [n]: per grid tile the nodata pixels among its owned pixels inside H x W.
+    One pass over the image (dsic_mask_classify_u8) and one small copy."""
+    return _classify("mask_classify_u8", img, g, (C,), (nodata,))
 
 
 def delta_planes(img, g, C, nodata, ids):
     """ids int32 [n] on the device -> (d planes int32 [n, th*tw/32], popcounts int32 [n])."""
-    n = ids.numel()
-    planes = torch.empty((n, g["th"] * g["tw"] // 32), dtype=torch.int32, device=img.device)
-    pop = torch.zeros(n, dtype=torch.int32, device=img.device)
-    _lib.check(_lib.load().dsic_mask_delta_planes_u8(_p(img), g["H"], g["W"], C, g["th"], g["tw"], nodata, _p(ids), n,
-                                                     _p(planes), _p(pop), _stream()), "mask_delta_planes_u8")
-    return planes, pop
+    return _delta_planes("mask_delta_planes_u8", img, g, (C,), (nodata,), ids)
 
 
 def pack_on_device(planes, pop, ids, th, tw):
@@ -172,35 +177,18 @@ def pack_on_device(planes, pop, ids, th, tw):
 
 def check_fill(fill, top, what) -> int:
     """fill as an int in 0 .. top (255 for uint8 images, 65535 for uint16), else ValueError."""
-    try:
-        v = -1 if isinstance(fill, (bool, np.bool_)) else operator.index(fill)
-    except TypeError:
-        v = -1
-    if not 0 <= v <= top:
-        raise ValueError(f"{what}: fill={fill!r} must be an integer from 0 to {top}")
-    return v
+    return _int_option(fill, "fill", top, what)
 
 
 def classify_valid(valid, g) -> np.ndarray:
     """uint8 [H,W] on the device, 0 = invalid -> int64 [n]: per grid tile the invalid pixels among its owned pixels
     inside H x W (dsic_valid_classify: classify of a one-channel image whose nodata value is 0)."""
-    L = _lib.load()
-    counts = torch.zeros(g["n"], dtype=torch.int32, device=valid.device)
-    for first in range(0, g["n"], 65535):
-        n = min(65535, g["n"] - first)
-        _lib.check(L.dsic_valid_classify(_p(valid), g["H"], g["W"], g["th"], g["tw"], first, n, _p(counts[first:]),
-                                         _stream()), "valid_classify")
-    return counts.cpu().numpy().astype(np.int64)
+    return _classify("valid_classify", valid, g, (), ())
 
 
 def delta_planes_valid(valid, g, ids):
     """delta_planes of a validity image (dsic_valid_delta_planes)."""
-    n = ids.numel()
-    planes = torch.empty((n, g["th"] * g["tw"] // 32), dtype=torch.int32, device=valid.device)
-    pop = torch.zeros(n, dtype=torch.int32, device=valid.device)
-    _lib.check(_lib.load().dsic_valid_delta_planes(_p(valid), g["H"], g["W"], g["th"], g["tw"], _p(ids), n, _p(planes),
-                                                   _p(pop), _stream()), "valid_delta_planes")
-    return planes, pop
+    return _delta_planes("valid_delta_planes", valid, g, (), (), ids)
 
 
 @torch.no_grad()

@@ -6,8 +6,10 @@ function forwards raw pointers to libdsic_hip.so.
 from __future__ import annotations
 
 import ctypes
+import operator
 import os
 
+import numpy as np
 import torch
 
 from . import lib as _lib
@@ -22,6 +24,18 @@ def _stream():
     # one process drives one GPU (torch.distributed, one rank per device): the current stream of the
     # current device.  Tensors on another device are rejected by _f32c's callers' pointer checks.
     return ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+
+
+def _int_option(value, name, top, what, note="") -> int:
+    """An integer option of the image codec (nodata, fill, max_error, tolerance): value as an int in 0 .. top, else
+    ValueError.  A bool, NumPy's included, is no integer here."""
+    try:
+        v = -1 if isinstance(value, (bool, np.bool_)) else operator.index(value)
+    except TypeError:
+        v = -1
+    if not 0 <= v <= top:
+        raise ValueError(f"{what}: {name}={value!r} must be an integer from 0{note} to {top}")
+    return v
 
 
 def _f32c(t: torch.Tensor, name: str) -> torch.Tensor:

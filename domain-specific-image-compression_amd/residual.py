@@ -23,14 +23,13 @@ The residual block of a batch (little endian):
 from __future__ import annotations
 
 import collections
-import operator
 import struct
 
 import numpy as np
 import torch
 
 from . import lib as _lib
-from .ops import _p, _stream
+from .ops import _int_option, _p, _stream
 
 MAGIC = b"DSICR\x00"
 BANDS = 16
@@ -42,13 +41,7 @@ _REC = struct.Struct("<iII")       # per tile: smin, L, span_bytes
 
 def check_max_error(max_error, what) -> int:
     """max_error as an int in 0 .. 127, else ValueError."""
-    try:
-        tau = operator.index(max_error)
-    except TypeError:
-        tau = -1
-    if isinstance(max_error, bool) or not 0 <= tau <= 127:
-        raise ValueError(f"{what}: max_error={max_error!r} must be an integer from 0 (lossless) to 127")
-    return tau
+    return _int_option(max_error, "max_error", 127, what, " (lossless)")
 
 
 def q_max(tau) -> int:

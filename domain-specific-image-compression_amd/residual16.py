@@ -26,7 +26,6 @@ The wide residual block of a batch (little endian):
 """
 from __future__ import annotations
 
-import operator
 import struct
 
 import numpy as np
@@ -34,7 +33,7 @@ import torch
 
 from . import lib as _lib
 from . import residual as _residual
-from .ops import _p, _stream
+from .ops import _int_option, _p, _stream
 
 MAGIC = b"DSICW\x00"
 BANDS = _residual.BANDS
@@ -50,13 +49,7 @@ FORMAT = _residual.BlockFormat(MAGIC, _REC, "wide residual", lambda tau: TOP, PL
 
 def check_tolerance(tolerance, what) -> int:
     """tolerance as an int in 0 .. 32767, else ValueError."""
-    try:
-        tau = operator.index(tolerance)
-    except TypeError:
-        tau = -1
-    if isinstance(tolerance, bool) or not 0 <= tau <= MAX_TOLERANCE:
-        raise ValueError(f"{what}: tolerance={tolerance!r} must be an integer from 0 (lossless) to {MAX_TOLERANCE}")
-    return tau
+    return _int_option(tolerance, "tolerance", MAX_TOLERANCE, what, " (lossless)")
 
 
 def q16_max(tau) -> int:

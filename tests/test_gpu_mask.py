@@ -181,6 +181,55 @@ def test_mask_kernels_equal_the_restatement(H, W, tile, C):
                       f"{what} apply_f32 {win}")
 
 
+def test_mask_pack_of_more_than_256_tiles_in_one_call():
+    """290 records in one dsic_mask_pack, so the offsets scan of its head kernel runs a second pass of 256 with the
+    carry of the first (mask.MAX_TILES lets the codec send 1024).  A 544 x 544 x 3 image in tiles of 32 (17 x 17 = 289,
+    and the number 289 outside the grid): a wedge above row 480 makes list-mode tiles of differing lengths, speckle
+    below it makes tiles 255 .. 288 raw, on both sides of record 256.  Steps 2 to 4 of the kernel test above."""
+    L = lib.load()
+    H = W = 544
+    C, th, tw, v, off = 3, 32, 32, 7, 1
+    grid = R.tiles(H, W, th, tw)
+    n, D, raw = len(grid), th * tw // 32, th * tw // 8
+    rng = np.random.default_rng(544)
+    yy, xx = np.mgrid[:H, :W]
+    mask = np.where(yy < 480, 2 * yy + xx < 816, rng.random((H, W)) < 0.5)
+    img = _image(mask, C, v, rng)
+    ids = list(range(n)) + [n]
+    ms = [R.m_plane(mask, g, th, tw) for g in grid]
+    ds = [R.delta(m) for m in ms] + [np.zeros((th, tw), bool)]
+    pays = [R.payload(d) for d in ds]
+    modes = [mode for mode, _ in pays]
+    assert n == 289 and len(ids) > 256 and set(modes) == {0, 1}
+    assert all(modes[t] == 0 for t in range(255, 289)), "raw tiles on both sides of record 256"
+    assert len({len(body) for mode, body in pays[:255]}) > 2, "list payloads of differing lengths before them"
+    d_img, d_ids = _inside(img, off), _i32(ids)
+    planes, pop = Out(4 * D * (n + 1)), Out(4 * (n + 1), fill=0)
+    lib.check(L.dsic_mask_delta_planes_u8(_p(d_img), H, W, C, th, tw, v, _p(d_ids), n + 1, _p(planes.view),
+                                          _p(pop.view), _stream()), "delta planes")
+    _same(planes.host("planes"), np.concatenate([R.plane_dwords(d) for d in ds]), "planes")
+    _same(pop.host("popcounts"), np.array([int(d.sum()) for d in ds], dtype="<i4"), "popcounts")
+    want = b"".join(struct.pack("<3I", t, mode, len(body)) for t, (mode, body) in zip(ids, pays))
+    want += b"".join(body for _, body in pays)
+    out, ws = Out((n + 1) * (12 + raw)), Out(8 * (n + 3))
+    lib.check(L.dsic_mask_pack(_p(planes.view), _p(pop.view), _p(d_ids), n + 1, th, tw, _p(ws.view), _p(out.view),
+                               _stream()), "pack")
+    got = out.host("pack")
+    assert ws.host("ws")[:16].view("<i8").tolist() == [len(want), 0]
+    _same(got[:len(want)], np.frombuffer(want, np.uint8), "pack")
+    assert (got[len(want):] == U8_FILL).all(), "pack wrote past its bytes"
+    blob = b"".join(body for _, body in pays)
+    desc, at = [], 0
+    for mode, body in pays:
+        desc.append((mode, at, len(body)))
+        at += len(body)
+    d_desc, d_blob = _i32(desc), _inside(np.frombuffer(blob + b"\0" * 16, np.uint8), off)
+    mplanes = Out(4 * D * (n + 1))
+    lib.check(L.dsic_mask_unpack(_p(d_blob), len(blob), _p(d_desc), n + 1, th, tw, _p(mplanes.view), _stream()),
+              "unpack")
+    _same(mplanes.host("unpack"), np.concatenate([R.plane_dwords(m) for m in ms + [ds[-1]]]), "unpack")
+
+
 def test_the_last_position_of_a_u16_tile():
     """one 256 x 256 tile whose only nodata pixel is the last: d has bit 65535 alone"""
     L = lib.load()

@@ -180,9 +180,9 @@ def _guards_intact(buf, fill):
     return bool(torch.isnan(ends).all()) if isinstance(fill, float) else bool((ends == fill).all())
 
 
-def _adversarial(C, seed):
-    """x uint8 [2][32][48][C] and x_hat float32 [2][C][32][48]: x_hat at and beside every k/255, below 0 and above 1,
-    r = +255 and -255 in both tiles."""
+def _adversarial(C, seed, NT=NT):
+    """x uint8 [NT][32][48][C] and x_hat float32 [NT][C][32][48]: x_hat at and beside every k/255, below 0 and above 1,
+    r = +255 and -255 in every tile."""
     rng = np.random.default_rng(seed)
     k = (np.arange(256, dtype=np.float32) / np.float32(255.0)).astype(np.float32)
     edge = np.concatenate([np.nextafter(k, np.float32(-1)), k, np.nextafter(k, np.float32(2)),
@@ -202,7 +202,7 @@ def _adversarial(C, seed):
     return x, x_hat
 
 
-def _flat(C, delta):
+def _flat(C, delta, NT=NT):
     """every pixel delta above its prediction: one symbol, L = 1"""
     x_hat = np.full((NT, C, TH, TW), 0.5, dtype=np.float32)
     x = np.full((NT, TH, TW, C), 127 + delta, dtype=np.uint8)
@@ -216,9 +216,19 @@ CASES = [("adv", 0), ("adv", 2), ("adv", 127), ("flat", 0)]
 @pytest.mark.parametrize("C", [3, 4])
 @pytest.mark.parametrize("kind,tau", CASES)
 def test_kernels_against_numpy_and_the_oracle(C, kind, tau):
+    _kernels_case(C, kind, tau, NT)
+
+
+def test_kernels_with_more_than_256_pieces_in_one_block():
+    """14 tiles at C = 3 are (3 + 16) * 14 = 266 pieces, so the offsets scan of dsic_residual_pack's head kernel runs a
+    second pass of 256 with the carry of the first; the two owned rectangles repeat."""
+    _kernels_case(3, "adv", 2, 14)
+
+
+def _kernels_case(C, kind, tau, NT):
     L = lib.load()
-    x, x_hat = _adversarial(C, 7 * C + tau) if kind == "adv" else _flat(C, 3)
-    own = OWN if kind == "adv" else [OWN[0], OWN[0]]
+    x, x_hat = _adversarial(C, 7 * C + tau, NT) if kind == "adv" else _flat(C, 3, NT)
+    own = (OWN if kind == "adv" else [OWN[0], OWN[0]]) * (NT // 2)
     Q, Lmax, npix = R.q_max(tau), R.lmax(tau), TH * TW
     want_q = np.stack([R.tile_q(x[t], x_hat[t], own[t], tau) for t in range(NT)])
     want_hist = np.stack([R.histogram(want_q[t], tau) for t in range(NT)])

@@ -336,17 +336,20 @@ def test_quantize_against_numpy(C, tau):
     assert (q1.cpu().numpy()[0] == want[1]).all()
 
 
-def _edge_q(C, m, sign, seed):
-    """q int64 [2][C][32][48]: tile 0 random in [-m, m] with sign * m reached once and -sign * m never, tile 1 quiet
-    inside its owned rectangle and 0 outside."""
+def _edge_q(C, m, sign, seed, NT=NT):
+    """q int64 [NT][C][32][48]: an even tile random in [-m, m] with sign * m reached once and -sign * m never, an odd
+    tile quiet inside tile 1's owned rectangle and 0 outside."""
     rng = np.random.default_rng(seed)
     q = np.zeros((NT, C, TH, TW), dtype=np.int64)
-    q[0] = rng.integers(-m, m + 1, size=(C, TH, TW))
-    q[0][np.abs(q[0]) == m] = 0
-    q[0, C - 1, 31, 47] = sign * m
-    q[0, 0, :4, :8] = 0                                                # a whole wave's worth of zeros among the rest
     y0, y1, x0, x1 = OWN[1]
-    q[1][:, y0:y1, x0:x1] = rng.integers(-3, 4, size=(C, y1 - y0, x1 - x0))
+    for t in range(NT):
+        if t % 2:
+            q[t][:, y0:y1, x0:x1] = rng.integers(-3, 4, size=(C, y1 - y0, x1 - x0))
+            continue
+        q[t] = rng.integers(-m, m + 1, size=(C, TH, TW))
+        q[t][np.abs(q[t]) == m] = 0
+        q[t, C - 1, 31, 47] = sign * m
+        q[t, 0, :4, :8] = 0                                            # a whole wave's worth of zeros among the rest
     return q
 
 
@@ -355,13 +358,23 @@ def _edge_q(C, m, sign, seed):
 def test_split_tables_strings_and_block(C, m, k):
     """split on each side of every k edge (the maximum with both signs), then the tables against residual_ref.table,
     the strings against the coder oracle, and the block against the reference's pack_block"""
+    _split_case(C, m, k, NT)
+
+
+def test_a_block_of_more_than_256_pieces():
+    """13 tiles at C = 3 are (3 + 1 + 16) * 13 = 260 pieces, so the offsets scan of dsic_residual_pack_u16's head kernel
+    runs a second pass of 256 with the carry of the first; the two kinds of tile alternate."""
+    _split_case(3, 511, 2, 13)
+
+
+def _split_case(C, m, k, NT):
     L = lib.load()
     tau = 3
     npix, per = TH * TW, C * TH * TW
     for sign in (1, -1):
-        qn = _edge_q(C, m, sign, 11 * C + m)
+        qn = _edge_q(C, m, sign, 11 * C + m, NT)
         d_q = _dev(qn.astype(np.int32))
-        d_max = _dev(np.array([m, int(np.abs(qn[1]).max())], dtype=np.int32))
+        d_max = _dev(np.abs(qn).reshape(NT, -1).max(axis=1).astype(np.int32))
         hbuf, hi = _guarded((NT, C, TH, TW), torch.float32, float("nan"))
         sbuf, hist = _guarded((NT, C, 512), torch.int32, -1, inner=0)
         kbuf, kk = _guarded((NT,), torch.int32, -1)
@@ -369,7 +382,7 @@ def test_split_tables_strings_and_block(C, m, k):
         lib.check(L.dsic_residual_split_u16(_p(d_q), _p(d_max), NT, C, TH, TW, _p(hi), _p(hist), _p(kk), _p(planes),
                                             _stream()), "residual_split_u16")
         refs = [R.split(qn[t]) for t in range(NT)]
-        assert [r[0] for r in refs] == [k, 0] == kk.cpu().tolist()
+        assert [r[0] for r in refs] == ([k, 0] * NT)[:NT] == kk.cpu().tolist()
         got_planes = planes.cpu().numpy()
         for t, (kt, want_hi, want_lo) in enumerate(refs):
             assert (hi[t].cpu().numpy() == want_hi).all()
