@@ -1473,3 +1473,4 @@ def decompress_valid(src, y0=0, x0=0, h=None, w=None, level=0, device="cuda"):
 
 from .view import ImageReader, stretch_from_histogram, view_level  # noqa: E402  (view.py builds on the functions above)
 from .view import affine_q16, rotation_affine, warp_level, warp_window, window_affine  # noqa: E402
+from .view import COLORMAPS, colormap_from_anchors  # noqa: E402

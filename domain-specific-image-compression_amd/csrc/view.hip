@@ -18,13 +18,17 @@
 // nearest: source row (y0 2 oh + (2 i + 1) h) / (2 oh) >> l = (y0 + (2 i + 1) h / (2 oh)) >> l, columns likewise; a copy.
 // render (codec.ImageReader.render, the _render exports): the same pixel, of which chosen channels are stretched to
 // bytes between two values per channel, with the validity as alpha; the resampled samples never reach memory.
+// index views (codec.ImageReader.render_index, the _index_render exports): the same pixel again, of which one or two
+// channels become an index (a band, a difference, a normalised difference) that is stretched to a byte and sent through
+// a colour map of 256 entries.
 //
 // A wave covers 64 consecutive pixels of an output row, so its loads walk the source rows in step and its stores are
 // one run of 64 C elements; each source pixel is needed by at most two output rows and two output columns when the
 // level fits the scale (codec.view_level), which the caches absorb.
 //
 // Here: the geometry (View, view_check), the samplers and the kernels.  In render.h, shared with warp.hip: Render and
-// stretch_byte, the display check (display_options, display_of) and the small host checks.
+// stretch_byte, the display check (display_options, display_of), the index tail and its check (index_value, index_stage,
+// index_tail, index_options, index_of) and the small host checks.
 #include <limits.h>
 
 #include "common.h"
@@ -169,6 +173,33 @@ __global__ __launch_bounds__(VIEW_BX * VIEW_BY) void render_kernel(const T* __re
   }
 }
 
+// The index view of the window (dsic_window_index_render_u8 / _u16): resample_pixel for the one or two bands of the
+// index, then render.h's index tail: the index of the resampled samples, stretched to a byte k, through the colour map
+// cm[k], which the workgroup stages in LDS once.  3 + alpha bytes per pixel, stored as render_kernel stores them.
+template <typename T, bool V>
+__global__ __launch_bounds__(VIEW_BX * VIEW_BY) void index_render_kernel(const T* __restrict__ src,
+                                                                         const uint8_t* __restrict__ sval,
+                                                                         uint8_t* __restrict__ dst, View v, int C, int mode,
+                                                                         int nodata, IndexRender r,
+                                                                         const uint8_t* __restrict__ cmap, int bx,
+                                                                         int64_t nblocks) {
+  __shared__ uint32_t cm[VIEW_BX * VIEW_BY];
+  static_assert(VIEW_BX * VIEW_BY == 256, "one colour map entry per thread");
+  index_stage(cmap, cm, threadIdx.y * VIEW_BX + threadIdx.x);
+  const int n = 3 + r.alpha;
+  const bool dwords = n == 4 && ((uintptr_t)dst & 3) == 0;
+  for (int64_t blk = blockIdx.x; blk < nblocks; blk += gridDim.x) {
+    const int64_t by = blk / bx;
+    const int j = (int)(blk - by * bx) * VIEW_BX + threadIdx.x;
+    const int64_t i64 = by * VIEW_BY + threadIdx.y;
+    if (i64 >= v.oh || j >= v.ow) continue;
+    const int i = (int)i64;
+    uint32_t m[4] = {0u, 0u, 0u, 0u};
+    const bool ok = resample_pixel<T, V>(src, sval, v, C, mode, nodata, i, j, r.need, m);
+    index_tail(r, cm, ok, m, dst + ((int64_t)i * v.ow + j) * n, dwords);
+  }
+}
+
 // float32 [C][.][.], C <= 8
 __global__ __launch_bounds__(VIEW_BX * VIEW_BY) void resample_f32_kernel(const float* __restrict__ src,
                                                                          float* __restrict__ dst, View v, int C,
@@ -309,6 +340,31 @@ static int render(const char* what, const T* src, const uint8_t* sval, const Vie
   return check_launch(what);
 }
 
+template <typename T>
+static int index_render(const char* what, const T* src, const uint8_t* sval, const View& v, int C, int kind, int a, int b,
+                        int lo, int hi, const uint8_t* cmap, uint8_t* dst, int mode, int nodata, int alpha, int background,
+                        void* stream) {
+  int bx;
+  int64_t nblocks;
+  IndexRender r;
+  const int n = 3 + alpha;
+  const int64_t spix = (int64_t)v.sh * v.sw, opix = (int64_t)v.oh * v.ow;
+  int status = index_options(what, kind, alpha, background);
+  if (status == DSIC_OK) status = view_check(what, src, dst, v, C, 1, 4, (int)sizeof(T), 1, n, mode, &bx, &nblocks);
+  if (status == DSIC_OK)
+    status = index_of<T>(what, C, kind, a, b, lo, hi, cmap, nodata, alpha, background, dst, n * opix, &r);
+  if (status != DSIC_OK) return status;
+  DSIC_REQUIRE(windows_apart(src, (int64_t)sizeof(T) * C * spix, sval, spix, dst, n * opix, nullptr, 0),
+               "%s: src and dst overlap", what);
+  if (sval)
+    hipLaunchKernelGGL((index_render_kernel<T, true>), launch_grid(nblocks), dim3(VIEW_BX, VIEW_BY), 0, (hipStream_t)stream,
+                       src, sval, dst, v, C, mode, 0, r, cmap, bx, nblocks);
+  else
+    hipLaunchKernelGGL((index_render_kernel<T, false>), launch_grid(nblocks), dim3(VIEW_BX, VIEW_BY), 0, (hipStream_t)stream,
+                       src, sval, dst, v, C, mode, nodata, r, cmap, bx, nblocks);
+  return check_launch(what);
+}
+
 }  // namespace dsic
 
 using namespace dsic;
@@ -373,4 +429,22 @@ extern "C" int dsic_window_render_u16(const uint16_t* src_hwc, const uint8_t* sr
   const View v = view_of(sh, sw, sy0, sx0, shift, y0, x0, h, w, oh, ow);
   return render<uint16_t>("window_render_u16", src_hwc, src_valid, v, C, bands, nb, lohi, dst, mode, nodata, alpha,
                           background, stream);
+}
+
+extern "C" int dsic_window_index_render_u8(const uint8_t* src_hwc, const uint8_t* src_valid, int sh, int sw, int sy0,
+                                           int sx0, int C, int shift, int y0, int x0, int h, int w, int kind, int band_a,
+                                           int band_b, int lo, int hi, const uint8_t* cmap_dev, uint8_t* dst, int oh, int ow,
+                                           int mode, int nodata, int alpha, int background, void* stream) {
+  const View v = view_of(sh, sw, sy0, sx0, shift, y0, x0, h, w, oh, ow);
+  return index_render<uint8_t>("window_index_render_u8", src_hwc, src_valid, v, C, kind, band_a, band_b, lo, hi, cmap_dev,
+                               dst, mode, nodata, alpha, background, stream);
+}
+
+extern "C" int dsic_window_index_render_u16(const uint16_t* src_hwc, const uint8_t* src_valid, int sh, int sw, int sy0,
+                                            int sx0, int C, int shift, int y0, int x0, int h, int w, int kind, int band_a,
+                                            int band_b, int lo, int hi, const uint8_t* cmap_dev, uint8_t* dst, int oh,
+                                            int ow, int mode, int nodata, int alpha, int background, void* stream) {
+  const View v = view_of(sh, sw, sy0, sx0, shift, y0, x0, h, w, oh, ow);
+  return index_render<uint16_t>("window_index_render_u16", src_hwc, src_valid, v, C, kind, band_a, band_b, lo, hi, cmap_dev,
+                                dst, mode, nodata, alpha, background, stream);
 }

@@ -22,7 +22,8 @@
 // contiguous elements.  Taps are also clamped to the source window, so a wrong plan cannot read outside the allocation.
 //
 // Here: the geometry (Warp, warp_check, warp_axis), the sampler and the kernels.  In render.h, shared with view.hip:
-// Render and stretch_byte, the display check (display_options, display_of) and the small host checks.
+// Render and stretch_byte, the display check (display_options, display_of), the index tail and its check (index_value,
+// index_stage, index_tail, index_options, index_of) and the small host checks.
 #include <limits.h>
 
 #include "common.h"
@@ -212,6 +213,29 @@ __global__ __launch_bounds__(WARP_TILE * WARP_TILE) void warp_render_kernel(cons
   }
 }
 
+// The index view of the warped window (dsic_window_warp_index_render_u8 / _u16): warp_pixel, then render.h's index
+// tail with the colour map staged in LDS, as view.hip's index_render_kernel.
+template <typename T, bool V>
+__global__ __launch_bounds__(WARP_TILE * WARP_TILE) void warp_index_render_kernel(const T* __restrict__ src,
+                                                                                  const uint8_t* __restrict__ sval,
+                                                                                  uint8_t* __restrict__ dst, Warp g, int C,
+                                                                                  int mode, int nodata, IndexRender r,
+                                                                                  const uint8_t* __restrict__ cmap, int bx,
+                                                                                  int64_t nblocks) {
+  __shared__ uint32_t cm[WARP_TILE * WARP_TILE];
+  static_assert(WARP_TILE * WARP_TILE == 256, "one colour map entry per thread");
+  index_stage(cmap, cm, threadIdx.x);
+  const int n = 3 + r.alpha;
+  const bool dwords = n == 4 && ((uintptr_t)dst & 3) == 0;
+  for (int64_t blk = blockIdx.x; blk < nblocks; blk += gridDim.x) {
+    int i, j;
+    if (!warp_where(g, blk, bx, &i, &j)) continue;
+    uint32_t m[4];
+    const bool ok = warp_pixel<T, V>(src, sval, g, C, mode, nodata, 0u, i, j, m);
+    index_tail(r, cm, ok, m, dst + ((int64_t)i * g.ow + j) * n, dwords);
+  }
+}
+
 // One axis of the host check: the level indices that the taps of all inside samples can take, from the positions of the
 // four corner pixels (P is affine in (i, j), the floor monotone).  false: no sample is inside on this axis.
 static bool warp_axis(const int64_t* m, int oh, int ow, int64_t NP, int L, int l, int mode, int64_t* a, int64_t* b) {
@@ -321,6 +345,29 @@ static int warp_render(const char* what, const T* src, const uint8_t* sval, cons
   return check_launch(what);
 }
 
+template <typename T>
+static int warp_index_render(const char* what, const T* src, const uint8_t* sval, const Warp& g, int H, int W,
+                             const int64_t* m, int C, int kind, int a, int b, int lo, int hi, const uint8_t* cmap,
+                             uint8_t* dst, int mode, int nodata, int alpha, int background, void* stream) {
+  int bx;
+  int64_t nblocks;
+  IndexRender r;
+  const int n = 3 + alpha;
+  int status = index_options(what, kind, alpha, background);
+  if (status == DSIC_OK)
+    status = warp_check(what, src, sval, dst, nullptr, g, H, W, m, C, 1, (int)sizeof(T), 1, n, mode, &bx, &nblocks);
+  if (status == DSIC_OK)
+    status = index_of<T>(what, C, kind, a, b, lo, hi, cmap, nodata, alpha, background, dst, (int64_t)n * g.oh * g.ow, &r);
+  if (status != DSIC_OK) return status;
+  if (sval)
+    hipLaunchKernelGGL((warp_index_render_kernel<T, true>), launch_grid(nblocks), dim3(WARP_TILE * WARP_TILE), 0,
+                       (hipStream_t)stream, src, sval, dst, g, C, mode, -1, r, cmap, bx, nblocks);
+  else
+    hipLaunchKernelGGL((warp_index_render_kernel<T, false>), launch_grid(nblocks), dim3(WARP_TILE * WARP_TILE), 0,
+                       (hipStream_t)stream, src, sval, dst, g, C, mode, nodata, r, cmap, bx, nblocks);
+  return check_launch(what);
+}
+
 }  // namespace dsic
 
 using namespace dsic;
@@ -357,4 +404,24 @@ extern "C" int dsic_window_warp_render_u16(const uint16_t* src_hwc, const uint8_
   const Warp g = warp_of(sh, sw, sy0, sx0, shift, LH, LW, H, W, m, oh, ow);
   return warp_render<uint16_t>("window_warp_render_u16", src_hwc, src_valid, g, H, W, m, C, bands, nb, lohi, dst, mode,
                                nodata, alpha, background, stream);
+}
+
+extern "C" int dsic_window_warp_index_render_u8(const uint8_t* src_hwc, const uint8_t* src_valid, int sh, int sw, int sy0,
+                                                int sx0, int C, int shift, int LH, int LW, int H, int W, const int64_t* m,
+                                                int kind, int band_a, int band_b, int lo, int hi, const uint8_t* cmap_dev,
+                                                uint8_t* dst, int oh, int ow, int mode, int nodata, int alpha,
+                                                int background, void* stream) {
+  const Warp g = warp_of(sh, sw, sy0, sx0, shift, LH, LW, H, W, m, oh, ow);
+  return warp_index_render<uint8_t>("window_warp_index_render_u8", src_hwc, src_valid, g, H, W, m, C, kind, band_a, band_b,
+                                    lo, hi, cmap_dev, dst, mode, nodata, alpha, background, stream);
+}
+
+extern "C" int dsic_window_warp_index_render_u16(const uint16_t* src_hwc, const uint8_t* src_valid, int sh, int sw, int sy0,
+                                                 int sx0, int C, int shift, int LH, int LW, int H, int W, const int64_t* m,
+                                                 int kind, int band_a, int band_b, int lo, int hi, const uint8_t* cmap_dev,
+                                                 uint8_t* dst, int oh, int ow, int mode, int nodata, int alpha,
+                                                 int background, void* stream) {
+  const Warp g = warp_of(sh, sw, sy0, sx0, shift, LH, LW, H, W, m, oh, ow);
+  return warp_index_render<uint16_t>("window_warp_index_render_u16", src_hwc, src_valid, g, H, W, m, C, kind, band_a, band_b,
+                                     lo, hi, cmap_dev, dst, mode, nodata, alpha, background, stream);
 }

@@ -9,6 +9,9 @@ values per band, with the validity as an alpha channel; histogram and stretch de
 (csrc/histogram.hip, stretch_from_histogram).  read_warped and render_warped do both for an affine view: a 2 x 3
 matrix quantised once to Q16 (affine_q16), the level its scale asks for (warp_level), the window of that level which
 holds every tap (warp_window), and one launch of the bilinear, cubic or nearest sampler (csrc/warp.hip).
+render_index and render_index_warped show an index of one or two bands (a normalised difference such as NDVI, a
+difference, a band) through a colour map in that same launch (csrc/render.h's index tail); index_histogram and
+index_stretch derive its stretch from the data, colormap_from_anchors and COLORMAPS supply the maps.
 
 The cache holds what the stitch and blend calls consume: per (level, tile) the tile's g_s output, float32
 [C, th, tw], not clamped, and for a near-lossless level its q plane.  A window is served by collecting its tiles, in
@@ -191,6 +194,50 @@ def stretch_from_histogram(hist, percent=(2, 98)) -> list:
     return out
 
 
+# ---- index views: an index of one or two bands through a colour map --------------------------------------------------
+INDEX_KINDS = {"band": 0, "difference": 1, "nd": 2}             # DSIC_INDEX_* of include/dsic_hip.h
+INDEX_SCALE = 10000                                              # a normalised difference is 10000 (A - B) / (A + B)
+_IndexShow = collections.namedtuple("_IndexShow", "kind a b stretch colormap alpha background")
+
+
+def index_range(kind, top) -> tuple:
+    """(vmin, vmax) of an index kind over samples in 0 .. top: the table of include/dsic_hip.h."""
+    return {"band": (0, top), "difference": (-top, top), "nd": (-INDEX_SCALE, INDEX_SCALE)}[kind]
+
+
+def colormap_from_anchors(anchors) -> np.ndarray:
+    """A colour map from anchors [(p, (r, g, b)), ...] (pure Python / NumPy) -> uint8 [256, 3].  The p are strictly
+    increasing integers, the first 0 and the last 255, the colours integers in 0 .. 255.  Between neighbouring anchors
+    p0 < p1 with D = p1 - p0, entry i is (2 (c0 (p1 - i) + c1 (i - p0)) + D) // (2 D) per component: the straight line,
+    rounded half up, through the anchors themselves."""
+    try:
+        pts = [(operator.index(p), tuple(operator.index(v) for v in c)) for p, c in anchors]
+    except (TypeError, ValueError):
+        raise ValueError(f"colormap_from_anchors: anchors={anchors!r} is not a sequence of (p, (r, g, b)) in "
+                         "integers") from None
+    if len(pts) < 2 or pts[0][0] != 0 or pts[-1][0] != 255 or any(a[0] >= b[0] for a, b in zip(pts, pts[1:])):
+        raise ValueError(f"colormap_from_anchors: the positions {[p for p, _ in pts]} must rise strictly from 0 to 255")
+    if any(len(c) != 3 or not all(0 <= v <= 255 for v in c) for _, c in pts):
+        raise ValueError("colormap_from_anchors: a colour is three integers in 0 .. 255")
+    cmap = np.zeros((256, 3), dtype=np.uint8)
+    for (p0, c0), (p1, c1) in zip(pts, pts[1:]):
+        D = p1 - p0
+        for i in range(p0, p1 + 1):
+            cmap[i] = [(2 * (a * (p1 - i) + b * (i - p0)) + D) // (2 * D) for a, b in zip(c0, c1)]
+    return cmap
+
+
+COLORMAPS = {
+    "grey": colormap_from_anchors([(0, (0, 0, 0)), (255, (255, 255, 255))]),
+    # brown -> pale yellow -> dark green
+    "ndvi": colormap_from_anchors([(0, (120, 70, 20)), (128, (255, 250, 190)), (192, (90, 170, 60)), (255, (0, 80, 20))]),
+    # blue -> white -> red, white at 128
+    "diverging": colormap_from_anchors([(0, (20, 50, 160)), (128, (255, 255, 255)), (255, (170, 20, 30))]),
+    # black -> red -> yellow -> white
+    "heat": colormap_from_anchors([(0, (0, 0, 0)), (96, (255, 0, 0)), (192, (255, 255, 0)), (255, (255, 255, 255))]),
+}
+
+
 def _has_q(ix):
     """Whether a level carries a residual layer: max_error (version 4) or tolerance (version 9)."""
     return ix.get("max_error") is not None or ix.get("tolerance") is not None
@@ -291,6 +338,8 @@ class ImageReader:
         self._lru, self._used = collections.OrderedDict(), 0       # (level, tile) -> None, oldest first
         self._stats = dict(_new_stats(), tiles=0)
         self._hists = {}                                           # level -> its histogram, counted once
+        self._index_hists = {}                                     # (level, kind, a, b) -> an index's histogram
+        self._cmaps = {}                                           # name -> the colour map on the device
         self._closed = False
 
     def __enter__(self):
@@ -304,6 +353,8 @@ class ImageReader:
         self._lru.clear()
         self._open.clear()
         self._hists.clear()
+        self._index_hists.clear()
+        self._cmaps.clear()
         self._used, self._closed = 0, True
 
     # ---- the stream ---------------------------------------------------------------------------------------------
@@ -736,16 +787,186 @@ class ImageReader:
     def render_many(self, requests, alpha=False, background=0, resampling="average", stats=None):
         """requests: dicts with `window` and optionally `size`, `level`, `bands` and `stretch`, as render takes them
         -> the list [render(*window, size, level, bands, stretch, alpha, background, resampling) for each], bit for
-        bit.  Missing tiles are decoded once over the union of the requests, as read_many does it."""
+        bit.  A request with `index` is an index view: its `stretch` is one pair and it may name a `colormap`, as
+        render_index takes them, and its entry is render_index(*window, index, size, level, stretch, colormap, alpha,
+        background, resampling).  Missing tiles are decoded once over the union of the requests, as read_many does
+        it."""
         before, st = self._source.bytes_read, _new_stats()
         plans = [self._plan(r["window"], r.get("size"), r.get("level"), resampling) for r in requests]
-        displays = [self._display(p[0], r.get("bands"), r.get("stretch"), alpha, background)
+        displays = [self._index_display(p[0], r["index"], r.get("stretch"), r.get("colormap", "grey"), alpha, background,
+                                        "ImageReader.render_many")
+                    if r.get("index") is not None else self._display(p[0], r.get("bands"), r.get("stretch"), alpha, background)
                     for p, r in zip(plans, requests)]
-        displays = [(d[0], self._default_stretch(p[0], d[1], st)) + d[2:] for p, d in zip(plans, displays)]
+        displays = [self._index_defaults(p[0], d, st) if isinstance(d, _IndexShow)
+                    else (d[0], self._default_stretch(p[0], d[1], st)) + d[2:] for p, d in zip(plans, displays)]
         shared = self._ensure_union(plans, st)
-        imgs = [self._render(level, lw, view, d, resampling, st, shared) for (level, lw, view), d in zip(plans, displays)]
+        imgs = [(self._render_index if isinstance(d, _IndexShow) else self._render)(level, lw, view, d, resampling, st, shared)
+                for (level, lw, view), d in zip(plans, displays)]
         self._finish(st, before, stats)
         return imgs
+
+    # ---- index views --------------------------------------------------------------------------------------------
+    def _check_index(self, ix, index, what):
+        """index = ("nd", a, b), ("difference", a, b) or ("band", a) against a level -> (kind name, a, b)."""
+        try:
+            name, bands = index[0], tuple(operator.index(v) for v in index[1:])
+        except (TypeError, IndexError, KeyError):
+            raise ValueError(f"{what}: index={index!r} is not ('nd', a, b), ('difference', a, b) or ('band', a)") from None
+        if not isinstance(name, str) or name not in INDEX_KINDS or len(bands) != (1 if name == "band" else 2):
+            raise ValueError(f"{what}: index={index!r} is not ('nd', a, b), ('difference', a, b) or ('band', a)")
+        if not all(0 <= v < ix["C"] for v in bands):
+            raise ValueError(f"{what}: index={index!r} must name bands in 0 .. {ix['C'] - 1}")
+        return name, bands[0], bands[-1]
+
+    def _index_display(self, level, index, stretch, colormap, alpha, background, what):
+        """render_index's arguments checked against a level -> _IndexShow, the stretch still None where not given and
+        the colour map a name or a uint8 [256, 3] array."""
+        ix = self._open[level][1]
+        top = self._display_out(ix)[1]
+        kind, a, b = self._check_index(ix, index, what)
+        if stretch is not None:
+            try:
+                stretch = tuple(operator.index(v) for v in stretch)
+            except TypeError:
+                raise ValueError(f"{what}: stretch={stretch!r} is not one pair of integers (lo, hi)") from None
+            vmin, vmax = index_range(kind, top)
+            if len(stretch) != 2:
+                raise ValueError(f"{what}: stretch={stretch!r} is not one pair of integers (lo, hi)")
+            if not vmin <= stretch[0] <= stretch[1] <= vmax:
+                raise ValueError(f"{what}: stretch pair ({stretch[0]}, {stretch[1]}) must have {vmin} <= lo <= hi <= {vmax}")
+        if isinstance(colormap, str):
+            if colormap not in COLORMAPS:
+                raise ValueError(f"{what}: colormap={colormap!r} ({', '.join(COLORMAPS)}, or a uint8 [256, 3] array)")
+        else:
+            try:
+                table = colormap.cpu().numpy() if isinstance(colormap, torch.Tensor) else np.asarray(colormap)
+            except (TypeError, ValueError, RuntimeError):
+                table = None
+            if table is None or table.dtype != np.uint8 or table.shape != (256, 3):
+                raise ValueError(f"{what}: colormap must be one of {', '.join(COLORMAPS)}, or a uint8 [256, 3] array")
+            colormap = np.ascontiguousarray(table)
+        try:
+            background = operator.index(background)
+        except TypeError:
+            raise ValueError(f"{what}: background={background!r} is not an integer") from None
+        if not 0 <= background <= 255:
+            raise ValueError(f"{what}: background={background} must be in 0 .. 255")
+        if alpha and "nodata" in ix:
+            raise ValueError(f"{what}: alpha=True needs a validity mask (compress_image with valid=, stream version "
+                             f"{_c.VERSION_VALID}); a nodata stream marks its pixels by value")
+        return _IndexShow(kind, a, b, stretch, colormap, int(bool(alpha)), background)
+
+    def _index_defaults(self, level, show, st):
+        """The stretch where none was given ((-10000, 10000) for a normalised difference, render's pair of the band
+        for a band, index_stretch for a difference) and the colour map on the device (a named one: once per reader)."""
+        stretch = show.stretch
+        if stretch is None and show.kind == "nd":
+            stretch = (-INDEX_SCALE, INDEX_SCALE)
+        elif stretch is None and show.kind == "band":
+            stretch = tuple(self._default_stretch(level, None, st)[show.a])
+        elif stretch is None:
+            stretch = self._index_stretch((show.kind, show.a, show.b), (2, 98), None, st)
+        cmap = show.colormap
+        if isinstance(cmap, str):
+            if cmap not in self._cmaps:
+                self._cmaps[cmap] = torch.from_numpy(COLORMAPS[cmap]).to(self._dev)
+            cmap = self._cmaps[cmap]
+        else:
+            cmap = torch.from_numpy(cmap).to(self._dev)
+        return show._replace(stretch=stretch, colormap=cmap)
+
+    def _render_index(self, level, lw, view, show, resampling, st, ensured):
+        """One planned request through the index kernel (dsic_window_index_render_u8 / _u16)."""
+        ix = self._open[level][1]
+        shift = 0 if view is None else level
+        if view is None:
+            view = (tuple(int(v) for v in lw), (int(lw[2]), int(lw[3])), RESAMPLING[resampling])
+        (y0, x0, h, w), (oh, ow), mode = view
+        img, valid = self._source_window(level, lw, self._display_out(ix)[0], st, ensured)
+        dst = torch.empty((oh, ow, 3 + show.alpha), dtype=torch.uint8, device=self._dev)
+        _call_by_width("window_index_render", img, _opt(valid), lw[2], lw[3], lw[0], lw[1], ix["C"], shift, y0, x0, h, w,
+                       INDEX_KINDS[show.kind], show.a, show.b, *show.stretch, _p(show.colormap), _p(dst), oh, ow, mode,
+                       ix.get("nodata", -1) if mode == 0 else -1, show.alpha, show.background, _stream())
+        return dst
+
+    @torch.no_grad()
+    def render_index(self, y0, x0, h, w, index, size=None, level=None, stretch=None, colormap="grey", alpha=False,
+                     background=0, resampling="average", stats=None):
+        """The window as an index view: torch.uint8 [oh, ow, 3 (+ 1)] on the device, in one launch over the window
+        that read would resample (dsic_window_index_render_u8 / _u16).  Window, size, level, resampling and stats are
+        render's.
+        index: ("nd", a, b), the normalised difference 10000 (A - B) / (A + B) of bands a and b rounded half up, in
+        -10000 .. 10000 (NDVI: a the near infrared band, b the red one); ("difference", a, b), A - B in -top .. top
+        with top = 255 (65535 for a uint16 stream); or ("band", a), the sample itself.  It is taken from the samples
+        read(..., size, resampling) returns, bit for bit (include/dsic_hip.h has the integer arithmetic).
+        stretch: one pair (lo, hi) in index units; the index becomes the byte k = 255 (clip(v, lo, hi) - lo) /
+        (hi - lo) rounded half up, 0 where lo == hi.  None = (-10000, 10000) for "nd", render's default pair of the
+        band for "band", index_stretch(index) for "difference" (whose first use counts the coarsest level).
+        colormap: a name of codec.COLORMAPS ("grey", "ndvi", "diverging", "heat"), or a uint8 [256, 3] array or tensor;
+        the pixel is colormap[k].
+        A pixel with nothing valid under it, and an "nd" pixel with A + B = 0, is `background` in the three bands;
+        alpha = True adds a last channel, 0 there and 255 elsewhere.
+        ValueError before any decode or launch for an index, stretch, colormap, background or resampling out of these
+        bounds, and for alpha = True on a nodata stream (version 5)."""
+        before, st = self._source.bytes_read, _new_stats()
+        level, lw, view = self._plan((y0, x0, h, w), size, level, resampling)
+        show = self._index_display(level, index, stretch, colormap, alpha, background, "ImageReader.render_index")
+        img = self._render_index(level, lw, view, self._index_defaults(level, show, st), resampling, st, False)
+        if size is not None:
+            st.update(level=level, level_window=tuple(lw))
+        self._finish(st, before, stats)
+        return img
+
+    @torch.no_grad()
+    def index_histogram(self, index, level=None):
+        """hist[u] = the number of pixels of `level` (default: the coarsest) that count and whose index is
+        u = v - vmin: NumPy int64 [20001] for ("nd", a, b), [2 top + 1] for ("difference", a, b); ("band", a) is
+        histogram(level)[a].  The pixels histogram counts are counted, less those of a normalised difference with
+        A + B = 0.  Read in strips through the reader's window path as histogram reads (dsic_index_histogram_u8 /
+        _u16 per strip); the result is kept per level and index."""
+        before, st = self._source.bytes_read, _new_stats()
+        hist = self._index_histogram(index, level, st)
+        self._finish(st, before, None)
+        return hist
+
+    def _index_histogram(self, index, level, st):
+        level, _, ix = self._level(len(self.levels) - 1 if level is None else level)
+        kind, a, b = self._check_index(ix, index, "ImageReader.index_histogram")
+        if kind == "band":
+            return self._histogram(level, st)[a]
+        key = (level, kind, a, b)
+        if key not in self._index_hists:
+            out, top = self._display_out(ix)
+            H, W, C, g = ix["H"], ix["W"], ix["C"], ix["grid"]
+            vmin, vmax = index_range(kind, top)
+            total = torch.zeros((vmax - vmin + 1,), dtype=torch.int64, device=self._dev)
+            part = torch.empty((vmax - vmin + 1,), dtype=torch.int32, device=self._dev)        # the kernel's uint32 counters
+            rows = g["th"] * max(1, self.batch // g["nx"])         # tile rows that fill about one decode batch
+            for y in range(0, H, rows):
+                h = min(rows, H - y)
+                img, valid = self._source_window(level, (y, 0, h, W), out, st)
+                part.zero_()
+                _call_by_width("index_histogram", img, _opt(valid), h, W, C, ix.get("nodata", -1), INDEX_KINDS[kind], a, b,
+                               _p(part), _stream())
+                total += part.to(torch.int64) & 0xFFFFFFFF
+            self._index_hists[key] = total.cpu().numpy()
+        return self._index_hists[key].copy()
+
+    def index_stretch(self, index, percent=(2, 98), level=None):
+        """The percentile pair of an index in index units: stretch_from_histogram's rule on index_histogram(index,
+        level), shifted by vmin."""
+        _check_percent(percent)                                    # before anything is decoded
+        before, st = self._source.bytes_read, _new_stats()
+        pair = self._index_stretch(index, percent, level, st)
+        self._finish(st, before, None)
+        return pair
+
+    def _index_stretch(self, index, percent, level, st):
+        level, _, ix = self._level(len(self.levels) - 1 if level is None else level)
+        kind = self._check_index(ix, index, "ImageReader.index_stretch")[0]
+        vmin = index_range(kind, self._display_out(ix)[1])[0]
+        lo, hi = stretch_from_histogram(self._index_histogram(index, level, st)[None], percent)[0]
+        return lo + vmin, hi + vmin
 
     # ---- warped views -------------------------------------------------------------------------------------------
     def _plan_warp(self, matrix, size, level, resampling, what):
@@ -832,5 +1053,35 @@ class ImageReader:
                            *self.levels[level], *self.levels[0], (ctypes.c_int64 * 6)(*m),
                            (ctypes.c_int * len(bands))(*bands), len(bands), _c._lohi(stretch), _p(img), oh, ow, mode,
                            ix.get("nodata", -1), alpha, background, _stream())
+        self._finish(st, before, stats, level=level, level_window=lw, matrix_q16=m)
+        return img
+
+    @torch.no_grad()
+    def render_index_warped(self, matrix, size, index, level=None, stretch=None, colormap="grey", alpha=False,
+                            background=0, resampling="bilinear", stats=None):
+        """The affine view read_warped(matrix, size, level, resampling) as an index view: torch.uint8
+        [oh, ow, 3 (+ 1)] in one launch (dsic_window_warp_index_render_u8 / _u16).  index, stretch, colormap, alpha
+        and background are render_index's, with its default stretch; the index is taken from read_warped's samples,
+        bit for bit.  A pixel outside the image, with nothing counting under it, or with an undefined index is
+        `background` and, with alpha = True, alpha 0.  A view beside the image decodes and launches nothing.
+        ValueError as read_warped and render_index raise it."""
+        what = "ImageReader.render_index_warped"
+        before, st = self._source.bytes_read, _new_stats()
+        level, m, (oh, ow), mode, lw = self._plan_warp(matrix, size, level, resampling, what)
+        show = self._index_display(level, index, stretch, colormap, alpha, background, what)
+        ix = self._open[level][1]
+        n = 3 + show.alpha
+        if lw is None:                                             # beside the image: no stretch needed, nothing decoded
+            img = torch.full((oh, ow, n), show.background, dtype=torch.uint8, device=self._dev)
+            if show.alpha:
+                img[:, :, n - 1] = 0
+        else:
+            show = self._index_defaults(level, show, st)
+            src, valid = self._source_window(level, lw, self._display_out(ix)[0], st)
+            img = torch.empty((oh, ow, n), dtype=torch.uint8, device=self._dev)
+            _call_by_width("window_warp_index_render", src, _opt(valid), lw[2], lw[3], lw[0], lw[1], ix["C"], level,
+                           *self.levels[level], *self.levels[0], (ctypes.c_int64 * 6)(*m), INDEX_KINDS[show.kind], show.a,
+                           show.b, *show.stretch, _p(show.colormap), _p(img), oh, ow, mode, ix.get("nodata", -1), show.alpha,
+                           show.background, _stream())
         self._finish(st, before, stats, level=level, level_window=lw, matrix_q16=m)
         return img

@@ -931,6 +931,72 @@ int dsic_window_warp_render_u16(const uint16_t* src_hwc, const uint8_t* src_vali
                                 uint8_t* dst, int oh, int ow, int mode, int nodata, int alpha,
                                 int background, void* stream);
 
+/* ---- index views (codec.ImageReader.render_index, .render_index_warped, .index_histogram) ----
+ * An index is (kind, a, b): a and b are band numbers of the stream, b is ignored for a band.  It is
+ * taken from the sample that the resample or warp call would write for the same request: resample
+ * first, index after, as the render calls stretch that sample.  top is 255 or 65535, A the sample
+ * of band a, B the sample of band b, s = A + B.  The index value v is kept as the unsigned
+ * u = v - vmin:
+ *
+ *   kind                      u                       v = u + vmin              vmin .. vmax      defined
+ *   DSIC_INDEX_BAND           A                       the sample itself         0 .. top          always
+ *   DSIC_INDEX_DIFFERENCE     A - B + top             A - B                     -top .. top       always
+ *   DSIC_INDEX_ND             (40000 A + s) / (2 s)   10000 (A - B) / (A + B)   -10000 .. 10000   s != 0
+ *                             (unsigned 32-bit)       rounded half up
+ *
+ * 40000 * 65535 + 131070 < 2^32, so the normalised difference is one 32-bit unsigned division per
+ * pixel; the scale 10000 is the customary integer NDVI.  A normalised difference with s = 0 is
+ * invalid, exactly as a pixel with nothing valid under it: background, alpha 0, not counted.
+ * The stretch pair (lo, hi) is given in v units, vmin <= lo <= hi <= vmax; the byte is k = the
+ * stretch of the render calls applied to (u, lo - vmin, hi - vmin): 510 * 131070 + 131070 < 2^32.
+ * Colour map: cmap_dev is uint8 [256][3] on the device and the output bands are cmap[k][0..2].
+ * dst is uint8 [oh][ow][3 + alpha]; an invalid pixel gets background in the three bands and, for
+ * alpha = 1, alpha 0; every other pixel gets alpha 255.
+ * dsic_window_index_render_u8 / _u16: the geometry, src_valid, mode and nodata of
+ *   dsic_window_render_u8 / _u16.  dsic_window_warp_index_render_u8 / _u16: those of
+ *   dsic_window_warp_render_u8 / _u16.
+ *   DSIC_EINVAL, nothing written: what the sibling refuses of geometry, pointers, overlap and
+ *   alignment; kind outside the three; a band outside 0..C-1; a pair that is not vmin <= lo <= hi
+ *   <= vmax; a null cmap_dev; cmap overlapping dst; alpha outside 0..1; background outside 0..255.
+ * dsic_index_histogram_u8 / _u16: hist[u] += the number of counted pixels of img [H][W][C] whose
+ *   index is u: 20001 uint32 on the device for DSIC_INDEX_ND, 2 top + 1 (511 or 131071) for
+ *   DSIC_INDEX_DIFFERENCE.  Counted is what dsic_band_histogram_u8 / _u16 count, less the pixels of
+ *   a normalised difference with s = 0.  The caller zeroes hist; several calls sum into it;
+ *   integer atomic adds: no dependence on any order.
+ *   DSIC_EINVAL: what dsic_band_histogram_u8 refuses; a band outside 0..C-1; a kind other than
+ *   these two (DSIC_INDEX_BAND: dsic_band_histogram_u8 / _u16 count a band). */
+#define DSIC_INDEX_BAND 0
+#define DSIC_INDEX_DIFFERENCE 1
+#define DSIC_INDEX_ND 2
+int dsic_window_index_render_u8(const uint8_t* src_hwc, const uint8_t* src_valid, int sh, int sw,
+                                int sy0, int sx0, int C, int shift, int y0, int x0, int h, int w,
+                                int kind, int band_a, int band_b, int lo, int hi,
+                                const uint8_t* cmap_dev, uint8_t* dst, int oh, int ow, int mode,
+                                int nodata, int alpha, int background, void* stream);
+int dsic_window_index_render_u16(const uint16_t* src_hwc, const uint8_t* src_valid, int sh, int sw,
+                                 int sy0, int sx0, int C, int shift, int y0, int x0, int h, int w,
+                                 int kind, int band_a, int band_b, int lo, int hi,
+                                 const uint8_t* cmap_dev, uint8_t* dst, int oh, int ow, int mode,
+                                 int nodata, int alpha, int background, void* stream);
+int dsic_window_warp_index_render_u8(const uint8_t* src_hwc, const uint8_t* src_valid, int sh,
+                                     int sw, int sy0, int sx0, int C, int shift, int LH, int LW,
+                                     int H, int W, const int64_t* m, int kind, int band_a,
+                                     int band_b, int lo, int hi, const uint8_t* cmap_dev,
+                                     uint8_t* dst, int oh, int ow, int mode, int nodata, int alpha,
+                                     int background, void* stream);
+int dsic_window_warp_index_render_u16(const uint16_t* src_hwc, const uint8_t* src_valid, int sh,
+                                      int sw, int sy0, int sx0, int C, int shift, int LH, int LW,
+                                      int H, int W, const int64_t* m, int kind, int band_a,
+                                      int band_b, int lo, int hi, const uint8_t* cmap_dev,
+                                      uint8_t* dst, int oh, int ow, int mode, int nodata, int alpha,
+                                      int background, void* stream);
+int dsic_index_histogram_u8(const uint8_t* img_hwc, const uint8_t* valid_hw, int H, int W, int C,
+                            int nodata, int kind, int band_a, int band_b, uint32_t* hist,
+                            void* stream);
+int dsic_index_histogram_u16(const uint16_t* img_hwc, const uint8_t* valid_hw, int H, int W, int C,
+                             int nodata, int kind, int band_a, int band_b, uint32_t* hist,
+                             void* stream);
+
 /* HIP stream limited to the CUs whose bit is set in mask_host[words] (bit i of
  * word i/32 = CU i).  Used to give the range coder its own few CUs beside the
  * conv kernels; there is no reference counterpart (the reference is

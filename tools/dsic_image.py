@@ -12,6 +12,7 @@ an image.
     python tools/dsic_image.py render     --weights CKPT.pt IN.dsic OUT [--region Y0,X0,H,W] [--size OH,OW] [--level L]
                                           [--bands B | B,B,B] [--stretch LO,HI[,LO,HI...]] [--percent P0,P1] [--alpha]
                                           [--background V] [--resampling average|nearest]
+                                          [--index KIND:A[,B] [--colormap NAME] [--index-stretch LO,HI | --percent P0,P1]]
                                           [--rotate DEG [--center Y,X] [--scale S] | --affine M00,M01,M02,M10,M11,M12]
                                           [--resampling bilinear|cubic|nearest]
     python tools/dsic_image.py info       IN.dsic
@@ -51,6 +52,13 @@ validity mask of a version-8 stream as an alpha channel, --background V (0 .. 25
 region (default: the whole image) is in level-0 pixels with --size, else in --level's own.  OUT is .npy, a binary .ppm
 (three bands) or .pgm (one band), both without alpha, or .png where PIL is importable.  The level read and the stretch
 used are printed.
+--index KIND:A[,B] renders an index of the stream's bands through a colour map instead of the bands themselves
+(codec.ImageReader.render_index / render_index_warped; with --region/--size and with --rotate/--affine): nd:A,B is the
+normalised difference 10000 (A - B) / (A + B) of bands A and B (NDVI: A the near infrared, B the red band),
+difference:A,B is A - B, band:A the band itself.  --colormap NAME (grey, the default, ndvi, diverging or heat) turns
+the stretched index into three bands; --index-stretch LO,HI gives the index values shown as the map's first and last
+colour (a negative LO is written --index-stretch=-2000,6000), --percent P0,P1 asks for the percentiles of the coarsest level's index instead, and without either the
+reader's default holds (nd: -10000,10000).  --bands and --stretch do not go with it.
 --rotate DEG with --size OH,OW (decompress and render) reads an affine view instead of a window
 (codec.ImageReader.read_warped / render_warped): OH x OW pixels centred on the level-0 position --center Y,X (default:
 the image's centre), the image turned counter-clockwise by DEG degrees, at --scale S level-0 pixels per output pixel
@@ -249,6 +257,25 @@ def render_main(a, ap, region, size, level_given, matrix=None):
             ap.error(f"{name} {text}: {what}")
         return values
 
+    index = None
+    if a.index is not None:
+        kind, _, rest = a.index.partition(":")
+        try:
+            index = (kind,) + tuple(int(v) for v in rest.split(","))
+        except ValueError:
+            index = ()
+        if kind not in ("nd", "difference", "band") or len(index) != (2 if kind == "band" else 3):
+            ap.error(f"--index {a.index}: nd:A,B, difference:A,B or band:A with band numbers A, B")
+        if a.bands is not None or a.stretch is not None:
+            ap.error("--bands and --stretch do not go with --index; --index-stretch LO,HI is its pair")
+        if a.index_stretch is not None and a.percent is not None:
+            ap.error("--index-stretch and --percent exclude each other")
+        if a.colormap not in codec.COLORMAPS:
+            ap.error(f"--colormap {a.colormap}: one of {', '.join(codec.COLORMAPS)}")
+    elif a.colormap != "grey" or a.index_stretch is not None:
+        ap.error("--colormap and --index-stretch go with --index")
+    pair = None if a.index_stretch is None else tuple(numbers(a.index_stretch, int, "--index-stretch", (2,),
+                                                              "two integers LO,HI in the index's units"))
     bands = None if a.bands is None else tuple(numbers(a.bands, int, "--bands", (1, 3), "one band B or three B,B,B"))
     if a.stretch is not None and a.percent is not None:
         ap.error("--stretch and --percent exclude each other")
@@ -270,6 +297,10 @@ def render_main(a, ap, region, size, level_given, matrix=None):
         if matrix is not None and level_given:
             codec.stream_index(f, level=a.level)                           # a level the stream does not hold
     C = ix["C"]
+    if index is not None and not all(0 <= b < C for b in index[1:]):
+        ap.error(f"--index {a.index}: the stream holds bands 0 .. {C - 1}")
+    if index is not None:
+        bands = (0, 0, 0)                                                  # an index view has three bands
     if bands is None:
         bands = (0, 1, 2) if C >= 3 else (0,)
     if not all(0 <= b < C for b in bands):
@@ -286,6 +317,8 @@ def render_main(a, ap, region, size, level_given, matrix=None):
         region = [0, 0, ix["H"], ix["W"]]
     model = load_model(a.weights, a.min_nu, a.max_nu)
     stats = {}
+    if index is not None:
+        return render_index_main(a, model, index, pair, region, size, level_given, matrix)
     with open(a.src, "rb") as f, codec.ImageReader(model, f, batch=a.batch) as reader:
         if stretch is None:                                                # --percent asks for the percentiles on any stream
             wanted = a.percent is not None or reader.kind == codec.KIND_U16_HWC
@@ -307,6 +340,32 @@ def render_main(a, ap, region, size, level_given, matrix=None):
     print(f"[dsic_image] window {region[2]}x{region[3]} at ({region[0]}, {region[1]}) as {img.shape[0]}x{img.shape[1]} "
           f"({a.resampling}) from level {stats.get('level', a.level)}, bands {','.join(str(b) for b in bands)}"
           + (" + alpha" if a.alpha else "") + ", stretch " + ", ".join(f"({lo}, {hi})" for lo, hi in stretch)
+          + f": {len(stats['tiles'])} tile(s) -> {path}")
+
+
+def render_index_main(a, model, index, pair, region, size, level_given, matrix):
+    """render --index: the arguments are checked; the pair comes from --index-stretch, --percent or the reader."""
+    from dsic_amd import codec
+    stats = {}
+    level = a.level if level_given else None
+    with open(a.src, "rb") as f, codec.ImageReader(model, f, batch=a.batch) as reader:
+        try:
+            if pair is None and a.percent is not None:
+                pair = reader.index_stretch(index, tuple(float(v) for v in a.percent.split(",")))
+            shown = dict(index=index, level=level, stretch=pair, colormap=a.colormap, alpha=a.alpha,
+                         background=a.background, resampling=a.resampling, stats=stats)
+            if matrix is not None:
+                img = reader.render_index_warped(matrix, tuple(size), **shown)
+            else:
+                img = reader.render_index(*region, size=None if size is None else tuple(size), **shown)
+        except ValueError as e:
+            raise SystemExit(f"[dsic_image] {e}")
+    path = write_display(a.dst, img.cpu().numpy())
+    what = (f"affine view {', '.join(f'{v / 65536:g}' for v in stats['matrix_q16'])}" if matrix is not None
+            else f"window {region[2]}x{region[3]} at ({region[0]}, {region[1]})")
+    print(f"[dsic_image] {what} as {img.shape[0]}x{img.shape[1]} ({a.resampling}) from level "
+          f"{stats.get('level', a.level)}, index {a.index}, colormap {a.colormap}" + (" + alpha" if a.alpha else "")
+          + ", stretch " + ("the default" if pair is None else f"({pair[0]}, {pair[1]})")
           + f": {len(stats['tiles'])} tile(s) -> {path}")
 
 
@@ -406,6 +465,12 @@ def main(argv=None):
     ap.add_argument("--percent", default=None, metavar="P0,P1",
                     help="render without --stretch: stretch between these percentiles of the coarsest level (uint16 streams: "
                          "by default 2,98; other streams: only when given)")
+    ap.add_argument("--index", default=None, metavar="KIND:A[,B]",
+                    help="render: an index view, nd:A,B (normalised difference), difference:A,B or band:A")
+    ap.add_argument("--colormap", default="grey", metavar="NAME", help="render --index: grey, ndvi, diverging or heat")
+    ap.add_argument("--index-stretch", default=None, metavar="LO,HI",
+                    help="render --index: the index values shown as the colour map's first and last entry; a negative LO as "
+                         "--index-stretch=LO,HI")
     ap.add_argument("--alpha", action="store_true", help="render: add the validity mask as an alpha channel")
     ap.add_argument("--background", type=int, default=0, metavar="V", help="render: what invalid pixels show (0 .. 255)")
     ap.add_argument("--min-nu", type=float, default=2.0)
@@ -460,8 +525,10 @@ def main(argv=None):
         if a.out is not None:
             ap.error("--out goes with decompress")
         return render_main(a, ap, region, size, given, matrix)
-    if a.bands is not None or a.stretch is not None or a.percent is not None or a.alpha or a.background:
-        ap.error("--bands, --stretch, --percent, --alpha and --background go with render")
+    if (a.bands is not None or a.stretch is not None or a.percent is not None or a.alpha or a.background
+            or a.index is not None or a.colormap != "grey" or a.index_stretch is not None):
+        ap.error("--bands, --stretch, --percent, --alpha, --background, --index, --colormap and --index-stretch go with "
+                 "render")
     if a.mode == "decompress" and not a.dst.endswith(".npy"):
         with open(a.src, "rb") as f:                                       # the heads only: no model, no GPU
             if a.out == "u16" or (a.out is None and codec.stream_index(f, level=a.level)["kind"] == codec.KIND_U16_HWC):

@@ -1,6 +1,6 @@
 """Pan and zoom: codec.ImageReader against one decompress_region call per frame, and the resampling kernel alone.
 
-    python tools/view_bench.py [--size 4096] [--tile 256] [--reps 3] [--json profiles/view_bench.json] [--only warp]
+    python tools/view_bench.py [--size 4096] [--tile 256] [--reps 3] [--json profiles/view_bench.json] [--only warp|index]
 
 The scene of image_codec_bench.py (synthetic patches side by side, uint8) is coded once with overviews=3.  A viewport
 of 768 rows x 1024 columns pans right in 32 steps of 64 pixels (33 frames).  Per frame, alternately in one process:
@@ -23,6 +23,12 @@ render(..., alpha=True) and with render_warped at 0 and at 30 degrees about the 
 per output pixel, bilinear and cubic: the median wall clock of 30 calls each, the order rotating from round to round,
 and each call's kernel alone on the window it planned (device events, as above).  --only warp measures that record
 alone and puts it into the --json file beside the records already there.
+index: the same frame and the same requests as index views: render_index with ("nd", 0, 1) through "ndvi" beside
+render with three bands, render_index_warped beside render_warped at 0 and 30 degrees (bilinear), all with alpha, each
+as a call (the median wall clock of 30, the order rotating) and as its kernel alone on the window it planned; and
+index_histogram(("nd", 0, 1)) and (("difference", 0, 1)) beside histogram through fresh readers on the coarsest and the
+full level, with the kernels alone on the full level, scene and constant image.  --only index measures that record
+alone.
 Records, not bars."""
 from __future__ import annotations
 
@@ -120,6 +126,81 @@ def _warp_record(model, stream, win, batch, rounds=30):
     return rec
 
 
+def _index_record(model, stream, img, win, batch, rounds=30):
+    """The `index` record: see the module's docstring."""
+    import torch
+    from dsic_amd import codec, lib
+    from dsic_amd.ops import _p, _stream
+    L = lib.load()
+    cy, cx, scale = win[0] + win[2] / 2, win[1] + win[3] / 2, win[2] / SIZE[0]
+    index, nd = ("nd", 0, 1), 2
+    views = {deg: codec.rotation_affine(cy, cx, deg, scale, *SIZE) for deg in (0, 30)}
+    rec = {"view_size": list(SIZE), "index": list(index), "colormap": "ndvi", "rounds": rounds}
+    bands, lohi = (ctypes.c_int * 3)(0, 1, 2), codec._lohi([(0, 255)] * 3)
+    cmap = torch.from_numpy(codec.COLORMAPS["ndvi"]).cuda()
+    rgba = torch.empty(SIZE + (4,), dtype=torch.uint8, device="cuda")
+    with codec.ImageReader(model, stream, batch=batch) as r:
+        calls = {"render": lambda st=None: r.render(*win, size=SIZE, alpha=True, stats=st),
+                 "render_index": lambda st=None: r.render_index(*win, index, size=SIZE, colormap="ndvi", alpha=True, stats=st)}
+        for deg, matrix in views.items():
+            calls[f"render_warped {deg} deg"] = lambda st=None, m=matrix: r.render_warped(m, SIZE, alpha=True, stats=st)
+            calls[f"render_index_warped {deg} deg"] = lambda st=None, m=matrix: r.render_index_warped(
+                m, SIZE, index, colormap="ndvi", alpha=True, stats=st)
+        for fn in calls.values():                                          # untimed: the tiles into the cache, every shape
+            fn(), fn()
+        torch.cuda.synchronize()
+        times, names = {name: [] for name in calls}, list(calls)
+        for k in range(rounds):
+            for name in names[k % len(names):] + names[:k % len(names)]:
+                times[name].append(_frame_ms(calls[name]))
+        H, W = r.levels[0]
+        for name in names:
+            st = {}
+            calls[name](st)
+            level, lw = st["level"], st["level_window"]
+            src = torch.randint(0, 256, (lw[2], lw[3], 3), dtype=torch.uint8, device="cuda")
+            head = (_p(src), None, lw[2], lw[3], lw[0], lw[1], 3, level)
+            if "warped" in name:
+                head += (*r.levels[level], H, W, (ctypes.c_int64 * 6)(*st["matrix_q16"]))
+                export = "window_warp_index_render_u8" if "index" in name else "window_warp_render_u8"
+            else:
+                head += tuple(win)
+                export = "window_index_render_u8" if "index" in name else "window_render_u8"
+            show = (nd, 0, 1, -10000, 10000, _p(cmap)) if "index" in name else (bands, 3, lohi)
+
+            def launch(export=export, head=head, show=show):
+                lib.check(getattr(L, "dsic_" + export)(*head, *show, _p(rgba), *SIZE, 0, -1, 1, 0, _stream()), export)
+            rec[name] = {"call_median_ms": round(statistics.median(times[name]), 4),
+                         "call_max_ms": round(max(times[name]), 4), "level": level, "level_window": list(lw),
+                         "kernel_us_per_launch": round(_per_launch_us(launch), 2)}
+    hist = {}
+    counted = {"histogram": lambda r, lv: r.histogram(lv), "index_histogram nd": lambda r, lv: r.index_histogram(index, lv),
+               "index_histogram difference": lambda r, lv: r.index_histogram(("difference", 0, 1), lv)}
+    with codec.ImageReader(model, stream, batch=batch) as r:               # untimed: the first call of every shape
+        for fn in counted.values():
+            fn(r, None), fn(r, 0)
+    for name, fn in counted.items():
+        for where, lv in (("coarsest_level", None), ("full_level", 0)):
+            with codec.ImageReader(model, stream, batch=batch) as r:
+                hist[f"{name} {where}_reader_ms"] = round(_frame_ms(lambda: fn(r, lv)), 2)
+    side = img.shape[0]
+    for what, image in (("scene", img), ("constant", torch.full_like(img, 77))):
+        counts = torch.zeros((3, 256), dtype=torch.int32, device="cuda")
+
+        def launch_band():
+            lib.check(L.dsic_band_histogram_u8(_p(image), None, side, side, 3, -1, _p(counts), _stream()), "band_histogram_u8")
+        hist[f"kernel band_histogram_u8 {what}_us"] = round(_per_launch_us(launch_band, n=10), 1)
+        for label, kind, bins in (("nd", nd, 20001), ("difference", 1, 511)):
+            part = torch.zeros((bins,), dtype=torch.int32, device="cuda")
+
+            def launch_index(kind=kind, part=part):
+                lib.check(L.dsic_index_histogram_u8(_p(image), None, side, side, 3, -1, kind, 0, 1, _p(part), _stream()),
+                          "index_histogram_u8")
+            hist[f"kernel index_histogram_u8 {label} {what}_us"] = round(_per_launch_us(launch_index, n=10), 1)
+    rec["histogram"] = hist
+    return rec
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--size", type=int, default=4096)
@@ -127,7 +208,7 @@ def main():
     ap.add_argument("--batch", type=int, default=64)
     ap.add_argument("--reps", type=int, default=3)
     ap.add_argument("--json", default=os.path.join(ROOT, "profiles", "view_bench.json"))
-    ap.add_argument("--only", choices=("warp",), default=None,
+    ap.add_argument("--only", choices=("warp", "index"), default=None,
                     help="measure this record alone and put it into the --json file beside the others")
     a = ap.parse_args()
 
@@ -153,11 +234,14 @@ def main():
     frames = [(y0, x_first + STEP * k, VIEW_H, VIEW_W) for k in range(STEPS + 1)]
     assert frames[-1][1] + VIEW_W <= a.size and y0 + VIEW_H <= a.size
     level = codec.view_level(4, VIEW_H, VIEW_W, *SIZE)
-    if a.only == "warp":
+    if a.only is not None:
         with open(a.json) as f:
             res = json.load(f)
-        res["warp"] = _warp_record(model, stream, frames[STEPS // 2], a.batch)
-        print(json.dumps(res["warp"]))
+        if a.only == "warp":
+            res["warp"] = _warp_record(model, stream, frames[STEPS // 2], a.batch)
+        else:
+            res["index"] = _index_record(model, stream, img, frames[STEPS // 2], a.batch)
+        print(json.dumps(res[a.only]))
         with open(a.json, "w") as f:
             json.dump(res, f, indent=1)
         return
@@ -261,6 +345,7 @@ def main():
             hist[f"kernel_{kind}_{name}_us"] = round(per_launch_us(launch_hist, n=10), 1)
     res["histogram"] = hist
     res["warp"] = _warp_record(model, stream, frames[STEPS // 2], a.batch)
+    res["index"] = _index_record(model, stream, img, frames[STEPS // 2], a.batch)
     print(json.dumps(res))
     with open(a.json, "w") as f:
         json.dump(res, f, indent=1)
