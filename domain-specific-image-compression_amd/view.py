@@ -12,6 +12,8 @@ holds every tap (warp_window), and one launch of the bilinear, cubic or nearest 
 render_index and render_index_warped show an index of one or two bands (a normalised difference such as NDVI, a
 difference, a band) through a colour map in that same launch (csrc/render.h's index tail); index_histogram and
 index_stretch derive its stretch from the data, colormap_from_anchors and COLORMAPS supply the maps.
+SceneStack places several readers on one grid, a mosaic or a temporal stack, and combines the parts they serve of a
+window in one launch (csrc/composite.hip): first, last, mean or median over the scenes that are valid at a pixel.
 
 The cache holds what the stitch and blend calls consume: per (level, tile) the tile's g_s output, float32
 [C, th, tw], not clamped, and for a near-lossless level its q plane.  A window is served by collecting its tiles, in
@@ -261,6 +263,35 @@ def _check_size(size, what, top=None, bound="at least (1, 1)"):
     if min(oh, ow) < 1 or (top is not None and max(oh, ow) > top):
         raise ValueError(f"{what}: size={size!r} must be {bound}")
     return oh, ow
+
+
+def _display_args(what, C, top, bands, stretch, background):
+    """The display arguments of a render over C bands of samples 0 .. top -> (bands, None or the stretch pairs,
+    background); `what` names the caller in a ValueError."""
+    try:
+        bands = ((0, 1, 2) if C >= 3 else (0,)) if bands is None else tuple(operator.index(b) for b in bands)
+    except TypeError:
+        raise ValueError(f"{what}: bands={bands!r} is not a sequence of band numbers") from None
+    if len(bands) not in (1, 3) or not all(0 <= b < C for b in bands):
+        raise ValueError(f"{what}: bands={bands!r} must be 1 or 3 of the bands 0 .. {C - 1}")
+    if stretch is not None:
+        try:
+            stretch = [tuple(operator.index(v) for v in pair) for pair in stretch]
+        except TypeError:
+            raise ValueError(f"{what}: stretch={stretch!r} is not a sequence of integer pairs (lo, hi)") from None
+        if len(stretch) != C or any(len(pair) != 2 for pair in stretch):
+            raise ValueError(f"{what}: stretch={stretch!r} must hold one pair (lo, hi) for each of the {C} bands of the "
+                             "stream")
+        for lo, hi in stretch:
+            if not 0 <= lo <= hi <= top:
+                raise ValueError(f"{what}: stretch pair ({lo}, {hi}) must have 0 <= lo <= hi <= {top}")
+    try:
+        background = operator.index(background)
+    except TypeError:
+        raise ValueError(f"{what}: background={background!r} is not an integer") from None
+    if not 0 <= background <= 255:
+        raise ValueError(f"{what}: background={background} must be in 0 .. 255")
+    return bands, stretch, background
 
 
 def _opt(t):
@@ -701,31 +732,8 @@ class ImageReader:
     def _display(self, level, bands, stretch, alpha, background):
         """render's arguments checked against a level -> (bands, None or the stretch pairs, alpha, background)."""
         ix = self._open[level][1]
-        C, top = ix["C"], self._display_out(ix)[1]
-        try:
-            bands = ((0, 1, 2) if C >= 3 else (0,)) if bands is None else tuple(operator.index(b) for b in bands)
-        except TypeError:
-            raise ValueError(f"ImageReader.render: bands={bands!r} is not a sequence of band numbers") from None
-        if len(bands) not in (1, 3) or not all(0 <= b < C for b in bands):
-            raise ValueError(f"ImageReader.render: bands={bands!r} must be 1 or 3 of the bands 0 .. {C - 1}")
-        if stretch is not None:
-            try:
-                stretch = [tuple(operator.index(v) for v in pair) for pair in stretch]
-            except TypeError:
-                raise ValueError(f"ImageReader.render: stretch={stretch!r} is not a sequence of integer pairs "
-                                 "(lo, hi)") from None
-            if len(stretch) != C or any(len(pair) != 2 for pair in stretch):
-                raise ValueError(f"ImageReader.render: stretch={stretch!r} must hold one pair (lo, hi) for each of the "
-                                 f"{C} bands of the stream")
-            for lo, hi in stretch:
-                if not 0 <= lo <= hi <= top:
-                    raise ValueError(f"ImageReader.render: stretch pair ({lo}, {hi}) must have 0 <= lo <= hi <= {top}")
-        try:
-            background = operator.index(background)
-        except TypeError:
-            raise ValueError(f"ImageReader.render: background={background!r} is not an integer") from None
-        if not 0 <= background <= 255:
-            raise ValueError(f"ImageReader.render: background={background} must be in 0 .. 255")
+        bands, stretch, background = _display_args("ImageReader.render", ix["C"], self._display_out(ix)[1], bands, stretch,
+                                                   background)
         if alpha and "nodata" in ix:
             raise ValueError("ImageReader.render: alpha=True needs a validity mask (compress_image with valid=, stream "
                              f"version {_c.VERSION_VALID}); a nodata stream marks its pixels by value")
@@ -1085,3 +1093,205 @@ class ImageReader:
                            show.background, _stream())
         self._finish(st, before, stats, level=level, level_window=lw, matrix_q16=m)
         return img
+
+
+# ---- scene stacks: mosaics and per-pixel composites over several readers, csrc/composite.hip -------------------------
+# A stack places scenes (open readers of one integer kind and one band count) on one level-0 grid, scene s at its offset
+# (oy, ox).  The stack has L levels, L the largest number such that every reader holds L levels and every offset is a
+# multiple of 2^(L-1); level l of the stack has the shape overview_shapes gives its grid, and scene s lies there at
+# (oy >> l, ox >> l) with its own level-l size.  That always fits: a reader's level l has ceil(h / 2^l) rows, oy is a
+# multiple of 2^l, so the scene ends at row oy / 2^l + ceil(h / 2^l) = ceil((oy + h) / 2^l) <= ceil(H / 2^l); columns
+# likewise.  stack_levels and stack_parts are the planning, pure Python.
+REDUCE = {"first": 0, "last": 1, "mean": 2, "median": 3}          # DSIC_COMPOSITE_* of include/dsic_hip.h
+MAX_SCENES = 16
+
+
+def _offsets(offsets, n, what):
+    if offsets is None:
+        return [(0, 0)] * n
+    try:
+        offsets = [tuple(operator.index(v) for v in pair) for pair in offsets]
+    except TypeError:
+        raise ValueError(f"{what}: offsets={offsets!r} is not a sequence of integer pairs (oy, ox)") from None
+    if len(offsets) != n or any(len(pair) != 2 or min(pair) < 0 for pair in offsets):
+        raise ValueError(f"{what}: offsets={offsets!r} must hold one pair (oy, ox) >= 0 for each of the {n} scenes")
+    return offsets
+
+
+def stack_levels(level_lists, offsets=None, shape=None) -> list:
+    """The level shapes [(H, W), ...] of a stack (pure Python).  level_lists: per scene the list of its reader's level
+    shapes, level 0 first; offsets: per scene its level-0 position (oy, ox) >= 0 in the stack's grid, default all
+    (0, 0); shape: (H, W) of the grid, default the bounding box of the scenes.  The stack has L levels, the largest
+    number such that every scene has at least L levels and every offset is a multiple of 2^(L-1); the result is
+    overview_shapes(H, W, L - 1).  ValueError for no scene or more than 16, and for a scene that leaves the grid."""
+    what = "stack_levels"
+    level_lists = [[(int(h), int(w)) for h, w in levels] for levels in level_lists]
+    if not 1 <= len(level_lists) <= MAX_SCENES or not all(level_lists):
+        raise ValueError(f"{what}: {len(level_lists)} scenes (1 .. {MAX_SCENES}, each with at least one level)")
+    offsets = _offsets(offsets, len(level_lists), what)
+    box = (max(oy + lv[0][0] for (oy, _), lv in zip(offsets, level_lists)),
+           max(ox + lv[0][1] for (_, ox), lv in zip(offsets, level_lists)))
+    if shape is None:
+        shape = box
+    H, W = _check_size(shape, what)
+    if box[0] > H or box[1] > W:
+        raise ValueError(f"{what}: the scenes reach to ({box[0]}, {box[1]}), outside the {H}x{W} grid")
+    L = min(len(lv) for lv in level_lists)
+    while L > 1 and any(v % (1 << (L - 1)) for pair in offsets for v in pair):
+        L -= 1
+    return _c.overview_shapes(H, W, L - 1)
+
+
+def stack_parts(level, scenes, window) -> list:
+    """The scenes a window of a stack's level meets (pure Python).  scenes: per scene ((oy, ox), level shapes), as
+    stack_levels takes them; window = (y0, x0, h, w) in the grid of `level`.  Per scene that meets the window, in list
+    order: (scene number, the scene's own window (sy, sx, h, w) of its level `level`, the rect (dy, dx, h, w) of that
+    part inside the window)."""
+    y0, x0, h, w = (operator.index(v) for v in window)
+    parts = []
+    for s, ((oy, ox), levels) in enumerate(scenes):
+        sy, sx = oy >> level, ox >> level
+        sh, sw = levels[level]
+        ya, yb, xa, xb = max(y0, sy), min(y0 + h, sy + sh), max(x0, sx), min(x0 + w, sx + sw)
+        if ya < yb and xa < xb:
+            parts.append((s, (ya - sy, xa - sx, yb - ya, xb - xa), (ya - y0, xa - x0, yb - ya, xb - xa)))
+    return parts
+
+
+class SceneStack:
+    """Several open ImageReaders as one picture: SceneStack(readers, offsets=None, shape=None).
+    readers: 1 .. 16 open ImageReaders of one integer kind (uint8 or uint16) and one band count; a float32-kind stream
+    is a ValueError.  offsets: one (oy, ox) >= 0 per reader, the level-0 position of that scene in the stack's grid;
+    the default, all (0, 0), is a temporal stack.  shape: (H, W) of the grid, default the bounding box; a scene that
+    leaves it is a ValueError.  levels: the level shapes stack_levels gives.  The stack does not own the readers: it
+    closes none, and a read through a closed one is the reader's ValueError."""
+
+    def __init__(self, readers, offsets=None, shape=None):
+        what = "SceneStack"
+        self.readers = list(readers)
+        if not 1 <= len(self.readers) <= MAX_SCENES:
+            raise ValueError(f"{what}: {len(self.readers)} readers (1 .. {MAX_SCENES})")
+        kinds = {r.kind for r in self.readers}
+        if kinds - {_c.KIND_U8_HWC, _c.KIND_U16_HWC}:
+            raise ValueError(f"{what}: a float32-kind stream; a stack holds uint8 or uint16 scenes")
+        if len(kinds) != 1 or len({r.shape[2] for r in self.readers}) != 1:
+            raise ValueError(f"{what}: the readers must be of one kind and one band count, got "
+                             f"{[('u16' if r.kind == _c.KIND_U16_HWC else 'u8', r.shape[2]) for r in self.readers]}")
+        self.kind, self.C = kinds.pop(), self.readers[0].shape[2]
+        self.offsets = _offsets(offsets, len(self.readers), what)
+        self._scenes = [(o, r.levels) for o, r in zip(self.offsets, self.readers)]
+        self.levels = stack_levels([lv for _, lv in self._scenes], self.offsets, shape)
+        self._dev = self.readers[0]._dev
+        self._dtype = torch.uint16 if self.kind == _c.KIND_U16_HWC else torch.uint8
+
+    @property
+    def shape(self):
+        return self.levels[0] + (self.C,)
+
+    def _check_window(self, what, window, level, reduce):
+        try:
+            level = operator.index(level)
+            window = tuple(operator.index(v) for v in window)
+        except TypeError:
+            raise ValueError(f"{what}: window {window!r}, level={level!r}: not integers") from None
+        if not 0 <= level < len(self.levels):
+            raise ValueError(f"{what}: level={level}: the stack holds levels 0 .. {len(self.levels) - 1}")
+        if reduce not in REDUCE:
+            raise ValueError(f"{what}: reduce={reduce!r} ({', '.join(REDUCE)})")
+        y0, x0, h, w = window
+        H, W = self.levels[level]
+        if y0 < 0 or x0 < 0 or h < 1 or w < 1 or y0 + h > H or x0 + w > W:
+            raise ValueError(f"{what}: window {h}x{w} at ({y0}, {x0}) is empty or outside the {H}x{W} level {level}")
+        return level, window
+
+    def _composite(self, window, level, reduce, fill, with_valid, with_count, stats):
+        """One window of a level -> (image, its uint8 validity or None, its uint8 counts or None)."""
+        _, _, h, w = window
+        top = 65535 if self.kind == _c.KIND_U16_HWC else 255
+        try:
+            fill = operator.index(fill)
+        except TypeError:
+            raise ValueError(f"SceneStack: fill={fill!r} is not an integer") from None
+        if not 0 <= fill <= top:
+            raise ValueError(f"SceneStack: fill={fill} must be in 0 .. {top}")
+        parts = stack_parts(level, self._scenes, window)
+        total = dict(_new_stats(), parts=len(parts))
+        srcs = []
+        for s, part, rect in parts:
+            r = self.readers[s]
+            before, st = r._source.bytes_read, _new_stats()
+            r._level(level)
+            img, valid = r._source_window(level, part, None, st)   # reader.read(*part, level=level, with_valid=True)
+            r._finish(st, before, None)
+            for key in _COUNTERS:
+                total[key] += st[key]
+            total["tiles"] += [(s,) + t for t in st["tiles"]]
+            srcs.append((img, valid, rect, r._open[level][1].get("nodata", -1)))
+        if stats is not None:
+            stats.update(total)
+        if not srcs:                                               # no scene under the window: nothing to launch
+            img = torch.from_numpy(np.full((h, w, self.C), fill, dtype=np.uint16 if top == 65535 else np.uint8)).to(self._dev)
+            zeros = lambda want: torch.zeros((h, w), dtype=torch.uint8, device=self._dev) if want else None
+            return img, zeros(with_valid), zeros(with_count)
+        n = len(srcs)
+        dst = torch.empty((h, w, self.C), dtype=self._dtype, device=self._dev)
+        dval = torch.empty((h, w), dtype=torch.uint8, device=self._dev) if with_valid else None
+        dcnt = torch.empty((h, w), dtype=torch.uint8, device=self._dev) if with_count else None
+        what = "window_composite" + ("_u16" if top == 65535 else "_u8")
+        status = getattr(_lib.load(), "dsic_" + what)(
+            (ctypes.c_void_p * n)(*[_p(img) for img, _, _, _ in srcs]), (ctypes.c_void_p * n)(*[_opt(v) for _, v, _, _ in srcs]),
+            (ctypes.c_int * (4 * n))(*[v for _, _, rect, _ in srcs for v in rect]),
+            (ctypes.c_int * n)(*[nd for _, _, _, nd in srcs]), n, self.C, _p(dst), _opt(dval), _opt(dcnt), h, w,
+            REDUCE[reduce], fill, _stream())
+        _lib.check(status, what)
+        return dst, dval, dcnt
+
+    @torch.no_grad()
+    def read(self, y0, x0, h, w, level=0, reduce="first", fill=0, with_valid=False, with_count=False, stats=None):
+        """The window rows [y0, y0+h) x columns [x0, x0+w) of the stack's level `level`, in that level's own grid:
+        [h, w, C] of the readers' kind on the device.  Every scene that meets the window serves its part through its
+        own reader and cache, exactly what reader.read(*part, level=level, with_valid=True) returns; a stream with a
+        validity mask brings its validity, a nodata stream (version 5) its nodata value, which is compared by the
+        kernel.  One launch (dsic_window_composite_u8 / _u16) then takes, per pixel, the scenes that are valid there,
+        in the order of `readers`: reduce = "first" or "last" the pixel of the first or last of them, "mean" per band
+        their mean rounded half up, "median" per band their median (an even count: the mean of the two middle values,
+        rounded half up).  A pixel under no valid scene is `fill` in every band.  A window that no scene meets launches
+        nothing and is a filled tensor.
+        A result of level l is the composite of the scenes' level-l pixels.  It is not the halving of the level-0
+        composite: median and halving do not commute, nor do first and halving where validity differs.
+        with_valid adds valid, torch.bool [h, w]: whether any scene counted; with_count adds count, torch.uint8
+        [h, w]: how many did.  The order is (image, valid, count).
+        stats (a dict) receives the sum of the readers' counters of this call (hits, decoded, decode_batches,
+        bytes_read, bytes_uploaded), tiles as (scene, level, tile) and parts, the number of scenes that met the window.
+        ValueError for a window that is empty or outside the level, a level the stack does not hold, an unknown
+        reduce, a fill beyond the kind, and whatever a reader raises (a closed one among it)."""
+        level, window = self._check_window("SceneStack.read", (y0, x0, h, w), level, reduce)
+        img, valid, count = self._composite(window, level, reduce, fill, with_valid, with_count, stats)
+        out = (img,) + ((valid.bool(),) if with_valid else ()) + ((count,) if with_count else ())
+        return out if len(out) > 1 else img
+
+    @torch.no_grad()
+    def render(self, y0, x0, h, w, level=0, reduce="first", bands=None, stretch=None, alpha=False, background=0):
+        """read(y0, x0, h, w, level, reduce) as display pixels: torch.uint8 [h, w, nb (+ 1)].  The composite with its
+        validity goes through one dsic_window_render_u8 / _u16 call at identity geometry (shift 0, region = the
+        window, size (h, w), nearest), so the display pixels are ImageReader.render's: bands, stretch, alpha and
+        background mean what they mean there, and a pixel under no valid scene is background, alpha 0.
+        stretch = None is (0, 255) per band for a uint8 stack; a uint16 stack has no histogram of its own and needs a
+        stretch: a ValueError without one."""
+        what = "SceneStack.render"
+        level, window = self._check_window(what, (y0, x0, h, w), level, reduce)
+        top = 65535 if self.kind == _c.KIND_U16_HWC else 255
+        bands, stretch, background = _display_args(what, self.C, top, bands, stretch, background)
+        if stretch is None:
+            if top == 65535:
+                raise ValueError(f"{what}: a uint16 stack needs stretch=: it has no histogram of its own (a reader's "
+                                 "stretch() gives one scene's)")
+            stretch = [(0, 255)] * self.C
+        alpha = int(bool(alpha))
+        img, valid, _ = self._composite(window, level, reduce, 0, True, False, None)
+        y0, x0, h, w = window
+        dst = torch.empty((h, w, len(bands) + alpha), dtype=torch.uint8, device=self._dev)
+        _call_by_width("window_render", img, _p(valid), h, w, y0, x0, self.C, 0, y0, x0, h, w,
+                       (ctypes.c_int * len(bands))(*bands), len(bands), _c._lohi(stretch), _p(dst), h, w,
+                       RESAMPLING["nearest"], -1, alpha, background, _stream())
+        return dst

@@ -997,6 +997,47 @@ int dsic_index_histogram_u16(const uint16_t* img_hwc, const uint8_t* valid_hw, i
                              int nodata, int kind, int band_a, int band_b, uint32_t* hist,
                              void* stream);
 
+/* ---- scene stacks (codec.SceneStack.read, .render): n placed windows into one ----
+ * dsic_window_composite_u8 / _u16: a mosaic or a per-pixel composite of n source windows in one
+ *   launch, without a workspace.  src, src_valid, rect and nodata are host arrays of n entries,
+ *   read before the call returns.  src[i] is a dense device window [h_i][w_i][C]; src_valid[i] is
+ *   NULL or uint8 [h_i][w_i], 0 = invalid; rect[4 i .. 4 i + 3] = (dy, dx, h, w) is where source i
+ *   lies inside the oh x ow output: sources may overlap and may leave holes; nodata[i] is -1 for
+ *   none, or a pixel value: a pixel of source i whose C channels all equal it is invalid.
+ *   The candidates of output pixel p are the sources i, in list order, whose rect contains p,
+ *   whose src_valid, if given, is not zero at p, and in which p is not nodata; k is their number.
+ *
+ *   mode                        result, all integer
+ *   DSIC_COMPOSITE_FIRST   0    the pixel of the first candidate
+ *   DSIC_COMPOSITE_LAST    1    the pixel of the last candidate
+ *   DSIC_COMPOSITE_MEAN    2    per band (2 S + k) / (2 k), S the sum over the candidates: S / k
+ *                               rounded half up; 2 * 16 * 65535 + 16 < 2^32
+ *   DSIC_COMPOSITE_MEDIAN  3    per band, the bands on their own: of the candidates' values sorted
+ *                               as v[0 .. k-1], v[(k - 1) / 2] for odd k and
+ *                               (v[k / 2 - 1] + v[k / 2] + 1) >> 1 for even k
+ *
+ *   k = 0 gives fill in every band.  dst_hwc is [oh][ow][C]; dst_valid (NULL: not wanted), uint8
+ *   [oh][ow], receives k > 0 as 1 or 0; dst_count (NULL: not wanted), uint8 [oh][ow], receives k.
+ *   All buffers at any element alignment.  first and last read validity bytes (of a source with a
+ *   nodata value: its pixels) up to the winner and the winner's pixel, and with dst_count the
+ *   validity of the whole list; mean and median read every candidate's pixel.
+ *   DSIC_EINVAL, nothing written: n outside 1..16; C outside 1..4; oh or ow under 1 or
+ *   oh ow >= 2^31; a null array, a null src[i] or a null dst_hwc; a rect with h or w under 1 or not
+ *   inside the output; mode outside 0..3; fill or a nodata[i] beyond the element type; an output
+ *   overlapping an input or another output. */
+#define DSIC_COMPOSITE_FIRST 0
+#define DSIC_COMPOSITE_LAST 1
+#define DSIC_COMPOSITE_MEAN 2
+#define DSIC_COMPOSITE_MEDIAN 3
+int dsic_window_composite_u8(const uint8_t* const* src, const uint8_t* const* src_valid,
+                             const int* rect, const int* nodata, int n, int C, uint8_t* dst_hwc,
+                             uint8_t* dst_valid, uint8_t* dst_count, int oh, int ow, int mode,
+                             int fill, void* stream);
+int dsic_window_composite_u16(const uint16_t* const* src, const uint8_t* const* src_valid,
+                              const int* rect, const int* nodata, int n, int C, uint16_t* dst_hwc,
+                              uint8_t* dst_valid, uint8_t* dst_count, int oh, int ow, int mode,
+                              int fill, void* stream);
+
 /* HIP stream limited to the CUs whose bit is set in mask_host[words] (bit i of
  * word i/32 = CU i).  Used to give the range coder its own few CUs beside the
  * conv kernels; there is no reference counterpart (the reference is

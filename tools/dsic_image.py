@@ -15,6 +15,9 @@ an image.
                                           [--index KIND:A[,B] [--colormap NAME] [--index-stretch LO,HI | --percent P0,P1]]
                                           [--rotate DEG [--center Y,X] [--scale S] | --affine M00,M01,M02,M10,M11,M12]
                                           [--resampling bilinear|cubic|nearest]
+    python tools/dsic_image.py composite  --weights CKPT.pt OUT --scene FILE[@Y,X] [--scene FILE[@Y,X] ...]
+                                          [--reduce first|last|mean|median] [--region Y0,X0,H,W] [--level L] [--fill V]
+                                          [--count-out FILE.npy] [--valid-out FILE.npy]
     python tools/dsic_image.py info       IN.dsic
 
 --segments K (2, 4, 8 or 16) codes every tile's y string as K independent strings, which a decoder reads on K waves per
@@ -66,6 +69,13 @@ the image's centre), the image turned counter-clockwise by DEG degrees, at --sca
 order, level-0 pixels per output pixel.  Such a view is sampled with --resampling bilinear (the default), cubic or
 nearest from the level its scale asks for (or --level L); pixels outside the image are fill (render: --background, and
 alpha 0).  --region does not go with it.
+composite writes a window of a scene stack (codec.SceneStack.read): every --scene FILE[@Y,X] (1 .. 16 streams of one
+integer kind and one band count) is a scene whose level-0 position in the stack's grid is Y,X (default 0,0; all at 0,0
+is a temporal stack), the grid is their bounding box, and each pixel is the --reduce (first, the default, last, mean or
+median) of the scenes that are valid there, in the order given; a pixel under no valid scene is --fill V (default 0).
+--region (default: the whole level) is in --level's own pixels; --level L needs L + 1 levels in every stream and
+offsets that are multiples of 2^L.  --count-out FILE.npy writes how many scenes counted per pixel (uint8 [h,w]),
+--valid-out FILE.npy whether any did (bool [h,w]).  OUT follows decompress's conventions.
 
 The state dict is loaded plain or from under "model" (code/modelv2/eval_selfcontained_entropy.py:130-134); the model's
 N, M, input channels and spatial_params are read from its shapes.  Images are PNG through PIL when PIL is importable
@@ -369,6 +379,52 @@ def render_index_main(a, model, index, pair, region, size, level_given, matrix):
           + f": {len(stats['tiles'])} tile(s) -> {path}")
 
 
+def composite_main(a, ap, region):
+    """composite: a window of the stack of --scene's streams -> OUT (a.src), with the optional count and validity."""
+    import contextlib
+
+    import numpy as np
+    import torch
+    from dsic_amd import codec
+    if a.dst is not None or not a.scene or a.weights is None:
+        ap.error("composite needs OUT, --weights and at least one --scene FILE[@Y,X]")
+    for path in (a.count_out, a.valid_out):
+        if path is not None and not path.endswith(".npy"):
+            ap.error("--count-out and --valid-out take FILE.npy")
+    files, offsets = [], []
+    for text in a.scene:
+        path, _, pos = text.rpartition("@")
+        try:
+            oy, ox = (int(v) for v in pos.split(","))
+        except ValueError:
+            path, oy, ox = text, 0, 0                                      # no position: the text is the file's name
+        files.append(path)
+        offsets.append((oy, ox))
+    model = load_model(a.weights, a.min_nu, a.max_nu)
+    with contextlib.ExitStack() as held:
+        readers = [held.enter_context(codec.ImageReader(model, held.enter_context(open(f, "rb")), batch=a.batch))
+                   for f in files]
+        try:
+            stack = codec.SceneStack(readers, offsets)
+            if region is None:
+                region = (0, 0) + tuple(stack.levels[min(max(a.level, 0), len(stack.levels) - 1)])
+            stats = {}
+            img, valid, count = stack.read(*region, level=a.level, reduce=a.reduce, fill=a.fill or 0, with_valid=True,
+                                           with_count=True, stats=stats)
+        except ValueError as e:
+            ap.error(str(e))
+    if img.dtype != torch.uint8 and not a.src.endswith(".npy"):
+        ap.error(f"{a.src}: a uint16 image is written as .npy only")
+    path = write_image(a.src, img)
+    print(f"[dsic_image] {a.reduce} of {len(files)} scene(s) on a {stack.levels[0][0]}x{stack.levels[0][1]} grid, "
+          f"{len(stack.levels)} level(s): window {region[2]}x{region[3]} at ({region[0]}, {region[1]}) of level {a.level}, "
+          f"{stats['parts']} scene(s) met, {len(stats['tiles'])} tile(s), {int(valid.sum())} valid pixel(s) -> {path}")
+    if a.count_out is not None:
+        np.save(a.count_out, count.cpu().numpy())
+    if a.valid_out is not None:
+        np.save(a.valid_out, valid.cpu().numpy())
+
+
 def print_info(ix):
     """stream_index's dict as text: geometry, tile grid, and bytes / bpp of every batch (bpp over the pixels its tiles
     own).  For a level of a DSICP stream the bytes and bpp of the first line are the whole pyramid's over the pixels
@@ -414,7 +470,7 @@ def print_info(ix):
 
 def main(argv=None):
     ap = argparse.ArgumentParser(description=__doc__.splitlines()[0])
-    ap.add_argument("mode", choices=("compress", "decompress", "render", "info"))
+    ap.add_argument("mode", choices=("compress", "decompress", "render", "composite", "info"))
     ap.add_argument("src")
     ap.add_argument("dst", nargs="?")
     ap.add_argument("--weights")
@@ -473,6 +529,12 @@ def main(argv=None):
                          "--index-stretch=LO,HI")
     ap.add_argument("--alpha", action="store_true", help="render: add the validity mask as an alpha channel")
     ap.add_argument("--background", type=int, default=0, metavar="V", help="render: what invalid pixels show (0 .. 255)")
+    ap.add_argument("--scene", action="append", default=None, metavar="FILE[@Y,X]",
+                    help="composite: a scene's stream and its level-0 position in the stack's grid (default 0,0); repeatable")
+    ap.add_argument("--reduce", choices=("first", "last", "mean", "median"), default="first",
+                    help="composite: what a pixel takes from the scenes that are valid there")
+    ap.add_argument("--count-out", default=None, metavar="FILE.npy",
+                    help="composite: also write how many scenes counted per pixel, uint8 [h,w]")
     ap.add_argument("--min-nu", type=float, default=2.0)
     ap.add_argument("--max-nu", type=float, default=100.0)
     a = ap.parse_args(argv)
@@ -492,7 +554,9 @@ def main(argv=None):
                       f"{tiles} tile(s)" + masked)
             print_info(ix)
         return
-    if a.dst is None or a.weights is None:
+    if a.mode != "composite" and (a.scene is not None or a.reduce != "first" or a.count_out is not None):
+        ap.error("--scene, --reduce and --count-out go with composite")
+    if a.mode != "composite" and (a.dst is None or a.weights is None):
         ap.error(f"{a.mode} needs a destination and --weights")
     region = None
     if a.region is not None:
@@ -500,8 +564,8 @@ def main(argv=None):
             region = [int(v) for v in a.region.split(",")]
         except ValueError:
             region = []
-        if a.mode not in ("decompress", "render") or len(region) != 4:
-            ap.error("--region Y0,X0,H,W (four integers) goes with decompress or render")
+        if a.mode not in ("decompress", "render", "composite") or len(region) != 4:
+            ap.error("--region Y0,X0,H,W (four integers) goes with decompress, render or composite")
     size = None
     if a.size is not None:
         try:
@@ -513,6 +577,11 @@ def main(argv=None):
             ap.error("--size OH,OW (two integers) goes with decompress --region, --rotate or --affine, or with render")
     if a.scale is not None and a.mode != "compress" and a.rotate is None:
         ap.error("--scale goes with compress, or with --rotate")
+    if a.mode == "composite":
+        if (size is not None or a.rotate is not None or a.affine is not None or a.valid is not None or a.out is not None
+                or a.bands is not None or a.stretch is not None or a.index is not None or a.alpha):
+            ap.error("composite takes --scene, --reduce, --region, --level, --fill, --count-out and --valid-out")
+        return composite_main(a, ap, region)
     matrix = warp_matrix(a, ap, region, size)
     if (a.valid is not None or a.fill is not None) and a.mode != "compress":
         ap.error("--valid and --fill go with compress")

@@ -1,6 +1,6 @@
 """Pan and zoom: codec.ImageReader against one decompress_region call per frame, and the resampling kernel alone.
 
-    python tools/view_bench.py [--size 4096] [--tile 256] [--reps 3] [--json profiles/view_bench.json] [--only warp|index]
+    python tools/view_bench.py [--size 4096] [--tile 256] [--reps 3] [--json profiles/view_bench.json] [--only warp|index|composite]
 
 The scene of image_codec_bench.py (synthetic patches side by side, uint8) is coded once with overviews=3.  A viewport
 of 768 rows x 1024 columns pans right in 32 steps of 64 pixels (33 frames).  Per frame, alternately in one process:
@@ -29,6 +29,14 @@ as a call (the median wall clock of 30, the order rotating) and as its kernel al
 index_histogram(("nd", 0, 1)) and (("difference", 0, 1)) beside histogram through fresh readers on the coarsest and the
 full level, with the kernels alone on the full level, scene and constant image.  --only index measures that record
 alone.
+composite (--only composite alone; --size 1024 is the measured one): 16 uint16 x 4 synthetic scenes of --size, each with
+a validity mask of its own (blocks of 64 x 64 pixels, six in ten valid), coded once, as temporal stacks of the first 4,
+8 and 16.  Per n and mode: SceneStack.read of the whole grid from warm caches (the median wall clock of 7 calls, the
+readers' window assembly included), dsic_window_composite_u16 alone on the readers' windows (device events, as above),
+the bytes that launch must move (the validity bytes it has to look at, the pixels it needs, the image it writes), and
+the same image built with torch.where / torch.sort on the padded int32 stack [n, H, W, C] (built outside the timing;
+checked equal once).  Those windows fit the caches, so the kernel and the torch expression are timed again on 16
+random 4096 x 4096 x 4 sources with masks of the same kind: 2 GB of pixels, past the 256 MB Infinity Cache.
 Records, not bars."""
 from __future__ import annotations
 
@@ -201,6 +209,110 @@ def _index_record(model, stream, img, win, batch, rounds=30):
     return rec
 
 
+def _composite_kernels(imgs, masks, size, C, reads=None):
+    """dsic_window_composite_u16 alone on n = 4, 8, 16 full-cover sources (imgs uint16 [size, size, C], masks uint8
+    [size, size]) per mode, the bytes it must move, and the same image from torch on the padded int32 stack.
+    reads: n -> mode -> the image a SceneStack returned for the same sources, held equal to both."""
+    import torch
+    from dsic_amd import lib
+    from dsic_amd.ops import _p, _stream
+    L, out, big = lib.load(), {}, 1 << 20
+    dst = torch.empty((size, size, C), dtype=torch.uint16, device="cuda")
+    for n in (4, 8, 16):
+        vals = torch.stack([i.view(torch.int16).to(torch.int32) & 0xFFFF for i in imgs[:n]])   # int32 [n, H, W, C]
+        ok = torch.stack(masks[:n]).bool()
+        k = ok.sum(0)
+        src = (ctypes.c_void_p * n)(*[_p(i) for i in imgs[:n]])
+        sv = (ctypes.c_void_p * n)(*[_p(m) for m in masks[:n]])
+        rect, nodata = (ctypes.c_int * (4 * n))(*([0, 0, size, size] * n)), (ctypes.c_int * n)(*([-1] * n))
+        first = torch.where(k > 0, ok.int().argmax(0) + 1, n)                               # sources looked at up to the winner
+        last = torch.where(k > 0, ok.flip(0).int().argmax(0) + 1, n)
+        px, out_bytes = 2 * C, size * size * 2 * C
+        need = {"first": (int(first.sum()), px * int((k > 0).sum())), "last": (int(last.sum()), px * int((k > 0).sum())),
+                "mean": (n * size * size, px * int(k.sum())), "median": (n * size * size, px * int(k.sum()))}
+
+        def by_torch(mode):
+            if mode in ("first", "last"):
+                img = torch.zeros_like(vals[0])
+                for i in (range(n - 1, -1, -1) if mode == "first" else range(n)):
+                    img = torch.where(ok[i][..., None], vals[i], img)
+                return img
+            kk = k.clamp(min=1)[..., None]
+            if mode == "mean":
+                return torch.where(k[..., None] > 0, (2 * (vals * ok[..., None]).sum(0) + kk) // (2 * kk), 0)
+            v = torch.sort(torch.where(ok[..., None], vals, big), dim=0).values
+            at = lambda idx: torch.gather(v, 0, idx.expand(1, size, size, C))[0]
+            return torch.where(k[..., None] > 0, (at(((kk - 1) // 2)[None]) + at((kk // 2)[None]) + 1) >> 1, 0)
+
+        for mode, code in (("first", 0), ("last", 1), ("mean", 2), ("median", 3)):
+            def launch(code=code):
+                lib.check(L.dsic_window_composite_u16(src, sv, rect, nodata, n, C, _p(dst), None, None, size, size, code, 0,
+                                                      _stream()), "window_composite_u16")
+            launch()
+            want = by_torch(mode)
+            assert torch.equal(dst.view(torch.int16).to(torch.int32) & 0xFFFF, want), (n, mode)
+            if reads is not None:
+                assert torch.equal(reads[n][mode].view(torch.int16).to(torch.int32) & 0xFFFF, want), (n, mode)
+            del want
+            torch_ms = sorted(_frame_ms(lambda: by_torch(mode)) for _ in range(5))[2]
+            us = _per_launch_us(launch, n=20)
+            moved = sum(need[mode]) + out_bytes
+            out[f"n={n} {mode}"] = {"kernel_ms": round(us / 1e3, 4), "bytes_validity": need[mode][0], "bytes_pixels": need[mode][1],
+                                    "bytes_output": out_bytes, "GB_per_s": round(moved / us / 1e3, 1),
+                                    "torch_median_ms": round(torch_ms, 3), "torch_over_kernel": round(torch_ms * 1e3 / us, 1)}
+        del vals, ok
+    return out
+
+
+def _block_masks(size, rng, n=16):
+    import numpy as np
+    import torch
+    return [torch.from_numpy(np.kron(rng.random((size // 64, size // 64)) < 0.6, np.ones((64, 64), dtype=bool))).cuda()
+            for _ in range(n)]
+
+
+def _composite_record(size, tile, batch, kernel_size=4096):
+    """The `composite` record: see the module's docstring."""
+    import numpy as np
+    import torch
+    from dsic_amd import codec
+    from dsic_amd import synthetic as S
+    from dsic_amd.model import CompressionModel
+    sd = S.make_state_dict(seed=1, N=128, M=192, in_ch=4, spatial_params=False)
+    model = CompressionModel(N=128, M=192, spatial_params=False, min_nu=2, max_nu=100.0, in_ch=4)
+    model.load_state_dict({k: torch.from_numpy(v) for k, v in sd.items()}, strict=True)
+    model = model.cuda().eval()
+    per, C, rng = size // tile, 4, np.random.default_rng(11)
+    streams = []
+    for s, valid in enumerate(_block_masks(size, rng)):
+        p = S.make_patches(1000 * s, per * per, tile, tile, C)
+        scene = p.reshape(per, per, C, tile, tile).transpose(0, 3, 1, 4, 2).reshape(size, size, C) * 10000 + 0.5
+        streams.append(codec.compress_image(model, torch.from_numpy(scene.astype(np.uint16)).cuda(), tile=tile, batch=batch,
+                                            scale=[(0, 12000)] * C, valid=valid, fill=0))
+    readers = [codec.ImageReader(model, st, batch=batch) for st in streams]
+    window = (0, 0, size, size)
+    parts = [r.read(*window, with_valid=True) for r in readers]
+    rec = {"scenes": f"16 of {size}x{size} uint16 x {C}, tile {tile}, a validity mask each", "read": {}}
+    reads = {}
+    for n in (4, 8, 16):
+        stack = codec.SceneStack(readers[:n])
+        reads[n] = {mode: stack.read(*window, reduce=mode) for mode in ("first", "last", "mean", "median")}
+        for mode in reads[n]:
+            calls = sorted(_frame_ms(lambda: stack.read(*window, reduce=mode)) for _ in range(7))
+            rec["read"][f"n={n} {mode}"] = {"read_median_ms": round(calls[3], 3)}
+    rec["kernel_on_the_scenes"] = _composite_kernels([p[0] for p in parts], [p[1].to(torch.uint8) for p in parts], size, C, reads)
+    for r in readers:
+        r.close()
+    del parts, reads
+    # past the caches: 16 sources of kernel_size^2 are 2 GB of pixels, against 256 MB of Infinity Cache
+    imgs = [torch.randint(0, 10001, (kernel_size, kernel_size, C), dtype=torch.int32, device="cuda").to(torch.int16)
+            .view(torch.uint16) for _ in range(16)]
+    masks = [m.to(torch.uint8) for m in _block_masks(kernel_size, rng)]
+    rec["kernel_size"] = kernel_size
+    rec["kernel_past_the_caches"] = _composite_kernels(imgs, masks, kernel_size, C)
+    return rec
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--size", type=int, default=4096)
@@ -208,7 +320,7 @@ def main():
     ap.add_argument("--batch", type=int, default=64)
     ap.add_argument("--reps", type=int, default=3)
     ap.add_argument("--json", default=os.path.join(ROOT, "profiles", "view_bench.json"))
-    ap.add_argument("--only", choices=("warp", "index"), default=None,
+    ap.add_argument("--only", choices=("warp", "index", "composite"), default=None,
                     help="measure this record alone and put it into the --json file beside the others")
     a = ap.parse_args()
 
@@ -221,6 +333,16 @@ def main():
 
     if not torch.cuda.is_available():
         raise SystemExit("view_bench: no GPU; nothing is measured without one")
+    if a.only == "composite":                                              # scenes of its own: nothing below is needed
+        res = {}
+        if os.path.exists(a.json):
+            with open(a.json) as f:
+                res = json.load(f)
+        res["composite"] = _composite_record(a.size, a.tile, a.batch)
+        print(json.dumps(res["composite"]))
+        with open(a.json, "w") as f:
+            json.dump(res, f, indent=1)
+        return
     sd = S.make_state_dict(seed=1)
     model = CompressionModel(N=128, M=192, spatial_params=False, min_nu=2, max_nu=100.0)
     model.load_state_dict({k: torch.from_numpy(v) for k, v in sd.items()}, strict=True)
