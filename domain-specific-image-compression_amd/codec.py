@@ -90,7 +90,8 @@ version-8 stream of its own image and mask, with level 0's fill and scale.
 ImageReader (view.py) keeps a stream open for pan and zoom: levels opened once, decoded tiles cached on the device and
 assembled by the calls decompress_region makes (_assemble_window), requests decoded together (read_many), and windows
 resampled to a size asked for from the level view_level picks (csrc/view.hip).  SceneStack (view.py) places several
-readers on one grid and composites their windows per pixel in one launch (csrc/composite.hip).
+readers on one grid and composites their windows per pixel in one launch (csrc/composite.hip): first, last, mean,
+median, or the whole pixel of the scene whose index is largest or smallest (stack_reduce names the forms).
 """
 from __future__ import annotations
 
@@ -1475,4 +1476,4 @@ def decompress_valid(src, y0=0, x0=0, h=None, w=None, level=0, device="cuda"):
 from .view import ImageReader, stretch_from_histogram, view_level  # noqa: E402  (view.py builds on the functions above)
 from .view import affine_q16, rotation_affine, warp_level, warp_window, window_affine  # noqa: E402
 from .view import COLORMAPS, colormap_from_anchors  # noqa: E402
-from .view import SceneStack, stack_levels, stack_parts  # noqa: E402
+from .view import SceneStack, stack_levels, stack_parts, stack_reduce  # noqa: E402

@@ -19,6 +19,14 @@
 //     than any sample, so the k candidates sort to the front).  The slots go through Batcher's odd-even merge network
 //     with packed 16-bit minima and maxima, two bands at a time, and the two middle slots are picked by compares against
 //     constants: no array is indexed by a variable, nothing goes to scratch.
+//   rank (max, min; dsic_window_composite_pick_u8 / _u16 alone): a candidate must also have a defined index
+//     (render.h's index_value of its bands a and b); the whole pixel of the candidate with the largest or smallest u,
+//     the first of equals.  Instantiated and unrolled as the median, every slot a register, in two passes: the
+//     validity bytes of the whole list, all in flight together, then per source that passed bands a and b (all bands
+//     of one with a nodata value) and the ranking, one unsigned compare, strict, walking front to back.  The winner's
+//     pixel is loaded alone.
+//   The source plane (dst_source of the pick exports): the id of the winner, 255 for k = 0.  The id of a source rides
+//     in the table entry (its last field, unused before); pick is instantiated a second time with the store.
 #include "common.h"
 #include "render.h"
 
@@ -26,12 +34,14 @@ namespace dsic {
 
 constexpr int COMPOSITE_MAX = 16;
 constexpr int COMPOSITE_FIRST = 0, COMPOSITE_LAST = 1, COMPOSITE_MEAN = 2, COMPOSITE_MEDIAN = 3;  // DSIC_COMPOSITE_*
+constexpr int COMPOSITE_RANK_MAX = 4, COMPOSITE_RANK_MIN = 5;  // DSIC_COMPOSITE_MAX, _MIN: the pick exports alone
+constexpr int COMPOSITE_NO_SOURCE = 255;                       // the source plane where k = 0
 constexpr int COMPOSITE_BX = 64, COMPOSITE_BY = 4;  // output pixels of a workgroup: 4 rows of 64
 
 struct CompositeSource {
   const void* px;        // [h][w][C]
   const uint8_t* valid;  // null, or [h][w]
-  int dy, dx, h, w, nodata, unused;
+  int dy, dx, h, w, nodata, id;  // id: what the source plane names the source by
 };
 
 struct CompositeTable {
@@ -75,19 +85,23 @@ __device__ __forceinline__ void composite_store(const uint32_t m[4], int k, int 
     const int i = (int)i64;                                                   \
     const int64_t at = (int64_t)i * ow + j;
 
-template <typename T, int C>
+// SRC: with the source plane dsrc (not null then)
+template <typename T, int C, bool SRC>
 __global__ __launch_bounds__(COMPOSITE_BX* COMPOSITE_BY) void composite_pick_kernel(
     CompositeTable tab, int n, int last, T* __restrict__ dst, uint8_t* __restrict__ dval, uint8_t* __restrict__ dcnt,
-    int oh, int ow, int fill, int bx, int64_t nblocks) {
+    uint8_t* __restrict__ dsrc, int oh, int ow, int fill, int bx, int64_t nblocks) {
   COMPOSITE_PIXEL_LOOP
     const T* win = nullptr;
-    int k = 0;
+    int k = 0, wid = COMPOSITE_NO_SOURCE;
     for (int t = 0; t < n; ++t) {
       const CompositeSource& e = tab.s[last ? n - 1 - t : t];
       int64_t q;
       if (live && (dcnt || !win) && composite_candidate<T, C>(e, i, j, &q)) {
         ++k;
-        if (!win) win = (const T*)e.px + q * C;
+        if (!win) {
+          win = (const T*)e.px + q * C;
+          if constexpr (SRC) wid = e.id;
+        }
       }
       if (!dcnt && !__builtin_amdgcn_ballot_w64(live && !win)) break;  // every lane of the wave has its winner
     }
@@ -98,6 +112,7 @@ __global__ __launch_bounds__(COMPOSITE_BX* COMPOSITE_BY) void composite_pick_ker
       for (int c = 0; c < C; ++c) m[c] = (uint32_t)win[c];
     }
     composite_store<T, C>(m, k, fill, at, dst, dval, dcnt);
+    if constexpr (SRC) dsrc[at] = (uint8_t)wid;
   }
 }
 
@@ -222,50 +237,141 @@ __global__ __launch_bounds__(COMPOSITE_BX* COMPOSITE_BY) void composite_median_k
   }
 }
 
+// max and min of the pick exports.  kind, a, b: the index (b = a for a band); smallest: min.  One workgroup per launch
+// block, as the median.
+template <typename T, int C, int N>
+__global__ __launch_bounds__(COMPOSITE_BX* COMPOSITE_BY) void composite_rank_kernel(
+    CompositeTable tab, int n, T* __restrict__ dst, uint8_t* __restrict__ dval, uint8_t* __restrict__ dcnt,
+    uint8_t* __restrict__ dsrc, int oh, int ow, int fill, int bx, int kind, int a, int b, int smallest) {
+  const int64_t blk = blockIdx.x, by = blk / bx;
+  const int j = (int)(blk - by * bx) * COMPOSITE_BX + threadIdx.x;
+  const int64_t i64 = by * COMPOSITE_BY + threadIdx.y;
+  if (i64 >= oh || j >= ow) return;
+  const int i = (int)i64;
+  const int64_t at = (int64_t)i * ow + j;
+  uint32_t ok[N];  // the lane's validity byte in source t, 0 outside its rect
+  // the validity bytes of the whole list, all in flight together
+#pragma unroll
+  for (int t = 0; t < N; ++t) {
+    ok[t] = 0u;
+    if (t < n) {
+      const CompositeSource& e = tab.s[t];
+      const int yy = i - e.dy, xx = j - e.dx;
+      if ((unsigned)yy < (unsigned)e.h && (unsigned)xx < (unsigned)e.w)
+        ok[t] = e.valid ? (uint32_t)e.valid[(int64_t)yy * e.w + xx] : 1u;
+    }
+  }
+  // bands a and b of every source that passed (of one with a nodata value all bands) and the ranking: r = u + 1 (max)
+  // or ~u (min) is at least 1 (u <= 131070), 0 stands for no candidate yet, and the strict compare keeps the first of
+  // equals
+  const uint32_t top = (uint32_t)(T)~(T)0;
+  const T* win = nullptr;
+  uint32_t best = 0u;
+  int k = 0, wid = COMPOSITE_NO_SOURCE;
+#pragma unroll
+  for (int t = 0; t < N; ++t) {
+    if (t < n && ok[t]) {
+      const CompositeSource& e = tab.s[t];
+      const T* p = (const T*)e.px + ((int64_t)(i - e.dy) * e.w + (j - e.dx)) * C;
+      const uint32_t A = (uint32_t)p[a], B = (uint32_t)p[b];
+      bool nd = e.nodata >= 0;
+      if (nd) {
+#pragma unroll
+        for (int c = 0; c < C; ++c) nd = nd && (int)p[c] == e.nodata;
+      }
+      uint32_t u;
+      if (!nd && index_value(kind, A, B, top, &u)) {
+        ++k;
+        const uint32_t r = smallest ? ~u : u + 1u;
+        if (r > best) best = r, win = p, wid = e.id;
+      }
+    }
+  }
+  uint32_t m[4] = {0u, 0u, 0u, 0u};
+  if (win) {
+#pragma unroll
+    for (int c = 0; c < C; ++c) m[c] = (uint32_t)win[c];
+  }
+  composite_store<T, C>(m, k, fill, at, dst, dval, dcnt);
+  if (dsrc) dsrc[at] = (uint8_t)wid;
+}
+
 #undef COMPOSITE_PIXEL_LOOP
 
+// The index of a ranked launch (kind, a, b: b = a for a band; nothing is read of it for the other modes).
+struct CompositeIndex {
+  int kind, a, b;
+};
+
 template <typename T, int C>
-static void composite_launch(const CompositeTable& tab, int n, T* dst, uint8_t* dval, uint8_t* dcnt, int oh, int ow,
-                             int mode, int fill, hipStream_t stream) {
+static void composite_launch(const CompositeTable& tab, int n, T* dst, uint8_t* dval, uint8_t* dcnt, uint8_t* dsrc, int oh,
+                             int ow, int mode, const CompositeIndex& ix, int fill, hipStream_t stream) {
   const int bx = (ow + COMPOSITE_BX - 1) / COMPOSITE_BX;
   const int64_t nblocks = (int64_t)bx * ((oh + COMPOSITE_BY - 1) / COMPOSITE_BY);
   // oh ow < 2^31: fewer than 2^31 workgroups of 4 rows of 64
   const dim3 grid = launch_grid(nblocks), every((unsigned)nblocks), block(COMPOSITE_BX, COMPOSITE_BY);
-  if (mode == COMPOSITE_FIRST || mode == COMPOSITE_LAST)
-    hipLaunchKernelGGL((composite_pick_kernel<T, C>), grid, block, 0, stream, tab, n, (int)(mode == COMPOSITE_LAST), dst,
-                       dval, dcnt, oh, ow, fill, bx, nblocks);
+  const int smallest = mode == COMPOSITE_RANK_MIN;
+  if ((mode == COMPOSITE_FIRST || mode == COMPOSITE_LAST) && dsrc)
+    hipLaunchKernelGGL((composite_pick_kernel<T, C, true>), grid, block, 0, stream, tab, n, (int)(mode == COMPOSITE_LAST),
+                       dst, dval, dcnt, dsrc, oh, ow, fill, bx, nblocks);
+  else if (mode == COMPOSITE_FIRST || mode == COMPOSITE_LAST)
+    hipLaunchKernelGGL((composite_pick_kernel<T, C, false>), grid, block, 0, stream, tab, n, (int)(mode == COMPOSITE_LAST),
+                       dst, dval, dcnt, dsrc, oh, ow, fill, bx, nblocks);
   else if (mode == COMPOSITE_MEAN)
     hipLaunchKernelGGL((composite_mean_kernel<T, C>), grid, block, 0, stream, tab, n, dst, dval, dcnt, oh, ow, fill, bx,
                        nblocks);
-  else if (n <= 4)
+  else if (mode == COMPOSITE_MEDIAN && n <= 4)
     hipLaunchKernelGGL((composite_median_kernel<T, C, 4>), every, block, 0, stream, tab, n, dst, dval, dcnt, oh, ow, fill,
                        bx);
-  else if (n <= 8)
+  else if (mode == COMPOSITE_MEDIAN && n <= 8)
     hipLaunchKernelGGL((composite_median_kernel<T, C, 8>), every, block, 0, stream, tab, n, dst, dval, dcnt, oh, ow, fill,
                        bx);
-  else
+  else if (mode == COMPOSITE_MEDIAN)
     hipLaunchKernelGGL((composite_median_kernel<T, C, 16>), every, block, 0, stream, tab, n, dst, dval, dcnt, oh, ow,
                        fill, bx);
+  else if (n <= 4)
+    hipLaunchKernelGGL((composite_rank_kernel<T, C, 4>), every, block, 0, stream, tab, n, dst, dval, dcnt, dsrc, oh, ow,
+                       fill, bx, ix.kind, ix.a, ix.b, smallest);
+  else if (n <= 8)
+    hipLaunchKernelGGL((composite_rank_kernel<T, C, 8>), every, block, 0, stream, tab, n, dst, dval, dcnt, dsrc, oh, ow,
+                       fill, bx, ix.kind, ix.a, ix.b, smallest);
+  else
+    hipLaunchKernelGGL((composite_rank_kernel<T, C, 16>), every, block, 0, stream, tab, n, dst, dval, dcnt, dsrc, oh, ow,
+                       fill, bx, ix.kind, ix.a, ix.b, smallest);
 }
 
+// Both families of exports.  pick: dsic_window_composite_pick_u8 / _u16, whose modes are first, last, max and min and
+// which take id, dsrc and the index; the other two pass null, null and nothing to read.
 template <typename T>
-static int composite(const char* what, const T* const* src, const uint8_t* const* src_valid, const int* rect,
-                     const int* nodata, int n, int C, T* dst, uint8_t* dval, uint8_t* dcnt, int oh, int ow, int mode,
-                     int fill, void* stream) {
+static int composite(const char* what, bool pick, const T* const* src, const uint8_t* const* src_valid, const int* rect,
+                     const int* nodata, const int* id, int n, int C, T* dst, uint8_t* dval, uint8_t* dcnt, uint8_t* dsrc,
+                     int oh, int ow, int mode, CompositeIndex ix, int fill, void* stream) {
   DSIC_REQUIRE(n >= 1 && n <= COMPOSITE_MAX, "%s: n=%d sources (1..%d)", what, n, COMPOSITE_MAX);
   DSIC_REQUIRE(C >= 1 && C <= 4, "%s: C=%d must be in 1..4", what, C);
   DSIC_REQUIRE(oh >= 1 && ow >= 1 && (int64_t)oh * ow < ((int64_t)1 << 31),
                "%s: output %dx%d must be at least 1x1 and under 2^31 pixels", what, oh, ow);
   DSIC_REQUIRE(src && src_valid && rect && nodata && dst, "%s: null pointer", what);
-  DSIC_REQUIRE(mode >= COMPOSITE_FIRST && mode <= COMPOSITE_MEDIAN, "%s: mode=%d (0 first, 1 last, 2 mean, 3 median)", what,
-               mode);
+  if (pick) {
+    const bool ranked = mode == COMPOSITE_RANK_MAX || mode == COMPOSITE_RANK_MIN;
+    DSIC_REQUIRE(mode == COMPOSITE_FIRST || mode == COMPOSITE_LAST || ranked, "%s: mode=%d (0 first, 1 last, 4 max, 5 min)",
+                 what, mode);
+    if (ranked) {
+      DSIC_REQUIRE(ix.kind >= INDEX_BAND && ix.kind <= INDEX_ND, "%s: kind=%d (0 band, 1 difference, 2 nd)", what, ix.kind);
+      const int status = index_bands(what, C, ix.kind, ix.a, ix.b);
+      if (status != DSIC_OK) return status;
+      if (ix.kind == INDEX_BAND) ix.b = ix.a;
+    }
+  } else {
+    DSIC_REQUIRE(mode >= COMPOSITE_FIRST && mode <= COMPOSITE_MEDIAN, "%s: mode=%d (0 first, 1 last, 2 mean, 3 median)", what,
+                 mode);
+  }
   DSIC_REQUIRE(pixel_value<T>(fill, 0), "%s: fill=%d must be a pixel value", what, fill);
   const int64_t px = (int64_t)sizeof(T) * C, opix = (int64_t)oh * ow;
   DSIC_REQUIRE(((uintptr_t)dst & (sizeof(T) - 1)) == 0, "%s: dst must be %d-byte aligned", what, (int)sizeof(T));
-  const void* outs[3] = {dst, dval, dcnt};
-  const int64_t obytes[3] = {px * opix, opix, opix};
-  for (int a = 0; a < 3; ++a)
-    for (int b = a + 1; b < 3; ++b)
+  const void* outs[4] = {dst, dval, dcnt, dsrc};
+  const int64_t obytes[4] = {px * opix, opix, opix, opix};
+  for (int a = 0; a < 4; ++a)
+    for (int b = a + 1; b < 4; ++b)
       DSIC_REQUIRE(!outs[a] || !outs[b] || buffers_apart(outs[a], obytes[a], outs[b], obytes[b]), "%s: the outputs overlap",
                    what);
   CompositeTable tab = {};
@@ -276,20 +382,22 @@ static int composite(const char* what, const T* const* src, const uint8_t* const
     DSIC_REQUIRE(dy >= 0 && dx >= 0 && (int64_t)dy + h <= oh && (int64_t)dx + w <= ow,
                  "%s: source %d: rect %dx%d at (%d, %d) is not inside the output %dx%d", what, i, h, w, dy, dx, oh, ow);
     DSIC_REQUIRE(pixel_value<T>(nodata[i], -1), "%s: source %d: nodata=%d (-1 for none, or a pixel value)", what, i, nodata[i]);
+    DSIC_REQUIRE(!id || (id[i] >= 0 && id[i] < COMPOSITE_NO_SOURCE), "%s: source %d: id=%d must be in 0..%d", what, i,
+                 id ? id[i] : 0, COMPOSITE_NO_SOURCE - 1);
     DSIC_REQUIRE(((uintptr_t)src[i] & (sizeof(T) - 1)) == 0, "%s: source %d must be %d-byte aligned", what, i, (int)sizeof(T));
     const int64_t spix = (int64_t)h * w;
-    for (int a = 0; a < 3; ++a)
+    for (int a = 0; a < 4; ++a)
       DSIC_REQUIRE(!outs[a] || (buffers_apart(src[i], px * spix, outs[a], obytes[a]) &&
                                 (!src_valid[i] || buffers_apart(src_valid[i], spix, outs[a], obytes[a]))),
                    "%s: source %d and an output overlap", what, i);
-    tab.s[i] = {src[i], src_valid[i], dy, dx, h, w, nodata[i], 0};
+    tab.s[i] = {src[i], src_valid[i], dy, dx, h, w, nodata[i], id ? id[i] : i};
   }
   const hipStream_t s = (hipStream_t)stream;
   switch (C) {
-    case 1: composite_launch<T, 1>(tab, n, dst, dval, dcnt, oh, ow, mode, fill, s); break;
-    case 2: composite_launch<T, 2>(tab, n, dst, dval, dcnt, oh, ow, mode, fill, s); break;
-    case 3: composite_launch<T, 3>(tab, n, dst, dval, dcnt, oh, ow, mode, fill, s); break;
-    default: composite_launch<T, 4>(tab, n, dst, dval, dcnt, oh, ow, mode, fill, s); break;
+    case 1: composite_launch<T, 1>(tab, n, dst, dval, dcnt, dsrc, oh, ow, mode, ix, fill, s); break;
+    case 2: composite_launch<T, 2>(tab, n, dst, dval, dcnt, dsrc, oh, ow, mode, ix, fill, s); break;
+    case 3: composite_launch<T, 3>(tab, n, dst, dval, dcnt, dsrc, oh, ow, mode, ix, fill, s); break;
+    default: composite_launch<T, 4>(tab, n, dst, dval, dcnt, dsrc, oh, ow, mode, ix, fill, s); break;
   }
   return check_launch(what);
 }
@@ -301,13 +409,29 @@ using namespace dsic;
 extern "C" int dsic_window_composite_u8(const uint8_t* const* src, const uint8_t* const* src_valid, const int* rect,
                                         const int* nodata, int n, int C, uint8_t* dst_hwc, uint8_t* dst_valid,
                                         uint8_t* dst_count, int oh, int ow, int mode, int fill, void* stream) {
-  return composite<uint8_t>("window_composite_u8", src, src_valid, rect, nodata, n, C, dst_hwc, dst_valid, dst_count, oh, ow,
-                            mode, fill, stream);
+  return composite<uint8_t>("window_composite_u8", false, src, src_valid, rect, nodata, nullptr, n, C, dst_hwc, dst_valid,
+                            dst_count, nullptr, oh, ow, mode, {0, 0, 0}, fill, stream);
 }
 
 extern "C" int dsic_window_composite_u16(const uint16_t* const* src, const uint8_t* const* src_valid, const int* rect,
                                          const int* nodata, int n, int C, uint16_t* dst_hwc, uint8_t* dst_valid,
                                          uint8_t* dst_count, int oh, int ow, int mode, int fill, void* stream) {
-  return composite<uint16_t>("window_composite_u16", src, src_valid, rect, nodata, n, C, dst_hwc, dst_valid, dst_count, oh,
-                             ow, mode, fill, stream);
+  return composite<uint16_t>("window_composite_u16", false, src, src_valid, rect, nodata, nullptr, n, C, dst_hwc, dst_valid,
+                             dst_count, nullptr, oh, ow, mode, {0, 0, 0}, fill, stream);
+}
+
+extern "C" int dsic_window_composite_pick_u8(const uint8_t* const* src, const uint8_t* const* src_valid, const int* rect,
+                                             const int* nodata, const int* id, int n, int C, uint8_t* dst_hwc,
+                                             uint8_t* dst_valid, uint8_t* dst_count, uint8_t* dst_source, int oh, int ow,
+                                             int mode, int kind, int a, int b, int fill, void* stream) {
+  return composite<uint8_t>("window_composite_pick_u8", true, src, src_valid, rect, nodata, id, n, C, dst_hwc, dst_valid,
+                            dst_count, dst_source, oh, ow, mode, {kind, a, b}, fill, stream);
+}
+
+extern "C" int dsic_window_composite_pick_u16(const uint16_t* const* src, const uint8_t* const* src_valid, const int* rect,
+                                              const int* nodata, const int* id, int n, int C, uint16_t* dst_hwc,
+                                              uint8_t* dst_valid, uint8_t* dst_count, uint8_t* dst_source, int oh, int ow,
+                                              int mode, int kind, int a, int b, int fill, void* stream) {
+  return composite<uint16_t>("window_composite_pick_u16", true, src, src_valid, rect, nodata, id, n, C, dst_hwc, dst_valid,
+                             dst_count, dst_source, oh, ow, mode, {kind, a, b}, fill, stream);
 }

@@ -166,6 +166,8 @@ SIGNATURES = {
     "dsic_index_histogram_u16": (c_int, [_P, _P] + [c_int] * 7 + [_P, _P]),
     "dsic_window_composite_u8": (c_int, [_P, _P, _P, _P, c_int, c_int, _P, _P, _P] + [c_int] * 4 + [_P]),
     "dsic_window_composite_u16": (c_int, [_P, _P, _P, _P, c_int, c_int, _P, _P, _P] + [c_int] * 4 + [_P]),
+    "dsic_window_composite_pick_u8": (c_int, [_P, _P, _P, _P, _P, c_int, c_int, _P, _P, _P, _P] + [c_int] * 7 + [_P]),
+    "dsic_window_composite_pick_u16": (c_int, [_P, _P, _P, _P, _P, c_int, c_int, _P, _P, _P, _P] + [c_int] * 7 + [_P]),
     "dsic_stream_create_masked":(c_int, [_P, c_int, _P]),
     "dsic_stream_destroy": (c_int, [_P]),
     "dsic_range_decode": (c_int, [_P, c_int64, _P, c_int, c_int, _P, c_int, _P, c_int, c_int, c_int,

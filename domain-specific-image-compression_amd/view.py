@@ -13,7 +13,8 @@ render_index and render_index_warped show an index of one or two bands (a normal
 difference, a band) through a colour map in that same launch (csrc/render.h's index tail); index_histogram and
 index_stretch derive its stretch from the data, colormap_from_anchors and COLORMAPS supply the maps.
 SceneStack places several readers on one grid, a mosaic or a temporal stack, and combines the parts they serve of a
-window in one launch (csrc/composite.hip): first, last, mean or median over the scenes that are valid at a pixel.
+window in one launch (csrc/composite.hip): first, last, mean or median over the scenes that are valid at a pixel, or the
+whole pixel of the scene whose index (an NDVI, say) is largest or smallest there, with the scene's number beside it.
 
 The cache holds what the stitch and blend calls consume: per (level, tile) the tile's g_s output, float32
 [C, th, tw], not clamped, and for a near-lossless level its q plane.  A window is served by collecting its tiles, in
@@ -292,6 +293,63 @@ def _display_args(what, C, top, bands, stretch, background):
     if not 0 <= background <= 255:
         raise ValueError(f"{what}: background={background} must be in 0 .. 255")
     return bands, stretch, background
+
+
+def _check_index(C, index, what):
+    """index = ("nd", a, b), ("difference", a, b) or ("band", a) over C bands -> (kind name, a, b); `what` names the
+    caller in a ValueError."""
+    try:
+        name, bands = index[0], tuple(operator.index(v) for v in index[1:])
+    except (TypeError, IndexError, KeyError):
+        raise ValueError(f"{what}: index={index!r} is not ('nd', a, b), ('difference', a, b) or ('band', a)") from None
+    if not isinstance(name, str) or name not in INDEX_KINDS or len(bands) != (1 if name == "band" else 2):
+        raise ValueError(f"{what}: index={index!r} is not ('nd', a, b), ('difference', a, b) or ('band', a)")
+    if not all(0 <= v < C for v in bands):
+        raise ValueError(f"{what}: index={index!r} must name bands in 0 .. {C - 1}")
+    return name, bands[0], bands[-1]
+
+
+def _index_args(what, C, top, index, stretch, colormap, background):
+    """The arguments of an index view over C bands of samples 0 .. top -> ((kind name, a, b), None or the stretch pair,
+    the colour map as a name or a uint8 [256, 3] array, background); `what` names the caller in a ValueError."""
+    kind, a, b = _check_index(C, index, what)
+    if stretch is not None:
+        try:
+            stretch = tuple(operator.index(v) for v in stretch)
+        except TypeError:
+            raise ValueError(f"{what}: stretch={stretch!r} is not one pair of integers (lo, hi)") from None
+        vmin, vmax = index_range(kind, top)
+        if len(stretch) != 2:
+            raise ValueError(f"{what}: stretch={stretch!r} is not one pair of integers (lo, hi)")
+        if not vmin <= stretch[0] <= stretch[1] <= vmax:
+            raise ValueError(f"{what}: stretch pair ({stretch[0]}, {stretch[1]}) must have {vmin} <= lo <= hi <= {vmax}")
+    if isinstance(colormap, str):
+        if colormap not in COLORMAPS:
+            raise ValueError(f"{what}: colormap={colormap!r} ({', '.join(COLORMAPS)}, or a uint8 [256, 3] array)")
+    else:
+        try:
+            table = colormap.cpu().numpy() if isinstance(colormap, torch.Tensor) else np.asarray(colormap)
+        except (TypeError, ValueError, RuntimeError):
+            table = None
+        if table is None or table.dtype != np.uint8 or table.shape != (256, 3):
+            raise ValueError(f"{what}: colormap must be one of {', '.join(COLORMAPS)}, or a uint8 [256, 3] array")
+        colormap = np.ascontiguousarray(table)
+    try:
+        background = operator.index(background)
+    except TypeError:
+        raise ValueError(f"{what}: background={background!r} is not an integer") from None
+    if not 0 <= background <= 255:
+        raise ValueError(f"{what}: background={background} must be in 0 .. 255")
+    return (kind, a, b), stretch, colormap, background
+
+
+def _device_colormap(cache, colormap, dev):
+    """A checked colour map on the device; a named one once per cache (a reader's, a stack's)."""
+    if not isinstance(colormap, str):
+        return torch.from_numpy(colormap).to(dev)
+    if colormap not in cache:
+        cache[colormap] = torch.from_numpy(COLORMAPS[colormap]).to(dev)
+    return cache[colormap]
 
 
 def _opt(t):
@@ -816,49 +874,14 @@ class ImageReader:
     # ---- index views --------------------------------------------------------------------------------------------
     def _check_index(self, ix, index, what):
         """index = ("nd", a, b), ("difference", a, b) or ("band", a) against a level -> (kind name, a, b)."""
-        try:
-            name, bands = index[0], tuple(operator.index(v) for v in index[1:])
-        except (TypeError, IndexError, KeyError):
-            raise ValueError(f"{what}: index={index!r} is not ('nd', a, b), ('difference', a, b) or ('band', a)") from None
-        if not isinstance(name, str) or name not in INDEX_KINDS or len(bands) != (1 if name == "band" else 2):
-            raise ValueError(f"{what}: index={index!r} is not ('nd', a, b), ('difference', a, b) or ('band', a)")
-        if not all(0 <= v < ix["C"] for v in bands):
-            raise ValueError(f"{what}: index={index!r} must name bands in 0 .. {ix['C'] - 1}")
-        return name, bands[0], bands[-1]
+        return _check_index(ix["C"], index, what)
 
     def _index_display(self, level, index, stretch, colormap, alpha, background, what):
         """render_index's arguments checked against a level -> _IndexShow, the stretch still None where not given and
         the colour map a name or a uint8 [256, 3] array."""
         ix = self._open[level][1]
         top = self._display_out(ix)[1]
-        kind, a, b = self._check_index(ix, index, what)
-        if stretch is not None:
-            try:
-                stretch = tuple(operator.index(v) for v in stretch)
-            except TypeError:
-                raise ValueError(f"{what}: stretch={stretch!r} is not one pair of integers (lo, hi)") from None
-            vmin, vmax = index_range(kind, top)
-            if len(stretch) != 2:
-                raise ValueError(f"{what}: stretch={stretch!r} is not one pair of integers (lo, hi)")
-            if not vmin <= stretch[0] <= stretch[1] <= vmax:
-                raise ValueError(f"{what}: stretch pair ({stretch[0]}, {stretch[1]}) must have {vmin} <= lo <= hi <= {vmax}")
-        if isinstance(colormap, str):
-            if colormap not in COLORMAPS:
-                raise ValueError(f"{what}: colormap={colormap!r} ({', '.join(COLORMAPS)}, or a uint8 [256, 3] array)")
-        else:
-            try:
-                table = colormap.cpu().numpy() if isinstance(colormap, torch.Tensor) else np.asarray(colormap)
-            except (TypeError, ValueError, RuntimeError):
-                table = None
-            if table is None or table.dtype != np.uint8 or table.shape != (256, 3):
-                raise ValueError(f"{what}: colormap must be one of {', '.join(COLORMAPS)}, or a uint8 [256, 3] array")
-            colormap = np.ascontiguousarray(table)
-        try:
-            background = operator.index(background)
-        except TypeError:
-            raise ValueError(f"{what}: background={background!r} is not an integer") from None
-        if not 0 <= background <= 255:
-            raise ValueError(f"{what}: background={background} must be in 0 .. 255")
+        (kind, a, b), stretch, colormap, background = _index_args(what, ix["C"], top, index, stretch, colormap, background)
         if alpha and "nodata" in ix:
             raise ValueError(f"{what}: alpha=True needs a validity mask (compress_image with valid=, stream version "
                              f"{_c.VERSION_VALID}); a nodata stream marks its pixels by value")
@@ -874,14 +897,7 @@ class ImageReader:
             stretch = tuple(self._default_stretch(level, None, st)[show.a])
         elif stretch is None:
             stretch = self._index_stretch((show.kind, show.a, show.b), (2, 98), None, st)
-        cmap = show.colormap
-        if isinstance(cmap, str):
-            if cmap not in self._cmaps:
-                self._cmaps[cmap] = torch.from_numpy(COLORMAPS[cmap]).to(self._dev)
-            cmap = self._cmaps[cmap]
-        else:
-            cmap = torch.from_numpy(cmap).to(self._dev)
-        return show._replace(stretch=stretch, colormap=cmap)
+        return show._replace(stretch=stretch, colormap=_device_colormap(self._cmaps, show.colormap, self._dev))
 
     def _render_index(self, level, lw, view, show, resampling, st, ensured):
         """One planned request through the index kernel (dsic_window_index_render_u8 / _u16)."""
@@ -1103,7 +1119,25 @@ class ImageReader:
 # multiple of 2^l, so the scene ends at row oy / 2^l + ceil(h / 2^l) = ceil((oy + h) / 2^l) <= ceil(H / 2^l); columns
 # likewise.  stack_levels and stack_parts are the planning, pure Python.
 REDUCE = {"first": 0, "last": 1, "mean": 2, "median": 3}          # DSIC_COMPOSITE_* of include/dsic_hip.h
+RANKED = {"max": 4, "min": 5}                                     # DSIC_COMPOSITE_MAX, _MIN: the pick exports alone
 MAX_SCENES = 16
+NO_SOURCE = 255                                                   # the source plane where no scene counted
+
+
+def stack_reduce(reduce, C, what="stack_reduce") -> tuple:
+    """A stack's reduce over C bands -> (mode, kind, a, b), the integers of include/dsic_hip.h (pure Python).  reduce is
+    "first", "last", "mean" or "median" (kind, a and b are 0 then), or a ranked one, ("max", index) or ("min", index):
+    per pixel the whole pixel of the scene whose index is largest or smallest there, the first of equals.  index is
+    ("nd", a, b), ("difference", a, b) or ("band", a), as ImageReader.render_index takes it (b = a for a band).
+    ValueError for anything else; `what` names the caller in it."""
+    if isinstance(reduce, str) and reduce in REDUCE:
+        return REDUCE[reduce], 0, 0, 0
+    forms = f"{', '.join(REDUCE)}, or ('max', index) / ('min', index) with index ('nd', a, b), ('difference', a, b) or ('band', a)"
+    if isinstance(reduce, str) or not isinstance(reduce, (tuple, list)) or len(reduce) != 2 or \
+            not isinstance(reduce[0], str) or reduce[0] not in RANKED:
+        raise ValueError(f"{what}: reduce={reduce!r} ({forms})")
+    kind, a, b = _check_index(C, reduce[1], f"{what}: reduce={reduce!r} ({forms})")
+    return RANKED[reduce[0]], INDEX_KINDS[kind], a, b
 
 
 def _offsets(offsets, n, what):
@@ -1183,6 +1217,7 @@ class SceneStack:
         self.levels = stack_levels([lv for _, lv in self._scenes], self.offsets, shape)
         self._dev = self.readers[0]._dev
         self._dtype = torch.uint16 if self.kind == _c.KIND_U16_HWC else torch.uint8
+        self._cmaps = {}                                           # name -> the colour map on the device
 
     @property
     def shape(self):
@@ -1196,17 +1231,19 @@ class SceneStack:
             raise ValueError(f"{what}: window {window!r}, level={level!r}: not integers") from None
         if not 0 <= level < len(self.levels):
             raise ValueError(f"{what}: level={level}: the stack holds levels 0 .. {len(self.levels) - 1}")
-        if reduce not in REDUCE:
-            raise ValueError(f"{what}: reduce={reduce!r} ({', '.join(REDUCE)})")
+        code = stack_reduce(reduce, self.C, what)
         y0, x0, h, w = window
         H, W = self.levels[level]
         if y0 < 0 or x0 < 0 or h < 1 or w < 1 or y0 + h > H or x0 + w > W:
             raise ValueError(f"{what}: window {h}x{w} at ({y0}, {x0}) is empty or outside the {H}x{W} level {level}")
-        return level, window
+        return level, window, code
 
-    def _composite(self, window, level, reduce, fill, with_valid, with_count, stats):
-        """One window of a level -> (image, its uint8 validity or None, its uint8 counts or None)."""
+    def _composite(self, window, level, code, fill, with_valid, with_count, stats, with_source=False):
+        """One window of a level, code = stack_reduce's -> (image, its uint8 validity or None, its uint8 counts or None,
+        its uint8 scene numbers or None).  A ranked reduce and a source plane go through dsic_window_composite_pick_u8 /
+        _u16 with the scene numbers as ids, everything else through dsic_window_composite_u8 / _u16 as before."""
         _, _, h, w = window
+        mode, kind, a, b = code
         top = 65535 if self.kind == _c.KIND_U16_HWC else 255
         try:
             fill = operator.index(fill)
@@ -1231,23 +1268,31 @@ class SceneStack:
             stats.update(total)
         if not srcs:                                               # no scene under the window: nothing to launch
             img = torch.from_numpy(np.full((h, w, self.C), fill, dtype=np.uint16 if top == 65535 else np.uint8)).to(self._dev)
-            zeros = lambda want: torch.zeros((h, w), dtype=torch.uint8, device=self._dev) if want else None
-            return img, zeros(with_valid), zeros(with_count)
+            plane = lambda want, v=0: torch.full((h, w), v, dtype=torch.uint8, device=self._dev) if want else None
+            return img, plane(with_valid), plane(with_count), plane(with_source, NO_SOURCE)
         n = len(srcs)
         dst = torch.empty((h, w, self.C), dtype=self._dtype, device=self._dev)
         dval = torch.empty((h, w), dtype=torch.uint8, device=self._dev) if with_valid else None
         dcnt = torch.empty((h, w), dtype=torch.uint8, device=self._dev) if with_count else None
-        what = "window_composite" + ("_u16" if top == 65535 else "_u8")
-        status = getattr(_lib.load(), "dsic_" + what)(
-            (ctypes.c_void_p * n)(*[_p(img) for img, _, _, _ in srcs]), (ctypes.c_void_p * n)(*[_opt(v) for _, v, _, _ in srcs]),
-            (ctypes.c_int * (4 * n))(*[v for _, _, rect, _ in srcs for v in rect]),
-            (ctypes.c_int * n)(*[nd for _, _, _, nd in srcs]), n, self.C, _p(dst), _opt(dval), _opt(dcnt), h, w,
-            REDUCE[reduce], fill, _stream())
+        dsrc = torch.empty((h, w), dtype=torch.uint8, device=self._dev) if with_source else None
+        pick = with_source or mode in RANKED.values()
+        what = "window_composite" + ("_pick" if pick else "") + ("_u16" if top == 65535 else "_u8")
+        tables = [(ctypes.c_void_p * n)(*[_p(img) for img, _, _, _ in srcs]), (ctypes.c_void_p * n)(*[_opt(v) for _, v, _, _ in srcs]),
+                  (ctypes.c_int * (4 * n))(*[v for _, _, rect, _ in srcs for v in rect]),
+                  (ctypes.c_int * n)(*[nd for _, _, _, nd in srcs])]
+        if pick:                                                   # the scene numbers travel as ids: parts skips scenes
+            status = getattr(_lib.load(), "dsic_" + what)(
+                *tables, (ctypes.c_int * n)(*[s for s, _, _ in parts]), n, self.C, _p(dst), _opt(dval), _opt(dcnt), _opt(dsrc),
+                h, w, mode, kind, a, b, fill, _stream())
+        else:
+            status = getattr(_lib.load(), "dsic_" + what)(*tables, n, self.C, _p(dst), _opt(dval), _opt(dcnt), h, w, mode,
+                                                          fill, _stream())
         _lib.check(status, what)
-        return dst, dval, dcnt
+        return dst, dval, dcnt, dsrc
 
     @torch.no_grad()
-    def read(self, y0, x0, h, w, level=0, reduce="first", fill=0, with_valid=False, with_count=False, stats=None):
+    def read(self, y0, x0, h, w, level=0, reduce="first", fill=0, with_valid=False, with_count=False, stats=None,
+             with_source=False):
         """The window rows [y0, y0+h) x columns [x0, x0+w) of the stack's level `level`, in that level's own grid:
         [h, w, C] of the readers' kind on the device.  Every scene that meets the window serves its part through its
         own reader and cache, exactly what reader.read(*part, level=level, with_valid=True) returns; a stream with a
@@ -1257,17 +1302,28 @@ class SceneStack:
         their mean rounded half up, "median" per band their median (an even count: the mean of the two middle values,
         rounded half up).  A pixel under no valid scene is `fill` in every band.  A window that no scene meets launches
         nothing and is a filled tensor.
+        Best-pixel composites: reduce = ("max", index) or ("min", index), index = ("nd", a, b), ("difference", a, b) or
+        ("band", a) as render_index takes it, keeps per pixel the whole pixel, all bands of one date, of the scene
+        whose index is largest or smallest there; among equals the first in the order of `readers`.  A scene counts
+        only where its index is defined: an "nd" pixel with A + B = 0 is no candidate.  ("max", ("nd", nir, red)) is
+        the maximum-NDVI composite (dsic_window_composite_pick_u8 / _u16; stack_reduce names the forms).
+        with_source adds source, torch.uint8 [h, w]: the number, in `readers`, of the scene the pixel was taken from,
+        255 where none counted; for "first", "last" and the ranked reduces, a ValueError for "mean" and "median",
+        which mix scenes.
         A result of level l is the composite of the scenes' level-l pixels.  It is not the halving of the level-0
         composite: median and halving do not commute, nor do first and halving where validity differs.
         with_valid adds valid, torch.bool [h, w]: whether any scene counted; with_count adds count, torch.uint8
-        [h, w]: how many did.  The order is (image, valid, count).
+        [h, w]: how many did.  The order is (image, valid, count, source).
         stats (a dict) receives the sum of the readers' counters of this call (hits, decoded, decode_batches,
         bytes_read, bytes_uploaded), tiles as (scene, level, tile) and parts, the number of scenes that met the window.
         ValueError for a window that is empty or outside the level, a level the stack does not hold, an unknown
         reduce, a fill beyond the kind, and whatever a reader raises (a closed one among it)."""
-        level, window = self._check_window("SceneStack.read", (y0, x0, h, w), level, reduce)
-        img, valid, count = self._composite(window, level, reduce, fill, with_valid, with_count, stats)
-        out = (img,) + ((valid.bool(),) if with_valid else ()) + ((count,) if with_count else ())
+        level, window, code = self._check_window("SceneStack.read", (y0, x0, h, w), level, reduce)
+        if with_source and code[0] in (REDUCE["mean"], REDUCE["median"]):
+            raise ValueError(f"SceneStack.read: with_source goes with first, last, max and min; reduce={reduce!r} mixes scenes")
+        img, valid, count, source = self._composite(window, level, code, fill, with_valid, with_count, stats, with_source)
+        out = (img,) + ((valid.bool(),) if with_valid else ()) + ((count,) if with_count else ()) + \
+            ((source,) if with_source else ())
         return out if len(out) > 1 else img
 
     @torch.no_grad()
@@ -1279,7 +1335,7 @@ class SceneStack:
         stretch = None is (0, 255) per band for a uint8 stack; a uint16 stack has no histogram of its own and needs a
         stretch: a ValueError without one."""
         what = "SceneStack.render"
-        level, window = self._check_window(what, (y0, x0, h, w), level, reduce)
+        level, window, code = self._check_window(what, (y0, x0, h, w), level, reduce)
         top = 65535 if self.kind == _c.KIND_U16_HWC else 255
         bands, stretch, background = _display_args(what, self.C, top, bands, stretch, background)
         if stretch is None:
@@ -1288,10 +1344,41 @@ class SceneStack:
                                  "stretch() gives one scene's)")
             stretch = [(0, 255)] * self.C
         alpha = int(bool(alpha))
-        img, valid, _ = self._composite(window, level, reduce, 0, True, False, None)
+        img, valid, _, _ = self._composite(window, level, code, 0, True, False, None)
         y0, x0, h, w = window
         dst = torch.empty((h, w, len(bands) + alpha), dtype=torch.uint8, device=self._dev)
         _call_by_width("window_render", img, _p(valid), h, w, y0, x0, self.C, 0, y0, x0, h, w,
                        (ctypes.c_int * len(bands))(*bands), len(bands), _c._lohi(stretch), _p(dst), h, w,
                        RESAMPLING["nearest"], -1, alpha, background, _stream())
+        return dst
+
+    @torch.no_grad()
+    def render_index(self, y0, x0, h, w, index, level=0, reduce="first", stretch=None, colormap="grey", alpha=False,
+                     background=0):
+        """read(y0, x0, h, w, level, reduce) as an index view: torch.uint8 [h, w, 3 (+ 1)].  The composite with its
+        validity goes through one dsic_window_index_render_u8 / _u16 call at identity geometry (shift 0, region = the
+        window, size (h, w), nearest), as render goes through the render call, so the result is
+        ImageReader.render_index's arithmetic on read's result, bit for bit: index, stretch, colormap, alpha and
+        background mean what they mean there; a pixel under no valid scene, and an "nd" pixel with A + B = 0, is
+        background, alpha 0.  reduce is read's, a ranked one among them: the NDVI of a maximum-NDVI composite is
+        render_index(..., ("nd", 3, 0), reduce=("max", ("nd", 3, 0))).
+        stretch = None is (-10000, 10000) for "nd" and the index's full range for a uint8 stack; a uint16 stack has no
+        histogram of its own and needs a stretch for "band" and "difference": a ValueError without one.  Named colour
+        maps are kept on the device, once per stack."""
+        what = "SceneStack.render_index"
+        level, window, code = self._check_window(what, (y0, x0, h, w), level, reduce)
+        top = 65535 if self.kind == _c.KIND_U16_HWC else 255
+        (kind, a, b), stretch, colormap, background = _index_args(what, self.C, top, index, stretch, colormap, background)
+        if stretch is None:
+            if kind != "nd" and top == 65535:
+                raise ValueError(f"{what}: a uint16 stack needs stretch=: it has no histogram of its own (a reader's "
+                                 "stretch() gives one scene's)")
+            stretch = index_range(kind, top)
+        alpha = int(bool(alpha))
+        cmap = _device_colormap(self._cmaps, colormap, self._dev)
+        img, valid, _, _ = self._composite(window, level, code, 0, True, False, None)
+        y0, x0, h, w = window
+        dst = torch.empty((h, w, 3 + alpha), dtype=torch.uint8, device=self._dev)
+        _call_by_width("window_index_render", img, _p(valid), h, w, y0, x0, self.C, 0, y0, x0, h, w, INDEX_KINDS[kind], a, b,
+                       *stretch, _p(cmap), _p(dst), h, w, RESAMPLING["nearest"], -1, alpha, background, _stream())
         return dst

@@ -1038,6 +1038,48 @@ int dsic_window_composite_u16(const uint16_t* const* src, const uint8_t* const* 
                               uint8_t* dst_valid, uint8_t* dst_count, int oh, int ow, int mode,
                               int fill, void* stream);
 
+/* ---- best-pixel composites (codec.SceneStack.read with a ranked reduce, with_source=) ----
+ * dsic_window_composite_pick_u8 / _u16: the whole pixel of one candidate per output pixel, and
+ *   which source it came from.  src, src_valid, rect, nodata, n, C, dst_hwc, dst_valid, dst_count,
+ *   oh, ow and fill are those of dsic_window_composite_u8 / _u16, and so are the candidates: the
+ *   sources i, in list order, whose rect contains p, whose src_valid, if given, is not zero at p,
+ *   and in which p is not nodata.  (kind, a, b) is an index of the table of the index views above,
+ *   with top = 255 or 65535: u = its unsigned value of the candidate's samples A of band a and B
+ *   of band b.  For the two ranked modes a candidate must also have a defined index: a
+ *   DSIC_INDEX_ND candidate with A + B = 0 is not a candidate.  k is the number of candidates.
+ *
+ *   mode                        result: all C bands of one candidate
+ *   DSIC_COMPOSITE_FIRST   0    the first candidate
+ *   DSIC_COMPOSITE_LAST    1    the last candidate
+ *   DSIC_COMPOSITE_MAX     4    the candidate with the largest u
+ *   DSIC_COMPOSITE_MIN     5    the candidate with the smallest u
+ *                               ties, in both: the candidate that comes first in list order
+ *
+ *   k = 0 gives fill in every band.  dst_valid receives k > 0, dst_count k, as above.  dst_source
+ *   (NULL: not wanted), uint8 [oh][ow], receives the id of the winning source and 255 where k = 0.
+ *   id is NULL, then the id of source i is i, or a host array of n values in 0..254, read before
+ *   the call returns.  kind, a and b are ignored for first and last.  Everything is integer: u is
+ *   at most 131070, the ranking is one unsigned comparison per candidate, nothing is divided
+ *   beyond the one division of a normalised difference.  One launch, no workspace; all buffers at
+ *   any element alignment.  max and min read every source's validity and bands a and b of every
+ *   candidate, and the winner's pixel.  first and last without id and dst_source write the bytes
+ *   of dsic_window_composite_u8 / _u16.
+ *   DSIC_EINVAL, nothing written: what dsic_window_composite_u8 / _u16 refuse, with mode outside
+ *   {0, 1, 4, 5}; for max and min a kind outside the three or a band outside 0..C-1; an id outside
+ *   0..254; dst_source overlapping an input or another output. */
+#define DSIC_COMPOSITE_MAX 4
+#define DSIC_COMPOSITE_MIN 5
+int dsic_window_composite_pick_u8(const uint8_t* const* src, const uint8_t* const* src_valid,
+                                  const int* rect, const int* nodata, const int* id, int n, int C,
+                                  uint8_t* dst_hwc, uint8_t* dst_valid, uint8_t* dst_count,
+                                  uint8_t* dst_source, int oh, int ow, int mode, int kind, int a,
+                                  int b, int fill, void* stream);
+int dsic_window_composite_pick_u16(const uint16_t* const* src, const uint8_t* const* src_valid,
+                                   const int* rect, const int* nodata, const int* id, int n, int C,
+                                   uint16_t* dst_hwc, uint8_t* dst_valid, uint8_t* dst_count,
+                                   uint8_t* dst_source, int oh, int ow, int mode, int kind, int a,
+                                   int b, int fill, void* stream);
+
 /* HIP stream limited to the CUs whose bit is set in mask_host[words] (bit i of
  * word i/32 = CU i).  Used to give the range coder its own few CUs beside the
  * conv kernels; there is no reference counterpart (the reference is

@@ -16,8 +16,9 @@ an image.
                                           [--rotate DEG [--center Y,X] [--scale S] | --affine M00,M01,M02,M10,M11,M12]
                                           [--resampling bilinear|cubic|nearest]
     python tools/dsic_image.py composite  --weights CKPT.pt OUT --scene FILE[@Y,X] [--scene FILE[@Y,X] ...]
-                                          [--reduce first|last|mean|median] [--region Y0,X0,H,W] [--level L] [--fill V]
-                                          [--count-out FILE.npy] [--valid-out FILE.npy]
+                                          [--reduce first|last|mean|median|max|min] [--index nd:A,B|difference:A,B|band:A]
+                                          [--region Y0,X0,H,W] [--level L] [--fill V]
+                                          [--count-out FILE.npy] [--valid-out FILE.npy] [--source-out FILE.npy]
     python tools/dsic_image.py info       IN.dsic
 
 --segments K (2, 4, 8 or 16) codes every tile's y string as K independent strings, which a decoder reads on K waves per
@@ -76,6 +77,10 @@ median) of the scenes that are valid there, in the order given; a pixel under no
 --region (default: the whole level) is in --level's own pixels; --level L needs L + 1 levels in every stream and
 offsets that are multiples of 2^L.  --count-out FILE.npy writes how many scenes counted per pixel (uint8 [h,w]),
 --valid-out FILE.npy whether any did (bool [h,w]).  OUT follows decompress's conventions.
+--reduce max and --reduce min are the best-pixel composites: with --index nd:A,B, difference:A,B or band:A (render's
+spelling) a pixel is the whole pixel, every band, of the scene whose index is largest or smallest there, the first of
+equals; --reduce max --index nd:NIR,RED is the maximum-NDVI composite.  --source-out FILE.npy (first, last, max, min)
+writes the number of the scene, in the order of --scene, each pixel was taken from (uint8 [h,w], 255 under no scene).
 
 The state dict is loaded plain or from under "model" (code/modelv2/eval_selfcontained_entropy.py:130-134); the model's
 N, M, input channels and spatial_params are read from its shapes.  Images are PNG through PIL when PIL is importable
@@ -269,13 +274,7 @@ def render_main(a, ap, region, size, level_given, matrix=None):
 
     index = None
     if a.index is not None:
-        kind, _, rest = a.index.partition(":")
-        try:
-            index = (kind,) + tuple(int(v) for v in rest.split(","))
-        except ValueError:
-            index = ()
-        if kind not in ("nd", "difference", "band") or len(index) != (2 if kind == "band" else 3):
-            ap.error(f"--index {a.index}: nd:A,B, difference:A,B or band:A with band numbers A, B")
+        index = parse_index(a, ap)
         if a.bands is not None or a.stretch is not None:
             ap.error("--bands and --stretch do not go with --index; --index-stretch LO,HI is its pair")
         if a.index_stretch is not None and a.percent is not None:
@@ -379,8 +378,21 @@ def render_index_main(a, model, index, pair, region, size, level_given, matrix):
           + f": {len(stats['tiles'])} tile(s) -> {path}")
 
 
+def parse_index(a, ap):
+    """--index KIND:A[,B] -> ("nd", A, B), ("difference", A, B) or ("band", A)"""
+    kind, _, rest = a.index.partition(":")
+    try:
+        index = (kind,) + tuple(int(v) for v in rest.split(","))
+    except ValueError:
+        index = ()
+    if kind not in ("nd", "difference", "band") or len(index) != (2 if kind == "band" else 3):
+        ap.error(f"--index {a.index}: nd:A,B, difference:A,B or band:A with band numbers A, B")
+    return index
+
+
 def composite_main(a, ap, region):
-    """composite: a window of the stack of --scene's streams -> OUT (a.src), with the optional count and validity."""
+    """composite: a window of the stack of --scene's streams -> OUT (a.src), with the optional count, validity and
+    source plane."""
     import contextlib
 
     import numpy as np
@@ -388,9 +400,15 @@ def composite_main(a, ap, region):
     from dsic_amd import codec
     if a.dst is not None or not a.scene or a.weights is None:
         ap.error("composite needs OUT, --weights and at least one --scene FILE[@Y,X]")
-    for path in (a.count_out, a.valid_out):
+    for path in (a.count_out, a.valid_out, a.source_out):
         if path is not None and not path.endswith(".npy"):
-            ap.error("--count-out and --valid-out take FILE.npy")
+            ap.error("--count-out, --valid-out and --source-out take FILE.npy")
+    ranked = a.reduce in ("max", "min")
+    if ranked != (a.index is not None):
+        ap.error("composite --reduce max and --reduce min take --index nd:A,B, difference:A,B or band:A, and no other reduce does")
+    if a.source_out is not None and a.reduce in ("mean", "median"):
+        ap.error("--source-out goes with --reduce first, last, max and min")
+    reduce = (a.reduce, parse_index(a, ap)) if ranked else a.reduce
     files, offsets = [], []
     for text in a.scene:
         path, _, pos = text.rpartition("@")
@@ -409,20 +427,22 @@ def composite_main(a, ap, region):
             if region is None:
                 region = (0, 0) + tuple(stack.levels[min(max(a.level, 0), len(stack.levels) - 1)])
             stats = {}
-            img, valid, count = stack.read(*region, level=a.level, reduce=a.reduce, fill=a.fill or 0, with_valid=True,
-                                           with_count=True, stats=stats)
+            img, valid, count, *source = stack.read(*region, level=a.level, reduce=reduce, fill=a.fill or 0, with_valid=True,
+                                                    with_count=True, stats=stats, with_source=a.source_out is not None)
         except ValueError as e:
             ap.error(str(e))
     if img.dtype != torch.uint8 and not a.src.endswith(".npy"):
         ap.error(f"{a.src}: a uint16 image is written as .npy only")
     path = write_image(a.src, img)
-    print(f"[dsic_image] {a.reduce} of {len(files)} scene(s) on a {stack.levels[0][0]}x{stack.levels[0][1]} grid, "
+    print(f"[dsic_image] {a.reduce}{' of ' + a.index if ranked else ''} of {len(files)} scene(s) on a {stack.levels[0][0]}x{stack.levels[0][1]} grid, "
           f"{len(stack.levels)} level(s): window {region[2]}x{region[3]} at ({region[0]}, {region[1]}) of level {a.level}, "
           f"{stats['parts']} scene(s) met, {len(stats['tiles'])} tile(s), {int(valid.sum())} valid pixel(s) -> {path}")
     if a.count_out is not None:
         np.save(a.count_out, count.cpu().numpy())
     if a.valid_out is not None:
         np.save(a.valid_out, valid.cpu().numpy())
+    if a.source_out is not None:
+        np.save(a.source_out, source[0].cpu().numpy())
 
 
 def print_info(ix):
@@ -531,8 +551,11 @@ def main(argv=None):
     ap.add_argument("--background", type=int, default=0, metavar="V", help="render: what invalid pixels show (0 .. 255)")
     ap.add_argument("--scene", action="append", default=None, metavar="FILE[@Y,X]",
                     help="composite: a scene's stream and its level-0 position in the stack's grid (default 0,0); repeatable")
-    ap.add_argument("--reduce", choices=("first", "last", "mean", "median"), default="first",
-                    help="composite: what a pixel takes from the scenes that are valid there")
+    ap.add_argument("--reduce", choices=("first", "last", "mean", "median", "max", "min"), default="first",
+                    help="composite: what a pixel takes from the scenes that are valid there; max and min: the whole pixel of "
+                         "the scene whose --index is largest or smallest")
+    ap.add_argument("--source-out", default=None, metavar="FILE.npy",
+                    help="composite: also write the number of the scene each pixel was taken from, uint8 [h,w], 255 = none")
     ap.add_argument("--count-out", default=None, metavar="FILE.npy",
                     help="composite: also write how many scenes counted per pixel, uint8 [h,w]")
     ap.add_argument("--min-nu", type=float, default=2.0)
@@ -554,8 +577,9 @@ def main(argv=None):
                       f"{tiles} tile(s)" + masked)
             print_info(ix)
         return
-    if a.mode != "composite" and (a.scene is not None or a.reduce != "first" or a.count_out is not None):
-        ap.error("--scene, --reduce and --count-out go with composite")
+    if a.mode != "composite" and (a.scene is not None or a.reduce != "first" or a.count_out is not None
+                                  or a.source_out is not None):
+        ap.error("--scene, --reduce, --count-out and --source-out go with composite")
     if a.mode != "composite" and (a.dst is None or a.weights is None):
         ap.error(f"{a.mode} needs a destination and --weights")
     region = None
@@ -579,8 +603,10 @@ def main(argv=None):
         ap.error("--scale goes with compress, or with --rotate")
     if a.mode == "composite":
         if (size is not None or a.rotate is not None or a.affine is not None or a.valid is not None or a.out is not None
-                or a.bands is not None or a.stretch is not None or a.index is not None or a.alpha):
-            ap.error("composite takes --scene, --reduce, --region, --level, --fill, --count-out and --valid-out")
+                or a.bands is not None or a.stretch is not None or a.alpha or a.colormap != "grey"
+                or a.index_stretch is not None):
+            ap.error("composite takes --scene, --reduce, --index, --region, --level, --fill, --count-out, --valid-out and "
+                     "--source-out")
         return composite_main(a, ap, region)
     matrix = warp_matrix(a, ap, region, size)
     if (a.valid is not None or a.fill is not None) and a.mode != "compress":

@@ -31,7 +31,8 @@ full level, with the kernels alone on the full level, scene and constant image. 
 alone.
 composite (--only composite alone; --size 1024 is the measured one): 16 uint16 x 4 synthetic scenes of --size, each with
 a validity mask of its own (blocks of 64 x 64 pixels, six in ten valid), coded once, as temporal stacks of the first 4,
-8 and 16.  Per n and mode: SceneStack.read of the whole grid from warm caches (the median wall clock of 7 calls, the
+8 and 16.  Per n and mode (first, last, mean, median, and max over ("nd", 3, 0) through
+dsic_window_composite_pick_u16, on the same inputs and under the median's byte model): SceneStack.read of the whole grid from warm caches (the median wall clock of 7 calls, the
 readers' window assembly included), dsic_window_composite_u16 alone on the readers' windows (device events, as above),
 the bytes that launch must move (the validity bytes it has to look at, the pixels it needs, the image it writes), and
 the same image built with torch.where / torch.sort on the padded int32 stack [n, H, W, C] (built outside the timing;
@@ -209,6 +210,9 @@ def _index_record(model, stream, img, win, batch, rounds=30):
     return rec
 
 
+MAX_INDEX = ("nd", 3, 0)                         # the index of the composite record's `max` rows
+
+
 def _composite_kernels(imgs, masks, size, C, reads=None):
     """dsic_window_composite_u16 alone on n = 4, 8, 16 full-cover sources (imgs uint16 [size, size, C], masks uint8
     [size, size]) per mode, the bytes it must move, and the same image from torch on the padded int32 stack.
@@ -229,7 +233,9 @@ def _composite_kernels(imgs, masks, size, C, reads=None):
         last = torch.where(k > 0, ok.flip(0).int().argmax(0) + 1, n)
         px, out_bytes = 2 * C, size * size * 2 * C
         need = {"first": (int(first.sum()), px * int((k > 0).sum())), "last": (int(last.sum()), px * int((k > 0).sum())),
-                "mean": (n * size * size, px * int(k.sum())), "median": (n * size * size, px * int(k.sum()))}
+                "mean": (n * size * size, px * int(k.sum())), "median": (n * size * size, px * int(k.sum())),
+                # max: all n validity bytes; bands a and b of every candidate fetch the lines of its pixel
+                "max": (n * size * size, px * int(k.sum()))}
 
         def by_torch(mode):
             if mode in ("first", "last"):
@@ -240,12 +246,24 @@ def _composite_kernels(imgs, masks, size, C, reads=None):
             kk = k.clamp(min=1)[..., None]
             if mode == "mean":
                 return torch.where(k[..., None] > 0, (2 * (vals * ok[..., None]).sum(0) + kk) // (2 * kk), 0)
+            if mode == "max":                                              # the largest nd of bands 3 and 0, the first of equals
+                A, s = vals[..., MAX_INDEX[1]], vals[..., MAX_INDEX[1]] + vals[..., MAX_INDEX[2]]
+                u = torch.where(ok & (s > 0), (40000 * A.long() + s) // (2 * s).clamp(min=1), -1)
+                key = u * n + (n - 1 - torch.arange(n, device=u.device)[:, None, None])      # one maximum per pixel
+                win = key.argmax(0)
+                img = torch.gather(vals, 0, win[None, ..., None].expand(1, size, size, C))[0]
+                return torch.where((u >= 0).any(0)[..., None], img, 0)
             v = torch.sort(torch.where(ok[..., None], vals, big), dim=0).values
             at = lambda idx: torch.gather(v, 0, idx.expand(1, size, size, C))[0]
             return torch.where(k[..., None] > 0, (at(((kk - 1) // 2)[None]) + at((kk // 2)[None]) + 1) >> 1, 0)
 
-        for mode, code in (("first", 0), ("last", 1), ("mean", 2), ("median", 3)):
+        for mode, code in (("first", 0), ("last", 1), ("mean", 2), ("median", 3), ("max", 4)):
             def launch(code=code):
+                if code == 4:                                              # DSIC_COMPOSITE_MAX: the pick export alone
+                    lib.check(L.dsic_window_composite_pick_u16(src, sv, rect, nodata, None, n, C, _p(dst), None, None, None,
+                                                               size, size, code, 2, MAX_INDEX[1], MAX_INDEX[2], 0, _stream()),
+                              "window_composite_pick_u16")
+                    return
                 lib.check(L.dsic_window_composite_u16(src, sv, rect, nodata, n, C, _p(dst), None, None, size, size, code, 0,
                                                       _stream()), "window_composite_u16")
             launch()
@@ -296,9 +314,10 @@ def _composite_record(size, tile, batch, kernel_size=4096):
     reads = {}
     for n in (4, 8, 16):
         stack = codec.SceneStack(readers[:n])
-        reads[n] = {mode: stack.read(*window, reduce=mode) for mode in ("first", "last", "mean", "median")}
+        reduces = {"first": "first", "last": "last", "mean": "mean", "median": "median", "max": ("max", MAX_INDEX)}
+        reads[n] = {mode: stack.read(*window, reduce=reduce) for mode, reduce in reduces.items()}
         for mode in reads[n]:
-            calls = sorted(_frame_ms(lambda: stack.read(*window, reduce=mode)) for _ in range(7))
+            calls = sorted(_frame_ms(lambda: stack.read(*window, reduce=reduces[mode])) for _ in range(7))
             rec["read"][f"n={n} {mode}"] = {"read_median_ms": round(calls[3], 3)}
     rec["kernel_on_the_scenes"] = _composite_kernels([p[0] for p in parts], [p[1].to(torch.uint8) for p in parts], size, C, reads)
     for r in readers:
