@@ -3,8 +3,8 @@
 Each function gives the selected part of one kernel's output (a tile row, a band of output rows, a window) and asks its
 source for rows by number; it never holds the image.  None of them states a kernel's arithmetic: each cuts the rows the
 part depends on out of the source and hands them, with their origin, to the full restatement of codec_ref, u16_ref,
-pyramid_ref, valid_ref, mask_ref, view_ref or render_ref.  test_big_scene_cpu.py shows on small images that every part
-equals the same part of the full restatement.
+pyramid_ref, valid_ref, mask_ref, view_ref, render_ref, warp_ref, index_ref, composite_ref or best_pixel_ref.
+test_big_scene_cpu.py shows on small images that every part equals the same part of the full restatement.
 
 A source has H, W, C, kind ("u8", "u16" HWC; "f32" CHW), rows(ys) -> the rows ys in that layout, and valid(ys) -> uint8
 [len(ys)][W].  ArraySource wraps a host array, SceneSource a closed-form scene of big_scene.py.
@@ -13,14 +13,18 @@ import functools
 
 import numpy as np
 
+import best_pixel_ref
 import blend_ref
 import codec_ref
+import composite_ref
+import index_ref
 import mask_ref
 import pyramid_ref
 import render_ref
 import u16_ref
 import valid_ref
 import view_ref
+import warp_ref
 
 
 class ArraySource:
@@ -190,6 +194,97 @@ def render(src, with_valid, shift, region, size, bands, pairs, mode, nodata, alp
     ys = np.arange(ya, yb)
     return render_ref.render(src.rows(ys), src.valid(ys) if with_valid else None, ya, 0, shift, region, size, bands,
                              pairs, mode, nodata, alpha, background)
+
+
+def index_render(src, with_valid, shift, region, size, index, pair, cmap, mode, nodata, alpha, background):
+    """the index view of the same window: the resample of valid_ref (a validity window) or view_ref, then
+    index_ref.display_index, as test_gpu_index.py pairs them"""
+    ya, yb = _level_rows(src.H, shift, region)
+    ys = np.arange(ya, yb)
+    if with_valid:
+        res, ok = valid_ref.resample(src.rows(ys), src.valid(ys), ya, 0, shift, region, size, mode, 0)
+    else:
+        res, ok = view_ref.resample(src.rows(ys), ya, 0, shift, region, size, mode, nodata if mode == "average" else None), None
+    return index_ref.display_index(res, ok, index, pair, cmap, alpha, background)
+
+
+# ---- warped reads of a whole level ----------------------------------------------------------------------------------
+def warp_image(src, l):
+    """(H, W) of the level-0 image whose level l the source is: warp_ref.image_size of its sides"""
+    return warp_ref.image_size(src.H, l), warp_ref.image_size(src.W, l)
+
+
+def warp(src, l, m, size, mode, with_valid=False, nodata=None, fill=0):
+    """warp_ref.warp with the whole source as the level-l window at (0, 0): only the rows of warp_ref.warp_window are
+    cut out, those of the cubic taps for every mode (they hold the others', and warp_ref.warp asserts that every tap
+    lies inside what it was given), so that the modes of one view ask the source for the same rows"""
+    H, W = warp_image(src, l)
+    win = warp_ref.warp_window(l, src.H, src.W, H, W, m, *size, 2) or (0, 0, 1, 1)
+    ys = np.arange(win[0], win[0] + win[2])
+    return warp_ref.warp(src.rows(ys), src.valid(ys) if with_valid else None, win[0], 0, l, src.H, src.W, H, W, m, size, mode,
+                         nodata, fill)
+
+
+def warp_render(src, l, m, size, mode, with_valid, nodata, bands, pairs, alpha, background):
+    res, ok = warp(src, l, m, size, mode, with_valid, nodata, 0)
+    return render_ref.display(res, ok, bands, pairs, alpha, background)
+
+
+def warp_index(src, l, m, size, mode, with_valid, nodata, index, pair, cmap, alpha, background):
+    res, ok = warp(src, l, m, size, mode, with_valid, nodata, 0)
+    return index_ref.display_index(res, ok, index, pair, cmap, alpha, background)
+
+
+def warp_rows(img, val, geometry, m, size, mode, nodata, fill, i0, i1, j0=0, j1=None):
+    """Output rows [i0, i1) (columns [j0, j1) of them) of the warped view of a small host image, the whole level l:
+    geometry = (l, LH, LW, H, W).  The view with m2 + m0 i0 + m1 j0 and m5 + m3 i0 + m4 j0 in the place of m2 and m5,
+    exactly: P is affine in i and j, and m0 (2 (i + i0) + 1) + 2 m2 = m0 (2 i + 1) + 2 (m2 + m0 i0)."""
+    l, LH, LW, H, W = geometry
+    j1 = size[1] if j1 is None else j1
+    assert 0 <= i0 < i1 <= size[0] and 0 <= j0 < j1 <= size[1] and img.shape[:2] == (LH, LW)
+    moved = (m[0], m[1], m[2] + m[0] * i0 + m[1] * j0, m[3], m[4], m[5] + m[3] * i0 + m[4] * j0)
+    return warp_ref.warp(img, val, 0, 0, l, LH, LW, H, W, moved, (i1 - i0, j1 - j0), mode, nodata, fill)
+
+
+# ---- composites -----------------------------------------------------------------------------------------------------
+class NoValidity:
+    """a source handed to the composite without its validity window"""
+
+    def __init__(self, src):
+        self.rows, self.valid = src.rows, None
+
+
+def _validity(s, ys):
+    if s.valid is None or (isinstance(s, ArraySource) and s.val is None):
+        return None
+    return s.valid(ys)
+
+
+def composite_rows(sources, rects, nodata, ids, C, oh, ow, mode, index, fill, y0, y1):
+    """Output rows [y0, y1) of a composite of placed sources (anything with rows(ys) and valid(ys); valid = None: no
+    validity window): every source is cut to the band and its rect moved, one that misses the band is dropped, the
+    others keep their order and ids.  index = None: composite_ref.composite -> (dst, valid, count); else
+    best_pixel_ref.pick -> (dst, valid, count, source).  A band that no source meets has no candidate anywhere, which
+    both restatements give for a source that is nowhere valid: the first source's first row stands in, invalid."""
+    assert 0 <= y0 < y1 <= oh
+    srcs, vals, cut, nds, kept = [], [], [], [], []
+    for k, (s, (dy, dx, h, w)) in enumerate(zip(sources, rects)):
+        a, b = max(dy, y0), min(dy + h, y1)
+        if a < b:
+            ys = np.arange(a - dy, b - dy)
+            srcs.append(s.rows(ys))
+            vals.append(_validity(s, ys))
+            cut.append((a - y0, dx, b - a, w))
+            nds.append(nodata[k])
+            kept.append(k)
+    if not srcs:
+        dy, dx, h, w = rects[0]
+        srcs, cut, nds, kept = [sources[0].rows(np.arange(1))], [(0, dx, 1, w)], [nodata[0]], [0]
+        vals = [np.zeros((1, w), dtype=np.uint8)]
+    if index is None:
+        return composite_ref.composite(srcs, vals, cut, nds, C, y1 - y0, ow, mode, fill)
+    return best_pixel_ref.pick(srcs, vals, cut, nds, [k if ids is None else ids[k] for k in kept], C, y1 - y0, ow, mode, index,
+                               fill)                                            # without ids a source's id is its position
 
 
 # ---- writers ------------------------------------------------------------------------------------------------------

@@ -155,6 +155,17 @@ class Scene:
         h = self.H if rows is None else rows
         return (self.C, h, self.W) if self.layout == "chw" else (h, self.W, self.C)
 
+    def samples(self, xp, y, x, c):
+        """The formula with the planted nodata value, without the single plants, at broadcastable coordinates -> int64:
+        what rows() evaluates, and what a read at any other offset of the image would find."""
+        v = value(y, x, c, self.kind)
+        if self.nodata is not None:
+            cls = nodata_class(y, x)
+            # a pixel that must not be nodata gets channel 0 moved off the value; it costs nothing elsewhere
+            off = (self.nodata + 1) % (256 if self.kind == "u8" else 65536)
+            v = xp.where(cls == 0, v * 0 + self.nodata, xp.where((cls == 1) & (c == 0) & (v == self.nodata), v * 0 + off, v))
+        return v
+
     def rows(self, xp, ys):
         """The samples of the rows `ys` (any order, repeats allowed): [len(ys)][W][C], or [C][len(ys)][W] for CHW."""
         ys = np.asarray(ys, dtype=np.int64)
@@ -163,12 +174,7 @@ class Scene:
             y, x, c = y[None, :, None], x[None, None, :], c[:, None, None]
         else:
             y, x, c = y[:, None, None], x[None, :, None], c[None, None, :]
-        v = value(y, x, c, self.kind)
-        if self.nodata is not None:
-            cls = nodata_class(y, x)
-            # a pixel that must not be nodata gets channel 0 moved off the value; it costs nothing elsewhere
-            off = (self.nodata + 1) % (256 if self.kind == "u8" else 65536)
-            v = xp.where(cls == 0, v * 0 + self.nodata, xp.where((cls == 1) & (c == 0) & (v == self.nodata), v * 0 + off, v))
+        v = self.samples(xp, y, x, c)
         for py, px, pc, pv in self.plants:
             for k in np.flatnonzero(ys == py):
                 if self.layout == "chw":
