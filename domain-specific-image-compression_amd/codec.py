@@ -92,6 +92,8 @@ assembled by the calls decompress_region makes (_assemble_window), requests deco
 resampled to a size asked for from the level view_level picks (csrc/view.hip).  SceneStack (view.py) places several
 readers on one grid and composites their windows per pixel in one launch (csrc/composite.hip): first, last, mean,
 median, or the whole pixel of the scene whose index is largest or smallest (stack_reduce names the forms).
+SceneStack.read_warped samples every scene under its own affine and combines them in the same launch
+(csrc/warp_composite.hip; compose_q16 and stack_warp_parts are its planning).
 """
 from __future__ import annotations
 
@@ -1477,3 +1479,4 @@ from .view import ImageReader, stretch_from_histogram, view_level  # noqa: E402 
 from .view import affine_q16, rotation_affine, warp_level, warp_window, window_affine  # noqa: E402
 from .view import COLORMAPS, colormap_from_anchors  # noqa: E402
 from .view import SceneStack, stack_levels, stack_parts, stack_reduce  # noqa: E402
+from .view import check_q16, compose_q16, stack_warp_parts  # noqa: E402

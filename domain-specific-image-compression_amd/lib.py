@@ -168,6 +168,8 @@ SIGNATURES = {
     "dsic_window_composite_u16": (c_int, [_P, _P, _P, _P, c_int, c_int, _P, _P, _P] + [c_int] * 4 + [_P]),
     "dsic_window_composite_pick_u8": (c_int, [_P, _P, _P, _P, _P, c_int, c_int, _P, _P, _P, _P] + [c_int] * 7 + [_P]),
     "dsic_window_composite_pick_u16": (c_int, [_P, _P, _P, _P, _P, c_int, c_int, _P, _P, _P, _P] + [c_int] * 7 + [_P]),
+    "dsic_window_warp_composite_u8": (c_int, [_P, c_int, c_int, _P, _P, _P, _P] + [c_int] * 8 + [_P]),
+    "dsic_window_warp_composite_u16": (c_int, [_P, c_int, c_int, _P, _P, _P, _P] + [c_int] * 8 + [_P]),
     "dsic_stream_create_masked":(c_int, [_P, c_int, _P]),
     "dsic_stream_destroy": (c_int, [_P]),
     "dsic_range_decode": (c_int, [_P, c_int64, _P, c_int, c_int, _P, c_int, _P, c_int, c_int, c_int,
@@ -179,6 +181,16 @@ SIGNATURES = {
     "dsic_host_pmf_to_uint16_cdf": (c_int, [_P, c_int, c_int, _P]),
     "dsic_host_cdf_table": (c_int, [c_int, ctypes.c_float, ctypes.c_float, c_int, c_int, _P, _P]),
 }
+
+
+class WarpSource(ctypes.Structure):
+    """dsic_warp_source of include/dsic_hip.h: one scene of a dsic_window_warp_composite_u8 / _u16 call.  A host array of
+    them is (WarpSource * n)(...)."""
+    _fields_ = ([("src", c_void_p), ("src_valid", c_void_p)]
+                + [(name, c_int) for name in ("sh", "sw", "sy0", "sx0", "shift", "LH", "LW", "H", "W", "nodata", "id",
+                                              "reserved")]
+                + [("m", c_int64 * 6)])
+
 
 _lib = None
 

@@ -15,6 +15,9 @@ index_stretch derive its stretch from the data, colormap_from_anchors and COLORM
 SceneStack places several readers on one grid, a mosaic or a temporal stack, and combines the parts they serve of a
 window in one launch (csrc/composite.hip): first, last, mean or median over the scenes that are valid at a pixel, or the
 whole pixel of the scene whose index (an NDVI, say) is largest or smallest there, with the scene's number beside it.
+Its read_warped, render_warped and render_index_warped do that for an affine view: the view's matrix composed with every
+scene's own (compose_q16), the scenes it meets planned as a reader plans a warped read (stack_warp_parts), and one
+launch that samples every scene and reduces the samples (csrc/warp_composite.hip).
 
 The cache holds what the stitch and blend calls consume: per (level, tile) the tile's g_s output, float32
 [C, th, tw], not clamped, and for a near-lossless level its q plane.  A window is served by collecting its tiles, in
@@ -90,6 +93,18 @@ def check_q16(m) -> tuple:
         if k % 3 != 2 and abs(v) > WARP_COEF:
             raise ValueError(f"affine matrix: the coefficient {v} / 65536 must be at most 1024 in size")
     return m
+
+
+def compose_q16(scene_q16, view_q16) -> tuple:
+    """The Q16 matrix of a scene under a view (pure Python integers).  scene_q16 = A: scene level-0 pixels per grid pixel;
+    view_q16 = V: grid pixels per output pixel; both within check_q16's bounds.  With rnd(x) = (x + 32768) >> 16,
+    M0 = rnd(A0 V0 + A1 V3), M1 = rnd(A0 V1 + A1 V4), M2 = rnd(A0 V2 + A1 V5) + A2, and M3 .. M5 likewise from A3, A4, A5:
+    output pixel -> scene level-0 position, the product rounded once per entry.  A scene at the integer offset (oy, ox),
+    A = (65536, 0, -oy 65536, 0, 65536, -ox 65536), composes exactly.  ValueError (check_q16's) if the result leaves the
+    bounds."""
+    A, V = check_q16(scene_q16), check_q16(view_q16)
+    rnd = lambda x: (x + 32768) >> 16
+    return check_q16(tuple(rnd(A[r] * V[c] + A[r + 1] * V[3 + c]) + (A[r + 2] if c == 2 else 0) for r in (0, 3) for c in range(3)))
 
 
 def window_affine(y0, x0, h, w, oh, ow) -> list:
@@ -1192,15 +1207,37 @@ def stack_parts(level, scenes, window) -> list:
     return parts
 
 
+def stack_warp_parts(scenes, view_q16, size, mode) -> list:
+    """The scenes an affine view of a stack's grid meets (pure Python).  scenes: per scene (its Q16 matrix A, scene
+    level-0 pixels per grid pixel, and its reader's level shapes, level 0 first); view_q16: grid pixels per output pixel;
+    size = (oh, ow); mode: 0 bilinear, 1 nearest, 2 cubic, or the resampling's name.  Per scene that the view meets, in
+    list order: (scene number, M = compose_q16(A, view_q16), level = warp_level(number of levels, M), the window of that
+    level warp_window gives).  A scene whose warp_window is None, wholly beside the view, is left out."""
+    oh, ow = _check_size(size, "stack_warp_parts", WARP_SIDE, "(1, 1) .. (2^20, 2^20)")
+    mode = WARP_RESAMPLING.get(mode, mode) if isinstance(mode, str) else mode
+    parts = []
+    for s, (A, levels) in enumerate(scenes):
+        m = compose_q16(A, view_q16)
+        level = warp_level(len(levels), m)
+        lw = warp_window(level, *levels[level], *levels[0], m, oh, ow, mode)
+        if lw is not None:
+            parts.append((s, m, level, lw))
+    return parts
+
+
 class SceneStack:
-    """Several open ImageReaders as one picture: SceneStack(readers, offsets=None, shape=None).
+    """Several open ImageReaders as one picture: SceneStack(readers, offsets=None, shape=None, placements=None).
     readers: 1 .. 16 open ImageReaders of one integer kind (uint8 or uint16) and one band count; a float32-kind stream
     is a ValueError.  offsets: one (oy, ox) >= 0 per reader, the level-0 position of that scene in the stack's grid;
     the default, all (0, 0), is a temporal stack.  shape: (H, W) of the grid, default the bounding box; a scene that
     leaves it is a ValueError.  levels: the level shapes stack_levels gives.  The stack does not own the readers: it
-    closes none, and a read through a closed one is the reader's ValueError."""
+    closes none, and a read through a closed one is the reader's ValueError.
+    placements (instead of offsets; needs shape): one 2 x 3 matrix per reader in affine_q16's convention, scene level-0
+    pixels per grid pixel, quantised once with affine_q16: scenes that differ in resolution or orientation, or lie a
+    fraction of a pixel apart.  Such a stack has the single level `shape` and serves the warped methods only
+    (read_warped, render_warped, render_index_warped)."""
 
-    def __init__(self, readers, offsets=None, shape=None):
+    def __init__(self, readers, offsets=None, shape=None, placements=None):
         what = "SceneStack"
         self.readers = list(readers)
         if not 1 <= len(self.readers) <= MAX_SCENES:
@@ -1212,9 +1249,25 @@ class SceneStack:
             raise ValueError(f"{what}: the readers must be of one kind and one band count, got "
                              f"{[('u16' if r.kind == _c.KIND_U16_HWC else 'u8', r.shape[2]) for r in self.readers]}")
         self.kind, self.C = kinds.pop(), self.readers[0].shape[2]
-        self.offsets = _offsets(offsets, len(self.readers), what)
-        self._scenes = [(o, r.levels) for o, r in zip(self.offsets, self.readers)]
-        self.levels = stack_levels([lv for _, lv in self._scenes], self.offsets, shape)
+        self.placements = None
+        if placements is not None:
+            if offsets is not None:
+                raise ValueError(f"{what}: placements and offsets exclude each other")
+            if shape is None:
+                raise ValueError(f"{what}: placements need shape=(H, W), the grid they place the scenes on")
+            placements = list(placements)
+            if len(placements) != len(self.readers):
+                raise ValueError(f"{what}: {len(placements)} placements for {len(self.readers)} readers")
+            self.placements = [affine_q16(m) for m in placements]
+            self.offsets, self._scenes = None, None
+            self.levels = [_check_size(shape, what)]
+            self._warp_scenes = [(m, r.levels) for m, r in zip(self.placements, self.readers)]
+        else:
+            self.offsets = _offsets(offsets, len(self.readers), what)
+            self._scenes = [(o, r.levels) for o, r in zip(self.offsets, self.readers)]
+            self.levels = stack_levels([lv for _, lv in self._scenes], self.offsets, shape)
+            self._warp_scenes = [(check_q16((65536, 0, -oy * 65536, 0, 65536, -ox * 65536)), r.levels)
+                                 for (oy, ox), r in zip(self.offsets, self.readers)]
         self._dev = self.readers[0]._dev
         self._dtype = torch.uint16 if self.kind == _c.KIND_U16_HWC else torch.uint8
         self._cmaps = {}                                           # name -> the colour map on the device
@@ -1224,6 +1277,9 @@ class SceneStack:
         return self.levels[0] + (self.C,)
 
     def _check_window(self, what, window, level, reduce):
+        if self.placements is not None:
+            raise ValueError(f"{what}: a stack with placements has no common pixel grid to cut windows from; take "
+                             "read_warped (render_warped, render_index_warped)")
         try:
             level = operator.index(level)
             window = tuple(operator.index(v) for v in window)
@@ -1336,21 +1392,9 @@ class SceneStack:
         stretch: a ValueError without one."""
         what = "SceneStack.render"
         level, window, code = self._check_window(what, (y0, x0, h, w), level, reduce)
-        top = 65535 if self.kind == _c.KIND_U16_HWC else 255
-        bands, stretch, background = _display_args(what, self.C, top, bands, stretch, background)
-        if stretch is None:
-            if top == 65535:
-                raise ValueError(f"{what}: a uint16 stack needs stretch=: it has no histogram of its own (a reader's "
-                                 "stretch() gives one scene's)")
-            stretch = [(0, 255)] * self.C
-        alpha = int(bool(alpha))
+        show = self._display_args(what, bands, stretch, alpha, background)
         img, valid, _, _ = self._composite(window, level, code, 0, True, False, None)
-        y0, x0, h, w = window
-        dst = torch.empty((h, w, len(bands) + alpha), dtype=torch.uint8, device=self._dev)
-        _call_by_width("window_render", img, _p(valid), h, w, y0, x0, self.C, 0, y0, x0, h, w,
-                       (ctypes.c_int * len(bands))(*bands), len(bands), _c._lohi(stretch), _p(dst), h, w,
-                       RESAMPLING["nearest"], -1, alpha, background, _stream())
-        return dst
+        return self._display(img, valid, window[0], window[1], *show)
 
     @torch.no_grad()
     def render_index(self, y0, x0, h, w, index, level=0, reduce="first", stretch=None, colormap="grey", alpha=False,
@@ -1367,6 +1411,34 @@ class SceneStack:
         maps are kept on the device, once per stack."""
         what = "SceneStack.render_index"
         level, window, code = self._check_window(what, (y0, x0, h, w), level, reduce)
+        show = self._index_args(what, index, stretch, colormap, alpha, background)
+        img, valid, _, _ = self._composite(window, level, code, 0, True, False, None)
+        return self._index_display(img, valid, window[0], window[1], *show)
+
+    # ---- the display tails, shared by the window methods and the warped ones -------------------------------------
+    def _display_args(self, what, bands, stretch, alpha, background):
+        """render's display arguments, checked -> (bands, stretch, alpha, background)"""
+        top = 65535 if self.kind == _c.KIND_U16_HWC else 255
+        bands, stretch, background = _display_args(what, self.C, top, bands, stretch, background)
+        if stretch is None:
+            if top == 65535:
+                raise ValueError(f"{what}: a uint16 stack needs stretch=: it has no histogram of its own (a reader's "
+                                 "stretch() gives one scene's)")
+            stretch = [(0, 255)] * self.C
+        return bands, stretch, int(bool(alpha)), background
+
+    def _display(self, img, valid, y0, x0, bands, stretch, alpha, background):
+        """A composite [h, w, C] with its uint8 validity, cut at (y0, x0), through one dsic_window_render_u8 / _u16 call
+        at identity geometry."""
+        h, w = img.shape[:2]
+        dst = torch.empty((h, w, len(bands) + alpha), dtype=torch.uint8, device=self._dev)
+        _call_by_width("window_render", img, _p(valid), h, w, y0, x0, self.C, 0, y0, x0, h, w,
+                       (ctypes.c_int * len(bands))(*bands), len(bands), _c._lohi(stretch), _p(dst), h, w,
+                       RESAMPLING["nearest"], -1, alpha, background, _stream())
+        return dst
+
+    def _index_args(self, what, index, stretch, colormap, alpha, background):
+        """render_index's arguments, checked -> ((kind, a, b), stretch, the colour map on the device, alpha, background)"""
         top = 65535 if self.kind == _c.KIND_U16_HWC else 255
         (kind, a, b), stretch, colormap, background = _index_args(what, self.C, top, index, stretch, colormap, background)
         if stretch is None:
@@ -1374,11 +1446,122 @@ class SceneStack:
                 raise ValueError(f"{what}: a uint16 stack needs stretch=: it has no histogram of its own (a reader's "
                                  "stretch() gives one scene's)")
             stretch = index_range(kind, top)
-        alpha = int(bool(alpha))
-        cmap = _device_colormap(self._cmaps, colormap, self._dev)
-        img, valid, _, _ = self._composite(window, level, code, 0, True, False, None)
-        y0, x0, h, w = window
+        return (kind, a, b), stretch, _device_colormap(self._cmaps, colormap, self._dev), int(bool(alpha)), background
+
+    def _index_display(self, img, valid, y0, x0, index, stretch, cmap, alpha, background):
+        """As _display, through one dsic_window_index_render_u8 / _u16 call."""
+        h, w = img.shape[:2]
+        kind, a, b = index
         dst = torch.empty((h, w, 3 + alpha), dtype=torch.uint8, device=self._dev)
         _call_by_width("window_index_render", img, _p(valid), h, w, y0, x0, self.C, 0, y0, x0, h, w, INDEX_KINDS[kind], a, b,
                        *stretch, _p(cmap), _p(dst), h, w, RESAMPLING["nearest"], -1, alpha, background, _stream())
         return dst
+
+    # ---- warped views: every scene under its own affine, csrc/warp_composite.hip -----------------------------------
+    def _check_warp(self, what, matrix, size, reduce, resampling):
+        """A warped request -> (the view's Q16 matrix, (oh, ow), the sample mode, stack_reduce's code)"""
+        if resampling not in WARP_RESAMPLING:
+            raise ValueError(f"{what}: resampling={resampling!r} ({', '.join(WARP_RESAMPLING)})")
+        v = affine_q16(matrix)
+        oh, ow = _check_size(size, what, WARP_SIDE, "(1, 1) .. (2^20, 2^20)")
+        if oh * ow >= 1 << 31:
+            raise ValueError(f"{what}: size ({oh}, {ow}) must stay under 2^31 pixels")
+        return v, (oh, ow), WARP_RESAMPLING[resampling], stack_reduce(reduce, self.C, what)
+
+    def _warp_composite(self, v, size, mode, code, fill, with_valid, with_count, with_source, stats):
+        """_composite for an affine view: (image, uint8 validity or None, uint8 counts or None, uint8 scene numbers or
+        None) of one dsic_window_warp_composite_u8 / _u16 call over the scenes stack_warp_parts names."""
+        oh, ow = size
+        reduce_mode, kind, a, b = code
+        top = 65535 if self.kind == _c.KIND_U16_HWC else 255
+        try:
+            fill = operator.index(fill)
+        except TypeError:
+            raise ValueError(f"SceneStack: fill={fill!r} is not an integer") from None
+        if not 0 <= fill <= top:
+            raise ValueError(f"SceneStack: fill={fill} must be in 0 .. {top}")
+        parts = stack_warp_parts(self._warp_scenes, v, size, mode)
+        total = dict(_new_stats(), parts=len(parts), view_q16=v, scenes=[s for s, _, _, _ in parts],
+                     levels=[level for _, _, level, _ in parts], level_windows=[lw for _, _, _, lw in parts],
+                     matrix_q16=[m for _, m, _, _ in parts])
+        table, keep = (_lib.WarpSource * max(len(parts), 1))(), []
+        for at, (s, m, level, lw) in enumerate(parts):
+            r = self.readers[s]
+            before, st = r._source.bytes_read, _new_stats()
+            r._level(level)
+            img, valid = r._source_window(level, lw, None, st)      # as ImageReader.read_warped brings its window in
+            r._finish(st, before, None)
+            for key in _COUNTERS:
+                total[key] += st[key]
+            total["tiles"] += [(s,) + t for t in st["tiles"]]
+            keep.append((img, valid))
+            table[at] = _lib.WarpSource(_p(img), _opt(valid), lw[2], lw[3], lw[0], lw[1], level, *r.levels[level], *r.levels[0],
+                                        r._open[level][1].get("nodata", -1), s, 0, (ctypes.c_int64 * 6)(*m))
+        if stats is not None:
+            stats.update(total)
+        if not parts:                                              # no scene under the view: nothing to launch
+            img = torch.from_numpy(np.full((oh, ow, self.C), fill, dtype=np.uint16 if top == 65535 else np.uint8)).to(self._dev)
+            plane = lambda want, v=0: torch.full((oh, ow), v, dtype=torch.uint8, device=self._dev) if want else None
+            return img, plane(with_valid), plane(with_count), plane(with_source, NO_SOURCE)
+        dst = torch.empty((oh, ow, self.C), dtype=self._dtype, device=self._dev)
+        dval = torch.empty((oh, ow), dtype=torch.uint8, device=self._dev) if with_valid else None
+        dcnt = torch.empty((oh, ow), dtype=torch.uint8, device=self._dev) if with_count else None
+        dsrc = torch.empty((oh, ow), dtype=torch.uint8, device=self._dev) if with_source else None
+        what = "window_warp_composite" + ("_u16" if top == 65535 else "_u8")
+        status = getattr(_lib.load(), "dsic_" + what)(table, len(parts), self.C, _p(dst), _opt(dval), _opt(dcnt), _opt(dsrc),
+                                                      oh, ow, mode, reduce_mode, kind, a, b, fill, _stream())
+        _lib.check(status, what)
+        return dst, dval, dcnt, dsrc
+
+    @torch.no_grad()
+    def read_warped(self, matrix, size, reduce="first", resampling="bilinear", fill=0, with_valid=False, with_count=False,
+                    with_source=False, stats=None):
+        """An affine view of the stack: [oh, ow, C] of the readers' kind on the device, size = (oh, ow).  matrix: 2 x 3
+        in (row, column) order, grid pixels per output pixel, as ImageReader.read_warped takes level-0 pixels per output
+        pixel; window_affine and rotation_affine build it.  It is quantised once (affine_q16) and composed with every
+        scene's own matrix (compose_q16): a scene at an offset, or a placed one, is sampled at its own positions, from
+        the level its own scale asks for (stack_warp_parts), with resampling "bilinear", "cubic" or "nearest" as
+        ImageReader.read_warped defines them.  Each scene's window comes in through its reader's cache with its validity
+        or nodata value; one launch (dsic_window_warp_composite_u8 / _u16) then samples every scene and combines the
+        samples per pixel with `reduce`, read's reduces with read's rules: the result is, bit for bit, read's composite
+        of the images reader.read_warped(scene matrix, size, with_valid=True) would give, which never reach memory.
+        The view window_affine(y0, x0, h, w, h, w) of a stack with offsets is read(y0, x0, h, w) for nearest and
+        bilinear.  fill, with_valid, with_count, with_source and the order of the results are read's; a view that meets
+        no scene launches nothing.
+        stats (a dict) receives the readers' summed counters and tiles as read's does, parts, and per part scenes,
+        levels, level_windows and matrix_q16, with view_q16.
+        ValueError for a matrix or size out of bounds (a composed matrix among them), oh ow >= 2^31, an unknown
+        resampling or reduce, with_source with mean or median, a fill beyond the kind, and whatever a reader raises."""
+        what = "SceneStack.read_warped"
+        v, size, mode, code = self._check_warp(what, matrix, size, reduce, resampling)
+        if with_source and code[0] in (REDUCE["mean"], REDUCE["median"]):
+            raise ValueError(f"{what}: with_source goes with first, last, max and min; reduce={reduce!r} mixes scenes")
+        img, valid, count, source = self._warp_composite(v, size, mode, code, fill, with_valid, with_count, with_source, stats)
+        out = (img,) + ((valid.bool(),) if with_valid else ()) + ((count,) if with_count else ()) + \
+            ((source,) if with_source else ())
+        return out if len(out) > 1 else img
+
+    @torch.no_grad()
+    def render_warped(self, matrix, size, reduce="first", bands=None, stretch=None, alpha=False, background=0,
+                      resampling="bilinear"):
+        """read_warped(matrix, size, reduce, resampling) as display pixels: torch.uint8 [oh, ow, nb (+ 1)].  The composite
+        with its validity goes through one dsic_window_render_u8 / _u16 call at identity geometry, exactly as render's
+        does: bands, stretch, alpha, background, their defaults and their errors are render's."""
+        what = "SceneStack.render_warped"
+        v, size, mode, code = self._check_warp(what, matrix, size, reduce, resampling)
+        show = self._display_args(what, bands, stretch, alpha, background)
+        img, valid, _, _ = self._warp_composite(v, size, mode, code, 0, True, False, False, None)
+        return self._display(img, valid, 0, 0, *show)
+
+    @torch.no_grad()
+    def render_index_warped(self, matrix, size, index, reduce="first", stretch=None, colormap="grey", alpha=False,
+                            background=0, resampling="bilinear"):
+        """read_warped(matrix, size, reduce, resampling) as an index view: torch.uint8 [oh, ow, 3 (+ 1)].  The composite
+        with its validity goes through one dsic_window_index_render_u8 / _u16 call at identity geometry, exactly as
+        render_index's does: index, stretch, colormap, alpha, background, their defaults and their errors are
+        render_index's."""
+        what = "SceneStack.render_index_warped"
+        v, size, mode, code = self._check_warp(what, matrix, size, reduce, resampling)
+        show = self._index_args(what, index, stretch, colormap, alpha, background)
+        img, valid, _, _ = self._warp_composite(v, size, mode, code, 0, True, False, False, None)
+        return self._index_display(img, valid, 0, 0, *show)

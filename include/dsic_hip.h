@@ -1080,6 +1080,56 @@ int dsic_window_composite_pick_u16(const uint16_t* const* src, const uint8_t* co
                                    uint8_t* dst_source, int oh, int ow, int mode, int kind, int a,
                                    int b, int fill, void* stream);
 
+/* ---- warped scene stacks (codec.SceneStack.read_warped, .render_warped, .render_index_warped) ----
+ * dsic_window_warp_composite_u8 / _u16: n scenes, 1..16, each under its own affine, sampled and
+ *   combined per output pixel in one launch, without a workspace and without an intermediate in
+ *   memory.  sources is a host array of n dsic_warp_source structs, read before the call returns
+ *   (one struct per source rather than parallel arrays: one ctypes.Structure on the Python side).
+ *   A source carries what dsic_window_warp_u8 / _u16 take for one scene: src (a device window
+ *   [sh][sw][C] of the export's element type), src_valid (NULL: none), sh, sw, sy0, sx0, shift, LH,
+ *   LW, H, W and its own Q16 matrix m[6] (output pixel -> that scene's level-0 position); nodata
+ *   (-1: none); the id (0..254) that dst_source names it by; reserved is 0.  Shared: C, oh, ow,
+ *   fill, sample_mode (0 bilinear, 1 nearest, 2 cubic, as the warp calls number their mode),
+ *   reduce_mode (DSIC_COMPOSITE_FIRST, _LAST, _MEAN, _MEDIAN, _MAX or _MIN) and (kind, a, b), the
+ *   index of the two ranked modes (ignored for the others).  Outputs: dst_hwc [oh][ow][C] and the
+ *   optional uint8 planes dst_valid, dst_count and dst_source [oh][ow] (NULL: not wanted).
+ *
+ *   The result is defined as the chain of the exports above, bit for bit:
+ *   1. for each source i, dsic_window_warp_u8 / _u16 with that source's arguments, mode =
+ *      sample_mode, any fill and a dst_valid gives an oh x ow image S_i and its validity V_i;
+ *   2. dsic_window_composite_u8 / _u16 (first, last, mean, median) or
+ *      dsic_window_composite_pick_u8 / _u16 (max, min, and any call with dst_source) over the n
+ *      pairs (S_i, V_i), each with the rect (0, 0, oh, ow), nodata[i] and id[i], with mode =
+ *      reduce_mode, (kind, a, b) and fill, gives dst_hwc, dst_valid, dst_count and dst_source.
+ *   So a source with src_valid ignores its nodata value under the taps, as step 1 does, and a
+ *   sampled pixel whose C channels all equal nodata is no candidate, as step 2 has it.  The
+ *   candidate rule, the rounding of mean, the median of an even count, the index and its defined
+ *   values, the first of ties, fill and source 255 where k = 0 are those stated for the composite
+ *   and pick calls above.  All buffers at any element alignment.
+ *   DSIC_EINVAL, nothing written, in the words of the calls of the chain where one applies: n
+ *   outside 1..16; a null sources or dst_hwc; C outside 3..4 (u8), 1..4 (u16); sample_mode outside
+ *   0..2; oh or ow outside 1..2^20 or oh ow >= 2^31; reduce_mode outside 0..5; for max and min a
+ *   kind outside the three or a band outside 0..C-1; dst_source with mean or median; fill beyond
+ *   the element type; misaligned dst_hwc; outputs that overlap; then per source, named by its
+ *   number: a null src; what the warp calls refuse of shift, H, W, LH, LW, the source window, the
+ *   matrix and the taps; a nodata beyond the element type; an id outside 0..254; a misaligned src;
+ *   a src or src_valid overlapping an output. */
+typedef struct dsic_warp_source {
+  const void* src;
+  const uint8_t* src_valid;
+  int sh, sw, sy0, sx0, shift, LH, LW, H, W;
+  int nodata, id, reserved;
+  int64_t m[6];
+} dsic_warp_source;
+int dsic_window_warp_composite_u8(const dsic_warp_source* sources, int n, int C, uint8_t* dst_hwc,
+                                  uint8_t* dst_valid, uint8_t* dst_count, uint8_t* dst_source,
+                                  int oh, int ow, int sample_mode, int reduce_mode, int kind, int a,
+                                  int b, int fill, void* stream);
+int dsic_window_warp_composite_u16(const dsic_warp_source* sources, int n, int C, uint16_t* dst_hwc,
+                                   uint8_t* dst_valid, uint8_t* dst_count, uint8_t* dst_source,
+                                   int oh, int ow, int sample_mode, int reduce_mode, int kind,
+                                   int a, int b, int fill, void* stream);
+
 /* HIP stream limited to the CUs whose bit is set in mask_host[words] (bit i of
  * word i/32 = CU i).  Used to give the range coder its own few CUs beside the
  * conv kernels; there is no reference counterpart (the reference is

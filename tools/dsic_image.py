@@ -19,6 +19,8 @@ an image.
                                           [--reduce first|last|mean|median|max|min] [--index nd:A,B|difference:A,B|band:A]
                                           [--region Y0,X0,H,W] [--level L] [--fill V]
                                           [--count-out FILE.npy] [--valid-out FILE.npy] [--source-out FILE.npy]
+                                          [--size OH,OW --rotate DEG [--center Y,X] [--scale S] | --affine M00,...,M12]
+                                          [--resampling bilinear|cubic|nearest] [--grid H,W]
     python tools/dsic_image.py info       IN.dsic
 
 --segments K (2, 4, 8 or 16) codes every tile's y string as K independent strings, which a decoder reads on K waves per
@@ -81,6 +83,12 @@ offsets that are multiples of 2^L.  --count-out FILE.npy writes how many scenes 
 spelling) a pixel is the whole pixel, every band, of the scene whose index is largest or smallest there, the first of
 equals; --reduce max --index nd:NIR,RED is the maximum-NDVI composite.  --source-out FILE.npy (first, last, max, min)
 writes the number of the scene, in the order of --scene, each pixel was taken from (uint8 [h,w], 255 under no scene).
+composite with --rotate DEG [--center Y,X] [--scale S] or --affine, and --size OH,OW, writes an affine view of the stack
+instead of a window (codec.SceneStack.read_warped): the options are decompress's, counted in the stack's grid (--center
+defaults to the grid's centre), and every scene is sampled under its own matrix with --resampling bilinear (the default),
+cubic or nearest in the same launch that reduces them.  --scene FILE@M00,M01,M02,M10,M11,M12 places a scene by a 2 x 3
+matrix, scene level-0 pixels per grid pixel, for scenes of another resolution or orientation (warped views only);
+--grid H,W is the stack's grid (default: the bounding box, with placements the first scene's size).
 
 The state dict is loaded plain or from under "model" (code/modelv2/eval_selfcontained_entropy.py:130-134); the model's
 N, M, input channels and spatial_params are read from its shapes.  Images are PNG through PIL when PIL is importable
@@ -390,9 +398,46 @@ def parse_index(a, ap):
     return index
 
 
-def composite_main(a, ap, region):
-    """composite: a window of the stack of --scene's streams -> OUT (a.src), with the optional count, validity and
-    source plane."""
+def composite_view(a, ap, region, size):
+    """composite's view options, every argument error before the model is loaded -> None for a window of the stack, or a
+    function of the stack's grid (H, W) that gives the view's 2 x 3 matrix, grid pixels per output pixel."""
+    from dsic_amd import codec
+    if a.rotate is None and a.affine is None:
+        if size is not None or a.center is not None or a.scale is not None or a.resampling is not None:
+            ap.error("composite: --size, --center, --scale and --resampling go with --rotate or --affine")
+        return None
+    if a.rotate is not None and a.affine is not None:
+        ap.error("--rotate and --affine exclude each other")
+    if region is not None or a.level:
+        ap.error("--region and --level do not go with --rotate or --affine: the matrix says where the view lies")
+    if size is None:
+        ap.error("--rotate and --affine need --size OH,OW")
+    if not (1 <= size[0] <= 1 << 20 and 1 <= size[1] <= 1 << 20):
+        ap.error(f"--size {a.size}: a warped view has 1 .. 2^20 pixels a side")
+    if a.resampling == "average":
+        ap.error("--resampling average goes with --region; a warped view takes bilinear, cubic or nearest")
+    a.resampling = a.resampling or "bilinear"
+    try:
+        if a.affine is not None:
+            if a.center is not None or a.scale is not None:
+                ap.error("--center and --scale go with --rotate")
+            values = [float(v) for v in a.affine.split(",")]
+            if len(values) != 6:
+                raise ValueError(f"--affine {a.affine}: six numbers M00,M01,M02,M10,M11,M12")
+            codec.affine_q16([values[:3], values[3:]])
+            return lambda H, W: [values[:3], values[3:]]
+        scale = 1.0 if a.scale is None else float(a.scale)
+        center = None if a.center is None else [float(v) for v in a.center.split(",")]
+        if center is not None and len(center) != 2:
+            raise ValueError(f"--center {a.center}: two numbers Y,X")
+    except ValueError as e:
+        ap.error(str(e) if str(e).startswith(("--", "af")) else "--affine, --center and --scale take numbers")
+    return lambda H, W: codec.rotation_affine(*(center or (H / 2, W / 2)), a.rotate, scale, size[0], size[1])
+
+
+def composite_main(a, ap, region, size=None):
+    """composite: a window of the stack of --scene's streams, or with --rotate / --affine an affine view of it -> OUT
+    (a.src), with the optional count, validity and source plane."""
     import contextlib
 
     import numpy as np
@@ -409,21 +454,43 @@ def composite_main(a, ap, region):
     if a.source_out is not None and a.reduce in ("mean", "median"):
         ap.error("--source-out goes with --reduce first, last, max and min")
     reduce = (a.reduce, parse_index(a, ap)) if ranked else a.reduce
-    files, offsets = [], []
+    view = composite_view(a, ap, region, size)
+    files, offsets, placed = [], [], False
     for text in a.scene:
         path, _, pos = text.rpartition("@")
         try:
-            oy, ox = (int(v) for v in pos.split(","))
+            where = [float(v) for v in pos.split(",")]
+            if len(where) == 2:
+                where = [int(v) for v in pos.split(",")]
+            elif len(where) != 6:
+                raise ValueError
         except ValueError:
-            path, oy, ox = text, 0, 0                                      # no position: the text is the file's name
+            path, where = text, [0, 0]                                     # no position: the text is the file's name
+        placed = placed or len(where) == 6
         files.append(path)
-        offsets.append((oy, ox))
+        offsets.append(where)
+    grid = None
+    if a.grid is not None:
+        try:
+            grid = tuple(int(v) for v in a.grid.split(","))
+        except ValueError:
+            grid = ()
+        if len(grid) != 2:
+            ap.error("--grid H,W (two integers)")
+    if placed and view is None:
+        ap.error("--scene FILE@M00,M01,M02,M10,M11,M12 places a scene for a warped view: give --rotate or --affine with --size")
     model = load_model(a.weights, a.min_nu, a.max_nu)
     with contextlib.ExitStack() as held:
         readers = [held.enter_context(codec.ImageReader(model, held.enter_context(open(f, "rb")), batch=a.batch))
                    for f in files]
         try:
-            stack = codec.SceneStack(readers, offsets)
+            if placed:                                                     # an offset among placements: its matrix
+                matrices = [[w[:3], w[3:]] if len(w) == 6 else [[1, 0, -w[0]], [0, 1, -w[1]]] for w in offsets]
+                stack = codec.SceneStack(readers, shape=grid or readers[0].levels[0], placements=matrices)
+            else:
+                stack = codec.SceneStack(readers, [tuple(w) for w in offsets], grid)
+            if view is not None:
+                return composite_warped(a, ap, stack, view(*stack.levels[0]), size, reduce, ranked, len(files))
             if region is None:
                 region = (0, 0) + tuple(stack.levels[min(max(a.level, 0), len(stack.levels) - 1)])
             stats = {}
@@ -443,6 +510,25 @@ def composite_main(a, ap, region):
         np.save(a.valid_out, valid.cpu().numpy())
     if a.source_out is not None:
         np.save(a.source_out, source[0].cpu().numpy())
+
+
+def composite_warped(a, ap, stack, matrix, size, reduce, ranked, scenes):
+    """composite with --rotate or --affine: SceneStack.read_warped -> OUT and the optional planes"""
+    import numpy as np
+    import torch
+    stats = {}
+    img, valid, count, *source = stack.read_warped(matrix, size, reduce=reduce, resampling=a.resampling, fill=a.fill or 0,
+                                                   with_valid=True, with_count=True, stats=stats,
+                                                   with_source=a.source_out is not None)
+    if img.dtype != torch.uint8 and not a.src.endswith(".npy"):
+        ap.error(f"{a.src}: a uint16 image is written as .npy only")
+    path = write_image(a.src, img)
+    print(f"[dsic_image] {a.reduce}{' of ' + a.index if ranked else ''} of {scenes} scene(s) on a {stack.levels[0][0]}x{stack.levels[0][1]} grid: "
+          f"warped view {size[0]}x{size[1]}, {a.resampling}, {stats['parts']} scene(s) met at level(s) {stats['levels']}, "
+          f"{len(stats['tiles'])} tile(s), {int(valid.sum())} valid pixel(s) -> {path}")
+    for out, plane in ((a.count_out, count), (a.valid_out, valid), (a.source_out, source[0] if source else None)):
+        if out is not None:
+            np.save(out, plane.cpu().numpy())
 
 
 def print_info(ix):
@@ -549,8 +635,11 @@ def main(argv=None):
                          "--index-stretch=LO,HI")
     ap.add_argument("--alpha", action="store_true", help="render: add the validity mask as an alpha channel")
     ap.add_argument("--background", type=int, default=0, metavar="V", help="render: what invalid pixels show (0 .. 255)")
-    ap.add_argument("--scene", action="append", default=None, metavar="FILE[@Y,X]",
-                    help="composite: a scene's stream and its level-0 position in the stack's grid (default 0,0); repeatable")
+    ap.add_argument("--scene", action="append", default=None, metavar="FILE[@Y,X | @M00,M01,M02,M10,M11,M12]",
+                    help="composite: a scene's stream and its level-0 position in the stack's grid (default 0,0), or with six "
+                         "numbers its placement, scene level-0 pixels per grid pixel (warped views only); repeatable")
+    ap.add_argument("--grid", default=None, metavar="H,W",
+                    help="composite: the stack's grid (default: the scenes' bounding box; with placements the first scene's size)")
     ap.add_argument("--reduce", choices=("first", "last", "mean", "median", "max", "min"), default="first",
                     help="composite: what a pixel takes from the scenes that are valid there; max and min: the whole pixel of "
                          "the scene whose --index is largest or smallest")
@@ -602,12 +691,11 @@ def main(argv=None):
     if a.scale is not None and a.mode != "compress" and a.rotate is None:
         ap.error("--scale goes with compress, or with --rotate")
     if a.mode == "composite":
-        if (size is not None or a.rotate is not None or a.affine is not None or a.valid is not None or a.out is not None
-                or a.bands is not None or a.stretch is not None or a.alpha or a.colormap != "grey"
-                or a.index_stretch is not None):
-            ap.error("composite takes --scene, --reduce, --index, --region, --level, --fill, --count-out, --valid-out and "
-                     "--source-out")
-        return composite_main(a, ap, region)
+        if (a.valid is not None or a.out is not None or a.bands is not None or a.stretch is not None or a.alpha
+                or a.colormap != "grey" or a.index_stretch is not None):
+            ap.error("composite takes --scene, --reduce, --index, --region, --level, --fill, --count-out, --valid-out, "
+                     "--source-out, and for a warped view --rotate, --center, --scale, --affine, --size, --resampling and --grid")
+        return composite_main(a, ap, region, size)
     matrix = warp_matrix(a, ap, region, size)
     if (a.valid is not None or a.fill is not None) and a.mode != "compress":
         ap.error("--valid and --fill go with compress")

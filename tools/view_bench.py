@@ -1,6 +1,6 @@
 """Pan and zoom: codec.ImageReader against one decompress_region call per frame, and the resampling kernel alone.
 
-    python tools/view_bench.py [--size 4096] [--tile 256] [--reps 3] [--json profiles/view_bench.json] [--only warp|index|composite]
+    python tools/view_bench.py [--size 4096] [--tile 256] [--reps 3] [--json profiles/view_bench.json] [--only warp|index|composite|warp_composite]
 
 The scene of image_codec_bench.py (synthetic patches side by side, uint8) is coded once with overviews=3.  A viewport
 of 768 rows x 1024 columns pans right in 32 steps of 64 pixels (33 frames).  Per frame, alternately in one process:
@@ -38,6 +38,15 @@ the bytes that launch must move (the validity bytes it has to look at, the pixel
 the same image built with torch.where / torch.sort on the padded int32 stack [n, H, W, C] (built outside the timing;
 checked equal once).  Those windows fit the caches, so the kernel and the torch expression are timed again on 16
 random 4096 x 4096 x 4 sources with masks of the same kind: 2 GB of pixels, past the 256 MB Infinity Cache.
+warp_composite (--only warp_composite alone): those 16 random 4096 x 4096 x 4 sources and masks under a 4096 x 4096 view
+turned by 30 degrees at 0.8 level-0 pixels per output pixel, every source a fraction of a pixel off the others.  Per row
+(n = 4, 8, 16 x first, mean, median, max at bilinear; n = 16 median at cubic and at nearest): the one launch of
+dsic_window_warp_composite_u16 beside the chain it is defined as, n launches of dsic_window_warp_u16 into n full-size
+intermediates and one of dsic_window_composite(_pick)_u16 over them, in the same process on the same inputs, checked
+equal once; device events, 20 launches after 5, three rounds alternating.  A fused figure is "within" up to the chain's
+slowest round, "margin" up to that plus the chain's spread, else "OUTSIDE".  Each row states a byte model: the validity
+and pixel lines under the taps of the sources looked at plus the output, and for the chain that plus n oh ow (C elem + 1)
+written and read again.
 Records, not bars."""
 from __future__ import annotations
 
@@ -332,6 +341,80 @@ def _composite_record(size, tile, batch, kernel_size=4096):
     return rec
 
 
+def _warp_composite_record(kernel_size=4096, rounds=3):
+    """The `warp_composite` record: see the module's docstring."""
+    import numpy as np
+    import torch
+    from dsic_amd import codec, lib
+    from dsic_amd.ops import _p, _stream
+    L, C, size, rng = lib.load(), 4, kernel_size, np.random.default_rng(12)
+    imgs = [torch.randint(0, 10001, (size, size, C), dtype=torch.int32, device="cuda").to(torch.int16).view(torch.uint16)
+            for _ in range(16)]
+    masks = [m.to(torch.uint8) for m in _block_masks(size, rng)]
+    # the view of warp_ref's rot30 (0.8 level-0 pixels per output pixel about the centre), each source a fraction of a
+    # pixel off the others
+    base = codec.rotation_affine(size / 2, size / 2, 30, 0.8, size, size)
+    mats = [codec.affine_q16([[base[0][0], base[0][1], base[0][2] + 0.13 * i], [base[1][0], base[1][1], base[1][2] - 0.21 * i]])
+            for i in range(16)]
+    table = (lib.WarpSource * 16)(*[lib.WarpSource(_p(imgs[i]), _p(masks[i]), size, size, 0, 0, 0, size, size, size, size, -1, i, 0,
+                                                   (ctypes.c_int64 * 6)(*mats[i])) for i in range(16)])
+    mids = [torch.empty((size, size, C), dtype=torch.uint16, device="cuda") for _ in range(16)]
+    mvals = [torch.empty((size, size), dtype=torch.uint8, device="cuda") for _ in range(16)]
+    dst, want = (torch.empty((size, size, C), dtype=torch.uint16, device="cuda") for _ in range(2))
+    rect, nodata = (ctypes.c_int * 64)(*([0, 0, size, size] * 16)), (ctypes.c_int * 16)(*([-1] * 16))
+    src = (ctypes.c_void_p * 16)(*[_p(t) for t in mids])
+    sv = (ctypes.c_void_p * 16)(*[_p(t) for t in mvals])
+    rows = [(n, mode, "bilinear") for n in (4, 8, 16) for mode in ("first", "mean", "median", "max")]
+    rows += [(16, "median", "cubic"), (16, "median", "nearest")]
+    codes = {"first": 0, "mean": 2, "median": 3, "max": 4}
+    taps = {"bilinear": 4, "nearest": 1, "cubic": 16}
+    out = {}
+    for n, mode, resampling in rows:
+        sample, code = {"bilinear": 0, "nearest": 1, "cubic": 2}[resampling], codes[mode]
+
+        def fused(to=dst):
+            lib.check(L.dsic_window_warp_composite_u16(table, n, C, _p(to), None, None, None, size, size, sample, code, 2,
+                                                       MAX_INDEX[1], MAX_INDEX[2], 0, _stream()), "window_warp_composite_u16")
+
+        def chain(to=want):
+            for i in range(n):
+                lib.check(L.dsic_window_warp_u16(_p(imgs[i]), _p(masks[i]), size, size, 0, 0, C, 0, size, size, size, size,
+                                                 (ctypes.c_int64 * 6)(*mats[i]), _p(mids[i]), _p(mvals[i]), size, size, sample, -1, 0,
+                                                 _stream()), "window_warp_u16")
+            if code == 4:
+                lib.check(L.dsic_window_composite_pick_u16(src, sv, rect, nodata, None, n, C, _p(to), None, None, None, size, size,
+                                                           code, 2, MAX_INDEX[1], MAX_INDEX[2], 0, _stream()),
+                          "window_composite_pick_u16")
+            else:
+                lib.check(L.dsic_window_composite_u16(src, sv, rect, nodata, n, C, _p(to), None, None, size, size, code, 0,
+                                                      _stream()), "window_composite_u16")
+        fused()
+        chain()
+        torch.cuda.synchronize()
+        assert torch.equal(dst.view(torch.int16), want.view(torch.int16)), (n, mode, resampling)
+        f_us, c_us = [], []
+        for _ in range(rounds):                                            # alternating: the chain's spread is the yardstick's
+            c_us.append(_per_launch_us(chain, n=20))
+            f_us.append(_per_launch_us(fused, n=20))
+        # bytes: an output pixel advances 0.8 level pixels a side, so the taps of all output pixels cover the 0.64 of a
+        # source that the view meets, each line once if the caches hold it between neighbours (a lower bound on the
+        # traffic under the taps); first stops at the winner, about 1 / 0.6 sources per pixel
+        opix, under = size * size, 0.64 * size * size
+        looked = min(n, 1 / 0.6) if mode == "first" else n
+        fused_bytes = int(looked * under * (2 * C + 1) + opix * 2 * C)
+        chain_bytes = int(n * under * (2 * C + 1) + opix * 2 * C + 2 * n * opix * (2 * C + 1))
+        slow, spread = max(c_us), max(c_us) - min(c_us)
+        marks = ["within" if f <= slow else "margin" if f <= slow + spread else "OUTSIDE" for f in f_us]
+        out[f"n={n} {mode} {resampling}"] = {
+            "fused_us": [round(v, 1) for v in f_us], "chain_us": [round(v, 1) for v in c_us], "marks": marks,
+            "launches_fused": 1, "launches_chain": n + 1, "taps_per_source": taps[resampling],
+            "bytes_fused_model": fused_bytes, "bytes_chain_model": chain_bytes,
+            "fused_GB_per_s": round(fused_bytes / statistics.median(f_us) / 1e3, 1),
+            "chain_over_fused": round(statistics.median(c_us) / statistics.median(f_us), 2)}
+    return {"sources": f"16 random {size}x{size}x{C} uint16 with 64x64-block validity, rot30 at 0.8, sub-pixel offsets per source",
+            "timing": f"device events, 20 launches after 5, {rounds} alternating rounds, chain first", "rows": out}
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--size", type=int, default=4096)
@@ -339,7 +422,7 @@ def main():
     ap.add_argument("--batch", type=int, default=64)
     ap.add_argument("--reps", type=int, default=3)
     ap.add_argument("--json", default=os.path.join(ROOT, "profiles", "view_bench.json"))
-    ap.add_argument("--only", choices=("warp", "index", "composite"), default=None,
+    ap.add_argument("--only", choices=("warp", "index", "composite", "warp_composite"), default=None,
                     help="measure this record alone and put it into the --json file beside the others")
     a = ap.parse_args()
 
@@ -352,13 +435,13 @@ def main():
 
     if not torch.cuda.is_available():
         raise SystemExit("view_bench: no GPU; nothing is measured without one")
-    if a.only == "composite":                                              # scenes of its own: nothing below is needed
+    if a.only in ("composite", "warp_composite"):                          # inputs of their own: nothing below is needed
         res = {}
         if os.path.exists(a.json):
             with open(a.json) as f:
                 res = json.load(f)
-        res["composite"] = _composite_record(a.size, a.tile, a.batch)
-        print(json.dumps(res["composite"]))
+        res[a.only] = _composite_record(a.size, a.tile, a.batch) if a.only == "composite" else _warp_composite_record()
+        print(json.dumps(res[a.only]))
         with open(a.json, "w") as f:
             json.dump(res, f, indent=1)
         return
