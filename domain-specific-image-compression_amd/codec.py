@@ -89,7 +89,9 @@ version-8 stream of its own image and mask, with level 0's fill and scale.
 
 ImageReader (view.py) keeps a stream open for pan and zoom: levels opened once, decoded tiles cached on the device and
 assembled by the calls decompress_region makes (_assemble_window), requests decoded together (read_many), and windows
-resampled to a size asked for from the level view_level picks (csrc/view.hip).  SceneStack (view.py) places several
+resampled to a size asked for from the level view_level picks (csrc/view.hip); read_warped samples an affine view
+(csrc/warp.hip) and read_gridded a reprojected one, its sample positions interpolated from a coordinate mesh
+(csrc/grid.hip; affine_grid, projective_grid, function_grid, grid_level and grid_window are its planning).  SceneStack (view.py) places several
 readers on one grid and composites their windows per pixel in one launch (csrc/composite.hip): first, last, mean,
 median, or the whole pixel of the scene whose index is largest or smallest (stack_reduce names the forms).
 SceneStack.read_warped samples every scene under its own affine and combines them in the same launch
@@ -1480,3 +1482,5 @@ from .view import affine_q16, rotation_affine, warp_level, warp_window, window_a
 from .view import COLORMAPS, colormap_from_anchors  # noqa: E402
 from .view import SceneStack, stack_levels, stack_parts, stack_reduce  # noqa: E402
 from .view import check_q16, compose_q16, stack_warp_parts  # noqa: E402
+from .view import GRID_NONE, GRID_STEPS, affine_grid, check_grid, function_grid, grid_error, grid_level  # noqa: E402
+from .view import grid_shape, grid_window, projective_grid  # noqa: E402

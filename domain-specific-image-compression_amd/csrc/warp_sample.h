@@ -1,4 +1,5 @@
-// The affine sampler, shared by warp.hip (one scene per launch) and warp_composite.hip (up to 16 scenes per launch).
+// The affine sampler, shared by warp.hip (one scene per launch), warp_composite.hip (up to 16 scenes per launch) and
+// grid.hip (one scene under a coordinate mesh).
 //
 // The geometry is integer.  m[6] is the 2 x 3 matrix in (row, column) order in Q16, level-0 pixels per output pixel.
 // Output pixel (i, j) samples the level-0 position P / 2^17 with
@@ -14,8 +15,10 @@
 // A tap counts iff its validity byte is not 0 (src_valid), else iff its channels do not all equal nodata (nodata >= 0),
 // else always.  Taps are also clamped to the source window, so a wrong plan cannot read outside the allocation.
 //
-// Here: the geometry (Warp, warp_of), the sampler (warp_tap, cubic_weights, warp_load, warp_pixel), the work split
-// (warp_where) and the part of the host check that looks at one scene's geometry (warp_axis, warp_geometry).
+// Here: the geometry (Warp, warp_of), the sampler (warp_tap, cubic_weights, warp_load, warp_sample_at: the sample at a
+// position; warp_pixel: the affine position of (i, j), then that sample), the work split (warp_where) and the part of
+// the host check that looks at one scene's geometry (warp_frame, warp_axis_taps, warp_axis, warp_holds, warp_geometry).
+// grid.hip samples the same way at positions interpolated from a mesh.
 #pragma once
 #include <limits.h>
 
@@ -61,13 +64,13 @@ __device__ __forceinline__ bool warp_load(const T* __restrict__ src, const uint8
   return !nd;
 }
 
-// One output pixel (i, j): its C samples into out (channels from C on: 0), and whether it is valid.  T = uint8_t or
-// uint16_t, [.][.][C] with C <= 4; V: a validity window beside the source; nodata < 0 = none.
+// The sample at the level-0 position (Py, Px) / 2^17: its C values into out (channels from C on: 0), and whether it is
+// valid.  T = uint8_t or uint16_t, [.][.][C] with C <= 4; V: a validity window beside the source; nodata < 0 = none.
+// Whoever states where output pixel (i, j) samples calls it: warp_pixel below (an affine), grid.hip (a mesh).
 template <typename T, bool V>
-__device__ __forceinline__ bool warp_pixel(const T* __restrict__ src, const uint8_t* __restrict__ sval, const Warp& g, int C,
-                                           int mode, int nodata, uint32_t fill, int i, int j, uint32_t out[4]) {
-  const int64_t Py = g.m[0] * (2 * i + 1) + g.m[1] * (2 * j + 1) + 2 * g.m[2];
-  const int64_t Px = g.m[3] * (2 * i + 1) + g.m[4] * (2 * j + 1) + 2 * g.m[5];
+__device__ __forceinline__ bool warp_sample_at(const T* __restrict__ src, const uint8_t* __restrict__ sval, const Warp& g,
+                                               int C, int mode, int nodata, uint32_t fill, int64_t Py, int64_t Px,
+                                               uint32_t out[4]) {
 #pragma unroll
   for (int c = 0; c < 4; ++c) out[c] = c < C ? fill : 0u;
   if (Py < 0 || Py >= g.HP || Px < 0 || Px >= g.WP) return false;
@@ -142,6 +145,15 @@ __device__ __forceinline__ bool warp_pixel(const T* __restrict__ src, const uint
   return true;
 }
 
+// One output pixel (i, j) of the affine view g.m: its position, then the sample there.
+template <typename T, bool V>
+__device__ __forceinline__ bool warp_pixel(const T* __restrict__ src, const uint8_t* __restrict__ sval, const Warp& g, int C,
+                                           int mode, int nodata, uint32_t fill, int i, int j, uint32_t out[4]) {
+  const int64_t Py = g.m[0] * (2 * i + 1) + g.m[1] * (2 * j + 1) + 2 * g.m[2];
+  const int64_t Px = g.m[3] * (2 * i + 1) + g.m[4] * (2 * j + 1) + 2 * g.m[5];
+  return warp_sample_at<T, V>(src, sval, g, C, mode, nodata, fill, Py, Px, out);
+}
+
 // output pixel of thread t of block blk of an oh x ow output: wave t / 64 owns patch (t / 128, (t / 64) % 2), lane
 // t % 64 its pixel ((t % 64) / 8, t % 8)
 __device__ __forceinline__ bool warp_where(int oh, int ow, int64_t blk, int bx, int* i, int* j) {
@@ -157,15 +169,10 @@ __device__ __forceinline__ bool warp_where(const Warp& g, int64_t blk, int bx, i
   return warp_where(g.oh, g.ow, blk, bx, i, j);
 }
 
-// One axis of the host check: the level indices that the taps of all inside samples can take, from the positions of the
-// four corner pixels (P is affine in (i, j), the floor monotone).  false: no sample is inside on this axis.
-static bool warp_axis(const int64_t* m, int oh, int ow, int64_t NP, int L, int l, int mode, int64_t* a, int64_t* b) {
-  int64_t lo = INT64_MAX, hi = INT64_MIN;
-  for (int k = 0; k < 4; ++k) {
-    const int64_t i = (k & 1) ? oh - 1 : 0, j = (k & 2) ? ow - 1 : 0;
-    const int64_t P = m[0] * (2 * i + 1) + m[1] * (2 * j + 1) + 2 * m[2];
-    lo = P < lo ? P : lo, hi = P > hi ? P : hi;
-  }
+// One axis of the host check: the level indices a .. b that the taps of all inside samples can take when the positions
+// (Q17) lie in lo .. hi: cut to the image, widened by the mode's taps, clamped to the level.  false: no sample is inside
+// on this axis.  warp_axis (an affine) and grid.hip (a mesh) find lo and hi.
+static bool warp_axis_taps(int64_t lo, int64_t hi, int64_t NP, int L, int l, int mode, int64_t* a, int64_t* b) {
   if (hi < 0 || lo >= NP) return false;
   lo = lo < 0 ? 0 : lo, hi = hi >= NP ? NP - 1 : hi;
   if (mode == 1) {
@@ -180,10 +187,19 @@ static bool warp_axis(const int64_t* m, int oh, int ow, int64_t NP, int L, int l
   return true;
 }
 
-// The geometry of one scene under a view of g.oh x g.ow pixels sampled with `mode` (in 0..2): the level, the source
-// window, the output size, the matrix, and that the window holds every tap.  warp_check and the composite's per-source
-// check both run it, so both refuse the same things in the same words.
-static int warp_geometry(const char* what, const Warp& g, int H, int W, const int64_t* m, int mode) {
+// The same from the positions of the four corner pixels of an affine view: P is affine in (i, j), the floor monotone.
+static bool warp_axis(const int64_t* m, int oh, int ow, int64_t NP, int L, int l, int mode, int64_t* a, int64_t* b) {
+  int64_t lo = INT64_MAX, hi = INT64_MIN;
+  for (int k = 0; k < 4; ++k) {
+    const int64_t i = (k & 1) ? oh - 1 : 0, j = (k & 2) ? ow - 1 : 0;
+    const int64_t P = m[0] * (2 * i + 1) + m[1] * (2 * j + 1) + 2 * m[2];
+    lo = P < lo ? P : lo, hi = P > hi ? P : hi;
+  }
+  return warp_axis_taps(lo, hi, NP, L, l, mode, a, b);
+}
+
+// The frame of one scene under a view of g.oh x g.ow pixels: the level, the source window and the output size.
+static int warp_frame(const char* what, const Warp& g, int H, int W) {
   DSIC_REQUIRE(g.shift >= 0 && g.shift <= 15, "%s: shift=%d must be in 0..15", what, g.shift);
   DSIC_REQUIRE(H >= 1 && W >= 1 && H <= (1 << 30) && W <= (1 << 30), "%s: image %dx%d", what, H, W);
   DSIC_REQUIRE(g.LH == (int)(((int64_t)H + ((int64_t)1 << g.shift) - 1) >> g.shift) &&
@@ -194,6 +210,24 @@ static int warp_geometry(const char* what, const Warp& g, int H, int W, const in
                "%s: source window %dx%d at (%d, %d) of a %dx%d level", what, g.sh, g.sw, g.sy0, g.sx0, g.LH, g.LW);
   DSIC_REQUIRE(g.oh >= 1 && g.ow >= 1 && g.oh <= WARP_SIDE && g.ow <= WARP_SIDE, "%s: output %dx%d must be 1x1 .. 2^20x2^20",
                what, g.oh, g.ow);
+  return DSIC_OK;
+}
+
+// The words for a source window that does not hold the taps ya .. yb, xa .. xb.
+static int warp_holds(const char* what, const Warp& g, int64_t ya, int64_t yb, int64_t xa, int64_t xb) {
+  DSIC_REQUIRE(ya >= g.sy0 && yb < (int64_t)g.sy0 + g.sh && xa >= g.sx0 && xb < (int64_t)g.sx0 + g.sw,
+               "%s: the view's taps cover rows %lld..%lld, columns %lld..%lld of level %d, outside the source window "
+               "%dx%d at (%d, %d)",
+               what, (long long)ya, (long long)yb, (long long)xa, (long long)xb, g.shift, g.sh, g.sw, g.sy0, g.sx0);
+  return DSIC_OK;
+}
+
+// The geometry of one scene under an affine view sampled with `mode` (in 0..2): the frame, the matrix, and that the
+// window holds every tap.  warp_check and the composite's per-source check both run it, so both refuse the same things
+// in the same words.
+static int warp_geometry(const char* what, const Warp& g, int H, int W, const int64_t* m, int mode) {
+  const int status = warp_frame(what, g, H, W);
+  if (status != DSIC_OK) return status;
   for (int k = 0; k < 6; ++k) {
     const int64_t bound = k % 3 == 2 ? WARP_SHIFT - 1 : WARP_COEF;
     DSIC_REQUIRE(m[k] >= -bound && m[k] <= bound, "%s: matrix entry %d = %lld is outside +-%lld (Q16)", what, k,
@@ -202,10 +236,7 @@ static int warp_geometry(const char* what, const Warp& g, int H, int W, const in
   int64_t ya = 0, yb = 0, xa = 0, xb = 0;
   if (warp_axis(m, g.oh, g.ow, g.HP, g.LH, g.shift, mode, &ya, &yb) &&
       warp_axis(m + 3, g.oh, g.ow, g.WP, g.LW, g.shift, mode, &xa, &xb))
-    DSIC_REQUIRE(ya >= g.sy0 && yb < (int64_t)g.sy0 + g.sh && xa >= g.sx0 && xb < (int64_t)g.sx0 + g.sw,
-                 "%s: the view's taps cover rows %lld..%lld, columns %lld..%lld of level %d, outside the source window "
-                 "%dx%d at (%d, %d)",
-                 what, (long long)ya, (long long)yb, (long long)xa, (long long)xb, g.shift, g.sh, g.sw, g.sy0, g.sx0);
+    return warp_holds(what, g, ya, yb, xa, xb);
   return DSIC_OK;
 }
 

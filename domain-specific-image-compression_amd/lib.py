@@ -164,6 +164,12 @@ SIGNATURES = {
     "dsic_window_warp_index_render_u16": (c_int, [_P, _P] + [c_int] * 10 + [_P] + [c_int] * 5 + [_P, _P] + [c_int] * 6 + [_P]),
     "dsic_index_histogram_u8": (c_int, [_P, _P] + [c_int] * 7 + [_P, _P]),
     "dsic_index_histogram_u16": (c_int, [_P, _P] + [c_int] * 7 + [_P, _P]),
+    "dsic_window_grid_u8": (c_int, [_P, _P] + [c_int] * 10 + [_P, _P, c_int, _P, _P] + [c_int] * 5 + [_P]),
+    "dsic_window_grid_u16": (c_int, [_P, _P] + [c_int] * 10 + [_P, _P, c_int, _P, _P] + [c_int] * 5 + [_P]),
+    "dsic_window_grid_render_u8": (c_int, [_P, _P] + [c_int] * 10 + [_P, _P, c_int, _P, c_int, _P, _P] + [c_int] * 6 + [_P]),
+    "dsic_window_grid_render_u16": (c_int, [_P, _P] + [c_int] * 10 + [_P, _P, c_int, _P, c_int, _P, _P] + [c_int] * 6 + [_P]),
+    "dsic_window_grid_index_render_u8": (c_int, [_P, _P] + [c_int] * 10 + [_P, _P] + [c_int] * 6 + [_P, _P] + [c_int] * 6 + [_P]),
+    "dsic_window_grid_index_render_u16": (c_int, [_P, _P] + [c_int] * 10 + [_P, _P] + [c_int] * 6 + [_P, _P] + [c_int] * 6 + [_P]),
     "dsic_window_composite_u8": (c_int, [_P, _P, _P, _P, c_int, c_int, _P, _P, _P] + [c_int] * 4 + [_P]),
     "dsic_window_composite_u16": (c_int, [_P, _P, _P, _P, c_int, c_int, _P, _P, _P] + [c_int] * 4 + [_P]),
     "dsic_window_composite_pick_u8": (c_int, [_P, _P, _P, _P, _P, c_int, c_int, _P, _P, _P, _P] + [c_int] * 7 + [_P]),

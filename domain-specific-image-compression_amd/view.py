@@ -9,6 +9,10 @@ values per band, with the validity as an alpha channel; histogram and stretch de
 (csrc/histogram.hip, stretch_from_histogram).  read_warped and render_warped do both for an affine view: a 2 x 3
 matrix quantised once to Q16 (affine_q16), the level its scale asks for (warp_level), the window of that level which
 holds every tap (warp_window), and one launch of the bilinear, cubic or nearest sampler (csrc/warp.hip).
+read_gridded, render_gridded and render_index_gridded do the same for a view that is not affine, a reprojection or a
+tilted view: the exact map evaluated on a coarse mesh of output positions (function_grid, projective_grid, affine_grid),
+interpolated bilinearly between the nodes in integers and sampled by the same sampler (csrc/grid.hip; grid_level and
+grid_window plan it).
 render_index and render_index_warped show an index of one or two bands (a normalised difference such as NDVI, a
 difference, a band) through a colour map in that same launch (csrc/render.h's index tail); index_histogram and
 index_stretch derive its stretch from the data, colormap_from_anchors and COLORMAPS supply the maps.
@@ -148,7 +152,12 @@ def _warp_axis(m3, oh, ow, N, L, l, mode):
     """One axis of warp_window: the level indices (first, last) that the taps of all inside samples can take, from the
     positions of the four corner pixels, or None if no sample is inside on this axis."""
     P = [m3[0] * (2 * i + 1) + m3[1] * (2 * j + 1) + 2 * m3[2] for i in (0, oh - 1) for j in (0, ow - 1)]
-    lo, hi = min(P), max(P)
+    return _axis_taps(min(P), max(P), N, L, l, mode)
+
+
+def _axis_taps(lo, hi, N, L, l, mode):
+    """The level indices (first, last) of the taps of all inside samples whose positions (Q17) lie in lo .. hi: cut to
+    the image, widened by the mode's taps, clamped to the level; None if no sample is inside on this axis."""
     if hi < 0 or lo >= N << 17:
         return None
     lo, hi = max(lo, 0), min(hi, (N << 17) - 1)
@@ -174,6 +183,193 @@ def warp_window(level, LH, LW, H, W, m, oh, ow, mode):
     if mode not in (0, 1, 2) or level < 0 or min(LH, LW, H, W) < 1:
         raise ValueError(f"warp_window: mode {mode}, level {level}, {LH}x{LW} of {H}x{W}")
     ys, xs = _warp_axis(m[:3], oh, ow, H, LH, level, mode), _warp_axis(m[3:], oh, ow, W, LW, level, mode)
+    if ys is None or xs is None:
+        return None
+    return ys[0], xs[0], ys[1] - ys[0] + 1, xs[1] - xs[0] + 1
+
+
+# ---- gridded reads: a view through a coordinate mesh, csrc/grid.hip --------------------------------------------------
+# A view of oh x ow pixels with the step S = 2^s carries a mesh G, int64 [nh + 1][nw + 1][2], nh = ceil(oh / S), nw =
+# ceil(ow / S): node (a, b) holds the level-0 position (y, x) in Q16 of the output corner (a S, b S), in the frame of the
+# affine matrix (pixel (i, j) has its centre at (i + 1/2, j + 1/2)), every entry under 2^48 in size, or GRID_NONE in its
+# y entry: no position here.  Pixel (i, j) samples the bilinear combination of its cell's four nodes at its centre
+# (include/dsic_hip.h states the integer rule); a cell with a none node is fill and invalid.  The helpers below are
+# NumPy and Python integers and need no GPU.
+GRID_STEPS = (16, 32, 64)
+GRID_NONE = -(1 << 63)
+GRID_BOUND, GRID_NODES = 1 << 48, 1 << 22                        # |entry| < 2^48; at most 2^22 nodes
+
+
+def grid_shape(size, step) -> tuple:
+    """The shape (nh + 1, nw + 1, 2) of the mesh of a view of size = (oh, ow) with the given step."""
+    oh, ow = _check_size(size, "grid_shape", WARP_SIDE, "(1, 1) .. (2^20, 2^20)")
+    if step not in GRID_STEPS:
+        raise ValueError(f"grid_shape: step={step!r} must be one of {GRID_STEPS}")
+    shape = (-(-oh // step) + 1, -(-ow // step) + 1, 2)
+    if shape[0] * shape[1] > GRID_NODES:
+        raise ValueError(f"grid_shape: size ({oh}, {ow}) at step {step} takes {shape[0]}x{shape[1]} nodes, over 2^22")
+    return shape
+
+
+def check_grid(grid, size, step) -> np.ndarray:
+    """A mesh for a view of `size` with `step` as a contiguous int64 array, checked as the library checks it: an integer
+    array of grid_shape(size, step), every entry under 2^48 in size or GRID_NONE in a node's y entry (the x entry of such
+    a node is not looked at).  ValueError otherwise."""
+    shape = grid_shape(size, step)
+    G = grid.cpu().numpy() if isinstance(grid, torch.Tensor) else np.asarray(grid)
+    if G.dtype.kind not in "iu" or G.shape != shape:
+        raise ValueError(f"mesh: an integer array of shape {shape} is needed for size {tuple(size)} at step {step}, not "
+                         f"{G.dtype} {G.shape}")
+    if G.dtype.kind == "u" and G.size and int(G.max()) >= GRID_BOUND:
+        raise ValueError("mesh: every entry must be under 2^48 in size (Q16)")
+    G = np.ascontiguousarray(G, dtype=np.int64)
+    some = G[..., 0] != GRID_NONE
+    if (G[..., 1][some] == GRID_NONE).any():
+        raise ValueError("mesh: GRID_NONE in the x entry of a node whose y entry holds a position; it belongs in y")
+    if (np.abs(G[some]) >= GRID_BOUND).any():
+        raise ValueError("mesh: every entry must be under 2^48 in size (Q16), or GRID_NONE in a node's y entry")
+    return G
+
+
+def _grid_nodes(size, step):
+    """the output corner coordinates (a S, b S) of the nodes, int64 [nh + 1, 1] and [1, nw + 1]"""
+    nh1, nw1, _ = grid_shape(size, step)
+    return np.arange(nh1, dtype=np.int64)[:, None] * step, np.arange(nw1, dtype=np.int64)[None, :] * step
+
+
+def affine_grid(matrix_q16, size, step) -> np.ndarray:
+    """The mesh of the affine view with the six Q16 integers matrix_q16, exactly: node (a, b) = m0 a S + m1 b S + m2 per
+    axis.  A gridded read of it is read_warped of that matrix at the same level, bit for bit."""
+    m = check_q16(matrix_q16)
+    i, j = _grid_nodes(size, step)
+    return check_grid(np.stack([m[0] * i + m[1] * j + m[2], m[3] * i + m[4] * j + m[5]], axis=-1), size, step)
+
+
+def function_grid(fn, size, step) -> np.ndarray:
+    """The mesh of an arbitrary map: fn(i, j) takes two float64 arrays of one shape, the output corner coordinates of
+    the nodes (rows i, columns j, in output pixels), and returns (y, x), their level-0 positions in pixels.  Each value is
+    rounded once to Q16, np.rint(v * 65536); a node with a value that is not finite is none."""
+    i, j = _grid_nodes(size, step)
+    i, j = np.broadcast_arrays(i.astype(np.float64), j.astype(np.float64))
+    y, x = fn(i.copy(), j.copy())
+    v = np.stack(np.broadcast_arrays(np.asarray(y, dtype=np.float64), np.asarray(x, dtype=np.float64)), axis=-1)
+    if v.shape != i.shape + (2,):
+        raise ValueError(f"function_grid: fn returned arrays of shape {v.shape[:-1]} for nodes of shape {i.shape}")
+    none = ~np.isfinite(v).all(axis=-1)                          # of the values themselves: a huge finite one is an error
+    with np.errstate(over="ignore", invalid="ignore"):
+        v = np.rint(v * 65536)
+    if not (np.abs(v[~none]) < GRID_BOUND).all():
+        raise ValueError("function_grid: a position of 2^32 pixels or more in size")
+    G = np.where(none[..., None], 0, v).astype(np.int64)
+    G[none, 0] = GRID_NONE
+    return check_grid(G, size, step)
+
+
+def projective_grid(h3x3, size, step) -> np.ndarray:
+    """The mesh of the projective view (y', x', w') = h3x3 (i, j, 1), y = y' / w', x = x' / w', in (row, column) order as
+    the affine matrix, i and j output corner coordinates.  The nine numbers are taken as the exact rationals they are and
+    each node is rounded once, half to even, to Q16 (pure Python integers).  A node with a denominator <= 0 is none."""
+    from fractions import Fraction
+    try:
+        rows = [[Fraction(v) for v in row] for row in h3x3]
+        if len(rows) != 3 or any(len(row) != 3 for row in rows):
+            raise TypeError
+    except (TypeError, ValueError, OverflowError):
+        raise ValueError(f"projective_grid: h3x3={h3x3!r} is not three rows of three finite numbers") from None
+    den = math.lcm(*(v.denominator for row in rows for v in row))
+    h = [[int(v * den) for v in row] for row in rows]
+    nh1, nw1, _ = grid_shape(size, step)
+    G = np.zeros((nh1, nw1, 2), dtype=np.int64)
+    for a in range(nh1):
+        for b in range(nw1):
+            py, px, w = (r[0] * a * step + r[1] * b * step + r[2] for r in h)
+            if w <= 0:
+                G[a, b, 0] = GRID_NONE
+                continue
+            for k, p in enumerate((py, px)):
+                q, r = divmod(p * 65536, w)                      # floor and remainder; round half to even
+                q += 1 if 2 * r > w or (2 * r == w and q & 1) else 0
+                if abs(q) >= GRID_BOUND:
+                    raise ValueError("projective_grid: a position of 2^32 pixels or more in size")
+                G[a, b, k] = q
+    return check_grid(G, size, step)
+
+
+def _whole_cells(G):
+    """bool [nh][nw]: the cells none of whose four nodes is none"""
+    some = G[..., 0] != GRID_NONE
+    return some[:-1, :-1] & some[:-1, 1:] & some[1:, :-1] & some[1:, 1:]
+
+
+def grid_error(fn, grid, size, step) -> float:
+    """The largest distance, in level-0 pixels, between fn and the mesh's interpolation at the centres of the cells
+    (where a bilinear interpolant of a smooth map is farthest off): how a caller chooses the step.  fn as function_grid
+    takes it; cells with a none node, or where fn is not finite, are left out; 0.0 if none is left."""
+    G = check_grid(grid, size, step)
+    i, j = _grid_nodes(size, step)
+    ci, cj = np.broadcast_arrays(i[:-1].astype(np.float64) + step / 2, j[:, :-1].astype(np.float64) + step / 2)
+    y, x = fn(ci.copy(), cj.copy())
+    g = G.astype(np.float64)
+    mid = (g[:-1, :-1] + g[:-1, 1:] + g[1:, :-1] + g[1:, 1:]) / (4 * 65536.0)
+    d = np.hypot(np.asarray(y, dtype=np.float64) - mid[..., 0], np.asarray(x, dtype=np.float64) - mid[..., 1])
+    d = d[_whole_cells(G) & np.isfinite(d)]
+    return float(d.max()) if d.size else 0.0
+
+
+def grid_level(n_levels, grid, step) -> int:
+    """The overview level to sample a mesh from, exactly: the largest l < n_levels with 4^l 2^32 S^2 <= min |E|^2 over
+    all mesh edges E = G[a+1][b] - G[a][b] and G[a][b+1] - G[a][b] between nodes that are not none, else 0.  On an affine
+    mesh this is warp_level of its matrix.  Where the mesh's scale varies, the parts that minify past the chosen level are
+    sampled sparsely, as warp_level says of a view minified past the coarsest level; pass level= to choose otherwise."""
+    n_levels = operator.index(n_levels)
+    if n_levels < 1 or step not in GRID_STEPS:
+        raise ValueError(f"grid_level: {n_levels} level(s), step {step!r}")
+    G = np.asarray(grid)
+    if G.dtype != np.int64 or G.ndim != 3 or G.shape[2] != 2:
+        raise ValueError("grid_level: the mesh must be an int64 array [nh + 1][nw + 1][2] (check_grid)")
+    some = G[..., 0] != GRID_NONE
+    least = None
+    for E, both in ((G[1:] - G[:-1], some[1:] & some[:-1]), (G[:, 1:] - G[:, :-1], some[:, 1:] & some[:, :-1])):
+        E = E[both]                                              # |entry| < 2^49
+        if not E.size:
+            continue
+        small = (np.abs(E) < 1 << 31).all(axis=1)               # squares and their sum fit in int64
+        found = [int((E[small] * E[small]).sum(axis=1).min())] if small.any() else []
+        found += [int(dy) ** 2 + int(dx) ** 2 for dy, dx in E[~small]]          # Python integers for the rest
+        least = min(found + ([] if least is None else [least]))
+    if least is None:
+        return 0
+    for l in range(n_levels - 1, 0, -1):
+        if (step * step) << (2 * l + 32) <= least:
+            return l
+    return 0
+
+
+def grid_window(level, LH, LW, H, W, grid, mode):
+    """The window (y0, x0, h, w) of overview level `level` (LH x LW, of an H x W image) that holds every tap a gridded
+    view of the mesh can take, mode 0 bilinear, 1 nearest, 2 cubic.  Per axis the bilinear combination of a cell lies
+    between the smallest and the largest of its four nodes, so the positions lie between the minimum and the maximum,
+    doubled to Q17, over the nodes of all cells without a none node; they are cut to the image, widened by the mode's taps
+    and clamped to the level as warp_window does it.  None if that box misses the image or no cell is whole.  On an affine
+    mesh the box contains warp_window's and is in general a little larger (it reaches the cell corners); the result of a
+    read does not depend on it, because taps clamp to the level first.  The library refuses a source window that does not
+    contain this one."""
+    level, LH, LW, H, W, mode = (operator.index(v) for v in (level, LH, LW, H, W, mode))
+    if mode not in (0, 1, 2) or level < 0 or min(LH, LW, H, W) < 1:
+        raise ValueError(f"grid_window: mode {mode}, level {level}, {LH}x{LW} of {H}x{W}")
+    G = np.asarray(grid)
+    if G.dtype != np.int64 or G.ndim != 3 or G.shape[2] != 2:
+        raise ValueError("grid_window: the mesh must be an int64 array [nh + 1][nw + 1][2] (check_grid)")
+    whole = _whole_cells(G)
+    if not whole.any():
+        return None
+    used = np.zeros(G.shape[:2], dtype=bool)
+    for da in (0, 1):
+        for db in (0, 1):
+            used[da:da + whole.shape[0], db:db + whole.shape[1]] |= whole
+    nodes = G[used]
+    ys = _axis_taps(2 * int(nodes[:, 0].min()), 2 * int(nodes[:, 0].max()), H, LH, level, mode)
+    xs = _axis_taps(2 * int(nodes[:, 1].min()), 2 * int(nodes[:, 1].max()), W, LW, level, mode)
     if ys is None or xs is None:
         return None
     return ys[0], xs[0], ys[1] - ys[0] + 1, xs[1] - xs[0] + 1
@@ -444,6 +640,7 @@ class ImageReader:
         self._hists = {}                                           # level -> its histogram, counted once
         self._index_hists = {}                                     # (level, kind, a, b) -> an index's histogram
         self._cmaps = {}                                           # name -> the colour map on the device
+        self._meshes = collections.OrderedDict()                   # a mesh's values -> its device copy, oldest first
         self._closed = False
 
     def __enter__(self):
@@ -459,6 +656,7 @@ class ImageReader:
         self._hists.clear()
         self._index_hists.clear()
         self._cmaps.clear()
+        self._meshes.clear()
         self._used, self._closed = 0, True
 
     # ---- the stream ---------------------------------------------------------------------------------------------
@@ -1043,24 +1241,9 @@ class ImageReader:
         what = "ImageReader.read_warped"
         _c._check_out(out, None, what)
         before, st = self._source.bytes_read, _new_stats()
-        level, m, (oh, ow), mode, lw = self._plan_warp(matrix, size, level, resampling, what)
-        ix = self._open[level][1]
-        kind = _c._check_out(out, ix, what)
-        if kind == _c.KIND_F32_CHW:
-            raise ValueError(f"{what}: the result would be float32; the warped samplers are integer, take out='u8'")
-        fill = ix.get("fill", ix.get("nodata", 0))
-        dtype = torch.uint16 if kind == _c.KIND_U16_HWC else torch.uint8
-        if lw is None:
-            host = np.full((oh, ow, ix["C"]), fill, dtype=np.uint16 if dtype == torch.uint16 else np.uint8)
-            img = torch.from_numpy(host).to(self._dev)
-            oval = torch.zeros((oh, ow), dtype=torch.uint8, device=self._dev)
-        else:
-            src, valid = self._source_window(level, lw, out, st)
-            img = torch.empty((oh, ow, ix["C"]), dtype=dtype, device=self._dev)
-            oval = torch.empty((oh, ow), dtype=torch.uint8, device=self._dev) if with_valid else None
-            _call_by_width("window_warp", src, _opt(valid), lw[2], lw[3], lw[0], lw[1], ix["C"], level, *self.levels[level],
-                           *self.levels[0], (ctypes.c_int64 * 6)(*m), _p(img), _opt(oval), oh, ow, mode,
-                           ix.get("nodata", -1), fill, _stream())
+        level, m, size, mode, lw = self._plan_warp(matrix, size, level, resampling, what)
+        img, oval = self._read_sampled(what, "window_warp", lambda: ((ctypes.c_int64 * 6)(*m),), level, size, mode, lw, out,
+                                       with_valid, st)
         self._finish(st, before, stats, level=level, level_window=lw, matrix_q16=m)
         return (img, oval.bool()) if with_valid else img
 
@@ -1076,22 +1259,9 @@ class ImageReader:
         ValueError as read_warped and render raise it."""
         what = "ImageReader.render_warped"
         before, st = self._source.bytes_read, _new_stats()
-        level, m, (oh, ow), mode, lw = self._plan_warp(matrix, size, level, resampling, what)
-        bands, stretch, alpha, background = self._display(level, bands, stretch, alpha, background)
-        ix = self._open[level][1]
-        n = len(bands) + alpha
-        if lw is None:                                             # beside the image: no stretch needed, nothing decoded
-            img = torch.full((oh, ow, n), background, dtype=torch.uint8, device=self._dev)
-            if alpha:
-                img[:, :, n - 1] = 0
-        else:
-            stretch = self._default_stretch(level, stretch, st)
-            src, valid = self._source_window(level, lw, self._display_out(ix)[0], st)
-            img = torch.empty((oh, ow, n), dtype=torch.uint8, device=self._dev)
-            _call_by_width("window_warp_render", src, _opt(valid), lw[2], lw[3], lw[0], lw[1], ix["C"], level,
-                           *self.levels[level], *self.levels[0], (ctypes.c_int64 * 6)(*m),
-                           (ctypes.c_int * len(bands))(*bands), len(bands), _c._lohi(stretch), _p(img), oh, ow, mode,
-                           ix.get("nodata", -1), alpha, background, _stream())
+        level, m, size, mode, lw = self._plan_warp(matrix, size, level, resampling, what)
+        display = self._display(level, bands, stretch, alpha, background)
+        img = self._render_sampled("window_warp_render", lambda: ((ctypes.c_int64 * 6)(*m),), level, size, mode, lw, display, st)
         self._finish(st, before, stats, level=level, level_window=lw, matrix_q16=m)
         return img
 
@@ -1106,23 +1276,154 @@ class ImageReader:
         ValueError as read_warped and render_index raise it."""
         what = "ImageReader.render_index_warped"
         before, st = self._source.bytes_read, _new_stats()
-        level, m, (oh, ow), mode, lw = self._plan_warp(matrix, size, level, resampling, what)
+        level, m, size, mode, lw = self._plan_warp(matrix, size, level, resampling, what)
         show = self._index_display(level, index, stretch, colormap, alpha, background, what)
-        ix = self._open[level][1]
+        img = self._render_index_sampled("window_warp_index_render", lambda: ((ctypes.c_int64 * 6)(*m),), level, size, mode, lw,
+                                         show, st)
+        self._finish(st, before, stats, level=level, level_window=lw, matrix_q16=m)
+        return img
+
+    # ---- what the warped and the gridded views share: `where` gives the arguments that say where a pixel samples (the
+    # matrix; the mesh's two copies and the step) and is asked only when there is something to launch ----------------
+    def _read_sampled(self, what, stem, where, level, size, mode, lw, out, with_valid, st):
+        """-> (image, validity bytes or None) of one dsic_<stem>_u8 / _u16 call on the planned window lw of `level`"""
+        (oh, ow), ix = size, self._open[level][1]
+        kind = _c._check_out(out, ix, what)
+        if kind == _c.KIND_F32_CHW:
+            raise ValueError(f"{what}: the result would be float32; the warped samplers are integer, take out='u8'")
+        fill = ix.get("fill", ix.get("nodata", 0))
+        dtype = torch.uint16 if kind == _c.KIND_U16_HWC else torch.uint8
+        if lw is None:
+            host = np.full((oh, ow, ix["C"]), fill, dtype=np.uint16 if dtype == torch.uint16 else np.uint8)
+            return torch.from_numpy(host).to(self._dev), torch.zeros((oh, ow), dtype=torch.uint8, device=self._dev)
+        src, valid = self._source_window(level, lw, out, st)
+        img = torch.empty((oh, ow, ix["C"]), dtype=dtype, device=self._dev)
+        oval = torch.empty((oh, ow), dtype=torch.uint8, device=self._dev) if with_valid else None
+        _call_by_width(stem, src, _opt(valid), lw[2], lw[3], lw[0], lw[1], ix["C"], level, *self.levels[level],
+                       *self.levels[0], *where(), _p(img), _opt(oval), oh, ow, mode, ix.get("nodata", -1), fill, _stream())
+        return img, oval
+
+    def _render_sampled(self, stem, where, level, size, mode, lw, display, st):
+        (oh, ow), ix = size, self._open[level][1]
+        bands, stretch, alpha, background = display
+        n = len(bands) + alpha
+        if lw is None:                                             # beside the image: no stretch needed, nothing decoded
+            img = torch.full((oh, ow, n), background, dtype=torch.uint8, device=self._dev)
+            if alpha:
+                img[:, :, n - 1] = 0
+            return img
+        stretch = self._default_stretch(level, stretch, st)
+        src, valid = self._source_window(level, lw, self._display_out(ix)[0], st)
+        img = torch.empty((oh, ow, n), dtype=torch.uint8, device=self._dev)
+        _call_by_width(stem, src, _opt(valid), lw[2], lw[3], lw[0], lw[1], ix["C"], level, *self.levels[level],
+                       *self.levels[0], *where(), (ctypes.c_int * len(bands))(*bands), len(bands), _c._lohi(stretch), _p(img),
+                       oh, ow, mode, ix.get("nodata", -1), alpha, background, _stream())
+        return img
+
+    def _render_index_sampled(self, stem, where, level, size, mode, lw, show, st):
+        (oh, ow), ix = size, self._open[level][1]
         n = 3 + show.alpha
         if lw is None:                                             # beside the image: no stretch needed, nothing decoded
             img = torch.full((oh, ow, n), show.background, dtype=torch.uint8, device=self._dev)
             if show.alpha:
                 img[:, :, n - 1] = 0
+            return img
+        show = self._index_defaults(level, show, st)
+        src, valid = self._source_window(level, lw, self._display_out(ix)[0], st)
+        img = torch.empty((oh, ow, n), dtype=torch.uint8, device=self._dev)
+        _call_by_width(stem, src, _opt(valid), lw[2], lw[3], lw[0], lw[1], ix["C"], level, *self.levels[level],
+                       *self.levels[0], *where(), INDEX_KINDS[show.kind], show.a, show.b, *show.stretch, _p(show.colormap),
+                       _p(img), oh, ow, mode, ix.get("nodata", -1), show.alpha, show.background, _stream())
+        return img
+
+    # ---- gridded views: sample positions from a coordinate mesh, csrc/grid.hip ---------------------------------------
+    def _device_mesh(self, G):
+        """The checked mesh on the device.  The copies of the last few meshes of up to 1 MiB are kept, keyed on their
+        values, so panning and rendering with one mesh uploads it once; a larger mesh is uploaded per call."""
+        if G.nbytes > 1 << 20:
+            return torch.from_numpy(G).to(self._dev)
+        key = (G.shape, G.tobytes())
+        if key in self._meshes:
+            self._meshes.move_to_end(key)
         else:
-            show = self._index_defaults(level, show, st)
-            src, valid = self._source_window(level, lw, self._display_out(ix)[0], st)
-            img = torch.empty((oh, ow, n), dtype=torch.uint8, device=self._dev)
-            _call_by_width("window_warp_index_render", src, _opt(valid), lw[2], lw[3], lw[0], lw[1], ix["C"], level,
-                           *self.levels[level], *self.levels[0], (ctypes.c_int64 * 6)(*m), INDEX_KINDS[show.kind], show.a,
-                           show.b, *show.stretch, _p(show.colormap), _p(img), oh, ow, mode, ix.get("nodata", -1), show.alpha,
-                           show.background, _stream())
-        self._finish(st, before, stats, level=level, level_window=lw, matrix_q16=m)
+            self._meshes[key] = torch.from_numpy(G).to(self._dev)
+            if len(self._meshes) > 8:
+                self._meshes.popitem(last=False)
+        return self._meshes[key]
+
+    def _plan_grid(self, grid, size, step, level, resampling, what):
+        """A gridded request -> (level, (oh, ow), mode, the level's window or None, where): `where`
+        uploads the mesh and gives the library's three mesh arguments."""
+        if resampling not in WARP_RESAMPLING:
+            raise ValueError(f"{what}: resampling={resampling!r} ({', '.join(WARP_RESAMPLING)})")
+        oh, ow = _check_size(size, what, WARP_SIDE, "(1, 1) .. (2^20, 2^20)")
+        try:
+            G = check_grid(grid, (oh, ow), step)
+        except ValueError as e:
+            raise ValueError(f"{what}: {e}") from None
+        if level is None:
+            level = grid_level(len(self.levels), G, step)
+        level = self._level(level)[0]
+        mode = WARP_RESAMPLING[resampling]
+        held = []                                                  # the device copy lives as long as the plan
+
+        def where():
+            held.append(self._device_mesh(G))
+            return G.ctypes.data, _p(held[-1]), step
+        return level, (oh, ow), mode, grid_window(level, *self.levels[level], *self.levels[0], G, mode), where
+
+    @torch.no_grad()
+    def read_gridded(self, grid, size, step=16, level=None, resampling="bilinear", out=None, stats=None, with_valid=False):
+        """A reprojected view of the image: uint8 or uint16 [oh, ow, C] on the device, size = (oh, ow), in one launch
+        (dsic_window_grid_u8 / _u16).  grid is a coordinate mesh, an integer array of grid_shape(size, step): node
+        (a, b) holds the level-0 position (y, x) in Q16 of the output corner (a step, b step), or GRID_NONE in its y
+        entry for "no position here"; affine_grid, projective_grid and function_grid make one, grid_error tells how far
+        a step's mesh is from the exact map.  Output pixel (i, j) samples the bilinear combination of its cell's four
+        nodes at its centre, an integer rule defined bit for bit (include/dsic_hip.h); every pixel of a cell with a
+        none node is fill and invalid.  From the position on, everything is read_warped's: resampling, fill, masks and
+        nodata, with_valid, out.  read_gridded(affine_grid(m, size, step), size, step, level=L) is
+        read_warped of the matrix m at level L, bit for bit.
+        The level sampled is `level`, or grid_level(number of levels, the mesh, step); the window of it that holds every
+        tap (grid_window) comes in through the cache as read_warped brings its window in.  A view wholly beside the
+        image, or without a whole cell, decodes nothing and launches nothing.
+        stats: as read's, with level, level_window (None beside the image) and grid_step.
+        ValueError as read_warped raises it, and for a step outside GRID_STEPS or a mesh check_grid refuses."""
+        what = "ImageReader.read_gridded"
+        _c._check_out(out, None, what)
+        before, st = self._source.bytes_read, _new_stats()
+        level, size, mode, lw, where = self._plan_grid(grid, size, step, level, resampling, what)
+        img, oval = self._read_sampled(what, "window_grid", where, level, size, mode, lw, out, with_valid, st)
+        self._finish(st, before, stats, level=level, level_window=lw, grid_step=step)
+        return (img, oval.bool()) if with_valid else img
+
+    @torch.no_grad()
+    def render_gridded(self, grid, size, step=16, level=None, bands=None, stretch=None, alpha=False, background=0,
+                       resampling="bilinear", stats=None):
+        """The view read_gridded(grid, size, step, level, resampling) as display pixels: torch.uint8 [oh, ow, nb (+ 1)] in
+        one launch (dsic_window_grid_render_u8 / _u16), as render_warped shows read_warped: bands, stretch, alpha and
+        background are render's, with its default stretch; an invalid pixel is `background` and, with alpha, alpha 0.
+        ValueError as read_gridded and render raise it."""
+        what = "ImageReader.render_gridded"
+        before, st = self._source.bytes_read, _new_stats()
+        level, size, mode, lw, where = self._plan_grid(grid, size, step, level, resampling, what)
+        display = self._display(level, bands, stretch, alpha, background)
+        img = self._render_sampled("window_grid_render", where, level, size, mode, lw, display, st)
+        self._finish(st, before, stats, level=level, level_window=lw, grid_step=step)
+        return img
+
+    @torch.no_grad()
+    def render_index_gridded(self, grid, size, index, step=16, level=None, stretch=None, colormap="grey", alpha=False,
+                             background=0, resampling="bilinear", stats=None):
+        """The view read_gridded(grid, size, step, level, resampling) as an index view: torch.uint8 [oh, ow, 3 (+ 1)] in
+        one launch (dsic_window_grid_index_render_u8 / _u16), as render_index_warped shows read_warped: index, stretch,
+        colormap, alpha and background are render_index's, with its default stretch.
+        ValueError as read_gridded and render_index raise it."""
+        what = "ImageReader.render_index_gridded"
+        before, st = self._source.bytes_read, _new_stats()
+        level, size, mode, lw, where = self._plan_grid(grid, size, step, level, resampling, what)
+        show = self._index_display(level, index, stretch, colormap, alpha, background, what)
+        img = self._render_index_sampled("window_grid_index_render", where, level, size, mode, lw, show, st)
+        self._finish(st, before, stats, level=level, level_window=lw, grid_step=step)
         return img
 
 

@@ -997,6 +997,75 @@ int dsic_index_histogram_u16(const uint16_t* img_hwc, const uint8_t* valid_hw, i
                              int nodata, int kind, int band_a, int band_b, uint32_t* hist,
                              void* stream);
 
+/* ---- gridded reads (codec.ImageReader.read_gridded, .render_gridded, .render_index_gridded) ----
+ * A reprojected view: the warp calls with the rule "where does output pixel (i, j) sample" given
+ * by a coordinate mesh instead of a matrix.  step = S = 2^s is 16, 32 or 64; nh = ceil(oh / S), nw
+ * = ceil(ow / S).  The mesh G is int64 [nh + 1][nw + 1][2]: node (a, b) holds the level-0 position
+ * (y, x) in Q16 of the output corner (a S, b S), in the frame of the warp calls' matrix (pixel
+ * (i, j) has its centre at (i + 1/2, j + 1/2)).  Every entry is under 2^48 in size, or a node has
+ * DSIC_GRID_NONE = -2^63 in its y entry: no position here (its x entry is then not looked at).
+ * With a = i >> s, b = j >> s, fu = 2 (i - a S) + 1, fv = 2 (j - b S) + 1, per axis
+ *   P = ((2S - fu) (2S - fv) G[a][b] + (2S - fu) fv G[a][b+1] + fu (2S - fv) G[a+1][b]
+ *        + fu fv G[a+1][b+1]) >> (2 s + 1)
+ * (an arithmetic shift: a floor; the weights sum to 2^(2s+2) <= 2^14, the sum stays under 2^62) is
+ * the position in Q17, and everything after it - the inside test, the level, the taps, the
+ * weights, the masks, fill and validity - is what the warp calls state for their P.  Every pixel
+ * of a cell with a none node is fill, validity 0.  For G[a][b] = m0 a S + m1 b S + m2 per axis, P
+ * = m0 (2 i + 1) + m1 (2 j + 1) + 2 m2: on an affine mesh the result is the warp call's, bit for
+ * bit, for every step and mode.
+ * The mesh is given twice and the library still allocates nothing: mesh_host is what the call
+ * checks before it returns, mesh_dev (the same values, uploaded by the caller, 8-byte aligned) is
+ * what the kernel reads.  Taps are clamped to the source window as well as to the level, so a
+ * device copy that differs cannot make the kernel read outside the source allocation.
+ * The other arguments, the three kinds of call and their outputs are those of
+ * dsic_window_warp_u8 / _u16, dsic_window_warp_render_u8 / _u16 and
+ * dsic_window_warp_index_render_u8 / _u16.
+ * DSIC_EINVAL, nothing written: what the warp sibling refuses, less its matrix; a step other than
+ *   16, 32, 64; more than 2^22 nodes; an entry of 2^48 or more in size; a none mark in an x entry
+ *   whose y entry holds a position; a source window that does not contain every tap the mesh can
+ *   ask for: per axis the positions of a cell lie between the smallest and largest of its four
+ *   nodes, so the box is the minimum and maximum over the nodes of all cells without a none node,
+ *   doubled to Q17, cut to the image, widened by the mode's taps and clamped to the level (no such
+ *   cell, or a box beside the image: any window will do); a mesh_dev that is misaligned or
+ *   overlaps an output. */
+#define DSIC_GRID_NONE INT64_MIN
+int dsic_window_grid_u8(const uint8_t* src_hwc, const uint8_t* src_valid, int sh, int sw, int sy0,
+                        int sx0, int C, int shift, int LH, int LW, int H, int W,
+                        const int64_t* mesh_host, const int64_t* mesh_dev, int step,
+                        uint8_t* dst_hwc, uint8_t* dst_valid, int oh, int ow, int mode, int nodata,
+                        int fill, void* stream);
+int dsic_window_grid_u16(const uint16_t* src_hwc, const uint8_t* src_valid, int sh, int sw,
+                         int sy0, int sx0, int C, int shift, int LH, int LW, int H, int W,
+                         const int64_t* mesh_host, const int64_t* mesh_dev, int step,
+                         uint16_t* dst_hwc, uint8_t* dst_valid, int oh, int ow, int mode,
+                         int nodata, int fill, void* stream);
+int dsic_window_grid_render_u8(const uint8_t* src_hwc, const uint8_t* src_valid, int sh, int sw,
+                               int sy0, int sx0, int C, int shift, int LH, int LW, int H, int W,
+                               const int64_t* mesh_host, const int64_t* mesh_dev, int step,
+                               const int* bands, int nb, const uint32_t* lohi, uint8_t* dst, int oh,
+                               int ow, int mode, int nodata, int alpha, int background,
+                               void* stream);
+int dsic_window_grid_render_u16(const uint16_t* src_hwc, const uint8_t* src_valid, int sh, int sw,
+                                int sy0, int sx0, int C, int shift, int LH, int LW, int H, int W,
+                                const int64_t* mesh_host, const int64_t* mesh_dev, int step,
+                                const int* bands, int nb, const uint32_t* lohi, uint8_t* dst,
+                                int oh, int ow, int mode, int nodata, int alpha, int background,
+                                void* stream);
+int dsic_window_grid_index_render_u8(const uint8_t* src_hwc, const uint8_t* src_valid, int sh,
+                                     int sw, int sy0, int sx0, int C, int shift, int LH, int LW,
+                                     int H, int W, const int64_t* mesh_host,
+                                     const int64_t* mesh_dev, int step, int kind, int band_a,
+                                     int band_b, int lo, int hi, const uint8_t* cmap_dev,
+                                     uint8_t* dst, int oh, int ow, int mode, int nodata, int alpha,
+                                     int background, void* stream);
+int dsic_window_grid_index_render_u16(const uint16_t* src_hwc, const uint8_t* src_valid, int sh,
+                                      int sw, int sy0, int sx0, int C, int shift, int LH, int LW,
+                                      int H, int W, const int64_t* mesh_host,
+                                      const int64_t* mesh_dev, int step, int kind, int band_a,
+                                      int band_b, int lo, int hi, const uint8_t* cmap_dev,
+                                      uint8_t* dst, int oh, int ow, int mode, int nodata, int alpha,
+                                      int background, void* stream);
+
 /* ---- scene stacks (codec.SceneStack.read, .render): n placed windows into one ----
  * dsic_window_composite_u8 / _u16: a mosaic or a per-pixel composite of n source windows in one
  *   launch, without a workspace.  src, src_valid, rect and nodata are host arrays of n entries,

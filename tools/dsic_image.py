@@ -7,13 +7,15 @@ an image.
     python tools/dsic_image.py decompress --weights CKPT.pt IN.dsic OUT.png [--out u8|f32|u16] [--region Y0,X0,H,W]
                                           [--level L] [--size OH,OW] [--resampling average|nearest]
                                           [--valid-out FILE.npy]
-                                          [--rotate DEG [--center Y,X] [--scale S] | --affine M00,M01,M02,M10,M11,M12]
+                                          [--rotate DEG [--center Y,X] [--scale S] | --affine M00,M01,M02,M10,M11,M12
+                                           | --grid FILE.npy [--grid-step S] | --projective H00,...,H22]
                                           [--resampling bilinear|cubic|nearest]
     python tools/dsic_image.py render     --weights CKPT.pt IN.dsic OUT [--region Y0,X0,H,W] [--size OH,OW] [--level L]
                                           [--bands B | B,B,B] [--stretch LO,HI[,LO,HI...]] [--percent P0,P1] [--alpha]
                                           [--background V] [--resampling average|nearest]
                                           [--index KIND:A[,B] [--colormap NAME] [--index-stretch LO,HI | --percent P0,P1]]
-                                          [--rotate DEG [--center Y,X] [--scale S] | --affine M00,M01,M02,M10,M11,M12]
+                                          [--rotate DEG [--center Y,X] [--scale S] | --affine M00,M01,M02,M10,M11,M12
+                                           | --grid FILE.npy [--grid-step S] | --projective H00,...,H22]
                                           [--resampling bilinear|cubic|nearest]
     python tools/dsic_image.py composite  --weights CKPT.pt OUT --scene FILE[@Y,X] [--scene FILE[@Y,X] ...]
                                           [--reduce first|last|mean|median|max|min] [--index nd:A,B|difference:A,B|band:A]
@@ -72,6 +74,12 @@ the image's centre), the image turned counter-clockwise by DEG degrees, at --sca
 order, level-0 pixels per output pixel.  Such a view is sampled with --resampling bilinear (the default), cubic or
 nearest from the level its scale asks for (or --level L); pixels outside the image are fill (render: --background, and
 alpha 0).  --region does not go with it.
+--grid FILE.npy with --size OH,OW (decompress and render) reads a reprojected view through a coordinate mesh
+(codec.ImageReader.read_gridded / render_gridded / render_index_gridded): FILE.npy is int64 [ceil(OH/S) + 1, ceil(OW/S) + 1,
+2], node (a, b) the level-0 position (y, x) in Q16 of the output corner (a S, b S), -2^63 in y for "no position here";
+--grid-step S is 16 (the default), 32 or 64.  --projective H00,...,H22 builds the mesh of the 3 x 3 projective map
+(y', x', w') = H (i, j, 1) instead (codec.projective_grid).  Resampling, level and fill are --rotate's; --rotate, --affine
+and --region do not go with either.
 composite writes a window of a scene stack (codec.SceneStack.read): every --scene FILE[@Y,X] (1 .. 16 streams of one
 integer kind and one band count) is a scene whose level-0 position in the stack's grid is Y,X (default 0,0; all at 0,0
 is a temporal stack), the grid is their bounding box, and each pixel is the --reduce (first, the default, last, mean or
@@ -220,6 +228,10 @@ def warp_matrix(a, ap, region, size):
             ap.error(f"{name} {text}: {what}")
         return values
 
+    if a.mode != "composite" and (a.grid is not None or a.projective is not None):
+        return mesh_view(a, ap, region, size, floats)
+    if a.grid_step is not None:
+        ap.error("--grid-step goes with --grid FILE.npy or --projective")
     warped = a.rotate is not None or a.affine is not None
     if not warped:
         if a.center is not None or (a.scale is not None and a.mode != "compress"):
@@ -267,8 +279,53 @@ def warp_matrix(a, ap, region, size):
     return matrix
 
 
+def mesh_view(a, ap, region, size, floats):
+    """--grid FILE.npy / --projective / --grid-step -> {"grid": the checked mesh, "step": S}, the view of a gridded read
+    (codec.ImageReader.read_gridded); every argument error before the model is loaded."""
+    import numpy as np
+    from dsic_amd import codec
+    if a.mode not in ("decompress", "render"):
+        ap.error("--grid FILE.npy and --projective go with decompress or render")
+    if a.grid is not None and a.projective is not None:
+        ap.error("--grid and --projective exclude each other")
+    if a.rotate is not None or a.affine is not None or region is not None or a.center is not None or a.scale is not None:
+        ap.error("--rotate, --affine, --center, --scale and --region do not go with --grid or --projective: the mesh says "
+                 "where the view lies")
+    if size is None:
+        ap.error("--grid and --projective need --size OH,OW")
+    if a.resampling == "average":
+        ap.error("--resampling average goes with --region; a gridded view takes bilinear, cubic or nearest")
+    a.resampling = a.resampling or "bilinear"
+    if a.valid_out is not None:
+        ap.error("--valid-out does not go with --grid or --projective")
+    step = 16 if a.grid_step is None else a.grid_step
+    try:
+        if a.projective is not None:
+            values = floats(a.projective, 9, "--projective", "nine numbers H00,...,H22")
+            grid = codec.projective_grid([values[:3], values[3:6], values[6:]], tuple(size), step)
+        else:
+            grid = codec.check_grid(np.load(a.grid), tuple(size), step)
+    except (OSError, ValueError) as e:
+        ap.error(f"--grid {a.grid}: {e}" if a.grid is not None else str(e))
+    return {"grid": grid, "step": step}
+
+
+def view_call(reader, stem, view, size, **kw):
+    """reader.<stem>_warped of an affine view (a matrix), or reader.<stem>_gridded of a mesh view (mesh_view's dict)"""
+    if isinstance(view, dict):
+        return getattr(reader, stem + "_gridded")(view["grid"], size, step=view["step"], **kw)
+    return getattr(reader, stem + "_warped")(view, size, **kw)
+
+
+def view_words(view, stats):
+    if isinstance(view, dict):
+        return f"mesh view of {view['grid'].shape[0]}x{view['grid'].shape[1]} nodes at step {stats['grid_step']}"
+    return f"affine view {', '.join(f'{v / 65536:g}' for v in stats['matrix_q16'])}"
+
+
 def render_main(a, ap, region, size, level_given, matrix=None):
-    """The render mode: every argument error before the model is loaded."""
+    """The render mode: every argument error before the model is loaded.  matrix: None for a window, else the affine or
+    mesh view of warp_matrix."""
     from dsic_amd import codec
 
     def numbers(text, cast, name, counts, what):
@@ -341,11 +398,10 @@ def render_main(a, ap, region, size, level_given, matrix=None):
             wanted = a.percent is not None or reader.kind == codec.KIND_U16_HWC
             stretch = reader.stretch(percent) if wanted else [(0, 255)] * C
         if matrix is not None:
-            img = reader.render_warped(matrix, tuple(size), level=a.level if level_given else None, bands=bands,
-                                       stretch=stretch, alpha=a.alpha, background=a.background, resampling=a.resampling,
-                                       stats=stats)
+            img = view_call(reader, "render", matrix, tuple(size), level=a.level if level_given else None, bands=bands,
+                            stretch=stretch, alpha=a.alpha, background=a.background, resampling=a.resampling, stats=stats)
             path = write_display(a.dst, img.cpu().numpy())
-            print(f"[dsic_image] affine view {', '.join(f'{v / 65536:g}' for v in stats['matrix_q16'])} as "
+            print(f"[dsic_image] {view_words(matrix, stats)} as "
                   f"{img.shape[0]}x{img.shape[1]} ({a.resampling}) from level {stats['level']}, bands "
                   f"{','.join(str(b) for b in bands)}" + (" + alpha" if a.alpha else "") + ", stretch "
                   + ", ".join(f"({lo}, {hi})" for lo, hi in stretch) + f": {len(stats['tiles'])} tile(s) -> {path}")
@@ -372,13 +428,13 @@ def render_index_main(a, model, index, pair, region, size, level_given, matrix):
             shown = dict(index=index, level=level, stretch=pair, colormap=a.colormap, alpha=a.alpha,
                          background=a.background, resampling=a.resampling, stats=stats)
             if matrix is not None:
-                img = reader.render_index_warped(matrix, tuple(size), **shown)
+                img = view_call(reader, "render_index", matrix, tuple(size), **shown)
             else:
                 img = reader.render_index(*region, size=None if size is None else tuple(size), **shown)
         except ValueError as e:
             raise SystemExit(f"[dsic_image] {e}")
     path = write_display(a.dst, img.cpu().numpy())
-    what = (f"affine view {', '.join(f'{v / 65536:g}' for v in stats['matrix_q16'])}" if matrix is not None
+    what = (view_words(matrix, stats) if matrix is not None
             else f"window {region[2]}x{region[3]} at ({region[0]}, {region[1]})")
     print(f"[dsic_image] {what} as {img.shape[0]}x{img.shape[1]} ({a.resampling}) from level "
           f"{stats.get('level', a.level)}, index {a.index}, colormap {a.colormap}" + (" + alpha" if a.alpha else "")
@@ -638,8 +694,15 @@ def main(argv=None):
     ap.add_argument("--scene", action="append", default=None, metavar="FILE[@Y,X | @M00,M01,M02,M10,M11,M12]",
                     help="composite: a scene's stream and its level-0 position in the stack's grid (default 0,0), or with six "
                          "numbers its placement, scene level-0 pixels per grid pixel (warped views only); repeatable")
-    ap.add_argument("--grid", default=None, metavar="H,W",
-                    help="composite: the stack's grid (default: the scenes' bounding box; with placements the first scene's size)")
+    ap.add_argument("--grid", default=None, metavar="H,W | FILE.npy",
+                    help="composite: the stack's grid H,W (default: the scenes' bounding box; with placements the first "
+                         "scene's size); decompress, render: with --size, a reprojected view through the coordinate mesh "
+                         "FILE.npy, int64 [ceil(OH/S)+1, ceil(OW/S)+1, 2] of level-0 positions (y, x) in Q16")
+    ap.add_argument("--grid-step", type=int, default=None, metavar="S", help="--grid FILE.npy, --projective: the mesh's step, "
+                    "16 (the default), 32 or 64 output pixels")
+    ap.add_argument("--projective", default=None, metavar="H00,H01,H02,H10,H11,H12,H20,H21,H22",
+                    help="decompress, render: with --size, the view (y', x', w') = H (i, j, 1), y = y'/w', x = x'/w', through "
+                         "a mesh of its exact positions (codec.projective_grid)")
     ap.add_argument("--reduce", choices=("first", "last", "mean", "median", "max", "min"), default="first",
                     help="composite: what a pixel takes from the scenes that are valid there; max and min: the whole pixel of "
                          "the scene whose --index is largest or smallest")
@@ -685,14 +748,17 @@ def main(argv=None):
             size = [int(v) for v in a.size.split(",")]
         except ValueError:
             size = []
-        warped = a.rotate is not None or a.affine is not None
+        meshed = a.mode != "composite" and (a.grid is not None or a.projective is not None)   # composite's --grid is H,W
+        warped = a.rotate is not None or a.affine is not None or meshed
         if (region is None and a.mode != "render" and not warped) or len(size) != 2:
-            ap.error("--size OH,OW (two integers) goes with decompress --region, --rotate or --affine, or with render")
+            ap.error("--size OH,OW (two integers) goes with decompress --region, --rotate, --affine, --grid or --projective, "
+                     "or with render")
     if a.scale is not None and a.mode != "compress" and a.rotate is None:
         ap.error("--scale goes with compress, or with --rotate")
     if a.mode == "composite":
         if (a.valid is not None or a.out is not None or a.bands is not None or a.stretch is not None or a.alpha
-                or a.colormap != "grey" or a.index_stretch is not None):
+                or a.colormap != "grey" or a.index_stretch is not None or a.projective is not None
+                or a.grid_step is not None):
             ap.error("composite takes --scene, --reduce, --index, --region, --level, --fill, --count-out, --valid-out, "
                      "--source-out, and for a warped view --rotate, --center, --scale, --affine, --size, --resampling and --grid")
         return composite_main(a, ap, region, size)
@@ -747,11 +813,11 @@ def main(argv=None):
     elif matrix is not None:
         stats = {}
         with open(a.src, "rb") as f, codec.ImageReader(model, f, batch=a.batch) as reader:
-            img = reader.read_warped(matrix, tuple(size), level=a.level if given else None, out=a.out,
-                                     resampling=a.resampling, stats=stats)
+            img = view_call(reader, "read", matrix, tuple(size), level=a.level if given else None, out=a.out,
+                            resampling=a.resampling, stats=stats)
             stats["bytes_read"] = reader.stats["bytes_read"]                  # the heads included
         path = write_image(a.dst, img)
-        print(f"[dsic_image] affine view {', '.join(f'{v / 65536:g}' for v in stats['matrix_q16'])} as {size[0]}x{size[1]} "
+        print(f"[dsic_image] {view_words(matrix, stats)} as {size[0]}x{size[1]} "
               f"({a.resampling}) from level {stats['level']}: {len(stats['tiles'])} tile(s), "
               f"{stats['bytes_read']} of {os.path.getsize(a.src)} bytes read -> {path}")
     elif size is not None:

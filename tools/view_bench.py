@@ -1,6 +1,6 @@
 """Pan and zoom: codec.ImageReader against one decompress_region call per frame, and the resampling kernel alone.
 
-    python tools/view_bench.py [--size 4096] [--tile 256] [--reps 3] [--json profiles/view_bench.json] [--only warp|index|composite|warp_composite]
+    python tools/view_bench.py [--size 4096] [--tile 256] [--reps 3] [--json profiles/view_bench.json] [--only warp|grid|index|composite|warp_composite]
 
 The scene of image_codec_bench.py (synthetic patches side by side, uint8) is coded once with overviews=3.  A viewport
 of 768 rows x 1024 columns pans right in 32 steps of 64 pixels (33 frames).  Per frame, alternately in one process:
@@ -23,6 +23,12 @@ render(..., alpha=True) and with render_warped at 0 and at 30 degrees about the 
 per output pixel, bilinear and cubic: the median wall clock of 30 calls each, the order rotating from round to round,
 and each call's kernel alone on the window it planned (device events, as above).  --only warp measures that record
 alone and puts it into the --json file beside the records already there.
+grid (--only grid alone): the same four warped views as render_warped, and each as render_gridded of its affine mesh
+(codec.affine_grid) at the steps 16 and 64 at the same level, so the same pixels bit for bit; and one tilted view
+(codec.projective_grid, step 16) with the distance grid_error gives its mesh at every step.  Calls and kernels are timed
+as in the warp record, all in one rotation, so a gridded figure stands beside the affine one of the same process.
+Those kernels take about 10 us, near the launch itself, and the host reads the mesh before every launch; so `large` times
+the render kernels alone on a 4096 x 4096 view turned by 30 degrees, affine against its mesh at the steps 16 and 64.
 index: the same frame and the same requests as index views: render_index with ("nd", 0, 1) through "ndvi" beside
 render with three bands, render_index_warped beside render_warped at 0 and 30 degrees (bilinear), all with alpha, each
 as a call (the median wall clock of 30, the order rotating) and as its kernel alone on the window it planned; and
@@ -142,6 +148,107 @@ def _warp_record(model, stream, win, batch, rounds=30):
                          "call_max_ms": round(max(times[name]), 4), "level": level, "level_window": list(lw),
                          "kernel_us_per_launch": round(_per_launch_us(launch), 2)}
     return rec
+
+
+def _grid_record(model, stream, win, batch, rounds=30):
+    """The `grid` record: see the module's docstring."""
+    import torch
+    from dsic_amd import codec, lib
+    from dsic_amd.ops import _p, _stream
+    L = lib.load()
+    cy, cx, scale = win[0] + win[2] / 2, win[1] + win[3] / 2, win[2] / SIZE[0]
+    rec = {"view_size": list(SIZE), "level0_pixels_per_output_pixel": scale, "centre": [cy, cx], "rounds": rounds}
+    bands, lohi = (ctypes.c_int * 3)(0, 1, 2), codec._lohi([(0, 255)] * 3)
+    rgba = torch.empty(SIZE + (4,), dtype=torch.uint8, device="cuda")
+    # a tilted view of the same frame: the far edge a quarter shorter
+    tilt = [[scale, 0, win[0]], [0, scale, win[1]], [0.25 / SIZE[0], 0, 1]]
+    with codec.ImageReader(model, stream, batch=batch) as r:
+        H, W = r.levels[0]
+        calls, plans = {}, {}
+        for deg in (0, 30):
+            for res in ("bilinear", "cubic"):
+                matrix = codec.rotation_affine(cy, cx, deg, scale, *SIZE)
+                m = codec.affine_q16(matrix)
+                level = codec.warp_level(len(r.levels), m)
+                name = f"{deg} deg {res}"
+                calls[f"render_warped {name}"] = lambda matrix=matrix, res=res: r.render_warped(
+                    matrix, SIZE, alpha=True, resampling=res)
+                plans[f"render_warped {name}"] = (None, m, None, res, level)
+                for S in (16, 64):
+                    mesh = codec.affine_grid(m, SIZE, S)
+                    calls[f"render_gridded {name} step {S}"] = lambda mesh=mesh, S=S, res=res, level=level: r.render_gridded(
+                        mesh, SIZE, S, level=level, alpha=True, resampling=res)
+                    plans[f"render_gridded {name} step {S}"] = (mesh, None, S, res, level)
+        tilted = codec.projective_grid(tilt, SIZE, 16)
+        name = "render_gridded projective bilinear step 16"
+        calls[name] = lambda: r.render_gridded(tilted, SIZE, 16, alpha=True)
+        plans[name] = (tilted, None, 16, "bilinear", codec.grid_level(len(r.levels), tilted, 16))
+
+        def exact(i, j):                                                   # the map the tilted meshes interpolate
+            w = 0.25 / SIZE[0] * i + 1
+            return (scale * i + win[0]) / w, (scale * j + win[1]) / w
+        rec["projective_grid_error_pixels"] = {str(S): round(codec.grid_error(exact, codec.projective_grid(tilt, SIZE, S), SIZE, S), 6)
+                                               for S in codec.GRID_STEPS}
+        for fn in calls.values():                                          # untimed: the tiles into the cache, every shape
+            fn(), fn()
+        torch.cuda.synchronize()
+        times, names = {name: [] for name in calls}, list(calls)
+        for k in range(rounds):
+            for name in names[k % len(names):] + names[:k % len(names)]:
+                times[name].append(_frame_ms(calls[name]))
+        for name in names:
+            mesh, m, S, res, level = plans[name]
+            mode = {"bilinear": 0, "cubic": 2}[res]
+            if mesh is None:
+                lw = codec.warp_window(level, *r.levels[level], H, W, m, *SIZE, mode)
+                where = ((ctypes.c_int64 * 6)(*m),)
+                export = L.dsic_window_warp_render_u8
+            else:
+                lw = codec.grid_window(level, *r.levels[level], H, W, mesh, mode)
+                dev = torch.from_numpy(mesh).cuda()
+                where = (mesh.ctypes.data, _p(dev), S)
+                export = L.dsic_window_grid_render_u8
+            src = torch.randint(0, 256, (lw[2], lw[3], 3), dtype=torch.uint8, device="cuda")
+
+            def launch():
+                lib.check(export(_p(src), None, lw[2], lw[3], lw[0], lw[1], 3, level, *r.levels[level], H, W, *where, bands, 3,
+                                 lohi, _p(rgba), *SIZE, mode, -1, 1, 0, _stream()), name)
+            rec[name] = {"call_median_ms": round(statistics.median(times[name]), 4),
+                         "call_max_ms": round(max(times[name]), 4), "level": level, "level_window": list(lw),
+                         "kernel_us_per_launch": round(_per_launch_us(launch), 2)}
+    rec["large"] = _grid_large(L, lib, bands, lohi)
+    return rec
+
+
+def _grid_large(L, lib, bands, lohi, side=4096, rounds=3):
+    """The kernels alone where the launch and the host's look at the mesh do not show: a 4096 x 4096 view of a random
+    4096 x 4096 x 3 level turned by 30 degrees at 0.8 level pixels per output pixel (warp_ref's rot30), as
+    dsic_window_warp_render_u8 and as dsic_window_grid_render_u8 of its affine mesh at the steps 16 and 64; device
+    events, 20 launches after 5, three rounds, the three kinds alternating within a round."""
+    import torch
+    from dsic_amd import codec
+    from dsic_amd.ops import _p, _stream
+    src = torch.randint(0, 256, (side, side, 3), dtype=torch.uint8, device="cuda")
+    rgba = torch.empty((side, side, 4), dtype=torch.uint8, device="cuda")
+    m = codec.affine_q16(codec.rotation_affine(side / 2, side / 2, 30, 0.8, side, side))
+    out = {"view_size": [side, side], "matrix_q16": list(m), "rounds": rounds}
+    for res, mode in (("bilinear", 0), ("cubic", 2)):
+        kinds = {"warp": (L.dsic_window_warp_render_u8, ((ctypes.c_int64 * 6)(*m),), None)}
+        for S in (16, 64):
+            mesh = codec.affine_grid(m, (side, side), S)
+            kinds[f"grid step {S}"] = (L.dsic_window_grid_render_u8, (mesh.ctypes.data, None, S), torch.from_numpy(mesh).cuda())
+        us = {k: [] for k in kinds}
+        for _ in range(rounds):
+            for k, (export, where, dev) in kinds.items():
+                if dev is not None:
+                    where = (where[0], _p(dev), where[2])
+
+                def launch():
+                    lib.check(export(_p(src), None, side, side, 0, 0, 3, 0, side, side, side, side, *where, bands, 3, lohi,
+                                     _p(rgba), side, side, mode, -1, 1, 0, _stream()), k)
+                us[k].append(round(_per_launch_us(launch, 20), 1))
+        out[res] = us
+    return out
 
 
 def _index_record(model, stream, img, win, batch, rounds=30):
@@ -422,7 +529,7 @@ def main():
     ap.add_argument("--batch", type=int, default=64)
     ap.add_argument("--reps", type=int, default=3)
     ap.add_argument("--json", default=os.path.join(ROOT, "profiles", "view_bench.json"))
-    ap.add_argument("--only", choices=("warp", "index", "composite", "warp_composite"), default=None,
+    ap.add_argument("--only", choices=("warp", "grid", "index", "composite", "warp_composite"), default=None,
                     help="measure this record alone and put it into the --json file beside the others")
     a = ap.parse_args()
 
@@ -463,6 +570,8 @@ def main():
             res = json.load(f)
         if a.only == "warp":
             res["warp"] = _warp_record(model, stream, frames[STEPS // 2], a.batch)
+        elif a.only == "grid":
+            res["grid"] = _grid_record(model, stream, frames[STEPS // 2], a.batch)
         else:
             res["index"] = _index_record(model, stream, img, frames[STEPS // 2], a.batch)
         print(json.dumps(res[a.only]))
