@@ -96,6 +96,9 @@ readers on one grid and composites their windows per pixel in one launch (csrc/c
 median, or the whole pixel of the scene whose index is largest or smallest (stack_reduce names the forms).
 SceneStack.read_warped samples every scene under its own affine and combines them in the same launch
 (csrc/warp_composite.hip; compose_q16 and stack_warp_parts are its planning).
+ImageReader.zonal_stats and SceneStack.zonal_stats measure instead of showing: per zone of a uint16 zone raster the count,
+sum, sum of squares, minimum and maximum of every band or of an index, in integers, reduced on the device strip by strip
+(csrc/zonal.hip); zonal_table makes means and deviations of the table, zonal_percentile medians of the optional bins.
 """
 from __future__ import annotations
 
@@ -1484,3 +1487,4 @@ from .view import SceneStack, stack_levels, stack_parts, stack_reduce  # noqa: E
 from .view import check_q16, compose_q16, stack_warp_parts  # noqa: E402
 from .view import GRID_NONE, GRID_STEPS, affine_grid, check_grid, function_grid, grid_error, grid_level  # noqa: E402
 from .view import grid_shape, grid_window, projective_grid  # noqa: E402
+from .view import ZONE_NONE, zonal_args, zonal_percentile, zonal_table  # noqa: E402

@@ -16,6 +16,8 @@ LIB_PATH = os.environ.get("DSIC_LIB") or os.path.join(HERE, "libdsic_hip.so")
 
 DSIC_OK, DSIC_EINVAL, DSIC_EHIP = 0, 1, 2
 ACT_NONE, ACT_GDN, ACT_IGDN, ACT_RELU = 0, 1, 2, 3
+ZONAL_BANDS = -1                   # DSIC_ZONAL_BANDS: dsic_zonal_stats_* measure every band
+ZONAL_LDS_BYTES = 40960            # DSIC_ZONAL_LDS_BYTES: a table of Z K 40 bytes up to this is gathered in LDS
 
 _P = c_void_p
 # name -> (restype, argtypes); mirrors include/dsic_hip.h one to one
@@ -176,6 +178,8 @@ SIGNATURES = {
     "dsic_window_composite_pick_u16": (c_int, [_P, _P, _P, _P, _P, c_int, c_int, _P, _P, _P, _P] + [c_int] * 7 + [_P]),
     "dsic_window_warp_composite_u8": (c_int, [_P, c_int, c_int, _P, _P, _P, _P] + [c_int] * 8 + [_P]),
     "dsic_window_warp_composite_u16": (c_int, [_P, c_int, c_int, _P, _P, _P, _P] + [c_int] * 8 + [_P]),
+    "dsic_zonal_stats_u8": (c_int, [_P, _P, _P] + [c_int] * 8 + [_P, _P, _P, _P]),
+    "dsic_zonal_stats_u16": (c_int, [_P, _P, _P] + [c_int] * 8 + [_P, _P, _P, _P]),
     "dsic_stream_create_masked":(c_int, [_P, c_int, _P]),
     "dsic_stream_destroy": (c_int, [_P]),
     "dsic_range_decode": (c_int, [_P, c_int64, _P, c_int, c_int, _P, c_int, _P, c_int, c_int, c_int,

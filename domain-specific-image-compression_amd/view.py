@@ -22,6 +22,10 @@ whole pixel of the scene whose index (an NDVI, say) is largest or smallest there
 Its read_warped, render_warped and render_index_warped do that for an affine view: the view's matrix composed with every
 scene's own (compose_q16), the scenes it meets planned as a reader plans a warped read (stack_warp_parts), and one
 launch that samples every scene and reduces the samples (csrc/warp_composite.hip).
+zonal_stats, of a reader and of a stack, ends in numbers instead of pixels: per zone of a zone raster (fields, parcels,
+catchments) the count, mean, spread, minimum and maximum of every band or of an index, and on request a 256-bin
+histogram per zone for medians, reduced on the device from the tiles under the zones alone (csrc/zonal.hip; zonal_args
+checks a request, zonal_table turns the device table into the result, zonal_percentile reads percentiles off the bins).
 
 The cache holds what the stitch and blend calls consume: per (level, tile) the tile's g_s output, float32
 [C, th, tw], not clamped, and for a near-lossless level its q plane.  A window is served by collecting its tiles, in
@@ -450,6 +454,147 @@ COLORMAPS = {
     # black -> red -> yellow -> white
     "heat": colormap_from_anchors([(0, (0, 0, 0)), (96, (255, 0, 0)), (192, (255, 255, 0)), (255, (255, 255, 255))]),
 }
+
+
+# ---- zonal statistics: per zone of a zone raster, the moments and extremes of the bands or of an index ----------------
+ZONE_NONE = 65535                                                # the id that belongs to no zone, whatever n_zones is
+ZONAL_WORDS = 5                                                  # count, sum, sum of squares, min, max
+_I64_MAX, _I64_MIN = (1 << 63) - 1, -(1 << 63)
+
+
+def zonal_args(what, zones, level_shape, C, top, y0=0, x0=0, of=None, n_zones=None, bins=None) -> tuple:
+    """The arguments of a zonal_stats call over a level of level_shape = (H, W) with C bands of samples 0 .. top, checked
+    (pure Python / NumPy, and torch for a tensor of zones) -> (the zones as a contiguous uint16 array or tensor, (y0, x0,
+    h, w), (what, a, b) as dsic_zonal_stats_u8 takes them, K, Z, vmin, None or the K pairs in u units).  `what` names
+    the caller in a ValueError: zones that are not uint16 [h, w] or leave the level, an `of` that is no index of the
+    bands, an n_zones outside 1 .. 65535, bins that are not one pair vmin <= lo <= hi <= vmax per value."""
+    if isinstance(zones, torch.Tensor):
+        u16 = zones.dtype == torch.uint16
+    else:
+        u16 = isinstance(zones, np.ndarray) and zones.dtype == np.uint16
+    shape = tuple(zones.shape) if u16 else ()
+    if not u16 or len(shape) != 2 or min(shape) < 1:
+        raise ValueError(f"{what}: zones must be a uint16 NumPy array or torch tensor [h, w] of at least 1 x 1, got "
+                         f"{type(zones).__name__} {getattr(zones, 'dtype', '')} {list(getattr(zones, 'shape', ()))}")
+    try:
+        y0, x0 = operator.index(y0), operator.index(x0)
+    except TypeError:
+        raise ValueError(f"{what}: y0={y0!r}, x0={x0!r}: not integers") from None
+    (h, w), (H, W) = shape, level_shape
+    if y0 < 0 or x0 < 0 or y0 + h > H or x0 + w > W:
+        raise ValueError(f"{what}: zones {h}x{w} at ({y0}, {x0}) leave the {H}x{W} level")
+    if h * w >= 1 << 32:
+        raise ValueError(f"{what}: zones {h}x{w}: 2^32 pixels or more")
+    if of is None:
+        code, K, kind = (_lib.ZONAL_BANDS, 0, 0), C, "band"
+    else:
+        kind, a, b = _check_index(C, of, what)
+        code, K = (INDEX_KINDS[kind], a, b), 1
+    vmin, vmax = index_range(kind, top)
+    if n_zones is None:
+        flat = zones.reshape(-1)
+        if isinstance(zones, torch.Tensor):                      # torch has no comparison of uint16: widen first
+            flat = flat.contiguous().view(torch.int16).to(torch.int32) & 0xFFFF
+        real = flat[flat != ZONE_NONE]
+        n_zones = int(real.max()) + 1 if real.shape[0] else 1
+    try:
+        n_zones = operator.index(n_zones)
+    except TypeError:
+        raise ValueError(f"{what}: n_zones={n_zones!r} is not an integer") from None
+    if not 1 <= n_zones <= 65535:
+        raise ValueError(f"{what}: n_zones={n_zones} must be in 1 .. 65535")
+    pairs = None
+    if bins is not None:
+        try:
+            pairs = [tuple(operator.index(v) for v in pair) for pair in bins]
+        except TypeError:
+            raise ValueError(f"{what}: bins={bins!r} is not a sequence of integer pairs (lo, hi)") from None
+        if len(pairs) != K or any(len(pair) != 2 for pair in pairs):
+            raise ValueError(f"{what}: bins={bins!r} must hold one pair (lo, hi) for each of the {K} values of a pixel")
+        for lo, hi in pairs:
+            if not vmin <= lo <= hi <= vmax:
+                raise ValueError(f"{what}: bins pair ({lo}, {hi}) must have {vmin} <= lo <= hi <= {vmax}")
+        pairs = [(lo - vmin, hi - vmin) for lo, hi in pairs]
+    zones = zones.contiguous() if isinstance(zones, torch.Tensor) else np.ascontiguousarray(zones)
+    return zones, (y0, x0, h, w), code, K, n_zones, vmin, pairs
+
+
+def zonal_table(stats_words, hist=None) -> dict:
+    """The result of a zonal_stats call from its device table (pure Python / NumPy).  stats_words: [Z, K, 5] 64-bit words
+    (int64 or uint64, an array or a tensor), as dsic_zonal_stats_u8 / _u16 leave them: count, sum, sum of squares, min,
+    max.  -> a dict of NumPy arrays [Z, K]: count, sum, min, max int64 (min and max 0 where count is 0), sumsq uint64,
+    mean and std float64, nan where count is 0.  mean = sum / n and std = sqrt((n sumsq - sum^2) / n^2), the population's,
+    are taken from Python's integers with one true division each: no cancellation between floats enters.
+    hist: None, or the [Z, K, 256] counters of the same call -> `hist` int64 beside them."""
+    words = stats_words.cpu().numpy() if isinstance(stats_words, torch.Tensor) else np.asarray(stats_words)
+    if words.ndim != 3 or words.shape[2] != ZONAL_WORDS or words.dtype not in (np.int64, np.uint64):
+        raise ValueError(f"zonal_table: stats_words must be 64-bit words [Z, K, {ZONAL_WORDS}]")
+    words = np.ascontiguousarray(words)
+    Z, K, _ = words.shape
+    signed, unsigned = words.view(np.int64), words.view(np.uint64)
+    count = unsigned[:, :, 0].astype(np.int64)                   # under 2^32 pixels per call: far from 2^63
+    some = count != 0
+    out = {"count": count, "sum": signed[:, :, 1].copy(), "sumsq": unsigned[:, :, 2].copy(),
+           "min": np.where(some, signed[:, :, 3], 0), "max": np.where(some, signed[:, :, 4], 0),
+           "mean": np.full((Z, K), np.nan), "std": np.full((Z, K), np.nan)}
+    for z, k in zip(*np.nonzero(some)):
+        n, s, q = int(count[z, k]), int(out["sum"][z, k]), int(out["sumsq"][z, k])
+        out["mean"][z, k] = s / n
+        out["std"][z, k] = math.sqrt((n * q - s * s) / (n * n))
+    if hist is not None:
+        h = hist.cpu().numpy() if isinstance(hist, torch.Tensor) else np.asarray(hist)
+        if h.shape != (Z, K, 256) or h.dtype.kind not in "iu":
+            raise ValueError(f"zonal_table: hist must be integer counters [{Z}, {K}, 256]")
+        out["hist"] = h.astype(np.int64) & 0xFFFFFFFF if h.dtype.itemsize == 4 else h.astype(np.int64)
+    return out
+
+
+def zonal_percentile(result, q) -> np.ndarray:
+    """The q-th percentile (0 <= q <= 100) per zone and value of a zonal_stats result that has bins, in value units:
+    float64 [Z, K], nan for a zone without pixels.  stretch_from_histogram's rule for one q: the bin is the least k whose
+    cumulative count reaches max(1, ceil(round(100 q) n / 10000)); its value is lo + k (hi - lo) / 255 rounded half up,
+    the middle of the values the stretch sends to k.  With bins (0, 255) on a uint8 band that is the exact percentile,
+    q = 50 the (lower) median."""
+    p = _check_percent((q, q))[0]
+    if "hist" not in result or "bins" not in result:
+        raise ValueError("zonal_percentile: the result has no histogram; ask zonal_stats for bins=")
+    hist, bins = np.asarray(result["hist"]), np.asarray(result["bins"])
+    Z, K, _ = hist.shape
+    out = np.full((Z, K), np.nan)
+    for k in range(K):
+        lo, hi = int(bins[k][0]), int(bins[k][1])
+        picked = stretch_from_histogram(hist[:, k, :], (p, p))
+        for z in range(Z):
+            if hist[z, k].any():
+                out[z, k] = lo + (2 * picked[z][0] * (hi - lo) + 255) // 510
+    return out
+
+
+class _ZonalRun:
+    """The device side of one zonal_stats call: the table with its initial words, the optional histogram, and the strips
+    that accumulate into them."""
+
+    def __init__(self, dev, code, K, Z, pairs):
+        self.code, self.K, self.Z = code, K, Z
+        self.table = torch.zeros((Z, K, ZONAL_WORDS), dtype=torch.int64, device=dev)
+        self.table[:, :, 3] = _I64_MAX
+        self.table[:, :, 4] = _I64_MIN
+        self.hist = self.lohi = None
+        if pairs is not None:
+            self.hist = torch.zeros((Z, K, 256), dtype=torch.int32, device=dev)       # the kernel's uint32 counters
+            self.lohi = (ctypes.c_uint32 * (2 * K))(*[v for pair in pairs for v in pair])
+
+    def strip(self, img, valid, zones, nodata):
+        """img [h, w, C] with its validity or None, and the zones of the same rows, contiguous: one call."""
+        h, w, C = img.shape
+        _call_by_width("zonal_stats", img, _opt(valid), _p(zones), h, w, C, nodata, *self.code, self.Z, _p(self.table),
+                       self.lohi, _opt(self.hist), _stream())
+
+    def result(self, vmin, pairs):
+        out = zonal_table(self.table, self.hist)
+        if pairs is not None:
+            out["bins"] = np.array([(lo + vmin, hi + vmin) for lo, hi in pairs], dtype=np.int64)
+        return out
 
 
 def _has_q(ix):
@@ -1205,6 +1350,46 @@ class ImageReader:
         lo, hi = stretch_from_histogram(self._index_histogram(index, level, st)[None], percent)[0]
         return lo + vmin, hi + vmin
 
+    # ---- zonal statistics ----------------------------------------------------------------------------------------
+    @torch.no_grad()
+    def zonal_stats(self, zones, y0=0, x0=0, level=0, of=None, n_zones=None, bins=None, stats=None):
+        """Per zone, how many pixels count and the mean, spread, minimum and maximum of each band or of an index, from
+        the tiles under the zones alone.  zones: a NumPy or torch uint16 raster [h, w] laid at (y0, x0) of `level`'s own
+        pixel grid; a pixel belongs to zone zones[p] if that is under n_zones (default: one more than the largest id
+        other than 65535, the customary "none"), every other id to no zone.  of = None measures every band (K = C values
+        per pixel); an index as render_index takes it, ("nd", a, b), ("difference", a, b) or ("band", a), measures that
+        index (K = 1), a normalised difference in units of 1 / 10000 and only where it is defined.  The pixels that
+        histogram counts are counted: the valid ones of a stream with a validity mask, of a nodata stream those that are
+        not nodata; a float32-kind stream is measured in its out="u8" form.
+        -> zonal_table's dict of NumPy arrays [n_zones, K]: count, sum, sumsq, min, max, mean, std.  bins: None, or one
+        pair (lo, hi) per value in value units: the result then has hist, int64 [n_zones, K, 256], the counts of
+        the render stretch's byte between lo and hi ((0, 255) on a uint8 band: the exact histogram), and bins;
+        zonal_percentile reads medians and other percentiles off them.
+        The window is read in strips of whole tile rows through the reader's own window path, so the cache and its limits
+        apply; the zone raster goes to the device once, and every strip accumulates into one table on the device
+        (dsic_zonal_stats_u8 / _u16).  Nothing is kept: a second call measures again, from the cached tiles.
+        stats (a dict) receives the call's counters as read's.  ValueError: zones of another dtype or shape, or that
+        leave the level; an unknown index; n_zones outside 1 .. 65535; bins that are not one ordered pair per value
+        inside the value range."""
+        what = "ImageReader.zonal_stats"
+        before, st = self._source.bytes_read, _new_stats()
+        level, _, ix = self._level(level)
+        out, top = self._display_out(ix)
+        zones, (y0, x0, h, w), code, K, Z, vmin, pairs = zonal_args(what, zones, (ix["H"], ix["W"]), ix["C"], top, y0, x0, of,
+                                                                    n_zones, bins)
+        zdev = (zones if isinstance(zones, torch.Tensor) else torch.from_numpy(zones)).to(self._dev)
+        run = _ZonalRun(self._dev, code, K, Z, pairs)
+        g = ix["grid"]
+        rows = g["th"] * max(1, self.batch // (-(-w // g["tw"]) + 1))    # tile rows that fill about one decode batch
+        y = y0
+        while y < y0 + h:
+            hh = min((y // rows + 1) * rows, y0 + h) - y           # strips end where tile rows end
+            img, valid = self._source_window(level, (y, x0, hh, w), out, st)
+            run.strip(img.contiguous(), valid, zdev[y - y0:y - y0 + hh], ix.get("nodata", -1))
+            y += hh
+        self._finish(st, before, stats)
+        return run.result(vmin, pairs)
+
     # ---- warped views -------------------------------------------------------------------------------------------
     def _plan_warp(self, matrix, size, level, resampling, what):
         """A warped request -> (level, the Q16 matrix, (oh, ow), mode, the level's window or None)."""
@@ -1717,6 +1902,34 @@ class SceneStack:
         return self._index_display(img, valid, window[0], window[1], *show)
 
     # ---- the display tails, shared by the window methods and the warped ones -------------------------------------
+    @torch.no_grad()
+    def zonal_stats(self, zones, y0=0, x0=0, level=0, reduce="first", of=None, n_zones=None, bins=None, fill=0):
+        """ImageReader.zonal_stats of the composite: per zone the statistics of read(y0, x0, h, w, level, reduce, fill,
+        with_valid=True) under the zone raster [h, w] laid at (y0, x0) of the stack's level, so the per-field mean of a
+        median composite or of a maximum-NDVI one.  A pixel under no valid scene does not count.  The window is
+        composited in strips of tile rows, and every strip accumulates into one table on the device
+        (dsic_zonal_stats_u8 / _u16 on the strip with its validity plane).  zones, of, n_zones, bins and the result are
+        ImageReader.zonal_stats's; reduce and fill are read's."""
+        what = "SceneStack.zonal_stats"
+        top = 65535 if self.kind == _c.KIND_U16_HWC else 255
+        shape = tuple(getattr(zones, "shape", ()))
+        if len(shape) != 2:
+            zonal_args(what, zones, (0, 0), self.C, top)           # raises: no raster
+        level, _, rcode = self._check_window(what, (y0, x0) + shape, level, reduce)
+        zones, (y0, x0, h, w), code, K, Z, vmin, pairs = zonal_args(what, zones, self.levels[level], self.C, top, y0, x0, of,
+                                                                    n_zones, bins)
+        zdev = (zones if isinstance(zones, torch.Tensor) else torch.from_numpy(zones)).to(self._dev)
+        run = _ZonalRun(self._dev, code, K, Z, pairs)
+        g = self.readers[0]._level(level)[2]["grid"]
+        rows = g["th"] * max(1, self.readers[0].batch // (-(-w // g["tw"]) + 1))
+        y = y0
+        while y < y0 + h:
+            hh = min((y // rows + 1) * rows, y0 + h) - y
+            img, valid, _, _ = self._composite((y, x0, hh, w), level, rcode, fill, True, False, None)
+            run.strip(img, valid, zdev[y - y0:y - y0 + hh], -1)
+            y += hh
+        return run.result(vmin, pairs)
+
     def _display_args(self, what, bands, stretch, alpha, background):
         """render's display arguments, checked -> (bands, stretch, alpha, background)"""
         top = 65535 if self.kind == _c.KIND_U16_HWC else 255

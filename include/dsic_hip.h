@@ -1199,6 +1199,52 @@ int dsic_window_warp_composite_u16(const dsic_warp_source* sources, int n, int C
                                    int oh, int ow, int sample_mode, int reduce_mode, int kind,
                                    int a, int b, int fill, void* stream);
 
+/* ---- zonal statistics (codec.ImageReader.zonal_stats, codec.SceneStack.zonal_stats) ----
+ * Per zone of a zone raster, the moments and extremes of the bands or of an index.  Integer and
+ * bit for bit.  img [H][W][C] is uint8 or uint16, C in 1..4; valid_hw (NULL: none), uint8 [H][W],
+ * leaves out its zeros; nodata (-1: none) leaves out the pixels whose C channels all equal it, as
+ * dsic_band_histogram_u8 / _u16 count.  zones_hw is uint16 [H][W] and Z, 1..65535, the number of
+ * zones: pixel p belongs to zone z = zones[p] iff z < Z.  Every other id belongs to no zone and is
+ * ignored, 65535 being the customary "none"; an id at or above Z never produces a write.
+ * what says which values v a pixel has:
+ *   DSIC_ZONAL_BANDS (-1): every band, K = C values, v = px[k], u = v; band_a, band_b are ignored.
+ *   DSIC_INDEX_BAND / _DIFFERENCE / _ND of bands a, b: K = 1 value, v = u + vmin with u and vmin
+ *     of the index table above: px[a], px[a] - px[b], or the normalised difference in units of
+ *     1 / 10000 rounded half up.  A pixel whose index is not defined (A + B = 0) is left out, as
+ *     dsic_index_histogram_u8 / _u16 leave it out.
+ * stats is [Z][K][5] 64-bit words on the device, and the call accumulates into it, per zone z and
+ * value k over the counted pixels of the zone:
+ *   [0] += their number (unsigned)          [3] = min([3], their least v)    (signed)
+ *   [1] += the sum of v (signed)            [4] = max([4], their largest v)  (signed)
+ *   [2] += the sum of v^2 (unsigned; |v| <= 65535 and H W < 2^32, so it fits: the moments are
+ *          taken of v, not of u)
+ *   The caller sets words 0..2 to 0, word 3 to INT64_MAX and word 4 to INT64_MIN before the first
+ *   call; several calls (the strips of a window) accumulate into one table on the device.  Integer
+ *   atomic adds, minima and maxima: no dependence on any order.  A zone without a counted pixel
+ *   keeps its words.
+ * hist (NULL: none) is uint32 [Z][K][256] on the device, zeroed by the caller, and lohi, given
+ *   exactly when hist is, 2 K words on the host read before the call returns: per value k the pair
+ *   (lo, hi) in u units.  hist[z][k][stretch(u, lo, hi)] += 1 per counted pixel, stretch the byte
+ *   of the render calls (255 (clamp(u) - lo) / (hi - lo) rounded half up).  A uint8 band with
+ *   (0, 255) has its exact per-zone histogram; anything wider has 256 equal steps from lo to hi.
+ * A table of at most DSIC_ZONAL_LDS_BYTES (Z K 40 bytes) is gathered in LDS per workgroup and
+ *   flushed once; a larger one takes the 64-bit atomics in global memory.  Same results.
+ * DSIC_EINVAL, nothing written: a null img, zones or stats; C outside 1..4; H or W under 1 or
+ *   H W >= 2^32; Z outside 1..65535; what outside -1..2; a band outside 0..C-1; nodata beyond
+ *   the element type; img not aligned to its element, zones to 2, stats to 8, hist or lohi to 4
+ *   bytes; lohi without hist or hist without lohi; a pair that is not 0 <= lo <= hi <= vmax -
+ *   vmin (top for the bands); stats or hist overlapping img, valid_hw or zones_hw, or each
+ *   other. */
+#define DSIC_ZONAL_BANDS (-1)
+#define DSIC_ZONAL_LDS_BYTES 40960
+int dsic_zonal_stats_u8(const uint8_t* img_hwc, const uint8_t* valid_hw, const uint16_t* zones_hw,
+                        int H, int W, int C, int nodata, int what, int band_a, int band_b, int Z,
+                        uint64_t* stats, const uint32_t* lohi, uint32_t* hist, void* stream);
+int dsic_zonal_stats_u16(const uint16_t* img_hwc, const uint8_t* valid_hw,
+                         const uint16_t* zones_hw, int H, int W, int C, int nodata, int what,
+                         int band_a, int band_b, int Z, uint64_t* stats, const uint32_t* lohi,
+                         uint32_t* hist, void* stream);
+
 /* HIP stream limited to the CUs whose bit is set in mask_host[words] (bit i of
  * word i/32 = CU i).  Used to give the range coder its own few CUs beside the
  * conv kernels; there is no reference counterpart (the reference is

@@ -23,6 +23,8 @@ an image.
                                           [--count-out FILE.npy] [--valid-out FILE.npy] [--source-out FILE.npy]
                                           [--size OH,OW --rotate DEG [--center Y,X] [--scale S] | --affine M00,...,M12]
                                           [--resampling bilinear|cubic|nearest] [--grid H,W]
+    python tools/dsic_image.py zonal      --weights CKPT.pt IN.dsic --zones FILE.npy [--at Y,X] [--level L]
+                                          [--index nd:A,B|difference:A,B|band:A | --band B] [--bins LO,HI] --out FILE.csv
     python tools/dsic_image.py info       IN.dsic
 
 --segments K (2, 4, 8 or 16) codes every tile's y string as K independent strings, which a decoder reads on K waves per
@@ -97,6 +99,11 @@ defaults to the grid's centre), and every scene is sampled under its own matrix 
 cubic or nearest in the same launch that reduces them.  --scene FILE@M00,M01,M02,M10,M11,M12 places a scene by a 2 x 3
 matrix, scene level-0 pixels per grid pixel, for scenes of another resolution or orientation (warped views only);
 --grid H,W is the stack's grid (default: the bounding box, with placements the first scene's size).
+zonal writes a table instead of an image (codec.ImageReader.zonal_stats): --zones FILE.npy is a uint16 raster [h,w] of
+zone ids (65535: no zone) laid at --at Y,X (default 0,0) of --level's pixels, and FILE.csv gets one row per zone and
+value, zone,value,count,mean,std,min,max: of every band, of --band B alone, or of --index (render's spelling; nd in units
+of 1/10000).  Only the tiles under the raster are decoded.  --bins LO,HI also counts 256 bins between LO and HI per
+zone and adds the median read off them (0,255 on a uint8 band: the exact median).
 
 The state dict is loaded plain or from under "model" (code/modelv2/eval_selfcontained_entropy.py:130-134); the model's
 N, M, input channels and spatial_params are read from its shapes.  Images are PNG through PIL when PIL is importable
@@ -630,9 +637,72 @@ def print_info(ix):
               f"{8.0 * c['bytes'] / pixels:.4f} bpp over {pixels} pixels")
 
 
+def zonal_main(a, ap):
+    """zonal: every argument error before the model or the stream is touched, then codec.ImageReader.zonal_stats and one
+    CSV row per zone and value."""
+    import numpy as np
+    if a.zones is None or a.out is None or a.weights is None or not a.out.endswith(".csv"):
+        ap.error("zonal needs --weights, --zones FILE.npy and --out FILE.csv")
+    other = (a.dst, a.region, a.size, a.rotate, a.affine, a.center, a.scale, a.grid, a.projective, a.grid_step, a.bands,
+             a.stretch, a.percent, a.index_stretch, a.scene, a.valid, a.fill, a.valid_out, a.count_out, a.source_out,
+             a.resampling, a.nodata, a.max_error, a.tolerance)
+    if any(v is not None for v in other) or a.alpha or a.background or a.colormap != "grey" or a.reduce != "first":
+        ap.error("zonal takes SRC, --weights, --zones, --at, --level, --index or --band, --bins, --out and --batch")
+    if a.index is not None and a.band is not None:
+        ap.error("--index and --band exclude each other")
+    of = parse_index(a, ap) if a.index is not None else None if a.band is None else ("band", a.band)
+    if of is not None and min(of[1:]) < 0:
+        ap.error(f"--index / --band: band numbers are 0 or more, got {of[1:]}")
+    pairs = {}
+    for name, text, what in (("--at", a.at, "Y,X, two integers of 0 or more"), ("--bins", a.bins, "LO,HI, two integers, LO <= HI")):
+        if text is None:
+            continue
+        try:
+            pair = [int(v) for v in text.split(",")]
+        except ValueError:
+            pair = []
+        if len(pair) != 2 or (name == "--at" and min(pair) < 0) or (name == "--bins" and pair[0] > pair[1]):
+            ap.error(f"{name} {text}: {what}")
+        pairs[name] = pair
+    if a.level < 0:
+        ap.error(f"--level {a.level}: 0 or more")
+    try:
+        zones = np.load(a.zones)
+    except (OSError, ValueError) as e:
+        ap.error(f"--zones {a.zones}: {e}")
+    if not isinstance(zones, np.ndarray) or zones.dtype != np.uint16 or zones.ndim != 2 or zones.size == 0:
+        ap.error(f"--zones {a.zones}: a uint16 array [h, w]; 65535 marks pixels of no zone")
+    from dsic_amd import codec
+    model = load_model(a.weights, a.min_nu, a.max_nu)
+    y0, x0 = pairs.get("--at", (0, 0))
+    stats = {}
+    with open(a.src, "rb") as f, codec.ImageReader(model, f, batch=a.batch) as reader:
+        K = reader.shape[2] if of is None else 1
+        try:
+            res = reader.zonal_stats(zones, y0, x0, level=a.level, of=of, stats=stats,
+                                     bins=None if a.bins is None else [tuple(pairs["--bins"])] * K)
+        except ValueError as e:
+            ap.error(str(e))
+        stats["bytes_read"] = reader.stats["bytes_read"]                      # the heads included
+    median = codec.zonal_percentile(res, 50) if a.bins is not None else None
+    names = [str(k) for k in range(K)] if of is None else [a.index if a.index is not None else str(a.band)]
+    with open(a.out, "w") as f:
+        f.write("zone,value,count,mean,std,min,max" + (",median" if median is not None else "") + "\n")
+        for z in range(res["count"].shape[0]):
+            for k in range(K):
+                row = [z, names[k].replace(",", ";"), int(res["count"][z, k]), repr(float(res["mean"][z, k])),
+                       repr(float(res["std"][z, k])), int(res["min"][z, k]), int(res["max"][z, k])]
+                if median is not None:
+                    row.append(repr(float(median[z, k])))
+                f.write(",".join(str(v) for v in row) + "\n")
+    print(f"[dsic_image] {res['count'].shape[0]} zone(s) x {K} value(s) over {zones.shape[0]}x{zones.shape[1]} pixels at "
+          f"({y0}, {x0}) of level {a.level}: {len(stats['tiles'])} tile(s), {stats['bytes_read']} of "
+          f"{os.path.getsize(a.src)} bytes read -> {a.out}")
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser(description=__doc__.splitlines()[0])
-    ap.add_argument("mode", choices=("compress", "decompress", "render", "composite", "info"))
+    ap.add_argument("mode", choices=("compress", "decompress", "render", "composite", "zonal", "info"))
     ap.add_argument("src")
     ap.add_argument("dst", nargs="?")
     ap.add_argument("--weights")
@@ -646,8 +716,8 @@ def main(argv=None):
     ap.add_argument("--tolerance", type=int, default=None, metavar="T",
                     help="compress, uint16 images: every decoded value within T (0 .. 32767) of the original; 0 = "
                          "lossless")
-    ap.add_argument("--out", choices=("u8", "f32", "u16"), default=None,
-                    help="decoded kind (default: the encoder's input's; u16 only for a uint16 stream)")
+    ap.add_argument("--out", default=None, metavar="u8|f32|u16 | FILE.csv",
+                    help="decoded kind (default: the encoder's input's; u16 only for a uint16 stream); zonal: the table's file")
     ap.add_argument("--scale", default=None, metavar="LO,HI[,LO,HI...] | S",
                     help="compress, uint16 images: the (lo, hi) that map to 0 and 1, one pair for all bands or one per "
                          "band (default: each band's minimum and maximum); with --rotate: level-0 pixels per output "
@@ -710,9 +780,21 @@ def main(argv=None):
                     help="composite: also write the number of the scene each pixel was taken from, uint8 [h,w], 255 = none")
     ap.add_argument("--count-out", default=None, metavar="FILE.npy",
                     help="composite: also write how many scenes counted per pixel, uint8 [h,w]")
+    ap.add_argument("--zones", default=None, metavar="FILE.npy", help="zonal: the zone raster, uint16 [h,w]; 65535 = no zone")
+    ap.add_argument("--at", default=None, metavar="Y,X", help="zonal: where the raster lies in --level's pixels (default 0,0)")
+    ap.add_argument("--band", type=int, default=None, metavar="B", help="zonal: measure this band only (default: every band)")
+    ap.add_argument("--bins", default=None, metavar="LO,HI",
+                    help="zonal: also count 256 bins between LO and HI per zone and write the median; a negative LO as "
+                         "--bins=LO,HI")
     ap.add_argument("--min-nu", type=float, default=2.0)
     ap.add_argument("--max-nu", type=float, default=100.0)
     a = ap.parse_args(argv)
+    if a.mode == "zonal":
+        return zonal_main(a, ap)
+    if a.zones is not None or a.at is not None or a.band is not None or a.bins is not None:
+        ap.error("--zones, --at, --band and --bins go with zonal")
+    if a.out not in (None, "u8", "f32", "u16"):
+        ap.error(f"argument --out: invalid choice: {a.out!r} (choose from 'u8', 'f32', 'u16')")
     from dsic_amd import codec
     if a.mode == "info":
         with open(a.src, "rb") as f:

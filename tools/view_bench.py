@@ -1,6 +1,6 @@
 """Pan and zoom: codec.ImageReader against one decompress_region call per frame, and the resampling kernel alone.
 
-    python tools/view_bench.py [--size 4096] [--tile 256] [--reps 3] [--json profiles/view_bench.json] [--only warp|grid|index|composite|warp_composite]
+    python tools/view_bench.py [--size 4096] [--tile 256] [--reps 3] [--json profiles/view_bench.json] [--only warp|grid|index|composite|warp_composite|zonal]
 
 The scene of image_codec_bench.py (synthetic patches side by side, uint8) is coded once with overviews=3.  A viewport
 of 768 rows x 1024 columns pans right in 32 steps of 64 pixels (33 frames).  Per frame, alternately in one process:
@@ -53,6 +53,12 @@ equal once; device events, 20 launches after 5, three rounds alternating.  A fus
 slowest round, "margin" up to that plus the chain's spread, else "OUTSIDE".  Each row states a byte model: the validity
 and pixel lines under the taps of the sources looked at plus the output, and for the chain that plus n oh ow (C elem + 1)
 written and read again.
+zonal (--only zonal alone): dsic_zonal_stats_u16 on 4096 x 4096 x 4 random uint16 pixels on the device, as a reader's cached
+level hands them over, under three zone rasters, one zone (Z = 1, and again as zone 0 of Z = 4096), blocks of 64 x 64 pixels
+(4096 zones) and per-pixel noise over 4096 zones, and under 256 blocks of 256 x 256 pixels, whose table fits LDS as the
+single zone's does; every band and ("nd", 3, 0).  Beside each: dsic_band_histogram_u16
+on the same pixels, the same table composed in torch on the same device tensors (int64 copies, scatter_add_ and
+scatter_reduce_; checked equal once), and the bytes read per second against the read probe of tools/hbm_bw.py.
 Records, not bars."""
 from __future__ import annotations
 
@@ -522,6 +528,86 @@ def _warp_composite_record(kernel_size=4096, rounds=3):
             "timing": f"device events, 20 launches after 5, {rounds} alternating rounds, chain first", "rows": out}
 
 
+def _zonal_torch(img, zones, Z, of):
+    """The table of dsic_zonal_stats_u16 composed in torch on the same device tensors: widened int64 copies, scatter_add_
+    for count, sum and sum of squares, scatter_reduce_ for the extremes; ids at or above Z go to a row that is cut off."""
+    import torch
+    px = img.view(torch.int16).to(torch.int64).bitwise_and_(0xFFFF).reshape(-1, img.shape[2])
+    idx = zones.view(torch.int16).to(torch.int64).bitwise_and_(0xFFFF).reshape(-1)
+    idx = torch.where(idx < Z, idx, Z)
+    if of is None:
+        v = px
+    else:
+        A, B = px[:, of[1]], px[:, of[2]]
+        s = A + B
+        idx = torch.where(s != 0, idx, Z)
+        v = ((40000 * A + s) // (2 * s).clamp_(min=1) - 10000)[:, None]
+    K = v.shape[1]
+    at = idx[:, None].expand(-1, K)
+    table = torch.zeros((Z + 1, K, 5), dtype=torch.int64, device=img.device)
+    table[:, :, 3], table[:, :, 4] = (1 << 63) - 1, -(1 << 63)
+    table[:, :, 0].scatter_add_(0, at, torch.ones_like(v))
+    table[:, :, 1].scatter_add_(0, at, v)
+    table[:, :, 2].scatter_add_(0, at, v * v)
+    table[:, :, 3].scatter_reduce_(0, at, v, "amin")
+    table[:, :, 4].scatter_reduce_(0, at, v, "amax")
+    return table[:Z]
+
+
+def _zonal_record(size=4096, C=4, Z=4096):
+    """The `zonal` record: see the module's docstring."""
+    import torch
+    from dsic_amd import lib
+    from dsic_amd.ops import _p, _stream
+    L = lib.load()
+    img = torch.randint(0, 10001, (size, size, C), dtype=torch.int32, device="cuda").to(torch.int16).view(torch.uint16)
+    y, x = torch.meshgrid(torch.arange(size, device="cuda"), torch.arange(size, device="cuda"), indexing="ij")
+    rasters = {"one zone": (1, torch.zeros((size, size), dtype=torch.int32, device="cuda")),
+               "one zone of 4096": (Z, torch.zeros((size, size), dtype=torch.int32, device="cuda")),
+               "64 x 64 blocks": (Z, ((y // 64) * (size // 64) + x // 64).to(torch.int32) % Z),
+               "per-pixel noise": (Z, torch.randint(0, Z, (size, size), dtype=torch.int32, device="cuda")),
+               "256 x 256 blocks, 256 zones": (256, ((y // 256) * (size // 256) + x // 256).to(torch.int32) % 256)}
+    rasters = {k: (nz, v.to(torch.int16).view(torch.uint16).contiguous()) for k, (nz, v) in rasters.items()}
+    # the read probe of tools/hbm_bw.py: the sum of 2.1 GB of float32
+    probe = torch.empty(64 * 256 * 256 * 128, dtype=torch.float32, device="cuda").fill_(1.0)
+    probe_us = _per_launch_us(lambda: probe.sum(), n=10)
+    read_TB_s = probe.numel() * 4 / probe_us / 1e6
+    del probe
+    hist = torch.zeros((C, 65536), dtype=torch.int32, device="cuda")
+    hist_us = _per_launch_us(lambda: lib.check(L.dsic_band_histogram_u16(_p(img), None, size, size, C, -1, _p(hist), _stream()),
+                                               "band_histogram_u16"), n=20)
+    rows = {}
+    for name, (Z, zones) in rasters.items():
+        for label, of in (("bands", None), ("nd", ("nd", 3, 0))):
+            K = C if of is None else 1
+            code = (lib.ZONAL_BANDS, 0, 0) if of is None else (2, of[1], of[2])
+            table = torch.zeros((Z, K, 5), dtype=torch.int64, device="cuda")
+
+            def fresh():
+                table.zero_()
+                table[:, :, 3], table[:, :, 4] = (1 << 63) - 1, -(1 << 63)
+
+            def kernel():
+                lib.check(L.dsic_zonal_stats_u16(_p(img), None, _p(zones), size, size, C, -1, *code, Z, _p(table), None, None,
+                                                 _stream()), "zonal_stats_u16")
+            fresh()
+            kernel()
+            want = _zonal_torch(img, zones, Z, of)
+            torch.cuda.synchronize()
+            assert torch.equal(table, want), (name, label)
+            k_us = _per_launch_us(kernel, n=20)
+            t_us = _per_launch_us(lambda: _zonal_torch(img, zones, Z, of), n=3)
+            moved = size * size * (2 * C + 2)                              # the pixels and the zone ids, read once
+            rows[f"{name}, {label}"] = {
+                "kernel_us": round(k_us, 1), "torch_us": round(t_us, 1), "torch_over_kernel": round(t_us / k_us, 2),
+                "band_histogram_u16_us": round(hist_us, 1), "bytes_read": moved, "GB_per_s": round(moved / k_us / 1e3, 1),
+                "fraction_of_read_probe": round(moved / k_us / 1e6 / read_TB_s, 3), "zones": Z,
+                "table": "LDS" if Z * K * 40 <= lib.ZONAL_LDS_BYTES else "global atomics"}
+    return {"pixels": f"{size}x{size}x{C} uint16, random in 0..10000, no validity plane",
+            "timing": "device events, 20 launches after 5 (torch: 3 after 5)", "read_probe_TB_per_s": round(read_TB_s, 2),
+            "rows": rows}
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--size", type=int, default=4096)
@@ -529,7 +615,7 @@ def main():
     ap.add_argument("--batch", type=int, default=64)
     ap.add_argument("--reps", type=int, default=3)
     ap.add_argument("--json", default=os.path.join(ROOT, "profiles", "view_bench.json"))
-    ap.add_argument("--only", choices=("warp", "grid", "index", "composite", "warp_composite"), default=None,
+    ap.add_argument("--only", choices=("warp", "grid", "index", "composite", "warp_composite", "zonal"), default=None,
                     help="measure this record alone and put it into the --json file beside the others")
     a = ap.parse_args()
 
@@ -542,12 +628,13 @@ def main():
 
     if not torch.cuda.is_available():
         raise SystemExit("view_bench: no GPU; nothing is measured without one")
-    if a.only in ("composite", "warp_composite"):                          # inputs of their own: nothing below is needed
+    if a.only in ("composite", "warp_composite", "zonal"):                 # inputs of their own: nothing below is needed
         res = {}
         if os.path.exists(a.json):
             with open(a.json) as f:
                 res = json.load(f)
-        res[a.only] = _composite_record(a.size, a.tile, a.batch) if a.only == "composite" else _warp_composite_record()
+        res[a.only] = _composite_record(a.size, a.tile, a.batch) if a.only == "composite" else \
+            _zonal_record() if a.only == "zonal" else _warp_composite_record()
         print(json.dumps(res[a.only]))
         with open(a.json, "w") as f:
             json.dump(res, f, indent=1)
